@@ -19,7 +19,9 @@ as a child, BEFORE anything here touches the GPU -- and exits with the child's c
                             1.61 ms = 47 % of the f32-MFMA peak at 1024, 1.37 ms = 55 % at 2048; 12 and 16 gain nothing more).
   --driver single|threads : ONE host thread drives every context through trl_detect_embed_begin / _end (default), or one blocking
                             host thread per context (round 2's scheme; --embed-group then groups per worker).
-Rank 0 prints ONE JSON line.
+  --dump-outputs DIR      : after the timed region, the arrays the last timed step returned go to DIR/<name>.npy (the inputs are
+                            seeded: two builds run with the same flags can be compared output for output).
+Rank 0 prints ONE JSON line; its ms_per_step is the wall time of the timed region over --steps.
 """
 import argparse
 import json
@@ -201,7 +203,54 @@ def parse_args(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group and run the per-step collective even with ONE rank: exercises the RCCL branch "
                          "(init, all-gather of the result rows, barrier, all-reduce of the time) on a single-GPU box")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: larger outputs are cut to a fixed seeded sample of rows, DIR/<name>_rows.npy)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(out, d, clip):
+    """What a caller of the timed path receives from one step, as host arrays: this rank's detector / embedder outputs
+    (Engine.detect_embed) and the drift result over the clip (Engine.drift_score).  ``clip``: the drift ran over rows gathered
+    from every rank, dumped as clip_emb / clip_valid.  Float32 arrays stay float32, the integer ones become float64 (exact)."""
+    import numpy as np
+    src = {k: out[k] for k in ("box", "prob", "rect", "valid", "emb")}
+    if clip:
+        src["clip_emb"], src["clip_valid"] = d["emb_all"], d["valid_all"]
+    src["sims"], src["flags"] = d["sims"], d["flags"]
+    arrays = {}
+    for k, v in src.items():
+        a = v.cpu().numpy()
+        arrays[k] = a if a.dtype == np.float32 else a.astype(np.float64)
+    arrays["drift"] = np.array([d["score"], d["run"], d["hits"], d["total"]], np.float64)   # not sampled
+    return arrays
+
+
+def write_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES, fixed=("drift",)):
+    """arrays -> dirname/<name>.npy.  If they hold more than ``limit`` bytes, every array but ``fixed`` is cut to the same seeded
+    fraction of its rows (arrays of equal length keep the same rows), whose indices go to <name>_rows.npy."""
+    import numpy as np
+    sampled = [k for k in arrays if k not in fixed]
+    total = sum(a.nbytes for a in arrays.values())
+    budget = limit - 2 * 256 * len(arrays)                                      # .npy headers of the arrays and their row indices
+    if total > budget:
+        rowed = sum(arrays[k].nbytes + 8 * len(arrays[k]) for k in sampled)   # + the float64 row index of each
+        frac = (budget - (total - sum(arrays[k].nbytes for k in sampled))) / rowed
+        arrays = dict(arrays)
+        for k in sampled:
+            a = arrays[k]
+            rows = np.sort(np.random.default_rng(0).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            arrays[k], arrays[k + "_rows"] = a[rows], rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return arrays
 
 
 def rank_command(args, argv, have_gpus, environ=None):
@@ -453,6 +502,8 @@ def main():
     (out, d), acc = run_steps(args.steps)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(out, d, clip=use_dist and sharded))
     pnet_ms, pyr_ms = acc["pnet_ms"], acc["pyramid_ms"]
     if use_dist:
         tdev = dev if args.backend == "nccl" else torch.device("cpu")

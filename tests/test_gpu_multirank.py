@@ -70,6 +70,25 @@ def test_config3_concurrent_ingest_rehearsal(engine):
         assert r["config"]["scores"][s] == engine.drift_score(out["emb"], out["valid"], n * 4, 30)["score"], s
 
 
+def test_bench_dump_outputs_are_the_last_step(engine, tmp_path):
+    """`--dump-outputs DIR` writes what the timed path returned in its last step: the same arrays a single detect_embed +
+    drift_score call gives for the bench's seeded frames, and the embeddings the result line's CRC describes."""
+    n = 6
+    r = _bench("--batch", str(n), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path))
+    assert r["steps"] == 3
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(got) == ["box", "drift", "emb", "flags", "prob", "rect", "sims", "valid"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    fr = truely_amd.synthetic.synthetic_frames(n, 720, 1280, seed=0)
+    out = engine.detect_embed(fr)
+    d = engine.drift_score(out["emb"], out["valid"], n * 4, 30)
+    for k in ("box", "prob", "rect", "valid", "emb"):
+        assert np.array_equal(got[k], out[k].cpu().numpy()), k
+    assert np.array_equal(got["sims"], d["sims"].cpu().numpy()) and np.array_equal(got["flags"], d["flags"].cpu().numpy())
+    assert got["drift"].tolist() == [d["score"], d["run"], d["hits"], d["total"]] and d["score"] == r["config"]["score"]
+    assert r["config"]["emb_crc32"] == zlib.crc32(got["emb"].tobytes())
+
+
 def test_rccl_needs_as_many_gpus_as_ranks():
     """On this one-GPU box the RCCL launch must fail loudly instead of silently running one rank."""
     if torch.cuda.device_count() >= 2:

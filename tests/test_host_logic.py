@@ -188,6 +188,44 @@ def test_bench_multi_gpu_launch_is_correct_by_construction():
     assert body.index("spawn_ranks(args)") < body.index("import torch")  # the parent never touches the GPU
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float32 / float64 .npy files (integers exactly), at most 64 MB in all --
+    larger outputs are cut to the same seeded rows of every per-frame array, with the row indices beside them.  --steps >= 1."""
+    import torch
+    import bench
+    assert bench.parse_args(["--dump-outputs", str(tmp_path), "--steps", "3"]).dump_outputs == str(tmp_path)
+    assert bench.parse_args([]).dump_outputs is None
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    n, rng = 5, np.random.default_rng(1)
+    out = {"box": torch.from_numpy(rng.random((n, 4), np.float32)), "prob": torch.from_numpy(rng.random(n, np.float32)),
+           "rect": torch.from_numpy(rng.integers(-9, 4000, (n, 4)).astype(np.int32)),
+           "valid": torch.tensor([1, 0, 1, 1, 0], dtype=torch.uint8), "emb": torch.from_numpy(rng.random((n, 512), np.float32))}
+    d = {"score": 7, "run": 2, "hits": 3, "total": 5, "sims": torch.from_numpy(rng.random(2 * n, np.float32)),
+         "flags": torch.tensor([0, 1] * n, dtype=torch.uint8), "emb_all": out["emb"].repeat(2, 1), "valid_all": out["valid"].repeat(2)}
+    arrays = bench.step_outputs(out, d, clip=False)
+    assert sorted(arrays) == ["box", "drift", "emb", "flags", "prob", "rect", "sims", "valid"]
+    assert sorted(bench.step_outputs(out, d, clip=True)) == sorted(list(arrays) + ["clip_emb", "clip_valid"])
+    bench.write_outputs(str(tmp_path / "all"), arrays)
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "all" / f"{k}.npy")
+        assert b.dtype in (np.float32, np.float64) and np.array_equal(a, b), k
+    assert np.array_equal(np.load(tmp_path / "all" / "rect.npy"), out["rect"].numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "drift.npy"), [7, 2, 3, 5])
+    # over the limit: a fixed sample of rows, the same rows in arrays of equal length, the scalars whole
+    limit = 8192
+    cut = bench.write_outputs(str(tmp_path / "cut"), arrays, limit=limit)
+    files = sorted(os.listdir(tmp_path / "cut"))
+    assert sum(os.path.getsize(tmp_path / "cut" / f) for f in files) <= limit
+    assert "emb_rows.npy" in files and "drift_rows.npy" not in files
+    rows = np.load(tmp_path / "cut" / "emb_rows.npy").astype(np.int64)
+    assert 1 <= len(rows) < n and np.array_equal(np.load(tmp_path / "cut" / "emb.npy"), arrays["emb"][rows])
+    assert np.array_equal(np.load(tmp_path / "cut" / "box_rows.npy"), rows)
+    assert np.array_equal(np.load(tmp_path / "cut" / "drift.npy"), arrays["drift"])
+    again = bench.write_outputs(str(tmp_path / "cut2"), arrays, limit=limit)
+    assert all(np.array_equal(cut[k], again[k]) for k in cut)
+
+
 def test_analysis_service_keeps_event_loop_free():
     """requests queue on one worker, in order, while the event loop keeps running."""
     import asyncio
@@ -342,14 +380,17 @@ def test_mp4_probe_plain_file(tmp_path):
     assert mp4probe.probe(__file__) is None and video_io.describe(__file__) == "unknown container"
 
 
-def test_mp4_probe_reference_sample():
+def test_mp4_probe_reference_sample(tmp_path):
     """The reference's own sample clip (BASELINE configs[0]; fragmented mp4 from yt-dlp): the container facts SURVEY section 6
-    lists -- 640x360, 30 fps, 960 frames -- read by this build's demultiplexer.  (Decoding it needs OpenCV: DESIGN section 8.)"""
-    import glob
+    lists -- 640x360, 30 fps, 960 frames -- read by this build's demultiplexer.  (Decoding it needs OpenCV: DESIGN section 8.)
+    The clip is stored as its skeleton (tests/golden/make_mp4_skeleton.py): every container byte and NAL unit header of the
+    original, the coded pictures zeroed."""
+    import gzip
     from truely_amd import mp4probe
-    files = glob.glob("/root/reference/test/*.mp4")
-    if not files:
-        pytest.skip("the reference checkout is not present on this box")
+    path = tmp_path / "sample.mp4"
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "sample_clip_skeleton.mp4.gz"), "rb") as f:
+        path.write_bytes(f.read())
+    files = [str(path)]
     i = mp4probe.probe(files[0])
     assert (i.width, i.height, i.frame_count, i.fragmented, i.codec) == (640, 360, 960, True, "avc1")
     assert abs(i.fps - 30.0) < 1e-9 and i.profile_idc == 77 and len(i.sps) == 1 and len(i.pps) == 1

@@ -200,6 +200,20 @@ int  trl_debug_batch_capacity(trl_ctx* ctx, float t2_per_frame, float t3_per_fra
 /* test hook: level `level` of one frame's image pyramid as the fused PNet kernel reads it; d_out holds h*w*3 floats
  * (capacity: at least (int(H*m+1))*(int(W*m+1))*3 with m = 12/min_face_size) */
 int  trl_debug_pyramid_level(trl_ctx* ctx, const uint8_t* d_frame, int H, int W, int level, float* d_out, int* h, int* w, void* stream);
+/* test hook: the image pyramid of an n-frame device batch, built by the same pyramid pass trl_detect_embed's fused PNet makes.
+ * d_out receives the raw workspace: n x *pyr_stride pixels of 3 floats (frame f, level l at f * pyr_stride + pix0), each level's
+ * padding up to pix_pad pixels included.  d_out == NULL: layout only, nothing is launched.  h_levels receives {pix0, h, w, pix_pad}
+ * per level (room for max_levels levels), *n_levels the level count.  More than 16 levels: TRL_ERR_INVALID. (ABI v7) */
+int  trl_debug_pyramid_batch(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W, float* d_out, long long* pyr_stride,
+                             int32_t* h_levels, int max_levels, int* n_levels, void* stream);
+/* test hook: what the last pyramid pass of this context chose for each level (host bookkeeping of the pass; *n_levels = 0 when it
+ * was refused).  Rows of TRL_PYR_PLAN_COLS ints: {kernel (TRL_PYR_* below), row_bands, col_bands, cols_per_band, frames per
+ * launch, khmax (tallest bin, source rows)}; the band fields are 0 for the per-level and fine-level kernels, frames per launch
+ * is n for the one-pass kernels and the frame chunk for the per-level ones. (ABI v7) */
+#define TRL_PYR_PLAN_COLS 6
+enum { TRL_PYR_FINE = 1, TRL_PYR_S4 = 2, TRL_PYR_S8 = 3, TRL_PYR_SW4 = 4, TRL_PYR_SW8 = 5,
+       TRL_PYR_L0_3 = 6, TRL_PYR_L0_4 = 7, TRL_PYR_L0_5 = 8, TRL_PYR_L1 = 9, TRL_PYR_L2 = 10 };
+int  trl_debug_pyramid_plan(trl_ctx* ctx, int32_t* h_rows, int max_levels, int* n_levels);
 /* test hook: fill the activation workspaces with a byte pattern (0xFF -> NaNs) before the next call */
 int  trl_debug_poison(trl_ctx* ctx, int byte);
 /* PNet on one pyramid level of frame 0: face-prob map and regression map (device outputs). */

@@ -541,7 +541,8 @@ def test_frame_buffer_at_dword_alignment_only(engine, oracle, offset):
     assert bool((big[:offset] == 0xFF).all()) and bool((big[offset + nbytes:] == 0xFF).all())
 
 
-@pytest.mark.parametrize("H,W", [(180, 320), (97, 131), (720, 1280), (1080, 1920), (2160, 3840)])
+@pytest.mark.parametrize("H,W", [(180, 320), (97, 131), (720, 1280), (1080, 1920), (2160, 3840),
+                                 (1081, 1927), (900, 1602), (255, 2001), (720, 1366)])
 def test_pyramid_levels_bit_exact(engine, oracle, H, W):
     """Every level of the production pyramid (what the fused PNet kernel reads) against imresample + normalise of the
     oracle, pixel for pixel.  4K exercises the multiply-high row decode beyond its exact range (fix-up step), table

@@ -67,6 +67,25 @@ def test_area_resample_bit_exact_vs_torch(oracle):
     assert np.array_equal(a, b)
 
 
+@pytest.mark.parametrize("H,W,sizes", [
+    (97, 131, [(98, 132)]),                            # h = H + 1: the upsampled level 0 of min_face_size 12
+    (720, 1280, [(721, 1281)]),
+    (1500, 1400, [(15, 14), (13, 12), (11, 17)]),      # bins of 100-136 px: beyond the exhaustively checked pyr_div range (<= 96)
+    (3316, 331, [(13, 7), (12, 3), (11, 2)]),          # bins of 256-302 rows (the streaming passes' 16-bit column sum limit)
+    (1081, 1927, [(649, 1157), (460, 820), (23, 41)]),  # odd wide frames
+    (255, 2001, [(153, 1201), (77, 604), (13, 102)]),
+])
+def test_area_resample_bit_exact_vs_torch_at_pyramid_edges(oracle, H, W, sizes):
+    """The pyramid tests' reference itself, pinned to F.interpolate(mode="area") at the shape classes the GPU pyramid tests
+    (tests/test_gpu_pyramid.py) reach: upsampling, large bins, bins of ~256 rows, odd wide frames."""
+    fr = np.random.default_rng(H * W).integers(0, 256, (H, W, 3), dtype=np.uint8)
+    im = torch.as_tensor(fr).unsqueeze(0).permute(0, 3, 1, 2).float()
+    for (h, w) in sizes:
+        a = oracle.area_resample_norm(fr, 0, H, 0, W, h, w)
+        b = ((F.interpolate(im, size=(h, w), mode="area") - 127.5) * 0.0078125)[0].permute(1, 2, 0).numpy()
+        assert np.array_equal(a.view(np.uint32), np.ascontiguousarray(b).view(np.uint32)), (h, w)
+
+
 def test_networks_close_to_torch(oracle, tref):
     rng = np.random.default_rng(1)
     lvl = rng.uniform(-1, 1, (57, 83, 3)).astype(np.float32)

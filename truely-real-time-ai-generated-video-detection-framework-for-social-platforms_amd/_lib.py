@@ -55,6 +55,8 @@ _SIGNATURES = {
     "trl_debug_list_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "trl_debug_poison": (C.c_int, [_vp, _i]),
     "trl_debug_pyramid_level": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "trl_debug_pyramid_batch": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong), _vp, _i, C.POINTER(_i), _vp]),
+    "trl_debug_pyramid_plan": (C.c_int, [_vp, _vp, _i, C.POINTER(_i)]),
     "trl_debug_pnet_level": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i), _vp]),
     "trl_debug_rnet": (C.c_int, [_vp, _vp, _i, _vp, _vp]),
     "trl_debug_onet": (C.c_int, [_vp, _vp, _i, _vp, _vp]),

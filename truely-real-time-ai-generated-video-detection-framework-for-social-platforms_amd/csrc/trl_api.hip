@@ -655,6 +655,29 @@ int trl_debug_pyramid_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, in
     return TRL_OK;
 }
 
+int trl_debug_pyramid_batch(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_out, long long* pyr_stride,
+                            int32_t* h_levels, int max_levels, int* n_levels, void* stream) {
+    TRL_CHECK(check_call(c, d_frames, n, H, W));
+    if (!pyr_stride || !n_levels || (max_levels > 0 && !h_levels)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    if (d_out) {
+        c->scratch.reset();
+        TRL_CHECK(trl_ensure(c, c->scratch, trl_pnet_fused_bytes(c, n, H, W) + (1u << 20)));
+    }
+    TRL_CHECK(trl_pyramid_export_batch(c, d_frames, n, H, W, d_out, pyr_stride, h_levels, max_levels, n_levels, s));
+    TRL_HIP(hipStreamSynchronize(s));
+    return TRL_OK;
+}
+
+int trl_debug_pyramid_plan(trl_ctx* c, int32_t* h_rows, int max_levels, int* n_levels) {
+    TRL_CHECK(check_idle(c));
+    if (!n_levels || (max_levels > 0 && !h_rows)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
+    *n_levels = c->pyr_plan.L;
+    for (int l = 0; l < c->pyr_plan.L && l < max_levels; l++)
+        for (int k = 0; k < TRL_PYR_PLAN_COLS; k++) h_rows[l * TRL_PYR_PLAN_COLS + k] = c->pyr_plan.row[l][k];
+    return TRL_OK;
+}
+
 int trl_debug_pnet_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, int level, float* d_prob, float* d_reg, int* oh, int* ow,
                          void* stream) {
     TRL_CHECK(check_call(c, d_frame, 1, H, W));

@@ -95,6 +95,8 @@ struct trl_ctx {
     int pyr_tab_H = 0, pyr_tab_W = 0;
     // one-pass kernel for the finest levels (k_pyramid_fine): ownership table inside pyr_tab, source tile shape; nlev == 0: not usable for this shape
     struct { int nlev = 0, own0 = 0, band_cols = 0, strip_rows = 0, n_bands = 0, n_strips = 0; } pyr_fine;
+    // what the last build_pyramid chose per level (trl_debug_pyramid_plan): rows of TRL_PYR_PLAN_COLS ints; L = 0 after a refused call
+    struct { int L = 0; int32_t row[16][TRL_PYR_PLAN_COLS] = {}; } pyr_plan;
 };
 
 // Optional device-wide ordering of the wide phases of different contexts (trl_api.hip; OFF by default, trl_debug_option
@@ -141,3 +143,5 @@ int trl_pnet_prepare(trl_ctx* c);
 size_t trl_pnet_fused_bytes(trl_ctx* c, int n, int H, int W);
 int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, hipEvent_t* ev, hipStream_t s);
 int trl_pyramid_export(trl_ctx* c, const uint8_t* d_frame, int H, int W, int level, float* d_out, int* h, int* w, hipStream_t s);
+int trl_pyramid_export_batch(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_out, long long* pyr_stride,
+                             int32_t* h_levels, int max_levels, int* n_levels, hipStream_t s);

@@ -1818,7 +1818,13 @@ static int build_pyramid(trl_ctx* c, const uint8_t* d_frames, int n, int H, int 
     if (H > 16383 || W > 16383) { trl_set_error("frame larger than 16383 px"); return TRL_ERR_INVALID; }
     std::vector<uint32_t> tab;
     const bool new_shape = (c->pyr_tab == nullptr || c->pyr_tab_H != H || c->pyr_tab_W != W);
+    c->pyr_plan.L = 0;
     TRL_CHECK(fill_args(c, n, H, W, a, new_shape ? &tab : nullptr));
+    // the kernel each level takes, recorded as it is chosen below (trl_debug_pyramid_plan)
+    auto plan = [&](int l, int kind, int rb, int cb, int cpb, int frames) {
+        int32_t* r = c->pyr_plan.row[l];
+        r[0] = kind; r[1] = rb; r[2] = cb; r[3] = cpb; r[4] = frames; r[5] = a.lv[l].khmax;
+    };
     if (new_shape) {   // bin-edge tables depend on (H, W) only: built once per frame shape
         // k_pyramid_fine: which output columns / rows of the (up to three) finest levels belong to which source tile -- those whose
         // bins START in it.  A band must not own more than 64 columns of any level (one wave = one level's columns of the band).
@@ -1931,7 +1937,11 @@ static int build_pyramid(trl_ctx* c, const uint8_t* d_frames, int n, int H, int 
                 else k_pyramid_stream_w<8><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
             }
             TRL_LAUNCH_CHECK();
-            for (int q = 0; q < gn; q++) streamed[lv_idx[g0 + q]] = true;
+            const int kind = wide ? (sa.nlev <= 4 ? TRL_PYR_SW4 : TRL_PYR_SW8) : (sa.nlev <= 4 ? TRL_PYR_S4 : TRL_PYR_S8);
+            for (int q = 0; q < gn; q++) {
+                streamed[lv_idx[g0 + q]] = true;
+                plan(lv_idx[g0 + q], kind, sa.row_bands, sa.col_bands, sa.cols_per_band, n);
+            }
         }
         return TRL_OK;
     };
@@ -1950,7 +1960,7 @@ static int build_pyramid(trl_ctx* c, const uint8_t* d_frames, int n, int H, int 
         for (int l = 0; l < 3; l++) fa.g[l] = a.lv[l < fa.nlev ? l : 0];
         k_pyramid_fine<<<dim3(fa.n_bands, n, fa.n_strips), 192, 0, s>>>(d_frames, fa, c->pyr_tab, pyr);
         TRL_LAUNCH_CHECK();
-        for (int l = 0; l < fa.nlev; l++) streamed[l] = true;
+        for (int l = 0; l < fa.nlev; l++) { streamed[l] = true; plan(l, TRL_PYR_FINE, 0, 0, 0, n); }
     }
     for (int f0 = 0; f0 < n; f0 += chunk) {
         const int nf = (n - f0 < chunk) ? n - f0 : chunk;
@@ -1960,17 +1970,20 @@ static int build_pyramid(trl_ctx* c, const uint8_t* d_frames, int n, int H, int 
             pa.H = H; pa.W = W; pa.n_frames = n; pa.f0 = f0; pa.pyr_stride = a.pyr_stride; pa.g = a.lv[l];
             const int threads = pa.g.pix_pad << pa.g.gshift;
             dim3 grid(pa.g.mode == 0 ? (threads + 511) / 512 : (threads + 255) / 256, nf);   // mode 0: two pixels per thread
+            int kind;
             if (pa.g.mode == 0) {
-                if (pa.g.khmax <= 3 && pa.g.nd <= 3) k_pyramid0<3, false><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr);
-                else if (pa.g.khmax <= 4) k_pyramid0<4, true><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr);
-                else k_pyramid0<5, true><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr);
+                if (pa.g.khmax <= 3 && pa.g.nd <= 3) { kind = TRL_PYR_L0_3; k_pyramid0<3, false><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
+                else if (pa.g.khmax <= 4) { kind = TRL_PYR_L0_4; k_pyramid0<4, true><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
+                else { kind = TRL_PYR_L0_5; k_pyramid0<5, true><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
             }
-            else if (pa.g.mode == 1) k_pyramid<1><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr);
-            else k_pyramid<2><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr);
+            else if (pa.g.mode == 1) { kind = TRL_PYR_L1; k_pyramid<1><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
+            else { kind = TRL_PYR_L2; k_pyramid<2><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
             TRL_LAUNCH_CHECK();
+            if (f0 == 0) plan(l, kind, 0, 0, 0, chunk);
         }
     }
     if (ev) TRL_HIP(hipEventRecord(ev[1], s));
+    c->pyr_plan.L = a.L;
     return TRL_OK;
 }
 
@@ -1989,6 +2002,26 @@ int trl_pyramid_export(trl_ctx* c, const uint8_t* d_frame, int H, int W, int lev
     k_export_level<<<(g.h * g.w + 255) / 256, 256, 0, s>>>(a.pyr + g.pix0, g.h * g.w, d_out);
     TRL_LAUNCH_CHECK();
     *h = g.h; *w = g.w;
+    return TRL_OK;
+}
+
+// debug / test hook: the raw pyramid workspace of an n-frame batch (every frame, every level, the padding included) as the
+// production pass above leaves it; d_out == nullptr: the layout alone
+int trl_pyramid_export_batch(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_out, long long* pyr_stride,
+                             int32_t* h_levels, int max_levels, int* n_levels, hipStream_t s) {
+    PnetArgs a;
+    if (d_out) {
+        TRL_CHECK(build_pyramid(c, d_frames, n, H, W, a, nullptr, s));
+        TRL_HIP(hipMemcpyAsync(d_out, a.pyr, (size_t)a.pyr_stride * n * sizeof(PyrPx), hipMemcpyDeviceToDevice, s));
+    } else {
+        TRL_CHECK(fill_args(c, n, H, W, a));
+    }
+    *pyr_stride = a.pyr_stride;
+    *n_levels = a.L;
+    for (int l = 0; l < a.L && l < max_levels; l++) {
+        const PLevel& g = a.lv[l];
+        h_levels[4 * l + 0] = g.pix0; h_levels[4 * l + 1] = g.h; h_levels[4 * l + 2] = g.w; h_levels[4 * l + 3] = g.pix_pad;
+    }
     return TRL_OK;
 }
 

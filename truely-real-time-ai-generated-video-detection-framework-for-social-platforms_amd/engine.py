@@ -268,6 +268,34 @@ class Engine:
         _lib.check(self.lib.trl_debug_pyramid_level(self._h, _ptr(fr), H, W, int(level), _ptr(out), C.byref(h), C.byref(w), self._stream()))
         return out[:h.value * w.value * 3].view(h.value, w.value, 3)
 
+    def pyramid_batch(self, frames):
+        """Test hook: the pyramid of an n-frame batch through the production pyramid pass, as the raw workspace
+        (n, pyr_stride, 3) float32 -- frame f, level l at [f, pix0:pix0 + h*w], the level's padding up to pix0 + pix_pad -- and the
+        per-level layout, a list of dicts {pix0, h, w, pix_pad}."""
+        fr = self._frames(frames)
+        n, H, W, _ = fr.shape
+        stride, L = C.c_longlong(), C.c_int()
+        lv = np.zeros((16, 4), np.int32)
+        _lib.check(self.lib.trl_debug_pyramid_batch(self._h, _ptr(fr), n, H, W, None, C.byref(stride), lv.ctypes.data_as(C.c_void_p), 16,
+                                                    C.byref(L), self._stream()))
+        out = torch.empty((n, stride.value, 3), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.trl_debug_pyramid_batch(self._h, _ptr(fr), n, H, W, _ptr(out), C.byref(stride), lv.ctypes.data_as(C.c_void_p), 16,
+                                                    C.byref(L), self._stream()))
+        levels = [dict(zip(("pix0", "h", "w", "pix_pad"), (int(v) for v in lv[l]))) for l in range(L.value)]
+        return out, levels
+
+    PYR_KERNELS = {1: "F", 2: "S4", 3: "S8", 4: "SW4", 5: "SW8", 6: "L0-3", 7: "L0-4", 8: "L0-5", 9: "L1", 10: "L2"}   # TRL_PYR_*
+
+    def pyramid_plan(self):
+        """Test hook: what the last pyramid pass of this context chose per level, a list of dicts {kernel ("F", "S4", "S8", "SW4",
+        "SW8", "L0-3", "L0-4", "L0-5", "L1", "L2"), row_bands, col_bands, cols_per_band, frames_per_launch, khmax}; [] after a
+        refused call."""
+        rows = np.zeros((16, 6), np.int32)
+        L = C.c_int()
+        _lib.check(self.lib.trl_debug_pyramid_plan(self._h, rows.ctypes.data_as(C.c_void_p), 16, C.byref(L)))
+        keys = ("row_bands", "col_bands", "cols_per_band", "frames_per_launch", "khmax")
+        return [dict(kernel=self.PYR_KERNELS[int(r[0])], **dict(zip(keys, (int(v) for v in r[1:])))) for r in rows[:L.value]]
+
     def batch_capacity(self, t2_per_frame: float = 0.0, t3_per_frame: float = 0.0) -> int:
         """Test hook: set the optimistic R-/O-Net candidate capacities (per frame) and return the attempts the last call took."""
         k = C.c_int()

@@ -37,7 +37,8 @@ typedef enum {
     TRL_ERR_HIP = -2,       /* HIP runtime error (message has hipGetErrorString) */
     TRL_ERR_WEIGHTS = -3,   /* blob malformed or tensor missing */
     TRL_ERR_CAPACITY = -4,  /* (ABI <= 6: a candidate list exceeded its configured capacity.  Since ABI 7 no input can
-                             *  produce it: lists grow to what the content needs, as detect_face() has no limit) */
+                             *  produce it: lists grow to what the content needs, as detect_face() has no limit;
+                             *  trl_jpeg_header returns it for a buffer that is too small) */
     TRL_ERR_STATE = -5      /* call order (e.g. no weights loaded) */
 } trl_status;
 
@@ -251,6 +252,25 @@ int  trl_debug_pnet_kernel_ms(trl_ctx* ctx, float* ms);
  * event pair on its stream (trl_debug_timings out[0]); fused launches of different contexts on one device are ordered one after
  * the other, so that pair measures execution, not queueing. (ABI v6) */
 int  trl_debug_pnet_span(trl_ctx* ctx, int reset, double* ms_sum, int32_t* launches);
+
+/* ---- Motion-JPEG output (run()'s annotated video, server/model.py:35-36,77) ------------------------------------------------
+ * A baseline JPEG encoder whose files are byte-identical to Pillow's Image.save(format="JPEG", quality, subsampling=2) on the
+ * RGB frame (libjpeg-turbo: 4:2:0, Annex K tables scaled by quality, no restart markers, no optimisation; SOI, APP0 JFIF, DQT
+ * luma, DQT chroma, SOF0, DHT DC0 AC0 DC1 AC1, SOS, scan, EOI).  An encoder object owns its workspace and is independent of
+ * every cascade context.  (ABI v7) */
+typedef struct trl_jpeg trl_jpeg;
+/* An encoder for H x W frames (1..65535 px per side) at `quality` (clamped to 1..100 as libjpeg does), batches of up to max_frames. */
+int  trl_jpeg_create(int device, int H, int W, int quality, int max_frames, trl_jpeg** out);
+int  trl_jpeg_destroy(trl_jpeg* enc);
+/* n u8 BGR frames [H][W][3] at d_bgr + k * frame_stride bytes (frame_stride >= H*W*3 when n > 1) -> n complete JPEG files back to
+ * back at d_out.  h_sizes (host, n entries) receives every file's size whether or not it fitted: frame k starts at the sum of the
+ * sizes before it, and a file that would end past `capacity` bytes is not written, nor anything after it.  Sum(h_sizes) > capacity:
+ * grow the buffer and call again.  All work is queued on `stream`; the call returns after one synchronisation (to read the sizes). */
+int  trl_jpeg_encode(trl_jpeg* enc, const uint8_t* d_bgr, int n, long long frame_stride, uint8_t* d_out, long long capacity,
+                     long long* h_sizes, void* stream);
+/* Host only, no GPU: the bytes every file of such an encoder starts with (SOI .. SOS).  *len receives the length; a buffer of
+ * fewer than *len bytes gives TRL_ERR_CAPACITY and is left untouched. */
+int  trl_jpeg_header(int H, int W, int quality, uint8_t* buf, size_t cap, int* len);
 
 #ifdef __cplusplus
 }

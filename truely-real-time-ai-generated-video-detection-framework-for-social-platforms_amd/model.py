@@ -209,7 +209,8 @@ def run(video_path_one: str, video_path_two: str, engine: Engine | None = None) 
     streams and the pinned buffers are created on the first call and cached on the engine.
 
     Environment: TRUELY_ANNOTATE=0 writes the frames without boxes / text; TRUELY_WRITE_OUTPUT=0 skips the output stage
-    (benchmarking only: the server requires a non-empty file, server.py:612-627)."""
+    (benchmarking only: the server requires a non-empty file, server.py:612-627); TRUELY_JPEG=pillow encodes the Motion-JPEG
+    output with Pillow on the writer thread instead of on the engine's GPU (the same bytes, slower)."""
     start_time = time.time()
     # model.py:20-22
     if not os.path.exists(video_path_one) or os.path.getsize(video_path_one) == 0:
@@ -259,7 +260,8 @@ def _run_locked(ctx: _RunCtx, cap, fps: int, width: int, height: int, video_path
     all_rows = write_out and yuv                          # 4:2:0 + output: every frame is converted on the device for the writer
     rows = win * step if all_rows else win
     pinned, pinned_np, raw_dev = ctx.buffers(rows, row_bytes, yuv, height, width)
-    sink = video_io.open_writer(video_path_two, fps, (width, height)) if write_out else None
+    jpeg_dev = dev if os.environ.get("TRUELY_JPEG", "device") != "pillow" else None      # MJPEG output encoded on the GPU
+    sink = video_io.open_writer(video_path_two, fps, (width, height), device=jpeg_dev) if write_out else None
     writer = video_io.AsyncWriter(sink, annotate=os.environ.get("TRUELY_ANNOTATE", "1") != "0")
     reader = _WindowReader(cap, step, win, pinned_np, all_rows, keep_host=write_out and not yuv, frame_shape=(height, width, 3))
     for k in range(len(pinned)):

@@ -7,8 +7,9 @@ the build environment, so two back-ends exist behind the same tiny interface:
 * ``cv2`` when importable (real .mp4 in, annotated .mp4 out, like the reference);
 * the raw "TRLV" container (fps header + uint8 frames, BGR or -- what a hardware decoder hands over -- NV12) used by the
   tests and the benchmark.  NV12 clips take the device ingest path of ``model.run`` (SURVEY section 8(f) rank 1);
-* Motion-JPEG in AVI (``AviMjpegWriter`` / ``AviMjpegReader``, Pillow's libjpeg): the annotated OUTPUT when OpenCV is absent -- a
-  bounded standard file instead of raw frames -- and the one compressed INPUT this build decodes by itself;
+* Motion-JPEG in AVI (``AviMjpegWriter`` / ``AviMjpegReader``): the annotated OUTPUT when OpenCV is absent -- a bounded standard
+  file instead of raw frames, encoded by Pillow's libjpeg or, byte-identical, by the HIP encoder (jpeg.DeviceJpeg) -- and the one
+  compressed INPUT this build decodes by itself (Pillow);
 * YUV4MPEG2 (``.y4m``, 4:2:0 progressive): the uncompressed interchange format every decoder can emit
   (``ffmpeg -i clip.mp4 -pix_fmt yuv420p clip.y4m``).  Planes are repacked to NV12 on the fly and take the same device ingest.
 ``AsyncWriter`` is the decoupled, skippable annotated-output stage: drawing and encoding run on their
@@ -190,11 +191,27 @@ class AviMjpegWriter:
     past ~3.9 GB are dropped with a warning and the file is still closed properly."""
     LIMIT = 0xE8000000
 
-    def __init__(self, path, fps, size, quality: int = 80, threads: int | None = None):
+    BATCH = 32                                       # frames per device encoder call
+
+    def __init__(self, path, fps, size, quality: int = 80, threads: int | None = None, encoder: str = "pillow", device=None):
+        """``encoder="device"``: frames are collected into a pinned batch of ``BATCH``, encoded on the GPU ``device`` by
+        jpeg.DeviceJpeg (byte-identical files) and appended in order; ``"pillow"``: Pillow's libjpeg on the calling thread."""
         from PIL import Image                        # noqa: F401  (fail at open time, not on the writer thread)
         import collections
         import concurrent.futures
+        if encoder not in ("pillow", "device"):
+            raise ValueError(f"encoder must be 'pillow' or 'device', not {encoder!r}")
         self.path, self.w, self.h, self.fps, self.quality = path, int(size[0]), int(size[1]), max(1, int(round(fps))), int(quality)
+        self.encoder = encoder
+        self.dev_enc = self.batch = None
+        self.pending = 0
+        if encoder == "device":
+            import torch
+            from .jpeg import DeviceJpeg
+            self.dev_enc = DeviceJpeg(self.w, self.h, self.quality, device=device, max_frames=self.BATCH)
+            self.batch = torch.empty((self.BATCH, self.h, self.w, 3), dtype=torch.uint8).pin_memory()
+            self.batch_np = self.batch.numpy()
+            threads = 1
         self.threads = int(os.environ.get("TRUELY_ENCODE_THREADS", "1")) if threads is None else int(threads)
         self.pool = concurrent.futures.ThreadPoolExecutor(self.threads, thread_name_prefix="truely-jpeg") if self.threads > 1 else None
         self.inflight = collections.deque()
@@ -239,10 +256,23 @@ class AviMjpegWriter:
         self.max_chunk = max(self.max_chunk, len(data))
         self.n += 1
 
+    def _flush_device(self):
+        if self.pending:
+            for data in self.dev_enc.encode(self.batch[:self.pending]):
+                self._append(data)
+            self.pending = 0
+
     def write(self, frame):
         """Encode + append.  TRUELY_ENCODE_THREADS > 1 encodes on a small pool and appends in call order (at most 2 x threads
         encoded frames wait in memory); measured here Pillow's encoder holds the GIL for most of a frame (x1.3 with four
-        threads, ~750 frames/s of 360p per core), so the default is the writer thread alone."""
+        threads, ~750 frames/s of 360p per core), so the default is the writer thread alone.  The device encoder copies the frame
+        into its pinned batch and encodes every ``BATCH`` frames."""
+        if self.dev_enc is not None:
+            self.batch_np[self.pending] = frame
+            self.pending += 1
+            if self.pending == self.BATCH:
+                self._flush_device()
+            return
         if self.pool is None:
             self._append(self._encode(frame))
             return
@@ -251,6 +281,9 @@ class AviMjpegWriter:
             self._append(self.inflight.popleft().result())
 
     def release(self):
+        if self.dev_enc is not None:
+            self._flush_device()
+            self.dev_enc = None
         while self.inflight:
             self._append(self.inflight.popleft().result())
         if self.pool is not None:
@@ -440,16 +473,19 @@ def describe(path) -> str:
             f"{' (fragmented mp4)' if i.fragmented else ''}: decoding needs opencv-python (cv2.VideoCapture), or hand run() decoder output as an NV12 TRLV clip")
 
 
-def open_writer(path, fps, size, like_raw: bool = False):
+def open_writer(path, fps, size, like_raw: bool = False, device=None):
     """The sink of ``run()``'s annotated output (server/model.py:35-36).  ``*.trlv``: the raw container (tests, byte-exact
     read-back).  Otherwise OpenCV's H.264 writer when importable, like the reference; without OpenCV a Motion-JPEG AVI stream
-    (bounded size, plays anywhere -- but it is MJPEG/AVI whatever the file is called: H.264 needs OpenCV)."""
+    (bounded size, plays anywhere -- but it is MJPEG/AVI whatever the file is called: H.264 needs OpenCV), encoded on the GPU
+    ``device`` when one is given (byte-identical to Pillow's encoder, which is used otherwise)."""
     if str(path).lower().endswith(".trlv"):
         return RawWriter(path, fps, size)
     if cv2 is not None:  # pragma: no cover
         return cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*"H264"), fps, size)
     if not str(path).lower().endswith(".avi"):       # the server names the file *.mp4 and serves it as video/mp4: say what it really is
         print(f"Note: OpenCV is not installed, {os.path.basename(str(path))} is written as Motion-JPEG in an AVI container (not H.264)")
+    if device is not None:
+        return AviMjpegWriter(path, fps, size, encoder="device", device=device)
     return AviMjpegWriter(path, fps, size)
 
 

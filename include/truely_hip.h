@@ -195,6 +195,12 @@ int  trl_debug_list_stats(trl_ctx* ctx, long long* h_out8);
  * call queued on its device by ANY context, so that with several contexts in flight it runs alone (a timing aid: the HIP event
  * pair of trl_debug_timings is then the launch's duration).  Results never depend on them. (ABI v7) */
 int  trl_debug_option(trl_ctx* ctx, const char* key, int value);
+/* test hook: the fused PNet screens conv3 of every 32-cell M-tile on the fp16 matrix cores and recomputes it with the exact f32
+ * chain only where some cell's screened logit difference d satisfies d + A X + B >= the prefilter bound (X: the cell's largest
+ * |conv2 activation|).  Returns A, B (computed at weight load) and whether the screen is on (*on = 0: the conv3 weights do not fit
+ * fp16, or trl_debug_option(ctx, "pnet_screen", 0) switched it off; every M-tile then takes the exact path).  Results are the
+ * same either way. (ABI v7) */
+int  trl_debug_pnet_screen_bound(trl_ctx* ctx, float* A, float* B, int* on);
 /* test hook: the R-/O-Net launches are sized by optimistic per-frame candidate capacities; set them (<= 0 keeps a value) and read
  * how many attempts the last call took (a too-small capacity makes the call re-run itself with a larger one) */
 int  trl_debug_batch_capacity(trl_ctx* ctx, float t2_per_frame, float t3_per_frame, int* last_attempts);

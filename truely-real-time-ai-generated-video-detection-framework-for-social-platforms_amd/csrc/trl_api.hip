@@ -74,7 +74,7 @@ int trl_create(const trl_config* cfg, trl_ctx** out) {
     // execution span of every fused PNet launch (two atomics per workgroup, summed on the device: trl_debug_pnet_span);
     // TRL_PNET_CLOCK additionally selects the DBG instantiation with per-phase wave clocks
     c->pnet_prof = trl_tune_set("TRL_PNET_CLOCK");
-    if (hipMalloc((void**)&c->pnet_clk, 8 * 40) != hipSuccess || hipMemset(c->pnet_clk, 0, 8 * 40) != hipSuccess || hipMemset(c->pnet_clk, 0xFF, 8) != hipSuccess ||
+    if (hipMalloc((void**)&c->pnet_clk, 8 * 41) != hipSuccess || hipMemset(c->pnet_clk, 0, 8 * 41) != hipSuccess || hipMemset(c->pnet_clk, 0xFF, 8) != hipSuccess ||
         hipMalloc((void**)&c->pnet_cursor, 64) != hipSuccess || hipHostMalloc((void**)&c->h_pinned, 1024) != hipSuccess ||
         hipEventCreate(&c->ev_call0) != hipSuccess || hipEventCreate(&c->ev_call1) != hipSuccess) {
         trl_set_error("context allocation failed: %s", hipGetErrorString(hipGetLastError()));
@@ -99,13 +99,15 @@ int trl_destroy(trl_ctx* c) {
     if (c->pyr_tab) (void)hipFree(c->pyr_tab);
     if (c->pnet_clk) {
         // TRL_PNET_CLOCK: where the waves of the fused PNet launches spent their time (shader clocks per tile and wave, DBG instantiation)
-        unsigned long long t[40];
+        unsigned long long t[41];
         if (c->pnet_prof && hipMemcpy(t, c->pnet_clk, sizeof t, hipMemcpyDeviceToHost) == hipSuccess && t[2 + 32] > 0) {
             static const char* nm[8] = {"phase0", "barrier0", "phase1", "barrier1", "phase2", "barrier2", "phase3", "barrier3"};
             const double tiles = (double)t[2 + 32];
             fprintf(stderr, "[TRL_PNET_CLOCK] shader clocks per tile (wave 0..3), %.0f workgroup-tiles\n", tiles);
             for (int k = 0; k < 8; k++)
                 fprintf(stderr, "[TRL_PNET_CLOCK] %-9s %8.0f %8.0f %8.0f %8.0f\n", nm[k], t[2 + k] / tiles, t[2 + 8 + k] / tiles, t[2 + 16 + k] / tiles, t[2 + 24 + k] / tiles);
+            fprintf(stderr, "[TRL_PNET_CLOCK] fp16 screen: %llu M-tiles screened, %llu confirmed (%.2f %%)\n", t[39], t[40],
+                    t[39] ? 100.0 * (double)t[40] / (double)t[39] : 0.0);
         }
         (void)hipFree(c->pnet_clk);
     }
@@ -804,8 +806,15 @@ int trl_debug_option(trl_ctx* c, const char* key, int value) {
     TRL_CHECK(check_idle(c));
     if (!strcmp(key, "rnet_chunk") && value >= 16) { c->rnet_chunk = value; return TRL_OK; }
     if (!strcmp(key, "onet_chunk") && value >= 16) { c->onet_chunk = value; return TRL_OK; }
+    if (!strcmp(key, "pnet_screen") && (value == 0 || value == 1)) { c->pnet_screen = value; return TRL_OK; }
     trl_set_error("unknown option '%s' (or value %d out of range)", key, value);
     return TRL_ERR_INVALID;
+}
+
+int trl_debug_pnet_screen_bound(trl_ctx* c, float* A, float* B, int* on) {
+    if (!c || !A || !B || !on) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
+    *A = c->pnet_scrA; *B = c->pnet_scrB; *on = c->pnet_screen_ok && c->pnet_screen;
+    return TRL_OK;
 }
 
 int trl_debug_batch_capacity(trl_ctx* c, float t2_per_frame, float t3_per_frame, int* last_attempts) {

@@ -63,9 +63,12 @@ struct trl_ctx {
     float last_ms[4] = {0, 0, 0, 0};
     int pnet_mono1 = 0;              // conv1 PReLU slopes all >= 0
     int pnet_unit = 0;               // no PNet PReLU slope above 1 (negative ones allowed): prelu(v) == max(v, s v)
+    float pnet_scrA = 0.f, pnet_scrB = 0.f;   // fp16 conv3 screen of the fused PNet: |d_screen - d_exact| <= A X + B (trl_pnet_prepare)
+    int pnet_screen_ok = 0;          // the conv3 weights fit fp16 (else the screen is off for this net)
+    int pnet_screen = 1;             // trl_debug_option "pnet_screen": 0 = every M-tile takes the exact f32 path
     int pnet_run = 0;                // > 0: tiles per cursor fetch of the fused PNet launch (trl_debug_pnet_run); 0 = automatic
     int32_t* pnet_cursor = nullptr;           // device: 8 per-XCD tile cursors of the fused PNet launch
-    unsigned long long* pnet_clk = nullptr;   // device: [0] first-start / [1] last-end wall clock of the fused PNet launch in flight, [2..35] phase clocks (DBG), [36] summed spans, [37] launches
+    unsigned long long* pnet_clk = nullptr;   // device: [0] first-start / [1] last-end wall clock of the fused PNet launch in flight, [2..35] phase clocks (DBG), [36] summed spans, [37] launches, [39] / [40] screened / confirmed M-tiles (DBG)
     bool pnet_prof = false;                   // TRL_PNET_CLOCK: the DBG instantiation with per-phase wave clocks
     float pnet_kernel_ms = 0.f;      // its span in ms (collect_timings)
     int dbg_poison = -1;             // >= 0 after trl_debug_poison: byte written into every newly allocated workspace

@@ -18,7 +18,8 @@
 //                 All four layers run on the f32 matrix cores -- the layers with few output channels (conv1: 10, heads: 6)
 //                 on v_mfma_f32_4x4x1_16B_f32 with the weight block broadcast (no padding of N to 16), conv2 on
 //                 v_mfma_f32_16x16x4_f32, conv3 on v_mfma_f32_32x32x2_f32 -- k ascending, accumulator seeded with the
-//                 bias: the same fmaf chain as the oracle, so maps and candidates are bit-identical.
+//                 bias: the same fmaf chain as the oracle, so maps and candidates are bit-identical.  conv3 is first screened on
+//                 v_mfma_f32_32x32x16_f16 with a rigorous error bound: only the M-tiles that may hold a candidate take the f32 chain.
 //                 conv1 / conv2 / head weights live in registers for the whole launch (6+23+4 VGPRs per lane),
 //                 conv3's in LDS; activations never leave the CU: HBM traffic is the pyramid read only.  f32 MFMA and VALU share the FP32 pipe, so the loops carry almost no VALU: the
 //                 tile decode is scalar (multiply-high by host magic numbers), LDS addresses are lane bases +
@@ -31,6 +32,7 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes at dword alignment
 struct __attribute__((packed, aligned(4))) u32x3_a4 { unsigned x, y, z; };
 
@@ -99,6 +101,7 @@ struct PnetArgs {
     const float *b1, *b2, *b3, *bh, *s1, *s2, *s3;
     float thr; int rec_stride;                 // record slots per frame (LvLayout::S)
     float dthr;                                // logit-difference prefilter: no cell with logit1 - logit0 < dthr can reach thr (-inf: off)
+    float scrA, scrB; int screen;              // fp16 conv3 screen: |d_screen - d_exact| <= scrA X + scrB (screen = 0: every M-tile exact)
     int dbg_skip;                              // timing-only ablation mask (TRL_PNET_SKIP); read by the DBG instantiation only
     int32_t* lvl_cnt; Cand* lvl_rec; int32_t* flags;
     int32_t* xcd_next;                         // per-XCD dynamic tile cursor (8 counters, zeroed before the launch)
@@ -599,7 +602,8 @@ template <bool UNIT, bool NEG1, bool DBG>
 __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
     __shared__ __attribute__((aligned(16))) float RA[REGION_A];   // input tile [42][42][3]  ->  conv2 out [324][17]
     __shared__ __attribute__((aligned(16))) float RB[REGION_B];   // pooled [400][10] (+ the reach of conv2's zero-weight k padding)
-    __shared__ __attribute__((aligned(16))) float T3all[72];      // conv3 bias[32], PReLU slopes[32] (a lane's 16 channels differ per register), head bias[8] (phase 3)
+    __shared__ __attribute__((aligned(16))) float T3all[108];     // conv3 bias[32], PReLU slopes[32] (a lane's 16 channels differ per register), head bias[8],
+                                                                  // screen: logit-difference weights f32(w1 - w0)[32], bias f32(b1 - b0) (phase 3)
     extern __shared__ __attribute__((aligned(16))) float DYN[];  // DYN_LDS bytes, then whatever a tuning run pads (TRL_PNET_XLDS)
     float* const B3S = DYN;                                       // conv3 weights [k][cout]: read per k-chain batch, not held in VGPRs
     float* const CP0 = DYN + 144 * 32;                            // per band row: carried pooled columns [20][4][10], conv2 columns [18][2][17]
@@ -623,6 +627,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
     // (vectors are zero padded to 128 floats)
     const float bias2 = a.b2[l15], slope2 = a.s2[l15];
     if (tid < 32) { T3all[tid] = a.b3[tid]; T3all[32 + tid] = a.s3[tid]; if (tid < 8) T3all[64 + tid] = a.bh[tid]; }   // (published by the barrier below)
+    if (tid < 32) { T3all[72 + tid] = a.wh[tid * 32 + 1] - a.wh[tid * 32]; if (tid == 0) T3all[104] = a.bh[1] - a.bh[0]; }
     // general instantiation only: the per-channel med3 selector (+inf: max(v, s v), -inf: min(v, s v)); dead code when UNIT
     const float sel2 = trl_prelu_sel(slope2);
     const f32x4 bias2v = {bias2, bias2, bias2, bias2};
@@ -812,6 +817,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
         if (DBG && prof) { const unsigned long long t = clock64(); pt[k] += t - pt_last; pt_last = t; }
     };
     if (DBG && prof) pt_last = clock64();
+    unsigned nscr = 0, ncnf = 0;                  // DBG: M-tiles this wave screened / confirmed (clk[39], clk[40])
     for (; tile < t_end; tile = tile_nxt, cur = nxt, rot++) {
         const int f = cur.f, l = cur.l, ty = cur.ty, tx = cur.tx;
         const TileId& g = cur;
@@ -1270,11 +1276,64 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
             // only the first: those output rows lie below the level).  The head chain of the first rides in the MFMA stream of the
             // second -- one 8-cycle block instruction after every second 64-cycle one, so its 32 dependent steps never wait.
             const int mt0 = wave, mt1 = wave + 4;
-            if (2 * mt0 < vrows) {
+            const bool has0 = 2 * mt0 < vrows, has1 = 2 * mt1 < vrows;
+            bool cf0 = has0, cf1 = has1;                        // M-tiles that take the exact f32 path
+            // fp16 screen: conv3 of each M-tile on v_mfma_f32_32x32x16_f16, one instruction per 3x3 tap
+            // (K = the 16 conv2 channels), in the transposed layout of conv3 below -- lane l: cell l & 31, channels
+            // 8 (q >> 2) + (q & 3) + 4 hh.  Operands are rounded from the f32 tile and weights in LDS as they are read.  Then PReLU and
+            // the logit difference d (one 16-term chain per half, the halves added): an M-tile is confirmed when some valid cell
+            // has d + A X + B >= dthr (X: the cell's largest |conv2 input|), d is not finite or X exceeds fp16.  A cell the exact
+            // path would let through the prefilter (d_exact >= dthr) always confirms its M-tile, so the records are unchanged.
+            if (has0 && a.screen) {
+                const int sb0 = ((mt0 * 2 + (l31 >> 4)) * C2_T + (l31 & 15)) * C2_LD + 8 * hh;
+                auto screen = [&](int mt, int sb) __attribute__((always_inline)) {
+                    f32x16 S;
+#pragma unroll
+                    for (int qa = 0; qa < 4; qa++) {
+                        const f32x4 b4 = T3[2 * qa + hh];
+#pragma unroll
+                        for (int qb = 0; qb < 4; qb++) S[4 * qa + qb] = b4[qb];
+                    }
+                    float xm = 0.f;
+#pragma unroll
+                    for (int tap = 0; tap < 9; tap++) {
+                        const int to = ((tap / 3) * C2_T + tap % 3) * C2_LD;
+                        f16x8 wv, xv;
+#pragma unroll
+                        for (int j = 0; j < 8; j++) {
+                            wv[j] = (_Float16)B3S[(tap * 16 + 8 * hh + j) * 32 + l31];
+                            const float v = RA[sb + to + j];
+                            xm = fmaxf(xm, fabsf(v));
+                            xv[j] = (_Float16)v;
+                        }
+                        S = __builtin_amdgcn_mfma_f32_32x32x16_f16(wv, xv, S, 0, 0, 0);
+                    }
+                    float part = 0.f;
+#pragma unroll
+                    for (int qa = 0; qa < 4; qa++) {
+                        const f32x4 s4 = T3[8 + 2 * qa + hh], w4 = T3[18 + 2 * qa + hh];   // slopes, difference weights
+#pragma unroll
+                        for (int qb = 0; qb < 4; qb++)
+                            part = __builtin_fmaf(w4[qb], prelu_t<UNIT>(S[4 * qa + qb], s4[qb], UNIT ? 0.f : trl_prelu_sel(s4[qb])), part);
+                    }
+                    const auto pp = __builtin_amdgcn_permlane32_swap(__float_as_uint(part), __float_as_uint(part), false, false);
+                    const auto px = __builtin_amdgcn_permlane32_swap(__float_as_uint(xm), __float_as_uint(xm), false, false);
+                    const float d = (part + __uint_as_float(pp[1])) + T3all[104];
+                    const float X = fmaxf(xm, __uint_as_float(px[1]));
+                    const float E = __builtin_fmaf(a.scrA, X, a.scrB);
+                    const int oy = ty * TS + mt * 2 + (lane >> 4), ox = tx * TS + (lane & 15);
+                    const bool hit = !(d + E < a.dthr) || !(fabsf(d) <= 3.402823466e38f) || X > 65504.f;
+                    return __builtin_amdgcn_ballot_w64(lane < 32 && oy < g.oh && ox < g.ow && hit) != 0;
+                };
+                cf0 = screen(mt0, sb0);
+                if (has1) cf1 = screen(mt1, sb0 + 8 * C2_T * C2_LD);   // M-tile mt0 + 4: 8 conv2 rows down
+                if (DBG) { nscr += has1 ? 2 : 1; ncnf += (cf0 ? 1 : 0) + (cf1 ? 1 : 0); }
+            }
+            if (cf0 && cf1) {
                 f32x16 P0;
                 f32x4 hq0 = T3[16 + hh];                        // head bias of this half's output group
                 conv3(mt0, P0, [](auto, auto) {});
-                if (2 * mt1 < vrows) {
+                {
                     f32x16 P1;
                     f32x4 hq1 = T3[16 + hh];
                     conv3(mt1, P1, [&](auto SX, auto UU) __attribute__((always_inline)) {
@@ -1289,11 +1348,15 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
                     heads_all(P1, hq1);
                     emit(mt0, hq0);
                     emit(mt1, hq1);
-                } else {
-                    strips_get();
-                    heads_all(P0, hq0);
-                    emit(mt0, hq0);
                 }
+            } else if (cf0 || cf1) {
+                const int mt = cf0 ? mt0 : mt1;
+                f32x16 P0;
+                f32x4 hq0 = T3[16 + hh];
+                conv3(mt, P0, [](auto, auto) {});
+                strips_get();
+                heads_all(P0, hq0);
+                emit(mt, hq0);
             } else {
                 strips_get();
             }
@@ -1309,6 +1372,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
         for (int k = 0; k < 8; k++) atomicAdd(&a.clk[2 + 8 * wave + k], pt[k]);
         if (wave == 0) atomicAdd(&a.clk[2 + 32], (unsigned long long)rot);
     }
+    if (DBG && lane == 0 && nscr) { atomicAdd(&a.clk[39], (unsigned long long)nscr); atomicAdd(&a.clk[40], (unsigned long long)ncnf); }
     if (DBG && tid == 0) atomicMax(&a.clk[1], (unsigned long long)wall_clock64());
 }
 
@@ -1320,6 +1384,52 @@ __global__ void k_pnet_span(unsigned long long* clk) {
     const unsigned long long d = t1 > t0 ? t1 - t0 : 0ull;
     clk[36] += d; clk[37] += 1ull; clk[38] = d;
     clk[0] = ~0ull; clk[1] = 0ull;
+}
+
+// Error bound of the fp16 conv3 screen: for a cell whose 3x3x16 conv2 inputs satisfy |x| <= X <= 65504,
+// |d_screen - d_exact| <= A X + B, d = logit1 - logit0.  Operands round once to fp16 (relative 2^-11, absolute 2^-14 for a
+// subnormal kept or flushed), the MFMA sums 145 terms in an unspecified order (taken at 2u per addition), the exact chain is 145
+// fmaf; PReLU is Lipschitz with max(1, |slope|); the exact heads are two 33-term chains and a subtraction, the screened
+// difference head one 36-term chain over f32(w1 - w0).  Double precision, then A and B rounded up (tools/pnet_screen_audit.py
+// states the same bound, tests/test_pnet_screen_cpu.py compares the two).
+static int pnet_screen_bound(trl_ctx* c, const DevW* w3, const DevW* wh) {
+    std::vector<float> W(144 * 32), H(32 * 32), b3(32), s3(32), bh(8);
+    TRL_HIP(hipMemcpy(W.data(), w3->p, W.size() * sizeof(float), hipMemcpyDeviceToHost));
+    TRL_HIP(hipMemcpy(H.data(), wh->p, H.size() * sizeof(float), hipMemcpyDeviceToHost));
+    TRL_HIP(hipMemcpy(b3.data(), trl_v(c, "pnet.conv3.b")->p, 32 * sizeof(float), hipMemcpyDeviceToHost));
+    TRL_HIP(hipMemcpy(s3.data(), trl_v(c, "pnet.prelu3")->p, 32 * sizeof(float), hipMemcpyDeviceToHost));
+    TRL_HIP(hipMemcpy(bh.data(), trl_v(c, "pnet.heads.b")->p, 2 * sizeof(float), hipMemcpyDeviceToHost));
+    c->pnet_screen_ok = 0; c->pnet_scrA = c->pnet_scrB = __builtin_inff();
+    for (float v : W) if (!(fabsf(v) <= 65504.f)) return TRL_OK;          // a weight fp16 cannot hold: no screen for this net
+    const double u = ldexp(1.0, -24), uh = ldexp(1.0, -11), tiny = ldexp(1.0, -14);
+    auto gamma = [](int n, double uu) { return n * uu / (1.0 - n * uu); };
+    const double ge = gamma(145, u), gs = gamma(145, 2 * u), g35 = gamma(35, u), g36 = gamma(36, u);
+    double Sa = 0, Sb = fabs((double)bh[0]) + fabs((double)bh[1]);
+    double ad = 0, bd = 0, wdP_a = 0, wdP_b = 0;
+    for (int co = 0; co < 32; co++) {
+        double W1 = 0, D = 0;
+        for (int k = 0; k < 144; k++) {
+            const double w = W[k * 32 + co], aw = fabs(w);
+            W1 += aw;
+            D += aw < tiny ? aw : fabs((double)(float)(_Float16)W[k * 32 + co] - w);
+        }
+        const double b = fabs((double)b3[co]), L = fmax(1.0, fabs((double)s3[co]));
+        const double a3 = D * (1 + uh) + W1 * uh + gs * (W1 + D) * (1 + uh) + ge * W1;
+        const double b3e = D * tiny + W1 * tiny + gs * (b + (W1 + D) * tiny) + ge * b;
+        const double aM = W1 * (1 + ge), bM = b * (1 + ge);
+        const double ap = L * (1 + u) * a3 + 2 * u * L * aM, bp = L * (1 + u) * b3e + 2 * u * L * bM;
+        const double aP = L * (1 + u) * aM, bP = L * (1 + u) * bM;
+        const double w0 = H[co * 32 + 0], w1 = H[co * 32 + 1], wd = fabs(w1 - w0);
+        Sa += (fabs(w0) + fabs(w1)) * aP; Sb += (fabs(w0) + fabs(w1)) * bP;
+        ad += wd * ap; bd += wd * bp;
+        wdP_a += wd * (aP + ap); wdP_b += wd * (bP + bp);
+    }
+    ad += g36 * (1 + u) * wdP_a;
+    bd += g36 * (1 + u) * (fabs((double)bh[1] - (double)bh[0]) + wdP_b);
+    const double A = (g35 * Sa + ad) * (1 + ldexp(1.0, -10)), B = (g35 * Sb + bd) * (1 + ldexp(1.0, -10));
+    auto up = [](double v) { float f = (float)v; return (double)f < v ? nextafterf(f, __builtin_inff()) : f; };
+    c->pnet_scrA = up(A); c->pnet_scrB = up(B); c->pnet_screen_ok = 1;
+    return TRL_OK;
 }
 
 int trl_pnet_prepare(trl_ctx* c) {
@@ -1343,7 +1453,7 @@ int trl_pnet_prepare(trl_ctx* c) {
         TRL_HIP(hipMemcpy(h.data(), v->p, h.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (float x : h) if (!(x <= 1.f)) c->pnet_unit = 0;
     }
-    return TRL_OK;
+    return pnet_screen_bound(c, w3, wh);
 }
 
 // ceil(2^32 / d) for the kernel's sdiv(); d == 1 would need 2^32: 2^32 - 1 gives q = n - 1 (or 0), which sdiv's upward correction
@@ -1424,6 +1534,7 @@ static int fill_args(trl_ctx* c, int n, int H, int W, PnetArgs& a, std::vector<u
     // p = softmax(logit0, logit1)[1] >= thr needs logit1 - logit0 >= ln(thr / (1 - thr)) up to the rounding of the float softmax
     // (~1e-6 relative); 0.05 below that bound the probability is short of thr by 0.05 thr (1 - thr) >= 4.9e-4 for thr in [0.01, 0.99]
     a.dthr = (a.thr >= 0.01f && a.thr <= 0.99f) ? (float)(log((double)a.thr / (1.0 - (double)a.thr)) - 0.05) : -__builtin_inff();
+    a.scrA = c->pnet_scrA; a.scrB = c->pnet_scrB; a.screen = c->pnet_screen && c->pnet_screen_ok;
     a.dbg_skip = trl_tune_int("TRL_PNET_SKIP", 0);
     a.lvl_cnt = c->cb.lvl_cnt; a.lvl_rec = c->cb.lvl_rec; a.flags = c->cb.flags;
     a.clk = c->pnet_clk; a.prof = c->pnet_prof ? 1 : 0;

@@ -303,7 +303,7 @@ class Engine:
         return k.value
 
     def option(self, key: str, value: int):
-        """Test hook (``trl_debug_option``): "rnet_chunk" / "onet_chunk" (this context), "no_fnconv" (process-wide)."""
+        """Test hook (``trl_debug_option``): "rnet_chunk" / "onet_chunk" / "pnet_screen" (this context), "no_fnconv" (process-wide)."""
         _lib.check(self.lib.trl_debug_option(self._h, key.encode(), int(value)))
 
     def nms_tiers(self, small: int = 0, full: int = 0):
@@ -317,6 +317,12 @@ class Engine:
         _lib.check(self.lib.trl_debug_list_stats(self._h, t))
         keys = ("attempts", "spill_lists", "spill_used", "spill_cap", "cap_frame", "slots_per_frame", "max_level_count", "max_frame_total")
         return dict(zip(keys, (int(v) for v in t)))
+
+    def pnet_screen_bound(self):
+        """Test hook: (A, B, on) of the fused PNet's fp16 conv3 screen, |d_screen - d_exact| <= A X + B."""
+        A, B, on = C.c_float(), C.c_float(), C.c_int()
+        _lib.check(self.lib.trl_debug_pnet_screen_bound(self._h, C.byref(A), C.byref(B), C.byref(on)))
+        return float(A.value), float(B.value), bool(on.value)
 
     def pnet_run(self, run: int = 0):
         """Test / tuning hook: tiles per cursor fetch of the fused PNet launch (0 = automatic); > 1 exercises the halo carry."""

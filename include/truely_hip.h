@@ -221,6 +221,25 @@ int  trl_debug_pyramid_batch(trl_ctx* ctx, const uint8_t* d_frames, int n, int H
 enum { TRL_PYR_FINE = 1, TRL_PYR_S4 = 2, TRL_PYR_S8 = 3, TRL_PYR_SW4 = 4, TRL_PYR_SW8 = 5,
        TRL_PYR_L0_3 = 6, TRL_PYR_L0_4 = 7, TRL_PYR_L0_5 = 8, TRL_PYR_L1 = 9, TRL_PYR_L2 = 10 };
 int  trl_debug_pyramid_plan(trl_ctx* ctx, int32_t* h_rows, int max_levels, int* n_levels);
+/* test hook: the conv launches of the context's last embedder call, in walk order: one row per conv, recorded host-side where the
+ * launcher picks the kernel (no device work, no influence on the choice).  family = TRL_FNK_* below; bm / bn / bk = the workgroup
+ * tile and K chunk of the instantiation; pad = its PAD template argument (0 for families without one); nz = convs sharing the launch
+ * (grouped small-map launches); precision = 0 f32, 1 bf16, 2 fp16; has_res = the conv adds a residual.  *n_rows = the call's conv
+ * count (rows past max_rows are not written). (ABI v7) */
+enum { TRL_FNK_FN_CONV = 1, TRL_FNK_FN_SPLIT4 = 2, TRL_FNK_CONV_TAP = 3, TRL_FNK_IGEMM_VEC = 4, TRL_FNK_IGEMM_SCALAR = 5,
+       TRL_FNK_SPLITK4 = 6, TRL_FNK_SPLITK4_TAP = 7, TRL_FNK_TAP48 = 8, TRL_FNK_BF16 = 9 };
+typedef struct {
+    int32_t conv, family, bm, bn, bk, pad, nz, m, cout, k, precision, has_res;
+    char layer[48];
+} trl_fn_plan_row;
+int  trl_debug_facenet_plan(trl_ctx* ctx, trl_fn_plan_row* h_rows, int max_rows, int* n_rows);
+/* test hook: arm conv `conv_index` (the walk order of trl_debug_facenet_plan; -1 disarms).  The next embedder call on ctx copies
+ * that conv's input view, residual view (if any) and output view right behind its launch, on the call's stream, into buffers of
+ * the context: dense NHWC in the activation's element type (f32, or 16-bit in reduced-precision mode).  The call disarms it.
+ * trl_debug_facenet_capture_read: view 0 input / 1 residual / 2 output; dims = {n, h, w, c, bytes per element} (c = 0: no such
+ * view); h_dst may be NULL to query the dims, else it receives n*h*w*c elements if they fit max_bytes (TRL_ERR_INVALID if not). */
+int  trl_debug_facenet_capture(trl_ctx* ctx, int conv_index);
+int  trl_debug_facenet_capture_read(trl_ctx* ctx, int view, void* h_dst, size_t max_bytes, int32_t* dims5);
 /* test hook: fill the activation workspaces with a byte pattern (0xFF -> NaNs) before the next call */
 int  trl_debug_poison(trl_ctx* ctx, int byte);
 /* PNet on one pyramid level of frame 0: face-prob map and regression map (device outputs). */

@@ -520,7 +520,7 @@ def test_begin_end_contract(engine):
 def test_large_embedder_batches_cross_kernel_families(engine, oracle):
     """ONE embedder call over more than 335 faces at 80x80 pushes block35's GEMMs past M = 16384 rows: the small-map family
     (fn_conv, 16x16x4 MFMA, grouped launches) hands over to the generic conv_tap kernels (32x32x2 MFMA).  bench.py's grouped
-    embedder (768 faces per call) runs exactly that.  The embeddings must be the bits of 256-face calls and of the oracle --
+    embedder (2,048 faces per call by default) runs exactly that.  The embeddings must be the bits of 256-face calls and of the oracle --
     and again with the small-map family switched off altogether (trl_debug_option "no_fnconv")."""
     fr = truely_amd.synthetic.synthetic_frames(8, 360, 640, seed=11)
     c = engine.detect_crop(fr)

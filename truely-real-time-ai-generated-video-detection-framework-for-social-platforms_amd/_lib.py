@@ -57,6 +57,9 @@ _SIGNATURES = {
     "trl_debug_pyramid_level": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i), _vp]),
     "trl_debug_pyramid_batch": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong), _vp, _i, C.POINTER(_i), _vp]),
     "trl_debug_pyramid_plan": (C.c_int, [_vp, _vp, _i, C.POINTER(_i)]),
+    "trl_debug_facenet_plan": (C.c_int, [_vp, _vp, _i, C.POINTER(_i)]),
+    "trl_debug_facenet_capture": (C.c_int, [_vp, _i]),
+    "trl_debug_facenet_capture_read": (C.c_int, [_vp, _i, _vp, C.c_size_t, _vp]),
     "trl_debug_pnet_level": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i), _vp]),
     "trl_debug_rnet": (C.c_int, [_vp, _vp, _i, _vp, _vp]),
     "trl_debug_onet": (C.c_int, [_vp, _vp, _i, _vp, _vp]),

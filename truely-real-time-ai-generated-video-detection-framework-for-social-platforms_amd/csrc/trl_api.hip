@@ -97,6 +97,7 @@ int trl_destroy(trl_ctx* c) {
     if (c->scratch.base) (void)hipFree(c->scratch.base);
     if (c->sims_tmp.base) (void)hipFree(c->sims_tmp.base);
     if (c->pyr_tab) (void)hipFree(c->pyr_tab);
+    for (auto& b : c->fn_cap) if (b.p) (void)hipFree(b.p);
     if (c->pnet_clk) {
         // TRL_PNET_CLOCK: where the waves of the fused PNet launches spent their time (shader clocks per tile and wave, DBG instantiation)
         unsigned long long t[41];
@@ -285,6 +286,16 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
     TRL_CHECK(merge_heads("rnet", {"dense5_1", "dense5_2"}));
     TRL_CHECK(merge_heads("onet", {"dense6_1", "dense6_2", "dense6_3"}));
 
+    if (c->cfg.embed_precision == 2) {   // an fp16 conv weight that rounds past +-65504 would become inf: refuse the blob instead
+        for (auto& p : items) {
+            if (!p.mat || p.name.rfind("facenet.", 0) != 0 || p.name == "facenet.conv2d_1a.w" || p.name == "facenet.last_linear.w") continue;
+            for (size_t i = 0; i < (size_t)p.K * p.Cout; i++)
+                if (!(fabsf(p.src[i]) < 65520.f)) {   // 65520 is the rounding midpoint to the next (infinite) binade; NaN fails too
+                    trl_set_error("weight %s[%zu] = %g is outside the fp16 range", p.name.c_str(), i, p.src[i]);
+                    return TRL_ERR_WEIGHTS;
+                }
+        }
+    }
     std::vector<char> host(total, 0);
     for (auto& p : items) {
         float* dst = (float*)(host.data() + p.off);
@@ -677,6 +688,34 @@ int trl_debug_pyramid_plan(trl_ctx* c, int32_t* h_rows, int max_levels, int* n_l
     *n_levels = c->pyr_plan.L;
     for (int l = 0; l < c->pyr_plan.L && l < max_levels; l++)
         for (int k = 0; k < TRL_PYR_PLAN_COLS; k++) h_rows[l * TRL_PYR_PLAN_COLS + k] = c->pyr_plan.row[l][k];
+    return TRL_OK;
+}
+
+int trl_debug_facenet_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, int* n_rows) {
+    TRL_CHECK(check_idle(c));
+    if (!n_rows || (max_rows > 0 && !h_rows)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
+    *n_rows = (int)c->fn_plan.size();
+    for (int i = 0; i < *n_rows && i < max_rows; i++) h_rows[i] = c->fn_plan[i];
+    return TRL_OK;
+}
+
+int trl_debug_facenet_capture(trl_ctx* c, int conv_index) {
+    TRL_CHECK(check_idle(c));
+    c->fn_cap_arm = conv_index < 0 ? -1 : conv_index;
+    return TRL_OK;
+}
+
+int trl_debug_facenet_capture_read(trl_ctx* c, int view, void* h_dst, size_t max_bytes, int32_t* dims5) {
+    TRL_CHECK(check_idle(c));
+    if (view < 0 || view > 2 || !dims5) { trl_set_error("bad capture view %d", view); return TRL_ERR_INVALID; }
+    const auto& b = c->fn_cap[view];
+    for (int k = 0; k < 5; k++) dims5[k] = b.dims[k];
+    if (!h_dst || b.dims[3] == 0) return TRL_OK;
+    const size_t bytes = (size_t)b.dims[0] * b.dims[1] * b.dims[2] * b.dims[3] * b.dims[4];
+    if (bytes > max_bytes) { trl_set_error("capture needs %zu bytes", bytes); return TRL_ERR_INVALID; }
+    TRL_HIP(hipSetDevice(c->cfg.device));
+    TRL_HIP(hipDeviceSynchronize());
+    TRL_HIP(hipMemcpy(h_dst, b.p, bytes, hipMemcpyDeviceToHost));
     return TRL_OK;
 }
 

@@ -10,7 +10,7 @@
 // conv_bf16: whole-tap implicit GEMM (see conv_tap in trl_layers.hip): K chunks of BK channels of one filter tap,
 // scalar im2col cursor, A = [pixel][k] and B = [cout][k] staged k-contiguous in LDS so that an MFMA operand is one
 // ds_read_b128 (8 bf16); rows padded by 16 bytes: the 32 rows x 2 k-halves of an operand read hit distinct banks.
-#include "trl_common.h"
+#include "trl_ctx.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -20,13 +20,18 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 __device__ __forceinline__ float bf2f(uint16_t h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {            // round to nearest even (inputs are finite)
+__device__ __forceinline__ uint16_t f2bf(float f) {            // round to nearest even; NaN stays a (quiet) NaN
     const unsigned u = __builtin_bit_cast(unsigned, f);
+    if (f != f) return (uint16_t)((u >> 16) | 0x40u);
     return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
 }
 
 // P = 1: bf16 (8 exponent bits: no range concerns), P = 2: IEEE fp16 (3 more mantissa bits; FaceNet's activations are O(1..100),
-// far inside +-65504, and a value that did overflow would surface as inf -> NaN embedding, never as a silent wrong number)
+// far inside +-65504).  A value that does overflow fp16 becomes +-inf, the next conv turns it into NaN where signs mix, and every
+// 16-bit kernel passes a NaN on (lp_relu, lp_max below; MFMA, residual add and the average pool do by IEEE rules), so the face's
+// embedding comes out NaN -- never a finite wrong number.  The f32 ReLU / max would map NaN to 0 / drop it.
+__device__ __forceinline__ float lp_relu(float v) { return v > 0.f || v != v ? v : 0.f; }          // bits of finite / inf inputs unchanged
+__device__ __forceinline__ float lp_max(float v, float best) { return v > best || v != v ? v : best; }   // a NaN, once seen, is kept
 template <int P> __device__ __forceinline__ float lp2f(uint16_t h) {
     if (P == 1) return bf2f(h);
     return (float)__builtin_bit_cast(_Float16, h);
@@ -164,7 +169,7 @@ __global__ __launch_bounds__(256) void conv_bf16(ConvArgs a) {
                 float v = acc[tm][tn][i];
                 if (a.scale) v = __builtin_fmaf(v, sc, sf);
                 if (a.res) v = v * a.res_scale + lp2f<P>(rg[(size_t)mr * a.ldres + n]);
-                if (a.act == TRL_ACT_RELU) v = v > 0.f ? v : 0.f;
+                if (a.act == TRL_ACT_RELU) v = lp_relu(v);
                 yg[(size_t)mr * a.ldy + a.yoff + n] = f2lp<P>(v);
             }
         }
@@ -210,8 +215,8 @@ __global__ void k_maxpool_bf16(const uint16_t* __restrict__ x, int N, int H, int
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float lo = lp2f<P>((uint16_t)(v[j] & 0xFFFFu)), hi = lp2f<P>((uint16_t)(v[j] >> 16));
-                    best[2 * j] = lo > best[2 * j] ? lo : best[2 * j];
-                    best[2 * j + 1] = hi > best[2 * j + 1] ? hi : best[2 * j + 1];
+                    best[2 * j] = lp_max(lo, best[2 * j]);
+                    best[2 * j + 1] = lp_max(hi, best[2 * j + 1]);
                 }
             }
         u32x4 o;
@@ -236,6 +241,7 @@ template <int BM, int BN, int BK>
 int launch_bf16(const ConvArgs& a, hipStream_t s) {
     dim3 grid((a.M + BM - 1) / BM, (a.Cout + BN - 1) / BN);
     const bool pad = a.ph || a.pw;
+    g_trl_conv_choice = TrlConvChoice{TRL_FNK_BF16, BM, BN, BK, pad, 1};
     if (a.lowp == 2) {
         if (pad) conv_bf16<BM, BN, BK, true, 2><<<grid, 256, 0, s>>>(a); else conv_bf16<BM, BN, BK, false, 2><<<grid, 256, 0, s>>>(a);
     } else {

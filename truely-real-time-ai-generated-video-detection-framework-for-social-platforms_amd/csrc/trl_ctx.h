@@ -100,7 +100,16 @@ struct trl_ctx {
     struct { int nlev = 0, own0 = 0, band_cols = 0, strip_rows = 0, n_bands = 0, n_strips = 0; } pyr_fine;
     // what the last build_pyramid chose per level (trl_debug_pyramid_plan): rows of TRL_PYR_PLAN_COLS ints; L = 0 after a refused call
     struct { int L = 0; int32_t row[16][TRL_PYR_PLAN_COLS] = {}; } pyr_plan;
+    std::vector<trl_fn_plan_row> fn_plan;   // the conv launches of the last embedder call (trl_debug_facenet_plan)
+    // trl_debug_facenet_capture: armed conv index (-1: off) and its three copied views (input / residual / output)
+    int fn_cap_arm = -1;
+    struct { void* p = nullptr; size_t cap = 0; int32_t dims[5] = {0, 0, 0, 0, 0}; } fn_cap[3];
 };
+
+// The kernel a conv launcher picked (set by trl_launch_conv / trl_launch_fn_group / trl_launch_conv_bf16 as they choose, read by
+// the FaceNet walker for trl_debug_facenet_plan): host bookkeeping only.
+struct TrlConvChoice { int family = 0, bm = 0, bn = 0, bk = 0, pad = 0, nz = 1; };
+extern thread_local TrlConvChoice g_trl_conv_choice;
 
 // Optional device-wide ordering of the wide phases of different contexts (trl_api.hip; OFF by default, trl_debug_option
 // "pnet_gate"): a fused PNet launch waits for the END of the most recent call queued on the device, whichever context queued it,

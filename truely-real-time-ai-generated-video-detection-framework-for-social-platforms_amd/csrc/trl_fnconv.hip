@@ -13,7 +13,7 @@
 // ascending -- v_mfma_f32_16x16x4_f32 is that chain, 4 k per instruction; layers with OH*OW <= 9 and K >= 512 use
 // FOUR chains over consecutive quarters of k combined as (c0 + c1) + (c2 + c3) (SPLIT4: one wave per quarter).
 // A tap that lies in the padding for every output row contributes fmaf(0, w, acc) == acc and is skipped.
-#include "trl_common.h"
+#include "trl_ctx.h"
 #include <stdlib.h>
 #include <stdio.h>
 #include <type_traits>
@@ -556,6 +556,7 @@ int trl_launch_fn_group(const ConvArgs* convs, int nz, hipStream_t s) {
     int fbm = 0, fbn = 0;
     if (force && sscanf(force, "%dx%d", &fbm, &fbn) == 2) t = Tile{fbm, fbn};
     else t = pick_tile(M, nz == 1 ? convs[0].Cout : N, sp, nz);
+    g_trl_conv_choice = TrlConvChoice{sp ? TRL_FNK_FN_SPLIT4 : TRL_FNK_FN_CONV, t.bm, t.bn, FBK, 0, nz};
     static const int skip = trl_tune_int("TRL_FN_SKIP", 0);
     g.skip = skip;
     g.dbg = nullptr;

@@ -13,7 +13,7 @@
 //   staging     A (pixels x k) gathered from NHWC into LDS as [k][m]; B (k x cout) as [k][n];
 //               ds_read_b32 operand reads are conflict-free (32 consecutive floats per half-wave).
 //               Next chunk's global loads are issued before the MFMAs of the current chunk.
-#include "trl_common.h"
+#include "trl_ctx.h"
 #include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -720,6 +720,7 @@ __global__ __launch_bounds__(256) void conv_tap48(ConvArgs a) {
 
 template <int BM, int BN, int WM, int WN, int BK>
 int launch_tap(const ConvArgs& a, dim3 grid, hipStream_t s) {
+    g_trl_conv_choice = TrlConvChoice{TRL_FNK_CONV_TAP, BM, BN, BK, a.ph || a.pw, 1};
     if (a.ph || a.pw) conv_tap<BM, BN, WM, WN, BK, true><<<grid, 256, 0, s>>>(a);
     else conv_tap<BM, BN, WM, WN, BK, false><<<grid, 256, 0, s>>>(a);
     TRL_LAUNCH_CHECK();
@@ -739,6 +740,7 @@ int launch_cfg(const ConvArgs& a, bool vec, hipStream_t s) {
         if (BM == 128 && BN == 64 && a.Cin % 28 == 0) return launch_tap<BM, BN, WM, WN, 28>(a, grid, s);
         if (a.Cin % 16 == 0) return launch_tap<BM, BN, WM, WN, 16>(a, grid, s);
     }
+    g_trl_conv_choice = vec ? TrlConvChoice{TRL_FNK_IGEMM_VEC, BM, BN, BK, 0, 1} : TrlConvChoice{TRL_FNK_IGEMM_SCALAR, BM, BN, 16, 0, 1};
     if (vec) conv_igemm<BM, BN, WM, WN, BK, true><<<grid, 256, 0, s>>>(a);
     else conv_igemm<BM, BN, WM, WN, 16, false><<<grid, 256, 0, s>>>(a);
     TRL_LAUNCH_CHECK();
@@ -922,10 +924,13 @@ int trl_launch_conv(const ConvArgs& a, hipStream_t s) {
         const bool small = (long long)a.N * a.H * a.W * a.ldx + a.xoff < 0x7fffffffll && (long long)a.K * a.ldw < 0x7fffffffll;
         const bool pad = a.ph || a.pw;
         if (!tap_off && small && a.K == a.KH * a.KW * a.Cin && a.Cin % 32 == 0 && segK % 32 == 0) {
+            g_trl_conv_choice = TrlConvChoice{TRL_FNK_SPLITK4_TAP, 32, 64, 32, pad, 1};
             if (pad) conv_splitk4_tap<32, true><<<grid, 256, 0, s>>>(a); else conv_splitk4_tap<32, false><<<grid, 256, 0, s>>>(a);
         } else if (!tap_off && small && a.K == a.KH * a.KW * a.Cin && a.Cin % 16 == 0 && segK % 16 == 0) {
+            g_trl_conv_choice = TrlConvChoice{TRL_FNK_SPLITK4_TAP, 32, 64, 16, pad, 1};
             if (pad) conv_splitk4_tap<16, true><<<grid, 256, 0, s>>>(a); else conv_splitk4_tap<16, false><<<grid, 256, 0, s>>>(a);
         } else {
+            g_trl_conv_choice = TrlConvChoice{TRL_FNK_SPLITK4, 32, 64, 32, 0, 1};
             conv_splitk4<<<grid, 256, 0, s>>>(a);
         }
         TRL_LAUNCH_CHECK();
@@ -940,6 +945,7 @@ int trl_launch_conv(const ConvArgs& a, hipStream_t s) {
         if (vec && !tap_off && small && a.Cout == 48 && a.ldw >= 48 && a.M >= 16384 && a.K == a.KH * a.KW * a.Cin && (a.Cin % 28 == 0 || a.Cin % 32 == 0)) {
             dim3 grid((a.M + 127) / 128, 1);
             const bool pad = a.ph || a.pw;
+            g_trl_conv_choice = TrlConvChoice{TRL_FNK_TAP48, 128, 48, a.Cin % 32 == 0 ? 32 : 28, pad, 1};
             if (a.Cin % 32 == 0) { if (pad) conv_tap48<32, true><<<grid, 256, 0, s>>>(a); else conv_tap48<32, false><<<grid, 256, 0, s>>>(a); }
             else { if (pad) conv_tap48<28, true><<<grid, 256, 0, s>>>(a); else conv_tap48<28, false><<<grid, 256, 0, s>>>(a); }
             TRL_LAUNCH_CHECK();

@@ -6,6 +6,9 @@
 // buffer (Act.coff / Act.ld), so torch.cat costs nothing.
 #include "trl_ctx.h"
 #include <stdlib.h>
+#include <string.h>
+
+thread_local TrlConvChoice g_trl_conv_choice;
 
 namespace {
 
@@ -15,6 +18,49 @@ struct Runner {
     int err = TRL_OK;
     const int32_t* m_dev = nullptr;   // device-sized batch (candidate lists): item count lives on the device, see ConvArgs
     int m_base = 0;
+    // FaceNet only: the plan rows of trl_debug_facenet_plan and the armed capture of trl_debug_facenet_capture (conv index = walk order)
+    std::vector<trl_fn_plan_row>* plan = nullptr;
+    int nconv = 0;
+    std::string layer;                // name of the conv being issued (set by bconv / resid)
+    struct ConvMeta { int idx; std::string layer; Act x, y; bool has_res; Act res; };
+    std::vector<ConvMeta> pending_meta;
+
+    // Host bookkeeping behind a launch: the plan row (g_trl_conv_choice is what the launcher just picked) and, when this conv is
+    // the armed one, stream-ordered copies of its views -- before any later kernel can reuse a slice.
+    void launched(const ConvArgs& a, const ConvMeta& m) {
+        if (!plan) return;
+        trl_fn_plan_row r;
+        memset(&r, 0, sizeof(r));
+        const TrlConvChoice& ch = g_trl_conv_choice;
+        r.conv = m.idx; r.family = ch.family; r.bm = ch.bm; r.bn = ch.bn; r.bk = ch.bk; r.pad = ch.pad; r.nz = ch.nz;
+        r.m = a.M; r.cout = a.Cout; r.k = a.K; r.precision = a.lowp; r.has_res = m.has_res;
+        strncpy(r.layer, m.layer.c_str(), sizeof(r.layer) - 1);
+        plan->push_back(r);
+        if (c->fn_cap_arm != m.idx) return;
+        int st = capture(0, m.x, 1 << 30, 0);
+        if (st == TRL_OK && m.has_res) st = capture(1, m.res, 1 << 30, 0);
+        if (st == TRL_OK) st = capture(2, m.y, a.ysplit, a.yskip);
+        if (st != TRL_OK && err == TRL_OK) err = st;
+    }
+    int capture(int v, const Act& a, int ysplit, int yskip) {
+        auto& b = c->fn_cap[v];
+        const size_t es = a.bf ? sizeof(uint16_t) : sizeof(float), row = (size_t)a.c * es, need = row * a.pixels();
+        if (b.cap < need) {
+            if (b.p) TRL_HIP(hipFree(b.p));
+            b.p = nullptr; b.cap = 0;
+            TRL_HIP(hipMalloc(&b.p, need));
+            b.cap = need;
+        }
+        const char* src = reinterpret_cast<const char*>(a.p) + (size_t)a.coff * es;
+        const int c0 = ysplit < a.c ? ysplit : a.c;    // a scattered destination (block35_grouped): columns >= ysplit sit yskip further
+        TRL_HIP(hipMemcpy2DAsync(b.p, row, src, (size_t)a.ld * es, (size_t)c0 * es, a.pixels(), hipMemcpyDeviceToDevice, s));
+        if (c0 < a.c)
+            TRL_HIP(hipMemcpy2DAsync(static_cast<char*>(b.p) + (size_t)c0 * es, row, src + (size_t)(c0 + yskip) * es, (size_t)a.ld * es,
+                                     (size_t)(a.c - c0) * es, a.pixels(), hipMemcpyDeviceToDevice, s));
+        const int32_t d[5] = {a.n, a.h, a.w, a.c, (int32_t)es};
+        memcpy(b.dims, d, sizeof(d));
+        return TRL_OK;
+    }
 
     Act alloc(int n, int h, int w, int ch, bool bf = false) {
         Act a;
@@ -38,18 +84,26 @@ struct Runner {
     std::vector<ConvArgs> pending;
     bool grouping = false;
     int ysplit = 1 << 30, yskip = 0;   // destination scatter of the next conv: output column n >= ysplit lands yskip channels further
-    void begin_group() { grouping = true; pending.clear(); }
+    void begin_group() { grouping = true; pending.clear(); pending_meta.clear(); }
     void end_group() {
         grouping = false;
-        if (pending.empty() || err != TRL_OK) { pending.clear(); return; }
+        if (pending.empty() || err != TRL_OK) { pending.clear(); pending_meta.clear(); return; }
         bool all = pending.size() <= 3;
         for (auto& a : pending) all = all && trl_fn_eligible(a);
         if (all) for (auto& a : pending) all = all && (trl_fn_split4_rule(a) == trl_fn_split4_rule(pending[0]));
         int st = TRL_OK;
-        if (all) st = trl_launch_fn_group(pending.data(), (int)pending.size(), s);
-        else for (auto& a : pending) { st = trl_launch_conv(a, s); if (st != TRL_OK) break; }
+        if (all) {
+            st = trl_launch_fn_group(pending.data(), (int)pending.size(), s);
+            if (st == TRL_OK) for (size_t i = 0; i < pending.size(); i++) launched(pending[i], pending_meta[i]);
+        } else {
+            for (size_t i = 0; i < pending.size(); i++) {
+                st = trl_launch_conv(pending[i], s);
+                if (st != TRL_OK) break;
+                launched(pending[i], pending_meta[i]);
+            }
+        }
         if (st != TRL_OK) err = st;
-        pending.clear();
+        pending.clear(); pending_meta.clear();
     }
 
     // generic conv launcher; `into` selects a pre-allocated (concat) destination view
@@ -77,6 +131,7 @@ struct Runner {
         a.m_dev = m_dev; a.m_base = m_base; a.m_per = OH * OW;
         a.ysplit = ysplit; a.yskip = yskip;
         if (yskip && !trl_fn_eligible(a)) { trl_set_error("scattered destination needs the small-map conv family"); err = TRL_ERR_STATE; return y; }
+        ConvMeta meta{nconv++, layer, x, y, res != nullptr, res ? *res : Act()};
         if (x.bf) {   // reduced-precision embedder: bf16 in / out / residual, transposed bf16 weights
             if (!w->pt || y.bf != true || (res && !res->bf) || act == TRL_ACT_PRELU) {
                 trl_set_error("bf16 conv without bf16 weights / destination");
@@ -87,15 +142,18 @@ struct Runner {
             if (res) a.res = reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(res->p) + res->coff);
             int st = trl_launch_conv_bf16(a, s);
             if (st != TRL_OK) err = st;
+            else launched(a, meta);
             return y;
         }
-        if (grouping) { pending.push_back(a); return y; }
+        if (grouping) { pending.push_back(a); pending_meta.push_back(meta); return y; }
         int st = trl_launch_conv(a, s);
         if (st != TRL_OK) err = st;
+        else launched(a, meta);
         return y;
     }
     // BasicConv2d: conv(no bias) + folded BN + ReLU
     Act bconv(const Act& x, const std::string& name, int kh, int kw, int sh, int sw, int ph, int pw, const Act* into = nullptr) {
+        if (plan) layer = name;
         return conv(x, trl_w(c, name + ".w"), nullptr, trl_v(c, name + ".scale"), trl_v(c, name + ".shift"), nullptr,
                     kh, kw, sh, sw, ph, pw, TRL_ACT_RELU, into, nullptr, 0.f);
     }
@@ -106,6 +164,7 @@ struct Runner {
                     nullptr, nullptr, 0.f);
     }
     Act resid(const Act& cat, const Act& x, const std::string& name, float scale, bool relu) {
+        if (plan) layer = name;
         return conv(cat, trl_w(c, name + ".w"), trl_v(c, name + ".b"), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0,
                     relu ? TRL_ACT_RELU : TRL_ACT_NONE, nullptr, &x, scale);
     }
@@ -177,6 +236,10 @@ Act block8(Runner& R, const Act& x, const std::string& p, float scale, bool relu
 int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s) {
     if (n <= 0) return TRL_OK;
     Runner R{c, s};
+    c->fn_plan.clear();
+    R.plan = &c->fn_plan;
+    if (c->fn_cap_arm >= 0) for (auto& b : c->fn_cap) b.dims[3] = 0;
+    struct Disarm { trl_ctx* c; ~Disarm() { c->fn_cap_arm = -1; } } disarm{c};   // a capture covers one call, whatever its outcome
     Act x0; x0.p = const_cast<float*>(d_faces); x0.n = n; x0.h = h; x0.w = w; x0.c = 3; x0.ld = 3; x0.coff = 0;
     const std::string f = "facenet.";
     Act x = R.bconv(x0, f + "conv2d_1a", 3, 3, 2, 2, 0, 0);
@@ -239,6 +302,7 @@ int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const
         if (x.bf) TRL_CHECK(trl_launch_gap_bf16(reinterpret_cast<const uint16_t*>(x.p), n, x.h * x.w, x.c, g.p, s, c->cfg.embed_precision));
         else TRL_CHECK(trl_launch_gap(x.p, n, x.h * x.w, x.c, g.p, s));
     }
+    R.layer = f + "last_linear";
     Act e = R.conv(g, trl_w(c, f + "last_linear.w"), nullptr, trl_v(c, f + "last_bn.scale"), trl_v(c, f + "last_bn.shift"),
                    nullptr, 1, 1, 1, 1, 0, 0, TRL_ACT_NONE, nullptr, nullptr, 0.f);
     if (R.err != TRL_OK) return R.err;

@@ -296,6 +296,49 @@ class Engine:
         keys = ("row_bands", "col_bands", "cols_per_band", "frames_per_launch", "khmax")
         return [dict(kernel=self.PYR_KERNELS[int(r[0])], **dict(zip(keys, (int(v) for v in r[1:])))) for r in rows[:L.value]]
 
+    FN_FAMILIES = {1: "fn_conv", 2: "fn_conv_split4", 3: "conv_tap", 4: "conv_igemm_vec", 5: "conv_igemm_scalar",
+                   6: "conv_splitk4", 7: "conv_splitk4_tap", 8: "conv_tap48", 9: "conv_bf16"}   # TRL_FNK_*
+    FN_PLAN_DTYPE = np.dtype([(k, np.int32) for k in ("conv", "family", "bm", "bn", "bk", "pad", "nz", "m", "cout", "k", "precision",
+                                                      "has_res")] + [("layer", "S48")])
+
+    def facenet_plan(self):
+        """Test hook: one dict per conv launch of this context's last embedder call, in walk order: conv (index), layer, family
+        ("fn_conv", "fn_conv_split4", "conv_tap", "conv_igemm_vec", "conv_igemm_scalar", "conv_splitk4", "conv_splitk4_tap",
+        "conv_tap48", "conv_bf16"), bm, bn, bk, pad, nz (convs sharing the launch), m, cout, k, precision (0 f32 / 1 bf16 / 2 fp16),
+        has_res."""
+        n = C.c_int()
+        _lib.check(self.lib.trl_debug_facenet_plan(self._h, None, 0, C.byref(n)))
+        rows = np.zeros(n.value, self.FN_PLAN_DTYPE)
+        _lib.check(self.lib.trl_debug_facenet_plan(self._h, rows.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        out = []
+        for r in rows:
+            d = {k: int(r[k]) for k in self.FN_PLAN_DTYPE.names if k != "layer"}
+            d["family"] = self.FN_FAMILIES[d["family"]]
+            d["layer"] = r["layer"].decode()
+            out.append(d)
+        return out
+
+    def facenet_capture(self, conv_index: int):
+        """Test hook: the next embedder call on this context copies conv ``conv_index``'s input, residual and output views
+        (walk order of facenet_plan; -1 disarms); read them with facenet_captured()."""
+        _lib.check(self.lib.trl_debug_facenet_capture(self._h, int(conv_index)))
+
+    def facenet_captured(self):
+        """(input, residual or None, output) of the last armed capture: dense NHWC numpy arrays, float32, or uint16 holding the
+        bf16 / fp16 bits in reduced-precision mode."""
+        out = []
+        for v in range(3):
+            dims = np.zeros(5, np.int32)
+            _lib.check(self.lib.trl_debug_facenet_capture_read(self._h, v, None, 0, dims.ctypes.data_as(C.c_void_p)))
+            if dims[3] == 0:
+                out.append(None)
+                continue
+            a = np.empty(tuple(int(d) for d in dims[:4]), np.float32 if dims[4] == 4 else np.uint16)
+            _lib.check(self.lib.trl_debug_facenet_capture_read(self._h, v, a.ctypes.data_as(C.c_void_p), a.nbytes,
+                                                               dims.ctypes.data_as(C.c_void_p)))
+            out.append(a)
+        return tuple(out)
+
     def batch_capacity(self, t2_per_frame: float = 0.0, t3_per_frame: float = 0.0) -> int:
         """Test hook: set the optimistic R-/O-Net candidate capacities (per frame) and return the attempts the last call took."""
         k = C.c_int()

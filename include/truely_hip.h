@@ -253,6 +253,15 @@ int  trl_debug_onet(trl_ctx* ctx, const float* d_crops, int n, float* d_out, voi
  * h_boxes = nb host rows x1,y1,x2,y2 (as after rerec); net = 24 (R-Net, d_out [nb][6]) or 48 (O-Net, d_out [nb][16]). */
 int  trl_debug_front_net(trl_ctx* ctx, const uint8_t* d_frame, int H, int W, const float* h_boxes, int nb, int net,
                          float* d_out, void* stream);
+/* The production stage-2 / stage-3 loop (chunked front kernel + layer tail, as the cascade runs it) at a caller-chosen launch
+ * capacity: h_recs = nb host rows (frame, x1, y1, x2, y2) over nf frames, cropped by pad() as the cascade's records are; the device
+ * total is nb, and capacity (>= 0, below or above nb) sizes every launch.  Chunks follow trl_debug_option "rnet_chunk" /
+ * "onet_chunk".  d_out: [capacity][6] (net = 24) or [capacity][16] (net = 48), device; rows past nb are not defined. (ABI v7) */
+int  trl_debug_stage_net(trl_ctx* ctx, const uint8_t* d_frames, int nf, int H, int W, const float* h_recs, int nb, int net,
+                         int capacity, float* d_out, void* stream);
+/* The tail conv launches of the last trl_debug_stage_net call, chunk after chunk, in the rows of
+ * trl_debug_facenet_plan: layer = "rnet.conv2", ..., "onet.heads", conv = row index.  Other calls do not record. (ABI v7) */
+int  trl_debug_mtcnn_plan(trl_ctx* ctx, trl_fn_plan_row* h_rows, int max_rows, int* n_rows);
 /* model.py:55-58 alone: crop rect (x0,y0,x1,y1 per frame, i32) -> f32 [n][80][80][3] in [0,1] */
 int  trl_debug_crop_resize(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W,
                            const int32_t* d_rect, const uint8_t* d_valid, float* d_faces, void* stream);

@@ -43,9 +43,10 @@ PREC = {0: "f32", 1: "bf16", 2: "fp16"}
 # small-map family on or off, f32 / bf16 / fp16).  Not listed, because only the tuning build reaches them: the fn_conv tiles
 # 32x64, 64x32, 64x96, 128x32, 128x64, 32x128, 16x64 and the fn_conv_split4 tiles 16x64, 32x64 (TRL_FN_FORCE1 / TRL_FN_FORCE4);
 # conv_tap with BK 16 where 32 channels divide Cin (TRL_CONV_BK16); conv_igemm_vec (TRL_NO_TAP); the 64-row tiles of M >= 16384
-# layers (TRL_CONV_BIGM).  Instantiated but never selected for FaceNet: conv_tap48 (Cout 48: R-Net conv2), conv_tap BK 28 (Cin 28:
-# R-Net), conv_splitk4 (K / 4 not a multiple of 16: the R-/O-Net dense layers), conv_tap with padding and BK 16 (every padded conv
-# has Cin % 32 == 0), conv_bf16 with padding and BK 16 (likewise).
+# layers (TRL_CONV_BIGM).  Instantiated but never selected for FaceNet: conv_tap48 (Cout 48: R-Net conv2, see test_gpu_stage_nets.py),
+# conv_tap BK 28 and conv_splitk4 (no shipped network selects them: R-Net's conv2, the one Cin 28 layer, takes conv_tap48 where a
+# 128 x 64 tile would apply, and the R-/O-Net dense layers take conv_splitk4_tap), conv_tap with padding and BK 16 (every padded
+# conv has Cin % 32 == 0), conv_bf16 with padding and BK 16 (likewise).
 EXPECTED_PATHS = {
     ("conv_igemm_scalar", 128, 32, 16, 0),                                            # the 3-channel stem
     ("fn_conv", 32, 32, 32, 0), ("fn_conv", 64, 64, 32, 0),

@@ -789,6 +789,66 @@ int trl_debug_front_net(trl_ctx* c, const uint8_t* d_frame, int H, int W, const 
     return TRL_OK;
 }
 
+// test hook: the production stage-2 / stage-3 loop (trl_stage_net, as the cascade runs it) over a launch capacity the caller
+// chooses.  h_recs: nb host rows (frame, x1, y1, x2, y2), turned into k_build_map's records by the same pad() rule; the device
+// total is nb, and record slots past it (the kernels read them, then discard them) hold a poison pattern.  The workspace is sized
+// like the cascade's: chunk = the rnet_chunk / onet_chunk option.  d_out: [capacity][6] (net = 24) or [capacity][16] (net = 48),
+// device; only rows of live candidates are defined.  trl_debug_mtcnn_plan then lists the tail's conv launches of every chunk.
+int trl_debug_stage_net(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const float* h_recs, int nb, int net, int capacity,
+                        float* d_out, void* stream) {
+    TRL_CHECK(check_call(c, d_frames, nf, H, W));
+    if ((nb > 0 && !h_recs) || (capacity > 0 && !d_out) || nb < 0 || nb > (1 << 24) || capacity < 0 || capacity > (1 << 24) ||
+        (net != 24 && net != 48)) {
+        trl_set_error("bad argument");
+        return TRL_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    TRL_HIP(hipSetDevice(c->cfg.device));
+    const int slots = nb > capacity ? nb : capacity;
+    Arena& A = c->arena;
+    TRL_CHECK(trl_ensure(c, A, (size_t)slots * 32 + (1u << 20)));
+    A.reset();
+    CascadeBufs& B = c->cb;
+    B = CascadeBufs();
+    B.n = nf; B.H = H; B.W = W;
+    B.cbox = (int32_t*)A.alloc((size_t)slots * 32 + 32);
+    int32_t* total = (int32_t*)A.alloc(64);
+    std::vector<int32_t> hb((size_t)slots * 8, (int32_t)0xA5A5A5A5);   // poison: frame / window words no live record has
+    for (int i = 0; i < nb; i++) {
+        const float* b = h_recs + 5 * i;
+        const int f = (int)b[0];
+        if (f < 0 || f >= nf) { trl_set_error("record %d: frame %d of %d", i, f, nf); return TRL_ERR_INVALID; }
+        const int bx = (int)truncf(b[1]), by = (int)truncf(b[2]), bex = (int)truncf(b[3]), bey = (int)truncf(b[4]);
+        const int x = bx < 1 ? 1 : bx, y = by < 1 ? 1 : by, ex = bex > W ? W : bex, ey = bey > H ? H : bey;
+        if (ey <= y - 1 || ex <= x - 1) { trl_set_error("record %d: empty crop window", i); return TRL_ERR_INVALID; }
+        int32_t* r = &hb[8 * (size_t)i];
+        r[0] = f; r[1] = y - 1; r[2] = x - 1; r[3] = ey - (y - 1); r[4] = ex - (x - 1); r[5] = r[6] = r[7] = 0;
+    }
+    TRL_HIP(hipMemcpyAsync(B.cbox, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s));
+    TRL_HIP(hipMemcpyAsync(total, &nb, 4, hipMemcpyHostToDevice, s));
+    TRL_HIP(hipStreamSynchronize(s));                      // the host vector goes out of scope
+    // workspace as the cascade sizes it (trl_cascade_detect): per candidate of a chunk 40 KB (R-Net) / 240 KB (O-Net)
+    const int CH = net == 24 ? c->rnet_chunk : c->onet_chunk, ch = capacity < CH ? capacity : CH;
+    c->scratch.reset();
+    TRL_CHECK(trl_ensure(c, c->scratch, (size_t)ch * (net == 24 ? 40 : 240) * 1024 + (1u << 20)));
+    c->mt_plan.clear();
+    c->mt_plan_arm = true;
+    const int st = trl_stage_net(c, net, d_frames, H, W, total, capacity, d_out, s);
+    c->mt_plan_arm = false;
+    TRL_CHECK(st);
+    TRL_HIP(hipStreamSynchronize(s));
+    B = CascadeBufs();                                     // no cascade state to inspect after this hook
+    return TRL_OK;
+}
+
+int trl_debug_mtcnn_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, int* n_rows) {
+    TRL_CHECK(check_idle(c));
+    if (!n_rows || (max_rows > 0 && !h_rows)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
+    *n_rows = (int)c->mt_plan.size();
+    for (int i = 0; i < *n_rows && i < max_rows; i++) h_rows[i] = c->mt_plan[i];
+    return TRL_OK;
+}
+
 int trl_debug_onet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) {
     if (!c || !c->have_weights || !d_crops || !d_out || n <= 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
     TRL_CHECK(check_idle(c));

@@ -1317,18 +1317,8 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     TRL_LAUNCH_CHECK();
     X.reset();   // stream order keeps the PNet workspace alive until its kernels are done: reuse needs no host sync
     float* out6 = (float*)X.alloc((size_t)cap2 * 24);
-    {
-        const int CH = c->rnet_chunk;
-        const size_t mk = X.off;
-        for (int t0 = 0; t0 < cap2; t0 += CH) {
-            const int nc = (cap2 - t0 < CH) ? cap2 - t0 : CH;
-            X.off = mk;
-            float* pool1 = (float*)X.alloc((size_t)nc * 11 * 11 * 28 * 4);
-            if (!pool1 || !out6) { trl_set_error("rnet workspace"); return TRL_ERR_STATE; }
-            TRL_CHECK(trl_launch_rnet_front(c, d_frames, H, W, B.off2 + n, t0, nc, pool1, s));   // crop + conv1 + pool1 in LDS
-            TRL_CHECK(trl_run_rnet_tail(c, pool1, nc, out6 + (size_t)t0 * 6, s, B.off2 + n, t0));
-        }
-    }
+    if (!out6) { trl_set_error("rnet workspace"); return TRL_ERR_STATE; }
+    TRL_CHECK(trl_stage_net(c, 24, d_frames, H, W, B.off2 + n, cap2, out6, s));
     k_stage2_post<<<n, th_f, sm_f, s>>>(full_f, capF, cap2, W, H, c->cfg.thr1, B.n1, B.s1_box, B.off2, out6, B.n2, B.s2_box, sp);
     TRL_LAUNCH_CHECK();
     }
@@ -1340,20 +1330,34 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     TRL_LAUNCH_CHECK();
     X.reset();
     float* out16 = (float*)X.alloc((size_t)cap3 * 64);
-    {
-        const int CH = c->onet_chunk;
-        const size_t mk = X.off;
-        for (int t0 = 0; t0 < cap3; t0 += CH) {
-            const int nc = (cap3 - t0 < CH) ? cap3 - t0 : CH;
-            X.off = mk;
-            float* pool1 = (float*)X.alloc((size_t)nc * 23 * 23 * 32 * 4);
-            if (!pool1 || !out16) { trl_set_error("onet workspace"); return TRL_ERR_STATE; }
-            TRL_CHECK(trl_launch_onet_front(c, d_frames, H, W, B.off3 + n, t0, nc, pool1, s));   // crop + conv1 + pool1 in LDS
-            TRL_CHECK(trl_run_onet_tail(c, pool1, nc, out16 + (size_t)t0 * 16, s, B.off3 + n, t0));
-        }
-    }
+    if (!out16) { trl_set_error("onet workspace"); return TRL_ERR_STATE; }
+    TRL_CHECK(trl_stage_net(c, 48, d_frames, H, W, B.off3 + n, cap3, out16, s));
     k_stage3_post<<<n, th_f, sm_f, s>>>(full_f, capF, cap3, c->cfg.thr2, B.n2, B.s2_box, B.off3, out16, B.n3, B.s3_box, B.s3_pts, sp);
     TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
+// One R-Net (net = 24) or O-Net (net = 48) stage over `cap` candidate slots: chunks of c->rnet_chunk / c->onet_chunk candidates,
+// each the fused front kernel (crop of record t0 + i of c->cb.cbox, conv1, pool1 in LDS) then the layer tail.  Launches are sized
+// by the capacity; the candidates that exist are the first *d_total, and every kernel skips the rest on the device.  The pooled
+// maps come from c->scratch behind its current offset (the caller's blocks below it stay intact).  d_out: [cap][6] / [cap][16].
+int trl_stage_net(trl_ctx* c, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float* d_out, hipStream_t s) {
+    Arena& X = c->scratch;
+    const int CH = net == 24 ? c->rnet_chunk : c->onet_chunk, P = net == 24 ? 11 : 23, C1 = net == 24 ? 28 : 32, NO = net == 24 ? 6 : 16;
+    const size_t mk = X.off;
+    for (int t0 = 0; t0 < cap; t0 += CH) {
+        const int nc = (cap - t0 < CH) ? cap - t0 : CH;
+        X.off = mk;
+        float* pool1 = (float*)X.alloc((size_t)nc * P * P * C1 * 4);
+        if (!pool1) { trl_set_error(net == 24 ? "rnet workspace" : "onet workspace"); return TRL_ERR_STATE; }
+        if (net == 24) {
+            TRL_CHECK(trl_launch_rnet_front(c, d_frames, H, W, d_total, t0, nc, pool1, s));   // crop + conv1 + pool1 in LDS
+            TRL_CHECK(trl_run_rnet_tail(c, pool1, nc, d_out + (size_t)t0 * NO, s, d_total, t0));
+        } else {
+            TRL_CHECK(trl_launch_onet_front(c, d_frames, H, W, d_total, t0, nc, pool1, s));
+            TRL_CHECK(trl_run_onet_tail(c, pool1, nc, d_out + (size_t)t0 * NO, s, d_total, t0));
+        }
+    }
     return TRL_OK;
 }
 

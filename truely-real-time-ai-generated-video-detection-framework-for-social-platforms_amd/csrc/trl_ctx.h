@@ -101,6 +101,10 @@ struct trl_ctx {
     // what the last build_pyramid chose per level (trl_debug_pyramid_plan): rows of TRL_PYR_PLAN_COLS ints; L = 0 after a refused call
     struct { int L = 0; int32_t row[16][TRL_PYR_PLAN_COLS] = {}; } pyr_plan;
     std::vector<trl_fn_plan_row> fn_plan;   // the conv launches of the last embedder call (trl_debug_facenet_plan)
+    // the R-/O-Net tail conv launches of the last trl_debug_stage_net call, every chunk (trl_debug_mtcnn_plan); recorded only
+    // while that hook runs (mt_plan_arm)
+    std::vector<trl_fn_plan_row> mt_plan;
+    bool mt_plan_arm = false;
     // trl_debug_facenet_capture: armed conv index (-1: off) and its three copied views (input / residual / output)
     int fn_cap_arm = -1;
     struct { void* p = nullptr; size_t cap = 0; int32_t dims[5] = {0, 0, 0, 0, 0}; } fn_cap[3];
@@ -132,6 +136,8 @@ int trl_run_rnet_tail(trl_ctx* c, const float* d_pool1, int n, float* d_out6, hi
 int trl_run_onet_tail(trl_ctx* c, const float* d_pool1, int n, float* d_out16, hipStream_t s, const int32_t* n_dev = nullptr, int n_base = 0);
 int trl_launch_rnet_front(trl_ctx* c, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc, float* d_pool, hipStream_t s);
 int trl_launch_onet_front(trl_ctx* c, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc, float* d_pool, hipStream_t s);
+// stage 2 / 3 network over `cap` candidate slots of c->cb.cbox, *d_total of them live (trl_cascade.hip): chunked front + tail
+int trl_stage_net(trl_ctx* c, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float* d_out, hipStream_t s);
 // PNet on one materialised level for nf frames: heads [nf][oh][ow][6]
 int trl_run_pnet_generic(trl_ctx* c, const float* d_level, int nf, int h, int w, float* d_heads, hipStream_t s);
 size_t trl_pnet_generic_bytes(int nf, int h, int w);

@@ -36,7 +36,7 @@ struct Runner {
         r.m = a.M; r.cout = a.Cout; r.k = a.K; r.precision = a.lowp; r.has_res = m.has_res;
         strncpy(r.layer, m.layer.c_str(), sizeof(r.layer) - 1);
         plan->push_back(r);
-        if (c->fn_cap_arm != m.idx) return;
+        if (plan != &c->fn_plan || c->fn_cap_arm != m.idx) return;   // captures are FaceNet convs only
         int st = capture(0, m.x, 1 << 30, 0);
         if (st == TRL_OK && m.has_res) st = capture(1, m.res, 1 << 30, 0);
         if (st == TRL_OK) st = capture(2, m.y, a.ysplit, a.yskip);
@@ -159,6 +159,7 @@ struct Runner {
     }
     // MTCNN conv (bias) + optional PReLU, valid padding
     Act mconv(const Act& x, const std::string& net, const std::string& name, const char* prelu, int k) {
+        if (plan) layer = net + "." + name;
         return conv(x, trl_w(c, net + "." + name + ".w"), trl_v(c, net + "." + name + ".b"), nullptr, nullptr,
                     prelu ? trl_v(c, net + "." + prelu) : nullptr, k, k, 1, 1, 0, 0, prelu ? TRL_ACT_PRELU : TRL_ACT_NONE,
                     nullptr, nullptr, 0.f);
@@ -350,12 +351,14 @@ int trl_run_rnet_tail(trl_ctx* c, const float* d_pool1, int n, float* d_out6, hi
     if (n <= 0) return TRL_OK;
     Runner R{c, s};
     R.m_dev = n_dev; R.m_base = n_base;
+    if (c->mt_plan_arm) { R.plan = &c->mt_plan; R.nconv = (int)c->mt_plan.size(); }   // trl_debug_stage_net: rows of every chunk
     Act x; x.p = const_cast<float*>(d_pool1); x.n = n; x.h = 11; x.w = 11; x.c = 28; x.ld = 28; x.coff = 0;
     x = R.mconv(x, "rnet", "conv2", "prelu2", 3);
     x = R.pool(x, 3, 2, 1);
     x = R.mconv(x, "rnet", "conv3", "prelu3", 2);
     x = R.mconv(x, "rnet", "dense4", "prelu4", 3);
     Act out; out.p = d_out6; out.n = n; out.h = 1; out.w = 1; out.c = 6; out.ld = 6; out.coff = 0;
+    if (R.plan) R.layer = "rnet.heads";
     R.conv(x, trl_w(c, "rnet.heads.w"), trl_v(c, "rnet.heads.b"), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0,
            TRL_ACT_NONE, &out, nullptr, 0.f);
     return R.err;
@@ -365,6 +368,7 @@ int trl_run_onet_tail(trl_ctx* c, const float* d_pool1, int n, float* d_out16, h
     if (n <= 0) return TRL_OK;
     Runner R{c, s};
     R.m_dev = n_dev; R.m_base = n_base;
+    if (c->mt_plan_arm) { R.plan = &c->mt_plan; R.nconv = (int)c->mt_plan.size(); }   // trl_debug_stage_net: rows of every chunk
     Act x; x.p = const_cast<float*>(d_pool1); x.n = n; x.h = 23; x.w = 23; x.c = 32; x.ld = 32; x.coff = 0;
     x = R.mconv(x, "onet", "conv2", "prelu2", 3);
     x = R.pool(x, 3, 2, 1);
@@ -373,6 +377,7 @@ int trl_run_onet_tail(trl_ctx* c, const float* d_pool1, int n, float* d_out16, h
     x = R.mconv(x, "onet", "conv4", "prelu4", 2);
     x = R.mconv(x, "onet", "dense5", "prelu5", 3);
     Act out; out.p = d_out16; out.n = n; out.h = 1; out.w = 1; out.c = 16; out.ld = 16; out.coff = 0;
+    if (R.plan) R.layer = "onet.heads";
     R.conv(x, trl_w(c, "onet.heads.w"), trl_v(c, "onet.heads.b"), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0,
            TRL_ACT_NONE, &out, nullptr, 0.f);
     return R.err;

@@ -306,10 +306,18 @@ class Engine:
         ("fn_conv", "fn_conv_split4", "conv_tap", "conv_igemm_vec", "conv_igemm_scalar", "conv_splitk4", "conv_splitk4_tap",
         "conv_tap48", "conv_bf16"), bm, bn, bk, pad, nz (convs sharing the launch), m, cout, k, precision (0 f32 / 1 bf16 / 2 fp16),
         has_res."""
+        return self._plan_rows(self.lib.trl_debug_facenet_plan)
+
+    def mtcnn_plan(self):
+        """Test hook: one dict per R-/O-Net tail conv launch of this context's last stage_net() call, chunk after chunk, with the
+        keys of facenet_plan (layer = "rnet.conv2", ..., "onet.heads"; conv = row index)."""
+        return self._plan_rows(self.lib.trl_debug_mtcnn_plan)
+
+    def _plan_rows(self, fn):
         n = C.c_int()
-        _lib.check(self.lib.trl_debug_facenet_plan(self._h, None, 0, C.byref(n)))
+        _lib.check(fn(self._h, None, 0, C.byref(n)))
         rows = np.zeros(n.value, self.FN_PLAN_DTYPE)
-        _lib.check(self.lib.trl_debug_facenet_plan(self._h, rows.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        _lib.check(fn(self._h, rows.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
         out = []
         for r in rows:
             d = {k: int(r[k]) for k in self.FN_PLAN_DTYPE.names if k != "layer"}
@@ -441,6 +449,20 @@ class Engine:
         b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)
         out = torch.empty((len(b), 6 if net == 24 else 16), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.trl_debug_front_net(self._h, _ptr(fr), H, W, b.ctypes.data_as(C.c_void_p), len(b), int(net), _ptr(out), self._stream()))
+        return out
+
+    def stage_net(self, frames, recs: np.ndarray, net: int, capacity: int, fill: float | None = None) -> torch.Tensor:
+        """Test hook: the production stage-2 / stage-3 loop (chunked front kernel + tail, trl_stage_net) over ``capacity``
+        candidate slots, ``len(recs)`` of them live: recs rows (frame, x1, y1, x2, y2).  Returns [capacity, 6] (net=24) or
+        [capacity, 16] (net=48); rows past len(recs) are not defined (``fill``, if given, is what the output held before)."""
+        fr = self._frames(frames)
+        nf, H, W, _ = fr.shape
+        r = np.ascontiguousarray(recs, np.float32).reshape(-1, 5)
+        shape = (int(capacity), 6 if net == 24 else 16)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device) if fill is None else \
+            torch.full(shape, fill, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.trl_debug_stage_net(self._h, _ptr(fr), nf, H, W, r.ctypes.data_as(C.c_void_p), len(r), int(net),
+                                                int(capacity), _ptr(out), self._stream()))
         return out
 
     def crop_resize(self, frames, rect: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:

@@ -259,6 +259,19 @@ int  trl_debug_front_net(trl_ctx* ctx, const uint8_t* d_frame, int H, int W, con
  * "onet_chunk".  d_out: [capacity][6] (net = 24) or [capacity][16] (net = 48), device; rows past nb are not defined. (ABI v7) */
 int  trl_debug_stage_net(trl_ctx* ctx, const uint8_t* d_frames, int nf, int H, int W, const float* h_recs, int nb, int net,
                          int capacity, float* d_out, void* stream);
+/* The cascade's list kernels on lists the caller builds, launched by the cascade's own host code (LDS tiers of
+ * trl_debug_nms_tiers, workgroup sizes, spill pool, overflow flags: trl_debug_list_stats).  h_caps: n_levels level capacities,
+ * then the per-frame capacity (multiples of 4).  kind 1: h_rows = 40-byte candidate records {x1, y1, x2, y2, score, r0..r3, cell}
+ * of every (frame, level) in append order, frame-major, h_counts [n][n_levels] -> per-level NMS, cross-level NMS, regression
+ * (read with trl_debug_level_keep, trl_debug_stage_boxes stage 1).  kind 2: h_rows = stage-1 rows {x1, y1, x2, y2, score} of every
+ * frame, h_counts [n], h_logits = R-Net outputs [total][6] -> stage-2 rows (trl_debug_stage_boxes stage 2).  kind 3: stage-2 rows
+ * and O-Net outputs [total][16] -> stage-3 rows (stage 3), their landmarks into h_pts [n][capacity][10] (nullable), and the
+ * detect() selection into d_boxes [n][max_faces][4], d_probs, d_points [n][max_faces][10], d_counts, d_box0 [n][4], d_prob0,
+ * d_rect [n][4], d_valid [n] (device).  Slots past the counts hold the trl_debug_poison byte.  A list the capacities cannot hold:
+ * TRL_ERR_CAPACITY. (ABI v7) */
+int  trl_debug_lists(trl_ctx* ctx, int kind, int n, int H, int W, const int32_t* h_caps, int n_levels, const int32_t* h_counts,
+                     const void* h_rows, const float* h_logits, float* h_pts, float* d_boxes, float* d_probs, float* d_points,
+                     int32_t* d_counts, float* d_box0, float* d_prob0, int32_t* d_rect, uint8_t* d_valid, void* stream);
 /* The tail conv launches of the last trl_debug_stage_net call, chunk after chunk, in the rows of
  * trl_debug_facenet_plan: layer = "rnet.conv2", ..., "onet.heads", conv = row index.  Other calls do not record. (ABI v7) */
 int  trl_debug_mtcnn_plan(trl_ctx* ctx, trl_fn_plan_row* h_rows, int max_rows, int* n_rows);

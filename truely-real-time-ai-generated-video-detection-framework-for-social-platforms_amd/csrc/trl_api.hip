@@ -841,6 +841,36 @@ int trl_debug_stage_net(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int 
     return TRL_OK;
 }
 
+// test hook: the cascade's list kernels on caller-built lists (trl_cascade_lists has the layout of every kind)
+int trl_debug_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* h_caps, int n_levels, const int32_t* h_counts,
+                    const void* h_rows, const float* h_logits, float* h_pts, float* d_boxes, float* d_probs, float* d_points,
+                    int32_t* d_counts, float* d_box0, float* d_prob0, int32_t* d_rect, uint8_t* d_valid, void* stream) {
+    TRL_CHECK(check_idle(c));
+    if (kind < 1 || kind > 3 || n <= 0 || n > 65535 || H < 12 || W < 12 || H > 16383 || W > 16383 || !h_caps || !h_counts ||
+        n_levels < (kind == 1 ? 1 : 0) || n_levels > 32 || (kind == 3 && !(d_boxes && d_probs && d_points && d_counts && d_box0 &&
+        d_prob0 && d_rect && d_valid))) {
+        trl_set_error("bad argument");
+        return TRL_ERR_INVALID;
+    }
+    long long slots = 0, total = 0;
+    for (int l = 0; l <= n_levels; l++) {
+        const int cap = h_caps[l];
+        if (cap < 4 || cap > (1 << 20) || (cap & 3)) { trl_set_error("capacity %d: multiples of 4 in [4, 2^20]", cap); return TRL_ERR_INVALID; }
+        if (l < n_levels) slots += cap;
+    }
+    if ((long long)n * (slots + h_caps[n_levels]) > (1ll << 26)) { trl_set_error("lists too large"); return TRL_ERR_INVALID; }
+    const int nc = kind == 1 ? n * n_levels : n;
+    for (int i = 0; i < nc; i++) {
+        const int cap = kind == 1 ? h_caps[i % n_levels] : h_caps[n_levels];
+        if (h_counts[i] < 0 || h_counts[i] > cap) { trl_set_error("list %d: count %d, capacity %d", i, h_counts[i], cap); return TRL_ERR_INVALID; }
+        total += h_counts[i];
+    }
+    if (total > 0 && (!h_rows || (kind > 1 && !h_logits))) { trl_set_error("null rows"); return TRL_ERR_INVALID; }
+    TRL_HIP(hipSetDevice(c->cfg.device));
+    return trl_cascade_lists(c, kind, n, H, W, h_caps, n_levels, h_counts, h_rows, h_logits, h_pts, d_boxes, d_probs, d_points, d_counts,
+                             d_box0, d_prob0, d_rect, d_valid, (hipStream_t)stream);
+}
+
 int trl_debug_mtcnn_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, int* n_rows) {
     TRL_CHECK(check_idle(c));
     if (!n_rows || (max_rows > 0 && !h_rows)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }

@@ -1132,6 +1132,80 @@ static size_t spill_need(long long cnt, int W, int H) {   // workspace of one sp
     return (size_t)(P * 12 + cnt * 28 + ((long long)(W >> 5) + 1) * ((H >> 5) + 1) * 4 + 256);
 }
 
+// spill workspace of a call: lists that can outgrow the LDS tier get theirs up front (bounded; a pool that still runs out is grown
+// by the re-run)
+static size_t spill_pool(const trl_ctx* c, int n, int H, int W) {
+    const LvLayout& G = c->cb.lay;
+    const int lds_full = c->nms_full;
+    size_t spill = c->spill_hint;
+    size_t per_frame = 0;
+    for (int l = 0; l < G.L; l++) if (G.capl[l] > lds_full) per_frame += spill_need(G.capl[l], W, H);
+    if (c->cb.capF > lds_full) per_frame += 3 * spill_need(c->cb.capF, W, H);
+    size_t up_front = per_frame * (size_t)n;
+    if (up_front > (8ull << 30)) up_front = 8ull << 30;
+    if (up_front > spill) spill = up_front;
+    return spill;
+}
+
+// How the list kernels (k_nms_level, k_nms_frame, k_stage2_post, k_stage3_post) are launched for the layout in c->cb: LDS tiers,
+// workgroup sizes, dynamic LDS.  One place for the cascade and the list test hook (trl_cascade_lists).
+struct ListLaunch {
+    int small_cap, full_l, full_f, max_capl, th_l, th_f;
+    size_t sm_s, sm_l, sm_f;
+};
+static int list_launch(trl_ctx* c, ListLaunch& ll) {
+    const LvLayout& G = c->cb.lay;
+    const int capF = c->cb.capF;
+    const int lds_full = c->nms_full, lds_small = c->nms_small < c->nms_full ? c->nms_small : c->nms_full;
+    // LDS tiers: no list is longer than its capacity, so the carve never exceeds what the call can produce
+    int max_capl = 4;
+    for (int l = 0; l < G.L; l++) if (G.capl[l] > max_capl) max_capl = G.capl[l];
+    ll.max_capl = max_capl;
+    ll.full_l = max_capl < lds_full ? max_capl : lds_full;
+    ll.full_f = capF < lds_full ? capF : lds_full;
+    // lists that can take the spill tier run with 1024 threads per workgroup: its cost is pair tests (candidates x boxes kept so far)
+    ll.th_l = max_capl > lds_full ? 1024 : 256;
+    ll.th_f = capF > lds_full ? 1024 : 256;
+    ll.sm_l = Smem::bytes(ll.full_l, ll.th_l);
+    ll.sm_f = Smem::bytes(ll.full_f, ll.th_f);
+    ll.small_cap = ll.full_l < lds_small ? ll.full_l : lds_small;
+    ll.sm_s = Smem::bytes(ll.small_cap);
+    TRL_CHECK(set_dyn_smem(k_nms_level, ll.sm_l));
+    TRL_CHECK(set_dyn_smem(k_nms_frame, ll.sm_f));
+    TRL_CHECK(set_dyn_smem(k_stage2_post, ll.sm_f));
+    TRL_CHECK(set_dyn_smem(k_stage3_post, ll.sm_f));
+    return TRL_OK;
+}
+// stage 1 after PNet: per (frame, level) batched_nms(0.5) in the small and the full tier, then per frame NMS 0.7 + regression
+static int launch_stage1_lists(trl_ctx* c, const ListLaunch& ll, int n, int H, int W, const Spill& sp, hipStream_t s) {
+    CascadeBufs& B = c->cb;
+    const LvLayout& G = B.lay;
+    const int L = G.L;
+    k_nms_level<<<n * L, 256, ll.sm_s, s>>>(G, ll.small_cap, 0, ll.small_cap == ll.max_capl ? 1 : 0, W, H, B.lvl_cnt, B.lvl_rec, B.lvl_keep_cnt, B.lvl_keep_idx, B.flags, sp);
+    TRL_LAUNCH_CHECK();
+    if (ll.small_cap < ll.max_capl) {
+        k_nms_level<<<n * L, ll.th_l, ll.sm_l, s>>>(G, ll.full_l, ll.small_cap + 1, 1, W, H, B.lvl_cnt, B.lvl_rec, B.lvl_keep_cnt, B.lvl_keep_idx, B.flags, sp);
+        TRL_LAUNCH_CHECK();
+    }
+    k_nms_frame<<<n, ll.th_f, ll.sm_f, s>>>(G, ll.full_f, B.capF, W, H, B.lvl_rec, B.lvl_keep_cnt, B.lvl_keep_idx, B.n1, B.s1_box, B.flags, sp);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+// stage 2 tail over the R-Net outputs out6 [cap2][6] (candidate off2[f] + i = row i of frame f)
+static int launch_stage2_post(trl_ctx* c, const ListLaunch& ll, int n, int H, int W, int cap2, const float* out6, const Spill& sp, hipStream_t s) {
+    CascadeBufs& B = c->cb;
+    k_stage2_post<<<n, ll.th_f, ll.sm_f, s>>>(ll.full_f, B.capF, cap2, W, H, c->cfg.thr1, B.n1, B.s1_box, B.off2, out6, B.n2, B.s2_box, sp);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+// stage 3 tail over the O-Net outputs out16 [cap3][16]
+static int launch_stage3_post(trl_ctx* c, const ListLaunch& ll, int n, int cap3, const float* out16, const Spill& sp, hipStream_t s) {
+    CascadeBufs& B = c->cb;
+    k_stage3_post<<<n, ll.th_f, ll.sm_f, s>>>(ll.full_f, B.capF, cap3, c->cfg.thr2, B.n2, B.s2_box, B.off3, out16, B.n3, B.s3_box, B.s3_pts, sp);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
 // detect_face() stages 1-3 for n frames; results stay in c->cb
 // `resume` = 2 / 3: re-run of a call whose R-Net / O-Net batch capacity was too small -- everything up to that stage is intact in
 // the cascade arena (the lists, the stage boxes, the counts), so the attempt starts at stage 2 / 3 instead of at the pyramid.
@@ -1143,17 +1217,7 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     if (!resume) plan_lists(c, L);
     const LvLayout& G = B.lay;
     const int capF = B.capF;
-    const int lds_full = c->nms_full, lds_small = c->nms_small < c->nms_full ? c->nms_small : c->nms_full;
-    // spill workspace: lists that can outgrow the LDS tier get theirs up front (bounded; a pool that still runs out is grown by the re-run)
-    size_t spill = c->spill_hint;
-    {
-        size_t per_frame = 0;
-        for (int l = 0; l < L; l++) if (G.capl[l] > lds_full) per_frame += spill_need(G.capl[l], W, H);
-        if (capF > lds_full) per_frame += 3 * spill_need(capF, W, H);
-        size_t up_front = per_frame * (size_t)n;
-        if (up_front > (8ull << 30)) up_front = 8ull << 30;
-        if (up_front > spill) spill = up_front;
-    }
+    const size_t spill = spill_pool(c, n, H, W);
     Arena& A = c->arena;      // cascade lists: live for the whole call (and for the debug hooks after it)
     Arena& X = c->scratch;    // activations: reset between stages
     if (resume) {
@@ -1279,31 +1343,9 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
             TRL_HIP(hipEventRecord(pe->second, s));
         }
     }
-    // LDS tiers: no list is longer than its capacity, so the carve never exceeds what the call can produce
-    int max_capl = 4;
-    for (int l = 0; l < L; l++) if (G.capl[l] > max_capl) max_capl = G.capl[l];
-    const int full_l = max_capl < lds_full ? max_capl : lds_full, full_f = capF < lds_full ? capF : lds_full;
-    // lists that can take the spill tier run with 1024 threads per workgroup: its cost is pair tests (candidates x boxes kept so far)
-    const int th_l = max_capl > lds_full ? 1024 : 256, th_f = capF > lds_full ? 1024 : 256;
-    const size_t sm_l = Smem::bytes(full_l, th_l), sm_f = Smem::bytes(full_f, th_f);
-    TRL_CHECK(set_dyn_smem(k_nms_level, sm_l));
-    TRL_CHECK(set_dyn_smem(k_nms_frame, sm_f));
-    TRL_CHECK(set_dyn_smem(k_stage2_post, sm_f));
-    TRL_CHECK(set_dyn_smem(k_stage3_post, sm_f));
-    if (!resume) {
-        const int small_cap = full_l < lds_small ? full_l : lds_small;
-        const size_t sm_s = Smem::bytes(small_cap);
-        k_nms_level<<<n * L, 256, sm_s, s>>>(G, small_cap, 0, small_cap == max_capl ? 1 : 0, W, H, B.lvl_cnt, B.lvl_rec, B.lvl_keep_cnt, B.lvl_keep_idx, B.flags, sp);
-        TRL_LAUNCH_CHECK();
-        if (small_cap < max_capl) {
-            k_nms_level<<<n * L, th_l, sm_l, s>>>(G, full_l, small_cap + 1, 1, W, H, B.lvl_cnt, B.lvl_rec, B.lvl_keep_cnt, B.lvl_keep_idx, B.flags, sp);
-            TRL_LAUNCH_CHECK();
-        }
-    }
-    if (!resume) {
-        k_nms_frame<<<n, th_f, sm_f, s>>>(G, full_f, capF, W, H, B.lvl_rec, B.lvl_keep_cnt, B.lvl_keep_idx, B.n1, B.s1_box, B.flags, sp);
-        TRL_LAUNCH_CHECK();
-    }
+    ListLaunch ll;
+    TRL_CHECK(list_launch(c, ll));
+    if (!resume) TRL_CHECK(launch_stage1_lists(c, ll, n, H, W, sp, s));
 
     // ---- stage 2: RNet ------------------------------------------------------------------------------
     // No host round trip: the candidate total stays on the device (off2[n]).  Launches are sized by an optimistic capacity
@@ -1319,8 +1361,7 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     float* out6 = (float*)X.alloc((size_t)cap2 * 24);
     if (!out6) { trl_set_error("rnet workspace"); return TRL_ERR_STATE; }
     TRL_CHECK(trl_stage_net(c, 24, d_frames, H, W, B.off2 + n, cap2, out6, s));
-    k_stage2_post<<<n, th_f, sm_f, s>>>(full_f, capF, cap2, W, H, c->cfg.thr1, B.n1, B.s1_box, B.off2, out6, B.n2, B.s2_box, sp);
-    TRL_LAUNCH_CHECK();
+    TRL_CHECK(launch_stage2_post(c, ll, n, H, W, cap2, out6, sp, s));
     }
 
     // ---- stage 3: ONet --------------------------------------------------------------------------------
@@ -1332,8 +1373,7 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     float* out16 = (float*)X.alloc((size_t)cap3 * 64);
     if (!out16) { trl_set_error("onet workspace"); return TRL_ERR_STATE; }
     TRL_CHECK(trl_stage_net(c, 48, d_frames, H, W, B.off3 + n, cap3, out16, s));
-    k_stage3_post<<<n, th_f, sm_f, s>>>(full_f, capF, cap3, c->cfg.thr2, B.n2, B.s2_box, B.off3, out16, B.n3, B.s3_box, B.s3_pts, sp);
-    TRL_LAUNCH_CHECK();
+    TRL_CHECK(launch_stage3_post(c, ll, n, cap3, out16, sp, s));
     return TRL_OK;
 }
 
@@ -1427,6 +1467,118 @@ int trl_cascade_check(trl_ctx* c, int n, int* retry) {
             const size_t want = (size_t)spill_used + (spill_used >> 2), d = c->spill_hint - (c->spill_hint >> 5);
             c->spill_hint = spill_used ? (want > d ? want : d) : (d > (1u << 20) ? d : 0);
         }
+    }
+    return TRL_OK;
+}
+
+// test hook behind trl_debug_lists: the list kernels on lists the caller provides, launched by the cascade's own code
+// (list_launch, launch_stage1_lists / launch_stage2_post / launch_stage3_post, trl_cascade_finish) with the cascade's spill pool
+// and overflow flags.  kind 1: h_rows = Cand records of every (frame, level), frame-major, h_counts [n][L]; kind 2: stage-1 rows
+// (x1, y1, x2, y2, score) of every frame, h_counts [n], h_logits the R-Net outputs [total][6]; kind 3: stage-2 rows, h_logits the
+// O-Net outputs [total][16], then k_select into the d_* outputs and the stage-3 landmarks into h_pts [n][capF][10] (nullable).
+// h_caps = the L level capacities, then capF.  Every slot the inputs do not fill holds the poison byte of trl_debug_poison (0xA5
+// without one).  The lists stay in c->cb for the inspection hooks (trl_debug_level_keep, trl_debug_stage_boxes).
+int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* h_caps, int L, const int32_t* h_counts, const void* h_rows,
+                      const float* h_logits, float* h_pts, float* d_boxes, float* d_probs, float* d_points, int32_t* d_counts, float* d_box0,
+                      float* d_prob0, int32_t* d_rect, uint8_t* d_valid, hipStream_t s) {
+    CascadeBufs& B = c->cb;
+    B = CascadeBufs();
+    LvLayout& G = B.lay;
+    G.L = L;
+    for (int l = 0; l < L; l++) { G.capl[l] = h_caps[l]; G.rec0[l] = G.S; G.S += h_caps[l]; }
+    B.capF = h_caps[L];
+    B.n = n; B.L = L; B.H = H; B.W = W;
+    const int capF = B.capF, nc = kind == 1 ? n * L : n;
+    long long total = 0;
+    for (int i = 0; i < nc; i++) total += h_counts[i];
+    const size_t spill = spill_pool(c, n, H, W);
+    Arena& A = c->arena;
+    const size_t need = (size_t)n * ((size_t)G.S * (sizeof(Cand) + 4) + (size_t)L * 8) + (size_t)n * capF * (5 * 3 + 10) * 4 +
+                        (size_t)n * 64 + spill + (1u << 20);
+    TRL_CHECK(trl_ensure(c, A, need));
+    A.reset();
+    B.lvl_cnt = (int32_t*)A.alloc((size_t)n * L * 4 + 4);
+    B.lvl_keep_cnt = (int32_t*)A.alloc((size_t)n * L * 4 + 4);
+    B.lvl_rec = (Cand*)A.alloc((size_t)n * G.S * sizeof(Cand) + 4);
+    B.lvl_keep_idx = (int32_t*)A.alloc((size_t)n * G.S * 4 + 4);
+    B.n1 = (int32_t*)A.alloc((size_t)n * 4); B.n2 = (int32_t*)A.alloc((size_t)n * 4); B.n3 = (int32_t*)A.alloc((size_t)n * 4);
+    B.s1_box = (float*)A.alloc((size_t)n * capF * 20); B.s2_box = (float*)A.alloc((size_t)n * capF * 20);
+    B.s3_box = (float*)A.alloc((size_t)n * capF * 20); B.s3_pts = (float*)A.alloc((size_t)n * capF * 40);
+    B.off2 = (int32_t*)A.alloc((size_t)(n + 1) * 4); B.off3 = (int32_t*)A.alloc((size_t)(n + 1) * 4);
+    const size_t live = A.off;
+    B.flags = (int32_t*)A.alloc(TRL_NFLAGS * 4);
+    B.spill = spill ? (char*)A.alloc(spill) : nullptr;
+    B.spill_cap = B.spill ? spill : 0;
+    if (!B.lvl_cnt || !B.lvl_keep_cnt || !B.lvl_rec || !B.lvl_keep_idx || !B.n1 || !B.n2 || !B.n3 || !B.s1_box || !B.s2_box || !B.s3_box ||
+        !B.s3_pts || !B.off2 || !B.off3 || !B.flags || (spill && !B.spill)) {
+        trl_set_error("list workspace allocation failed");
+        B = CascadeBufs();
+        return TRL_ERR_STATE;
+    }
+    B.arena_mark = A.off;
+    const int poison = c->dbg_poison >= 0 ? c->dbg_poison : 0xA5;
+    TRL_HIP(hipMemsetAsync(A.base, poison, live, s));
+    TRL_HIP(hipMemsetAsync(B.flags, 0, TRL_NFLAGS * 4, s));
+    // the caller's lists, packed, into the capacity layout; the poison stays in the slots behind the counts
+    std::vector<int32_t> cnt(h_counts, h_counts + nc);
+    std::vector<float> logits;
+    const int NO = kind == 2 ? 6 : 16;
+    if (kind == 1) {
+        const Cand* src = (const Cand*)h_rows;
+        TRL_HIP(hipMemcpyAsync(B.lvl_cnt, cnt.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
+        for (int f = 0; f < n; f++)
+            for (int l = 0; l < L; l++) {
+                const int k = cnt[f * L + l];
+                if (k) TRL_HIP(hipMemcpyAsync(B.lvl_rec + (size_t)f * G.S + G.rec0[l], src, (size_t)k * sizeof(Cand), hipMemcpyHostToDevice, s));
+                src += k;
+            }
+    } else {
+        const float* src = (const float*)h_rows;
+        float* rows = kind == 2 ? B.s1_box : B.s2_box;
+        TRL_HIP(hipMemcpyAsync(kind == 2 ? B.n1 : B.n2, cnt.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+        for (int f = 0; f < n; f++) {
+            if (cnt[f]) TRL_HIP(hipMemcpyAsync(rows + (size_t)f * capF * 5, src, (size_t)cnt[f] * 20, hipMemcpyHostToDevice, s));
+            src += 5 * (size_t)cnt[f];
+        }
+        logits.assign(h_logits, h_logits + (size_t)total * NO);
+    }
+    TRL_HIP(hipStreamSynchronize(s));                     // (host vectors)
+    const Spill sp{B.spill, (unsigned long long)B.spill_cap, B.flags};
+    ListLaunch ll;
+    TRL_CHECK(list_launch(c, ll));
+    if (kind == 1) {
+        TRL_CHECK(launch_stage1_lists(c, ll, n, H, W, sp, s));
+    } else {
+        // the net outputs: [cap][NO] in the scratch arena, cap = the candidate total (+ 64 poisoned rows behind it)
+        const int cap = (int)total + 64;
+        Arena& X = c->scratch;
+        X.reset();
+        TRL_CHECK(trl_ensure(c, X, (size_t)cap * NO * 4 + (1u << 20)));
+        X.reset();
+        float* out = (float*)X.alloc((size_t)cap * NO * 4);
+        if (!out) { trl_set_error("list hook net outputs"); return TRL_ERR_STATE; }
+        TRL_HIP(hipMemsetAsync(out, poison, (size_t)cap * NO * 4, s));
+        if (total) TRL_HIP(hipMemcpyAsync(out, logits.data(), logits.size() * 4, hipMemcpyHostToDevice, s));
+        if (kind == 2) {
+            k_scan_counts<<<1, 256, 0, s>>>(B.n1, n, B.off2, cap, B.flags, 0);
+            TRL_LAUNCH_CHECK();
+            TRL_CHECK(launch_stage2_post(c, ll, n, H, W, cap, out, sp, s));
+        } else {
+            k_scan_counts<<<1, 256, 0, s>>>(B.n2, n, B.off3, cap, B.flags, 1);
+            TRL_LAUNCH_CHECK();
+            TRL_CHECK(launch_stage3_post(c, ll, n, cap, out, sp, s));
+            TRL_CHECK(trl_cascade_finish(c, nullptr, n, H, W, d_boxes, d_probs, d_points, d_counts, d_box0, d_prob0, d_rect, d_valid, nullptr, s));
+        }
+        TRL_HIP(hipStreamSynchronize(s));                 // (the logits vector)
+    }
+    if (kind != 3) TRL_HIP(hipMemcpyAsync(c->h_pinned + 4, B.flags, TRL_NFLAGS * 4, hipMemcpyDeviceToHost, s));
+    if (kind == 3 && h_pts) TRL_HIP(hipMemcpyAsync(h_pts, B.s3_pts, (size_t)n * capF * 40, hipMemcpyDeviceToHost, s));
+    TRL_HIP(hipStreamSynchronize(s));
+    c->last_attempts = 1;
+    const int32_t* fl = c->h_pinned + 4;
+    if (fl[FLG_LEVEL] || fl[FLG_FRAME] || fl[FLG_SPILL]) {
+        trl_set_error("list hook: a capacity was too small (level %d, frame %d, spill %d)", fl[FLG_LEVEL], fl[FLG_FRAME], fl[FLG_SPILL]);
+        return TRL_ERR_CAPACITY;
     }
     return TRL_OK;
 }

@@ -147,6 +147,9 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
 int trl_cascade_finish(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, float* d_points,
                        int32_t* d_counts, float* d_box0, float* d_prob0, int32_t* d_rect, uint8_t* d_valid, float* d_pts0, hipStream_t s);
 int trl_cascade_check(trl_ctx* c, int n, int* retry);   // after the call's stream synchronisation
+int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* h_caps, int L, const int32_t* h_counts, const void* h_rows,
+                      const float* h_logits, float* h_pts, float* d_boxes, float* d_probs, float* d_points, int32_t* d_counts, float* d_box0,
+                      float* d_prob0, int32_t* d_rect, uint8_t* d_valid, hipStream_t s);   // trl_debug_lists
 int trl_launch_crop_resize80(const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid,
                              float* d_faces, hipStream_t s);
 int trl_launch_crop_aligned(const uint8_t* d_frames, int n, int H, int W, const float* d_pts0, const uint8_t* d_valid, int S, bool rgb,

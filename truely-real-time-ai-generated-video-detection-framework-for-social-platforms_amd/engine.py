@@ -465,6 +465,52 @@ class Engine:
                                                 int(capacity), _ptr(out), self._stream()))
         return out
 
+    def lists(self, kind: int, H: int, W: int, caps, counts, rows: np.ndarray, logits: np.ndarray | None = None) -> dict:
+        """Test hook (``trl_debug_lists``): the cascade's list kernels on caller-built lists of frames H x W, launched as the
+        cascade launches them.  ``caps`` = level capacities then the per-frame capacity.
+        kind 1: ``rows`` = CAND_DTYPE records of every (frame, level) in append order, ``counts`` [n][L] -> {"keep": [n][L] pick
+        lists (indices into that list's records), "rows1": [n] stage-1 rows}.
+        kind 2: ``rows`` = stage-1 rows [total][5] (frame-major), ``counts`` [n], ``logits`` [total][6] -> {"rows2": [n]}.
+        kind 3: stage-2 rows, ``logits`` [total][16] -> {"rows3", "pts3": [n] per frame, and the k_select outputs "boxes",
+        "probs", "points", "counts", "box0", "prob0", "rect", "valid" as numpy arrays}."""
+        caps = np.ascontiguousarray(caps, np.int32)
+        counts = np.ascontiguousarray(counts, np.int32)
+        n = counts.shape[0]
+        L = counts.shape[1] if kind == 1 else 0
+        assert len(caps) == L + 1
+        rows = np.ascontiguousarray(rows, self.CAND_DTYPE if kind == 1 else np.float32)
+        lg = None if logits is None else np.ascontiguousarray(logits, np.float32)
+        capF = int(caps[-1])
+        out = {}
+        if kind == 3:
+            mf = self.cfg.max_faces
+            dev = dict(boxes=torch.empty((n, mf, 4), dtype=torch.float32, device=self.device),
+                       probs=torch.empty((n, mf), dtype=torch.float32, device=self.device),
+                       points=torch.empty((n, mf, 10), dtype=torch.float32, device=self.device),
+                       counts=torch.empty((n,), dtype=torch.int32, device=self.device),
+                       box0=torch.empty((n, 4), dtype=torch.float32, device=self.device),
+                       prob0=torch.empty((n,), dtype=torch.float32, device=self.device),
+                       rect=torch.empty((n, 4), dtype=torch.int32, device=self.device),
+                       valid=torch.empty((n,), dtype=torch.uint8, device=self.device))
+            pts = np.zeros((n, capF, 10), np.float32)
+        else:
+            dev = dict.fromkeys(("boxes", "probs", "points", "counts", "box0", "prob0", "rect", "valid"))
+            pts = None
+        _lib.check(self.lib.trl_debug_lists(self._h, int(kind), n, int(H), int(W), caps.ctypes.data_as(C.c_void_p), L,
+                                            counts.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p),
+                                            None if lg is None else lg.ctypes.data_as(C.c_void_p),
+                                            None if pts is None else pts.ctypes.data_as(C.c_void_p),
+                                            *(_ptr(dev[k]) for k in ("boxes", "probs", "points", "counts", "box0", "prob0", "rect", "valid")),
+                                            self._stream()))
+        torch.cuda.synchronize(self.device)
+        if kind == 1:
+            out["keep"] = [[self.level_keep(f, l)[1] for l in range(L)] for f in range(n)]
+        out[f"rows{kind}"] = [self.stage_boxes(kind, f) for f in range(n)]
+        if kind == 3:
+            out["pts3"] = [pts[f, :len(out["rows3"][f])].copy() for f in range(n)]
+            out.update({k: v.cpu().numpy() for k, v in dev.items()})
+        return out
+
     def crop_resize(self, frames, rect: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:
         fr = self._frames(frames)
         n, H, W, _ = fr.shape

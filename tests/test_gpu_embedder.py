@@ -39,11 +39,10 @@ CASES = [
 ]
 PREC = {0: "f32", 1: "bf16", 2: "fp16"}
 
-# Every (family, bm, bn, bk, pad) the shipped dispatch selects for FaceNet's layer shapes (crops 80 and 160, any face count, the
-# small-map family on or off, f32 / bf16 / fp16).  Not listed, because only the tuning build reaches them: the fn_conv tiles
-# 32x64, 64x32, 64x96, 128x32, 128x64, 32x128, 16x64 and the fn_conv_split4 tiles 16x64, 32x64 (TRL_FN_FORCE1 / TRL_FN_FORCE4);
-# conv_tap with BK 16 where 32 channels divide Cin (TRL_CONV_BK16); conv_igemm_vec (TRL_NO_TAP); the 64-row tiles of M >= 16384
-# layers (TRL_CONV_BIGM).  Instantiated but never selected for FaceNet: conv_tap48 (Cout 48: R-Net conv2, see test_gpu_stage_nets.py),
+# Every (family, bm, bn, bk, pad) the dispatch selects for FaceNet's layer shapes (crops 80 and 160, any face count, the
+# small-map family on or off, f32 / bf16 / fp16); the fn_conv / fn_conv_split4 entries are every tile those families instantiate.
+# Instantiated but never selected for FaceNet: conv_igemm_vec (no tap chunk divides Cin, or inputs past 32-bit element offsets),
+# conv_tap48 (Cout 48: R-Net conv2, see test_gpu_stage_nets.py),
 # conv_tap BK 28 and conv_splitk4 (no shipped network selects them: R-Net's conv2, the one Cin 28 layer, takes conv_tap48 where a
 # 128 x 64 tile would apply, and the R-/O-Net dense layers take conv_splitk4_tap), conv_tap with padding and BK 16 (every padded
 # conv has Cin % 32 == 0), conv_bf16 with padding and BK 16 (likewise).

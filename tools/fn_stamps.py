@@ -1,6 +1,10 @@
 """Where do the waves of one small-map conv launch spend their cycles?  python tools/fn_stamps.py <launch index in one FaceNet pass>"""
 import ctypes as C, os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+# the stamps (trl_debug_fn_arm / trl_debug_fn_read) exist in the tuning build only (make -C .../csrc TUNING=1)
+os.environ.setdefault("TRUELY_HIP_LIB", os.path.join(ROOT, "truely-real-time-ai-generated-video-detection-framework-for-social-platforms_amd",
+                                                     "libtruely_hip_tuning.so"))
 import numpy as np, torch, truely_amd
 from truely_amd.engine import Engine
 from truely_amd import _lib

@@ -4,8 +4,10 @@
 
 hipcc embeds one gfx950 code object per translation unit in the .so's .hip_fatbin section (clang offload bundles); their
 AMDGPU metadata notes are printed with llvm-readelf.  Every PRODUCTION kernel is expected to have
-private_segment_fixed_size == 0; the diagnostic instantiations of k_pnet_fused (last template argument true:
-clock stamps + phase ablations, selected by TRL_PNET_CLOCK / TRL_PNET_SKIP only) are reported but may spill a few registers.
+private_segment_fixed_size == 0.  The shipped library holds production kernels only: the diagnostic
+instantiations (last template argument true: clock stamps + timing-only ablations) of k_pnet_fused, k_mtcnn_front, fn_conv and
+fn_conv_split4 exist in the tuning build alone, may spill a few registers there, and are not checked (kernels(lib) reads either
+build).
 A kernel whose metadata reserves a private segment is disassembled: LLVM sometimes leaves the frame of SGPR spill slots that all
 went to VGPR lanes (no memory instruction touches it) -- reported as "frame never accessed" and not counted as a spill."""
 import os
@@ -72,6 +74,5 @@ if __name__ == "__main__":
             continue
         note = "" if not k["scratch"] else (f" ({k['accesses']} scratch instructions)" if k["accesses"] else " (frame never accessed)")
         print(f"{dem[:110]:110s} vgpr {k['vgpr']:3d} agpr {k['agpr']:3d} sgpr {k['sgpr']:3d} lds {k['lds']:6d} scratch {k['scratch']}{note}")
-        diagnostic = "k_pnet_fused<" in dem and dem.split(">(")[0].endswith("true")
-        bad += k["accesses"] > 0 and not diagnostic
+        bad += k["accesses"] > 0
     sys.exit(1 if bad else 0)

@@ -39,7 +39,7 @@ timeout -k 10 200 python tools/time_facenet.py 10 768 >> $O/facenet_ms.txt 2>&1
 timeout -k 10 200 python tools/time_facenet.py 8 1024 >> $O/facenet_ms.txt 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_fn2048 -o s -f csv -- python3 tools/time_facenet.py 4 2048 > $O/stats_fn2048.log 2>&1
 timeout -k 10 200 python tools/time_facenet.py 6 2048 >> $O/facenet_ms.txt 2>&1
-timeout -k 10 200 python tools/fn_stamps.py 2 5 16 58 60 61 2>&1 | grep -E "launch|fn stamps" > $O/facenet_stamps.txt
+TRUELY_HIP_LIB=$TUNE_LIB timeout -k 10 200 python tools/fn_stamps.py 2 5 16 58 60 61 2>&1 | grep -E "launch|fn stamps" > $O/facenet_stamps.txt
 echo "facenet done"
 # where the waves of the fused PNet kernel spend their time (DBG instantiation: shader clocks per phase and barrier), its phase
 # ablation with SQ counters, and the batch sweeps

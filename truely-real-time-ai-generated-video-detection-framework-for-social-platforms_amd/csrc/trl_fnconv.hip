@@ -471,8 +471,10 @@ template <int BM, int BN, int WM, int WN>
 int launch1(const FnGroup& g, int nz, hipStream_t s) {
     int gx = 0, gy = 0;
     for (int z = 0; z < nz; z++) { gx = g.gx[z] > gx ? g.gx[z] : gx; gy = g.gy[z] > gy ? g.gy[z] : gy; }
-    if (g.dbg || g.skip) fn_conv<BM, BN, WM, WN, true><<<dim3(gx, gy, nz), 256, 0, s>>>(g);
-    else fn_conv<BM, BN, WM, WN, false><<<dim3(gx, gy, nz), 256, 0, s>>>(g);
+#ifdef TRL_TUNING
+    if (g.dbg || g.skip) { fn_conv<BM, BN, WM, WN, true><<<dim3(gx, gy, nz), 256, 0, s>>>(g); return TRL_OK; }
+#endif
+    fn_conv<BM, BN, WM, WN, false><<<dim3(gx, gy, nz), 256, 0, s>>>(g);
     return TRL_OK;
 }
 template <int BM, int BN>
@@ -484,20 +486,24 @@ int launch4(const FnGroup& g, int nz, hipStream_t s) {
     // The dynamic-LDS limit is a per-DEVICE function attribute (the 48x64 tile needs 67 KB, over the 64 KB default): set on every
     // launch -- a process may hold contexts on several devices, and worker threads launch concurrently (a host-side call, no
     // device work; a process-wide "already set" flag was wrong on both counts).
+#ifdef TRL_TUNING
     if (g.dbg || g.skip) {
         TRL_HIP(hipFuncSetAttribute((const void*)fn_conv_split4<BM, BN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         fn_conv_split4<BM, BN, true><<<dim3(gx, gy, nz), 256, bytes, s>>>(g);
-    } else {
-        TRL_HIP(hipFuncSetAttribute((const void*)fn_conv_split4<BM, BN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        fn_conv_split4<BM, BN, false><<<dim3(gx, gy, nz), 256, bytes, s>>>(g);
+        return TRL_OK;
     }
+#endif
+    TRL_HIP(hipFuncSetAttribute((const void*)fn_conv_split4<BM, BN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    fn_conv_split4<BM, BN, false><<<dim3(gx, gy, nz), 256, bytes, s>>>(g);
     return TRL_OK;
 }
 
+#ifdef TRL_TUNING
 // diagnostic stamps: the k-th launch after trl_debug_fn_arm(k) records per-wave cycle stamps
 unsigned long long* g_dbg_buf = nullptr;
 int g_dbg_arm = -1, g_dbg_waves = 0;
 constexpr int DBG_WAVES = 1 << 16;
+#endif
 
 bool fn_split4(const ConvArgs& a) { return a.OH * a.OW <= 9 && a.K >= 512 && (a.K & 15) == 0; }
 
@@ -507,8 +513,7 @@ bool trl_fn_split4_rule(const ConvArgs& a) { return fn_split4(a); }
 
 // Does this family take the layer?  Whole-tap chunks of 32 channels, float4-aligned input, 32-bit element offsets, small M.
 bool trl_fn_eligible(const ConvArgs& a) {
-    const bool off = g_trl_no_fnconv != 0 || trl_tune_set("TRL_NO_FNCONV");
-    if (off || a.lowp || a.m_dev) return false;
+    if (g_trl_no_fnconv || a.lowp || a.m_dev) return false;
     if (a.M <= 0 || a.M > 16384 || a.Cin % 32 != 0 || a.K != a.KH * a.KW * a.Cin) return false;
     if ((a.ldx & 3) || (a.xoff & 3) || (((uintptr_t)a.x) & 15) || (a.ldw & 3)) return false;
     if ((long long)a.N * a.H * a.W * a.ldx + a.xoff >= 0x7fffffffll || (long long)a.K * a.ldw >= 0x7fffffffll) return false;
@@ -525,10 +530,11 @@ bool trl_fn_eligible(const ConvArgs& a) {
     return true;
 }
 
-// Workgroup tile by MEASUREMENT (tools/tune_fn_tiles.sh: every tile forced in turn under rocprofv3, per-launch times compared at the
-// 256-face geometry M = 12544 / 2304 / 256): these launches live on occupancy, not on operand reuse -- 32x32 tiles (many small
-// workgroups hide each other's load latency) beat the "whole rounds of 256 CUs" model of the first version by 13 % overall; the
-// exceptions are the four-chain layers on 3x3 maps, whose wave-private staging favours 48-row tiles for N <= 256.
+// Workgroup tile by MEASUREMENT (single-chain 32x32, 32x64, 64x32, 64x64, 64x96, 128x32, 128x64, 32x128, 16x64 and four-chain
+// {16,32,48}x{32,64} each forced in turn under rocprofv3, per-launch times compared at the 256-face geometry M = 12544 / 2304 / 256):
+// these launches live on occupancy, not on operand reuse -- 32x32 tiles (many small workgroups hide each other's load latency) beat
+// the "whole rounds of 256 CUs" model of the first version by 13 % overall; the exceptions are the four-chain layers on 3x3 maps,
+// whose wave-private staging favours 48-row tiles for N <= 256.  Only the tiles returned here are instantiated.
 static Tile pick_tile(int M, int N, bool split4, int nz) {
     if (!split4) return (M <= 4096 && N >= 512) ? Tile{64, 64} : Tile{32, 32};
     if (nz > 1 || M <= 512) return Tile{16, 32};
@@ -547,25 +553,20 @@ int trl_launch_fn_group(const ConvArgs* convs, int nz, hipStream_t s) {
         N += convs[z].Cout;                                  // the group shares the chip: choose the tile for the combined width
     }
     FnGroup g;
-    // instantiated tiles: single chain {32,64,128}x{32,64,96,128} subset below; four chains {16,32,48}x{32,64}
-    Tile t;
-    // tuning aid: TRL_FN_FORCE1 / TRL_FN_FORCE4 = "BMxBN" forces the tile of every single-chain / four-chain launch
-    static const char* f1 = trl_tune_str("TRL_FN_FORCE1");
-    static const char* f4 = trl_tune_str("TRL_FN_FORCE4");
-    const char* force = sp ? f4 : f1;
-    int fbm = 0, fbn = 0;
-    if (force && sscanf(force, "%dx%d", &fbm, &fbn) == 2) t = Tile{fbm, fbn};
-    else t = pick_tile(M, nz == 1 ? convs[0].Cout : N, sp, nz);
+    const Tile t = pick_tile(M, nz == 1 ? convs[0].Cout : N, sp, nz);
     g_trl_conv_choice = TrlConvChoice{sp ? TRL_FNK_FN_SPLIT4 : TRL_FNK_FN_CONV, t.bm, t.bn, FBK, 0, nz};
     static const int skip = trl_tune_int("TRL_FN_SKIP", 0);
     g.skip = skip;
     g.dbg = nullptr;
+#ifdef TRL_TUNING
     if (g_dbg_arm >= 0 && g_dbg_arm-- == 0) g.dbg = g_dbg_buf;
+#endif
     for (int z = 0; z < 3; z++) {
         g.a[z] = convs[z < nz ? z : 0];
         g.gx[z] = z < nz ? (convs[z].M + t.bm - 1) / t.bm : 0;
         g.gy[z] = z < nz ? (convs[z].Cout + t.bn - 1) / t.bn : 0;
     }
+#ifdef TRL_TUNING
     if (g.dbg) {
         int gx = 0, gy = 0;
         for (int z = 0; z < nz; z++) { gx = g.gx[z] > gx ? g.gx[z] : gx; gy = g.gy[z] > gy ? g.gy[z] : gy; }
@@ -573,13 +574,13 @@ int trl_launch_fn_group(const ConvArgs* convs, int nz, hipStream_t s) {
         if (g_dbg_waves > DBG_WAVES) { g.dbg = nullptr; g_dbg_waves = 0; }
         else fprintf(stderr, "[fn stamps] tile %dx%d split4=%d grid %dx%dx%d M=%d N=%d K=%d Cin=%d\n", t.bm, t.bn, (int)sp, gx, gy, nz, convs[0].M, convs[0].Cout, convs[0].K, convs[0].Cin);
     }
+#endif
 #define FN1(BM, BN, WM, WN) if (t.bm == BM && t.bn == BN) { TRL_CHECK((launch1<BM, BN, WM, WN>(g, nz, s))); TRL_LAUNCH_CHECK(); return TRL_OK; }
 #define FN4(BM, BN) if (t.bm == BM && t.bn == BN) { TRL_CHECK((launch4<BM, BN>(g, nz, s))); TRL_LAUNCH_CHECK(); return TRL_OK; }
     if (sp) {
-        FN4(16, 32) FN4(16, 64) FN4(32, 32) FN4(32, 64) FN4(48, 32) FN4(48, 64)
+        FN4(16, 32) FN4(32, 32) FN4(48, 32) FN4(48, 64)
     } else {
-        FN1(32, 32, 2, 2) FN1(32, 64, 2, 2) FN1(64, 32, 2, 2) FN1(64, 64, 2, 2) FN1(64, 96, 2, 2) FN1(128, 32, 4, 1) FN1(128, 64, 4, 1)
-        FN1(32, 128, 1, 4) FN1(16, 64, 1, 4)
+        FN1(32, 32, 2, 2) FN1(64, 64, 2, 2)
     }
 #undef FN1
 #undef FN4
@@ -587,7 +588,8 @@ int trl_launch_fn_group(const ConvArgs* convs, int nz, hipStream_t s) {
     return TRL_ERR_STATE;
 }
 
-// Diagnostic: arm per-wave cycle stamps for the k-th small-map conv launch from now; read them back after a synchronise.
+#ifdef TRL_TUNING
+// Diagnostic (tuning build only): arm per-wave cycle stamps for the k-th small-map conv launch from now; read them back after a synchronise.
 // Rows of 8 u64 per wave: entry, loads issued, first chunk staged, K loop done, stores issued, wall clock (100 MHz).
 extern "C" int trl_debug_fn_arm(int k) {
     if (!g_dbg_buf && hipMalloc((void**)&g_dbg_buf, (size_t)DBG_WAVES * 64) != hipSuccess) return TRL_ERR_HIP;
@@ -603,3 +605,4 @@ extern "C" int trl_debug_fn_read(unsigned long long* h_rows, int max_waves, int*
     *n_waves = n;
     return TRL_OK;
 }
+#endif

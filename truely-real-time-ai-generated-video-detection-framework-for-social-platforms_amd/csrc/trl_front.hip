@@ -34,12 +34,9 @@ __device__ __forceinline__ unsigned valid_bytes(int rel, int nbytes) {   // 0xFF
 //       1 = all slopes >= 0: PReLU is monotone and commutes with max: med3(m, s m, +-inf) (any slope size);
 //       2 = all slopes in [0, 1]: prelu(m) == max(m, s m).
 // The kernel is VALU-bound (crop unpacking, pooling), and VALU shares the FP32 pipe with the f32 MFMAs.
-// DBG: the timing-only phase ablations (TRL_FRONT_SKIP, tools/front_ablation.sh); compiled out of the production instantiation.
-#ifndef TRL_FRONT_MINW
-#define TRL_FRONT_MINW 1      // tuning aid: minimum waves per SIMD the kernel is compiled for (register budget)
-#endif
+// DBG: the timing-only phase ablations (TRL_FRONT_SKIP, tools/front_ablation.sh); instantiated in the tuning build only.
 template <int S, int C1, int R, int MODE, bool DBG>
-__global__ __launch_bounds__(256, TRL_FRONT_MINW) void k_mtcnn_front(const uint8_t* __restrict__ frames, int nframes, int H, int W,
+__global__ __launch_bounds__(256, 1) void k_mtcnn_front(const uint8_t* __restrict__ frames, int nframes, int H, int W,
                                                      const int4* __restrict__ cbox, const int32_t* __restrict__ d_total, int t0,
                                                      const float* __restrict__ w1,
                                                      const float* __restrict__ b1, const float* __restrict__ s1,
@@ -543,8 +540,16 @@ int slope_mode(const DevV* sl, int n) {
 
 }  // namespace
 
-// timing-only ablation (TRL_FRONT_SKIP: 1/2 = R-Net crop / conv+pool, 4/8 = O-Net); 0 in production
+// One front launch; SKIP: the net's timing-only ablation bits (TRL_FRONT_SKIP: 1/2 = R-Net crop / conv+pool, 4/8 = O-Net), which
+// select the DBG instantiation -- tuning build only.
+#define TRL_FRONT_ARGS d_frames, c->cb.n, H, W, reinterpret_cast<const int4*>(c->cb.cbox), d_total, t0, w->p, b->p, sl->p, d_pool
+#ifdef TRL_TUNING
 static int front_dbg() { static const int v = trl_tune_int("TRL_FRONT_SKIP", 0); return v; }
+#define TRL_FRONT(S, C1, R, MODE, SKIP) do { if (SKIP) k_mtcnn_front<S, C1, R, MODE, true><<<nc, 256, 0, s>>>(TRL_FRONT_ARGS, SKIP); \
+                                             else k_mtcnn_front<S, C1, R, MODE, false><<<nc, 256, 0, s>>>(TRL_FRONT_ARGS, 0); } while (0)
+#else
+#define TRL_FRONT(S, C1, R, MODE, SKIP) k_mtcnn_front<S, C1, R, MODE, false><<<nc, 256, 0, s>>>(TRL_FRONT_ARGS, 0)
+#endif
 
 // R-Net front: pooled [nc][11][11][28]
 int trl_launch_rnet_front(trl_ctx* c, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc,
@@ -554,12 +559,8 @@ int trl_launch_rnet_front(trl_ctx* c, const uint8_t* d_frames, int H, int W, con
     const DevV *b = trl_v(c, "rnet.conv1.b"), *sl = trl_v(c, "rnet.prelu1");
     if (!w || !b || !sl || w->ld != 32 || w->K != 27) { trl_set_error("rnet.conv1 weights"); return TRL_ERR_WEIGHTS; }
     if (c->rnet_front_mode < 0) c->rnet_front_mode = slope_mode(sl, 28);
-    static const int rr = trl_tune_int("TRL_RNET_R", 4);     // tuning aid: pooled rows per conv1 strip
-#define TRL_RF(RR, MODE, DBG) k_mtcnn_front<24, 28, RR, MODE, DBG><<<nc, 256, 0, s>>>(d_frames, c->cb.n, H, W, reinterpret_cast<const int4*>(c->cb.cbox), \
-                                                                       d_total, t0, w->p, b->p, sl->p, d_pool, front_dbg() & 3)
-    if (front_dbg() & 3) { if (c->rnet_front_mode == 2) TRL_RF(4, 2, true); else if (c->rnet_front_mode == 1) TRL_RF(4, 1, true); else TRL_RF(4, 0, true); }
-    else if (c->rnet_front_mode == 2) { if (rr == 2) TRL_RF(2, 2, false); else if (rr == 3) TRL_RF(3, 2, false); else if (rr == 6) TRL_RF(6, 2, false); else TRL_RF(4, 2, false); }
-    else if (c->rnet_front_mode == 1) TRL_RF(4, 1, false); else TRL_RF(4, 0, false);
+#define TRL_RF(MODE) TRL_FRONT(24, 28, 4, MODE, front_dbg() & 3)   // four pooled rows per conv1 strip
+    if (c->rnet_front_mode == 2) TRL_RF(2); else if (c->rnet_front_mode == 1) TRL_RF(1); else TRL_RF(0);
 #undef TRL_RF
     TRL_LAUNCH_CHECK();
     return TRL_OK;
@@ -572,13 +573,9 @@ int trl_launch_onet_front(trl_ctx* c, const uint8_t* d_frames, int H, int W, con
     const DevV *b = trl_v(c, "onet.conv1.b"), *sl = trl_v(c, "onet.prelu1");
     if (!w || !b || !sl || w->ld != 32 || w->K != 27) { trl_set_error("onet.conv1 weights"); return TRL_ERR_WEIGHTS; }
     if (c->onet_front_mode < 0) c->onet_front_mode = slope_mode(sl, 32);
-    static const int orr = trl_tune_int("TRL_ONET_R", 1);   // measured: one pooled row per strip = 49 KB of LDS = three resident
-                                                                                   // workgroups per CU: 1.18 vs 1.27 ms (R = 3, two per CU) for the O-Net front
-#define TRL_OF(RR, MODE, DBG) k_mtcnn_front<48, 32, RR, MODE, DBG><<<nc, 256, 0, s>>>(d_frames, c->cb.n, H, W, reinterpret_cast<const int4*>(c->cb.cbox), \
-                                                                       d_total, t0, w->p, b->p, sl->p, d_pool, (front_dbg() >> 2) & 3)
-    if ((front_dbg() >> 2) & 3) { if (c->onet_front_mode == 2) TRL_OF(1, 2, true); else if (c->onet_front_mode == 1) TRL_OF(1, 1, true); else TRL_OF(1, 0, true); }
-    else if (c->onet_front_mode == 2) { if (orr == 3) TRL_OF(3, 2, false); else if (orr == 2) TRL_OF(2, 2, false); else if (orr == 4) TRL_OF(4, 2, false); else TRL_OF(1, 2, false); }
-    else if (c->onet_front_mode == 1) TRL_OF(1, 1, false); else TRL_OF(1, 0, false);
+    // measured: one pooled row per strip = 49 KB of LDS = three resident workgroups per CU: 1.18 vs 1.27 ms (R = 3, two per CU)
+#define TRL_OF(MODE) TRL_FRONT(48, 32, 1, MODE, (front_dbg() >> 2) & 3)
+    if (c->onet_front_mode == 2) TRL_OF(2); else if (c->onet_front_mode == 1) TRL_OF(1); else TRL_OF(0);
 #undef TRL_OF
     TRL_LAUNCH_CHECK();
     return TRL_OK;

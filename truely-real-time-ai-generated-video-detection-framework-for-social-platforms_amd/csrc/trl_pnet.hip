@@ -604,7 +604,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
     __shared__ __attribute__((aligned(16))) float RB[REGION_B];   // pooled [400][10] (+ the reach of conv2's zero-weight k padding)
     __shared__ __attribute__((aligned(16))) float T3all[108];     // conv3 bias[32], PReLU slopes[32] (a lane's 16 channels differ per register), head bias[8],
                                                                   // screen: logit-difference weights f32(w1 - w0)[32], bias f32(b1 - b0) (phase 3)
-    extern __shared__ __attribute__((aligned(16))) float DYN[];  // DYN_LDS bytes, then whatever a tuning run pads (TRL_PNET_XLDS)
+    extern __shared__ __attribute__((aligned(16))) float DYN[];  // DYN_LDS bytes
     float* const B3S = DYN;                                       // conv3 weights [k][cout]: read per k-chain batch, not held in VGPRs
     float* const CP0 = DYN + 144 * 32;                            // per band row: carried pooled columns [20][4][10], conv2 columns [18][2][17]
     float* const VP = CP0 + BAND * (CARRY_P + CARRY_C);           // carried pooled rows [4][20][10]
@@ -1943,8 +1943,7 @@ static int build_pyramid(trl_ctx* c, const uint8_t* d_frames, int n, int H, int 
         int nfine = 0;
         while (nfine < 3 && nfine < a.L && a.lv[nfine].mode == 0 && a.lv[nfine].h <= H && a.lv[nfine].w <= W) nfine++;
         if (nfine >= 2) {
-            static const int strip_env = trl_tune_int("TRL_PYR_FINE_STRIP", 0);   // tuning: source rows per tile
-            const int strip_rows = strip_env >= 8 ? strip_env : 24;
+            const int strip_rows = 24;                                            // source rows per tile
             int band_cols = (int)(62.0 * W / a.lv[0].w);
             std::vector<uint32_t> own;
             for (; band_cols >= 16; band_cols--) {
@@ -1988,82 +1987,65 @@ static int build_pyramid(trl_ctx* c, const uint8_t* d_frames, int n, int H, int 
     if (ev) TRL_HIP(hipEventRecord(ev[0], s));
     // Frames are resampled in chunks whose source bytes fit the 256 MiB Infinity Cache: every level re-reads the
     // whole source image, so the 2nd..11th level launches of a chunk are served on-die instead of from HBM.
-    static const int chunk_env = trl_tune_int("TRL_PYR_CHUNK", 0);
-    int chunk = chunk_env > 0 ? chunk_env : (int)((176ll << 20) / ((long long)H * W * 3));
+    int chunk = (int)((176ll << 20) / ((long long)H * W * 3));
     if (chunk < 1) chunk = 1;
     if (chunk > n) chunk = n;
-    // coarse levels: one streaming pass (k_pyramid_stream) when its preconditions hold, else the per-level kernels
-    // Streaming pass (k_pyramid_stream) for the coarse levels (mode != 0); optionally (TRL_PYR_STREAM_FINE=1) a second one for
-    // the fine levels.  A group that does not meet the kernel's preconditions falls back to the per-level kernels below.
-    static const bool stream_off = trl_tune_int("TRL_PYR_STREAM", 1) == 0;
-    static const bool fine_on = trl_tune_int("TRL_PYR_STREAM_FINE", 0) != 0;   // measured: 1.75 vs 1.83 ms, not worth a default
-    static const int bands_env = trl_tune_int("TRL_PYR_BANDS", 0);
-    static const int fbands_env = trl_tune_int("TRL_PYR_FINE_BANDS", 0);
+    // Coarse levels (mode != 0): streaming passes (k_pyramid_stream) in three row bands, at most 8 levels per launch (register budget
+    // of the per-level column sums), each launch reading the source once.  A group that does not meet the kernel's preconditions
+    // falls back to the per-level kernels below.  (Streaming the fine levels as well was measured: 1.75 vs 1.83 ms, not worth it.)
     bool streamed[16] = {};
-    static const int wide_env = trl_tune_int("TRL_PYR_STREAM_WIDE", 1);   // tuning: 0 = per-level kernels for frames wider than one band
-    auto stream_group = [&](bool fine, int row_bands) -> int {
-        // the levels of the group, at most 8 per launch (register budget of the per-level column sums): each launch reads the source once
-        int lv_idx[16], nsel = 0;
-        for (int l = 0; l < a.L; l++) if ((a.lv[l].mode == 0) == fine) lv_idx[nsel++] = l;
-        const bool wide = W * 3 > SBYTES;                                       // one workgroup cannot cover the row: wave-local pass
-        if (wide && !wide_env) return TRL_OK;
-        for (int g0 = 0; g0 < nsel; g0 += 8) {
-            const int gn = nsel - g0 < 8 ? nsel - g0 : 8;
-            PyrStreamArgs sa;
-            sa.nlev = 0;
-            int stab_words = 0, kwm = 0;
-            bool ok = true;
-            for (int q = 0; q < gn; q++) {
-                const PLevel& g = a.lv[lv_idx[g0 + q]];
-                if (g.khmax > 256) ok = false;
-                stab_words += g.h + g.w;
-                kwm = g.kwmax > kwm ? g.kwmax : kwm;
-                SLevel& t = sa.lv[sa.nlev++];
-                t.h = g.h; t.w = g.w; t.pix0 = g.pix0; t.pix_pad = g.pix_pad; t.ytab0 = g.ytab0; t.xtab0 = g.xtab0; t.khA = g.khA; t.kwA = g.kwA;
-                t.fastdiv = g.fastdiv; t.rkh[0] = g.rkh[0]; t.rkh[1] = g.rkh[1]; t.rkw[0] = g.rkw[0]; t.rkw[1] = g.rkw[1];
-            }
-            sa.H = H; sa.W = W; sa.n_frames = n; sa.pyr_stride = a.pyr_stride; sa.f0 = 0;   // every source row is read once: no Infinity-Cache chunking
-            sa.row_bands = H >= 256 ? row_bands : 1;
-            sa.rows_per_band = (H + sa.row_bands - 1) / sa.row_bands;
-            if (!ok || stab_words > STAB || n > 65535) continue;                 // these levels take the per-level kernels
-            if (!wide) {
-                if ((kwm + 2) * 3 > SBYTES / 2) continue;
-                sa.col_bands = 1; sa.cols_per_band = W;
-                const dim3 sgrid(sa.row_bands * sa.col_bands, n);
-                if (sa.nlev <= 4) k_pyramid_stream<4><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
-                else k_pyramid_stream<8><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
-            } else {
-                // a wave covers 1280 bytes = 426 whole pixels of a row; the bins that start in its segment may reach kwmax further
-                sa.cols_per_band = SW_BYTES / 3 - kwm;
-                if (sa.cols_per_band < 64) continue;
-                sa.col_bands = (W + sa.cols_per_band - 1) / sa.cols_per_band;
-                sa.cols_per_band = (W + sa.col_bands - 1) / sa.col_bands;           // even segments
-                // enough waves to fill the chip (~4 k) when the batch is small: more, shorter row bands (each reads on past its end
-                // until its last bins are complete, so not shorter than 256 rows)
-                int rbn = (4096 + n * sa.col_bands - 1) / (n * sa.col_bands);
-                if (rbn > H / 256) rbn = H / 256;
-                if (rbn > sa.row_bands) { sa.row_bands = rbn; sa.rows_per_band = (H + rbn - 1) / rbn; }
-                const dim3 sgrid((sa.row_bands * sa.col_bands + 3) / 4, n);
-                if (sa.nlev <= 4) k_pyramid_stream_w<4><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
-                else k_pyramid_stream_w<8><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
-            }
-            TRL_LAUNCH_CHECK();
-            const int kind = wide ? (sa.nlev <= 4 ? TRL_PYR_SW4 : TRL_PYR_SW8) : (sa.nlev <= 4 ? TRL_PYR_S4 : TRL_PYR_S8);
-            for (int q = 0; q < gn; q++) {
-                streamed[lv_idx[g0 + q]] = true;
-                plan(lv_idx[g0 + q], kind, sa.row_bands, sa.col_bands, sa.cols_per_band, n);
-            }
+    int lv_idx[16], nsel = 0;
+    for (int l = 0; l < a.L; l++) if (a.lv[l].mode != 0) lv_idx[nsel++] = l;
+    const bool wide = W * 3 > SBYTES;                                       // one workgroup cannot cover the row: wave-local pass
+    for (int g0 = 0; g0 < nsel; g0 += 8) {
+        const int gn = nsel - g0 < 8 ? nsel - g0 : 8;
+        PyrStreamArgs sa;
+        sa.nlev = 0;
+        int stab_words = 0, kwm = 0;
+        bool ok = true;
+        for (int q = 0; q < gn; q++) {
+            const PLevel& g = a.lv[lv_idx[g0 + q]];
+            if (g.khmax > 256) ok = false;
+            stab_words += g.h + g.w;
+            kwm = g.kwmax > kwm ? g.kwmax : kwm;
+            SLevel& t = sa.lv[sa.nlev++];
+            t.h = g.h; t.w = g.w; t.pix0 = g.pix0; t.pix_pad = g.pix_pad; t.ytab0 = g.ytab0; t.xtab0 = g.xtab0; t.khA = g.khA; t.kwA = g.kwA;
+            t.fastdiv = g.fastdiv; t.rkh[0] = g.rkh[0]; t.rkh[1] = g.rkh[1]; t.rkw[0] = g.rkw[0]; t.rkw[1] = g.rkw[1];
         }
-        return TRL_OK;
-    };
-    if (!stream_off) {
-        TRL_CHECK(stream_group(false, bands_env > 0 ? bands_env : 3));
-        if (fine_on) TRL_CHECK(stream_group(true, fbands_env > 0 ? fbands_env : 8));
+        sa.H = H; sa.W = W; sa.n_frames = n; sa.pyr_stride = a.pyr_stride; sa.f0 = 0;   // every source row is read once: no Infinity-Cache chunking
+        sa.row_bands = H >= 256 ? 3 : 1;
+        sa.rows_per_band = (H + sa.row_bands - 1) / sa.row_bands;
+        if (!ok || stab_words > STAB || n > 65535) continue;                 // these levels take the per-level kernels
+        if (!wide) {
+            if ((kwm + 2) * 3 > SBYTES / 2) continue;
+            sa.col_bands = 1; sa.cols_per_band = W;
+            const dim3 sgrid(sa.row_bands * sa.col_bands, n);
+            if (sa.nlev <= 4) k_pyramid_stream<4><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
+            else k_pyramid_stream<8><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
+        } else {
+            // a wave covers 1280 bytes = 426 whole pixels of a row; the bins that start in its segment may reach kwmax further
+            sa.cols_per_band = SW_BYTES / 3 - kwm;
+            if (sa.cols_per_band < 64) continue;
+            sa.col_bands = (W + sa.cols_per_band - 1) / sa.cols_per_band;
+            sa.cols_per_band = (W + sa.col_bands - 1) / sa.col_bands;           // even segments
+            // enough waves to fill the chip (~4 k) when the batch is small: more, shorter row bands (each reads on past its end
+            // until its last bins are complete, so not shorter than 256 rows)
+            int rbn = (4096 + n * sa.col_bands - 1) / (n * sa.col_bands);
+            if (rbn > H / 256) rbn = H / 256;
+            if (rbn > sa.row_bands) { sa.row_bands = rbn; sa.rows_per_band = (H + rbn - 1) / rbn; }
+            const dim3 sgrid((sa.row_bands * sa.col_bands + 3) / 4, n);
+            if (sa.nlev <= 4) k_pyramid_stream_w<4><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
+            else k_pyramid_stream_w<8><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
+        }
+        TRL_LAUNCH_CHECK();
+        const int kind = wide ? (sa.nlev <= 4 ? TRL_PYR_SW4 : TRL_PYR_SW8) : (sa.nlev <= 4 ? TRL_PYR_S4 : TRL_PYR_S8);
+        for (int q = 0; q < gn; q++) {
+            streamed[lv_idx[g0 + q]] = true;
+            plan(lv_idx[g0 + q], kind, sa.row_bands, sa.col_bands, sa.cols_per_band, n);
+        }
     }
-    const bool stream_ok = true;
-    // the finest levels in one pass over the source (TRL_PYR_FINE=0: the per-level kernels)
-    static const bool fine_off = trl_tune_int("TRL_PYR_FINE", 1) == 0;
-    if (!fine_off && c->pyr_fine.nlev >= 2 && n <= 65535 && c->pyr_fine.n_strips <= 65535) {
+    // the finest levels in one pass over the source
+    if (c->pyr_fine.nlev >= 2 && n <= 65535 && c->pyr_fine.n_strips <= 65535) {
         PyrFineArgs fa;
         fa.H = H; fa.W = W; fa.n_frames = n; fa.f0 = 0; fa.pyr_stride = a.pyr_stride;
         fa.nlev = c->pyr_fine.nlev; fa.band_cols = c->pyr_fine.band_cols; fa.strip_rows = c->pyr_fine.strip_rows;
@@ -2076,7 +2058,7 @@ static int build_pyramid(trl_ctx* c, const uint8_t* d_frames, int n, int H, int 
     for (int f0 = 0; f0 < n; f0 += chunk) {
         const int nf = (n - f0 < chunk) ? n - f0 : chunk;
         for (int l = 0; l < a.L; l++) {
-            if (stream_ok && streamed[l]) continue;
+            if (streamed[l]) continue;
             PyrArgs pa;
             pa.H = H; pa.W = W; pa.n_frames = n; pa.f0 = f0; pa.pyr_stride = a.pyr_stride; pa.g = a.lv[l];
             const int threads = pa.g.pix_pad << pa.g.gshift;
@@ -2140,8 +2122,7 @@ int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     PnetArgs a;
     TRL_CHECK(build_pyramid(c, d_frames, n, H, W, a, ev, s));
     const int total_tiles = a.tiles_per_frame * n;
-    static const int grid_env = trl_tune_int("TRL_PNET_GRID", 0);   // experiment: workgroups of the persistent launch
-    int grid = grid_env > 0 ? grid_env : 256 * 2;   // 2 resident workgroups per CU (<= 256 VGPRs)
+    int grid = 256 * 2;   // 2 resident workgroups per CU (<= 256 VGPRs)
     if (grid > ((total_tiles + 7) / 8) * 8) grid = ((total_tiles + 7) / 8) * 8;
     if (grid < 8) grid = 8;
     TRL_HIP(hipMemsetAsync(c->pnet_cursor, 0, 8 * sizeof(int32_t), s));
@@ -2150,7 +2131,6 @@ int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     // memory-bound and DO overlap that call's narrow kernels (trl_gate_wait, trl_api.hip).
     TRL_CHECK(trl_gate_wait(c, s));
     if (ev) TRL_HIP(hipEventRecord(ev[2], s));   // the event pair brackets the kernel alone (HIP events on the launch's stream)
-    static const int xlds = trl_tune_int("TRL_PNET_XLDS", 0);   // experiment: unused dynamic LDS, lowers the resident workgroups per CU
     // instantiation: slopes all <= 1 or not, a negative conv1 slope or not, diagnostics (TRL_PNET_CLOCK / TRL_PNET_SKIP) or not
 #ifdef TRL_TUNING
     const bool dbg = c->pnet_prof || a.dbg_skip || trl_tune_set("TRL_PNET_SPAN");   // the instantiation with clock stamps / ablations
@@ -2159,14 +2139,13 @@ int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
 #endif
     // Tiles per cursor fetch: a run of 24 = 8 columns of a 3-row band (7 of 8 columns carry horizontally, 2 of 3 rows vertically);
     // small batches keep shorter runs, down to single tiles, so that every CU gets work
-    // (TRL_PNET_RUN / trl_debug_pnet_run override: tuning, and tests that exercise the carry path on small frames)
-    static const int run_env = trl_tune_int("TRL_PNET_RUN", 0);
+    // (trl_debug_pnet_run overrides it: tests that exercise the carry path on small frames)
     const int auto_run = (total_tiles / 8) / 128;
-    a.run = c->pnet_run > 0 ? c->pnet_run : (run_env > 0 ? run_env : (auto_run < 1 ? 1 : (auto_run > 8 * BAND ? 8 * BAND : auto_run)));
+    a.run = c->pnet_run > 0 ? c->pnet_run : (auto_run < 1 ? 1 : (auto_run > 8 * BAND ? 8 * BAND : auto_run));
     auto launch = [&](auto kern) {
         // static + dynamic LDS exceed the default 64 KB per workgroup
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, DYN_LDS + xlds) != hipSuccess) return false;
-        kern<<<grid, 256, DYN_LDS + xlds, s>>>(a);
+        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, DYN_LDS) != hipSuccess) return false;
+        kern<<<grid, 256, DYN_LDS, s>>>(a);
         return true;
     };
     bool launched = false;
@@ -2178,7 +2157,7 @@ int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     if (c->pnet_unit) { if (c->pnet_mono1) TRL_PK(true, false); else TRL_PK(true, true); }
     else { if (c->pnet_mono1) TRL_PK(false, false); else TRL_PK(false, true); }
 #undef TRL_PK
-    if (!launched) { trl_set_error("k_pnet_fused: %d bytes of dynamic LDS refused", DYN_LDS + xlds); return TRL_ERR_HIP; }
+    if (!launched) { trl_set_error("k_pnet_fused: %d bytes of dynamic LDS refused", DYN_LDS); return TRL_ERR_HIP; }
     TRL_LAUNCH_CHECK();
     if (ev) TRL_HIP(hipEventRecord(ev[3], s));
     if (dbg) {

@@ -21,6 +21,10 @@ as a child, BEFORE anything here touches the GPU -- and exits with the child's c
                             host thread per context (round 2's scheme; --embed-group then groups per worker).
   --dump-outputs DIR      : after the timed region, the arrays the last timed step returned go to DIR/<name>.npy (the inputs are
                             seeded: two builds run with the same flags can be compared output for output).
+  --full                  : after the timed region, also what the headline figure does not need: the dominant kernel timed alone
+                            (roofline.kernel_ms_alone / frac_alone, a few extra steps) and the torch-CPU baseline (cpu_baseline,
+                            about 25 s; skipped with --no-cpu-baseline).  Without it those fields are null and a run does only
+                            set-up, warm-up, the timed steps, --dump-outputs and the result line.
 Rank 0 prints ONE JSON line; its ms_per_step is the wall time of the timed region over --steps.
 """
 import argparse
@@ -175,7 +179,10 @@ def parse_args(argv=None):
     ap.add_argument("--config", type=int, default=1, choices=sorted(CONFIGS))
     ap.add_argument("--mode", default="sharded", choices=["sharded", "streams"])
     ap.add_argument("--batch", type=int, default=None, help="frames per GPU per step (default: the config's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also time the dominant kernel alone and run the torch-CPU baseline (off by default: "
+                         "a plain run does only what the headline figure needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the torch-CPU baseline")
     ap.add_argument("--pnet-mode", type=int, default=None)
     ap.add_argument("--prelu", default="unit", choices=["unit", "general"],
                     help="synthetic PReLU slopes: 'unit' in [0.05,0.3] (the seeded default: max(v, s*v) fast path); 'general' "
@@ -515,11 +522,11 @@ def main():
     else:
         scores = [int(d["score"])]
 
-    # After the timed region (never part of `value`): the dominant kernel alone -- a few strictly sequential steps on one context,
-    # nothing else queued on the GPU -- as a cross-check of the figure above (with --in-flight 2 it is the launch duration free of
-    # the queueing behind the other context's launch).
+    # --full, after the timed region (never part of `value`): the dominant kernel alone -- a few strictly sequential steps on one
+    # context, nothing else queued on the GPU -- as a cross-check of the figure above (with --in-flight 2 it is the launch duration
+    # free of the queueing behind the other context's launch).
     iso_ms = None
-    if rank == 0 and eng.cfg.pnet_mode == 0 and frames is not None:
+    if args.full and rank == 0 and eng.cfg.pnet_mode == 0 and frames is not None:
         torch.cuda.synchronize()
         tot = 0.0
         for _ in range(4):
@@ -564,7 +571,7 @@ def main():
                        "emb_crc32": zlib.crc32(emb_all.tobytes()), "mode": args.mode, "ingest": args.ingest,
                        "pnet_path": "fused" if eng.cfg.pnet_mode == 0 else "generic layers",
                        "parallelism": par, "backend": args.backend if use_dist else None, "batches_in_flight": F, "driver": args.driver,
-                       "embed_group": max(1, args.embed_group)},
+                       "embed_group": max(1, args.embed_group), "full": args.full},
             "roofline": {"bound": "mfma", "achieved": round(achieved, 3), "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(achieved / PEAK_F32_MFMA_TFLOPS, 4), "traffic": traffic,
                          "kernel": "k_pnet_fused (PNet over the pyramid: 83% of the conv FLOPs at 720p)",
@@ -574,7 +581,7 @@ def main():
                          "frac_alone": None if iso_ms is None else round(2.0 * macs / (iso_ms / 1e3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
                          "pyramid_ms_per_step": round(pyr_ms / args.steps, 3)},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = host_cores()
             res["cpu_baseline"] = cpu_baseline(frames_np, threads, cfg)
         else:

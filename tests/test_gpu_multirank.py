@@ -18,8 +18,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*flags, timeout=600):
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+def _bench(*flags, timeout=600, **environ):
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **environ)
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags], capture_output=True, text=True, timeout=timeout,
                        env=env, cwd=ROOT)
@@ -87,6 +87,22 @@ def test_bench_dump_outputs_are_the_last_step(engine, tmp_path):
     assert np.array_equal(got["sims"], d["sims"].cpu().numpy()) and np.array_equal(got["flags"], d["flags"].cpu().numpy())
     assert got["drift"].tolist() == [d["score"], d["run"], d["hits"], d["total"]] and d["score"] == r["config"]["score"]
     assert r["config"]["emb_crc32"] == zlib.crc32(got["emb"].tobytes())
+
+
+def test_bench_full_adds_the_figures_a_plain_run_skips():
+    """A plain run leaves the CPU baseline and the kernel-alone cross-check out (null in the line); --full runs both after the
+    timed region, and the two runs compute the same results."""
+    n = 6
+    plain = _bench("--batch", str(n), "--steps", "2", "--warmup", "1")
+    assert plain["config"]["full"] is False and plain["cpu_baseline"] is None
+    assert plain["roofline"]["kernel_ms_alone"] is None and plain["roofline"]["frac_alone"] is None
+    full = _bench("--batch", str(n), "--steps", "2", "--warmup", "1", "--full", TRUELY_CPU_BASELINE_SECONDS="1")
+    assert full["config"]["full"] is True
+    c = full["cpu_baseline"]
+    assert c["kind"] == "port" and c["unit"] == "frames/s" and c["cores"] >= 1 and c["value"] > 0 and c["batched"]["value"] > 0
+    assert full["roofline"]["kernel_ms_alone"] > 0 and full["roofline"]["frac_alone"] > 0
+    for k in ("emb_crc32", "score", "valid_faces", "candidates_per_step"):
+        assert full["config"][k] == plain["config"][k], k
 
 
 def test_rccl_needs_as_many_gpus_as_ranks():

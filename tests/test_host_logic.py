@@ -128,8 +128,8 @@ def test_bench_flop_model_matches_survey():
 
 
 def test_committed_bench_line_keeps_the_contract():
-    """The newest committed bench line (profiles/roundN_bench.json, written by the driver's command on the GPU box) carries every
-    field the measurement contract names, with consistent values: BASELINE's metric and workload, whole-job throughput =
+    """The newest committed bench line (profiles/roundN_bench.json, written by `bench.py --full` in tools/refresh_profiles.sh) carries
+    every field the measurement contract names, with consistent values: BASELINE's metric and workload, whole-job throughput =
     frames x steps / time, the roofline object of the dominant kernel (achieved = algorithmic FLOPs / measured launch duration,
     frac = achieved / peak) and the CPU baseline of the oracle port on a bounded sample."""
     import glob
@@ -186,6 +186,15 @@ def test_bench_multi_gpu_launch_is_correct_by_construction():
     for later in ("init_process_group(", "Engine(blob", ".to(dev)", "torch.cuda.Stream(", "pin_memory()"):
         assert at < body.index(later), later
     assert body.index("spawn_ranks(args)") < body.index("import torch")  # the parent never touches the GPU
+
+
+def test_bench_full_is_opt_in():
+    """A plain run does only what the headline figure needs; the CPU baseline and the kernel-alone cross-check run with --full."""
+    import bench
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--steps", "3"])
+    assert a.full is True and a.no_cpu_baseline is False and a.steps == 3
+    assert bench.parse_args(["--full", "--no-cpu-baseline"]).no_cpu_baseline is True
 
 
 def test_bench_dump_outputs(tmp_path):

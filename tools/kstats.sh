@@ -7,7 +7,7 @@ python - > gpurun_out/kstats.txt <<'PY'
 import csv, glob, json
 f = glob.glob("gpurun_out/kstats/**/*kernel_stats.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
-steps = 8 + 2 + 4   # timed + warm-up + the cross-check calls after the region
+steps = 8 + 2   # timed + warm-up (a run without --full makes no calls after the region)
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 print("ms per step, kernels above 0.05 ms/step; total %.3f" % (tot / 1e6 / steps))
 for r in rows:

@@ -10,14 +10,14 @@ make -C "$GRAFT_REPO_ROOT/truely-real-time-ai-generated-video-detection-framewor
 O=gpurun_out/refresh
 TUNE_LIB="$GRAFT_REPO_ROOT/truely-real-time-ai-generated-video-detection-framework-for-social-platforms_amd/libtruely_hip_tuning.so"   # TRL_* switches: tuning build only
 rm -rf $O && mkdir -p $O
-B="--no-cpu-baseline"
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench done"; cut -c1-300 $O/bench.json
+B="--full --no-cpu-baseline"   # every line keeps the kernel-alone cross-check; only the first and --config 0 run the CPU baseline
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; echo "bench done"; cut -c1-300 $O/bench.json
 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --in-flight 2 $B > $O/bench_inflight2.json 2> $O/bench_inflight2.err
 timeout -k 10 300 python bench.py --steps 400 --warmup 5 $B > $O/bench_sustained.json 2> $O/bench_sustained.err; echo "sustained done"
 timeout -k 10 300 python bench.py --config 2 --steps 10 --warmup 2 $B > $O/bench_config2.json 2> $O/bench_config2.err
 timeout -k 10 300 python bench.py --config 4 --steps 6 --warmup 2 $B > $O/bench_config4.json 2> $O/bench_config4.err
 timeout -k 10 300 python bench.py --prelu general --steps 20 --warmup 5 $B > $O/bench_prelu_general.json 2> $O/bench_prelu_general.err
-timeout -k 10 300 python bench.py --config 0 --steps 20 --warmup 5 > $O/bench_config0.json 2> $O/bench_config0.err
+timeout -k 10 300 python bench.py --config 0 --steps 20 --warmup 5 --full > $O/bench_config0.json 2> $O/bench_config0.err
 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 $B --embed-group 1 > $O/bench_embed_group1.json 2> $O/bench_embed_group1.err
 timeout -k 10 300 python bench.py --gpus 2 --backend gloo --mode streams --ingest nv12 --steps 6 $B > $O/bench_gloo2_streams_nv12.json 2> $O/bench_gloo2_streams_nv12.err
 timeout -k 10 300 python bench.py --ingest nv12 --steps 10 $B > $O/bench_ingest_nv12.json 2> $O/bench_ingest_nv12.err

@@ -96,6 +96,32 @@ int  trl_mtcnn_detect(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W
 int  trl_mtcnn_detect_landmarks(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W,
                                 float* d_boxes, float* d_probs, float* d_points, int32_t* d_counts, void* stream);
 
+/* `mtcnn.detect(frame, landmarks=...)` with the box order chosen: order 0 = largest area first (select_largest=True, what the
+ * two calls above return); order 1 = detect_face's own order (select_largest=False): the pick order of the final NMS, i.e.
+ * descending score -- the stage-3 rows as trl_debug_stage_boxes(3) shows them, truncated to max_faces.  d_points may be NULL.
+ * (ABI v7, additive) */
+int  trl_mtcnn_detect_ordered(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W, int order,
+                              float* d_boxes, float* d_probs, float* d_points, int32_t* d_counts, void* stream);
+
+/* facenet-pytorch 2.6.0 MTCNN.select_boxes on detect's output (d_boxes [n][max_faces][4], d_probs [n][max_faces], d_counts [n],
+ * in the order detect returned them): d_pick [n] receives the slot of the selected box of each frame, or -1 (no face, or no box
+ * over the threshold).  method 0 = 'largest' (key (x2-x1)*(y2-y1) in f32), 1 = 'probability', 2 = 'largest_over_threshold'
+ * (boxes with prob > threshold (f32), then the area key), 3 = 'center_weighted_size' (f64 area - center_weight * squared
+ * distance of the f32 box centre from (W/2, H/2)).  Ties go to the LAST tied box in detect's order (np.argsort(key)[::-1] of a
+ * stable sort).  No host synchronisation.  (ABI v7, additive) */
+int  trl_select_faces(trl_ctx* ctx, int n, const float* d_boxes, const float* d_probs, const int32_t* d_counts, int H, int W,
+                      int method, float threshold, double center_weight, int32_t* d_pick, void* stream);
+
+/* facenet-pytorch 2.6.0 extract_face for m boxes of the n u8 frames [n][H][W][3]: row r crops frame d_frame_of[r] around
+ * d_boxes [m][4] (x1,y1,x2,y2 f32) with `margin` pixels of the S x S output (margin*(x2-x1)/(S-margin) in f64, clamp, int()),
+ * resamples the crop to S x S as crop_resize does for the input kind -- resample 0 = torch.Tensor (imresample, area, .byte()),
+ * 1 = PIL image (Image.BILINEAR, Pillow's two 8-bit passes), 2 = numpy array (cv2.INTER_AREA) -- keeping the frame's channel
+ * order, and writes d_out [m][S][S][3] f32 (NHWC, what trl_facenet_embed reads): (v-127.5)/128 with post_process, else v.
+ * d_status [m] (may be NULL): 1 = face written, 0 = d_frame_of[r] < 0 (zeros written), -1 = empty crop (zeros written;
+ * facenet-pytorch raises).  1 <= S <= 1024, 0 <= margin < S.  No host synchronisation.  (ABI v7, additive) */
+int  trl_extract_faces(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W, const int32_t* d_frame_of, const float* d_boxes,
+                       int m, int S, int margin, int resample, int post_process, float* d_out, int32_t* d_status, void* stream);
+
 /* server/model.py:59  `facenet_model(face_tensor)`:  InceptionResnetV1(...).eval() forward.
  *   d_faces : f32 [n][h][w][3] NHWC, already scaled as model.py:58 does (to_tensor: /255)
  *   d_emb   : f32 [n][512], L2-normalised */

@@ -34,6 +34,9 @@ _SIGNATURES = {
     "trl_load_weights": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "trl_mtcnn_detect": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "trl_mtcnn_detect_landmarks": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "trl_mtcnn_detect_ordered": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "trl_select_faces": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, C.c_double, _vp, _vp]),
+    "trl_extract_faces": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "trl_facenet_embed": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "trl_detect_embed": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "trl_detect_crop": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

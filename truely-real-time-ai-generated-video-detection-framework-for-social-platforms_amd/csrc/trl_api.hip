@@ -381,7 +381,7 @@ static void collect_timings(trl_ctx* c) {
 extern "C" {
 
 static int mtcnn_detect_impl(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, float* d_points,
-                             int32_t* d_counts, void* stream);
+                             int32_t* d_counts, void* stream, int order = 0);
 
 int trl_mtcnn_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, int32_t* d_counts,
                      void* stream) {
@@ -394,8 +394,14 @@ int trl_mtcnn_detect_landmarks(trl_ctx* c, const uint8_t* d_frames, int n, int H
     return mtcnn_detect_impl(c, d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, stream);
 }
 
+int trl_mtcnn_detect_ordered(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, int order, float* d_boxes, float* d_probs,
+                             float* d_points, int32_t* d_counts, void* stream) {
+    if (order != 0 && order != 1) { trl_set_error("bad box order %d (0 = area, 1 = detection order)", order); return TRL_ERR_INVALID; }
+    return mtcnn_detect_impl(c, d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, stream, order);
+}
+
 static int mtcnn_detect_impl(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, float* d_points,
-                             int32_t* d_counts, void* stream) {
+                             int32_t* d_counts, void* stream, int order) {
     TRL_CHECK(check_call(c, d_frames, n, H, W));
     if (!d_boxes || !d_probs || !d_counts) { trl_set_error("null output"); return TRL_ERR_INVALID; }
     hipStream_t s = (hipStream_t)stream;
@@ -411,7 +417,7 @@ static int mtcnn_detect_impl(trl_ctx* c, const uint8_t* d_frames, int n, int H, 
         TRL_HIP(hipMemsetAsync(d_boxes, 0, (size_t)n * c->cfg.max_faces * 16, s));
         TRL_HIP(hipMemsetAsync(d_probs, 0, (size_t)n * c->cfg.max_faces * 4, s));
         if (d_points) TRL_HIP(hipMemsetAsync(d_points, 0, (size_t)n * c->cfg.max_faces * 40, s));
-        TRL_CHECK(trl_cascade_finish(c, d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, box0, prob0, rect, valid, nullptr, s));
+        TRL_CHECK(trl_cascade_finish(c, d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, box0, prob0, rect, valid, nullptr, s, order));
         TRL_HIP(hipEventRecord(c->ev_call1, s));
         TRL_CHECK(trl_gate_record(c, s));
         TRL_HIP(hipStreamSynchronize(s));             // the call's one host synchronisation

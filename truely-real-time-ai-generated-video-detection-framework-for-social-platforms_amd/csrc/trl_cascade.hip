@@ -854,8 +854,9 @@ __global__ __launch_bounds__(1024) void k_stage3_post(int lds_cap, int capF, int
     if (threadIdx.x == 0) n3[f] = nk;
 }
 
-// MTCNN.detect(select_largest=True) ordering + model.py:49-54
-__global__ __launch_bounds__(64) void k_select(int capF, int max_faces, int W, int H, const int32_t* __restrict__ n3,
+// MTCNN.detect ordering + model.py:49-54.  order 0: select_largest=True (area order); order 1: select_largest=False, the rows in
+// detect_face's order (the pick order of the final NMS), i.e. rank = row.  box0 / rect / valid / pts0 always follow rank 0.
+__global__ __launch_bounds__(64) void k_select(int capF, int max_faces, int W, int H, int order, const int32_t* __restrict__ n3,
                                                const float* __restrict__ s3_box, const float* __restrict__ s3_pts,
                                                float* __restrict__ boxes, float* __restrict__ probs, float* __restrict__ points,
                                                int32_t* __restrict__ counts, float* __restrict__ box0, float* __restrict__ prob0,
@@ -865,11 +866,14 @@ __global__ __launch_bounds__(64) void k_select(int capF, int max_faces, int W, i
     const float* b = s3_box + (size_t)f * capF * 5;
     // rank of r in np.argsort(area)[::-1] with stable-sort tie semantics: descending area, ties -> higher index first
     for (int r = threadIdx.x; r < n; r += blockDim.x) {
-        const float ar = (b[5 * r + 2] - b[5 * r]) * (b[5 * r + 3] - b[5 * r + 1]);
-        int rank = 0;
-        for (int q = 0; q < n; q++) {
-            const float aq = (b[5 * q + 2] - b[5 * q]) * (b[5 * q + 3] - b[5 * q + 1]);
-            rank += (aq > ar) || (aq == ar && q > r);
+        int rank = r;
+        if (order == 0) {
+            const float ar = (b[5 * r + 2] - b[5 * r]) * (b[5 * r + 3] - b[5 * r + 1]);
+            rank = 0;
+            for (int q = 0; q < n; q++) {
+                const float aq = (b[5 * q + 2] - b[5 * q]) * (b[5 * q + 3] - b[5 * q + 1]);
+                rank += (aq > ar) || (aq == ar && q > r);
+            }
         }
         if (boxes && rank < max_faces) {
             float* o = boxes + ((size_t)f * max_faces + rank) * 4;
@@ -968,20 +972,11 @@ __global__ __launch_bounds__(256) void k_crop_area_std(const uint8_t* __restrict
     if (!valid[f]) { o[3 * p] = 0.f; o[3 * p + 1] = 0.f; o[3 * p + 2] = 0.f; return; }
     const int x0 = rect[4 * f], y0 = rect[4 * f + 1], iw = rect[4 * f + 2] - x0, ih = rect[4 * f + 3] - y0;
     const int oy = p / S, ox = p - oy * S;
-    const int ys = (int)(((long long)oy * ih) / S), ye = (int)((((long long)oy + 1) * ih + S - 1) / S);
-    const int xs = (int)(((long long)ox * iw) / S), xe = (int)((((long long)ox + 1) * iw + S - 1) / S);
-    unsigned s0 = 0, s1 = 0, s2 = 0;
-    const uint8_t* fp = frames + (size_t)f * H * W * 3;
-    for (int y = ys; y < ye; y++) {
-        const uint8_t* q = fp + ((size_t)(y0 + y) * W + x0 + xs) * 3;
-        for (int x = xs; x < xe; x++, q += 3) { s0 += q[0]; s1 += q[1]; s2 += q[2]; }
-    }
-    const float kh = (float)(ye - ys), kw = (float)(xe - xs);
-    const float b0 = (float)(unsigned char)((float)s0 / kh / kw), b1 = (float)(unsigned char)((float)s1 / kh / kw),
-                b2 = (float)(unsigned char)((float)s2 / kh / kw);
-    o[3 * p + (rgb ? 2 : 0)] = (b0 - 127.5f) / 128.0f;
-    o[3 * p + 1] = (b1 - 127.5f) / 128.0f;
-    o[3 * p + (rgb ? 0 : 2)] = (b2 - 127.5f) / 128.0f;
+    float b[3];
+    trl_area_pixel(frames + (size_t)f * H * W * 3, W, x0, y0, iw, ih, S, ox, oy, b);
+    o[3 * p + (rgb ? 2 : 0)] = (b[0] - 127.5f) / 128.0f;
+    o[3 * p + 1] = (b[1] - 127.5f) / 128.0f;
+    o[3 * p + (rgb ? 0 : 2)] = (b[2] - 127.5f) / 128.0f;
 }
 
 // SURVEY 8(f)-4 "landmark-aligned" embedding mode (trl_config.embed_mode 3; this project's own definition, restated in
@@ -1402,10 +1397,11 @@ int trl_stage_net(trl_ctx* c, int net, const uint8_t* d_frames, int H, int W, co
 }
 
 int trl_cascade_finish(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, float* d_points,
-                       int32_t* d_counts, float* d_box0, float* d_prob0, int32_t* d_rect, uint8_t* d_valid, float* d_pts0, hipStream_t s) {
+                       int32_t* d_counts, float* d_box0, float* d_prob0, int32_t* d_rect, uint8_t* d_valid, float* d_pts0, hipStream_t s,
+                       int order) {
     (void)d_frames;
     CascadeBufs& B = c->cb;
-    k_select<<<n, 64, 0, s>>>(B.capF, c->cfg.max_faces, W, H, B.n3, B.s3_box, B.s3_pts, d_boxes, d_probs, d_points, d_counts, d_box0, d_prob0,
+    k_select<<<n, 64, 0, s>>>(B.capF, c->cfg.max_faces, W, H, order, B.n3, B.s3_box, B.s3_pts, d_boxes, d_probs, d_points, d_counts, d_box0, d_prob0,
                               d_rect, d_valid, d_pts0);
     TRL_LAUNCH_CHECK();
     // overflow flags + stage totals travel to pinned host memory behind the kernels; trl_cascade_check reads them after the

@@ -216,4 +216,20 @@ __device__ __forceinline__ float trl_wave_dot512(const float* a, const float* b,
     for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
     return s;
 }
+// facenet-pytorch extract_face() for tensor input, one output pixel (ox, oy): imresample (area = adaptive average pooling) of the
+// iw x ih crop at (x0, y0) of the u8 frame fp [.][W][3] to S x S -- bins [floor(o*n/S), ceil((o+1)*n/S)), (float)sum / kh / kw --
+// then .byte() (truncation).  v receives the three channels in the frame's order.  Shared by k_crop_area_std and k_extract.
+__device__ __forceinline__ void trl_area_pixel(const uint8_t* fp, int W, int x0, int y0, int iw, int ih, int S, int ox, int oy, float v[3]) {
+    const int ys = (int)(((long long)oy * ih) / S), ye = (int)((((long long)oy + 1) * ih + S - 1) / S);
+    const int xs = (int)(((long long)ox * iw) / S), xe = (int)((((long long)ox + 1) * iw + S - 1) / S);
+    unsigned s0 = 0, s1 = 0, s2 = 0;
+    for (int y = ys; y < ye; y++) {
+        const uint8_t* q = fp + ((size_t)(y0 + y) * W + x0 + xs) * 3;
+        for (int x = xs; x < xe; x++, q += 3) { s0 += q[0]; s1 += q[1]; s2 += q[2]; }
+    }
+    const float kh = (float)(ye - ys), kw = (float)(xe - xs);
+    v[0] = (float)(unsigned char)((float)s0 / kh / kw);
+    v[1] = (float)(unsigned char)((float)s1 / kh / kw);
+    v[2] = (float)(unsigned char)((float)s2 / kh / kw);
+}
 #endif

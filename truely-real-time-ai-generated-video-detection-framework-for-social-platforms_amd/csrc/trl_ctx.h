@@ -145,7 +145,8 @@ size_t trl_pnet_generic_bytes(int nf, int h, int w);
 // cascade (trl_cascade.hip)
 int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, hipStream_t s, int resume = 0);
 int trl_cascade_finish(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, float* d_points,
-                       int32_t* d_counts, float* d_box0, float* d_prob0, int32_t* d_rect, uint8_t* d_valid, float* d_pts0, hipStream_t s);
+                       int32_t* d_counts, float* d_box0, float* d_prob0, int32_t* d_rect, uint8_t* d_valid, float* d_pts0, hipStream_t s,
+                       int order = 0);   // order: 0 = area (select_largest=True), 1 = detection order
 int trl_cascade_check(trl_ctx* c, int n, int* retry);   // after the call's stream synchronisation
 int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* h_caps, int L, const int32_t* h_counts, const void* h_rows,
                       const float* h_logits, float* h_pts, float* d_boxes, float* d_probs, float* d_points, int32_t* d_counts, float* d_box0,

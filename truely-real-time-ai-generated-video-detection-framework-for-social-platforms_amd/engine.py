@@ -17,6 +17,11 @@ from . import _lib
 from . import weights as _weights
 
 
+# trl_select_faces methods / trl_extract_faces resamplers (include/truely_hip.h)
+SELECTION_METHODS = {"largest": 0, "probability": 1, "largest_over_threshold": 2, "center_weighted_size": 3}
+RESAMPLERS = {"torch": 0, "pil": 1, "cv2": 2}
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
@@ -89,15 +94,21 @@ class Engine:
         return frames.to(self.device, non_blocking=True).contiguous()
 
     # server/model.py:47 for a batch
-    def mtcnn_detect(self, frames, landmarks: bool = False):
+    def mtcnn_detect(self, frames, landmarks: bool = False, select_largest: bool = True):
         """(boxes [n,max_faces,4], probs [n,max_faces], counts [n]) and, with ``landmarks=True``, points [n,max_faces,10]
-        (x0..x4, y0..y4) as the fourth element -- `mtcnn.detect(frame, landmarks=True)`."""
+        (x0..x4, y0..y4) as the fourth element -- `mtcnn.detect(frame, landmarks=True)`.  ``select_largest=False``: the boxes in
+        detect_face's order (descending score) instead of largest area first."""
         fr = self._frames(frames)
         n, H, W, _ = fr.shape
         mf = self.cfg.max_faces
         boxes = torch.empty((n, mf, 4), dtype=torch.float32, device=self.device)
         probs = torch.empty((n, mf), dtype=torch.float32, device=self.device)
         counts = torch.empty((n,), dtype=torch.int32, device=self.device)
+        if not select_largest:
+            points = torch.empty((n, mf, 10), dtype=torch.float32, device=self.device) if landmarks else None
+            _lib.check(self.lib.trl_mtcnn_detect_ordered(self._h, _ptr(fr), n, H, W, 1, _ptr(boxes), _ptr(probs), _ptr(points),
+                                                         _ptr(counts), self._stream()))
+            return (boxes, probs, counts, points) if landmarks else (boxes, probs, counts)
         if landmarks:
             points = torch.empty((n, mf, 10), dtype=torch.float32, device=self.device)
             _lib.check(self.lib.trl_mtcnn_detect_landmarks(self._h, _ptr(fr), n, H, W, _ptr(boxes), _ptr(probs), _ptr(points),
@@ -105,6 +116,74 @@ class Engine:
             return boxes, probs, counts, points
         _lib.check(self.lib.trl_mtcnn_detect(self._h, _ptr(fr), n, H, W, _ptr(boxes), _ptr(probs), _ptr(counts), self._stream()))
         return boxes, probs, counts
+
+    # facenet-pytorch MTCNN.select_boxes on detect's output (device tensors as mtcnn_detect returns them)
+    def select_faces(self, boxes: torch.Tensor, probs: torch.Tensor, counts: torch.Tensor, H: int, W: int, method: str = "largest",
+                     threshold: float = 0.9, center_weight: float = 2.0) -> torch.Tensor:
+        """pick [n] int32: the slot of the box select_boxes keeps in each frame, -1 for none.  boxes [n,max_faces,4], probs
+        [n,max_faces], counts [n] in detect's order; ties go to the last tied box.  No host synchronisation."""
+        mf = self.cfg.max_faces
+        boxes = boxes.to(self.device, torch.float32).contiguous()
+        probs = probs.to(self.device, torch.float32).contiguous()
+        counts = counts.to(self.device, torch.int32).contiguous()
+        n = counts.shape[0]
+        if tuple(boxes.shape) != (n, mf, 4) or tuple(probs.shape) != (n, mf):
+            raise ValueError(f"boxes / probs must be ({n}, {mf}, 4) / ({n}, {mf})")
+        pick = torch.empty((n,), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.trl_select_faces(self._h, n, _ptr(boxes), _ptr(probs), _ptr(counts), int(H), int(W), SELECTION_METHODS[method],
+                                             float(threshold), float(center_weight), _ptr(pick), self._stream()))
+        return pick
+
+    # facenet-pytorch extract_face for given boxes: faces [m, 3, S, S] f32 (a view of NHWC storage) + status [m] (1 face, 0 frame
+    # index -1, -1 empty crop)
+    def extract_boxes(self, frames, frame_of: torch.Tensor, boxes: torch.Tensor, image_size: int = 160, margin: int = 0,
+                      resample: str = "torch", post_process: bool = True):
+        fr = self._frames(frames)
+        n, H, W, _ = fr.shape
+        frame_of = frame_of.to(self.device, torch.int32).contiguous()
+        boxes = boxes.to(self.device, torch.float32).reshape(-1, 4).contiguous()
+        m, S = frame_of.shape[0], int(image_size)
+        if boxes.shape[0] != m:
+            raise ValueError("one box per row of frame_of")
+        out = torch.empty((m, S, S, 3), dtype=torch.float32, device=self.device)
+        status = torch.empty((m,), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.trl_extract_faces(self._h, _ptr(fr), n, H, W, _ptr(frame_of), _ptr(boxes), m, S, int(margin),
+                                              RESAMPLERS[resample], int(bool(post_process)), _ptr(out), _ptr(status), self._stream()))
+        return out.permute(0, 3, 1, 2), status
+
+    def extract_faces(self, frames, image_size: int = 160, margin: int = 0, resample: str = "torch", post_process: bool = True,
+                      keep_all: bool = False, select_largest: bool = True, selection_method: str | None = None) -> dict:
+        """facenet-pytorch ``MTCNN(image_size, margin, post_process, select_largest, selection_method, keep_all)(frames)`` for a
+        batch, device-resident.  resample: the input kind crop_resize sees ('torch' tensor, 'pil' image, 'cv2' numpy array).
+        Returns device tensors: ``faces`` [m, 3, S, S] f32 (a permuted view of NHWC rows, the layout facenet_embed reads),
+        ``frame`` [m] (frame of each row, -1 for none), ``box`` [m, 4], ``prob`` [m], ``status`` [m] (1 face, 0 none, -1 empty crop:
+        the library raises), and ``valid`` [n] uint8 (keep_all=False: row i is frame i) or ``counts`` [n] (keep_all=True: the
+        rows of every face, frame by frame in detect's order).  keep_all=False makes no host synchronisation after detect's;
+        keep_all=True makes one, for the number of faces."""
+        fr = self._frames(frames)
+        n = fr.shape[0]
+        H, W = fr.shape[1], fr.shape[2]
+        boxes, probs, counts = self.mtcnn_detect(fr, select_largest=select_largest)
+        d = self.device
+        if keep_all:
+            total = int(counts.sum().item())                  # the one synchronisation: the face count sizes the outputs
+            c64 = counts.long()
+            frame = torch.repeat_interleave(torch.arange(n, device=d), c64, output_size=total)
+            slot = torch.arange(total, device=d) - (torch.cumsum(c64, 0) - c64)[frame]
+            box, prob, frame_of = boxes[frame, slot], probs[frame, slot], frame.int()
+        else:
+            method = selection_method or ("largest" if select_largest else "probability")
+            pick = self.select_faces(boxes, probs, counts, H, W, method)
+            idx, rows = pick.clamp(min=0).long(), torch.arange(n, device=d)
+            box, prob = boxes[rows, idx], probs[rows, idx]
+            frame_of = torch.where(pick >= 0, rows.int(), torch.full_like(pick, -1))
+        faces, status = self.extract_boxes(fr, frame_of, box, image_size, margin, resample, post_process)
+        out = {"faces": faces, "frame": frame_of, "box": box, "prob": prob, "status": status}
+        if keep_all:
+            out["counts"] = counts
+        else:
+            out["valid"] = (status == 1).to(torch.uint8)
+        return out
 
     # server/model.py:59 for a batch; faces f32 (n, h, w, 3) NHWC in [0,1]
     def facenet_embed(self, faces: torch.Tensor) -> torch.Tensor:

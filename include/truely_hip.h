@@ -39,7 +39,9 @@ typedef enum {
     TRL_ERR_CAPACITY = -4,  /* (ABI <= 6: a candidate list exceeded its configured capacity.  Since ABI 7 no input can
                              *  produce it: lists grow to what the content needs, as detect_face() has no limit;
                              *  trl_jpeg_header returns it for a buffer that is too small) */
-    TRL_ERR_STATE = -5      /* call order (e.g. no weights loaded) */
+    TRL_ERR_STATE = -5      /* call order (e.g. no weights loaded).  A re-run bound also reports it ("candidate capacities
+                             *  did not converge"), which no input reaches: each re-run raises the one capacity that
+                             *  overflowed to the measured need, and there are five capacities (trl_api.hip) */
 } trl_status;
 
 typedef struct trl_ctx trl_ctx;
@@ -307,9 +309,10 @@ int  trl_debug_crop_resize(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, 
 /* embed_mode 3's crop alone: d_pts [n][10] = x0..x4, y0..y4 per frame -> f32 [n][S][S][3] */
 int  trl_debug_crop_aligned(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W, const float* d_pts,
                             const uint8_t* d_valid, int S, int rgb, float* d_faces, void* stream);
-/* Time (ms, HIP events on the call's stream) of the last trl_detect_embed call:
+/* Time (ms, HIP events on the call's stream) of the last trl_detect_embed / trl_detect_crop / trl_mtcnn_detect* call:
  * out[0] = PNet kernel (fused: the one persistent launch; generic: sum over levels),
- * out[1] = whole call, out[2] = number of PNet launches timed, out[3] = pyramid kernel. */
+ * out[1] = whole call, every attempt of a re-run call included (before this library version trl_mtcnn_detect* timed only the
+ * last attempt), out[2] = number of PNet launches timed, out[3] = pyramid kernel. */
 int  trl_debug_timings(trl_ctx* ctx, float* out4);
 /* R-Net / O-Net candidate totals of the last call over the whole batch: h_out2[0] = boxes that entered stage 2, [1] = stage 3 */
 int  trl_debug_stage_totals(trl_ctx* ctx, int32_t* h_out2);

@@ -350,6 +350,50 @@ def test_two_contexts_on_two_threads(blob):
             assert np.array_equal(got[j][k], ref[j][k]), (j, k)
 
 
+def test_first_runs_on_two_threads_share_one_run_context(engine, blob, tmp_path, monkeypatch):
+    """Two request threads make their first run() on a fresh engine at the same time: run() creates the engine's _RunCtx (second
+    context, streams, pinned ring) once, and both requests return the single-threaded score."""
+    import threading
+    from truely_amd import model, video_io
+    from truely_amd.engine import Engine
+    monkeypatch.setenv("TRUELY_WRITE_OUTPUT", "0")
+    H, W, fps = 180, 320, 30
+    src = str(tmp_path / "in.trlv")
+    video_io.write_raw(src, truely_amd.synthetic.synthetic_frames(40, H, W, seed=3), fps)
+    ref = model.run(src, str(tmp_path / "ref.avi"), engine=engine)
+    created = []
+
+    class CountingCtx(model._RunCtx):
+        def __init__(self, eng):
+            created.append(eng)
+            super().__init__(eng)
+
+    monkeypatch.setattr(model, "_RunCtx", CountingCtx)
+    eng = Engine(blob)
+    start = threading.Barrier(2)
+    scores, errs = [None, None], []
+
+    def worker(j):
+        try:
+            torch.cuda.set_device(eng.device)
+            start.wait()
+            scores[j] = model.run(src, str(tmp_path / f"out{j}.avi"), engine=eng)
+        except BaseException as e:
+            errs.append(e)
+
+    ths = [threading.Thread(target=worker, args=(j,)) for j in range(2)]
+    for t in ths:
+        t.start()
+    for t in ths:
+        t.join()
+    try:
+        assert not errs, errs
+        assert scores == [ref, ref]
+        assert created == [eng] and isinstance(eng.__dict__["_run_ctx"], CountingCtx)
+    finally:
+        eng.close()
+
+
 def test_analyze_video_with_batches_in_flight(blob):
     """model.analyze_video(engines=[e0, e1]): two contexts, two streams, two threads -- same bits as the sequential call."""
     from truely_amd.engine import Engine

@@ -328,21 +328,14 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
 }
 
 // ---- hot path ---------------------------------------------------------------------------------------
-// Every attempt raises the one capacity it found too small to what the content needs (level lists -> frame lists -> R-Net batch
-// -> O-Net batch, plus the spill workspace), so a call converges in at most a handful; the bound only guards against a bug.
-enum { TRL_MAX_ATTEMPTS = 12 };
-
-// A context holds at most one queued call (trl_detect_embed_begin .. _end); anything else that touches its workspaces meanwhile
-// would corrupt that call silently.
-static int check_idle(trl_ctx* c) {
+int trl_check_idle(trl_ctx* c) {
     if (!c) { trl_set_error("null context"); return TRL_ERR_INVALID; }
     if (c->pend.active) { trl_set_error("the context has a call in flight: trl_detect_embed_end() first"); return TRL_ERR_STATE; }
     return TRL_OK;
 }
 
 static int check_call(trl_ctx* c, const void* frames, int n, int H, int W) {
-    if (!c) { trl_set_error("null context"); return TRL_ERR_INVALID; }
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (!c->have_weights) { trl_set_error("trl_load_weights has not been called"); return TRL_ERR_STATE; }
     if (!frames || n <= 0 || n > 65535 || H < 12 || W < 12 || H > 16383 || W > 16383) {   // n: grid.y carries the frame index in several kernels
         trl_set_error("bad frame batch n=%d H=%d W=%d (1..65535 frames of 12..16383 px per side)", n, H, W);
@@ -378,117 +371,76 @@ static void collect_timings(trl_ctx* c) {
     }
 }
 
-extern "C" {
-
-static int mtcnn_detect_impl(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, float* d_points,
-                             int32_t* d_counts, void* stream, int order = 0);
-
-int trl_mtcnn_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, int32_t* d_counts,
-                     void* stream) {
-    return mtcnn_detect_impl(c, d_frames, n, H, W, d_boxes, d_probs, nullptr, d_counts, stream);
-}
-
-int trl_mtcnn_detect_landmarks(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs,
-                               float* d_points, int32_t* d_counts, void* stream) {
-    if (!d_points) { trl_set_error("null output"); return TRL_ERR_INVALID; }
-    return mtcnn_detect_impl(c, d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, stream);
-}
-
-int trl_mtcnn_detect_ordered(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, int order, float* d_boxes, float* d_probs,
-                             float* d_points, int32_t* d_counts, void* stream) {
-    if (order != 0 && order != 1) { trl_set_error("bad box order %d (0 = area, 1 = detection order)", order); return TRL_ERR_INVALID; }
-    return mtcnn_detect_impl(c, d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, stream, order);
-}
-
-static int mtcnn_detect_impl(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, float* d_points,
-                             int32_t* d_counts, void* stream, int order) {
-    TRL_CHECK(check_call(c, d_frames, n, H, W));
-    if (!d_boxes || !d_probs || !d_counts) { trl_set_error("null output"); return TRL_ERR_INVALID; }
-    hipStream_t s = (hipStream_t)stream;
-    TRL_HIP(hipSetDevice(c->cfg.device));
-    c->scratch_after_cascade = 0;
-    for (int attempt = 0;; attempt++) {
-        TRL_HIP(hipEventRecord(c->ev_call0, s));
-        TRL_CHECK(trl_cascade_detect(c, d_frames, n, H, W, s, attempt ? c->resume_stage : 0));
-        // scratch for the model.py-only outputs
-        float* box0 = (float*)c->arena.alloc((size_t)n * 16); float* prob0 = (float*)c->arena.alloc((size_t)n * 4);
-        int32_t* rect = (int32_t*)c->arena.alloc((size_t)n * 16); uint8_t* valid = (uint8_t*)c->arena.alloc((size_t)n);
-        if (!valid) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
-        TRL_HIP(hipMemsetAsync(d_boxes, 0, (size_t)n * c->cfg.max_faces * 16, s));
-        TRL_HIP(hipMemsetAsync(d_probs, 0, (size_t)n * c->cfg.max_faces * 4, s));
-        if (d_points) TRL_HIP(hipMemsetAsync(d_points, 0, (size_t)n * c->cfg.max_faces * 40, s));
-        TRL_CHECK(trl_cascade_finish(c, d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, box0, prob0, rect, valid, nullptr, s, order));
-        TRL_HIP(hipEventRecord(c->ev_call1, s));
-        TRL_CHECK(trl_gate_record(c, s));
-        TRL_HIP(hipStreamSynchronize(s));             // the call's one host synchronisation
-        int retry = 0;
-        TRL_CHECK(trl_cascade_check(c, n, &retry));
-        c->last_attempts = attempt + 1;
-        if (!retry) break;
-        if (attempt >= TRL_MAX_ATTEMPTS - 1) { trl_set_error("candidate capacities did not converge"); return TRL_ERR_STATE; }
-    }
-    collect_timings(c);
-    return TRL_OK;
-}
-
-int trl_facenet_embed(trl_ctx* c, const float* d_faces, int n, int h, int w, float* d_emb, void* stream) {
-    if (!c || !c->have_weights) { trl_set_error("context without weights"); return TRL_ERR_STATE; }
-    TRL_CHECK(check_idle(c));
-    if (!d_faces || !d_emb || n <= 0 || h < 75 || w < 75) { trl_set_error("bad face batch n=%d %dx%d (min 75x75)", n, h, w); return TRL_ERR_INVALID; }
-    TRL_HIP(hipSetDevice(c->cfg.device));
-    c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, (size_t)n * ((size_t)h * w * 110 + 400000) * 4 + (8u << 20)));
-    TRL_CHECK(trl_run_facenet(c, d_faces, n, h, w, nullptr, d_emb, (hipStream_t)stream));
-    return trl_gate_record(c, (hipStream_t)stream);
-}
-
-// model.py:47-58 (detect, largest box, crop + resize) and optionally :59 (embed).  d_faces_out != null: the crops are written there
-// (caller-owned [n][S][S][3] f32) and the embedder is NOT run (trl_detect_crop); else they live in scratch and are embedded.
-// Split in two so a host thread can keep several contexts busy: detect_embed_enqueue() queues ONE attempt of the call on the
-// stream and returns; detect_embed_wait() is the call's one host synchronisation, the capacity check and -- rarely -- the re-run.
-static int detect_embed_enqueue(trl_ctx* c) {
+// Every cascade entry point (trl_mtcnn_detect*, trl_detect_embed*, trl_detect_crop*) is one call in c->pend: call_begin()
+// validates it and queues its first attempt, call_wait() is the call's one host synchronisation, the capacity check and --
+// rarely -- the re-run; the blocking entry points do both.  call_enqueue() queues one attempt on the call's stream: the cascade
+// (from the stage the last check chose), then the outputs of the call's kind.
+static int call_enqueue(trl_ctx* c) {
     const trl_ctx::Pending& q = c->pend;
     hipStream_t s = (hipStream_t)q.stream;
     const int n = q.n, H = q.H, W = q.W;
-    const int S = c->cfg.embed_mode == 0 ? 80 : 160;
-    if (!q.attempt) TRL_HIP(hipEventRecord(c->ev_call0, s));
+    if (!q.attempt) TRL_HIP(hipEventRecord(c->ev_call0, s));   // trl_debug_timings: out[1] covers every attempt of the call
     TRL_CHECK(trl_cascade_detect(c, q.frames, n, H, W, s, q.attempt ? c->resume_stage : 0));
-    float* pts0 = nullptr;
-    if (c->cfg.embed_mode == 3) {                // the largest face's landmarks steer the aligned crop
-        pts0 = (float*)c->arena.alloc((size_t)n * 40);
-        if (!pts0) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
+    if (q.kind == trl_ctx::Pending::DETECT) {
+        // model.py's per-frame outputs are not asked for: scratch behind the lists
+        float* box0 = (float*)c->arena.alloc((size_t)n * 16); float* prob0 = (float*)c->arena.alloc((size_t)n * 4);
+        int32_t* rect = (int32_t*)c->arena.alloc((size_t)n * 16); uint8_t* valid = (uint8_t*)c->arena.alloc((size_t)n);
+        if (!valid) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
+        TRL_HIP(hipMemsetAsync(q.boxes, 0, (size_t)n * c->cfg.max_faces * 16, s));
+        TRL_HIP(hipMemsetAsync(q.probs, 0, (size_t)n * c->cfg.max_faces * 4, s));
+        if (q.points) TRL_HIP(hipMemsetAsync(q.points, 0, (size_t)n * c->cfg.max_faces * 40, s));
+        TRL_CHECK(trl_cascade_finish(c, q.frames, n, H, W, q.boxes, q.probs, q.points, q.counts, box0, prob0, rect, valid, nullptr, s, q.order));
+    } else {
+        // model.py:47-58 (detect, largest box, crop + resize) and, EMBED, :59 (embed).  CROP: the crops go to the caller's faces_out
+        // and the embedder does not run; EMBED: they live in scratch and are embedded.
+        const int S = c->cfg.embed_mode == 0 ? 80 : 160;
+        float* pts0 = nullptr;
+        if (c->cfg.embed_mode == 3) {                // the largest face's landmarks steer the aligned crop
+            pts0 = (float*)c->arena.alloc((size_t)n * 40);
+            if (!pts0) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
+        }
+        TRL_CHECK(trl_cascade_finish(c, q.frames, n, H, W, nullptr, nullptr, nullptr, nullptr, q.box, q.prob, q.rect, q.valid, pts0, s));
+        float* faces = q.faces_out;
+        if (!faces) {
+            c->scratch.reset();                      // stream order: the cascade's kernels are done with it before these run
+            faces = (float*)c->scratch.alloc((size_t)n * S * S * 3 * 4);
+            if (!faces) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
+        }
+        if (c->cfg.embed_mode == 0) TRL_CHECK(trl_launch_crop_resize80(q.frames, n, H, W, q.rect, q.valid, faces, s));
+        else if (c->cfg.embed_mode == 3) TRL_CHECK(trl_launch_crop_aligned(q.frames, n, H, W, pts0, q.valid, S, true, faces, s));
+        else TRL_CHECK(trl_launch_crop_area_std(q.frames, n, H, W, q.rect, q.valid, S, c->cfg.embed_mode == 2, faces, s));
+        if (!q.faces_out) TRL_CHECK(trl_run_facenet(c, faces, n, S, S, q.valid, q.emb, s));
     }
-    TRL_CHECK(trl_cascade_finish(c, q.frames, n, H, W, nullptr, nullptr, nullptr, nullptr, q.box, q.prob, q.rect, q.valid, pts0, s));
-    float* faces = q.faces_out;
-    if (!faces) {
-        c->scratch.reset();                      // stream order: the cascade's kernels are done with it before these run
-        faces = (float*)c->scratch.alloc((size_t)n * S * S * 3 * 4);
-        if (!faces) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
-    }
-    if (c->cfg.embed_mode == 0) TRL_CHECK(trl_launch_crop_resize80(q.frames, n, H, W, q.rect, q.valid, faces, s));
-    else if (c->cfg.embed_mode == 3) TRL_CHECK(trl_launch_crop_aligned(q.frames, n, H, W, pts0, q.valid, S, true, faces, s));
-    else TRL_CHECK(trl_launch_crop_area_std(q.frames, n, H, W, q.rect, q.valid, S, c->cfg.embed_mode == 2, faces, s));
-    if (!q.faces_out) TRL_CHECK(trl_run_facenet(c, faces, n, S, S, q.valid, q.emb, s));
     TRL_HIP(hipEventRecord(c->ev_call1, s));
     TRL_CHECK(trl_gate_record(c, s));
     return TRL_OK;
 }
 
-static int detect_embed_begin(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
-                              uint8_t* d_valid, float* d_emb, float* d_faces_out, void* stream) {
-    TRL_CHECK(check_call(c, d_frames, n, H, W));
-    if (c->pend.active) { trl_set_error("the context already has a call in flight: trl_detect_embed_end() first"); return TRL_ERR_STATE; }
-    if (!d_box || !d_prob || !d_rect || !d_valid || (!d_emb && !d_faces_out)) { trl_set_error("null output"); return TRL_ERR_INVALID; }
+// q: the call the entry point describes (trl_ctx::Pending: kind, frames, stream, outputs)
+static int call_begin(trl_ctx* c, const trl_ctx::Pending& q) {
+    TRL_CHECK(check_call(c, q.frames, q.n, q.H, q.W));
+    if (q.kind == trl_ctx::Pending::DETECT ? !(q.boxes && q.probs && q.counts) : !(q.box && q.prob && q.rect && q.valid && (q.emb || q.faces_out))) {
+        trl_set_error("null output");
+        return TRL_ERR_INVALID;
+    }
     TRL_HIP(hipSetDevice(c->cfg.device));
     const int S = c->cfg.embed_mode == 0 ? 80 : 160;
-    c->scratch_after_cascade = d_faces_out ? 0 : (size_t)n * ((size_t)S * S * 110 + 400000) * 4 + (8u << 20);
-    c->pend = trl_ctx::Pending{true, 0, d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, d_emb, d_faces_out, stream};
-    const int st = detect_embed_enqueue(c);
+    c->scratch_after_cascade = q.kind == trl_ctx::Pending::EMBED ? (size_t)q.n * ((size_t)S * S * 110 + 400000) * 4 + (8u << 20) : 0;
+    c->pend = q;
+    c->pend.active = true;
+    c->pend.attempt = 0;
+    const int st = call_enqueue(c);
     if (st != TRL_OK) c->pend.active = false;
     return st;
 }
 
-static int detect_embed_wait(trl_ctx* c) {
+// Every attempt that overflows a capacity raises that capacity to the need the attempt measured (trl_cascade_check), and a
+// stage's need is measured once the stages in front of it ran on complete lists.  There are five capacities -- level lists,
+// frame lists, spill workspace, R-Net batch, O-Net batch -- so a call converges in at most six attempts: the bound is never
+// reached by any input (detect_face() has no candidate limit, and neither has this call), it only turns a bug into an error.
+enum { TRL_MAX_ATTEMPTS = 12 };
+
+static int call_wait(trl_ctx* c) {
     if (!c) { trl_set_error("null context"); return TRL_ERR_INVALID; }
     if (!c->pend.active) { trl_set_error("no call in flight on this context"); return TRL_ERR_STATE; }
     TRL_HIP(hipSetDevice(c->cfg.device));
@@ -499,49 +451,91 @@ static int detect_embed_wait(trl_ctx* c) {
         int retry = 0;
         if ((st = trl_cascade_check(c, c->pend.n, &retry)) != TRL_OK) break;
         c->last_attempts = ++c->pend.attempt;
-        if (!retry) break;                            // (a retry re-runs the call with larger R-/O-Net batch capacities)
+        if (!retry) break;
         if (c->pend.attempt >= TRL_MAX_ATTEMPTS) { trl_set_error("candidate capacities did not converge"); st = TRL_ERR_STATE; break; }
-        if ((st = detect_embed_enqueue(c)) != TRL_OK) break;
+        if ((st = call_enqueue(c)) != TRL_OK) break;
     }
     c->pend.active = false;
     if (st == TRL_OK) collect_timings(c);
     return st;
 }
 
-static int detect_embed_impl(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
-                             uint8_t* d_valid, float* d_emb, float* d_faces_out, void* stream) {
-    TRL_CHECK(detect_embed_begin(c, d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, d_emb, d_faces_out, stream));
-    return detect_embed_wait(c);
+static int call_run(trl_ctx* c, const trl_ctx::Pending& q) {
+    TRL_CHECK(call_begin(c, q));
+    return call_wait(c);
 }
 
-int trl_detect_embed_begin(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
-                           uint8_t* d_valid, float* d_emb, void* stream) {
-    if (!d_emb) { trl_set_error("null output"); return TRL_ERR_INVALID; }
-    return detect_embed_begin(c, d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, d_emb, nullptr, stream);
+static trl_ctx::Pending detect_call(const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, float* d_points,
+                                    int32_t* d_counts, void* stream, int order) {
+    trl_ctx::Pending q;
+    q.kind = trl_ctx::Pending::DETECT;
+    q.frames = d_frames; q.n = n; q.H = H; q.W = W; q.stream = stream;
+    q.boxes = d_boxes; q.probs = d_probs; q.points = d_points; q.counts = d_counts; q.order = order;
+    return q;
 }
-int trl_detect_crop_begin(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
-                          uint8_t* d_valid, float* d_faces, void* stream) {
-    if (!d_faces) { trl_set_error("null output"); return TRL_ERR_INVALID; }
-    return detect_embed_begin(c, d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, nullptr, d_faces, stream);
+
+static trl_ctx::Pending embed_call(const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
+                                   uint8_t* d_valid, float* d_emb, float* d_faces_out, void* stream) {
+    trl_ctx::Pending q;
+    q.kind = d_emb ? trl_ctx::Pending::EMBED : trl_ctx::Pending::CROP;
+    q.frames = d_frames; q.n = n; q.H = H; q.W = W; q.stream = stream;
+    q.box = d_box; q.prob = d_prob; q.rect = d_rect; q.valid = d_valid; q.emb = d_emb; q.faces_out = d_faces_out;
+    return q;
 }
-int trl_detect_embed_end(trl_ctx* c) { return detect_embed_wait(c); }
+
+extern "C" {
+
+int trl_mtcnn_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, int32_t* d_counts,
+                     void* stream) {
+    return call_run(c, detect_call(d_frames, n, H, W, d_boxes, d_probs, nullptr, d_counts, stream, 0));
+}
+
+int trl_mtcnn_detect_landmarks(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs,
+                               float* d_points, int32_t* d_counts, void* stream) {
+    if (!d_points) { trl_set_error("null output"); return TRL_ERR_INVALID; }
+    return trl_mtcnn_detect_ordered(c, d_frames, n, H, W, 0, d_boxes, d_probs, d_points, d_counts, stream);
+}
+
+int trl_mtcnn_detect_ordered(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, int order, float* d_boxes, float* d_probs,
+                             float* d_points, int32_t* d_counts, void* stream) {
+    if (order != 0 && order != 1) { trl_set_error("bad box order %d (0 = area, 1 = detection order)", order); return TRL_ERR_INVALID; }
+    return call_run(c, detect_call(d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, stream, order));
+}
 
 int trl_detect_embed(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
                      uint8_t* d_valid, float* d_emb, void* stream) {
     if (!d_emb) { trl_set_error("null output"); return TRL_ERR_INVALID; }
-    return detect_embed_impl(c, d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, d_emb, nullptr, stream);
+    return call_run(c, embed_call(d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, d_emb, nullptr, stream));
 }
 
 int trl_detect_crop(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
                     uint8_t* d_valid, float* d_faces, void* stream) {
     if (!d_faces) { trl_set_error("null output"); return TRL_ERR_INVALID; }
-    return detect_embed_impl(c, d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, nullptr, d_faces, stream);
+    return call_run(c, embed_call(d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, nullptr, d_faces, stream));
 }
 
-int trl_facenet_embed_masked(trl_ctx* c, const float* d_faces, const uint8_t* d_valid, int n, int h, int w, float* d_emb, void* stream) {
+int trl_detect_embed_begin(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
+                           uint8_t* d_valid, float* d_emb, void* stream) {
+    if (!d_emb) { trl_set_error("null output"); return TRL_ERR_INVALID; }
+    return call_begin(c, embed_call(d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, d_emb, nullptr, stream));
+}
+
+int trl_detect_crop_begin(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
+                          uint8_t* d_valid, float* d_faces, void* stream) {
+    if (!d_faces) { trl_set_error("null output"); return TRL_ERR_INVALID; }
+    return call_begin(c, embed_call(d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, nullptr, d_faces, stream));
+}
+
+int trl_detect_embed_end(trl_ctx* c) { return call_wait(c); }
+
+}  // extern "C"
+
+// trl_facenet_embed / _masked: d_valid nullable (zero rows where it is 0)
+static int facenet_embed(trl_ctx* c, const float* d_faces, const uint8_t* d_valid, bool masked, int n, int h, int w, float* d_emb,
+                         void* stream) {
     if (!c || !c->have_weights) { trl_set_error("context without weights"); return TRL_ERR_STATE; }
-    TRL_CHECK(check_idle(c));
-    if (!d_faces || !d_valid || !d_emb || n <= 0 || h < 75 || w < 75) { trl_set_error("bad face batch n=%d %dx%d (min 75x75)", n, h, w); return TRL_ERR_INVALID; }
+    TRL_CHECK(trl_check_idle(c));
+    if (!d_faces || (masked && !d_valid) || !d_emb || n <= 0 || h < 75 || w < 75) { trl_set_error("bad face batch n=%d %dx%d (min 75x75)", n, h, w); return TRL_ERR_INVALID; }
     TRL_HIP(hipSetDevice(c->cfg.device));
     c->scratch.reset();
     TRL_CHECK(trl_ensure(c, c->scratch, (size_t)n * ((size_t)h * w * 110 + 400000) * 4 + (8u << 20)));
@@ -549,34 +543,44 @@ int trl_facenet_embed_masked(trl_ctx* c, const float* d_faces, const uint8_t* d_
     return trl_gate_record(c, (hipStream_t)stream);
 }
 
-int trl_drift_score(trl_ctx* c, const float* d_emb, const uint8_t* d_valid, int n, long long frame_count, int fps, float* d_sims,
-                    uint8_t* d_flags, int32_t* d_result, void* stream) {
-    if (!c || !d_emb || !d_valid || !d_result || n < 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
+// trl_drift_score / trl_drift_update: d_state nullable (no state carried across calls)
+static int drift(trl_ctx* c, void* d_state, const float* d_emb, const uint8_t* d_valid, int n, long long frame_count, int fps, float* d_sims,
+                 uint8_t* d_flags, int32_t* d_result, void* stream) {
     TRL_HIP(hipSetDevice(c->cfg.device));
     float* sims = d_sims;
     if (!sims) {   // the scan needs the similarities even when the caller does not want them
         TRL_CHECK(trl_ensure(c, c->sims_tmp, (size_t)(n > 0 ? n : 1) * sizeof(float)));
         sims = (float*)c->sims_tmp.base;
     }
-    return trl_launch_drift(d_emb, d_valid, n, frame_count, fps, sims, d_flags, d_result, (hipStream_t)stream);
+    return trl_launch_drift(d_emb, d_valid, n, frame_count, fps, sims, d_flags, d_result, (hipStream_t)stream, d_state);
+}
+
+extern "C" {
+
+int trl_facenet_embed(trl_ctx* c, const float* d_faces, int n, int h, int w, float* d_emb, void* stream) {
+    return facenet_embed(c, d_faces, nullptr, false, n, h, w, d_emb, stream);
+}
+
+int trl_facenet_embed_masked(trl_ctx* c, const float* d_faces, const uint8_t* d_valid, int n, int h, int w, float* d_emb, void* stream) {
+    return facenet_embed(c, d_faces, d_valid, true, n, h, w, d_emb, stream);
+}
+
+int trl_drift_score(trl_ctx* c, const float* d_emb, const uint8_t* d_valid, int n, long long frame_count, int fps, float* d_sims,
+                    uint8_t* d_flags, int32_t* d_result, void* stream) {
+    if (!c || !d_emb || !d_valid || !d_result || n < 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
+    return drift(c, nullptr, d_emb, d_valid, n, frame_count, fps, d_sims, d_flags, d_result, stream);
 }
 
 // trl_drift_score continued across the windows of ONE clip: d_state carries `previous embedding / run / hits` (model.py:60-75)
 int trl_drift_update(trl_ctx* c, void* d_state, const float* d_emb, const uint8_t* d_valid, int n, long long frame_count, int fps,
                      float* d_sims, uint8_t* d_flags, int32_t* d_result, void* stream) {
     if (!c || !d_state || !d_result || n < 0 || (n > 0 && (!d_emb || !d_valid)) || ((uintptr_t)d_state & 3)) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
-    TRL_HIP(hipSetDevice(c->cfg.device));
-    float* sims = d_sims;
-    if (!sims) {
-        TRL_CHECK(trl_ensure(c, c->sims_tmp, (size_t)(n > 0 ? n : 1) * sizeof(float)));
-        sims = (float*)c->sims_tmp.base;
-    }
-    return trl_launch_drift(d_emb, d_valid, n, frame_count, fps, sims, d_flags, d_result, (hipStream_t)stream, d_state);
+    return drift(c, d_state, d_emb, d_valid, n, frame_count, fps, d_sims, d_flags, d_result, stream);
 }
 
 // ---- inspection hooks ----------------------------------------------------------------------------------
 int trl_debug_stage_boxes(trl_ctx* c, int stage, int frame, float* h_boxes, int max_rows, int* n_out) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (!c->cb.n1 || frame < 0 || frame >= c->cb.n || stage < 1 || stage > 3 || !n_out || (max_rows > 0 && !h_boxes)) {
         trl_set_error("no cascade state");
         return TRL_ERR_STATE;
@@ -602,7 +606,7 @@ __global__ void k_poison_lds(unsigned word, int nwords) {
 // Fills every byte of the activation workspaces with `byte` (0xFF = NaN patterns, 0x7F = huge finite floats): a
 // result that depends on workspace contents left by an earlier call or process shows up as a parity failure.
 int trl_debug_poison(trl_ctx* c, int byte) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     TRL_HIP(hipSetDevice(c->cfg.device));
     TRL_HIP(hipDeviceSynchronize());
     c->dbg_poison = byte & 0xFF;                 // sticky: blocks allocated later are filled too
@@ -619,7 +623,7 @@ int trl_debug_poison(trl_ctx* c, int byte) {
 }
 
 int trl_debug_level_counts(trl_ctx* c, int frame, int32_t* h_cand, int32_t* h_keep, int* n_levels) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (!c->cb.lvl_cnt || frame < 0 || frame >= c->cb.n || !h_cand || !h_keep || !n_levels) { trl_set_error("no cascade state"); return TRL_ERR_STATE; }
     TRL_HIP(hipDeviceSynchronize());
     const int L = c->cb.L;
@@ -631,7 +635,7 @@ int trl_debug_level_counts(trl_ctx* c, int frame, int32_t* h_cand, int32_t* h_ke
 
 // Candidate records (generateBoundingBox rows) one (frame, level) of the last call produced, in append order
 int trl_debug_level_cands(trl_ctx* c, int frame, int level, void* h_rows, int max_rows, int* n_out) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (!c->cb.lvl_cnt || frame < 0 || frame >= c->cb.n || level < 0 || level >= c->cb.L || !n_out || (max_rows > 0 && !h_rows)) {
         trl_set_error("no cascade state");
         return TRL_ERR_STATE;
@@ -650,7 +654,7 @@ int trl_debug_level_cands(trl_ctx* c, int frame, int level, void* h_rows, int ma
 // The per-level NMS picks of one (frame, level) of the last call: indices into that level's candidate records (the rows
 // trl_debug_level_cands returns, in the same append order), in pick order (descending score)
 int trl_debug_level_keep(trl_ctx* c, int frame, int level, int32_t* h_idx, int max_rows, int* n_out) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (!c->cb.lvl_keep_cnt || frame < 0 || frame >= c->cb.n || level < 0 || level >= c->cb.L || !n_out || (max_rows > 0 && !h_idx)) {
         trl_set_error("no cascade state");
         return TRL_ERR_STATE;
@@ -689,7 +693,7 @@ int trl_debug_pyramid_batch(trl_ctx* c, const uint8_t* d_frames, int n, int H, i
 }
 
 int trl_debug_pyramid_plan(trl_ctx* c, int32_t* h_rows, int max_levels, int* n_levels) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (!n_levels || (max_levels > 0 && !h_rows)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
     *n_levels = c->pyr_plan.L;
     for (int l = 0; l < c->pyr_plan.L && l < max_levels; l++)
@@ -698,7 +702,7 @@ int trl_debug_pyramid_plan(trl_ctx* c, int32_t* h_rows, int max_levels, int* n_l
 }
 
 int trl_debug_facenet_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, int* n_rows) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (!n_rows || (max_rows > 0 && !h_rows)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
     *n_rows = (int)c->fn_plan.size();
     for (int i = 0; i < *n_rows && i < max_rows; i++) h_rows[i] = c->fn_plan[i];
@@ -706,13 +710,13 @@ int trl_debug_facenet_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, in
 }
 
 int trl_debug_facenet_capture(trl_ctx* c, int conv_index) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     c->fn_cap_arm = conv_index < 0 ? -1 : conv_index;
     return TRL_OK;
 }
 
 int trl_debug_facenet_capture_read(trl_ctx* c, int view, void* h_dst, size_t max_bytes, int32_t* dims5) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (view < 0 || view > 2 || !dims5) { trl_set_error("bad capture view %d", view); return TRL_ERR_INVALID; }
     const auto& b = c->fn_cap[view];
     for (int k = 0; k < 5; k++) dims5[k] = b.dims[k];
@@ -733,11 +737,9 @@ int trl_debug_pnet_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, int l
     if (level < 0 || level >= L) { trl_set_error("level %d out of range (%d levels)", level, L); return TRL_ERR_INVALID; }
     const LevelGeom& g = c->lv[level];
     c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, trl_pnet_generic_bytes(1, g.h, g.w) + (size_t)g.h * g.w * 12 + (size_t)g.oh * g.ow * 24 + (4u << 20)));
-    float* lvl = (float*)c->scratch.alloc((size_t)g.h * g.w * 12);
-    float* heads = (float*)c->scratch.alloc((size_t)g.oh * g.ow * 24);
-    TRL_CHECK(trl_launch_area_level(d_frame, 1, H, W, g.h, g.w, lvl, s));
-    TRL_CHECK(trl_run_pnet_generic(c, lvl, 1, g.h, g.w, heads, s));
+    TRL_CHECK(trl_ensure(c, c->scratch, trl_pnet_generic_level_bytes(g) + (4u << 20)));
+    float* heads;
+    TRL_CHECK(trl_pnet_generic_level(c, d_frame, 1, H, W, g, &heads, s));
     TRL_CHECK(trl_launch_heads_to_maps(heads, g.oh * g.ow, d_prob, d_reg, s));
     *oh = g.oh; *ow = g.ow;
     TRL_HIP(hipStreamSynchronize(s));
@@ -746,71 +748,33 @@ int trl_debug_pnet_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, int l
 
 int trl_debug_rnet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) {
     if (!c || !c->have_weights || !d_crops || !d_out || n <= 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     c->scratch.reset();
     TRL_CHECK(trl_ensure(c, c->scratch, (size_t)n * 100 * 1024 + (4u << 20)));
     return trl_run_rnet(c, d_crops, n, d_out, (hipStream_t)stream);
 }
-// test hook: the PRODUCTION stage-2 / stage-3 network path on caller-chosen boxes of frame 0 -- the fused front kernel
-// (k_mtcnn_front: pad(), crop, area resample, conv1, PReLU, pool) followed by the layer tail -- so its crop paths (small boxes,
-// big boxes, boxes clipped by the frame) are checked directly, not only through cascade records.  h_boxes: nb rows of
-// x1,y1,x2,y2 (host); d_out: [nb][6] (net = 24) or [nb][16] (net = 48), device.
-int trl_debug_front_net(trl_ctx* c, const uint8_t* d_frame, int H, int W, const float* h_boxes, int nb, int net, float* d_out, void* stream) {
-    TRL_CHECK(check_call(c, d_frame, 1, H, W));
-    if (!h_boxes || !d_out || nb <= 0 || nb > (1 << 20) || (net != 24 && net != 48)) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
-    hipStream_t s = (hipStream_t)stream;
-    TRL_HIP(hipSetDevice(c->cfg.device));
-    const int capF = nb;
-    Arena& A = c->arena;
-    TRL_CHECK(trl_ensure(c, A, (size_t)capF * 32 + (1u << 20)));
-    A.reset();
-    CascadeBufs& B = c->cb;
-    B = CascadeBufs();
-    B.n = 1; B.H = H; B.W = W;
-    B.cbox = (int32_t*)A.alloc((size_t)capF * 32);
-    int32_t* total = (int32_t*)A.alloc(64);
-    std::vector<int32_t> hb((size_t)nb * 8, 0);        // the records k_build_map writes: frame 0, pad()'s clamped crop window
-    for (int i = 0; i < nb; i++) {
-        const float* b = h_boxes + 4 * i;
-        const int bx = (int)truncf(b[0]), by = (int)truncf(b[1]), bex = (int)truncf(b[2]), bey = (int)truncf(b[3]);
-        const int x = bx < 1 ? 1 : bx, y = by < 1 ? 1 : by, ex = bex > W ? W : bex, ey = bey > H ? H : bey;
-        hb[8 * i + 1] = y - 1; hb[8 * i + 2] = x - 1; hb[8 * i + 3] = ey - (y - 1); hb[8 * i + 4] = ex - (x - 1);
-    }
-    TRL_HIP(hipMemcpyAsync(B.cbox, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s));
-    TRL_HIP(hipMemcpyAsync(total, &nb, 4, hipMemcpyHostToDevice, s));
-    TRL_HIP(hipStreamSynchronize(s));                      // the host vectors go out of scope
-    c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, (size_t)nb * 700 * 1024 + (4u << 20)));
-    if (net == 24) {
-        float* pool1 = (float*)c->scratch.alloc((size_t)nb * 11 * 11 * 28 * 4);
-        TRL_CHECK(trl_launch_rnet_front(c, d_frame, H, W, total, 0, nb, pool1, s));
-        TRL_CHECK(trl_run_rnet_tail(c, pool1, nb, d_out, s, total, 0));
-    } else {
-        float* pool1 = (float*)c->scratch.alloc((size_t)nb * 23 * 23 * 32 * 4);
-        TRL_CHECK(trl_launch_onet_front(c, d_frame, H, W, total, 0, nb, pool1, s));
-        TRL_CHECK(trl_run_onet_tail(c, pool1, nb, d_out, s, total, 0));
-    }
-    TRL_HIP(hipStreamSynchronize(s));
-    B = CascadeBufs();                                     // no cascade state to inspect after this hook
-    return TRL_OK;
-}
-
-// test hook: the production stage-2 / stage-3 loop (trl_stage_net, as the cascade runs it) over a launch capacity the caller
-// chooses.  h_recs: nb host rows (frame, x1, y1, x2, y2), turned into k_build_map's records by the same pad() rule; the device
+// The production stage-2 / stage-3 loop (trl_stage_net, as the cascade runs it) over a launch capacity the caller chooses.  h_rows:
+// nb host rows of `cols` floats -- (frame, x1, y1, x2, y2), or (x1, y1, x2, y2) of frame 0 when cols = 4 -- turned into
+// k_build_map's records by pad() (detect_face.py: trunc, x = max(x1, 1), ex = min(x2, W), crop [y-1:ey, x-1:ex]); the device
 // total is nb, and record slots past it (the kernels read them, then discard them) hold a poison pattern.  The workspace is sized
 // like the cascade's: chunk = the rnet_chunk / onet_chunk option.  d_out: [capacity][6] (net = 24) or [capacity][16] (net = 48),
 // device; only rows of live candidates are defined.  trl_debug_mtcnn_plan then lists the tail's conv launches of every chunk.
-int trl_debug_stage_net(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const float* h_recs, int nb, int net, int capacity,
-                        float* d_out, void* stream) {
-    TRL_CHECK(check_call(c, d_frames, nf, H, W));
-    if ((nb > 0 && !h_recs) || (capacity > 0 && !d_out) || nb < 0 || nb > (1 << 24) || capacity < 0 || capacity > (1 << 24) ||
-        (net != 24 && net != 48)) {
-        trl_set_error("bad argument");
-        return TRL_ERR_INVALID;
-    }
+static int stage_net_on_rows(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const float* h_rows, int cols, int nb, int net,
+                             int capacity, float* d_out, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     TRL_HIP(hipSetDevice(c->cfg.device));
     const int slots = nb > capacity ? nb : capacity;
+    std::vector<int32_t> hb((size_t)slots * 8, (int32_t)0xA5A5A5A5);   // poison: frame / window words no live record has
+    for (int i = 0; i < nb; i++) {
+        const float* b = h_rows + (size_t)cols * i + cols - 4;
+        const int f = cols == 5 ? (int)b[-1] : 0;
+        if (f < 0 || f >= nf) { trl_set_error("record %d: frame %d of %d", i, f, nf); return TRL_ERR_INVALID; }
+        const int bx = (int)truncf(b[0]), by = (int)truncf(b[1]), bex = (int)truncf(b[2]), bey = (int)truncf(b[3]);
+        const int x = bx < 1 ? 1 : bx, y = by < 1 ? 1 : by, ex = bex > W ? W : bex, ey = bey > H ? H : bey;
+        if (ey <= y - 1 || ex <= x - 1) { trl_set_error("record %d: empty crop window", i); return TRL_ERR_INVALID; }
+        int32_t* r = &hb[8 * (size_t)i];
+        r[0] = f; r[1] = y - 1; r[2] = x - 1; r[3] = ey - (y - 1); r[4] = ex - (x - 1); r[5] = r[6] = r[7] = 0;
+    }
     Arena& A = c->arena;
     TRL_CHECK(trl_ensure(c, A, (size_t)slots * 32 + (1u << 20)));
     A.reset();
@@ -819,17 +783,6 @@ int trl_debug_stage_net(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int 
     B.n = nf; B.H = H; B.W = W;
     B.cbox = (int32_t*)A.alloc((size_t)slots * 32 + 32);
     int32_t* total = (int32_t*)A.alloc(64);
-    std::vector<int32_t> hb((size_t)slots * 8, (int32_t)0xA5A5A5A5);   // poison: frame / window words no live record has
-    for (int i = 0; i < nb; i++) {
-        const float* b = h_recs + 5 * i;
-        const int f = (int)b[0];
-        if (f < 0 || f >= nf) { trl_set_error("record %d: frame %d of %d", i, f, nf); return TRL_ERR_INVALID; }
-        const int bx = (int)truncf(b[1]), by = (int)truncf(b[2]), bex = (int)truncf(b[3]), bey = (int)truncf(b[4]);
-        const int x = bx < 1 ? 1 : bx, y = by < 1 ? 1 : by, ex = bex > W ? W : bex, ey = bey > H ? H : bey;
-        if (ey <= y - 1 || ex <= x - 1) { trl_set_error("record %d: empty crop window", i); return TRL_ERR_INVALID; }
-        int32_t* r = &hb[8 * (size_t)i];
-        r[0] = f; r[1] = y - 1; r[2] = x - 1; r[3] = ey - (y - 1); r[4] = ex - (x - 1); r[5] = r[6] = r[7] = 0;
-    }
     TRL_HIP(hipMemcpyAsync(B.cbox, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s));
     TRL_HIP(hipMemcpyAsync(total, &nb, 4, hipMemcpyHostToDevice, s));
     TRL_HIP(hipStreamSynchronize(s));                      // the host vector goes out of scope
@@ -847,11 +800,32 @@ int trl_debug_stage_net(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int 
     return TRL_OK;
 }
 
+// test hook: the production stage-2 / stage-3 network path -- the fused front kernel (k_mtcnn_front: pad(), crop, area resample,
+// conv1, PReLU, pool) followed by the layer tail -- on caller-chosen boxes of frame 0, so its crop paths (small boxes, big boxes,
+// boxes clipped by the frame) are checked directly, not only through cascade records.  h_boxes: nb rows of x1,y1,x2,y2 (host),
+// none with an empty crop window; d_out: [nb][6] (net = 24) or [nb][16] (net = 48), device.
+int trl_debug_front_net(trl_ctx* c, const uint8_t* d_frame, int H, int W, const float* h_boxes, int nb, int net, float* d_out, void* stream) {
+    TRL_CHECK(check_call(c, d_frame, 1, H, W));
+    if (!h_boxes || !d_out || nb <= 0 || nb > (1 << 20) || (net != 24 && net != 48)) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
+    return stage_net_on_rows(c, d_frame, 1, H, W, h_boxes, 4, nb, net, nb, d_out, stream);
+}
+
+int trl_debug_stage_net(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const float* h_recs, int nb, int net, int capacity,
+                        float* d_out, void* stream) {
+    TRL_CHECK(check_call(c, d_frames, nf, H, W));
+    if ((nb > 0 && !h_recs) || (capacity > 0 && !d_out) || nb < 0 || nb > (1 << 24) || capacity < 0 || capacity > (1 << 24) ||
+        (net != 24 && net != 48)) {
+        trl_set_error("bad argument");
+        return TRL_ERR_INVALID;
+    }
+    return stage_net_on_rows(c, d_frames, nf, H, W, h_recs, 5, nb, net, capacity, d_out, stream);
+}
+
 // test hook: the cascade's list kernels on caller-built lists (trl_cascade_lists has the layout of every kind)
 int trl_debug_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* h_caps, int n_levels, const int32_t* h_counts,
                     const void* h_rows, const float* h_logits, float* h_pts, float* d_boxes, float* d_probs, float* d_points,
                     int32_t* d_counts, float* d_box0, float* d_prob0, int32_t* d_rect, uint8_t* d_valid, void* stream) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (kind < 1 || kind > 3 || n <= 0 || n > 65535 || H < 12 || W < 12 || H > 16383 || W > 16383 || !h_caps || !h_counts ||
         n_levels < (kind == 1 ? 1 : 0) || n_levels > 32 || (kind == 3 && !(d_boxes && d_probs && d_points && d_counts && d_box0 &&
         d_prob0 && d_rect && d_valid))) {
@@ -878,7 +852,7 @@ int trl_debug_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* h_
 }
 
 int trl_debug_mtcnn_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, int* n_rows) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (!n_rows || (max_rows > 0 && !h_rows)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
     *n_rows = (int)c->mt_plan.size();
     for (int i = 0; i < *n_rows && i < max_rows; i++) h_rows[i] = c->mt_plan[i];
@@ -887,7 +861,7 @@ int trl_debug_mtcnn_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, int*
 
 int trl_debug_onet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) {
     if (!c || !c->have_weights || !d_crops || !d_out || n <= 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     c->scratch.reset();
     TRL_CHECK(trl_ensure(c, c->scratch, (size_t)n * 640 * 1024 + (4u << 20)));
     return trl_run_onet(c, d_crops, n, d_out, (hipStream_t)stream);
@@ -908,7 +882,7 @@ int trl_debug_crop_aligned(trl_ctx* c, const uint8_t* d_frames, int n, int H, in
 // test hook: the LDS tiers of the sort + NMS kernels (candidates per list; 0 keeps a value).  Lists longer than `full` take the
 // spill tier (global memory): lowering it makes small test inputs exercise that tier.  Results never depend on the tiers.
 int trl_debug_nms_tiers(trl_ctx* c, int small_tier, int full_tier) {
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if ((small_tier && (small_tier < 16 || small_tier > 3072 || (small_tier & 3))) || (full_tier && (full_tier < 16 || full_tier > 3072 || (full_tier & 3)))) {
         trl_set_error("tiers must be multiples of 4 in [16, 3072]");
         return TRL_ERR_INVALID;
@@ -938,7 +912,7 @@ int trl_debug_option(trl_ctx* c, const char* key, int value) {
     if (!key) { trl_set_error("null key"); return TRL_ERR_INVALID; }
     if (!strcmp(key, "no_fnconv")) { g_trl_no_fnconv = value ? 1 : 0; return TRL_OK; }
     if (!strcmp(key, "pnet_gate")) { g_trl_pnet_gate = value ? 1 : 0; return TRL_OK; }
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     if (!strcmp(key, "rnet_chunk") && value >= 16) { c->rnet_chunk = value; return TRL_OK; }
     if (!strcmp(key, "onet_chunk") && value >= 16) { c->onet_chunk = value; return TRL_OK; }
     if (!strcmp(key, "pnet_screen") && (value == 0 || value == 1)) { c->pnet_screen = value; return TRL_OK; }
@@ -979,7 +953,7 @@ int trl_debug_pnet_span(trl_ctx* c, int reset, double* ms_sum, int32_t* launches
     if (!c || !ms_sum || !launches) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
     *ms_sum = 0.0; *launches = 0;
     if (!c->pnet_clk) return TRL_OK;
-    TRL_CHECK(check_idle(c));
+    TRL_CHECK(trl_check_idle(c));
     TRL_HIP(hipSetDevice(c->cfg.device));
     TRL_HIP(hipDeviceSynchronize());                 // the stamps are written by kernels on the callers' streams
     unsigned long long t[2] = {0, 0};

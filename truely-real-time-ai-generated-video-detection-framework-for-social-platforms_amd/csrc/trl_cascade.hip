@@ -1201,30 +1201,16 @@ static int launch_stage3_post(trl_ctx* c, const ListLaunch& ll, int n, int cap3,
     return TRL_OK;
 }
 
-// detect_face() stages 1-3 for n frames; results stay in c->cb
-// `resume` = 2 / 3: re-run of a call whose R-Net / O-Net batch capacity was too small -- everything up to that stage is intact in
-// the cascade arena (the lists, the stage boxes, the counts), so the attempt starts at stage 2 / 3 instead of at the pyramid.
-int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, hipStream_t s, int resume) {
-    const int L = trl_compute_levels(c, H, W);
+// The cascade's lists in c->arena for the layout in c->cb (n, L, lay, capF) and a spill pool of `spill` bytes, flags zeroed.  One
+// layout for the cascade and the list hook (trl_cascade_lists).  Behind them (B.arena_mark) the API layer allocates its per-frame
+// outputs, again on every attempt of a call.
+static int carve_lists(trl_ctx* c, size_t spill, hipStream_t s) {
     CascadeBufs& B = c->cb;
-    if (resume >= 2 && !(B.flags && B.n == n && B.L == L && B.H == H && B.W == W && L > 0)) resume = 0;   // nothing to resume from
-    B.n = n; B.L = L; B.H = H; B.W = W;
-    if (!resume) plan_lists(c, L);
     const LvLayout& G = B.lay;
-    const int capF = B.capF;
-    const size_t spill = spill_pool(c, n, H, W);
+    const int n = B.n, L = B.L, capF = B.capF;
     Arena& A = c->arena;      // cascade lists: live for the whole call (and for the debug hooks after it)
-    Arena& X = c->scratch;    // activations: reset between stages
-    if (resume) {
-        A.off = B.arena_mark;                                // the API layer's per-frame outputs are allocated again behind the lists
-        // the stages that run again report afresh (the stage-2 total of a resume at stage 3 stays: it is complete)
-        TRL_HIP(hipMemsetAsync(B.flags + FLG_T3, 0, 4, s));
-        TRL_HIP(hipMemsetAsync(B.flags + FLG_T3N, 0, 4, s));
-        if (resume == 2) { TRL_HIP(hipMemsetAsync(B.flags + FLG_T2, 0, 4, s)); TRL_HIP(hipMemsetAsync(B.flags + FLG_T2N, 0, 4, s)); }
-    }
     const size_t need = (size_t)n * ((size_t)G.S * (sizeof(Cand) + 4) + (size_t)L * 8) + (size_t)n * capF * (5 * 3 + 10 + 8) * 4 +
                         (size_t)n * 1024 + spill + (1u << 20);   // + the API layer's per-frame outputs (box0, prob0, rect, valid, pts0)
-    if (!resume) {
     TRL_CHECK(trl_ensure(c, A, need));
     A.reset();
     B.lvl_cnt = (int32_t*)A.alloc((size_t)n * L * 4);
@@ -1242,6 +1228,157 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     if (!B.flags || (spill && !B.spill)) { trl_set_error("cascade workspace allocation failed"); return TRL_ERR_STATE; }
     B.arena_mark = A.off;
     TRL_HIP(hipMemsetAsync(B.flags, 0, TRL_NFLAGS * 4, s));
+    return TRL_OK;
+}
+
+size_t trl_pnet_generic_level_bytes(const LevelGeom& g) {
+    return trl_pnet_generic_bytes(1, g.h, g.w) + (size_t)g.h * g.w * 12 + (size_t)g.oh * g.ow * 24 + 4096;
+}
+// frames per step of the generic path on level g: one step's workspace stays under 2 GB
+static int generic_chunk(const LevelGeom& g, int n) {
+    const int ch = (int)((size_t)(2048ull << 20) / trl_pnet_generic_level_bytes(g));
+    return ch < 1 ? 1 : (ch > n ? n : ch);
+}
+int trl_pnet_generic_level(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const LevelGeom& g, float** d_heads, hipStream_t s) {
+    Arena& X = c->scratch;
+    X.reset();
+    float* lvl = (float*)X.alloc((size_t)nf * g.h * g.w * 12);
+    float* heads = (float*)X.alloc((size_t)nf * g.oh * g.ow * 24);
+    if (!lvl || !heads) { trl_set_error("pnet generic workspace"); return TRL_ERR_STATE; }
+    TRL_CHECK(trl_launch_area_level(d_frames, nf, H, W, g.h, g.w, lvl, s));
+    TRL_CHECK(trl_run_pnet_generic(c, lvl, nf, g.h, g.w, heads, s));
+    *d_heads = heads;
+    return TRL_OK;
+}
+
+// the next (start, end) event pair of the call's PNet launches (pointers into c->pnet_ev: the fused path reserves it first)
+static int next_pnet_events(trl_ctx* c, std::pair<hipEvent_t, hipEvent_t>*& out) {
+    if ((int)c->pnet_ev.size() <= c->pnet_ev_used) {
+        hipEvent_t e0, e1;
+        TRL_HIP(hipEventCreate(&e0)); TRL_HIP(hipEventCreate(&e1));
+        c->pnet_ev.push_back({e0, e1});
+    }
+    out = &c->pnet_ev[c->pnet_ev_used++];
+    return TRL_OK;
+}
+
+// Capacities of the R-/O-Net candidate batches of this call, and ONE scratch workspace big enough for every stage: it is only
+// ever grown here, before anything of the call is queued (growing frees the old block)
+static int size_scratch(trl_ctx* c, int n, int H, int W, bool fused) {
+    Arena& X = c->scratch;
+    const int L = c->cb.L;
+    X.reset();
+    if (!fused) {
+        size_t mx = 0;
+        for (int l = 0; l < L; l++) {
+            const size_t p = trl_pnet_generic_level_bytes(c->lv[l]) * generic_chunk(c->lv[l], n);
+            if (p > mx) mx = p;
+        }
+        TRL_CHECK(trl_ensure(c, X, mx + (4u << 20)));
+    }
+    long long c2 = (long long)(c->t2_per_frame * n) + 64, c3 = (long long)(c->t3_per_frame * n) + 64;
+    const long long lim = (long long)n * c->cb.capF;
+    c->cap_t2 = (int)(c2 < lim ? c2 : lim);
+    c->cap_t3 = (int)(c3 < lim ? c3 : lim);
+    const int ch2 = c->cap_t2 < c->rnet_chunk ? c->cap_t2 : c->rnet_chunk, ch3 = c->cap_t3 < c->onet_chunk ? c->cap_t3 : c->onet_chunk;
+    // per candidate: the front kernel's pooled map + every activation of the tail (trl_run_rnet_tail / trl_run_onet_tail:
+    // R-Net 3388 + 3888 + 768 + 576 + 128 floats = 35 KB; O-Net 16928 + 28224 + 6400 + 4096 + 1024 + 1152 + 256 = 227 KB)
+    size_t need_x = (size_t)c->cap_t2 * 24 + (size_t)ch2 * (40 * 1024) + (1u << 20);
+    const size_t need3 = (size_t)c->cap_t3 * 64 + (size_t)ch3 * (240 * 1024) + (1u << 20);
+    if (need3 > need_x) need_x = need3;
+    if (fused) { const size_t p = trl_pnet_fused_bytes(c, n, H, W) + (1u << 20); if (p > need_x) need_x = p; }
+    if (c->scratch_after_cascade > need_x) need_x = c->scratch_after_cascade;   // the embedder that follows in the same call
+    return trl_ensure(c, X, need_x);
+}
+
+// stage 1, fused path: pyramid kernel + ONE persistent PNet launch over every (frame, level, tile)
+static int stage1_fused(trl_ctx* c, const uint8_t* d_frames, hipStream_t s) {
+    const CascadeBufs& B = c->cb;
+    std::pair<hipEvent_t, hipEvent_t>*pa, *pb;
+    c->pnet_ev.reserve(64);   // next_pnet_events hands out pointers into the vector: no reallocation below
+    TRL_CHECK(next_pnet_events(c, pa)); TRL_CHECK(next_pnet_events(c, pb));
+    hipEvent_t ev[4] = {pa->first, pa->second, pb->first, pb->second};
+    return trl_pnet_fused_all(c, d_frames, B.n, B.H, B.W, ev, s);
+}
+
+// stage 1, generic layer path: per level, the level materialised for a chunk of frames, PNet's layers, candidate records
+static int stage1_generic(trl_ctx* c, const uint8_t* d_frames, hipStream_t s) {
+    const CascadeBufs& B = c->cb;
+    const LvLayout& G = B.lay;
+    const int n = B.n, H = B.H, W = B.W, L = B.L;
+    for (int l = 0; l < L; l++) {
+        const LevelGeom& g = c->lv[l];
+        if (g.oh < 1 || g.ow < 1) continue;
+        std::pair<hipEvent_t, hipEvent_t>* pe;
+        TRL_CHECK(next_pnet_events(c, pe));
+        TRL_HIP(hipEventRecord(pe->first, s));
+        const int chunk = generic_chunk(g, n);
+        for (int f0 = 0; f0 < n; f0 += chunk) {
+            const int nf = (n - f0 < chunk) ? n - f0 : chunk;
+            float* heads;
+            TRL_CHECK(trl_pnet_generic_level(c, d_frames + (size_t)f0 * H * W * 3, nf, H, W, g, &heads, s));
+            const size_t total = (size_t)nf * g.oh * g.ow;
+            size_t blocks = (total + 255) / 256;
+            if (blocks > 16384) blocks = 16384;
+            k_pnet_collect<<<(unsigned)blocks, 256, 0, s>>>(heads, nf, f0, g.oh, g.ow, (float)g.scale, c->cfg.thr0, L, l, G.capl[l],
+                                                             G.rec0[l], G.S, B.lvl_cnt, B.lvl_rec, B.flags);
+            TRL_LAUNCH_CHECK();
+        }
+        TRL_HIP(hipEventRecord(pe->second, s));
+    }
+    return TRL_OK;
+}
+
+// stage 2: R-Net over the stage-1 boxes, then its tail.  No host round trip: the candidate total stays on the device (off2[n]).
+// Launches are sized by an optimistic capacity (c->cap_t2, from earlier calls) and workgroups past the real total exit at once;
+// if the total exceeds the capacity a flag is raised and the call is re-run with a larger one (trl_cascade_check).
+static int stage2(trl_ctx* c, const ListLaunch& ll, const uint8_t* d_frames, const Spill& sp, hipStream_t s) {
+    const CascadeBufs& B = c->cb;
+    const int n = B.n, H = B.H, W = B.W, cap2 = c->cap_t2;
+    k_scan_counts<<<1, 256, 0, s>>>(B.n1, n, B.off2, cap2, B.flags, 0);
+    TRL_LAUNCH_CHECK();
+    k_build_map<<<n, 64, 0, s>>>(B.n1, B.off2, B.s1_box, B.capF, W, H, B.cbox);
+    TRL_LAUNCH_CHECK();
+    c->scratch.reset();   // stream order keeps the PNet workspace alive until its kernels are done: reuse needs no host sync
+    float* out6 = (float*)c->scratch.alloc((size_t)cap2 * 24);
+    if (!out6) { trl_set_error("rnet workspace"); return TRL_ERR_STATE; }
+    TRL_CHECK(trl_stage_net(c, 24, d_frames, H, W, B.off2 + n, cap2, out6, s));
+    return launch_stage2_post(c, ll, n, H, W, cap2, out6, sp, s);
+}
+
+// stage 3: O-Net over the stage-2 boxes, then its tail (capacity c->cap_t3, as stage 2)
+static int stage3(trl_ctx* c, const ListLaunch& ll, const uint8_t* d_frames, const Spill& sp, hipStream_t s) {
+    const CascadeBufs& B = c->cb;
+    const int n = B.n, H = B.H, W = B.W, cap3 = c->cap_t3;
+    k_scan_counts<<<1, 256, 0, s>>>(B.n2, n, B.off3, cap3, B.flags, 1);
+    TRL_LAUNCH_CHECK();
+    k_build_map<<<n, 64, 0, s>>>(B.n2, B.off3, B.s2_box, B.capF, W, H, B.cbox);
+    TRL_LAUNCH_CHECK();
+    c->scratch.reset();
+    float* out16 = (float*)c->scratch.alloc((size_t)cap3 * 64);
+    if (!out16) { trl_set_error("onet workspace"); return TRL_ERR_STATE; }
+    TRL_CHECK(trl_stage_net(c, 48, d_frames, H, W, B.off3 + n, cap3, out16, s));
+    return launch_stage3_post(c, ll, n, cap3, out16, sp, s);
+}
+
+// detect_face() stages 1-3 for n frames; results stay in c->cb
+// `resume` = 2 / 3: re-run of a call whose R-Net / O-Net batch capacity was too small -- everything up to that stage is intact in
+// the cascade arena (the lists, the stage boxes, the counts), so the attempt starts at stage 2 / 3 instead of at the pyramid.
+int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, hipStream_t s, int resume) {
+    const int L = trl_compute_levels(c, H, W);
+    CascadeBufs& B = c->cb;
+    if (resume >= 2 && !(B.flags && B.n == n && B.L == L && B.H == H && B.W == W && L > 0)) resume = 0;   // nothing to resume from
+    B.n = n; B.L = L; B.H = H; B.W = W;
+    if (!resume) plan_lists(c, L);
+    const size_t spill = spill_pool(c, n, H, W);
+    if (resume) {
+        c->arena.off = B.arena_mark;                         // the API layer's per-frame outputs are allocated again behind the lists
+        // the stages that run again report afresh (the stage-2 total of a resume at stage 3 stays: it is complete)
+        TRL_HIP(hipMemsetAsync(B.flags + FLG_T3, 0, 4, s));
+        TRL_HIP(hipMemsetAsync(B.flags + FLG_T3N, 0, 4, s));
+        if (resume == 2) { TRL_HIP(hipMemsetAsync(B.flags + FLG_T2, 0, 4, s)); TRL_HIP(hipMemsetAsync(B.flags + FLG_T2N, 0, 4, s)); }
+    } else {
+        TRL_CHECK(carve_lists(c, spill, s));
     }
     const Spill sp{B.spill, (unsigned long long)B.spill_cap, B.flags};
     if (L == 0) {
@@ -1252,124 +1389,22 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
         TRL_HIP(hipMemsetAsync(B.n3, 0, (size_t)n * 4, s));
         TRL_HIP(hipMemsetAsync(B.off2, 0, (size_t)(n + 1) * 4, s));
         TRL_HIP(hipMemsetAsync(B.off3, 0, (size_t)(n + 1) * 4, s));
-        if (c->scratch_after_cascade) TRL_CHECK(trl_ensure(c, X, c->scratch_after_cascade));   // the crops + embedder of the same call
+        if (c->scratch_after_cascade) TRL_CHECK(trl_ensure(c, c->scratch, c->scratch_after_cascade));   // the crops + embedder of the same call
         return TRL_OK;
     }
-    if (!resume) TRL_HIP(hipMemsetAsync(B.lvl_cnt, 0, (size_t)n * L * 4, s));
-
-    // ---- stage 1: PNet over the pyramid ----------------------------------------------------------
-    if (!resume) c->pnet_ev_used = 0;
-    X.reset();
-    int chunk[32];
+    if (!resume) {
+        TRL_HIP(hipMemsetAsync(B.lvl_cnt, 0, (size_t)n * L * 4, s));
+        c->pnet_ev_used = 0;
+    }
     const bool fused = c->cfg.pnet_mode == 0 && L <= 16;   // the fused launch carries 16 level descriptors; taller pyramids (a
                                                            // 16 K frame at min_face_size 12) take the per-level path
-    if (!fused) {
-        size_t mx = 0;
-        for (int l = 0; l < L; l++) {
-            const LevelGeom& g = c->lv[l];
-            const size_t per = trl_pnet_generic_bytes(1, g.h, g.w) + (size_t)g.h * g.w * 12 + (size_t)g.oh * g.ow * 24 + 4096;
-            int ch = (int)((size_t)(2048ull << 20) / per);
-            if (ch < 1) ch = 1;
-            if (ch > n) ch = n;
-            chunk[l] = ch;
-            if (per * ch > mx) mx = per * ch;
-        }
-        TRL_CHECK(trl_ensure(c, X, mx + (4u << 20)));
-    }
-    auto next_ev = [&](std::pair<hipEvent_t, hipEvent_t>*& out) -> int {
-        if ((int)c->pnet_ev.size() <= c->pnet_ev_used) {
-            hipEvent_t e0, e1;
-            TRL_HIP(hipEventCreate(&e0)); TRL_HIP(hipEventCreate(&e1));
-            c->pnet_ev.push_back({e0, e1});
-        }
-        out = &c->pnet_ev[c->pnet_ev_used++];
-        return TRL_OK;
-    };
-    // capacities of the R-/O-Net candidate batches of this call, and ONE workspace big enough for every stage: it is only
-    // ever grown here, before anything is queued (growing frees the old block)
-    {
-        long long c2 = (long long)(c->t2_per_frame * n) + 64, c3 = (long long)(c->t3_per_frame * n) + 64;
-        const long long lim = (long long)n * capF;
-        c->cap_t2 = (int)(c2 < lim ? c2 : lim);
-        c->cap_t3 = (int)(c3 < lim ? c3 : lim);
-        const int TRL_CH2 = c->rnet_chunk, TRL_CH3 = c->onet_chunk;
-        const int ch2 = c->cap_t2 < TRL_CH2 ? c->cap_t2 : TRL_CH2, ch3 = c->cap_t3 < TRL_CH3 ? c->cap_t3 : TRL_CH3;
-        // per candidate: the front kernel's pooled map + every activation of the tail (trl_run_rnet_tail / trl_run_onet_tail:
-        // R-Net 3388 + 3888 + 768 + 576 + 128 floats = 35 KB; O-Net 16928 + 28224 + 6400 + 4096 + 1024 + 1152 + 256 = 227 KB)
-        size_t need_x = (size_t)c->cap_t2 * 24 + (size_t)ch2 * (40 * 1024) + (1u << 20);
-        const size_t need3 = (size_t)c->cap_t3 * 64 + (size_t)ch3 * (240 * 1024) + (1u << 20);
-        if (need3 > need_x) need_x = need3;
-        if (fused) { const size_t p = trl_pnet_fused_bytes(c, n, H, W) + (1u << 20); if (p > need_x) need_x = p; }
-        if (c->scratch_after_cascade > need_x) need_x = c->scratch_after_cascade;   // the embedder that follows in the same call
-        TRL_CHECK(trl_ensure(c, X, need_x));
-    }
-    if (resume) {
-        // stage 1 is intact
-    } else if (fused) {
-        // fused path: pyramid kernel + ONE persistent PNet launch over every (frame, level, tile)
-        std::pair<hipEvent_t, hipEvent_t>*pa, *pb;
-        c->pnet_ev.reserve(64);   // next_ev hands out pointers into the vector: no reallocation below
-        TRL_CHECK(next_ev(pa)); TRL_CHECK(next_ev(pb));
-        hipEvent_t ev[4] = {pa->first, pa->second, pb->first, pb->second};
-        TRL_CHECK(trl_pnet_fused_all(c, d_frames, n, H, W, ev, s));
-    } else {
-        for (int l = 0; l < L; l++) {
-            const LevelGeom& g = c->lv[l];
-            if (g.oh < 1 || g.ow < 1) continue;
-            std::pair<hipEvent_t, hipEvent_t>* pe;
-            TRL_CHECK(next_ev(pe));
-            TRL_HIP(hipEventRecord(pe->first, s));
-            // generic layer path: materialise the level for a chunk of frames
-            for (int f0 = 0; f0 < n; f0 += chunk[l]) {
-                const int nf = (n - f0 < chunk[l]) ? n - f0 : chunk[l];
-                X.reset();
-                float* lvl = (float*)X.alloc((size_t)nf * g.h * g.w * 12);
-                float* heads = (float*)X.alloc((size_t)nf * g.oh * g.ow * 24);
-                if (!lvl || !heads) { trl_set_error("pnet generic workspace"); return TRL_ERR_STATE; }
-                TRL_CHECK(trl_launch_area_level(d_frames + (size_t)f0 * H * W * 3, nf, H, W, g.h, g.w, lvl, s));
-                TRL_CHECK(trl_run_pnet_generic(c, lvl, nf, g.h, g.w, heads, s));
-                const size_t total = (size_t)nf * g.oh * g.ow;
-                size_t blocks = (total + 255) / 256;
-                if (blocks > 16384) blocks = 16384;
-                k_pnet_collect<<<(unsigned)blocks, 256, 0, s>>>(heads, nf, f0, g.oh, g.ow, (float)g.scale, c->cfg.thr0, L, l, G.capl[l],
-                                                                 G.rec0[l], G.S, B.lvl_cnt, B.lvl_rec, B.flags);
-                TRL_LAUNCH_CHECK();
-            }
-            TRL_HIP(hipEventRecord(pe->second, s));
-        }
-    }
+    TRL_CHECK(size_scratch(c, n, H, W, fused));
+    if (!resume) TRL_CHECK(fused ? stage1_fused(c, d_frames, s) : stage1_generic(c, d_frames, s));
     ListLaunch ll;
     TRL_CHECK(list_launch(c, ll));
     if (!resume) TRL_CHECK(launch_stage1_lists(c, ll, n, H, W, sp, s));
-
-    // ---- stage 2: RNet ------------------------------------------------------------------------------
-    // No host round trip: the candidate total stays on the device (off2[n]).  Launches are sized by an optimistic capacity
-    // (c->cap_t2, from earlier calls) and workgroups past the real total exit at once; if the total exceeds the capacity a
-    // flag is raised and the caller re-runs the call with a larger one (trl_cascade_run).
-    const int cap2 = c->cap_t2, cap3 = c->cap_t3;
-    if (resume < 3) {
-    k_scan_counts<<<1, 256, 0, s>>>(B.n1, n, B.off2, cap2, B.flags, 0);
-    TRL_LAUNCH_CHECK();
-    k_build_map<<<n, 64, 0, s>>>(B.n1, B.off2, B.s1_box, capF, W, H, B.cbox);
-    TRL_LAUNCH_CHECK();
-    X.reset();   // stream order keeps the PNet workspace alive until its kernels are done: reuse needs no host sync
-    float* out6 = (float*)X.alloc((size_t)cap2 * 24);
-    if (!out6) { trl_set_error("rnet workspace"); return TRL_ERR_STATE; }
-    TRL_CHECK(trl_stage_net(c, 24, d_frames, H, W, B.off2 + n, cap2, out6, s));
-    TRL_CHECK(launch_stage2_post(c, ll, n, H, W, cap2, out6, sp, s));
-    }
-
-    // ---- stage 3: ONet --------------------------------------------------------------------------------
-    k_scan_counts<<<1, 256, 0, s>>>(B.n2, n, B.off3, cap3, B.flags, 1);
-    TRL_LAUNCH_CHECK();
-    k_build_map<<<n, 64, 0, s>>>(B.n2, B.off3, B.s2_box, capF, W, H, B.cbox);
-    TRL_LAUNCH_CHECK();
-    X.reset();
-    float* out16 = (float*)X.alloc((size_t)cap3 * 64);
-    if (!out16) { trl_set_error("onet workspace"); return TRL_ERR_STATE; }
-    TRL_CHECK(trl_stage_net(c, 48, d_frames, H, W, B.off3 + n, cap3, out16, s));
-    TRL_CHECK(launch_stage3_post(c, ll, n, cap3, out16, sp, s));
-    return TRL_OK;
+    if (resume < 3) TRL_CHECK(stage2(c, ll, d_frames, sp, s));
+    return stage3(c, ll, d_frames, sp, s);
 }
 
 // One R-Net (net = 24) or O-Net (net = 48) stage over `cap` candidate slots: chunks of c->rnet_chunk / c->onet_chunk candidates,
@@ -1467,9 +1502,9 @@ int trl_cascade_check(trl_ctx* c, int n, int* retry) {
     return TRL_OK;
 }
 
-// test hook behind trl_debug_lists: the list kernels on lists the caller provides, launched by the cascade's own code
-// (list_launch, launch_stage1_lists / launch_stage2_post / launch_stage3_post, trl_cascade_finish) with the cascade's spill pool
-// and overflow flags.  kind 1: h_rows = Cand records of every (frame, level), frame-major, h_counts [n][L]; kind 2: stage-1 rows
+// test hook behind trl_debug_lists: the list kernels on lists the caller provides, in the cascade's own layout (carve_lists),
+// launched by its own code (list_launch, launch_stage1_lists / launch_stage2_post / launch_stage3_post, trl_cascade_finish) with
+// its spill pool and overflow flags.  kind 1: h_rows = Cand records of every (frame, level), frame-major, h_counts [n][L]; kind 2: stage-1 rows
 // (x1, y1, x2, y2, score) of every frame, h_counts [n], h_logits the R-Net outputs [total][6]; kind 3: stage-2 rows, h_logits the
 // O-Net outputs [total][16], then k_select into the d_* outputs and the stage-3 landmarks into h_pts [n][capF][10] (nullable).
 // h_caps = the L level capacities, then capF.  Every slot the inputs do not fill holds the poison byte of trl_debug_poison (0xA5
@@ -1487,34 +1522,10 @@ int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* 
     const int capF = B.capF, nc = kind == 1 ? n * L : n;
     long long total = 0;
     for (int i = 0; i < nc; i++) total += h_counts[i];
-    const size_t spill = spill_pool(c, n, H, W);
-    Arena& A = c->arena;
-    const size_t need = (size_t)n * ((size_t)G.S * (sizeof(Cand) + 4) + (size_t)L * 8) + (size_t)n * capF * (5 * 3 + 10) * 4 +
-                        (size_t)n * 64 + spill + (1u << 20);
-    TRL_CHECK(trl_ensure(c, A, need));
-    A.reset();
-    B.lvl_cnt = (int32_t*)A.alloc((size_t)n * L * 4 + 4);
-    B.lvl_keep_cnt = (int32_t*)A.alloc((size_t)n * L * 4 + 4);
-    B.lvl_rec = (Cand*)A.alloc((size_t)n * G.S * sizeof(Cand) + 4);
-    B.lvl_keep_idx = (int32_t*)A.alloc((size_t)n * G.S * 4 + 4);
-    B.n1 = (int32_t*)A.alloc((size_t)n * 4); B.n2 = (int32_t*)A.alloc((size_t)n * 4); B.n3 = (int32_t*)A.alloc((size_t)n * 4);
-    B.s1_box = (float*)A.alloc((size_t)n * capF * 20); B.s2_box = (float*)A.alloc((size_t)n * capF * 20);
-    B.s3_box = (float*)A.alloc((size_t)n * capF * 20); B.s3_pts = (float*)A.alloc((size_t)n * capF * 40);
-    B.off2 = (int32_t*)A.alloc((size_t)(n + 1) * 4); B.off3 = (int32_t*)A.alloc((size_t)(n + 1) * 4);
-    const size_t live = A.off;
-    B.flags = (int32_t*)A.alloc(TRL_NFLAGS * 4);
-    B.spill = spill ? (char*)A.alloc(spill) : nullptr;
-    B.spill_cap = B.spill ? spill : 0;
-    if (!B.lvl_cnt || !B.lvl_keep_cnt || !B.lvl_rec || !B.lvl_keep_idx || !B.n1 || !B.n2 || !B.n3 || !B.s1_box || !B.s2_box || !B.s3_box ||
-        !B.s3_pts || !B.off2 || !B.off3 || !B.flags || (spill && !B.spill)) {
-        trl_set_error("list workspace allocation failed");
-        B = CascadeBufs();
-        return TRL_ERR_STATE;
-    }
-    B.arena_mark = A.off;
+    const int st = carve_lists(c, spill_pool(c, n, H, W), s);
+    if (st != TRL_OK) { B = CascadeBufs(); return st; }
     const int poison = c->dbg_poison >= 0 ? c->dbg_poison : 0xA5;
-    TRL_HIP(hipMemsetAsync(A.base, poison, live, s));
-    TRL_HIP(hipMemsetAsync(B.flags, 0, TRL_NFLAGS * 4, s));
+    TRL_HIP(hipMemsetAsync(c->arena.base, poison, (size_t)((char*)B.flags - c->arena.base), s));   // every list (the flags stay zero)
     // the caller's lists, packed, into the capacity layout; the poison stays in the slots behind the counts
     std::vector<int32_t> cnt(h_counts, h_counts + nc);
     std::vector<float> logits;

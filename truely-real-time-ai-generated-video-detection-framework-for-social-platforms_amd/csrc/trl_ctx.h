@@ -87,12 +87,18 @@ struct trl_ctx {
     int resume_stage = 0;            // 2 / 3: the next attempt of the call in progress starts at that stage (trl_cascade_check)
     size_t scratch_after_cascade = 0;   // scratch bytes the rest of the call needs (crops + FaceNet): sized with the cascade's
     int rnet_front_mode = -1, onet_front_mode = -1;   // conv1 PReLU slope class (trl_front.hip), -1 = not yet classified
-    // the call queued by trl_detect_embed_begin / trl_detect_crop_begin and not yet finished by trl_detect_embed_end
+    // the call in progress: queued by trl_detect_embed_begin / trl_detect_crop_begin and not yet finished by trl_detect_embed_end,
+    // or a blocking trl_detect_embed / trl_detect_crop / trl_mtcnn_detect* between its enqueue and its wait (trl_api.hip)
     struct Pending {
-        bool active = false; int attempt = 0;
+        enum Kind { EMBED, CROP, DETECT };
+        bool active = false; int attempt = 0; Kind kind = EMBED;
         const uint8_t* frames = nullptr; int n = 0, H = 0, W = 0;
+        void* stream = nullptr;
+        // EMBED / CROP: model.py:47-58 per frame, then the embeddings (EMBED) or the crops into faces_out (CROP)
         float* box = nullptr; float* prob = nullptr; int32_t* rect = nullptr; uint8_t* valid = nullptr; float* emb = nullptr;
-        float* faces_out = nullptr; void* stream = nullptr;
+        float* faces_out = nullptr;
+        // DETECT: MTCNN.detect's boxes [n][max_faces][4], probs, points [n][max_faces][10] (nullable), counts; order as k_select's
+        float* boxes = nullptr; float* probs = nullptr; float* points = nullptr; int32_t* counts = nullptr; int order = 0;
     } pend;
     uint32_t* pyr_tab = nullptr;     // pyramid bin-edge tables for the last (H, W)
     int pyr_tab_H = 0, pyr_tab_W = 0;
@@ -124,6 +130,9 @@ int trl_gate_wait(trl_ctx* c, hipStream_t s);      // before the fused PNet laun
 int trl_gate_record(trl_ctx* c, hipStream_t s);    // behind the last kernel of a call
 extern int g_trl_pnet_gate;                        // trl_debug_option("pnet_gate"): 0 (default) / 1
 int trl_ensure(trl_ctx* c, Arena& a, size_t bytes);   // grow (never while blocks of `a` are live)
+// A context holds at most one call in flight (trl_detect_embed_begin .. _end); anything else that touches its workspaces meanwhile
+// would corrupt that call silently: TRL_ERR_STATE (and TRL_ERR_INVALID for a null context)
+int trl_check_idle(trl_ctx* c);
 const DevW* trl_w(trl_ctx* c, const std::string& name);
 const DevV* trl_v(trl_ctx* c, const std::string& name);
 
@@ -160,6 +169,10 @@ int trl_launch_crop_area_std(const uint8_t* d_frames, int n, int H, int W, const
 int trl_launch_area_level(const uint8_t* d_frames, int nf, int H, int W, int h, int w, float* d_level, hipStream_t s);
 int trl_launch_heads_to_maps(const float* d_heads, int cells, float* d_prob, float* d_reg, hipStream_t s);
 int trl_compute_levels(trl_ctx* c, int H, int W);
+// stage 1 on the generic layer path, one level g of nf frames: scratch bytes per frame, and the step itself -- the level
+// materialised in c->scratch (reset first), PNet's layers over it; *d_heads = [nf][oh][ow][6] behind it in c->scratch
+size_t trl_pnet_generic_level_bytes(const LevelGeom& g);
+int trl_pnet_generic_level(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const LevelGeom& g, float** d_heads, hipStream_t s);
 // fused PNet (trl_pnet.hip)
 int trl_pnet_prepare(trl_ctx* c);
 size_t trl_pnet_fused_bytes(trl_ctx* c, int n, int H, int W);

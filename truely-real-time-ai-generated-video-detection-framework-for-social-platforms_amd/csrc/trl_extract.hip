@@ -286,8 +286,7 @@ extern "C" {
 
 int trl_select_faces(trl_ctx* c, int n, const float* d_boxes, const float* d_probs, const int32_t* d_counts, int H, int W, int method,
                      float threshold, double center_weight, int32_t* d_pick, void* stream) {
-    if (!c) { trl_set_error("null context"); return TRL_ERR_INVALID; }
-    if (c->pend.active) { trl_set_error("the context has a call in flight: trl_detect_embed_end() first"); return TRL_ERR_STATE; }
+    TRL_CHECK(trl_check_idle(c));
     if (!d_boxes || !d_probs || !d_counts || !d_pick) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
     if (n <= 0 || n > 65535 || H < 1 || W < 1 || method < 0 || method > 3) {
         trl_set_error("bad selection n=%d H=%d W=%d method=%d", n, H, W, method);
@@ -302,8 +301,7 @@ int trl_select_faces(trl_ctx* c, int n, const float* d_boxes, const float* d_pro
 
 int trl_extract_faces(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, const int32_t* d_frame_of, const float* d_boxes, int m,
                       int S, int margin, int resample, int post_process, float* d_out, int32_t* d_status, void* stream) {
-    if (!c) { trl_set_error("null context"); return TRL_ERR_INVALID; }
-    if (c->pend.active) { trl_set_error("the context has a call in flight: trl_detect_embed_end() first"); return TRL_ERR_STATE; }
+    TRL_CHECK(trl_check_idle(c));
     if (!d_frames || ((!d_frame_of || !d_boxes || !d_out) && m != 0)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
     if (n <= 0 || n > 65535 || H < 1 || W < 1 || H > 16383 || W > 16383 || m < 0 || m > 65535) {
         trl_set_error("bad extraction batch n=%d H=%d W=%d m=%d", n, H, W, m);

@@ -193,27 +193,9 @@ class Engine:
         _lib.check(self.lib.trl_facenet_embed(self._h, _ptr(faces), n, h, w, _ptr(emb), self._stream()))
         return emb
 
-    # server/model.py:47-59 for a batch of sampled frames
-    def detect_embed(self, frames):
-        fr = self._frames(frames)
-        n, H, W, _ = fr.shape
-        d = self.device
-        out = {"box": torch.empty((n, 4), dtype=torch.float32, device=d), "prob": torch.empty((n,), dtype=torch.float32, device=d),
-               "rect": torch.empty((n, 4), dtype=torch.int32, device=d), "valid": torch.empty((n,), dtype=torch.uint8, device=d),
-               "emb": torch.empty((n, 512), dtype=torch.float32, device=d)}
-        _lib.check(self.lib.trl_detect_embed(self._h, _ptr(fr), n, H, W, _ptr(out["box"]), _ptr(out["prob"]), _ptr(out["rect"]),
-                                             _ptr(out["valid"]), _ptr(out["emb"]), self._stream()))
-        return out
-
-    # detect_embed / detect_crop split into "queue" and "finish" (trl_detect_embed_begin / _end): one host thread can keep
-    # several engines busy, each on its own stream, without a thread per engine (pipeline.detect_embed_overlapped)
-    def detect_embed_begin(self, frames, crop: bool = False, faces: torch.Tensor | None = None, valid: torch.Tensor | None = None):
-        """Queue detect_embed (or, with ``crop=True``, detect_crop) on the current stream and return at once; the outputs are
-        valid after :meth:`detect_embed_end`.  An engine holds one call in flight.  ``faces`` / ``valid`` (optional, crop mode):
-        caller-owned contiguous destination buffers -- a slot of a ring whose neighbours hold other batches' crops, so several
-        batches can be embedded in one call without a copy (pipeline.detect_embed_overlapped)."""
-        fr = self._frames(frames)
-        n, H, W, _ = fr.shape
+    def _call_outputs(self, n: int, crop: bool, faces: torch.Tensor | None = None, valid: torch.Tensor | None = None) -> dict:
+        """The outputs of a detect_embed (``emb``) / detect_crop (``faces``) call on n frames: new tensors, or the caller's
+        ``faces`` / ``valid`` (checked)."""
         d = self.device
         out = {"box": torch.empty((n, 4), dtype=torch.float32, device=d), "prob": torch.empty((n,), dtype=torch.float32, device=d),
                "rect": torch.empty((n, 4), dtype=torch.int32, device=d)}
@@ -229,10 +211,33 @@ class Engine:
             elif faces.shape != (n, S, S, 3) or faces.dtype != torch.float32 or not faces.is_contiguous():
                 raise ValueError(f"faces must be a contiguous float32 ({n}, {S}, {S}, 3) tensor")
             out["faces"] = faces
+        else:
+            out["emb"] = torch.empty((n, 512), dtype=torch.float32, device=d)
+        return out
+
+    # server/model.py:47-59 for a batch of sampled frames
+    def detect_embed(self, frames):
+        fr = self._frames(frames)
+        n, H, W, _ = fr.shape
+        out = self._call_outputs(n, crop=False)
+        _lib.check(self.lib.trl_detect_embed(self._h, _ptr(fr), n, H, W, _ptr(out["box"]), _ptr(out["prob"]), _ptr(out["rect"]),
+                                             _ptr(out["valid"]), _ptr(out["emb"]), self._stream()))
+        return out
+
+    # detect_embed / detect_crop split into "queue" and "finish" (trl_detect_embed_begin / _end): one host thread can keep
+    # several engines busy, each on its own stream, without a thread per engine (pipeline.detect_embed_overlapped)
+    def detect_embed_begin(self, frames, crop: bool = False, faces: torch.Tensor | None = None, valid: torch.Tensor | None = None):
+        """Queue detect_embed (or, with ``crop=True``, detect_crop) on the current stream and return at once; the outputs are
+        valid after :meth:`detect_embed_end`.  An engine holds one call in flight.  ``faces`` / ``valid`` (optional, crop mode):
+        caller-owned contiguous destination buffers -- a slot of a ring whose neighbours hold other batches' crops, so several
+        batches can be embedded in one call without a copy (pipeline.detect_embed_overlapped)."""
+        fr = self._frames(frames)
+        n, H, W, _ = fr.shape
+        out = self._call_outputs(n, crop, faces, valid)
+        if crop:
             _lib.check(self.lib.trl_detect_crop_begin(self._h, _ptr(fr), n, H, W, _ptr(out["box"]), _ptr(out["prob"]), _ptr(out["rect"]),
                                                       _ptr(out["valid"]), _ptr(out["faces"]), self._stream()))
         else:
-            out["emb"] = torch.empty((n, 512), dtype=torch.float32, device=d)
             _lib.check(self.lib.trl_detect_embed_begin(self._h, _ptr(fr), n, H, W, _ptr(out["box"]), _ptr(out["prob"]), _ptr(out["rect"]),
                                                        _ptr(out["valid"]), _ptr(out["emb"]), self._stream()))
         self._pending = (out, fr)            # the frame tensor must outlive the queued kernels
@@ -253,11 +258,7 @@ class Engine:
     def detect_crop(self, frames):
         fr = self._frames(frames)
         n, H, W, _ = fr.shape
-        d = self.device
-        S = 80 if self.cfg.embed_mode == 0 else 160
-        out = {"box": torch.empty((n, 4), dtype=torch.float32, device=d), "prob": torch.empty((n,), dtype=torch.float32, device=d),
-               "rect": torch.empty((n, 4), dtype=torch.int32, device=d), "valid": torch.empty((n,), dtype=torch.uint8, device=d),
-               "faces": torch.empty((n, S, S, 3), dtype=torch.float32, device=d)}
+        out = self._call_outputs(n, crop=True)
         _lib.check(self.lib.trl_detect_crop(self._h, _ptr(fr), n, H, W, _ptr(out["box"]), _ptr(out["prob"]), _ptr(out["rect"]),
                                             _ptr(out["valid"]), _ptr(out["faces"]), self._stream()))
         return out

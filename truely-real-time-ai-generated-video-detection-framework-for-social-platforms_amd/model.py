@@ -57,6 +57,9 @@ def analyze_video(frames, fps: int = 30, frame_count: int | None = None, engine:
     return out
 
 
+_RUN_CTX_LOCK = threading.Lock()                          # creates an engine's _RunCtx once, whichever run() call comes first
+
+
 class _RunCtx:
     """What run() keeps between calls, cached on the engine: a second cascade context (two windows in flight), their streams, and
     the pinned / device staging buffers of the reader.  The reference rebuilds its models per call (model.py:18-19); pinning
@@ -69,12 +72,12 @@ class _RunCtx:
         self.engines = [eng, eng.clone()]
         self.streams = [torch.cuda.Stream(eng.device) for _ in self.engines]
         self.lock = threading.Lock()                      # one run() at a time per engine (service workers are per GPU anyway)
-        self.pinned, self.pinned_np, self.raw_dev, self.bgr_dev = [], [], [], []
+        self.pinned, self.pinned_np, self.raw_dev = [], [], []
         self.key = None
 
     def buffers(self, rows: int, row_bytes: int, yuv: bool, H: int, W: int):
-        """Pinned ring of SLOTS windows of ``rows`` frames, one device staging buffer per engine (+ the converted BGR batch for 4:2:0
-        sources).  Grown when a clip needs more, otherwise reused."""
+        """Pinned ring of SLOTS windows of ``rows`` frames, one device staging buffer per engine.  Grown when a clip needs more,
+        otherwise reused."""
         key = (rows, row_bytes, yuv, H, W)
         if self.key != key:
             dev = self.engines[0].device
@@ -230,7 +233,10 @@ def run(video_path_one: str, video_path_two: str, engine: Engine | None = None) 
         eng = engine or default_engine()
         ctx = eng.__dict__.get("_run_ctx")
         if ctx is None:
-            ctx = eng._run_ctx = _RunCtx(eng)
+            with _RUN_CTX_LOCK:
+                ctx = eng.__dict__.get("_run_ctx")
+                if ctx is None:
+                    ctx = eng._run_ctx = _RunCtx(eng)
     except BaseException:
         cap.release()
         raise

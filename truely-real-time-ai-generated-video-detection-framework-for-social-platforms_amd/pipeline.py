@@ -8,9 +8,7 @@ drift state machine (model.py:60-66), which consumes their embeddings in order.
 """
 from __future__ import annotations
 
-import queue
-import threading
-from typing import Callable, Iterable, List, Sequence
+from typing import Callable, List, Sequence
 
 import torch
 
@@ -258,54 +256,3 @@ def detect_embed_overlapped(engines: Sequence[Engine], batches, on_result: Calla
         ov.abandon()
         raise
 
-
-def detect_embed_pipelined(engines: Sequence[Engine], batches: Iterable, on_result: Callable[[int, dict], None] | None = None,
-                           embed_group: int = 1) -> List[dict]:
-    """``engines[j]`` processes batches j, j+F, j+2F, ... (F = len(engines)) on its own stream and thread; with
-    ``embed_group`` > 1 each engine embeds the faces of that many of ITS consecutive batches in one call (see
-    ``detect_embed_grouped``).  Returns the per-batch results in batch order; ``on_result(i, out)`` (optional) is called in
-    batch order on the calling thread as results arrive."""
-    batches = list(batches)
-    F = len(engines)
-    if F == 0:
-        raise ValueError("need at least one engine")
-    if F == 1 or len(batches) <= 1:
-        outs = detect_embed_grouped(engines[0], batches, embed_group)
-        if on_result:
-            for i, out in enumerate(outs):
-                on_result(i, out)
-        return outs
-    dev = engines[0].device
-    streams = [torch.cuda.Stream(dev) for _ in range(F)]
-    qs = [queue.Queue() for _ in range(F)]
-
-    def worker(j):
-        try:
-            torch.cuda.set_device(dev)
-            with torch.cuda.stream(streams[j]):
-                mine = list(range(j, len(batches), F))
-                G = max(1, int(embed_group))
-                for g0 in range(0, len(mine), G):
-                    outs_j = detect_embed_grouped(engines[j], [batches[i] for i in mine[g0:g0 + G]], G)
-                    streams[j].synchronize()      # the consumer uses the tensors on another stream
-                    for out in outs_j:
-                        qs[j].put(out)
-        except BaseException as e:                 # surfaced by the consumer
-            qs[j].put(e)
-
-    ths = [threading.Thread(target=worker, args=(j,), daemon=True) for j in range(F)]
-    for t in ths:
-        t.start()
-    outs = []
-    try:
-        for i in range(len(batches)):
-            item = qs[i % F].get()
-            if isinstance(item, BaseException):
-                raise item
-            if on_result:
-                on_result(i, item)
-            outs.append(item)
-    finally:
-        for t in ths:
-            t.join()
-    return outs

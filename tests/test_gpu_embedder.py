@@ -39,9 +39,10 @@ CASES = [
 ]
 PREC = {0: "f32", 1: "bf16", 2: "fp16"}
 
-# Every (family, bm, bn, bk, pad) the dispatch selects for FaceNet's layer shapes (crops 80 and 160, any face count, the
+# Every (family, bm, bn, bk, pad) the dispatch selects for FaceNet's layer shapes at crops of 80 and 160 px (any face count, the
 # small-map family on or off, f32 / bf16 / fp16); the fn_conv / fn_conv_split4 entries are every tile those families instantiate.
-# Instantiated but never selected for FaceNet: conv_igemm_vec (no tap chunk divides Cin, or inputs past 32-bit element offsets),
+# test_gpu_embedder_sizes.py finds no other path at 75 to 224 px, square or not, within its workspace cap.  Instantiated but never
+# selected for FaceNet at those sizes: conv_igemm_vec (no tap chunk divides Cin, or inputs past 32-bit element offsets),
 # conv_tap48 (Cout 48: R-Net conv2, see test_gpu_stage_nets.py),
 # conv_tap BK 28 and conv_splitk4 (no shipped network selects them: R-Net's conv2, the one Cin 28 layer, takes conv_tap48 where a
 # 128 x 64 tile would apply, and the R-/O-Net dense layers take conv_splitk4_tap), conv_tap with padding and BK 16 (every padded

@@ -186,7 +186,10 @@ int  trl_drift_update(trl_ctx* ctx, void* d_state, const float* d_emb, const uin
 /* SURVEY 8(f)-1, device-side ingest in place of the CPU decode + sampling at server/model.py:43,46:
  * d_nv12 holds n_in decoder-output frames (NV12: H*W luma bytes, then H/2 rows of interleaved U,V);
  * frames 0, step, 2*step, ... are converted to u8 BGR [n_out][H][W][3] (OpenCV's integer BT.601
- * limited-range arithmetic) ready for trl_detect_embed.  step = max(1, int(fps / 7)) (model.py:40). */
+ * limited-range arithmetic) ready for trl_detect_embed.  step = max(1, int(fps / 7)) (model.py:40).
+ * *n_out = ceil(n_in / step).  H even and >= 2, W % 4 == 0 and >= 4, both buffers 4-byte aligned, step >= 1, n_in >= 0:
+ * TRL_ERR_INVALID otherwise, with nothing written.  n_in = 0 is an empty batch: TRL_OK, *n_out = 0, and the two
+ * buffers are not looked at (they may be NULL, as the pointer of a 0-frame tensor is). */
 int  trl_ingest_nv12(trl_ctx* ctx, const uint8_t* d_nv12, int n_in, int H, int W, int step,
                      uint8_t* d_bgr, int* n_out, void* stream);
 /* the same for PLANAR 4:2:0 (I420: Y plane, U plane, V plane -- YUV4MPEG2 files, software decoders): no host-side repacking (ABI v7) */

@@ -153,7 +153,7 @@ def test_nv12_ingest_with_sampling(engine, oracle):
     assert out.shape == (3, H, W, 3)                                    # frames 0, 4, 8 (model.py:46)
     for j, i in enumerate(range(0, n, step)):
         assert np.array_equal(out[j], oracle.nv12_to_bgr(nv12[i], H, W)), i
-    with pytest.raises(Exception):
+    with pytest.raises(ValueError, match="uint8"):
         engine.ingest_nv12(nv12[:, :-3], H, W, step)
 
 

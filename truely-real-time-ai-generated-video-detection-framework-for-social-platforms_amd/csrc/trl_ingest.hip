@@ -14,7 +14,15 @@ namespace {
 
 constexpr int CY = 1220542, CUB = 2116026, CUG = -409993, CVG = -852492, CVR = 1673527, SHIFT = 20;
 
-__device__ __forceinline__ unsigned sat8(int v) { return v < 0 ? 0u : (v > 255 ? 255u : (unsigned)v); }
+// The empty asm keeps the clamp and the byte packing below apart.  Left to itself the compiler fuses `sat8(a >> 20) | sat8(b >> 20) << 8`
+// into gfx950's v_ashr_pk_u8_i32, which writes only 16 bits of its destination, and then ORs bytes 2 and 3 into that register as if
+// its upper half were zero.  The output was right only while register allocation happened to pick a register whose upper half was:
+// a build whose one change was `if` for the grid-stride `for` had stray bits in bytes 2 and 3 of every dword (tests/test_gpu_ingest.py).
+__device__ __forceinline__ unsigned sat8(int v) {
+    unsigned r = v < 0 ? 0u : (v > 255 ? 255u : (unsigned)v);
+    asm("" : "+v"(r));
+    return r;
+}
 
 struct __attribute__((packed, aligned(4))) u32x3 { unsigned x, y, z; };
 
@@ -74,12 +82,13 @@ __global__ __launch_bounds__(256) void k_nv12_to_bgr(const uint8_t* __restrict__
 }  // namespace
 
 static int ingest_420(trl_ctx* c, const uint8_t* d_in, int n_in, int H, int W, int step, bool planar, uint8_t* d_bgr, int* n_out, void* stream) {
-    if (!c || !d_in || !d_bgr || !n_out || n_in < 0 || step < 1) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
+    if (!c || !n_out || n_in < 0 || step < 1) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
     if ((W & 3) || (H & 1) || W < 4 || H < 2) { trl_set_error("4:2:0 ingest needs W %% 4 == 0 and even H (got %dx%d)", W, H); return TRL_ERR_INVALID; }
+    const int no = (int)(((long long)n_in + step - 1) / step);  // frames i with i % step == 0 (model.py:46)
+    if (no == 0) { *n_out = 0; return TRL_OK; }                // an empty batch has no buffers: a 0-frame tensor's pointer is null
+    if (!d_in || !d_bgr) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
     if (((uintptr_t)d_in & 3) || ((uintptr_t)d_bgr & 3)) { trl_set_error("buffers must be 4-byte aligned"); return TRL_ERR_INVALID; }
-    const int no = (n_in + step - 1) / step;                   // frames i with i % step == 0 (model.py:46)
     *n_out = no;
-    if (no == 0) return TRL_OK;
     TRL_HIP(hipSetDevice(c->cfg.device));
     const long long total = (long long)no * (H >> 1) * (W >> 2);
     long long blocks = (total + 255) / 256;

@@ -39,8 +39,9 @@ def bgr_to_nv12(frames: np.ndarray) -> np.ndarray:
 class Nv12Uploader:
     """Pinned double-buffered NV12 upload + device-side colour conversion / sampling for one engine.
 
-    ``upload(nv12_host, step)`` returns the u8 BGR device batch of frames ``0, step, 2*step, ...``; the returned tensor
-    is one of two alternating device buffers, valid until the second-next call (the engine consumes it before then)."""
+    ``upload(nv12_host, step)`` returns the u8 BGR device batch of frames ``0, step, 2*step, ...`` as a fresh tensor
+    (``Engine.ingest_nv12`` allocates it): it stays valid for as long as the caller holds it, whatever is uploaded next.  Only
+    the staging buffers -- ``slots`` pinned host buffers and as many device NV12 buffers -- alternate."""
 
     def __init__(self, engine: Engine, H: int, W: int, max_frames: int, slots: int = 2):
         self.eng, self.H, self.W, self.max_frames = engine, int(H), int(W), int(max_frames)

@@ -351,6 +351,34 @@ int  trl_jpeg_encode(trl_jpeg* enc, const uint8_t* d_bgr, int n, long long frame
  * fewer than *len bytes gives TRL_ERR_CAPACITY and is left untouched. */
 int  trl_jpeg_header(int H, int W, int quality, uint8_t* buf, size_t cap, int* len);
 
+/* ---- Annotation on device frames (run()'s rectangle and caption, server/model.py:67-74) ----------------------------------------
+ * Draws on u8 BGR frames in device memory exactly the bytes annotate.py's own rasteriser (the one used when OpenCV is absent)
+ * draws on a host frame, so that frames can go from the colour conversion to the JPEG encoder without visiting the host.
+ * Needs no context and no weights; the device is the one that owns d_bgr.  (ABI v7, additive) */
+typedef struct {
+    int32_t frame;              /* which frame of the batch, 0 <= frame < n; a frame may be listed once per call */
+    int32_t x0, y0, x1, y1;     /* cv2.rectangle corners (either order), drawn first; may lie outside the frame */
+    int32_t thickness;          /* of the rectangle; 0 = no rectangle */
+    int32_t seg_begin, seg_end; /* this frame's segments: segs[seg_begin .. seg_end), blended in that order after the rectangle */
+    uint8_t rect_bgr[3];
+    uint8_t text_bgr[3];
+    uint8_t reserved[2];
+} trl_draw_frame;               /* 40 bytes */
+/* One anti-aliased thick segment from (x0, y0) to (x0 + dx, y0 + dy): coverage of the pixel centre (x, y) is
+ * clip(reach - distance to the segment, 0, 1) with reach = thickness / 2 + 0.5, L2 = dx*dx + dy*dy (0: a dot).  The caller
+ * computes the six numbers in double precision and rounds each once (annotate.draw_list); the kernel's arithmetic is float32. */
+typedef struct { float x0, y0, dx, dy, L2, reach; } trl_draw_seg;
+/* Device bytes trl_draw needs for lists of these lengths. */
+size_t trl_draw_workspace(int n_frames, int n_segs);
+/* n u8 BGR frames [H][W][3] at d_bgr + k * frame_stride bytes (frame_stride >= H*W*3; H, W >= 1).  `frames` and `segs` are HOST
+ * lists: the call checks them, copies what the kernel needs into d_work (device, 16-byte aligned, work_bytes >=
+ * trl_draw_workspace(n_frames, n_segs)) and queues the copy and the kernel on `stream`; it returns without synchronising, the
+ * host lists may be reused at once, and d_work must stay untouched until the queued work has run.  TRL_ERR_INVALID with nothing
+ * drawn: a frame index outside [0, n) or listed twice, a segment range outside the list, a value that is not finite, a negative
+ * thickness, a stride below H*W*3, sizes below 1, a workspace too small.  n_frames = 0: TRL_OK, nothing is looked at. */
+int  trl_draw(uint8_t* d_bgr, int n, long long frame_stride, int H, int W, const trl_draw_frame* frames, int n_frames,
+              const trl_draw_seg* segs, int n_segs, void* d_work, size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

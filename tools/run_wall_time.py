@@ -3,6 +3,7 @@
 re-encoding of every frame).
 
     python tools/run_wall_time.py [out.json] [--long]
+    python tools/run_wall_time.py [out.json] --output-on=R [--p720]
 
 * BASELINE configs[0]'s shape: the reference's sample clip (test/*.mp4: 640x360, 30 fps, 960 frames, H.264) cannot be decoded
   without OpenCV, so the clip is 960 seeded synthetic frames of that shape in the raw TRLV container (BGR and NV12) and as a
@@ -11,6 +12,10 @@ re-encoding of every frame).
   calls with the output stage skipped (where only the sampled frames are read from the file at all).
 * --long: a 10-minute 720p clip (18,000 frames, 30 fps, 4,500 analysed) as NV12 TRLV and as YUV4MPEG2, output skipped, in
   /dev/shm (25 GB each, written and deleted one after the other).
+* --output-on=R: only the path users hit -- warm calls with the annotated output written, R timed repeats (every one listed,
+  so the spread is known) for the BGR, NV12 and YUV4MPEG2 clips of configs[0]'s shape; --p720 adds a 240-frame 720p clip of
+  each kind (a 360p frame is small enough that per-call overheads dominate).  To compare two trees, run this mode from each of
+  them in turn, several times, in one session.
 Each line also carries the plain file-read rate of the same bytes into pinned memory (no GPU work): the bound of this path."""
 import json
 import os
@@ -67,8 +72,44 @@ def timed(label, src, dst, env, n_frames, step, repeat=1):
             "analysed_frames_per_s": round(n_an / best, 1), "score": int(score), "output_bytes": size}
 
 
+def output_on(repeats, p720):
+    """Warm output-on calls: every repeat's seconds per clip kind."""
+    fps = 30
+    res = {"mode": "warm calls, annotated output written", "repeats": repeats, "runs": []}
+    for H, W, N, hold in [(360, 640, 960, 20)] + ([(720, 1280, 240, 20)] if p720 else []):
+        uniq = truely_amd.synthetic.synthetic_frames(N // hold, H, W, seed=21)
+        nv = bgr_to_nv12(uniq)
+        with tempfile.TemporaryDirectory() as td:
+            srcs = {"BGR": os.path.join(td, "c.trlv"), "NV12": os.path.join(td, "c_nv12.trlv"), "YUV4MPEG2": os.path.join(td, "c.y4m")}
+            video_io.write_raw(srcs["BGR"], uniq[np.arange(N) // hold], fps)
+            video_io.write_raw(srcs["NV12"], nv[np.arange(N) // hold], fps, pixfmt="nv12", size=(W, H))
+            video_io.write_y4m(srcs["YUV4MPEG2"], nv[np.arange(N) // hold], fps, (W, H))
+            dst = os.path.join(td, "out.avi")
+            for kind, src in srcs.items():
+                secs, score, size = [], None, None
+                for k in range(repeats + 1):                      # the first call of a shape is the warm-up
+                    t0 = time.perf_counter()
+                    score = model.run(src, dst)
+                    dt = time.perf_counter() - t0
+                    size = os.path.getsize(dst)
+                    os.remove(dst)
+                    if k:
+                        secs.append(round(dt, 4))
+                res["runs"].append({"clip": f"{kind} {N} frames {W}x{H}", "seconds": secs, "median": round(float(np.median(secs)), 4),
+                                    "min": min(secs), "max": max(secs), "score": int(score), "output_bytes": size})
+    return res
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    rep = [a for a in sys.argv[1:] if a.startswith("--output-on")]
+    if rep:
+        os.environ.pop("TRUELY_WRITE_OUTPUT", None)
+        line = json.dumps(output_on(int(rep[0].partition("=")[2] or 5), "--p720" in sys.argv))
+        print(line)
+        if args:
+            open(args[0], "w").write(line + "\n")
+        return
     H, W, fps, N = 360, 640, 30, 960
     uniq = truely_amd.synthetic.synthetic_frames(48, H, W, seed=21)           # 48 distinct frames, each held for 20 (0.67 s)
     res = {"clip": f"{N} frames {W}x{H} @ {fps} fps (BASELINE configs[0] shape, seeded synthetic frames), {N // 4} analysed",

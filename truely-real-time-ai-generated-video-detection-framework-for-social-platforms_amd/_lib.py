@@ -82,6 +82,8 @@ _SIGNATURES = {
     "trl_jpeg_destroy": (C.c_int, [_vp]),
     "trl_jpeg_encode": (C.c_int, [_vp, _vp, _i, C.c_longlong, _vp, C.c_longlong, _vp, _vp]),
     "trl_jpeg_header": (C.c_int, [_i, _i, _i, _vp, C.c_size_t, C.POINTER(_i)]),
+    "trl_draw_workspace": (C.c_size_t, [_i, _i]),
+    "trl_draw": (C.c_int, [_vp, _i, C.c_longlong, _i, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

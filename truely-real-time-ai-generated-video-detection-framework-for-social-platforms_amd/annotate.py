@@ -14,6 +14,10 @@ When ``cv2`` is importable it is used and the output is OpenCV's, byte for byte.
   Frame" / "Real Frame"), rasterised as anti-aliased thick strokes by exact distance-to-segment coverage.  The glyph
   outlines are this project's own stroke tables in the Hershey style, NOT OpenCV's data: text is legible and lands where
   OpenCV puts it, but is not pixel-identical (the scores, boxes and every decision are unaffected -- annotation is cosmetic).
+
+The same drawing exists on the GPU (``trl_draw``, csrc/trl_annotate.hip), byte for byte: ``DrawList`` / ``draw_list`` lay the
+rectangles and the text out on the host, in float64 like the functions below, and ``draw_device`` / ``annotate_device`` paint
+them on a device batch in place, so that ``run()``'s frames need not visit the host between the decoder and the encoder.
 """
 from __future__ import annotations
 
@@ -127,3 +131,126 @@ def annotate(frame: np.ndarray, index: int, rect, flagged: bool) -> None:
     else:
         rectangle(frame, (x0, y0), (x1, y1), (0, 255, 0), 2)
         put_text(frame, "Real Frame", (x0, y0 - 10), 0.5, (0, 255, 0), 2)
+
+
+# ---- the same drawing as lists for the device kernel (include/truely_hip.h: trl_draw_frame, trl_draw_seg) ----------------------
+FRAME_DTYPE = np.dtype([("frame", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("thickness", "<i4"),
+                        ("seg_begin", "<i4"), ("seg_end", "<i4"), ("rect_bgr", "u1", (3,)), ("text_bgr", "u1", (3,)),
+                        ("reserved", "u1", (2,))])
+SEG_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("dx", "<f4"), ("dy", "<f4"), ("L2", "<f4"), ("reach", "<f4")])
+
+
+def text_segments(text: str, org, scale: float, thickness: int = 1) -> list:
+    """``put_text``'s segments in drawing order as (x0, y0, dx, dy, L2, half + 0.5) in float64: the six Python floats that
+    ``_blend_segment`` feeds into its float32 array expression, where numpy rounds each of them once to float32."""
+    x, y = float(org[0]), float(org[1])
+    half = max(thickness, 1) / 2.0
+    out = []
+    for ch in text:
+        adv, strokes = _G.get(ch, _G[" "])
+        for line in strokes:
+            for (ax, ay), (bx, by) in zip(line[:-1], line[1:]):
+                x0, y0, x1, y1 = x + ax * scale, y - ay * scale, x + bx * scale, y - by * scale
+                dx, dy = x1 - x0, y1 - y0
+                out.append((x0, y0, dx, dy, dx * dx + dy * dy, half + 0.5))
+        x += adv * scale
+    return out
+
+
+def _bgr(color):
+    c = [int(v) for v in color]
+    if len(c) != 3 or any(v < 0 or v > 255 for v in c):
+        raise ValueError(f"colour must be three bytes (B, G, R), got {color!r}")
+    return c
+
+
+class DrawList:
+    """What ``rectangle`` and ``put_text`` would draw on the frames of a batch, collected for one ``trl_draw`` call.  A frame
+    (row of the batch) takes at most one rectangle and one text, the rectangle first -- the order ``annotate`` draws in, so the
+    text overwrites the rectangle; anything more goes into a second list, drawn by a second call."""
+
+    def __init__(self):
+        self.rows: dict = {}                              # row -> [rect | None, (colour, segments) | None]
+        self.nseg = 0
+
+    def rectangle(self, row: int, pt1, pt2, color, thickness: int = 1) -> None:
+        e = self.rows.setdefault(int(row), [None, None])
+        if e[0] is not None or e[1] is not None:
+            raise ValueError(f"frame {row} already has a rectangle or a text: a rectangle comes first, once per list")
+        e[0] = (int(pt1[0]), int(pt1[1]), int(pt2[0]), int(pt2[1]), max(int(thickness), 1), _bgr(color))
+
+    def put_text(self, row: int, text: str, org, scale: float, color, thickness: int = 1) -> None:
+        e = self.rows.setdefault(int(row), [None, None])
+        if e[1] is not None:
+            raise ValueError(f"frame {row} already has a text: one per list")
+        e[1] = (_bgr(color), text_segments(text, org, scale, thickness))
+        self.nseg += len(e[1][1])
+
+    def arrays(self):
+        """(frames, segs): structured arrays in the layout of trl_draw_frame / trl_draw_seg, frames in row order."""
+        frames = np.zeros(len(self.rows), FRAME_DTYPE)
+        segs = np.zeros(self.nseg, SEG_DTYPE)
+        k = 0
+        for i, row in enumerate(sorted(self.rows)):
+            rect, text = self.rows[row]
+            f = frames[i]
+            f["frame"] = row
+            if rect is not None:
+                f["x0"], f["y0"], f["x1"], f["y1"], f["thickness"] = rect[:5]
+                f["rect_bgr"] = rect[5]
+            f["seg_begin"] = k
+            if text is not None:
+                f["text_bgr"] = text[0]
+                if text[1]:
+                    segs[k:k + len(text[1])] = np.array(text[1], np.float64).astype(np.float32).view(SEG_DTYPE).reshape(-1)
+                    k += len(text[1])
+            f["seg_end"] = k
+        return frames, segs
+
+
+def draw_list(notes):
+    """``annotate``'s drawing for the noted frames of a batch: notes = (frame_row, frame_index, rect, flagged) -- ``annotate``'s
+    arguments with the row of the batch in front.  Returns (frames, segs) for ``draw_device``; no notes, empty lists."""
+    dl = DrawList()
+    for row, index, rect, flagged in notes:
+        x0, y0, x1, y1 = (int(v) for v in rect)
+        if flagged:
+            dl.rectangle(row, (x0, y0), (x1, y1), (0, 0, 255), 2)
+            dl.put_text(row, f"AI Detected - Frame {index}", (10, 30), 1, (0, 0, 255), 2)
+        else:
+            dl.rectangle(row, (x0, y0), (x1, y1), (0, 255, 0), 2)
+            dl.put_text(row, "Real Frame", (x0, y0 - 10), 0.5, (0, 255, 0), 2)
+    return dl.arrays()
+
+
+def draw_device(frames, flist, segs, stream=None) -> None:
+    """Paint the lists of ``DrawList.arrays`` / ``draw_list`` on a device batch in place: ``frames`` is a uint8 BGR tensor
+    (n, H, W, 3) on a GPU, each frame dense, any stride between frames.  The work is queued on ``stream`` (default: the current
+    stream) and the call returns without synchronising.  The glyphs are this module's own whether or not OpenCV is installed."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3):
+        raise ValueError("draw_device needs a uint8 (n, H, W, 3) tensor on a GPU")
+    n, H, W = (int(v) for v in frames.shape[:3])
+    if len(flist) == 0 or n == 0:
+        return
+    if tuple(frames.stride()[1:]) != (W * 3, 3, 1) or (n > 1 and frames.stride(0) < H * W * 3):
+        raise ValueError("draw_device draws in place: every frame must be dense (H, W, 3)")
+    flist = np.ascontiguousarray(flist, FRAME_DTYPE)
+    segs = np.ascontiguousarray(segs, SEG_DTYPE)
+    lib = _lib.load()
+    stream = stream if stream is not None else torch.cuda.current_stream(frames.device)
+    need = lib.trl_draw_workspace(len(flist), len(segs))
+    with torch.cuda.stream(stream):
+        work = torch.empty(need, dtype=torch.uint8, device=frames.device)      # (freed back to this stream's pool: stream-ordered)
+    _lib.check(lib.trl_draw(C.c_void_p(frames.data_ptr()), n, frames.stride(0) if n > 1 else H * W * 3, H, W,
+                            flist.ctypes.data_as(C.c_void_p), len(flist), segs.ctypes.data_as(C.c_void_p), len(segs),
+                            C.c_void_p(work.data_ptr()), need, C.c_void_p(stream.cuda_stream)))
+    frames.record_stream(stream)
+
+
+def annotate_device(frames, notes, stream=None) -> None:
+    """``annotate`` on the noted frames of a device batch, in place: notes = (frame_row, frame_index, rect, flagged)."""
+    flist, segs = draw_list(notes)
+    draw_device(frames, flist, segs, stream)

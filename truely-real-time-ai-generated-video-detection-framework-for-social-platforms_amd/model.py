@@ -72,24 +72,27 @@ class _RunCtx:
         self.engines = [eng, eng.clone()]
         self.streams = [torch.cuda.Stream(eng.device) for _ in self.engines]
         self.lock = threading.Lock()                      # one run() at a time per engine (service workers are per GPU anyway)
-        self.pinned, self.pinned_np, self.raw_dev = [], [], []
-        self.key = None
+        self.flat, self.flat_dev = [], []                 # the storage: SLOTS pinned byte buffers, one device buffer per engine
+        self.capacity = 0                                 # bytes each of them holds
 
     def buffers(self, rows: int, row_bytes: int, yuv: bool, H: int, W: int):
-        """Pinned ring of SLOTS windows of ``rows`` frames, one device staging buffer per engine.  Grown when a clip needs more,
-        otherwise reused."""
-        key = (rows, row_bytes, yuv, H, W)
-        if self.key != key:
+        """Pinned ring of SLOTS windows of ``rows`` frames, one device staging buffer per engine, as (rows, row_bytes) views of
+        storage that is kept between calls: grown when a clip needs more, otherwise reused.  (A service alternates between
+        window sizes -- output written or skipped, BGR or 4:2:0 -- and pinning memory costs more than analysing a short clip.)"""
+        need = rows * row_bytes
+        if need > self.capacity:
             dev = self.engines[0].device
-            self.pinned = [torch.empty((rows, row_bytes), dtype=torch.uint8).pin_memory() for _ in range(self.SLOTS)]
-            self.pinned_np = [t.numpy() for t in self.pinned]
-            self.raw_dev = [torch.empty((rows, row_bytes), dtype=torch.uint8, device=dev) for _ in self.engines]
-            self.key = key
-        return self.pinned, self.pinned_np, self.raw_dev
+            self.flat = self.flat_dev = []                # (released first: the two generations need not coexist)
+            self.capacity = 0
+            self.flat = [torch.empty(need, dtype=torch.uint8).pin_memory() for _ in range(self.SLOTS)]
+            self.flat_dev = [torch.empty(need, dtype=torch.uint8, device=dev) for _ in self.engines]
+            self.capacity = need
+        pinned = [t[:need].view(rows, row_bytes) for t in self.flat]
+        return pinned, [t.numpy() for t in pinned], [t[:need].view(rows, row_bytes) for t in self.flat_dev]
 
     def close(self):
-        self.pinned = self.pinned_np = self.raw_dev = []
-        self.key = None
+        self.flat = self.flat_dev = []
+        self.capacity = 0
         self.engines[1].close()
 
 
@@ -205,7 +208,10 @@ def run(video_path_one: str, video_path_two: str, engine: Engine | None = None) 
     Sampled frames (model.py:40,46) travel to the GPU through pinned memory: BGR as they are, 4:2:0 clips (NV12 from a hardware
     decoder, planar I420 from YUV4MPEG2 files) at 1.5 bytes per pixel with the colour conversion on the device
     (``trl_ingest_nv12`` / ``trl_ingest_i420``).  When the output stage is skipped only the sampled frames are read at all from
-    containers that allow it; when it is on, every frame reaches the writer (4:2:0 clips: converted on the device, copied back).
+    containers that allow it; when it is on, every frame reaches the writer.  With the Motion-JPEG sink and its device encoder
+    (the default without OpenCV) every frame of a window is uploaded (4:2:0: converted on the device), the boxes and captions
+    are drawn on the device (``annotate.annotate_device``) and the frames are encoded where they lie: only the JPEG files come
+    back.  Otherwise (raw ``.trlv`` sink, OpenCV, Pillow encoder, ``TRUELY_DRAW=host``) the writer thread draws on host frames.
 
     ``engine`` (optional, not in the reference's signature): the context to run on -- a multi-GPU service keeps one per device
     (service.AnalysisService(gpus=[...])); default: the process-wide engine on the current device.  The second context, the
@@ -213,7 +219,9 @@ def run(video_path_one: str, video_path_two: str, engine: Engine | None = None) 
 
     Environment: TRUELY_ANNOTATE=0 writes the frames without boxes / text; TRUELY_WRITE_OUTPUT=0 skips the output stage
     (benchmarking only: the server requires a non-empty file, server.py:612-627); TRUELY_JPEG=pillow encodes the Motion-JPEG
-    output with Pillow on the writer thread instead of on the engine's GPU (the same bytes, slower)."""
+    output with Pillow on the writer thread instead of on the engine's GPU (the same bytes, slower); TRUELY_DRAW=host draws the
+    annotations on the writer thread and sends host frames to the device encoder (the same bytes; the path before the device
+    drawing existed)."""
     start_time = time.time()
     # model.py:20-22
     if not os.path.exists(video_path_one) or os.path.getsize(video_path_one) == 0:
@@ -263,22 +271,25 @@ def _run_locked(ctx: _RunCtx, cap, fps: int, width: int, height: int, video_path
         total = getattr(cap, "n", 0)
         if total:                                         # a short clip still gets a few windows: reading overlaps the device work
             win = max(16, min(win, -(-((total + step - 1) // step) // 4)))
-    all_rows = write_out and yuv                          # 4:2:0 + output: every frame is converted on the device for the writer
+    jpeg_dev = dev if os.environ.get("TRUELY_JPEG", "device") != "pillow" else None      # MJPEG output encoded on the GPU
+    # frames stay on the device from the upload to the encoder: the sink encodes there and nothing asks for the host drawing
+    on_dev = (write_out and video_io.encodes_on_device(video_path_two, jpeg_dev)
+              and os.environ.get("TRUELY_DRAW", "device") != "host")
+    all_rows = write_out and (yuv or on_dev)              # every frame of a window goes to the device (4:2:0: converted there)
     rows = win * step if all_rows else win
     pinned, pinned_np, raw_dev = ctx.buffers(rows, row_bytes, yuv, height, width)
-    jpeg_dev = dev if os.environ.get("TRUELY_JPEG", "device") != "pillow" else None      # MJPEG output encoded on the GPU
     sink = video_io.open_writer(video_path_two, fps, (width, height), device=jpeg_dev) if write_out else None
-    writer = video_io.AsyncWriter(sink, annotate=os.environ.get("TRUELY_ANNOTATE", "1") != "0")
-    reader = _WindowReader(cap, step, win, pinned_np, all_rows, keep_host=write_out and not yuv, frame_shape=(height, width, 3))
+    writer = video_io.AsyncWriter(sink, annotate=os.environ.get("TRUELY_ANNOTATE", "1") != "0", depth=4 * BATCH * step if on_dev else 64)
+    reader = _WindowReader(cap, step, win, pinned_np, all_rows, keep_host=write_out and not all_rows, frame_shape=(height, width, 3))
     for k in range(len(pinned)):
         reader.free.put((k, None))
     state = eng.drift_state()
-    meta: dict = {}                                       # window index -> (first, nframes, host frames | device BGR frames)
+    meta: dict = {}                                       # window index -> (first, nframes, host frames | device BGR frames, event)
     seen = [0]                                            # frames decoded up to the last delivered window
     last = [None]
 
     def on_result(i, out):
-        first, nfr, frames = meta.pop(i)
+        first, nfr, frames, ready = meta.pop(i)
         seen[0] = first + nfr
         d = eng.drift_update(state, out["emb"], out["valid"], first + nfr, fps, want_flags=write_out, sync=False)   # model.py:60-66
         last[0] = d["result"]
@@ -290,6 +301,9 @@ def _run_locked(ctx: _RunCtx, cap, fps: int, width: int, height: int, video_path
         for j in range(len(vmask)):
             if vmask[j] and sims[j] <= 1.5:               # a face with a previous embedding (model.py:60,67-74)
                 notes[j * step] = (first + j * step, rect[j], bool(flags[j]))
+        if on_dev:                                        # the window's frames are the writer's own: drawn on and encoded in place
+            writer.put_batch(frames[:nfr], [(k,) + notes[k] for k in sorted(notes)], ready)
+            return
         if isinstance(frames, torch.Tensor):
             frames = frames.cpu().numpy()
         for k in range(nfr):
@@ -317,14 +331,22 @@ def _run_locked(ctx: _RunCtx, cap, fps: int, width: int, height: int, video_path
                 ev.record(torch.cuda.current_stream(dev))
                 reader.free.put((slot, ev))               # the reader refills the slot once this copy has finished
                 if yuv:
-                    bgr = eng_j_ingest(j, raw, nrows)
-                    if all_rows:
-                        meta[wi] = (first, nfr, bgr)
-                        return bgr[::step].contiguous()
-                    meta[wi] = (first, nfr, None)
-                    return bgr
-                meta[wi] = (first, nfr, host)
-                return raw.view(nrows, height, width, 3)
+                    bgr = eng_j_ingest(j, raw, nrows)     # a tensor of its own per window: nothing refills it
+                    if not all_rows:
+                        meta[wi] = (first, nfr, None, None)
+                        return bgr
+                elif on_dev:                              # raw_dev[j] is refilled by this context's next window: the writer gets a copy
+                    bgr = raw.view(nrows, height, width, 3).clone()
+                else:
+                    meta[wi] = (first, nfr, host, None)
+                    return raw.view(nrows, height, width, 3)
+                sampled = bgr[::step].contiguous()        # the cascade reads its own gather, the writer draws on `bgr`
+                done = None
+                if on_dev:
+                    done = torch.cuda.Event()
+                    done.record(torch.cuda.current_stream(dev))
+                meta[wi] = (first, nfr, bgr, done)
+                return sampled
 
             def eng_j_ingest(j, raw, nrows):
                 return ctx.engines[j].ingest_nv12(raw, height, width, 1, planar=pixfmt == "i420")

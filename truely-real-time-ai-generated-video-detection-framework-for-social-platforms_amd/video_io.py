@@ -19,7 +19,6 @@ server/model.py:67-77).
 from __future__ import annotations
 
 import os
-import queue
 import struct
 import threading
 
@@ -262,6 +261,16 @@ class AviMjpegWriter:
                 self._append(data)
             self.pending = 0
 
+    def write_device(self, frames):
+        """Encode + append a device batch (n, H, W, 3) uint8 BGR of any length, in chunks of ``BATCH``; device encoder only.
+        Frames handed to ``write()`` before it come first.  Nothing but the files crosses to the host.  The encoder's work is
+        ordered after what is queued on the current stream."""
+        if self.dev_enc is None:
+            raise ValueError("write_device needs the device encoder (encoder='device')")
+        self._flush_device()
+        for data in self.dev_enc.encode(frames):
+            self._append(data)
+
     def write(self, frame):
         """Encode + append.  TRUELY_ENCODE_THREADS > 1 encodes on a small pool and appends in call order (at most 2 x threads
         encoded frames wait in memory); measured here Pillow's encoder holds the GIL for most of a frame (x1.3 with four
@@ -388,26 +397,51 @@ class AviMjpegReader:
 
 class AsyncWriter:
     """Decoupled annotated-output stage.  ``put(frame, note)`` hands a frame (and, for sampled frames that were compared with
-    their predecessor, ``note = (frame_index, rect, flagged)``) to a worker thread that draws (annotate.py) and encodes.
-    ``annotate=False`` skips the drawing, ``sink=None`` skips the stage altogether (benchmarks); the queue is bounded, so a slow
-    encoder applies back-pressure instead of growing memory."""
+    their predecessor, ``note = (frame_index, rect, flagged)``) to a worker thread that draws (annotate.py) and encodes;
+    ``put_batch(frames, notes)`` hands over a whole device batch, drawn on (``trl_draw``) and encoded where it lies.
+    ``annotate=False`` skips the drawing, ``sink=None`` skips the stage altogether (benchmarks); the queue is bounded -- by
+    ``depth`` FRAMES, whether they arrive one by one or in batches -- so a slow encoder applies back-pressure instead of
+    growing memory."""
 
     def __init__(self, sink, annotate: bool = True, depth: int = 64):
+        import collections
         self.sink, self.annotate, self.frames = sink, annotate, 0
         self.err = None
-        self.q = queue.Queue(maxsize=depth)
+        self.depth, self.queued = max(1, int(depth)), 0   # frames the queue may hold / holds
+        self.items = collections.deque()                  # (item, frames in it)
+        self.cv = threading.Condition()
         self.th = threading.Thread(target=self._work, name="truely-writer", daemon=True) if sink is not None else None
         if self.th:
             self.th.start()
 
+    def _push(self, item, n: int):
+        with self.cv:
+            while self.queued and self.queued + n > self.depth:      # (a batch larger than the whole queue goes in alone)
+                self.cv.wait()
+            self.items.append((item, n))
+            self.queued += n
+            self.cv.notify_all()
+
+    def _pop(self):
+        with self.cv:
+            while not self.items:
+                self.cv.wait()
+            item, n = self.items.popleft()
+            self.queued -= n
+            self.cv.notify_all()
+        return item
+
     def _work(self):
         while True:
-            item = self.q.get()
+            item = self._pop()
             if item is None:
                 return
             if self.err is not None:
                 continue                                  # keep draining so the producer never blocks on a dead stage
             try:
+                if len(item) == 3:
+                    self._write_batch(*item)
+                    continue
                 frame, note = item
                 if note is not None and self.annotate:
                     _annotate.annotate(frame, *note)
@@ -415,14 +449,33 @@ class AsyncWriter:
             except BaseException as e:                    # surfaced by close()
                 self.err = e
 
+    def _write_batch(self, frames, notes, ready):
+        import torch
+        stream = self.sink.dev_enc.stream                 # drawing and encoding are ordered on the encoder's stream
+        with torch.cuda.stream(stream):
+            if ready is not None:
+                stream.wait_event(ready)                  # the producer has finished with these frames
+            if notes and self.annotate:
+                _annotate.annotate_device(frames, notes, stream=stream)
+            self.sink.write_device(frames)
+
     def put(self, frame, note=None):
         self.frames += 1
         if self.th:
-            self.q.put((frame, note))
+            self._push((frame, note), 1)
+
+    def put_batch(self, frames, notes=(), ready=None):
+        """A device batch (n, H, W, 3) for a sink with ``write_device``; notes = (row, frame_index, rect, flagged) for the rows to
+        annotate; ``ready``: an event recorded once the producer's work on these frames was queued (the writer's stream waits
+        for it).  The frames are drawn on in place: they are the writer's from here on."""
+        n = int(frames.shape[0])
+        self.frames += n
+        if self.th and n:
+            self._push((frames, list(notes), ready), n)
 
     def close(self):
         if self.th:
-            self.q.put(None)
+            self._push(None, 0)
             self.th.join()
         if self.sink is not None:
             self.sink.release()
@@ -489,9 +542,30 @@ def open_writer(path, fps, size, like_raw: bool = False, device=None):
     return AviMjpegWriter(path, fps, size)
 
 
-def draw_box(frame: np.ndarray, x0, y0, x1, y1, color, thickness=2):
+def encodes_on_device(path, device) -> bool:
+    """Whether ``open_writer(path, ..., device=device)`` gives a sink that encodes on the GPU (``AviMjpegWriter.write_device``)."""
+    return device is not None and cv2 is None and not str(path).lower().endswith(".trlv")
+
+
+def _on_device(frame):
+    return hasattr(frame, "is_cuda") and frame.is_cuda
+
+
+def draw_box(frame, x0, y0, x1, y1, color, thickness=2):
+    """A rectangle on a host frame (H, W, 3) -- or, in place, on a frame that lies on a GPU (a uint8 tensor: ``trl_draw``)."""
+    if _on_device(frame):
+        dl = _annotate.DrawList()
+        dl.rectangle(0, (x0, y0), (x1, y1), color, thickness)
+        _annotate.draw_device(frame.unsqueeze(0), *dl.arrays())
+        return
     _annotate.rectangle(frame, (x0, y0), (x1, y1), color, thickness)
 
 
 def put_text(frame, text, org, scale, color, thickness):
+    """Text on a host frame -- or, in place, on a frame that lies on a GPU (this module's own glyphs)."""
+    if _on_device(frame):
+        dl = _annotate.DrawList()
+        dl.put_text(0, text, org, scale, color, thickness)
+        _annotate.draw_device(frame.unsqueeze(0), *dl.arrays())
+        return
     _annotate.put_text(frame, text, org, scale, color, thickness)

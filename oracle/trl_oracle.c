@@ -1135,7 +1135,7 @@ void orc_nv12_to_bgr(const uint8_t* nv12, int H, int W, uint8_t* bgr) {
         }
 }
 
-/* ---- self test backing a DEVICE-side shortcut (csrc/trl_pnet.hip:pyr_div) ---------------------------------
+/* ---- self test backing a DEVICE-side shortcut (csrc/trl_pyramid.hip:pyr_div) ---------------------------------
  * The pyramid kernel divides by the bin height and width with q0 = RN(a r), e = fma(-b, q0, a), q = fma(e, r, q0),
  * r = RN(1/b), instead of two IEEE divisions.  The oracle itself keeps the true divisions (orc_area_resample_norm);
  * this routine checks, for every bin size kh, kw <= kmax and every possible byte sum s <= 255 kh kw, that both

@@ -1,4 +1,4 @@
-"""GPU tests of the image pyramid at every kernel path build_pyramid() (csrc/trl_pnet.hip) can take, at every frame of a batch,
+"""GPU tests of the image pyramid at every kernel path trl_pyramid_build() (csrc/trl_pyramid.hip) can take, at every frame of a batch,
 and of the cascade at non-default MTCNN min_face_size / factor.
 
 The pyramid pass picks a kernel per level from the frame shape, the batch size and the MTCNN parameters: the fine-level pass (F),
@@ -31,7 +31,7 @@ CASES = [
     (300, 16383, 1, 40, 0.709),    # L2: coarse levels too wide for the streaming pass (sum of h + w > 6144); odd row pitch
     (3316, 3316, 6, 52, 0.709),    # L1 / L2 (bins of 257+ rows) in chunks of 5 frames: launches with f0 > 0; SW8 with 12 row bands
 ]
-# every path and the case that reaches it (the dispatch of build_pyramid, trl_pnet.hip)
+# every path and the case that reaches it (the dispatch of trl_pyramid_build, trl_pyramid.hip)
 REQUIRED = {
     "F": (720, 1280, 3, 20, 0.709),
     "F with 3 levels": (720, 1280, 3, 20, 0.709),
@@ -159,7 +159,7 @@ def reached_paths(case, levels, plan):
         got.add("SW8 + SW4 (second group of 8)")
     for p, lv in zip(plan, levels):
         if p["kernel"].startswith("SW"):
-            # byte offset of a wave's first source byte mod 4 (k_pyramid_stream_w: load_row's `sh`), over frames, rows, segments
+            # byte offset of a wave's first source byte mod 4 (k_pyramid_stream<NL, OwnWave>: load_row's `sh`), over frames, rows, segments
             for f in range(min(n, 4)):
                 for y in range(4):
                     for cs in range(p["col_bands"]):
@@ -196,7 +196,7 @@ def reached_paths(case, levels, plan):
 
 
 def test_plan_covers_every_path(engine_for):
-    """Each path of build_pyramid is reached by the case REQUIRED names for it, as the pass itself records it."""
+    """Each path of trl_pyramid_build is reached by the case REQUIRED names for it, as the pass itself records it."""
     reached = {}
     for case in CASES:
         fr = np.zeros(case[:2] + (3,), np.uint8)[None].repeat(case[2], 0)

@@ -242,7 +242,7 @@ def test_nv12_to_bgr_known_values(oracle):
 
 def test_reciprocal_division_is_exact(oracle):
     """The pyramid kernel divides bin sums by kh and kw through precomputed reciprocals + two fmas
-    (csrc/trl_pnet.hip:pyr_div, enabled for bins <= 96).  Every (kh, kw, sum) triple must reproduce the two
+    (csrc/trl_pyramid.hip:pyr_div, enabled for bins <= 96).  Every (kh, kw, sum) triple must reproduce the two
     IEEE divisions of the reference expression bit for bit -- exhaustive, ~5.5e9 cases, a few seconds."""
     assert oracle.selftest_recip_div(96) == 0
 

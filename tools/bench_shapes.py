@@ -1,6 +1,6 @@
 """Supplementary timings at BASELINE.json's other frame shapes (fp32 path, synthetic frames); NOT the headline metric.
 python tools/bench_shapes.py > gpurun_out/shapes.json"""
-import sys; sys.path.insert(0, "/root/repo")
+import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import json, statistics, time
 import torch, truely_amd
 from truely_amd.engine import Engine

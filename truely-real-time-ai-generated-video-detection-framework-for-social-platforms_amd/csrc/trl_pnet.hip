@@ -1,13 +1,8 @@
 // trl_pnet.hip -- MTCNN stage 1 (PNet over the image pyramid) for gfx950, the dominant kernel of the
 // hot path (83 % of the conv FLOPs at 720p; server/model.py:47 -> detect_face stage 1).
 //
-// Per batch of frames: one k_pyramid launch per (level, Infinity-Cache-sized frame chunk), then ONE fused launch.
-//
-//  k_pyramid      u8 BGR frames -> every pyramid level, imresample (F.interpolate mode="area") +
-//                 (x-127.5)*0.0078125, stored as three floats {b,g,r} per pixel (12 B, streamed past the caches).  One
-//                 lane (fine levels) or lane group (coarse levels) per output pixel, dword-aligned 16/12-byte
-//                 loads + v_dot4 byte sums (integer-exact, order independent), bin edges by exact multiply-high
-//                 division, bin mean by the exhaustively verified reciprocal division (pyr_div).
+// Per batch of frames: the image pyramid of every frame (trl_pyramid.hip: u8 BGR -> every level as three floats per pixel), then
+// ONE fused launch over it.
 //
 //  k_pnet_fused   ONE persistent launch over all (frame, level, 16x16-cell tile) work items.  Per tile,
 //                 entirely in LDS / registers:
@@ -26,15 +21,13 @@
 //                 compile-time offsets, pooling precedes PReLU when the slopes allow, edge logic only on edge tiles.
 //                 blockIdx -> tile mapping keeps an XCD on a contiguous run of tiles (halo rows of
 //                 neighbouring tiles hit the same L2).
-#include "trl_ctx.h"
+#include "trl_pyramid.h"
 #include <stdlib.h>
 #include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes at dword alignment
-struct __attribute__((packed, aligned(4))) u32x3_a4 { unsigned x, y, z; };
 
 namespace {
 
@@ -66,36 +59,27 @@ constexpr int VCARRY_C = 2 * C2_T * C2_LD;           // 612 floats: 2 conv2 rows
 constexpr int DYN_LDS = (144 * 32 + BAND * (CARRY_P + CARRY_C) + VCARRY_P + VCARRY_C) * 4;   // conv3 weights + the carry strips (dynamic: static LDS is capped at 64 KB)
 static_assert((144 * 32) % 4 == 0 && CARRY_P % 4 == 0 && CARRY_C % 4 == 0 && VCARRY_P % 4 == 0, "strips stay 16-byte aligned");
 
-// One pyramid pixel = three floats (a fourth padding float would be 25 % of the pyramid's write + read traffic).
-struct PyrPx { float b, g, r; };
-typedef float f32x3_nt __attribute__((ext_vector_type(3), aligned(4)));
-
+// A level as k_pnet_fused reads it.  The kernel indexes lv[] by sizeof(PLevel) and loads its members by their offsets, so both are
+// pinned: the words `kept*` (and PnetArgs::kept) are where members of the pyramid kernels lay before those moved to trl_pyramid.hip;
+// nothing writes or reads them, and taking them out would change the fused kernel's code.
 struct PLevel {
     int h, w, oh, ow;        // level size, PNet map size
     int tiles_x, tile0;      // tiles per row, first tile index of the level inside a frame
     int tiles_y;             // tile rows
     unsigned bmagic;         // ceil(2^32 / (BAND * tiles_x)): band of a tile index
     int pix0;                // pixel offset of the level inside a frame's pyramid
-    int pix_pad;             // h*w rounded up to 64 (pyramid slots of the level)
-    int gshift, work0;       // pyramid kernel: log2(lanes per pixel), first thread of the level inside a frame
-    int ytab0, xtab0;        // offsets of the level's row / column bin-edge tables
-    int mode, nd, grshift;   // pyramid kernel path, re-aligned dwords per row (mode 0), log2 groups per row (mode 1)
-    unsigned wmagic;         // ceil(2^32 / w): pixel / w by __umulhi
+    int kept0[9];
     unsigned txmagic;        // ceil(2^32 / tiles_x): tile decode stays on the scalar unit
-    int khA, kwA, khmax, kwmax;   // adaptive-pool bins of the level are khA or khA+1 rows (kwA / kwA+1 columns)
-    float rkh[2], rkw[2];    // RN(1/khA), RN(1/(khA+1)), same for kw: reciprocal division (see pyr_div)
-    int fastdiv;             // bin sizes small enough for the exhaustively verified reciprocal division
-    unsigned vmA[4], vmB[4]; // mode 0: valid-byte masks of the 4 re-aligned dwords of a row for bins kwA / kwA+1 wide
-    unsigned hmagic;         // ceil(2^32 / h); with wmagic: bin edges by multiply-high when 'arith' (no table load in the
-    int arith;               // dependent-latency chain of a pixel): requires H*h*h < 2^32 and W*w*w < 2^32
+    int kept1[19];
     float scale;
     int cap, rec0;           // candidate records of the level: slots per frame, first slot inside a frame's block (LvLayout)
 };
+static_assert(sizeof(PLevel) == 164 && offsetof(PLevel, txmagic) == 72 && offsetof(PLevel, scale) == 152, "k_pnet_fused's argument layout");
 struct PnetArgs {
     const PyrPx* pyr; long long pyr_stride;    // pixels per frame
     int n_frames, L, tiles_per_frame, H, W;
     unsigned tpf_magic;                        // ceil(2^32 / tiles_per_frame)
-    long long work_per_frame;                  // pyramid kernel threads per frame
+    long long kept;
     PLevel lv[16];
     const float *w1, *w2, *w3, *wh;            // [Kpad][32] zero padded
     const float *b1, *b2, *b3, *bh, *s1, *s2, *s3;
@@ -109,421 +93,6 @@ struct PnetArgs {
     unsigned long long* clk;                   // [0] = earliest workgroup start, [1] = latest workgroup end (device wall clock); DBG: [2..] phase clocks
     int prof;                                  // DBG instantiation: accumulate the per-phase wave clocks
 };
-
-// ---- pyramid -------------------------------------------------------------------------------------
-// One LANE GROUP of G lanes per output pixel (G = 1, 4, 16 or 64 by level: coarse levels average
-// thousands of source bytes per pixel, so their bins are split across lanes and summed with xor
-// shuffles -- integer sums, exact in any order).  Bytes are fetched as aligned dwords; the three
-// channel sums of a dword are three v_dot4_u32_u8 against 0/1 byte masks selected by the dword's
-// phase (byte offset mod 3) inside the BGR span.
-__device__ __forceinline__ void dword_sums(unsigned v, int rel, int nbytes, unsigned& s0, unsigned& s1, unsigned& s2) {
-    // rel = byte offset of this dword relative to the first byte of the span (-3 .. nbytes-1)
-    const int lo = rel < 0 ? -rel : 0;
-    const int hi = (nbytes - rel) < 4 ? (nbytes - rel) : 4;
-    const unsigned vm = (hi >= 4 ? 0xFFFFFFFFu : ((1u << (8 * hi)) - 1u)) & ~((1u << (8 * lo)) - 1u);
-    v &= vm;
-    const int phase = (rel + 3) % 3;   // channel of byte 0 of the dword
-    const unsigned m0 = phase == 0 ? 0x01000001u : (phase == 1 ? 0x00010000u : 0x00000100u);
-    const unsigned m1 = phase == 0 ? 0x00000100u : (phase == 1 ? 0x01000001u : 0x00010000u);
-    const unsigned m2 = phase == 0 ? 0x00010000u : (phase == 1 ? 0x00000100u : 0x01000001u);
-    s0 = __builtin_amdgcn_udot4(v, m0, s0, false);
-    s1 = __builtin_amdgcn_udot4(v, m1, s1, false);
-    s2 = __builtin_amdgcn_udot4(v, m2, s2, false);
-}
-
-// Bin edges are precomputed on the host (one packed (start | end<<16) word per output row / column of
-// every level): the kernel does no 64-bit or repeated integer division.  grid = (blocks, frames).
-// Three per-level modes (wave-uniform):
-//   0  small bins (<= 5 px wide): one lane per pixel; each source row is 4-5 aligned dwords re-aligned to
-//      the bin's first byte with v_alignbyte, so the BGR byte->channel masks are compile-time constants;
-//   1  big bins, row pitch a multiple of 4 bytes: a lane owns one 12-byte group (4 whole pixels, constant
-//      channel phase) of the bin for every (rl-th) source row: 3 coalesced loads + 9 v_dot4 per 12 bytes;
-//   2  generic fallback (odd row pitch): flattened (row, dword) walk with per-dword masks.
-__device__ __forceinline__ unsigned chan_mask(int p, int c) {   // dword whose byte 0 has channel p: bytes of channel c
-    const int d = (c - p + 3) % 3;                               // byte index of the first byte of channel c
-    return d == 0 ? 0x01000001u : (d == 1 ? 0x00000100u : 0x00010000u);
-}
-__device__ __forceinline__ unsigned valid_bytes(int rel, int nbytes) {   // 0xFF for bytes b of the dword with 0 <= rel+b < nbytes
-    const int lo = rel < 0 ? -rel : 0;
-    int hi = nbytes - rel; hi = hi < 0 ? 0 : (hi > 4 ? 4 : hi);
-    if (lo >= hi) return 0u;
-    return (hi >= 4 ? 0xFFFFFFFFu : ((1u << (8 * hi)) - 1u)) & ~((1u << (8 * lo)) - 1u);
-}
-
-// The pyramid is written once and read once, much later, by the PNet kernel: stream it past the caches so the source
-// frame (re-read by every level) keeps its L2 / Infinity Cache lines.
-typedef float f32x4_nt __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void pyr_store(PyrPx* dst, const float4& v) {
-    static_assert(sizeof(PyrPx) == 12, "layout");
-    f32x3_nt t = {v.x, v.y, v.z};
-    __builtin_nontemporal_store(t, reinterpret_cast<f32x3_nt*>(dst));
-}
-
-// Correctly rounded a / b from r = RN(1/b) (Markstein): q0 = RN(a r), e = a - b q0 (exact in one fma), q = RN(q0 + e r).
-// For a = integer sums up to 255 kh kw and the bin sizes used here (kh, kw <= 96) the result equals the IEEE
-// quotient for EVERY input -- checked exhaustively by the oracle's self test (oracle/trl_oracle.c:orc_selftest_recip_div);
-// larger bins take the true division.  3 VALU ops instead of the ~11 of v_div_scale/v_rcp/v_div_fmas/v_div_fixup.
-__device__ __forceinline__ float pyr_div(float a, float b, float r) {
-    const float q0 = a * r;
-    const float e = __builtin_fmaf(-b, q0, a);
-    return __builtin_fmaf(e, r, q0);
-}
-__device__ __forceinline__ float pyr_norm(unsigned s, int kh, int kw, const PLevel& g) {
-    const float a = (float)s, fkh = (float)kh, fkw = (float)kw;
-    float q;
-    if (g.fastdiv) {
-        const float r1 = kh == g.khA ? g.rkh[0] : g.rkh[1], r2 = kw == g.kwA ? g.rkw[0] : g.rkw[1];
-        q = pyr_div(pyr_div(a, fkh, r1), fkw, r2);
-    } else {
-        q = a / fkh / fkw;
-    }
-    return (q - 127.5f) * 0.0078125f;
-}
-
-struct PyrArgs { int H, W, n_frames, f0; long long pyr_stride; PLevel g; };
-
-// threads q = q0, q0 + qstep, ... of level g of frame f
-template <int MODE, typename A>
-__device__ __forceinline__ void pyr_level(const uint8_t* __restrict__ frames, const A& a, const PLevel& g, const uint32_t* __restrict__ tab,
-                                          PyrPx* __restrict__ pyr, int f, int q0, int qstep) {
-    const int per_frame = g.pix_pad << g.gshift;            // threads of this level per frame
-    constexpr int mode = MODE;
-    const uint32_t* base32 = reinterpret_cast<const uint32_t*>(frames);
-    const long long fbase = (long long)f * a.H * a.W * 3;
-    const long long last_dw = ((long long)a.n_frames * a.H * a.W * 3 - 1) >> 2;
-    const int row_bytes = a.W * 3;
-    for (int q = q0; q < per_frame; q += qstep) {
-        const int w = g.w, gsh = g.gshift, G = 1 << gsh;
-        const int pixel = q >> gsh, sub = q & (G - 1);
-        const bool valid = pixel < g.h * w;
-        unsigned s0 = 0, s1 = 0, s2 = 0;
-        int kh = 1, kw = 1;
-        if (valid) {
-            int oy = (int)__umulhi((unsigned)pixel, g.wmagic);       // floor(pixel / w) or one above it (large levels): fix up
-            oy -= (oy * w > pixel) ? 1 : 0;
-            const int ox = pixel - oy * w;
-            const uint32_t ty = tab[g.ytab0 + oy], tx = tab[g.xtab0 + ox];
-            const int ys = ty & 0xFFFF, ye = ty >> 16, xs = tx & 0xFFFF, xe = tx >> 16;
-            kh = ye - ys; kw = xe - xs;
-            const int nbytes = kw * 3;
-            const long long o0 = fbase + (long long)ys * row_bytes + xs * 3;   // first byte of the bin
-            if (mode == 1) {
-                const int grsh = g.grshift, grp = sub & ((1 << grsh) - 1), rlane = sub >> grsh, rl = G >> grsh;
-                const int sh = (int)(o0 & 3);
-                const int rel = -sh + 12 * grp;                      // offset of this lane's group relative to the bin's first byte
-                if (rel < nbytes) {
-                    const int ph = (3 - sh % 3) % 3;                 // channel of the byte at the aligned start (12*grp keeps it)
-                    unsigned mk[3][3];
-#pragma unroll
-                    for (int j = 0; j < 3; j++) {
-                        const unsigned vb = valid_bytes(rel + 4 * j, nbytes) & 0x01010101u;
-#pragma unroll
-                        for (int c = 0; c < 3; c++) mk[j][c] = chan_mask((ph + j) % 3, c) & vb;
-                    }
-                    long long dw = ((o0 - sh) >> 2) + 3 * grp + (long long)rlane * (row_bytes >> 2);
-                    const long long dstep = (long long)rl * (row_bytes >> 2);
-                    for (int y = rlane; y < kh; y += 4 * rl, dw += 4 * dstep) {
-                        unsigned w3[4][3];
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const bool act = y + r * rl < kh;
-                            const long long d = act ? dw + r * dstep : dw;
-                            if (d + 2 <= last_dw) {
-                                const u32x3_a4 v3 = *reinterpret_cast<const u32x3_a4*>(base32 + d);
-                                w3[r][0] = v3.x; w3[r][1] = v3.y; w3[r][2] = v3.z;
-                            } else {
-                                w3[r][0] = base32[d]; w3[r][1] = base32[d + 1 <= last_dw ? d + 1 : last_dw]; w3[r][2] = base32[last_dw];
-                            }
-                            if (!act) { w3[r][0] = 0u; w3[r][1] = 0u; w3[r][2] = 0u; }
-                        }
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            s0 = __builtin_amdgcn_udot4(w3[r][0], mk[0][0], s0, false); s1 = __builtin_amdgcn_udot4(w3[r][0], mk[0][1], s1, false);
-                            s2 = __builtin_amdgcn_udot4(w3[r][0], mk[0][2], s2, false);
-                            s0 = __builtin_amdgcn_udot4(w3[r][1], mk[1][0], s0, false); s1 = __builtin_amdgcn_udot4(w3[r][1], mk[1][1], s1, false);
-                            s2 = __builtin_amdgcn_udot4(w3[r][1], mk[1][2], s2, false);
-                            s0 = __builtin_amdgcn_udot4(w3[r][2], mk[2][0], s0, false); s1 = __builtin_amdgcn_udot4(w3[r][2], mk[2][1], s1, false);
-                            s2 = __builtin_amdgcn_udot4(w3[r][2], mk[2][2], s2, false);
-                        }
-                    }
-                }
-            } else {
-                const int ndw = (nbytes + 6) >> 2;            // dwords per row for the worst alignment
-                int row = 0, d = sub;
-                while (d >= ndw) { d -= ndw; row++; }
-                while (row < kh) {
-                    const long long o = o0 + (long long)row * row_bytes;
-                    const long long al = (o & ~3ll) + 4 * d;
-                    const int rel = (int)(al - o);
-                    if (rel < nbytes) dword_sums(base32[al >> 2], rel, nbytes, s0, s1, s2);
-                    d += G;
-                    while (d >= ndw) { d -= ndw; row++; }
-                }
-            }
-        }
-        for (int off = G >> 1; off >= 1; off >>= 1) {
-            s0 += __shfl_xor((int)s0, off, 64); s1 += __shfl_xor((int)s1, off, 64); s2 += __shfl_xor((int)s2, off, 64);
-        }
-        if (sub == 0 && pixel < g.pix_pad) {
-            float4 o4;
-            o4.x = valid ? pyr_norm(s0, kh, kw, g) : 0.f;
-            o4.y = valid ? pyr_norm(s1, kh, kw, g) : 0.f;
-            o4.z = valid ? pyr_norm(s2, kh, kw, g) : 0.f;
-            o4.w = 0.f;
-            pyr_store(pyr + ((long long)f * a.pyr_stride + g.pix0 + pixel), o4);
-        }
-    }
-}
-
-// Mode 0 (bins <= 5 px wide and <= 5 rows: the three finest levels = 85 % of the output pixels): one lane per pixel.
-// VALU-bound, so everything per-row is pared down: the frame base is a scalar, the lane offset 32-bit; rows are
-// unrolled to the level's khmax (scalar) and only the last one can be dead; the byte masks of the two possible bin
-// widths are picked, not computed.
-// ROWS = the level's khmax (3..5), FOUR = bins reach 5 px (a 5th dword per row).  Two pixels per thread per pass: the row
-// loads of both are issued before either is consumed -- the kernel is bound by memory latency at 8 waves per SIMD, so
-// loads in flight per wave are what counts (specialising on ROWS / FOUR keeps it under 64 VGPRs).
-template <int ROWS, bool FOUR, typename A>
-__device__ __forceinline__ void pyr_level0(const uint8_t* __restrict__ frames, const A& a, const PLevel& g, const uint32_t* __restrict__ tab,
-                                           PyrPx* __restrict__ pyr, int f, int q0, int qstep) {
-    constexpr int ND = FOUR ? 5 : 4;                                                 // dwords fetched per row
-    const long long fbase = (long long)f * a.H * a.W * 3;
-    const long long total = (long long)a.n_frames * a.H * a.W * 3;
-    const int fb3 = (int)(fbase & 3);
-    const char* fptr = reinterpret_cast<const char*>(frames) + (fbase - fb3);     // dword aligned, scalar
-    const int row_bytes = a.W * 3;
-    const bool lastf = f == a.n_frames - 1;                                          // other frames may read into their successor
-    const unsigned avail = ((unsigned)fb3 + (unsigned)a.H * row_bytes + 3u) & ~3u;  // bytes from fptr to the end of the last dword
-    struct Px { unsigned ww[ROWS][ND]; unsigned shv[ROWS]; int kh, kw; bool valid; };
-    auto prep = [&](int pixel, Px& p) __attribute__((always_inline)) {
-        p.valid = pixel < g.h * g.w;
-        p.kh = 1; p.kw = 1;
-        if (!p.valid) return;
-        int oy = (int)__umulhi((unsigned)pixel, g.wmagic);       // floor(pixel / w) or one above it (large levels): fix up
-        oy -= (oy * g.w > pixel) ? 1 : 0;
-        const int ox = pixel - oy * g.w;
-        int ys, kh, xs, kw;
-        if (g.arith) {   // adaptive_avg_pool2d edges [floor(i*in/out), ceil((i+1)*in/out)) without touching memory
-            ys = (int)__umulhi((unsigned)(oy * a.H), g.hmagic);
-            kh = (int)__umulhi((unsigned)((oy + 1) * a.H + g.h - 1), g.hmagic) - ys;
-            xs = (int)__umulhi((unsigned)(ox * a.W), g.wmagic);
-            kw = (int)__umulhi((unsigned)((ox + 1) * a.W + g.w - 1), g.wmagic) - xs;
-        } else {
-            const uint32_t ty = tab[g.ytab0 + oy], tx = tab[g.xtab0 + ox];
-            ys = ty & 0xFFFF; kh = (int)(ty >> 16) - ys; xs = tx & 0xFFFF; kw = (int)(tx >> 16) - xs;
-        }
-        p.kh = kh; p.kw = kw;
-        const unsigned lo0 = (unsigned)(ys * row_bytes + xs * 3 + fb3);        // byte offset from fptr of the bin's first byte
-        // the aligned 16/20-byte fetch of the LAST row may run past the end of the frame buffer only for the very
-        // last pixels of the last frame: those take per-dword clamped loads
-        const bool safe = !lastf || (lo0 & ~3u) + (unsigned)((kh - 1) * row_bytes) + 4u * ND <= avail;
-#pragma unroll
-        for (int r = 0; r < ROWS; r++) {
-            const unsigned lo = lo0 + (unsigned)((r < kh ? r : kh - 1) * row_bytes);
-            p.shv[r] = lo & 3u;
-            const char* q = fptr + (lo & ~3u);
-            if (safe) {
-                const u32x4_a4 v4 = *reinterpret_cast<const u32x4_a4*>(q);
-                p.ww[r][0] = v4[0]; p.ww[r][1] = v4[1]; p.ww[r][2] = v4[2]; p.ww[r][3] = v4[3];
-                if (FOUR) p.ww[r][ND - 1] = *reinterpret_cast<const uint32_t*>(q + 16);
-            } else {
-                const long long lim = ((total - 1) >> 2) * 4 - (fbase - fb3);   // offset of the last dword holding frame bytes
-#pragma unroll
-                for (int j = 0; j < ND; j++) {
-                    const long long o = (long long)(lo & ~3u) + 4 * j;
-                    p.ww[r][j] = *reinterpret_cast<const uint32_t*>(fptr + (o < lim ? o : lim));
-                }
-            }
-        }
-    };
-    auto finish = [&](int pixel, const Px& p) __attribute__((always_inline)) {
-        if (pixel >= g.pix_pad) return;
-        float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (p.valid) {
-            const bool wA = p.kw == g.kwA;                                      // a level has two bin widths: pick, don't compute
-            const unsigned vm0 = wA ? g.vmA[0] : g.vmB[0], vm1 = wA ? g.vmA[1] : g.vmB[1], vm2 = wA ? g.vmA[2] : g.vmB[2],
-                           vm3 = wA ? g.vmA[3] : g.vmB[3];
-            unsigned s0 = 0, s1 = 0, s2 = 0;
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) {
-                const bool act = r < p.kh;                                       // only the last unrolled row can be dead
-                const unsigned sh = p.shv[r];
-                const unsigned d0 = __builtin_amdgcn_alignbyte(p.ww[r][1], p.ww[r][0], sh) & (act ? vm0 : 0u);
-                const unsigned d1 = __builtin_amdgcn_alignbyte(p.ww[r][2], p.ww[r][1], sh) & (act ? vm1 : 0u);
-                const unsigned d2 = __builtin_amdgcn_alignbyte(FOUR ? p.ww[r][3] : 0u, p.ww[r][2], sh) & (act ? vm2 : 0u);
-                s0 = __builtin_amdgcn_udot4(d0, 0x01000001u, s0, false); s1 = __builtin_amdgcn_udot4(d0, 0x00000100u, s1, false);
-                s2 = __builtin_amdgcn_udot4(d0, 0x00010000u, s2, false);
-                s0 = __builtin_amdgcn_udot4(d1, 0x00010000u, s0, false); s1 = __builtin_amdgcn_udot4(d1, 0x01000001u, s1, false);
-                s2 = __builtin_amdgcn_udot4(d1, 0x00000100u, s2, false);
-                s0 = __builtin_amdgcn_udot4(d2, 0x00000100u, s0, false); s1 = __builtin_amdgcn_udot4(d2, 0x00010000u, s1, false);
-                s2 = __builtin_amdgcn_udot4(d2, 0x01000001u, s2, false);
-                if (FOUR) {
-                    const unsigned d3 = __builtin_amdgcn_alignbyte(p.ww[r][4], p.ww[r][3], sh) & (act ? vm3 : 0u);
-                    s0 = __builtin_amdgcn_udot4(d3, 0x01000001u, s0, false); s1 = __builtin_amdgcn_udot4(d3, 0x00000100u, s1, false);
-                    s2 = __builtin_amdgcn_udot4(d3, 0x00010000u, s2, false);
-                }
-            }
-            o4.x = pyr_norm(s0, p.kh, p.kw, g); o4.y = pyr_norm(s1, p.kh, p.kw, g); o4.z = pyr_norm(s2, p.kh, p.kw, g);
-        }
-        pyr_store(pyr + ((long long)f * a.pyr_stride + g.pix0 + pixel), o4);
-    };
-    for (int pixel = q0; pixel < g.pix_pad; pixel += 2 * qstep) {
-        Px pa, pb;
-        prep(pixel, pa);
-        prep(pixel + qstep, pb);          // beyond pix_pad: invalid, nothing loaded, nothing stored
-        finish(pixel, pa);
-        finish(pixel + qstep, pb);
-    }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void k_pyramid(const uint8_t* __restrict__ frames, PyrArgs a, const uint32_t* __restrict__ tab,
-                                                 PyrPx* __restrict__ pyr) {
-    if (MODE == 0) pyr_level0<5, true>(frames, a, a.g, tab, pyr, a.f0 + blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-    else pyr_level<MODE>(frames, a, a.g, tab, pyr, a.f0 + blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-}
-
-// mode 0, specialised on the level's row count / dword count (register budget = occupancy = loads in flight)
-template <int ROWS, bool FOUR>
-__global__ __launch_bounds__(256) void k_pyramid0(const uint8_t* __restrict__ frames, PyrArgs a, const uint32_t* __restrict__ tab,
-                                                  PyrPx* __restrict__ pyr) {
-    pyr_level0<ROWS, FOUR>(frames, a, a.g, tab, pyr, a.f0 + blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-}
-
-// The three finest levels in ONE pass over the source (round 3).  A workgroup owns a source tile (a band of `band_cols` source
-// columns x a strip of `strip_rows` source rows); wave L walks the tile's source rows for level L: its 64 lanes are the output
-// columns of that level whose bins START in the band, its output rows those whose bins start in the strip (a bin may run past the
-// tile: the wave simply reads on).  The three waves read the same source rows at about the same time, so the frame bytes come from
-// HBM once and from the CU's L1 / the L2 for the other two levels -- the per-level kernels above re-read the whole frame chunk
-// from the Infinity Cache for every level.  Inside a wave: a source row's three channel sums are formed once and added to the (at
-// most two: H >= h) bins that contain it, column quantities are per-lane constants, row quantities wave-uniform (SALU); integer
-// sums, the same division and normalisation (pyr_norm): bit-identical pixels.  D source rows in flight per lane.
-struct PyrFineArgs {
-    int H, W, n_frames, f0; long long pyr_stride;
-    int nlev, band_cols, strip_rows, n_bands, n_strips;
-    int own0;                      // offset in `tab` of the ownership table: [level][band] (ox_lo, ox_hi), then [level][strip] (oy_lo, oy_hi)
-    PLevel g[3];
-};
-template <bool FOUR>
-__device__ __forceinline__ void pyr_fine_wave(const uint8_t* __restrict__ frames, const PyrFineArgs& a, const PLevel& g, const uint32_t* __restrict__ tab,
-                                              PyrPx* __restrict__ pyr, int f, int ox_lo, int ox_hi, int oy0, int oy1, int lane, bool pad_wave) {
-    constexpr int ND = FOUR ? 5 : 4, D = 6;                                          // (4 and 8 rows in flight measured the same)
-    PyrPx* const out = pyr + ((long long)f * a.pyr_stride + g.pix0);
-    if (pad_wave && g.h * g.w + lane < g.pix_pad) pyr_store(out + (g.h * g.w + lane), make_float4(0.f, 0.f, 0.f, 0.f));   // the level's padding pixels: zeros, as ever
-    if (oy0 >= oy1 || ox_lo >= ox_hi) return;                                        // wave-uniform
-    const int ox = ox_lo + lane;
-    const bool valid = ox < ox_hi;
-    // ---- column quantities: constants of the lane for the whole strip ----
-    const uint32_t tx = tab[g.xtab0 + (valid ? ox : ox_hi - 1)];
-    const int xs = tx & 0xFFFF, kw = (int)(tx >> 16) - xs;
-    const long long fbase = (long long)f * a.H * a.W * 3;
-    const int fb3 = (int)(fbase & 3);
-    const char* fptr = reinterpret_cast<const char*>(frames) + (fbase - fb3);      // dword aligned, scalar
-    const unsigned row_bytes = (unsigned)a.W * 3u;
-    const unsigned lx = (unsigned)(xs * 3 + fb3);                                   // the bin's first byte inside a source row, from fptr
-    const bool wA = kw == g.kwA;
-    const unsigned vm0 = wA ? g.vmA[0] : g.vmB[0], vm1 = wA ? g.vmA[1] : g.vmB[1], vm2 = wA ? g.vmA[2] : g.vmB[2], vm3 = wA ? g.vmA[3] : g.vmB[3];
-    const bool lastf = f == a.n_frames - 1;
-    const long long lim = ((((long long)a.n_frames * a.H * a.W * 3) - 1) >> 2) * 4 - (fbase - fb3);   // last dword holding frame bytes, from fptr
-    // a source row: ND aligned dwords from the bin's first byte.  SLOW = a strip that reads the last row of the last frame, which
-    // may not be read past the end of the buffer: clamped dwords (the pipelined loop stays single-path)
-    auto fetch = [&](auto SLOW_T, int y, unsigned (&w)[ND]) __attribute__((always_inline)) {
-        const unsigned lo = (unsigned)y * row_bytes + lx;
-        const char* q = fptr + (lo & ~3u);
-        if (!decltype(SLOW_T)::value) {
-            const u32x4_a4 v4 = *reinterpret_cast<const u32x4_a4*>(q);
-            w[0] = v4[0]; w[1] = v4[1]; w[2] = v4[2]; w[3] = v4[3];
-            if (FOUR) w[ND - 1] = *reinterpret_cast<const uint32_t*>(q + 16);
-        } else {
-#pragma unroll
-            for (int j = 0; j < ND; j++) {
-                const long long o = (long long)(lo & ~3u) + 4 * j;
-                w[j] = *reinterpret_cast<const uint32_t*>(fptr + (o < lim ? o : lim));
-            }
-        }
-    };
-    auto rowsum = [&](int y, const unsigned (&w)[ND], unsigned& r0, unsigned& r1, unsigned& r2) __attribute__((always_inline)) {
-        const unsigned sh = ((unsigned)y * row_bytes + lx) & 3u;
-        const unsigned d0 = __builtin_amdgcn_alignbyte(w[1], w[0], sh) & vm0;
-        const unsigned d1 = __builtin_amdgcn_alignbyte(w[2], w[1], sh) & vm1;
-        const unsigned d2 = __builtin_amdgcn_alignbyte(w[3], w[2], sh) & vm2;
-        r0 = __builtin_amdgcn_udot4(d0, 0x01000001u, 0u, false); r1 = __builtin_amdgcn_udot4(d0, 0x00000100u, 0u, false);
-        r2 = __builtin_amdgcn_udot4(d0, 0x00010000u, 0u, false);
-        r0 = __builtin_amdgcn_udot4(d1, 0x00010000u, r0, false); r1 = __builtin_amdgcn_udot4(d1, 0x01000001u, r1, false);
-        r2 = __builtin_amdgcn_udot4(d1, 0x00000100u, r2, false);
-        r0 = __builtin_amdgcn_udot4(d2, 0x00000100u, r0, false); r1 = __builtin_amdgcn_udot4(d2, 0x00010000u, r1, false);
-        r2 = __builtin_amdgcn_udot4(d2, 0x01000001u, r2, false);
-        if (FOUR) {
-            const unsigned d3 = __builtin_amdgcn_alignbyte(w[4], w[3], sh) & vm3;
-            r0 = __builtin_amdgcn_udot4(d3, 0x01000001u, r0, false); r1 = __builtin_amdgcn_udot4(d3, 0x00000100u, r1, false);
-            r2 = __builtin_amdgcn_udot4(d3, 0x00010000u, r2, false);
-        }
-    };
-    // ---- row quantities: wave-uniform ----
-    auto edges = [&](int oy, int& ys, int& ye) __attribute__((always_inline)) {     // bin [ys, ye) of output row oy; past the strip: never
-        if (oy >= oy1) { ys = 0x7fffffff; ye = 0x7fffffff; return; }
-        if (g.arith) {
-            ys = (int)__umulhi((unsigned)(oy * a.H), g.hmagic);
-            ye = (int)__umulhi((unsigned)((oy + 1) * a.H + g.h - 1), g.hmagic);
-        } else {
-            const uint32_t t = tab[g.ytab0 + oy];
-            ys = (int)(t & 0xFFFF); ye = (int)(t >> 16);
-        }
-        ys = __builtin_amdgcn_readfirstlane(ys); ye = __builtin_amdgcn_readfirstlane(ye);
-    };
-    int ys_first, ye_first, ys_last, yend;
-    edges(oy0, ys_first, ye_first);
-    edges(oy1 - 1, ys_last, yend);                                                   // the wave's source rows: [ys_first, yend)
-    auto run = [&](auto SLOW_T) __attribute__((always_inline)) {
-        int oy = oy0, ys_c = ys_first, ye_c = ye_first, ys_n, ye_n;
-        edges(oy + 1, ys_n, ye_n);
-        unsigned c0 = 0, c1 = 0, c2 = 0, n0 = 0, n1 = 0, n2 = 0;                    // channel sums of the current bin and of the next one
-        unsigned ring[D][ND];
-        const int ycl = yend - 1;                                                    // rows past the wave's last bin are never touched
-#pragma unroll
-        for (int k = 0; k < D; k++) fetch(SLOW_T, ys_first + k < ycl ? ys_first + k : ycl, ring[k]);
-        for (int yb = ys_first; yb < yend; yb += D) {
-#pragma unroll
-            for (int k = 0; k < D; k++) {
-                const int y = yb + k;                                                // wave-uniform
-                unsigned r0, r1, r2;
-                rowsum(y, ring[k], r0, r1, r2);                                      // (rows at and past yend: a re-read row, sums unused)
-                fetch(SLOW_T, y + D < ycl ? y + D : ycl, ring[k]);
-                if (y < yend) {
-                    c0 += r0; c1 += r1; c2 += r2;
-                    if (y >= ys_n) { n0 += r0; n1 += r1; n2 += r2; }
-                    if (y + 1 == ye_c) {                                           // the current bin is complete
-                        if (valid) {
-                            const int kh = ye_c - ys_c;
-                            float4 o4;
-                            o4.x = pyr_norm(c0, kh, kw, g); o4.y = pyr_norm(c1, kh, kw, g); o4.z = pyr_norm(c2, kh, kw, g); o4.w = 0.f;
-                            pyr_store(out + (oy * g.w + ox), o4);
-                        }
-                        c0 = n0; c1 = n1; c2 = n2; n0 = 0; n1 = 0; n2 = 0;
-                        oy++;
-                        ys_c = ys_n; ye_c = ye_n;
-                        edges(oy + 1, ys_n, ye_n);
-                    }
-                }
-            }
-        }
-    };
-    if (lastf && yend >= a.H) run(std::true_type{}); else run(std::false_type{});
-}
-
-__global__ __launch_bounds__(192) void k_pyramid_fine(const uint8_t* __restrict__ frames, PyrFineArgs a, const uint32_t* __restrict__ tab,
-                                                      PyrPx* __restrict__ pyr) {
-    const int lane = threadIdx.x & 63, lvl = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    if (lvl >= a.nlev) return;
-    const int band = blockIdx.x, strip = blockIdx.z, f = a.f0 + blockIdx.y;
-    const uint32_t* own = tab + a.own0;
-    const uint32_t cb = own[lvl * a.n_bands + band], rb = own[3 * a.n_bands + lvl * a.n_strips + strip];
-    const int ox_lo = __builtin_amdgcn_readfirstlane((int)(cb & 0xFFFF)), ox_hi = __builtin_amdgcn_readfirstlane((int)(cb >> 16));
-    const int oy_lo = __builtin_amdgcn_readfirstlane((int)(rb & 0xFFFF)), oy_hi = __builtin_amdgcn_readfirstlane((int)(rb >> 16));
-    const bool pad_wave = band == 0 && strip == 0;
-    if (lvl == 0) { if (a.g[0].kwmax * 3 + 3 > 16) pyr_fine_wave<true>(frames, a, a.g[0], tab, pyr, f, ox_lo, ox_hi, oy_lo, oy_hi, lane, pad_wave); else pyr_fine_wave<false>(frames, a, a.g[0], tab, pyr, f, ox_lo, ox_hi, oy_lo, oy_hi, lane, pad_wave); }
-    else if (lvl == 1) { if (a.g[1].kwmax * 3 + 3 > 16) pyr_fine_wave<true>(frames, a, a.g[1], tab, pyr, f, ox_lo, ox_hi, oy_lo, oy_hi, lane, pad_wave); else pyr_fine_wave<false>(frames, a, a.g[1], tab, pyr, f, ox_lo, ox_hi, oy_lo, oy_hi, lane, pad_wave); }
-    else { if (a.g[2].kwmax * 3 + 3 > 16) pyr_fine_wave<true>(frames, a, a.g[2], tab, pyr, f, ox_lo, ox_hi, oy_lo, oy_hi, lane, pad_wave); else pyr_fine_wave<false>(frames, a, a.g[2], tab, pyr, f, ox_lo, ox_hi, oy_lo, oy_hi, lane, pad_wave); }
-}
 
 // ---- fused PNet --------------------------------------------------------------------------------------
 
@@ -1460,13 +1029,11 @@ int trl_pnet_prepare(trl_ctx* c) {
 // step turns into n -- no special case on the device
 static unsigned sdiv_magic(int d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
-static int fill_args(trl_ctx* c, int n, int H, int W, PnetArgs& a, std::vector<uint32_t>* tab = nullptr) {
-    const int L = trl_compute_levels(c, H, W);
-    if (L > 16) { trl_set_error("more than 16 pyramid levels"); return TRL_ERR_INVALID; }
-    if (L < 1) { trl_set_error("frame %dx%d has no pyramid level at min_face_size %d", W, H, c->cfg.min_face_size); return TRL_ERR_INVALID; }
-    a.n_frames = n; a.L = L; a.H = H; a.W = W;
-    int tiles = 0, ntab = 0; long long pix = 0, work = 0;
-    for (int l = 0; l < L; l++) {
+static void fill_args(trl_ctx* c, int n, int H, int W, const PyrLayout& lay, const PyrPx* pyr, PnetArgs& a) {
+    a.pyr = pyr; a.pyr_stride = lay.pyr_stride;
+    a.n_frames = n; a.L = lay.L; a.H = H; a.W = W;
+    int tiles = 0;
+    for (int l = 0; l < lay.L; l++) {
         const LevelGeom& g = c->lv[l];
         PLevel& p = a.lv[l];
         p.h = g.h; p.w = g.w; p.oh = g.oh; p.ow = g.ow;
@@ -1475,58 +1042,13 @@ static int fill_args(trl_ctx* c, int n, int H, int W, PnetArgs& a, std::vector<u
         p.tile0 = tiles;
         p.tiles_y = (g.oh + TS - 1) / TS;
         p.bmagic = sdiv_magic(BAND * p.tiles_x);
-        tiles += p.tiles_x * ((g.oh + TS - 1) / TS);
-        p.pix0 = (int)pix;
-        p.pix_pad = (int)(((long long)g.h * g.w + 63) & ~63ll);
-        pix += p.pix_pad;
-        // pyramid kernel path and lanes per output pixel
-        const int khmax = (H + g.h - 1) / g.h + 1, kwmax = (W + g.w - 1) / g.w + 1;   // upper bounds of the bin sizes
-        p.khA = (H + g.h - 1) / g.h; p.kwA = (W + g.w - 1) / g.w;
-        p.khmax = (H % g.h) ? p.khA + 1 : p.khA; p.kwmax = (W % g.w) ? p.kwA + 1 : p.kwA;
-        p.rkh[0] = 1.0f / (float)p.khA; p.rkh[1] = 1.0f / (float)(p.khA + 1);
-        p.rkw[0] = 1.0f / (float)p.kwA; p.rkw[1] = 1.0f / (float)(p.kwA + 1);
-        p.fastdiv = (p.khA + 1 <= 96 && p.kwA + 1 <= 96) ? 1 : 0;
-        for (int d = 0; d < 4; d++) {
-            auto vb = [](int rel, int nbytes) { int hi = nbytes - rel; hi = hi < 0 ? 0 : (hi > 4 ? 4 : hi); return hi >= 4 ? 0xFFFFFFFFu : ((1u << (8 * hi)) - 1u); };
-            p.vmA[d] = vb(4 * d, 3 * p.kwA); p.vmB[d] = vb(4 * d, 3 * (p.kwA + 1));
-        }
-        p.wmagic = (unsigned)((0x100000000ull + g.w - 1) / g.w);
-        p.hmagic = (unsigned)((0x100000000ull + g.h - 1) / g.h);
-        // floor(n / d) == umulhi(n, ceil(2^32 / d)) for every n with n * d < 2^32 (n <= (in + 1) * out here)
-        p.arith = ((unsigned long long)(H + 1) * g.h * g.h < 0x100000000ull && (unsigned long long)(W + 1) * g.w * g.w < 0x100000000ull &&
-                   g.h > 1 && g.w > 1) ? 1 : 0;
-        p.nd = 3; p.grshift = 0;
-        if (kwmax * 3 <= 15 && khmax <= 5) {
-            p.mode = 0; p.gshift = 0; p.nd = kwmax * 3 <= 9 ? 3 : 4;
-        } else if ((W * 3) % 4 == 0) {
-            p.mode = 1;
-            const int ngr = (kwmax * 3 + 3 + 11) / 12;
-            while ((1 << p.grshift) < ngr) p.grshift++;
-            int rlsh = 0;
-            while ((khmax >> rlsh) > 8 && p.grshift + rlsh < 6) rlsh++;
-            p.gshift = p.grshift + rlsh;
-            if (p.gshift > 6) { p.mode = 2; p.gshift = 6; }
-        } else {
-            p.mode = 2;
-            const int dwords = khmax * ((kwmax * 3 + 6) / 4);
-            p.gshift = dwords <= 40 ? 0 : (dwords <= 160 ? 2 : (dwords <= 640 ? 4 : 6));
-        }
-        p.work0 = (int)work;
-        work += (long long)p.pix_pad << p.gshift;
-        // adaptive_avg_pool2d bin edges: [floor(i*in/out), ceil((i+1)*in/out))
-        p.ytab0 = ntab; ntab += g.h;
-        p.xtab0 = ntab; ntab += g.w;
-        if (tab) {
-            for (int i = 0; i < g.h; i++) tab->push_back((uint32_t)(((long long)i * H) / g.h) | ((uint32_t)((((long long)i + 1) * H + g.h - 1) / g.h) << 16));
-            for (int i = 0; i < g.w; i++) tab->push_back((uint32_t)(((long long)i * W) / g.w) | ((uint32_t)((((long long)i + 1) * W + g.w - 1) / g.w) << 16));
-        }
+        tiles += p.tiles_x * p.tiles_y;
+        p.pix0 = lay.lv[l].pix0;
         p.scale = (float)g.scale;
         p.cap = c->cb.lay.capl[l]; p.rec0 = c->cb.lay.rec0[l];   // (set by trl_cascade_detect before the fused launch)
     }
     a.tiles_per_frame = tiles;
     a.tpf_magic = sdiv_magic(tiles);
-    a.pyr_stride = pix;
-    a.work_per_frame = work;
     a.w1 = trl_w(c, "pnet.conv1.w")->p; a.w2 = trl_w(c, "pnet.conv2.w")->p; a.w3 = trl_w(c, "pnet.conv3.w")->p; a.wh = trl_w(c, "pnet.heads.w")->p;
     a.b1 = trl_v(c, "pnet.conv1.b")->p; a.b2 = trl_v(c, "pnet.conv2.b")->p; a.b3 = trl_v(c, "pnet.conv3.b")->p; a.bh = trl_v(c, "pnet.heads.b")->p;
     a.s1 = trl_v(c, "pnet.prelu1")->p; a.s2 = trl_v(c, "pnet.prelu2")->p; a.s3 = trl_v(c, "pnet.prelu3")->p;
@@ -1539,588 +1061,22 @@ static int fill_args(trl_ctx* c, int n, int H, int W, PnetArgs& a, std::vector<u
     a.lvl_cnt = c->cb.lvl_cnt; a.lvl_rec = c->cb.lvl_rec; a.flags = c->cb.flags;
     a.clk = c->pnet_clk; a.prof = c->pnet_prof ? 1 : 0;
     a.xcd_next = c->pnet_cursor;
-    return TRL_OK;
 }
 
 size_t trl_pnet_fused_bytes(trl_ctx* c, int n, int H, int W) {
-    PnetArgs a;
-    if (fill_args(c, n, H, W, a) != TRL_OK) return 0;
-    return (size_t)a.pyr_stride * n * sizeof(PyrPx) + 4096;
+    PyrLayout lay;
+    if (trl_pyramid_layout(c, H, W, lay) != TRL_OK) return 0;
+    return trl_pyramid_bytes(lay, n) + 4096;
 }
 
-// All pyramid levels of all n frames: pyramid kernel + one persistent fused launch.
-// ev[0..1] bracket the pyramid kernel, ev[2..3] the fused kernel (HIP events on the same stream).
-namespace {
-
-// ---- coarse levels in ONE streaming pass ------------------------------------------------------------------
-// The per-level kernels above make every level re-read its whole source chunk; for the coarse levels (bins wider than
-// 5 px: 8 of the 11 levels at 720p, 15 % of the pixels) that re-read IS the cost (~55 us per level and 64 frames,
-// whatever the level's size).  k_pyramid_stream reads each source row ONCE for all of them:
-//   * a workgroup owns a band of the frame (rows [R0,R1) x a column band of <= 4096 bytes) and walks its rows top down;
-//     thread t owns 16 consecutive bytes of the row (one dword-aligned 16-byte load + 1 dword, re-aligned by a scalar shift);
-//   * per level it keeps the column sums of the current output row's bin in registers (16 byte-columns, packed 16-bit);
-//     at the bin's last source row the sums go to LDS, the horizontal bins are reduced, normalised (pyr_norm) and stored,
-//     and the accumulators restart (with the current row when consecutive bins share it);
-//   * a band computes the bins that START inside it and reads on past its end until they are complete (no atomics).
-// Integer sums in any order are exact, so the result is bit-identical to the per-level kernels (tests: every level, 180p..4K).
-constexpr int SMAXL = 12;               // coarse levels per launch
-constexpr int SBYTES = 4096;            // bytes of a source row a workgroup covers (256 threads x 16)
-struct SLevel { int h, w, pix0, pix_pad, ytab0, xtab0, khA, kwA, fastdiv; float rkh[2], rkw[2]; };
-struct PyrStreamArgs {
-    int H, W, n_frames, f0, nlev, rows_per_band, cols_per_band, row_bands, col_bands;
-    long long pyr_stride;
-    SLevel lv[SMAXL];
-};
-
-__device__ __forceinline__ float stream_norm(unsigned s, int kh, int kw, const SLevel& g) {
-    const float a = (float)s, fkh = (float)kh, fkw = (float)kw;
-    float q;
-    if (g.fastdiv) {
-        const float r1 = kh == g.khA ? g.rkh[0] : g.rkh[1], r2 = kw == g.kwA ? g.rkw[0] : g.rkw[1];
-        q = pyr_div(pyr_div(a, fkh, r1), fkw, r2);
-    } else {
-        q = a / fkh / fkw;
-    }
-    return (q - 127.5f) * 0.0078125f;
-}
-
-constexpr int STAB = 6144;              // bin-edge words of the coarse levels kept in LDS (rows + columns of every level)
-template <int NL>
-__global__ __launch_bounds__(256) void k_pyramid_stream(const uint8_t* __restrict__ frames, PyrStreamArgs a, const uint32_t* __restrict__ gtab,
-                                                        PyrPx* __restrict__ pyr) {
-    __shared__ unsigned colbuf[SBYTES];
-    __shared__ uint32_t tab[STAB];          // the levels' edge tables, re-based: level l rows at ty0[l], columns at tx0[l]
-    const int tid = threadIdx.x;
-    const int f = a.f0 + blockIdx.y;
-    const int rb = blockIdx.x / a.col_bands, cb = blockIdx.x - rb * a.col_bands;
-    const int R0 = rb * a.rows_per_band, R1 = (R0 + a.rows_per_band < a.H) ? R0 + a.rows_per_band : a.H;
-    const int C0 = cb * a.cols_per_band, C1 = (C0 + a.cols_per_band < a.W) ? C0 + a.cols_per_band : a.W;
-    const int row_bytes = a.W * 3;
-    const long long fbase = (long long)f * a.H * row_bytes;
-    const long long last_dw = ((long long)a.n_frames * a.H * row_bytes - 1) >> 2;
-    const uint32_t* base32 = reinterpret_cast<const uint32_t*>(frames);
-    // edge tables of the handled levels -> LDS (a flush would otherwise end in a dependent global load)
-    int ty0[NL], tx0[NL];
-    {
-        int pos = 0;
-#pragma unroll
-        for (int l = 0; l < NL; l++) {
-            ty0[l] = tx0[l] = 0;
-            if (l < a.nlev) {
-                const SLevel& g = a.lv[l];
-                ty0[l] = pos; tx0[l] = pos + g.h;
-                for (int i = tid; i < g.h; i += 256) tab[pos + i] = gtab[g.ytab0 + i];
-                for (int i = tid; i < g.w; i += 256) tab[pos + g.h + i] = gtab[g.xtab0 + i];
-                pos += g.h + g.w;
-            }
-        }
-    }
-    __syncthreads();
-
-    // per level (all scalar): owned output rows [j, jend), owned output columns [ox0, ox1), current bin rows [ys, ye)
-    int j[NL], jend[NL], ys[NL], ye[NL], ox0[NL], ox1[NL];
-    int yend = R0;
-#pragma unroll
-    for (int l = 0; l < NL; l++) {
-        j[l] = jend[l] = 0; ys[l] = ye[l] = 0x7fffffff; ox0[l] = ox1[l] = 0;
-        if (l < a.nlev) {
-            const SLevel& g = a.lv[l];
-            auto first_at_or_after = [&](int tab0, int n_out, int n_in, int pos) {   // first bin whose start >= pos
-                if (pos >= n_in) return n_out;
-                int q = (int)(((long long)pos * n_out + n_in - 1) / n_in);
-                if (q > n_out) q = n_out;
-                while (q > 0 && (int)(tab[tab0 + q - 1] & 0xFFFF) >= pos) q--;
-                while (q < n_out && (int)(tab[tab0 + q] & 0xFFFF) < pos) q++;
-                return q;
-            };
-            j[l] = first_at_or_after(ty0[l], g.h, a.H, R0);
-            jend[l] = first_at_or_after(ty0[l], g.h, a.H, R1);
-            ox0[l] = first_at_or_after(tx0[l], g.w, a.W, C0);
-            ox1[l] = first_at_or_after(tx0[l], g.w, a.W, C1);
-            if (j[l] < jend[l] && ox0[l] < ox1[l]) {
-                const uint32_t t0 = tab[ty0[l] + j[l]], t1 = tab[ty0[l] + jend[l] - 1];
-                ys[l] = t0 & 0xFFFF; ye[l] = t0 >> 16;
-                yend = ((int)(t1 >> 16) > yend) ? (int)(t1 >> 16) : yend;
-            } else {
-                j[l] = jend[l];
-            }
-        }
-    }
-    // zero the 64-pixel padding behind each level once per frame
-    if (blockIdx.x == 0) {
-#pragma unroll
-        for (int l = 0; l < NL; l++)
-            if (l < a.nlev) {
-                const SLevel& g = a.lv[l];
-                for (int p = g.h * g.w + tid; p < g.pix_pad; p += 256)
-                    pyr_store(pyr + ((long long)f * a.pyr_stride + g.pix0 + p), make_float4(0.f, 0.f, 0.f, 0.f));
-            }
-    }
-    if (yend <= R0) return;
-
-    unsigned ev[NL][4], od[NL][4];          // packed 16-bit column sums: bytes 0,2 / 1,3 of each of the thread's 4 dwords
-#pragma unroll
-    for (int l = 0; l < NL; l++)
-#pragma unroll
-        for (int d = 0; d < 4; d++) { ev[l][d] = 0; od[l][d] = 0; }
-
-    // one source row: this thread's 16 bytes at byte offset C0*3 + 16*tid of row y
-    auto load_row = [&](int y, unsigned (&w)[5], unsigned& sh) {
-        const int yy = y < a.H ? y : a.H - 1;                                    // rows past the frame are never accumulated
-        const long long o = fbase + (long long)yy * row_bytes + (long long)C0 * 3;   // scalar
-        sh = (unsigned)(o & 3);
-        const long long dw = (o >> 2) + 4 * tid;
-        if (dw + 4 <= last_dw) {
-            const u32x4_a4 v4 = *reinterpret_cast<const u32x4_a4*>(base32 + dw);
-            w[0] = v4[0]; w[1] = v4[1]; w[2] = v4[2]; w[3] = v4[3];
-            w[4] = base32[dw + 4];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 5; k++) w[k] = base32[dw + k <= last_dw ? dw + k : last_dw];
-        }
-    };
-    auto consume = [&](int y, const unsigned (&w)[5], unsigned sh) {
-        unsigned v[4];
-#pragma unroll
-        for (int d = 0; d < 4; d++) v[d] = __builtin_amdgcn_alignbyte(w[d + 1], w[d], sh);
-#pragma unroll
-        for (int l = 0; l < NL; l++) {
-            if (l < a.nlev && y >= ys[l] && y < ye[l]) {                         // uniform
-#pragma unroll
-                for (int d = 0; d < 4; d++) { ev[l][d] += v[d] & 0x00FF00FFu; od[l][d] += (v[d] >> 8) & 0x00FF00FFu; }
-                if (y == ye[l] - 1) {
-                    // ---- the bin row is complete: column sums -> LDS -> horizontal bins -> normalise -> store ----
-                    const SLevel& g = a.lv[l];
-                    const int kh = ye[l] - ys[l];
-#pragma unroll
-                    for (int d = 0; d < 4; d++) {
-                        colbuf[16 * tid + 4 * d + 0] = ev[l][d] & 0xFFFFu; colbuf[16 * tid + 4 * d + 1] = od[l][d] & 0xFFFFu;
-                        colbuf[16 * tid + 4 * d + 2] = ev[l][d] >> 16;     colbuf[16 * tid + 4 * d + 3] = od[l][d] >> 16;
-                    }
-                    __syncthreads();
-                    for (int ox = ox0[l] + tid; ox < ox1[l]; ox += 256) {
-                        const uint32_t tx = tab[tx0[l] + ox];
-                        const int xs = tx & 0xFFFF, xe = tx >> 16;
-                        unsigned s0 = 0, s1 = 0, s2 = 0;
-                        for (int xx = xs; xx < xe; xx++) {
-                            const unsigned* p = colbuf + (xx - C0) * 3;
-                            s0 += p[0]; s1 += p[1]; s2 += p[2];
-                        }
-                        float4 o4;
-                        o4.x = stream_norm(s0, kh, xe - xs, g); o4.y = stream_norm(s1, kh, xe - xs, g); o4.z = stream_norm(s2, kh, xe - xs, g);
-                        o4.w = 0.f;
-                        pyr_store(pyr + ((long long)f * a.pyr_stride + g.pix0 + (long long)j[l] * g.w + ox), o4);
-                    }
-                    __syncthreads();
-                    // next owned bin of this level; consecutive bins may share this source row
-                    j[l]++;
-                    if (j[l] < jend[l]) {
-                        const uint32_t t0 = tab[ty0[l] + j[l]];
-                        ys[l] = t0 & 0xFFFF; ye[l] = t0 >> 16;
-                    } else {
-                        ys[l] = ye[l] = 0x7fffffff;
-                    }
-                    const bool again = ys[l] <= y;
-#pragma unroll
-                    for (int d = 0; d < 4; d++) {
-                        ev[l][d] = again ? (v[d] & 0x00FF00FFu) : 0u;
-                        od[l][d] = again ? ((v[d] >> 8) & 0x00FF00FFu) : 0u;
-                    }
-                }
-            }
-        }
-    };
-
-    // rows in groups of four: the loads of the next group are in flight while this one is consumed
-    unsigned wb[4][5], shb[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) load_row(R0 + u, wb[u], shb[u]);
-    for (int y = R0; y < yend; y += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            unsigned wc[5];
-#pragma unroll
-            for (int k = 0; k < 5; k++) wc[k] = wb[u][k];
-            const unsigned shc = shb[u];
-            if (y + u + 4 < yend) load_row(y + u + 4, wb[u], shb[u]);
-            if (y + u < yend) consume(y + u, wc, shc);
-        }
-    }
-}
-
-// ---- the same pass with WAVE-local ownership, for frames wider than one 4096-byte band (round 4) -------------------------------
-// k_pyramid_stream covers a whole row with one workgroup and therefore stops at W = 1365; 1080p and 4K frames took the per-level
-// kernels (55 launches per step at 4K, each re-reading the source).  Here a WAVE owns a segment of source columns for a band of rows
-// and never talks to another wave: lane i holds 20 consecutive bytes of the row (5 dwords + 1 for the re-alignment), the segment is
-// 64 x 20 = 1280 bytes = 426 pixels of which the last kwmax overlap the next segment, so that every bin that STARTS in the segment
-// is covered by the wave's own loads.  A completed bin row is flushed through the wave's private LDS strip (LDS operations of one
-// wave execute in order: no barrier), reduced, normalised and stored.  Integer sums: bit-identical.  (At 720p, where both apply,
-// the block-wide pass is faster -- 0.63 vs 1.11 ms: every wave pays all ~165 flush round trips alone -- so it keeps the narrow frames.)
-constexpr int SW_BYTES = 1280;           // bytes of a source row per wave
-template <int NL>
-__global__ __launch_bounds__(256) void k_pyramid_stream_w(const uint8_t* __restrict__ frames, PyrStreamArgs a, const uint32_t* __restrict__ gtab,
-                                                          PyrPx* __restrict__ pyr) {
-    __shared__ unsigned colbuf_all[4][SW_BYTES];
-    __shared__ uint32_t tab[STAB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int f = a.f0 + blockIdx.y;
-    const int row_bytes = a.W * 3;
-    const long long fbase = (long long)f * a.H * row_bytes;
-    const long long last_dw = ((long long)a.n_frames * a.H * row_bytes - 1) >> 2;
-    const uint32_t* base32 = reinterpret_cast<const uint32_t*>(frames);
-    int ty0[NL], tx0[NL];
-    {
-        int pos = 0;
-#pragma unroll
-        for (int l = 0; l < NL; l++) {
-            ty0[l] = tx0[l] = 0;
-            if (l < a.nlev) {
-                const SLevel& g = a.lv[l];
-                ty0[l] = pos; tx0[l] = pos + g.h;
-                for (int i = tid; i < g.h; i += 256) tab[pos + i] = gtab[g.ytab0 + i];
-                for (int i = tid; i < g.w; i += 256) tab[pos + g.h + i] = gtab[g.xtab0 + i];
-                pos += g.h + g.w;
-            }
-        }
-    }
-    __syncthreads();                                     // the only block barrier: from here on the waves are on their own
-    const int unit = blockIdx.x * 4 + wave;              // (row band, column segment) of this wave
-    if (unit >= a.row_bands * a.col_bands) return;
-    const int rb = unit / a.col_bands, cs = unit - rb * a.col_bands;
-    const int R0 = rb * a.rows_per_band, R1 = (R0 + a.rows_per_band < a.H) ? R0 + a.rows_per_band : a.H;
-    const int C0 = cs * a.cols_per_band, C1 = (C0 + a.cols_per_band < a.W) ? C0 + a.cols_per_band : a.W;
-    unsigned* colbuf = colbuf_all[wave];
-
-    int j[NL], jend[NL], ys[NL], ye[NL], ox0[NL], ox1[NL];
-    int yend = R0;
-#pragma unroll
-    for (int l = 0; l < NL; l++) {
-        j[l] = jend[l] = 0; ys[l] = ye[l] = 0x7fffffff; ox0[l] = ox1[l] = 0;
-        if (l < a.nlev) {
-            const SLevel& g = a.lv[l];
-            auto first_at_or_after = [&](int tab0, int n_out, int n_in, int pos) {   // first bin whose start >= pos
-                if (pos >= n_in) return n_out;
-                int q = (int)(((long long)pos * n_out + n_in - 1) / n_in);
-                if (q > n_out) q = n_out;
-                while (q > 0 && (int)(tab[tab0 + q - 1] & 0xFFFF) >= pos) q--;
-                while (q < n_out && (int)(tab[tab0 + q] & 0xFFFF) < pos) q++;
-                return q;
-            };
-            j[l] = __builtin_amdgcn_readfirstlane(first_at_or_after(ty0[l], g.h, a.H, R0));
-            jend[l] = __builtin_amdgcn_readfirstlane(first_at_or_after(ty0[l], g.h, a.H, R1));
-            ox0[l] = __builtin_amdgcn_readfirstlane(first_at_or_after(tx0[l], g.w, a.W, C0));
-            ox1[l] = __builtin_amdgcn_readfirstlane(first_at_or_after(tx0[l], g.w, a.W, C1));
-            if (j[l] < jend[l] && ox0[l] < ox1[l]) {
-                const uint32_t t0 = tab[ty0[l] + j[l]], t1 = tab[ty0[l] + jend[l] - 1];
-                ys[l] = __builtin_amdgcn_readfirstlane((int)(t0 & 0xFFFF)); ye[l] = __builtin_amdgcn_readfirstlane((int)(t0 >> 16));
-                const int e1 = __builtin_amdgcn_readfirstlane((int)(t1 >> 16));
-                yend = e1 > yend ? e1 : yend;
-            } else {
-                j[l] = jend[l];
-            }
-        }
-    }
-    if (unit == 0) {                                     // zero the 64-pixel padding behind each level once per frame
-#pragma unroll
-        for (int l = 0; l < NL; l++)
-            if (l < a.nlev) {
-                const SLevel& g = a.lv[l];
-                for (int p = g.h * g.w + lane; p < g.pix_pad; p += 64)
-                    pyr_store(pyr + ((long long)f * a.pyr_stride + g.pix0 + p), make_float4(0.f, 0.f, 0.f, 0.f));
-            }
-    }
-    if (yend <= R0) return;
-
-    unsigned ev[NL][5], od[NL][5];          // packed 16-bit column sums: bytes 0,2 / 1,3 of each of the lane's 5 dwords
-#pragma unroll
-    for (int l = 0; l < NL; l++)
-#pragma unroll
-        for (int d = 0; d < 5; d++) { ev[l][d] = 0; od[l][d] = 0; }
-
-    // one source row: this lane's 20 bytes at byte offset C0*3 + 20*lane of row y (+ the dword behind them for the re-alignment)
-    auto load_row = [&](int y, unsigned (&w)[6], unsigned& sh) {
-        const int yy = y < a.H ? y : a.H - 1;                                    // rows past the frame are never accumulated
-        const long long o = fbase + (long long)yy * row_bytes + (long long)C0 * 3;   // scalar
-        sh = (unsigned)(o & 3);
-        const long long dw = (o >> 2) + 5 * lane;
-        if (dw + 5 <= last_dw) {
-            const u32x4_a4 v4 = *reinterpret_cast<const u32x4_a4*>(base32 + dw);
-            w[0] = v4[0]; w[1] = v4[1]; w[2] = v4[2]; w[3] = v4[3];
-            w[4] = base32[dw + 4]; w[5] = base32[dw + 5];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 6; k++) w[k] = base32[dw + k <= last_dw ? dw + k : last_dw];
-        }
-    };
-    auto consume = [&](int y, const unsigned (&w)[6], unsigned sh) {
-        unsigned v[5];
-#pragma unroll
-        for (int d = 0; d < 5; d++) v[d] = __builtin_amdgcn_alignbyte(w[d + 1], w[d], sh);
-#pragma unroll
-        for (int l = 0; l < NL; l++) {
-            if (l < a.nlev && y >= ys[l] && y < ye[l]) {                         // wave-uniform
-#pragma unroll
-                for (int d = 0; d < 5; d++) { ev[l][d] += v[d] & 0x00FF00FFu; od[l][d] += (v[d] >> 8) & 0x00FF00FFu; }
-                if (y == ye[l] - 1) {
-                    // ---- the bin row is complete: column sums -> the wave's LDS strip -> horizontal bins -> normalise -> store ----
-                    const SLevel& g = a.lv[l];
-                    const int kh = ye[l] - ys[l];
-#pragma unroll
-                    for (int d = 0; d < 5; d++) {
-                        colbuf[20 * lane + 4 * d + 0] = ev[l][d] & 0xFFFFu; colbuf[20 * lane + 4 * d + 1] = od[l][d] & 0xFFFFu;
-                        colbuf[20 * lane + 4 * d + 2] = ev[l][d] >> 16;     colbuf[20 * lane + 4 * d + 3] = od[l][d] >> 16;
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    for (int ox = ox0[l] + lane; ox < ox1[l]; ox += 64) {
-                        const uint32_t tx = tab[tx0[l] + ox];
-                        const int xs = tx & 0xFFFF, xe = tx >> 16;
-                        unsigned s0 = 0, s1 = 0, s2 = 0;
-                        for (int xx = xs; xx < xe; xx++) {
-                            const unsigned* p = colbuf + (xx - C0) * 3;
-                            s0 += p[0]; s1 += p[1]; s2 += p[2];
-                        }
-                        float4 o4;
-                        o4.x = stream_norm(s0, kh, xe - xs, g); o4.y = stream_norm(s1, kh, xe - xs, g); o4.z = stream_norm(s2, kh, xe - xs, g);
-                        o4.w = 0.f;
-                        pyr_store(pyr + ((long long)f * a.pyr_stride + g.pix0 + (long long)j[l] * g.w + ox), o4);
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    // next owned bin of this level; consecutive bins may share this source row
-                    j[l]++;
-                    if (j[l] < jend[l]) {
-                        const uint32_t t0 = tab[ty0[l] + j[l]];
-                        ys[l] = __builtin_amdgcn_readfirstlane((int)(t0 & 0xFFFF)); ye[l] = __builtin_amdgcn_readfirstlane((int)(t0 >> 16));
-                    } else {
-                        ys[l] = ye[l] = 0x7fffffff;
-                    }
-                    const bool again = ys[l] <= y;
-#pragma unroll
-                    for (int d = 0; d < 5; d++) {
-                        ev[l][d] = again ? (v[d] & 0x00FF00FFu) : 0u;
-                        od[l][d] = again ? ((v[d] >> 8) & 0x00FF00FFu) : 0u;
-                    }
-                }
-            }
-        }
-    };
-
-    // rows in groups of four: the loads of the next group are in flight while this one is consumed
-    unsigned wb[4][6], shb[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) load_row(R0 + u, wb[u], shb[u]);
-    for (int y = R0; y < yend; y += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            unsigned wc[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) wc[k] = wb[u][k];
-            const unsigned shc = shb[u];
-            if (y + u + 4 < yend) load_row(y + u + 4, wb[u], shb[u]);
-            if (y + u < yend) consume(y + u, wc, shc);
-        }
-    }
-}
-
-}  // namespace
-
-// The pyramid of all n frames (production path of both the fused PNet and the debug export below).
-static int build_pyramid(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, PnetArgs& a, hipEvent_t* ev, hipStream_t s) {
-    if (((uintptr_t)d_frames & 3) != 0) { trl_set_error("frame buffer must be 4-byte aligned"); return TRL_ERR_INVALID; }
-    if (H > 16383 || W > 16383) { trl_set_error("frame larger than 16383 px"); return TRL_ERR_INVALID; }
-    std::vector<uint32_t> tab;
-    const bool new_shape = (c->pyr_tab == nullptr || c->pyr_tab_H != H || c->pyr_tab_W != W);
-    c->pyr_plan.L = 0;
-    TRL_CHECK(fill_args(c, n, H, W, a, new_shape ? &tab : nullptr));
-    // the kernel each level takes, recorded as it is chosen below (trl_debug_pyramid_plan)
-    auto plan = [&](int l, int kind, int rb, int cb, int cpb, int frames) {
-        int32_t* r = c->pyr_plan.row[l];
-        r[0] = kind; r[1] = rb; r[2] = cb; r[3] = cpb; r[4] = frames; r[5] = a.lv[l].khmax;
-    };
-    if (new_shape) {   // bin-edge tables depend on (H, W) only: built once per frame shape
-        // k_pyramid_fine: which output columns / rows of the (up to three) finest levels belong to which source tile -- those whose
-        // bins START in it.  A band must not own more than 64 columns of any level (one wave = one level's columns of the band).
-        c->pyr_fine.nlev = 0;
-        int nfine = 0;
-        while (nfine < 3 && nfine < a.L && a.lv[nfine].mode == 0 && a.lv[nfine].h <= H && a.lv[nfine].w <= W) nfine++;
-        if (nfine >= 2) {
-            const int strip_rows = 24;                                            // source rows per tile
-            int band_cols = (int)(62.0 * W / a.lv[0].w);
-            std::vector<uint32_t> own;
-            for (; band_cols >= 16; band_cols--) {
-                const int nb = (W + band_cols - 1) / band_cols, ns = (H + strip_rows - 1) / strip_rows;
-                own.assign((size_t)3 * nb + (size_t)3 * ns, 0u);
-                bool ok = true;
-                for (int l = 0; l < nfine && ok; l++) {
-                    const PLevel& g = a.lv[l];
-                    int o = 0;
-                    for (int b = 0; b < nb; b++) {                   // columns: bin starts are non-decreasing in ox
-                        const int lo = o;
-                        while (o < g.w && (int)(tab[g.xtab0 + o] & 0xFFFF) < (b + 1) * band_cols) o++;
-                        if (o - lo > 64) { ok = false; break; }
-                        own[(size_t)l * nb + b] = (uint32_t)lo | ((uint32_t)o << 16);
-                    }
-                    o = 0;
-                    for (int t = 0; t < ns; t++) {
-                        const int lo = o;
-                        while (o < g.h && (int)(tab[g.ytab0 + o] & 0xFFFF) < (t + 1) * strip_rows) o++;
-                        own[(size_t)3 * nb + (size_t)l * ns + t] = (uint32_t)lo | ((uint32_t)o << 16);
-                    }
-                }
-                if (ok) {
-                    c->pyr_fine.nlev = nfine; c->pyr_fine.own0 = (int)tab.size(); c->pyr_fine.band_cols = band_cols; c->pyr_fine.strip_rows = strip_rows;
-                    c->pyr_fine.n_bands = nb; c->pyr_fine.n_strips = ns;
-                    tab.insert(tab.end(), own.begin(), own.end());
-                    break;
-                }
-            }
-        }
-        TRL_HIP(hipStreamSynchronize(s));
-        if (c->pyr_tab) TRL_HIP(hipFree(c->pyr_tab));
-        c->pyr_tab = nullptr;
-        TRL_HIP(hipMalloc((void**)&c->pyr_tab, tab.size() * 4 + 64));
-        TRL_HIP(hipMemcpy(c->pyr_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-        c->pyr_tab_H = H; c->pyr_tab_W = W;
-    }
-    PyrPx* pyr = (PyrPx*)c->scratch.alloc((size_t)a.pyr_stride * n * sizeof(PyrPx));
-    if (!pyr) { trl_set_error("pyramid workspace"); return TRL_ERR_STATE; }
-    a.pyr = pyr;
-    if (ev) TRL_HIP(hipEventRecord(ev[0], s));
-    // Frames are resampled in chunks whose source bytes fit the 256 MiB Infinity Cache: every level re-reads the
-    // whole source image, so the 2nd..11th level launches of a chunk are served on-die instead of from HBM.
-    int chunk = (int)((176ll << 20) / ((long long)H * W * 3));
-    if (chunk < 1) chunk = 1;
-    if (chunk > n) chunk = n;
-    // Coarse levels (mode != 0): streaming passes (k_pyramid_stream) in three row bands, at most 8 levels per launch (register budget
-    // of the per-level column sums), each launch reading the source once.  A group that does not meet the kernel's preconditions
-    // falls back to the per-level kernels below.  (Streaming the fine levels as well was measured: 1.75 vs 1.83 ms, not worth it.)
-    bool streamed[16] = {};
-    int lv_idx[16], nsel = 0;
-    for (int l = 0; l < a.L; l++) if (a.lv[l].mode != 0) lv_idx[nsel++] = l;
-    const bool wide = W * 3 > SBYTES;                                       // one workgroup cannot cover the row: wave-local pass
-    for (int g0 = 0; g0 < nsel; g0 += 8) {
-        const int gn = nsel - g0 < 8 ? nsel - g0 : 8;
-        PyrStreamArgs sa;
-        sa.nlev = 0;
-        int stab_words = 0, kwm = 0;
-        bool ok = true;
-        for (int q = 0; q < gn; q++) {
-            const PLevel& g = a.lv[lv_idx[g0 + q]];
-            if (g.khmax > 256) ok = false;
-            stab_words += g.h + g.w;
-            kwm = g.kwmax > kwm ? g.kwmax : kwm;
-            SLevel& t = sa.lv[sa.nlev++];
-            t.h = g.h; t.w = g.w; t.pix0 = g.pix0; t.pix_pad = g.pix_pad; t.ytab0 = g.ytab0; t.xtab0 = g.xtab0; t.khA = g.khA; t.kwA = g.kwA;
-            t.fastdiv = g.fastdiv; t.rkh[0] = g.rkh[0]; t.rkh[1] = g.rkh[1]; t.rkw[0] = g.rkw[0]; t.rkw[1] = g.rkw[1];
-        }
-        sa.H = H; sa.W = W; sa.n_frames = n; sa.pyr_stride = a.pyr_stride; sa.f0 = 0;   // every source row is read once: no Infinity-Cache chunking
-        sa.row_bands = H >= 256 ? 3 : 1;
-        sa.rows_per_band = (H + sa.row_bands - 1) / sa.row_bands;
-        if (!ok || stab_words > STAB || n > 65535) continue;                 // these levels take the per-level kernels
-        if (!wide) {
-            if ((kwm + 2) * 3 > SBYTES / 2) continue;
-            sa.col_bands = 1; sa.cols_per_band = W;
-            const dim3 sgrid(sa.row_bands * sa.col_bands, n);
-            if (sa.nlev <= 4) k_pyramid_stream<4><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
-            else k_pyramid_stream<8><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
-        } else {
-            // a wave covers 1280 bytes = 426 whole pixels of a row; the bins that start in its segment may reach kwmax further
-            sa.cols_per_band = SW_BYTES / 3 - kwm;
-            if (sa.cols_per_band < 64) continue;
-            sa.col_bands = (W + sa.cols_per_band - 1) / sa.cols_per_band;
-            sa.cols_per_band = (W + sa.col_bands - 1) / sa.col_bands;           // even segments
-            // enough waves to fill the chip (~4 k) when the batch is small: more, shorter row bands (each reads on past its end
-            // until its last bins are complete, so not shorter than 256 rows)
-            int rbn = (4096 + n * sa.col_bands - 1) / (n * sa.col_bands);
-            if (rbn > H / 256) rbn = H / 256;
-            if (rbn > sa.row_bands) { sa.row_bands = rbn; sa.rows_per_band = (H + rbn - 1) / rbn; }
-            const dim3 sgrid((sa.row_bands * sa.col_bands + 3) / 4, n);
-            if (sa.nlev <= 4) k_pyramid_stream_w<4><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
-            else k_pyramid_stream_w<8><<<sgrid, 256, 0, s>>>(d_frames, sa, c->pyr_tab, pyr);
-        }
-        TRL_LAUNCH_CHECK();
-        const int kind = wide ? (sa.nlev <= 4 ? TRL_PYR_SW4 : TRL_PYR_SW8) : (sa.nlev <= 4 ? TRL_PYR_S4 : TRL_PYR_S8);
-        for (int q = 0; q < gn; q++) {
-            streamed[lv_idx[g0 + q]] = true;
-            plan(lv_idx[g0 + q], kind, sa.row_bands, sa.col_bands, sa.cols_per_band, n);
-        }
-    }
-    // the finest levels in one pass over the source
-    if (c->pyr_fine.nlev >= 2 && n <= 65535 && c->pyr_fine.n_strips <= 65535) {
-        PyrFineArgs fa;
-        fa.H = H; fa.W = W; fa.n_frames = n; fa.f0 = 0; fa.pyr_stride = a.pyr_stride;
-        fa.nlev = c->pyr_fine.nlev; fa.band_cols = c->pyr_fine.band_cols; fa.strip_rows = c->pyr_fine.strip_rows;
-        fa.n_bands = c->pyr_fine.n_bands; fa.n_strips = c->pyr_fine.n_strips; fa.own0 = c->pyr_fine.own0;
-        for (int l = 0; l < 3; l++) fa.g[l] = a.lv[l < fa.nlev ? l : 0];
-        k_pyramid_fine<<<dim3(fa.n_bands, n, fa.n_strips), 192, 0, s>>>(d_frames, fa, c->pyr_tab, pyr);
-        TRL_LAUNCH_CHECK();
-        for (int l = 0; l < fa.nlev; l++) { streamed[l] = true; plan(l, TRL_PYR_FINE, 0, 0, 0, n); }
-    }
-    for (int f0 = 0; f0 < n; f0 += chunk) {
-        const int nf = (n - f0 < chunk) ? n - f0 : chunk;
-        for (int l = 0; l < a.L; l++) {
-            if (streamed[l]) continue;
-            PyrArgs pa;
-            pa.H = H; pa.W = W; pa.n_frames = n; pa.f0 = f0; pa.pyr_stride = a.pyr_stride; pa.g = a.lv[l];
-            const int threads = pa.g.pix_pad << pa.g.gshift;
-            dim3 grid(pa.g.mode == 0 ? (threads + 511) / 512 : (threads + 255) / 256, nf);   // mode 0: two pixels per thread
-            int kind;
-            if (pa.g.mode == 0) {
-                if (pa.g.khmax <= 3 && pa.g.nd <= 3) { kind = TRL_PYR_L0_3; k_pyramid0<3, false><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
-                else if (pa.g.khmax <= 4) { kind = TRL_PYR_L0_4; k_pyramid0<4, true><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
-                else { kind = TRL_PYR_L0_5; k_pyramid0<5, true><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
-            }
-            else if (pa.g.mode == 1) { kind = TRL_PYR_L1; k_pyramid<1><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
-            else { kind = TRL_PYR_L2; k_pyramid<2><<<grid, 256, 0, s>>>(d_frames, pa, c->pyr_tab, pyr); }
-            TRL_LAUNCH_CHECK();
-            if (f0 == 0) plan(l, kind, 0, 0, 0, chunk);
-        }
-    }
-    if (ev) TRL_HIP(hipEventRecord(ev[1], s));
-    c->pyr_plan.L = a.L;
-    return TRL_OK;
-}
-
-// debug / test hook: level `level` of ONE frame's pyramid exactly as the fused PNet kernel reads it -> d_out [h][w][3]
-__global__ void k_export_level(const PyrPx* __restrict__ pyr, int npix, float* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const PyrPx v = pyr[i];
-    out[3 * i + 0] = v.b; out[3 * i + 1] = v.g; out[3 * i + 2] = v.r;
-}
-int trl_pyramid_export(trl_ctx* c, const uint8_t* d_frame, int H, int W, int level, float* d_out, int* h, int* w, hipStream_t s) {
-    PnetArgs a;
-    TRL_CHECK(build_pyramid(c, d_frame, 1, H, W, a, nullptr, s));
-    if (level < 0 || level >= a.L) { trl_set_error("level %d out of range (%d levels)", level, a.L); return TRL_ERR_INVALID; }
-    const PLevel& g = a.lv[level];
-    k_export_level<<<(g.h * g.w + 255) / 256, 256, 0, s>>>(a.pyr + g.pix0, g.h * g.w, d_out);
-    TRL_LAUNCH_CHECK();
-    *h = g.h; *w = g.w;
-    return TRL_OK;
-}
-
-// debug / test hook: the raw pyramid workspace of an n-frame batch (every frame, every level, the padding included) as the
-// production pass above leaves it; d_out == nullptr: the layout alone
-int trl_pyramid_export_batch(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_out, long long* pyr_stride,
-                             int32_t* h_levels, int max_levels, int* n_levels, hipStream_t s) {
-    PnetArgs a;
-    if (d_out) {
-        TRL_CHECK(build_pyramid(c, d_frames, n, H, W, a, nullptr, s));
-        TRL_HIP(hipMemcpyAsync(d_out, a.pyr, (size_t)a.pyr_stride * n * sizeof(PyrPx), hipMemcpyDeviceToDevice, s));
-    } else {
-        TRL_CHECK(fill_args(c, n, H, W, a));
-    }
-    *pyr_stride = a.pyr_stride;
-    *n_levels = a.L;
-    for (int l = 0; l < a.L && l < max_levels; l++) {
-        const PLevel& g = a.lv[l];
-        h_levels[4 * l + 0] = g.pix0; h_levels[4 * l + 1] = g.h; h_levels[4 * l + 2] = g.w; h_levels[4 * l + 3] = g.pix_pad;
-    }
-    return TRL_OK;
-}
-
+// All pyramid levels of all n frames: the pyramid kernels + one persistent fused launch.
+// ev[0..1] bracket the pyramid kernels, ev[2..3] the fused kernel (HIP events on the same stream).
 int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, hipEvent_t* ev, hipStream_t s) {
+    PyrLayout lay;
+    PyrPx* pyr = nullptr;
+    TRL_CHECK(trl_pyramid_build(c, d_frames, n, H, W, lay, &pyr, ev, s));
     PnetArgs a;
-    TRL_CHECK(build_pyramid(c, d_frames, n, H, W, a, ev, s));
+    fill_args(c, n, H, W, lay, pyr, a);
     const int total_tiles = a.tiles_per_frame * n;
     int grid = 256 * 2;   // 2 resident workgroups per CU (<= 256 VGPRs)
     if (grid > ((total_tiles + 7) / 8) * 8) grid = ((total_tiles + 7) / 8) * 8;

@@ -306,12 +306,23 @@ int  trl_debug_lists(trl_ctx* ctx, int kind, int n, int H, int W, const int32_t*
 /* The tail conv launches of the last trl_debug_stage_net call, chunk after chunk, in the rows of
  * trl_debug_facenet_plan: layer = "rnet.conv2", ..., "onet.heads", conv = row index.  Other calls do not record. (ABI v7) */
 int  trl_debug_mtcnn_plan(trl_ctx* ctx, trl_fn_plan_row* h_rows, int max_rows, int* n_rows);
-/* model.py:55-58 alone: crop rect (x0,y0,x1,y1 per frame, i32) -> f32 [n][80][80][3] in [0,1] */
+/* The three face-crop kernels alone, on caller-chosen rows.  Common to all three: frames u8 [n][H][W][3] with H, W >= 1 (the
+ * cascade's 12 px minimum does not apply), d_valid u8 [n]; a row with valid = 0 gets an all-zero face and its rectangle / points
+ * are never read.  PRECONDITION of a row with valid = 1 (the cascade's selection kernel guarantees it; the hooks do not check
+ * device memory): 0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H.  Nothing outside the rectangle is read.
+ * trl_debug_crop_resize = model.py:55-58: d_rect i32 [n][4] = x0,y0,x1,y1 -> f32 [n][80][80][3] in [0,1].  Its kernel takes the
+ * frame index from grid x, so any n > 0 is legal; the other two take it from grid y: 1 <= n <= 65535, the bound every public
+ * entry point already applies to a frame batch. */
 int  trl_debug_crop_resize(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W,
                            const int32_t* d_rect, const uint8_t* d_valid, float* d_faces, void* stream);
-/* embed_mode 3's crop alone: d_pts [n][10] = x0..x4, y0..y4 per frame -> f32 [n][S][S][3] */
+/* embed_mode 3's crop alone: d_pts [n][10] = x0..x4, y0..y4 per frame -> f32 [n][S][S][3], 1 <= S <= 4096 (any values, NaN
+ * included: samples outside the frame replicate its border) */
 int  trl_debug_crop_aligned(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W, const float* d_pts,
                             const uint8_t* d_valid, int S, int rgb, float* d_faces, void* stream);
+/* embed_mode 1 / 2's crop alone (extract_face for tensor input: area pooling to S x S, .byte(), (v - 127.5) / 128; rgb != 0
+ * reverses the channels): d_rect as for trl_debug_crop_resize -> f32 [n][S][S][3], 1 <= S <= 4096. (ABI v7) */
+int  trl_debug_crop_area(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect,
+                         const uint8_t* d_valid, int S, int rgb, float* d_faces, void* stream);
 /* Time (ms, HIP events on the call's stream) of the last trl_detect_embed / trl_detect_crop / trl_mtcnn_detect* call:
  * out[0] = PNet kernel (fused: the one persistent launch; generic: sum over levels),
  * out[1] = whole call, every attempt of a re-run call included (before this library version trl_mtcnn_detect* timed only the

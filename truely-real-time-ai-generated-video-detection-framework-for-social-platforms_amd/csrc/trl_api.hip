@@ -1,5 +1,6 @@
 // trl_api.hip -- C ABI of libtruely_hip.so (see include/truely_hip.h for the contract and the
 // reference lines each entry point replaces).
+#include <limits.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -866,16 +867,33 @@ int trl_debug_onet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* 
     TRL_CHECK(trl_ensure(c, c->scratch, (size_t)n * 640 * 1024 + (4u << 20)));
     return trl_run_onet(c, d_crops, n, d_out, (hipStream_t)stream);
 }
+// test hooks: the three face-crop kernels alone (include/truely_hip.h states the precondition on valid rows).  k_crop_resize80
+// indexes frames by grid x, so any n is a legal launch; k_crop_aligned / k_crop_area_std index them by grid y, which the public
+// entry points bound through check_call -- these hooks apply the same 65535.
+static int check_crop_hook(trl_ctx* c, const void* d_frames, int n, int n_max, int H, int W, const void* d_rows, const void* d_valid,
+                           int S, const void* d_faces) {
+    if (!c || !d_frames || !d_rows || !d_valid || !d_faces || n <= 0 || n > n_max || H < 1 || W < 1 || S < 1 || S > 4096) {
+        trl_set_error("bad argument (n=%d H=%d W=%d S=%d)", n, H, W, S);
+        return TRL_ERR_INVALID;
+    }
+    return TRL_OK;
+}
 int trl_debug_crop_resize(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid,
                           float* d_faces, void* stream) {
-    if (!c || !d_frames || !d_rect || !d_valid || !d_faces || n <= 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
+    TRL_CHECK(check_crop_hook(c, d_frames, n, INT_MAX, H, W, d_rect, d_valid, 80, d_faces));
     return trl_launch_crop_resize80(d_frames, n, H, W, d_rect, d_valid, d_faces, (hipStream_t)stream);
 }
 // embedding mode 3's crop alone: d_pts [n][10] (x0..x4, y0..y4 per frame) -> f32 [n][S][S][3]
 int trl_debug_crop_aligned(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, const float* d_pts, const uint8_t* d_valid, int S,
                            int rgb, float* d_faces, void* stream) {
-    if (!c || !d_frames || !d_pts || !d_valid || !d_faces || n <= 0 || H < 1 || W < 1 || S < 1) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
+    TRL_CHECK(check_crop_hook(c, d_frames, n, 65535, H, W, d_pts, d_valid, S, d_faces));
     return trl_launch_crop_aligned(d_frames, n, H, W, d_pts, d_valid, S, rgb != 0, d_faces, (hipStream_t)stream);
+}
+// embedding modes 1 / 2's crop alone: d_rect [n][4] -> f32 [n][S][S][3]
+int trl_debug_crop_area(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid, int S,
+                        int rgb, float* d_faces, void* stream) {
+    TRL_CHECK(check_crop_hook(c, d_frames, n, 65535, H, W, d_rect, d_valid, S, d_faces));
+    return trl_launch_crop_area_std(d_frames, n, H, W, d_rect, d_valid, S, rgb != 0, d_faces, (hipStream_t)stream);
 }
 // test hook: set the optimistic R-/O-Net batch capacities (candidates per frame) the next call starts from, and read back how
 // many attempts the last call needed (> 1: a capacity was too small and the call was re-run with a larger one)

@@ -591,24 +591,50 @@ class Engine:
             out.update({k: v.cpu().numpy() for k, v in dev.items()})
         return out
 
-    def crop_resize(self, frames, rect: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:
+    def _faces_out(self, out: torch.Tensor | None, n: int, S: int) -> torch.Tensor:
+        """The destination of a crop hook: a new tensor, or the caller's (e.g. pre-filled, to see what the kernel wrote)."""
+        if out is None:
+            return torch.empty((n, S, S, 3), dtype=torch.float32, device=self.device)
+        if out.shape != (n, S, S, 3) or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 ({n}, {S}, {S}, 3) tensor on {self.device}")
+        return out
+
+    def crop_resize(self, frames, rect: torch.Tensor, valid: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The default crop alone (model.py:55-58): each frame's rectangle (rect [n,4] = x0, y0, x1, y1) -> 80 x 80, / 255."""
         fr = self._frames(frames)
         n, H, W, _ = fr.shape
         rect = rect.to(self.device, torch.int32).contiguous(); valid = valid.to(self.device, torch.uint8).contiguous()
-        out = torch.empty((n, 80, 80, 3), dtype=torch.float32, device=self.device)
+        if rect.shape != (n, 4) or valid.shape != (n,):
+            raise ValueError("rect must be (n, 4) and valid (n,)")
+        out = self._faces_out(out, n, 80)
         _lib.check(self.lib.trl_debug_crop_resize(self._h, _ptr(fr), n, H, W, _ptr(rect), _ptr(valid), _ptr(out), self._stream()))
         return out
 
-    def crop_aligned(self, frames, pts: torch.Tensor, valid: torch.Tensor, S: int = 160, rgb: bool = True) -> torch.Tensor:
+    def crop_aligned(self, frames, pts: torch.Tensor, valid: torch.Tensor, S: int = 160, rgb: bool = True,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
         """Embedding mode 3's crop alone: five-point similarity alignment of each frame's face (pts [n,10] = x0..x4, y0..y4)."""
         fr = self._frames(frames)
         n, H, W, _ = fr.shape
         pts = pts.to(self.device, torch.float32).contiguous(); valid = valid.to(self.device, torch.uint8).contiguous()
         if pts.shape != (n, 10) or valid.shape != (n,):
             raise ValueError("pts must be (n, 10) and valid (n,)")
-        out = torch.empty((n, S, S, 3), dtype=torch.float32, device=self.device)
+        out = self._faces_out(out, n, int(S))
         _lib.check(self.lib.trl_debug_crop_aligned(self._h, _ptr(fr), n, H, W, _ptr(pts), _ptr(valid), int(S), int(bool(rgb)), _ptr(out),
                                                    self._stream()))
+        return out
+
+    def crop_area(self, frames, rect: torch.Tensor, valid: torch.Tensor, S: int = 160, rgb: bool = False,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+        """Embedding mode 1 / 2's crop alone: each frame's rectangle (rect [n,4] = x0, y0, x1, y1) area-pooled to S x S,
+        truncated to bytes, (v - 127.5) / 128, channels reversed when ``rgb``."""
+        fr = self._frames(frames)
+        n, H, W, _ = fr.shape
+        rect = rect.to(self.device, torch.int32).contiguous(); valid = valid.to(self.device, torch.uint8).contiguous()
+        if rect.shape != (n, 4) or valid.shape != (n,):
+            raise ValueError("rect must be (n, 4) and valid (n,)")
+        out = self._faces_out(out, n, int(S))
+        _lib.check(self.lib.trl_debug_crop_area(self._h, _ptr(fr), n, H, W, _ptr(rect), _ptr(valid), int(S), int(bool(rgb)), _ptr(out),
+                                                self._stream()))
         return out
 
     def levels(self, H: int, W: int) -> int:

@@ -4,7 +4,7 @@ cascade's k_nms_level / k_nms_frame / k_stage2_post / k_stage3_post / k_select w
 
 numpy / torch float32, one rounding per operation, in the reference's operation order; NMS, bbreg, rerec and pad are
 oracle/torch_ref.py's.  `route` restates how the cascade's host code sends a list to an LDS tier or to the spill tier
-(trl_cascade.hip: list_launch, k_nms_level, big_bitonic, big_greedy), so a test can show that a case reaches the edge it names.
+(trl_cascade.hip: list_launch, k_nms_level, sort_and_suppress, big_greedy), so a test can show that a case reaches the edge it names.
 """
 from __future__ import annotations
 
@@ -155,6 +155,17 @@ def route(ll, cnt, level=True):
         return ("full" if level else "lds", th, next_pow2(cnt), 0, 0)
     C = pow2_floor(cap)
     return ("spill", th, next_pow2(cnt), C, C * 8 // 20)
+
+
+def spill_bytes(kind, part, cnt, W, H):
+    """Bytes one spilled list of cnt entries takes from the spill pool (trl_cascade.hip: SpillWs::bytes, spill_alloc): sort keys
+    and payloads for P = next_pow2(cnt) slots (12 bytes each), kept box + area per entry (20 bytes) plus the grid's `next` link
+    (4) where the NMS is torchvision's -- kinds 1 and 2 -- and a kept-payload array of its own (4) where the list is not written
+    straight into the kernel's output -- every list but k_nms_level's --, the grid's heads (one int per 32-px cell of the frame,
+    kinds 1 and 2), rounded up to 256.  kind 1: part "level" = k_nms_level, "frame" = k_nms_frame."""
+    entry = 24 if (kind == 1 and part == "level") or kind == 3 else 28
+    grid = 0 if kind == 3 else ((W >> 5) + 1) * ((H >> 5) + 1) * 4
+    return (next_pow2(cnt) * 12 + cnt * entry + grid + 255) // 256 * 256
 
 
 # ---- lists built to sit on the kernels' edges ----

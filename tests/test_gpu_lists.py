@@ -61,10 +61,14 @@ def _check(case, ref, got, tag):
 
 
 def _expect_spill(case, ref, tiers):
-    """Lists that the routing restatement sends to the spill tier (list_stats counts them)."""
+    """(lists, bytes): the lists that the routing restatement sends to the spill tier and the pool bytes they request
+    (list_stats reports both)."""
     lv, fr = R.list_lengths(case, ref)
     ll = R.launch(tiers[0], tiers[1], case["caps"][:-1], case["caps"][-1])
-    return sum(R.route(ll, c, True)[0] == "spill" for c in lv) + sum(R.route(ll, c, False)[0] == "spill" for c in fr if c > 0)
+    W, H, kind = case["W"], case["H"], case["kind"]
+    spilled = [R.spill_bytes(1, "level", c, W, H) for c in lv if R.route(ll, c, True)[0] == "spill"]
+    spilled += [R.spill_bytes(kind, "frame", c, W, H) for c in fr if c > 0 and R.route(ll, c, False)[0] == "spill"]
+    return len(spilled), sum(spilled)
 
 
 @pytest.fixture(scope="module")
@@ -91,7 +95,7 @@ def test_list_kernels_at_edges(list_engine, oracle, tiers, kind):
                 got = _run(eng, case, order=1 if k == 1 else None)
                 _check(case, ref, got, f"tiers {tiers} kind {kind} {fam} n={n}")
                 st = eng.list_stats()
-                assert st["spill_lists"] == _expect_spill(case, ref, tiers), (tiers, kind, fam, n, st)
+                assert (st["spill_lists"], st["spill_used"]) == _expect_spill(case, ref, tiers), (tiers, kind, fam, n, st)
     finally:
         eng.nms_tiers(512, 2048)
 

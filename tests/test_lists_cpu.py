@@ -90,6 +90,18 @@ def test_probabilities_from_logits(oracle):
     assert p[0] == p[2] and p[3] > p[1] > p[4] > p[0] and (p > F32(0.7)).all()
 
 
+def test_spill_bytes_per_kind():
+    """The pool bytes of one spilled list in a 640 x 480 frame (21 x 16 grid cells = 1344 bytes of heads), by hand:
+    k_nms_level 513: 1024 * 12 + 513 * 24 + 1344 = 25944 -> 102 * 256; k_nms_frame 513: 1024 * 12 + 513 * 28 + 1344 = 27996 ->
+    110 * 256; k_stage2_post 2049: 4096 * 12 + 2049 * 28 + 1344 = 107868 -> 422 * 256; k_stage3_post 2049 (no grid):
+    4096 * 12 + 2049 * 24 = 98328 -> 385 * 256, and 64: 64 * 12 + 64 * 24 = 2304 = 9 * 256 exactly (no rounding past it)."""
+    assert R.spill_bytes(1, "level", 513, 640, 480) == 26112
+    assert R.spill_bytes(1, "frame", 513, 640, 480) == 28160
+    assert R.spill_bytes(2, "level", 2049, 640, 480) == 108032
+    assert R.spill_bytes(3, "level", 2049, 640, 480) == 98560
+    assert R.spill_bytes(3, "level", 64, 640, 480) == 2304
+
+
 @pytest.mark.parametrize("tiers", TIERS, ids=lambda t: f"{t[0]}-{t[1]}")
 def test_cases_reach_the_edges_they_name(oracle, tiers):
     """Restating list_launch / k_nms_level routing: the lengths test_gpu_lists.py builds for a tier pair reach the small tier

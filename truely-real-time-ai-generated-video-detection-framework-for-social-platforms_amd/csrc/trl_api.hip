@@ -916,11 +916,11 @@ int trl_debug_list_stats(trl_ctx* c, long long* h_out8) {
     if (!c || !h_out8) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
     const int32_t* f = c->h_pinned + 4;
     unsigned long long used = 0;
-    memcpy(&used, f + 8, 8);
+    memcpy(&used, f + FLG_SPILL_CUR, 8);
     int mx = 0;
-    for (int l = 0; l < 32; l++) if (f[16 + l] > mx) mx = f[16 + l];
-    h_out8[0] = c->last_attempts; h_out8[1] = f[10]; h_out8[2] = (long long)used; h_out8[3] = (long long)c->cb.spill_cap;
-    h_out8[4] = c->cb.capF; h_out8[5] = c->cb.lay.S; h_out8[6] = mx; h_out8[7] = f[6];
+    for (int l = 0; l < 32; l++) if (f[FLG_LEVEL_MAX + l] > mx) mx = f[FLG_LEVEL_MAX + l];
+    h_out8[0] = c->last_attempts; h_out8[1] = f[FLG_SPILL_LISTS]; h_out8[2] = (long long)used; h_out8[3] = (long long)c->cb.spill_cap;
+    h_out8[4] = c->cb.capF; h_out8[5] = c->cb.lay.S; h_out8[6] = mx; h_out8[7] = f[FLG_FRAME_MAX];
     return TRL_OK;
 }
 
@@ -955,7 +955,7 @@ int trl_debug_batch_capacity(trl_ctx* c, float t2_per_frame, float t3_per_frame,
 // R-Net / O-Net candidate totals of the last call (what the front kernels and the tails processed)
 int trl_debug_stage_totals(trl_ctx* c, int32_t* h_out2) {
     if (!c || !h_out2) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
-    h_out2[0] = c->h_pinned[4 + 4]; h_out2[1] = c->h_pinned[4 + 5];
+    h_out2[0] = c->h_pinned[4 + FLG_T2N]; h_out2[1] = c->h_pinned[4 + FLG_T3N];
     return TRL_OK;
 }
 

@@ -1,14 +1,16 @@
 // trl_cascade.hip -- the data-dependent part of MTCNN.detect on the device (gfx950).
 //
 // Restates facenet_pytorch 2.6.0 utils/detect_face.py::detect_face + MTCNN.detect
-// (select_largest=True) as called at server/model.py:47, and model.py:49-58 (int cast, clamp,
-// crop, cv2.resize INTER_LINEAR u8, to_tensor).  Everything stays on the GPU; candidates live in
+// (select_largest=True) as called at server/model.py:47, and model.py:49-54 (int cast, clamp; the crops
+// of model.py:55-58 are trl_crops.hip's).  Everything stays on the GPU; candidates live in
 // fixed-capacity per-frame lists.  One workgroup owns one (frame, level) or one frame segment:
 //   sort   : bitonic sort in LDS on a 64-bit key  (~score | tie-break index) -> exactly the order of
 //            a stable descending sort, so results do not depend on the order candidates were
 //            appended by the PNet kernel's atomics;
 //   NMS    : greedy suppression in sorted order, all lanes test one kept box against the rest;
 //   compact: ordered compaction by block scan, so list order equals the reference's `pick` order.
+// The four list kernels (k_nms_level, k_nms_frame, k_stage2_post, k_stage3_post) share one routine for the first two
+// (sort_and_suppress: LDS tier and spill tier) and one for the third (write_rows); a kernel adds its keys, its boxes and its rows.
 // All float expressions follow the reference's operation order (one rounding per op,
 // -ffp-contract=off), so boxes / keep masks are bit-identical to the oracle.
 #include "trl_ctx.h"
@@ -27,23 +29,27 @@ __device__ __forceinline__ uint32_t f2ord(float f) {   // ascending-order preser
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// The 64-bit sort key: ascending keys = descending score, ties by ascending `tie`.  NO_KEY sorts behind every entry.
+__device__ __forceinline__ uint64_t sort_key(float score, uint32_t tie) { return ((uint64_t)~f2ord(score) << 32) | tie; }
+constexpr uint64_t NO_KEY = ~0ull;
+
 // ---- block primitives ------------------------------------------------------------------------
-__device__ void block_bitonic(uint64_t* key, uint32_t* id, int P) {
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < P; t += blockDim.x) {
-                const int u = t ^ j;
-                if (u > t) {
-                    const bool up = ((t & k) == 0);
-                    const uint64_t a = key[t], b = key[u];
-                    if ((a > b) == up) {
-                        key[t] = b; key[u] = a;
-                        const uint32_t ia = id[t]; id[t] = id[u]; id[u] = ia;
-                    }
+// The bitonic network's compare-exchange distances j0, j0/2, .., 1 of merge width k on C LDS-resident entries that are entries
+// [base, base + C) of the list.  A list that fits LDS is sorted by `for k = 2, 4, .., P: steps(key, id, P, 0, k, k / 2)`.
+__device__ void lds_bitonic_steps(uint64_t* key, uint32_t* id, int C, int base, int k, int j0) {
+    for (int j = j0; j > 0; j >>= 1) {
+        for (int t = threadIdx.x; t < C; t += blockDim.x) {
+            const int u = t ^ j;
+            if (u > t) {
+                const bool up = (((base + t) & k) == 0);
+                const uint64_t a = key[t], b = key[u];
+                if ((a > b) == up) {
+                    key[t] = b; key[u] = a;
+                    const uint32_t ia = id[t]; id[t] = id[u]; id[u] = ia;
                 }
             }
-            __syncthreads();
         }
+        __syncthreads();
     }
 }
 __device__ __forceinline__ int next_pow2(int n) {
@@ -74,6 +80,11 @@ __device__ __forceinline__ bool nms_suppresses(const float4 bi, const float ai, 
         const float ovr = inter / (ai + aj - inter);
         return ovr > thr;
     }
+}
+
+template <bool MIN_MODE>
+__device__ __forceinline__ float box_area(const float4 b) {   // nms_numpy's +1 extents / torchvision's plain ones
+    return MIN_MODE ? (b.z - b.x + 1.f) * (b.w - b.y + 1.f) : (b.z - b.x) * (b.w - b.y);
 }
 
 // Greedy NMS over boxes already in descending-score order.  MIN_MODE = facenet_pytorch
@@ -178,10 +189,7 @@ struct Smem {   // carve the dynamic LDS for capacity `cap`
 //            sequential rule, so the pick order and every keep decision equal the LDS tier's (and the reference's).
 // Workspace comes from a bump pool in the cascade arena (one atomic per list); a pool that runs out raises a flag and the call is
 // re-run with a larger one, like every other capacity (trl_cascade_check).
-struct Spill { char* base; unsigned long long cap; int32_t* flags; };
-enum { FLG_LEVEL = 0, FLG_FRAME = 1, FLG_T2 = 2, FLG_T3 = 3, FLG_T2N = 4, FLG_T3N = 5, FLG_FRAME_MAX = 6, FLG_SPILL = 7,
-       FLG_SPILL_CUR = 8 /* u64 */, FLG_SPILL_LISTS = 10, FLG_LEVEL_MAX = 16 /* [32] */ };
-
+struct Spill { char* base; unsigned long long cap; int32_t* flags; };   // the pool and the overflow words (trl_ctx.h FLG_*)
 __device__ char* spill_alloc(const Spill& sp, size_t bytes) {   // every thread of the workgroup calls it; uniform result
     __shared__ unsigned long long off_s;
     bytes = (bytes + 255) & ~(size_t)255;
@@ -199,23 +207,6 @@ __device__ __forceinline__ int pow2_floor(int n) {
     int p = 1;
     while (2 * p <= n) p <<= 1;
     return p;
-}
-// compare-exchange distances j0, j0/2, .., 1 of merge width k on the LDS-resident chunk [base, base + C) of the list
-__device__ void lds_bitonic_steps(uint64_t* key, uint32_t* id, int C, int base, int k, int j0) {
-    for (int j = j0; j > 0; j >>= 1) {
-        for (int t = threadIdx.x; t < C; t += blockDim.x) {
-            const int u = t ^ j;
-            if (u > t) {
-                const bool up = (((base + t) & k) == 0);
-                const uint64_t a = key[t], b = key[u];
-                if ((a > b) == up) {
-                    key[t] = b; key[u] = a;
-                    const uint32_t ia = id[t]; id[t] = id[u]; id[u] = ia;
-                }
-            }
-        }
-        __syncthreads();
-    }
 }
 // ascending sort of gk[0..P) (P a power of two, padded with ~0 keys) with payload gi, by one workgroup; lk / li: LDS for C entries
 __device__ void big_bitonic(uint64_t* gk, uint32_t* gi, int P, uint64_t* lk, uint32_t* li, int C) {
@@ -295,7 +286,7 @@ __device__ int big_greedy(const Smem& S, int C, const uint32_t* gi, int m, float
                 const uint32_t id = gi[base + t];
                 const float4 b = box_of(id);
                 bt[e] = b;
-                at[e] = MIN_MODE ? (b.z - b.x + 1.f) * (b.w - b.y + 1.f) : (b.z - b.x) * (b.w - b.y);
+                at[e] = box_area<MIN_MODE>(b);
                 S.box[t] = b; S.area[t] = at[e]; S.id[t] = id;
                 sp[e] = false;
             }
@@ -358,6 +349,82 @@ __device__ int big_greedy(const Smem& S, int C, const uint32_t* gi, int m, float
     return K;
 }
 
+// Workspace of one spilled list of n entries, P = next_pow2(n) sort slots:  gk | gi | kbox | karea | [kid] | [next | head].
+// kid is part of it unless the kept payloads go straight to the caller's array (kid_out); next / head are the kept grid (IoU mode).
+// bytes() is what the list asks of the pool -- the kernels and the host's up-front bound (spill_need) share it.
+struct SpillWs {
+    uint64_t* gk; uint32_t* gi; float4* kbox; float* karea; uint32_t* kid; KeptGrid grid;
+    static __host__ __device__ size_t grid_cells(int W, int H) { return (size_t)((W >> GRID_SHIFT) + 1) * (size_t)((H >> GRID_SHIFT) + 1); }
+    static __host__ __device__ size_t bytes(size_t P, size_t n, bool own_kid, bool grid, int W, int H) {
+        return P * 12 + n * (20 + (own_kid ? 4 : 0) + (grid ? 4 : 0)) + (grid ? grid_cells(W, H) * 4 : 0);
+    }
+    __device__ SpillWs(char* w, int P, int n, uint32_t* kid_out, bool with_grid, int W, int H) {
+        gk = (uint64_t*)w; gi = (uint32_t*)(gk + P);
+        kbox = (float4*)(gi + P); karea = (float*)(kbox + n);
+        int* rest = (int*)(karea + n);
+        kid = kid_out ? kid_out : (uint32_t*)rest;
+        if (!kid_out) rest += n;
+        grid = with_grid ? KeptGrid{rest + n, rest, (W >> GRID_SHIFT) + 1, (H >> GRID_SHIFT) + 1} : KeptGrid{nullptr, nullptr, 0, 0};
+    }
+};
+
+// What sort_and_suppress leaves: n kept entries in pick order, entry r = payload id(r), box(r).  keep != null: the list sits in LDS
+// at the sorted positions keep[r] (S.id, S.box); otherwise in the spill workspace (kid, kbox).
+struct Kept {
+    int n; const int* keep; const uint32_t* ids; const float4* boxes;
+    __device__ uint32_t id(int r) const { return ids[keep ? keep[r] : r]; }
+    __device__ float4 box(int r) const { return boxes[keep ? keep[r] : r]; }
+};
+
+// Sort + greedy NMS of one list of n >= 1 entries by one workgroup (every thread calls it), in the LDS tier (n <= lds_cap) or the
+// spill tier.  key_of(t, id) = entry t's sort_key, or NO_KEY when it is under the list's threshold (THRESHOLD lists only), and may
+// replace its payload id (default t); box_of(id) = the box NMS sees.  kid_out (nullable) receives the kept payloads in pick order.
+// A spilled list that finds no workspace is dropped (spill_alloc raises FLG_SPILL: the call is re-run): count 0, like an empty one.
+template <bool MIN_MODE, bool THRESHOLD, class KeyOf, class BoxOf>
+__device__ __forceinline__ Kept sort_and_suppress(const Smem& S, int lds_cap, int n, float nms_thr, const Spill& sp, uint32_t* kid_out, int W, int H,
+                                                  KeyOf key_of, BoxOf box_of) {
+    const int P = next_pow2(n);
+    auto make_keys = [&](uint64_t* key, uint32_t* id) {   // P keys (NO_KEY behind the list) + payloads; returns the survivors
+        if (THRESHOLD) {
+            if (threadIdx.x == 0) S.scal[4] = 0;
+            __syncthreads();
+        }
+        int mine = 0;
+        for (int t = threadIdx.x; t < P; t += blockDim.x) {
+            uint64_t k = NO_KEY;
+            uint32_t i = t;
+            if (t < n) k = key_of(t, i);
+            mine += k != NO_KEY;
+            key[t] = k; id[t] = i;
+        }
+        if (THRESHOLD && mine) atomicAdd(&S.scal[4], mine);
+        __syncthreads();
+        return THRESHOLD ? S.scal[4] : n;                 // (scal is reused by the NMS, behind the sort's barriers)
+    };
+    const Kept none{0, nullptr, nullptr, nullptr};
+    if (n > lds_cap) {
+        char* w = spill_alloc(sp, SpillWs::bytes(P, n, !kid_out, !MIN_MODE, W, H));
+        if (!w) return none;
+        const SpillWs ws(w, P, n, kid_out, !MIN_MODE, W, H);
+        const int m = make_keys(ws.gk, ws.gi), C = pow2_floor(lds_cap);
+        if (m == 0) return none;
+        big_bitonic(ws.gk, ws.gi, P, S.key, S.id, C);
+        return Kept{big_greedy<MIN_MODE>(S, C, ws.gi, m, nms_thr, box_of, ws.kbox, ws.karea, ws.kid, ws.grid), nullptr, ws.kid, ws.kbox};
+    }
+    const int m = make_keys(S.key, S.id);
+    if (m == 0) return none;
+    for (int k = 2; k <= P; k <<= 1) lds_bitonic_steps(S.key, S.id, P, 0, k, k >> 1);
+    for (int t = threadIdx.x; t < m; t += blockDim.x) {
+        const float4 b = box_of(S.id[t]);
+        S.box[t] = b; S.area[t] = box_area<MIN_MODE>(b);
+    }
+    __syncthreads();
+    const int nk = block_nms<MIN_MODE>(S.box, S.area, m, nms_thr, S.sup, S.keep, S.scal);
+    if (kid_out) for (int r = threadIdx.x; r < nk; r += blockDim.x) kid_out[r] = S.id[S.keep[r]];
+    return Kept{nk, S.keep, S.id, S.box};
+}
+
+
 // rerec() of one box
 __device__ __forceinline__ void rerec1(float& x1, float& y1, float& x2, float& y2) {
     const float h = y2 - y1, w = x2 - x1;
@@ -375,6 +442,34 @@ __device__ __forceinline__ bool pad1(float x1, float y1, float x2, float y2, int
     ex = bex > W ? W : bex;
     ey = bey > H ? H : bey;
     return (ey > y - 1) && (ex > x - 1);
+}
+
+// Kept list -> rows (x1, y1, x2, y2, score) at fout, in pick order, without the rows whose clipped box is empty; returns the row
+// count.  row_of(r, box, score) = row of kept entry r and whether it stays.  Chunks of `cap` rows staged in LDS (ordered
+// compaction by block scan); a list of the LDS tier is one chunk.  row_of must not read S.box / S.aux / S.flg.
+template <class RowOf>
+__device__ __forceinline__ int write_rows(const Smem& S, int cap, int n, float* fout, RowOf row_of) {
+    int out = 0;
+    for (int base = 0; base < n; base += cap) {
+        const int nc = n - base < cap ? n - base : cap;
+        if (base) __syncthreads();                        // (the previous chunk's rows have left LDS)
+        for (int r = threadIdx.x; r < nc; r += blockDim.x) {
+            float4 b;
+            float score;
+            S.flg[r] = row_of(base + r, b, score) ? 1 : 0;
+            S.box[r] = b; S.aux[r] = score;
+        }
+        __syncthreads();
+        const int m = block_compact_positions(S.flg, nc, S.pos, S.part);
+        for (int r = threadIdx.x; r < nc; r += blockDim.x) {
+            if (!S.flg[r]) continue;
+            float* o = fout + (size_t)(out + S.pos[r]) * 5;
+            const float4 b = S.box[r];
+            o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = S.aux[r];
+        }
+        out += m;
+    }
+    return out;
 }
 
 // ---- imresample (F.interpolate mode="area") of whole frames to one pyramid level --------------
@@ -413,7 +508,7 @@ __global__ void k_pnet_collect(const float* __restrict__ heads, int nf, int f0, 
         const int f = f0 + (int)(idx / ((size_t)oh * ow));
         const int y = cell / ow, x = cell - y * ow;
         const int slot = atomicAdd(&lvl_cnt[f * L + l], 1);
-        if (slot >= cap) { flags[0] = 1; continue; }
+        if (slot >= cap) { flags[FLG_LEVEL] = 1; continue; }
         Cand c;
         c.x1 = floorf((2.f * (float)x + 1.f) / scale);
         c.y1 = floorf((2.f * (float)y + 1.f) / scale);
@@ -433,6 +528,8 @@ __global__ void k_heads_to_maps(const float* __restrict__ heads, int cells, floa
     prob[i] = trl_softmax2_p1(hd[0], hd[1]);
     reg[4 * i + 0] = hd[2]; reg[4 * i + 1] = hd[3]; reg[4 * i + 2] = hd[4]; reg[4 * i + 3] = hd[5];
 }
+
+__device__ __forceinline__ float4 cand_box(const Cand& c) { return make_float4(c.x1, c.y1, c.x2, c.y2); }
 
 // ---- stage 1a: per (frame, level) batched_nms(0.5) ------------------------------------------
 // Two launches share the segments: the SMALL tier (LDS sized for `lds_cap` = 512 candidates: ~24 KB, six workgroups per CU) takes
@@ -457,42 +554,10 @@ __global__ __launch_bounds__(1024) void k_nms_level(LvLayout G, int lds_cap, int
     if (cnt == 0) { if (threadIdx.x == 0) keep_cnt[seg] = 0; return; }
     const Cand* recs = lvl_rec + (size_t)f * G.S + G.rec0[l];
     int32_t* kout = keep_idx + (size_t)f * G.S + G.rec0[l];
-    if (cnt > lds_cap) {                                                          // ---- spill tier
-        const int P = next_pow2(cnt);
-        const int gx = (W >> GRID_SHIFT) + 1, gy = (H >> GRID_SHIFT) + 1;
-        char* w = spill_alloc(sp, (size_t)P * 12 + (size_t)cnt * 24 + (size_t)gx * gy * 4);
-        if (!w) { if (threadIdx.x == 0) keep_cnt[seg] = 0; return; }
-        uint64_t* gk = (uint64_t*)w; uint32_t* gi = (uint32_t*)(gk + P);
-        float4* kbox = (float4*)(gi + P); float* karea = (float*)(kbox + cnt);
-        const KeptGrid grid{(int*)(karea + cnt) + cnt, (int*)(karea + cnt), gx, gy};
-        for (int t = threadIdx.x; t < P; t += blockDim.x) {
-            gk[t] = t < cnt ? (((uint64_t)(~f2ord(recs[t].score))) << 32) | (uint32_t)recs[t].cell : ~0ull;
-            gi[t] = t;
-        }
-        __syncthreads();
-        big_bitonic(gk, gi, P, S.key, S.id, pow2_floor(lds_cap));
-        const int nk = big_greedy<false>(S, pow2_floor(lds_cap), gi, cnt, 0.5f,
-                                         [&](uint32_t id) { const Cand& c = recs[id]; return make_float4(c.x1, c.y1, c.x2, c.y2); },
-                                         kbox, karea, (uint32_t*)kout, grid);
-        if (threadIdx.x == 0) keep_cnt[seg] = nk;
-        return;
-    }
-    const int P = next_pow2(cnt);
-    for (int t = threadIdx.x; t < P; t += blockDim.x) {
-        S.key[t] = t < cnt ? (((uint64_t)(~f2ord(recs[t].score))) << 32) | (uint32_t)recs[t].cell : ~0ull;
-        S.id[t] = t;
-    }
-    __syncthreads();
-    block_bitonic(S.key, S.id, P);
-    for (int t = threadIdx.x; t < cnt; t += blockDim.x) {
-        const Cand& c = recs[S.id[t]];
-        S.box[t] = make_float4(c.x1, c.y1, c.x2, c.y2);
-        S.area[t] = (c.x2 - c.x1) * (c.y2 - c.y1);
-    }
-    __syncthreads();
-    const int nk = block_nms<false>(S.box, S.area, cnt, 0.5f, S.sup, S.keep, S.scal);
-    for (int r = threadIdx.x; r < nk; r += blockDim.x) kout[r] = (int)S.id[S.keep[r]];
-    if (threadIdx.x == 0) keep_cnt[seg] = nk;
+    const Kept K = sort_and_suppress<false, false>(S, lds_cap, cnt, 0.5f, sp, (uint32_t*)kout, W, H,
+        [&](int t, uint32_t&) { return sort_key(recs[t].score, (uint32_t)recs[t].cell); },   // ties: raster (cell) order
+        [&](uint32_t id) { return cand_box(recs[id]); });
+    if (threadIdx.x == 0) keep_cnt[seg] = K.n;
 }
 
 // ---- stage 1b: per frame batched_nms(0.7) over all levels, regress, rerec ----------------------
@@ -524,86 +589,20 @@ __global__ __launch_bounds__(1024) void k_nms_frame(LvLayout G, int lds_cap, int
     if (total == 0 || total > capF) { if (threadIdx.x == 0) n1[f] = 0; return; }
     const Cand* frec = lvl_rec + (size_t)f * G.S;
     const int32_t* fkeep = keep_idx + (size_t)f * G.S;
-    auto fill = [&](int e, uint64_t& key, uint32_t& gid) {   // entry e of the concatenated per-level pick lists
-        int l = 0;
-        while (e >= offs[l + 1]) l++;
-        gid = (uint32_t)(G.rec0[l] + fkeep[G.rec0[l] + (e - offs[l])]);
-        key = (((uint64_t)(~f2ord(frec[gid].score))) << 32) | (uint32_t)e;   // e = position in the concatenated list
-    };
-    float* fout = s1_box + (size_t)f * capF * 5;
-    if (total > lds_cap) {                                                        // ---- spill tier
-        const int P = next_pow2(total), C = pow2_floor(lds_cap);
-        const int gx = (W >> GRID_SHIFT) + 1, gy = (H >> GRID_SHIFT) + 1;
-        char* w = spill_alloc(sp, (size_t)P * 12 + (size_t)total * 28 + (size_t)gx * gy * 4);
-        if (!w) { if (threadIdx.x == 0) n1[f] = 0; return; }
-        uint64_t* gk = (uint64_t*)w; uint32_t* gi = (uint32_t*)(gk + P);
-        float4* kbox = (float4*)(gi + P); float* karea = (float*)(kbox + total); uint32_t* kid = (uint32_t*)(karea + total);
-        const KeptGrid grid{(int*)(kid + total) + total, (int*)(kid + total), gx, gy};
-        for (int e = threadIdx.x; e < P; e += blockDim.x) {
-            uint64_t k = ~0ull; uint32_t g = 0;
-            if (e < total) fill(e, k, g);
-            gk[e] = k; gi[e] = g;
-        }
-        __syncthreads();
-        big_bitonic(gk, gi, P, S.key, S.id, C);
-        const int nk = big_greedy<false>(S, C, gi, total, 0.7f,
-                                         [&](uint32_t id) { const Cand& c = frec[id]; return make_float4(c.x1, c.y1, c.x2, c.y2); },
-                                         kbox, karea, kid, grid);
-        int out = 0;                                                              // rows written so far (ordered compaction, chunk by chunk)
-        for (int base = 0; base < nk; base += C) {
-            const int nc = nk - base < C ? nk - base : C;
-            for (int r = threadIdx.x; r < nc; r += blockDim.x) {
-                const Cand& c = frec[kid[base + r]];
-                float4 b;
-                S.flg[r] = stage1_row(c, W, H, b) ? 1 : 0;
-                S.box[r] = b; S.aux[r] = c.score;
-            }
-            __syncthreads();
-            const int m = block_compact_positions(S.flg, nc, S.pos, S.part);
-            for (int r = threadIdx.x; r < nc; r += blockDim.x) {
-                if (!S.flg[r]) continue;
-                float* o = fout + (size_t)(out + S.pos[r]) * 5;
-                const float4 b = S.box[r];
-                o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = S.aux[r];
-            }
-            out += m;
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) n1[f] = out;
-        return;
-    }
-    const int P = next_pow2(total);
-    for (int e = threadIdx.x; e < P; e += blockDim.x) {
-        uint64_t k = ~0ull; uint32_t g = 0;
-        if (e < total) fill(e, k, g);
-        S.key[e] = k; S.id[e] = g;
-    }
-    __syncthreads();
-    block_bitonic(S.key, S.id, P);
-    for (int t = threadIdx.x; t < total; t += blockDim.x) {
-        const Cand& c = frec[S.id[t]];
-        S.box[t] = make_float4(c.x1, c.y1, c.x2, c.y2);
-        S.area[t] = (c.x2 - c.x1) * (c.y2 - c.y1);
-    }
-    __syncthreads();
-    const int nk = block_nms<false>(S.box, S.area, total, 0.7f, S.sup, S.keep, S.scal);
-    // regress with the PNet offsets (w,h WITHOUT +1), rerec, drop empty clipped boxes
-    for (int r = threadIdx.x; r < nk; r += blockDim.x) {
-        const Cand& c = frec[S.id[S.keep[r]]];
-        float4 b;
-        S.flg[r] = stage1_row(c, W, H, b) ? 1 : 0;
-        S.box[r] = b;   // box[] no longer needed by NMS
-        S.aux[r] = c.score;
-    }
-    __syncthreads();
-    const int m = block_compact_positions(S.flg, nk, S.pos, S.part);
-    for (int r = threadIdx.x; r < nk; r += blockDim.x) {
-        if (!S.flg[r]) continue;
-        float* o = fout + (size_t)S.pos[r] * 5;
-        const float4 b = S.box[r];
-        o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = S.aux[r];
-    }
-    if (threadIdx.x == 0) n1[f] = m;
+    const Kept K = sort_and_suppress<false, false>(S, lds_cap, total, 0.7f, sp, nullptr, W, H,
+        [&](int e, uint32_t& gid) {                          // entry e of the concatenated per-level pick lists
+            int l = 0;
+            while (e >= offs[l + 1]) l++;
+            gid = (uint32_t)(G.rec0[l] + fkeep[G.rec0[l] + (e - offs[l])]);
+            return sort_key(frec[gid].score, (uint32_t)e);   // ties: position in the concatenated list
+        },
+        [&](uint32_t id) { return cand_box(frec[id]); });
+    const int out = write_rows(S, lds_cap, K.n, s1_box + (size_t)f * capF * 5, [&](int r, float4& b, float& score) {
+        const Cand& c = frec[K.id(r)];
+        score = c.score;
+        return stage1_row(c, W, H, b);
+    });
+    if (threadIdx.x == 0) n1[f] = out;
 }
 
 // exclusive scan of per-frame counts; off[n] = total.  Also the candidate -> (frame, local) map.
@@ -626,7 +625,7 @@ __global__ __launch_bounds__(256) void k_scan_counts(const int32_t* __restrict__
     int run = part[t];
     for (int i = b; i < e; i++) { off[i] = run; run += cnt[i]; }
     // the batch the next stage processes was sized by an optimistic capacity: report the real total and whether it fits
-    if (t == 0) { const int total = part[256]; off[n] = total; flags[4 + slot] = total; if (total > cap_total) flags[2 + slot] = 1; }
+    if (t == 0) { const int total = part[256]; off[n] = total; flags[FLG_T2N + slot] = total; if (total > cap_total) flags[FLG_T2 + slot] = 1; }
 }
 // Candidate list of a stage in launch order: candidate t = off[f] + i is box i of frame f.  The record holds what the front kernel
 // needs to start its crop -- frame index and pad()'s clamped window (detect_face.py pad(): x = max(x1, 1), ex = min(x2, W), crop
@@ -667,100 +666,17 @@ __global__ __launch_bounds__(1024) void k_stage2_post(int lds_cap, int capF, int
     if (cnt == 0 || off2[gridDim.x] > cap_total) { if (threadIdx.x == 0) n2[f] = 0; return; }
     const float* logits = out6 + (size_t)off2[f] * 6;
     const float* fb = s1_box + (size_t)f * capF * 5;
-    float* fout = s2_box + (size_t)f * capF * 5;
-    const int P = next_pow2(cnt);
-    if (threadIdx.x == 0) S.scal[4] = 0;
-    __syncthreads();
-    if (cnt > lds_cap) {                                                          // ---- spill tier
-        const int C = pow2_floor(lds_cap);
-        const int gx = (W >> GRID_SHIFT) + 1, gy = (H >> GRID_SHIFT) + 1;
-        char* w = spill_alloc(sp, (size_t)P * 12 + (size_t)cnt * 28 + (size_t)gx * gy * 4);
-        if (!w) { if (threadIdx.x == 0) n2[f] = 0; return; }
-        uint64_t* gk = (uint64_t*)w; uint32_t* gi = (uint32_t*)(gk + P);
-        float4* kbox = (float4*)(gi + P); float* karea = (float*)(kbox + cnt); uint32_t* kid = (uint32_t*)(karea + cnt);
-        const KeptGrid grid{(int*)(kid + cnt) + cnt, (int*)(kid + cnt), gx, gy};
-        int mine = 0;
-        for (int i = threadIdx.x; i < P; i += blockDim.x) {
-            uint64_t k = ~0ull;
-            if (i < cnt) {
-                const float p = trl_softmax2_p1(logits[6 * i], logits[6 * i + 1]);
-                if (p > thr) { k = (((uint64_t)(~f2ord(p))) << 32) | (uint32_t)i; mine++; }
-            }
-            gk[i] = k; gi[i] = i;
-        }
-        if (mine) atomicAdd(&S.scal[4], mine);
-        __syncthreads();
-        const int m = S.scal[4];
-        __syncthreads();                                                          // (scal is reused by the NMS below)
-        if (m == 0) { if (threadIdx.x == 0) n2[f] = 0; return; }
-        big_bitonic(gk, gi, P, S.key, S.id, C);
-        const int nk = big_greedy<false>(S, C, gi, m, 0.7f,
-                                         [&](uint32_t i) { const float* b = fb + 5 * i; return make_float4(b[0], b[1], b[2], b[3]); },
-                                         kbox, karea, kid, grid);
-        int out = 0;
-        for (int base = 0; base < nk; base += C) {
-            const int nc = nk - base < C ? nk - base : C;
-            for (int r = threadIdx.x; r < nc; r += blockDim.x) {
-                const int i = (int)kid[base + r];
-                float4 b;
-                S.flg[r] = stage2_row(kbox[base + r], logits + 6 * i + 2, W, H, b) ? 1 : 0;
-                S.box[r] = b; S.aux[r] = trl_softmax2_p1(logits[6 * i], logits[6 * i + 1]);
-            }
-            __syncthreads();
-            const int mm = block_compact_positions(S.flg, nc, S.pos, S.part);
-            for (int r = threadIdx.x; r < nc; r += blockDim.x) {
-                if (!S.flg[r]) continue;
-                float* o = fout + (size_t)(out + S.pos[r]) * 5;
-                const float4 b = S.box[r];
-                o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = S.aux[r];
-            }
-            out += mm;
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) n2[f] = out;
-        return;
-    }
-    for (int i = threadIdx.x; i < P; i += blockDim.x) {
-        uint64_t k = ~0ull;
-        if (i < cnt) {
-            const float p = trl_softmax2_p1(logits[6 * i], logits[6 * i + 1]);
-            S.aux[i] = p;
-            if (p > thr) { k = (((uint64_t)(~f2ord(p))) << 32) | (uint32_t)i; atomicAdd(&S.scal[4], 1); }
-        }
-        S.key[i] = k; S.id[i] = i;
-    }
-    __syncthreads();
-    const int m = S.scal[4];
-    if (m == 0) { if (threadIdx.x == 0) n2[f] = 0; return; }
-    block_bitonic(S.key, S.id, P);
-    for (int t = threadIdx.x; t < m; t += blockDim.x) {
-        const float* b = fb + 5 * S.id[t];
-        S.box[t] = make_float4(b[0], b[1], b[2], b[3]);
-        S.area[t] = (b[2] - b[0]) * (b[3] - b[1]);
-    }
-    __syncthreads();
-    const int nk = block_nms<false>(S.box, S.area, m, 0.7f, S.sup, S.keep, S.scal);
-    // bbreg (+1 widths), rerec; rows go to s2_box provisionally at r, then are compacted in place
-    for (int r = threadIdx.x; r < nk; r += blockDim.x) {
-        const int i = (int)S.id[S.keep[r]];
-        float4 b;
-        S.flg[r] = stage2_row(S.box[S.keep[r]], logits + 6 * i + 2, W, H, b) ? 1 : 0;
-        float* o = fout + (size_t)r * 5;
-        o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w; o[4] = S.aux[i];
-    }
-    __syncthreads();
-    const int mm = block_compact_positions(S.flg, nk, S.pos, S.part);
-    // in-place ordered compaction (pos[r] <= r): rounds of blockDim rows, reads precede writes
-    float row[5];
-    for (int base = 0; base < nk; base += blockDim.x) {
-        const int r = base + threadIdx.x;
-        bool live = r < nk && S.flg[r];
-        if (live) { const float* o = fout + (size_t)r * 5; for (int q = 0; q < 5; q++) row[q] = o[q]; }
-        __syncthreads();
-        if (live) { float* o = fout + (size_t)S.pos[r] * 5; for (int q = 0; q < 5; q++) o[q] = row[q]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) n2[f] = mm;
+    auto prob = [&](int i) { return trl_softmax2_p1(logits[6 * i], logits[6 * i + 1]); };
+    auto s1 = [&](uint32_t i) { const float* b = fb + 5 * i; return make_float4(b[0], b[1], b[2], b[3]); };
+    const Kept K = sort_and_suppress<false, true>(S, lds_cap, cnt, 0.7f, sp, nullptr, W, H,
+        [&](int i, uint32_t&) { const float p = prob(i); return p > thr ? sort_key(p, (uint32_t)i) : NO_KEY; },
+        s1);
+    const int out = write_rows(S, lds_cap, K.n, s2_box + (size_t)f * capF * 5, [&](int r, float4& b, float& score) {
+        const int i = (int)K.id(r);
+        score = prob(i);
+        return stage2_row(s1(i), logits + 6 * i + 2, W, H, b);
+    });
+    if (threadIdx.x == 0) n2[f] = out;
 }
 
 // ---- stage 3 tail: thr2, landmarks, bbreg, nms 'Min' 0.7 --------------------------------------
@@ -785,73 +701,19 @@ __global__ __launch_bounds__(1024) void k_stage3_post(int lds_cap, int capF, int
     if (cnt == 0 || off3[gridDim.x] > cap_total) { if (threadIdx.x == 0) n3[f] = 0; return; }   // see k_stage2_post
     const float* logits = out16 + (size_t)off3[f] * 16;
     const float* fb = s2_box + (size_t)f * capF * 5;
-    const int P = next_pow2(cnt);
-    if (threadIdx.x == 0) S.scal[4] = 0;
-    __syncthreads();
-    if (cnt > lds_cap) {                                                          // ---- spill tier
-        const int C = pow2_floor(lds_cap);
-        char* w = spill_alloc(sp, (size_t)P * 12 + (size_t)cnt * 24);
-        if (!w) { if (threadIdx.x == 0) n3[f] = 0; return; }
-        uint64_t* gk = (uint64_t*)w; uint32_t* gi = (uint32_t*)(gk + P);
-        float4* kbox = (float4*)(gi + P); float* karea = (float*)(kbox + cnt); uint32_t* kid = (uint32_t*)(karea + cnt);
-        int mine = 0;
-        for (int i = threadIdx.x; i < P; i += blockDim.x) {
-            uint64_t k = ~0ull;
-            if (i < cnt) {
-                const float p = trl_softmax2_p1(logits[16 * i], logits[16 * i + 1]);
-                if (p > thr) { k = (((uint64_t)(~f2ord(p))) << 32) | (uint32_t)(~(uint32_t)i); mine++; }
-            }
-            gk[i] = k; gi[i] = i;
-        }
-        if (mine) atomicAdd(&S.scal[4], mine);
-        __syncthreads();
-        const int m = S.scal[4];
-        __syncthreads();
-        if (m == 0) { if (threadIdx.x == 0) n3[f] = 0; return; }
-        big_bitonic(gk, gi, P, S.key, S.id, C);
-        const int nk = big_greedy<true>(S, C, gi, m, 0.7f,
-                                        [&](uint32_t i) { return stage3_box(fb + 5 * i, logits + 16 * i + 2); }, kbox, karea, kid,
-                                        KeptGrid{nullptr, nullptr, 0, 0});
-        for (int r = threadIdx.x; r < nk; r += blockDim.x) {
-            const int i = (int)kid[r];
-            const float4 bb = kbox[r];
-            float* o = s3_box + ((size_t)f * capF + r) * 5;
-            o[0] = bb.x; o[1] = bb.y; o[2] = bb.z; o[3] = bb.w; o[4] = trl_softmax2_p1(logits[16 * i], logits[16 * i + 1]);
-            stage3_points(fb + 5 * i, logits + 16 * i + 6, s3_pts + ((size_t)f * capF + r) * 10);
-        }
-        if (threadIdx.x == 0) n3[f] = nk;
-        return;
-    }
-    for (int i = threadIdx.x; i < P; i += blockDim.x) {
-        uint64_t k = ~0ull;
-        if (i < cnt) {
-            const float p = trl_softmax2_p1(logits[16 * i], logits[16 * i + 1]);
-            S.aux[i] = p;
-            // np.argsort ascending then take-from-the-end: descending score, ties -> higher index first
-            if (p > thr) { k = (((uint64_t)(~f2ord(p))) << 32) | (uint32_t)(~(uint32_t)i); atomicAdd(&S.scal[4], 1); }
-        }
-        S.key[i] = k; S.id[i] = i;
-    }
-    __syncthreads();
-    const int m = S.scal[4];
-    if (m == 0) { if (threadIdx.x == 0) n3[f] = 0; return; }
-    block_bitonic(S.key, S.id, P);
-    for (int t = threadIdx.x; t < m; t += blockDim.x) {
-        const int i = (int)S.id[t];
-        const float4 bb = stage3_box(fb + 5 * i, logits + 16 * i + 2);
-        S.box[t] = bb;
-        S.area[t] = (bb.z - bb.x + 1.f) * (bb.w - bb.y + 1.f);
-    }
-    __syncthreads();
-    const int nk = block_nms<true>(S.box, S.area, m, 0.7f, S.sup, S.keep, S.scal);
-    for (int r = threadIdx.x; r < nk; r += blockDim.x) {
-        const int t = S.keep[r], i = (int)S.id[t];
-        const float4 bb = S.box[t];
+    auto prob = [&](int i) { return trl_softmax2_p1(logits[16 * i], logits[16 * i + 1]); };
+    // np.argsort ascending then take-from-the-end: descending score, ties -> higher index first
+    const Kept K = sort_and_suppress<true, true>(S, lds_cap, cnt, 0.7f, sp, nullptr, 0, 0,
+        [&](int i, uint32_t&) { const float p = prob(i); return p > thr ? sort_key(p, ~(uint32_t)i) : NO_KEY; },
+        [&](uint32_t i) { return stage3_box(fb + 5 * i, logits + 16 * i + 2); });
+    for (int r = threadIdx.x; r < K.n; r += blockDim.x) {
+        const int i = (int)K.id(r);
+        const float4 bb = K.box(r);
         float* o = s3_box + ((size_t)f * capF + r) * 5;
-        o[0] = bb.x; o[1] = bb.y; o[2] = bb.z; o[3] = bb.w; o[4] = S.aux[i];
+        o[0] = bb.x; o[1] = bb.y; o[2] = bb.z; o[3] = bb.w; o[4] = prob(i);
         stage3_points(fb + 5 * i, logits + 16 * i + 6, s3_pts + ((size_t)f * capF + r) * 10);
     }
-    if (threadIdx.x == 0) n3[f] = nk;
+    if (threadIdx.x == 0) n3[f] = K.n;
 }
 
 // MTCNN.detect ordering + model.py:49-54.  order 0: select_largest=True (area order); order 1: select_largest=False, the rows in
@@ -912,121 +774,6 @@ __global__ __launch_bounds__(64) void k_select(int capF, int max_faces, int W, i
     }
 }
 
-// model.py:55-58: frame[y0:y1, x0:x1] -> cv2.resize(.., (80,80)) INTER_LINEAR (u8 fixed point) -> /255
-__device__ __forceinline__ int sat_short_round(float v) {
-    int r = (int)__builtin_rintf(v);
-    return r < -32768 ? -32768 : (r > 32767 ? 32767 : r);
-}
-__global__ __launch_bounds__(256) void k_crop_resize80(const uint8_t* __restrict__ frames, int H, int W, const int32_t* __restrict__ rect,
-                                                       const uint8_t* __restrict__ valid, float* __restrict__ out) {
-    constexpr int O = 80;
-    __shared__ int xofs[O], xofs1[O], a0[O], a1[O], ys0[O], ys1[O], b0[O], b1[O];
-    const int f = blockIdx.x;
-    float* o = out + (size_t)f * O * O * 3;
-    if (!valid[f]) {
-        for (int p = threadIdx.x; p < O * O * 3; p += blockDim.x) o[p] = 0.f;
-        return;
-    }
-    const int x0 = rect[4 * f], y0 = rect[4 * f + 1], sw = rect[4 * f + 2] - x0, sh = rect[4 * f + 3] - y0;
-    const double scale_x = 1. / ((double)O / sw), scale_y = 1. / ((double)O / sh);
-    if (threadIdx.x < O) {
-        const int d = threadIdx.x;
-        float fx = (float)((d + 0.5) * scale_x - 0.5);
-        int sx = (int)floorf(fx);
-        fx -= sx;
-        if (sx < 0) { fx = 0; sx = 0; }
-        if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-        xofs[d] = sx; xofs1[d] = sx + 1 > sw - 1 ? sw - 1 : sx + 1;
-        a0[d] = sat_short_round((1.f - fx) * 2048.f); a1[d] = sat_short_round(fx * 2048.f);
-    } else if (threadIdx.x < 2 * O) {
-        const int d = threadIdx.x - O;
-        float fy = (float)((d + 0.5) * scale_y - 0.5);
-        int sy = (int)floorf(fy);
-        fy -= sy;
-        b0[d] = sat_short_round((1.f - fy) * 2048.f); b1[d] = sat_short_round(fy * 2048.f);
-        ys0[d] = sy < 0 ? 0 : (sy > sh - 1 ? sh - 1 : sy);
-        ys1[d] = sy + 1 < 0 ? 0 : (sy + 1 > sh - 1 ? sh - 1 : sy + 1);
-    }
-    __syncthreads();
-    const uint8_t* fp = frames + ((size_t)f * H + y0) * W * 3 + (size_t)x0 * 3;
-    for (int p = threadIdx.x; p < O * O * 3; p += blockDim.x) {
-        const int c = p % 3, dx = (p / 3) % O, dy = p / (3 * O);
-        const uint8_t* S0 = fp + (size_t)ys0[dy] * W * 3;
-        const uint8_t* S1 = fp + (size_t)ys1[dy] * W * 3;
-        const int r0 = S0[xofs[dx] * 3 + c] * a0[dx] + S0[xofs1[dx] * 3 + c] * a1[dx];
-        const int r1 = S1[xofs[dx] * 3 + c] * a0[dx] + S1[xofs1[dx] * 3 + c] * a1[dx];
-        int v = (((b0[dy] * (r0 >> 4)) >> 16) + ((b1[dy] * (r1 >> 4)) >> 16) + 2) >> 2;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        o[p] = (float)v / 255.0f;   // to_tensor
-    }
-}
-
-// SURVEY 8(f)-4 native embedding mode: facenet-pytorch extract_face() for tensor input = crop -> imresample (area)
-// to SxS -> .byte() (truncation) -> fixed_image_standardization (x-127.5)/128, optionally BGR -> RGB.
-__global__ __launch_bounds__(256) void k_crop_area_std(const uint8_t* __restrict__ frames, int H, int W, const int32_t* __restrict__ rect,
-                                                       const uint8_t* __restrict__ valid, int S, int rgb, float* __restrict__ out) {
-    const int f = blockIdx.y;
-    float* o = out + (size_t)f * S * S * 3;
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= S * S) return;
-    if (!valid[f]) { o[3 * p] = 0.f; o[3 * p + 1] = 0.f; o[3 * p + 2] = 0.f; return; }
-    const int x0 = rect[4 * f], y0 = rect[4 * f + 1], iw = rect[4 * f + 2] - x0, ih = rect[4 * f + 3] - y0;
-    const int oy = p / S, ox = p - oy * S;
-    float b[3];
-    trl_area_pixel(frames + (size_t)f * H * W * 3, W, x0, y0, iw, ih, S, ox, oy, b);
-    o[3 * p + (rgb ? 2 : 0)] = (b[0] - 127.5f) / 128.0f;
-    o[3 * p + 1] = (b[1] - 127.5f) / 128.0f;
-    o[3 * p + (rgb ? 0 : 2)] = (b[2] - 127.5f) / 128.0f;
-}
-
-// SURVEY 8(f)-4 "landmark-aligned" embedding mode (trl_config.embed_mode 3; this project's own definition, restated in
-// oracle/trl_oracle.c orc_crop_aligned): least-squares similarity from the scaled 112x112 five-point template to the face's
-// O-Net landmarks, estimated as the inverse map (double, fixed operation order), bilinear sample of the u8 frame with
-// replicated borders (float), (v-127.5)/128, optional BGR -> RGB.  One thread per output pixel; every thread of a face
-// recomputes the six transform parameters (60 flops) rather than paying a second launch.
-__constant__ double TPL_X[5] = {54.706571428571436, 105.04542857142857, 80.036, 59.35614285714286, 101.04271428571428};
-__constant__ double TPL_Y[5] = {73.85185714285714, 73.57342857142856, 102.48085714285713, 131.9507142857143, 131.72014285714286};
-__global__ __launch_bounds__(256) void k_crop_aligned(const uint8_t* __restrict__ frames, int H, int W, const float* __restrict__ pts0,
-                                                      const uint8_t* __restrict__ valid, int S, int rgb, float* __restrict__ out) {
-    const int f = blockIdx.y;
-    float* o = out + (size_t)f * S * S * 3;
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= S * S) return;
-    if (!valid[f]) { o[3 * p] = 0.f; o[3 * p + 1] = 0.f; o[3 * p + 2] = 0.f; return; }
-    const float* pts = pts0 + 10 * f;
-    double tx = 0., ty = 0., px = 0., py = 0.;
-#pragma unroll
-    for (int j = 0; j < 5; j++) { tx += TPL_X[j]; ty += TPL_Y[j]; px += (double)pts[j]; py += (double)pts[5 + j]; }
-    tx = tx / 5.; ty = ty / 5.; px = px / 5.; py = py / 5.;
-    double sdd = 0., sde = 0., scr = 0.;
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-        const double dx = TPL_X[j] - tx, dy = TPL_Y[j] - ty, ex = (double)pts[j] - px, ey = (double)pts[5 + j] - py;
-        sdd = sdd + (dx * dx + dy * dy);
-        sde = sde + (dx * ex + dy * ey);
-        scr = scr + (dx * ey - dy * ex);
-    }
-    const double a = sde / sdd, b = scr / sdd;
-    const int v = p / S, u = p - v * S;
-    const double du = (double)u - tx, dv = (double)v - ty;
-    const double x = (a * du - b * dv) + px, y = (b * du + a * dv) + py;
-    const double xf = floor(x), yf = floor(y);
-    const float fx = (float)(x - xf), fy = (float)(y - yf);
-    const double xc = (xf >= -1.) ? (xf > (double)W ? (double)W : xf) : -1., yc = (yf >= -1.) ? (yf > (double)H ? (double)H : yf) : -1.;   // NaN -> -1
-    int x0 = (int)xc, y0 = (int)yc, x1 = x0 + 1, y1 = y0 + 1;
-    x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0); x1 = x1 < 0 ? 0 : (x1 > W - 1 ? W - 1 : x1);
-    y0 = y0 < 0 ? 0 : (y0 > H - 1 ? H - 1 : y0); y1 = y1 < 0 ? 0 : (y1 > H - 1 ? H - 1 : y1);
-    const uint8_t* fp = frames + (size_t)f * H * W * 3;
-    const uint8_t *r0 = fp + (size_t)y0 * W * 3, *r1 = fp + (size_t)y1 * W * 3;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float p00 = (float)r0[x0 * 3 + c], p01 = (float)r0[x1 * 3 + c], p10 = (float)r1[x0 * 3 + c], p11 = (float)r1[x1 * 3 + c];
-        const float top = p00 + fx * (p01 - p00), bot = p10 + fx * (p11 - p10);
-        const float val = top + fy * (bot - top);
-        o[3 * p + (rgb ? 2 - c : c)] = (val - 127.5f) / 128.0f;
-    }
-}
-
 template <typename K>
 int set_dyn_smem(K kernel, size_t bytes) {
     TRL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -1069,29 +816,6 @@ int trl_launch_heads_to_maps(const float* d_heads, int cells, float* d_prob, flo
     TRL_LAUNCH_CHECK();
     return TRL_OK;
 }
-int trl_launch_crop_area_std(const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid, int S,
-                             bool rgb, float* d_faces, hipStream_t s) {
-    if (n <= 0) return TRL_OK;
-    k_crop_area_std<<<dim3((S * S + 255) / 256, n), 256, 0, s>>>(d_frames, H, W, d_rect, d_valid, S, rgb ? 1 : 0, d_faces);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
-}
-int trl_launch_crop_aligned(const uint8_t* d_frames, int n, int H, int W, const float* d_pts0, const uint8_t* d_valid, int S, bool rgb,
-                            float* d_faces, hipStream_t s) {
-    if (n <= 0) return TRL_OK;
-    k_crop_aligned<<<dim3((S * S + 255) / 256, n), 256, 0, s>>>(d_frames, H, W, d_pts0, d_valid, S, rgb ? 1 : 0, d_faces);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
-}
-int trl_launch_crop_resize80(const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid,
-                             float* d_faces, hipStream_t s) {
-    if (n <= 0) return TRL_OK;
-    k_crop_resize80<<<n, 256, 0, s>>>(d_frames, H, W, d_rect, d_valid, d_faces);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
-}
-
-
 
 // Record slots per level and rows per frame of this call: the configured start values, raised to what recent calls needed
 // (trl_cascade_check), never beyond what the geometry can produce (a level has oh x ow cells; a frame's stage-1 list is a subset
@@ -1121,10 +845,10 @@ static void plan_lists(trl_ctx* c, int L) {
     if (wantF < 4) wantF = 4;
     B.capF = (int)((wantF + 3) & ~3ll);
 }
-static size_t spill_need(long long cnt, int W, int H) {   // workspace of one spilled list of cnt entries (k_nms_level .. k_stage3_post)
+static size_t spill_need(long long cnt, int W, int H) {   // upper bound of the workspace of one spilled list of cnt entries, whichever kernel spills it
     long long P = 2;
     while (P < cnt) P <<= 1;
-    return (size_t)(P * 12 + cnt * 28 + ((long long)(W >> 5) + 1) * ((H >> 5) + 1) * 4 + 256);
+    return SpillWs::bytes((size_t)P, (size_t)cnt, true, true, W, H) + 256;
 }
 
 // spill workspace of a call: lists that can outgrow the LDS tier get theirs up front (bounded; a pool that still runs out is grown

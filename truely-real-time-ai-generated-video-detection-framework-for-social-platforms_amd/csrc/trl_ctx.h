@@ -37,12 +37,16 @@ struct CascadeBufs {   // device pointers into the arena, valid until the next c
     float* s3_pts = nullptr;                           // [n][capF][10]
     int32_t* off2 = nullptr; int32_t* off3 = nullptr; // [n+1] exclusive scans of n1 / n2
     int32_t* cbox = nullptr;     // [n*capF][8]: candidate t of the current stage = {frame, y0, x0, ih, iw, 0, 0, 0} (pad()'s crop window)
-    int32_t* flags = nullptr;        // [TRL_NFLAGS]: see trl_cascade.hip
+    int32_t* flags = nullptr;        // [TRL_NFLAGS]: the FLG_* words below
     size_t arena_mark = 0;           // arena offset behind the cascade's own blocks (where a resumed attempt re-allocates the API outputs)
     char* spill = nullptr;           // global-memory workspace of the NMS spill tier (lists longer than the LDS tier)
     size_t spill_cap = 0;
 };
 enum { TRL_NFLAGS = 64 };            // int32 words of CascadeBufs::flags (copied to pinned host memory behind every call)
+// The words: a capacity of the attempt was too small (level record list, per-frame list, R-/O-Net batch, spill pool) and what the
+// attempt measured (the R-/O-Net candidate totals, the largest per-frame and per-level counts, the spill bytes asked for)
+enum { FLG_LEVEL = 0, FLG_FRAME = 1, FLG_T2 = 2, FLG_T3 = 3, FLG_T2N = 4, FLG_T3N = 5, FLG_FRAME_MAX = 6, FLG_SPILL = 7,
+       FLG_SPILL_CUR = 8 /* u64 */, FLG_SPILL_LISTS = 10, FLG_LEVEL_MAX = 16 /* [32] */ };
 
 struct trl_ctx {
     trl_config cfg;
@@ -160,15 +164,16 @@ int trl_cascade_check(trl_ctx* c, int n, int* retry);   // after the call's stre
 int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* h_caps, int L, const int32_t* h_counts, const void* h_rows,
                       const float* h_logits, float* h_pts, float* d_boxes, float* d_probs, float* d_points, int32_t* d_counts, float* d_box0,
                       float* d_prob0, int32_t* d_rect, uint8_t* d_valid, hipStream_t s);   // trl_debug_lists
+int trl_launch_area_level(const uint8_t* d_frames, int nf, int H, int W, int h, int w, float* d_level, hipStream_t s);
+int trl_launch_heads_to_maps(const float* d_heads, int cells, float* d_prob, float* d_reg, hipStream_t s);
+int trl_compute_levels(trl_ctx* c, int H, int W);
+// the crops between the cascade and the embedder (trl_crops.hip)
 int trl_launch_crop_resize80(const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid,
                              float* d_faces, hipStream_t s);
 int trl_launch_crop_aligned(const uint8_t* d_frames, int n, int H, int W, const float* d_pts0, const uint8_t* d_valid, int S, bool rgb,
                             float* d_faces, hipStream_t s);
 int trl_launch_crop_area_std(const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid, int S,
                              bool rgb, float* d_faces, hipStream_t s);
-int trl_launch_area_level(const uint8_t* d_frames, int nf, int H, int W, int h, int w, float* d_level, hipStream_t s);
-int trl_launch_heads_to_maps(const float* d_heads, int cells, float* d_prob, float* d_reg, hipStream_t s);
-int trl_compute_levels(trl_ctx* c, int H, int W);
 // stage 1 on the generic layer path, one level g of nf frames: scratch bytes per frame, and the step itself -- the level
 // materialised in c->scratch (reset first), PNet's layers over it; *d_heads = [nf][oh][ow][6] behind it in c->scratch
 size_t trl_pnet_generic_level_bytes(const LevelGeom& g);

@@ -7,7 +7,7 @@
 //   k_extract_plan : one workgroup per face: the crop box (margin in f64 from the f32 box, clamp, int()), the row status and the
 //                    separable coefficient tables of the resampler (Pillow BILINEAR, OpenCV INTER_AREA) into a workspace
 //   k_extract      : one workgroup per (face, band of output rows): torch = imresample (area) per pixel through trl_area_pixel
-//                    (the code k_crop_area_std runs), cv2 integer scales = block means, else the two separable passes with the
+//                    (the code trl_crops.hip's k_crop_area_std runs), cv2 integer scales = block means, else the two separable passes with the
 //                    horizontal pass staged in LDS, chunk by chunk of the vertical taps
 // The double-precision coefficient arithmetic relies on -ffp-contract=off (csrc/Makefile), like the rest of the library.
 #include "trl_ctx.h"

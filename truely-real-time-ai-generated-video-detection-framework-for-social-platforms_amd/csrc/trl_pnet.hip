@@ -835,7 +835,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
                                 c.cell = oy * g.ow + ox;
                                 a.lvl_rec[(size_t)f * a.rec_stride + a.lv[l].rec0 + sl] = c;
                             } else {
-                                a.flags[0] = 1;
+                                a.flags[FLG_LEVEL] = 1;
                             }
                         }
                     }

@@ -84,7 +84,13 @@ int  trl_destroy(trl_ctx* ctx);
 int  trl_load_weights(trl_ctx* ctx, const void* host_blob, size_t nbytes);
 
 /* server/model.py:47  `boxes, probs = mtcnn.detect(frame)` for a batch of n frames.
- *   d_frames : u8  [n][H][W][3]  BGR as cv2.VideoCapture.read() yields (model.py:43)
+ *   d_frames : u8  [n][H][W][3]  BGR as cv2.VideoCapture.read() yields (model.py:43).  The ADDRESS must be a multiple of 4,
+ *              here and in every call that takes a frame batch for the cascade or one of its stages (a device allocation's
+ *              start always is; a view `buf[k:]`, or `frames[1:]` of a batch whose frames are not a multiple of 4 bytes, need
+ *              not be): the pyramid and front kernels turn d_frames into dword and 16-byte loads.  Any other address:
+ *              TRL_ERR_INVALID, nothing launched.  The frame size itself is free (frames inside a batch sit at any byte
+ *              phase).  A load may cover the whole dword that holds the batch's last byte, i.e. up to 3 bytes past it, which
+ *              an aligned device allocation always grants; those bytes never reach a result.
  *   d_boxes  : f32 [n][max_faces][4]   x1,y1,x2,y2, largest area first (select_largest=True)
  *   d_probs  : f32 [n][max_faces]
  *   d_counts : i32 [n]                 number of faces (0 <=> detect() returned None) */
@@ -290,6 +296,15 @@ int  trl_debug_front_net(trl_ctx* ctx, const uint8_t* d_frame, int H, int W, con
  * "onet_chunk".  d_out: [capacity][6] (net = 24) or [capacity][16] (net = 48), device; rows past nb are not defined. (ABI v7) */
 int  trl_debug_stage_net(trl_ctx* ctx, const uint8_t* d_frames, int nf, int H, int W, const float* h_recs, int nb, int net,
                          int capacity, float* d_out, void* stream);
+/* k_mtcnn_front (crop, area resample, conv1, PReLU, pool) ALONE, on windows the caller gives directly: h_win = nb host rows of
+ * int32 {frame, y0, x0, ih, iw}, the record the cascade's k_build_map writes after pad() -- rows y0 .. y0+ih-1 and columns
+ * x0 .. x0+iw-1 of that frame.  Each row is checked (0 <= frame < nf, ih, iw >= 1, the window inside the frame: TRL_ERR_INVALID
+ * otherwise, nothing launched).  The device total is nb; the launch covers `capacity` slots (one chunk at t0 = 0, as the first
+ * chunk of trl_debug_stage_net), and record slots past nb hold that hook's poison.  d_pool: [capacity][11][11][28] (net = 24) or
+ * [capacity][23][23][32] (net = 48), device, written directly by the kernel: maps past nb are not touched.  No tail runs.
+ * (ABI v7, additive) */
+int  trl_debug_front(trl_ctx* ctx, const uint8_t* d_frames, int nf, int H, int W, const int32_t* h_win, int nb, int net,
+                     int capacity, float* d_pool, void* stream);
 /* The cascade's list kernels on lists the caller builds, launched by the cascade's own host code (LDS tiers of
  * trl_debug_nms_tiers, workgroup sizes, spill pool, overflow flags: trl_debug_list_stats).  h_caps: n_levels level capacities,
  * then the per-frame capacity (multiples of 4).  kind 1: h_rows = 40-byte candidate records {x1, y1, x2, y2, score, r0..r3, cell}

@@ -104,6 +104,14 @@ class Oracle:
         self.lib.orc_onet(C.c_void_p(self.ctx), _p(crops), n, _p(prob), _p(reg), _p(pts))
         return prob, reg, pts
 
+    def front(self, crops, net):
+        """conv1 + PReLU + MaxPool(3, 2, ceil) of R-Net (net=24) / O-Net (net=48) on prepared crops [n][net][net][3]."""
+        crops = np.ascontiguousarray(crops, np.float32); n = crops.shape[0]
+        assert net in (24, 48) and crops.shape[1:] == (net, net, 3)
+        out = np.empty((n, 11, 11, 28) if net == 24 else (n, 23, 23, 32), np.float32)
+        self.lib.orc_front(C.c_void_p(self.ctx), _p(crops), n, int(net), _p(out))
+        return out
+
     def nms_iou(self, boxes, scores, thr):
         boxes = np.ascontiguousarray(boxes, np.float32); scores = np.ascontiguousarray(scores, np.float32)
         keep = np.empty((max(1, len(scores)),), np.int32)

@@ -330,6 +330,17 @@ void orc_onet(const orc_ctx* c, const float* crops, int n, float* prob, float* r
     tfree(&cls); tfree(&box); tfree(&lmk);
 }
 
+/* The front of R-Net (net = 24) / O-Net (net = 48) alone: conv1 + PReLU + MaxPool(3, 2, ceil) of prepared net x net x 3 crops,
+ * through the functions orc_rnet / orc_onet call.  out: [n][11][11][28] or [n][23][23][32]. */
+void orc_front(const orc_ctx* c, const float* crops, int n, int net, float* out) {
+    if (n <= 0 || (net != 24 && net != 48)) return;
+    T x = {n, net, net, 3, (float*)crops};
+    T a = conv_prelu(c, net == 24 ? "rnet" : "onet", "conv1", "prelu1", &x, 3);
+    T p1 = maxpool(&a, 3, 2, 1); tfree(&a);
+    memcpy(out, p1.d, (size_t)n * p1.h * p1.w * p1.c * sizeof(float));
+    tfree(&p1);
+}
+
 /* ------------------------------------------------------------------------- */
 /* detect_face helpers (RECALLED: facenet_pytorch/models/utils/detect_face.py) */
 /* ------------------------------------------------------------------------- */

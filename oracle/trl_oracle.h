@@ -76,6 +76,9 @@ void  orc_area_resample_norm(const uint8_t* img, int H, int W, int y0, int y1, i
 void  orc_pnet_level(const orc_ctx*, const float* in, int h, int w, float* prob, float* reg, int* oh, int* ow);
 void  orc_rnet(const orc_ctx*, const float* crops /*[n][24][24][3]*/, int n, float* prob, float* reg);
 void  orc_onet(const orc_ctx*, const float* crops /*[n][48][48][3]*/, int n, float* prob, float* reg, float* pts);
+/* conv1 + PReLU + MaxPool(3, 2, ceil) of R-Net (net = 24) / O-Net (net = 48) alone, the same code the two calls above run:
+ * crops [n][net][net][3] -> out [n][11][11][28] / [n][23][23][32] (what the GPU's front kernel writes) */
+void  orc_front(const orc_ctx*, const float* crops, int n, int net, float* out);
 /* greedy IoU NMS as torchvision.ops.nms: returns #kept, keep[] = indices in descending-score order */
 int   orc_nms_iou(const float* boxes /*[n][4]*/, const float* scores, int n, float thr, int* keep);
 /* facenet_pytorch nms_numpy(..., 'Min'), +1 areas; ties resolved as a stable ascending argsort */

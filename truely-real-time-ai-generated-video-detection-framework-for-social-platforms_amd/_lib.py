@@ -68,6 +68,7 @@ _SIGNATURES = {
     "trl_debug_onet": (C.c_int, [_vp, _vp, _i, _vp, _vp]),
     "trl_debug_front_net": (C.c_int, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "trl_debug_stage_net": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "trl_debug_front": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
     "trl_debug_mtcnn_plan": (C.c_int, [_vp, _vp, _i, C.POINTER(_i)]),
     "trl_debug_lists": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "trl_debug_crop_resize": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -342,6 +342,8 @@ static int check_call(trl_ctx* c, const void* frames, int n, int H, int W) {
         trl_set_error("bad frame batch n=%d H=%d W=%d (1..65535 frames of 12..16383 px per side)", n, H, W);
         return TRL_ERR_INVALID;
     }
+    // the pyramid and front kernels turn the frame pointer into dword and 16-byte loads (include/truely_hip.h)
+    if (((uintptr_t)frames & 3) != 0) { trl_set_error("frame buffer must be 4-byte aligned"); return TRL_ERR_INVALID; }
     return TRL_OK;
 }
 
@@ -754,6 +756,24 @@ int trl_debug_rnet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* 
     TRL_CHECK(trl_ensure(c, c->scratch, (size_t)n * 100 * 1024 + (4u << 20)));
     return trl_run_rnet(c, d_crops, n, d_out, (hipStream_t)stream);
 }
+// k_build_map's records on the device for a front launch outside the cascade: hb holds `slots` records of 8 words (the live ones
+// first); c->cb then describes the batch and the record list, *total is the device-side count nb.
+static int upload_records(trl_ctx* c, int nf, int H, int W, const std::vector<int32_t>& hb, int slots, int nb, int32_t** total, hipStream_t s) {
+    Arena& A = c->arena;
+    TRL_CHECK(trl_ensure(c, A, (size_t)slots * 32 + (1u << 20)));
+    A.reset();
+    CascadeBufs& B = c->cb;
+    B = CascadeBufs();
+    B.n = nf; B.H = H; B.W = W;
+    B.cbox = (int32_t*)A.alloc((size_t)slots * 32 + 32);
+    *total = (int32_t*)A.alloc(64);
+    TRL_HIP(hipMemcpyAsync(B.cbox, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s));
+    TRL_HIP(hipMemcpyAsync(*total, &nb, 4, hipMemcpyHostToDevice, s));
+    TRL_HIP(hipStreamSynchronize(s));                      // the host data may go out of scope
+    return TRL_OK;
+}
+static const int32_t kRecordPoison = (int32_t)0xA5A5A5A5;  // frame / window words no live record has
+
 // The production stage-2 / stage-3 loop (trl_stage_net, as the cascade runs it) over a launch capacity the caller chooses.  h_rows:
 // nb host rows of `cols` floats -- (frame, x1, y1, x2, y2), or (x1, y1, x2, y2) of frame 0 when cols = 4 -- turned into
 // k_build_map's records by pad() (detect_face.py: trunc, x = max(x1, 1), ex = min(x2, W), crop [y-1:ey, x-1:ex]); the device
@@ -765,7 +785,7 @@ static int stage_net_on_rows(trl_ctx* c, const uint8_t* d_frames, int nf, int H,
     hipStream_t s = (hipStream_t)stream;
     TRL_HIP(hipSetDevice(c->cfg.device));
     const int slots = nb > capacity ? nb : capacity;
-    std::vector<int32_t> hb((size_t)slots * 8, (int32_t)0xA5A5A5A5);   // poison: frame / window words no live record has
+    std::vector<int32_t> hb((size_t)slots * 8, kRecordPoison);
     for (int i = 0; i < nb; i++) {
         const float* b = h_rows + (size_t)cols * i + cols - 4;
         const int f = cols == 5 ? (int)b[-1] : 0;
@@ -776,17 +796,8 @@ static int stage_net_on_rows(trl_ctx* c, const uint8_t* d_frames, int nf, int H,
         int32_t* r = &hb[8 * (size_t)i];
         r[0] = f; r[1] = y - 1; r[2] = x - 1; r[3] = ey - (y - 1); r[4] = ex - (x - 1); r[5] = r[6] = r[7] = 0;
     }
-    Arena& A = c->arena;
-    TRL_CHECK(trl_ensure(c, A, (size_t)slots * 32 + (1u << 20)));
-    A.reset();
-    CascadeBufs& B = c->cb;
-    B = CascadeBufs();
-    B.n = nf; B.H = H; B.W = W;
-    B.cbox = (int32_t*)A.alloc((size_t)slots * 32 + 32);
-    int32_t* total = (int32_t*)A.alloc(64);
-    TRL_HIP(hipMemcpyAsync(B.cbox, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s));
-    TRL_HIP(hipMemcpyAsync(total, &nb, 4, hipMemcpyHostToDevice, s));
-    TRL_HIP(hipStreamSynchronize(s));                      // the host vector goes out of scope
+    int32_t* total = nullptr;
+    TRL_CHECK(upload_records(c, nf, H, W, hb, slots, nb, &total, s));
     // workspace as the cascade sizes it (trl_cascade_detect): per candidate of a chunk 40 KB (R-Net) / 240 KB (O-Net)
     const int CH = net == 24 ? c->rnet_chunk : c->onet_chunk, ch = capacity < CH ? capacity : CH;
     c->scratch.reset();
@@ -797,7 +808,7 @@ static int stage_net_on_rows(trl_ctx* c, const uint8_t* d_frames, int nf, int H,
     c->mt_plan_arm = false;
     TRL_CHECK(st);
     TRL_HIP(hipStreamSynchronize(s));
-    B = CascadeBufs();                                     // no cascade state to inspect after this hook
+    c->cb = CascadeBufs();                                 // no cascade state to inspect after this hook
     return TRL_OK;
 }
 
@@ -820,6 +831,43 @@ int trl_debug_stage_net(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int 
         return TRL_ERR_INVALID;
     }
     return stage_net_on_rows(c, d_frames, nf, H, W, h_recs, 5, nb, net, capacity, d_out, stream);
+}
+
+// test hook: k_mtcnn_front alone.  h_win: nb host rows {frame, y0, x0, ih, iw}, k_build_map's record given directly (no pad()); the
+// kernel checks nothing, so every row is checked here.  Record slots nb .. capacity-1 hold the poison of stage_net_on_rows, the
+// device total is nb, and the launch is trl_stage_net's: one chunk at t0 = 0 over `capacity` slots, writing the pooled maps
+// [capacity][11][11][28] (net = 24) / [capacity][23][23][32] (net = 48) straight into d_pool.  No tail runs.
+int trl_debug_front(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const int32_t* h_win, int nb, int net, int capacity,
+                    float* d_pool, void* stream) {
+    TRL_CHECK(check_call(c, d_frames, nf, H, W));
+    if ((nb > 0 && !h_win) || (capacity > 0 && !d_pool) || nb < 0 || nb > (1 << 20) || capacity < 0 || capacity > (1 << 20) ||
+        (net != 24 && net != 48)) {
+        trl_set_error("bad argument");
+        return TRL_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    TRL_HIP(hipSetDevice(c->cfg.device));
+    const int slots = nb > capacity ? nb : capacity;
+    std::vector<int32_t> hb((size_t)slots * 8, kRecordPoison);
+    for (int i = 0; i < nb; i++) {
+        const int32_t* r = h_win + 5 * (size_t)i;
+        const long long f = r[0], y0 = r[1], x0 = r[2], ih = r[3], iw = r[4];
+        if (f < 0 || f >= nf || ih < 1 || iw < 1 || y0 < 0 || x0 < 0 || y0 + ih > H || x0 + iw > W) {
+            trl_set_error("window %d: frame %lld of %d, rows %lld + %lld of %d, columns %lld + %lld of %d", i, f, nf, y0, ih, H, x0, iw, W);
+            return TRL_ERR_INVALID;
+        }
+        int32_t* q = &hb[8 * (size_t)i];
+        for (int k = 0; k < 5; k++) q[k] = r[k];
+        q[5] = q[6] = q[7] = 0;
+    }
+    int32_t* total = nullptr;
+    TRL_CHECK(upload_records(c, nf, H, W, hb, slots, nb, &total, s));
+    const int st = net == 24 ? trl_launch_rnet_front(c, d_frames, H, W, total, 0, capacity, d_pool, s)
+                             : trl_launch_onet_front(c, d_frames, H, W, total, 0, capacity, d_pool, s);
+    TRL_CHECK(st);
+    TRL_HIP(hipStreamSynchronize(s));
+    c->cb = CascadeBufs();
+    return TRL_OK;
 }
 
 // test hook: the cascade's list kernels on caller-built lists (trl_cascade_lists has the layout of every kind)

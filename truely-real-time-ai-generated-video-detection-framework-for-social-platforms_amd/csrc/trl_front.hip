@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256, 1) void k_mtcnn_front(const uint8_t* __restric
             // bound by dependent round trips, not by bytes.  A chunk is 63 payload dwords: lane i re-aligns dword i
             // with dword i+1 taken from lane i+1 by a DPP wave shift (no second load); lane 63 only feeds lane 62.
             // Addressing is a scalar row base plus a clamped 32-bit lane offset, the re-alignment shift is a scalar per
-            // row, bytes accumulate in packed 16-bit halves (<= 256 rows x 255 per flush).
+            // row, bytes accumulate in one 32-bit sum per byte column and bin (v_dot4 with a one-hot weight), flushed once per segment.
             static_assert((S / 4) % 2 == 0, "rows per wave must pair up");
             constexpr int CAP2 = (COLCAP / 2) & ~3;
             unsigned* colA = colbuf;
@@ -180,7 +180,30 @@ __global__ __launch_bounds__(256, 1) void k_mtcnn_front(const uint8_t* __restric
             const int kwA0 = (iw + S - 1) / S;
             const float rkw0 = 1.0f / (float)kwA0, rkw1 = 1.0f / (float)(kwA0 + 1);
             const bool fastdiv = ih <= 94 * S && iw <= 94 * S;      // every bin <= 96 x 96: the verified domain of rdiv
-            for (int oyA = wave; oyA < S; oyA += 8) {
+            // A bin wider than half the strip (kw * 3 > CAP2 - 4: windows wider than ~7,400 px for S = 24, ~10,200 px for S = 48)
+            // cannot go through the column sums: such a window takes one bin per wave at a time, lanes along the bin's pixels,
+            // byte loads, the two IEEE divisions (it is far outside fastdiv's domain).  Rare and not tuned.
+            const bool wide_bin = (kwA0 + 1) * 3 > CAP2 - 4;
+            for (int p = wave; wide_bin && p < S * S; p += 4) {
+                const int oy = p / S, ox = p - oy * S;
+                const int ys = (oy * ih) / S, ye = ((oy + 1) * ih + S - 1) / S;
+                const int xs = (ox * iw) / S, xe = ((ox + 1) * iw + S - 1) / S;
+                unsigned a0 = 0, a1 = 0, a2 = 0;
+                for (int y = ys; y < ye; y++) {
+                    const uint8_t* row = frames + fbyte0 + ((long long)(y0 + y) * W + x0) * 3;
+                    for (int x = xs + lane; x < xe; x += 64) { a0 += row[3 * x]; a1 += row[3 * x + 1]; a2 += row[3 * x + 2]; }
+                }
+                for (int off = 32; off >= 1; off >>= 1) {
+                    a0 += __shfl_xor((int)a0, off, 64); a1 += __shfl_xor((int)a1, off, 64); a2 += __shfl_xor((int)a2, off, 64);
+                }
+                if (lane == 0) {
+                    const float fkh = (float)(ye - ys), fkw = (float)(xe - xs);
+                    in_s[3 * p + 0] = ((float)a0 / fkh / fkw - 127.5f) * 0.0078125f;
+                    in_s[3 * p + 1] = ((float)a1 / fkh / fkw - 127.5f) * 0.0078125f;
+                    in_s[3 * p + 2] = ((float)a2 / fkh / fkw - 127.5f) * 0.0078125f;
+                }
+            }
+            for (int oyA = wave; !wide_bin && oyA < S; oyA += 8) {
                 const int oyB = oyA + 4;
                 const int ysA = (oyA * ih) / S, yeA = ((oyA + 1) * ih + S - 1) / S, khA = yeA - ysA;
                 const int ysB = (oyB * ih) / S, yeB = ((oyB + 1) * ih + S - 1) / S, khB = yeB - ysB;

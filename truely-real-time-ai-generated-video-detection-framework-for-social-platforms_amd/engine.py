@@ -545,6 +545,24 @@ class Engine:
                                                 int(capacity), _ptr(out), self._stream()))
         return out
 
+    def front_pool(self, frames, win: np.ndarray, net: int, capacity: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Test hook (``trl_debug_front``): the front kernel's own output.  ``win`` rows are int32 (frame, y0, x0, ih, iw), the
+        crop window itself; the launch covers ``capacity`` slots (default len(win)).  Returns the pooled maps [capacity, 11, 11, 28]
+        (net=24) or [capacity, 23, 23, 32] (net=48); maps past len(win) keep what ``out`` held.  A device tensor is passed on as it
+        is; its address must be a multiple of 4, as for every call that takes frames."""
+        fr = self._frames(frames)
+        nf, H, W, _ = fr.shape
+        w = np.ascontiguousarray(win, np.int32).reshape(-1, 5)
+        cap = len(w) if capacity is None else int(capacity)
+        shape = (cap, 11, 11, 28) if net == 24 else (cap, 23, 23, 32)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
+        _lib.check(self.lib.trl_debug_front(self._h, _ptr(fr), nf, H, W, w.ctypes.data_as(C.c_void_p), len(w), int(net), cap, _ptr(out),
+                                            self._stream()))
+        return out
+
     def lists(self, kind: int, H: int, W: int, caps, counts, rows: np.ndarray, logits: np.ndarray | None = None) -> dict:
         """Test hook (``trl_debug_lists``): the cascade's list kernels on caller-built lists of frames H x W, launched as the
         cascade launches them.  ``caps`` = level capacities then the per-frame capacity.

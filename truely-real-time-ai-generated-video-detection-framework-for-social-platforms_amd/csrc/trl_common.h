@@ -222,10 +222,14 @@ __device__ __forceinline__ float trl_wave_dot512(const float* a, const float* b,
 __device__ __forceinline__ void trl_area_pixel(const uint8_t* fp, int W, int x0, int y0, int iw, int ih, int S, int ox, int oy, float v[3]) {
     const int ys = (int)(((long long)oy * ih) / S), ye = (int)((((long long)oy + 1) * ih + S - 1) / S);
     const int xs = (int)(((long long)ox * iw) / S), xe = (int)((((long long)ox + 1) * iw + S - 1) / S);
-    unsigned s0 = 0, s1 = 0, s2 = 0;
+    // 64-bit sums: a bin of more than 16 843 009 pixels (S = 1 on a 4105 x 4104 crop) passes 2^32.  One row of a bin (< 16384
+    // pixels) fits 32 bits, so the inner loop stays 32-bit; (float) of the sum is the same value for every sum below 2^32.
+    unsigned long long s0 = 0, s1 = 0, s2 = 0;
     for (int y = ys; y < ye; y++) {
         const uint8_t* q = fp + ((size_t)(y0 + y) * W + x0 + xs) * 3;
-        for (int x = xs; x < xe; x++, q += 3) { s0 += q[0]; s1 += q[1]; s2 += q[2]; }
+        unsigned r0 = 0, r1 = 0, r2 = 0;
+        for (int x = xs; x < xe; x++, q += 3) { r0 += q[0]; r1 += q[1]; r2 += q[2]; }
+        s0 += r0; s1 += r1; s2 += r2;
     }
     const float kh = (float)(ye - ys), kw = (float)(xe - xs);
     v[0] = (float)(unsigned char)((float)s0 / kh / kw);

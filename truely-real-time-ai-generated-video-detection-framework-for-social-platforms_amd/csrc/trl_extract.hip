@@ -8,7 +8,9 @@
 //                    separable coefficient tables of the resampler (Pillow BILINEAR, OpenCV INTER_AREA) into a workspace
 //   k_extract      : one workgroup per (face, band of output rows): torch = imresample (area) per pixel through trl_area_pixel
 //                    (the code trl_crops.hip's k_crop_area_std runs), cv2 integer scales = block means, else the two separable passes with the
-//                    horizontal pass staged in LDS, chunk by chunk of the vertical taps
+//                    horizontal pass staged in LDS, chunk by chunk of the vertical taps.  Pillow's Image.resize runs the vertical
+//                    pass first for a crop more than 100 times as tall as wide that it shrinks vertically (ih > 100 * iw and
+//                    S < ih; both passes round to 8 bits, so the order shows in the bytes): such a crop takes that order here
 // The double-precision coefficient arithmetic relies on -ffp-contract=off (csrc/Makefile), like the rest of the library.
 #include "trl_ctx.h"
 #include <float.h>
@@ -19,10 +21,11 @@ constexpr int XB = 256;                 // threads of an extraction workgroup
 constexpr int XBAND = 8;                // output rows per workgroup
 constexpr int XACC = 12;                // output values of one row per thread: 3 * 1024 / 256
 constexpr int XTMP = 16384;             // LDS words for horizontal-pass rows (64 KB)
-constexpr int HDR = 8;                  // plan header words: x0 y0 iw ih status cv_mode kx ky
+constexpr int HDR = 8;                  // plan header words: x0 y0 iw ih status mode kx ky (mode: CV_* for cv2, PIL_* for pil)
 
 enum { R_TORCH = 0, R_PIL = 1, R_CV2 = 2 };
 enum { CV_FAST = 0, CV_AREA = 1, CV_LINEAR = 2 };
+enum { PIL_HFIRST = 0, PIL_VFIRST = 1 };
 
 // ---- select_boxes --------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_pick_faces(int n, int max_faces, const float* __restrict__ boxes, const float* __restrict__ probs,
@@ -143,6 +146,8 @@ __global__ __launch_bounds__(256) void k_extract_plan(int n, int H, int W, const
             if (sx >= 1. && sy >= 1.) mode = (fabs(sx - kx) < DBL_EPSILON && fabs(sy - ky) < DBL_EPSILON) ? CV_FAST : CV_AREA;
             else mode = CV_LINEAR;
         }
+        // Image.resize (Pillow 12.2, Image.py): "if self.size[1] > self.size[0] * 100 and size[1] < self.size[1]" resizes vertically first
+        if (st == 1 && resample == R_PIL) mode = (ih > iw * 100 && S < ih) ? PIL_VFIRST : PIL_HFIRST;
         hd[0] = x0; hd[1] = y0; hd[2] = iw; hd[3] = ih; hd[4] = st; hd[5] = mode; hd[6] = kx; hd[7] = ky;
         if (status) status[r] = st;
     }
@@ -213,6 +218,34 @@ __global__ __launch_bounds__(XB) void k_extract(int H, int W, const uint8_t* __r
     // thread accumulates its output values of the row over those taps in tap order
     const int32_t *Xlo = P + HDR, *Xcnt = Xlo + S, *Xw = Xlo + 2 * S;
     const int32_t *Ylo = Xlo + (size_t)S * (2 + Kx), *Ycnt = Ylo + S, *Yw = Ylo + 2 * S;
+    if (resample == R_PIL && mode == PIL_VFIRST) {
+        // vertical pass first: ih > 100 * iw and ih <= 16383 leave iw <= 163 columns, so the vertically filtered row (3 * iw
+        // values, rounded and clipped to 8 bits) is one short LDS row and the vertical taps need no chunks
+        const int srclen = 3 * iw;
+        for (int oy = oy0; oy < oy1; oy++) {
+            const int ylo = Ylo[oy], ycnt = Ycnt[oy];
+            const int32_t* yw = Yw + (size_t)oy * Ky;
+            __syncthreads();                                  // the previous row's readers are done
+            for (int e = threadIdx.x; e < srclen; e += XB) {
+                const uint8_t* col = fp + ((size_t)(y0 + ylo) * W + x0) * 3 + e;
+                int a = 1 << 21;
+                for (int t = 0; t < ycnt; t++) a += yw[t] * (int)col[(size_t)t * W * 3];
+                a >>= 22;
+                tmp[e] = a < 0 ? 0 : (a > 255 ? 255 : a);
+            }
+            __syncthreads();
+            float* orow = o + (size_t)oy * rowlen;
+            for (int p = threadIdx.x; p < rowlen; p += XB) {
+                const int ox = p / 3, c = p - 3 * ox, xl = Xlo[ox], xc = Xcnt[ox];
+                const int32_t* xw = Xw + (size_t)ox * Kx;
+                int a = 1 << 21;
+                for (int t = 0; t < xc; t++) a += xw[t] * tmp[3 * (xl + t) + c];
+                a >>= 22;
+                orow[p] = post((float)(a < 0 ? 0 : (a > 255 ? 255 : a)), post_process);
+            }
+        }
+        return;
+    }
     const int T = XTMP / rowlen;
     const int kind = resample == R_PIL ? 0 : (mode == CV_AREA ? 1 : 2);
     for (int oy = oy0; oy < oy1; oy++) {

@@ -10,11 +10,12 @@
 // conv_bf16: whole-tap implicit GEMM (see conv_tap in trl_layers.hip): K chunks of BK channels of one filter tap,
 // scalar im2col cursor, A = [pixel][k] and B = [cout][k] staged k-contiguous in LDS so that an MFMA operand is one
 // ds_read_b128 (8 bf16); rows padded by 16 bytes: the 32 rows x 2 k-halves of an operand read hit distinct banks.
-#include "trl_ctx.h"
+// Row decode, tap cursor, bias seed and the accumulator-to-row map come from trl_conv.h; the finish is this file's own
+// (16-bit residual, lp_relu, one rounding per stored value).
+#include "trl_conv.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -69,13 +70,9 @@ __global__ __launch_bounds__(256) void conv_bf16(ConvArgs a) {
     for (int i = 0; i < APT; i++) {
         const int row = tid / KG + (256 / KG) * i;
         const int m = m0 + row;
-        const int mm = (m < a.M && row < BM) ? m : 0;
-        const int ohw = a.OH * a.OW;
-        const int nimg = mm / ohw;
-        const int rem = mm - nimg * ohw;
-        const int oy = rem / a.OW, ox = rem - oy * a.OW;
-        iy0[i] = oy * a.sh - a.ph; ix0[i] = ox * a.sw - a.pw;
-        aoff[i] = ((nimg * a.H + iy0[i]) * a.W + ix0[i]) * a.ldx + a.xoff + 8 * ag;
+        const ConvRow px = conv_row(a, m, m < a.M && row < BM);
+        iy0[i] = px.iy0; ix0[i] = px.ix0;
+        aoff[i] = px.off(a) + 8 * ag;
         ain[i] = row < BM;
     }
     const int bg = tid % KG;
@@ -84,25 +81,24 @@ __global__ __launch_bounds__(256) void conv_bf16(ConvArgs a) {
     for (int i = 0; i < BPT; i++) boff[i] = (n0 + tid / KG + (256 / KG) * i) * a.ldwt + 8 * bg;   // wt rows are padded to 64 couts
 
     u32x4 areg[APT], breg[BPT];
-    int ky = 0, kx = 0, c0 = 0, k0 = 0;
+    TapCursor cur;
     auto load_chunk = [&]() __attribute__((always_inline)) {
-        const int soff = (ky * a.W + kx) * a.ldx + c0;
+        const int soff = cur.soff(a);
 #pragma unroll
         for (int i = 0; i < APT; i++) {
             u32x4 v = {0u, 0u, 0u, 0u};
             bool ok = ain[i];
-            if (PAD) ok = ok && (unsigned)(iy0[i] + ky) < (unsigned)a.H && (unsigned)(ix0[i] + kx) < (unsigned)a.W;
+            if (PAD) ok &= cur.inside(a, iy0[i], ix0[i]);
             if (ok) v = *reinterpret_cast<const u32x4*>(xg + (aoff[i] + soff));
             areg[i] = v;
         }
 #pragma unroll
         for (int i = 0; i < BPT; i++) {
             u32x4 v = {0u, 0u, 0u, 0u};
-            if (BSLOTS % 256 == 0 || tid + 256 * i < BSLOTS) v = *reinterpret_cast<const u32x4*>(a.wt + (boff[i] + k0));
+            if (BSLOTS % 256 == 0 || tid + 256 * i < BSLOTS) v = *reinterpret_cast<const u32x4*>(a.wt + (boff[i] + cur.k0));
             breg[i] = v;
         }
-        k0 += BK; c0 += BK;
-        if (c0 >= a.Cin) { c0 = 0; if (++kx == a.KW) { kx = 0; ++ky; } }
+        cur.advance(a, BK);
     };
     auto store_chunk = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -120,8 +116,7 @@ __global__ __launch_bounds__(256) void conv_bf16(ConvArgs a) {
     f32x16 acc[TM][TN];
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
-        const int n = n0 + (wn * TN + tn) * 32 + r;
-        const float b = (a.bias != nullptr && n < a.Cout) ? a.bias[n] : 0.f;
+        const float b = conv_bias(a, n0 + (wn * TN + tn) * 32 + r);
 #pragma unroll
         for (int tm = 0; tm < TM; tm++)
 #pragma unroll
@@ -164,7 +159,7 @@ __global__ __launch_bounds__(256) void conv_bf16(ConvArgs a) {
         for (int tm = 0; tm < TM; tm++) {
 #pragma unroll
             for (int i = 0; i < 16; i++) {
-                const int mr = m0 + (wm * TM + tm) * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                const int mr = mfma32_row(m0 + (wm * TM + tm) * 32, i, h);
                 if (mr >= a.M) continue;
                 float v = acc[tm][tn][i];
                 if (a.scale) v = __builtin_fmaf(v, sc, sf);
@@ -239,24 +234,16 @@ __global__ void k_gap_bf16(const uint16_t* __restrict__ x, int N, int HW, int C,
 
 template <int BM, int BN, int BK>
 int launch_bf16(const ConvArgs& a, hipStream_t s) {
-    dim3 grid((a.M + BM - 1) / BM, (a.Cout + BN - 1) / BN);
-    const bool pad = a.ph || a.pw;
-    g_trl_conv_choice = TrlConvChoice{TRL_FNK_BF16, BM, BN, BK, pad, 1};
-    if (a.lowp == 2) {
-        if (pad) conv_bf16<BM, BN, BK, true, 2><<<grid, 256, 0, s>>>(a); else conv_bf16<BM, BN, BK, false, 2><<<grid, 256, 0, s>>>(a);
-    } else {
-        if (pad) conv_bf16<BM, BN, BK, true, 1><<<grid, 256, 0, s>>>(a); else conv_bf16<BM, BN, BK, false, 1><<<grid, 256, 0, s>>>(a);
-    }
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
+    const dim3 grid((a.M + BM - 1) / BM, (a.Cout + BN - 1) / BN);
+    if (a.lowp == 2) return conv_launch_twin(TRL_FNK_BF16, BM, BN, BK, conv_bf16<BM, BN, BK, true, 2>, conv_bf16<BM, BN, BK, false, 2>, a, grid, s);
+    return conv_launch_twin(TRL_FNK_BF16, BM, BN, BK, conv_bf16<BM, BN, BK, true, 1>, conv_bf16<BM, BN, BK, false, 1>, a, grid, s);
 }
 
 }  // namespace
 
 int trl_launch_conv_bf16(const ConvArgs& a, hipStream_t s) {
     if (a.M <= 0) return TRL_OK;
-    if (!a.wt || a.K != a.KH * a.KW * a.Cin || (a.Cin % 16) || (a.ldx % 8) || (a.xoff % 8) || (((uintptr_t)a.x) & 15) ||
-        (long long)a.N * a.H * a.W * a.ldx + a.xoff >= 0x7fffffffll) {
+    if (!a.wt || !trl_conv_taps32(a) || (a.Cin % 16) || (a.ldx % 8) || (a.xoff % 8) || (((uintptr_t)a.x) & 15)) {
         trl_set_error("bf16 conv: unsupported layer shape (Cin=%d ldx=%d xoff=%d K=%d)", a.Cin, a.ldx, a.xoff, a.K);
         return TRL_ERR_INVALID;
     }

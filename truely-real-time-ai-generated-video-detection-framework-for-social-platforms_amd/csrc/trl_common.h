@@ -152,7 +152,14 @@ __device__ __forceinline__ int trl_live_rows(const ConvArgs& a) {   // rows of t
 
 // ---- kernels (launch wrappers) ----------------------------------------------------------------
 int trl_launch_conv(const ConvArgs& a, hipStream_t s);
-bool trl_fn_split4_rule(const ConvArgs& a);                                // the oracle's four-chain rule applies to the layer
+// what the conv launchers ask of a layer, each written once:
+// the oracle's four-chain rule for tiny maps with long reductions (oracle/trl_oracle.c conv2d) applies to the layer
+inline bool trl_fn_split4_rule(const ConvArgs& a) { return a.OH * a.OW <= 9 && a.K >= 512 && (a.K & 15) == 0; }
+// K chunks can be whole filter taps and a 32-bit element offset reaches all of x (the kernels with a scalar im2col cursor)
+inline bool trl_conv_taps32(const ConvArgs& a) { return a.K == a.KH * a.KW * a.Cin && (long long)a.N * a.H * a.W * a.ldx + a.xoff < 0x7fffffffll; }
+inline bool trl_conv_small(const ConvArgs& a) { return trl_conv_taps32(a) && (long long)a.K * a.ldw < 0x7fffffffll; }   // ... and all of w
+// the input can be gathered as aligned float4
+inline bool trl_conv_vec(const ConvArgs& a) { return (a.Cin % 4 == 0) && (a.ldx % 4 == 0) && (a.xoff % 4 == 0) && (((uintptr_t)a.x & 15) == 0); }
 bool trl_fn_eligible(const ConvArgs& a);                                   // trl_fnconv.hip: small-map conv family
 int trl_launch_fn_group(const ConvArgs* convs, int nz, hipStream_t s);     // 1..3 independent convs in one launch
 int trl_launch_maxpool(const float* x, int N, int H, int W, int C, int ldx, int xoff, int k, int st,

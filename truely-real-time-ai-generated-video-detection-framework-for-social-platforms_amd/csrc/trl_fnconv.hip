@@ -13,13 +13,16 @@
 // ascending -- v_mfma_f32_16x16x4_f32 is that chain, 4 k per instruction; layers with OH*OW <= 9 and K >= 512 use
 // FOUR chains over consecutive quarters of k combined as (c0 + c1) + (c2 + c3) (SPLIT4: one wave per quarter).
 // A tap that lies in the padding for every output row contributes fmaf(0, w, acc) == acc and is skipped.
-#include "trl_ctx.h"
-#include <stdlib.h>
+//
+// The epilogue (conv_col / conv_finish, the ysplit / yskip column), the accumulator-to-row map and fn_conv's bias seed are
+// trl_conv.h's; these kernels request their residual values before the K loop and hand conv_finish the value.  Their row decode
+// and tap cursor (and fn_conv_split4's bias seed) stay written out here: on trl_conv.h's ConvRow / TapCursor / conv_bias the two
+// kernels compiled to reordered code that measured 1 - 2 % slower per launch (profiles/conv_refactor_timing.txt); as they stand
+// their device code equals the hand-written kernels' instruction for instruction.
+#include "trl_conv.h"
 #include <stdio.h>
 #include <type_traits>
 #include <utility>
-
-typedef float f32x4m __attribute__((ext_vector_type(4)));
 
 struct FnGroup {
     ConvArgs a[3];
@@ -46,29 +49,6 @@ typedef float f32x2m __attribute__((ext_vector_type(2)));
 // uniform: the tap (ky, kx) lies in the zero padding for EVERY output pixel (1x1 maps with padded 1x3 / 3x1 filters)
 __device__ __forceinline__ bool fn_dead_tap(const ConvArgs& a, int ky, int kx) {
     return a.H == 1 && a.W == 1 && (ky != a.ph || kx != a.pw);
-}
-
-// Per-column epilogue constants live in registers; the residual values of a lane's outputs are all requested before the first
-// store (stores may alias the residual buffer as far as the compiler knows: per-element load/store pairs would serialise on
-// memory latency -- the first version of this kernel spent 80 % of its time there).
-struct FnCol { float sc, sf, sl; };
-__device__ __forceinline__ FnCol fn_col(const ConvArgs& a, int n) {
-    FnCol c;
-    const bool ok = n < a.Cout;
-    c.sc = (a.scale && ok) ? a.scale[n] : 1.f;
-    c.sf = (a.scale && ok) ? a.shift[n] : 0.f;
-    c.sl = (a.act == TRL_ACT_PRELU && ok) ? a.slope[n] : 0.f;
-    return c;
-}
-__device__ __forceinline__ float fn_finish(const ConvArgs& a, const FnCol& c, float v, float r) {
-    if (a.scale) v = __builtin_fmaf(v, c.sc, c.sf);
-    if (a.res) {
-        v = v * a.res_scale;
-        v = v + r;
-    }
-    if (a.act == TRL_ACT_RELU) v = v > 0.f ? v : 0.f;
-    else if (a.act == TRL_ACT_PRELU) v = v > 0.f ? v : c.sl * v;
-    return v;
 }
 
 // ---- single chain: the four waves tile BM x BN as WM x WN ----------------------------------------------------------------
@@ -103,7 +83,7 @@ __global__ __launch_bounds__(256) void fn_conv(FnGroup g) {
     // contributes to a chunk, so a wave's load touches 16 cache lines, not 64 (a row-per-lane gather spent half of every wave's
     // life waiting on the vector L1: SQ_WAIT_ANY 52 % in the first version).  Rows past M re-read row 0 (never stored).
     int aoff[APT], adst[APT];
-    bool ain[APT][1];
+    bool ain[APT];
     int iy0v[APT], ix0v[APT];
     const int ohw = a.OH * a.OW;
 #pragma unroll
@@ -116,7 +96,7 @@ __global__ __launch_bounds__(256) void fn_conv(FnGroup g) {
         iy0v[i] = oy * a.sh - a.ph; ix0v[i] = ox * a.sw - a.pw;
         aoff[i] = ((nimg * a.H + iy0v[i]) * a.W + ix0v[i]) * a.ldx + a.xoff + 4 * gk;
         adst[i] = row * LDK + 4 * gk;
-        ain[i][0] = slot < ASL;
+        ain[i] = slot < ASL;
     }
     int boff[BPT], bdst[BPT];
 #pragma unroll
@@ -130,24 +110,24 @@ __global__ __launch_bounds__(256) void fn_conv(FnGroup g) {
     }
     const bool pad = a.ph || a.pw;
 
-    f32x4m ar[FDEPTH][APT], br[FDEPTH][BPT];   // ext_vector arrays stay in registers (HIP float4 structs captured by a lambda do not)
+    f32x4 ar[FDEPTH][APT], br[FDEPTH][BPT];   // ext_vector arrays stay in registers (HIP float4 structs captured by a lambda do not)
     int ky = 0, kx = 0, c0 = 0, k0 = 0;                    // scalar cursor of the next chunk to load
     auto load = [&](auto ST) __attribute__((always_inline)) {
         constexpr int st = decltype(ST)::value;
         const int soff = (ky * a.W + kx) * a.ldx + c0;
 #pragma unroll
         for (int i = 0; i < APT; i++) {
-            f32x4m v = {0.f, 0.f, 0.f, 0.f};
-            bool ok = ain[i][0];
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            bool ok = ain[i];
             if (pad) ok = ok && (unsigned)(iy0v[i] + ky) < (unsigned)a.H && (unsigned)(ix0v[i] + kx) < (unsigned)a.W;
-            if (ok && !(skipm & 2)) v = *reinterpret_cast<const f32x4m*>(a.x + (aoff[i] + soff));
+            if (ok && !(skipm & 2)) v = *reinterpret_cast<const f32x4*>(a.x + (aoff[i] + soff));
             ar[st][i] = v;
         }
         const float* wrow = a.w + (size_t)k0 * a.ldw;
 #pragma unroll
         for (int i = 0; i < BPT; i++) {
-            f32x4m v = {0.f, 0.f, 0.f, 0.f};
-            if ((BSL % 256 == 0 || tid + 256 * i < BSL) && !(skipm & 2)) v = *reinterpret_cast<const f32x4m*>(wrow + boff[i]);
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if ((BSL % 256 == 0 || tid + 256 * i < BSL) && !(skipm & 2)) v = *reinterpret_cast<const f32x4*>(wrow + boff[i]);
             br[st][i] = v;
         }
         k0 += FBK; c0 += FBK;
@@ -159,23 +139,22 @@ __global__ __launch_bounds__(256) void fn_conv(FnGroup g) {
         float* Bs = Bsm + buf * BSZ;
 #pragma unroll
         for (int i = 0; i < APT; i++) {
-            if (ASL % 256 == 0 || ain[i][0]) {      // two 8-byte stores (row stride 136 B keeps 8-byte alignment)
+            if (ASL % 256 == 0 || ain[i]) {      // two 8-byte stores (row stride 136 B keeps 8-byte alignment)
                 *reinterpret_cast<f32x2m*>(&As[adst[i]]) = f32x2m{ar[st][i][0], ar[st][i][1]};
                 *reinterpret_cast<f32x2m*>(&As[adst[i] + 2]) = f32x2m{ar[st][i][2], ar[st][i][3]};
             }
         }
 #pragma unroll
         for (int i = 0; i < BPT; i++)
-            if (BSL % 256 == 0 || tid + 256 * i < BSL) *reinterpret_cast<f32x4m*>(&Bs[bdst[i]]) = br[st][i];
+            if (BSL % 256 == 0 || tid + 256 * i < BSL) *reinterpret_cast<f32x4*>(&Bs[bdst[i]]) = br[st][i];
     };
 
-    f32x4m acc[TM][TN];
+    f32x4 acc[TM][TN];
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
-        const int n = n0 + (wn * TN + tn) * 16 + l15;
-        const float b = (a.bias != nullptr && n < a.Cout) ? a.bias[n] : 0.f;     // the chain starts at the bias
+        const float b = conv_bias(a, n0 + (wn * TN + tn) * 16 + l15);     // the chain starts at the bias
 #pragma unroll
-        for (int tm = 0; tm < TM; tm++) acc[tm][tn] = f32x4m{b, b, b, b};
+        for (int tm = 0; tm < TM; tm++) acc[tm][tn] = f32x4{b, b, b, b};
     }
     // All operands of a chunk are requested before its first MFMA (hipcc sinks each LDS read next to its use, which exposes
     // the LDS latency once per k-step: 2-3x the MFMA time of these short steps).
@@ -208,17 +187,17 @@ __global__ __launch_bounds__(256) void fn_conv(FnGroup g) {
     // epilogue operands are requested NOW, behind the first chunks: per-column constants and the residual values of this
     // lane's outputs arrive while the K loop runs (fetched after it, their round trip was the whole epilogue)
     const float* __restrict__ rp = a.res;
-    FnCol colc[TN];
+    ConvCol colc[TN];
     float rv[TM][TN][4];
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
         const int n = n0 + (wn * TN + tn) * 16 + l15;
-        colc[tn] = fn_col(a, n);
+        colc[tn] = conv_col(a, n);
 #pragma unroll
         for (int tm = 0; tm < TM; tm++)
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                const int mr = m0 + (wm * TM + tm) * 16 + kq * 4 + q;
+                const int mr = mfma16_row(m0 + (wm * TM + tm) * 16, q, kq);
                 rv[tm][tn][q] = (rp && mr < a.M && n < a.Cout) ? rp[(size_t)mr * a.ldres + n] : 0.f;
             }
     }
@@ -258,8 +237,8 @@ __global__ __launch_bounds__(256) void fn_conv(FnGroup g) {
         for (int tm = 0; tm < TM; tm++)
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                const int mr = m0 + (wm * TM + tm) * 16 + kq * 4 + q;
-                if (mr < a.M) yp[(size_t)mr * a.ldy + a.yoff + n + (n >= a.ysplit ? a.yskip : 0)] = fn_finish(a, colc[tn], acc[tm][tn][q], rv[tm][tn][q]);
+                const int mr = mfma16_row(m0 + (wm * TM + tm) * 16, q, kq);
+                if (mr < a.M) yp[(size_t)mr * a.ldy + a.yoff + n + conv_yskip(a, n)] = conv_finish(a, colc[tn], acc[tm][tn][q], rv[tm][tn][q]);
             }
     }
     if (dbgp && lane == 0) {
@@ -332,7 +311,7 @@ __global__ __launch_bounds__(256) void fn_conv_split4(FnGroup g) {
     // scalar cursor of the wave's quarter
     const int tap0 = ks / a.Cin;
     int c0 = ks - tap0 * a.Cin, ky = tap0 / a.KW, kx = tap0 - ky * a.KW, k0 = ks;
-    f32x4m ar[FDEPTH][APL], br[FDEPTH][BPL];
+    f32x4 ar[FDEPTH][APL], br[FDEPTH][BPL];
     bool live[FDEPTH];                                       // chunk in the stage is not an all-padding tap (indexed at compile time)
     auto load = [&](auto ST) __attribute__((always_inline)) {
         constexpr int st = decltype(ST)::value;
@@ -342,15 +321,15 @@ __global__ __launch_bounds__(256) void fn_conv_split4(FnGroup g) {
             const int soff = (ky * a.W + kx) * a.ldx + c0;
 #pragma unroll
             for (int i = 0; i < APL; i++) {
-                f32x4m v = {0.f, 0.f, 0.f, 0.f};
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
                 bool ok = true;
                 if (pad) ok = (unsigned)(iy0v[i] + ky) < (unsigned)a.H && (unsigned)(ix0v[i] + kx) < (unsigned)a.W;
-                if (ok && !(skipm & 2)) v = *reinterpret_cast<const f32x4m*>(a.x + (aoff[i] + soff));
+                if (ok && !(skipm & 2)) v = *reinterpret_cast<const f32x4*>(a.x + (aoff[i] + soff));
                 ar[st][i] = v;
             }
             const float* wrow = a.w + (size_t)k0 * a.ldw;
 #pragma unroll
-            for (int i = 0; i < BPL; i++) br[st][i] = (skipm & 2) ? f32x4m{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4m*>(wrow + boff[i]);
+            for (int i = 0; i < BPL; i++) br[st][i] = (skipm & 2) ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(wrow + boff[i]);
         }
         k0 += FBK; c0 += FBK;
         if (c0 >= a.Cin) { c0 = 0; if (++kx == a.KW) { kx = 0; ++ky; } }
@@ -363,16 +342,16 @@ __global__ __launch_bounds__(256) void fn_conv_split4(FnGroup g) {
             *reinterpret_cast<f32x2m*>(&As[adst[i] + 2]) = f32x2m{ar[st][i][2], ar[st][i][3]};
         }
 #pragma unroll
-        for (int i = 0; i < BPL; i++) *reinterpret_cast<f32x4m*>(&Bs[bdst[i]]) = br[st][i];
+        for (int i = 0; i < BPL; i++) *reinterpret_cast<f32x4*>(&Bs[bdst[i]]) = br[st][i];
     };
 
-    f32x4m acc[TM][TN];
+    f32x4 acc[TM][TN];
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
         const int n = n0 + tn * 16 + l15;
         const float b = (wave == 0 && a.bias != nullptr && n < a.Cout) ? a.bias[n] : 0.f;   // chain 0 starts at the bias
 #pragma unroll
-        for (int tm = 0; tm < TM; tm++) acc[tm][tn] = f32x4m{b, b, b, b};
+        for (int tm = 0; tm < TM; tm++) acc[tm][tn] = f32x4{b, b, b, b};
     }
     auto compute = [&]() __attribute__((always_inline)) {      // every operand of the chunk first, then the MFMAs (see fn_conv)
         float av[FBK / 4][TM], bv[FBK / 4][TN];
@@ -411,14 +390,14 @@ __global__ __launch_bounds__(256) void fn_conv_split4(FnGroup g) {
     fn_static_for(SEQ, [&](auto J) __attribute__((always_inline)) { if (decltype(J)::value < nchunks) load(J); });
     // epilogue operands requested behind the first chunks (see fn_conv): thread (wave = q, lane) finishes element q of every block
     const float* __restrict__ rp = a.res;
-    FnCol cc[TN];
+    ConvCol cc[TN];
 #pragma unroll
-    for (int tn = 0; tn < TN; tn++) cc[tn] = fn_col(a, n0 + tn * 16 + l15);
+    for (int tn = 0; tn < TN; tn++) cc[tn] = conv_col(a, n0 + tn * 16 + l15);
     float rv[TM * TN];
 #pragma unroll
     for (int blk = 0; blk < TM * TN; blk++) {
         const int tm = blk / TN, tn = blk - tm * TN;
-        const int mr = m0 + tm * 16 + kq * 4 + wave;
+        const int mr = mfma16_row(m0 + tm * 16, wave, kq);
         const int n = n0 + tn * 16 + l15;
         rv[blk] = (rp && mr < a.M && n < a.Cout) ? rp[(size_t)mr * a.ldres + n] : 0.f;
     }
@@ -453,11 +432,11 @@ __global__ __launch_bounds__(256) void fn_conv_split4(FnGroup g) {
     for (int blk = 0; blk < TM * TN; blk++) {
         const int tm = blk / TN, tn = blk - tm * TN;
         const int e = tid + 256 * blk;
-        const int mr = m0 + tm * 16 + kq * 4 + wave;
+        const int mr = mfma16_row(m0 + tm * 16, wave, kq);
         const int n = n0 + tn * 16 + l15;
         if (mr >= a.M || n >= a.Cout) continue;
         const float v = (red[e] + red[RED + e]) + (red[2 * RED + e] + red[3 * RED + e]);
-        yp[(size_t)mr * a.ldy + a.yoff + n + (n >= a.ysplit ? a.yskip : 0)] = fn_finish(a, cc[tn], v, rv[blk]);
+        yp[(size_t)mr * a.ldy + a.yoff + n + conv_yskip(a, n)] = conv_finish(a, cc[tn], v, rv[blk]);
     }
     if (dbgp && lane == 0) {
         unsigned long long* d = dbgp + (size_t)(((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 + wave) * 8;
@@ -505,19 +484,14 @@ int g_dbg_arm = -1, g_dbg_waves = 0;
 constexpr int DBG_WAVES = 1 << 16;
 #endif
 
-bool fn_split4(const ConvArgs& a) { return a.OH * a.OW <= 9 && a.K >= 512 && (a.K & 15) == 0; }
-
 }  // namespace
-
-bool trl_fn_split4_rule(const ConvArgs& a) { return fn_split4(a); }
 
 // Does this family take the layer?  Whole-tap chunks of 32 channels, float4-aligned input, 32-bit element offsets, small M.
 bool trl_fn_eligible(const ConvArgs& a) {
     if (g_trl_no_fnconv || a.lowp || a.m_dev) return false;
-    if (a.M <= 0 || a.M > 16384 || a.Cin % 32 != 0 || a.K != a.KH * a.KW * a.Cin) return false;
-    if ((a.ldx & 3) || (a.xoff & 3) || (((uintptr_t)a.x) & 15) || (a.ldw & 3)) return false;
-    if ((long long)a.N * a.H * a.W * a.ldx + a.xoff >= 0x7fffffffll || (long long)a.K * a.ldw >= 0x7fffffffll) return false;
-    if (fn_split4(a)) {
+    if (a.M <= 0 || a.M > 16384 || a.Cin % 32 != 0) return false;
+    if (!trl_conv_vec(a) || (a.ldw & 3) || !trl_conv_small(a)) return false;
+    if (trl_fn_split4_rule(a)) {
         const int seg = a.K >> 2;
         if (a.H == 1 && a.W == 1 && (a.ph || a.pw)) {         // quarters clipped to the centre tap must align to chunks
             const int lo = (a.ph * a.KW + a.pw) * a.Cin, hi = lo + a.Cin;
@@ -545,10 +519,10 @@ static Tile pick_tile(int M, int N, bool split4, int nz) {
 // Up to three convs of the SAME class (all split-4 or all single-chain) in one launch; they must not depend on each other.
 int trl_launch_fn_group(const ConvArgs* convs, int nz, hipStream_t s) {
     if (nz < 1 || nz > 3) { trl_set_error("fn group size"); return TRL_ERR_INVALID; }
-    const bool sp = fn_split4(convs[0]);
+    const bool sp = trl_fn_split4_rule(convs[0]);
     int M = 0, N = 0;
     for (int z = 0; z < nz; z++) {
-        if (!trl_fn_eligible(convs[z]) || fn_split4(convs[z]) != sp) { trl_set_error("fn group: ineligible or mixed convs"); return TRL_ERR_INVALID; }
+        if (!trl_fn_eligible(convs[z]) || trl_fn_split4_rule(convs[z]) != sp) { trl_set_error("fn group: ineligible or mixed convs"); return TRL_ERR_INVALID; }
         M = convs[z].M > M ? convs[z].M : M;
         N += convs[z].Cout;                                  // the group shares the chip: choose the tile for the combined width
     }

@@ -13,11 +13,10 @@
 //   staging     A (pixels x k) gathered from NHWC into LDS as [k][m]; B (k x cout) as [k][n];
 //               ds_read_b32 operand reads are conflict-free (32 consecutive floats per half-wave).
 //               Next chunk's global loads are issued before the MFMAs of the current chunk.
-#include "trl_ctx.h"
-#include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4s __attribute__((ext_vector_type(4)));
+//
+// What every conv kernel shares -- row decode, the k cursors, the bias seed, the epilogue, the accumulator-to-row maps, the
+// four-chain tail, the launch helpers -- is in trl_conv.h; the kernels below are tiles, loaders and K-loop schedules.
+#include "trl_conv.h"
 
 namespace {
 
@@ -41,31 +40,15 @@ __global__ __launch_bounds__(256) void conv_igemm(ConvArgs a) {
     const int row = tid % BM;
     const int m = m0 + row;
     const bool mvalid = m < a.M;
-    const int mm = mvalid ? m : 0;
-    const int ohw = a.OH * a.OW;
-    const int nimg = mm / ohw;
-    const int rem = mm - nimg * ohw;
-    const int oy = rem / a.OW, ox = rem - oy * a.OW;
-    const int iy0 = oy * a.sh - a.ph, ix0 = ox * a.sw - a.pw;
-    const float* xbase = a.x + (size_t)nimg * a.H * a.W * a.ldx + a.xoff;
+    const ConvRow px = conv_row(a, m, mvalid);             // 64-bit addressing: this kernel serves inputs past 2^31 elements
 
     float4 areg[APT];
     float4 breg[BPT];
     const int kpad = (a.K + 15) & ~15;   // rows present in the zero-padded weight matrix
 
-    // Per-slot im2col cursor for the vector path: (channel, kx, ky) of the slot's current k, advanced by BK per
-    // chunk with a carry loop instead of two integer divisions per load (f32 MFMA shares the FP32 pipe with the
-    // VALU on gfx950, so every VALU instruction in the K loop is paid in matrix throughput).
-    int cur_c[APT], cur_kx[APT], cur_ky[APT];
+    SlotCursor cur[APT];                                   // the vector path's per-slot im2col cursors
 #pragma unroll
-    for (int i = 0; i < APT; i++) {
-        const int slot = tid + i * 256;
-        const int k = 4 * (slot / BM);
-        const int tap = k / a.Cin;
-        cur_c[i] = k - tap * a.Cin;
-        cur_ky[i] = tap / a.KW;
-        cur_kx[i] = tap - cur_ky[i] * a.KW;
-    }
+    for (int i = 0; i < APT; i++) cur[i].start(a, 4 * ((tid + i * 256) / BM));
     auto load_chunk = [&](int k0) {
 #pragma unroll
         for (int i = 0; i < APT; i++) {
@@ -74,11 +57,8 @@ __global__ __launch_bounds__(256) void conv_igemm(ConvArgs a) {
             if (slot < ASLOTS && mvalid) {
                 const int k = k0 + 4 * (slot / BM);
                 if (VEC) {
-                    if (k < a.K) {
-                        const int iy = iy0 + cur_ky[i], ix = ix0 + cur_kx[i];
-                        if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
-                            v = *reinterpret_cast<const float4*>(xbase + ((size_t)iy * a.W + ix) * a.ldx + cur_c[i]);
-                    }
+                    if (k < a.K && px.inside(a, cur[i].ky, cur[i].kx))
+                        v = *reinterpret_cast<const float4*>(px.ptr(a, cur[i].ky, cur[i].kx, cur[i].c));
                 } else {
                     float t[4];
 #pragma unroll
@@ -88,22 +68,14 @@ __global__ __launch_bounds__(256) void conv_igemm(ConvArgs a) {
                         if (kk < a.K) {
                             const int tap = kk / a.Cin, c = kk - tap * a.Cin;
                             const int ky = tap / a.KW, kx = tap - ky * a.KW;
-                            const int iy = iy0 + ky, ix = ix0 + kx;
-                            if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
-                                t[j] = xbase[((size_t)iy * a.W + ix) * a.ldx + c];
+                            if (px.inside(a, ky, kx)) t[j] = *px.ptr(a, ky, kx, c);
                         }
                     }
                     v = make_float4(t[0], t[1], t[2], t[3]);
                 }
             }
             areg[i] = v;
-            if (VEC) {   // advance the cursor to the next chunk
-                cur_c[i] += BK;
-                while (cur_c[i] >= a.Cin) {
-                    cur_c[i] -= a.Cin;
-                    if (++cur_kx[i] == a.KW) { cur_kx[i] = 0; ++cur_ky[i]; }
-                }
-            }
+            if (VEC) cur[i].advance(a, BK);   // to the next chunk
         }
 #pragma unroll
         for (int i = 0; i < BPT; i++) {
@@ -142,8 +114,7 @@ __global__ __launch_bounds__(256) void conv_igemm(ConvArgs a) {
     f32x16 acc[TM][TN];
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
-        const int n = n0 + (wn * TN + tn) * 32 + r;
-        const float b = (a.bias != nullptr && n < a.Cout) ? a.bias[n] : 0.f;
+        const float b = conv_bias(a, n0 + (wn * TN + tn) * 32 + r);
 #pragma unroll
         for (int tm = 0; tm < TM; tm++)
 #pragma unroll
@@ -177,24 +148,13 @@ __global__ __launch_bounds__(256) void conv_igemm(ConvArgs a) {
     for (int tn = 0; tn < TN; tn++) {
         const int n = n0 + (wn * TN + tn) * 32 + r;
         if (n >= a.Cout) continue;
-        const float sc = a.scale ? a.scale[n] : 1.f;
-        const float sf = a.scale ? a.shift[n] : 0.f;
-        const float sl = a.act == TRL_ACT_PRELU ? a.slope[n] : 0.f;
+        const ConvCol col = conv_col(a, n);
 #pragma unroll
         for (int tm = 0; tm < TM; tm++) {
 #pragma unroll
             for (int i = 0; i < 16; i++) {
-                const int mr = m0 + (wm * TM + tm) * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (mr >= a.M) continue;
-                float v = acc[tm][tn][i];
-                if (a.scale) v = __builtin_fmaf(v, sc, sf);
-                if (a.res) {
-                    v = v * a.res_scale;
-                    v = v + a.res[(size_t)mr * a.ldres + n];
-                }
-                if (a.act == TRL_ACT_RELU) v = v > 0.f ? v : 0.f;
-                else if (a.act == TRL_ACT_PRELU) v = v > 0.f ? v : sl * v;
-                a.y[(size_t)mr * a.ldy + a.yoff + n] = v;
+                const int mr = mfma32_row(m0 + (wm * TM + tm) * 32, i, h);
+                if (mr < a.M) conv_store(a, col, mr, n, acc[tm][tn][i]);
             }
         }
     }
@@ -218,41 +178,22 @@ __global__ __launch_bounds__(256) void conv_splitk4(ConvArgs a) {
 
     const int m = m0 + r;
     const bool mvalid = m < a.M;
-    const int mm = mvalid ? m : 0;
-    const int ohw = a.OH * a.OW;
-    const int nimg = mm / ohw;
-    const int rem = mm - nimg * ohw;
-    const int oy = rem / a.OW, ox = rem - oy * a.OW;
-    const int iy0 = oy * a.sh - a.ph, ix0 = ox * a.sw - a.pw;
-    const float* xbase = a.x + (size_t)nimg * a.H * a.W * a.ldx + a.xoff;
+    const ConvRow px = conv_row(a, m, mvalid);             // 64-bit addressing, as conv_igemm
 
     // A: 32 rows x 8 float4 groups per chunk = 4 slots per lane (same row, groups h, h+2, h+4, h+6)
-    int cur_c[4], cur_kx[4], cur_ky[4];
+    SlotCursor cur[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int k = ks + 4 * (h + 2 * i);
-        const int tap = k / a.Cin;
-        cur_c[i] = k - tap * a.Cin;
-        cur_ky[i] = tap / a.KW;
-        cur_kx[i] = tap - cur_ky[i] * a.KW;
-    }
+    for (int i = 0; i < 4; i++) cur[i].start(a, ks + 4 * (h + 2 * i));
     float4 areg[4], breg[8];
     auto load_chunk = [&](int k0) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int k = k0 + 4 * (h + 2 * i);
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (mvalid && k < ke) {
-                const int iy = iy0 + cur_ky[i], ix = ix0 + cur_kx[i];
-                if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
-                    v = *reinterpret_cast<const float4*>(xbase + ((size_t)iy * a.W + ix) * a.ldx + cur_c[i]);
-            }
+            if (mvalid && k < ke && px.inside(a, cur[i].ky, cur[i].kx))
+                v = *reinterpret_cast<const float4*>(px.ptr(a, cur[i].ky, cur[i].kx, cur[i].c));
             areg[i] = v;
-            cur_c[i] += BK;
-            while (cur_c[i] >= a.Cin) {
-                cur_c[i] -= a.Cin;
-                if (++cur_kx[i] == a.KW) { cur_kx[i] = 0; ++cur_ky[i]; }
-            }
+            cur[i].advance(a, BK);
         }
 #pragma unroll
         for (int i = 0; i < 8; i++) {
@@ -281,8 +222,7 @@ __global__ __launch_bounds__(256) void conv_splitk4(ConvArgs a) {
     f32x16 acc[2];
 #pragma unroll
     for (int tn = 0; tn < 2; tn++) {
-        const int n = n0 + tn * 32 + r;
-        const float b = (wave == 0 && a.bias != nullptr && n < a.Cout) ? a.bias[n] : 0.f;   // chain 0 starts at the bias
+        const float b = conv_bias(a, n0 + tn * 32 + r, wave == 0);
 #pragma unroll
         for (int i = 0; i < 16; i++) acc[tn][i] = b;
     }
@@ -298,30 +238,7 @@ __global__ __launch_bounds__(256) void conv_splitk4(ConvArgs a) {
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b1, acc[1], 0, 0, 0);
         }
     }
-    __syncthreads();
-    float* red = &Bs[0][0];                              // [wave][tn][reg][lane]
-#pragma unroll
-    for (int tn = 0; tn < 2; tn++)
-#pragma unroll
-        for (int i = 0; i < 16; i++) red[((wave * 2 + tn) * 16 + i) * 64 + lane] = acc[tn][i];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const int e = tid + 256 * j;
-        const int tn = e >> 10, reg = (e >> 6) & 15, ln = e & 63;
-        const int mr = m0 + (reg & 3) + 8 * (reg >> 2) + 4 * (ln >> 5);
-        const int n = n0 + tn * 32 + (ln & 31);
-        if (mr >= a.M || n >= a.Cout) continue;
-        float v = (red[e] + red[2048 + e]) + (red[4096 + e] + red[6144 + e]);
-        if (a.scale) v = __builtin_fmaf(v, a.scale[n], a.shift[n]);
-        if (a.res) {
-            v = v * a.res_scale;
-            v = v + a.res[(size_t)mr * a.ldres + n];
-        }
-        if (a.act == TRL_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (a.act == TRL_ACT_PRELU) v = v > 0.f ? v : a.slope[n] * v;
-        a.y[(size_t)mr * a.ldy + a.yoff + n] = v;
-    }
+    conv_split4_tail(a, &Bs[0][0], acc, m0, n0, tid, wave);   // the staging buffers become the partial tiles
 }
 
 // conv_splitk4_tap: conv_splitk4 with whole-tap chunks (Cin % BKC == 0 and (K/4) % BKC == 0): the im2col cursor of a
@@ -339,36 +256,28 @@ __global__ __launch_bounds__(256) void conv_splitk4_tap(ConvArgs a) {
     const int segK = a.K >> 2, ks = wave * segK;
 
     const int m = m0 + r;
-    const int mm = m < a.M ? m : 0;
-    const int ohw = a.OH * a.OW;
-    const int nimg = mm / ohw;
-    const int rem = mm - nimg * ohw;
-    const int oy = rem / a.OW, ox = rem - oy * a.OW;
-    const int iy0 = oy * a.sh - a.ph, ix0 = ox * a.sw - a.pw;
-    const int aoff = ((nimg * a.H + iy0) * a.W + ix0) * a.ldx + a.xoff + 4 * h;
+    const ConvRow px = conv_row(a, m, m < a.M);
+    const int aoff = px.off(a) + 4 * h;
     int bn = n0 + 4 * (lane & 15);
     bn = bn < a.ldw ? bn : 0;
     const int boff = (lane >> 4) * a.ldw + bn;
 
-    // scalar cursor of the wave's quarter
-    const int tap0 = ks / a.Cin;
-    int c0 = ks - tap0 * a.Cin, ky = tap0 / a.KW, kx = tap0 - ky * a.KW, k0 = ks;
-    f32x4s areg[AS], breg[BSL];
+    TapCursor cur(a, ks);                                    // scalar cursor of the wave's quarter
+    f32x4 areg[AS], breg[BSL];
     auto load_chunk = [&]() __attribute__((always_inline)) {
-        const int soff = (ky * a.W + kx) * a.ldx + c0;
+        const int soff = cur.soff(a);
         bool inside = true;
-        if (PAD) inside = (unsigned)(iy0 + ky) < (unsigned)a.H && (unsigned)(ix0 + kx) < (unsigned)a.W;
+        if (PAD) inside = cur.inside(a, px.iy0, px.ix0);
 #pragma unroll
         for (int i = 0; i < AS; i++) {
-            f32x4s v = {0.f, 0.f, 0.f, 0.f};
-            if (inside) v = *reinterpret_cast<const f32x4s*>(a.x + (aoff + soff + 8 * i));
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (inside) v = *reinterpret_cast<const f32x4*>(a.x + (aoff + soff + 8 * i));
             areg[i] = v;
         }
-        const float* wrow = a.w + (size_t)k0 * a.ldw;
+        const float* wrow = a.w + (size_t)cur.k0 * a.ldw;
 #pragma unroll
-        for (int i = 0; i < BSL; i++) breg[i] = *reinterpret_cast<const f32x4s*>(wrow + (boff + 4 * i * a.ldw));
-        k0 += BKC; c0 += BKC;
-        if (c0 >= a.Cin) { c0 = 0; if (++kx == a.KW) { kx = 0; ++ky; } }
+        for (int i = 0; i < BSL; i++) breg[i] = *reinterpret_cast<const f32x4*>(wrow + (boff + 4 * i * a.ldw));
+        cur.advance(a, BKC);
     };
     float* Aw = As[wave];
     float* Bw = Bs[wave];
@@ -380,14 +289,13 @@ __global__ __launch_bounds__(256) void conv_splitk4_tap(ConvArgs a) {
             Aw[(4 * g + 2) * BM + r] = areg[i][2]; Aw[(4 * g + 3) * BM + r] = areg[i][3];
         }
 #pragma unroll
-        for (int i = 0; i < BSL; i++) *reinterpret_cast<f32x4s*>(&Bw[((lane >> 4) + 4 * i) * BN + 4 * (lane & 15)]) = breg[i];
+        for (int i = 0; i < BSL; i++) *reinterpret_cast<f32x4*>(&Bw[((lane >> 4) + 4 * i) * BN + 4 * (lane & 15)]) = breg[i];
     };
 
     f32x16 acc[2];
 #pragma unroll
     for (int tn = 0; tn < 2; tn++) {
-        const int n = n0 + tn * 32 + r;
-        const float b = (wave == 0 && a.bias != nullptr && n < a.Cout) ? a.bias[n] : 0.f;   // chain 0 starts at the bias
+        const float b = conv_bias(a, n0 + tn * 32 + r, wave == 0);
 #pragma unroll
         for (int i = 0; i < 16; i++) acc[tn][i] = b;
     }
@@ -404,30 +312,7 @@ __global__ __launch_bounds__(256) void conv_splitk4_tap(ConvArgs a) {
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b1, acc[1], 0, 0, 0);
         }
     }
-    __syncthreads();
-    float* red = &Bs[0][0];                              // [wave][tn][reg][lane]
-#pragma unroll
-    for (int tn = 0; tn < 2; tn++)
-#pragma unroll
-        for (int i = 0; i < 16; i++) red[((wave * 2 + tn) * 16 + i) * 64 + lane] = acc[tn][i];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const int e = tid + 256 * j;
-        const int tn = e >> 10, reg = (e >> 6) & 15, ln = e & 63;
-        const int mr = m0 + (reg & 3) + 8 * (reg >> 2) + 4 * (ln >> 5);
-        const int n = n0 + tn * 32 + (ln & 31);
-        if (mr >= a.M || n >= a.Cout) continue;
-        float v = (red[e] + red[2048 + e]) + (red[4096 + e] + red[6144 + e]);
-        if (a.scale) v = __builtin_fmaf(v, a.scale[n], a.shift[n]);
-        if (a.res) {
-            v = v * a.res_scale;
-            v = v + a.res[(size_t)mr * a.ldres + n];
-        }
-        if (a.act == TRL_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (a.act == TRL_ACT_PRELU) v = v > 0.f ? v : a.slope[n] * v;
-        a.y[(size_t)mr * a.ldy + a.yoff + n] = v;
-    }
+    conv_split4_tail(a, &Bs[0][0], acc, m0, n0, tid, wave);   // the staging buffers become the partial tiles
 }
 
 // conv_tap: the same implicit GEMM for layers whose K chunks never straddle a filter tap (Cin % BK == 0): the
@@ -458,19 +343,15 @@ __global__ __launch_bounds__(256) void conv_tap(ConvArgs a) {
     // channels one pixel contributes to a chunk, so a wave's load touches 64 / KG pixels' lines instead of 64 (row-per-lane
     // gathers spend the vector L1's request rate, not its bandwidth: round 2).  Element offset of
     // (image, iy0, ix0, channel 4 g) from a.x; rows past M re-read row 0 (never stored).
-    const int ohw = a.OH * a.OW;
     int aoff[APT], adst[APT], iy0v[APT], ix0v[APT];
 #pragma unroll
     for (int i = 0; i < APT; i++) {
         const int slot = tid + 256 * i;
         const int g = slot % KG, row = slot / KG;
         const int m = m0 + row;
-        const int mm = (m < a.M && row < BM) ? m : 0;
-        const int nimg = mm / ohw;
-        const int rem = mm - nimg * ohw;
-        const int oy = rem / a.OW, ox = rem - oy * a.OW;
-        iy0v[i] = oy * a.sh - a.ph; ix0v[i] = ox * a.sw - a.pw;
-        aoff[i] = ((nimg * a.H + iy0v[i]) * a.W + ix0v[i]) * a.ldx + a.xoff + 4 * g;      // < 2^31: checked by the launcher
+        const ConvRow px = conv_row(a, m, m < a.M && row < BM);
+        iy0v[i] = px.iy0; ix0v[i] = px.ix0;
+        aoff[i] = px.off(a) + 4 * g;                            // < 2^31: checked by the launcher
         adst[i] = row * LDA + 4 * g;
     }
     // ---- per-thread B slot: (k row kk0, column n) ------------------------------------------------------------
@@ -482,28 +363,25 @@ __global__ __launch_bounds__(256) void conv_tap(ConvArgs a) {
 
     float4 areg[APT];
     float4 breg[BPT];
-    int ky = 0, kx = 0, c0 = 0;                                 // scalar cursor of the NEXT chunk to load
-    int k0 = 0;
+    TapCursor cur;                                              // scalar cursor of the NEXT chunk to load
     auto load_chunk = [&]() {
-        const int soff = (ky * a.W + kx) * a.ldx + c0;         // scalar
+        const int soff = cur.soff(a);                           // scalar
 #pragma unroll
         for (int i = 0; i < APT; i++) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             bool ok = ASLOTS % 256 == 0 || tid + i * 256 < ASLOTS;
-            if (PAD) ok = ok && (unsigned)(iy0v[i] + ky) < (unsigned)a.H && (unsigned)(ix0v[i] + kx) < (unsigned)a.W;
+            if (PAD) ok &= cur.inside(a, iy0v[i], ix0v[i]);
             if (ok) v = *reinterpret_cast<const float4*>(a.x + (aoff[i] + soff));
             areg[i] = v;
         }
-        const float* wrow = a.w + (size_t)k0 * a.ldw;           // scalar
+        const float* wrow = a.w + (size_t)cur.k0 * a.ldw;       // scalar
 #pragma unroll
         for (int i = 0; i < BPT; i++) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (BSLOTS % 256 == 0 || tid + i * 256 < BSLOTS) v = *reinterpret_cast<const float4*>(wrow + (boff + BKSTEP * i * a.ldw));
             breg[i] = v;
         }
-        // advance: next BK channels of the tap, else next tap
-        k0 += BK; c0 += BK;
-        if (c0 >= a.Cin) { c0 = 0; if (++kx == a.KW) { kx = 0; ++ky; } }
+        cur.advance(a, BK);
     };
     auto store_chunk = [&]() {
 #pragma unroll
@@ -524,8 +402,7 @@ __global__ __launch_bounds__(256) void conv_tap(ConvArgs a) {
     f32x16 acc[TM][TN];
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
-        const int n = n0 + (wn * TN + tn) * 32 + r;
-        const float b = (a.bias != nullptr && n < a.Cout) ? a.bias[n] : 0.f;
+        const float b = conv_bias(a, n0 + (wn * TN + tn) * 32 + r);
 #pragma unroll
         for (int tm = 0; tm < TM; tm++)
 #pragma unroll
@@ -554,29 +431,18 @@ __global__ __launch_bounds__(256) void conv_tap(ConvArgs a) {
         __syncthreads();
     }
 
-    // ---- epilogue (as conv_igemm) --------------------------------------------------------------------------------
+    // ---- epilogue ------------------------------------------------------------------------------
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
         const int n = n0 + (wn * TN + tn) * 32 + r;
         if (n >= a.Cout) continue;
-        const float sc = a.scale ? a.scale[n] : 1.f;
-        const float sf = a.scale ? a.shift[n] : 0.f;
-        const float sl = a.act == TRL_ACT_PRELU ? a.slope[n] : 0.f;
+        const ConvCol col = conv_col(a, n);
 #pragma unroll
         for (int tm = 0; tm < TM; tm++) {
 #pragma unroll
             for (int i = 0; i < 16; i++) {
-                const int mr = m0 + (wm * TM + tm) * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (mr >= a.M) continue;
-                float v = acc[tm][tn][i];
-                if (a.scale) v = __builtin_fmaf(v, sc, sf);
-                if (a.res) {
-                    v = v * a.res_scale;
-                    v = v + a.res[(size_t)mr * a.ldres + n];
-                }
-                if (a.act == TRL_ACT_RELU) v = v > 0.f ? v : 0.f;
-                else if (a.act == TRL_ACT_PRELU) v = v > 0.f ? v : sl * v;
-                a.y[(size_t)mr * a.ldy + a.yoff + n] = v;
+                const int mr = mfma32_row(m0 + (wm * TM + tm) * 32, i, h);
+                if (mr < a.M) conv_store(a, col, mr, n, acc[tm][tn][i]);
             }
         }
     }
@@ -586,7 +452,6 @@ __global__ __launch_bounds__(256) void conv_tap(ConvArgs a) {
 // v_mfma_f32_16x16x4_f32 -- three 16-column tiles instead of two 32-column ones, so no MFMA cycle is spent on the 16 padding
 // columns a 64-wide tile would carry (25 % of that layer).  Same LDS layout ([k][m], [k][n]) and loader as conv_tap; each of the
 // 4 waves owns 32 rows = 2 x 3 accumulator tiles; k = 4s + (lane >> 4) ascending, bias-seeded: the oracle's chain.
-typedef float f32x4t __attribute__((ext_vector_type(4)));
 template <int BK, bool PAD>
 __global__ __launch_bounds__(256) void conv_tap48(ConvArgs a) {
     constexpr int BM = 128, BN = 48;
@@ -601,9 +466,12 @@ __global__ __launch_bounds__(256) void conv_tap48(ConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, kq = lane >> 4;
     const int m0 = blockIdx.x * BM;
+    __builtin_assume(a.Cout == BN);         // the launcher's condition: no column of the tile lies past the layer's
     if (m0 >= trl_live_rows(a)) return;     // device-sized batch: nothing of this tile exists (block-uniform)
 
     const int row = tid % BM, g0 = tid / BM;
+    // (row decode and cursor written out, not ConvRow / TapCursor: with them this kernel's reordered code measured 1.2 % slower,
+    // profiles/conv_refactor_timing.txt; as it stands its device code equals the hand-written kernel's)
     const int m = m0 + row;
     const int mm = m < a.M ? m : 0;
     const int ohw = a.OH * a.OW;
@@ -662,12 +530,12 @@ __global__ __launch_bounds__(256) void conv_tap48(ConvArgs a) {
         }
     };
 
-    f32x4t acc[2][3];
+    f32x4 acc[2][3];
 #pragma unroll
     for (int tn = 0; tn < 3; tn++) {
-        const float b = a.bias != nullptr ? a.bias[tn * 16 + l15] : 0.f;
+        const float b = conv_bias(a, tn * 16 + l15);
 #pragma unroll
-        for (int tm = 0; tm < 2; tm++) acc[tm][tn] = f32x4t{b, b, b, b};
+        for (int tm = 0; tm < 2; tm++) acc[tm][tn] = f32x4{b, b, b, b};
     }
 
     const int nchunks = a.K / BK;
@@ -695,54 +563,44 @@ __global__ __launch_bounds__(256) void conv_tap48(ConvArgs a) {
 #pragma unroll
     for (int tn = 0; tn < 3; tn++) {
         const int n = tn * 16 + l15;
-        const float sc = a.scale ? a.scale[n] : 1.f;
-        const float sf = a.scale ? a.shift[n] : 0.f;
-        const float sl = a.act == TRL_ACT_PRELU ? a.slope[n] : 0.f;
+        const ConvCol col = conv_col(a, n);
 #pragma unroll
         for (int tm = 0; tm < 2; tm++) {
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                const int mr = m0 + wave * 32 + tm * 16 + kq * 4 + q;
+                const int mr = mfma16_row(m0 + wave * 32 + tm * 16, q, kq);
                 if (mr >= a.M) continue;
-                float v = acc[tm][tn][q];
-                if (a.scale) v = __builtin_fmaf(v, sc, sf);
-                if (a.res) {
-                    v = v * a.res_scale;
-                    v = v + a.res[(size_t)mr * a.ldres + n];
-                }
-                if (a.act == TRL_ACT_RELU) v = v > 0.f ? v : 0.f;
-                else if (a.act == TRL_ACT_PRELU) v = v > 0.f ? v : sl * v;
-                a.y[(size_t)mr * a.ldy + a.yoff + n] = v;
+                conv_store(a, col, mr, n, acc[tm][tn][q]);
             }
         }
     }
 }
 
+// ---- launchers: one per kernel family; the recorded choice and the PAD twin are conv_launch_twin's business ---------------
 template <int BM, int BN, int WM, int WN, int BK>
 int launch_tap(const ConvArgs& a, dim3 grid, hipStream_t s) {
-    g_trl_conv_choice = TrlConvChoice{TRL_FNK_CONV_TAP, BM, BN, BK, a.ph || a.pw, 1};
-    if (a.ph || a.pw) conv_tap<BM, BN, WM, WN, BK, true><<<grid, 256, 0, s>>>(a);
-    else conv_tap<BM, BN, WM, WN, BK, false><<<grid, 256, 0, s>>>(a);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
+    return conv_launch_twin(TRL_FNK_CONV_TAP, BM, BN, BK, conv_tap<BM, BN, WM, WN, BK, true>, conv_tap<BM, BN, WM, WN, BK, false>, a, grid, s);
+}
+template <int BK>
+int launch_tap48(const ConvArgs& a, hipStream_t s) {
+    return conv_launch_twin(TRL_FNK_TAP48, 128, 48, BK, conv_tap48<BK, true>, conv_tap48<BK, false>, a, dim3((a.M + 127) / 128, 1), s);
+}
+template <int BKC>
+int launch_splitk4_tap(const ConvArgs& a, dim3 grid, hipStream_t s) {
+    return conv_launch_twin(TRL_FNK_SPLITK4_TAP, 32, 64, BKC, conv_splitk4_tap<BKC, true>, conv_splitk4_tap<BKC, false>, a, grid, s);
 }
 
 template <int BM, int BN, int WM, int WN, int BK>
 int launch_cfg(const ConvArgs& a, bool vec, hipStream_t s) {
     dim3 grid((a.M + BM - 1) / BM, (a.Cout + BN - 1) / BN);
-    // whole-tap chunks (conv_tap) whenever the channel count allows it and 32-bit element offsets suffice
-    const long long x_elems = (long long)a.N * a.H * a.W * a.ldx + a.xoff;
-    if (vec && a.K == a.KH * a.KW * a.Cin && x_elems < 0x7fffffffll && (long long)a.K * a.ldw < 0x7fffffffll) {
+    if (vec && trl_conv_small(a)) {   // whole-tap chunks (conv_tap) whenever the channel count allows it
         if (BK >= 64 && a.Cin % 64 == 0) return launch_tap<BM, BN, WM, WN, 64>(a, grid, s);
         if (a.Cin % 32 == 0) return launch_tap<BM, BN, WM, WN, 32>(a, grid, s);
         if (BM == 128 && BN == 64 && a.Cin % 28 == 0) return launch_tap<BM, BN, WM, WN, 28>(a, grid, s);
         if (a.Cin % 16 == 0) return launch_tap<BM, BN, WM, WN, 16>(a, grid, s);
     }
-    g_trl_conv_choice = vec ? TrlConvChoice{TRL_FNK_IGEMM_VEC, BM, BN, BK, 0, 1} : TrlConvChoice{TRL_FNK_IGEMM_SCALAR, BM, BN, 16, 0, 1};
-    if (vec) conv_igemm<BM, BN, WM, WN, BK, true><<<grid, 256, 0, s>>>(a);
-    else conv_igemm<BM, BN, WM, WN, 16, false><<<grid, 256, 0, s>>>(a);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
+    if (vec) return conv_launch(TRL_FNK_IGEMM_VEC, BM, BN, BK, 0, conv_igemm<BM, BN, WM, WN, BK, true>, a, grid, s);
+    return conv_launch(TRL_FNK_IGEMM_SCALAR, BM, BN, 16, 0, conv_igemm<BM, BN, WM, WN, 16, false>, a, grid, s);
 }
 
 // ---- max pool -------------------------------------------------------------------------------
@@ -912,42 +770,23 @@ __global__ __launch_bounds__(256) void drift_scan_kernel(const float* __restrict
 int trl_launch_conv(const ConvArgs& a, hipStream_t s) {
     if (a.M <= 0) return TRL_OK;
     if (trl_fn_eligible(a)) return trl_launch_fn_group(&a, 1, s);   // small maps (FaceNet's 7x7 / 3x3 / 1x1 stages): trl_fnconv.hip
-    const bool vec = (a.Cin % 4 == 0) && (a.ldx % 4 == 0) && (a.xoff % 4 == 0) && (((uintptr_t)a.x & 15) == 0);
-    // The oracle's four-chain rule for tiny maps with long reductions (oracle/trl_oracle.c conv2d)
-    if (a.OH * a.OW <= 9 && a.K >= 512 && (a.K & 15) == 0) {
+    const bool vec = trl_conv_vec(a), small = trl_conv_small(a);
+    if (trl_fn_split4_rule(a)) {                                    // four chains: one wave per quarter of k, a 32x64 tile per workgroup
         if (!vec) { trl_set_error("split-K layer needs Cin %% 4 == 0 and 16-byte aligned input"); return TRL_ERR_INVALID; }
-        dim3 grid((a.M + 31) / 32, (a.Cout + 63) / 64);
+        const dim3 grid((a.M + 31) / 32, (a.Cout + 63) / 64);
         const int segK = a.K >> 2;
-        const bool small = (long long)a.N * a.H * a.W * a.ldx + a.xoff < 0x7fffffffll && (long long)a.K * a.ldw < 0x7fffffffll;
-        const bool pad = a.ph || a.pw;
-        if (small && a.K == a.KH * a.KW * a.Cin && a.Cin % 32 == 0 && segK % 32 == 0) {
-            g_trl_conv_choice = TrlConvChoice{TRL_FNK_SPLITK4_TAP, 32, 64, 32, pad, 1};
-            if (pad) conv_splitk4_tap<32, true><<<grid, 256, 0, s>>>(a); else conv_splitk4_tap<32, false><<<grid, 256, 0, s>>>(a);
-        } else if (small && a.K == a.KH * a.KW * a.Cin && a.Cin % 16 == 0 && segK % 16 == 0) {
-            g_trl_conv_choice = TrlConvChoice{TRL_FNK_SPLITK4_TAP, 32, 64, 16, pad, 1};
-            if (pad) conv_splitk4_tap<16, true><<<grid, 256, 0, s>>>(a); else conv_splitk4_tap<16, false><<<grid, 256, 0, s>>>(a);
-        } else {
-            g_trl_conv_choice = TrlConvChoice{TRL_FNK_SPLITK4, 32, 64, 32, 0, 1};
-            conv_splitk4<<<grid, 256, 0, s>>>(a);
-        }
-        TRL_LAUNCH_CHECK();
-        return TRL_OK;
+        if (small && a.Cin % 32 == 0 && segK % 32 == 0) return launch_splitk4_tap<32>(a, grid, s);
+        if (small && a.Cin % 16 == 0 && segK % 16 == 0) return launch_splitk4_tap<16>(a, grid, s);
+        return conv_launch(TRL_FNK_SPLITK4, 32, 64, 32, 0, conv_splitk4, a, grid, s);
+    }
+    // Cout == 48 with whole-tap chunks: the 128 x 48 tile (no padded MFMA columns)
+    if (vec && small && a.Cout == 48 && a.ldw >= 48 && a.M >= 16384) {
+        if (a.Cin % 32 == 0) return launch_tap48<32>(a, s);
+        if (a.Cin % 28 == 0) return launch_tap48<28>(a, s);
     }
     // Deep K chunks (BK = 64) when K is long: a chunk's MFMAs (BK/2 x 64 cycles per wave tile) must cover
     // the global-load round trip of the next chunk, the only latency hiding a lone workgroup per CU has.
     const bool deep = a.K >= 192;
-    {   // Cout == 48 with whole-tap chunks: the 128 x 48 tile (no padded MFMA columns)
-        const bool small = (long long)a.N * a.H * a.W * a.ldx + a.xoff < 0x7fffffffll && (long long)a.K * a.ldw < 0x7fffffffll;
-        if (vec && small && a.Cout == 48 && a.ldw >= 48 && a.M >= 16384 && a.K == a.KH * a.KW * a.Cin && (a.Cin % 28 == 0 || a.Cin % 32 == 0)) {
-            dim3 grid((a.M + 127) / 128, 1);
-            const bool pad = a.ph || a.pw;
-            g_trl_conv_choice = TrlConvChoice{TRL_FNK_TAP48, 128, 48, a.Cin % 32 == 0 ? 32 : 28, pad, 1};
-            if (a.Cin % 32 == 0) { if (pad) conv_tap48<32, true><<<grid, 256, 0, s>>>(a); else conv_tap48<32, false><<<grid, 256, 0, s>>>(a); }
-            else { if (pad) conv_tap48<28, true><<<grid, 256, 0, s>>>(a); else conv_tap48<28, false><<<grid, 256, 0, s>>>(a); }
-            TRL_LAUNCH_CHECK();
-            return TRL_OK;
-        }
-    }
     if (a.Cout <= 32) return deep ? launch_cfg<128, 32, 4, 1, 64>(a, vec, s) : launch_cfg<128, 32, 4, 1, 16>(a, vec, s);
     if (a.M >= 16384) return deep ? launch_cfg<128, 64, 2, 2, 32>(a, vec, s) : launch_cfg<128, 64, 2, 2, 16>(a, vec, s);
     if (a.M >= 1024) return deep ? launch_cfg<64, 64, 2, 2, 64>(a, vec, s) : launch_cfg<64, 64, 2, 2, 16>(a, vec, s);

@@ -377,6 +377,45 @@ int  trl_jpeg_encode(trl_jpeg* enc, const uint8_t* d_bgr, int n, long long frame
  * fewer than *len bytes gives TRL_ERR_CAPACITY and is left untouched. */
 int  trl_jpeg_header(int H, int W, int quality, uint8_t* buf, size_t cap, int* len);
 
+/* ---- Motion-JPEG input (run() on Motion-JPEG AVI) -----------------------------------------------------------------------------
+ * A baseline JPEG decoder whose BGR frames are byte-identical to np.asarray(Image.open(f).convert("RGB"))[:, :, ::-1]
+ * (libjpeg-turbo's default path: islow IDCT, fancy upsampling, 16-bit-fixed colour tables).  Decoded on the device: SOF0, 8 bit,
+ * Huffman, three components in one interleaved scan, luma 2x2 / 2x1 / 1x1 over chroma 1x1, any 8-bit DQT, any DHT, any DRI, any
+ * APPn other than APP14 (with a JFIF APP0 or without one libjpeg reads such components as YCbCr).  Everything else is not
+ * attempted and is left to the caller (Pillow).  (ABI v7, additive) */
+typedef struct trl_jpegd trl_jpegd;
+typedef struct {
+    int32_t width, height;      /* of the SOF0 frame (0 if the parser did not get that far) */
+    int32_t h_samp, v_samp;     /* luma sampling factors; chroma is 1x1 */
+    int32_t restart_interval;   /* DRI, in MCUs; 0 = none */
+    int32_t scan_offset;        /* of the first entropy-coded byte */
+    int32_t supported;          /* 1: the device decoder attempts this file */
+    int32_t reason;             /* 0, or why not: 1 truncated headers, 2 no SOI, 3 not SOF0 (progressive, arithmetic, ...), 4 not
+                                 * 8 bit, 5 not three YCbCr components, 6 sampling, 7 DQT (16 bit, malformed, missing), 8 DHT
+                                 * (malformed, over-long, missing), 9 not one interleaved full scan, 10 Adobe APP14, 11 an
+                                 * unexpected marker or malformed segment, 12 zero size */
+} trl_jpegd_info;
+/* Host only, no GPU: what the marker parser finds in one file up to SOS. */
+int  trl_jpegd_parse(const uint8_t* file, size_t len, trl_jpegd_info* info);
+/* A decoder for H x W frames (1..65535 px per side), batches of up to max_frames files that lie in a buffer of max_bytes bytes.
+ * It owns its workspace (coefficients and sample planes, processed in chunks of frames when a batch needs more than 384 MiB). */
+int  trl_jpegd_create(int device, int H, int W, int max_frames, long long max_bytes, trl_jpegd** out);
+int  trl_jpegd_destroy(trl_jpegd* dec);
+/* TEST HOOK, not part of the decoding interface (it is in the shipped library because the GPU suite runs against the shipped
+ * library; it reads no environment and changes no result): fills the decoder's whole device workspace (coefficients, sample planes, tables, segment lists) with `byte`.  The
+ * decoder must be idle.  A call after it must give the same frames: every byte it reads it has written in that call. */
+int  trl_jpegd_debug_poison(trl_jpegd* dec, int byte);
+/* n files: file k is sizes[k] bytes at offsets[k] of a buffer that the caller holds twice, on the host (h_files: the headers
+ * are parsed there, and the restart markers of DRI streams are located there) and on the device (d_files: the entropy-coded
+ * bytes are read there and nowhere else).  Frame k goes to d_bgr + k * frame_stride as u8 BGR [H][W][3].  h_status[k]: 0 decoded
+ * on the device; 1 not attempted (unsupported or malformed headers, a size other than the decoder's, more than 16 distinct table
+ * sets or 2^20 restart intervals in one call); 2 the entropy decoder met something irregular (an invalid code, a run past
+ * coefficient 63, bytes running out, an unexpected marker, bytes left over) or a dequantised value outside int16.  A frame with
+ * status 1 or 2 has no byte written.  TRL_ERR_INVALID with nothing queued: n > max_frames, a file outside the buffer, a stride
+ * below H*W*3 when n > 1.  All work is queued on `stream`; the call returns after one synchronisation (to read the statuses). */
+int  trl_jpegd_decode(trl_jpegd* dec, const uint8_t* h_files, const uint8_t* d_files, const long long* offsets, const long long* sizes,
+                      int n, uint8_t* d_bgr, long long frame_stride, int32_t* h_status, void* stream);
+
 /* ---- Annotation on device frames (run()'s rectangle and caption, server/model.py:67-74) ----------------------------------------
  * Draws on u8 BGR frames in device memory exactly the bytes annotate.py's own rasteriser (the one used when OpenCV is absent)
  * draws on a host frame, so that frames can go from the colour conversion to the JPEG encoder without visiting the host.

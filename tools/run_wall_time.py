@@ -4,6 +4,7 @@ re-encoding of every frame).
 
     python tools/run_wall_time.py [out.json] [--long]
     python tools/run_wall_time.py [out.json] --output-on=R [--p720]
+    python tools/run_wall_time.py [out.json] --mjpeg=R [--p720]
 
 * BASELINE configs[0]'s shape: the reference's sample clip (test/*.mp4: 640x360, 30 fps, 960 frames, H.264) cannot be decoded
   without OpenCV, so the clip is 960 seeded synthetic frames of that shape in the raw TRLV container (BGR and NV12) and as a
@@ -16,6 +17,10 @@ re-encoding of every frame).
   so the spread is known) for the BGR, NV12 and YUV4MPEG2 clips of configs[0]'s shape; --p720 adds a 240-frame 720p clip of
   each kind (a 360p frame is small enough that per-call overheads dominate).  To compare two trees, run this mode from each of
   them in turn, several times, in one session.
+* --mjpeg=R: the clip as Motion-JPEG AVI, written by AviMjpegWriter from the same frames (quality 80, 4:2:0, no restart markers)
+  and once more with a restart marker per MCU row (Pillow's restart_marker_rows=1: the stream kind with DRI) -- warm calls with
+  the output skipped and with the annotated output written, R timed repeats each, every one listed; --p720 adds the 240-frame
+  720p clip.  TRUELY_MJPEG in the environment selects the decoder as in run().  To compare two trees, as above.
 Each line also carries the plain file-read rate of the same bytes into pinned memory (no GPU work): the bound of this path."""
 import json
 import os
@@ -100,8 +105,59 @@ def output_on(repeats, p720):
     return res
 
 
+def mjpeg_input(repeats, p720):
+    """Warm calls on Motion-JPEG AVI input, without and with restart markers, output skipped and written."""
+    import io
+    from PIL import Image
+    fps = 30
+    res = {"mode": "warm calls, Motion-JPEG AVI input", "repeats": repeats, "TRUELY_MJPEG": os.environ.get("TRUELY_MJPEG", ""), "runs": []}
+    for H, W, N, hold in [(360, 640, 960, 20)] + ([(720, 1280, 240, 20)] if p720 else []):
+        uniq = truely_amd.synthetic.synthetic_frames(N // hold, H, W, seed=21)
+        with tempfile.TemporaryDirectory() as td:
+            dst = os.path.join(td, "out.avi")
+            for kind in ("no DRI", "DRI"):
+                src = os.path.join(td, "c.avi")
+                w = video_io.AviMjpegWriter(src, fps, (W, H))
+                # (a tree from before the writer had these two methods -- the parent of the comparison -- has them as _encode / _append)
+                encode, append = getattr(w, "encode_frame", None) or w._encode, getattr(w, "append_encoded", None) or w._append
+                files = []
+                for f in uniq:
+                    if kind == "DRI":
+                        b = io.BytesIO()
+                        Image.fromarray(np.ascontiguousarray(f[:, :, ::-1]), "RGB").save(b, format="JPEG", quality=80, subsampling=2, restart_marker_rows=1)
+                        files.append(b.getvalue())
+                    else:
+                        files.append(encode(f))
+                for i in range(N):
+                    append(files[i // hold])
+                w.release()
+                for out_on in (False, True):
+                    os.environ["TRUELY_WRITE_OUTPUT"] = "1" if out_on else "0"
+                    secs, score = [], None
+                    for k in range(repeats + 1):                  # the first call of a shape is the warm-up
+                        t0 = time.perf_counter()
+                        score = model.run(src, dst)
+                        dt = time.perf_counter() - t0
+                        if os.path.exists(dst):
+                            os.remove(dst)
+                        if k:
+                            secs.append(round(dt, 4))
+                    res["runs"].append({"clip": f"MJPEG {kind} {N} frames {W}x{H}", "output": "written" if out_on else "skipped",
+                                        "file_bytes": os.path.getsize(src), "seconds": secs, "median": round(float(np.median(secs)), 4),
+                                        "min": min(secs), "max": max(secs), "score": int(score)})
+    os.environ.pop("TRUELY_WRITE_OUTPUT", None)
+    return res
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    mj = [a for a in sys.argv[1:] if a.startswith("--mjpeg")]
+    if mj:
+        line = json.dumps(mjpeg_input(int(mj[0].partition("=")[2] or 5), "--p720" in sys.argv))
+        print(line)
+        if args:
+            open(args[0], "w").write(line + "\n")
+        return
     rep = [a for a in sys.argv[1:] if a.startswith("--output-on")]
     if rep:
         os.environ.pop("TRUELY_WRITE_OUTPUT", None)

@@ -16,6 +16,10 @@ class TrlConfig(C.Structure):
                 ("max_faces", C.c_int), ("pnet_mode", C.c_int), ("embed_mode", C.c_int), ("embed_precision", C.c_int)]
 
 
+class TrlJpegdInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "h_samp", "v_samp", "restart_interval", "scan_offset", "supported", "reason")]
+
+
 class TrlError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"libtruely_hip status {status}: {msg}")
@@ -84,6 +88,11 @@ _SIGNATURES = {
     "trl_jpeg_destroy": (C.c_int, [_vp]),
     "trl_jpeg_encode": (C.c_int, [_vp, _vp, _i, C.c_longlong, _vp, C.c_longlong, _vp, _vp]),
     "trl_jpeg_header": (C.c_int, [_i, _i, _i, _vp, C.c_size_t, C.POINTER(_i)]),
+    "trl_jpegd_parse": (C.c_int, [_vp, C.c_size_t, _vp]),
+    "trl_jpegd_create": (C.c_int, [_i, _i, _i, _i, C.c_longlong, C.POINTER(_vp)]),
+    "trl_jpegd_destroy": (C.c_int, [_vp]),
+    "trl_jpegd_debug_poison": (C.c_int, [_vp, _i]),
+    "trl_jpegd_decode": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _vp, C.c_longlong, _vp, _vp]),
     "trl_draw_workspace": (C.c_size_t, [_i, _i]),
     "trl_draw": (C.c_int, [_vp, _i, C.c_longlong, _i, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp]),
 }

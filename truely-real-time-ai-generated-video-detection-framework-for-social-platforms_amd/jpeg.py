@@ -1,4 +1,5 @@
-"""``DeviceJpeg``: the Motion-JPEG encoder of ``trl_jpeg.hip`` behind a small Python object.
+"""``DeviceJpeg`` and ``DeviceJpegDecoder``: the Motion-JPEG encoder of ``trl_jpeg.hip`` and the decoder of ``trl_jpegd.hip``, each
+behind a small Python object.
 
 Each frame's file is byte-identical to Pillow's ``Image.save(format="JPEG", quality=q, subsampling=2)`` of the RGB frame, which is
 what ``AviMjpegWriter`` writes with its Pillow encoder: the device encoder changes how fast ``run()``'s annotated output is
@@ -108,3 +109,111 @@ class DeviceJpeg:
         data = self.host[:total].numpy()
         ends = np.cumsum(sizes)
         return [data[e - s:e].tobytes() for s, e in zip(sizes, ends)]
+
+
+class DeviceJpegDecoder:
+    """The baseline-JPEG decoder of ``trl_jpegd.hip`` behind a small Python object: Motion-JPEG frames to BGR on the GPU, byte for
+    byte what ``np.asarray(Image.open(f).convert("RGB"))[:, :, ::-1]`` gives.
+
+    ``decode(files)``: a list of n JPEG files (``bytes``) -> ``(frames, status)``: a uint8 device tensor (n, H, W, 3) in BGR and a
+    numpy array of n statuses -- 0 decoded on the device, 1 not attempted (progressive, grayscale, another size, ...), 2 the
+    entropy decoder met something irregular.  A frame whose status is not 0 is left unwritten (zero here): the caller decodes it
+    with Pillow.  The object has its own stream, workspace and pinned staging; batches above ``max_frames`` are split.
+
+    ``decode_into(h_arena, d_arena, offsets, sizes, out)`` is the form ``run()`` uses: the files already lie in a pinned host
+    arena and in its device copy; the work is queued on the current stream and the call returns after one synchronisation."""
+
+    def __init__(self, W: int, H: int, device=None, max_frames: int = 32):
+        if device is None:
+            device = torch.cuda.current_device()
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"DeviceJpegDecoder needs a GPU device, got {self.device}")
+        self.W, self.H, self.max_frames = int(W), int(H), int(max_frames)
+        self.lib = _lib.load()
+        self.stream = torch.cuda.Stream(self.device)
+        self.h = None
+        self.max_bytes = 0
+        self._create(self.max_frames * (self.H * self.W * 3 + 65536))
+        self.host = self.dev = None                       # staging of decode(): pinned arena and its device copy
+        self.status = np.zeros(self.max_frames, np.int32)
+
+    def _create(self, max_bytes: int):
+        h = C.c_void_p()
+        _lib.check(self.lib.trl_jpegd_create(self.device.index or 0, self.H, self.W, self.max_frames, int(max_bytes), C.byref(h)))
+        if self.h is not None:
+            self.lib.trl_jpegd_destroy(self.h)
+        self.h, self.max_bytes = h, int(max_bytes)
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.lib.trl_jpegd_destroy(h)
+            self.h = None
+
+    def decode_into(self, h_arena: torch.Tensor, d_arena: torch.Tensor, offsets, sizes, out: torch.Tensor) -> np.ndarray:
+        """Files k = sizes[k] bytes at offsets[k] of ``h_arena`` (host uint8, read during the call) and of ``d_arena`` (its device
+        copy, whose upload is queued on the current stream or finished) -> ``out[k]`` (uint8 device (n, H, W, 3), any stride
+        between frames).  Returns the statuses; frames whose status is not 0 are untouched."""
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        sizes = np.ascontiguousarray(sizes, np.int64)
+        n = len(offsets)
+        if len(sizes) != n or out.shape[0] != n:
+            raise ValueError(f"{n} offsets, {len(sizes)} sizes, {out.shape[0]} output frames")
+        if out.dtype != torch.uint8 or out.dim() != 4 or tuple(out.shape[1:]) != (self.H, self.W, 3) or out.device != self.device:
+            raise ValueError(f"expected uint8 frames (n, {self.H}, {self.W}, 3) on {self.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+        if n and tuple(out.stride()[1:]) != (self.W * 3, 3, 1):
+            raise ValueError("output frames must be dense")
+        if h_arena.dtype != torch.uint8 or d_arena.dtype != torch.uint8 or h_arena.is_cuda or d_arena.device != self.device:
+            raise ValueError("arenas: uint8, one on the host and its copy on the decoder's device")
+        nbytes = min(h_arena.numel(), d_arena.numel())
+        if nbytes > self.max_bytes:
+            self._create(nbytes)
+        status = np.zeros(n, np.int32)
+        stream = torch.cuda.current_stream(self.device)
+        stride = out.stride(0) if n > 1 else self.H * self.W * 3
+        for k in range(0, n, self.max_frames):
+            m = min(self.max_frames, n - k)
+            st = self.status[:m]
+            _lib.check(self._decode(h_arena, d_arena, nbytes, offsets[k:k + m], sizes[k:k + m], m, out[k:k + m], stride, st, stream))
+            status[k:k + m] = st
+        return status
+
+    def _decode(self, h_arena, d_arena, nbytes, offsets, sizes, m, out, stride, st, stream):
+        if m and (int((offsets + sizes).max()) > nbytes or int(offsets.min()) < 0 or int(sizes.min()) < 0):
+            raise ValueError(f"a file lies outside the arena of {nbytes} bytes")     # (the library checks against max_bytes >= nbytes)
+        return self.lib.trl_jpegd_decode(self.h, C.c_void_p(h_arena.data_ptr()), C.c_void_p(d_arena.data_ptr()),
+                                         offsets.ctypes.data_as(C.c_void_p), sizes.ctypes.data_as(C.c_void_p), m,
+                                         C.c_void_p(out.data_ptr()), stride, st.ctypes.data_as(C.c_void_p), C.c_void_p(stream.cuda_stream))
+
+    def decode(self, files):
+        files = list(files)
+        n = len(files)
+        frames = torch.zeros((n, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+        status = np.zeros(n, np.int32)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        for k in range(0, n, self.max_frames):
+            part = files[k:k + self.max_frames]
+            sizes = np.array([len(f) for f in part], np.int64)
+            offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+            total = int(sizes.sum())
+            if self.host is None or self.host.numel() < max(total, 1):
+                cap = max(total + total // 4, 1 << 16)
+                self.host = torch.empty(cap, dtype=torch.uint8).pin_memory()
+                self.dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
+            hn = self.host.numpy()
+            for o, f in zip(offsets, part):
+                hn[o:o + len(f)] = np.frombuffer(f, np.uint8)
+            with torch.cuda.stream(self.stream):
+                self.dev[:total].copy_(self.host[:total], non_blocking=True)
+                status[k:k + len(part)] = self.decode_into(self.host, self.dev, offsets, sizes, frames[k:k + len(part)])
+        frames.record_stream(self.stream)
+        return frames, status
+
+
+def jpeg_info(data: bytes) -> dict:
+    """What the decoder's marker parser finds in one JPEG file (host only, no GPU): ``trl_jpegd_parse`` as a dict."""
+    info = _lib.TrlJpegdInfo()
+    buf = (C.c_ubyte * max(len(data), 1)).from_buffer_copy(data if data else b"\0")
+    _lib.check(_lib.load().trl_jpegd_parse(buf, len(data), C.byref(info)))
+    return {n: getattr(info, n) for n, _ in info._fields_}

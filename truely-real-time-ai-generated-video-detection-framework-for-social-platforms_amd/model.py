@@ -74,6 +74,19 @@ class _RunCtx:
         self.lock = threading.Lock()                      # one run() at a time per engine (service workers are per GPU anyway)
         self.flat, self.flat_dev = [], []                 # the storage: SLOTS pinned byte buffers, one device buffer per engine
         self.capacity = 0                                 # bytes each of them holds
+        self.jpegd: dict = {}                             # (engine index, H, W, frames) -> jpeg.DeviceJpegDecoder
+
+    def decoder(self, j: int, H: int, W: int, frames: int):
+        """Engine j's Motion-JPEG decoder for H x W clips and windows of up to ``frames`` frames, kept between calls (one size at
+        a time: a service that alternates between sizes rebuilds it, as it re-pins its buffers)."""
+        key = (j, H, W, frames)
+        dec = self.jpegd.get(key)
+        if dec is None:
+            from .jpeg import DeviceJpegDecoder
+            for k in [k for k in self.jpegd if k[0] == j]:
+                del self.jpegd[k]
+            dec = self.jpegd[key] = DeviceJpegDecoder(W, H, device=self.engines[0].device, max_frames=frames)
+        return dec
 
     def buffers(self, rows: int, row_bytes: int, yuv: bool, H: int, W: int):
         """Pinned ring of SLOTS windows of ``rows`` frames, one device staging buffer per engine, as (rows, row_bytes) views of
@@ -93,6 +106,7 @@ class _RunCtx:
     def close(self):
         self.flat = self.flat_dev = []
         self.capacity = 0
+        self.jpegd = {}
         self.engines[1].close()
 
 
@@ -101,12 +115,15 @@ class _WindowReader(threading.Thread):
     clips, decoding) overlap the device work of earlier windows.  Containers with fixed-size frames (TRLV, YUV4MPEG2) are read
     with positioned reads straight into pinned memory, several in parallel, and only the frames that are needed: every frame when
     the output is written, the sampled ones otherwise (model.py:46 -- `cap.read()` has to decode them all, a raw container does
-    not).  Other sources go through ``cap.read()``.
+    not).  A source of compressed, independently decodable frames (``compressed``: Motion-JPEG AVI) is read the same way, but
+    what lands in the slot is the needed frames' compressed chunks, back to back: a pinned byte arena that run() uploads and
+    decodes on the device.  Other sources go through ``cap.read()``.
 
     Items on ``full``: (slot, rows, first, nframes, host_frames) per window, an exception, or None at the end of the clip.
-    rows = frames in the slot (sampled frames, or every frame of the window when ``all_rows``)."""
+    rows = frames in the slot (sampled frames, or every frame of the window when ``all_rows``).  For a compressed source the
+    last field is (offsets, sizes, frame indices) of the rows' chunks in the slot."""
 
-    def __init__(self, cap, step: int, win: int, slots_np, all_rows: bool, keep_host: bool, frame_shape):
+    def __init__(self, cap, step: int, win: int, slots_np, all_rows: bool, keep_host: bool, frame_shape, compressed: bool = False):
         super().__init__(name="truely-reader", daemon=True)
         self.cap, self.step, self.win, self.slots_np = cap, step, win, slots_np
         self.all_rows, self.keep_host, self.frame_shape = all_rows, keep_host, frame_shape
@@ -115,10 +132,11 @@ class _WindowReader(threading.Thread):
         self.frame_count = 0
         self.stop = False
         self.random = bool(getattr(cap, "stride", 0)) and hasattr(cap, "frame_offset")
+        self.compressed = compressed
 
     def run(self):
         try:
-            (self._run_random if self.random else self._run_sequential)()
+            (self._run_compressed if self.compressed else self._run_random if self.random else self._run_sequential)()
             self.full.put(None)
         except BaseException as e:  # noqa: BLE001 - surfaced by the consumer
             self.full.put(e)
@@ -171,6 +189,33 @@ class _WindowReader(threading.Thread):
         finally:
             pool.shutdown(wait=True)
 
+    def _run_compressed(self):
+        import concurrent.futures
+        cap, step, win = self.cap, self.step, self.win
+        n, per = cap.n, win * step
+        pool = concurrent.futures.ThreadPoolExecutor(max_workers=4, thread_name_prefix="truely-read")
+        try:
+            for first in range(0, n, per):
+                slot = self._slot()
+                if slot is None:
+                    return
+                nfr = min(per, n - first)
+                idx = list(range(first, first + nfr)) if self.all_rows else list(range(first, first + nfr, step))
+                arena = self.slots_np[slot].reshape(-1)
+                budget = arena.size // max(1, len(idx))   # (a slot row holds a raw frame: no JPEG of that frame is larger in practice)
+                # a chunk above the budget gets no room: the device decoder then does not attempt it and the host decodes it
+                sizes = np.array([cap.frames[i][1] if cap.frames[i][1] <= budget else 0 for i in idx], np.int64)
+                offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+                got = list(pool.map(lambda k: cap.read_chunk(idx[k], arena[offsets[k]:offsets[k] + sizes[k]]) if sizes[k] else 0,
+                                    range(len(idx))))
+                for k, g in enumerate(got):
+                    if g < sizes[k]:                      # the file ends inside the chunk: what is there is what Pillow would be given
+                        sizes[k] = g
+                self.frame_count = first + nfr
+                self.full.put((slot, len(idx), first, nfr, (offsets, sizes, idx)))
+        finally:
+            pool.shutdown(wait=True)
+
     def _run_sequential(self):
         cap, step, win = self.cap, self.step, self.win
         per = win * step
@@ -213,6 +258,15 @@ def run(video_path_one: str, video_path_two: str, engine: Engine | None = None) 
     are drawn on the device (``annotate.annotate_device``) and the frames are encoded where they lie: only the JPEG files come
     back.  Otherwise (raw ``.trlv`` sink, OpenCV, Pillow encoder, ``TRUELY_DRAW=host``) the writer thread draws on host frames.
 
+    Motion-JPEG AVI input (the one compressed input this build opens without OpenCV) stays compressed until it is on the device:
+    the reader thread reads the chunks of the frames a window needs by position -- every frame when the output is written, the
+    sampled ones otherwise -- into a pinned arena, the arena is uploaded and decoded on the window's stream
+    (``jpeg.DeviceJpegDecoder``: the frames Pillow decodes, byte for byte), and from there the window goes on like the device
+    paths above.  A frame the device decoder does not attempt (progressive, grayscale, ...) or finds irregular is decoded with
+    Pillow and copied into place; one that Pillow cannot decode either, or whose size is not the header's, ends the clip there
+    as a failed ``cap.read()`` does.  (With the output skipped only sampled frames are looked at, so a damaged frame between
+    them goes unnoticed, as in a raw container.)
+
     ``engine`` (optional, not in the reference's signature): the context to run on -- a multi-GPU service keeps one per device
     (service.AnalysisService(gpus=[...])); default: the process-wide engine on the current device.  The second context, the
     streams and the pinned buffers are created on the first call and cached on the engine.
@@ -221,7 +275,8 @@ def run(video_path_one: str, video_path_two: str, engine: Engine | None = None) 
     (benchmarking only: the server requires a non-empty file, server.py:612-627); TRUELY_JPEG=pillow encodes the Motion-JPEG
     output with Pillow on the writer thread instead of on the engine's GPU (the same bytes, slower); TRUELY_DRAW=host draws the
     annotations on the writer thread and sends host frames to the device encoder (the same bytes; the path before the device
-    drawing existed)."""
+    drawing existed); TRUELY_MJPEG=pillow decodes Motion-JPEG input with Pillow, frame by frame on the reader thread (the same
+    frames; the path before the device decoder existed, and the escape hatch)."""
     start_time = time.time()
     # model.py:20-22
     if not os.path.exists(video_path_one) or os.path.getsize(video_path_one) == 0:
@@ -275,12 +330,16 @@ def _run_locked(ctx: _RunCtx, cap, fps: int, width: int, height: int, video_path
     # frames stay on the device from the upload to the encoder: the sink encodes there and nothing asks for the host drawing
     on_dev = (write_out and video_io.encodes_on_device(video_path_two, jpeg_dev)
               and os.environ.get("TRUELY_DRAW", "device") != "host")
-    all_rows = write_out and (yuv or on_dev)              # every frame of a window goes to the device (4:2:0: converted there)
+    mjpeg = getattr(cap, "compressed", None) == "mjpeg" and os.environ.get("TRUELY_MJPEG", "device") != "pillow"
+    all_rows = write_out and (yuv or on_dev or mjpeg)     # every frame of a window goes to the device (4:2:0: converted there,
+                                                          # Motion-JPEG: decoded there)
     rows = win * step if all_rows else win
     pinned, pinned_np, raw_dev = ctx.buffers(rows, row_bytes, yuv, height, width)
     sink = video_io.open_writer(video_path_two, fps, (width, height), device=jpeg_dev) if write_out else None
     writer = video_io.AsyncWriter(sink, annotate=os.environ.get("TRUELY_ANNOTATE", "1") != "0", depth=4 * BATCH * step if on_dev else 64)
-    reader = _WindowReader(cap, step, win, pinned_np, all_rows, keep_host=write_out and not all_rows, frame_shape=(height, width, 3))
+    reader = _WindowReader(cap, step, win, pinned_np, all_rows, keep_host=write_out and not all_rows, frame_shape=(height, width, 3),
+                           compressed=mjpeg)
+    ended = [None]                                        # Motion-JPEG: the frame that could not be decoded, where the clip ends
     for k in range(len(pinned)):
         reader.free.put((k, None))
     state = eng.drift_state()
@@ -309,6 +368,26 @@ def _run_locked(ctx: _RunCtx, cap, fps: int, width: int, height: int, video_path
         for k in range(nfr):
             writer.put(frames[k], notes.get(k))
 
+    def decode_window(j, slot, nrows, first, nfr, chunks):
+        """Under engine j's stream: the window's compressed arena -> device -> BGR frames (nrows, H, W, 3), with Pillow for the
+        frames the device decoder leaves.  Returns (frames, rows, frames of the clip they cover): fewer than given when a frame
+        cannot be decoded at all -- the clip ends there (``ended``)."""
+        offsets, sizes, idx = chunks
+        total = int(offsets[-1] + sizes[-1])
+        h_arena = pinned[slot].view(-1)
+        d_arena = raw_dev[j].view(-1)
+        d_arena[:total].copy_(h_arena[:total], non_blocking=True)
+        bgr = torch.empty((nrows, height, width, 3), dtype=torch.uint8, device=dev)
+        status = ctx.decoder(j, height, width, rows).decode_into(h_arena, d_arena, offsets, sizes, bgr)   # synchronises stream j
+        reader.free.put((slot, None))                     # the upload has finished: the reader may refill the slot
+        for k in np.nonzero(status)[0]:
+            frame = cap.decode_host(cap.read_chunk(idx[k]), idx[k])
+            if frame is None:
+                ended[0] = idx[k]
+                return bgr[:k], int(k), idx[k] - first
+            bgr[k].copy_(torch.from_numpy(frame))
+        return bgr, nrows, nfr
+
     ov = Overlapped(ctx.engines, on_result=on_result, streams=ctx.streams, embed_group=1 if write_out else 4, collect=False)
     reader.start()
     # Whatever fails in the loop -- an allocation failure, a damaged clip -- the reader and writer threads must end and both
@@ -322,6 +401,28 @@ def _run_locked(ctx: _RunCtx, cap, fps: int, width: int, height: int, video_path
             if isinstance(item, BaseException):
                 raise item
             slot, nrows, first, nfr, host = item
+            if mjpeg:
+                j = ov.count % ov.F                       # the engine Overlapped queues this window on
+                with torch.cuda.stream(ctx.streams[j]):
+                    bgr, nrows, nfr = decode_window(j, slot, nrows, first, nfr, host)
+                if nrows > 0:
+                    def decoded(j, bgr=bgr, wi=wi, first=first, nfr=nfr):
+                        """Under engine j's stream, the one the window was decoded on: the sampled gather the cascade reads, and
+                        the event behind which the writer may draw on the window's frames."""
+                        sampled = bgr[::step].contiguous() if all_rows else bgr
+                        done = None
+                        if on_dev:
+                            done = torch.cuda.Event()
+                            done.record(torch.cuda.current_stream(dev))
+                        meta[wi] = (first, nfr, bgr if write_out else None, done)
+                        return sampled
+                    ov.push(decoded)
+                    wi += 1
+                if ended[0] is not None:
+                    reader.stop = True
+                    reader.free.put(None)
+                    break
+                continue
 
             def batch(j, slot=slot, nrows=nrows, wi=wi, first=first, nfr=nfr, host=host):
                 """Under engine j's stream: pinned window -> device, (4:2:0: colour conversion), the sampled BGR batch."""
@@ -371,7 +472,7 @@ def _run_locked(ctx: _RunCtx, cap, fps: int, width: int, height: int, video_path
     reader.join()
     cap.release()
     writer.close()
-    frame_count = reader.frame_count
+    frame_count = reader.frame_count if ended[0] is None else ended[0]
     if frame_count == 0:    # model.py:83-85
         print("Error: No frames were processed")
         return 0

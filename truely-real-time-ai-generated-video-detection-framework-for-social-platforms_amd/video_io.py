@@ -9,7 +9,9 @@ the build environment, so two back-ends exist behind the same tiny interface:
   tests and the benchmark.  NV12 clips take the device ingest path of ``model.run`` (SURVEY section 8(f) rank 1);
 * Motion-JPEG in AVI (``AviMjpegWriter`` / ``AviMjpegReader``): the annotated OUTPUT when OpenCV is absent -- a bounded standard
   file instead of raw frames, encoded by Pillow's libjpeg or, byte-identical, by the HIP encoder (jpeg.DeviceJpeg) -- and the one
-  compressed INPUT this build decodes by itself (Pillow);
+  compressed INPUT this build decodes by itself: ``run()`` reads the chunks of the frames it needs by position and decodes them
+  on the GPU (jpeg.DeviceJpegDecoder: baseline 4:2:0 / 4:2:2 / 4:4:4, byte-identical to Pillow), with Pillow for any frame
+  the device decoder does not attempt and for ``cap.read()``;
 * YUV4MPEG2 (``.y4m``, 4:2:0 progressive): the uncompressed interchange format every decoder can emit
   (``ffmpeg -i clip.mp4 -pix_fmt yuv420p clip.y4m``).  Planes are repacked to NV12 on the fly and take the same device ingest.
 ``AsyncWriter`` is the decoupled, skippable annotated-output stage: drawing and encoding run on their
@@ -255,6 +257,15 @@ class AviMjpegWriter:
         self.max_chunk = max(self.max_chunk, len(data))
         self.n += 1
 
+    def encode_frame(self, frame) -> bytes:
+        """One BGR frame -> the JPEG file this writer's Pillow encoder makes of it (nothing is appended)."""
+        return self._encode(frame)
+
+    def append_encoded(self, data: bytes):
+        """Append one already encoded JPEG file as the next frame's chunk (tools and tests that build clips from files of their
+        own: restart markers, progressive or damaged frames)."""
+        self._append(data)
+
     def _flush_device(self):
         if self.pending:
             for data in self.dev_enc.encode(self.batch[:self.pending]):
@@ -307,8 +318,11 @@ class AviMjpegWriter:
 class AviMjpegReader:
     """Reads the Motion-JPEG AVI files ``AviMjpegWriter`` (or any encoder: ``ffmpeg -c:v mjpeg out.avi``) produces: walks the
     'movi' list, decodes each '00dc' / '00db' chunk with Pillow -> BGR frames like ``cap.read()``.  The one COMPRESSED input
-    this build can decode without OpenCV."""
+    this build can decode without OpenCV.  JPEG frames are independent of each other: ``frames`` indexes the chunks,
+    ``read_chunk(i)`` reads one by position, and ``run()`` decodes them on the GPU (jpeg.DeviceJpegDecoder, the same bytes as
+    Pillow's) -- only the frames it needs; ``decode_host`` is the Pillow decoder for the frames the device does not attempt."""
     pixfmt = "bgr"
+    compressed = "mjpeg"                             # frames are independently decodable compressed chunks
 
     def __init__(self, path):
         self.f = open(path, "rb")
@@ -371,25 +385,48 @@ class AviMjpegReader:
     def isOpened(self):
         return True
 
-    def read(self):
+    def read_chunk(self, i: int, dst=None):
+        """Frame i's compressed chunk by a positioned read (thread-safe, independent of ``read()``'s position): the bytes, or with
+        ``dst`` (a writable buffer of at least the chunk's size) the number of bytes read into it."""
+        off, size = self.frames[i]
+        fd = self.f.fileno()
+        if dst is None:
+            return os.pread(fd, size, off)
+        mv, got = memoryview(dst)[:size], 0
+        while got < size:
+            k = os.preadv(fd, [mv[got:]], off + got)
+            if k <= 0:
+                break
+            got += k
+        return got
+
+    def decode_host(self, data, i: int):
+        """Frame i's chunk -> BGR frame with Pillow, or None (with a warning) for a chunk that cannot be decoded or whose size
+        is not the header's: the clip ends there."""
         from PIL import Image
         import io
+        try:
+            im = Image.open(io.BytesIO(data)).convert("RGB")
+        except Exception as e:  # noqa: BLE001 - a damaged frame ends the clip like a failed cap.read() -- but not silently
+            print(f"Warning: frame {i} of {self.n} cannot be decoded ({e}): the clip is analysed up to it")
+            return None
+        a = np.asarray(im, np.uint8)
+        if a.shape[0] != self.height or a.shape[1] != self.width:
+            print(f"Warning: frame {i} of {self.n} is {a.shape[1]}x{a.shape[0]}, the header says {self.width}x{self.height}: "
+                  f"the clip is analysed up to it")
+            return None
+        return np.ascontiguousarray(a[:, :, ::-1])
+
+    def read(self):
         if self.i >= self.n:
             return False, None
         off, size = self.frames[self.i]
         self.f.seek(off)
-        try:
-            im = Image.open(io.BytesIO(self.f.read(size))).convert("RGB")
-        except Exception as e:  # noqa: BLE001 - a damaged frame ends the clip like a failed cap.read() -- but not silently
-            print(f"Warning: frame {self.i} of {self.n} cannot be decoded ({e}): the clip is analysed up to it")
+        frame = self.decode_host(self.f.read(size), self.i)
+        if frame is None:
             return False, None
         self.i += 1
-        a = np.asarray(im, np.uint8)
-        if a.shape[0] != self.height or a.shape[1] != self.width:
-            print(f"Warning: frame {self.i - 1} of {self.n} is {a.shape[1]}x{a.shape[0]}, the header says {self.width}x{self.height}: "
-                  f"the clip is analysed up to it")
-            return False, None
-        return True, np.ascontiguousarray(a[:, :, ::-1])
+        return True, frame
 
     def release(self):
         self.f.close()

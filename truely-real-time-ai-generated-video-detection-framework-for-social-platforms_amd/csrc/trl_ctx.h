@@ -106,6 +106,7 @@ struct trl_ctx {
     } pend;
     uint32_t* pyr_tab = nullptr;     // pyramid bin-edge tables for the last (H, W)
     int pyr_tab_H = 0, pyr_tab_W = 0;
+    int pyr_row_bands = 0;           // trl_debug_option "pyr_row_bands": > 0 forces the row bands of the streaming pyramid pass (tests)
     // one-pass kernel for the finest levels (k_pyramid_fine): ownership table inside pyr_tab, source tile shape; nlev == 0: not usable for this shape
     struct { int nlev = 0, own0 = 0, band_cols = 0, strip_rows = 0, n_bands = 0, n_strips = 0; } pyr_fine;
     // what the last build_pyramid chose per level (trl_debug_pyramid_plan): rows of TRL_PYR_PLAN_COLS ints; L = 0 after a refused call

@@ -16,6 +16,7 @@
 
 typedef unsigned u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes at dword alignment
 struct __attribute__((packed, aligned(4))) u32x3_a4 { unsigned x, y, z; };
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));            // two 16-bit sums of a dword: packed adds, no carry between them
 
 namespace {
 
@@ -76,6 +77,12 @@ __device__ __forceinline__ float pyr_div(float a, float b, float r) {
     const float q0 = a * r;
     const float e = __builtin_fmaf(-b, q0, a);
     return __builtin_fmaf(e, r, q0);
+}
+// s / kh / kw, normalised; r1 = RN(1/kh), r2 = RN(1/kw) when `fast`
+__device__ __forceinline__ float pyr_norm(unsigned s, float fkh, float fkw, float r1, float r2, bool fast) {
+    const float a = (float)s;
+    const float q = fast ? pyr_div(pyr_div(a, fkh, r1), fkw, r2) : a / fkh / fkw;
+    return (q - 127.5f) * 0.0078125f;
 }
 __device__ __forceinline__ float pyr_norm(unsigned s, int kh, int kw, const PyrBins& g) {
     const float a = (float)s, fkh = (float)kh, fkw = (float)kw;
@@ -440,209 +447,291 @@ __global__ __launch_bounds__(192) void k_pyramid_fine(const uint8_t* __restrict_
 //   * an owner -- a workgroup or a wave, see OwnBlock / OwnWave -- takes a unit of the frame (rows [R0,R1) x a segment of columns) and
 //     walks its rows top down; a lane holds 16 or 20 consecutive bytes of the row (one dword-aligned 16-byte load + 1 or 2 dwords,
 //     re-aligned by a scalar shift);
-//   * per level it keeps the column sums of the current output row's bin in registers (packed 16-bit, one per byte column);
-//     at the bin's last source row the sums go to LDS, the horizontal bins are reduced, normalised (pyr_norm) and stored,
-//     and the accumulators restart (with the current row when consecutive bins share it);
+//   * it keeps ONE running sum P of the rows walked so far (packed 16-bit, one field per byte column, updated once per row whatever
+//     the number of levels) and, per level, the snapshot S_l = P before the current bin's first row (without that row when the bin
+//     starts on the row that ends its predecessor).  At the bin's last row its column sums are P - S_l per field.  The fields wrap
+//     (a band of 290 rows of 255s overflows 16 bits) and the difference is still exact, because a streamed bin's column sum is below
+//     2^16: launch_coarse refuses khmax > 256 -- the limit that test_packed_column_sums_at_the_256_row_limit pins now bounds the
+//     wrapped running sum as well;
+//   * the column sums go to an LDS strip of 16-bit words; 2^gs lanes share an output pixel, each issues the reads of four of the
+//     bin's columns before its first add, and the group is summed with DPP adds; normalised (pyr_norm) and stored.  The block-wide
+//     pass alternates two strips, so one barrier per flush suffices;
+//   * the per-level state lives in lanes (lane L = level L), not in scalar registers: a row costs two vector compares whatever
+//     the number of levels, and the flush is written once per row slot (3 k instructions instead of 25 k);
 //   * a unit computes the bins that START inside it and reads on past its end until they are complete (no atomics).
 // Integer sums in any order are exact, so the result is bit-identical to the per-level kernels (tests: every level, 180p..4K).
 constexpr int SMAXL = 12;               // coarse levels per launch
 constexpr int SBYTES = 4096;            // bytes of a source row a workgroup covers (256 threads x 16)
 constexpr int SW_BYTES = 1280;          // bytes of a source row a wave covers (64 lanes x 20)
-constexpr int STAB = 6144;              // bin-edge words of the coarse levels kept in LDS (rows + columns of every level)
+constexpr int STAB = 6144;              // most bin-edge words of a launch's levels (rows + columns) kept in LDS; a launch allocates its own
 struct PyrStreamArgs {
     int H, W, n_frames, nlev, rows_per_band, cols_per_band, row_bands, col_bands;
+    int tab0, tab_words;                // the span of the device table that holds the launch's levels
     long long pyr_stride;
     PyrBins lv[SMAXL];
 };
 
-// Who owns a unit of the pass (a band of rows x a segment of BYTES source bytes per row) and the LDS strip its bin rows are flushed
-// through.  A lane holds DW dwords of the row (+ 1 for the re-alignment); a workgroup holds UNITS units.
-//   OwnBlock  the workgroup: one unit covers the whole row of a frame up to 1,365 px wide; the flush is bracketed by block barriers.
+// Who owns a unit of the pass (a band of rows x a segment of BYTES source bytes per row) and the STRIPS LDS strips its bin rows are
+// flushed through.  A lane holds DW dwords of the row (+ 1 for the re-alignment); a workgroup holds UNITS units.
+//   OwnBlock  the workgroup: one unit covers the whole row of a frame up to 1,365 px wide; a block barrier between a flush's strip
+//             writes and its reads, and two strips in turn instead of a second one.
 //   OwnWave   one wave, which never talks to another (frames wider than one 4096-byte band: 1080p, 4K).  The segment is 64 x 20 =
 //             1280 bytes = 426 pixels of which the last kwmax overlap the next segment, so that every bin that STARTS in the segment
-//             is covered by the wave's own loads; LDS operations of one wave execute in order: no barrier, and row quantities are
-//             pinned to SGPRs.  (At 720p, where both apply, the block-wide pass is faster -- 0.63 vs 1.11 ms: every wave pays all
-//             ~165 flush round trips alone -- so it keeps the narrow frames.)
+//             is covered by the wave's own loads; LDS operations of one wave execute in order: no barrier, one strip.  (At 720p,
+//             where both apply, the block-wide pass was the faster one when both were last compared -- 0.63 vs 1.11 ms: every wave
+//             pays all ~165 flush round trips alone -- so it keeps the narrow frames.)
 struct OwnBlock {
-    static constexpr int LANES = 256, DW = 4, UNITS = 1, BYTES = SBYTES;
+    static constexpr int LANES = 256, DW = 4, UNITS = 1, BYTES = SBYTES, STRIPS = 2;
     static __device__ __forceinline__ int lane() { return threadIdx.x; }
     static __device__ __forceinline__ int slot() { return 0; }                   // unit of the workgroup
     static __device__ __forceinline__ void sync() { __syncthreads(); }
-    static __device__ __forceinline__ int uni(int x) { return x; }
 };
 struct OwnWave {
-    static constexpr int LANES = 64, DW = 5, UNITS = 4, BYTES = SW_BYTES;
+    static constexpr int LANES = 64, DW = 5, UNITS = 4, BYTES = SW_BYTES, STRIPS = 1;
     static __device__ __forceinline__ int lane() { return threadIdx.x & 63; }
     static __device__ __forceinline__ int slot() { return __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6); }
     static __device__ __forceinline__ void sync() { __builtin_amdgcn_wave_barrier(); }
-    static __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 };
+
+extern __shared__ uint4 stream_lds[];
+template <class Own> constexpr int stream_strip_words() { return Own::UNITS * Own::STRIPS * Own::BYTES; }   // 16-bit words
+// sums of 2, 4, 8 and 16 neighbouring lanes: s + the value of the lane a DPP pattern names
+template <int CTRL> __device__ __forceinline__ unsigned dpp_add(unsigned s) {
+    return s + (unsigned)__builtin_amdgcn_update_dpp(0, (int)s, CTRL, 0xF, 0xF, false);
+}
 
 template <int NL, class Own>
 __global__ __launch_bounds__(256) void k_pyramid_stream(const uint8_t* __restrict__ frames, PyrStreamArgs a, const uint32_t* __restrict__ gtab,
                                                         PyrPx* __restrict__ pyr) {
     constexpr int DW = Own::DW, LANES = Own::LANES;
     static_assert(Own::BYTES == 4 * DW * LANES && Own::UNITS * LANES == 256, "a lane's dwords tile the segment, the units the workgroup");
-    __shared__ unsigned colbuf_all[Own::UNITS * Own::BYTES];   // one word per byte column of a unit's segment
-    __shared__ uint32_t tab[STAB];          // the levels' edge tables, re-based: level l rows at ty0[l], columns at tx0[l]
+    // dynamic LDS: per unit STRIPS strips of one 16-bit word per byte column of its segment, then the levels' edge tables, re-based
+    // (a level's rows at its ty0, its columns at its tx0): as many words as the launch's levels have rows and columns
+    unsigned short* const strips = reinterpret_cast<unsigned short*>(stream_lds);
+    uint32_t* const tab = reinterpret_cast<uint32_t*>(strips + stream_strip_words<Own>());
     const int tid = threadIdx.x, lane = Own::lane(), slot = Own::slot();
     const int f = blockIdx.y;
     const int row_bytes = a.W * 3;
     const long long fbase = (long long)f * a.H * row_bytes;
     const long long last_dw = ((long long)a.n_frames * a.H * row_bytes - 1) >> 2;
     const uint32_t* base32 = reinterpret_cast<const uint32_t*>(frames);
-    // edge tables of the handled levels -> LDS (a flush would otherwise end in a dependent global load)
-    int ty0[NL], tx0[NL];
-    {
-        int pos = 0;
-#pragma unroll
-        for (int l = 0; l < NL; l++) {
-            ty0[l] = tx0[l] = 0;
-            if (l < a.nlev) {
-                const PyrBins& g = a.lv[l];
-                ty0[l] = pos; tx0[l] = pos + g.h;
-                for (int i = tid; i < g.h; i += 256) tab[pos + i] = gtab[g.ytab0 + i];
-                for (int i = tid; i < g.w; i += 256) tab[pos + g.h + i] = gtab[g.xtab0 + i];
-                pos += g.h + g.w;
-            }
-        }
-    }
+    // edge tables of the handled levels -> LDS (a flush would otherwise end in a dependent global load): one flat copy of the span
+    // that holds them, every load in flight at once
+    for (int i = tid; i < a.tab_words; i += 256) tab[i] = gtab[a.tab0 + i];
     __syncthreads();                                     // (OwnWave: the only block barrier, from here on the waves are on their own)
     const int unit = blockIdx.x * Own::UNITS + slot;     // (row band, column segment)
     if (Own::UNITS > 1 && unit >= a.row_bands * a.col_bands) return;
     const int rb = unit / a.col_bands, cb = unit - rb * a.col_bands;
     const int R0 = rb * a.rows_per_band, R1 = (R0 + a.rows_per_band < a.H) ? R0 + a.rows_per_band : a.H;
     const int C0 = cb * a.cols_per_band, C1 = (C0 + a.cols_per_band < a.W) ? C0 + a.cols_per_band : a.W;
-    unsigned* colbuf = colbuf_all + slot * Own::BYTES;
+    unsigned short* const colbuf = strips + slot * Own::STRIPS * Own::BYTES;
+    int flip = 0;                                        // OwnBlock: the strip the next flush goes through
 
-    // per level (all uniform): owned output rows [j, jend), owned output columns [ox0, ox1), current bin rows [ys, ye)
-    int j[NL], jend[NL], ys[NL], ye[NL], ox0[NL], ox1[NL];
-    int yend = R0;
-#pragma unroll
-    for (int l = 0; l < NL; l++) {
-        j[l] = jend[l] = 0; ys[l] = ye[l] = 0x7fffffff; ox0[l] = ox1[l] = 0;
-        if (l < a.nlev) {
-            const PyrBins& g = a.lv[l];
-            auto first_at_or_after = [&](int tab0, int n_out, int n_in, int pos) {   // first bin whose start >= pos
-                if (pos >= n_in) return n_out;
-                int q = (int)(((long long)pos * n_out + n_in - 1) / n_in);
-                if (q > n_out) q = n_out;
-                while (q > 0 && (int)(tab[tab0 + q - 1] & 0xFFFF) >= pos) q--;
-                while (q < n_out && (int)(tab[tab0 + q] & 0xFFFF) < pos) q++;
-                return q;
-            };
-            j[l] = Own::uni(first_at_or_after(ty0[l], g.h, a.H, R0));
-            jend[l] = Own::uni(first_at_or_after(ty0[l], g.h, a.H, R1));
-            ox0[l] = Own::uni(first_at_or_after(tx0[l], g.w, a.W, C0));
-            ox1[l] = Own::uni(first_at_or_after(tx0[l], g.w, a.W, C1));
-            if (j[l] < jend[l] && ox0[l] < ox1[l]) {
-                const uint32_t t0 = tab[ty0[l] + j[l]], t1 = tab[ty0[l] + jend[l] - 1];
-                ys[l] = Own::uni((int)(t0 & 0xFFFF)); ye[l] = Own::uni((int)(t0 >> 16));
-                const int e1 = Own::uni((int)(t1 >> 16));
-                yend = e1 > yend ? e1 : yend;
-            } else {
-                j[l] = jend[l];
-            }
+    // Level state lives in LANES: lane L of every wave holds the quantities of level L (all waves of a workgroup the same values), so
+    // that a row costs two vector compares, not two scalar tests per level, and the flush below exists once per row slot, for a level
+    // index read from the compare's mask.  Per level: owned output rows [j, jend), owned output columns [ox0, ox1), current bin rows
+    // [ys, ye), gs = log2 of the lanes that share one output pixel of a flush, table offsets, and what normalising needs (as VALUES: a
+    // per-lane choice between two members of the argument block compiles to a choice of address and a global load per channel).
+    const int L = threadIdx.x & 63;
+    const bool has = L < a.nlev;
+    const PyrBins& gl = a.lv[has ? L : 0];
+    const int v_ty0 = gl.ytab0 - a.tab0, v_tx0 = gl.xtab0 - a.tab0, v_w = gl.w, v_pix0 = gl.pix0, v_khA = gl.khA, v_kwA = gl.kwA,
+              v_fast = gl.fastdiv;
+    const float v_rkh0 = gl.rkh[0], v_rkh1 = gl.rkh[1], v_rkw0 = gl.rkw[0], v_rkw1 = gl.rkw[1];
+    int v_j = 0, v_jend = 0, v_ys = 0x7fffffff, v_ye = 0x7fffffff, v_ox0 = 0, v_ox1 = 0, v_gs = 0, v_e1 = R0;
+    if (has) {
+        auto first_at_or_after = [&](int tab0, int n_out, int n_in, int pos) {   // first bin whose start >= pos
+            if (pos >= n_in) return n_out;
+            int q = (int)(((long long)pos * n_out + n_in - 1) / n_in);
+            if (q > n_out) q = n_out;
+            while (q > 0 && (int)(tab[tab0 + q - 1] & 0xFFFF) >= pos) q--;
+            while (q < n_out && (int)(tab[tab0 + q] & 0xFFFF) < pos) q++;
+            return q;
+        };
+        v_j = first_at_or_after(v_ty0, gl.h, a.H, R0);
+        v_jend = first_at_or_after(v_ty0, gl.h, a.H, R1);
+        v_ox0 = first_at_or_after(v_tx0, gl.w, a.W, C0);
+        v_ox1 = first_at_or_after(v_tx0, gl.w, a.W, C1);
+        while (v_gs < 4 && ((v_ox1 - v_ox0) << (v_gs + 1)) <= LANES && (2 << v_gs) <= gl.kwA) v_gs++;   // within a DPP row
+        if (v_j < v_jend && v_ox0 < v_ox1) {
+            const uint32_t t0 = tab[v_ty0 + v_j], t1 = tab[v_ty0 + v_jend - 1];
+            v_ys = (int)(t0 & 0xFFFF); v_ye = (int)(t0 >> 16);
+            v_e1 = (int)(t1 >> 16);
+        } else {
+            v_j = v_jend;
         }
     }
+    auto rl = [](int v, int l) { return __builtin_amdgcn_readlane(v, l); };
+    auto rlf = [](float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); };
+    int yend = R0;
+    for (int l = 0; l < a.nlev; l++) { const int e1 = rl(v_e1, l); yend = e1 > yend ? e1 : yend; }
     if (unit == 0) {                                     // zero the 64-pixel padding behind each level once per frame
-#pragma unroll
-        for (int l = 0; l < NL; l++)
-            if (l < a.nlev) {
-                const PyrBins& g = a.lv[l];
-                for (int p = g.h * g.w + lane; p < g.pix_pad; p += LANES)
-                    pyr_store(pyr + ((long long)f * a.pyr_stride + g.pix0 + p), make_float4(0.f, 0.f, 0.f, 0.f));
-            }
+        for (int l = 0; l < a.nlev; l++) {
+            const PyrBins& g = a.lv[l];
+            for (int p = g.h * g.w + lane; p < g.pix_pad; p += LANES)
+                pyr_store(pyr + ((long long)f * a.pyr_stride + g.pix0 + p), make_float4(0.f, 0.f, 0.f, 0.f));
+        }
     }
     if (yend <= R0) return;
 
-    unsigned ev[NL][DW], od[NL][DW];        // packed 16-bit column sums: bytes 0,2 / 1,3 of each of the lane's DW dwords
+    // packed 16-bit column sums, bytes 0,2 / 1,3 of each of the lane's DW dwords: the running sum of every row walked so far and, per
+    // level, its value before the current bin's first row (fields wrap on their own: v_pk_add_u16 / v_pk_sub_u16)
+    u16x2 pe[DW], po[DW], se[NL][DW], so[NL][DW];
+#pragma unroll
+    for (int d = 0; d < DW; d++) { pe[d] = 0; po[d] = 0; }
 #pragma unroll
     for (int l = 0; l < NL; l++)
 #pragma unroll
-        for (int d = 0; d < DW; d++) { ev[l][d] = 0; od[l][d] = 0; }
+        for (int d = 0; d < DW; d++) { se[l][d] = 0; so[l][d] = 0; }
 
     // one source row: this lane's 4*DW bytes at byte offset C0*3 + 4*DW*lane of row y (+ the dword behind them for the re-alignment)
+    // The SAME memory instructions for every lane and row, issued unconditionally: the compiler counts the loads in flight behind
+    // the row it waits for only when every path issues the same number (a conditional or two-shaped load made it wait for all but
+    // the newest row).  A lane whose window would end past the frame buffer moves it back to end there and shifts the dwords up
+    // again when the row is consumed (rows at the very end of the last frame: `tail`).
+    const long long lim_dw = last_dw - DW > 0 ? last_dw - DW : 0;
     auto load_row = [&](int y, unsigned (&w)[DW + 1], unsigned& sh) {
         const int yy = y < a.H ? y : a.H - 1;                                    // rows past the frame are never accumulated
         const long long o = fbase + (long long)yy * row_bytes + (long long)C0 * 3;   // scalar
         sh = (unsigned)(o & 3);
-        const long long dw = (o >> 2) + DW * lane;
-        if (dw + DW <= last_dw) {
-            const u32x4_a4 v4 = *reinterpret_cast<const u32x4_a4*>(base32 + dw);
-            w[0] = v4[0]; w[1] = v4[1]; w[2] = v4[2]; w[3] = v4[3];
+        long long dw = (o >> 2) + DW * lane;
+        dw = dw < lim_dw ? dw : lim_dw;
+        const u32x4_a4 v4 = *reinterpret_cast<const u32x4_a4*>(base32 + dw);
+        w[0] = v4[0]; w[1] = v4[1]; w[2] = v4[2]; w[3] = v4[3];
 #pragma unroll
-            for (int k = 4; k <= DW; k++) w[k] = base32[dw + k];
-        } else {
+        for (int k = 4; k <= DW; k++) w[k] = base32[dw + k];
+    };
+    auto fix_tail = [&](int y, unsigned (&w)[DW + 1]) {
+        const int yy = y < a.H ? y : a.H - 1;
+        const long long dw0 = (fbase + (long long)yy * row_bytes + (long long)C0 * 3) >> 2;   // scalar
+        if (dw0 + DW * (LANES - 1) <= lim_dw) return;                                        // uniform: no lane moved its window
+        const long long over = dw0 + DW * lane - lim_dw;                        // dwords the window was moved back by
 #pragma unroll
-            for (int k = 0; k <= DW; k++) w[k] = base32[dw + k <= last_dw ? dw + k : last_dw];
+        for (int m = 1; m <= DW; m++)
+            if (over == m) {
+#pragma unroll
+                for (int k = 0; k + m <= DW; k++) w[k] = w[k + m];              // (what lies past the buffer is past the frame: unused)
+            }
+    };
+    // the row's bytes 0,2 / 1,3 of each dword, re-aligned to the segment's first byte
+    auto unpack = [&](int y, unsigned (&w)[DW + 1], unsigned sh, u16x2 (&re)[DW], u16x2 (&ro)[DW]) {
+        fix_tail(y, w);
+#pragma unroll
+        for (int d = 0; d < DW; d++) {
+            const unsigned v = __builtin_amdgcn_alignbyte(w[d + 1], w[d], sh);
+            re[d] = __builtin_bit_cast(u16x2, v & 0x00FF00FFu); ro[d] = __builtin_bit_cast(u16x2, (v >> 8) & 0x00FF00FFu);
         }
     };
-    auto consume = [&](int y, const unsigned (&w)[DW + 1], unsigned sh) {
-        unsigned v[DW];
+    auto consume = [&](int y, const u16x2 (&re)[DW], const u16x2 (&ro)[DW]) {
+        const unsigned starts = (unsigned)__builtin_amdgcn_ballot_w64(v_ys == y);     // levels with a bin that starts on this row
+        const unsigned ends = (unsigned)__builtin_amdgcn_ballot_w64(v_ye == y + 1);   // ... that ends on it
+        if (starts) {
 #pragma unroll
-        for (int d = 0; d < DW; d++) v[d] = __builtin_amdgcn_alignbyte(w[d + 1], w[d], sh);
+            for (int l = 0; l < NL; l++)
+                if (starts >> l & 1) {
 #pragma unroll
-        for (int l = 0; l < NL; l++) {
-            if (l < a.nlev && y >= ys[l] && y < ye[l]) {                         // uniform
+                    for (int d = 0; d < DW; d++) { se[l][d] = pe[d]; so[l][d] = po[d]; }
+                }
+        }
 #pragma unroll
-                for (int d = 0; d < DW; d++) { ev[l][d] += v[d] & 0x00FF00FFu; od[l][d] += (v[d] >> 8) & 0x00FF00FFu; }
-                if (y == ye[l] - 1) {
-                    // ---- the bin row is complete: column sums -> the unit's LDS strip -> horizontal bins -> normalise -> store ----
-                    const PyrBins& g = a.lv[l];
-                    const int kh = ye[l] - ys[l];
+        for (int d = 0; d < DW; d++) { pe[d] += re[d]; po[d] += ro[d]; }
+        for (unsigned m = ends; m; m &= m - 1) {
+            // ---- a bin row of level l is complete: column sums -> the unit's LDS strip -> horizontal bins -> normalise -> store ----
+            const int l = __builtin_ctz(m);
+            u16x2 ce[DW], co[DW];
 #pragma unroll
-                    for (int d = 0; d < DW; d++) {
-                        colbuf[4 * DW * lane + 4 * d + 0] = ev[l][d] & 0xFFFFu; colbuf[4 * DW * lane + 4 * d + 1] = od[l][d] & 0xFFFFu;
-                        colbuf[4 * DW * lane + 4 * d + 2] = ev[l][d] >> 16;     colbuf[4 * DW * lane + 4 * d + 3] = od[l][d] >> 16;
+            for (int k = 0; k < NL; k++)
+                if (l == k) {
+#pragma unroll
+                    for (int d = 0; d < DW; d++) { ce[d] = pe[d] - se[k][d]; co[d] = po[d] - so[k][d]; }
+                }
+            const int jl = rl(v_j, l), kh = rl(v_ye, l) - rl(v_ys, l), ox0 = rl(v_ox0, l), ox1 = rl(v_ox1, l), gsh = rl(v_gs, l);
+            const int ty0 = rl(v_ty0, l), tx0 = rl(v_tx0, l), kwA = rl(v_kwA, l);
+            const float fkh = (float)kh, rh = kh == rl(v_khA, l) ? rlf(v_rkh0, l) : rlf(v_rkh1, l), rw0 = rlf(v_rkw0, l), rw1 = rlf(v_rkw1, l);
+            const bool fast = rl(v_fast, l) != 0;
+            PyrPx* const orow = pyr + ((long long)f * a.pyr_stride + rl(v_pix0, l) + (long long)jl * rl(v_w, l));
+            unsigned short* const strip = colbuf + flip * Own::BYTES;
+            uint2* const dst = reinterpret_cast<uint2*>(strip + 4 * DW * lane);
+#pragma unroll
+            for (int d = 0; d < DW; d++) dst[d] = make_uint2(ce[d].x | ((unsigned)co[d].x << 16), ce[d].y | ((unsigned)co[d].y << 16));
+            Own::sync();
+            // 2^gs lanes per output pixel, each takes every 2^gs-th column of the bin: the reads of four columns are issued
+            // before the first add, the group is summed across lanes (DPP)
+            const int nth = (ox1 - ox0) << gsh;
+            for (int t = lane; t < nth; t += LANES) {
+                const int ox = ox0 + (t >> gsh), sub = t & ((1 << gsh) - 1);
+                const uint32_t tx = tab[tx0 + ox];
+                const int xs = tx & 0xFFFF, xe = tx >> 16;
+                unsigned s0 = 0, s1 = 0, s2 = 0;
+                for (int x0 = xs + sub; x0 < xe; x0 += 4 << gsh) {
+                    unsigned q[4][3];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const int xx = x0 + (k << gsh);
+                        const unsigned short* p = strip + ((xx < xe ? xx : x0) - C0) * 3;
+                        q[k][0] = p[0]; q[k][1] = p[1]; q[k][2] = p[2];
                     }
-                    Own::sync();
-                    for (int ox = ox0[l] + lane; ox < ox1[l]; ox += LANES) {
-                        const uint32_t tx = tab[tx0[l] + ox];
-                        const int xs = tx & 0xFFFF, xe = tx >> 16;
-                        unsigned s0 = 0, s1 = 0, s2 = 0;
-                        for (int xx = xs; xx < xe; xx++) {
-                            const unsigned* p = colbuf + (xx - C0) * 3;
-                            s0 += p[0]; s1 += p[1]; s2 += p[2];
-                        }
-                        float4 o4;
-                        o4.x = pyr_norm(s0, kh, xe - xs, g); o4.y = pyr_norm(s1, kh, xe - xs, g); o4.z = pyr_norm(s2, kh, xe - xs, g);
-                        o4.w = 0.f;
-                        pyr_store(pyr + ((long long)f * a.pyr_stride + g.pix0 + (long long)j[l] * g.w + ox), o4);
-                    }
-                    Own::sync();
-                    // next owned bin of this level; consecutive bins may share this source row
-                    j[l]++;
-                    if (j[l] < jend[l]) {
-                        const uint32_t t0 = tab[ty0[l] + j[l]];
-                        ys[l] = Own::uni((int)(t0 & 0xFFFF)); ye[l] = Own::uni((int)(t0 >> 16));
-                    } else {
-                        ys[l] = ye[l] = 0x7fffffff;
-                    }
-                    const bool again = ys[l] <= y;
 #pragma unroll
-                    for (int d = 0; d < DW; d++) {
-                        ev[l][d] = again ? (v[d] & 0x00FF00FFu) : 0u;
-                        od[l][d] = again ? ((v[d] >> 8) & 0x00FF00FFu) : 0u;
+                    for (int k = 0; k < 4; k++) {
+                        const bool in = x0 + (k << gsh) < xe;
+                        s0 += in ? q[k][0] : 0u; s1 += in ? q[k][1] : 0u; s2 += in ? q[k][2] : 0u;
                     }
                 }
+                if (gsh > 0) { s0 = dpp_add<0xB1>(s0); s1 = dpp_add<0xB1>(s1); s2 = dpp_add<0xB1>(s2); }      // lane ^ 1
+                if (gsh > 1) { s0 = dpp_add<0x4E>(s0); s1 = dpp_add<0x4E>(s1); s2 = dpp_add<0x4E>(s2); }      // lane ^ 2
+                if (gsh > 2) { s0 = dpp_add<0x141>(s0); s1 = dpp_add<0x141>(s1); s2 = dpp_add<0x141>(s2); }   // the other quad
+                if (gsh > 3) { s0 = dpp_add<0x140>(s0); s1 = dpp_add<0x140>(s1); s2 = dpp_add<0x140>(s2); }   // the other eight
+                if (sub == 0) {
+                    const float fkw = (float)(xe - xs), rw = xe - xs == kwA ? rw0 : rw1;
+                    float4 o4;
+                    o4.x = pyr_norm(s0, fkh, fkw, rh, rw, fast); o4.y = pyr_norm(s1, fkh, fkw, rh, rw, fast);
+                    o4.z = pyr_norm(s2, fkh, fkw, rh, rw, fast); o4.w = 0.f;
+                    pyr_store(orow + ox, o4);
+                }
+            }
+            // OwnBlock: the next flush writes the other strip, and the one after it comes behind that flush's barrier, which
+            // every wave reaches with these reads done: one barrier per flush
+            if (Own::STRIPS > 1) flip ^= 1; else Own::sync();
+            // next owned bin of this level; consecutive bins may share this source row
+            int nys = 0x7fffffff, nye = 0x7fffffff;
+            if (jl + 1 < rl(v_jend, l)) {
+                const uint32_t t0 = tab[ty0 + jl + 1];
+                nys = __builtin_amdgcn_readfirstlane((int)(t0 & 0xFFFF)); nye = __builtin_amdgcn_readfirstlane((int)(t0 >> 16));
+            }
+            if (L == l) { v_j = jl + 1; v_ys = nys; v_ye = nye; }
+            if (nys <= y) {                                                      // it starts on this row: the sum without it
+#pragma unroll
+                for (int k = 0; k < NL; k++)
+                    if (l == k) {
+#pragma unroll
+                        for (int d = 0; d < DW; d++) { se[k][d] = pe[d] - re[d]; so[k][d] = po[d] - ro[d]; }
+                    }
             }
         }
     };
 
-    // rows in groups of four: the loads of the next group are in flight while this one is consumed
-    unsigned wb[4][DW + 1], shb[4];
+    // rows in groups of PF: the loads of the next group are issued, all of them, before this group is consumed, and move into this
+    // group's registers behind it -- the only place that waits for them.  (Reloading a row's registers as soon as the row was consumed
+    // looked tighter, but the compiler rotated the registers with moves at the loop's end that waited for every load in flight.)
+    // Groups of 2 measured like 3 and 4 with the same waves per SIMD and cost 10 VGPRs less per row; 1 is slower (0.46 vs 0.42 ms).
+    constexpr int PF = 2;
+    unsigned wb[PF][DW + 1], shb[PF], wn[PF][DW + 1], shn[PF];
 #pragma unroll
-    for (int u = 0; u < 4; u++) load_row(R0 + u, wb[u], shb[u]);
-    for (int y = R0; y < yend; y += 4) {
+    for (int u = 0; u < PF; u++) load_row(R0 + u, wb[u], shb[u]);
+    for (int y = R0; y < yend; y += PF) {
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
-            unsigned wc[DW + 1];
+        for (int u = 0; u < PF; u++) load_row(y + PF + u, wn[u], shn[u]);   // (past the unit's end: a row of the frame, unused)
 #pragma unroll
-            for (int k = 0; k <= DW; k++) wc[k] = wb[u][k];
-            const unsigned shc = shb[u];
-            if (y + u + 4 < yend) load_row(y + u + 4, wb[u], shb[u]);
-            if (y + u < yend) consume(y + u, wc, shc);
+        for (int u = 0; u < PF; u++) {
+            u16x2 re[DW], ro[DW];
+            unpack(y + u, wb[u], shb[u], re, ro);
+            if (y + u < yend) consume(y + u, re, ro);
+        }
+#pragma unroll
+        for (int u = 0; u < PF; u++) {
+#pragma unroll
+            for (int k = 0; k <= DW; k++) wb[u][k] = wn[u][k];
+            shb[u] = shn[u];
         }
     }
 }
@@ -769,8 +858,11 @@ static void plan_row(const PyrJob& j, int l, int kind, int rb, int cb, int cpb, 
     r[0] = kind; r[1] = rb; r[2] = cb; r[3] = cpb; r[4] = frames; r[5] = j.lay.lv[l].khmax;
 }
 
-// Coarse levels (mode != 0): streaming passes in three row bands, at most 8 levels per launch (register budget of the per-level
-// column sums), each launch reading the source once -- every source row once, so no Infinity-Cache chunking.  A group that does not
+// Coarse levels (mode != 0): streaming passes in three row bands whatever the batch (at 256 x 720p that is one workgroup per resident
+// slot at the kernel's 3 waves per SIMD; 4 and 6 bands measured slower on this kernel, 0.50 and 0.43 against 0.42 ms, and 5 and 8
+// on its first stage, profiles/pyramid_stream_bands.txt: the rows a band reads past its end are read again; smaller batches were
+// not swept), at most 8 levels per launch (register budget of the per-level
+// snapshots), each launch reading the source once -- every source row once, so no Infinity-Cache chunking.  A group that does not
 // meet the kernel's preconditions is left to the per-level kernels.  (Streaming the fine levels as well was measured: 1.75 vs
 // 1.83 ms, not worth it.)
 static int launch_coarse(const PyrJob& j, bool (&taken)[16]) {
@@ -782,25 +874,31 @@ static int launch_coarse(const PyrJob& j, bool (&taken)[16]) {
         const int gn = nsel - g0 < 8 ? nsel - g0 : 8;
         PyrStreamArgs sa;
         sa.nlev = 0;
-        int stab_words = 0, kwm = 0;
+        int tab_lo = 0x7fffffff, tab_hi = 0, kwm = 0;
         bool ok = true;
         for (int q = 0; q < gn; q++) {
             const PyrLevel& g = j.lay.lv[lv_idx[g0 + q]];
-            if (g.khmax > 256) ok = false;
-            stab_words += g.h + g.w;
+            if (g.khmax > 256) ok = false;                                   // a bin's column sum must fit 16 bits (it may wrap, see the kernel)
+            tab_lo = g.ytab0 < tab_lo ? g.ytab0 : tab_lo;
+            tab_hi = g.xtab0 + g.w > tab_hi ? g.xtab0 + g.w : tab_hi;
             kwm = g.kwmax > kwm ? g.kwmax : kwm;
             sa.lv[sa.nlev++] = g;
         }
+        const int stab_words = tab_hi - tab_lo;                               // rows + columns of the group's levels (they are neighbours)
+        sa.tab0 = tab_lo; sa.tab_words = stab_words;
         sa.H = H; sa.W = W; sa.n_frames = n; sa.pyr_stride = j.lay.pyr_stride;
-        sa.row_bands = H >= 256 ? 3 : 1;
+        const int forced = j.c->pyr_row_bands;                                // test hook: 0 = the policy below
+        sa.row_bands = forced > 0 ? (forced < H ? forced : H) : (H >= 256 ? 3 : 1);
         sa.rows_per_band = (H + sa.row_bands - 1) / sa.row_bands;
+        sa.row_bands = (H + sa.rows_per_band - 1) / sa.rows_per_band;         // every band has a row
         if (!ok || stab_words > STAB || n > 65535) continue;
         if (!wide) {
             if ((kwm + 2) * 3 > SBYTES / 2) continue;
             sa.col_bands = 1; sa.cols_per_band = W;
             const dim3 sgrid(sa.row_bands * sa.col_bands, n);
-            if (sa.nlev <= 4) k_pyramid_stream<4, OwnBlock><<<sgrid, 256, 0, j.s>>>(j.frames, sa, j.c->pyr_tab, j.pyr);
-            else k_pyramid_stream<8, OwnBlock><<<sgrid, 256, 0, j.s>>>(j.frames, sa, j.c->pyr_tab, j.pyr);
+            const size_t lds = stream_strip_words<OwnBlock>() * 2 + (size_t)stab_words * 4;
+            if (sa.nlev <= 4) k_pyramid_stream<4, OwnBlock><<<sgrid, 256, lds, j.s>>>(j.frames, sa, j.c->pyr_tab, j.pyr);
+            else k_pyramid_stream<8, OwnBlock><<<sgrid, 256, lds, j.s>>>(j.frames, sa, j.c->pyr_tab, j.pyr);
         } else {
             // a wave covers 1280 bytes = 426 whole pixels of a row; the bins that start in its segment may reach kwmax further
             sa.cols_per_band = SW_BYTES / 3 - kwm;
@@ -811,10 +909,11 @@ static int launch_coarse(const PyrJob& j, bool (&taken)[16]) {
             // until its last bins are complete, so not shorter than 256 rows)
             int rbn = (4096 + n * sa.col_bands - 1) / (n * sa.col_bands);
             if (rbn > H / 256) rbn = H / 256;
-            if (rbn > sa.row_bands) { sa.row_bands = rbn; sa.rows_per_band = (H + rbn - 1) / rbn; }
+            if (rbn > sa.row_bands && forced <= 0) { sa.row_bands = rbn; sa.rows_per_band = (H + rbn - 1) / rbn; }
             const dim3 sgrid((sa.row_bands * sa.col_bands + 3) / 4, n);
-            if (sa.nlev <= 4) k_pyramid_stream<4, OwnWave><<<sgrid, 256, 0, j.s>>>(j.frames, sa, j.c->pyr_tab, j.pyr);
-            else k_pyramid_stream<8, OwnWave><<<sgrid, 256, 0, j.s>>>(j.frames, sa, j.c->pyr_tab, j.pyr);
+            const size_t lds = stream_strip_words<OwnWave>() * 2 + (size_t)stab_words * 4;
+            if (sa.nlev <= 4) k_pyramid_stream<4, OwnWave><<<sgrid, 256, lds, j.s>>>(j.frames, sa, j.c->pyr_tab, j.pyr);
+            else k_pyramid_stream<8, OwnWave><<<sgrid, 256, lds, j.s>>>(j.frames, sa, j.c->pyr_tab, j.pyr);
         }
         TRL_LAUNCH_CHECK();
         const int kind = wide ? (sa.nlev <= 4 ? TRL_PYR_SW4 : TRL_PYR_SW8) : (sa.nlev <= 4 ? TRL_PYR_S4 : TRL_PYR_S8);

@@ -81,6 +81,9 @@ int  trl_default_config(trl_config* cfg);
  * packed weights (TRLW0001 blob from weights.pack_state_dicts) once, reuse for every clip. */
 int  trl_create(const trl_config* cfg, trl_ctx** out);
 int  trl_destroy(trl_ctx* ctx);
+/* trl_load_weights checks every tensor the four networks use -- present, and of the shape its layer needs -- and returns
+ * TRL_ERR_WEIGHTS, naming the tensor, for a blob that falls short: no later call can miss one.  A context whose load was
+ * refused has no weights. */
 int  trl_load_weights(trl_ctx* ctx, const void* host_blob, size_t nbytes);
 
 /* server/model.py:47  `boxes, probs = mtcnn.detect(frame)` for a batch of n frames.

@@ -116,7 +116,9 @@ def test_bad_arguments_are_rejected(engine):
 
 def test_malformed_weight_blobs_are_rejected(blob):
     """trl_load_weights trusts nothing in the blob's directory: bad magic, a truncated blob, an entry whose byte range leaves the
-    blob, a shape that does not account for the entry's bytes and a missing tensor are all TRL_ERR_WEIGHTS, not a crash."""
+    blob, a shape that does not account for the entry's bytes, a missing tensor of any of the four nets (a PReLU slope, a bias, a
+    conv matrix, a folded batch norm, whichever code would have been the first to miss it) and a slope vector one element short of
+    its conv's channels are all TRL_ERR_WEIGHTS at load, not a crash, a device fault or wrong embeddings at a later call."""
     import struct
     from truely_amd.engine import Engine
     from truely_amd._lib import TrlError
@@ -135,8 +137,12 @@ def test_malformed_weight_blobs_are_rejected(blob):
     bad = [b"XXXXXXXX" + blob[8:], blob[:16 + ent.size * n - 8], patched(0, off=len(blob) - 4), patched(0, off=2 ** 63, nb=2 ** 63),
            patched(0, d0=d0 + 1), patched(0, nb=nb - 4)]
     t = weights.unpack_tensors(blob)
-    t.pop("pnet.conv4_2.w")
-    bad.append(weights.pack_tensors(t))
+    for gone in ("pnet.conv4_2.w", "pnet.prelu1", "pnet.conv3.b", "rnet.prelu2", "onet.conv4.b", "rnet.conv1.w", "facenet.conv2d_2a.scale",
+                 "facenet.repeat_2.3.conv2d.b", "facenet.last_bn.shift"):
+        assert gone in t
+        bad.append(weights.pack_tensors({k: v for k, v in t.items() if k != gone}))
+    assert t["onet.prelu3"].shape == (t["onet.conv3.w"].shape[-1],)
+    bad.append(weights.pack_tensors({**t, "onet.prelu3": t["onet.prelu3"][:-1]}))
     for b in bad:
         with pytest.raises(TrlError) as e:
             Engine(b)

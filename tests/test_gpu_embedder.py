@@ -225,7 +225,7 @@ def _geometry(layer):
 
 
 def _layer_params(T, layer):
-    """(w [K][Cout], bias or None, scale or None, shift or None) as the library packs them (fuse_bconv concatenates columns)."""
+    """(w [K][Cout], bias or None, scale or None, shift or None) as the library packs them (concat_cols in trl_load_weights concatenates columns)."""
     if layer.endswith(".fused"):
         fam, blk, _ = _split(layer)
         cat = lambda suf: np.concatenate([T[f"{blk}.{q}.{suf}"] for q in FUSED_PARTS[fam]], axis=-1)

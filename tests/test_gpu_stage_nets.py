@@ -1,7 +1,7 @@
 """Stages 2 and 3 of the detector (R-Net / O-Net) per candidate, at the launch capacities the product uses.
 
 Each stage is trl_stage_net: chunks of rnet_chunk / onet_chunk candidate slots, each one k_mtcnn_front launch (crop, area
-resample, conv1, PReLU, pool) and a tail of generic layer kernels (trl_run_rnet_tail / trl_run_onet_tail).  Two things make the
+resample, conv1, PReLU, pool) and a tail of generic layer kernels (trl_run_net from the descriptor's tail layer).  Two things make the
 tail unusual: the kernel and tile of every conv are chosen from the CAPACITY (M = chunk slots x OH x OW, trl_launch_conv /
 launch_cfg), because the live count exists only on the device; and every kernel skips the dead rows itself (trl_live_rows in the
 conv kernels, the clamped N of maxpool_kernel's grid-stride loop).
@@ -25,7 +25,7 @@ NF, H, W = 4, 360, 640
 SENTINEL = np.float32(-12345.678)   # what the output held before the call: tiles past the live rows must leave it
 CAP_MAX = 49152              # the default R-Net chunk, and the largest per-launch capacity
 
-# (layer, input side, Cin, kernel, Cout) of the two tails' convs, in launch order (trl_run_rnet_tail / trl_run_onet_tail)
+# (layer, input side, Cin, kernel, Cout) of the two tails' convs, in launch order (trl_nets[] in csrc/trl_nets.hip, from each net's tail layer)
 TAIL = {
     24: [("rnet.conv2", 11, 28, 3, 48), ("rnet.conv3", 4, 48, 2, 64), ("rnet.dense4", 3, 64, 3, 128), ("rnet.heads", 1, 128, 1, 6)],
     48: [("onet.conv2", 23, 32, 3, 64), ("onet.conv3", 10, 64, 3, 64), ("onet.conv4", 4, 64, 2, 128),

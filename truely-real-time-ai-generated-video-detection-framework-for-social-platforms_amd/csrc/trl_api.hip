@@ -201,91 +201,64 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
         if (e.ndim == 2) add_mat(name, (int)e.dims[0], (int)e.dims[1], src);
         else if (e.ndim == 1) add_vec(name, (int)e.dims[0], src);
     }
-    // merged heads: the 1x1 class and regression (and landmark) convs share their input, so they run as
-    // one [K][6] / [K][16] matrix; each output column is still its own fmaf chain (bit-identical).
+    // Convs that read the same input run as ONE conv: out + ".w" = the parts' matrices side by side (same K), out + suffix = their
+    // per-column vectors likewise, for every suffix.  Each output column keeps its own fmaf chain, so results are unchanged.
     std::vector<std::vector<float>> keep_alive;
-    auto merge_heads = [&](const std::string& net, const std::vector<std::string>& parts) -> int {
+    keep_alive.reserve(512);                       // (add_mat / add_vec keep pointers into it)
+    auto concat_cols = [&](const std::string& out, const std::vector<std::string>& parts, std::initializer_list<const char*> suffixes) -> int {
         int K = -1, tot = 0;
         for (auto& p : parts) {
-            auto it = idx.find(net + "." + p + ".w");
-            auto ib = idx.find(net + "." + p + ".b");
-            if (it == idx.end() || ib == idx.end()) { trl_set_error("missing head %s.%s", net.c_str(), p.c_str()); return TRL_ERR_WEIGHTS; }
+            auto it = idx.find(p + ".w");
+            if (it == idx.end() || it->second->ndim != 2) { trl_set_error("missing tensor %s.w", p.c_str()); return TRL_ERR_WEIGHTS; }
             if (K < 0) K = (int)it->second->dims[0];
-            if (K != (int)it->second->dims[0] || ib->second->dims[0] != it->second->dims[1]) {
-                trl_set_error("head %s.%s has an unexpected shape", net.c_str(), p.c_str());
-                return TRL_ERR_WEIGHTS;
+            if (K != (int)it->second->dims[0]) { trl_set_error("%s.w: the convs merged into %s disagree on K", p.c_str(), out.c_str()); return TRL_ERR_WEIGHTS; }
+            for (const char* sfx : suffixes) {
+                auto iv = idx.find(p + sfx);
+                if (iv == idx.end()) { trl_set_error("missing tensor %s%s", p.c_str(), sfx); return TRL_ERR_WEIGHTS; }
+                if (iv->second->ndim != 1 || iv->second->dims[0] != it->second->dims[1]) { trl_set_error("tensor %s%s has an unexpected shape", p.c_str(), sfx); return TRL_ERR_WEIGHTS; }
             }
             tot += (int)it->second->dims[1];
         }
         keep_alive.emplace_back((size_t)K * tot);
-        keep_alive.emplace_back((size_t)tot);       // (keep_alive is reserved below: the references stay valid)
-        std::vector<float>& bias = keep_alive[keep_alive.size() - 1];
-        std::vector<float>& wm = keep_alive[keep_alive.size() - 2];
-        int col = 0;
-        for (auto& p : parts) {
-            const Entry* e = idx[net + "." + p + ".w"];
-            const Entry* eb = idx[net + "." + p + ".b"];
-            const float* src = (const float*)(b + e->offset);
-            const float* sb = (const float*)(b + eb->offset);
-            const int co = (int)e->dims[1];
-            for (int k = 0; k < K; k++) for (int j = 0; j < co; j++) wm[(size_t)k * tot + col + j] = src[(size_t)k * co + j];
-            for (int j = 0; j < co; j++) bias[col + j] = sb[j];
-            col += co;
-        }
-        add_mat(net + ".heads.w", K, tot, wm.data());
-        add_vec(net + ".heads.b", tot, bias.data());
-        return TRL_OK;
-    };
-    keep_alive.reserve(512);
-    // FaceNet: 1x1 BasicConv2d branches that read the same input run as ONE conv with concatenated output
-    // columns (each column keeps its own fmaf chain, so results are unchanged): fewer, wider launches.
-    auto fuse_bconv = [&](const std::string& out, const std::vector<std::string>& parts) -> int {
-        int K = -1, tot = 0;
-        for (auto& p : parts) {
-            auto it = idx.find(p + ".w");
-            if (it == idx.end() || idx.find(p + ".scale") == idx.end() || idx.find(p + ".shift") == idx.end()) {
-                trl_set_error("missing tensors of %s", p.c_str());
-                return TRL_ERR_WEIGHTS;
-            }
-            if (K < 0) K = (int)it->second->dims[0];
-            if (K != (int)it->second->dims[0]) { trl_set_error("fused convs disagree on K (%s)", p.c_str()); return TRL_ERR_WEIGHTS; }
-            tot += (int)it->second->dims[1];
-        }
-        keep_alive.emplace_back((size_t)K * tot); const size_t iw = keep_alive.size() - 1;
-        keep_alive.emplace_back((size_t)tot);      const size_t isc = keep_alive.size() - 1;
-        keep_alive.emplace_back((size_t)tot);      const size_t ish = keep_alive.size() - 1;
+        std::vector<float>& wm = keep_alive.back();
         int col = 0;
         for (auto& p : parts) {
             const Entry* e = idx[p + ".w"];
             const float* src = (const float*)(b + e->offset);
-            const float* ssc = (const float*)(b + idx[p + ".scale"]->offset);
-            const float* ssh = (const float*)(b + idx[p + ".shift"]->offset);
             const int co = (int)e->dims[1];
-            for (int k = 0; k < K; k++) for (int j = 0; j < co; j++) keep_alive[iw][(size_t)k * tot + col + j] = src[(size_t)k * co + j];
-            for (int j = 0; j < co; j++) { keep_alive[isc][col + j] = ssc[j]; keep_alive[ish][col + j] = ssh[j]; }
+            for (int k = 0; k < K; k++) for (int j = 0; j < co; j++) wm[(size_t)k * tot + col + j] = src[(size_t)k * co + j];
             col += co;
         }
-        add_mat(out + ".w", K, tot, keep_alive[iw].data());
-        add_vec(out + ".scale", tot, keep_alive[isc].data());
-        add_vec(out + ".shift", tot, keep_alive[ish].data());
+        add_mat(out + ".w", K, tot, wm.data());
+        for (const char* sfx : suffixes) {
+            keep_alive.emplace_back();
+            std::vector<float>& v = keep_alive.back();
+            for (auto& p : parts) {
+                const Entry* e = idx[p + sfx];
+                v.insert(v.end(), (const float*)(b + e->offset), (const float*)(b + e->offset) + e->dims[0]);
+            }
+            add_vec(out + sfx, tot, v.data());
+        }
         return TRL_OK;
     };
+    const auto bn = {".scale", ".shift"};           // FaceNet's 1x1 BasicConv2d branches: folded batch norm per column
     for (int i = 0; i < 5; i++) {
         const std::string p = "facenet.repeat_1." + std::to_string(i);
-        TRL_CHECK(fuse_bconv(p + ".fused", {p + ".branch0", p + ".branch2.0", p + ".branch1.0"}));   // [b0 | b2.0 | b1.0]
+        TRL_CHECK(concat_cols(p + ".fused", {p + ".branch0", p + ".branch2.0", p + ".branch1.0"}, bn));   // [b0 | b2.0 | b1.0]
     }
     for (int i = 0; i < 10; i++) {
         const std::string p = "facenet.repeat_2." + std::to_string(i);
-        TRL_CHECK(fuse_bconv(p + ".fused", {p + ".branch0", p + ".branch1.0"}));
+        TRL_CHECK(concat_cols(p + ".fused", {p + ".branch0", p + ".branch1.0"}, bn));
     }
     for (int i = 0; i < 6; i++) {
         const std::string p = i < 5 ? "facenet.repeat_3." + std::to_string(i) : std::string("facenet.block8");
-        TRL_CHECK(fuse_bconv(p + ".fused", {p + ".branch0", p + ".branch1.0"}));
+        TRL_CHECK(concat_cols(p + ".fused", {p + ".branch0", p + ".branch1.0"}, bn));
     }
-    TRL_CHECK(fuse_bconv("facenet.mixed_7a.fused", {"facenet.mixed_7a.branch0.0", "facenet.mixed_7a.branch1.0", "facenet.mixed_7a.branch2.0"}));
-    TRL_CHECK(merge_heads("pnet", {"conv4_1", "conv4_2"}));
-    TRL_CHECK(merge_heads("rnet", {"dense5_1", "dense5_2"}));
-    TRL_CHECK(merge_heads("onet", {"dense6_1", "dense6_2", "dense6_3"}));
+    TRL_CHECK(concat_cols("facenet.mixed_7a.fused", {"facenet.mixed_7a.branch0.0", "facenet.mixed_7a.branch1.0", "facenet.mixed_7a.branch2.0"}, bn));
+    // merged heads: the 1x1 class and regression (and landmark) convs as one [K][6] / [K][16] matrix
+    TRL_CHECK(concat_cols("pnet.heads", {"pnet.conv4_1", "pnet.conv4_2"}, {".b"}));
+    TRL_CHECK(concat_cols("rnet.heads", {"rnet.dense5_1", "rnet.dense5_2"}, {".b"}));
+    TRL_CHECK(concat_cols("onet.heads", {"onet.dense6_1", "onet.dense6_2", "onet.dense6_3"}, {".b"}));
 
     if (c->cfg.embed_precision == 2) {   // an fp16 conv weight that rounds past +-65504 would become inf: refuse the blob instead
         for (auto& p : items) {
@@ -303,6 +276,7 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
         if (p.mat) { for (int k = 0; k < p.K; k++) memcpy(dst + (size_t)k * p.ld, p.src + (size_t)k * p.Cout, (size_t)p.Cout * 4); }
         else memcpy(dst, p.src, (size_t)p.n * 4);
     }
+    c->have_weights = false;                       // (a refused blob leaves the context without weights)
     if (c->wdev) { TRL_HIP(hipDeviceSynchronize()); TRL_HIP(hipFree(c->wdev)); c->wdev = nullptr; }
     TRL_HIP(hipMalloc((void**)&c->wdev, total));
     TRL_HIP(hipMemcpy(c->wdev, host.data(), total, hipMemcpyHostToDevice));
@@ -314,8 +288,12 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
         else { DevV v; v.p = (float*)(c->wdev + p.off); v.n = p.n; c->V[p.name] = v; }
     }
 
-    TRL_CHECK(trl_pnet_prepare(c));
-    c->rnet_front_mode = c->onet_front_mode = -1;
+    // Every tensor the four nets use is checked here, never at a call: the MTCNN layers resolve into c->mt, what the kernels
+    // choose by (slope classes, the conv3 screen bound) comes from the host image, and the embedder's walk runs once in its
+    // check-only mode over one 160 x 160 face (every geometry names the same tensors).
+    TRL_CHECK(trl_resolve_nets(c, host.data()));
+    TRL_CHECK(trl_pnet_prepare(c, host.data()));
+    TRL_CHECK(trl_run_facenet(c, nullptr, 1, 160, 160, nullptr, nullptr, nullptr, true));
     if (c->cfg.embed_precision >= 1) {   // bf16 / fp16 copies of the embedder's conv weights (all but the 3-channel stem and the final linear)
         for (auto& kv : c->W) {
             const std::string& nm = kv.first;
@@ -428,7 +406,7 @@ static int call_begin(trl_ctx* c, const trl_ctx::Pending& q) {
     }
     TRL_HIP(hipSetDevice(c->cfg.device));
     const int S = c->cfg.embed_mode == 0 ? 80 : 160;
-    c->scratch_after_cascade = q.kind == trl_ctx::Pending::EMBED ? (size_t)q.n * ((size_t)S * S * 110 + 400000) * 4 + (8u << 20) : 0;
+    c->scratch_after_cascade = q.kind == trl_ctx::Pending::EMBED ? trl_facenet_bytes(q.n, S, S) : 0;
     c->pend = q;
     c->pend.active = true;
     c->pend.attempt = 0;
@@ -541,7 +519,7 @@ static int facenet_embed(trl_ctx* c, const float* d_faces, const uint8_t* d_vali
     if (!d_faces || (masked && !d_valid) || !d_emb || n <= 0 || h < 75 || w < 75) { trl_set_error("bad face batch n=%d %dx%d (min 75x75)", n, h, w); return TRL_ERR_INVALID; }
     TRL_HIP(hipSetDevice(c->cfg.device));
     c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, (size_t)n * ((size_t)h * w * 110 + 400000) * 4 + (8u << 20)));
+    TRL_CHECK(trl_ensure(c, c->scratch, trl_facenet_bytes(n, h, w)));
     TRL_CHECK(trl_run_facenet(c, d_faces, n, h, w, d_valid, d_emb, (hipStream_t)stream));
     return trl_gate_record(c, (hipStream_t)stream);
 }
@@ -749,13 +727,16 @@ int trl_debug_pnet_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, int l
     return TRL_OK;
 }
 
-int trl_debug_rnet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) {
+// test hooks: a whole net through the layer kernels over n crops [n][side][side][3]: d_out [n][6] (R-Net) / [n][16] (O-Net)
+static int debug_net(trl_ctx* c, const NetDesc& d, const float* d_crops, int n, float* d_out, void* stream) {
     if (!c || !c->have_weights || !d_crops || !d_out || n <= 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
     TRL_CHECK(trl_check_idle(c));
     c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, (size_t)n * 100 * 1024 + (4u << 20)));
-    return trl_run_rnet(c, d_crops, n, d_out, (hipStream_t)stream);
+    TRL_CHECK(trl_ensure(c, c->scratch, trl_net_bytes(d, n)));
+    return trl_run_net(c, d, 0, Act::dense(d_crops, n, d.side, d.side, 3), d_out, (hipStream_t)stream);
 }
+int trl_debug_rnet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) { return debug_net(c, trl_nets[TRL_RNET], d_crops, n, d_out, stream); }
+int trl_debug_onet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) { return debug_net(c, trl_nets[TRL_ONET], d_crops, n, d_out, stream); }
 // k_build_map's records on the device for a front launch outside the cascade: hb holds `slots` records of 8 words (the live ones
 // first); c->cb then describes the batch and the record list, *total is the device-side count nb.
 static int upload_records(trl_ctx* c, int nf, int H, int W, const std::vector<int32_t>& hb, int slots, int nb, int32_t** total, hipStream_t s) {
@@ -798,10 +779,10 @@ static int stage_net_on_rows(trl_ctx* c, const uint8_t* d_frames, int nf, int H,
     }
     int32_t* total = nullptr;
     TRL_CHECK(upload_records(c, nf, H, W, hb, slots, nb, &total, s));
-    // workspace as the cascade sizes it (trl_cascade_detect): per candidate of a chunk 40 KB (R-Net) / 240 KB (O-Net)
-    const int CH = net == 24 ? c->rnet_chunk : c->onet_chunk, ch = capacity < CH ? capacity : CH;
+    // workspace as the cascade sizes it (trl_cascade_detect)
+    const NetDesc& d = trl_net_of(net);
     c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, (size_t)ch * (net == 24 ? 40 : 240) * 1024 + (1u << 20)));
+    TRL_CHECK(trl_ensure(c, c->scratch, trl_stage_bytes(d, capacity < c->*d.chunk ? capacity : c->*d.chunk)));
     c->mt_plan.clear();
     c->mt_plan_arm = true;
     const int st = trl_stage_net(c, net, d_frames, H, W, total, capacity, d_out, s);
@@ -862,9 +843,7 @@ int trl_debug_front(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, c
     }
     int32_t* total = nullptr;
     TRL_CHECK(upload_records(c, nf, H, W, hb, slots, nb, &total, s));
-    const int st = net == 24 ? trl_launch_rnet_front(c, d_frames, H, W, total, 0, capacity, d_pool, s)
-                             : trl_launch_onet_front(c, d_frames, H, W, total, 0, capacity, d_pool, s);
-    TRL_CHECK(st);
+    TRL_CHECK(trl_launch_front(c, trl_net_of(net), d_frames, H, W, total, 0, capacity, d_pool, s));
     TRL_HIP(hipStreamSynchronize(s));
     c->cb = CascadeBufs();
     return TRL_OK;
@@ -908,13 +887,6 @@ int trl_debug_mtcnn_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, int*
     return TRL_OK;
 }
 
-int trl_debug_onet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) {
-    if (!c || !c->have_weights || !d_crops || !d_out || n <= 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
-    TRL_CHECK(trl_check_idle(c));
-    c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, (size_t)n * 640 * 1024 + (4u << 20)));
-    return trl_run_onet(c, d_crops, n, d_out, (hipStream_t)stream);
-}
 // test hooks: the three face-crop kernels alone (include/truely_hip.h states the precondition on valid rows).  k_crop_resize80
 // indexes frames by grid x, so any n is a legal launch; k_crop_aligned / k_crop_area_std index them by grid y, which the public
 // entry points bound through check_call -- these hooks apply the same 65535.

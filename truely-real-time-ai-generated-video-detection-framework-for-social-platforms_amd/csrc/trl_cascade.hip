@@ -970,7 +970,7 @@ int trl_pnet_generic_level(trl_ctx* c, const uint8_t* d_frames, int nf, int H, i
     float* heads = (float*)X.alloc((size_t)nf * g.oh * g.ow * 24);
     if (!lvl || !heads) { trl_set_error("pnet generic workspace"); return TRL_ERR_STATE; }
     TRL_CHECK(trl_launch_area_level(d_frames, nf, H, W, g.h, g.w, lvl, s));
-    TRL_CHECK(trl_run_pnet_generic(c, lvl, nf, g.h, g.w, heads, s));
+    TRL_CHECK(trl_run_net(c, trl_nets[TRL_PNET], 0, Act::dense(lvl, nf, g.h, g.w, 3), heads, s));   // heads [nf][oh][ow][6]
     *d_heads = heads;
     return TRL_OK;
 }
@@ -1005,10 +1005,9 @@ static int size_scratch(trl_ctx* c, int n, int H, int W, bool fused) {
     c->cap_t2 = (int)(c2 < lim ? c2 : lim);
     c->cap_t3 = (int)(c3 < lim ? c3 : lim);
     const int ch2 = c->cap_t2 < c->rnet_chunk ? c->cap_t2 : c->rnet_chunk, ch3 = c->cap_t3 < c->onet_chunk ? c->cap_t3 : c->onet_chunk;
-    // per candidate: the front kernel's pooled map + every activation of the tail (trl_run_rnet_tail / trl_run_onet_tail:
-    // R-Net 3388 + 3888 + 768 + 576 + 128 floats = 35 KB; O-Net 16928 + 28224 + 6400 + 4096 + 1024 + 1152 + 256 = 227 KB)
-    size_t need_x = (size_t)c->cap_t2 * 24 + (size_t)ch2 * (40 * 1024) + (1u << 20);
-    const size_t need3 = (size_t)c->cap_t3 * 64 + (size_t)ch3 * (240 * 1024) + (1u << 20);
+    // the stage's output rows + per candidate of a chunk the front kernel's pooled map and every activation of the tail
+    size_t need_x = (size_t)c->cap_t2 * 24 + trl_stage_bytes(trl_nets[TRL_RNET], ch2);
+    const size_t need3 = (size_t)c->cap_t3 * 64 + trl_stage_bytes(trl_nets[TRL_ONET], ch3);
     if (need3 > need_x) need_x = need3;
     if (fused) { const size_t p = trl_pnet_fused_bytes(c, n, H, W) + (1u << 20); if (p > need_x) need_x = p; }
     if (c->scratch_after_cascade > need_x) need_x = c->scratch_after_cascade;   // the embedder that follows in the same call
@@ -1137,20 +1136,16 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
 // maps come from c->scratch behind its current offset (the caller's blocks below it stay intact).  d_out: [cap][6] / [cap][16].
 int trl_stage_net(trl_ctx* c, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float* d_out, hipStream_t s) {
     Arena& X = c->scratch;
-    const int CH = net == 24 ? c->rnet_chunk : c->onet_chunk, P = net == 24 ? 11 : 23, C1 = net == 24 ? 28 : 32, NO = net == 24 ? 6 : 16;
+    const NetDesc& d = trl_net_of(net);
+    const int CH = c->*d.chunk;
     const size_t mk = X.off;
     for (int t0 = 0; t0 < cap; t0 += CH) {
         const int nc = (cap - t0 < CH) ? cap - t0 : CH;
         X.off = mk;
-        float* pool1 = (float*)X.alloc((size_t)nc * P * P * C1 * 4);
-        if (!pool1) { trl_set_error(net == 24 ? "rnet workspace" : "onet workspace"); return TRL_ERR_STATE; }
-        if (net == 24) {
-            TRL_CHECK(trl_launch_rnet_front(c, d_frames, H, W, d_total, t0, nc, pool1, s));   // crop + conv1 + pool1 in LDS
-            TRL_CHECK(trl_run_rnet_tail(c, pool1, nc, d_out + (size_t)t0 * NO, s, d_total, t0));
-        } else {
-            TRL_CHECK(trl_launch_onet_front(c, d_frames, H, W, d_total, t0, nc, pool1, s));
-            TRL_CHECK(trl_run_onet_tail(c, pool1, nc, d_out + (size_t)t0 * NO, s, d_total, t0));
-        }
+        float* pool1 = (float*)X.alloc((size_t)nc * d.P * d.P * d.C1 * 4);
+        if (!pool1) { trl_set_error("%s workspace", d.name); return TRL_ERR_STATE; }
+        TRL_CHECK(trl_launch_front(c, d, d_frames, H, W, d_total, t0, nc, pool1, s));   // crop + conv1 + pool1 in LDS
+        TRL_CHECK(trl_run_net(c, d, d.tail, Act::dense(pool1, nc, d.P, d.P, d.C1), d_out + (size_t)t0 * d.nout, s, d_total, t0));
     }
     return TRL_OK;
 }

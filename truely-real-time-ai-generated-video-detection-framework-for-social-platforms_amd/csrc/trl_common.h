@@ -62,6 +62,11 @@ struct Act {
     int coff = 0;                      // channel offset of the view inside the pixel
     bool bf = false;                   // elements are bf16 (2 bytes), p is then a uint16_t* in disguise (embed_precision = 1)
     size_t pixels() const { return (size_t)n * h * w; }
+    static Act dense(const float* p, int n, int h, int w, int c) {   // a whole f32 buffer [n][h][w][c]
+        Act a;
+        a.p = const_cast<float*>(p); a.n = n; a.h = h; a.w = w; a.c = c; a.ld = c;
+        return a;
+    }
 };
 
 enum { TRL_ACT_NONE = 0, TRL_ACT_RELU = 1, TRL_ACT_PRELU = 2 };

@@ -48,6 +48,27 @@ enum { TRL_NFLAGS = 64 };            // int32 words of CascadeBufs::flags (copie
 enum { FLG_LEVEL = 0, FLG_FRAME = 1, FLG_T2 = 2, FLG_T3 = 3, FLG_T2N = 4, FLG_T3N = 5, FLG_FRAME_MAX = 6, FLG_SPILL = 7,
        FLG_SPILL_CUR = 8 /* u64 */, FLG_SPILL_LISTS = 10, FLG_LEVEL_MAX = 16 /* [32] */ };
 
+// One MTCNN network, described once (the table trl_nets[] in trl_nets.hip): the layer walker, the front launcher, the cascade's
+// stage loop, the workspace sizes and the loader's tensor check all read it.
+struct NetLayer { const char* name; const char* prelu; int k, st, cout; };   // a valid k x k conv `name` (+ bias, + PReLU `prelu` or none) of
+                                                                             // cout channels; name == null: a ceil-mode max pool k / st
+struct trl_ctx;
+struct NetDesc {
+    const char* name;
+    int side;                        // crop side (0: PNet takes any map)
+    int nl; NetLayer layer[9];       // the last one is the merged heads conv, written straight into the caller's output
+    int tail;                        // first layer behind the fused front kernel (trl_front.hip), whose pooled map is [P][P][C1]
+    int P, C1;
+    int nout;                        // output floats per item
+    int trl_ctx::*chunk;             // the context's candidates-per-launch-set option of this net
+    size_t full_bytes, tail_bytes;   // activation workspace per item of the whole net / of the tail with its pooled map (R-Net tail:
+                                     // 3388 + 3888 + 768 + 576 + 128 floats = 35 KB; O-Net: 16928 + 28224 + 6400 + 4096 + 1024 + 1152 + 256 = 227 KB)
+};
+enum { TRL_PNET = 0, TRL_RNET = 1, TRL_ONET = 2 };
+extern const NetDesc trl_nets[3];
+inline const NetDesc& trl_net_of(int net) { return trl_nets[net == 24 ? TRL_RNET : TRL_ONET]; }   // the API's net argument: 24 / 48
+struct NetLayerW { const DevW* w = nullptr; const float* b = nullptr; const float* slope = nullptr; };   // a conv layer's device tensors
+
 struct trl_ctx {
     trl_config cfg;
     bool have_weights = false;
@@ -55,6 +76,10 @@ struct trl_ctx {
     size_t wbytes = 0;
     std::unordered_map<std::string, DevW> W;
     std::unordered_map<std::string, DevV> V;
+    // Resolved by trl_load_weights, which refuses a blob that lacks or mis-shapes any of them: the tensors of every layer of
+    // trl_nets[] and the conv1 PReLU slope class of R-Net / O-Net (trl_front.hip).  No MTCNN path looks a tensor up by name.
+    NetLayerW mt[3][9];
+    int front_mode[3] = {0, 0, 0};
     Arena arena;                     // per-call persistent blocks (cascade lists)
     Arena scratch;                   // transient activations; only ever grown while empty
     Arena sims_tmp;                  // similarities when trl_drift_score is called with d_sims == NULL
@@ -90,7 +115,6 @@ struct trl_ctx {
     int last_attempts = 0;           // attempts the last call took (test hook)
     int resume_stage = 0;            // 2 / 3: the next attempt of the call in progress starts at that stage (trl_cascade_check)
     size_t scratch_after_cascade = 0;   // scratch bytes the rest of the call needs (crops + FaceNet): sized with the cascade's
-    int rnet_front_mode = -1, onet_front_mode = -1;   // conv1 PReLU slope class (trl_front.hip), -1 = not yet classified
     // the call in progress: queued by trl_detect_embed_begin / trl_detect_crop_begin and not yet finished by trl_detect_embed_end,
     // or a blocking trl_detect_embed / trl_detect_crop / trl_mtcnn_detect* between its enqueue and its wait (trl_api.hip)
     struct Pending {
@@ -142,18 +166,23 @@ const DevW* trl_w(trl_ctx* c, const std::string& name);
 const DevV* trl_v(trl_ctx* c, const std::string& name);
 
 // networks (trl_nets.hip)
-int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s);
-int trl_run_rnet(trl_ctx* c, const float* d_crops, int n, float* d_out6, hipStream_t s);
-int trl_run_onet(trl_ctx* c, const float* d_crops, int n, float* d_out16, hipStream_t s);
-// n = CAPACITY of the launch; the candidates that exist are clamp(*n_dev - n_base, 0, n) (device-sized, no host sync)
-int trl_run_rnet_tail(trl_ctx* c, const float* d_pool1, int n, float* d_out6, hipStream_t s, const int32_t* n_dev = nullptr, int n_base = 0);
-int trl_run_onet_tail(trl_ctx* c, const float* d_pool1, int n, float* d_out16, hipStream_t s, const int32_t* n_dev = nullptr, int n_base = 0);
-int trl_launch_rnet_front(trl_ctx* c, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc, float* d_pool, hipStream_t s);
-int trl_launch_onet_front(trl_ctx* c, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc, float* d_pool, hipStream_t s);
+// check_only: the walk of trl_load_weights -- shapes and tensors are checked, nothing is allocated, launched or copied
+int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s, bool check_only = false);
+inline size_t trl_facenet_bytes(int n, int h, int w) { return (size_t)n * ((size_t)h * w * 110 + 400000) * 4 + (8u << 20); }   // its scratch
+// Layers first .. last of net d over x (x.n items; the maps of layer `first`): d_out [x.n][oh][ow][d.nout].  With m_dev, x.n is the
+// CAPACITY of the launch and the items that exist are clamp(*m_dev - m_base, 0, x.n) (device-sized, no host sync).  While
+// c->mt_plan_arm its conv launches are appended to c->mt_plan ("rnet.conv2" .. "onet.heads").
+int trl_run_net(trl_ctx* c, const NetDesc& d, int first, const Act& x, float* d_out, hipStream_t s, const int32_t* m_dev = nullptr, int m_base = 0);
+inline size_t trl_net_bytes(const NetDesc& d, int n) { return (size_t)n * d.full_bytes + (4u << 20); }        // scratch of the whole net over n crops
+inline size_t trl_stage_bytes(const NetDesc& d, int chunk) { return (size_t)chunk * d.tail_bytes + (1u << 20); }   // ... of one chunk of trl_stage_net
+// trl_load_weights, after the upload: himg is the staged host image, laid out like c->wdev (trl_host_of reads a device tensor's copy)
+int trl_resolve_nets(trl_ctx* c, const char* himg);
+inline const float* trl_host_of(const trl_ctx* c, const char* himg, const float* dev) { return (const float*)(himg + ((const char*)dev - c->wdev)); }
+int trl_front_slope_class(const float* h_slope, int n);
+// the fused front kernel of R-Net / O-Net over records t0 .. t0 + nc - 1 of c->cb.cbox: pooled maps [nc][P][P][C1]
+int trl_launch_front(trl_ctx* c, const NetDesc& d, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc, float* d_pool, hipStream_t s);
 // stage 2 / 3 network over `cap` candidate slots of c->cb.cbox, *d_total of them live (trl_cascade.hip): chunked front + tail
 int trl_stage_net(trl_ctx* c, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float* d_out, hipStream_t s);
-// PNet on one materialised level for nf frames: heads [nf][oh][ow][6]
-int trl_run_pnet_generic(trl_ctx* c, const float* d_level, int nf, int h, int w, float* d_heads, hipStream_t s);
 size_t trl_pnet_generic_bytes(int nf, int h, int w);
 
 // cascade (trl_cascade.hip)
@@ -180,7 +209,7 @@ int trl_launch_crop_area_std(const uint8_t* d_frames, int n, int H, int W, const
 size_t trl_pnet_generic_level_bytes(const LevelGeom& g);
 int trl_pnet_generic_level(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const LevelGeom& g, float** d_heads, hipStream_t s);
 // fused PNet (trl_pnet.hip)
-int trl_pnet_prepare(trl_ctx* c);
+int trl_pnet_prepare(trl_ctx* c, const char* himg);   // slope classes and the screen bound, from the host image
 size_t trl_pnet_fused_bytes(trl_ctx* c, int n, int H, int W);
 int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, hipEvent_t* ev, hipStream_t s);
 int trl_pyramid_export(trl_ctx* c, const uint8_t* d_frame, int H, int W, int level, float* d_out, int* h, int* w, hipStream_t s);

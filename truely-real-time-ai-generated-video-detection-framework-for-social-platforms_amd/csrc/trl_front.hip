@@ -549,23 +549,21 @@ __global__ __launch_bounds__(256, 1) void k_mtcnn_front(const uint8_t* __restric
     }
 }
 
-// conv1 PReLU slope class of a net (see MODE above)
-int slope_mode(const DevV* sl, int n) {
-    std::vector<float> h(n);
-    if (hipMemcpy(h.data(), sl->p, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+}  // namespace
+
+// conv1 PReLU slope class of a net (see MODE above), from the loader's host copy of the slopes
+int trl_front_slope_class(const float* h_slope, int n) {
     int mode = 2;
-    for (float v : h) {
-        if (!(v >= 0.f)) return 0;
-        if (!(v <= 1.f)) mode = 1;
+    for (int i = 0; i < n; i++) {
+        if (!(h_slope[i] >= 0.f)) return 0;
+        if (!(h_slope[i] <= 1.f)) mode = 1;
     }
     return mode;
 }
 
-}  // namespace
-
 // One front launch; SKIP: the net's timing-only ablation bits (TRL_FRONT_SKIP: 1/2 = R-Net crop / conv+pool, 4/8 = O-Net), which
 // select the DBG instantiation -- tuning build only.
-#define TRL_FRONT_ARGS d_frames, c->cb.n, H, W, reinterpret_cast<const int4*>(c->cb.cbox), d_total, t0, w->p, b->p, sl->p, d_pool
+#define TRL_FRONT_ARGS d_frames, c->cb.n, H, W, reinterpret_cast<const int4*>(c->cb.cbox), d_total, t0, l.w->p, l.b, l.slope, d_pool
 #ifdef TRL_TUNING
 static int front_dbg() { static const int v = trl_tune_int("TRL_FRONT_SKIP", 0); return v; }
 #define TRL_FRONT(S, C1, R, MODE, SKIP) do { if (SKIP) k_mtcnn_front<S, C1, R, MODE, true><<<nc, 256, 0, s>>>(TRL_FRONT_ARGS, SKIP); \
@@ -574,32 +572,19 @@ static int front_dbg() { static const int v = trl_tune_int("TRL_FRONT_SKIP", 0);
 #define TRL_FRONT(S, C1, R, MODE, SKIP) k_mtcnn_front<S, C1, R, MODE, false><<<nc, 256, 0, s>>>(TRL_FRONT_ARGS, 0)
 #endif
 
-// R-Net front: pooled [nc][11][11][28]
-int trl_launch_rnet_front(trl_ctx* c, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc,
-                          float* d_pool, hipStream_t s) {
+// every slope class of one net's instantiation
+#define TRL_FRONT3(S, C1, R, SKIP) do { if (mode == 2) TRL_FRONT(S, C1, R, 2, SKIP); else if (mode == 1) TRL_FRONT(S, C1, R, 1, SKIP); \
+                                        else TRL_FRONT(S, C1, R, 0, SKIP); } while (0)
+
+int trl_launch_front(trl_ctx* c, const NetDesc& d, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc,
+                     float* d_pool, hipStream_t s) {
     if (nc <= 0) return TRL_OK;
-    const DevW* w = trl_w(c, "rnet.conv1.w");
-    const DevV *b = trl_v(c, "rnet.conv1.b"), *sl = trl_v(c, "rnet.prelu1");
-    if (!w || !b || !sl || w->ld != 32 || w->K != 27) { trl_set_error("rnet.conv1 weights"); return TRL_ERR_WEIGHTS; }
-    if (c->rnet_front_mode < 0) c->rnet_front_mode = slope_mode(sl, 28);
-#define TRL_RF(MODE) TRL_FRONT(24, 28, 4, MODE, front_dbg() & 3)   // four pooled rows per conv1 strip
-    if (c->rnet_front_mode == 2) TRL_RF(2); else if (c->rnet_front_mode == 1) TRL_RF(1); else TRL_RF(0);
-#undef TRL_RF
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
-}
-// O-Net front: pooled [nc][23][23][32]
-int trl_launch_onet_front(trl_ctx* c, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc,
-                          float* d_pool, hipStream_t s) {
-    if (nc <= 0) return TRL_OK;
-    const DevW* w = trl_w(c, "onet.conv1.w");
-    const DevV *b = trl_v(c, "onet.conv1.b"), *sl = trl_v(c, "onet.prelu1");
-    if (!w || !b || !sl || w->ld != 32 || w->K != 27) { trl_set_error("onet.conv1 weights"); return TRL_ERR_WEIGHTS; }
-    if (c->onet_front_mode < 0) c->onet_front_mode = slope_mode(sl, 32);
-    // measured: one pooled row per strip = 49 KB of LDS = three resident workgroups per CU: 1.18 vs 1.27 ms (R = 3, two per CU)
-#define TRL_OF(MODE) TRL_FRONT(48, 32, 1, MODE, (front_dbg() >> 2) & 3)
-    if (c->onet_front_mode == 2) TRL_OF(2); else if (c->onet_front_mode == 1) TRL_OF(1); else TRL_OF(0);
-#undef TRL_OF
+    const NetLayerW& l = c->mt[&d - trl_nets][0];   // conv1 [27][C1] in 32 columns, checked at load
+    const int mode = c->front_mode[&d - trl_nets];
+    // R-Net: four pooled rows per conv1 strip.  O-Net, measured: one pooled row per strip = 49 KB of LDS = three resident
+    // workgroups per CU: 1.18 vs 1.27 ms (R = 3, two per CU)
+    if (d.side == 24) TRL_FRONT3(24, 28, 4, front_dbg() & 3);
+    else TRL_FRONT3(48, 32, 1, (front_dbg() >> 2) & 3);
     TRL_LAUNCH_CHECK();
     return TRL_OK;
 }

@@ -10,6 +10,19 @@
 
 thread_local TrlConvChoice g_trl_conv_choice;
 
+const NetDesc trl_nets[3] = {
+    {"pnet", 0, 5, {{"conv1", "prelu1", 3, 1, 10}, {nullptr, nullptr, 2, 2, 0}, {"conv2", "prelu2", 3, 1, 16}, {"conv3", "prelu3", 3, 1, 32},
+                    {"heads", nullptr, 1, 1, 6}},
+     0, 0, 0, 6, nullptr, 0, 0},   // (its workspace follows the level: trl_pnet_generic_bytes)
+    {"rnet", 24, 7, {{"conv1", "prelu1", 3, 1, 28}, {nullptr, nullptr, 3, 2, 0}, {"conv2", "prelu2", 3, 1, 48}, {nullptr, nullptr, 3, 2, 0},
+                     {"conv3", "prelu3", 2, 1, 64}, {"dense4", "prelu4", 3, 1, 128}, {"heads", nullptr, 1, 1, 6}},
+     2, 11, 28, 6, &trl_ctx::rnet_chunk, 100 * 1024, 40 * 1024},
+    {"onet", 48, 9, {{"conv1", "prelu1", 3, 1, 32}, {nullptr, nullptr, 3, 2, 0}, {"conv2", "prelu2", 3, 1, 64}, {nullptr, nullptr, 3, 2, 0},
+                     {"conv3", "prelu3", 3, 1, 64}, {nullptr, nullptr, 2, 2, 0}, {"conv4", "prelu4", 2, 1, 128}, {"dense5", "prelu5", 3, 1, 256},
+                     {"heads", nullptr, 1, 1, 16}},
+     2, 23, 32, 16, &trl_ctx::onet_chunk, 640 * 1024, 240 * 1024},
+};
+
 namespace {
 
 struct Runner {
@@ -18,7 +31,8 @@ struct Runner {
     int err = TRL_OK;
     const int32_t* m_dev = nullptr;   // device-sized batch (candidate lists): item count lives on the device, see ConvArgs
     int m_base = 0;
-    // FaceNet only: the plan rows of trl_debug_facenet_plan and the armed capture of trl_debug_facenet_capture (conv index = walk order)
+    bool check_only = false;          // trl_load_weights' walk: shapes and tensors only -- alloc() hands out no memory, issue() launches nothing
+    // the plan rows of trl_debug_facenet_plan and the armed capture of trl_debug_facenet_capture (conv index = walk order)
     std::vector<trl_fn_plan_row>* plan = nullptr;
     int nconv = 0;
     std::string layer;                // name of the conv being issued (set by bconv / resid)
@@ -65,6 +79,7 @@ struct Runner {
     Act alloc(int n, int h, int w, int ch, bool bf = false) {
         Act a;
         a.n = n; a.h = h; a.w = w; a.c = ch; a.ld = ch; a.coff = 0; a.bf = bf;
+        if (check_only) return a;
         a.p = (float*)c->scratch.alloc((size_t)n * h * w * ch * (bf ? sizeof(uint16_t) : sizeof(float)) + 64);
         if (!a.p && err == TRL_OK) {
             trl_set_error("activation scratch exhausted (%zu of %zu bytes used)", c->scratch.off, c->scratch.cap);
@@ -106,8 +121,27 @@ struct Runner {
         pending.clear(); pending_meta.clear();
     }
 
+    // Every launch of a walk that is no conv goes out through here
+    template <class F> void issue(F&& launch) {
+        if (check_only || err != TRL_OK) return;
+        const int st = launch();
+        if (st != TRL_OK) err = st;
+    }
+    // A tensor the walk names is required: a miss is TRL_ERR_WEIGHTS (trl_w / trl_v say which), never "this layer has none"
+    const DevW* mat(const std::string& name) {
+        const DevW* w = trl_w(c, name);
+        if (!w && err == TRL_OK) err = TRL_ERR_WEIGHTS;
+        return w;
+    }
+    const float* vec(const std::string& name, const DevW* w) {   // one value per output column of w
+        const DevV* v = trl_v(c, name);
+        if (v && w && v->n != w->Cout) { trl_set_error("weight vector '%s' has %d elements, its conv %d columns", name.c_str(), v->n, w->Cout); v = nullptr; }
+        if (!v && err == TRL_OK) err = TRL_ERR_WEIGHTS;
+        return v ? v->p : nullptr;
+    }
+
     // generic conv launcher; `into` selects a pre-allocated (concat) destination view
-    Act conv(const Act& x, const DevW* w, const DevV* bias, const DevV* scale, const DevV* shift, const DevV* slope,
+    Act conv(const Act& x, const DevW* w, const float* bias, const float* scale, const float* shift, const float* slope,
              int kh, int kw, int sh, int sw, int ph, int pw, int act, const Act* into, const Act* res, float res_scale) {
         const int OH = (x.h + 2 * ph - kh) / sh + 1, OW = (x.w + 2 * pw - kw) / sw + 1;
         Act y = into ? *into : alloc(x.n, OH, OW, w ? w->Cout : 0, x.bf);
@@ -117,12 +151,11 @@ struct Runner {
             err = TRL_ERR_WEIGHTS;
             return y;
         }
+        if (check_only) return y;
         ConvArgs a;
         a.x = x.p; a.N = x.n; a.H = x.h; a.W = x.w; a.Cin = x.c; a.ldx = x.ld; a.xoff = x.coff;
         a.w = w->p; a.ldw = w->ld; a.K = w->K;
-        a.bias = bias ? bias->p : nullptr;
-        a.scale = scale ? scale->p : nullptr; a.shift = shift ? shift->p : nullptr;
-        a.slope = slope ? slope->p : nullptr;
+        a.bias = bias; a.scale = scale; a.shift = shift; a.slope = slope;
         a.res = res ? res->p + res->coff : nullptr; a.ldres = res ? res->ld : 0; a.res_scale = res_scale;
         a.y = y.p; a.ldy = y.ld; a.yoff = y.coff;
         a.KH = kh; a.KW = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw;
@@ -154,33 +187,23 @@ struct Runner {
     // BasicConv2d: conv(no bias) + folded BN + ReLU
     Act bconv(const Act& x, const std::string& name, int kh, int kw, int sh, int sw, int ph, int pw, const Act* into = nullptr) {
         if (plan) layer = name;
-        return conv(x, trl_w(c, name + ".w"), nullptr, trl_v(c, name + ".scale"), trl_v(c, name + ".shift"), nullptr,
-                    kh, kw, sh, sw, ph, pw, TRL_ACT_RELU, into, nullptr, 0.f);
-    }
-    // MTCNN conv (bias) + optional PReLU, valid padding
-    Act mconv(const Act& x, const std::string& net, const std::string& name, const char* prelu, int k) {
-        if (plan) layer = net + "." + name;
-        return conv(x, trl_w(c, net + "." + name + ".w"), trl_v(c, net + "." + name + ".b"), nullptr, nullptr,
-                    prelu ? trl_v(c, net + "." + prelu) : nullptr, k, k, 1, 1, 0, 0, prelu ? TRL_ACT_PRELU : TRL_ACT_NONE,
-                    nullptr, nullptr, 0.f);
+        const DevW* w = mat(name + ".w");
+        return conv(x, w, nullptr, vec(name + ".scale", w), vec(name + ".shift", w), nullptr, kh, kw, sh, sw, ph, pw, TRL_ACT_RELU, into, nullptr, 0.f);
     }
     Act resid(const Act& cat, const Act& x, const std::string& name, float scale, bool relu) {
         if (plan) layer = name;
-        return conv(cat, trl_w(c, name + ".w"), trl_v(c, name + ".b"), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0,
-                    relu ? TRL_ACT_RELU : TRL_ACT_NONE, nullptr, &x, scale);
+        const DevW* w = mat(name + ".w");
+        return conv(cat, w, vec(name + ".b", w), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0, relu ? TRL_ACT_RELU : TRL_ACT_NONE, nullptr, &x, scale);
     }
     Act pool(const Act& x, int k, int st, int ceil_mode, const Act* into = nullptr) {
         const int OH = trl_pool_out(x.h, k, st, ceil_mode), OW = trl_pool_out(x.w, k, st, ceil_mode);
         Act y = into ? *into : alloc(x.n, OH, OW, x.c, x.bf);
         if (err != TRL_OK) return y;
-        if (x.bf) {
-            int e = trl_launch_maxpool_bf16(reinterpret_cast<const uint16_t*>(x.p), x.n, x.h, x.w, x.c, x.ld, x.coff, k, st,
-                                            reinterpret_cast<uint16_t*>(y.p), y.ld, y.coff, OH, OW, s, c->cfg.embed_precision);
-            if (e != TRL_OK) err = e;
-            return y;
-        }
-        int e = trl_launch_maxpool(x.p, x.n, x.h, x.w, x.c, x.ld, x.coff, k, st, ceil_mode, y.p, y.ld, y.coff, OH, OW, s, m_dev, m_base);
-        if (e != TRL_OK) err = e;
+        issue([&] {
+            if (x.bf) return trl_launch_maxpool_bf16(reinterpret_cast<const uint16_t*>(x.p), x.n, x.h, x.w, x.c, x.ld, x.coff, k, st,
+                                                     reinterpret_cast<uint16_t*>(y.p), y.ld, y.coff, OH, OW, s, c->cfg.embed_precision);
+            return trl_launch_maxpool(x.p, x.n, x.h, x.w, x.c, x.ld, x.coff, k, st, ceil_mode, y.p, y.ld, y.coff, OH, OW, s, m_dev, m_base);
+        });
         return y;
     }
 };
@@ -234,20 +257,22 @@ Act block8(Runner& R, const Act& x, const std::string& p, float scale, bool relu
 }  // namespace
 
 // InceptionResnetV1.eval().forward (server/model.py:59)
-int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s) {
+int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s, bool check_only) {
     if (n <= 0) return TRL_OK;
     Runner R{c, s};
-    c->fn_plan.clear();
-    R.plan = &c->fn_plan;
-    if (c->fn_cap_arm >= 0) for (auto& b : c->fn_cap) b.dims[3] = 0;
-    struct Disarm { trl_ctx* c; ~Disarm() { c->fn_cap_arm = -1; } } disarm{c};   // a capture covers one call, whatever its outcome
-    Act x0; x0.p = const_cast<float*>(d_faces); x0.n = n; x0.h = h; x0.w = w; x0.c = 3; x0.ld = 3; x0.coff = 0;
+    R.check_only = check_only;
+    struct Disarm { trl_ctx* c; ~Disarm() { if (c) c->fn_cap_arm = -1; } } disarm{check_only ? nullptr : c};   // a capture covers one call, whatever its outcome
+    if (!check_only) {
+        c->fn_plan.clear();
+        R.plan = &c->fn_plan;
+        if (c->fn_cap_arm >= 0) for (auto& b : c->fn_cap) b.dims[3] = 0;
+    }
+    const Act x0 = Act::dense(d_faces, n, h, w, 3);
     const std::string f = "facenet.";
     Act x = R.bconv(x0, f + "conv2d_1a", 3, 3, 2, 2, 0, 0);
     if (c->cfg.embed_precision >= 1) {   // everything after the 3-channel stem conv runs on 16-bit activations (trl_bf16.hip)
         Act xb = R.alloc(x.n, x.h, x.w, x.c, true);
-        if (R.err != TRL_OK) return R.err;
-        TRL_CHECK(trl_launch_to_bf16(x.p, x.pixels() * x.c, reinterpret_cast<uint16_t*>(xb.p), s, c->cfg.embed_precision));
+        R.issue([&] { return trl_launch_to_bf16(x.p, x.pixels() * x.c, reinterpret_cast<uint16_t*>(xb.p), s, c->cfg.embed_precision); });
         x = xb;
     }
     x = R.bconv(x, f + "conv2d_2a", 3, 3, 1, 1, 0, 0);
@@ -299,88 +324,67 @@ int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const
         g = x;                                   // a 1x1 map IS its average (sum of one element / 1.0f, exact): no kernel
     } else {
         g = R.alloc(n, 1, 1, x.c);
-        if (R.err != TRL_OK) return R.err;
-        if (x.bf) TRL_CHECK(trl_launch_gap_bf16(reinterpret_cast<const uint16_t*>(x.p), n, x.h * x.w, x.c, g.p, s, c->cfg.embed_precision));
-        else TRL_CHECK(trl_launch_gap(x.p, n, x.h * x.w, x.c, g.p, s));
+        R.issue([&] {
+            if (x.bf) return trl_launch_gap_bf16(reinterpret_cast<const uint16_t*>(x.p), n, x.h * x.w, x.c, g.p, s, c->cfg.embed_precision);
+            return trl_launch_gap(x.p, n, x.h * x.w, x.c, g.p, s);
+        });
     }
     R.layer = f + "last_linear";
-    Act e = R.conv(g, trl_w(c, f + "last_linear.w"), nullptr, trl_v(c, f + "last_bn.scale"), trl_v(c, f + "last_bn.shift"),
-                   nullptr, 1, 1, 1, 1, 0, 0, TRL_ACT_NONE, nullptr, nullptr, 0.f);
-    if (R.err != TRL_OK) return R.err;
-    return trl_launch_l2norm512(e.p, d_valid, n, d_emb, s);
-}
-
-// RNet: d_out6[n][6] = {logit0, logit1, reg0..3}
-int trl_run_rnet(trl_ctx* c, const float* d_crops, int n, float* d_out6, hipStream_t s) {
-    if (n <= 0) return TRL_OK;
-    Runner R{c, s};
-    Act x0; x0.p = const_cast<float*>(d_crops); x0.n = n; x0.h = 24; x0.w = 24; x0.c = 3; x0.ld = 3; x0.coff = 0;
-    Act x = R.mconv(x0, "rnet", "conv1", "prelu1", 3);
-    x = R.pool(x, 3, 2, 1);
-    x = R.mconv(x, "rnet", "conv2", "prelu2", 3);
-    x = R.pool(x, 3, 2, 1);
-    x = R.mconv(x, "rnet", "conv3", "prelu3", 2);
-    x = R.mconv(x, "rnet", "dense4", "prelu4", 3);
-    Act out; out.p = d_out6; out.n = n; out.h = 1; out.w = 1; out.c = 6; out.ld = 6; out.coff = 0;
-    R.conv(x, trl_w(c, "rnet.heads.w"), trl_v(c, "rnet.heads.b"), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0,
-           TRL_ACT_NONE, &out, nullptr, 0.f);
+    const DevW* wl = R.mat(f + "last_linear.w");
+    Act e = R.conv(g, wl, nullptr, R.vec(f + "last_bn.scale", wl), R.vec(f + "last_bn.shift", wl), nullptr, 1, 1, 1, 1, 0, 0, TRL_ACT_NONE, nullptr, nullptr, 0.f);
+    R.issue([&] { return trl_launch_l2norm512(e.p, d_valid, n, d_emb, s); });
     return R.err;
 }
 
-// ONet: d_out16[n][16] = {logit0, logit1, reg0..3, landmarks0..9}
-int trl_run_onet(trl_ctx* c, const float* d_crops, int n, float* d_out16, hipStream_t s) {
-    if (n <= 0) return TRL_OK;
+// The one walker of the MTCNN nets (contract: trl_ctx.h)
+int trl_run_net(trl_ctx* c, const NetDesc& d, int first, const Act& x0, float* d_out, hipStream_t s, const int32_t* m_dev, int m_base) {
+    if (x0.n <= 0) return TRL_OK;
     Runner R{c, s};
-    Act x0; x0.p = const_cast<float*>(d_crops); x0.n = n; x0.h = 48; x0.w = 48; x0.c = 3; x0.ld = 3; x0.coff = 0;
-    Act x = R.mconv(x0, "onet", "conv1", "prelu1", 3);
-    x = R.pool(x, 3, 2, 1);
-    x = R.mconv(x, "onet", "conv2", "prelu2", 3);
-    x = R.pool(x, 3, 2, 1);
-    x = R.mconv(x, "onet", "conv3", "prelu3", 3);
-    x = R.pool(x, 2, 2, 1);
-    x = R.mconv(x, "onet", "conv4", "prelu4", 2);
-    x = R.mconv(x, "onet", "dense5", "prelu5", 3);
-    Act out; out.p = d_out16; out.n = n; out.h = 1; out.w = 1; out.c = 16; out.ld = 16; out.coff = 0;
-    R.conv(x, trl_w(c, "onet.heads.w"), trl_v(c, "onet.heads.b"), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0,
-           TRL_ACT_NONE, &out, nullptr, 0.f);
-    return R.err;
-}
-
-// R-Net from the fused front end's pooled map [n][11][11][28]
-int trl_run_rnet_tail(trl_ctx* c, const float* d_pool1, int n, float* d_out6, hipStream_t s, const int32_t* n_dev, int n_base) {
-    if (n <= 0) return TRL_OK;
-    Runner R{c, s};
-    R.m_dev = n_dev; R.m_base = n_base;
+    R.m_dev = m_dev; R.m_base = m_base;
     if (c->mt_plan_arm) { R.plan = &c->mt_plan; R.nconv = (int)c->mt_plan.size(); }   // trl_debug_stage_net: rows of every chunk
-    Act x; x.p = const_cast<float*>(d_pool1); x.n = n; x.h = 11; x.w = 11; x.c = 28; x.ld = 28; x.coff = 0;
-    x = R.mconv(x, "rnet", "conv2", "prelu2", 3);
-    x = R.pool(x, 3, 2, 1);
-    x = R.mconv(x, "rnet", "conv3", "prelu3", 2);
-    x = R.mconv(x, "rnet", "dense4", "prelu4", 3);
-    Act out; out.p = d_out6; out.n = n; out.h = 1; out.w = 1; out.c = 6; out.ld = 6; out.coff = 0;
-    if (R.plan) R.layer = "rnet.heads";
-    R.conv(x, trl_w(c, "rnet.heads.w"), trl_v(c, "rnet.heads.b"), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0,
-           TRL_ACT_NONE, &out, nullptr, 0.f);
+    const NetLayerW* lw = c->mt[&d - trl_nets];
+    Act x = x0;
+    for (int i = first; i < d.nl; i++) {
+        const NetLayer& L = d.layer[i];
+        if (!L.name) { x = R.pool(x, L.k, L.st, 1); continue; }
+        if (R.plan) R.layer = std::string(d.name) + "." + L.name;
+        const Act out = Act::dense(d_out, x.n, x.h - L.k + 1, x.w - L.k + 1, d.nout);
+        x = R.conv(x, lw[i].w, lw[i].b, nullptr, nullptr, lw[i].slope, L.k, L.k, 1, 1, 0, 0, L.prelu ? TRL_ACT_PRELU : TRL_ACT_NONE,
+                   i == d.nl - 1 ? &out : nullptr, nullptr, 0.f);
+    }
     return R.err;
 }
-// O-Net from the fused front end's pooled map [n][23][23][32]
-int trl_run_onet_tail(trl_ctx* c, const float* d_pool1, int n, float* d_out16, hipStream_t s, const int32_t* n_dev, int n_base) {
-    if (n <= 0) return TRL_OK;
-    Runner R{c, s};
-    R.m_dev = n_dev; R.m_base = n_base;
-    if (c->mt_plan_arm) { R.plan = &c->mt_plan; R.nconv = (int)c->mt_plan.size(); }   // trl_debug_stage_net: rows of every chunk
-    Act x; x.p = const_cast<float*>(d_pool1); x.n = n; x.h = 23; x.w = 23; x.c = 32; x.ld = 32; x.coff = 0;
-    x = R.mconv(x, "onet", "conv2", "prelu2", 3);
-    x = R.pool(x, 3, 2, 1);
-    x = R.mconv(x, "onet", "conv3", "prelu3", 3);
-    x = R.pool(x, 2, 2, 1);
-    x = R.mconv(x, "onet", "conv4", "prelu4", 2);
-    x = R.mconv(x, "onet", "dense5", "prelu5", 3);
-    Act out; out.p = d_out16; out.n = n; out.h = 1; out.w = 1; out.c = 16; out.ld = 16; out.coff = 0;
-    if (R.plan) R.layer = "onet.heads";
-    R.conv(x, trl_w(c, "onet.heads.w"), trl_v(c, "onet.heads.b"), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0,
-           TRL_ACT_NONE, &out, nullptr, 0.f);
-    return R.err;
+
+// trl_load_weights: every tensor trl_nets[] names exists with the shape its layer gives it -- K = k k Cin, cout columns, cout
+// biases and slopes -- and is resolved into c->mt; then what the kernels choose by: the conv1 slope class of the front kernel
+int trl_resolve_nets(trl_ctx* c, const char* himg) {
+    for (int id = 0; id < 3; id++) {
+        const NetDesc& d = trl_nets[id];
+        int cin = 3;
+        for (int i = 0; i < d.nl; i++) {
+            const NetLayer& L = d.layer[i];
+            c->mt[id][i] = NetLayerW();
+            if (!L.name) continue;
+            const std::string net = std::string(d.name) + ".", base = net + L.name;
+            const DevW* w = trl_w(c, base + ".w");
+            const DevV* b = trl_v(c, base + ".b");
+            const DevV* sl = L.prelu ? trl_v(c, net + L.prelu) : nullptr;
+            if (!w || !b || (L.prelu && !sl)) return TRL_ERR_WEIGHTS;   // (trl_w / trl_v named it)
+            if (w->K != L.k * L.k * cin || w->Cout != L.cout) {
+                trl_set_error("tensor '%s.w' is [%d][%d], its layer needs [%d][%d]", base.c_str(), w->K, w->Cout, L.k * L.k * cin, L.cout);
+                return TRL_ERR_WEIGHTS;
+            }
+            if (b->n != L.cout || (sl && sl->n != L.cout)) {
+                trl_set_error("tensor '%s' has %d elements, its layer %d channels", b->n != L.cout ? (base + ".b").c_str() : (net + L.prelu).c_str(),
+                              b->n != L.cout ? b->n : sl->n, L.cout);
+                return TRL_ERR_WEIGHTS;
+            }
+            c->mt[id][i] = NetLayerW{w, b->p, sl ? sl->p : nullptr};
+            cin = L.cout;
+        }
+        if (d.side) c->front_mode[id] = trl_front_slope_class(trl_host_of(c, himg, c->mt[id][0].slope), d.layer[0].cout);
+    }
+    return TRL_OK;
 }
 
 size_t trl_pnet_generic_bytes(int nf, int h, int w) {
@@ -389,16 +393,3 @@ size_t trl_pnet_generic_bytes(int nf, int h, int w) {
     return (size_t)nf * (c1 + p1 + c2 + c3) * sizeof(float) + 4096;
 }
 
-// PNet through the generic layer kernels (validation path / fallback): heads [nf][oh][ow][6]
-int trl_run_pnet_generic(trl_ctx* c, const float* d_level, int nf, int h, int w, float* d_heads, hipStream_t s) {
-    Runner R{c, s};
-    Act x0; x0.p = const_cast<float*>(d_level); x0.n = nf; x0.h = h; x0.w = w; x0.c = 3; x0.ld = 3; x0.coff = 0;
-    Act x = R.mconv(x0, "pnet", "conv1", "prelu1", 3);
-    x = R.pool(x, 2, 2, 1);
-    x = R.mconv(x, "pnet", "conv2", "prelu2", 3);
-    x = R.mconv(x, "pnet", "conv3", "prelu3", 3);
-    Act out; out.p = d_heads; out.n = nf; out.h = x.h; out.w = x.w; out.c = 6; out.ld = 6; out.coff = 0;
-    R.conv(x, trl_w(c, "pnet.heads.w"), trl_v(c, "pnet.heads.b"), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0,
-           TRL_ACT_NONE, &out, nullptr, 0.f);
-    return R.err;
-}

@@ -960,16 +960,11 @@ __global__ void k_pnet_span(unsigned long long* clk) {
 // subnormal kept or flushed), the MFMA sums 145 terms in an unspecified order (taken at 2u per addition), the exact chain is 145
 // fmaf; PReLU is Lipschitz with max(1, |slope|); the exact heads are two 33-term chains and a subtraction, the screened
 // difference head one 36-term chain over f32(w1 - w0).  Double precision, then A and B rounded up (tools/pnet_screen_audit.py
-// states the same bound, tests/test_pnet_screen_cpu.py compares the two).
-static int pnet_screen_bound(trl_ctx* c, const DevW* w3, const DevW* wh) {
-    std::vector<float> W(144 * 32), H(32 * 32), b3(32), s3(32), bh(8);
-    TRL_HIP(hipMemcpy(W.data(), w3->p, W.size() * sizeof(float), hipMemcpyDeviceToHost));
-    TRL_HIP(hipMemcpy(H.data(), wh->p, H.size() * sizeof(float), hipMemcpyDeviceToHost));
-    TRL_HIP(hipMemcpy(b3.data(), trl_v(c, "pnet.conv3.b")->p, 32 * sizeof(float), hipMemcpyDeviceToHost));
-    TRL_HIP(hipMemcpy(s3.data(), trl_v(c, "pnet.prelu3")->p, 32 * sizeof(float), hipMemcpyDeviceToHost));
-    TRL_HIP(hipMemcpy(bh.data(), trl_v(c, "pnet.heads.b")->p, 2 * sizeof(float), hipMemcpyDeviceToHost));
+// states the same bound, tests/test_pnet_screen_cpu.py compares the two).  W [144][32], H [32][32] (zero padded), b3, s3, bh: the
+// loader's host copies of conv3.w, heads.w, conv3.b, prelu3, heads.b.
+static void pnet_screen_bound(trl_ctx* c, const float* W, const float* H, const float* b3, const float* s3, const float* bh) {
     c->pnet_screen_ok = 0; c->pnet_scrA = c->pnet_scrB = __builtin_inff();
-    for (float v : W) if (!(fabsf(v) <= 65504.f)) return TRL_OK;          // a weight fp16 cannot hold: no screen for this net
+    for (int i = 0; i < 144 * 32; i++) if (!(fabsf(W[i]) <= 65504.f)) return;   // a weight fp16 cannot hold: no screen for this net
     const double u = ldexp(1.0, -24), uh = ldexp(1.0, -11), tiny = ldexp(1.0, -14);
     auto gamma = [](int n, double uu) { return n * uu / (1.0 - n * uu); };
     const double ge = gamma(145, u), gs = gamma(145, 2 * u), g35 = gamma(35, u), g36 = gamma(36, u);
@@ -998,31 +993,24 @@ static int pnet_screen_bound(trl_ctx* c, const DevW* w3, const DevW* wh) {
     const double A = (g35 * Sa + ad) * (1 + ldexp(1.0, -10)), B = (g35 * Sb + bd) * (1 + ldexp(1.0, -10));
     auto up = [](double v) { float f = (float)v; return (double)f < v ? nextafterf(f, __builtin_inff()) : f; };
     c->pnet_scrA = up(A); c->pnet_scrB = up(B); c->pnet_screen_ok = 1;
-    return TRL_OK;
 }
 
-int trl_pnet_prepare(trl_ctx* c) {
-    for (const char* n : {"pnet.conv1.w", "pnet.conv2.w", "pnet.conv3.w", "pnet.heads.w"}) {
-        const DevW* w = trl_w(c, n);
-        if (!w || w->ld != 32) { trl_set_error("PNet weight %s missing or wrong shape", n); return TRL_ERR_WEIGHTS; }
+// PNet's layers in c->mt (trl_resolve_nets has checked their shapes: [27][10], [90][16], [144][32], [32][6], each in 32 columns)
+enum { PN_CONV1 = 0, PN_CONV2 = 2, PN_CONV3 = 3, PN_HEADS = 4 };
+
+int trl_pnet_prepare(trl_ctx* c, const char* himg) {
+    const NetLayerW* l = c->mt[TRL_PNET];
+    auto host = [&](const float* dev) { return trl_host_of(c, himg, dev); };
+    c->pnet_mono1 = c->pnet_unit = 1;
+    for (int i : {PN_CONV1, PN_CONV2, PN_CONV3}) {
+        const float* sl = host(l[i].slope);
+        for (int k = 0; k < l[i].w->Cout; k++) {
+            if (i == PN_CONV1 && !(sl[k] >= 0.f)) c->pnet_mono1 = 0;
+            if (!(sl[k] <= 1.f)) c->pnet_unit = 0;
+        }
     }
-    const DevW *w1 = trl_w(c, "pnet.conv1.w"), *w2 = trl_w(c, "pnet.conv2.w"), *w3 = trl_w(c, "pnet.conv3.w"), *wh = trl_w(c, "pnet.heads.w");
-    if (w1->K != 27 || w1->Cout != 10 || w2->K != 90 || w2->Cout != 16 || w3->K != 144 || w3->Cout != 32 || wh->K != 32 || wh->Cout != 6) {
-        trl_set_error("PNet weights have unexpected shapes");
-        return TRL_ERR_WEIGHTS;
-    }
-    float sl[10];
-    TRL_HIP(hipMemcpy(sl, trl_v(c, "pnet.prelu1")->p, sizeof sl, hipMemcpyDeviceToHost));
-    c->pnet_mono1 = 1;
-    for (float v : sl) if (!(v >= 0.f)) c->pnet_mono1 = 0;
-    c->pnet_unit = 1;
-    for (const char* n : {"pnet.prelu1", "pnet.prelu2", "pnet.prelu3"}) {
-        const DevV* v = trl_v(c, n);
-        std::vector<float> h(v->n);
-        TRL_HIP(hipMemcpy(h.data(), v->p, h.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (float x : h) if (!(x <= 1.f)) c->pnet_unit = 0;
-    }
-    return pnet_screen_bound(c, w3, wh);
+    pnet_screen_bound(c, host(l[PN_CONV3].w->p), host(l[PN_HEADS].w->p), host(l[PN_CONV3].b), host(l[PN_CONV3].slope), host(l[PN_HEADS].b));
+    return TRL_OK;
 }
 
 // ceil(2^32 / d) for the kernel's sdiv(); d == 1 would need 2^32: 2^32 - 1 gives q = n - 1 (or 0), which sdiv's upward correction
@@ -1049,9 +1037,10 @@ static void fill_args(trl_ctx* c, int n, int H, int W, const PyrLayout& lay, con
     }
     a.tiles_per_frame = tiles;
     a.tpf_magic = sdiv_magic(tiles);
-    a.w1 = trl_w(c, "pnet.conv1.w")->p; a.w2 = trl_w(c, "pnet.conv2.w")->p; a.w3 = trl_w(c, "pnet.conv3.w")->p; a.wh = trl_w(c, "pnet.heads.w")->p;
-    a.b1 = trl_v(c, "pnet.conv1.b")->p; a.b2 = trl_v(c, "pnet.conv2.b")->p; a.b3 = trl_v(c, "pnet.conv3.b")->p; a.bh = trl_v(c, "pnet.heads.b")->p;
-    a.s1 = trl_v(c, "pnet.prelu1")->p; a.s2 = trl_v(c, "pnet.prelu2")->p; a.s3 = trl_v(c, "pnet.prelu3")->p;
+    const NetLayerW* l = c->mt[TRL_PNET];
+    a.w1 = l[PN_CONV1].w->p; a.w2 = l[PN_CONV2].w->p; a.w3 = l[PN_CONV3].w->p; a.wh = l[PN_HEADS].w->p;
+    a.b1 = l[PN_CONV1].b; a.b2 = l[PN_CONV2].b; a.b3 = l[PN_CONV3].b; a.bh = l[PN_HEADS].b;
+    a.s1 = l[PN_CONV1].slope; a.s2 = l[PN_CONV2].slope; a.s3 = l[PN_CONV3].slope;
     a.thr = c->cfg.thr0; a.rec_stride = c->cb.lay.S;
     // p = softmax(logit0, logit1)[1] >= thr needs logit1 - logit0 >= ln(thr / (1 - thr)) up to the rounding of the float softmax
     // (~1e-6 relative); 0.05 below that bound the probability is short of thr by 0.05 thr (1 - thr) >= 4.9e-4 for thr in [0.01, 0.99]

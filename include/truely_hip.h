@@ -411,11 +411,13 @@ int  trl_jpegd_debug_poison(trl_jpegd* dec, int byte);
 /* n files: file k is sizes[k] bytes at offsets[k] of a buffer that the caller holds twice, on the host (h_files: the headers
  * are parsed there, and the restart markers of DRI streams are located there) and on the device (d_files: the entropy-coded
  * bytes are read there and nowhere else).  Frame k goes to d_bgr + k * frame_stride as u8 BGR [H][W][3].  h_status[k]: 0 decoded
- * on the device; 1 not attempted (unsupported or malformed headers, a size other than the decoder's, more than 16 distinct table
- * sets or 2^20 restart intervals in one call); 2 the entropy decoder met something irregular (an invalid code, a run past
- * coefficient 63, bytes running out, an unexpected marker, bytes left over) or a dequantised value outside int16.  A frame with
- * status 1 or 2 has no byte written.  TRL_ERR_INVALID with nothing queued: n > max_frames, a file outside the buffer, a stride
- * below H*W*3 when n > 1.  All work is queued on `stream`; the call returns after one synchronisation (to read the statuses). */
+ * on the device; 1 not attempted (unsupported or malformed headers, a size other than the decoder's, more than 2^20 restart
+ * intervals in one call); 2 the entropy decoder met something irregular (an invalid code, a run past coefficient 63, bytes
+ * running out, an unexpected marker, bytes left over) or a block holds coefficients outside the IDCT's gate (values at which
+ * 16-bit and 32-bit arithmetic part; no encoder makes them from pixels).  A frame with status 1 or 2 has no byte written.
+ * TRL_ERR_INVALID with nothing queued: n > max_frames, a file outside the buffer, a stride below H*W*3 when n > 1.  All work is
+ * queued on `stream`; the call returns after one synchronisation to read the statuses; where a file brings a 17th distinct
+ * table set (a clip normally has one), the call goes on from that file as a second pass with a synchronisation of its own. */
 int  trl_jpegd_decode(trl_jpegd* dec, const uint8_t* h_files, const uint8_t* d_files, const long long* offsets, const long long* sizes,
                       int n, uint8_t* d_bgr, long long frame_stride, int32_t* h_status, void* stream);
 

@@ -12,10 +12,16 @@ default decompression path (JDCT_ISLOW, fancy upsampling, no merged upsampling, 
   component's downsampled_width x downsampled_height (plain replication when downsampled_width <= 2, as jinit_upsampler chooses),
   jdcolor.c's 16-bit-fixed YCbCr -> RGB tables.
 
-libjpeg-turbo's SIMD IDCT multiplies coefficient and quantiser in 16 bits while its C code uses a long, so the two differ once a
-dequantised value leaves the int16 range.  No encoder makes such a value from pixels (|value| stays near 1024); a stream that holds
-one is ``Irregular`` here and on the device, and Pillow decides what that frame is.  The IDCT below is int32 arithmetic that wraps,
-which is what the kernel computes; within the int16 gate and for coefficients an encoder made from pixels nothing wraps."""
+The IDCT below is int32 arithmetic that wraps and a range-limit mask, which is what the kernel computes and what jidctint.c's C
+code computes on a long as long as nothing wraps.  Pillow's libjpeg-turbo runs a SIMD IDCT instead: 16-bit products, 16-bit sums in
+front of its multiplies, a saturated 16-bit workspace after pass 1 and a saturated 8-bit result.  The three agree only while no
+value reaches a point where one of them wraps or saturates, and a dequantised value inside int16 does not ensure that (a white
+frame whose DC quantiser is 8 has a DC of 8128 and an output of 1016 + 128: the mask wraps it, the SIMD code saturates it).  So
+``idct_islow`` carries the kernel's gate ("The IDCT gate"), tested on exact values before anything can have
+wrapped: in either pass the sums |x0| + |x4|, |x2| + |x6| and |x1| + |x3| + |x5| + |x7| of a column's / row's inputs stay within
+32767 (that bounds the dequantised values too), every pass-1 output lies in int16, and every descaled result lies in
+[-512, 511], the range the mask leaves alone.  A block outside any of these makes the frame ``Irregular`` here and on the device,
+and Pillow decides what that frame is.  No encoder makes such a block from pixels."""
 import numpy as np
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
@@ -257,16 +263,30 @@ def _idct_1d(x, shift):
     return np.stack([(o + rnd) >> shift for o in out])
 
 
-def idct_islow(coef, quant):
-    """(by, bx, 64) int16 natural order, quant (64,) -> u8 plane (by*8, bx*8)."""
+def _pass_wide(x):
+    """The kernel's jd_pass_wide on axis 0 of x (8, ...): a 16-bit sum in front of a multiply may leave int16."""
+    a = np.abs(x)
+    return bool(((a[0] + a[4] > 32767) | (a[2] + a[6] > 32767) | (a[1] + a[3] + a[5] + a[7] > 32767)).any())
+
+
+def idct_islow(coef, quant, gate=True):
+    """(by, bx, 64) int16 natural order, quant (64,) -> u8 plane (by*8, bx*8).  gate=False: the arithmetic alone, as it was before
+    the gate (for counting what the gate turns away)."""
     by, bx = coef.shape[:2]
-    v = coef.astype(np.int32) * quant.astype(np.int32)
-    if v.size and (np.abs(v) > 32767).any():
-        raise Irregular("dequantised value outside int16")
+    v = coef.astype(np.int32) * quant.astype(np.int32)                # |int16 x u8| < 2^23: exact
     with np.errstate(over="ignore"):
-        x = v.reshape(by, bx, 8, 8)                                   # [.., row, col]
-        ws = _idct_1d(np.moveaxis(x, 2, 0), 11)                       # columns: axis 0 = row index -> (8 rows, by, bx, col)
-        out = _idct_1d(np.moveaxis(ws, 3, 0), 18)                     # rows: axis 0 = col index -> (8 cols, 8 rows, by, bx)
+        x = np.moveaxis(v.reshape(by, bx, 8, 8), 2, 0)                # [row, by, bx, col]: columns are transformed first
+        if gate and _pass_wide(x):
+            raise Irregular("pass 1: a 16-bit input sum outside int16")
+        ws = _idct_1d(x, 11)                                          # (8 rows, by, bx, col)
+        if gate and ((ws < -32768) | (ws > 32767)).any():
+            raise Irregular("pass 1: workspace outside int16")
+        x = np.moveaxis(ws, 3, 0)                                     # [col, row, by, bx]
+        if gate and _pass_wide(x):
+            raise Irregular("pass 2: a 16-bit input sum outside int16")
+        out = _idct_1d(x, 18)                                         # (8 cols, 8 rows, by, bx)
+    if gate and ((out < -512) | (out > 511)).any():
+        raise Irregular("descaled value outside [-512, 511]")
     s = out & 1023
     s = np.where(s >= 512, s - 1024, s)
     px = np.clip(s + 128, 0, 255).astype(np.uint8)                    # [col, row, by, bx]
@@ -322,12 +342,12 @@ def color_bgr(y, cb, cr):
     return np.clip(np.stack([b, g, r], -1), 0, 255).astype(np.uint8)
 
 
-def decode(data):
+def decode(data, gate=True):
     """A JPEG file -> BGR u8 (H, W, 3); Unsupported / Irregular where the device decoder reports status 1 / 2."""
     info = parse(data)
     H, W, hs, vs = info["H"], info["W"], info["hs"], info["vs"]
     coefs = entropy_decode(data, info)
-    planes = [idct_islow(coefs[c], info["quant"][c]) for c in range(3)]
+    planes = [idct_islow(coefs[c], info["quant"][c], gate) for c in range(3)]
     dw, dh = (W + hs - 1) // hs, (H + vs - 1) // vs
     if (hs, vs) == (2, 2):
         cb, cr = (upsample_h2v2(planes[c], dw, dh) for c in (1, 2))

@@ -141,10 +141,46 @@ def test_sentinels_and_damaged_files_in_a_batch():
         seen.add(int(status[k]))
         if want == 0:
             assert np.array_equal(frame, ref), kinds[k]
+            assert np.array_equal(frame, cases.pillow_bgr(files[k])), f"{kinds[k]}: status 0 but not Pillow's bytes"
         else:
             assert (frame == 0xA5).all(), f"{kinds[k]}: status {status[k]} but bytes were written"
     assert (got[n * (fb + gap):] == 0xA5).all()
     assert {1, 2} <= seen
+
+
+@pytest.mark.parametrize("sub", [0, 1, 2])
+@pytest.mark.parametrize("size", cases.SYN_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_synthetic_table(size, sub):
+    """Streams no encoder writes from pixels (edited headers, hand-coded scans, coefficients up to and past the IDCT gate), one call
+    per size and subsampling with more table sets than the call's cache of 16 holds and a gated frame between good ones wherever
+    there is one: a "pillow" frame has status 0 and Pillow's bytes, a "gated" frame status 2 and its poison, as have the gaps."""
+    W, H = size
+    table = cases.synthetic_files(W, H, sub)
+    good, gated = [r for r in table if r[2] == "pillow"], [r for r in table if r[2] == "gated"]
+    assert len(good) > len(gated) >= 40
+    rows = [good[0]]
+    for k, g in enumerate(gated):
+        rows += [g, good[1 + k]]
+    rows += good[1 + len(gated):]
+    files = [d for _, d, _ in rows]
+    assert len({cases.table_set(d) for d in files}) > 16
+    n = len(files)
+    dec = jpeg.DeviceJpegDecoder(W, H, max_frames=n)
+    fb, gap = H * W * 3, 96
+    out = torch.full((n * (fb + gap) + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
+    rc, status = raw_decode(dec, files, out, fb + gap)
+    assert rc == 0, _lib.load().trl_last_error()
+    got = out.cpu().numpy()
+    wrong = [(label, expect, int(st)) for (label, _, expect), st in zip(rows, status) if st != (0 if expect == "pillow" else 2)]
+    assert not wrong, wrong
+    for k, (label, data, expect) in enumerate(rows):
+        frame = got[k * (fb + gap):k * (fb + gap) + fb].reshape(H, W, 3)
+        assert (got[k * (fb + gap) + fb:(k + 1) * (fb + gap)] == 0xA5).all(), f"gap after frame {k}"
+        if expect == "pillow":
+            assert np.array_equal(frame, cases.pillow_bgr(data)), label
+        else:
+            assert (frame == 0xA5).all(), f"{label}: status 2 but bytes were written"
+    assert (got[n * (fb + gap):] == 0xA5).all()
 
 
 def test_refusals_write_nothing():
@@ -327,6 +363,27 @@ def test_run_progressive_frame_goes_through_the_fallback(probe, tmp_path):
         b = io.BytesIO()
         Image.fromarray(np.ascontiguousarray(f[:, :, ::-1])).save(b, "JPEG", quality=92, progressive=True)
         return b.getvalue()
+    src = str(tmp_path / "clip.avi")
+    write_avi(src, clip, edit=edit)
+    for write_out in (False, True):
+        dev, _ = compare_paths(probe, src, write_out, fallback_frames=1)
+        assert (16, False) in dev["reads"]                 # the fallback read that chunk again, for Pillow
+        assert dev["frame_count"] == 36
+
+
+def test_run_gated_frame_goes_through_the_fallback(probe, tmp_path):
+    """A sampled frame whose quantisers were multiplied by 16: regular baseline JPEG inside the former int16 gate, with outputs far
+    outside what the IDCT's range limit leaves alone.  The device reports it irregular and Pillow decides what it is."""
+    H, W = 180, 320
+    probe.hw = (H, W)
+    clip = truely_amd.synthetic.synthetic_frames(36, H, W, seed=3)
+
+    def edit(k, data, f):
+        if k != 16:
+            return data
+        out = cases.rescaled(data, lambda t, i, q: 16 * q)
+        assert cases.gate_expectation(out) == "gated" and not cases.former_gate_trips(out)
+        return out
     src = str(tmp_path / "clip.avi")
     write_avi(src, clip, edit=edit)
     for write_out in (False, True):

@@ -4,7 +4,11 @@
 path; these tests pin it to Pillow's bytes over sizes, subsamplings, qualities, content and encoder options chosen to reach every
 edge case (partial edge MCUs, one-sample chroma, stuffed 0xFF bytes, optimised tables, restart intervals with RST7 -> RST0), pin
 ``trl_jpegd_parse`` (host-only C ABI) to what Pillow reads from the same headers, and run the decoder's parser and its shared
-entropy-decode function in a stand-alone, sanitized host program over a fixed table of damaged streams."""
+entropy-decode function in a stand-alone, sanitized host program over a fixed table of damaged streams.
+
+The synthetic table (``jpegd_cases.synthetic_files``) holds what Pillow's encoder never writes: edited headers, scans coded by the
+tests' own baseline writer, and coefficients large enough to reach the IDCT gate.  Its "pillow" streams must decode to Pillow's
+bytes, its "gated" streams must be refused."""
 import io
 import os
 import shutil
@@ -158,3 +162,140 @@ def test_fuzz_program_damaged_files(fuzz_program, tmp_path):
         seen.add(status)
     assert {1, 2} <= seen
     print("sanitized" if sanitized else "built without sanitizers")
+
+
+# ---- the synthetic table ---------------------------------------------------------------------------------------------------------
+SYN = pytest.mark.parametrize("size,sub", [(s, sub) for s in cases.SYN_SIZES for sub in (0, 1, 2)], ids=lambda v: f"{v[0]}x{v[1]}" if isinstance(v, tuple) else f"sub{v}")
+
+
+@SYN
+def test_writer_round_trip(size, sub):
+    """The reference's entropy decoder returns from every written file the coefficients the writer was given."""
+    n = 0
+    for label, data, _ in cases.synthetic_files(*size, sub):
+        want = cases.written_coefficients(data)
+        if want is not None:
+            assert np.array_equal(ref_coefficients(data), want), label
+            n += 1
+    assert n >= 40
+
+
+@pytest.mark.parametrize("sub", [0, 1, 2])
+def test_writer_covers_the_entropy_cases(sub):
+    """At 64 x 48 the written scans hold every DC category 0..11, AC categories 1..10, zero runs of 16, 32 and 47, blocks without
+    EOB and blocks of a DC alone, 16-bit codes, stuffed bytes, and more than eight restart intervals (RST7 -> RST0)."""
+    seen = {}
+    table = cases.entropy_files(64, 48, sub, seen)
+    assert seen["dc"] == set(range(12))
+    assert {s & 15 for s in seen["ac"]} >= set(range(1, 11)) and {0x00, 0xF0} <= seen["ac"]
+    assert {16, 32, 47} <= seen["zrl"]
+    assert min(seen["len"]) == 2 and max(seen["len"]) == 16
+    assert seen["rst"] == set(range(0xD0, 0xD8))
+    files = dict(table)
+    contents = dict(cases.entropy_contents(64, 48, *cases.SUB_HV[sub]))
+    assert any(b[63] != 0 for blocks in cases.coded_blocks(contents["zrl-and-no-eob"], *cases.SUB_HV[sub]) for b in blocks)
+    assert any(not b[1:].any() for blocks in cases.coded_blocks(contents["zrl-and-no-eob"], *cases.SUB_HV[sub]) for b in blocks)
+    for label, data in table:
+        info = jpegd_ref.parse(data)
+        scan = data[info["scan"]:]
+        if label == "dense-stuffed-std-ri0":                       # (the content was chosen for this file; others stuff by chance)
+            assert b"\xff\x00" in scan, label
+        marks = [scan[i + 1] for i in range(len(scan) - 1) if scan[i] == 0xFF and 0xD0 <= scan[i + 1] <= 0xD7]
+        mcus = 8 * 6 // (info["hs"] * info["vs"])
+        assert len(marks) == ((mcus - 1) // info["ri"] if info["ri"] else 0), label
+        if label.endswith("-ri1"):
+            assert len(marks) > 8 and marks[7:9] == [0xD7, 0xD0]
+    intervals = {jpegd_ref.parse(d)["ri"] for d in files.values()}
+    mcus = 8 * 6 // (cases.SUB_HV[sub][0] * cases.SUB_HV[sub][1])
+    assert {0, 1} <= intervals and any(r > mcus for r in intervals) and any(1 < r < mcus and mcus % r for r in intervals)
+
+
+@SYN
+def test_synthetic_files_in_the_reference(size, sub):
+    """Every "pillow" stream decodes in the restatement to Pillow's bytes, every "gated" stream raises Irregular; neither half of
+    the magnitude family is a token one, and all but a handful of its streams passed the former gate."""
+    W, H = size
+    table = cases.synthetic_files(W, H, sub)
+    count = {"pillow": 0, "gated": 0}
+    differ = former = 0
+    for label, data, expect in table:
+        pil = cases.pillow_bgr(data)
+        assert pil.shape == (H, W, 3)
+        if expect == "pillow":
+            assert np.array_equal(jpegd_ref.decode(data), pil), label
+        else:
+            with pytest.raises(jpegd_ref.Irregular):
+                jpegd_ref.decode(data)
+            differ += not np.array_equal(jpegd_ref.decode(data, gate=False), pil)
+        if label.startswith("magnitude-"):
+            count[expect] += 1
+            former += cases.former_gate_trips(data)
+            assert cases.gate_expectation(data) == expect, label      # the expectations written by hand follow from the conditions
+        else:
+            assert expect == "pillow" and cases.gate_expectation(data) == "pillow", label
+    total = sum(count.values())
+    assert 3 * count["pillow"] >= total and 3 * count["gated"] >= total, count
+    assert former <= 3
+    # evidence, not a contract: it depends on whether this Pillow's libjpeg-turbo runs a SIMD IDCT
+    print(f"{W}x{H} subsampling {sub}: the arithmetic without the gate decodes {differ} of {count['gated']} gated streams to other bytes than Pillow")
+
+
+def test_gate_edges_of_a_dc_only_block():
+    """(dc + 4) >> 3 is a DC-only block's output: the streams on either side of 511 | 512 and -512 | -513 are in the table, the inner
+    ones owed to Pillow and the outer ones gated; single AC coefficients have their pairs too."""
+    by_value = {q * c: e for q, c, e in cases.DC_EDGES}
+    assert [(v, (v + 4) >> 3, by_value[v]) for v in (4090, 4092, -4100, -4101)] == [
+        (4090, 511, "pillow"), (4092, 512, "gated"), (-4100, -512, "pillow"), (-4101, -513, "gated")]
+    table = {label: e for label, _, e in cases.synthetic_files(17, 17, 2)}
+    for pos in cases.AC_POSITIONS:
+        edge = cases._ac_edge(pos)
+        assert [table[f"magnitude-ac{pos}-16x{c}"] for c in (edge, edge + 1, -edge, -edge - 1)] == ["pillow", "gated", "pillow", "gated"]
+
+
+@pytest.mark.parametrize("sub", [0, 1, 2])
+def test_parse_on_edited_headers(sub):
+    """trl_jpegd_parse agrees with the reference parser and with what Pillow reads on every header edit."""
+    for W, H in cases.SYN_SIZES:
+        for label, data in cases.header_edit_files(W, H, sub):
+            info = jpeg.jpeg_info(data)
+            ref = jpegd_ref.parse(data)
+            im = Image.open(io.BytesIO(data))
+            assert info["supported"] == 1 and info["reason"] == 0, (W, H, label, info)
+            assert (info["width"], info["height"]) == im.size == (ref["W"], ref["H"]) == (W, H), label
+            assert (info["h_samp"], info["v_samp"]) == _pillow_sampling(im) == (ref["hs"], ref["vs"]) == cases.SUB_HV[sub], label
+            assert info["restart_interval"] == ref["ri"] and info["scan_offset"] == ref["scan"], label
+            assert (ref["ri"] != 0) == (label in ("fill-bytes-rst", "marker-like-segments-fill", "dri-twice")), label
+
+
+def test_rgb_component_ids_stay_unsupported():
+    for label, data in cases.rgb_id_files():
+        info = jpeg.jpeg_info(data)
+        assert info["supported"] == 0 and info["reason"] == jpegd_ref.R_COMPONENTS, (label, info)
+        with pytest.raises(jpegd_ref.Unsupported) as e:
+            jpegd_ref.parse(data)
+        assert e.value.reason == jpegd_ref.R_COMPONENTS
+
+
+@pytest.mark.parametrize("sub", [0, 1, 2])
+def test_fuzz_program_synthetic_files(fuzz_program, tmp_path, sub):
+    """The shared entropy-decode function, built for the CPU: the coefficients the writer was given, and for edited Pillow files
+    the reference's (the IDCT gate is not its business: gated streams decode here too)."""
+    program, _ = fuzz_program
+    table = [row for size in cases.SYN_SIZES for row in cases.synthetic_files(*size, sub)]
+    for (label, data, _), (status, coef) in zip(table, run_fuzz(program, [d for _, d, _ in table], str(tmp_path))):
+        assert status == 0, label
+        want = cases.written_coefficients(data)
+        assert np.array_equal(coef, ref_coefficients(data) if want is None else want), label
+
+
+def test_damaged_files_that_decode_equal_pillow():
+    """Wherever the restatement decodes a damaged stream, it decodes what Pillow decodes."""
+    n = 0
+    for label, data in cases.damaged_files():
+        try:
+            got = jpegd_ref.decode(data)
+        except (jpegd_ref.Unsupported, jpegd_ref.Irregular):
+            continue
+        assert np.array_equal(got, cases.pillow_bgr(data)), label
+        n += 1
+    assert n >= 10

@@ -8,12 +8,13 @@
 //                   whole wave, lane 0 runs jpegd_decode_segment (trl_jpegd_huff.h) and writes the non-zero coefficients as
 //                   int16 into the zeroed coefficient slot of its frame.  The batch supplies the parallelism.
 //   k_jpegd_idct    one thread per 8x8 block: dequantise, jidctint.c's jpeg_idct_islow, u8 sample planes padded to whole MCUs.
-//                   A dequantised value outside int16 (no encoder makes one from pixels; libjpeg-turbo's SIMD and C code differ
-//                   there) marks the frame irregular.
+//                   A block that reaches a value at which jidctint.c's arithmetic on a long, this kernel's wrapping 32-bit
+//                   arithmetic and a saturating 16-bit SIMD IDCT can part (no encoder makes one from pixels) marks the frame
+//                   irregular: the gate of DESIGN.md section 7.
 //   k_jpegd_color   one thread per pixel: jdsample.c's h2v2 / h2v1 fancy upsampling on the component's own width and height,
 //                   jdcolor.c's 16-bit-fixed YCbCr -> RGB, three bytes written once.  Frames whose status is not 0 are skipped.
 //
-// A frame that is not attempted (status 1) or whose entropy decode is irregular (status 2) has no byte written; the caller
+// A frame that is not attempted (status 1) or whose entropy decode or coefficients are irregular (status 2) has no byte written; the caller
 // decodes it with Pillow.  All work is queued on the caller's stream, nothing is allocated inside a call, and the call
 // synchronises once, to read the statuses.
 #include "trl_common.h"
@@ -90,6 +91,13 @@ __device__ __forceinline__ uint32_t jd_range_limit(int v) {      // sample_range
     return (uint32_t)min(max(s + 128, 0), 255);
 }
 
+// One 1-D pass's inputs: true where a sum that jidctint.c forms from them before it multiplies (x0 +- x4, x2 + x6, and among the
+// odd inputs x7 + x1, x5 + x3, x7 + x3, x5 + x1 and the sum of all four) may leave int16.  The inputs are exact and, in pass 1,
+// below 2^23 in magnitude, so the tests themselves cannot wrap.
+__device__ __forceinline__ bool jd_pass_wide(const int (&x)[8]) {
+    return abs(x[0]) + abs(x[4]) > 32767 || abs(x[2]) + abs(x[6]) > 32767 || abs(x[1]) + abs(x[3]) + abs(x[5]) + abs(x[7]) > 32767;
+}
+
 __global__ __launch_bounds__(64) void k_jpegd_idct(const int16_t* __restrict__ coef, size_t coef_stride, const JdFrame* __restrict__ frames,
                                                    const JdTables* __restrict__ tabs, int H, int W, int f0, uint8_t* __restrict__ planes,
                                                    size_t plane_stride, int* __restrict__ status) {
@@ -104,31 +112,35 @@ __global__ __launch_bounds__(64) void k_jpegd_idct(const int16_t* __restrict__ c
     const int by = rel / g.bw[c], bx = rel - by * g.bw[c];
     const uint4* cp = (const uint4*)(coef + (size_t)fi * coef_stride + (size_t)blk * 64);
     const uint4* qp = (const uint4*)tabs[fr.tabset].quant[c];
-    uint32_t v[8][8];
-    bool wide = false;
+    int v[8][8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const uint4 cw = cp[r], qw = qp[r];
         const uint32_t cs[4] = {cw.x, cw.y, cw.z, cw.w}, qs[4] = {qw.x, qw.y, qw.z, qw.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int lo = (int)(int16_t)(cs[j] & 0xFFFF) * (int)(qs[j] & 0xFFFF);
-            const int hi = (int)(int16_t)(cs[j] >> 16) * (int)(qs[j] >> 16);
-            wide |= lo > 32767 || lo < -32767 || hi > 32767 || hi < -32767;
-            v[r][2 * j] = (uint32_t)lo;
-            v[r][2 * j + 1] = (uint32_t)hi;
+            v[r][2 * j] = (int)(int16_t)(cs[j] & 0xFFFF) * (int)(qs[j] & 0xFFFF);      // |int16 x u16| < 2^31: exact
+            v[r][2 * j + 1] = (int)(int16_t)(cs[j] >> 16) * (int)(qs[j] >> 16);
         }
     }
-    if (wide) { atomicMax(&status[f], JD_ST_IRREGULAR); return; }
+    // The gate ("The IDCT gate"): every test is made on exact values, before anything can have wrapped.
+    bool wide = false;
     int ws[8][8];
 #pragma unroll
     for (int col = 0; col < 8; ++col) {
-        const uint32_t x[8] = {v[0][col], v[1][col], v[2][col], v[3][col], v[4][col], v[5][col], v[6][col], v[7][col]};
+        const int in[8] = {v[0][col], v[1][col], v[2][col], v[3][col], v[4][col], v[5][col], v[6][col], v[7][col]};
+        wide |= jd_pass_wide(in);
+        const uint32_t x[8] = {(uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3],
+                               (uint32_t)in[4], (uint32_t)in[5], (uint32_t)in[6], (uint32_t)in[7]};
         int o[8];
         jd_idct_1d<11>(x, o);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) ws[r][col] = o[r];
+        for (int r = 0; r < 8; ++r) {
+            wide |= (uint32_t)(o[r] + 32768) > 65535u;                  // the workspace as a 16-bit quantity (dc << 2 included)
+            ws[r][col] = o[r];
+        }
     }
+    if (wide) { atomicMax(&status[f], JD_ST_IRREGULAR); return; }       // (before pass 2: its inputs must be known to be 16 bit)
     const int pw = g.bw[c] * 8;
     size_t pbase = 0;                                                   // planes: Y, Cb, Cr, each padded to whole MCUs
     if (c >= 1) pbase += (size_t)g.bw[0] * 8 * g.mcuy * g.vs * 8;
@@ -136,15 +148,19 @@ __global__ __launch_bounds__(64) void k_jpegd_idct(const int16_t* __restrict__ c
     uint8_t* dst = planes + (size_t)fi * plane_stride + pbase + (size_t)by * 8 * pw + (size_t)bx * 8;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
+        wide |= jd_pass_wide(ws[r]);
         const uint32_t x[8] = {(uint32_t)ws[r][0], (uint32_t)ws[r][1], (uint32_t)ws[r][2], (uint32_t)ws[r][3],
                                (uint32_t)ws[r][4], (uint32_t)ws[r][5], (uint32_t)ws[r][6], (uint32_t)ws[r][7]};
         int o[8];
         jd_idct_1d<18>(x, o);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wide |= (uint32_t)(o[j] + 512) > 1023u;    // the range the mask leaves alone
         uint2 w;
         w.x = jd_range_limit(o[0]) | jd_range_limit(o[1]) << 8 | jd_range_limit(o[2]) << 16 | jd_range_limit(o[3]) << 24;
         w.y = jd_range_limit(o[4]) | jd_range_limit(o[5]) << 8 | jd_range_limit(o[6]) << 16 | jd_range_limit(o[7]) << 24;
-        *(uint2*)(dst + (size_t)r * pw) = w;
+        *(uint2*)(dst + (size_t)r * pw) = w;                            // (a plane is workspace: k_jpegd_color skips a gated frame)
     }
+    if (wide) atomicMax(&status[f], JD_ST_IRREGULAR);
 }
 
 // One chroma sample at output pixel (x, y): jdsample.c's fancy upsampling on the component's dw x dh samples (pw = row pitch).
@@ -324,7 +340,7 @@ int trl_jpegd_decode(trl_jpegd* d, const uint8_t* h_files, const uint8_t* d_file
     // ---- host: headers, tables, segments ----
     static thread_local JdParsed ps;
     static thread_local JdTables tb;
-    int ntab = 0;
+    int ntab = 0, n_now = n;                                             // frames [0, n_now) are decoded by this pass
     size_t nseg = 0;
     for (int k = 0; k < n; ++k) {
         d->seg_first[k] = nseg;
@@ -338,7 +354,7 @@ int trl_jpegd_decode(trl_jpegd* d, const uint8_t* h_files, const uint8_t* d_file
         int t = 0;
         while (t < ntab && memcmp(&d->h_tabs[t], &tb, sizeof(tb)) != 0) ++t;
         if (t == ntab) {
-            if (ntab == kMaxTabSets) continue;
+            if (ntab == kMaxTabSets) { n_now = k; break; }               // the table cache is full: the rest is a call of its own
             memcpy(&d->h_tabs[ntab++], &tb, sizeof(tb));
         }
         const JdGeom g = jd_geom(d->H, d->W, ps.hs, ps.vs);
@@ -348,16 +364,16 @@ int trl_jpegd_decode(trl_jpegd* d, const uint8_t* h_files, const uint8_t* d_file
         d->h_frames[k] = JdFrame{t, ps.hs, ps.vs, 0};
         d->h_status[k] = JD_ST_OK;
     }
-    d->seg_first[n] = nseg;
+    d->seg_first[n_now] = nseg;
 
     // ---- device ----
-    TRL_HIP(hipMemcpyAsync(d->d_frames, d->h_frames, (size_t)n * sizeof(JdFrame), hipMemcpyHostToDevice, s));
-    TRL_HIP(hipMemcpyAsync(d->d_status, d->h_status, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    TRL_HIP(hipMemcpyAsync(d->d_frames, d->h_frames, (size_t)n_now * sizeof(JdFrame), hipMemcpyHostToDevice, s));
+    TRL_HIP(hipMemcpyAsync(d->d_status, d->h_status, (size_t)n_now * sizeof(int), hipMemcpyHostToDevice, s));
     if (ntab) TRL_HIP(hipMemcpyAsync(d->d_tabs, d->h_tabs, (size_t)ntab * sizeof(JdTables), hipMemcpyHostToDevice, s));
     if (nseg) TRL_HIP(hipMemcpyAsync(d->d_segs, d->h_segs, nseg * sizeof(JdSeg), hipMemcpyHostToDevice, s));
     const int max_blocks = (int)(d->coef_stride / 64);
-    for (int f0 = 0; f0 < n && nseg; f0 += d->chunk) {
-        const int cn = std::min(d->chunk, n - f0);
+    for (int f0 = 0; f0 < n_now && nseg; f0 += d->chunk) {
+        const int cn = std::min(d->chunk, n_now - f0);
         const size_t s0 = d->seg_first[f0], s1 = d->seg_first[f0 + cn];
         if (s1 == s0) continue;
         TRL_HIP(hipMemsetAsync(d->coef, 0, (size_t)cn * d->coef_stride * 2, s));
@@ -371,9 +387,12 @@ int trl_jpegd_decode(trl_jpegd* d, const uint8_t* h_files, const uint8_t* d_file
                            d->d_frames, d->d_status, d->H, d->W, f0, d_bgr, frame_stride);
         TRL_LAUNCH_CHECK();
     }
-    TRL_HIP(hipMemcpyAsync(d->h_status, d->d_status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    TRL_HIP(hipMemcpyAsync(d->h_status, d->d_status, (size_t)n_now * sizeof(int), hipMemcpyDeviceToHost, s));
     TRL_HIP(hipStreamSynchronize(s));
-    memcpy(h_status, d->h_status, (size_t)n * sizeof(int));
+    memcpy(h_status, d->h_status, (size_t)n_now * sizeof(int));
+    if (n_now < n)                                                       // (the stream is idle: the pinned tables may be rewritten)
+        return trl_jpegd_decode(d, h_files, d_files, offsets + n_now, sizes + n_now, n - n_now, d_bgr + (size_t)n_now * frame_stride,
+                                frame_stride, h_status + n_now, stream);
     return TRL_OK;
 }
 

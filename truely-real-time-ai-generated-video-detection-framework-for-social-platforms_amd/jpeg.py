@@ -117,7 +117,7 @@ class DeviceJpegDecoder:
 
     ``decode(files)``: a list of n JPEG files (``bytes``) -> ``(frames, status)``: a uint8 device tensor (n, H, W, 3) in BGR and a
     numpy array of n statuses -- 0 decoded on the device, 1 not attempted (progressive, grayscale, another size, ...), 2 the
-    entropy decoder met something irregular.  A frame whose status is not 0 is left unwritten (zero here): the caller decodes it
+    entropy decoder met something irregular or a block lies outside the IDCT's gate (coefficients no encoder makes from pixels).  A frame whose status is not 0 is left unwritten (zero here): the caller decodes it
     with Pillow.  The object has its own stream, workspace and pinned staging; batches above ``max_frames`` are split.
 
     ``decode_into(h_arena, d_arena, offsets, sizes, out)`` is the form ``run()`` uses: the files already lie in a pinned host

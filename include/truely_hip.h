@@ -138,6 +138,21 @@ int  trl_extract_faces(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, int 
  *   d_emb   : f32 [n][512], L2-normalised */
 int  trl_facenet_embed(trl_ctx* ctx, const float* d_faces, int n, int h, int w, float* d_emb, void* stream);
 
+/* InceptionResnetV1(classify=True): the checkpoint's `logits` layer (vggface2: 512 -> 8631 classes, casia-webface: 10575), when the
+ * blob holds it ("facenet.logits.w" [512][C] and "facenet.logits.b" [C], both or neither, 1 <= C <= 65535: trl_load_weights
+ * refuses anything else).  (ABI v7, additive)
+ * trl_facenet_num_classes: *C = classes of the loaded checkpoint's logits layer; *C = 0 when the blob has none.
+ * trl_facenet_features: InceptionResnetV1 up to and including last_bn -- what F.normalize / logits read.  d_faces as
+ *   trl_facenet_embed; d_valid nullable (zero rows where !valid, as trl_facenet_embed_masked); d_feat f32 [n][512].
+ * trl_facenet_logits: logits = feat @ W + b for n rows: d_logits f32, row r at d_logits + r*ld, ld >= C; columns C..ld-1 are
+ *   not written.  logit[r][c] is the f32 chain acc = b[c]; k = 0..511 ascending: acc = fmaf(feat[r][k], W[k][c], acc), whatever
+ *   n (always f32, also under embed_precision 1 / 2).  No host synchronisation.
+ * Refusals as trl_facenet_embed's: a context with a call in flight or without weights TRL_ERR_STATE; a blob without logits
+ * TRL_ERR_WEIGHTS ("the loaded checkpoint has no logits layer"); null pointers, n < 1, ld < C TRL_ERR_INVALID, nothing launched. */
+int  trl_facenet_num_classes(trl_ctx* ctx, int* C);
+int  trl_facenet_features(trl_ctx* ctx, const float* d_faces, const uint8_t* d_valid, int n, int h, int w, float* d_feat, void* stream);
+int  trl_facenet_logits(trl_ctx* ctx, const float* d_feat, int n, float* d_logits, long long ld, void* stream);
+
 /* server/model.py:47-59 fused for a batch of sampled frames: detect, take boxes[0], int-cast +
  * clamp (model.py:49-53), crop, cv2.resize(...,(80,80)) (model.py:55-57), to_tensor (model.py:58),
  * embed (model.py:59).

@@ -42,6 +42,9 @@ _SIGNATURES = {
     "trl_select_faces": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, C.c_double, _vp, _vp]),
     "trl_extract_faces": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "trl_facenet_embed": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "trl_facenet_num_classes": (C.c_int, [_vp, C.POINTER(_i)]),
+    "trl_facenet_features": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "trl_facenet_logits": (C.c_int, [_vp, _vp, _i, _vp, C.c_longlong, _vp]),
     "trl_detect_embed": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "trl_detect_crop": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "trl_detect_embed_begin": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -259,10 +259,30 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
     TRL_CHECK(concat_cols("pnet.heads", {"pnet.conv4_1", "pnet.conv4_2"}, {".b"}));
     TRL_CHECK(concat_cols("rnet.heads", {"rnet.dense5_1", "rnet.dense5_2"}, {".b"}));
     TRL_CHECK(concat_cols("onet.heads", {"onet.dense6_1", "onet.dense6_2", "onet.dense6_3"}, {".b"}));
+    // InceptionResnetV1's classifier is optional (a blob packed from a checkpoint without `logits`, or with include_logits=False):
+    // both tensors or neither, w [512][C] and b [C], 1 <= C <= 65535 (the kernel's grid.y carries the class groups)
+    const char* const lw_name = "facenet.logits.w";
+    const char* const lb_name = "facenet.logits.b";
+    {
+        auto iw = idx.find(lw_name), ib = idx.find(lb_name);
+        const char* bad = nullptr;
+        if (iw != idx.end() || ib != idx.end()) {
+            if (iw == idx.end()) { trl_set_error("missing tensor %s (the blob holds %s)", lw_name, lb_name); bad = lw_name; }
+            else if (ib == idx.end()) { trl_set_error("missing tensor %s (the blob holds %s)", lb_name, lw_name); bad = lb_name; }
+            else if (iw->second->ndim != 2 || iw->second->dims[0] != 512 || iw->second->dims[1] < 1 || iw->second->dims[1] > 65535) {
+                trl_set_error("tensor '%s' must be [512][C] with 1 <= C <= 65535", lw_name);
+                bad = lw_name;
+            } else if (ib->second->ndim != 1 || ib->second->dims[0] != iw->second->dims[1]) {
+                trl_set_error("tensor '%s' must hold the %u biases of %s", lb_name, iw->second->dims[1], lw_name);
+                bad = lb_name;
+            }
+        }
+        if (bad) { c->have_weights = false; return TRL_ERR_WEIGHTS; }   // (a refused blob leaves the context without weights)
+    }
 
     if (c->cfg.embed_precision == 2) {   // an fp16 conv weight that rounds past +-65504 would become inf: refuse the blob instead
         for (auto& p : items) {
-            if (!p.mat || p.name.rfind("facenet.", 0) != 0 || p.name == "facenet.conv2d_1a.w" || p.name == "facenet.last_linear.w") continue;
+            if (!p.mat || p.name.rfind("facenet.", 0) != 0 || p.name == "facenet.conv2d_1a.w" || p.name == "facenet.last_linear.w" || p.name == lw_name) continue;
             for (size_t i = 0; i < (size_t)p.K * p.Cout; i++)
                 if (!(fabsf(p.src[i]) < 65520.f)) {   // 65520 is the rounding midpoint to the next (infinite) binade; NaN fails too
                     trl_set_error("weight %s[%zu] = %g is outside the fp16 range", p.name.c_str(), i, p.src[i]);
@@ -283,6 +303,7 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
     c->wbytes = total;
     for (auto& kv : c->W) if (kv.second.pt) (void)hipFree(kv.second.pt);
     c->W.clear(); c->V.clear();
+    c->logits_w = nullptr; c->logits_b = nullptr; c->num_classes = 0;
     for (auto& p : items) {
         if (p.mat) { DevW w; w.p = (float*)(c->wdev + p.off); w.K = p.K; w.Cout = p.Cout; w.Kpad = p.Kpad; w.ld = p.ld; c->W[p.name] = w; }
         else { DevV v; v.p = (float*)(c->wdev + p.off); v.n = p.n; c->V[p.name] = v; }
@@ -294,10 +315,15 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
     TRL_CHECK(trl_resolve_nets(c, host.data()));
     TRL_CHECK(trl_pnet_prepare(c, host.data()));
     TRL_CHECK(trl_run_facenet(c, nullptr, 1, 160, 160, nullptr, nullptr, nullptr, true));
-    if (c->cfg.embed_precision >= 1) {   // bf16 / fp16 copies of the embedder's conv weights (all but the 3-channel stem and the final linear)
+    if (idx.count(lw_name)) {                        // (shapes checked above)
+        c->logits_w = trl_w(c, lw_name);
+        c->logits_b = trl_v(c, lb_name)->p;
+        c->num_classes = c->logits_w->Cout;
+    }
+    if (c->cfg.embed_precision >= 1) {   // bf16 / fp16 copies of the embedder's conv weights (all but the 3-channel stem, the final linear and the classifier)
         for (auto& kv : c->W) {
             const std::string& nm = kv.first;
-            if (nm.rfind("facenet.", 0) != 0 || nm == "facenet.conv2d_1a.w" || nm == "facenet.last_linear.w") continue;
+            if (nm.rfind("facenet.", 0) != 0 || nm == "facenet.conv2d_1a.w" || nm == "facenet.last_linear.w" || nm == lw_name) continue;
             TRL_CHECK(trl_make_weight_bf16(&kv.second, nullptr, c->cfg.embed_precision));
         }
         TRL_HIP(hipDeviceSynchronize());
@@ -511,16 +537,16 @@ int trl_detect_embed_end(trl_ctx* c) { return call_wait(c); }
 
 }  // extern "C"
 
-// trl_facenet_embed / _masked: d_valid nullable (zero rows where it is 0)
+// trl_facenet_embed / _masked / trl_facenet_features: d_valid nullable (zero rows where it is 0)
 static int facenet_embed(trl_ctx* c, const float* d_faces, const uint8_t* d_valid, bool masked, int n, int h, int w, float* d_emb,
-                         void* stream) {
+                         void* stream, bool features = false) {
     if (!c || !c->have_weights) { trl_set_error("context without weights"); return TRL_ERR_STATE; }
     TRL_CHECK(trl_check_idle(c));
     if (!d_faces || (masked && !d_valid) || !d_emb || n <= 0 || h < 75 || w < 75) { trl_set_error("bad face batch n=%d %dx%d (min 75x75)", n, h, w); return TRL_ERR_INVALID; }
     TRL_HIP(hipSetDevice(c->cfg.device));
     c->scratch.reset();
     TRL_CHECK(trl_ensure(c, c->scratch, trl_facenet_bytes(n, h, w)));
-    TRL_CHECK(trl_run_facenet(c, d_faces, n, h, w, d_valid, d_emb, (hipStream_t)stream));
+    TRL_CHECK(trl_run_facenet(c, d_faces, n, h, w, d_valid, d_emb, (hipStream_t)stream, false, features));
     return trl_gate_record(c, (hipStream_t)stream);
 }
 
@@ -544,6 +570,29 @@ int trl_facenet_embed(trl_ctx* c, const float* d_faces, int n, int h, int w, flo
 
 int trl_facenet_embed_masked(trl_ctx* c, const float* d_faces, const uint8_t* d_valid, int n, int h, int w, float* d_emb, void* stream) {
     return facenet_embed(c, d_faces, d_valid, true, n, h, w, d_emb, stream);
+}
+
+int trl_facenet_features(trl_ctx* c, const float* d_faces, const uint8_t* d_valid, int n, int h, int w, float* d_feat, void* stream) {
+    return facenet_embed(c, d_faces, d_valid, false, n, h, w, d_feat, stream, true);
+}
+
+int trl_facenet_num_classes(trl_ctx* c, int* C) {
+    if (!c || !C) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
+    if (!c->have_weights) { trl_set_error("context without weights"); return TRL_ERR_STATE; }
+    *C = c->num_classes;
+    return TRL_OK;
+}
+
+int trl_facenet_logits(trl_ctx* c, const float* d_feat, int n, float* d_logits, long long ld, void* stream) {
+    if (!c || !c->have_weights) { trl_set_error("context without weights"); return TRL_ERR_STATE; }
+    TRL_CHECK(trl_check_idle(c));
+    if (!c->logits_w) { trl_set_error("the loaded checkpoint has no logits layer"); return TRL_ERR_WEIGHTS; }
+    if (!d_feat || !d_logits || n < 1 || ld < c->num_classes) {
+        trl_set_error("bad logits call n=%d ld=%lld (%d classes)", n, ld, c->num_classes);
+        return TRL_ERR_INVALID;
+    }
+    TRL_HIP(hipSetDevice(c->cfg.device));
+    return trl_launch_logits(d_feat, n, c->logits_w->p, c->logits_w->ld, c->logits_b, c->num_classes, d_logits, ld, (hipStream_t)stream);
 }
 
 int trl_drift_score(trl_ctx* c, const float* d_emb, const uint8_t* d_valid, int n, long long frame_count, int fps, float* d_sims,

@@ -179,6 +179,10 @@ int trl_launch_maxpool_bf16(const uint16_t* x, int N, int H, int W, int C, int l
                             int yoff, int OH, int OW, hipStream_t s, int fmt = 1);
 int trl_launch_gap_bf16(const uint16_t* x, int N, int HW, int C, float* y, hipStream_t s, int fmt = 1);
 int trl_launch_l2norm512(const float* x, const uint8_t* valid, int n, float* y, hipStream_t s);
+int trl_launch_feat512(const float* x, const uint8_t* valid, int n, float* y, hipStream_t s);   // the rows as they are, zeros where !valid
+// the classifier head (trl_logits.hip): y[r * ld + c] = chain(bias[c]; k ascending: fmaf(feat[r][k], w[k * ldw + c])), r < n, c < C
+// (n <= 16 takes a 16-row kernel, n > 16 a 32-row one: the same bits)
+int trl_launch_logits(const float* feat, int n, const float* w, int ldw, const float* bias, int C, float* y, long long ld, hipStream_t s);
 int trl_launch_drift(const float* emb, const uint8_t* valid, int n, long long frame_count, int fps,
                      float* sims, uint8_t* flags, int32_t* result, hipStream_t s, void* state = nullptr);
 

@@ -80,6 +80,10 @@ struct trl_ctx {
     // trl_nets[] and the conv1 PReLU slope class of R-Net / O-Net (trl_front.hip).  No MTCNN path looks a tensor up by name.
     NetLayerW mt[3][9];
     int front_mode[3] = {0, 0, 0};
+    // InceptionResnetV1's classifier, when the blob holds one ("facenet.logits.w" [512][C] / ".b" [C], both or neither): always f32
+    const DevW* logits_w = nullptr;
+    const float* logits_b = nullptr;
+    int num_classes = 0;
     Arena arena;                     // per-call persistent blocks (cascade lists)
     Arena scratch;                   // transient activations; only ever grown while empty
     Arena sims_tmp;                  // similarities when trl_drift_score is called with d_sims == NULL
@@ -167,7 +171,9 @@ const DevV* trl_v(trl_ctx* c, const std::string& name);
 
 // networks (trl_nets.hip)
 // check_only: the walk of trl_load_weights -- shapes and tensors are checked, nothing is allocated, launched or copied
-int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s, bool check_only = false);
+// features: d_emb receives the 512 values in front of F.normalize (last_bn's output) instead of the embedding
+int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s, bool check_only = false,
+                    bool features = false);
 inline size_t trl_facenet_bytes(int n, int h, int w) { return (size_t)n * ((size_t)h * w * 110 + 400000) * 4 + (8u << 20); }   // its scratch
 // Layers first .. last of net d over x (x.n items; the maps of layer `first`): d_out [x.n][oh][ow][d.nout].  With m_dev, x.n is the
 // CAPACITY of the launch and the items that exist are clamp(*m_dev - m_base, 0, x.n) (device-sized, no host sync).  While

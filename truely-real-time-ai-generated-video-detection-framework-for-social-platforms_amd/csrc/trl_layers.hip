@@ -671,6 +671,14 @@ __global__ __launch_bounds__(64) void l2norm512_kernel(const float* __restrict__
     for (int i = 0; i < 8; i++) o[lane + 64 * i] = v[lane + 64 * i] / nrm;
 }
 
+// trl_facenet_features: what l2norm512_kernel reads, copied out (zero rows where !valid)
+__global__ __launch_bounds__(64) void feat512_kernel(const float* __restrict__ x, const uint8_t* __restrict__ valid, int n, float* __restrict__ y) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    if (row >= n) return;
+    const bool live = !valid || valid[row];
+    for (int i = 0; i < 8; i++) y[(size_t)row * 512 + lane + 64 * i] = live ? x[(size_t)row * 512 + lane + 64 * i] : 0.f;
+}
+
 // Carry of the drift state machine between consecutive windows of one clip (trl_drift_update): what model.py's loop variables
 // `previous_embedding`, `consecutive_count` and `ai_detected_frames` hold between two sampled frames (model.py:60-75).
 struct DriftState {
@@ -818,6 +826,13 @@ int trl_launch_gap(const float* x, int N, int HW, int C, float* y, hipStream_t s
 int trl_launch_l2norm512(const float* x, const uint8_t* valid, int n, float* y, hipStream_t s) {
     if (n <= 0) return TRL_OK;
     l2norm512_kernel<<<n, 64, 0, s>>>(x, valid, n, y);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
+int trl_launch_feat512(const float* x, const uint8_t* valid, int n, float* y, hipStream_t s) {
+    if (n <= 0) return TRL_OK;
+    feat512_kernel<<<n, 64, 0, s>>>(x, valid, n, y);
     TRL_LAUNCH_CHECK();
     return TRL_OK;
 }

@@ -257,7 +257,7 @@ Act block8(Runner& R, const Act& x, const std::string& p, float scale, bool relu
 }  // namespace
 
 // InceptionResnetV1.eval().forward (server/model.py:59)
-int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s, bool check_only) {
+int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s, bool check_only, bool features) {
     if (n <= 0) return TRL_OK;
     Runner R{c, s};
     R.check_only = check_only;
@@ -332,7 +332,8 @@ int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const
     R.layer = f + "last_linear";
     const DevW* wl = R.mat(f + "last_linear.w");
     Act e = R.conv(g, wl, nullptr, R.vec(f + "last_bn.scale", wl), R.vec(f + "last_bn.shift", wl), nullptr, 1, 1, 1, 1, 0, 0, TRL_ACT_NONE, nullptr, nullptr, 0.f);
-    R.issue([&] { return trl_launch_l2norm512(e.p, d_valid, n, d_emb, s); });
+    // (features: the walk ends in front of the normalisation -- trl_facenet_features, what the logits layer reads)
+    R.issue([&] { return features ? trl_launch_feat512(e.p, d_valid, n, d_emb, s) : trl_launch_l2norm512(e.p, d_valid, n, d_emb, s); });
     return R.err;
 }
 

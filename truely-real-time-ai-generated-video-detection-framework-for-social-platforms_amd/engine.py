@@ -193,6 +193,34 @@ class Engine:
         _lib.check(self.lib.trl_facenet_embed(self._h, _ptr(faces), n, h, w, _ptr(emb), self._stream()))
         return emb
 
+    # InceptionResnetV1(classify=True): the trunk up to last_bn, then the checkpoint's logits layer
+    @property
+    def num_classes(self) -> int:
+        """Classes of the loaded checkpoint's logits layer; 0 when the blob holds none."""
+        c = C.c_int(0)
+        _lib.check(self.lib.trl_facenet_num_classes(self._h, C.byref(c)))
+        return int(c.value)
+
+    def facenet_features(self, faces: torch.Tensor, valid: torch.Tensor | None = None) -> torch.Tensor:
+        """(n, 512): what ``F.normalize`` and ``logits`` read (last_bn's output); zero rows where ``valid`` is 0."""
+        faces = faces.to(self.device, torch.float32).contiguous()
+        if valid is not None:
+            valid = valid.to(self.device, torch.uint8).contiguous()
+        n, h, w, _ = faces.shape
+        feat = torch.empty((n, 512), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.trl_facenet_features(self._h, _ptr(faces), _ptr(valid), n, h, w, _ptr(feat), self._stream()))
+        return feat
+
+    def facenet_logits(self, feat: torch.Tensor) -> torch.Tensor:
+        """(n, C) = feat @ W + b in f32, one fma chain over ascending k per logit."""
+        feat = feat.to(self.device, torch.float32).contiguous()
+        if feat.dim() != 2 or feat.shape[1] != 512:
+            raise ValueError("expected (n, 512) features")
+        n, nc = feat.shape[0], self.num_classes
+        out = torch.empty((n, nc), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.trl_facenet_logits(self._h, _ptr(feat), n, _ptr(out), nc, self._stream()))
+        return out
+
     def _call_outputs(self, n: int, crop: bool, faces: torch.Tensor | None = None, valid: torch.Tensor | None = None) -> dict:
         """The outputs of a detect_embed (``emb``) / detect_crop (``faces``) call on n frames: new tensors, or the caller's
         ``faces`` / ``valid`` (checked)."""

@@ -4,7 +4,8 @@
     emb = facenet_model(face_tensor).detach().numpy().flatten()          # server/model.py:59
 
 ``__call__`` takes the ``(n, 3, H, W)`` float tensor that ``to_tensor`` produced and returns an
-``(n, 512)`` L2-normalised tensor on the input's device.  No checkpoint can be downloaded in the
+``(n, 512)`` L2-normalised tensor on the input's device -- or, with ``classify=True`` (at construction, or by setting the
+attribute later), the ``(n, C)`` logits of the checkpoint's classifier.  No checkpoint can be downloaded in the
 build environment, so ``pretrained`` only selects which packed weight blob the engine holds
 (TRUELY_WEIGHTS, else seeded synthetic weights)."""
 from __future__ import annotations
@@ -17,10 +18,20 @@ from .engine import Engine, default_engine
 class InceptionResnetV1:
     def __init__(self, pretrained=None, classify=False, num_classes=None, dropout_prob=0.6, device=None,
                  engine: Engine | None = None):
-        if classify:
-            raise NotImplementedError("classify=True (logits head) is not on the reference's hot path")
         self.pretrained = pretrained
         self.engine = engine or default_engine()
+        self.classify = bool(classify)
+        self.num_classes = self.engine.num_classes or None     # (dropout_prob: the model is eval-only here)
+        if num_classes is not None and self.num_classes is not None and int(num_classes) != self.num_classes:
+            raise ValueError(f"num_classes={num_classes}, but the engine's checkpoint has {self.num_classes} classes")
+        if self.classify:
+            self._need_logits()
+
+    def _need_logits(self):
+        if not self.engine.num_classes:
+            raise ValueError("classify=True needs a checkpoint with a logits layer: pack one that has `logits.weight` / "
+                             "`logits.bias` and point TRUELY_WEIGHTS at it, or build the engine from "
+                             "weights.synthetic_state_dicts(num_classes=...)")
 
     def eval(self):
         return self
@@ -37,5 +48,9 @@ class InceptionResnetV1:
             raise ValueError("expected (n, 3, H, W)")
         dev = x.device
         nhwc = x.to(self.engine.device, torch.float32).permute(0, 2, 3, 1).contiguous()
-        emb = self.engine.facenet_embed(nhwc)
-        return emb if dev.type == "cuda" else emb.to(dev)
+        if self.classify:
+            self._need_logits()
+            out = self.engine.facenet_logits(self.engine.facenet_features(nhwc))
+        else:
+            out = self.engine.facenet_embed(nhwc)
+        return out if dev.type == "cuda" else out.to(dev)

@@ -137,8 +137,12 @@ MTCNN_DENSE = {  # net -> [(name, out, (c,h,w) or in, prelu_name)]
 
 # ---- packing ---------------------------------------------------------------------------------
 
-def canonical_tensors(pnet: Mapping, rnet: Mapping, onet: Mapping, facenet: Mapping) -> Dict[str, np.ndarray]:
-    """state_dicts (facenet-pytorch key layout) -> {canonical name: float32 array}."""
+def canonical_tensors(pnet: Mapping, rnet: Mapping, onet: Mapping, facenet: Mapping, include_logits: bool = True) -> Dict[str, np.ndarray]:
+    """state_dicts (facenet-pytorch key layout) -> {canonical name: float32 array}.
+
+    A FaceNet checkpoint that holds the classifier (``logits.weight`` [C][512] and ``logits.bias`` [C]: vggface2 8631 classes,
+    casia-webface 10575) adds ``facenet.logits.w`` [512][C] and ``facenet.logits.b`` [C] behind every other tensor, unless
+    ``include_logits`` is false; one of the two keys without the other is an error."""
     out: Dict[str, np.ndarray] = {}
     for net, sd in (("pnet", pnet), ("rnet", rnet), ("onet", onet)):
         for name, _co, _ci, _k, prelu in MTCNN_CONVS[net]:
@@ -167,6 +171,16 @@ def canonical_tensors(pnet: Mapping, rnet: Mapping, onet: Mapping, facenet: Mapp
     a, b = _fold_bn(facenet, "last_bn")
     out["facenet.last_bn.scale"] = a
     out["facenet.last_bn.shift"] = b
+    has_w, has_b = "logits.weight" in facenet, "logits.bias" in facenet
+    if has_w != has_b:
+        raise ValueError("the FaceNet state dict holds logits.%s without logits.%s" % (("weight", "bias") if has_w else ("bias", "weight")))
+    if has_w and include_logits:
+        w = _np(facenet["logits.weight"]).astype(np.float32)
+        bias = _np(facenet["logits.bias"]).astype(np.float32)
+        if w.ndim != 2 or w.shape[1] != 512 or bias.shape != (w.shape[0],):
+            raise ValueError(f"logits.weight {w.shape} / logits.bias {bias.shape}: expected [C][512] and [C]")
+        out["facenet.logits.w"] = np.ascontiguousarray(w.T)
+        out["facenet.logits.b"] = bias
     return out
 
 
@@ -205,8 +219,8 @@ def unpack_tensors(blob: bytes) -> Dict[str, np.ndarray]:
     return out
 
 
-def pack_state_dicts(pnet, rnet, onet, facenet) -> bytes:
-    return pack_tensors(canonical_tensors(pnet, rnet, onet, facenet))
+def pack_state_dicts(pnet, rnet, onet, facenet, include_logits: bool = True) -> bytes:
+    return pack_tensors(canonical_tensors(pnet, rnet, onet, facenet, include_logits))
 
 
 # ---- synthetic weights ---------------------------------------------------------------------
@@ -227,8 +241,10 @@ def _load_calibration(seed: int):
     return {"pnet": 0.0, "rnet": 0.0, "onet": 0.0}, None, None
 
 
-def synthetic_state_dicts(seed: int = 0, calibration: Mapping[str, float] | None = None, use_file: bool = True):
-    """Seeded random weights with facenet-pytorch's state_dict key layout and shapes."""
+def synthetic_state_dicts(seed: int = 0, calibration: Mapping[str, float] | None = None, use_file: bool = True,
+                          num_classes: int | None = None):
+    """Seeded random weights with facenet-pytorch's state_dict key layout and shapes.  ``num_classes``: also the classifier,
+    ``logits.weight`` [C][512] and ``logits.bias`` [C], from a generator of its own (every other tensor keeps its values)."""
     rng = np.random.default_rng(seed)
     cal, bn_mean, bn_var = _load_calibration(seed) if use_file else ({"pnet": 0.0, "rnet": 0.0, "onet": 0.0}, None, None)
     if calibration:
@@ -291,7 +307,18 @@ def synthetic_state_dicts(seed: int = 0, calibration: Mapping[str, float] | None
         fn["last_bn.running_var"] = bn_var
         fn["last_bn.weight"] = np.ones(512, np.float32)
         fn["last_bn.bias"] = np.zeros(512, np.float32)
+    if num_classes is not None:
+        fn.update(synthetic_logits(seed, num_classes))
     return nets["pnet"], nets["rnet"], nets["onet"], fn
+
+
+def synthetic_logits(seed: int, num_classes: int) -> Dict[str, np.ndarray]:
+    """The seeded classifier of :func:`synthetic_state_dicts`: ``logits.weight`` [C][512] ~ N(0, 1/512) and ``logits.bias`` [C]
+    ~ 0.1 N(0, 1), from a generator that belongs to them alone."""
+    rng = np.random.default_rng([int(seed), 0x106175])
+    c = int(num_classes)
+    return {"logits.weight": (rng.standard_normal((c, 512)) * np.sqrt(1.0 / 512)).astype(np.float32),
+            "logits.bias": (rng.standard_normal(c) * 0.1).astype(np.float32)}
 
 
 # Face-logit offsets that give the generalised slopes the SAME candidate mix as the seeded ones on the bench clip (R-Net / O-Net

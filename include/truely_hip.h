@@ -361,6 +361,13 @@ int  trl_debug_crop_area(trl_ctx* ctx, const uint8_t* d_frames, int n, int H, in
  * out[1] = whole call, every attempt of a re-run call included (before this library version trl_mtcnn_detect* timed only the
  * last attempt), out[2] = number of PNet launches timed, out[3] = pyramid kernel. */
 int  trl_debug_timings(trl_ctx* ctx, float* out4);
+/* The context's two workspaces.  Every one of them is sized by a dry run of the code that carves it (the same allocation sequence
+ * against an arena that only counts), so "need" below is exactly what the real run takes.  h_out6 = {scratch capacity (bytes),
+ * scratch high-water offset of the last call that used it, cascade-list arena capacity, arena offset, arena need of the last
+ * cascade call or trl_debug_lists, dry-run need of the call `what` describes}: what = 0 none (0 bytes); 1 = trl_facenet_embed /
+ * _masked / trl_facenet_features on n faces of h x w; 24 / 48 = trl_debug_rnet / trl_debug_onet on n crops (h, w ignored).
+ * Nothing runs, nothing is allocated or synchronised.  (ABI v7, additive) */
+int  trl_debug_workspace(trl_ctx* ctx, int what, int n, int h, int w, long long* h_out6);
 /* R-Net / O-Net candidate totals of the last call over the whole batch: h_out2[0] = boxes that entered stage 2, [1] = stage 3 */
 int  trl_debug_stage_totals(trl_ctx* ctx, int32_t* h_out2);
 /* test / tuning hook: consecutive tiles (band order: three tile rows, column by column) a workgroup of the fused PNet launch takes

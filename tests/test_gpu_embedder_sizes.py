@@ -12,8 +12,9 @@ from the code below (_thresholds) for that geometry.
 - the drop-in API: InceptionResnetV1 on a non-square batch, resnet(MTCNN(image_size=S)(img)), the smallest sizes accepted and
   the next smaller refused.
 
-Each call's workspace, faces x (h x w x 110 + 400000) x 4 bytes, stays within that of the largest case of test_gpu_embedder.py
-(2,048 faces of 80 px, 9.0 GB).  That cap puts these thresholds out of reach (faces needed; OUT_OF_REACH, checked against
+Each call's budget, faces x (h x w x 110 + 400000) x 4 bytes (workspace() below: the rule by which cases are chosen, not what a
+call reserves), stays within that of the largest case of test_gpu_embedder.py (2,048 faces of 80 px).  That cap puts these
+thresholds out of reach (faces needed; OUT_OF_REACH, checked against
 _thresholds):
   75 x 75            block8, mixed_7a's stride-2 convs and last_linear (1 x 1 maps): the four-chain tile past M = 4,096 (4,097),
                      leaving the small-map family (16,385)
@@ -41,7 +42,8 @@ pytestmark = pytest.mark.gpu
 
 
 def workspace(h, w, n):
-    """Bytes trl_facenet_embed reserves for n faces of h x w (trl_api.hip, facenet_embed), less its fixed 8 MB."""
+    """The budget rule by which cases are chosen: n faces of h x w count as n x (h x w x 110 + 400000) x 4 bytes.  (What a call
+    reserves is the dry-run count of its walk: Engine.workspace, tests/test_gpu_workspace.py.)"""
     return n * (h * w * 110 + 400000) * 4
 
 

@@ -310,11 +310,13 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
     }
 
     // Every tensor the four nets use is checked here, never at a call: the MTCNN layers resolve into c->mt, what the kernels
-    // choose by (slope classes, the conv3 screen bound) comes from the host image, and the embedder's walk runs once in its
-    // check-only mode over one 160 x 160 face (every geometry names the same tensors).
+    // choose by (slope classes, the conv3 screen bound) comes from the host image, and the embedder's walk runs once over a
+    // counting arena on one 160 x 160 face (every geometry names the same tensors).
     TRL_CHECK(trl_resolve_nets(c, host.data()));
     TRL_CHECK(trl_pnet_prepare(c, host.data()));
-    TRL_CHECK(trl_run_facenet(c, nullptr, 1, 160, 160, nullptr, nullptr, nullptr, true));
+    Arena count = Arena::counter();
+    TRL_CHECK(trl_run_facenet(c, count, nullptr, 1, 160, 160, nullptr, nullptr, nullptr));
+    c->fn_need_key[0] = 0;
     if (idx.count(lw_name)) {                        // (shapes checked above)
         c->logits_w = trl_w(c, lw_name);
         c->logits_b = trl_v(c, lb_name)->p;
@@ -378,6 +380,35 @@ static void collect_timings(trl_ctx* c) {
     }
 }
 
+// The crops of call q (model.py:55-58 per frame, by embed_mode) into the caller's faces_out, or into a block of X in front of the
+// embedder's walk, which then runs over them
+static int crop_embed(trl_ctx* c, Arena& X, const trl_ctx::Pending& q, hipStream_t s) {
+    const int n = q.n, H = q.H, W = q.W, S = c->cfg.embed_mode == 0 ? 80 : 160;
+    float* faces = q.faces_out;
+    if (!faces) {
+        X.reset();                                   // stream order: the cascade's kernels are done with it before these run
+        faces = (float*)X.alloc((size_t)n * S * S * 3 * 4);
+        if (!faces) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
+    }
+    if (!X.counting) {
+        if (c->cfg.embed_mode == 0) TRL_CHECK(trl_launch_crop_resize80(q.frames, n, H, W, q.rect, q.valid, faces, s));
+        else if (c->cfg.embed_mode == 3) TRL_CHECK(trl_launch_crop_aligned(q.frames, n, H, W, c->cb.pts0, q.valid, S, true, faces, s));
+        else TRL_CHECK(trl_launch_crop_area_std(q.frames, n, H, W, q.rect, q.valid, S, c->cfg.embed_mode == 2, faces, s));
+    }
+    return q.faces_out ? TRL_OK : trl_run_facenet(c, X, faces, n, S, S, q.valid, q.emb, s);
+}
+// c->fn_need_bytes = the count of an embedder call on n faces of h x w -- with `crops`, of crop_embed for an EMBED call of n
+// frames.  It stays for the next call with the same key: equal batches pay one comparison, not a second walk
+static int embed_need(trl_ctx* c, bool crops, int n, int h, int w) {
+    const int key[6] = {n, h, w, c->cfg.embed_precision, g_trl_no_fnconv, crops};
+    if (memcmp(key, c->fn_need_key, sizeof key) == 0) return TRL_OK;
+    Arena count = Arena::counter();
+    trl_ctx::Pending q; q.n = n;
+    TRL_CHECK(crops ? crop_embed(c, count, q, nullptr) : trl_run_facenet(c, count, nullptr, n, h, w, nullptr, nullptr, nullptr));
+    memcpy(c->fn_need_key, key, sizeof key);
+    c->fn_need_bytes = count.high;
+    return TRL_OK;
+}
 // Every cascade entry point (trl_mtcnn_detect*, trl_detect_embed*, trl_detect_crop*) is one call in c->pend: call_begin()
 // validates it and queues its first attempt, call_wait() is the call's one host synchronisation, the capacity check and --
 // rarely -- the re-run; the blocking entry points do both.  call_enqueue() queues one attempt on the call's stream: the cascade
@@ -389,34 +420,17 @@ static int call_enqueue(trl_ctx* c) {
     if (!q.attempt) TRL_HIP(hipEventRecord(c->ev_call0, s));   // trl_debug_timings: out[1] covers every attempt of the call
     TRL_CHECK(trl_cascade_detect(c, q.frames, n, H, W, s, q.attempt ? c->resume_stage : 0));
     if (q.kind == trl_ctx::Pending::DETECT) {
-        // model.py's per-frame outputs are not asked for: scratch behind the lists
-        float* box0 = (float*)c->arena.alloc((size_t)n * 16); float* prob0 = (float*)c->arena.alloc((size_t)n * 4);
-        int32_t* rect = (int32_t*)c->arena.alloc((size_t)n * 16); uint8_t* valid = (uint8_t*)c->arena.alloc((size_t)n);
-        if (!valid) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
+        // model.py's per-frame outputs are not asked for: they go to the blocks behind the lists
         TRL_HIP(hipMemsetAsync(q.boxes, 0, (size_t)n * c->cfg.max_faces * 16, s));
         TRL_HIP(hipMemsetAsync(q.probs, 0, (size_t)n * c->cfg.max_faces * 4, s));
         if (q.points) TRL_HIP(hipMemsetAsync(q.points, 0, (size_t)n * c->cfg.max_faces * 40, s));
-        TRL_CHECK(trl_cascade_finish(c, q.frames, n, H, W, q.boxes, q.probs, q.points, q.counts, box0, prob0, rect, valid, nullptr, s, q.order));
+        TRL_CHECK(trl_cascade_finish(c, q.frames, n, H, W, q.boxes, q.probs, q.points, q.counts, c->cb.box0, c->cb.prob0, c->cb.rect, c->cb.valid, nullptr, s, q.order));
     } else {
         // model.py:47-58 (detect, largest box, crop + resize) and, EMBED, :59 (embed).  CROP: the crops go to the caller's faces_out
-        // and the embedder does not run; EMBED: they live in scratch and are embedded.
-        const int S = c->cfg.embed_mode == 0 ? 80 : 160;
-        float* pts0 = nullptr;
-        if (c->cfg.embed_mode == 3) {                // the largest face's landmarks steer the aligned crop
-            pts0 = (float*)c->arena.alloc((size_t)n * 40);
-            if (!pts0) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
-        }
-        TRL_CHECK(trl_cascade_finish(c, q.frames, n, H, W, nullptr, nullptr, nullptr, nullptr, q.box, q.prob, q.rect, q.valid, pts0, s));
-        float* faces = q.faces_out;
-        if (!faces) {
-            c->scratch.reset();                      // stream order: the cascade's kernels are done with it before these run
-            faces = (float*)c->scratch.alloc((size_t)n * S * S * 3 * 4);
-            if (!faces) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
-        }
-        if (c->cfg.embed_mode == 0) TRL_CHECK(trl_launch_crop_resize80(q.frames, n, H, W, q.rect, q.valid, faces, s));
-        else if (c->cfg.embed_mode == 3) TRL_CHECK(trl_launch_crop_aligned(q.frames, n, H, W, pts0, q.valid, S, true, faces, s));
-        else TRL_CHECK(trl_launch_crop_area_std(q.frames, n, H, W, q.rect, q.valid, S, c->cfg.embed_mode == 2, faces, s));
-        if (!q.faces_out) TRL_CHECK(trl_run_facenet(c, faces, n, S, S, q.valid, q.emb, s));
+        // and the embedder does not run; EMBED: they live in scratch and are embedded.  (pts0: the landmarks that steer embed_mode 3's crop)
+        TRL_CHECK(trl_cascade_finish(c, q.frames, n, H, W, nullptr, nullptr, nullptr, nullptr, q.box, q.prob, q.rect, q.valid,
+                                     c->cfg.embed_mode == 3 ? c->cb.pts0 : nullptr, s));
+        TRL_CHECK(crop_embed(c, c->scratch, q, s));
     }
     TRL_HIP(hipEventRecord(c->ev_call1, s));
     TRL_CHECK(trl_gate_record(c, s));
@@ -432,7 +446,8 @@ static int call_begin(trl_ctx* c, const trl_ctx::Pending& q) {
     }
     TRL_HIP(hipSetDevice(c->cfg.device));
     const int S = c->cfg.embed_mode == 0 ? 80 : 160;
-    c->scratch_after_cascade = q.kind == trl_ctx::Pending::EMBED ? trl_facenet_bytes(q.n, S, S) : 0;
+    if (q.kind == trl_ctx::Pending::EMBED) TRL_CHECK(embed_need(c, true, q.n, S, S));
+    c->scratch_after_cascade = q.kind == trl_ctx::Pending::EMBED ? c->fn_need_bytes : 0;
     c->pend = q;
     c->pend.active = true;
     c->pend.attempt = 0;
@@ -544,9 +559,9 @@ static int facenet_embed(trl_ctx* c, const float* d_faces, const uint8_t* d_vali
     TRL_CHECK(trl_check_idle(c));
     if (!d_faces || (masked && !d_valid) || !d_emb || n <= 0 || h < 75 || w < 75) { trl_set_error("bad face batch n=%d %dx%d (min 75x75)", n, h, w); return TRL_ERR_INVALID; }
     TRL_HIP(hipSetDevice(c->cfg.device));
-    c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, trl_facenet_bytes(n, h, w)));
-    TRL_CHECK(trl_run_facenet(c, d_faces, n, h, w, d_valid, d_emb, (hipStream_t)stream, false, features));
+    TRL_CHECK(embed_need(c, false, n, h, w));
+    TRL_CHECK(trl_scratch_begin(c, c->fn_need_bytes));
+    TRL_CHECK(trl_run_facenet(c, c->scratch, d_faces, n, h, w, d_valid, d_emb, (hipStream_t)stream, features));
     return trl_gate_record(c, (hipStream_t)stream);
 }
 
@@ -701,8 +716,7 @@ int trl_debug_level_keep(trl_ctx* c, int frame, int level, int32_t* h_idx, int m
 int trl_debug_pyramid_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, int level, float* d_out, int* h, int* w, void* stream) {
     TRL_CHECK(check_call(c, d_frame, 1, H, W));
     hipStream_t s = (hipStream_t)stream;
-    c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, trl_pnet_fused_bytes(c, 1, H, W) + (1u << 20)));
+    TRL_CHECK(trl_scratch_begin(c, trl_pnet_fused_bytes(c, 1, H, W) + (1u << 20)));
     TRL_CHECK(trl_pyramid_export(c, d_frame, H, W, level, d_out, h, w, s));
     TRL_HIP(hipStreamSynchronize(s));
     return TRL_OK;
@@ -713,10 +727,7 @@ int trl_debug_pyramid_batch(trl_ctx* c, const uint8_t* d_frames, int n, int H, i
     TRL_CHECK(check_call(c, d_frames, n, H, W));
     if (!pyr_stride || !n_levels || (max_levels > 0 && !h_levels)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
     hipStream_t s = (hipStream_t)stream;
-    if (d_out) {
-        c->scratch.reset();
-        TRL_CHECK(trl_ensure(c, c->scratch, trl_pnet_fused_bytes(c, n, H, W) + (1u << 20)));
-    }
+    if (d_out) TRL_CHECK(trl_scratch_begin(c, trl_pnet_fused_bytes(c, n, H, W) + (1u << 20)));
     TRL_CHECK(trl_pyramid_export_batch(c, d_frames, n, H, W, d_out, pyr_stride, h_levels, max_levels, n_levels, s));
     TRL_HIP(hipStreamSynchronize(s));
     return TRL_OK;
@@ -766,10 +777,8 @@ int trl_debug_pnet_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, int l
     const int L = trl_compute_levels(c, H, W);
     if (level < 0 || level >= L) { trl_set_error("level %d out of range (%d levels)", level, L); return TRL_ERR_INVALID; }
     const LevelGeom& g = c->lv[level];
-    c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, trl_pnet_generic_level_bytes(g) + (4u << 20)));
     float* heads;
-    TRL_CHECK(trl_pnet_generic_level(c, d_frame, 1, H, W, g, &heads, s));
+    TRL_CHECK(trl_carve_scratch(c, [&](Arena& X) { return trl_pnet_generic_level(c, X, d_frame, 1, H, W, g, &heads, s); }));
     TRL_CHECK(trl_launch_heads_to_maps(heads, g.oh * g.ow, d_prob, d_reg, s));
     *oh = g.oh; *ow = g.ow;
     TRL_HIP(hipStreamSynchronize(s));
@@ -780,9 +789,7 @@ int trl_debug_pnet_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, int l
 static int debug_net(trl_ctx* c, const NetDesc& d, const float* d_crops, int n, float* d_out, void* stream) {
     if (!c || !c->have_weights || !d_crops || !d_out || n <= 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
     TRL_CHECK(trl_check_idle(c));
-    c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, trl_net_bytes(d, n)));
-    return trl_run_net(c, d, 0, Act::dense(d_crops, n, d.side, d.side, 3), d_out, (hipStream_t)stream);
+    return trl_carve_scratch(c, [&](Arena& X) { return trl_run_net(c, X, d, 0, Act::dense(d_crops, n, d.side, d.side, 3), d_out, (hipStream_t)stream); });
 }
 int trl_debug_rnet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) { return debug_net(c, trl_nets[TRL_RNET], d_crops, n, d_out, stream); }
 int trl_debug_onet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) { return debug_net(c, trl_nets[TRL_ONET], d_crops, n, d_out, stream); }
@@ -828,13 +835,9 @@ static int stage_net_on_rows(trl_ctx* c, const uint8_t* d_frames, int nf, int H,
     }
     int32_t* total = nullptr;
     TRL_CHECK(upload_records(c, nf, H, W, hb, slots, nb, &total, s));
-    // workspace as the cascade sizes it (trl_cascade_detect)
-    const NetDesc& d = trl_net_of(net);
-    c->scratch.reset();
-    TRL_CHECK(trl_ensure(c, c->scratch, trl_stage_bytes(d, capacity < c->*d.chunk ? capacity : c->*d.chunk)));
     c->mt_plan.clear();
     c->mt_plan_arm = true;
-    const int st = trl_stage_net(c, net, d_frames, H, W, total, capacity, d_out, s);
+    const int st = trl_carve_scratch(c, [&](Arena& X) { return trl_stage_net(c, X, net, d_frames, H, W, total, capacity, d_out, s); });
     c->mt_plan_arm = false;
     TRL_CHECK(st);
     TRL_HIP(hipStreamSynchronize(s));
@@ -926,6 +929,20 @@ int trl_debug_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* h_
     TRL_HIP(hipSetDevice(c->cfg.device));
     return trl_cascade_lists(c, kind, n, H, W, h_caps, n_levels, h_counts, h_rows, h_logits, h_pts, d_boxes, d_probs, d_points, d_counts,
                              d_box0, d_prob0, d_rect, d_valid, (hipStream_t)stream);
+}
+
+// the context's two arenas and, for `what` = 1 (embedder call on n faces of h x w) / 24 / 48 (trl_debug_rnet / _onet on n crops),
+// the count of that call, with the call's own argument checks: host bookkeeping only
+int trl_debug_workspace(trl_ctx* c, int what, int n, int h, int w, long long* h_out6) {
+    TRL_CHECK(trl_check_idle(c));
+    if (!h_out6 || (what != 0 && what != 1 && what != 24 && what != 48) || (what && n <= 0) || (what == 1 && (h < 75 || w < 75))) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
+    if (what && !c->have_weights) { trl_set_error("context without weights"); return TRL_ERR_STATE; }
+    Arena X = Arena::counter();
+    if (what == 1) TRL_CHECK(embed_need(c, false, n, h, w));
+    else if (what) { const NetDesc& d = trl_net_of(what); TRL_CHECK(trl_run_net(c, X, d, 0, Act::dense(nullptr, n, d.side, d.side, 3), nullptr, nullptr)); }
+    const size_t v[6] = {c->scratch.cap, c->scratch.high, c->arena.cap, c->arena.off, c->arena_need, what == 1 ? c->fn_need_bytes : X.high};
+    for (int k = 0; k < 6; k++) h_out6[k] = (long long)v[k];
+    return TRL_OK;
 }
 
 int trl_debug_mtcnn_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, int* n_rows) {

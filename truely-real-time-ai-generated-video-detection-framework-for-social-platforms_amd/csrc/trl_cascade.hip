@@ -14,6 +14,7 @@
 // All float expressions follow the reference's operation order (one rounding per op,
 // -ffp-contract=off), so boxes / keep masks are bit-identical to the oracle.
 #include "trl_ctx.h"
+#include <algorithm>
 #include <stdlib.h>
 #include <string.h>
 
@@ -925,17 +926,11 @@ static int launch_stage3_post(trl_ctx* c, const ListLaunch& ll, int n, int cap3,
     return TRL_OK;
 }
 
-// The cascade's lists in c->arena for the layout in c->cb (n, L, lay, capF) and a spill pool of `spill` bytes, flags zeroed.  One
-// layout for the cascade and the list hook (trl_cascade_lists).  Behind them (B.arena_mark) the API layer allocates its per-frame
-// outputs, again on every attempt of a call.
-static int carve_lists(trl_ctx* c, size_t spill, hipStream_t s) {
-    CascadeBufs& B = c->cb;
+// The cascade's blocks for B's geometry (n, L, lay, capF) and a spill pool of `spill` bytes: the lists, then k_select's per-frame
+// outputs.  One layout for the cascade and the list hook (trl_cascade_lists)
+static void layout_lists(CascadeBufs& B, Arena& A, size_t spill) {
     const LvLayout& G = B.lay;
     const int n = B.n, L = B.L, capF = B.capF;
-    Arena& A = c->arena;      // cascade lists: live for the whole call (and for the debug hooks after it)
-    const size_t need = (size_t)n * ((size_t)G.S * (sizeof(Cand) + 4) + (size_t)L * 8) + (size_t)n * capF * (5 * 3 + 10 + 8) * 4 +
-                        (size_t)n * 1024 + spill + (1u << 20);   // + the API layer's per-frame outputs (box0, prob0, rect, valid, pts0)
-    TRL_CHECK(trl_ensure(c, A, need));
     A.reset();
     B.lvl_cnt = (int32_t*)A.alloc((size_t)n * L * 4);
     B.lvl_keep_cnt = (int32_t*)A.alloc((size_t)n * L * 4);
@@ -949,28 +944,29 @@ static int carve_lists(trl_ctx* c, size_t spill, hipStream_t s) {
     B.flags = (int32_t*)A.alloc(TRL_NFLAGS * 4);
     B.spill = spill ? (char*)A.alloc(spill) : nullptr;
     B.spill_cap = B.spill ? spill : 0;
-    if (!B.flags || (spill && !B.spill)) { trl_set_error("cascade workspace allocation failed"); return TRL_ERR_STATE; }
-    B.arena_mark = A.off;
+    B.box0 = (float*)A.alloc((size_t)n * 16); B.prob0 = (float*)A.alloc((size_t)n * 4);
+    B.rect = (int32_t*)A.alloc((size_t)n * 16); B.valid = (uint8_t*)A.alloc((size_t)n);
+    B.pts0 = (float*)A.alloc((size_t)n * 40);
+}
+// ... carved from c->arena (live for the whole call, and for the debug hooks after it) for the layout in c->cb, flags zeroed
+static int carve_lists(trl_ctx* c, size_t spill, hipStream_t s) {
+    CascadeBufs& B = c->cb;
+    Arena count = Arena::counter();
+    layout_lists(B, count, spill);
+    TRL_CHECK(trl_ensure(c, c->arena, c->arena_need = count.off));
+    layout_lists(B, c->arena, spill);
+    if (c->arena.off != c->arena_need) { trl_set_error("cascade workspace allocation failed"); return TRL_ERR_STATE; }
     TRL_HIP(hipMemsetAsync(B.flags, 0, TRL_NFLAGS * 4, s));
     return TRL_OK;
 }
 
-size_t trl_pnet_generic_level_bytes(const LevelGeom& g) {
-    return trl_pnet_generic_bytes(1, g.h, g.w) + (size_t)g.h * g.w * 12 + (size_t)g.oh * g.ow * 24 + 4096;
-}
-// frames per step of the generic path on level g: one step's workspace stays under 2 GB
-static int generic_chunk(const LevelGeom& g, int n) {
-    const int ch = (int)((size_t)(2048ull << 20) / trl_pnet_generic_level_bytes(g));
-    return ch < 1 ? 1 : (ch > n ? n : ch);
-}
-int trl_pnet_generic_level(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const LevelGeom& g, float** d_heads, hipStream_t s) {
-    Arena& X = c->scratch;
+int trl_pnet_generic_level(trl_ctx* c, Arena& X, const uint8_t* d_frames, int nf, int H, int W, const LevelGeom& g, float** d_heads, hipStream_t s) {
     X.reset();
     float* lvl = (float*)X.alloc((size_t)nf * g.h * g.w * 12);
     float* heads = (float*)X.alloc((size_t)nf * g.oh * g.ow * 24);
     if (!lvl || !heads) { trl_set_error("pnet generic workspace"); return TRL_ERR_STATE; }
-    TRL_CHECK(trl_launch_area_level(d_frames, nf, H, W, g.h, g.w, lvl, s));
-    TRL_CHECK(trl_run_net(c, trl_nets[TRL_PNET], 0, Act::dense(lvl, nf, g.h, g.w, 3), heads, s));   // heads [nf][oh][ow][6]
+    if (!X.counting) TRL_CHECK(trl_launch_area_level(d_frames, nf, H, W, g.h, g.w, lvl, s));
+    TRL_CHECK(trl_run_net(c, X, trl_nets[TRL_PNET], 0, Act::dense(lvl, nf, g.h, g.w, 3), heads, s));   // heads [nf][oh][ow][6]
     *d_heads = heads;
     return TRL_OK;
 }
@@ -986,32 +982,36 @@ static int next_pnet_events(trl_ctx* c, std::pair<hipEvent_t, hipEvent_t>*& out)
     return TRL_OK;
 }
 
+// stage 2 / 3 carves X from its start (stream order: the stage in front is done with it): *d_out = [cap][nout], then trl_stage_net's
+static int stage_carve(trl_ctx* c, Arena& X, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float** d_out, hipStream_t s) {
+    const NetDesc& d = trl_net_of(net);
+    X.reset();
+    *d_out = (float*)X.alloc((size_t)cap * d.nout * 4);
+    if (!*d_out) { trl_set_error("%s workspace", d.name); return TRL_ERR_STATE; }
+    return trl_stage_net(c, X, net, d_frames, H, W, d_total, cap, *d_out, s);
+}
+
 // Capacities of the R-/O-Net candidate batches of this call, and ONE scratch workspace big enough for every stage: it is only
 // ever grown here, before anything of the call is queued (growing frees the old block)
 static int size_scratch(trl_ctx* c, int n, int H, int W, bool fused) {
-    Arena& X = c->scratch;
-    const int L = c->cb.L;
-    X.reset();
-    if (!fused) {
-        size_t mx = 0;
-        for (int l = 0; l < L; l++) {
-            const size_t p = trl_pnet_generic_level_bytes(c->lv[l]) * generic_chunk(c->lv[l], n);
-            if (p > mx) mx = p;
-        }
-        TRL_CHECK(trl_ensure(c, X, mx + (4u << 20)));
-    }
     long long c2 = (long long)(c->t2_per_frame * n) + 64, c3 = (long long)(c->t3_per_frame * n) + 64;
     const long long lim = (long long)n * c->cb.capF;
     c->cap_t2 = (int)(c2 < lim ? c2 : lim);
     c->cap_t3 = (int)(c3 < lim ? c3 : lim);
-    const int ch2 = c->cap_t2 < c->rnet_chunk ? c->cap_t2 : c->rnet_chunk, ch3 = c->cap_t3 < c->onet_chunk ? c->cap_t3 : c->onet_chunk;
-    // the stage's output rows + per candidate of a chunk the front kernel's pooled map and every activation of the tail
-    size_t need_x = (size_t)c->cap_t2 * 24 + trl_stage_bytes(trl_nets[TRL_RNET], ch2);
-    const size_t need3 = (size_t)c->cap_t3 * 64 + trl_stage_bytes(trl_nets[TRL_ONET], ch3);
-    if (need3 > need_x) need_x = need3;
-    if (fused) { const size_t p = trl_pnet_fused_bytes(c, n, H, W) + (1u << 20); if (p > need_x) need_x = p; }
-    if (c->scratch_after_cascade > need_x) need_x = c->scratch_after_cascade;   // the embedder that follows in the same call
-    return trl_ensure(c, X, need_x);
+    // one counting arena under all that carves the scratch in turn (each from a reset): its high-water mark is the call's need
+    Arena X = Arena::counter();
+    X.high = std::max(c->scratch_after_cascade, fused ? trl_pnet_fused_bytes(c, n, H, W) + (1u << 20) : 0);
+    float* o;
+    for (int l = 0; l < c->cb.L && !fused; l++) {
+        LevelGeom& g = c->lv[l];
+        if (g.oh < 1 || g.ow < 1) continue;
+        TRL_CHECK(trl_pnet_generic_level(c, X, nullptr, 1, 0, 0, g, &o, nullptr));
+        g.chunk = (int)std::min<size_t>(n, std::max<size_t>(1, (size_t)(2048ull << 20) / X.off));
+        TRL_CHECK(trl_pnet_generic_level(c, X, nullptr, g.chunk, 0, 0, g, &o, nullptr));
+    }
+    TRL_CHECK(stage_carve(c, X, 24, nullptr, 0, 0, nullptr, c->cap_t2, &o, nullptr));
+    TRL_CHECK(stage_carve(c, X, 48, nullptr, 0, 0, nullptr, c->cap_t3, &o, nullptr));
+    return trl_scratch_begin(c, X.high);
 }
 
 // stage 1, fused path: pyramid kernel + ONE persistent PNet launch over every (frame, level, tile)
@@ -1035,11 +1035,11 @@ static int stage1_generic(trl_ctx* c, const uint8_t* d_frames, hipStream_t s) {
         std::pair<hipEvent_t, hipEvent_t>* pe;
         TRL_CHECK(next_pnet_events(c, pe));
         TRL_HIP(hipEventRecord(pe->first, s));
-        const int chunk = generic_chunk(g, n);
+        const int chunk = g.chunk;
         for (int f0 = 0; f0 < n; f0 += chunk) {
             const int nf = (n - f0 < chunk) ? n - f0 : chunk;
             float* heads;
-            TRL_CHECK(trl_pnet_generic_level(c, d_frames + (size_t)f0 * H * W * 3, nf, H, W, g, &heads, s));
+            TRL_CHECK(trl_pnet_generic_level(c, c->scratch, d_frames + (size_t)f0 * H * W * 3, nf, H, W, g, &heads, s));
             const size_t total = (size_t)nf * g.oh * g.ow;
             size_t blocks = (total + 255) / 256;
             if (blocks > 16384) blocks = 16384;
@@ -1062,10 +1062,8 @@ static int stage2(trl_ctx* c, const ListLaunch& ll, const uint8_t* d_frames, con
     TRL_LAUNCH_CHECK();
     k_build_map<<<n, 64, 0, s>>>(B.n1, B.off2, B.s1_box, B.capF, W, H, B.cbox);
     TRL_LAUNCH_CHECK();
-    c->scratch.reset();   // stream order keeps the PNet workspace alive until its kernels are done: reuse needs no host sync
-    float* out6 = (float*)c->scratch.alloc((size_t)cap2 * 24);
-    if (!out6) { trl_set_error("rnet workspace"); return TRL_ERR_STATE; }
-    TRL_CHECK(trl_stage_net(c, 24, d_frames, H, W, B.off2 + n, cap2, out6, s));
+    float* out6;
+    TRL_CHECK(stage_carve(c, c->scratch, 24, d_frames, H, W, B.off2 + n, cap2, &out6, s));
     return launch_stage2_post(c, ll, n, H, W, cap2, out6, sp, s);
 }
 
@@ -1077,10 +1075,8 @@ static int stage3(trl_ctx* c, const ListLaunch& ll, const uint8_t* d_frames, con
     TRL_LAUNCH_CHECK();
     k_build_map<<<n, 64, 0, s>>>(B.n2, B.off3, B.s2_box, B.capF, W, H, B.cbox);
     TRL_LAUNCH_CHECK();
-    c->scratch.reset();
-    float* out16 = (float*)c->scratch.alloc((size_t)cap3 * 64);
-    if (!out16) { trl_set_error("onet workspace"); return TRL_ERR_STATE; }
-    TRL_CHECK(trl_stage_net(c, 48, d_frames, H, W, B.off3 + n, cap3, out16, s));
+    float* out16;
+    TRL_CHECK(stage_carve(c, c->scratch, 48, d_frames, H, W, B.off3 + n, cap3, &out16, s));
     return launch_stage3_post(c, ll, n, cap3, out16, sp, s);
 }
 
@@ -1095,7 +1091,6 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     if (!resume) plan_lists(c, L);
     const size_t spill = spill_pool(c, n, H, W);
     if (resume) {
-        c->arena.off = B.arena_mark;                         // the API layer's per-frame outputs are allocated again behind the lists
         // the stages that run again report afresh (the stage-2 total of a resume at stage 3 stays: it is complete)
         TRL_HIP(hipMemsetAsync(B.flags + FLG_T3, 0, 4, s));
         TRL_HIP(hipMemsetAsync(B.flags + FLG_T3N, 0, 4, s));
@@ -1112,7 +1107,7 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
         TRL_HIP(hipMemsetAsync(B.n3, 0, (size_t)n * 4, s));
         TRL_HIP(hipMemsetAsync(B.off2, 0, (size_t)(n + 1) * 4, s));
         TRL_HIP(hipMemsetAsync(B.off3, 0, (size_t)(n + 1) * 4, s));
-        if (c->scratch_after_cascade) TRL_CHECK(trl_ensure(c, c->scratch, c->scratch_after_cascade));   // the crops + embedder of the same call
+        TRL_CHECK(trl_scratch_begin(c, c->scratch_after_cascade));   // the crops + embedder of the same call
         return TRL_OK;
     }
     if (!resume) {
@@ -1133,9 +1128,9 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
 // One R-Net (net = 24) or O-Net (net = 48) stage over `cap` candidate slots: chunks of c->rnet_chunk / c->onet_chunk candidates,
 // each the fused front kernel (crop of record t0 + i of c->cb.cbox, conv1, pool1 in LDS) then the layer tail.  Launches are sized
 // by the capacity; the candidates that exist are the first *d_total, and every kernel skips the rest on the device.  The pooled
-// maps come from c->scratch behind its current offset (the caller's blocks below it stay intact).  d_out: [cap][6] / [cap][16].
-int trl_stage_net(trl_ctx* c, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float* d_out, hipStream_t s) {
-    Arena& X = c->scratch;
+// maps come from X behind its current offset (the caller's blocks below it stay intact).  d_out: [cap][6] / [cap][16].  Over a
+// counting X one chunk is walked: the first is the largest.
+int trl_stage_net(trl_ctx* c, Arena& X, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float* d_out, hipStream_t s) {
     const NetDesc& d = trl_net_of(net);
     const int CH = c->*d.chunk;
     const size_t mk = X.off;
@@ -1144,8 +1139,9 @@ int trl_stage_net(trl_ctx* c, int net, const uint8_t* d_frames, int H, int W, co
         X.off = mk;
         float* pool1 = (float*)X.alloc((size_t)nc * d.P * d.P * d.C1 * 4);
         if (!pool1) { trl_set_error("%s workspace", d.name); return TRL_ERR_STATE; }
-        TRL_CHECK(trl_launch_front(c, d, d_frames, H, W, d_total, t0, nc, pool1, s));   // crop + conv1 + pool1 in LDS
-        TRL_CHECK(trl_run_net(c, d, d.tail, Act::dense(pool1, nc, d.P, d.P, d.C1), d_out + (size_t)t0 * d.nout, s, d_total, t0));
+        if (!X.counting) TRL_CHECK(trl_launch_front(c, d, d_frames, H, W, d_total, t0, nc, pool1, s));   // crop + conv1 + pool1 in LDS
+        TRL_CHECK(trl_run_net(c, X, d, d.tail, Act::dense(pool1, nc, d.P, d.P, d.C1), d_out + (size_t)t0 * d.nout, s, d_total, t0));
+        if (X.counting) break;
     }
     return TRL_OK;
 }
@@ -1278,9 +1274,7 @@ int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* 
         // the net outputs: [cap][NO] in the scratch arena, cap = the candidate total (+ 64 poisoned rows behind it)
         const int cap = (int)total + 64;
         Arena& X = c->scratch;
-        X.reset();
-        TRL_CHECK(trl_ensure(c, X, (size_t)cap * NO * 4 + (1u << 20)));
-        X.reset();
+        TRL_CHECK(trl_scratch_begin(c, (size_t)cap * NO * 4 + (1u << 20)));
         float* out = (float*)X.alloc((size_t)cap * NO * 4);
         if (!out) { trl_set_error("list hook net outputs"); return TRL_ERR_STATE; }
         TRL_HIP(hipMemsetAsync(out, poison, (size_t)cap * NO * 4, s));

@@ -90,16 +90,21 @@ struct ConvArgs {
     const uint16_t* wt = nullptr; int ldwt = 0;
 };
 
-// bump allocator over one device allocation
+// bump allocator over one device allocation.  Every workspace is sized by a dry run of the code that carves it over a COUNTING arena
+// (no base, never full, the same alignment): code handed one launches nothing and does not dereference what alloc returns (a token).
 struct Arena {
     char* base = nullptr;
     size_t cap = 0, off = 0;
+    size_t high = 0;          // largest off since it was last zeroed (a reset() keeps it)
+    bool counting = false;
+    static Arena counter() { Arena a; a.counting = true; return a; }
     void reset() { off = 0; }
     void* alloc(size_t bytes) {
         size_t a = (off + 255) & ~(size_t)255;
-        if (a + bytes > cap) return nullptr;
+        if (!counting && a + bytes > cap) return nullptr;
         off = a + bytes;
-        return base + a;
+        if (off > high) high = off;
+        return counting ? (void*)this : base + a;
     }
 };
 

@@ -13,6 +13,7 @@ struct LevelGeom {
     double scale;
     int h, w;        // pyramid level size
     int oh, ow;      // PNet output map size
+    int chunk;       // generic path: frames per step, so that one step's workspace stays under 2 GB (size_scratch)
 };
 
 // Candidate lists of one call.  Level l of every frame owns capl[l] record slots (never more than the level has cells); a frame's
@@ -38,9 +39,9 @@ struct CascadeBufs {   // device pointers into the arena, valid until the next c
     int32_t* off2 = nullptr; int32_t* off3 = nullptr; // [n+1] exclusive scans of n1 / n2
     int32_t* cbox = nullptr;     // [n*capF][8]: candidate t of the current stage = {frame, y0, x0, ih, iw, 0, 0, 0} (pad()'s crop window)
     int32_t* flags = nullptr;        // [TRL_NFLAGS]: the FLG_* words below
-    size_t arena_mark = 0;           // arena offset behind the cascade's own blocks (where a resumed attempt re-allocates the API outputs)
     char* spill = nullptr;           // global-memory workspace of the NMS spill tier (lists longer than the LDS tier)
     size_t spill_cap = 0;
+    float* box0 = nullptr; float* prob0 = nullptr; int32_t* rect = nullptr; uint8_t* valid = nullptr; float* pts0 = nullptr;   // k_select's per-frame outputs where the call asks for none
 };
 enum { TRL_NFLAGS = 64 };            // int32 words of CascadeBufs::flags (copied to pinned host memory behind every call)
 // The words: a capacity of the attempt was too small (level record list, per-frame list, R-/O-Net batch, spill pool) and what the
@@ -49,7 +50,7 @@ enum { FLG_LEVEL = 0, FLG_FRAME = 1, FLG_T2 = 2, FLG_T3 = 3, FLG_T2N = 4, FLG_T3
        FLG_SPILL_CUR = 8 /* u64 */, FLG_SPILL_LISTS = 10, FLG_LEVEL_MAX = 16 /* [32] */ };
 
 // One MTCNN network, described once (the table trl_nets[] in trl_nets.hip): the layer walker, the front launcher, the cascade's
-// stage loop, the workspace sizes and the loader's tensor check all read it.
+// stage loop and the loader's tensor check all read it.
 struct NetLayer { const char* name; const char* prelu; int k, st, cout; };   // a valid k x k conv `name` (+ bias, + PReLU `prelu` or none) of
                                                                              // cout channels; name == null: a ceil-mode max pool k / st
 struct trl_ctx;
@@ -61,8 +62,6 @@ struct NetDesc {
     int P, C1;
     int nout;                        // output floats per item
     int trl_ctx::*chunk;             // the context's candidates-per-launch-set option of this net
-    size_t full_bytes, tail_bytes;   // activation workspace per item of the whole net / of the tail with its pooled map (R-Net tail:
-                                     // 3388 + 3888 + 768 + 576 + 128 floats = 35 KB; O-Net: 16928 + 28224 + 6400 + 4096 + 1024 + 1152 + 256 = 227 KB)
 };
 enum { TRL_PNET = 0, TRL_RNET = 1, TRL_ONET = 2 };
 extern const NetDesc trl_nets[3];
@@ -85,7 +84,9 @@ struct trl_ctx {
     const float* logits_b = nullptr;
     int num_classes = 0;
     Arena arena;                     // per-call persistent blocks (cascade lists)
-    Arena scratch;                   // transient activations; only ever grown while empty
+    Arena scratch;                   // transient activations; only ever grown while empty (trl_scratch_begin)
+    size_t arena_need = 0;           // the count of the last list layout (trl_debug_workspace)
+    int fn_need_key[6] = {0}; size_t fn_need_bytes = 0;   // the last embedder dry run (embed_need): what its walk branches on, its count
     Arena sims_tmp;                  // similarities when trl_drift_score is called with d_sims == NULL
     int32_t* h_pinned = nullptr;     // small pinned host scratch
     CascadeBufs cb;
@@ -163,24 +164,30 @@ int trl_gate_wait(trl_ctx* c, hipStream_t s);      // before the fused PNet laun
 int trl_gate_record(trl_ctx* c, hipStream_t s);    // behind the last kernel of a call
 extern int g_trl_pnet_gate;                        // trl_debug_option("pnet_gate"): 0 (default) / 1
 int trl_ensure(trl_ctx* c, Arena& a, size_t bytes);   // grow (never while blocks of `a` are live)
+// a call's first use of the scratch: empty, a new high-water mark, at least `bytes` (the count of the carve that follows); where one
+// carve is the whole call (trl_carve_scratch), carve(X) over a counting arena, then over the scratch grown to that count
+inline int trl_scratch_begin(trl_ctx* c, size_t bytes) { c->scratch.off = c->scratch.high = 0; return trl_ensure(c, c->scratch, bytes); }
+template <class F> int trl_carve_scratch(trl_ctx* c, F&& carve) {
+    Arena X = Arena::counter();
+    TRL_CHECK(carve(X)); TRL_CHECK(trl_scratch_begin(c, X.high));
+    return carve(c->scratch);
+}
 // A context holds at most one call in flight (trl_detect_embed_begin .. _end); anything else that touches its workspaces meanwhile
 // would corrupt that call silently: TRL_ERR_STATE (and TRL_ERR_INVALID for a null context)
 int trl_check_idle(trl_ctx* c);
 const DevW* trl_w(trl_ctx* c, const std::string& name);
 const DevV* trl_v(trl_ctx* c, const std::string& name);
 
-// networks (trl_nets.hip)
-// check_only: the walk of trl_load_weights -- shapes and tensors are checked, nothing is allocated, launched or copied
+// networks (trl_nets.hip).  Every walk takes its activations from X; over a counting X it still checks every shape and tensor
+// (the walk of trl_load_weights).
 // features: d_emb receives the 512 values in front of F.normalize (last_bn's output) instead of the embedding
-int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s, bool check_only = false,
+int trl_run_facenet(trl_ctx* c, Arena& X, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s,
                     bool features = false);
-inline size_t trl_facenet_bytes(int n, int h, int w) { return (size_t)n * ((size_t)h * w * 110 + 400000) * 4 + (8u << 20); }   // its scratch
 // Layers first .. last of net d over x (x.n items; the maps of layer `first`): d_out [x.n][oh][ow][d.nout].  With m_dev, x.n is the
 // CAPACITY of the launch and the items that exist are clamp(*m_dev - m_base, 0, x.n) (device-sized, no host sync).  While
 // c->mt_plan_arm its conv launches are appended to c->mt_plan ("rnet.conv2" .. "onet.heads").
-int trl_run_net(trl_ctx* c, const NetDesc& d, int first, const Act& x, float* d_out, hipStream_t s, const int32_t* m_dev = nullptr, int m_base = 0);
-inline size_t trl_net_bytes(const NetDesc& d, int n) { return (size_t)n * d.full_bytes + (4u << 20); }        // scratch of the whole net over n crops
-inline size_t trl_stage_bytes(const NetDesc& d, int chunk) { return (size_t)chunk * d.tail_bytes + (1u << 20); }   // ... of one chunk of trl_stage_net
+int trl_run_net(trl_ctx* c, Arena& X, const NetDesc& d, int first, const Act& x, float* d_out, hipStream_t s, const int32_t* m_dev = nullptr,
+                int m_base = 0);
 // trl_load_weights, after the upload: himg is the staged host image, laid out like c->wdev (trl_host_of reads a device tensor's copy)
 int trl_resolve_nets(trl_ctx* c, const char* himg);
 inline const float* trl_host_of(const trl_ctx* c, const char* himg, const float* dev) { return (const float*)(himg + ((const char*)dev - c->wdev)); }
@@ -188,8 +195,7 @@ int trl_front_slope_class(const float* h_slope, int n);
 // the fused front kernel of R-Net / O-Net over records t0 .. t0 + nc - 1 of c->cb.cbox: pooled maps [nc][P][P][C1]
 int trl_launch_front(trl_ctx* c, const NetDesc& d, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int t0, int nc, float* d_pool, hipStream_t s);
 // stage 2 / 3 network over `cap` candidate slots of c->cb.cbox, *d_total of them live (trl_cascade.hip): chunked front + tail
-int trl_stage_net(trl_ctx* c, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float* d_out, hipStream_t s);
-size_t trl_pnet_generic_bytes(int nf, int h, int w);
+int trl_stage_net(trl_ctx* c, Arena& X, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float* d_out, hipStream_t s);
 
 // cascade (trl_cascade.hip)
 int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, hipStream_t s, int resume = 0);
@@ -210,10 +216,9 @@ int trl_launch_crop_aligned(const uint8_t* d_frames, int n, int H, int W, const 
                             float* d_faces, hipStream_t s);
 int trl_launch_crop_area_std(const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid, int S,
                              bool rgb, float* d_faces, hipStream_t s);
-// stage 1 on the generic layer path, one level g of nf frames: scratch bytes per frame, and the step itself -- the level
-// materialised in c->scratch (reset first), PNet's layers over it; *d_heads = [nf][oh][ow][6] behind it in c->scratch
-size_t trl_pnet_generic_level_bytes(const LevelGeom& g);
-int trl_pnet_generic_level(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, const LevelGeom& g, float** d_heads, hipStream_t s);
+// stage 1 on the generic layer path, one level g of nf frames: the level materialised in X (reset first), *d_heads =
+// [nf][oh][ow][6] behind it, PNet's layers over it
+int trl_pnet_generic_level(trl_ctx* c, Arena& X, const uint8_t* d_frames, int nf, int H, int W, const LevelGeom& g, float** d_heads, hipStream_t s);
 // fused PNet (trl_pnet.hip)
 int trl_pnet_prepare(trl_ctx* c, const char* himg);   // slope classes and the screen bound, from the host image
 size_t trl_pnet_fused_bytes(trl_ctx* c, int n, int H, int W);

@@ -352,8 +352,7 @@ int trl_extract_faces(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, 
     const int fx = (W + S - 1) / S, fy = (H + S - 1) / S;
     const int Kx = 2 * (fx > 1 ? fx : 1) + 3, Ky = 2 * (fy > 1 ? fy : 1) + 3;
     const size_t words = HDR + (size_t)S * (4 + Kx + Ky);
-    c->scratch.reset();                      // stream order: earlier users of the scratch arena are done before these kernels run
-    TRL_CHECK(trl_ensure(c, c->scratch, (size_t)m * words * 4 + 4096));
+    TRL_CHECK(trl_scratch_begin(c, (size_t)m * words * 4 + 4096));   // stream order: earlier users of the scratch arena are done before these kernels run
     int32_t* plan = (int32_t*)c->scratch.alloc((size_t)m * words * 4);
     if (!plan) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
     k_extract_plan<<<m, 256, 0, s>>>(n, H, W, d_frame_of, d_boxes, S, margin, resample, Kx, Ky, plan, d_status);

@@ -13,14 +13,14 @@ thread_local TrlConvChoice g_trl_conv_choice;
 const NetDesc trl_nets[3] = {
     {"pnet", 0, 5, {{"conv1", "prelu1", 3, 1, 10}, {nullptr, nullptr, 2, 2, 0}, {"conv2", "prelu2", 3, 1, 16}, {"conv3", "prelu3", 3, 1, 32},
                     {"heads", nullptr, 1, 1, 6}},
-     0, 0, 0, 6, nullptr, 0, 0},   // (its workspace follows the level: trl_pnet_generic_bytes)
+     0, 0, 0, 6, nullptr},
     {"rnet", 24, 7, {{"conv1", "prelu1", 3, 1, 28}, {nullptr, nullptr, 3, 2, 0}, {"conv2", "prelu2", 3, 1, 48}, {nullptr, nullptr, 3, 2, 0},
                      {"conv3", "prelu3", 2, 1, 64}, {"dense4", "prelu4", 3, 1, 128}, {"heads", nullptr, 1, 1, 6}},
-     2, 11, 28, 6, &trl_ctx::rnet_chunk, 100 * 1024, 40 * 1024},
+     2, 11, 28, 6, &trl_ctx::rnet_chunk},
     {"onet", 48, 9, {{"conv1", "prelu1", 3, 1, 32}, {nullptr, nullptr, 3, 2, 0}, {"conv2", "prelu2", 3, 1, 64}, {nullptr, nullptr, 3, 2, 0},
                      {"conv3", "prelu3", 3, 1, 64}, {nullptr, nullptr, 2, 2, 0}, {"conv4", "prelu4", 2, 1, 128}, {"dense5", "prelu5", 3, 1, 256},
                      {"heads", nullptr, 1, 1, 16}},
-     2, 23, 32, 16, &trl_ctx::onet_chunk, 640 * 1024, 240 * 1024},
+     2, 23, 32, 16, &trl_ctx::onet_chunk},
 };
 
 namespace {
@@ -28,10 +28,11 @@ namespace {
 struct Runner {
     trl_ctx* c;
     hipStream_t s;
+    Arena& X;                         // where alloc() takes the activations from
+    const bool check_only = X.counting;   // a counting X: shapes and tensors only -- alloc() counts, issue() launches nothing
     int err = TRL_OK;
     const int32_t* m_dev = nullptr;   // device-sized batch (candidate lists): item count lives on the device, see ConvArgs
     int m_base = 0;
-    bool check_only = false;          // trl_load_weights' walk: shapes and tensors only -- alloc() hands out no memory, issue() launches nothing
     // the plan rows of trl_debug_facenet_plan and the armed capture of trl_debug_facenet_capture (conv index = walk order)
     std::vector<trl_fn_plan_row>* plan = nullptr;
     int nconv = 0;
@@ -79,10 +80,9 @@ struct Runner {
     Act alloc(int n, int h, int w, int ch, bool bf = false) {
         Act a;
         a.n = n; a.h = h; a.w = w; a.c = ch; a.ld = ch; a.coff = 0; a.bf = bf;
-        if (check_only) return a;
-        a.p = (float*)c->scratch.alloc((size_t)n * h * w * ch * (bf ? sizeof(uint16_t) : sizeof(float)) + 64);
+        a.p = (float*)X.alloc((size_t)n * h * w * ch * (bf ? sizeof(uint16_t) : sizeof(float)) + 64);
         if (!a.p && err == TRL_OK) {
-            trl_set_error("activation scratch exhausted (%zu of %zu bytes used)", c->scratch.off, c->scratch.cap);
+            trl_set_error("activation scratch exhausted (%zu of %zu bytes used)", X.off, X.cap);
             err = TRL_ERR_STATE;
         }
         return a;
@@ -257,10 +257,10 @@ Act block8(Runner& R, const Act& x, const std::string& p, float scale, bool relu
 }  // namespace
 
 // InceptionResnetV1.eval().forward (server/model.py:59)
-int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s, bool check_only, bool features) {
+int trl_run_facenet(trl_ctx* c, Arena& X, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s, bool features) {
     if (n <= 0) return TRL_OK;
-    Runner R{c, s};
-    R.check_only = check_only;
+    Runner R{c, s, X};
+    const bool check_only = X.counting;
     struct Disarm { trl_ctx* c; ~Disarm() { if (c) c->fn_cap_arm = -1; } } disarm{check_only ? nullptr : c};   // a capture covers one call, whatever its outcome
     if (!check_only) {
         c->fn_plan.clear();
@@ -338,9 +338,9 @@ int trl_run_facenet(trl_ctx* c, const float* d_faces, int n, int h, int w, const
 }
 
 // The one walker of the MTCNN nets (contract: trl_ctx.h)
-int trl_run_net(trl_ctx* c, const NetDesc& d, int first, const Act& x0, float* d_out, hipStream_t s, const int32_t* m_dev, int m_base) {
+int trl_run_net(trl_ctx* c, Arena& X, const NetDesc& d, int first, const Act& x0, float* d_out, hipStream_t s, const int32_t* m_dev, int m_base) {
     if (x0.n <= 0) return TRL_OK;
-    Runner R{c, s};
+    Runner R{c, s, X};
     R.m_dev = m_dev; R.m_base = m_base;
     if (c->mt_plan_arm) { R.plan = &c->mt_plan; R.nconv = (int)c->mt_plan.size(); }   // trl_debug_stage_net: rows of every chunk
     const NetLayerW* lw = c->mt[&d - trl_nets];
@@ -388,9 +388,4 @@ int trl_resolve_nets(trl_ctx* c, const char* himg) {
     return TRL_OK;
 }
 
-size_t trl_pnet_generic_bytes(int nf, int h, int w) {
-    const size_t c1 = (size_t)(h - 2) * (w - 2) * 10, ph = (h - 2 + 1) / 2, pw = (w - 2 + 1) / 2;
-    const size_t p1 = ph * pw * 10, c2 = (ph - 2) * (pw - 2) * 16, c3 = (ph - 4) * (pw - 4) * 32;
-    return (size_t)nf * (c1 + p1 + c2 + c3) * sizeof(float) + 4096;
-}
 

@@ -494,6 +494,14 @@ class Engine:
         _lib.check(self.lib.trl_debug_stage_totals(self._h, t))
         return int(t[0]), int(t[1])
 
+    def workspace(self, what: int = 0, n: int = 0, h: int = 0, w: int = 0) -> dict:
+        """Test hook (``trl_debug_workspace``): the two workspaces of the context in bytes -- ``scratch_cap``, ``scratch_high`` (the
+        high-water offset of the last call that used the scratch), ``arena_cap``, ``arena_off``, ``arena_need`` -- and ``need``, the
+        dry-run count of a call that is not run: what=1 facenet_embed on n faces of h x w, what=24 / 48 rnet() / onet() on n crops."""
+        o = (C.c_longlong * 6)()
+        _lib.check(self.lib.trl_debug_workspace(self._h, int(what), int(n), int(h), int(w), o))
+        return dict(zip(("scratch_cap", "scratch_high", "arena_cap", "arena_off", "arena_need", "need"), (int(v) for v in o)))
+
     def poison_workspaces(self, byte: int = 0xFF):
         """Test hook: fill the activation workspaces with a byte pattern (0xFF = NaNs)."""
         _lib.check(self.lib.trl_debug_poison(self._h, int(byte)))

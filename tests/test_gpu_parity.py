@@ -586,6 +586,35 @@ def test_batch_capacity_overflow_reruns_the_call(blob, oracle):
     assert (rb is None and k0 == 0) or np.array_equal(b[0, :k0].cpu().numpy(), rb)
 
 
+def test_capacity_overflows_settle_to_the_measured_plan(blob, oracle):
+    """One call on start capacities that are all too small for its content (the noise frames of the spill-pool test, lists of 64,
+    tiers 16 / 64, one R-/O-Net candidate of head-room): the level lists overflow and the frame lists are grown in the same step,
+    then the R-Net batch, then the O-Net batch -- four attempts -- and the second call fits at once on slightly other capacities
+    (the hints settled from what the call measured).  The list statistics of both calls are pinned to what the library BEFORE
+    csrc/trl_capacity.h existed reported for the same script (its build selected with TRUELY_HIP_LIB):
+
+        TRUELY_HIP_LIB=<library of the commit before> python -c "<the four Engine lines below>; eng.detect_embed(noisy);
+            print(eng.list_stats(), eng.stage_totals()); eng.detect_embed(noisy); print(eng.list_stats(), eng.stage_totals())"
+
+    The spill pool does not overflow here, nor can small frames make it: lists that can outgrow the LDS tier get their workspace
+    up front, so the pool follows the list capacities (0 bytes at the first attempt, 39,296 once the lists had grown).  That
+    branch, and a frame list overflowing on its own, are covered on the CPU (tests/test_capacity_cpu.py)."""
+    from truely_amd.engine import Engine
+    eng = Engine(blob, cap_level=64, cap_frame=64)
+    eng.nms_tiers(16, 64)
+    eng.batch_capacity(0.25, 0.25)
+    noisy = np.random.default_rng(5).integers(0, 256, (2, 120, 160, 3), dtype=np.uint8)
+    ref = oracle.detect_embed(noisy)
+    measured = dict(spill_lists=8, spill_used=31232, slots_per_frame=348, max_level_count=82, max_frame_total=86)
+    for want in (dict(attempts=4, spill_cap=39296, cap_frame=108, **measured), dict(attempts=1, spill_cap=39968, cap_frame=112, **measured)):
+        out = eng.detect_embed(noisy)
+        assert eng.list_stats() == want
+        assert eng.stage_totals() == (171, 171)
+        assert eng.batch_capacity() == want["attempts"]
+        for k in ("box", "prob", "rect", "valid", "emb"):
+            assert np.array_equal(out[k].cpu().numpy(), ref[k]), k
+
+
 def test_multi_chunk_candidate_batches(blob, oracle):
     """R-/O-Net candidate batches larger than one launch set are processed in chunks (device-side `total - chunk_base` clamps).
     With the chunk sizes shrunk to 16 / 16 candidates (trl_debug_option) a 360p clip needs many chunks, some of them partially

@@ -418,7 +418,7 @@ static int call_enqueue(trl_ctx* c) {
     hipStream_t s = (hipStream_t)q.stream;
     const int n = q.n, H = q.H, W = q.W;
     if (!q.attempt) TRL_HIP(hipEventRecord(c->ev_call0, s));   // trl_debug_timings: out[1] covers every attempt of the call
-    TRL_CHECK(trl_cascade_detect(c, q.frames, n, H, W, s, q.attempt ? c->resume_stage : 0));
+    TRL_CHECK(trl_cascade_detect(c, q.frames, n, H, W, s, q.attempt ? c->caps.resume_stage : 0));
     if (q.kind == trl_ctx::Pending::DETECT) {
         // model.py's per-frame outputs are not asked for: they go to the blocks behind the lists
         TRL_HIP(hipMemsetAsync(q.boxes, 0, (size_t)n * c->cfg.max_faces * 16, s));
@@ -456,10 +456,14 @@ static int call_begin(trl_ctx* c, const trl_ctx::Pending& q) {
     return st;
 }
 
-// Every attempt that overflows a capacity raises that capacity to the need the attempt measured (trl_cascade_check), and a
-// stage's need is measured once the stages in front of it ran on complete lists.  There are five capacities -- level lists,
-// frame lists, spill workspace, R-Net batch, O-Net batch -- so a call converges in at most six attempts: the bound is never
-// reached by any input (detect_face() has no candidate limit, and neither has this call), it only turns a bug into an error.
+// Every attempt that overflows a capacity raises that capacity to the need the attempt measured (trl_caps_check), and a stage's
+// need is measured once the stages in front of it ran on complete lists.  There are five capacities -- level lists, frame lists,
+// spill workspace, R-Net batch, O-Net batch -- but a call can take more than six attempts: the spill pool can overflow twice (for
+// the level lists, and again for the frame lists that exist only once the level lists are complete), and a per-frame total
+// measured while the pool dropped lists is a lower bound.  The model device of tests/test_capacity_cpu.py (500 need sets, from
+// empty to every cell of a 16383 px frame a candidate) needed at most 7: level lists, spill pool + frame lists, frame lists,
+// spill pool, R-Net batch, O-Net batch, the attempt that fits.  The bound below is never reached by any input (detect_face()
+// has no candidate limit, and neither has this call), it only turns a bug into an error.
 enum { TRL_MAX_ATTEMPTS = 12 };
 
 static int call_wait(trl_ctx* c) {
@@ -472,7 +476,7 @@ static int call_wait(trl_ctx* c) {
         if ((st = (hipStreamSynchronize(s) == hipSuccess ? TRL_OK : TRL_ERR_HIP)) != TRL_OK) { trl_set_error("hipStreamSynchronize: %s", hipGetErrorString(hipGetLastError())); break; }
         int retry = 0;
         if ((st = trl_cascade_check(c, c->pend.n, &retry)) != TRL_OK) break;
-        c->last_attempts = ++c->pend.attempt;
+        c->caps.last_attempts = ++c->pend.attempt;
         if (!retry) break;
         if (c->pend.attempt >= TRL_MAX_ATTEMPTS) { trl_set_error("candidate capacities did not converge"); st = TRL_ERR_STATE; break; }
         if ((st = call_enqueue(c)) != TRL_OK) break;
@@ -626,12 +630,12 @@ int trl_drift_update(trl_ctx* c, void* d_state, const float* d_emb, const uint8_
 // ---- inspection hooks ----------------------------------------------------------------------------------
 int trl_debug_stage_boxes(trl_ctx* c, int stage, int frame, float* h_boxes, int max_rows, int* n_out) {
     TRL_CHECK(trl_check_idle(c));
-    if (!c->cb.n1 || frame < 0 || frame >= c->cb.n || stage < 1 || stage > 3 || !n_out || (max_rows > 0 && !h_boxes)) {
+    if (!c->cb.cnt[0] || frame < 0 || frame >= c->cb.n || stage < 1 || stage > 3 || !n_out || (max_rows > 0 && !h_boxes)) {
         trl_set_error("no cascade state");
         return TRL_ERR_STATE;
     }
-    const int32_t* cnt = stage == 1 ? c->cb.n1 : (stage == 2 ? c->cb.n2 : c->cb.n3);
-    const float* src = stage == 1 ? c->cb.s1_box : (stage == 2 ? c->cb.s2_box : c->cb.s3_box);
+    const int32_t* cnt = c->cb.cnt[stage - 1];
+    const float* src = c->cb.box[stage - 1];
     int32_t k = 0;
     TRL_HIP(hipDeviceSynchronize());
     TRL_HIP(hipMemcpy(&k, cnt + frame, 4, hipMemcpyDeviceToHost));
@@ -1005,7 +1009,7 @@ int trl_debug_list_stats(trl_ctx* c, long long* h_out8) {
     memcpy(&used, f + FLG_SPILL_CUR, 8);
     int mx = 0;
     for (int l = 0; l < 32; l++) if (f[FLG_LEVEL_MAX + l] > mx) mx = f[FLG_LEVEL_MAX + l];
-    h_out8[0] = c->last_attempts; h_out8[1] = f[FLG_SPILL_LISTS]; h_out8[2] = (long long)used; h_out8[3] = (long long)c->cb.spill_cap;
+    h_out8[0] = c->caps.last_attempts; h_out8[1] = f[FLG_SPILL_LISTS]; h_out8[2] = (long long)used; h_out8[3] = (long long)c->cb.spill_cap;
     h_out8[4] = c->cb.capF; h_out8[5] = c->cb.lay.S; h_out8[6] = mx; h_out8[7] = f[FLG_FRAME_MAX];
     return TRL_OK;
 }
@@ -1034,9 +1038,9 @@ int trl_debug_pnet_screen_bound(trl_ctx* c, float* A, float* B, int* on) {
 
 int trl_debug_batch_capacity(trl_ctx* c, float t2_per_frame, float t3_per_frame, int* last_attempts) {
     if (!c) { trl_set_error("null context"); return TRL_ERR_INVALID; }
-    if (t2_per_frame > 0.f) c->t2_per_frame = t2_per_frame;
-    if (t3_per_frame > 0.f) c->t3_per_frame = t3_per_frame;
-    if (last_attempts) *last_attempts = c->last_attempts;
+    if (t2_per_frame > 0.f) c->caps.t_per_frame[0] = t2_per_frame;
+    if (t3_per_frame > 0.f) c->caps.t_per_frame[1] = t3_per_frame;
+    if (last_attempts) *last_attempts = c->caps.last_attempts;
     return TRL_OK;
 }
 

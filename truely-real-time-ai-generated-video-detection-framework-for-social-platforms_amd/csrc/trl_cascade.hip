@@ -190,7 +190,7 @@ struct Smem {   // carve the dynamic LDS for capacity `cap`
 //            sequential rule, so the pick order and every keep decision equal the LDS tier's (and the reference's).
 // Workspace comes from a bump pool in the cascade arena (one atomic per list); a pool that runs out raises a flag and the call is
 // re-run with a larger one, like every other capacity (trl_cascade_check).
-struct Spill { char* base; unsigned long long cap; int32_t* flags; };   // the pool and the overflow words (trl_ctx.h FLG_*)
+struct Spill { char* base; unsigned long long cap; int32_t* flags; };   // the pool and the overflow words (trl_capacity.h FLG_*)
 __device__ char* spill_alloc(const Spill& sp, size_t bytes) {   // every thread of the workgroup calls it; uniform result
     __shared__ unsigned long long off_s;
     bytes = (bytes + 255) & ~(size_t)255;
@@ -818,33 +818,14 @@ int trl_launch_heads_to_maps(const float* d_heads, int cells, float* d_prob, flo
     return TRL_OK;
 }
 
-// Record slots per level and rows per frame of this call: the configured start values, raised to what recent calls needed
-// (trl_cascade_check), never beyond what the geometry can produce (a level has oh x ow cells; a frame's stage-1 list is a subset
-// of its cells) -- so a frame small enough cannot overflow at all.
-static void plan_lists(trl_ctx* c, int L) {
-    CascadeBufs& B = c->cb;
-    LvLayout& G = B.lay;
-    G = LvLayout();
-    G.L = L;
-    long long cells_total = 0;
-    int S = 0;
-    for (int l = 0; l < L; l++) {
-        const long long cells = (long long)c->lv[l].oh * c->lv[l].ow;
-        long long want = c->cfg.cap_level;
-        if ((long long)c->lvl_hint[l] > want) want = (long long)c->lvl_hint[l];
-        if (want > cells) want = cells;
-        if (want < 4) want = 4;
-        G.capl[l] = (int)((want + 3) & ~3ll);
-        G.rec0[l] = S;
-        S += G.capl[l];
-        cells_total += cells;
-    }
-    G.S = S;
-    long long wantF = c->cfg.cap_frame;
-    if ((long long)c->frame_hint > wantF) wantF = (long long)c->frame_hint;
-    if (wantF > cells_total) wantF = cells_total;
-    if (wantF < 4) wantF = 4;
-    B.capF = (int)((wantF + 3) & ~3ll);
+// The capacities of this attempt (trl_capacity.h): record slots per level, rows per frame, the R-/O-Net batches
+static void plan_caps(trl_ctx* c, int L, int n) {
+    long long cells[32];
+    for (int l = 0; l < L; l++) cells[l] = (long long)c->lv[l].oh * c->lv[l].ow;
+    const CascadePlan p = trl_caps_plan(c->caps, c->cfg.cap_level, c->cfg.cap_frame, cells, L, n);
+    c->cb.lay = p.lay;
+    c->cb.capF = p.capF;
+    c->caps.cap_t[0] = p.cap_t[0]; c->caps.cap_t[1] = p.cap_t[1];
 }
 static size_t spill_need(long long cnt, int W, int H) {   // upper bound of the workspace of one spilled list of cnt entries, whichever kernel spills it
     long long P = 2;
@@ -857,7 +838,7 @@ static size_t spill_need(long long cnt, int W, int H) {   // upper bound of the 
 static size_t spill_pool(const trl_ctx* c, int n, int H, int W) {
     const LvLayout& G = c->cb.lay;
     const int lds_full = c->nms_full;
-    size_t spill = c->spill_hint;
+    size_t spill = c->caps.spill_hint;
     size_t per_frame = 0;
     for (int l = 0; l < G.L; l++) if (G.capl[l] > lds_full) per_frame += spill_need(G.capl[l], W, H);
     if (c->cb.capF > lds_full) per_frame += 3 * spill_need(c->cb.capF, W, H);
@@ -907,21 +888,34 @@ static int launch_stage1_lists(trl_ctx* c, const ListLaunch& ll, int n, int H, i
         k_nms_level<<<n * L, ll.th_l, ll.sm_l, s>>>(G, ll.full_l, ll.small_cap + 1, 1, W, H, B.lvl_cnt, B.lvl_rec, B.lvl_keep_cnt, B.lvl_keep_idx, B.flags, sp);
         TRL_LAUNCH_CHECK();
     }
-    k_nms_frame<<<n, ll.th_f, ll.sm_f, s>>>(G, ll.full_f, B.capF, W, H, B.lvl_rec, B.lvl_keep_cnt, B.lvl_keep_idx, B.n1, B.s1_box, B.flags, sp);
+    k_nms_frame<<<n, ll.th_f, ll.sm_f, s>>>(G, ll.full_f, B.capF, W, H, B.lvl_rec, B.lvl_keep_cnt, B.lvl_keep_idx, B.cnt[0], B.box[0], B.flags, sp);
     TRL_LAUNCH_CHECK();
     return TRL_OK;
 }
-// stage 2 tail over the R-Net outputs out6 [cap2][6] (candidate off2[f] + i = row i of frame f)
-static int launch_stage2_post(trl_ctx* c, const ListLaunch& ll, int n, int H, int W, int cap2, const float* out6, const Spill& sp, hipStream_t s) {
-    CascadeBufs& B = c->cb;
-    k_stage2_post<<<n, ll.th_f, ll.sm_f, s>>>(ll.full_f, B.capF, cap2, W, H, c->cfg.thr1, B.n1, B.s1_box, B.off2, out6, B.n2, B.s2_box, sp);
+// Stages 2 and 3, described once: the net (trl_net_of), its threshold, and the launch of its tail kernel over the net's outputs
+// out [cap][nout] (candidate off[st][f] + i = row i of frame f).  Stage st + 2 reads the lists of index st and writes those of
+// st + 1; its flag slot is st (k_scan_counts) and its batch capacity c->caps.cap_t[st].
+struct StageDesc {
+    int net;
+    float trl_config::*thr;
+    void (*post)(const CascadeBufs& B, const ListLaunch& ll, int cap, float thr, const float* out, const Spill& sp, hipStream_t s);
+};
+static const StageDesc trl_stages[2] = {
+    {24, &trl_config::thr1, [](const CascadeBufs& B, const ListLaunch& ll, int cap, float thr, const float* out, const Spill& sp, hipStream_t s) {
+         k_stage2_post<<<B.n, ll.th_f, ll.sm_f, s>>>(ll.full_f, B.capF, cap, B.W, B.H, thr, B.cnt[0], B.box[0], B.off[0], out, B.cnt[1], B.box[1], sp);
+     }},
+    {48, &trl_config::thr2, [](const CascadeBufs& B, const ListLaunch& ll, int cap, float thr, const float* out, const Spill& sp, hipStream_t s) {
+         k_stage3_post<<<B.n, ll.th_f, ll.sm_f, s>>>(ll.full_f, B.capF, cap, thr, B.cnt[1], B.box[1], B.off[1], out, B.cnt[2], B.box[2], B.pts3, sp);
+     }},
+};
+// the batch of stage st + 2: the exclusive scan of its input counts, its total and whether it fits `cap` (flag slot st)
+static int launch_stage_scan(const CascadeBufs& B, int st, int cap, hipStream_t s) {
+    k_scan_counts<<<1, 256, 0, s>>>(B.cnt[st], B.n, B.off[st], cap, B.flags, st);
     TRL_LAUNCH_CHECK();
     return TRL_OK;
 }
-// stage 3 tail over the O-Net outputs out16 [cap3][16]
-static int launch_stage3_post(trl_ctx* c, const ListLaunch& ll, int n, int cap3, const float* out16, const Spill& sp, hipStream_t s) {
-    CascadeBufs& B = c->cb;
-    k_stage3_post<<<n, ll.th_f, ll.sm_f, s>>>(ll.full_f, B.capF, cap3, c->cfg.thr2, B.n2, B.s2_box, B.off3, out16, B.n3, B.s3_box, B.s3_pts, sp);
+static int launch_stage_post(trl_ctx* c, const ListLaunch& ll, int st, int cap, const float* out, const Spill& sp, hipStream_t s) {
+    trl_stages[st].post(c->cb, ll, cap, c->cfg.*trl_stages[st].thr, out, sp, s);
     TRL_LAUNCH_CHECK();
     return TRL_OK;
 }
@@ -936,10 +930,10 @@ static void layout_lists(CascadeBufs& B, Arena& A, size_t spill) {
     B.lvl_keep_cnt = (int32_t*)A.alloc((size_t)n * L * 4);
     B.lvl_rec = (Cand*)A.alloc((size_t)n * G.S * sizeof(Cand));
     B.lvl_keep_idx = (int32_t*)A.alloc((size_t)n * G.S * 4);
-    B.n1 = (int32_t*)A.alloc((size_t)n * 4); B.n2 = (int32_t*)A.alloc((size_t)n * 4); B.n3 = (int32_t*)A.alloc((size_t)n * 4);
-    B.s1_box = (float*)A.alloc((size_t)n * capF * 20); B.s2_box = (float*)A.alloc((size_t)n * capF * 20);
-    B.s3_box = (float*)A.alloc((size_t)n * capF * 20); B.s3_pts = (float*)A.alloc((size_t)n * capF * 40);
-    B.off2 = (int32_t*)A.alloc((size_t)(n + 1) * 4); B.off3 = (int32_t*)A.alloc((size_t)(n + 1) * 4);
+    for (int k = 0; k < 3; k++) B.cnt[k] = (int32_t*)A.alloc((size_t)n * 4);
+    for (int k = 0; k < 3; k++) B.box[k] = (float*)A.alloc((size_t)n * capF * 20);
+    B.pts3 = (float*)A.alloc((size_t)n * capF * 40);
+    for (int k = 0; k < 2; k++) B.off[k] = (int32_t*)A.alloc((size_t)(n + 1) * 4);
     B.cbox = (int32_t*)A.alloc((size_t)n * capF * 32);
     B.flags = (int32_t*)A.alloc(TRL_NFLAGS * 4);
     B.spill = spill ? (char*)A.alloc(spill) : nullptr;
@@ -991,13 +985,9 @@ static int stage_carve(trl_ctx* c, Arena& X, int net, const uint8_t* d_frames, i
     return trl_stage_net(c, X, net, d_frames, H, W, d_total, cap, *d_out, s);
 }
 
-// Capacities of the R-/O-Net candidate batches of this call, and ONE scratch workspace big enough for every stage: it is only
-// ever grown here, before anything of the call is queued (growing frees the old block)
+// ONE scratch workspace big enough for every stage at this attempt's batch capacities: it is only ever grown here, before
+// anything of the call is queued (growing frees the old block)
 static int size_scratch(trl_ctx* c, int n, int H, int W, bool fused) {
-    long long c2 = (long long)(c->t2_per_frame * n) + 64, c3 = (long long)(c->t3_per_frame * n) + 64;
-    const long long lim = (long long)n * c->cb.capF;
-    c->cap_t2 = (int)(c2 < lim ? c2 : lim);
-    c->cap_t3 = (int)(c3 < lim ? c3 : lim);
     // one counting arena under all that carves the scratch in turn (each from a reset): its high-water mark is the call's need
     Arena X = Arena::counter();
     X.high = std::max(c->scratch_after_cascade, fused ? trl_pnet_fused_bytes(c, n, H, W) + (1u << 20) : 0);
@@ -1009,8 +999,7 @@ static int size_scratch(trl_ctx* c, int n, int H, int W, bool fused) {
         g.chunk = (int)std::min<size_t>(n, std::max<size_t>(1, (size_t)(2048ull << 20) / X.off));
         TRL_CHECK(trl_pnet_generic_level(c, X, nullptr, g.chunk, 0, 0, g, &o, nullptr));
     }
-    TRL_CHECK(stage_carve(c, X, 24, nullptr, 0, 0, nullptr, c->cap_t2, &o, nullptr));
-    TRL_CHECK(stage_carve(c, X, 48, nullptr, 0, 0, nullptr, c->cap_t3, &o, nullptr));
+    for (int st = 0; st < 2; st++) TRL_CHECK(stage_carve(c, X, trl_stages[st].net, nullptr, 0, 0, nullptr, c->caps.cap_t[st], &o, nullptr));
     return trl_scratch_begin(c, X.high);
 }
 
@@ -1052,32 +1041,19 @@ static int stage1_generic(trl_ctx* c, const uint8_t* d_frames, hipStream_t s) {
     return TRL_OK;
 }
 
-// stage 2: R-Net over the stage-1 boxes, then its tail.  No host round trip: the candidate total stays on the device (off2[n]).
-// Launches are sized by an optimistic capacity (c->cap_t2, from earlier calls) and workgroups past the real total exit at once;
-// if the total exceeds the capacity a flag is raised and the call is re-run with a larger one (trl_cascade_check).
-static int stage2(trl_ctx* c, const ListLaunch& ll, const uint8_t* d_frames, const Spill& sp, hipStream_t s) {
+// Stage st + 2: R-Net over the stage-1 boxes / O-Net over the stage-2 boxes, then its tail.  No host round trip: the candidate
+// total stays on the device (off[st][n]).  Launches are sized by an optimistic capacity (c->caps.cap_t[st], from earlier calls) and
+// workgroups past the real total exit at once; if the total exceeds the capacity a flag is raised and the call is re-run with a
+// larger one (trl_cascade_check).
+static int stage_net_and_post(trl_ctx* c, int st, const ListLaunch& ll, const uint8_t* d_frames, const Spill& sp, hipStream_t s) {
     const CascadeBufs& B = c->cb;
-    const int n = B.n, H = B.H, W = B.W, cap2 = c->cap_t2;
-    k_scan_counts<<<1, 256, 0, s>>>(B.n1, n, B.off2, cap2, B.flags, 0);
+    const int n = B.n, H = B.H, W = B.W, cap = c->caps.cap_t[st];
+    TRL_CHECK(launch_stage_scan(B, st, cap, s));
+    k_build_map<<<n, 64, 0, s>>>(B.cnt[st], B.off[st], B.box[st], B.capF, W, H, B.cbox);
     TRL_LAUNCH_CHECK();
-    k_build_map<<<n, 64, 0, s>>>(B.n1, B.off2, B.s1_box, B.capF, W, H, B.cbox);
-    TRL_LAUNCH_CHECK();
-    float* out6;
-    TRL_CHECK(stage_carve(c, c->scratch, 24, d_frames, H, W, B.off2 + n, cap2, &out6, s));
-    return launch_stage2_post(c, ll, n, H, W, cap2, out6, sp, s);
-}
-
-// stage 3: O-Net over the stage-2 boxes, then its tail (capacity c->cap_t3, as stage 2)
-static int stage3(trl_ctx* c, const ListLaunch& ll, const uint8_t* d_frames, const Spill& sp, hipStream_t s) {
-    const CascadeBufs& B = c->cb;
-    const int n = B.n, H = B.H, W = B.W, cap3 = c->cap_t3;
-    k_scan_counts<<<1, 256, 0, s>>>(B.n2, n, B.off3, cap3, B.flags, 1);
-    TRL_LAUNCH_CHECK();
-    k_build_map<<<n, 64, 0, s>>>(B.n2, B.off3, B.s2_box, B.capF, W, H, B.cbox);
-    TRL_LAUNCH_CHECK();
-    float* out16;
-    TRL_CHECK(stage_carve(c, c->scratch, 48, d_frames, H, W, B.off3 + n, cap3, &out16, s));
-    return launch_stage3_post(c, ll, n, cap3, out16, sp, s);
+    float* out;
+    TRL_CHECK(stage_carve(c, c->scratch, trl_stages[st].net, d_frames, H, W, B.off[st] + n, cap, &out, s));
+    return launch_stage_post(c, ll, st, cap, out, sp, s);
 }
 
 // detect_face() stages 1-3 for n frames; results stay in c->cb
@@ -1088,13 +1064,14 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     CascadeBufs& B = c->cb;
     if (resume >= 2 && !(B.flags && B.n == n && B.L == L && B.H == H && B.W == W && L > 0)) resume = 0;   // nothing to resume from
     B.n = n; B.L = L; B.H = H; B.W = W;
-    if (!resume) plan_lists(c, L);
+    plan_caps(c, L, n);   // (a resumed attempt plans the lists it has: the check behind the last one raised a batch hint only)
     const size_t spill = spill_pool(c, n, H, W);
     if (resume) {
         // the stages that run again report afresh (the stage-2 total of a resume at stage 3 stays: it is complete)
-        TRL_HIP(hipMemsetAsync(B.flags + FLG_T3, 0, 4, s));
-        TRL_HIP(hipMemsetAsync(B.flags + FLG_T3N, 0, 4, s));
-        if (resume == 2) { TRL_HIP(hipMemsetAsync(B.flags + FLG_T2, 0, 4, s)); TRL_HIP(hipMemsetAsync(B.flags + FLG_T2N, 0, 4, s)); }
+        for (int st = resume - 2; st < 2; st++) {
+            TRL_HIP(hipMemsetAsync(B.flags + FLG_T2 + st, 0, 4, s));
+            TRL_HIP(hipMemsetAsync(B.flags + FLG_T2N + st, 0, 4, s));
+        }
     } else {
         TRL_CHECK(carve_lists(c, spill, s));
     }
@@ -1102,11 +1079,8 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     if (L == 0) {
         // min(H, W) * 12 / min_face_size < 12: detect_face() builds no scale at all and returns no boxes (the frame is smaller
         // than the smallest face looked for).  Every stage count is zero; k_select then reports "no face" for every frame.
-        TRL_HIP(hipMemsetAsync(B.n1, 0, (size_t)n * 4, s));
-        TRL_HIP(hipMemsetAsync(B.n2, 0, (size_t)n * 4, s));
-        TRL_HIP(hipMemsetAsync(B.n3, 0, (size_t)n * 4, s));
-        TRL_HIP(hipMemsetAsync(B.off2, 0, (size_t)(n + 1) * 4, s));
-        TRL_HIP(hipMemsetAsync(B.off3, 0, (size_t)(n + 1) * 4, s));
+        for (int k = 0; k < 3; k++) TRL_HIP(hipMemsetAsync(B.cnt[k], 0, (size_t)n * 4, s));
+        for (int k = 0; k < 2; k++) TRL_HIP(hipMemsetAsync(B.off[k], 0, (size_t)(n + 1) * 4, s));
         TRL_CHECK(trl_scratch_begin(c, c->scratch_after_cascade));   // the crops + embedder of the same call
         return TRL_OK;
     }
@@ -1121,8 +1095,8 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     ListLaunch ll;
     TRL_CHECK(list_launch(c, ll));
     if (!resume) TRL_CHECK(launch_stage1_lists(c, ll, n, H, W, sp, s));
-    if (resume < 3) TRL_CHECK(stage2(c, ll, d_frames, sp, s));
-    return stage3(c, ll, d_frames, sp, s);
+    for (int st = resume ? resume - 2 : 0; st < 2; st++) TRL_CHECK(stage_net_and_post(c, st, ll, d_frames, sp, s));
+    return TRL_OK;
 }
 
 // One R-Net (net = 24) or O-Net (net = 48) stage over `cap` candidate slots: chunks of c->rnet_chunk / c->onet_chunk candidates,
@@ -1151,7 +1125,7 @@ int trl_cascade_finish(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
                        int order) {
     (void)d_frames;
     CascadeBufs& B = c->cb;
-    k_select<<<n, 64, 0, s>>>(B.capF, c->cfg.max_faces, W, H, order, B.n3, B.s3_box, B.s3_pts, d_boxes, d_probs, d_points, d_counts, d_box0, d_prob0,
+    k_select<<<n, 64, 0, s>>>(B.capF, c->cfg.max_faces, W, H, order, B.cnt[2], B.box[2], B.pts3, d_boxes, d_probs, d_points, d_counts, d_box0, d_prob0,
                               d_rect, d_valid, d_pts0);
     TRL_LAUNCH_CHECK();
     // overflow flags + stage totals travel to pinned host memory behind the kernels; trl_cascade_check reads them after the
@@ -1165,60 +1139,12 @@ int trl_cascade_finish(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
 // attempt measured and the caller runs the call again (results of the attempt are incomplete, not wrong-but-plausible, and are
 // never delivered).  No input can make this fail: detect_face() (server/model.py:47) has no candidate limit.
 int trl_cascade_check(trl_ctx* c, int n, int* retry) {
-    const int32_t* f = c->h_pinned + 4;
-    const int L = c->cb.L;
-    *retry = 0;
-    c->resume_stage = 0;
-    unsigned long long spill_used = 0;
-    memcpy(&spill_used, f + FLG_SPILL_CUR, 8);
-    if (f[FLG_LEVEL]) {                                  // every later stage ran on truncated lists: their totals mean nothing
-        long long sum = 0;
-        for (int l = 0; l < L; l++) {
-            const float want = 1.25f * (float)f[FLG_LEVEL_MAX + l] + 4.f;
-            if (f[FLG_LEVEL_MAX + l] > c->cb.lay.capl[l] && want > c->lvl_hint[l]) c->lvl_hint[l] = want;
-            sum += f[FLG_LEVEL_MAX + l];
-        }
-        // a frame's stage-1 list is a subset of its candidates: when the per-frame lists of the batch stay under 8 GB at that bound,
-        // grow them in the same step (one attempt less for crowded content; otherwise the next attempt measures the real total)
-        if ((float)sum > c->frame_hint && (double)sum * 132.0 * (double)n < 8e9) c->frame_hint = (float)sum;
-        *retry = 1;
-        return TRL_OK;
-    }
-    if (f[FLG_SPILL]) {                                  // lists that found no workspace were dropped: later totals are incomplete
-        c->spill_hint = (size_t)spill_used * 2 + (16u << 20);
-        *retry = 1;
-        if (f[FLG_FRAME]) c->frame_hint = 1.25f * (float)f[FLG_FRAME_MAX] + 4.f;
-        return TRL_OK;
-    }
-    if (f[FLG_FRAME]) { c->frame_hint = 1.25f * (float)f[FLG_FRAME_MAX] + 4.f; *retry = 1; return TRL_OK; }
-    // keep ~25 % headroom over the largest batch seen, so a drifting clip rarely needs a second attempt
-    const float want2 = 1.25f * (float)f[FLG_T2N] / (float)n + 1.f, want3 = 1.25f * (float)f[FLG_T3N] / (float)n + 1.f;
-    if (f[FLG_T2]) { c->t2_per_frame = want2; *retry = 1; c->resume_stage = 2; }       // stage 3 ran on an incomplete stage 2: its total is meaningless
-    else if (f[FLG_T3]) { c->t3_per_frame = want3; *retry = 1; c->resume_stage = 3; }  // (stages 1 / 1-2 are intact: the re-run starts behind them)
-    if (!*retry) {
-        // follow the content: grow at once, decay 3 % per call towards what recent batches needed (never below the start values),
-        // so one crowded batch does not inflate every later call's launches and workspace for the life of the context
-        const float d2 = 0.97f * c->t2_per_frame, d3 = 0.97f * c->t3_per_frame;
-        c->t2_per_frame = want2 > d2 ? want2 : (d2 > 160.f ? d2 : (c->t2_per_frame < 160.f ? c->t2_per_frame : 160.f));
-        c->t3_per_frame = want3 > d3 ? want3 : (d3 > 48.f ? d3 : (c->t3_per_frame < 48.f ? c->t3_per_frame : 48.f));
-        for (int l = 0; l < L; l++) {                    // list capacities decay the same way (values below the configured start are ignored)
-            const float want = 1.25f * (float)f[FLG_LEVEL_MAX + l] + 4.f, d = 0.97f * c->lvl_hint[l];
-            c->lvl_hint[l] = want > d ? want : d;
-        }
-        {
-            const float want = 1.25f * (float)f[FLG_FRAME_MAX] + 4.f, d = 0.97f * c->frame_hint;
-            c->frame_hint = want > d ? want : d;
-        }
-        {
-            const size_t want = (size_t)spill_used + (spill_used >> 2), d = c->spill_hint - (c->spill_hint >> 5);
-            c->spill_hint = spill_used ? (want > d ? want : d) : (d > (1u << 20) ? d : 0);
-        }
-    }
+    *retry = trl_caps_check(c->caps, c->h_pinned + 4, n, c->cb.lay).retry;
     return TRL_OK;
 }
 
 // test hook behind trl_debug_lists: the list kernels on lists the caller provides, in the cascade's own layout (carve_lists),
-// launched by its own code (list_launch, launch_stage1_lists / launch_stage2_post / launch_stage3_post, trl_cascade_finish) with
+// launched by its own code (list_launch, launch_stage1_lists / launch_stage_scan / launch_stage_post, trl_cascade_finish) with
 // its spill pool and overflow flags.  kind 1: h_rows = Cand records of every (frame, level), frame-major, h_counts [n][L]; kind 2: stage-1 rows
 // (x1, y1, x2, y2, score) of every frame, h_counts [n], h_logits the R-Net outputs [total][6]; kind 3: stage-2 rows, h_logits the
 // O-Net outputs [total][16], then k_select into the d_* outputs and the stage-3 landmarks into h_pts [n][capF][10] (nullable).
@@ -1237,14 +1163,15 @@ int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* 
     const int capF = B.capF, nc = kind == 1 ? n * L : n;
     long long total = 0;
     for (int i = 0; i < nc; i++) total += h_counts[i];
-    const int st = carve_lists(c, spill_pool(c, n, H, W), s);
-    if (st != TRL_OK) { B = CascadeBufs(); return st; }
+    const int carved = carve_lists(c, spill_pool(c, n, H, W), s);
+    if (carved != TRL_OK) { B = CascadeBufs(); return carved; }
     const int poison = c->dbg_poison >= 0 ? c->dbg_poison : 0xA5;
     TRL_HIP(hipMemsetAsync(c->arena.base, poison, (size_t)((char*)B.flags - c->arena.base), s));   // every list (the flags stay zero)
     // the caller's lists, packed, into the capacity layout; the poison stays in the slots behind the counts
     std::vector<int32_t> cnt(h_counts, h_counts + nc);
     std::vector<float> logits;
-    const int NO = kind == 2 ? 6 : 16;
+    const int st = kind - 2;                              // kinds 2 / 3: the stage's index (trl_stages)
+    const int NO = kind == 1 ? 0 : trl_net_of(trl_stages[st].net).nout;
     if (kind == 1) {
         const Cand* src = (const Cand*)h_rows;
         TRL_HIP(hipMemcpyAsync(B.lvl_cnt, cnt.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
@@ -1256,8 +1183,8 @@ int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* 
             }
     } else {
         const float* src = (const float*)h_rows;
-        float* rows = kind == 2 ? B.s1_box : B.s2_box;
-        TRL_HIP(hipMemcpyAsync(kind == 2 ? B.n1 : B.n2, cnt.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+        float* rows = B.box[st];
+        TRL_HIP(hipMemcpyAsync(B.cnt[st], cnt.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
         for (int f = 0; f < n; f++) {
             if (cnt[f]) TRL_HIP(hipMemcpyAsync(rows + (size_t)f * capF * 5, src, (size_t)cnt[f] * 20, hipMemcpyHostToDevice, s));
             src += 5 * (size_t)cnt[f];
@@ -1279,22 +1206,17 @@ int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* 
         if (!out) { trl_set_error("list hook net outputs"); return TRL_ERR_STATE; }
         TRL_HIP(hipMemsetAsync(out, poison, (size_t)cap * NO * 4, s));
         if (total) TRL_HIP(hipMemcpyAsync(out, logits.data(), logits.size() * 4, hipMemcpyHostToDevice, s));
-        if (kind == 2) {
-            k_scan_counts<<<1, 256, 0, s>>>(B.n1, n, B.off2, cap, B.flags, 0);
-            TRL_LAUNCH_CHECK();
-            TRL_CHECK(launch_stage2_post(c, ll, n, H, W, cap, out, sp, s));
-        } else {
-            k_scan_counts<<<1, 256, 0, s>>>(B.n2, n, B.off3, cap, B.flags, 1);
-            TRL_LAUNCH_CHECK();
-            TRL_CHECK(launch_stage3_post(c, ll, n, cap, out, sp, s));
+        TRL_CHECK(launch_stage_scan(B, st, cap, s));
+        TRL_CHECK(launch_stage_post(c, ll, st, cap, out, sp, s));
+        if (kind == 3) {
             TRL_CHECK(trl_cascade_finish(c, nullptr, n, H, W, d_boxes, d_probs, d_points, d_counts, d_box0, d_prob0, d_rect, d_valid, nullptr, s));
         }
         TRL_HIP(hipStreamSynchronize(s));                 // (the logits vector)
     }
     if (kind != 3) TRL_HIP(hipMemcpyAsync(c->h_pinned + 4, B.flags, TRL_NFLAGS * 4, hipMemcpyDeviceToHost, s));
-    if (kind == 3 && h_pts) TRL_HIP(hipMemcpyAsync(h_pts, B.s3_pts, (size_t)n * capF * 40, hipMemcpyDeviceToHost, s));
+    if (kind == 3 && h_pts) TRL_HIP(hipMemcpyAsync(h_pts, B.pts3, (size_t)n * capF * 40, hipMemcpyDeviceToHost, s));
     TRL_HIP(hipStreamSynchronize(s));
-    c->last_attempts = 1;
+    c->caps.last_attempts = 1;
     const int32_t* fl = c->h_pinned + 4;
     if (fl[FLG_LEVEL] || fl[FLG_FRAME] || fl[FLG_SPILL]) {
         trl_set_error("list hook: a capacity was too small (level %d, frame %d, spill %d)", fl[FLG_LEVEL], fl[FLG_FRAME], fl[FLG_SPILL]);

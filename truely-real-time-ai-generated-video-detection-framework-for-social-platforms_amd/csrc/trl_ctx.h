@@ -1,6 +1,7 @@
 // trl_ctx.h -- the opaque context behind the C ABI.
 #pragma once
 #include "trl_common.h"
+#include "trl_capacity.h"   // LvLayout, the FLG_* words, CascadeCaps
 
 // One PNet candidate (generateBoundingBox row + its cell index).  40 bytes.
 struct Cand {
@@ -16,39 +17,25 @@ struct LevelGeom {
     int chunk;       // generic path: frames per step, so that one step's workspace stays under 2 GB (size_scratch)
 };
 
-// Candidate lists of one call.  Level l of every frame owns capl[l] record slots (never more than the level has cells); a frame's
-// records are contiguous: record (f, l, slot) = lvl_rec[f * S + rec0[l] + slot], S = sum of capl.  The per-frame box lists of
-// stages 1-3 hold capF rows.  Both capacities follow the content: a call that overflows one is re-run with larger lists
-// (trl_cascade_check), so no input can make the detector fail -- detect_face() has no candidate limit either.
-struct LvLayout {
-    int L = 0, S = 0;
-    int capl[32] = {0}, rec0[32] = {0};
-};
 struct CascadeBufs {   // device pointers into the arena, valid until the next call
     int n = 0, L = 0, H = 0, W = 0;
-    LvLayout lay;                    // record slots per level
-    int capF = 0;                    // rows per frame of s1_box / s2_box / s3_box / s3_pts
+    LvLayout lay;                    // record slots per level (trl_capacity.h).  Both list capacities follow the content: a call that
+    int capF = 0;                    // overflows one is re-run with larger lists.  capF: rows per frame of box[] / pts3
     int32_t* lvl_cnt = nullptr;      // [n][L]
     Cand* lvl_rec = nullptr;         // [n][S]
     int32_t* lvl_keep_cnt = nullptr; // [n][L]
     int32_t* lvl_keep_idx = nullptr; // [n][S]
-    int32_t* n1 = nullptr; float* s1_box = nullptr;   // [n], [n][capF][5]
-    int32_t* n2 = nullptr; float* s2_box = nullptr;   // [n], [n][capF][5]
-    int32_t* n3 = nullptr; float* s3_box = nullptr;   // [n], [n][capF][5]
-    float* s3_pts = nullptr;                           // [n][capF][10]
-    int32_t* off2 = nullptr; int32_t* off3 = nullptr; // [n+1] exclusive scans of n1 / n2
+    // the box lists behind stages 1-3, indexed by stage - 1
+    int32_t* cnt[3] = {nullptr, nullptr, nullptr};   // [n]
+    float* box[3] = {nullptr, nullptr, nullptr};     // [n][capF][5]
+    float* pts3 = nullptr;                           // [n][capF][10]: stage 3's landmarks
+    int32_t* off[2] = {nullptr, nullptr};            // [n+1] exclusive scans of cnt[0] / cnt[1]: the R-Net / O-Net batch
     int32_t* cbox = nullptr;     // [n*capF][8]: candidate t of the current stage = {frame, y0, x0, ih, iw, 0, 0, 0} (pad()'s crop window)
-    int32_t* flags = nullptr;        // [TRL_NFLAGS]: the FLG_* words below
+    int32_t* flags = nullptr;        // [TRL_NFLAGS]: the FLG_* words (trl_capacity.h)
     char* spill = nullptr;           // global-memory workspace of the NMS spill tier (lists longer than the LDS tier)
     size_t spill_cap = 0;
     float* box0 = nullptr; float* prob0 = nullptr; int32_t* rect = nullptr; uint8_t* valid = nullptr; float* pts0 = nullptr;   // k_select's per-frame outputs where the call asks for none
 };
-enum { TRL_NFLAGS = 64 };            // int32 words of CascadeBufs::flags (copied to pinned host memory behind every call)
-// The words: a capacity of the attempt was too small (level record list, per-frame list, R-/O-Net batch, spill pool) and what the
-// attempt measured (the R-/O-Net candidate totals, the largest per-frame and per-level counts, the spill bytes asked for)
-enum { FLG_LEVEL = 0, FLG_FRAME = 1, FLG_T2 = 2, FLG_T3 = 3, FLG_T2N = 4, FLG_T3N = 5, FLG_FRAME_MAX = 6, FLG_SPILL = 7,
-       FLG_SPILL_CUR = 8 /* u64 */, FLG_SPILL_LISTS = 10, FLG_LEVEL_MAX = 16 /* [32] */ };
-
 // One MTCNN network, described once (the table trl_nets[] in trl_nets.hip): the layer walker, the front launcher, the cascade's
 // stage loop and the loader's tensor check all read it.
 struct NetLayer { const char* name; const char* prelu; int k, st, cout; };   // a valid k x k conv `name` (+ bias, + PReLU `prelu` or none) of
@@ -106,19 +93,12 @@ struct trl_ctx {
     bool pnet_prof = false;                   // TRL_PNET_CLOCK: the DBG instantiation with per-phase wave clocks
     float pnet_kernel_ms = 0.f;      // its span in ms (collect_timings)
     int dbg_poison = -1;             // >= 0 after trl_debug_poison: byte written into every newly allocated workspace
-    // Optimistic capacities of the R-Net / O-Net candidate batches (candidates per frame): launches are sized by them and
-    // exit early on the device; a call that overflows one is re-run with a larger value (trl_cascade.hip)
-    float t2_per_frame = 160.f, t3_per_frame = 48.f;
-    int cap_t2 = 0, cap_t3 = 0;      // capacities of the call in progress
-    // Candidate-list capacities follow the content the same way: the largest per-level count / per-frame stage-1 total / spill
-    // workspace recent calls needed (with head-room, decaying towards the configured start values)
-    float lvl_hint[32] = {0}, frame_hint = 0.f;
-    size_t spill_hint = 0;
+    // Optimistic capacities of the candidate lists, the spill pool and the R-Net / O-Net batches: launches and workspaces are sized
+    // by them, and a call that overflows one is re-run with a larger value (trl_capacity.h)
+    CascadeCaps caps;
     int rnet_chunk = 49152, onet_chunk = 16384;   // R-/O-Net candidates per launch set (trl_cascade.hip; trl_debug_option shrinks them for tests)
     int nms_small = 512, nms_full = 2048;   // LDS tiers of the sort + NMS kernels (candidates); longer lists take the spill tier
                                             // (trl_debug_nms_tiers lowers them so that small test inputs reach every tier)
-    int last_attempts = 0;           // attempts the last call took (test hook)
-    int resume_stage = 0;            // 2 / 3: the next attempt of the call in progress starts at that stage (trl_cascade_check)
     size_t scratch_after_cascade = 0;   // scratch bytes the rest of the call needs (crops + FaceNet): sized with the cascade's
     // the call in progress: queued by trl_detect_embed_begin / trl_detect_crop_begin and not yet finished by trl_detect_embed_end,
     // or a blocking trl_detect_embed / trl_detect_crop / trl_mtcnn_detect* between its enqueue and its wait (trl_api.hip)

@@ -401,6 +401,28 @@ int  trl_jpeg_encode(trl_jpeg* enc, const uint8_t* d_bgr, int n, long long frame
 /* Host only, no GPU: the bytes every file of such an encoder starts with (SOI .. SOS).  *len receives the length; a buffer of
  * fewer than *len bytes gives TRL_ERR_CAPACITY and is left untouched. */
 int  trl_jpeg_header(int H, int W, int quality, uint8_t* buf, size_t cap, int* len);
+/* The encoder with Pillow's other baseline options: every file is byte-identical to Image.save(format="JPEG", quality=q,
+ * subsampling=s, restart_marker_rows=r | restart_marker_blocks=b, optimize=o) on the RGB frame.  (ABI v7, additive)
+ *   subsampling     Pillow's numbering: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0.  Anything else: TRL_ERR_INVALID.
+ *   restart_rows    a restart interval of that many MCU rows; restart_blocks: of that many MCUs (libjpeg counts MCUs, Pillow calls
+ *                   them blocks).  As in libjpeg, rows > 0 wins over blocks, and rows x MCUs-per-row above 65535 becomes 65535.  An
+ *                   interval of at least the frame's MCU count writes the DRI segment and no marker.  Negative values, and blocks
+ *                   above 65535 (Pillow writes a DRI that its own scan does not follow), are TRL_ERR_INVALID.
+ *   optimize        non-zero: per-frame optimal Huffman tables (libjpeg's two passes; four DHT segments DC0 AC0 DC1 AC1 per file).
+ *                   Frames of 9,227,465 or more luma coefficients are TRL_ERR_INVALID: libjpeg itself fails where such a frame's
+ *                   optimal code is deeper than 32 bits.
+ * {quality, 2, 0, 0, 0} is trl_jpeg_create's encoder, kernel for kernel.  Bad options allocate nothing. */
+typedef struct trl_jpeg_options {
+    int quality, subsampling, restart_rows, restart_blocks, optimize;
+} trl_jpeg_options;
+int  trl_jpeg_create_ex(int device, int H, int W, const trl_jpeg_options* opt, int max_frames, trl_jpeg** out);
+/* trl_jpeg_header with options (the DRI segment follows the DHTs).  With `optimize` every frame has a header of its own; this is
+ * then the standard-table header, whose length is an upper bound on every frame's header. */
+int  trl_jpeg_header_ex(int H, int W, const trl_jpeg_options* opt, uint8_t* buf, size_t cap, int* len);
+/* Host only: the optimal Huffman table of 256 symbol counts exactly as libjpeg's jpeg_gen_optimal_table builds it (the function
+ * the encoder runs on the device per frame and table).  bits[16]: codes per length; vals[256]: symbols in code order, *nvals of
+ * them; *maxlen (may be null): the longest code length before libjpeg's limiting step to 16. */
+int  trl_jpeg_optimal_table(const uint32_t* hist, uint8_t* bits, uint8_t* vals, int* nvals, int* maxlen);
 
 /* ---- Motion-JPEG input (run() on Motion-JPEG AVI) -----------------------------------------------------------------------------
  * A baseline JPEG decoder whose BGR frames are byte-identical to np.asarray(Image.open(f).convert("RGB"))[:, :, ::-1]

@@ -20,6 +20,10 @@ class TrlJpegdInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("width", "height", "h_samp", "v_samp", "restart_interval", "scan_offset", "supported", "reason")]
 
 
+class TrlJpegOptions(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("quality", "subsampling", "restart_rows", "restart_blocks", "optimize")]
+
+
 class TrlError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"libtruely_hip status {status}: {msg}")
@@ -92,6 +96,9 @@ _SIGNATURES = {
     "trl_jpeg_destroy": (C.c_int, [_vp]),
     "trl_jpeg_encode": (C.c_int, [_vp, _vp, _i, C.c_longlong, _vp, C.c_longlong, _vp, _vp]),
     "trl_jpeg_header": (C.c_int, [_i, _i, _i, _vp, C.c_size_t, C.POINTER(_i)]),
+    "trl_jpeg_create_ex": (C.c_int, [_i, _i, _i, C.POINTER(TrlJpegOptions), _i, C.POINTER(_vp)]),
+    "trl_jpeg_header_ex": (C.c_int, [_i, _i, C.POINTER(TrlJpegOptions), _vp, C.c_size_t, C.POINTER(_i)]),
+    "trl_jpeg_optimal_table": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
     "trl_jpegd_parse": (C.c_int, [_vp, C.c_size_t, _vp]),
     "trl_jpegd_create": (C.c_int, [_i, _i, _i, _i, C.c_longlong, C.POINTER(_vp)]),
     "trl_jpegd_destroy": (C.c_int, [_vp]),

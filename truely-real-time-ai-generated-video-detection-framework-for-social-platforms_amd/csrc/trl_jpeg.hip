@@ -1,17 +1,29 @@
 // trl_jpeg.hip -- baseline Motion-JPEG encoder for run()'s annotated output, byte-identical to Pillow's
-// Image.save(format="JPEG", quality=q, subsampling=2) (libjpeg-turbo's baseline path: 4:2:0, standard tables, no restart markers,
-// no optimisation).  Integer arithmetic only, so the bytes do not depend on the launch shape.  The rules (DESIGN.md "Motion-JPEG
-// on the device"; restated in numpy and pinned to Pillow by tests/test_jpeg_cpu.py):
+// Image.save(format="JPEG", quality=q, subsampling=s, restart_marker_rows=r | restart_marker_blocks=b, optimize=o) (libjpeg-turbo's
+// baseline path).  trl_jpeg_create writes the default kind of file: 4:2:0, standard tables, no restart markers; trl_jpeg_create_ex
+// takes the options.  Integer arithmetic only, so the bytes do not depend on the launch shape.  The rules (DESIGN.md "Motion-JPEG
+// on the device"; restated in numpy and pinned to Pillow by tests/test_jpeg_cpu.py and tests/jpeg_options_ref.py):
 //   colour      jccolor's 16-bit fixed point, BGR input
-//   edges       Y: last column / row replicated to whole blocks; chroma: full-resolution columns replicated to whole chroma
-//               blocks x 2, rows to an even count, h2v2 average with bias 1,2,1,2..., last chroma row replicated to whole blocks
+//   edges       every component: source columns and rows replicated (the last pixel repeats), which is what libjpeg's padding of
+//               each component to whole blocks amounts to, with these downsampling rules
+//               4:2:0 (MCU 16 x 16: Y00 Y01 Y10 Y11 Cb Cr)  chroma: full-resolution columns replicated to whole chroma blocks x 2,
+//                     rows to an even count, h2v2 average with bias 1,2,1,2..., last chroma row replicated to whole blocks
+//               4:2:2 (MCU 16 x 8: Y0 Y1 Cb Cr)             chroma: columns as for 4:2:0, h2v1 average with bias 0,1,0,1...
+//               4:4:4 (MCU 8 x 8: Y Cb Cr)                  no downsampling
 //   FDCT        jfdctint islow (CONST_BITS 13, PASS1_BITS 2) on sample - 128; quantisation (|c| + 4q) / 8q, sign restored
-//   dummies     Y blocks past the image in the last MCU column / row: zero AC, DC of the left neighbour (right edge) or of the
-//               MCU's Y01 (bottom edge)
-//   entropy     Annex K tables, DC predictor per component, ZRL / EOB, last byte padded with 1-bits, 0xFF stuffed as FF 00
+//   dummies     Y blocks past the image in the last MCU column / row: zero AC and
+//               4:2:0  the DC of the left neighbour (right edge) or of the MCU's Y01 (bottom edge)
+//               4:2:2  the DC of Y0 (right edge); an MCU is one block high, so there is no bottom dummy
+//               4:4:4  none: an MCU is one block
+//   entropy     DC predictor per component, ZRL / EOB, last byte padded with 1-bits, 0xFF stuffed as FF 00; Annex K tables
+//   restart     an interval of R MCUs (restart_rows x MCUs per row, at most 65535, else restart_blocks): DRI after the DHTs; at
+//               each interval start all three DC predictors are 0; each interval is padded with 1-bits to a byte (stuffed like
+//               any other byte when it comes out as 0xFF), FF D0 .. FF D7 follow, cycling, never stuffed; none after the last
+//   optimize    libjpeg's two passes: the symbols the scan will emit are counted per table (luma; Cb and Cr together), each of
+//               the four tables is jpeg_gen_optimal_table's (trl_jpeg_hufftab.h), and the frame's header carries its own DHTs
 // Pipeline per chunk of frames (all on the caller's stream; one host synchronisation per batch, to read the sizes):
 //   k_jpeg_blocks   a workgroup = 4 MCUs of one MCU row: BGR -> YCbCr + downsampling into LDS, FDCT, quantisation, zigzag,
-//                   dummy blocks -> int16 coefficients [frame][mcu][6][64]
+//                   dummy blocks -> int16 coefficients [frame][mcu][6][64]  (k_jpeg_blocks_ex<S>: the 4:4:4 and 4:2:2 MCUs)
 //   k_jpeg_bits     one wave per block, lane k = zigzag coefficient k: ballot -> run lengths -> the block's bit count
 //   k_jpeg_scan     one workgroup per frame: exclusive scan of the block bit counts
 //   k_jpeg_emit     one wave per block: each lane ORs its codes into the wave's LDS words at (block offset + lane prefix); the
@@ -20,7 +32,15 @@
 //   k_jpeg_ffcount  FF bytes per 4 KiB segment of each frame's scan
 //   k_jpeg_sizes    one workgroup per chunk: scan of the segment counts, frame sizes and output offsets
 //   k_jpeg_scatter  header + stuffed scan + EOI into the caller's buffer; a frame that would end past the capacity is not written
+// With options (anything but the defaults) the same stages run as k_jpeg_bits_ex / k_jpeg_scan_ex / k_jpeg_emit_ex and the <true>
+// instantiations of edges / ffcount / scatter: blocks per MCU and the interval are parameters, block bit offsets restart per
+// interval and the intervals' byte lengths (+ 2 marker bytes) are scanned again, the marker is part of the last block's bits so
+// that every word still has one writer, and the stuffing passes skip the marker bytes by the interval starts.  optimize adds
+// k_jpeg_hist (per-workgroup LDS histograms, added to the frame's by device-scope integer atomics that only later kernels read)
+// and k_jpeg_tables (one wave per frame and table, then the frame's header) in front of k_jpeg_bits_ex.  No further host
+// synchronisation: tables never visit the host.
 #include "trl_common.h"
+#include "trl_jpeg_hufftab.h"
 
 #include <stdio.h>
 #include <string.h>
@@ -91,7 +111,9 @@ void huff_codes(const uint8_t* bits, const uint8_t* vals, uint32_t* out) {
     }
 }
 
-size_t header_bytes(int H, int W, int quality, uint8_t* o) {   // o == nullptr: length only
+// sampling 0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0 (Pillow's numbering); dri > 0 adds a DRI segment where libjpeg puts it (after the
+// DHTs); dht_at / tail_at receive the offsets of the first DHT and of what follows the last (k_jpeg_tables splices there)
+size_t header_bytes(int H, int W, int quality, int sampling, int dri, uint8_t* o, int* dht_at = nullptr, int* tail_at = nullptr) {   // o == nullptr: length only
     size_t p = 0;
     auto put = [&](int v) { if (o) o[p] = (uint8_t)v; ++p; };
     auto seg = [&](int marker, int len) { put(0xFF); put(marker); put(len >> 8); put(len & 0xFF); };
@@ -106,7 +128,8 @@ size_t header_bytes(int H, int W, int quality, uint8_t* o) {   // o == nullptr: 
         for (int i = 0; i < 64; ++i) put(q[kZigzag[i]]);
     }
     seg(0xC0, 17);
-    for (int v : {8, H >> 8, H & 0xFF, W >> 8, W & 0xFF, 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1}) put(v);
+    for (int v : {8, H >> 8, H & 0xFF, W >> 8, W & 0xFF, 3, 1, sampling == 0 ? 0x11 : sampling == 1 ? 0x21 : 0x22, 0, 2, 0x11, 1, 3, 0x11, 1}) put(v);
+    if (dht_at) *dht_at = (int)p;
     for (int t = 0; t < 2; ++t) {
         seg(0xC4, 2 + 1 + 16 + 12);
         put(t);
@@ -119,6 +142,8 @@ size_t header_bytes(int H, int W, int quality, uint8_t* o) {   // o == nullptr: 
         for (int i = 0; i < 16; ++i) put(kAcBits[t][i]);
         for (int i = 0; i < nv; ++i) put(kAcVals[t][i]);
     }
+    if (tail_at) *tail_at = (int)p;
+    if (dri > 0) { seg(0xDD, 4); put(dri >> 8); put(dri & 0xFF); }
     seg(0xDA, 12);
     for (int v : {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0}) put(v);
     return p;
@@ -127,6 +152,32 @@ size_t header_bytes(int H, int W, int quality, uint8_t* o) {   // o == nullptr: 
 int check_shape(int H, int W) {
     if (H < 1 || W < 1 || H > 65535 || W > 65535) {
         trl_set_error("trl_jpeg: frame %d x %d outside 1..65535 px per side", W, H);
+        return TRL_ERR_INVALID;
+    }
+    return TRL_OK;
+}
+
+struct JOpt {               // trl_jpeg_options, checked and resolved for a frame size
+    int quality, sampling, bpm, mcuw, mcuh, mcux, mcuy, dri, optimize;
+    bool ex() const { return sampling != 2 || dri > 0 || optimize; }   // anything but the kind of file trl_jpeg_create writes
+};
+
+int resolve_options(const char* who, int H, int W, const trl_jpeg_options* o, JOpt* r) {
+    TRL_CHECK(check_shape(H, W));
+    if (!o) { trl_set_error("%s: null options", who); return TRL_ERR_INVALID; }
+    if (o->subsampling < 0 || o->subsampling > 2) { trl_set_error("%s: subsampling %d outside 0..2 (4:4:4, 4:2:2, 4:2:0)", who, o->subsampling); return TRL_ERR_INVALID; }
+    if (o->restart_rows < 0 || o->restart_blocks < 0 || o->restart_blocks > 65535) {
+        trl_set_error("%s: restart_rows %d / restart_blocks %d: rows >= 0, blocks 0..65535", who, o->restart_rows, o->restart_blocks);
+        return TRL_ERR_INVALID;
+    }
+    r->quality = o->quality; r->sampling = o->subsampling; r->optimize = o->optimize != 0;
+    r->bpm = o->subsampling == 0 ? 3 : o->subsampling == 1 ? 4 : 6;
+    r->mcuw = o->subsampling == 0 ? 8 : 16; r->mcuh = o->subsampling == 2 ? 16 : 8;
+    r->mcux = (W + r->mcuw - 1) / r->mcuw; r->mcuy = (H + r->mcuh - 1) / r->mcuh;
+    r->dri = o->restart_rows > 0 ? (int)std::min<long long>((long long)o->restart_rows * r->mcux, 65535) : o->restart_blocks;
+    // libjpeg fails on a histogram whose optimal code is deeper than 32 bits; fewer than 9,227,465 symbols cannot make one
+    if (r->optimize && (long long)r->mcux * r->mcuy * (r->bpm - 2) * 64 >= 9227465) {
+        trl_set_error("%s: optimize needs fewer than 9227465 luma coefficients per frame (%d x %d has more)", who, W, H);
         return TRL_ERR_INVALID;
     }
     return TRL_OK;
@@ -228,9 +279,8 @@ struct LaneCodes {
     __device__ int bits() const { return plen + nzrl * (int)(zrl & 0xFF); }
 };
 
-__device__ __forceinline__ LaneCodes lane_codes(const JTab* __restrict__ tab, const int16_t* __restrict__ blkc, int lane, int kind,
+__device__ __forceinline__ LaneCodes lane_codes(const JTab* __restrict__ tab, const int16_t* __restrict__ blkc, int lane, int t,
                                                 int pred) {
-    const int t = kind < 4 ? 0 : 1;
     const int v = blkc[lane];
     const unsigned long long mask = __ballot(v != 0);
     LaneCodes o{0u, 0, 0, tab->ac[t][0xF0]};
@@ -278,7 +328,7 @@ __global__ __launch_bounds__(256) void k_jpeg_bits(const int16_t* __restrict__ c
     const int j = (int)(g - f * blocks);
     const int16_t* fcoef = coef + (size_t)f * blocks * 64;
     const int pred = lane == 0 ? dc_pred(fcoef, j) : 0;
-    const LaneCodes lc = lane_codes(tab, fcoef + (size_t)j * 64, lane, j % 6, pred);
+    const LaneCodes lc = lane_codes(tab, fcoef + (size_t)j * 64, lane, j % 6 < 4 ? 0 : 1, pred);
     const int s = wave_sum(lc.bits());
     if (lane == 0) bits[g] = (uint32_t)s;
 }
@@ -342,7 +392,7 @@ __global__ __launch_bounds__(256) void k_jpeg_emit(const int16_t* __restrict__ c
         const int j = (int)(g - f * blocks);
         const int16_t* fcoef = coef + (size_t)f * blocks * 64;
         const int pred = lane == 0 ? dc_pred(fcoef, j) : 0;
-        const LaneCodes lc = lane_codes(tab, fcoef + (size_t)j * 64, lane, j % 6, pred);
+        const LaneCodes lc = lane_codes(tab, fcoef + (size_t)j * 64, lane, j % 6 < 4 ? 0 : 1, pred);
         int pre = lc.bits();                                 // inclusive -> exclusive wave prefix
         for (int o = 1; o < 64; o <<= 1) {
             const int y = __shfl_up(pre, o, 64);
@@ -380,6 +430,8 @@ __device__ __forceinline__ void word_range(const unsigned long long* off, const 
 
 // grid ceil(frames * blocks / 256), 256 threads: the words blocks share.  Block g writes its first word unless the previous block
 // ends in it, and its last word: each is the OR of its own part and the first words of the following blocks that start there.
+// EX: bits[] already holds the padding (k_jpeg_scan_ex).
+template <bool EX>
 __global__ __launch_bounds__(256) void k_jpeg_edges(int blocks, long long total, const unsigned long long* __restrict__ off,
                                                     const uint32_t* __restrict__ bits, const uint32_t* __restrict__ first,
                                                     const uint32_t* __restrict__ last, size_t scratch_per_frame,
@@ -390,11 +442,11 @@ __global__ __launch_bounds__(256) void k_jpeg_edges(int blocks, long long total,
     const int j = (int)(g - f * blocks);
     uint32_t* fs = scratch + (size_t)f * (scratch_per_frame >> 2);
     unsigned long long wf, wl, pf, pl;
-    word_range(off, bits, g, j == blocks - 1, wf, wl);
+    word_range(off, bits, g, !EX && j == blocks - 1, wf, wl);
     auto merged = [&](unsigned long long w, uint32_t v) {   // OR in the first words of the blocks after g that start in word w
         for (int h = j + 1; h < blocks; ++h) {
             unsigned long long hf, hl;
-            word_range(off, bits, g + (h - j), h == blocks - 1, hf, hl);
+            word_range(off, bits, g + (h - j), !EX && h == blocks - 1, hf, hl);
             if (hf != w) break;
             v |= first[g + (h - j)];
         }
@@ -409,10 +461,21 @@ __global__ __launch_bounds__(256) void k_jpeg_edges(int blocks, long long total,
     if (wl > wf) fs[wl] = merged(wl, last[g]);
 }
 
-// grid (segments per frame, frames of the chunk), 256 threads: FF bytes per 4 KiB segment of the scan
+// whether the 0xFF at byte p of a frame's stream is the first byte of a restart marker (interval k's marker ends at ist[k + 1])
+__device__ __forceinline__ bool marker_at(const unsigned long long* __restrict__ is, int nint, unsigned long long p) {
+    int lo = 1, hi = nint;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (is[mid] < p + 2) lo = mid + 1; else hi = mid;
+    }
+    return lo < nint && is[lo] == p + 2;
+}
+
+// grid (segments per frame, frames of the chunk), 256 threads: FF bytes to stuff per 4 KiB segment of the scan (EX: not the markers')
+template <bool EX>
 __global__ __launch_bounds__(256) void k_jpeg_ffcount(const uint8_t* __restrict__ scratch, size_t scratch_per_frame,
                                                       const unsigned long long* __restrict__ fbits, int segs_per_frame,
-                                                      uint32_t* __restrict__ segcnt) {
+                                                      uint32_t* __restrict__ segcnt, const unsigned long long* __restrict__ ist, int nint) {
     __shared__ int sh[4];
     const int f = blockIdx.y, seg = blockIdx.x, tid = threadIdx.x;
     const unsigned long long nbytes = (fbits[f] + 7) >> 3;
@@ -425,8 +488,10 @@ __global__ __launch_bounds__(256) void k_jpeg_ffcount(const uint8_t* __restrict_
     if (i0 < nbytes) {
         const uint4 q = *reinterpret_cast<const uint4*>(scratch + (size_t)f * scratch_per_frame + i0);
         const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-        for (int k = 0; k < 16; ++k)
-            cnt += (i0 + k < nbytes) && ((w[k >> 2] >> (8 * (k & 3))) & 0xFF) == 0xFF;
+        for (int k = 0; k < 16; ++k) {
+            const bool ff = (i0 + k < nbytes) && ((w[k >> 2] >> (8 * (k & 3))) & 0xFF) == 0xFF;
+            cnt += ff && !(EX && nint > 1 && marker_at(ist + (size_t)f * nint, nint, i0 + k));
+        }
     }
     cnt = wave_sum(cnt);
     if ((tid & 63) == 0) sh[tid >> 6] = cnt;
@@ -437,7 +502,8 @@ __global__ __launch_bounds__(256) void k_jpeg_ffcount(const uint8_t* __restrict_
 // one 1024-thread workgroup per chunk: segment counts -> offsets, frame sizes, output offsets (frame f0 + k starts at foff[f0 + k])
 __global__ __launch_bounds__(1024) void k_jpeg_sizes(uint32_t* __restrict__ segcnt, int segs_per_frame,
                                                      const unsigned long long* __restrict__ fbits, int frames, int f0, int hdr_len,
-                                                     long long* __restrict__ fsize, long long* __restrict__ foff) {
+                                                     const int* __restrict__ hlen, long long* __restrict__ fsize,
+                                                     long long* __restrict__ foff) {   // hlen: a header length per frame (optimize)
     __shared__ unsigned long long sh[1024];
     for (int f = 0; f < frames; ++f) {
         const unsigned long long nbytes = (fbits[f] + 7) >> 3;
@@ -446,7 +512,7 @@ __global__ __launch_bounds__(1024) void k_jpeg_sizes(uint32_t* __restrict__ segc
         const unsigned long long ff = block_exclusive_scan<unsigned long long>(
             [&](long long i) { return (unsigned long long)c[i]; }, [&](long long i, unsigned long long v) { c[i] = (uint32_t)v; }, nseg, sh);
         if (threadIdx.x == 0) {
-            const long long size = (long long)(hdr_len + nbytes + ff + 2);
+            const long long size = (long long)((hlen ? hlen[f] : hdr_len) + nbytes + ff + 2);
             fsize[f0 + f] = size;
             foff[f0 + f + 1] = foff[f0 + f] + size;
         }
@@ -455,13 +521,18 @@ __global__ __launch_bounds__(1024) void k_jpeg_sizes(uint32_t* __restrict__ segc
 }
 
 // grid (segments per frame, frames of the chunk), 256 threads: header, stuffed scan bytes and EOI of each frame that fits
+// EX: restart markers are copied unstuffed; hlen != nullptr: frame f's header is hlen[f] bytes at hdr + f * hdr_stride (optimize)
+template <bool EX>
 __global__ __launch_bounds__(256) void k_jpeg_scatter(const uint8_t* __restrict__ scratch, size_t scratch_per_frame,
                                                       const unsigned long long* __restrict__ fbits, const uint32_t* __restrict__ segoff,
                                                       int segs_per_frame, const uint8_t* __restrict__ hdr, int hdr_len, int f0,
                                                       const long long* __restrict__ fsize, const long long* __restrict__ foff,
-                                                      uint8_t* __restrict__ out, long long capacity) {
+                                                      uint8_t* __restrict__ out, long long capacity,
+                                                      const unsigned long long* __restrict__ ist, int nint, int hdr_stride,
+                                                      const int* __restrict__ hlen) {
     __shared__ int sh[256];
     const int f = blockIdx.y, seg = blockIdx.x, tid = threadIdx.x;
+    if (EX && hlen) { hdr += (size_t)f * hdr_stride; hdr_len = hlen[f]; }
     const unsigned long long nbytes = (fbits[f] + 7) >> 3;
     const long long o = foff[f0 + f], size = fsize[f0 + f];
     if (o + size > capacity) return;                         // the caller grows its buffer and re-runs
@@ -477,7 +548,10 @@ __global__ __launch_bounds__(256) void k_jpeg_scatter(const uint8_t* __restrict_
     if (i0 < nbytes) {
         const uint4 q = *reinterpret_cast<const uint4*>(scratch + (size_t)f * scratch_per_frame + i0);
         w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-        for (int k = 0; k < 16; ++k) cnt += (i0 + k < nbytes) && ((w[k >> 2] >> (8 * (k & 3))) & 0xFF) == 0xFF;
+        for (int k = 0; k < 16; ++k) {
+            const bool ff = (i0 + k < nbytes) && ((w[k >> 2] >> (8 * (k & 3))) & 0xFF) == 0xFF;
+            cnt += ff && !(EX && nint > 1 && marker_at(ist + (size_t)f * nint, nint, i0 + k));
+        }
     }
     sh[tid] = cnt;
     __syncthreads();
@@ -492,8 +566,258 @@ __global__ __launch_bounds__(256) void k_jpeg_scatter(const uint8_t* __restrict_
     for (int k = 0; k < 16 && i0 + k < nbytes; ++k) {
         const uint8_t b = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
         dst[q++] = b;
-        if (b == 0xFF) dst[q++] = 0;
+        if (b == 0xFF && !(EX && nint > 1 && marker_at(ist + (size_t)f * nint, nint, i0 + k))) dst[q++] = 0;
     }
+}
+
+// ---- the optioned path (trl_jpeg_create_ex with anything but the defaults) --------------------------------------------------------
+// Blocks per MCU (bpm) 3 / 4 / 6, a restart interval of R MCUs (no DRI: R = the frame's MCU count, one interval), and with
+// `optimize` a code table and a header per frame.  The default path above is untouched by it.
+
+// grid (ceil(mcux / MPW), mcuy, frames of the chunk), 256 threads: a 8 x 64 pixel strip of 8 x 8 MCUs (S = 0: Y Cb Cr) or of 16 x 8
+// MCUs (S = 1: Y0 Y1 Cb Cr, h2v1 average with bias 0,1,0,1...).  No vertical subsampling, so rows are only replicated.
+template <int S>
+__global__ __launch_bounds__(256) void k_jpeg_blocks_ex(const uint8_t* __restrict__ src, long long frame_stride, int H, int W,
+                                                        int mcux, int mcuy, const JTab* __restrict__ tab, int16_t* __restrict__ coef) {
+    constexpr int MW = S == 0 ? 8 : 16, BPM = S == 0 ? 3 : 4, MPW = 64 / MW, NB = MPW * BPM, NY = BPM - 2;
+    __shared__ int pix[3][8][64];
+    __shared__ int blk[NB][64];
+    __shared__ int16_t qz[NB][64];
+    const int tid = threadIdx.x, mx0 = blockIdx.x * MPW, my = blockIdx.y, f = blockIdx.z;
+    const uint8_t* fr = src + (size_t)f * frame_stride;
+    for (int i = tid; i < 8 * 64; i += 256) {
+        const int r = i >> 6, c = i & 63;
+        const int gy = min(8 * my + r, H - 1), gx = min(64 * (int)blockIdx.x + c, W - 1);
+        const uint8_t* p = fr + ((size_t)gy * W + gx) * 3;
+        const int B = p[0], G = p[1], R = p[2];
+        pix[0][r][c] = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
+        pix[1][r][c] = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
+        pix[2][r][c] = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
+    }
+    __syncthreads();
+    for (int i = tid; i < NB * 64; i += 256) {
+        const int b = i >> 6, r = (i >> 3) & 7, c = i & 7, m = b / BPM, kind = b % BPM;
+        int v;
+        if (S == 0) {
+            v = pix[kind][r][m * 8 + c];
+        } else if (kind < NY) {
+            v = pix[0][r][m * 16 + kind * 8 + c];
+        } else {
+            const int cc = 2 * (m * 8 + c);
+            v = (pix[kind - 1][r][cc] + pix[kind - 1][r][cc + 1] + (c & 1)) >> 1;
+        }
+        blk[b][(r << 3) | c] = v - 128;
+    }
+    __syncthreads();
+    if (tid < NB * 8) fdct8<true>(&blk[tid >> 3][(tid & 7) * 8], 1);
+    __syncthreads();
+    if (tid < NB * 8) fdct8<false>(&blk[tid >> 3][tid & 7], 8);
+    __syncthreads();
+    for (int i = tid; i < NB * 64; i += 256) {
+        const int b = i >> 6, z = i & 63;
+        const int c = blk[b][c_zigzag[z]], d = tab->qdiv[(b % BPM) < NY ? 0 : 1][c_zigzag[z]];
+        const int a = ((c < 0 ? -c : c) + (d >> 1)) / d;
+        qz[b][z] = (int16_t)(c < 0 ? -a : a);
+    }
+    __syncthreads();
+    const int bw = (W + 7) >> 3;
+    for (int i = tid; i < NB * 64; i += 256) {
+        const int b = i >> 6, z = i & 63, m = b / BPM, kind = b % BPM, mx = mx0 + m;
+        if (mx >= mcux) continue;
+        int v = qz[b][z];
+        if (S == 1 && kind == 1 && 2 * mx + 1 >= bw) v = z ? 0 : qz[b - 1][0];   // right dummy: zero AC, DC of Y0
+        coef[((((size_t)f * mcuy + my) * mcux + mx) * BPM + kind) * 64 + z] = (int16_t)v;
+    }
+}
+
+// the DC predictor of block j of a frame: the component's previous block, 0 at the start of each restart interval
+__device__ __forceinline__ int dc_pred_ex(const int16_t* __restrict__ fcoef, int j, int bpm, int R) {
+    const int mcu = j / bpm, kind = j % bpm, ny = bpm - 2;
+    if (kind >= 1 && kind < ny) return fcoef[(size_t)(j - 1) * 64];
+    if (mcu % R == 0) return 0;
+    return fcoef[(size_t)(j - bpm + (kind == 0 ? ny - 1 : 0)) * 64];
+}
+
+// grid ceil(frames * blocks / 4), 256 threads: one wave per block; tab_stride != 0: a table per frame (optimize)
+__global__ __launch_bounds__(256) void k_jpeg_bits_ex(const int16_t* __restrict__ coef, int blocks, long long total, int bpm, int R,
+                                                      const JTab* __restrict__ tab, int tab_stride, uint32_t* __restrict__ bits) {
+    const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (g >= total) return;                                  // wave-uniform
+    const long long f = g / blocks;
+    const int j = (int)(g - f * blocks);
+    const int16_t* fcoef = coef + (size_t)f * blocks * 64;
+    const int pred = lane == 0 ? dc_pred_ex(fcoef, j, bpm, R) : 0;
+    const LaneCodes lc = lane_codes(tab + (size_t)f * tab_stride, fcoef + (size_t)j * 64, lane, j % bpm < bpm - 2 ? 0 : 1, pred);
+    const int s = wave_sum(lc.bits());
+    if (lane == 0) bits[g] = (uint32_t)s;
+}
+
+// grid = frames of the chunk, 1024 threads.  The frame's scan with restart intervals is the intervals' bits back to back, each
+// padded to a byte and (but for the last) followed by the two marker bytes, which are part of the stream k_jpeg_emit_ex writes:
+//   off[j]   block j's bit offset in that stream (its offset within the interval + the interval's byte start)
+//   bits[j]  the interval's last block: its bits + the padding + 16 marker bits, so that every word has one owner as before
+//   ist[i]   interval i's byte start (k_jpeg_ffcount / k_jpeg_scatter find the marker bytes, which are not stuffed, by it)
+//   fbits    the stream's length in bits (whole bytes)
+__global__ __launch_bounds__(1024) void k_jpeg_scan_ex(uint32_t* __restrict__ bits, int blocks, int bpm, int R, int nint,
+                                                       unsigned long long* __restrict__ off, unsigned long long* __restrict__ ist,
+                                                       unsigned long long* __restrict__ ibase, unsigned long long* __restrict__ fbits) {
+    __shared__ unsigned long long sh[1024];
+    const size_t f = blockIdx.x;
+    uint32_t* b = bits + f * blocks;
+    unsigned long long* o = off + f * blocks;
+    unsigned long long* is = ist + f * nint;
+    unsigned long long* ib = ibase + f * nint;
+    const int per = R * bpm;                                 // blocks per interval
+    const unsigned long long t = block_exclusive_scan<unsigned long long>(
+        [&](long long i) { return (unsigned long long)b[i]; }, [&](long long i, unsigned long long v) { o[i] = v; }, blocks, sh);
+    __syncthreads();
+    for (int i = threadIdx.x; i < nint; i += 1024) {
+        const long long sb = (long long)i * per, eb = sb + per;
+        const unsigned long long len = (eb < blocks ? o[eb] : t) - o[sb];
+        ib[i] = o[sb];
+        is[i] = ((len + 7) >> 3) + (i < nint - 1 ? 2 : 0);
+    }
+    __syncthreads();
+    const unsigned long long nbytes = block_exclusive_scan<unsigned long long>(
+        [&](long long i) { return is[i]; }, [&](long long i, unsigned long long v) { is[i] = v; }, nint, sh);
+    __syncthreads();
+    for (int j = threadIdx.x; j < blocks; j += 1024) {
+        const int i = j / per;
+        const unsigned long long p = is[i] * 8 + (o[j] - ib[i]);
+        o[j] = p;
+        if (j == blocks - 1 || (j + 1) % per == 0) {
+            const unsigned long long end = p + b[j];
+            b[j] += (uint32_t)((0 - end) & 7) + (i < nint - 1 ? 16u : 0u);
+        }
+    }
+    if (threadIdx.x == 0) fbits[f] = nbytes * 8;
+}
+
+// as k_jpeg_emit; the last block of each interval adds the 1-bit padding and, but for the last interval, the RSTn marker
+__global__ __launch_bounds__(256) void k_jpeg_emit_ex(const int16_t* __restrict__ coef, int blocks, long long total, int bpm, int R,
+                                                      int nint, const JTab* __restrict__ tab, int tab_stride,
+                                                      const unsigned long long* __restrict__ off, const uint32_t* __restrict__ bits,
+                                                      size_t scratch_per_frame, uint32_t* __restrict__ scratch,
+                                                      uint32_t* __restrict__ first, uint32_t* __restrict__ last) {
+    __shared__ uint32_t buf[4][64];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long g = (long long)blockIdx.x * 4 + wv;
+    buf[wv][lane] = 0;
+    __syncthreads();
+    if (g < total) {                                         // wave-uniform
+        const long long f = g / blocks;
+        const int j = (int)(g - f * blocks);
+        const int16_t* fcoef = coef + (size_t)f * blocks * 64;
+        const int pred = lane == 0 ? dc_pred_ex(fcoef, j, bpm, R) : 0;
+        const LaneCodes lc = lane_codes(tab + (size_t)f * tab_stride, fcoef + (size_t)j * 64, lane, j % bpm < bpm - 2 ? 0 : 1, pred);
+        int pre = lc.bits();                                 // inclusive -> exclusive wave prefix
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(pre, o, 64);
+            if (lane >= o) pre += y;
+        }
+        const int raw = __shfl(pre, 63, 64);                 // the block's own bits
+        pre -= lc.bits();
+        const unsigned long long b0 = off[g];
+        const int s0 = (int)(b0 & 31);
+        int p = s0 + pre;
+        for (int z = 0; z < lc.nzrl; ++z, p += (int)(lc.zrl & 0xFF)) put_bits(buf[wv], p, lc.zrl >> 8, (int)(lc.zrl & 0xFF));
+        put_bits(buf[wv], p, lc.piece, lc.plen);
+        const int per = R * bpm, iv = j / per;
+        if (lane == 0 && (j == blocks - 1 || (j + 1) % per == 0)) {
+            int end = s0 + raw;
+            if (end & 7) { put_bits(buf[wv], end, 0xFFu >> (end & 7), 8 - (end & 7)); end = (end + 7) & ~7; }
+            if (iv < nint - 1) put_bits(buf[wv], end, 0xFFD0u | (uint32_t)(iv & 7), 16);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        const int nwords = (s0 + (int)bits[g] + 31) >> 5;    // bits[]: padding and marker included (k_jpeg_scan_ex)
+        if (lane < nwords) {
+            const uint32_t v = __builtin_bswap32(buf[wv][lane]);
+            if (lane == 0) first[g] = v;
+            else if (lane == nwords - 1) last[g] = v;
+            else scratch[(size_t)f * (scratch_per_frame >> 2) + (b0 >> 5) + lane] = v;
+        }
+    }
+}
+
+// optimize, pass 1.  grid (ceil(blocks / 64), frames of the chunk), 256 threads: a wave per block, 16 blocks per wave; the symbols
+// the entropy coder will emit, counted in LDS and added to the frame's four histograms [DC luma, AC luma, DC chroma, AC chroma]
+// (exact integer counts: the order of the additions is free).  hist is zeroed before the launch.
+__global__ __launch_bounds__(256) void k_jpeg_hist(const int16_t* __restrict__ coef, int blocks, int bpm, int R, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[4 * 256];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, f = blockIdx.y;
+    for (int i = tid; i < 1024; i += 256) h[i] = 0;
+    __syncthreads();
+    const int16_t* fcoef = coef + (size_t)f * blocks * 64;
+    for (int it = 0; it < 16; ++it) {
+        const int j = blockIdx.x * 64 + it * 4 + wv;
+        if (j >= blocks) break;                              // wave-uniform
+        const int t = j % bpm < bpm - 2 ? 0 : 1;
+        const int v = fcoef[(size_t)j * 64 + lane];
+        const unsigned long long mask = __ballot(v != 0);
+        if (lane == 0) {
+            const int diff = v - dc_pred_ex(fcoef, j, bpm, R);
+            atomicAdd(&h[(2 * t) * 256 + nbits_of(diff < 0 ? -diff : diff)], 1u);
+        } else if (v != 0) {
+            const unsigned long long below = mask & ((1ull << lane) - 1ull) & ~1ull;
+            const int prev = below ? 63 - __clzll(below) : 0;
+            const int run = lane - prev - 1;
+            if (run >> 4) atomicAdd(&h[(2 * t + 1) * 256 + 0xF0], (uint32_t)(run >> 4));
+            atomicAdd(&h[(2 * t + 1) * 256 + (((run & 15) << 4) | nbits_of(v < 0 ? -v : v))], 1u);
+        } else if (lane == 63) {
+            atomicAdd(&h[(2 * t + 1) * 256], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < 1024; i += 256)
+        if (h[i]) atomicAdd(&hist[(size_t)f * 1024 + i], h[i]);
+}
+
+// optimize, between the passes.  grid = frames of the chunk, 256 threads: wave t builds table t of the frame on its lane 0
+// (trl_jpeg_hufftab: a sequential procedure), then the workgroup writes the frame's code table and its header: the common header
+// up to the first DHT, the four DHTs in the order DC luma, AC luma, DC chroma, AC chroma, and the common header's DRI / SOS tail.
+__global__ __launch_bounds__(256) void k_jpeg_tables(const uint32_t* __restrict__ hist, const JTab* __restrict__ tab,
+                                                     const uint8_t* __restrict__ hdr, int hdr_len, int dht_at, int tail_at,
+                                                     JTab* __restrict__ ftab, uint8_t* __restrict__ fhdr, int fhdr_stride,
+                                                     int* __restrict__ hlen) {
+    __shared__ trl_hufftab_work work[4];
+    __shared__ uint8_t hb[4][16], hv[4][256];
+    __shared__ int nv[4];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, f = blockIdx.x;
+    JTab* ft = ftab + f;
+    if (lane == 0) {
+        nv[wv] = trl_jpeg_hufftab(hist + (size_t)f * 1024 + wv * 256, hb[wv], hv[wv], &work[wv], nullptr);
+        uint32_t* codes = (wv & 1) ? ft->ac[wv >> 1] : ft->dc[wv >> 1];
+        int code = 0, k = 0;
+        for (int len = 1; len <= 16; ++len) {
+            for (int i = 0; i < hb[wv][len - 1]; ++i) codes[hv[wv][k++]] = ((uint32_t)code++ << 8) | (uint32_t)len;
+            code <<= 1;
+        }
+    }
+    for (int i = tid; i < 128; i += 256) ft->qdiv[i >> 6][i & 63] = tab->qdiv[i >> 6][i & 63];
+    __syncthreads();
+    uint8_t* o = fhdr + (size_t)f * fhdr_stride;
+    for (int i = tid; i < dht_at; i += 256) o[i] = hdr[i];
+    int at = dht_at;
+    for (int t = 0; t < 4; ++t) {
+        const int n = nv[t], len = 2 + 1 + 16 + n;
+        for (int i = tid; i < 5 + 16 + n; i += 256) {
+            uint8_t v;
+            if (i == 0) v = 0xFF;
+            else if (i == 1) v = 0xC4;
+            else if (i == 2) v = (uint8_t)(len >> 8);
+            else if (i == 3) v = (uint8_t)len;
+            else if (i == 4) v = (uint8_t)(((t & 1) << 4) | (t >> 1));
+            else if (i < 21) v = hb[t][i - 5];
+            else v = hv[t][i - 21];
+            o[at + i] = v;
+        }
+        at += 2 + len;
+    }
+    for (int i = tid; i < hdr_len - tail_at; i += 256) o[at + i] = hdr[tail_at + i];
+    if (tid == 0) hlen[f] = at + hdr_len - tail_at;
 }
 
 }  // namespace
@@ -516,76 +840,109 @@ struct trl_jpeg {
     long long* fsize = nullptr;          // [max_frames]
     long long* foff = nullptr;           // [max_frames + 1]
     long long* h_sizes = nullptr;        // pinned [max_frames]
+    // the optioned path (JOpt::ex()): blocks per MCU, the interval in MCUs (no DRI: the MCU count), intervals per frame
+    bool ex = false, optimize = false;
+    int sampling = 2, bpm = 6, R = 0, nint = 1, dht_at = 0, tail_at = 0;
+    unsigned long long* ist = nullptr;   // [chunk][nint] interval byte starts
+    unsigned long long* ibase = nullptr; // [chunk][nint] interval bit starts before padding (k_jpeg_scan_ex's own)
+    uint32_t* hist = nullptr;            // optimize: [chunk][4][256] symbol counts
+    JTab* ftab = nullptr;                //           [chunk] code tables
+    uint8_t* fhdr = nullptr;             //           [chunk][1024] headers
+    int* hlen = nullptr;                 //           [chunk] their lengths
 };
+
+static int jpeg_create(const char* who, int device, int H, int W, const trl_jpeg_options* opt, int max_frames, trl_jpeg** out);
+
+// one chunk of frames on the optioned path: the stages of trl_jpeg_encode with the interval-aware kernels, and with `optimize` the
+// histogram and table kernels between the coefficients and the bit counts (tables never visit the host)
+static int encode_chunk_ex(trl_jpeg* e, const uint8_t* src, long long frame_stride, int cn, int f0, uint8_t* d_out, long long capacity,
+                           hipStream_t s) {
+    const long long total = (long long)cn * e->blocks;
+    if (e->sampling == 2)
+        hipLaunchKernelGGL(k_jpeg_blocks, dim3((e->mcux + kMcuPerWg - 1) / kMcuPerWg, e->mcuy, cn), dim3(256), 0, s, src, frame_stride,
+                           e->H, e->W, e->mcux, e->mcuy, e->tab, e->coef);
+    else if (e->sampling == 1)
+        hipLaunchKernelGGL(k_jpeg_blocks_ex<1>, dim3((e->mcux + 3) / 4, e->mcuy, cn), dim3(256), 0, s, src, frame_stride, e->H, e->W,
+                           e->mcux, e->mcuy, e->tab, e->coef);
+    else
+        hipLaunchKernelGGL(k_jpeg_blocks_ex<0>, dim3((e->mcux + 7) / 8, e->mcuy, cn), dim3(256), 0, s, src, frame_stride, e->H, e->W,
+                           e->mcux, e->mcuy, e->tab, e->coef);
+    TRL_LAUNCH_CHECK();
+    const JTab* tab = e->tab;
+    int tab_stride = 0;
+    if (e->optimize) {
+        TRL_HIP(hipMemsetAsync(e->hist, 0, (size_t)cn * 4096, s));
+        hipLaunchKernelGGL(k_jpeg_hist, dim3((e->blocks + 63) / 64, cn), dim3(256), 0, s, e->coef, e->blocks, e->bpm, e->R, e->hist);
+        TRL_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_jpeg_tables, dim3(cn), dim3(256), 0, s, e->hist, e->tab, e->hdr, e->hdr_len, e->dht_at, e->tail_at, e->ftab,
+                           e->fhdr, 1024, e->hlen);
+        TRL_LAUNCH_CHECK();
+        tab = e->ftab;
+        tab_stride = 1;
+    }
+    const unsigned wgs = (unsigned)((total + 3) / 4);
+    hipLaunchKernelGGL(k_jpeg_bits_ex, dim3(wgs), dim3(256), 0, s, e->coef, e->blocks, total, e->bpm, e->R, tab, tab_stride, e->bits);
+    TRL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jpeg_scan_ex, dim3(cn), dim3(1024), 0, s, e->bits, e->blocks, e->bpm, e->R, e->nint, e->off, e->ist, e->ibase,
+                       e->fbits);
+    TRL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jpeg_emit_ex, dim3(wgs), dim3(256), 0, s, e->coef, e->blocks, total, e->bpm, e->R, e->nint, tab, tab_stride,
+                       e->off, e->bits, e->scratch_per_frame, (uint32_t*)e->scratch, e->first, e->last);
+    TRL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jpeg_edges<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, e->blocks, total, e->off, e->bits,
+                       e->first, e->last, e->scratch_per_frame, (uint32_t*)e->scratch);
+    TRL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jpeg_ffcount<true>, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
+                       e->segs_per_frame, e->segcnt, e->ist, e->nint);
+    TRL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jpeg_sizes, dim3(1), dim3(1024), 0, s, e->segcnt, e->segs_per_frame, e->fbits, cn, f0, e->hdr_len, e->hlen,
+                       e->fsize, e->foff);
+    TRL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_jpeg_scatter<true>, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
+                       e->segcnt, e->segs_per_frame, e->optimize ? e->fhdr : e->hdr, e->hdr_len, f0, e->fsize, e->foff, d_out, capacity,
+                       e->ist, e->nint, e->optimize ? 1024 : 0, e->hlen);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
 
 extern "C" {
 
 int trl_jpeg_header(int H, int W, int quality, uint8_t* buf, size_t cap, int* len) {
     TRL_CHECK(check_shape(H, W));
     if (!len || (!buf && cap)) { trl_set_error("trl_jpeg_header: null argument"); return TRL_ERR_INVALID; }
-    const size_t n = header_bytes(H, W, quality, nullptr);
+    const size_t n = header_bytes(H, W, quality, 2, 0, nullptr);
     *len = (int)n;
     if (cap < n) { trl_set_error("trl_jpeg_header: %zu bytes needed, capacity %zu", n, cap); return TRL_ERR_CAPACITY; }
-    header_bytes(H, W, quality, buf);
+    header_bytes(H, W, quality, 2, 0, buf);
+    return TRL_OK;
+}
+
+int trl_jpeg_header_ex(int H, int W, const trl_jpeg_options* opt, uint8_t* buf, size_t cap, int* len) {
+    JOpt o;
+    TRL_CHECK(resolve_options("trl_jpeg_header_ex", H, W, opt, &o));
+    if (!len || (!buf && cap)) { trl_set_error("trl_jpeg_header_ex: null argument"); return TRL_ERR_INVALID; }
+    const size_t n = header_bytes(H, W, o.quality, o.sampling, o.dri, nullptr);
+    *len = (int)n;
+    if (cap < n) { trl_set_error("trl_jpeg_header_ex: %zu bytes needed, capacity %zu", n, cap); return TRL_ERR_CAPACITY; }
+    header_bytes(H, W, o.quality, o.sampling, o.dri, buf);
+    return TRL_OK;
+}
+
+int trl_jpeg_optimal_table(const uint32_t* hist, uint8_t* bits, uint8_t* vals, int* nvals, int* maxlen) {
+    if (!hist || !bits || !vals || !nvals) { trl_set_error("trl_jpeg_optimal_table: null argument"); return TRL_ERR_INVALID; }
+    trl_hufftab_work w;
+    *nvals = trl_jpeg_hufftab(hist, bits, vals, &w, maxlen);
     return TRL_OK;
 }
 
 int trl_jpeg_create(int device, int H, int W, int quality, int max_frames, trl_jpeg** out) {
-    if (!out) { trl_set_error("trl_jpeg_create: null argument"); return TRL_ERR_INVALID; }
-    *out = nullptr;
-    TRL_CHECK(check_shape(H, W));
-    if (max_frames < 1 || max_frames > 65535) { trl_set_error("trl_jpeg_create: max_frames %d outside 1..65535", max_frames); return TRL_ERR_INVALID; }
-    TRL_HIP(hipSetDevice(device));
-    trl_jpeg* e = new trl_jpeg;
-    e->device = device; e->H = H; e->W = W; e->quality = quality; e->max_frames = max_frames;
-    e->mcux = (W + 15) / 16; e->mcuy = (H + 15) / 16; e->blocks = e->mcux * e->mcuy * 6;
-    e->scratch_per_frame = (size_t)e->blocks * (kMaxBlockBits / 8);
-    e->segs_per_frame = (int)((e->scratch_per_frame + kSeg - 1) / kSeg);
-    const size_t per_frame = (size_t)e->blocks * (128 + 4 + 8 + 8) + e->scratch_per_frame + (size_t)e->segs_per_frame * 4 + 8;
-    e->chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)max_frames, kChunkBudget / per_frame));
-    uint8_t hdr[1024];
-    e->hdr_len = (int)header_bytes(H, W, quality, hdr);
-    JTab tab;
-    for (int t = 0; t < 2; ++t) {
-        uint8_t q[64];
-        quant_table(quality, t, q);
-        for (int i = 0; i < 64; ++i) tab.qdiv[t][i] = (uint16_t)(8 * q[i]);
-        uint8_t dcv[12];
-        for (int i = 0; i < 12; ++i) dcv[i] = (uint8_t)i;
-        uint32_t dc[256] = {0}, ac[256] = {0};
-        huff_codes(kDcBits[t], dcv, dc);
-        huff_codes(kAcBits[t], kAcVals[t], ac);
-        memcpy(tab.dc[t], dc, sizeof(tab.dc[t]));
-        memcpy(tab.ac[t], ac, sizeof(tab.ac[t]));
-    }
-    const size_t C = (size_t)e->chunk, B = (size_t)e->blocks;
-    size_t sz[] = {sizeof(JTab), 1024, C * B * 128, C * B * 4, C * B * 8, C * 8, C * e->segs_per_frame * 4, C * e->scratch_per_frame,
-                   (size_t)max_frames * 8, ((size_t)max_frames + 1) * 8, C * B * 4, C * B * 4};
-    size_t total = 0, offs[12];
-    for (int i = 0; i < 12; ++i) { offs[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
-    hipError_t st = hipMalloc(&e->mem, total);
-    if (st == hipSuccess) st = hipHostMalloc((void**)&e->h_sizes, (size_t)max_frames * 8, hipHostMallocDefault);
-    if (st != hipSuccess) {
-        trl_set_error("trl_jpeg_create: %zu device bytes for %d x %d frames: %s", total, W, H, hipGetErrorString(st));
-        if (e->mem) (void)hipFree(e->mem);
-        delete e;
-        return TRL_ERR_HIP;
-    }
-    uint8_t* m = (uint8_t*)e->mem;
-    e->tab = (JTab*)(m + offs[0]); e->hdr = m + offs[1]; e->coef = (int16_t*)(m + offs[2]); e->bits = (uint32_t*)(m + offs[3]);
-    e->off = (unsigned long long*)(m + offs[4]); e->fbits = (unsigned long long*)(m + offs[5]); e->segcnt = (uint32_t*)(m + offs[6]);
-    e->scratch = m + offs[7]; e->fsize = (long long*)(m + offs[8]); e->foff = (long long*)(m + offs[9]);
-    e->first = (uint32_t*)(m + offs[10]); e->last = (uint32_t*)(m + offs[11]);
-    st = hipMemcpy(e->tab, &tab, sizeof(JTab), hipMemcpyHostToDevice);
-    if (st == hipSuccess) st = hipMemcpy(e->hdr, hdr, e->hdr_len, hipMemcpyHostToDevice);
-    if (st != hipSuccess) {
-        trl_set_error("trl_jpeg_create: %s", hipGetErrorString(st));
-        (void)hipFree(e->mem); (void)hipHostFree(e->h_sizes);
-        delete e;
-        return TRL_ERR_HIP;
-    }
-    *out = e;
-    return TRL_OK;
+    const trl_jpeg_options opt = {quality, 2, 0, 0, 0};
+    return jpeg_create("trl_jpeg_create", device, H, W, &opt, max_frames, out);
+}
+
+int trl_jpeg_create_ex(int device, int H, int W, const trl_jpeg_options* opt, int max_frames, trl_jpeg** out) {
+    return jpeg_create("trl_jpeg_create_ex", device, H, W, opt, max_frames, out);
 }
 
 int trl_jpeg_destroy(trl_jpeg* e) {
@@ -613,6 +970,7 @@ int trl_jpeg_encode(trl_jpeg* e, const uint8_t* d_bgr, int n, long long frame_st
     for (int f0 = 0; f0 < n; f0 += e->chunk) {
         const int cn = std::min(e->chunk, n - f0);
         const long long total = (long long)cn * e->blocks;
+        if (e->ex) { TRL_CHECK(encode_chunk_ex(e, d_bgr + (size_t)f0 * frame_stride, frame_stride, cn, f0, d_out, capacity, s)); continue; }
         hipLaunchKernelGGL(k_jpeg_blocks, dim3((e->mcux + kMcuPerWg - 1) / kMcuPerWg, e->mcuy, cn), dim3(256), 0, s,
                            d_bgr + (size_t)f0 * frame_stride, frame_stride, e->H, e->W, e->mcux, e->mcuy, e->tab, e->coef);
         TRL_LAUNCH_CHECK();
@@ -624,17 +982,18 @@ int trl_jpeg_encode(trl_jpeg* e, const uint8_t* d_bgr, int n, long long frame_st
         hipLaunchKernelGGL(k_jpeg_emit, dim3(wgs), dim3(256), 0, s, e->coef, e->blocks, total, e->tab, e->off, e->bits,
                            e->scratch_per_frame, (uint32_t*)e->scratch, e->first, e->last);
         TRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_jpeg_edges, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, e->blocks, total, e->off, e->bits,
+        hipLaunchKernelGGL(k_jpeg_edges<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, e->blocks, total, e->off, e->bits,
                            e->first, e->last, e->scratch_per_frame, (uint32_t*)e->scratch);
         TRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_jpeg_ffcount, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
-                           e->segs_per_frame, e->segcnt);
+        hipLaunchKernelGGL(k_jpeg_ffcount<false>, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
+                           e->segs_per_frame, e->segcnt, nullptr, 0);
         TRL_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_jpeg_sizes, dim3(1), dim3(1024), 0, s, e->segcnt, e->segs_per_frame, e->fbits, cn, f0, e->hdr_len,
-                           e->fsize, e->foff);
+                           nullptr, e->fsize, e->foff);
         TRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_jpeg_scatter, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
-                           e->segcnt, e->segs_per_frame, e->hdr, e->hdr_len, f0, e->fsize, e->foff, d_out, capacity);
+        hipLaunchKernelGGL(k_jpeg_scatter<false>, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
+                           e->segcnt, e->segs_per_frame, e->hdr, e->hdr_len, f0, e->fsize, e->foff, d_out, capacity,
+                           nullptr, 0, 0, nullptr);
         TRL_LAUNCH_CHECK();
     }
     TRL_HIP(hipMemcpyAsync(e->h_sizes, e->fsize, (size_t)n * 8, hipMemcpyDeviceToHost, s));
@@ -644,3 +1003,72 @@ int trl_jpeg_encode(trl_jpeg* e, const uint8_t* d_bgr, int n, long long frame_st
 }
 
 }  // extern "C"
+
+static int jpeg_create(const char* who, int device, int H, int W, const trl_jpeg_options* opt, int max_frames, trl_jpeg** out) {
+    if (!out) { trl_set_error("%s: null argument", who); return TRL_ERR_INVALID; }
+    *out = nullptr;
+    JOpt o;
+    TRL_CHECK(resolve_options(who, H, W, opt, &o));
+    if (max_frames < 1 || max_frames > 65535) { trl_set_error("%s: max_frames %d outside 1..65535", who, max_frames); return TRL_ERR_INVALID; }
+    TRL_HIP(hipSetDevice(device));
+    trl_jpeg* e = new trl_jpeg;
+    e->device = device; e->H = H; e->W = W; e->quality = o.quality; e->max_frames = max_frames;
+    e->mcux = o.mcux; e->mcuy = o.mcuy; e->blocks = e->mcux * e->mcuy * o.bpm;
+    e->ex = o.ex(); e->optimize = o.optimize; e->sampling = o.sampling; e->bpm = o.bpm;
+    const int nmcu = e->mcux * e->mcuy;
+    e->R = o.dri > 0 ? o.dri : nmcu;
+    e->nint = (nmcu + e->R - 1) / e->R;
+    e->scratch_per_frame = (size_t)e->blocks * (kMaxBlockBits / 8);
+    e->segs_per_frame = (int)((e->scratch_per_frame + kSeg - 1) / kSeg);
+    const size_t NI = e->ex ? (size_t)e->nint : 0, OPT = e->optimize ? 1 : 0;
+    const size_t per_frame = (size_t)e->blocks * (128 + 4 + 8 + 8) + e->scratch_per_frame + (size_t)e->segs_per_frame * 4 + 8 + NI * 16 +
+                             OPT * (4096 + sizeof(JTab) + 1024 + 4);
+    e->chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)max_frames, kChunkBudget / per_frame));
+    uint8_t hdr[1024];
+    e->hdr_len = (int)header_bytes(H, W, o.quality, o.sampling, o.dri, hdr, &e->dht_at, &e->tail_at);
+    JTab tab;
+    for (int t = 0; t < 2; ++t) {
+        uint8_t q[64];
+        quant_table(o.quality, t, q);
+        for (int i = 0; i < 64; ++i) tab.qdiv[t][i] = (uint16_t)(8 * q[i]);
+        uint8_t dcv[12];
+        for (int i = 0; i < 12; ++i) dcv[i] = (uint8_t)i;
+        uint32_t dc[256] = {0}, ac[256] = {0};
+        huff_codes(kDcBits[t], dcv, dc);
+        huff_codes(kAcBits[t], kAcVals[t], ac);
+        memcpy(tab.dc[t], dc, sizeof(tab.dc[t]));
+        memcpy(tab.ac[t], ac, sizeof(tab.ac[t]));
+    }
+    const size_t C = (size_t)e->chunk, B = (size_t)e->blocks;
+    constexpr int kParts = 18;
+    size_t sz[kParts] = {sizeof(JTab), 1024, C * B * 128, C * B * 4, C * B * 8, C * 8, C * e->segs_per_frame * 4, C * e->scratch_per_frame,
+                         (size_t)max_frames * 8, ((size_t)max_frames + 1) * 8, C * B * 4, C * B * 4,
+                         C * NI * 8, C * NI * 8, OPT * C * 4096, OPT * C * sizeof(JTab), OPT * C * 1024, OPT * C * 4};
+    size_t total = 0, offs[kParts];
+    for (int i = 0; i < kParts; ++i) { offs[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
+    hipError_t st = hipMalloc(&e->mem, total);
+    if (st == hipSuccess) st = hipHostMalloc((void**)&e->h_sizes, (size_t)max_frames * 8, hipHostMallocDefault);
+    if (st != hipSuccess) {
+        trl_set_error("%s: %zu device bytes for %d x %d frames: %s", who, total, W, H, hipGetErrorString(st));
+        if (e->mem) (void)hipFree(e->mem);
+        delete e;
+        return TRL_ERR_HIP;
+    }
+    uint8_t* m = (uint8_t*)e->mem;
+    e->tab = (JTab*)(m + offs[0]); e->hdr = m + offs[1]; e->coef = (int16_t*)(m + offs[2]); e->bits = (uint32_t*)(m + offs[3]);
+    e->off = (unsigned long long*)(m + offs[4]); e->fbits = (unsigned long long*)(m + offs[5]); e->segcnt = (uint32_t*)(m + offs[6]);
+    e->scratch = m + offs[7]; e->fsize = (long long*)(m + offs[8]); e->foff = (long long*)(m + offs[9]);
+    e->first = (uint32_t*)(m + offs[10]); e->last = (uint32_t*)(m + offs[11]);
+    e->ist = (unsigned long long*)(m + offs[12]); e->ibase = (unsigned long long*)(m + offs[13]);
+    if (e->optimize) { e->hist = (uint32_t*)(m + offs[14]); e->ftab = (JTab*)(m + offs[15]); e->fhdr = m + offs[16]; e->hlen = (int*)(m + offs[17]); }
+    st = hipMemcpy(e->tab, &tab, sizeof(JTab), hipMemcpyHostToDevice);
+    if (st == hipSuccess) st = hipMemcpy(e->hdr, hdr, e->hdr_len, hipMemcpyHostToDevice);
+    if (st != hipSuccess) {
+        trl_set_error("%s: %s", who, hipGetErrorString(st));
+        (void)hipFree(e->mem); (void)hipHostFree(e->h_sizes);
+        delete e;
+        return TRL_ERR_HIP;
+    }
+    *out = e;
+    return TRL_OK;
+}

@@ -1,8 +1,9 @@
 """``DeviceJpeg`` and ``DeviceJpegDecoder``: the Motion-JPEG encoder of ``trl_jpeg.hip`` and the decoder of ``trl_jpegd.hip``, each
 behind a small Python object.
 
-Each frame's file is byte-identical to Pillow's ``Image.save(format="JPEG", quality=q, subsampling=2)`` of the RGB frame, which is
-what ``AviMjpegWriter`` writes with its Pillow encoder: the device encoder changes how fast ``run()``'s annotated output is
+Each frame's file is byte-identical to Pillow's ``Image.save(format="JPEG", quality=q, subsampling=s, restart_marker_rows=r |
+restart_marker_blocks=b, optimize=o)`` of the RGB frame (defaults: 4:2:0, no restart markers, standard tables), which is what
+``AviMjpegWriter`` writes with its Pillow encoder: the device encoder changes how fast ``run()``'s annotated output is
 written, not what is written.  The encoder owns its device workspace and its own stream, independent of the cascade contexts
 (run()'s contexts are busy while the writer thread encodes)."""
 from __future__ import annotations
@@ -17,25 +18,38 @@ from . import _lib
 
 class DeviceJpeg:
     """``encode(frames)``: a uint8 BGR batch (n, H, W, 3) -- host array or device tensor, any stride between frames -- to a list of
-    n JPEG files (bytes).  ``max_frames`` bounds one call's batch (larger batches are split)."""
+    n JPEG files (bytes).  ``max_frames`` bounds one call's batch (larger batches are split).  ``subsampling`` 0 / 1 / 2 = 4:4:4 /
+    4:2:2 / 4:2:0, ``restart_rows`` / ``restart_blocks`` (an interval in MCU rows / in MCUs; rows win) and ``optimize`` (per-frame
+    Huffman tables) mean what they mean to Pillow's ``Image.save``; a stream with ``restart_rows=1`` is the kind
+    ``DeviceJpegDecoder`` reads fastest."""
 
-    def __init__(self, W: int, H: int, quality: int = 80, device=None, max_frames: int = 32):
+    def __init__(self, W: int, H: int, quality: int = 80, device=None, max_frames: int = 32, subsampling: int = 2,
+                 restart_rows: int = 0, restart_blocks: int = 0, optimize: bool = False):
         if device is None:
             device = torch.cuda.current_device()
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if self.device.type != "cuda":
             raise ValueError(f"DeviceJpeg needs a GPU device, got {self.device}")
         self.W, self.H, self.quality, self.max_frames = int(W), int(H), int(quality), int(max_frames)
+        self.subsampling, self.restart_rows, self.restart_blocks = int(subsampling), int(restart_rows), int(restart_blocks)
+        self.optimize = bool(optimize)
         self.lib = _lib.load()
         self.stream = torch.cuda.Stream(self.device)
         h = C.c_void_p()
-        _lib.check(self.lib.trl_jpeg_create(self.device.index or 0, self.H, self.W, self.quality, self.max_frames, C.byref(h)))
+        opt = _lib.TrlJpegOptions(self.quality, self.subsampling, self.restart_rows, self.restart_blocks, int(self.optimize))
+        _lib.check(self.lib.trl_jpeg_create_ex(self.device.index or 0, self.H, self.W, C.byref(opt), self.max_frames, C.byref(h)))
         self.h = h
         n = C.c_int(0)
-        self.lib.trl_jpeg_header(self.H, self.W, self.quality, None, 0, C.byref(n))
-        self.header_len = n.value
-        # start capacity: a generous guess for ordinary content; the first batch that needs more grows it (grow and re-run)
-        self.capacity = self.max_frames * (self.header_len + 2 + self.H * self.W // 2 + 4096)
+        self.lib.trl_jpeg_header_ex(self.H, self.W, C.byref(opt), None, 0, C.byref(n))      # (no buffer: the length only)
+        self.header_len = n.value                         # (optimize: an upper bound on every frame's header)
+        # start capacity: a generous guess for ordinary content -- a third of a byte per sample (4:2:0 has 1.5 samples per pixel,
+        # 4:2:2 2, 4:4:4 3) and the restart markers; the first batch that needs more grows it (grow and re-run)
+        mw, mh = (8, 8) if self.subsampling == 0 else (16, 8) if self.subsampling == 1 else (16, 16)
+        mcux, mcuy = -(-self.W // mw), -(-self.H // mh)
+        interval = min(self.restart_rows * mcux, 65535) if self.restart_rows > 0 else self.restart_blocks
+        markers = 2 * (-(-mcux * mcuy // interval) - 1) if interval > 0 else 0
+        samples6 = (6, 4, 3)[self.subsampling]            # samples per pixel x 2
+        self.capacity = self.max_frames * (self.header_len + 2 + self.H * self.W * samples6 // 6 + markers + 4096)
         self.out = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
         self.host = torch.empty(self.capacity, dtype=torch.uint8).pin_memory()
         self.sizes = np.zeros(self.max_frames, np.int64)

@@ -276,7 +276,9 @@ def run(video_path_one: str, video_path_two: str, engine: Engine | None = None) 
     output with Pillow on the writer thread instead of on the engine's GPU (the same bytes, slower); TRUELY_DRAW=host draws the
     annotations on the writer thread and sends host frames to the device encoder (the same bytes; the path before the device
     drawing existed); TRUELY_MJPEG=pillow decodes Motion-JPEG input with Pillow, frame by frame on the reader thread (the same
-    frames; the path before the device decoder existed, and the escape hatch)."""
+    frames; the path before the device decoder existed, and the escape hatch); TRUELY_JPEG_SUBSAMPLING (420, 422, 444),
+    TRUELY_JPEG_RESTART_ROWS (MCU rows per restart interval) and TRUELY_JPEG_OPTIMIZE (1: per-frame Huffman tables) choose the
+    Motion-JPEG output's options for either encoder (video_io.jpeg_options_from_env; unset: the output is unchanged)."""
     start_time = time.time()
     # model.py:20-22
     if not os.path.exists(video_path_one) or os.path.getsize(video_path_one) == 0:

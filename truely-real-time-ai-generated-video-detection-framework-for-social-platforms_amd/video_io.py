@@ -194,22 +194,29 @@ class AviMjpegWriter:
 
     BATCH = 32                                       # frames per device encoder call
 
-    def __init__(self, path, fps, size, quality: int = 80, threads: int | None = None, encoder: str = "pillow", device=None):
+    def __init__(self, path, fps, size, quality: int = 80, threads: int | None = None, encoder: str = "pillow", device=None,
+                 subsampling: int = 2, restart_rows: int = 0, optimize: bool = False):
         """``encoder="device"``: frames are collected into a pinned batch of ``BATCH``, encoded on the GPU ``device`` by
-        jpeg.DeviceJpeg (byte-identical files) and appended in order; ``"pillow"``: Pillow's libjpeg on the calling thread."""
+        jpeg.DeviceJpeg (byte-identical files) and appended in order; ``"pillow"``: Pillow's libjpeg on the calling thread.
+        ``subsampling`` (0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0), ``restart_rows`` (a restart marker every that many MCU rows) and
+        ``optimize`` (per-frame Huffman tables) go to whichever encoder writes: the file does not depend on it."""
         from PIL import Image                        # noqa: F401  (fail at open time, not on the writer thread)
         import collections
         import concurrent.futures
         if encoder not in ("pillow", "device"):
             raise ValueError(f"encoder must be 'pillow' or 'device', not {encoder!r}")
         self.path, self.w, self.h, self.fps, self.quality = path, int(size[0]), int(size[1]), max(1, int(round(fps))), int(quality)
+        if subsampling not in (0, 1, 2) or int(restart_rows) < 0:
+            raise ValueError(f"subsampling must be 0, 1 or 2 and restart_rows >= 0, not {subsampling!r} / {restart_rows!r}")
+        self.subsampling, self.restart_rows, self.optimize = int(subsampling), int(restart_rows), bool(optimize)
         self.encoder = encoder
         self.dev_enc = self.batch = None
         self.pending = 0
         if encoder == "device":
             import torch
             from .jpeg import DeviceJpeg
-            self.dev_enc = DeviceJpeg(self.w, self.h, self.quality, device=device, max_frames=self.BATCH)
+            self.dev_enc = DeviceJpeg(self.w, self.h, self.quality, device=device, max_frames=self.BATCH, subsampling=self.subsampling,
+                                      restart_rows=self.restart_rows, optimize=self.optimize)
             self.batch = torch.empty((self.BATCH, self.h, self.w, 3), dtype=torch.uint8).pin_memory()
             self.batch_np = self.batch.numpy()
             threads = 1
@@ -241,7 +248,14 @@ class AviMjpegWriter:
         import io
         a = np.ascontiguousarray(np.asarray(frame, np.uint8)[:, :, ::-1])      # BGR (cap.read()) -> RGB
         buf = io.BytesIO()
-        Image.fromarray(a, "RGB").save(buf, format="JPEG", quality=self.quality, subsampling=2)
+        more = {"restart_marker_rows": self.restart_rows} if self.restart_rows else {}
+        if self.optimize:
+            from PIL import ImageFile
+            more["optimize"] = True
+            # Pillow hands libjpeg's second pass one buffer of w * h bytes (2 w h from quality 95) and fails on a larger file
+            # (noise at 4:4:4); MAXBLOCK is that buffer's lower bound
+            ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, a.size + 65536)
+        Image.fromarray(a, "RGB").save(buf, format="JPEG", quality=self.quality, subsampling=self.subsampling, **more)
         return buf.getvalue()
 
     def _append(self, data: bytes):
@@ -574,9 +588,33 @@ def open_writer(path, fps, size, like_raw: bool = False, device=None):
         return cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*"H264"), fps, size)
     if not str(path).lower().endswith(".avi"):       # the server names the file *.mp4 and serves it as video/mp4: say what it really is
         print(f"Note: OpenCV is not installed, {os.path.basename(str(path))} is written as Motion-JPEG in an AVI container (not H.264)")
+    opts = jpeg_options_from_env()
     if device is not None:
-        return AviMjpegWriter(path, fps, size, encoder="device", device=device)
-    return AviMjpegWriter(path, fps, size)
+        return AviMjpegWriter(path, fps, size, encoder="device", device=device, **opts)
+    return AviMjpegWriter(path, fps, size, **opts)
+
+
+def jpeg_options_from_env() -> dict:
+    """``AviMjpegWriter``'s JPEG options from the environment: ``TRUELY_JPEG_SUBSAMPLING`` (``420``, ``422``, ``444``),
+    ``TRUELY_JPEG_RESTART_ROWS`` (MCU rows per restart interval) and ``TRUELY_JPEG_OPTIMIZE`` (``1``: per-frame Huffman tables).
+    Unset (or empty) variables leave the writer's defaults, and with them every byte of the file, as they are."""
+    opts = {}
+    sub = os.environ.get("TRUELY_JPEG_SUBSAMPLING", "")
+    if sub:
+        if sub not in ("420", "422", "444"):
+            raise ValueError(f"TRUELY_JPEG_SUBSAMPLING must be 420, 422 or 444, not {sub!r}")
+        opts["subsampling"] = {"444": 0, "422": 1, "420": 2}[sub]
+    rows = os.environ.get("TRUELY_JPEG_RESTART_ROWS", "")
+    if rows:
+        if not rows.isdigit():
+            raise ValueError(f"TRUELY_JPEG_RESTART_ROWS must be a number of MCU rows, not {rows!r}")
+        opts["restart_rows"] = int(rows)
+    opt = os.environ.get("TRUELY_JPEG_OPTIMIZE", "")
+    if opt:
+        if opt not in ("0", "1"):
+            raise ValueError(f"TRUELY_JPEG_OPTIMIZE must be 0 or 1, not {opt!r}")
+        opts["optimize"] = opt == "1"
+    return opts
 
 
 def encodes_on_device(path, device) -> bool:

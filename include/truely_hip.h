@@ -493,6 +493,35 @@ size_t trl_draw_workspace(int n_frames, int n_segs);
 int  trl_draw(uint8_t* d_bgr, int n, long long frame_stride, int H, int W, const trl_draw_frame* frames, int n_frames,
               const trl_draw_seg* segs, int n_segs, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- Embedding match (the step after InceptionResnetV1: "whose face is this?") -------------------------------------------------
+ * A gallery of enrolled 512-float embeddings in device memory, the score matrix of n queries against it, and a fused top-k search
+ * that streams the gallery once and never writes that matrix.  Needs no context and no weights; all memory is the caller's, the
+ * device is the one that owns d_mat, all work is queued on `stream` and no call synchronises.  (ABI v7, additive)
+ *   layout   d_mat is k-major, [512][ld] f32 with ld a positive multiple of 32, padding columns zero; d_n2[ld] holds n2 of every
+ *            column.  Gallery row c is column c.
+ *   dot      dot(q, g) = chain(0; k = 0..511 ascending: acc = fmaf(q[k], g[k], acc)), one f32 chain; n2(x) = dot(x, x).
+ *   metric   0 cosine: dot / (sqrtf(n2 q) * sqrtf(n2 g)), larger is better, a zero row gives NaN.
+ *            1 euclidean: s = n2 q + n2 g; d2 = fmaf(-2, dot, s); d2 < 0 ? 0 : d2 (NaN stays NaN); sqrtf(d2), smaller is better.
+ *   order    better score first; equal scores (as floats: -0 == +0) to the lower gallery index; NaN scores after every other,
+ *            lower index first.  Slots past the gallery (k > m), and every slot of a row with d_valid[r] == 0: index -1, score NaN.
+ * Results are the same bits whatever n, strip length or stream.
+ * TRL_ERR_INVALID with nothing queued: ld or ldo out of range, k outside 1..16, a metric other than 0 / 1, c0 + m > ld, m > ld,
+ * m > 2^31 - 1, max_strip_cols no multiple of 128, a workspace too small or not 8-byte aligned, a null pointer. */
+/* d_rows [m][512] row-major (as the embedder writes them) -> columns c0 .. c0 + m - 1 of d_mat and their n2 into d_n2[c0 ..]. */
+int    trl_gallery_pack(const float* d_rows, long long m, float* d_mat, long long ld, float* d_n2, long long c0, void* stream);
+/* d_out[r * ldo + c] = score of query r against gallery row c, r < n, c < m (ldo >= m); nothing else is written. */
+int    trl_gallery_scores(const float* d_q, int n, const float* d_mat, long long ld, const float* d_n2, long long m, int metric,
+                          float* d_out, long long ldo, void* stream);
+/* Device bytes trl_gallery_search needs: n x k (score, index) pairs per strip of gallery columns.  The strip count follows from n
+ * and m and is bounded (512) unless max_strip_cols forces shorter strips, so the size does not grow with m.  0 on bad arguments. */
+size_t trl_gallery_search_workspace(int n, long long m, int k, int max_strip_cols);
+/* The k best gallery rows of each query, in order: d_score [n][k], d_index [n][k].  d_valid (n bytes) may be null: every row is
+ * searched.  max_strip_cols: 0, or the most gallery columns one workgroup walks (a multiple of 128; the tests use it to reach the
+ * merge of several strips at a small gallery).  n = 0: nothing is done; m = 0: the outputs are filled with -1 / NaN. */
+int    trl_gallery_search(const float* d_q, const uint8_t* d_valid, int n, const float* d_mat, long long ld, const float* d_n2,
+                          long long m, int metric, int k, float* d_score, int32_t* d_index, void* d_ws, size_t ws_bytes,
+                          int max_strip_cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

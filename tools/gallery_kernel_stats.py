@@ -1,0 +1,105 @@
+"""Kernel times of the gallery search (csrc/trl_gallery.hip) by the method of profiles/logits_kernel_stats.csv: rocprofv3 kernel
+trace, one process per shape, median of 10 warm launches (after 10 of warm-up) and of 5 cold ones, each behind a 1 GiB fill.
+
+    python tools/gallery_kernel_stats.py --all out_dir > profiles/gallery_kernel_stats.csv      # every shape, then the table
+    rocprofv3 --kernel-trace -d out_dir/m_n -o t -f csv -- python3 tools/gallery_kernel_stats.py run M N     (what --all starts)
+    python tools/gallery_kernel_stats.py --table out_dir
+
+A launch's time is k_gallery_search plus k_gallery_merge.  Next to it: the two floors of the shape -- one pass over the gallery,
+m * 2 KB at 8.0 TB/s, and 2 n 512 m FLOP at the 157.3 TFLOP/s f32-MFMA peak -- and what a user would
+otherwise write on the same device: torch.mm(q, rows.T) + torch.topk(k), cosine on rows normalised beforehand (the sum of every
+kernel the two calls launch, median of 10 after 10 of warm-up)."""
+import csv
+import glob
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+M_SHAPES, N_SHAPES, K = (1_000, 100_000, 1_000_000), (1, 32, 256), 5
+HBM_BYTES_PER_US, MFMA_FLOP_PER_US = 8.0e6, 157.3e6
+WARMUP, WARM, COLD = 10, 10, 5
+
+
+def run(m, n):
+    import torch
+    from truely_amd.gallery import FaceGallery
+    gen = torch.Generator(device="cuda").manual_seed(m + n)
+    rows = torch.nn.functional.normalize(torch.randn((m, 512), generator=gen, device="cuda"), dim=1)
+    q = torch.nn.functional.normalize(torch.randn((n, 512), generator=gen, device="cuda"), dim=1)
+    gal = FaceGallery(metric="cosine", capacity=m)
+    gal.add(rows, range(m))
+    torch.cuda.synchronize()
+    for _ in range(WARMUP + WARM):
+        idx, score = gal.search(q, k=K)
+    torch.cuda.synchronize()
+    for _ in range(WARMUP + WARM):
+        v, i = torch.topk(torch.mm(q, rows.t()), K, dim=1)
+    torch.cuda.synchronize()
+    big = torch.empty((1 << 30,), dtype=torch.uint8, device="cuda")
+    for c in range(COLD):
+        big.fill_(c)
+        gal.search(q, k=K)
+    torch.cuda.synchronize()
+    same = float((i == idx).float().mean())                   # (float32 sums in another order: near-ties may swap)
+    print(json.dumps({"m": m, "n": n, "workspace_bytes": int(gal.lib.trl_gallery_search_workspace(n, m, K, 0)), "torch_agreement": same}))
+
+
+def _trace(d):
+    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
+    rows = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(f))]
+    return sorted(rows)
+
+
+def table(out):
+    print("m,n,k,metric,state,launches,median_us,min_us,max_us,merge_median_us,workspace_bytes,floor_hbm_us,floor_mfma_us,torch_mm_topk_median_us")
+    for m in M_SHAPES:
+        for n in N_SHAPES:
+            d = os.path.join(out, f"{m}_{n}")
+            info = json.load(open(os.path.join(d, "info.json")))
+            tr = _trace(d)
+            first = next(i for i, r in enumerate(tr) if "k_gallery_search" in r[2])
+            tr = tr[first:]                                   # (behind the enrolment)
+            launches, other = [], []                          # per search launch: [search ns, merge ns]; kernels between searches
+            for s, e, name in tr:
+                if "k_gallery_search" in name:
+                    launches.append([e - s, 0])
+                elif "k_gallery_merge" in name:
+                    launches[-1][1] = e - s
+                elif len(launches) == WARMUP + WARM:
+                    other.append(e - s)
+            assert len(launches) == WARMUP + WARM + COLD, len(launches)
+            per = len(other) // (WARMUP + WARM)               # kernels of one mm + topk
+            torch_us = statistics.median(sum(other[i * per:(i + 1) * per]) for i in range(WARMUP, WARMUP + WARM)) / 1e3
+            hbm, mfma = m * 2048 / HBM_BYTES_PER_US, 2.0 * n * 512 * m / MFMA_FLOP_PER_US
+            for state, part in (("warm", launches[WARMUP:WARMUP + WARM]), ("cold", launches[WARMUP + WARM:])):
+                tot = [(a + b) / 1e3 for a, b in part]
+                print(f"{m},{n},{K},cosine,{state},{len(part)},{statistics.median(tot):.1f},{min(tot):.1f},{max(tot):.1f},"
+                      f"{statistics.median(b for _a, b in part) / 1e3:.1f},{info['workspace_bytes']},{hbm:.1f},{mfma:.1f},{torch_us:.1f}")
+
+
+def run_all(out):
+    for m in M_SHAPES:
+        for n in N_SHAPES:
+            d = os.path.join(out, f"{m}_{n}")
+            os.makedirs(d, exist_ok=True)
+            r = subprocess.run(["rocprofv3", "--kernel-trace", "-d", d, "-o", "t", "-f", "csv", "--", sys.executable, os.path.abspath(__file__),
+                                "run", str(m), str(n)], capture_output=True, text=True, timeout=300)
+            if r.returncode != 0:
+                sys.exit(f"shape {m} x {n} failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+            print(line, file=sys.stderr, flush=True)
+            open(os.path.join(d, "info.json"), "w").write(line)
+    table(out)
+
+
+if __name__ == "__main__":
+    if sys.argv[1] == "--all":
+        run_all(sys.argv[2])
+    elif sys.argv[1] == "--table":
+        table(sys.argv[2])
+    else:
+        run(int(sys.argv[2]), int(sys.argv[3]))

@@ -106,6 +106,10 @@ _SIGNATURES = {
     "trl_jpegd_decode": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _vp, C.c_longlong, _vp, _vp]),
     "trl_draw_workspace": (C.c_size_t, [_i, _i]),
     "trl_draw": (C.c_int, [_vp, _i, C.c_longlong, _i, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp]),
+    "trl_gallery_pack": (C.c_int, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp]),
+    "trl_gallery_scores": (C.c_int, [_vp, _i, _vp, C.c_longlong, _vp, C.c_longlong, _i, _vp, C.c_longlong, _vp]),
+    "trl_gallery_search_workspace": (C.c_size_t, [_i, C.c_longlong, _i, _i]),
+    "trl_gallery_search": (C.c_int, [_vp, _vp, _i, _vp, C.c_longlong, _vp, C.c_longlong, _i, _i, _vp, _vp, _vp, C.c_size_t, _i, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

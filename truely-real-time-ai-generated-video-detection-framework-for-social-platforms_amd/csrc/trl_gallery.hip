@@ -1,0 +1,415 @@
+// trl_gallery.hip -- embedding match: a gallery of enrolled 512-float embeddings on the device, the full
+// score matrix of n queries against it, and the fused top-k search that never writes that matrix.
+//
+// The gallery is k-major, [512][ld] f32 with ld a multiple of 32 and zero padding, plus n2[ld] -- the loader's layout of
+// facenet.logits.w, and for the reason trl_logits.hip gives: lane l's B operand of v_mfma_f32_32x32x2_f32 is one dword of a whole
+// 128-byte line, so the gallery goes from memory into the matrix core without touching LDS.  The main loop is k_logits' with a
+// zero bias: a workgroup holds a row tile of 32 queries in LDS ([32][514] words), each of its 4 waves owns 32 gallery columns of a
+// 128-column group, the columns stream through a three-deep register ring, and every output is ONE accumulator over ascending k:
+//     dot(q, g) = chain(0; k = 0..511: acc = fmaf(q[k], g[k], acc))                         
+// n2(x) = dot(x, x) is the same chain, taken once per gallery row at enrolment (k_gallery_pack) and once per query row per
+// workgroup (gl_fill_tile).  The epilogue turns accumulators into scores:
+//     cosine      dot / (sqrtf(n2 q) * sqrtf(n2 g))
+//     euclidean   s = n2 q + n2 g;  d2 = fmaf(-2, dot, s);  d2 < 0 ? 0 : d2;  sqrtf(d2)
+// k_gallery_scores stores them (rows < n, columns < m).  k_gallery_search keeps running lists of the k best matches in LDS
+// (trl_gallery_order.h): a wave puts its 32 x 32 scores through an LDS stage, then lane l walks row l & 31 over 16 of the 32
+// columns against a list of its own -- a score is compared with the list's k-th entry, kept in a register, and only survivors
+// are inserted: after a strip's first groups almost none, and the 64 lists of a wave are updated side by side.  A workgroup walks
+// a STRIP of column groups, merges its eight lists per row and writes n x k entries per strip; k_gallery_merge merges the strips
+// per row by the same order.  Scores do not depend on n, tile, strip or launch geometry (one chain per output), and the order is
+// total, so neither does the result.
+#include <algorithm>
+#include <utility>
+
+#include "trl_common.h"
+#include "trl_gallery_order.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int GL_K = 512;             // floats per embedding
+constexpr int GL_LDF = GL_K + 2;      // LDS row pitch in words (trl_logits.hip: 64 lanes of an A read on 64 banks)
+constexpr int GL_ROWS = 32;           // query rows of a tile
+constexpr int GL_CHUNK = 32;          // k-steps (of 2) per ring slot
+constexpr int GL_NCHUNK = GL_K / 2 / GL_CHUNK;
+constexpr int GL_GROUP = 128;         // gallery columns of a workgroup's step: 32 per wave
+constexpr int GL_TILE_WORDS = GL_ROWS * GL_LDF;
+constexpr int GL_INFO_WORDS = 3 * GL_ROWS;   // per row: n2, sqrtf(n2), and whether the row exists and is valid
+constexpr int GL_TARGET_WGS = 512;    // workgroups wanted: two rounds of one per CU on 256 CUs
+constexpr int GL_MAX_STRIPS = 512;    // of the default plan
+constexpr int GL_STAGE_WORDS = GL_ROWS * 33;   // a wave's 32 x 32 scores, rows 33 words apart
+constexpr int GL_LISTS = 8;           // lists per query row in a workgroup: two per wave
+
+template <int... I, typename F>
+__device__ __forceinline__ void gl_static_for(std::integer_sequence<int, I...>, F&& f) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+
+// rows row0 .. row0 + 31 of q -> tile (rows past n as zeros), and their n2 / sqrtf(n2) / live flag -> info.  Ends on a barrier.
+__device__ __forceinline__ int gl_fill_tile(float* tile, float* info, const float* __restrict__ q, const uint8_t* __restrict__ valid,
+                                            int n, long long row0, int tid) {
+    const int live = n - row0 < GL_ROWS ? (int)(n - row0) : GL_ROWS;
+    const float* src = q + (size_t)row0 * GL_K;
+    if ((reinterpret_cast<uintptr_t>(q) & 15) == 0) {
+#pragma unroll 4
+        for (int t = tid; t < GL_ROWS * GL_K / 4; t += 256) {
+            const int r = t >> 7, c = t & 127;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < live) v = *reinterpret_cast<const float4*>(src + (size_t)r * GL_K + 4 * c);
+            float2* d = reinterpret_cast<float2*>(tile + r * GL_LDF + 4 * c);      // (rows are 8-byte aligned: 514 words)
+            d[0] = make_float2(v.x, v.y);
+            d[1] = make_float2(v.z, v.w);
+        }
+    } else {
+#pragma unroll 4
+        for (int t = tid; t < GL_ROWS * GL_K; t += 256) {
+            const int r = t >> 9, k = t & 511;
+            tile[r * GL_LDF + k] = r < live ? src[(size_t)r * GL_K + k] : 0.f;
+        }
+    }
+    __syncthreads();
+    if (tid < GL_ROWS) {
+        const float* x = tile + tid * GL_LDF;
+        float acc = 0.f;
+#pragma unroll 16
+        for (int k = 0; k < GL_K; k++) acc = __builtin_fmaf(x[k], x[k], acc);
+        info[tid] = acc;
+        info[GL_ROWS + tid] = __builtin_sqrtf(acc);
+        reinterpret_cast<int*>(info)[2 * GL_ROWS + tid] = tid < live && (!valid || valid[row0 + tid] != 0);
+    }
+    __syncthreads();
+    return live;
+}
+
+// One wave: the 32 x 32 dots of the tile's rows against gallery columns c0 .. c0 + 31 (c0 + 31 < ld).  C/D map of the 32x32
+// forms: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5).
+__device__ __forceinline__ f32x16 gl_chain(const float* tile, const float* __restrict__ mat, size_t ld, long long c0, int lane) {
+    const int j = lane & 31, h = lane >> 5;
+    const float* wp = mat + (size_t)h * ld + c0 + j;
+    const float* xp = tile + j * GL_LDF + h;
+    const size_t step = 2 * ld;
+    float wb[3][GL_CHUNK], xa[2][GL_CHUNK];
+    // a ring slot's 32 k-rows are addressed from the slot's own base, which the compiler is kept from folding back into
+    // 256 multiples of ld: inside a loop over column groups those would be hoisted into more registers than there are
+    auto load_w = [&](int ch, float* o) __attribute__((always_inline)) {
+        const float* base = wp + (size_t)(ch * GL_CHUNK) * step;
+        asm volatile("" : "+v"(base));
+#pragma unroll
+        for (int u = 0; u < GL_CHUNK; u++) o[u] = base[(size_t)u * step];
+    };
+    auto load_x = [&](int ch, float* o) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < GL_CHUNK; u++) o[u] = xp[2 * (ch * GL_CHUNK + u)];
+    };
+    load_w(0, wb[0]);
+    load_w(1, wb[1]);
+    load_x(0, xa[0]);
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc[i] = 0.f;
+    gl_static_for(std::make_integer_sequence<int, GL_NCHUNK>{}, [&](auto CH) __attribute__((always_inline)) {
+        constexpr int ch = decltype(CH)::value;
+        if constexpr (ch + 2 < GL_NCHUNK) load_w(ch + 2, wb[(ch + 2) % 3]);
+        if constexpr (ch + 1 < GL_NCHUNK) load_x(ch + 1, xa[(ch + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < GL_CHUNK; u++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[ch & 1][u], wb[ch % 3][u], acc, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    return acc;
+}
+
+__device__ __forceinline__ float gl_score(int metric, float dot, float qn2, float qsq, float gn2, float gsq) {
+    if (metric == TRL_GL_COSINE) return dot / (qsq * gsq);
+    const float s = qn2 + gn2;
+    float d2 = __builtin_fmaf(-2.0f, dot, s);
+    d2 = d2 < 0.f ? 0.f : d2;                           // (NaN stays NaN)
+    return __builtin_sqrtf(d2);
+}
+
+// grid: x = group * tiles + tile (the row tile is the fast index: workgroups in flight share a few column groups in L2)
+__global__ __launch_bounds__(256) void k_gallery_scores(const float* __restrict__ q, int n, const float* __restrict__ mat, long long ld,
+                                                        const float* __restrict__ gn2, long long m, int metric, float* __restrict__ out,
+                                                        long long ldo, int tiles) {
+    extern __shared__ float gl_lds[];
+    float* tile = gl_lds;
+    float* info = gl_lds + GL_TILE_WORDS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long row0 = (long long)(blockIdx.x % (unsigned)tiles) * GL_ROWS, group = blockIdx.x / (unsigned)tiles;
+    const int live = gl_fill_tile(tile, info, q, nullptr, n, row0, tid);
+    const long long c0 = group * GL_GROUP + wave * 32;
+    if (c0 >= m) return;                                 // (behind the last barrier)
+    const f32x16 acc = gl_chain(tile, mat, (size_t)ld, c0, lane);
+    const int j = lane & 31, h = lane >> 5;
+    const long long col = c0 + j;
+    if (col >= m) return;
+    const float g2 = gn2[col], gs = __builtin_sqrtf(g2);
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int r = (i & 3) + 8 * (i >> 2) + 4 * h;
+        if (r < live) out[(size_t)(row0 + r) * (size_t)ldo + col] = gl_score(metric, acc[i], info[r], info[GL_ROWS + r], g2, gs);
+    }
+}
+
+// grid: x = strip * tiles + tile.  A workgroup walks column groups strip * gps .. (strip + 1) * gps - 1.  Each wave keeps its own
+// lists (two per row) and its own score stage: nothing crosses waves until the strip is done, so the group loop holds no barrier.
+// LDS: the tile, the row info, 4 stages of 32 x 33 words, 8 x 32 x k entries (93 KB at k = 5: one workgroup per CU).
+__global__ __launch_bounds__(256, 2) void k_gallery_search(const float* __restrict__ q, const uint8_t* __restrict__ valid, int n,
+                                                        const float* __restrict__ mat, long long ld, const float* __restrict__ gn2,
+                                                        long long m, int metric, int k, int tiles, long long gps, long long groups,
+                                                        TrlGlEntry* __restrict__ part, float* __restrict__ d_score,
+                                                        int32_t* __restrict__ d_index) {
+    extern __shared__ float gl_lds[];
+    float* tile = gl_lds;
+    float* info = gl_lds + GL_TILE_WORDS;
+    const int* rowok = reinterpret_cast<const int*>(info) + 2 * GL_ROWS;
+    float* stages = gl_lds + GL_TILE_WORDS + GL_INFO_WORDS;
+    TrlGlEntry* lists = reinterpret_cast<TrlGlEntry*>(stages + 4 * GL_STAGE_WORDS);              // (8-byte aligned: even word offset)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long row0 = (long long)(blockIdx.x % (unsigned)tiles) * GL_ROWS, strip = blockIdx.x / (unsigned)tiles;
+    float* stage = stages + wave * GL_STAGE_WORDS;
+    // lane l keeps the list of row l & 31 over columns 16 (l >> 5) .. + 15 of each of the wave's 32-column slabs
+    TrlGlEntry* mine = lists + ((wave * 2 + (lane >> 5)) * GL_ROWS + (lane & 31)) * k;
+    for (int e = 0; e < k; e++) mine[e] = trl_gl_empty();
+    const int live = gl_fill_tile(tile, info, q, valid, n, row0, tid);
+    const int j = lane & 31, h = lane >> 5;
+    const long long g_end = (strip + 1) * gps < groups ? (strip + 1) * gps : groups;
+    for (long long g = strip * gps; g < g_end; g++) {
+        const long long c0 = g * GL_GROUP + wave * 32;
+        if (c0 >= m) break;
+        const f32x16 acc = gl_chain(tile, mat, (size_t)ld, c0, lane);
+        const long long col = c0 + j;
+        const float g2 = gn2[col], gs = __builtin_sqrtf(g2);          // (col < ld: n2 has ld entries)
+        int h_here = h;                                               // (the 16 rows' LDS addresses are made here, not kept in
+        asm volatile("" : "+v"(h_here));                              // registers across the chain)
+        // the wave's 32 x 32 scores go through LDS, so that each lane can walk ONE row's scores against its own list: 64 lists
+        // are updated side by side, and after a strip's first groups a score is one LDS read and one comparison
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int r = (i & 3) + 8 * (i >> 2) + 4 * h_here;
+            stage[r * 33 + j] = gl_score(metric, acc[i], info[r], info[GL_ROWS + r], g2, gs);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");        // (wave-private data: the fence orders the wave's own LDS traffic)
+        __builtin_amdgcn_wave_barrier();
+        if (rowok[j]) {
+            const float* sr = stage + j * 33 + 16 * h_here;
+            const long long cb = c0 + 16 * h_here;
+            TrlGlEntry last = mine[k - 1];
+            for (int c = 0; c < 16 && cb + c < m; c++) {
+                const float sc = sr[c];
+                if (trl_gl_before(metric, sc, (int32_t)(cb + c), last.score, last.index)) {
+                    trl_gl_insert(mine, k, metric, sc, (int32_t)(cb + c));
+                    last = mine[k - 1];
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");        // the next group's scores follow these reads
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    if (tid < live) {
+        TrlGlEntry* L = lists + tid * k;                 // the row's first list takes the other seven
+        trl_gl_merge(L, k, metric, L + GL_ROWS * k, GL_LISTS - 1, (long long)GL_ROWS * k);
+        const size_t row = (size_t)(row0 + tid);
+        if (part) {
+            TrlGlEntry* o = part + ((size_t)strip * (size_t)n + row) * (size_t)k;
+            for (int e = 0; e < k; e++) o[e] = L[e];
+        } else {
+            for (int e = 0; e < k; e++) {
+                d_score[row * k + e] = L[e].score;
+                d_index[row * k + e] = L[e].index == TRL_GL_EMPTY ? -1 : L[e].index;
+            }
+        }
+    }
+}
+
+// one wave per query row: lane l merges strips l, l + 64, ... into a list of its own (a strip's k entries are loaded before they
+// are looked at: independent loads), then lane 0 merges the 64 lists -- all with the code the search kernel uses
+__global__ __launch_bounds__(64) void k_gallery_merge(const TrlGlEntry* __restrict__ part, int n, long long strips, int k, int metric,
+                                                      float* __restrict__ d_score, int32_t* __restrict__ d_index) {
+    __shared__ TrlGlEntry best[64 * TRL_GL_MAX_K];
+    const int lane = threadIdx.x;
+    const size_t row = blockIdx.x;
+    TrlGlEntry* mine = best + lane * k;
+    for (int e = 0; e < k; e++) mine[e] = trl_gl_empty();
+    for (long long s = lane; s < strips; s += 64) {
+        const TrlGlEntry* src = part + ((size_t)s * (size_t)n + row) * (size_t)k;
+        TrlGlEntry v[TRL_GL_MAX_K];
+#pragma unroll
+        for (int e = 0; e < TRL_GL_MAX_K; e++) v[e] = e < k ? src[e] : trl_gl_empty();
+#pragma unroll
+        for (int e = 0; e < TRL_GL_MAX_K; e++)
+            if (e < k) trl_gl_insert(mine, k, metric, v[e].score, v[e].index);
+    }
+    __syncthreads();
+    if (lane == 0) trl_gl_merge(best, k, metric, best + k, 63, k);
+    __syncthreads();
+    if (lane < k) {
+        d_score[row * k + lane] = best[lane].score;
+        d_index[row * k + lane] = best[lane].index == TRL_GL_EMPTY ? -1 : best[lane].index;
+    }
+}
+
+__global__ void k_gallery_fill(float* __restrict__ d_score, int32_t* __restrict__ d_index, long long count) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t < count) {
+        d_score[t] = __builtin_nanf("");
+        d_index[t] = -1;
+    }
+}
+
+// rows [m][512] -> columns c0 .. c0 + m - 1 of mat [512][ld] and n2[c0 ..]: a workgroup takes 32 rows through a [32][64] LDS tile
+// eight times (reads: 256 bytes of a row per 64 lanes; writes: 128 bytes of a k-row per 32 lanes), thread r < 32 carrying row r's
+// n2 chain across the eight tiles in ascending k.
+__global__ __launch_bounds__(256) void k_gallery_pack(const float* __restrict__ rows, long long m, float* __restrict__ mat, long long ld,
+                                                      float* __restrict__ n2, long long c0) {
+    __shared__ float t[GL_ROWS][65];
+    const int tid = threadIdx.x;
+    const long long row0 = (long long)blockIdx.x * GL_ROWS;
+    const int live = m - row0 < GL_ROWS ? (int)(m - row0) : GL_ROWS;
+    float acc = 0.f;
+    for (int k0 = 0; k0 < GL_K; k0 += 64) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int e = tid + 256 * i, r = e >> 6, kk = e & 63;
+            t[r][kk] = r < live ? rows[(size_t)(row0 + r) * GL_K + k0 + kk] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int e = tid + 256 * i, kk = e >> 5, r = e & 31;
+            if (r < live) mat[(size_t)(k0 + kk) * (size_t)ld + (size_t)(c0 + row0 + r)] = t[r][kk];
+        }
+        if (tid < GL_ROWS) {
+#pragma unroll 16
+            for (int kk = 0; kk < 64; kk++) acc = __builtin_fmaf(t[tid][kk], t[tid][kk], acc);
+        }
+        __syncthreads();
+    }
+    if (tid < live) n2[c0 + row0 + tid] = acc;
+}
+
+// ---- the search's plan and workspace, written once: trl_gallery_search_workspace is a dry run of gl_carve -------------------------
+struct GlPlan {
+    long long tiles = 0, groups = 0, gps = 0, strips = 0;
+};
+
+const char* gl_plan(int n, long long m, int k, int max_strip_cols, GlPlan* p) {
+    if (n < 0 || m < 0 || m > 0x7fffffffLL) return "n or m out of range (n >= 0, 0 <= m <= 2^31 - 1)";
+    if (k < 1 || k > TRL_GL_MAX_K) return "k outside 1..16";
+    if (max_strip_cols < 0 || max_strip_cols % GL_GROUP) return "max_strip_cols is not a multiple of 128";
+    *p = GlPlan();
+    if (n == 0 || m == 0) return nullptr;
+    p->tiles = (n + GL_ROWS - 1) / GL_ROWS;
+    p->groups = (m + GL_GROUP - 1) / GL_GROUP;
+    long long want = std::max<long long>(1, GL_TARGET_WGS / p->tiles);
+    want = std::min<long long>(want, std::min<long long>(GL_MAX_STRIPS, p->groups));
+    p->gps = (p->groups + want - 1) / want;
+    if (max_strip_cols > 0) p->gps = std::min<long long>(p->gps, max_strip_cols / GL_GROUP);
+    p->strips = (p->groups + p->gps - 1) / p->gps;
+    if (p->strips * p->tiles > 0x7fffffffLL) return "too many workgroups: raise max_strip_cols";
+    return nullptr;
+}
+
+// the strips' lists [strips][n][k]; none when one strip writes the result itself
+bool gl_carve(Arena& a, const GlPlan& p, int n, int k, TrlGlEntry** part) {
+    *part = nullptr;
+    if (p.strips > 1) {
+        *part = (TrlGlEntry*)a.alloc((size_t)p.strips * (size_t)n * (size_t)k * sizeof(TrlGlEntry));
+        if (!*part) return false;
+    }
+    return true;
+}
+
+int gl_device_of(const void* p) {
+    hipPointerAttribute_t attr;
+    TRL_HIP(hipPointerGetAttributes(&attr, p));
+    TRL_HIP(hipSetDevice(attr.device));
+    return TRL_OK;
+}
+
+const char* gl_check_gallery(const float* d_mat, long long ld, const float* d_n2, long long m) {
+    if (!d_mat || !d_n2) return "null gallery";
+    if (ld <= 0 || ld % 32) return "ld is not a positive multiple of 32";
+    if (m > ld) return "m > ld";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" int trl_gallery_pack(const float* d_rows, long long m, float* d_mat, long long ld, float* d_n2, long long c0, void* stream) {
+    if (m < 0 || c0 < 0 || m > 0x7fffffffLL) { trl_set_error("trl_gallery_pack: m = %lld rows at column %lld", m, c0); return TRL_ERR_INVALID; }
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, 0)) { trl_set_error("trl_gallery_pack: %s", why); return TRL_ERR_INVALID; }
+    if (c0 + m > ld) { trl_set_error("trl_gallery_pack: columns %lld..%lld of %lld", c0, c0 + m, ld); return TRL_ERR_INVALID; }
+    if (m == 0) return TRL_OK;
+    if (!d_rows) { trl_set_error("trl_gallery_pack: null rows"); return TRL_ERR_INVALID; }
+    TRL_CHECK(gl_device_of(d_mat));
+    k_gallery_pack<<<(unsigned)((m + GL_ROWS - 1) / GL_ROWS), 256, 0, (hipStream_t)stream>>>(d_rows, m, d_mat, ld, d_n2, c0);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
+extern "C" int trl_gallery_scores(const float* d_q, int n, const float* d_mat, long long ld, const float* d_n2, long long m, int metric,
+                                  float* d_out, long long ldo, void* stream) {
+    if (n < 0 || m < 0 || m > 0x7fffffffLL) { trl_set_error("trl_gallery_scores: n = %d, m = %lld", n, m); return TRL_ERR_INVALID; }
+    if (metric != TRL_GL_COSINE && metric != TRL_GL_EUCLIDEAN) { trl_set_error("trl_gallery_scores: metric %d (0 cosine, 1 euclidean)", metric); return TRL_ERR_INVALID; }
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) { trl_set_error("trl_gallery_scores: %s", why); return TRL_ERR_INVALID; }
+    if (ldo < m) { trl_set_error("trl_gallery_scores: ldo = %lld < m = %lld", ldo, m); return TRL_ERR_INVALID; }
+    if (n == 0 || m == 0) return TRL_OK;
+    if (!d_q || !d_out) { trl_set_error("trl_gallery_scores: null argument"); return TRL_ERR_INVALID; }
+    const long long tiles = (n + GL_ROWS - 1) / GL_ROWS, groups = (m + GL_GROUP - 1) / GL_GROUP;
+    if (tiles * groups > 0x7fffffffLL) { trl_set_error("trl_gallery_scores: %lld x %lld workgroups", tiles, groups); return TRL_ERR_INVALID; }
+    TRL_CHECK(gl_device_of(d_mat));
+    const int lds = (GL_TILE_WORDS + GL_INFO_WORDS) * 4;
+    TRL_HIP(hipFuncSetAttribute((const void*)k_gallery_scores, hipFuncAttributeMaxDynamicSharedMemorySize, lds));   // above the default 64 KB
+    k_gallery_scores<<<(unsigned)(tiles * groups), 256, lds, (hipStream_t)stream>>>(d_q, n, d_mat, ld, d_n2, m, metric, d_out, ldo, (int)tiles);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
+extern "C" size_t trl_gallery_search_workspace(int n, long long m, int k, int max_strip_cols) {
+    GlPlan p;
+    if (gl_plan(n, m, k, max_strip_cols, &p)) return 0;
+    Arena a = Arena::counter();
+    TrlGlEntry* part;
+    gl_carve(a, p, n, k, &part);
+    return a.high;
+}
+
+extern "C" int trl_gallery_search(const float* d_q, const uint8_t* d_valid, int n, const float* d_mat, long long ld, const float* d_n2,
+                                  long long m, int metric, int k, float* d_score, int32_t* d_index, void* d_ws, size_t ws_bytes,
+                                  int max_strip_cols, void* stream) {
+    GlPlan p;
+    if (const char* why = gl_plan(n, m, k, max_strip_cols, &p)) { trl_set_error("trl_gallery_search: %s", why); return TRL_ERR_INVALID; }
+    if (metric != TRL_GL_COSINE && metric != TRL_GL_EUCLIDEAN) { trl_set_error("trl_gallery_search: metric %d (0 cosine, 1 euclidean)", metric); return TRL_ERR_INVALID; }
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) { trl_set_error("trl_gallery_search: %s", why); return TRL_ERR_INVALID; }
+    if (n == 0) return TRL_OK;
+    if (!d_q || !d_score || !d_index) { trl_set_error("trl_gallery_search: null argument"); return TRL_ERR_INVALID; }
+    Arena a;
+    a.base = (char*)d_ws;
+    a.cap = d_ws ? ws_bytes : 0;
+    TrlGlEntry* part;
+    if (((uintptr_t)d_ws & 7) || !gl_carve(a, p, n, k, &part)) {
+        trl_set_error("trl_gallery_search: workspace of %zu bytes (need %zu, 8-byte aligned)", ws_bytes, trl_gallery_search_workspace(n, m, k, max_strip_cols));
+        return TRL_ERR_INVALID;
+    }
+    TRL_CHECK(gl_device_of(d_mat));
+    hipStream_t s = (hipStream_t)stream;
+    if (m == 0) {
+        const long long count = (long long)n * k;
+        k_gallery_fill<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(d_score, d_index, count);
+        TRL_LAUNCH_CHECK();
+        return TRL_OK;
+    }
+    const int lds = (GL_TILE_WORDS + GL_INFO_WORDS + 4 * GL_STAGE_WORDS) * 4 + GL_LISTS * GL_ROWS * k * (int)sizeof(TrlGlEntry);
+    TRL_HIP(hipFuncSetAttribute((const void*)k_gallery_search, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    k_gallery_search<<<(unsigned)(p.strips * p.tiles), 256, lds, s>>>(d_q, d_valid, n, d_mat, ld, d_n2, m, metric, k, (int)p.tiles, p.gps,
+                                                                     p.groups, part, d_score, d_index);
+    TRL_LAUNCH_CHECK();
+    if (part) {
+        k_gallery_merge<<<(unsigned)n, 64, 0, s>>>(part, n, p.strips, k, metric, d_score, d_index);
+        TRL_LAUNCH_CHECK();
+    }
+    return TRL_OK;
+}

@@ -1016,7 +1016,8 @@ int trl_debug_list_stats(trl_ctx* c, long long* h_out8) {
 
 // test hooks of the shipped library (it reads no environment variable): "rnet_chunk" / "onet_chunk" = candidates per R-/O-Net
 // launch set of this context (>= 16), "no_fnconv" = process-wide: FaceNet's small maps through the generic conv kernels,
-// "pyr_row_bands" = row bands of the streaming pyramid pass of this context (0 = the pass's own policy)
+// "pyr_row_bands" = row bands of the streaming pyramid pass of this context (0 = the pass's own policy), "tail_pool" = 1 (default):
+// the R-/O-Net tail pools run in their conv's epilogue where one exists, 0: every pool is its own launch (the same bits)
 int trl_debug_option(trl_ctx* c, const char* key, int value) {
     if (!key) { trl_set_error("null key"); return TRL_ERR_INVALID; }
     if (!strcmp(key, "no_fnconv")) { g_trl_no_fnconv = value ? 1 : 0; return TRL_OK; }
@@ -1026,6 +1027,7 @@ int trl_debug_option(trl_ctx* c, const char* key, int value) {
     if (!strcmp(key, "onet_chunk") && value >= 16) { c->onet_chunk = value; return TRL_OK; }
     if (!strcmp(key, "pnet_screen") && (value == 0 || value == 1)) { c->pnet_screen = value; return TRL_OK; }
     if (!strcmp(key, "pyr_row_bands") && value >= 0) { c->pyr_row_bands = value; return TRL_OK; }
+    if (!strcmp(key, "tail_pool") && (value == 0 || value == 1)) { c->tail_pool = value; return TRL_OK; }
     trl_set_error("unknown option '%s' (or value %d out of range)", key, value);
     return TRL_ERR_INVALID;
 }

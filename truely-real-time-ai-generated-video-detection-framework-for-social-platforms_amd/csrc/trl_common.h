@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/truely_hip.h"
+#include "trl_tailpool.h"
 
 // ---- error plumbing --------------------------------------------------------------------------
 void trl_set_error(const char* fmt, ...);
@@ -89,6 +90,15 @@ struct ConvArgs {
     int lowp = 0;                 // 1 / 2: x, y, res are bf16 / fp16 and the weights come from wt (conv_bf16, FaceNet only)
     const uint16_t* wt = nullptr; int ldwt = 0;
 };
+
+// A conv whose ceil-mode pk x pk / pst max pool runs in its own epilogue (trl_tailpool.h): y / ldy / yoff describe the POOLED map
+// [N][P][P][Cout] and OH / OW stay the conv's output size, which is never stored.  side: a buffer shaped like the pooled map for the
+// second parts of windows that meet a tile boundary (null where none can).
+struct ConvPoolArgs : ConvArgs {
+    float* side = nullptr;
+    int pk = 0, pst = 0;
+};
+enum { TRL_TAIL_POOL_BM = 128 };   // rows per tile of the two kernels that have the pooling epilogue
 
 // bump allocator over one device allocation.  Every workspace is sized by a dry run of the code that carves it over a COUNTING arena
 // (no base, never full, the same alignment): code handed one launches nothing and does not dereference what alloc returns (a token).
@@ -175,6 +185,11 @@ int trl_launch_fn_group(const ConvArgs* convs, int nz, hipStream_t s);     // 1.
 int trl_launch_maxpool(const float* x, int N, int H, int W, int C, int ldx, int xoff, int k, int st,
                        int ceil_mode, float* y, int ldy, int yoff, int OH, int OW, hipStream_t s,
                        const int32_t* n_dev = nullptr, int n_base = 0);
+// conv + the pool behind it in one launch (+ the fix-up of the cells two tiles share).  trl_conv_pool_family: the TRL_FNK_* family
+// trl_launch_conv picks for this conv when that family has a pooling epilogue for this pool, else 0 -- from shapes alone (a dry run
+// asks too: x and y need not point anywhere).  trl_launch_conv_pool records the plan row trl_launch_conv would.
+int trl_conv_pool_family(const ConvArgs& a, int pk, int pst);
+int trl_launch_conv_pool(const ConvPoolArgs& a, hipStream_t s);
 int trl_launch_gap(const float* x, int N, int HW, int C, float* y, hipStream_t s);
 // reduced-precision embedder (trl_bf16.hip)
 int trl_launch_conv_bf16(const ConvArgs& a, hipStream_t s);

@@ -9,6 +9,7 @@
 // as a callable, not as a value (conv_store).
 #pragma once
 #include "trl_ctx.h"
+#include "trl_tailpool.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -120,6 +121,54 @@ __device__ __forceinline__ int conv_yskip(const ConvArgs& a, int n) { return n >
 // (the tile's first row goes in, not on top: the sum keeps the association the kernels' address arithmetic was tuned with)
 __device__ __forceinline__ int mfma32_row(int row0, int i, int h) { return row0 + (i & 3) + 8 * (i >> 2) + 4 * h; }   // 32x32: i < 16, h = lane >> 5
 __device__ __forceinline__ int mfma16_row(int row0, int q, int kq) { return row0 + kq * 4 + q; }                      // 16x16: q < 4, kq = lane >> 4
+
+// ---- the pooling epilogue of conv_tap / conv_tap48 (geometry and the part / side / fix-up scheme: trl_tailpool.h) -----------------
+// The kernels' POOL template flag is 0 (store the map) or the pooled layer's geometry: the row <-> cell arithmetic is then
+// constants, multiplications and shifts -- with S, k and st in registers each cell costs integer divisions on the pipe the MFMAs
+// use, more than its nine comparisons.
+constexpr int conv_pool_flag(int S, int k, int st) { return (S << 8) | (k << 4) | st; }
+template <int POOL, int BM> constexpr TailPool conv_pool_geom() { return TailPool{POOL >> 8, (POOL >> 4) & 15, POOL & 15, BM}; }
+template <int POOL> struct ConvArgsOf { typedef ConvPoolArgs type; };
+template <> struct ConvArgsOf<0> { typedef ConvArgs type; };
+// what trl_conv_pool_family admits -- bias + PReLU, no folded BN, no residual -- said to the compiler, so that conv_finish in the
+// epilogue is its PReLU expression and no test of the layer's options per accumulator
+__device__ __forceinline__ void conv_pool_assume(const ConvArgs& a) {
+    __builtin_assume(a.scale == nullptr);
+    __builtin_assume(a.res == nullptr);
+    __builtin_assume(a.act == TRL_ACT_PRELU);
+}
+// One pass: T holds columns nbase .. nbase + PWC - 1 of the finished tile, [BM][PWC].  A thread takes four channels of a cell the
+// tile touches and reduces the window elements that lie in the tile, in maxpool_kernel's order and with its comparison.
+template <int POOL, int BM, int PWC>
+__device__ __forceinline__ void conv_pool_pass(const ConvPoolArgs& a, const float* T, int m0, int nbase, int tid) {
+    constexpr TailPool tp = conv_pool_geom<POOL, BM>();
+    constexpr int G = PWC / 4;                            // float4 groups per cell
+    static_assert(tp.ok() && PWC % 4 == 0 && 256 % G == 0, "pooling epilogue geometry");
+    const int t = m0 / BM;
+    const int gend = (a.M / tp.per()) * tp.cells();       // cells of the launch
+    const int g0 = tp.tile_cell0(t);
+    int g1 = tp.tile_cell1(t);
+    g1 = g1 < gend ? g1 : gend;
+    const int c4 = tid % G;
+#pragma unroll 1
+    for (int g = g0 + tid / G; g < g1; g += 256 / G) {
+        const int f = tp.first_row(g) - m0;               // tile row of the window's first element; < 0: it lies in the tile before
+        f32x4 best = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+#pragma unroll
+        for (int ky = 0; ky < tp.k; ky++)
+#pragma unroll
+            for (int kx = 0; kx < tp.k; kx++) {
+                const int lr = f + ky * tp.S + kx;
+                if ((unsigned)lr < (unsigned)BM) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(T + lr * PWC + 4 * c4);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) best[j] = v[j] > best[j] ? v[j] : best[j];
+                }
+            }
+        float* dst = (f < 0 ? a.side : a.y) + ((size_t)g * a.ldy + a.yoff + nbase + 4 * c4);
+        *reinterpret_cast<f32x4*>(dst) = best;
+    }
+}
 
 // ---- the four-chain tail of conv_splitk4 / conv_splitk4_tap ---------------------------------------------------------------
 // Wave w holds chain w's partial 32x64 tile (two 32x32 accumulators).  Partials to LDS as [wave][tn][reg][lane] (8,192 floats),

@@ -97,6 +97,7 @@ struct trl_ctx {
     // by them, and a call that overflows one is re-run with a larger value (trl_capacity.h)
     CascadeCaps caps;
     int rnet_chunk = 49152, onet_chunk = 16384;   // R-/O-Net candidates per launch set (trl_cascade.hip; trl_debug_option shrinks them for tests)
+    int tail_pool = 1;               // trl_debug_option "tail_pool": 0 = every R-/O-Net tail pool is its own launch (trl_run_net)
     int nms_small = 512, nms_full = 2048;   // LDS tiers of the sort + NMS kernels (candidates); longer lists take the spill tier
                                             // (trl_debug_nms_tiers lowers them so that small test inputs reach every tier)
     size_t scratch_after_cascade = 0;   // scratch bytes the rest of the call needs (crops + FaceNet): sized with the cascade's

@@ -322,8 +322,10 @@ __global__ __launch_bounds__(256) void conv_splitk4_tap(ConvArgs a) {
 // per-slot cursors and bounds tests; f32 MFMA and VALU share the FP32 pipe on gfx950, so that was ~30 % of the
 // loop.  Here it is ~20.  Same k order, same bias-seeded chain: bit-identical results.
 // PAD = the layer has spatial padding (taps falling outside the image load nothing and contribute zeros).
-template <int BM, int BN, int WM, int WN, int BK, bool PAD>
-__global__ __launch_bounds__(256) void conv_tap(ConvArgs a) {
+// POOL != 0 (conv_pool_flag: the geometry of the max pool behind the layer): the map is not stored -- the finished tile is staged in
+// LDS, 32 columns at a time over the dead A operand buffer, and the part of every pooling window that lies in this tile is reduced there (trl_tailpool.h).
+template <int BM, int BN, int WM, int WN, int BK, bool PAD, int POOL = 0>
+__global__ __launch_bounds__(256) void conv_tap(typename ConvArgsOf<POOL>::type a) {
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int KG = BK / 4;                                   // float4 groups along k per chunk
     constexpr int ASLOTS = BM * KG, APT = (ASLOTS + 255) / 256;
@@ -431,6 +433,25 @@ __global__ __launch_bounds__(256) void conv_tap(ConvArgs a) {
         __syncthreads();
     }
 
+    // ---- pooling epilogue: bias + PReLU as conv_finish does, then one 32-column half of the tile at a time ------------------------
+    if constexpr (POOL != 0) {
+        static_assert(TN == 1 && BM * 32 <= BM * LDA, "a [BM][32] half tile fits the A buffer");
+        conv_pool_assume(a);
+        const ConvCol col = conv_col(a, n0 + wn * 32 + r);
+        for (int p = 0; p < WN; p++) {
+            if (wn == p) {
+#pragma unroll
+                for (int tm = 0; tm < TM; tm++)
+#pragma unroll
+                    for (int i = 0; i < 16; i++) As[mfma32_row((wm * TM + tm) * 32, i, h) * 32 + r] = conv_finish(a, col, acc[tm][0][i], 0.f);
+            }
+            __syncthreads();
+            conv_pool_pass<POOL, BM, 32>(a, As, m0, n0 + p * 32, tid);
+            __syncthreads();
+        }
+        return;
+    }
+
     // ---- epilogue ------------------------------------------------------------------------------
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
@@ -452,8 +473,9 @@ __global__ __launch_bounds__(256) void conv_tap(ConvArgs a) {
 // v_mfma_f32_16x16x4_f32 -- three 16-column tiles instead of two 32-column ones, so no MFMA cycle is spent on the 16 padding
 // columns a 64-wide tile would carry (25 % of that layer).  Same LDS layout ([k][m], [k][n]) and loader as conv_tap; each of the
 // 4 waves owns 32 rows = 2 x 3 accumulator tiles; k = 4s + (lane >> 4) ascending, bias-seeded: the oracle's chain.
-template <int BK, bool PAD>
-__global__ __launch_bounds__(256) void conv_tap48(ConvArgs a) {
+// POOL: as conv_tap's, 16 columns (one accumulator tile column) at a time.
+template <int BK, bool PAD, int POOL = 0>
+__global__ __launch_bounds__(256) void conv_tap48(typename ConvArgsOf<POOL>::type a) {
     constexpr int BM = 128, BN = 48;
     constexpr int KG = BK / 4;
     constexpr int ASLOTS = BM * KG, APT = (ASLOTS + 255) / 256;
@@ -560,6 +582,23 @@ __global__ __launch_bounds__(256) void conv_tap48(ConvArgs a) {
         __syncthreads();
     }
 
+    if constexpr (POOL != 0) {
+        static_assert(BM * 16 <= BK * BM, "a [BM][16] tile column fits the A buffer");
+        conv_pool_assume(a);
+#pragma unroll
+        for (int tn = 0; tn < 3; tn++) {
+            const ConvCol col = conv_col(a, tn * 16 + l15);
+#pragma unroll
+            for (int tm = 0; tm < 2; tm++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) As[mfma16_row(wave * 32 + tm * 16, q, kq) * 16 + l15] = conv_finish(a, col, acc[tm][tn][q], 0.f);
+            __syncthreads();
+            conv_pool_pass<POOL, BM, 16>(a, As, m0, tn * 16, tid);
+            __syncthreads();
+        }
+        return;
+    }
+
 #pragma unroll
     for (int tn = 0; tn < 3; tn++) {
         const int n = tn * 16 + l15;
@@ -642,6 +681,29 @@ __global__ void maxpool_kernel(const float* __restrict__ x, int N, int H, int W,
         float* q = y + (((size_t)n * OH + oy) * OW + ox) * ldy + yoff + c;
         if (V == 4) *reinterpret_cast<float4*>(q) = make_float4(best[0], best[1 % V], best[2 % V], best[3 % V]);
         else q[0] = best[0];
+    }
+}
+
+// The fix-up behind a pooling epilogue: block b - 1 takes the cells cut by the boundary in front of tile b, whose second part lies in
+// `side`, and finishes them: pooled = side > pooled ? side : pooled (the scan's own comparison, trl_tailpool.h).  Boundaries at or
+// past the live rows have no cell of a live candidate.
+__global__ __launch_bounds__(128) void pool_fixup_kernel(float* __restrict__ y, const float* __restrict__ side, int ld, int yoff, int C,
+                                                          TailPool tp, int N, const int32_t* __restrict__ n_dev, int n_base) {
+    if (n_dev) {   // device-sized batch, as maxpool_kernel
+        int t = *n_dev - n_base;
+        N = t < 0 ? 0 : (t > N ? N : t);
+    }
+    const int b = blockIdx.x + 1;
+    if ((long long)b * tp.BM >= (long long)N * tp.per()) return;
+    const int g0 = tp.cut_cell0(b), gend = N * tp.cells();
+    int g1 = tp.cut_cell1(b);
+    g1 = g1 < gend ? g1 : gend;
+    const int G = C / 4;
+    for (int w = threadIdx.x; w < (g1 - g0) * G; w += blockDim.x) {
+        const int g = g0 + w / G, c4 = w - (w / G) * G;
+        const size_t e = (size_t)g * ld + yoff + 4 * c4;
+        const float4 A = *reinterpret_cast<const float4*>(y + e), B = *reinterpret_cast<const float4*>(side + e);
+        *reinterpret_cast<float4*>(y + e) = make_float4(B.x > A.x ? B.x : A.x, B.y > A.y ? B.y : A.y, B.z > A.z ? B.z : A.z, B.w > A.w ? B.w : A.w);
     }
 }
 
@@ -799,6 +861,44 @@ int trl_launch_conv(const ConvArgs& a, hipStream_t s) {
     if (a.M >= 16384) return deep ? launch_cfg<128, 64, 2, 2, 32>(a, vec, s) : launch_cfg<128, 64, 2, 2, 16>(a, vec, s);
     if (a.M >= 1024) return deep ? launch_cfg<64, 64, 2, 2, 64>(a, vec, s) : launch_cfg<64, 64, 2, 2, 16>(a, vec, s);
     return deep ? launch_cfg<32, 128, 1, 4, 64>(a, vec, s) : launch_cfg<32, 128, 1, 4, 16>(a, vec, s);
+}
+
+// ---- conv + pool in one launch ---------------------------------------------------------------------------------------------------
+// The conditions under which trl_launch_conv above reaches conv_tap<128,64,2,2,32,false> or conv_tap48<28,false>, restated on
+// shapes (the scratch is 256-byte aligned; trl_launch_conv_pool refuses a misaligned x), and the pools those have an epilogue for.
+int trl_conv_pool_family(const ConvArgs& a, int pk, int pst) {
+    if (a.M < 16384 || a.M > (1 << 30) || a.OH != a.OW || a.M != a.N * a.OH * a.OW || a.ph || a.pw || a.lowp) return 0;
+    if (a.res || a.scale || a.act != TRL_ACT_PRELU) return 0;      // bias + PReLU only (conv_pool_assume)
+    if (a.Cin % 4 || a.ldx % 4 || a.xoff % 4 || !trl_conv_small(a) || trl_fn_split4_rule(a)) return 0;
+    if (!a.m_dev && a.M == 16384) return 0;                        // (may be the small-map family's)
+    if (a.ldy != a.Cout || a.yoff) return 0;                       // the pooled map and the side buffer are dense
+    if (!TailPool{a.OH, pk, pst, TRL_TAIL_POOL_BM}.ok()) return 0;
+    const int flag = conv_pool_flag(a.OH, pk, pst);
+    if (a.Cout == 48 && a.ldw >= 48 && a.Cin % 32 != 0 && a.Cin % 28 == 0) return flag == conv_pool_flag(9, 3, 2) ? TRL_FNK_TAP48 : 0;
+    if (a.Cout == 64 && a.ldw >= 64 && a.K >= 192 && a.Cin % 32 == 0)
+        return flag == conv_pool_flag(21, 3, 2) || flag == conv_pool_flag(8, 2, 2) ? TRL_FNK_CONV_TAP : 0;
+    return 0;
+}
+
+int trl_launch_conv_pool(const ConvPoolArgs& a, hipStream_t s) {
+    const int family = trl_conv_pool_family(a, a.pk, a.pst);
+    const TailPool tp{a.OH, a.pk, a.pst, TRL_TAIL_POOL_BM};
+    if (!family || !trl_conv_vec(a) || trl_fn_eligible(a) || (((uintptr_t)a.y | (uintptr_t)a.side) & 15) || (tp.can_straddle() && !a.side)) {
+        trl_set_error("conv + pool launch on a layer without a pooling epilogue");
+        return TRL_ERR_STATE;
+    }
+    const dim3 grid((a.M + 127) / 128, 1);
+    const int flag = conv_pool_flag(a.OH, a.pk, a.pst);
+    g_trl_conv_choice = TrlConvChoice{family, 128, family == TRL_FNK_TAP48 ? 48 : 64, family == TRL_FNK_TAP48 ? 28 : 32, 0, 1};
+    if (family == TRL_FNK_TAP48) conv_tap48<28, false, conv_pool_flag(9, 3, 2)><<<grid, 256, 0, s>>>(a);
+    else if (flag == conv_pool_flag(21, 3, 2)) conv_tap<128, 64, 2, 2, 32, false, conv_pool_flag(21, 3, 2)><<<grid, 256, 0, s>>>(a);
+    else conv_tap<128, 64, 2, 2, 32, false, conv_pool_flag(8, 2, 2)><<<grid, 256, 0, s>>>(a);
+    TRL_LAUNCH_CHECK();
+    if (tp.can_straddle() && grid.x > 1) {
+        pool_fixup_kernel<<<grid.x - 1, 128, 0, s>>>(a.y, a.side, a.ldy, a.yoff, a.Cout, tp, a.N, a.m_dev, a.m_base);
+        TRL_LAUNCH_CHECK();
+    }
+    return TRL_OK;
 }
 
 int trl_launch_maxpool(const float* x, int N, int H, int W, int C, int ldx, int xoff, int k, int st, int ceil_mode,

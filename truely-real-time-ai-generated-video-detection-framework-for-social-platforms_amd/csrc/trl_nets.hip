@@ -184,6 +184,37 @@ struct Runner {
         else launched(a, meta);
         return y;
     }
+    // A valid k x k conv (bias, PReLU) of the MTCNN tails and the ceil-mode pk / pst max pool behind it as ONE launch, where the
+    // kernel the dispatch picks for the conv has a pooling epilogue for that pool (trl_conv_pool_family): *out = the pooled map; the
+    // conv's own map does not exist.  false: not taken, nothing done -- the caller issues conv and pool.
+    bool conv_pool(const Act& x, const NetLayerW& lw, int k, int act, int pk, int pst, Act* out) {
+        const DevW* w = lw.w;
+        if (err != TRL_OK || !w || x.bf || x.h != x.w || w->K != k * k * x.c) return false;
+        const int S = x.h - k + 1;
+        ConvPoolArgs a;
+        a.x = x.p; a.N = x.n; a.H = x.h; a.W = x.w; a.Cin = x.c; a.ldx = x.ld; a.xoff = x.coff;
+        a.w = w->p; a.ldw = w->ld; a.K = w->K;
+        a.bias = lw.b; a.scale = nullptr; a.shift = nullptr; a.slope = lw.slope;
+        a.res = nullptr; a.ldres = 0; a.res_scale = 0.f;
+        a.y = nullptr; a.ldy = w->Cout; a.yoff = 0;
+        a.KH = k; a.KW = k; a.sh = 1; a.sw = 1; a.ph = 0; a.pw = 0;
+        a.Cout = w->Cout; a.OH = S; a.OW = S; a.act = act;
+        a.M = x.n * S * S;
+        a.m_dev = m_dev; a.m_base = m_base; a.m_per = S * S;
+        a.pk = pk; a.pst = pst;
+        if (S < pk || (long long)x.n * S * S > (1 << 30) || !trl_conv_pool_family(a, pk, pst)) return false;
+        const TailPool tp{S, pk, pst, TRL_TAIL_POOL_BM};
+        const Act y = alloc(x.n, tp.P(), tp.P(), w->Cout);
+        const Act side = tp.can_straddle() ? alloc(x.n, tp.P(), tp.P(), w->Cout) : Act();   // second parts of windows two tiles share
+        *out = y;
+        if (err != TRL_OK || check_only) return true;
+        a.y = y.p; a.side = side.p;
+        ConvMeta meta{nconv++, layer, x, y, false, Act()};
+        const int st = trl_launch_conv_pool(a, s);
+        if (st != TRL_OK) err = st;
+        else launched(a, meta);
+        return true;
+    }
     // BasicConv2d: conv(no bias) + folded BN + ReLU
     Act bconv(const Act& x, const std::string& name, int kh, int kw, int sh, int sw, int ph, int pw, const Act* into = nullptr) {
         if (plan) layer = name;
@@ -349,6 +380,13 @@ int trl_run_net(trl_ctx* c, Arena& X, const NetDesc& d, int first, const Act& x0
         const NetLayer& L = d.layer[i];
         if (!L.name) { x = R.pool(x, L.k, L.st, 1); continue; }
         if (R.plan) R.layer = std::string(d.name) + "." + L.name;
+        // a pool directly behind the conv runs in the conv's epilogue where the kernel has one: the 128-row tiles of R-Net conv2 and
+        // O-Net conv2 / conv3 at production capacities (smaller launches, PNet and every other pool: separate launches as below)
+        if (c->tail_pool && i + 2 < d.nl && !d.layer[i + 1].name &&
+            R.conv_pool(x, lw[i], L.k, L.prelu ? TRL_ACT_PRELU : TRL_ACT_NONE, d.layer[i + 1].k, d.layer[i + 1].st, &x)) {
+            i++;
+            continue;
+        }
         const Act out = Act::dense(d_out, x.n, x.h - L.k + 1, x.w - L.k + 1, d.nout);
         x = R.conv(x, lw[i].w, lw[i].b, nullptr, nullptr, lw[i].slope, L.k, L.k, 1, 1, 0, 0, L.prelu ? TRL_ACT_PRELU : TRL_ACT_NONE,
                    i == d.nl - 1 ? &out : nullptr, nullptr, 0.f);

@@ -462,8 +462,8 @@ class Engine:
         return k.value
 
     def option(self, key: str, value: int):
-        """Test hook (``trl_debug_option``): "rnet_chunk" / "onet_chunk" / "pnet_screen" / "pyr_row_bands" (this context), "no_fnconv"
-        (process-wide)."""
+        """Test hook (``trl_debug_option``): "rnet_chunk" / "onet_chunk" / "pnet_screen" / "pyr_row_bands" / "tail_pool" (this
+        context), "no_fnconv" (process-wide)."""
         _lib.check(self.lib.trl_debug_option(self._h, key.encode(), int(value)))
 
     def nms_tiers(self, small: int = 0, full: int = 0):

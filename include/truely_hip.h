@@ -522,6 +522,41 @@ int    trl_gallery_search(const float* d_q, const uint8_t* d_valid, int n, const
                           long long m, int metric, int k, float* d_score, int32_t* d_index, void* d_ws, size_t ws_bytes,
                           int max_strip_cols, void* stream);
 
+/* ---- Embedding clustering ("which of these faces are the same person?") ---------------------------------------------------------
+ * DBSCAN over n embeddings without the n x n score matrix: a packed link bitmap (n^2 / 8 bytes) and labels computed from it, both
+ * on the device.  Context-free, caller-owned memory, work queued on `stream`, the device that of d_mat / d_count.  (ABI v7, additive)
+ *   score    score(i, j) is the gallery's (above), row i as the query and row j as the gallery row; it is symmetric bit for bit.
+ *   link     i != j, both rows valid, and score >= threshold (cosine) or score <= threshold (euclidean).  A NaN score never links.
+ *   degree   1 + the number of links of a valid row (a row counts itself, whatever its own score is); 0 for an invalid row.
+ *   core     degree >= min_samples.
+ *   cluster  a connected component of the link graph restricted to core rows; clusters are numbered 0, 1, ... in ascending order
+ *            of their smallest core member.
+ *   label    a core row: its cluster's number.  A valid row that is not core and links to a core row (a border row): the smallest
+ *            number among its core neighbours' clusters.  Every other row (noise, invalid rows): -1.
+ * This is sklearn.cluster.DBSCAN(metric="precomputed") on D = link ? 0 : 1, eps = 0.5, and it does not depend on visiting order.
+ * The result depends on the scores and the rule alone: not on strips, launch geometry or the number of rounds.
+ * TRL_ERR_INVALID with nothing queued: n < 0 or n > 65,536 (the bitmap is 512 MB there), pitch_words < ceil(n / 32), a threshold
+ * that is NaN or infinite, min_samples < 1, a metric other than 0 / 1, ld out of range or n > ld, max_strip_cols no multiple of
+ * 128, a workspace too small or not 8-byte aligned, a null pointer where one is needed. */
+/* d_q: the n rows [n][512]; d_mat / d_n2: THE SAME n rows packed by trl_gallery_pack at column 0 (the caller guarantees it).  Writes
+ * the bitmap -- bit b of d_adj[i * pitch_words + w] <=> link(i, 32 w + b), rows < n, words < ceil(n / 32), bits at columns >= n zero,
+ * nothing else -- and d_degree[i], i < n.  d_valid (n bytes) may be null: every row is valid.  max_strip_cols as in
+ * trl_gallery_search.  n = 0: nothing is done.  Does not synchronise. */
+int    trl_cluster_links(const float* d_q, const uint8_t* d_valid, int n, const float* d_mat, long long ld, const float* d_n2,
+                         int metric, float threshold, uint32_t* d_adj, long long pitch_words, int32_t* d_degree,
+                         int max_strip_cols, void* stream);
+/* Device bytes of trl_cluster_labels' d_ws (three int32 per row and the change flags).  0 on bad arguments. */
+size_t trl_cluster_workspace(int n);
+/* Labels from a bitmap and its degrees (degree 0 = invalid row; the bitmap must be symmetric with an empty diagonal, as
+ * trl_cluster_links writes it): d_labels [n] int32, d_core [n] uint8, *d_count = the number of clusters.  Components come from rounds
+ * of min-label hooking (a row, and the row its label names, take the smallest label among the row's core neighbours) and pointer
+ * jumping, one launch each; the host reads a device flag after every four rounds, so THIS CALL
+ * SYNCHRONISES `stream` (and cannot be captured into a graph).  *rounds_out (a host int, may be null): the rounds up to and including
+ * the first that changed nothing.  A loop that passes n rounds returns TRL_ERR_STATE.  n = 0: *d_count = 0, nothing else. */
+int    trl_cluster_labels(const uint32_t* d_adj, long long pitch_words, const int32_t* d_degree, int n, int min_samples,
+                          int32_t* d_labels, uint8_t* d_core, int32_t* d_count, void* d_ws, size_t ws_bytes, int* rounds_out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

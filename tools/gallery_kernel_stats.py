@@ -8,7 +8,17 @@ trace, one process per shape, median of 10 warm launches (after 10 of warm-up) a
 A launch's time is k_gallery_search plus k_gallery_merge.  Next to it: the two floors of the shape -- one pass over the gallery,
 m * 2 KB at 8.0 TB/s, and 2 n 512 m FLOP at the 157.3 TFLOP/s f32-MFMA peak -- and what a user would
 otherwise write on the same device: torch.mm(q, rows.T) + torch.topk(k), cosine on rows normalised beforehand (the sum of every
-kernel the two calls launch, median of 10 after 10 of warm-up)."""
+kernel the two calls launch, median of 10 after 10 of warm-up).
+
+Cluster mode (FaceGallery.cluster: trl_cluster_links + trl_cluster_labels), n rows against themselves:
+
+    python tools/gallery_kernel_stats.py --cluster out_dir > profiles/cluster_kernel_stats.csv
+    python tools/gallery_kernel_stats.py --cluster-table out_dir
+
+Per n one process under the same trace: 3 + 5 calls of cluster() (cosine 0.5, min_samples 4, on n / 16 identities of 16 noisy unit
+rows each, so that there is a graph to label), then 3 + 5 of scores() on the same n x n -- k_gallery_scores, the kernel whose
+main loop k_gallery_links shares, is the yardstick.  A row of the table is one kernel: its launches per call and the median over the
+5 measured calls of its time per call (the label kernels run once per round)."""
 import csv
 import glob
 import json
@@ -81,6 +91,68 @@ def table(out):
                       f"{statistics.median(b for _a, b in part) / 1e3:.1f},{info['workspace_bytes']},{hbm:.1f},{mfma:.1f},{torch_us:.1f}")
 
 
+CL_SHAPES, CL_WARMUP, CL_WARM, CL_PER_ID = (1_024, 8_192, 32_768), 3, 5, 16
+CL_KERNELS = ("k_gallery_links", "k_cluster_degree", "k_cluster_init", "k_cluster_hook", "k_cluster_jump", "k_cluster_number",
+              "k_cluster_assign", "k_gallery_scores")
+
+
+def run_cluster(n):
+    import torch
+    from truely_amd.gallery import FaceGallery
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    centres = torch.nn.functional.normalize(torch.randn((n // CL_PER_ID, 512), generator=gen, device="cuda"), dim=1)
+    rows = centres.repeat_interleave(CL_PER_ID, dim=0) + 0.03 * torch.randn((n, 512), generator=gen, device="cuda")
+    rows = torch.nn.functional.normalize(rows, dim=1)[torch.randperm(n, generator=gen, device="cuda")]
+    gal = FaceGallery(metric="cosine", capacity=n)
+    gal.add(rows, range(n))
+    torch.cuda.synchronize()
+    for _ in range(CL_WARMUP + CL_WARM):
+        info = gal.cluster(0.5, min_samples=4, return_info=True)
+    torch.cuda.synchronize()
+    for _ in range(CL_WARMUP + CL_WARM):
+        s = gal.scores(rows)
+    torch.cuda.synchronize()
+    labels = info["labels"]
+    print(json.dumps({"n": n, "rounds": info["rounds"], "n_clusters": info["n_clusters"], "noise": int((labels < 0).sum()),
+                      "mean_degree": float(info["degree"].float().mean()), "bitmap_bytes": n * ((n + 31) // 32) * 4,
+                      "score_matrix_bytes": int(s.numel()) * 4}))
+
+
+def table_cluster(out):
+    print("n,metric,kernel,launches_per_call,median_us_per_call,min_us_per_call,max_us_per_call,tflops,rounds,n_clusters,mean_degree,bitmap_bytes")
+    for n in CL_SHAPES:
+        d = os.path.join(out, f"cluster_{n}")
+        info = json.load(open(os.path.join(d, "info.json")))
+        tr = _trace(d)
+        calls, flat = CL_WARMUP + CL_WARM, {k: [] for k in CL_KERNELS}
+        for s, e, name in tr:
+            for k in CL_KERNELS:
+                if k in name:
+                    flat[k].append(e - s)
+        for k in CL_KERNELS:
+            assert flat[k] and len(flat[k]) % calls == 0, (n, k, len(flat[k]))
+            per = len(flat[k]) // calls
+            tot = [sum(flat[k][c * per:(c + 1) * per]) / 1e3 for c in range(CL_WARMUP, calls)]
+            med = statistics.median(tot)
+            tf = f"{2.0 * n * n * 512 / med / 1e6:.1f}" if k in ("k_gallery_links", "k_gallery_scores") else ""
+            print(f"{n},cosine,{k},{per},{med:.1f},{min(tot):.1f},{max(tot):.1f},{tf},{info['rounds']},{info['n_clusters']},"
+                  f"{info['mean_degree']:.2f},{info['bitmap_bytes']}")
+
+
+def run_all_cluster(out):
+    for n in CL_SHAPES:
+        d = os.path.join(out, f"cluster_{n}")
+        os.makedirs(d, exist_ok=True)
+        r = subprocess.run(["rocprofv3", "--kernel-trace", "-d", d, "-o", "t", "-f", "csv", "--", sys.executable, os.path.abspath(__file__),
+                            "run-cluster", str(n)], capture_output=True, text=True, timeout=300)
+        if r.returncode != 0:
+            sys.exit(f"cluster shape {n} failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+        print(line, file=sys.stderr, flush=True)
+        open(os.path.join(d, "info.json"), "w").write(line)
+    table_cluster(out)
+
+
 def run_all(out):
     for m in M_SHAPES:
         for n in N_SHAPES:
@@ -101,5 +173,11 @@ if __name__ == "__main__":
         run_all(sys.argv[2])
     elif sys.argv[1] == "--table":
         table(sys.argv[2])
+    elif sys.argv[1] == "--cluster":
+        run_all_cluster(sys.argv[2])
+    elif sys.argv[1] == "--cluster-table":
+        table_cluster(sys.argv[2])
+    elif sys.argv[1] == "run-cluster":
+        run_cluster(int(sys.argv[2]))
     else:
         run(int(sys.argv[2]), int(sys.argv[3]))

@@ -18,6 +18,9 @@
 // a STRIP of column groups, merges its eight lists per row and writes n x k entries per strip; k_gallery_merge merges the strips
 // per row by the same order.  Scores do not depend on n, tile, strip or launch geometry (one chain per output), and the order is
 // total, so neither does the result.
+//
+// Clustering (f-8) is the same main loop ended in a ballot: k_gallery_links writes the packed link bitmap of n rows against
+// themselves, and the k_cluster_* kernels turn it into DBSCAN labels by rounds of hooking and pointer jumping, a launch each.
 #include <algorithm>
 #include <utility>
 
@@ -290,6 +293,193 @@ __global__ __launch_bounds__(256) void k_gallery_pack(const float* __restrict__ 
     if (tid < live) n2[c0 + row0 + tid] = acc;
 }
 
+// ---- clustering: the link bitmap of n rows against themselves, then DBSCAN labels over it ----------------
+// k_gallery_links is k_gallery_search's frame -- gl_fill_tile, a strip of column groups per workgroup, gl_chain, gl_score -- with
+// another end: accumulator i of the 32 x 32 C/D map holds row (i & 3) + 8 (i >> 2) + 4 (lane >> 5) at column lane & 31, so the
+// ballot of its link predicate IS two finished words of the bitmap: the low half row r's word c0 / 32, the high half row r + 4's.
+// No LDS stage and no atomic: every word (rows < n, words < ceil(n / 32)) is written exactly once, by one wave, with a vector store.
+// Masked before the ballot: the diagonal, columns >= n, invalid columns, invalid or absent rows.  A NaN score fails both comparisons.
+__global__ __launch_bounds__(256, 2) void k_gallery_links(const float* __restrict__ q, const uint8_t* __restrict__ valid, int n,
+                                                       const float* __restrict__ mat, long long ld, const float* __restrict__ gn2,
+                                                       int metric, float thr, int tiles, long long gps, long long groups,
+                                                       uint32_t* __restrict__ adj, long long pitch) {
+    extern __shared__ float gl_lds[];
+    float* tile = gl_lds;
+    float* info = gl_lds + GL_TILE_WORDS;
+    const int* rowok = reinterpret_cast<const int*>(info) + 2 * GL_ROWS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long row0 = (long long)(blockIdx.x % (unsigned)tiles) * GL_ROWS, strip = blockIdx.x / (unsigned)tiles;
+    const int live = gl_fill_tile(tile, info, q, valid, n, row0, tid);
+    const int j = lane & 31, h = lane >> 5;
+    const long long g_end = (strip + 1) * gps < groups ? (strip + 1) * gps : groups;
+    for (long long g = strip * gps; g < g_end; g++) {
+        const long long c0 = g * GL_GROUP + wave * 32;
+        if (c0 >= n) break;
+        const f32x16 acc = gl_chain(tile, mat, (size_t)ld, c0, lane);
+        const long long col = c0 + j;
+        const float g2 = gn2[col], gs = __builtin_sqrtf(g2);          // (col < ld: n2 has ld entries)
+        const bool colok = col < n && (!valid || valid[col] != 0);
+        int h_here = h;                                               // (as in k_gallery_search: the 16 rows' LDS addresses are
+        asm volatile("" : "+v"(h_here));                              // made here, not kept in registers across the chain)
+        uint32_t* dst = adj + (size_t)row0 * (size_t)pitch + (size_t)(c0 >> 5);
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int r = (i & 3) + 8 * (i >> 2) + 4 * h_here;
+            const float sc = gl_score(metric, acc[i], info[r], info[GL_ROWS + r], g2, gs);
+            const bool hit = (metric == TRL_GL_COSINE ? sc >= thr : sc <= thr) && colok && rowok[r] != 0 && row0 + r != col;
+            const unsigned long long b = __ballot(hit);
+            if (j == 0 && r < live) dst[(size_t)r * (size_t)pitch] = h_here ? (uint32_t)(b >> 32) : (uint32_t)b;
+        }
+    }
+}
+
+// one wave per row: the row's popcount, + 1 for the row itself; 0 for an invalid row.  Not an atomic counter.
+__global__ __launch_bounds__(256) void k_cluster_degree(const uint32_t* __restrict__ adj, long long pitch, const uint8_t* __restrict__ valid,
+                                                        int n, int words, int32_t* __restrict__ degree) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const uint32_t* a = adj + (size_t)row * (size_t)pitch;
+    int c = 0;
+    for (int w = lane; w < words; w += 64) c += __popc(a[w]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+    if (lane == 0) degree[row] = (!valid || valid[row] != 0) ? c + 1 : 0;
+}
+
+// Labels.  Every kernel below reads buffers that no workgroup writes in the same launch, so nothing depends on one workgroup seeing
+// another's stores; a round is a copy and two launches (b = a; hook: a -> b; jump: b -> a) and the host decides between small
+// batches of rounds.
+constexpr int CL_NONE = 0x7fffffff;   // the label of a row that is not core
+constexpr int CL_JUMPS = 32;          // pointer chases of one jump launch (over a buffer the launch does not write)
+constexpr int CL_BATCH = 4;           // rounds queued between two looks at the change flags
+constexpr int CL_MAX_N = 65536;
+
+__global__ void k_cluster_init(const int32_t* __restrict__ degree, int n, int min_samples, uint8_t* __restrict__ core, int32_t* __restrict__ lab) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int d = degree[i];
+    const bool c = d > 0 && d >= min_samples;
+    core[i] = c;
+    lab[i] = c ? i : CL_NONE;
+}
+
+// the smallest of f(label of j) over the set bits j < n of bitmap row `a`, by one wave (every lane returns it); rows that are not
+// core carry CL_NONE and drop out of the minimum by themselves
+template <typename F>
+__device__ __forceinline__ int cl_row_min(const uint32_t* __restrict__ a, int n, int words, const int32_t* __restrict__ lab, int lane, F&& f) {
+    int m = CL_NONE;
+    for (int w = lane; w < words; w += 64) {
+        uint32_t bits = a[w];
+        if (w == words - 1 && (n & 31)) bits &= (1u << (n & 31)) - 1u;      // (a caller's bitmap is never followed past n)
+        while (bits) {
+            const int b = __ffs(bits) - 1;
+            bits &= bits - 1;
+            const int v = f(lab[32 * w + b]);
+            m = v < m ? v : m;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int o = __shfl_xor(m, off, 64);
+        m = o < m ? o : m;
+    }
+    return m;
+}
+
+// one wave per core row: m = the smallest label among the row's core neighbours; where m is below the row's own label, both the row
+// and the row its label names (its tree's root, after a jump) take it: out[row] = min(out[row], m), out[own] = min(out[own], m).
+// `out` is a copy of `in` made in front of the launch and this launch touches it with atomicMin only -- never a plain store beside
+// an atomic on one line -- and min commutes, so `out` does not depend on the order the waves run in.  *changed likewise is only
+// ever touched by atomics, the memset in front of the batch and the copy behind it, and lies in an allocation of its own.
+__global__ __launch_bounds__(256) void k_cluster_hook(const uint32_t* __restrict__ adj, long long pitch, int n, int words,
+                                                      const int32_t* __restrict__ in, int32_t* out, int* changed) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const int own = in[row];
+    if (own == CL_NONE) return;
+    const int m = cl_row_min(adj + (size_t)row * (size_t)pitch, n, words, in, lane, [](int l) { return l; });
+    if (lane == 0 && m < own) {
+        atomicMin(out + row, m);
+        atomicMin(out + own, m);
+        atomicOr(changed, 1);
+    }
+}
+
+// out = the label CL_JUMPS steps up the chain of `in` (labels only point downwards and a root points at itself, so the walk ends)
+__global__ void k_cluster_jump(const int32_t* __restrict__ in, int n, int32_t* __restrict__ out, int* changed) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int own = in[i];
+    int l = own;
+    if (own != CL_NONE) {
+        for (int s = 0; s < CL_JUMPS; s++) {
+            const int up = in[l];
+            if (up == l) break;
+            l = up;
+        }
+    }
+    out[i] = l;
+    if (l != own) atomicOr(changed, 1);
+}
+
+// one workgroup: cid[i] = the number of roots (core rows whose label is their own index) below i, for every root i; *count = roots.
+// Thread t owns rows t * per .. + per - 1; the 1,024 partial counts are scanned in LDS.
+__global__ __launch_bounds__(1024) void k_cluster_number(const int32_t* __restrict__ lab, int n, int per, int32_t* __restrict__ cid,
+                                                         int32_t* __restrict__ count) {
+    __shared__ int part[1024];
+    const int t = threadIdx.x;
+    const int lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+    int c = 0;
+    for (int i = lo; i < hi; i++) c += lab[i] == i;
+    part[t] = c;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int add = t >= off ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    int base = part[t] - c;
+    for (int i = lo; i < hi; i++) cid[i] = lab[i] == i ? base++ : -1;
+    if (t == 1023) *count = part[1023];
+}
+
+// one wave per row: a core row takes its root's number; a valid row that is not core the smallest number among its core
+// neighbours' clusters (a border row), -1 without one (noise); an invalid row -1
+__global__ __launch_bounds__(256) void k_cluster_assign(const uint32_t* __restrict__ adj, long long pitch, const int32_t* __restrict__ degree,
+                                                        int n, int words, const int32_t* __restrict__ lab, const int32_t* __restrict__ cid,
+                                                        int32_t* __restrict__ labels) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const int own = lab[row];
+    int out = -1;
+    if (own != CL_NONE) {
+        out = cid[own];
+    } else if (degree[row] > 0) {
+        const int m = cl_row_min(adj + (size_t)row * (size_t)pitch, n, words, lab, lane, [&](int l) { return l == CL_NONE ? CL_NONE : cid[l]; });
+        out = m == CL_NONE ? -1 : m;
+    }
+    if (lane == 0) labels[row] = out;
+}
+
+// the label stage's workspace, carved once: trl_cluster_workspace is a dry run of this
+struct ClWs {
+    int32_t *a = nullptr, *b = nullptr, *cid = nullptr;
+    int* changed = nullptr;           // CL_BATCH flags, in an allocation of their own
+};
+
+bool cl_carve(Arena& a, int n, ClWs* w) {
+    const size_t bytes = (size_t)n * sizeof(int32_t);
+    w->a = (int32_t*)a.alloc(bytes);
+    w->b = (int32_t*)a.alloc(bytes);
+    w->cid = (int32_t*)a.alloc(bytes);
+    w->changed = (int*)a.alloc(CL_BATCH * sizeof(int));
+    return w->a && w->b && w->cid && w->changed;
+}
+
 // ---- the search's plan and workspace, written once: trl_gallery_search_workspace is a dry run of gl_carve -------------------------
 struct GlPlan {
     long long tiles = 0, groups = 0, gps = 0, strips = 0;
@@ -411,5 +601,94 @@ extern "C" int trl_gallery_search(const float* d_q, const uint8_t* d_valid, int 
         k_gallery_merge<<<(unsigned)n, 64, 0, s>>>(part, n, p.strips, k, metric, d_score, d_index);
         TRL_LAUNCH_CHECK();
     }
+    return TRL_OK;
+}
+
+extern "C" int trl_cluster_links(const float* d_q, const uint8_t* d_valid, int n, const float* d_mat, long long ld, const float* d_n2,
+                                 int metric, float threshold, uint32_t* d_adj, long long pitch_words, int32_t* d_degree,
+                                 int max_strip_cols, void* stream) {
+    if (n < 0 || n > CL_MAX_N) { trl_set_error("trl_cluster_links: n = %d outside 0..%d", n, CL_MAX_N); return TRL_ERR_INVALID; }
+    GlPlan p;
+    if (const char* why = gl_plan(n, n, 1, max_strip_cols, &p)) { trl_set_error("trl_cluster_links: %s", why); return TRL_ERR_INVALID; }
+    if (metric != TRL_GL_COSINE && metric != TRL_GL_EUCLIDEAN) { trl_set_error("trl_cluster_links: metric %d (0 cosine, 1 euclidean)", metric); return TRL_ERR_INVALID; }
+    if (!(threshold - threshold == 0.f)) { trl_set_error("trl_cluster_links: the threshold is not finite"); return TRL_ERR_INVALID; }
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, n)) { trl_set_error("trl_cluster_links: %s", why); return TRL_ERR_INVALID; }
+    const int words = (n + 31) / 32;
+    if (pitch_words < words) { trl_set_error("trl_cluster_links: pitch_words = %lld < %d", pitch_words, words); return TRL_ERR_INVALID; }
+    if (n == 0) return TRL_OK;
+    if (!d_q || !d_adj || !d_degree) { trl_set_error("trl_cluster_links: null argument"); return TRL_ERR_INVALID; }
+    TRL_CHECK(gl_device_of(d_mat));
+    hipStream_t s = (hipStream_t)stream;
+    const int lds = (GL_TILE_WORDS + GL_INFO_WORDS) * 4;
+    TRL_HIP(hipFuncSetAttribute((const void*)k_gallery_links, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    k_gallery_links<<<(unsigned)(p.strips * p.tiles), 256, lds, s>>>(d_q, d_valid, n, d_mat, ld, d_n2, metric, threshold, (int)p.tiles, p.gps,
+                                                                    p.groups, d_adj, pitch_words);
+    TRL_LAUNCH_CHECK();
+    k_cluster_degree<<<(unsigned)((n + 3) / 4), 256, 0, s>>>(d_adj, pitch_words, d_valid, n, words, d_degree);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
+extern "C" size_t trl_cluster_workspace(int n) {
+    if (n < 0 || n > CL_MAX_N) return 0;
+    Arena a = Arena::counter();
+    ClWs w;
+    cl_carve(a, n, &w);
+    return a.high;
+}
+
+extern "C" int trl_cluster_labels(const uint32_t* d_adj, long long pitch_words, const int32_t* d_degree, int n, int min_samples,
+                                  int32_t* d_labels, uint8_t* d_core, int32_t* d_count, void* d_ws, size_t ws_bytes, int* rounds_out,
+                                  void* stream) {
+    if (n < 0 || n > CL_MAX_N) { trl_set_error("trl_cluster_labels: n = %d outside 0..%d", n, CL_MAX_N); return TRL_ERR_INVALID; }
+    if (min_samples < 1) { trl_set_error("trl_cluster_labels: min_samples = %d < 1", min_samples); return TRL_ERR_INVALID; }
+    const int words = (n + 31) / 32;
+    if (pitch_words < words) { trl_set_error("trl_cluster_labels: pitch_words = %lld < %d", pitch_words, words); return TRL_ERR_INVALID; }
+    if (!d_count) { trl_set_error("trl_cluster_labels: null count"); return TRL_ERR_INVALID; }
+    if (n > 0 && (!d_adj || !d_degree || !d_labels || !d_core)) { trl_set_error("trl_cluster_labels: null argument"); return TRL_ERR_INVALID; }
+    Arena a;
+    a.base = (char*)d_ws;
+    a.cap = d_ws ? ws_bytes : 0;
+    ClWs w;
+    if (n > 0 && (((uintptr_t)d_ws & 7) || !cl_carve(a, n, &w))) {
+        trl_set_error("trl_cluster_labels: workspace of %zu bytes (need %zu, 8-byte aligned)", ws_bytes, trl_cluster_workspace(n));
+        return TRL_ERR_INVALID;
+    }
+    TRL_CHECK(gl_device_of(d_count));
+    hipStream_t s = (hipStream_t)stream;
+    if (rounds_out) *rounds_out = 0;
+    if (n == 0) {
+        TRL_HIP(hipMemsetAsync(d_count, 0, sizeof(int32_t), s));
+        return TRL_OK;
+    }
+    const unsigned per_thread = (unsigned)((n + 255) / 256), per_wave = (unsigned)((n + 3) / 4);
+    k_cluster_init<<<per_thread, 256, 0, s>>>(d_degree, n, min_samples, d_core, w.a);
+    TRL_LAUNCH_CHECK();
+    // rounds of copy, hook (a -> b) and jump (b -> a) until one changes nothing.  Every round before that one lowers at least one label and
+    // a label is at least 0 and at most its row's index, so the loop ends; the bound of n rounds is a second line of defence.
+    int rounds = 0;
+    for (bool done = false; !done;) {
+        if (rounds >= n + CL_BATCH) { trl_set_error("trl_cluster_labels: no fixed point after %d rounds", rounds); return TRL_ERR_STATE; }
+        TRL_HIP(hipMemsetAsync(w.changed, 0, CL_BATCH * sizeof(int), s));
+        for (int r = 0; r < CL_BATCH; r++) {
+            TRL_HIP(hipMemcpyAsync(w.b, w.a, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            k_cluster_hook<<<per_wave, 256, 0, s>>>(d_adj, pitch_words, n, words, w.a, w.b, w.changed + r);
+            TRL_LAUNCH_CHECK();
+            k_cluster_jump<<<per_thread, 256, 0, s>>>(w.b, n, w.a, w.changed + r);
+            TRL_LAUNCH_CHECK();
+        }
+        int changed[CL_BATCH];
+        TRL_HIP(hipMemcpyAsync(changed, w.changed, sizeof(changed), hipMemcpyDeviceToHost, s));
+        TRL_HIP(hipStreamSynchronize(s));
+        for (int r = 0; r < CL_BATCH && !done; r++) {
+            rounds++;
+            done = changed[r] == 0;
+        }
+    }
+    if (rounds_out) *rounds_out = rounds;
+    k_cluster_number<<<1, 1024, 0, s>>>(w.a, n, (n + 1023) / 1024, w.cid, d_count);
+    TRL_LAUNCH_CHECK();
+    k_cluster_assign<<<per_wave, 256, 0, s>>>(d_adj, pitch_words, d_degree, n, words, w.a, w.cid, d_labels);
+    TRL_LAUNCH_CHECK();
     return TRL_OK;
 }

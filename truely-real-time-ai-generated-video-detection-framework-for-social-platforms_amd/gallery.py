@@ -13,7 +13,9 @@ product, then
     cosine      dot / (sqrt(n2 q) * sqrt(n2 g))                    larger is better; a zero row gives NaN
     euclidean   sqrt(max(n2 q + n2 g - 2 dot, 0))                  smaller is better
 
-and matches are ordered better score first, equal scores to the lower gallery index, NaN last.  Embeddings never visit the host."""
+and matches are ordered better score first, equal scores to the lower gallery index, NaN last.  ``cluster`` /
+``cluster_embeddings`` answer the question that needs no enrolled identities -- "which of these faces are the same person?" --
+with DBSCAN over the same scores, from a link bitmap instead of the score matrix.  Embeddings never visit the host."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,6 +27,7 @@ from . import _lib
 
 METRICS = {"cosine": 0, "euclidean": 1}
 MAX_K = 16
+MAX_CLUSTER_ROWS = 65536
 DIM = 512
 
 
@@ -122,12 +125,7 @@ class FaceGallery:
         n, m, k = q.shape[0], self._m, int(k)
         if not 1 <= k <= MAX_K:
             raise ValueError(f"k must be 1..{MAX_K}")
-        if valid is not None:
-            if isinstance(valid, np.ndarray):
-                valid = torch.from_numpy(valid)
-            valid = (valid.to(self.device) != 0).to(torch.uint8).contiguous()
-            if valid.shape != (n,):
-                raise ValueError(f"valid must have shape ({n},)")
+        valid = _valid(valid, n, self.device)
         idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
         score = torch.empty((n, k), dtype=torch.float32, device=self.device)
         need = self.lib.trl_gallery_search_workspace(n, m, k, max_strip_cols)
@@ -147,6 +145,65 @@ class FaceGallery:
             ok &= (score >= threshold) if self._metric == 0 else (score <= threshold)
         picks = torch.where(ok, idx, torch.full_like(idx, -1)).tolist()          # n integers to the host: the labels live there
         return [self._labels[i] if i >= 0 else None for i in picks], score
+
+    def cluster(self, threshold: float, min_samples: int = 1, valid=None, return_info: bool = False, max_strip_cols: int = 0):
+        """DBSCAN labels of the enrolled rows, (len(self),) int32 on the device: "which of these are the same person?".
+
+        Rows i != j are linked when their score passes ``threshold`` (identify's convention: cosine ``score >= threshold``,
+        euclidean ``score <= threshold``, both in float32; a NaN score never links).  A row with at least ``min_samples`` rows in
+        its neighbourhood, itself included, is a core row; clusters are the connected components of the links among core rows,
+        numbered in ascending order of their smallest core member; a row that is not core takes the smallest number among its
+        core neighbours' clusters, and -1 (noise) without one.  Rows whose ``valid`` entry is zero link to nothing and get -1.
+        ``min_samples=1`` is plain threshold connected components.  This is ``sklearn.cluster.DBSCAN(metric="precomputed")``
+        exactly.  The n x n scores are never written: the links are a bitmap of n * n / 8 bytes (n <= 65,536).
+
+        With ``return_info`` a dict: ``labels``, ``core`` (n,) uint8, ``degree`` (n,) int32 (links + 1; 0 for an invalid row),
+        ``n_clusters`` and ``rounds`` (ints).  The call synchronises the current stream."""
+        n = self._m
+        if n > MAX_CLUSTER_ROWS:
+            raise ValueError(f"cluster takes at most {MAX_CLUSTER_ROWS} rows, not {n}")
+        threshold, min_samples = float(threshold), int(min_samples)
+        valid = _valid(valid, n, self.device)
+        words = (n + 31) // 32
+        adj = torch.empty((n, words), dtype=torch.int32, device=self.device)
+        degree = torch.empty((n,), dtype=torch.int32, device=self.device)
+        labels = torch.empty((n,), dtype=torch.int32, device=self.device)
+        core = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        count = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        need = self.lib.trl_cluster_workspace(n)
+        ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
+        rows = self.rows() if n else None
+        rounds = C.c_int(0)
+        s = _stream(self.device)
+        _lib.check(self.lib.trl_cluster_links(_ptr(rows), _ptr(valid), n, _ptr(self._mat), self.ld, _ptr(self._n2), self._metric, threshold,
+                                              _ptr(adj), words, _ptr(degree), max_strip_cols, s))
+        _lib.check(self.lib.trl_cluster_labels(_ptr(adj), words, _ptr(degree), n, min_samples, _ptr(labels), _ptr(core), _ptr(count),
+                                               _ptr(ws), need, C.byref(rounds), s))
+        if not return_info:
+            return labels
+        return {"labels": labels, "core": core, "degree": degree, "n_clusters": int(count.item()), "rounds": rounds.value}
+
+
+def _valid(valid, n: int, device):
+    """None, or the mask as (n,) uint8 on `device`."""
+    if valid is None:
+        return None
+    if isinstance(valid, np.ndarray):
+        valid = torch.from_numpy(valid)
+    valid = (valid.to(device) != 0).to(torch.uint8).contiguous()
+    if valid.shape != (n,):
+        raise ValueError(f"valid must have shape ({n},)")
+    return valid
+
+
+def cluster_embeddings(emb, threshold: float, metric: str = "cosine", min_samples: int = 1, valid=None, device=None,
+                       return_info: bool = False):
+    """``FaceGallery.cluster`` for loose embeddings, (n, 512): the faces of a clip, an enrolment set to de-duplicate."""
+    if device is None:
+        device = emb.device if isinstance(emb, torch.Tensor) and emb.device.type == "cuda" else None
+    g = FaceGallery(metric=metric, device=device, capacity=max(len(emb), 1))
+    g.add(emb, range(len(emb)))
+    return g.cluster(threshold, min_samples=min_samples, valid=valid, return_info=return_info)
 
 
 def pairwise(a, b=None, metric: str = "euclidean", device=None) -> torch.Tensor:

@@ -101,6 +101,21 @@ def test_batch_of_three_640x360(dev, s, rr, rb, opt):
     check_round_trip(DeviceJpegDecoder(W, H, device=dev, max_frames=3), files)
 
 
+@pytest.mark.parametrize("s", [0, 1])
+def test_optioned_batch_larger_than_a_chunk(dev, s):
+    """Three 4K frames in one call with a marker per MCU row and optimize.  A block costs the workspace 372 bytes, so a 4:4:4 frame
+    (388,800 blocks) takes 145 MB and a 4:2:2 frame (259,200) 96 MB: the 256 MB budget holds one and two, and the call runs in
+    chunks of 1 + 1 + 1 and of 2 + 1.  A later chunk's frames use table, header-length and interval-start slots indexed within
+    the chunk and output offsets indexed across chunks; every file still equals Pillow's."""
+    from truely_amd.jpeg import DeviceJpeg
+    H, W = 2160, 3840
+    kinds = ("noise", "gradient", "saturated")
+    frames = np.stack([make_frame(k, H, W) for k in kinds])
+    enc = DeviceJpeg(W, H, 80, device=dev, max_frames=3, subsampling=s, restart_rows=1, optimize=True)
+    files = enc.encode(torch.from_numpy(frames).to(dev))
+    check_files(files, [expected(k, H, W, 0, 80, s, 1, 0, True) for k in kinds], s)
+
+
 @pytest.mark.parametrize("s", SAMPLINGS)
 def test_mixed_content_batch_keeps_tables_apart(dev, s):
     """Noise, a constant frame and a gradient in one batch under optimize: every frame carries its own four tables (the constant

@@ -22,39 +22,40 @@
 //   optimize    libjpeg's two passes: the symbols the scan will emit are counted per table (luma; Cb and Cr together), each of
 //               the four tables is jpeg_gen_optimal_table's (trl_jpeg_hufftab.h), and the frame's header carries its own DHTs
 // Pipeline per chunk of frames (all on the caller's stream; one host synchronisation per batch, to read the sizes):
-//   k_jpeg_blocks   a workgroup = 4 MCUs of one MCU row: BGR -> YCbCr + downsampling into LDS, FDCT, quantisation, zigzag,
-//                   dummy blocks -> int16 coefficients [frame][mcu][6][64]  (k_jpeg_blocks_ex<S>: the 4:4:4 and 4:2:2 MCUs)
-//   k_jpeg_bits     one wave per block, lane k = zigzag coefficient k: ballot -> run lengths -> the block's bit count
-//   k_jpeg_scan     one workgroup per frame: exclusive scan of the block bit counts
-//   k_jpeg_emit     one wave per block: each lane ORs its codes into the wave's LDS words at (block offset + lane prefix); the
-//                   words inside the block's range are stored, its first and last words set aside
-//   k_jpeg_edges    one thread per block: the words blocks share, merged by the one block that owns each (no atomics)
-//   k_jpeg_ffcount  FF bytes per 4 KiB segment of each frame's scan
-//   k_jpeg_sizes    one workgroup per chunk: scan of the segment counts, frame sizes and output offsets
-//   k_jpeg_scatter  header + stuffed scan + EOI into the caller's buffer; a frame that would end past the capacity is not written
-// With options (anything but the defaults) the same stages run as k_jpeg_bits_ex / k_jpeg_scan_ex / k_jpeg_emit_ex and the <true>
-// instantiations of edges / ffcount / scatter: blocks per MCU and the interval are parameters, block bit offsets restart per
-// interval and the intervals' byte lengths (+ 2 marker bytes) are scanned again, the marker is part of the last block's bits so
-// that every word still has one writer, and the stuffing passes skip the marker bytes by the interval starts.  optimize adds
-// k_jpeg_hist (per-workgroup LDS histograms, added to the frame's by device-scope integer atomics that only later kernels read)
-// and k_jpeg_tables (one wave per frame and table, then the frame's header) in front of k_jpeg_bits_ex.  No further host
-// synchronisation: tables never visit the host.
+//   k_jpeg_blocks<S>  a workgroup = a strip of one MCU row, 64 pixels wide (4 MCUs; 8 at 4:4:4): BGR -> YCbCr into LDS, the
+//                     sampling's chroma average, FDCT, quantisation, zigzag, dummy blocks -> int16 coefficients
+//                     [frame][mcu][blocks per MCU][64]
+//   k_jpeg_hist       optimize only: the symbols the scan will emit, per-workgroup LDS histograms added to the frame's by
+//   k_jpeg_tables     device-scope integer atomics that only later kernels read; then one wave per frame and table builds the
+//                     table, and the workgroup the frame's header.  Tables never visit the host.
+//   k_jpeg_bits       one wave per block, lane k = zigzag coefficient k: ballot -> run lengths -> the block's bit count
+//   k_jpeg_scan       one workgroup per frame: exclusive scan of the block bit counts; with restart intervals the offsets restart
+//                     per interval and the intervals' byte lengths (+ 2 marker bytes) are scanned again
+//   k_jpeg_emit       one wave per block: each lane ORs its codes into the wave's LDS words at (block offset + lane prefix); an
+//                     interval's last block adds the padding and, unless the interval is the frame's last, the marker, so that
+//                     every word has one writer; the words inside the block's range are stored, its first and last set aside
+//   k_jpeg_edges      one thread per block: the words blocks share, merged by the one block that owns each (no atomics)
+//   k_jpeg_ffcount    FF bytes per 4 KiB segment of each frame's scan (the markers' are found by the interval starts, and skipped)
+//   k_jpeg_sizes      one workgroup per chunk: scan of the segment counts, frame sizes and output offsets
+//   k_jpeg_scatter    header + stuffed scan + EOI into the caller's buffer; a frame that would end past the capacity is not written
+// Every stage is written once.  The entropy stages (bits .. scatter) are templates over a layout policy: FixedLayout is the
+// default kind of file with everything a constant (6 blocks per MCU, one interval, one table and one header), RunLayout carries
+// blocks per MCU, the interval, the interval count and the table stride as kernel arguments; an encoder launches one or the other
+// throughout (trl_jpeg::ex).
 #include "trl_common.h"
 #include "trl_jpeg_hufftab.h"
+#include "trl_zigzag.h"
 
 #include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
-constexpr int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-__constant__ int c_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+constexpr int kZigzag[64] = TRL_ZIGZAG_LIST;
+__constant__ int c_zigzag[64] = TRL_ZIGZAG_LIST;
 // ITU-T T.81 Annex K: quantisation tables (natural order) and Huffman tables (code counts per length, symbols)
 constexpr int kStdQ[2][64] = {
     {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
@@ -83,10 +84,23 @@ constexpr uint8_t kAcVals[2][162] = {
      0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
      0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
 
-constexpr int kMcuPerWg = 4;                  // k_jpeg_blocks: 4 MCUs = a 16 x 64 pixel strip, 24 blocks, 256 threads
 constexpr int kMaxBlockBits = 1792;           // >= 22 (DC) + 63 x 27 (AC) + 3 ZRL x 11 + EOB: 224 scratch bytes per block
 constexpr int kSeg = 4096;                    // bytes per stuffing segment (256 threads x 16 bytes)
 constexpr size_t kChunkBudget = 256u << 20;   // device workspace per chunk of frames
+constexpr int kHist = 4 * 256;                // optimize: symbol counts per frame [DC luma, AC luma, DC chroma, AC chroma][256]
+constexpr int kHdrCap = 1024;                 // bytes set aside for a header (the common one; with optimize one per frame)
+
+// What k_jpeg_blocks<S> needs to know of sampling S = 0 / 1 / 2 (4:4:4 / 4:2:2 / 4:2:0, Pillow's numbering): a workgroup's strip
+// is one MCU high and 64 pixels wide.
+template <int S>
+struct Sampling {
+    static constexpr int kRows = S == 2 ? 16 : 8;            // MCU height = strip rows
+    static constexpr int kMcuW = S == 0 ? 8 : 16;            // MCU width
+    static constexpr int kLuma = S == 0 ? 1 : S == 1 ? 2 : 4;// Y blocks per MCU (Y00 Y01 Y10 Y11; Cb and Cr follow)
+    static constexpr int kBpm = kLuma + 2;                   // blocks per MCU
+    static constexpr int kMcus = 64 / kMcuW;                 // MCUs per workgroup
+    static constexpr int kBlocks = kMcus * kBpm;             // blocks per workgroup: 24 / 16 / 24
+};
 
 struct JTab {
     uint16_t qdiv[2][64];   // 8 * quantiser, natural order (luma, chroma)
@@ -207,17 +221,20 @@ __device__ __forceinline__ void fdct8(int* d, int s) {
     d[1 * s] = descale(t7 * 12299 + z1 + z4, SH);                        // FIX_1_501321110
 }
 
-// grid (ceil(mcux / 4), mcuy, frames of the chunk), 256 threads
+// grid (ceil(mcux / Sampling<S>::kMcus), mcuy, frames of the chunk), 256 threads: one strip
+template <int S>
 __global__ __launch_bounds__(256) void k_jpeg_blocks(const uint8_t* __restrict__ src, long long frame_stride, int H, int W,
                                                      int mcux, int mcuy, const JTab* __restrict__ tab, int16_t* __restrict__ coef) {
-    __shared__ int pix[3][16][64];            // Y, Cb, Cr of the strip at full resolution (edge-replicated source pixels)
-    __shared__ int blk[24][64];               // centred samples -> FDCT output, natural order
-    __shared__ int16_t qz[24][64];            // quantised, zigzag order
-    const int tid = threadIdx.x, mx0 = blockIdx.x * kMcuPerWg, my = blockIdx.y, f = blockIdx.z;
+    using T = Sampling<S>;
+    constexpr int ROWS = T::kRows, MW = T::kMcuW, NY = T::kLuma, BPM = T::kBpm, NB = T::kBlocks;
+    __shared__ int pix[3][ROWS][64];          // Y, Cb, Cr of the strip at full resolution (edge-replicated source pixels)
+    __shared__ int blk[NB][64];               // centred samples -> FDCT output, natural order
+    __shared__ int16_t qz[NB][64];            // quantised, zigzag order
+    const int tid = threadIdx.x, mx0 = blockIdx.x * T::kMcus, my = blockIdx.y, f = blockIdx.z;
     const uint8_t* fr = src + (size_t)f * frame_stride;
-    for (int i = tid; i < 16 * 64; i += 256) {
+    for (int i = tid; i < ROWS * 64; i += 256) {
         const int r = i >> 6, c = i & 63;
-        const int gy = min(16 * my + r, H - 1), gx = min(16 * mx0 + c, W - 1);
+        const int gy = min(ROWS * my + r, H - 1), gx = min(MW * mx0 + c, W - 1);
         const uint8_t* p = fr + ((size_t)gy * W + gx) * 3;
         const int B = p[0], G = p[1], R = p[2];
         pix[0][r][c] = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
@@ -225,52 +242,110 @@ __global__ __launch_bounds__(256) void k_jpeg_blocks(const uint8_t* __restrict__
         pix[2][r][c] = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
     }
     __syncthreads();
-    const int crow_last = ((H + 1) >> 1) - 1 - 8 * my;           // last real chroma row of the strip (>= 0)
-    for (int i = tid; i < 24 * 64; i += 256) {
-        const int b = i >> 6, r = (i >> 3) & 7, c = i & 7, m = b / 6, kind = b % 6;
+    [[maybe_unused]] const int crow_last = ((H + 1) >> 1) - 1 - 8 * my;   // 4:2:0: last real chroma row of the strip (>= 0)
+    for (int i = tid; i < NB * 64; i += 256) {
+        const int b = i >> 6, r = (i >> 3) & 7, c = i & 7, m = b / BPM, kind = b % BPM;
         int v;
-        if (kind < 4) {
-            v = pix[0][(kind >> 1) * 8 + r][m * 16 + (kind & 1) * 8 + c];
+        if constexpr (S == 0) {                                          // an MCU is Y Cb Cr: every component is copied
+            v = pix[kind][r][m * 8 + c];
+        } else if (kind < NY) {
+            v = pix[0][(kind >> 1) * 8 + r][m * MW + (kind & 1) * 8 + c];
         } else {
-            const int (*pl)[64] = pix[kind - 3];
-            const int rr = 2 * min(r, crow_last), cc = 2 * (m * 8 + c);
-            v = (pl[rr][cc] + pl[rr][cc + 1] + pl[rr + 1][cc] + pl[rr + 1][cc + 1] + 1 + (c & 1)) >> 2;
+            const int (*pl)[64] = pix[kind - NY + 1];
+            if constexpr (S == 1) {                                      // h2v1, bias 0,1,0,1...
+                const int cc = 2 * (m * 8 + c);
+                v = (pl[r][cc] + pl[r][cc + 1] + (c & 1)) >> 1;
+            } else {                                                     // h2v2, bias 1,2,1,2...; the last real row repeats
+                const int rr = 2 * min(r, crow_last), cc = 2 * (m * 8 + c);
+                v = (pl[rr][cc] + pl[rr][cc + 1] + pl[rr + 1][cc] + pl[rr + 1][cc + 1] + 1 + (c & 1)) >> 2;
+            }
         }
         blk[b][(r << 3) | c] = v - 128;
     }
     __syncthreads();
-    if (tid < 192) fdct8<true>(&blk[tid >> 3][(tid & 7) * 8], 1);
+    if (tid < NB * 8) fdct8<true>(&blk[tid >> 3][(tid & 7) * 8], 1);
     __syncthreads();
-    if (tid < 192) fdct8<false>(&blk[tid >> 3][tid & 7], 8);
+    if (tid < NB * 8) fdct8<false>(&blk[tid >> 3][tid & 7], 8);
     __syncthreads();
-    for (int i = tid; i < 24 * 64; i += 256) {
+    for (int i = tid; i < NB * 64; i += 256) {
         const int b = i >> 6, z = i & 63;
-        const int c = blk[b][c_zigzag[z]], d = tab->qdiv[(b % 6) < 4 ? 0 : 1][c_zigzag[z]];
+        const int c = blk[b][c_zigzag[z]], d = tab->qdiv[(b % BPM) < NY ? 0 : 1][c_zigzag[z]];
         const int a = ((c < 0 ? -c : c) + (d >> 1)) / d;
         qz[b][z] = (int16_t)(c < 0 ? -a : a);
     }
     __syncthreads();
-    const int bw = (W + 7) >> 3, bh = (H + 7) >> 3;              // Y blocks holding image samples
-    for (int i = tid; i < 24 * 64; i += 256) {
-        const int b = i >> 6, z = i & 63, m = b / 6, kind = b % 6, mx = mx0 + m;
+    [[maybe_unused]] const int bw = (W + 7) >> 3, bh = (H + 7) >> 3;   // Y blocks holding image samples
+    for (int i = tid; i < NB * 64; i += 256) {
+        const int b = i >> 6, z = i & 63, m = b / BPM, kind = b % BPM, mx = mx0 + m;
         if (mx >= mcux) continue;
         int v = qz[b][z];
-        if (kind < 4) {
-            const bool right = 2 * mx + (kind & 1) >= bw, bottom = 2 * my + (kind >> 1) >= bh;
-            if (bottom) {                                        // the MCU's Y01 (itself a right dummy: Y00's DC)
-                v = z ? 0 : (2 * mx + 1 >= bw ? qz[m * 6][0] : qz[m * 6 + 1][0]);
-            } else if (right) {                                  // the left neighbour in the MCU
-                v = z ? 0 : qz[b - 1][0];
+        if constexpr (S != 0) {                                  // dummies: 4:4:4 none, 4:2:2 right only, 4:2:0 right and bottom
+            if (kind < NY) {
+                const bool right = 2 * mx + (kind & 1) >= bw, bottom = S == 2 && 2 * my + (kind >> 1) >= bh;
+                if (bottom) {                                    // the MCU's Y01 (itself a right dummy: Y00's DC)
+                    v = z ? 0 : (2 * mx + 1 >= bw ? qz[m * BPM][0] : qz[m * BPM + 1][0]);
+                } else if (right) {                              // the left neighbour in the MCU
+                    v = z ? 0 : qz[b - 1][0];
+                }
             }
         }
-        coef[(((size_t)f * mcuy + my) * mcux + mx) * 384 + kind * 64 + z] = (int16_t)v;
+        // One index, spelled per sampling so that each instantiation compiles to the store of the kernel it replaces: on the
+        // 4:2:0 spelling k_jpeg_blocks<0> measured 1.6 - 2.2 % slower (profiles/jpeg_refactor_kernel_stats.csv, s1_ rows).
+        const size_t mcu = ((size_t)f * mcuy + my) * mcux + mx;
+        coef[S == 2 ? mcu * (BPM * 64) + kind * 64 + z : (mcu * BPM + kind) * 64 + z] = (int16_t)v;
     }
 }
 
 __device__ __forceinline__ int nbits_of(int a) { return a ? 32 - __clz(a) : 0; }
 
+// How a frame's blocks are laid out for the entropy stages: blocks per MCU (component order in an MCU: the Y blocks, Cb, Cr),
+// the restart intervals, and whether each frame has a code table of its own.  FixedLayout is the default kind of file, all of it
+// constants, and is never a kernel argument; RunLayout is one.
+struct FixedLayout {
+    static constexpr bool kIntervals = false;                // one interval: the frame
+    __device__ static constexpr int bpm() { return 6; }
+    __device__ static constexpr int nint() { return 1; }
+    __device__ static constexpr int tab_stride() { return 0; }
+    __device__ static bool starts_interval(int mcu) { return mcu == 0; }
+    __device__ static bool ends_interval(int j, int blocks) { return j == blocks - 1; }
+    __device__ static constexpr int interval_of(int) { return 0; }
+};
+struct RunLayout {
+    static constexpr bool kIntervals = true;
+    int bpm_, R, nint_, tab_stride_;                         // R: MCUs per interval (no DRI: the frame's MCU count, one interval)
+    __device__ int bpm() const { return bpm_; }
+    __device__ int nint() const { return nint_; }
+    __device__ int tab_stride() const { return tab_stride_; }   // 1: a table per frame (optimize)
+    __device__ bool starts_interval(int mcu) const { return mcu % R == 0; }
+    __device__ int per() const { return R * bpm_; }          // blocks per interval
+    __device__ bool ends_interval(int j, int blocks) const { return j == blocks - 1 || (j + 1) % per() == 0; }
+    __device__ int interval_of(int j) const { return j / per(); }
+};
+// A kernel <L, LA...> ends its parameters with LA... la and begins with `const L lay{la...}`: LA is empty for FixedLayout and
+// the RunLayout itself otherwise (JPEG_STAGE launches either).
+
+template <class L>
+__device__ __forceinline__ int table_of(const L& lay, int j) { return j % lay.bpm() < lay.bpm() - 2 ? 0 : 1; }   // luma / chroma
+
+// the DC predictor of block j of a frame: the component's previous block, 0 at the start of each restart interval
+template <class L>
+__device__ __forceinline__ int dc_pred(const L& lay, const int16_t* __restrict__ fcoef, int j) {
+    const int bpm = lay.bpm(), mcu = j / bpm, kind = j % bpm, ny = bpm - 2;
+    if (kind >= 1 && kind < ny) return fcoef[(size_t)(j - 1) * 64];
+    if (lay.starts_interval(mcu)) return 0;
+    return fcoef[(size_t)(j - bpm + (kind == 0 ? ny - 1 : 0)) * 64];
+}
+
+// the zero run in front of the non-zero coefficient of lane `lane` (>= 1), given the ballot of the block's non-zero lanes
+__device__ __forceinline__ int run_before(unsigned long long mask, int lane) {
+    const unsigned long long below = mask & ((1ull << lane) - 1ull) & ~1ull;
+    const int prev = below ? 63 - __clzll(below) : 0;
+    return lane - prev - 1;
+}
+
 // The codes of lane k of a block (lane = zigzag index).  Up to three ZRL codes and one (code, magnitude) piece, or the EOB on
-// lane 63 when coefficient 63 is zero (its lane has no other bits, so the EOB lands at the block's end).
+// lane 63 when coefficient 63 is zero (its lane has no other bits, so the EOB lands at the block's end).  k_jpeg_hist counts
+// the same symbols on the same three branches: a classification shared through callbacks cost k_jpeg_bits 1 %.
 struct LaneCodes {
     uint32_t piece;   // (code << nb) | magnitude bits
     int plen;         // its length (0: none)
@@ -290,9 +365,7 @@ __device__ __forceinline__ LaneCodes lane_codes(const JTab* __restrict__ tab, co
         o.piece = ((e >> 8) << nb) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1u));
         o.plen = (int)(e & 0xFF) + nb;
     } else if (v != 0) {
-        const unsigned long long below = mask & ((1ull << lane) - 1ull) & ~1ull;
-        const int prev = below ? 63 - __clzll(below) : 0;
-        const int run = lane - prev - 1, a = v < 0 ? -v : v, nb = nbits_of(a);
+        const int run = run_before(mask, lane), a = v < 0 ? -v : v, nb = nbits_of(a);
         o.nzrl = run >> 4;
         const uint32_t e = tab->ac[t][((run & 15) << 4) | nb];
         o.piece = ((e >> 8) << nb) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << nb) - 1u));
@@ -305,30 +378,24 @@ __device__ __forceinline__ LaneCodes lane_codes(const JTab* __restrict__ tab, co
     return o;
 }
 
-// the DC predictor of block j of a frame (component order in an MCU: Y00 Y01 Y10 Y11 Cb Cr)
-__device__ __forceinline__ int dc_pred(const int16_t* __restrict__ fcoef, int j) {
-    const int mcu = j / 6, kind = j % 6;
-    if (kind >= 1 && kind <= 3) return fcoef[(size_t)(j - 1) * 64];
-    if (mcu == 0) return 0;
-    return fcoef[(size_t)(j - 6 + (kind == 0 ? 3 : 0)) * 64];
-}
-
 __device__ __forceinline__ int wave_sum(int x) {
     for (int o = 32; o; o >>= 1) x += __shfl_xor(x, o, 64);
     return x;
 }
 
 // grid ceil(frames * blocks / 4), 256 threads: one wave per block
+template <class L, class... LA>
 __global__ __launch_bounds__(256) void k_jpeg_bits(const int16_t* __restrict__ coef, int blocks, long long total,
-                                                   const JTab* __restrict__ tab, uint32_t* __restrict__ bits) {
+                                                   const JTab* __restrict__ tab, uint32_t* __restrict__ bits, LA... la) {
+    const L lay{la...};
     const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (g >= total) return;                                  // wave-uniform
+    if (g >= total) return;                                 // wave-uniform
     const long long f = g / blocks;
     const int j = (int)(g - f * blocks);
     const int16_t* fcoef = coef + (size_t)f * blocks * 64;
-    const int pred = lane == 0 ? dc_pred(fcoef, j) : 0;
-    const LaneCodes lc = lane_codes(tab, fcoef + (size_t)j * 64, lane, j % 6 < 4 ? 0 : 1, pred);
+    const int pred = lane == 0 ? dc_pred(lay, fcoef, j) : 0;
+    const LaneCodes lc = lane_codes(tab + (size_t)f * lay.tab_stride(), fcoef + (size_t)j * 64, lane, table_of(lay, j), pred);
     const int s = wave_sum(lc.bits());
     if (lane == 0) bits[g] = (uint32_t)s;
 }
@@ -356,15 +423,52 @@ __device__ T block_exclusive_scan(In in, Out out, long long n, T* sh) {
     return carry;
 }
 
-// grid = frames of the chunk, 1024 threads: block bit offsets and the frame's scan length in bits
-__global__ __launch_bounds__(1024) void k_jpeg_scan(const uint32_t* __restrict__ bits, int blocks, unsigned long long* __restrict__ off,
-                                                    unsigned long long* __restrict__ fbits) {
+// grid = frames of the chunk, 1024 threads: block bit offsets and the frame's scan length in bits.  With restart intervals the
+// frame's scan is the intervals' bits back to back, each padded to a byte and (but for the last) followed by the two marker
+// bytes, which are part of the stream k_jpeg_emit writes:
+//   off[j]   block j's bit offset in that stream (its offset within the interval + the interval's byte start)
+//   bits[j]  the interval's last block: its bits + the padding + 16 marker bits, so that every word has one owner
+//   ist[i]   interval i's byte start (k_jpeg_ffcount / k_jpeg_scatter find the marker bytes, which are not stuffed, by it)
+//   fbits    the stream's length in bits (whole bytes)
+// FixedLayout has none of that pass: bits[] stays as k_jpeg_bits wrote it, fbits is the sum, and the frame's one padding is
+// added where it is used (k_jpeg_emit, word_range).
+template <class L, class... LA>
+__global__ __launch_bounds__(1024) void k_jpeg_scan(uint32_t* __restrict__ bits, int blocks, unsigned long long* __restrict__ off,
+                                                    unsigned long long* __restrict__ fbits, unsigned long long* __restrict__ ist,
+                                                    unsigned long long* __restrict__ ibase, LA... la) {
     __shared__ unsigned long long sh[1024];
     const size_t f = blockIdx.x;
-    const uint32_t* b = bits + f * blocks;
+    uint32_t* b = bits + f * blocks;
     unsigned long long* o = off + f * blocks;
-    const unsigned long long t = block_exclusive_scan<unsigned long long>(
+    unsigned long long t = block_exclusive_scan<unsigned long long>(
         [&](long long i) { return (unsigned long long)b[i]; }, [&](long long i, unsigned long long v) { o[i] = v; }, blocks, sh);
+    if constexpr (L::kIntervals) {
+        const L lay{la...};
+        const int nint = lay.nint();
+        unsigned long long* is = ist + f * nint;
+        unsigned long long* ib = ibase + f * nint;           // interval bit starts before padding
+        __syncthreads();
+        for (int i = threadIdx.x; i < nint; i += 1024) {
+            const long long sb = (long long)i * lay.per(), eb = sb + lay.per();
+            const unsigned long long len = (eb < blocks ? o[eb] : t) - o[sb];
+            ib[i] = o[sb];
+            is[i] = ((len + 7) >> 3) + (i < nint - 1 ? 2 : 0);
+        }
+        __syncthreads();
+        const unsigned long long nbytes = block_exclusive_scan<unsigned long long>(
+            [&](long long i) { return is[i]; }, [&](long long i, unsigned long long v) { is[i] = v; }, nint, sh);
+        __syncthreads();
+        for (int j = threadIdx.x; j < blocks; j += 1024) {
+            const int i = lay.interval_of(j);
+            const unsigned long long p = is[i] * 8 + (o[j] - ib[i]);
+            o[j] = p;
+            if (lay.ends_interval(j, blocks)) {
+                const unsigned long long end = p + b[j];
+                b[j] += (uint32_t)((0 - end) & 7) + (i < nint - 1 ? 16u : 0u);
+            }
+        }
+        t = nbytes * 8;
+    }
     if (threadIdx.x == 0) fbits[f] = t;
 }
 
@@ -375,13 +479,17 @@ __device__ __forceinline__ void put_bits(uint32_t* w, int p, uint32_t val, int l
     if ((uint32_t)x) atomicOr(&w[(p >> 5) + 1], (uint32_t)x);
 }
 
-// grid ceil(frames * blocks / 4), 256 threads: one wave per block, LDS words per wave.  A block's words strictly inside its bit
+// grid ceil(frames * blocks / 4), 256 threads: one wave per block, LDS words per wave.  The last block of an interval adds the
+// 1-bit padding to a byte and, unless the interval is the frame's last, the RSTn marker.  A block's words strictly inside its bit
 // range are stored; its first and last words, which it may share with its neighbours, go to first[] / last[] for k_jpeg_edges.
 // No word is written twice and there are no global atomics: per-XCD L2s are not coherent with each other within a kernel.
+template <class L, class... LA>
 __global__ __launch_bounds__(256) void k_jpeg_emit(const int16_t* __restrict__ coef, int blocks, long long total,
                                                    const JTab* __restrict__ tab, const unsigned long long* __restrict__ off,
                                                    const uint32_t* __restrict__ bits, size_t scratch_per_frame,
-                                                   uint32_t* __restrict__ scratch, uint32_t* __restrict__ first, uint32_t* __restrict__ last) {
+                                                   uint32_t* __restrict__ scratch, uint32_t* __restrict__ first, uint32_t* __restrict__ last,
+                                                   LA... la) {
+    const L lay{la...};
     __shared__ uint32_t buf[4][64];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long g = (long long)blockIdx.x * 4 + wv;
@@ -391,25 +499,37 @@ __global__ __launch_bounds__(256) void k_jpeg_emit(const int16_t* __restrict__ c
         const long long f = g / blocks;
         const int j = (int)(g - f * blocks);
         const int16_t* fcoef = coef + (size_t)f * blocks * 64;
-        const int pred = lane == 0 ? dc_pred(fcoef, j) : 0;
-        const LaneCodes lc = lane_codes(tab, fcoef + (size_t)j * 64, lane, j % 6 < 4 ? 0 : 1, pred);
+        const int pred = lane == 0 ? dc_pred(lay, fcoef, j) : 0;
+        const LaneCodes lc = lane_codes(tab + (size_t)f * lay.tab_stride(), fcoef + (size_t)j * 64, lane, table_of(lay, j), pred);
         int pre = lc.bits();                                 // inclusive -> exclusive wave prefix
         for (int o = 1; o < 64; o <<= 1) {
             const int y = __shfl_up(pre, o, 64);
             if (lane >= o) pre += y;
         }
+        const int sum = __shfl(pre, 63, 64);                 // the block's bits
         pre -= lc.bits();
         const unsigned long long b0 = off[g];
         const int s0 = (int)(b0 & 31);
         int p = s0 + pre;
         for (int z = 0; z < lc.nzrl; ++z, p += (int)(lc.zrl & 0xFF)) put_bits(buf[wv], p, lc.zrl >> 8, (int)(lc.zrl & 0xFF));
         put_bits(buf[wv], p, lc.piece, lc.plen);
-        const int end = s0 + (int)bits[g];
-        if (j == blocks - 1 && lane == 0 && (end & 7)) put_bits(buf[wv], end, 0xFFu >> (end & 7), 8 - (end & 7));   // 1-bit padding
+        // With intervals k_jpeg_scan has added the padding and the marker to bits[g]; without, bits[g] is the block's own bits and
+        // spares the shuffle.  `pend` below is read from bits[g] in the first case and derived from the rule in the second:
+        // both MUST equal end + padding + marker bits, which is what the scan added.  (Deriving it in both forms measured 4 %
+        // slower with intervals: profiles/jpeg_refactor_kernel_stats.csv, alt_ rows.)
+        const int end = s0 + (L::kIntervals ? sum : (int)bits[g]);
+        // end of interval: pad with 1-bits to a byte, then the marker unless the interval is the frame's last
+        const bool ends = lay.ends_interval(j, blocks);
+        const int iv = lay.interval_of(j);
+        const bool marker = ends && iv < lay.nint() - 1;
+        if (lane == 0 && ends) {
+            if (end & 7) put_bits(buf[wv], end, 0xFFu >> (end & 7), 8 - (end & 7));
+            if (marker) put_bits(buf[wv], (end + 7) & ~7, 0xFFD0u | (uint32_t)(iv & 7), 16);
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        const int pend = j == blocks - 1 ? (end + 7) & ~7 : end;           // the last block's words include its padding
+        const int pend = L::kIntervals ? s0 + (int)bits[g] : ends ? (end + 7) & ~7 : end;   // the block's words include both
         const int nwords = (pend + 31) >> 5;
         if (lane < nwords) {
             const uint32_t v = __builtin_bswap32(buf[wv][lane]);
@@ -430,23 +550,23 @@ __device__ __forceinline__ void word_range(const unsigned long long* off, const 
 
 // grid ceil(frames * blocks / 256), 256 threads: the words blocks share.  Block g writes its first word unless the previous block
 // ends in it, and its last word: each is the OR of its own part and the first words of the following blocks that start there.
-// EX: bits[] already holds the padding (k_jpeg_scan_ex).
-template <bool EX>
+// With intervals bits[] already holds every padding (k_jpeg_scan); without, the frame's last block is padded here.
+template <class L, class... LA>
 __global__ __launch_bounds__(256) void k_jpeg_edges(int blocks, long long total, const unsigned long long* __restrict__ off,
                                                     const uint32_t* __restrict__ bits, const uint32_t* __restrict__ first,
                                                     const uint32_t* __restrict__ last, size_t scratch_per_frame,
-                                                    uint32_t* __restrict__ scratch) {
+                                                    uint32_t* __restrict__ scratch, LA...) {
     const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
     if (g >= total) return;
     const long long f = g / blocks;
     const int j = (int)(g - f * blocks);
     uint32_t* fs = scratch + (size_t)f * (scratch_per_frame >> 2);
     unsigned long long wf, wl, pf, pl;
-    word_range(off, bits, g, !EX && j == blocks - 1, wf, wl);
+    word_range(off, bits, g, !L::kIntervals && j == blocks - 1, wf, wl);
     auto merged = [&](unsigned long long w, uint32_t v) {   // OR in the first words of the blocks after g that start in word w
         for (int h = j + 1; h < blocks; ++h) {
             unsigned long long hf, hl;
-            word_range(off, bits, g + (h - j), !EX && h == blocks - 1, hf, hl);
+            word_range(off, bits, g + (h - j), !L::kIntervals && h == blocks - 1, hf, hl);
             if (hf != w) break;
             v |= first[g + (h - j)];
         }
@@ -471,11 +591,21 @@ __device__ __forceinline__ bool marker_at(const unsigned long long* __restrict__
     return lo < nint && is[lo] == p + 2;
 }
 
-// grid (segments per frame, frames of the chunk), 256 threads: FF bytes to stuff per 4 KiB segment of the scan (EX: not the markers')
-template <bool EX>
+// The stuffing rule: byte b at position p of a frame's stream (is: the frame's interval starts) gets a 0 after it when it is
+// 0xFF and not the first byte of a restart marker.  k_jpeg_ffcount counts by it what k_jpeg_scatter writes by it.
+template <class L>
+__device__ __forceinline__ bool stuffed(const L& lay, const unsigned long long* __restrict__ is, uint32_t b, unsigned long long p) {
+    return b == 0xFF && !(L::kIntervals && lay.nint() > 1 && marker_at(is, lay.nint(), p));
+}
+
+__device__ __forceinline__ uint8_t byte_of(const uint32_t (&w)[4], int k) { return (uint8_t)(w[k >> 2] >> (8 * (k & 3))); }
+
+// grid (segments per frame, frames of the chunk), 256 threads: bytes to stuff per 4 KiB segment of the scan
+template <class L, class... LA>
 __global__ __launch_bounds__(256) void k_jpeg_ffcount(const uint8_t* __restrict__ scratch, size_t scratch_per_frame,
                                                       const unsigned long long* __restrict__ fbits, int segs_per_frame,
-                                                      uint32_t* __restrict__ segcnt, const unsigned long long* __restrict__ ist, int nint) {
+                                                      uint32_t* __restrict__ segcnt, const unsigned long long* __restrict__ ist, LA... la) {
+    const L lay{la...};
     __shared__ int sh[4];
     const int f = blockIdx.y, seg = blockIdx.x, tid = threadIdx.x;
     const unsigned long long nbytes = (fbits[f] + 7) >> 3;
@@ -488,10 +618,7 @@ __global__ __launch_bounds__(256) void k_jpeg_ffcount(const uint8_t* __restrict_
     if (i0 < nbytes) {
         const uint4 q = *reinterpret_cast<const uint4*>(scratch + (size_t)f * scratch_per_frame + i0);
         const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-        for (int k = 0; k < 16; ++k) {
-            const bool ff = (i0 + k < nbytes) && ((w[k >> 2] >> (8 * (k & 3))) & 0xFF) == 0xFF;
-            cnt += ff && !(EX && nint > 1 && marker_at(ist + (size_t)f * nint, nint, i0 + k));
-        }
+        for (int k = 0; k < 16; ++k) cnt += (i0 + k < nbytes) && stuffed(lay, ist + (size_t)f * lay.nint(), byte_of(w, k), i0 + k);
     }
     cnt = wave_sum(cnt);
     if ((tid & 63) == 0) sh[tid >> 6] = cnt;
@@ -520,19 +647,20 @@ __global__ __launch_bounds__(1024) void k_jpeg_sizes(uint32_t* __restrict__ segc
     }
 }
 
-// grid (segments per frame, frames of the chunk), 256 threads: header, stuffed scan bytes and EOI of each frame that fits
-// EX: restart markers are copied unstuffed; hlen != nullptr: frame f's header is hlen[f] bytes at hdr + f * hdr_stride (optimize)
-template <bool EX>
+// grid (segments per frame, frames of the chunk), 256 threads: header, stuffed scan bytes and EOI of each frame that fits.
+// Restart markers are copied unstuffed; hlen != nullptr: frame f's header is hlen[f] bytes at hdr + f * hdr_stride (optimize)
+template <class L, class... LA>
 __global__ __launch_bounds__(256) void k_jpeg_scatter(const uint8_t* __restrict__ scratch, size_t scratch_per_frame,
                                                       const unsigned long long* __restrict__ fbits, const uint32_t* __restrict__ segoff,
                                                       int segs_per_frame, const uint8_t* __restrict__ hdr, int hdr_len, int f0,
                                                       const long long* __restrict__ fsize, const long long* __restrict__ foff,
                                                       uint8_t* __restrict__ out, long long capacity,
-                                                      const unsigned long long* __restrict__ ist, int nint, int hdr_stride,
-                                                      const int* __restrict__ hlen) {
+                                                      const unsigned long long* __restrict__ ist, int hdr_stride,
+                                                      const int* __restrict__ hlen, LA... la) {
+    const L lay{la...};
     __shared__ int sh[256];
     const int f = blockIdx.y, seg = blockIdx.x, tid = threadIdx.x;
-    if (EX && hlen) { hdr += (size_t)f * hdr_stride; hdr_len = hlen[f]; }
+    if (L::kIntervals && hlen) { hdr += (size_t)f * hdr_stride; hdr_len = hlen[f]; }
     const unsigned long long nbytes = (fbits[f] + 7) >> 3;
     const long long o = foff[f0 + f], size = fsize[f0 + f];
     if (o + size > capacity) return;                         // the caller grows its buffer and re-runs
@@ -548,10 +676,7 @@ __global__ __launch_bounds__(256) void k_jpeg_scatter(const uint8_t* __restrict_
     if (i0 < nbytes) {
         const uint4 q = *reinterpret_cast<const uint4*>(scratch + (size_t)f * scratch_per_frame + i0);
         w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-        for (int k = 0; k < 16; ++k) {
-            const bool ff = (i0 + k < nbytes) && ((w[k >> 2] >> (8 * (k & 3))) & 0xFF) == 0xFF;
-            cnt += ff && !(EX && nint > 1 && marker_at(ist + (size_t)f * nint, nint, i0 + k));
-        }
+        for (int k = 0; k < 16; ++k) cnt += (i0 + k < nbytes) && stuffed(lay, ist + (size_t)f * lay.nint(), byte_of(w, k), i0 + k);
     }
     sh[tid] = cnt;
     __syncthreads();
@@ -564,206 +689,33 @@ __global__ __launch_bounds__(256) void k_jpeg_scatter(const uint8_t* __restrict_
     if (i0 >= nbytes) return;
     unsigned long long q = hdr_len + i0 + segoff[(size_t)f * segs_per_frame + seg] + (unsigned long long)(sh[tid] - cnt);
     for (int k = 0; k < 16 && i0 + k < nbytes; ++k) {
-        const uint8_t b = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+        const uint8_t b = byte_of(w, k);
         dst[q++] = b;
-        if (b == 0xFF && !(EX && nint > 1 && marker_at(ist + (size_t)f * nint, nint, i0 + k))) dst[q++] = 0;
-    }
-}
-
-// ---- the optioned path (trl_jpeg_create_ex with anything but the defaults) --------------------------------------------------------
-// Blocks per MCU (bpm) 3 / 4 / 6, a restart interval of R MCUs (no DRI: R = the frame's MCU count, one interval), and with
-// `optimize` a code table and a header per frame.  The default path above is untouched by it.
-
-// grid (ceil(mcux / MPW), mcuy, frames of the chunk), 256 threads: a 8 x 64 pixel strip of 8 x 8 MCUs (S = 0: Y Cb Cr) or of 16 x 8
-// MCUs (S = 1: Y0 Y1 Cb Cr, h2v1 average with bias 0,1,0,1...).  No vertical subsampling, so rows are only replicated.
-template <int S>
-__global__ __launch_bounds__(256) void k_jpeg_blocks_ex(const uint8_t* __restrict__ src, long long frame_stride, int H, int W,
-                                                        int mcux, int mcuy, const JTab* __restrict__ tab, int16_t* __restrict__ coef) {
-    constexpr int MW = S == 0 ? 8 : 16, BPM = S == 0 ? 3 : 4, MPW = 64 / MW, NB = MPW * BPM, NY = BPM - 2;
-    __shared__ int pix[3][8][64];
-    __shared__ int blk[NB][64];
-    __shared__ int16_t qz[NB][64];
-    const int tid = threadIdx.x, mx0 = blockIdx.x * MPW, my = blockIdx.y, f = blockIdx.z;
-    const uint8_t* fr = src + (size_t)f * frame_stride;
-    for (int i = tid; i < 8 * 64; i += 256) {
-        const int r = i >> 6, c = i & 63;
-        const int gy = min(8 * my + r, H - 1), gx = min(64 * (int)blockIdx.x + c, W - 1);
-        const uint8_t* p = fr + ((size_t)gy * W + gx) * 3;
-        const int B = p[0], G = p[1], R = p[2];
-        pix[0][r][c] = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
-        pix[1][r][c] = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
-        pix[2][r][c] = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
-    }
-    __syncthreads();
-    for (int i = tid; i < NB * 64; i += 256) {
-        const int b = i >> 6, r = (i >> 3) & 7, c = i & 7, m = b / BPM, kind = b % BPM;
-        int v;
-        if (S == 0) {
-            v = pix[kind][r][m * 8 + c];
-        } else if (kind < NY) {
-            v = pix[0][r][m * 16 + kind * 8 + c];
-        } else {
-            const int cc = 2 * (m * 8 + c);
-            v = (pix[kind - 1][r][cc] + pix[kind - 1][r][cc + 1] + (c & 1)) >> 1;
-        }
-        blk[b][(r << 3) | c] = v - 128;
-    }
-    __syncthreads();
-    if (tid < NB * 8) fdct8<true>(&blk[tid >> 3][(tid & 7) * 8], 1);
-    __syncthreads();
-    if (tid < NB * 8) fdct8<false>(&blk[tid >> 3][tid & 7], 8);
-    __syncthreads();
-    for (int i = tid; i < NB * 64; i += 256) {
-        const int b = i >> 6, z = i & 63;
-        const int c = blk[b][c_zigzag[z]], d = tab->qdiv[(b % BPM) < NY ? 0 : 1][c_zigzag[z]];
-        const int a = ((c < 0 ? -c : c) + (d >> 1)) / d;
-        qz[b][z] = (int16_t)(c < 0 ? -a : a);
-    }
-    __syncthreads();
-    const int bw = (W + 7) >> 3;
-    for (int i = tid; i < NB * 64; i += 256) {
-        const int b = i >> 6, z = i & 63, m = b / BPM, kind = b % BPM, mx = mx0 + m;
-        if (mx >= mcux) continue;
-        int v = qz[b][z];
-        if (S == 1 && kind == 1 && 2 * mx + 1 >= bw) v = z ? 0 : qz[b - 1][0];   // right dummy: zero AC, DC of Y0
-        coef[((((size_t)f * mcuy + my) * mcux + mx) * BPM + kind) * 64 + z] = (int16_t)v;
-    }
-}
-
-// the DC predictor of block j of a frame: the component's previous block, 0 at the start of each restart interval
-__device__ __forceinline__ int dc_pred_ex(const int16_t* __restrict__ fcoef, int j, int bpm, int R) {
-    const int mcu = j / bpm, kind = j % bpm, ny = bpm - 2;
-    if (kind >= 1 && kind < ny) return fcoef[(size_t)(j - 1) * 64];
-    if (mcu % R == 0) return 0;
-    return fcoef[(size_t)(j - bpm + (kind == 0 ? ny - 1 : 0)) * 64];
-}
-
-// grid ceil(frames * blocks / 4), 256 threads: one wave per block; tab_stride != 0: a table per frame (optimize)
-__global__ __launch_bounds__(256) void k_jpeg_bits_ex(const int16_t* __restrict__ coef, int blocks, long long total, int bpm, int R,
-                                                      const JTab* __restrict__ tab, int tab_stride, uint32_t* __restrict__ bits) {
-    const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (g >= total) return;                                  // wave-uniform
-    const long long f = g / blocks;
-    const int j = (int)(g - f * blocks);
-    const int16_t* fcoef = coef + (size_t)f * blocks * 64;
-    const int pred = lane == 0 ? dc_pred_ex(fcoef, j, bpm, R) : 0;
-    const LaneCodes lc = lane_codes(tab + (size_t)f * tab_stride, fcoef + (size_t)j * 64, lane, j % bpm < bpm - 2 ? 0 : 1, pred);
-    const int s = wave_sum(lc.bits());
-    if (lane == 0) bits[g] = (uint32_t)s;
-}
-
-// grid = frames of the chunk, 1024 threads.  The frame's scan with restart intervals is the intervals' bits back to back, each
-// padded to a byte and (but for the last) followed by the two marker bytes, which are part of the stream k_jpeg_emit_ex writes:
-//   off[j]   block j's bit offset in that stream (its offset within the interval + the interval's byte start)
-//   bits[j]  the interval's last block: its bits + the padding + 16 marker bits, so that every word has one owner as before
-//   ist[i]   interval i's byte start (k_jpeg_ffcount / k_jpeg_scatter find the marker bytes, which are not stuffed, by it)
-//   fbits    the stream's length in bits (whole bytes)
-__global__ __launch_bounds__(1024) void k_jpeg_scan_ex(uint32_t* __restrict__ bits, int blocks, int bpm, int R, int nint,
-                                                       unsigned long long* __restrict__ off, unsigned long long* __restrict__ ist,
-                                                       unsigned long long* __restrict__ ibase, unsigned long long* __restrict__ fbits) {
-    __shared__ unsigned long long sh[1024];
-    const size_t f = blockIdx.x;
-    uint32_t* b = bits + f * blocks;
-    unsigned long long* o = off + f * blocks;
-    unsigned long long* is = ist + f * nint;
-    unsigned long long* ib = ibase + f * nint;
-    const int per = R * bpm;                                 // blocks per interval
-    const unsigned long long t = block_exclusive_scan<unsigned long long>(
-        [&](long long i) { return (unsigned long long)b[i]; }, [&](long long i, unsigned long long v) { o[i] = v; }, blocks, sh);
-    __syncthreads();
-    for (int i = threadIdx.x; i < nint; i += 1024) {
-        const long long sb = (long long)i * per, eb = sb + per;
-        const unsigned long long len = (eb < blocks ? o[eb] : t) - o[sb];
-        ib[i] = o[sb];
-        is[i] = ((len + 7) >> 3) + (i < nint - 1 ? 2 : 0);
-    }
-    __syncthreads();
-    const unsigned long long nbytes = block_exclusive_scan<unsigned long long>(
-        [&](long long i) { return is[i]; }, [&](long long i, unsigned long long v) { is[i] = v; }, nint, sh);
-    __syncthreads();
-    for (int j = threadIdx.x; j < blocks; j += 1024) {
-        const int i = j / per;
-        const unsigned long long p = is[i] * 8 + (o[j] - ib[i]);
-        o[j] = p;
-        if (j == blocks - 1 || (j + 1) % per == 0) {
-            const unsigned long long end = p + b[j];
-            b[j] += (uint32_t)((0 - end) & 7) + (i < nint - 1 ? 16u : 0u);
-        }
-    }
-    if (threadIdx.x == 0) fbits[f] = nbytes * 8;
-}
-
-// as k_jpeg_emit; the last block of each interval adds the 1-bit padding and, but for the last interval, the RSTn marker
-__global__ __launch_bounds__(256) void k_jpeg_emit_ex(const int16_t* __restrict__ coef, int blocks, long long total, int bpm, int R,
-                                                      int nint, const JTab* __restrict__ tab, int tab_stride,
-                                                      const unsigned long long* __restrict__ off, const uint32_t* __restrict__ bits,
-                                                      size_t scratch_per_frame, uint32_t* __restrict__ scratch,
-                                                      uint32_t* __restrict__ first, uint32_t* __restrict__ last) {
-    __shared__ uint32_t buf[4][64];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long g = (long long)blockIdx.x * 4 + wv;
-    buf[wv][lane] = 0;
-    __syncthreads();
-    if (g < total) {                                         // wave-uniform
-        const long long f = g / blocks;
-        const int j = (int)(g - f * blocks);
-        const int16_t* fcoef = coef + (size_t)f * blocks * 64;
-        const int pred = lane == 0 ? dc_pred_ex(fcoef, j, bpm, R) : 0;
-        const LaneCodes lc = lane_codes(tab + (size_t)f * tab_stride, fcoef + (size_t)j * 64, lane, j % bpm < bpm - 2 ? 0 : 1, pred);
-        int pre = lc.bits();                                 // inclusive -> exclusive wave prefix
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(pre, o, 64);
-            if (lane >= o) pre += y;
-        }
-        const int raw = __shfl(pre, 63, 64);                 // the block's own bits
-        pre -= lc.bits();
-        const unsigned long long b0 = off[g];
-        const int s0 = (int)(b0 & 31);
-        int p = s0 + pre;
-        for (int z = 0; z < lc.nzrl; ++z, p += (int)(lc.zrl & 0xFF)) put_bits(buf[wv], p, lc.zrl >> 8, (int)(lc.zrl & 0xFF));
-        put_bits(buf[wv], p, lc.piece, lc.plen);
-        const int per = R * bpm, iv = j / per;
-        if (lane == 0 && (j == blocks - 1 || (j + 1) % per == 0)) {
-            int end = s0 + raw;
-            if (end & 7) { put_bits(buf[wv], end, 0xFFu >> (end & 7), 8 - (end & 7)); end = (end + 7) & ~7; }
-            if (iv < nint - 1) put_bits(buf[wv], end, 0xFFD0u | (uint32_t)(iv & 7), 16);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        const int nwords = (s0 + (int)bits[g] + 31) >> 5;    // bits[]: padding and marker included (k_jpeg_scan_ex)
-        if (lane < nwords) {
-            const uint32_t v = __builtin_bswap32(buf[wv][lane]);
-            if (lane == 0) first[g] = v;
-            else if (lane == nwords - 1) last[g] = v;
-            else scratch[(size_t)f * (scratch_per_frame >> 2) + (b0 >> 5) + lane] = v;
-        }
+        if (stuffed(lay, ist + (size_t)f * lay.nint(), b, i0 + k)) dst[q++] = 0;
     }
 }
 
 // optimize, pass 1.  grid (ceil(blocks / 64), frames of the chunk), 256 threads: a wave per block, 16 blocks per wave; the symbols
 // the entropy coder will emit, counted in LDS and added to the frame's four histograms [DC luma, AC luma, DC chroma, AC chroma]
 // (exact integer counts: the order of the additions is free).  hist is zeroed before the launch.
-__global__ __launch_bounds__(256) void k_jpeg_hist(const int16_t* __restrict__ coef, int blocks, int bpm, int R, uint32_t* __restrict__ hist) {
-    __shared__ uint32_t h[4 * 256];
+__global__ __launch_bounds__(256) void k_jpeg_hist(const int16_t* __restrict__ coef, int blocks, uint32_t* __restrict__ hist, RunLayout lay) {
+    __shared__ uint32_t h[kHist];
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, f = blockIdx.y;
-    for (int i = tid; i < 1024; i += 256) h[i] = 0;
+    for (int i = tid; i < kHist; i += 256) h[i] = 0;
     __syncthreads();
     const int16_t* fcoef = coef + (size_t)f * blocks * 64;
     for (int it = 0; it < 16; ++it) {
         const int j = blockIdx.x * 64 + it * 4 + wv;
         if (j >= blocks) break;                              // wave-uniform
-        const int t = j % bpm < bpm - 2 ? 0 : 1;
+        const int pred = lane == 0 ? dc_pred(lay, fcoef, j) : 0;
+        const int t = table_of(lay, j);
         const int v = fcoef[(size_t)j * 64 + lane];
         const unsigned long long mask = __ballot(v != 0);
         if (lane == 0) {
-            const int diff = v - dc_pred_ex(fcoef, j, bpm, R);
+            const int diff = v - pred;
             atomicAdd(&h[(2 * t) * 256 + nbits_of(diff < 0 ? -diff : diff)], 1u);
         } else if (v != 0) {
-            const unsigned long long below = mask & ((1ull << lane) - 1ull) & ~1ull;
-            const int prev = below ? 63 - __clzll(below) : 0;
-            const int run = lane - prev - 1;
+            const int run = run_before(mask, lane);
             if (run >> 4) atomicAdd(&h[(2 * t + 1) * 256 + 0xF0], (uint32_t)(run >> 4));
             atomicAdd(&h[(2 * t + 1) * 256 + (((run & 15) << 4) | nbits_of(v < 0 ? -v : v))], 1u);
         } else if (lane == 63) {
@@ -771,8 +723,8 @@ __global__ __launch_bounds__(256) void k_jpeg_hist(const int16_t* __restrict__ c
         }
     }
     __syncthreads();
-    for (int i = tid; i < 1024; i += 256)
-        if (h[i]) atomicAdd(&hist[(size_t)f * 1024 + i], h[i]);
+    for (int i = tid; i < kHist; i += 256)
+        if (h[i]) atomicAdd(&hist[(size_t)f * kHist + i], h[i]);
 }
 
 // optimize, between the passes.  grid = frames of the chunk, 256 threads: wave t builds table t of the frame on its lane 0
@@ -788,7 +740,7 @@ __global__ __launch_bounds__(256) void k_jpeg_tables(const uint32_t* __restrict_
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, f = blockIdx.x;
     JTab* ft = ftab + f;
     if (lane == 0) {
-        nv[wv] = trl_jpeg_hufftab(hist + (size_t)f * 1024 + wv * 256, hb[wv], hv[wv], &work[wv], nullptr);
+        nv[wv] = trl_jpeg_hufftab(hist + (size_t)f * kHist + wv * 256, hb[wv], hv[wv], &work[wv], nullptr);
         uint32_t* codes = (wv & 1) ? ft->ac[wv >> 1] : ft->dc[wv >> 1];
         int code = 0, k = 0;
         for (int len = 1; len <= 16; ++len) {
@@ -844,89 +796,99 @@ struct trl_jpeg {
     bool ex = false, optimize = false;
     int sampling = 2, bpm = 6, R = 0, nint = 1, dht_at = 0, tail_at = 0;
     unsigned long long* ist = nullptr;   // [chunk][nint] interval byte starts
-    unsigned long long* ibase = nullptr; // [chunk][nint] interval bit starts before padding (k_jpeg_scan_ex's own)
+    unsigned long long* ibase = nullptr; // [chunk][nint] interval bit starts before padding (k_jpeg_scan's own)
     uint32_t* hist = nullptr;            // optimize: [chunk][4][256] symbol counts
     JTab* ftab = nullptr;                //           [chunk] code tables
-    uint8_t* fhdr = nullptr;             //           [chunk][1024] headers
+    uint8_t* fhdr = nullptr;             //           [chunk][kHdrCap] headers
     int* hlen = nullptr;                 //           [chunk] their lengths
 };
 
-static int jpeg_create(const char* who, int device, int H, int W, const trl_jpeg_options* opt, int max_frames, trl_jpeg** out);
+// The device workspace of an encoder that runs C frames at a time, carved from `a` into e's pointers; over a counting arena, its
+// size.  The only place that knows what a block or a frame costs: e->chunk and the allocation come from dry runs of it.
+static void carve(Arena& a, size_t C, trl_jpeg* e) {
+    auto take = [&](auto*& p, size_t n) { p = static_cast<std::remove_reference_t<decltype(p)>>(a.alloc(n * sizeof(*p))); };
+    const size_t B = C * (size_t)e->blocks, NI = e->ex ? C * (size_t)e->nint : 0;
+    take(e->tab, 1); take(e->hdr, kHdrCap);
+    take(e->coef, B * 64); take(e->bits, B); take(e->off, B); take(e->first, B); take(e->last, B);
+    take(e->fbits, C); take(e->segcnt, C * e->segs_per_frame); take(e->scratch, C * e->scratch_per_frame);
+    take(e->fsize, (size_t)e->max_frames); take(e->foff, (size_t)e->max_frames + 1);
+    take(e->ist, NI); take(e->ibase, NI);
+    if (e->optimize) { take(e->hist, C * kHist); take(e->ftab, C); take(e->fhdr, C * kHdrCap); take(e->hlen, C); }
+}
 
-// one chunk of frames on the optioned path: the stages of trl_jpeg_encode with the interval-aware kernels, and with `optimize` the
-// histogram and table kernels between the coefficients and the bit counts (tables never visit the host)
-static int encode_chunk_ex(trl_jpeg* e, const uint8_t* src, long long frame_stride, int cn, int f0, uint8_t* d_out, long long capacity,
-                           hipStream_t s) {
+// One stage of the pipeline: kernel k<FixedLayout>(args) or, for an encoder with options, k<RunLayout>(args, lay).
+#define JPEG_STAGE(k, grid, block, ...)                                                                          \
+    do {                                                                                                         \
+        if (e->ex) hipLaunchKernelGGL((k<RunLayout, RunLayout>), grid, block, 0, s, __VA_ARGS__, lay);           \
+        else hipLaunchKernelGGL((k<FixedLayout>), grid, block, 0, s, __VA_ARGS__);                               \
+        TRL_LAUNCH_CHECK();                                                                                      \
+    } while (0)
+
+template <int S>
+static void launch_blocks(const trl_jpeg* e, const uint8_t* src, long long frame_stride, int cn, hipStream_t s) {
+    hipLaunchKernelGGL(k_jpeg_blocks<S>, dim3((e->mcux + Sampling<S>::kMcus - 1) / Sampling<S>::kMcus, e->mcuy, cn), dim3(256), 0, s, src,
+                       frame_stride, e->H, e->W, e->mcux, e->mcuy, e->tab, e->coef);
+}
+
+// frames f0 .. f0 + cn of a batch, cn <= e->chunk: every kernel of the pipeline, on stream s
+static int encode_chunk(trl_jpeg* e, const uint8_t* src, long long frame_stride, int cn, int f0, uint8_t* d_out, long long capacity,
+                        hipStream_t s) {
     const long long total = (long long)cn * e->blocks;
-    if (e->sampling == 2)
-        hipLaunchKernelGGL(k_jpeg_blocks, dim3((e->mcux + kMcuPerWg - 1) / kMcuPerWg, e->mcuy, cn), dim3(256), 0, s, src, frame_stride,
-                           e->H, e->W, e->mcux, e->mcuy, e->tab, e->coef);
-    else if (e->sampling == 1)
-        hipLaunchKernelGGL(k_jpeg_blocks_ex<1>, dim3((e->mcux + 3) / 4, e->mcuy, cn), dim3(256), 0, s, src, frame_stride, e->H, e->W,
-                           e->mcux, e->mcuy, e->tab, e->coef);
-    else
-        hipLaunchKernelGGL(k_jpeg_blocks_ex<0>, dim3((e->mcux + 7) / 8, e->mcuy, cn), dim3(256), 0, s, src, frame_stride, e->H, e->W,
-                           e->mcux, e->mcuy, e->tab, e->coef);
+    const RunLayout lay{e->bpm, e->R, e->nint, e->optimize ? 1 : 0};
+    if (e->sampling == 2) launch_blocks<2>(e, src, frame_stride, cn, s);
+    else if (e->sampling == 1) launch_blocks<1>(e, src, frame_stride, cn, s);
+    else launch_blocks<0>(e, src, frame_stride, cn, s);
     TRL_LAUNCH_CHECK();
     const JTab* tab = e->tab;
-    int tab_stride = 0;
-    if (e->optimize) {
-        TRL_HIP(hipMemsetAsync(e->hist, 0, (size_t)cn * 4096, s));
-        hipLaunchKernelGGL(k_jpeg_hist, dim3((e->blocks + 63) / 64, cn), dim3(256), 0, s, e->coef, e->blocks, e->bpm, e->R, e->hist);
+    if (e->optimize) {                                       // a table and a header per frame, made on the device
+        TRL_HIP(hipMemsetAsync(e->hist, 0, (size_t)cn * kHist * sizeof(*e->hist), s));
+        hipLaunchKernelGGL(k_jpeg_hist, dim3((e->blocks + 63) / 64, cn), dim3(256), 0, s, e->coef, e->blocks, e->hist, lay);
         TRL_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_jpeg_tables, dim3(cn), dim3(256), 0, s, e->hist, e->tab, e->hdr, e->hdr_len, e->dht_at, e->tail_at, e->ftab,
-                           e->fhdr, 1024, e->hlen);
+                           e->fhdr, kHdrCap, e->hlen);
         TRL_LAUNCH_CHECK();
         tab = e->ftab;
-        tab_stride = 1;
     }
-    const unsigned wgs = (unsigned)((total + 3) / 4);
-    hipLaunchKernelGGL(k_jpeg_bits_ex, dim3(wgs), dim3(256), 0, s, e->coef, e->blocks, total, e->bpm, e->R, tab, tab_stride, e->bits);
-    TRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jpeg_scan_ex, dim3(cn), dim3(1024), 0, s, e->bits, e->blocks, e->bpm, e->R, e->nint, e->off, e->ist, e->ibase,
-                       e->fbits);
-    TRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jpeg_emit_ex, dim3(wgs), dim3(256), 0, s, e->coef, e->blocks, total, e->bpm, e->R, e->nint, tab, tab_stride,
-                       e->off, e->bits, e->scratch_per_frame, (uint32_t*)e->scratch, e->first, e->last);
-    TRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jpeg_edges<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, e->blocks, total, e->off, e->bits,
-                       e->first, e->last, e->scratch_per_frame, (uint32_t*)e->scratch);
-    TRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jpeg_ffcount<true>, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
-                       e->segs_per_frame, e->segcnt, e->ist, e->nint);
-    TRL_LAUNCH_CHECK();
+    const dim3 waves((unsigned)((total + 3) / 4)), threads((unsigned)((total + 255) / 256)), segs(e->segs_per_frame, cn);
+    JPEG_STAGE(k_jpeg_bits, waves, dim3(256), e->coef, e->blocks, total, tab, e->bits);
+    JPEG_STAGE(k_jpeg_scan, dim3(cn), dim3(1024), e->bits, e->blocks, e->off, e->fbits, e->ist, e->ibase);
+    JPEG_STAGE(k_jpeg_emit, waves, dim3(256), e->coef, e->blocks, total, tab, e->off, e->bits, e->scratch_per_frame,
+               (uint32_t*)e->scratch, e->first, e->last);
+    JPEG_STAGE(k_jpeg_edges, threads, dim3(256), e->blocks, total, e->off, e->bits, e->first, e->last, e->scratch_per_frame,
+               (uint32_t*)e->scratch);
+    JPEG_STAGE(k_jpeg_ffcount, segs, dim3(256), e->scratch, e->scratch_per_frame, e->fbits, e->segs_per_frame, e->segcnt, e->ist);
     hipLaunchKernelGGL(k_jpeg_sizes, dim3(1), dim3(1024), 0, s, e->segcnt, e->segs_per_frame, e->fbits, cn, f0, e->hdr_len, e->hlen,
                        e->fsize, e->foff);
     TRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_jpeg_scatter<true>, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
-                       e->segcnt, e->segs_per_frame, e->optimize ? e->fhdr : e->hdr, e->hdr_len, f0, e->fsize, e->foff, d_out, capacity,
-                       e->ist, e->nint, e->optimize ? 1024 : 0, e->hlen);
-    TRL_LAUNCH_CHECK();
+    JPEG_STAGE(k_jpeg_scatter, segs, dim3(256), e->scratch, e->scratch_per_frame, e->fbits, e->segcnt, e->segs_per_frame,
+               e->optimize ? e->fhdr : e->hdr, e->hdr_len, f0, e->fsize, e->foff, d_out, capacity, e->ist, e->optimize ? kHdrCap : 0,
+               e->hlen);
+    return TRL_OK;
+}
+#undef JPEG_STAGE
+
+static int jpeg_header(const char* who, int H, int W, const trl_jpeg_options* opt, uint8_t* buf, size_t cap, int* len) {
+    JOpt o;
+    TRL_CHECK(resolve_options(who, H, W, opt, &o));
+    if (!len || (!buf && cap)) { trl_set_error("%s: null argument", who); return TRL_ERR_INVALID; }
+    const size_t n = header_bytes(H, W, o.quality, o.sampling, o.dri, nullptr);
+    *len = (int)n;
+    if (cap < n) { trl_set_error("%s: %zu bytes needed, capacity %zu", who, n, cap); return TRL_ERR_CAPACITY; }
+    header_bytes(H, W, o.quality, o.sampling, o.dri, buf);
     return TRL_OK;
 }
 
+static int jpeg_create(const char* who, int device, int H, int W, const trl_jpeg_options* opt, int max_frames, trl_jpeg** out);
 
 extern "C" {
 
 int trl_jpeg_header(int H, int W, int quality, uint8_t* buf, size_t cap, int* len) {
-    TRL_CHECK(check_shape(H, W));
-    if (!len || (!buf && cap)) { trl_set_error("trl_jpeg_header: null argument"); return TRL_ERR_INVALID; }
-    const size_t n = header_bytes(H, W, quality, 2, 0, nullptr);
-    *len = (int)n;
-    if (cap < n) { trl_set_error("trl_jpeg_header: %zu bytes needed, capacity %zu", n, cap); return TRL_ERR_CAPACITY; }
-    header_bytes(H, W, quality, 2, 0, buf);
-    return TRL_OK;
+    const trl_jpeg_options opt = {quality, 2, 0, 0, 0};
+    return jpeg_header("trl_jpeg_header", H, W, &opt, buf, cap, len);
 }
 
 int trl_jpeg_header_ex(int H, int W, const trl_jpeg_options* opt, uint8_t* buf, size_t cap, int* len) {
-    JOpt o;
-    TRL_CHECK(resolve_options("trl_jpeg_header_ex", H, W, opt, &o));
-    if (!len || (!buf && cap)) { trl_set_error("trl_jpeg_header_ex: null argument"); return TRL_ERR_INVALID; }
-    const size_t n = header_bytes(H, W, o.quality, o.sampling, o.dri, nullptr);
-    *len = (int)n;
-    if (cap < n) { trl_set_error("trl_jpeg_header_ex: %zu bytes needed, capacity %zu", n, cap); return TRL_ERR_CAPACITY; }
-    header_bytes(H, W, o.quality, o.sampling, o.dri, buf);
-    return TRL_OK;
+    return jpeg_header("trl_jpeg_header_ex", H, W, opt, buf, cap, len);
 }
 
 int trl_jpeg_optimal_table(const uint32_t* hist, uint8_t* bits, uint8_t* vals, int* nvals, int* maxlen) {
@@ -967,38 +929,11 @@ int trl_jpeg_encode(trl_jpeg* e, const uint8_t* d_bgr, int n, long long frame_st
     TRL_HIP(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     TRL_HIP(hipMemsetAsync(e->foff, 0, sizeof(long long), s));
-    for (int f0 = 0; f0 < n; f0 += e->chunk) {
-        const int cn = std::min(e->chunk, n - f0);
-        const long long total = (long long)cn * e->blocks;
-        if (e->ex) { TRL_CHECK(encode_chunk_ex(e, d_bgr + (size_t)f0 * frame_stride, frame_stride, cn, f0, d_out, capacity, s)); continue; }
-        hipLaunchKernelGGL(k_jpeg_blocks, dim3((e->mcux + kMcuPerWg - 1) / kMcuPerWg, e->mcuy, cn), dim3(256), 0, s,
-                           d_bgr + (size_t)f0 * frame_stride, frame_stride, e->H, e->W, e->mcux, e->mcuy, e->tab, e->coef);
-        TRL_LAUNCH_CHECK();
-        const unsigned wgs = (unsigned)((total + 3) / 4);
-        hipLaunchKernelGGL(k_jpeg_bits, dim3(wgs), dim3(256), 0, s, e->coef, e->blocks, total, e->tab, e->bits);
-        TRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_jpeg_scan, dim3(cn), dim3(1024), 0, s, e->bits, e->blocks, e->off, e->fbits);
-        TRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_jpeg_emit, dim3(wgs), dim3(256), 0, s, e->coef, e->blocks, total, e->tab, e->off, e->bits,
-                           e->scratch_per_frame, (uint32_t*)e->scratch, e->first, e->last);
-        TRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_jpeg_edges<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, e->blocks, total, e->off, e->bits,
-                           e->first, e->last, e->scratch_per_frame, (uint32_t*)e->scratch);
-        TRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_jpeg_ffcount<false>, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
-                           e->segs_per_frame, e->segcnt, nullptr, 0);
-        TRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_jpeg_sizes, dim3(1), dim3(1024), 0, s, e->segcnt, e->segs_per_frame, e->fbits, cn, f0, e->hdr_len,
-                           nullptr, e->fsize, e->foff);
-        TRL_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_jpeg_scatter<false>, dim3(e->segs_per_frame, cn), dim3(256), 0, s, e->scratch, e->scratch_per_frame, e->fbits,
-                           e->segcnt, e->segs_per_frame, e->hdr, e->hdr_len, f0, e->fsize, e->foff, d_out, capacity,
-                           nullptr, 0, 0, nullptr);
-        TRL_LAUNCH_CHECK();
-    }
-    TRL_HIP(hipMemcpyAsync(e->h_sizes, e->fsize, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    for (int f0 = 0; f0 < n; f0 += e->chunk)
+        TRL_CHECK(encode_chunk(e, d_bgr + (size_t)f0 * frame_stride, frame_stride, std::min(e->chunk, n - f0), f0, d_out, capacity, s));
+    TRL_HIP(hipMemcpyAsync(e->h_sizes, e->fsize, (size_t)n * sizeof(*e->fsize), hipMemcpyDeviceToHost, s));
     TRL_HIP(hipStreamSynchronize(s));
-    memcpy(h_sizes, e->h_sizes, (size_t)n * 8);
+    memcpy(h_sizes, e->h_sizes, (size_t)n * sizeof(*e->fsize));
     return TRL_OK;
 }
 
@@ -1020,11 +955,10 @@ static int jpeg_create(const char* who, int device, int H, int W, const trl_jpeg
     e->nint = (nmcu + e->R - 1) / e->R;
     e->scratch_per_frame = (size_t)e->blocks * (kMaxBlockBits / 8);
     e->segs_per_frame = (int)((e->scratch_per_frame + kSeg - 1) / kSeg);
-    const size_t NI = e->ex ? (size_t)e->nint : 0, OPT = e->optimize ? 1 : 0;
-    const size_t per_frame = (size_t)e->blocks * (128 + 4 + 8 + 8) + e->scratch_per_frame + (size_t)e->segs_per_frame * 4 + 8 + NI * 16 +
-                             OPT * (4096 + sizeof(JTab) + 1024 + 4);
-    e->chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)max_frames, kChunkBudget / per_frame));
-    uint8_t hdr[1024];
+    auto bytes = [&](size_t C) { Arena count = Arena::counter(); carve(count, C, e); return count.off; };
+    e->chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)max_frames, kChunkBudget / (bytes(1) - bytes(0))));
+    const size_t total = bytes((size_t)e->chunk);
+    uint8_t hdr[kHdrCap];
     e->hdr_len = (int)header_bytes(H, W, o.quality, o.sampling, o.dri, hdr, &e->dht_at, &e->tail_at);
     JTab tab;
     for (int t = 0; t < 2; ++t) {
@@ -1039,28 +973,17 @@ static int jpeg_create(const char* who, int device, int H, int W, const trl_jpeg
         memcpy(tab.dc[t], dc, sizeof(tab.dc[t]));
         memcpy(tab.ac[t], ac, sizeof(tab.ac[t]));
     }
-    const size_t C = (size_t)e->chunk, B = (size_t)e->blocks;
-    constexpr int kParts = 18;
-    size_t sz[kParts] = {sizeof(JTab), 1024, C * B * 128, C * B * 4, C * B * 8, C * 8, C * e->segs_per_frame * 4, C * e->scratch_per_frame,
-                         (size_t)max_frames * 8, ((size_t)max_frames + 1) * 8, C * B * 4, C * B * 4,
-                         C * NI * 8, C * NI * 8, OPT * C * 4096, OPT * C * sizeof(JTab), OPT * C * 1024, OPT * C * 4};
-    size_t total = 0, offs[kParts];
-    for (int i = 0; i < kParts; ++i) { offs[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
     hipError_t st = hipMalloc(&e->mem, total);
-    if (st == hipSuccess) st = hipHostMalloc((void**)&e->h_sizes, (size_t)max_frames * 8, hipHostMallocDefault);
+    if (st == hipSuccess) st = hipHostMalloc((void**)&e->h_sizes, (size_t)max_frames * sizeof(*e->h_sizes), hipHostMallocDefault);
     if (st != hipSuccess) {
         trl_set_error("%s: %zu device bytes for %d x %d frames: %s", who, total, W, H, hipGetErrorString(st));
         if (e->mem) (void)hipFree(e->mem);
         delete e;
         return TRL_ERR_HIP;
     }
-    uint8_t* m = (uint8_t*)e->mem;
-    e->tab = (JTab*)(m + offs[0]); e->hdr = m + offs[1]; e->coef = (int16_t*)(m + offs[2]); e->bits = (uint32_t*)(m + offs[3]);
-    e->off = (unsigned long long*)(m + offs[4]); e->fbits = (unsigned long long*)(m + offs[5]); e->segcnt = (uint32_t*)(m + offs[6]);
-    e->scratch = m + offs[7]; e->fsize = (long long*)(m + offs[8]); e->foff = (long long*)(m + offs[9]);
-    e->first = (uint32_t*)(m + offs[10]); e->last = (uint32_t*)(m + offs[11]);
-    e->ist = (unsigned long long*)(m + offs[12]); e->ibase = (unsigned long long*)(m + offs[13]);
-    if (e->optimize) { e->hist = (uint32_t*)(m + offs[14]); e->ftab = (JTab*)(m + offs[15]); e->fhdr = m + offs[16]; e->hlen = (int*)(m + offs[17]); }
+    Arena a;
+    a.base = (char*)e->mem; a.cap = total;
+    carve(a, (size_t)e->chunk, e);
     st = hipMemcpy(e->tab, &tab, sizeof(JTab), hipMemcpyHostToDevice);
     if (st == hipSuccess) st = hipMemcpy(e->hdr, hdr, e->hdr_len, hipMemcpyHostToDevice);
     if (st != hipSuccess) {

@@ -34,9 +34,7 @@ constexpr size_t kChunkBudget = (size_t)384 << 20;  // coefficient + plane works
 struct JdFrame {
     int32_t tabset, hs, vs, pad;
 };
-__constant__ __attribute__((aligned(16))) uint8_t c_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__constant__ __attribute__((aligned(16))) uint8_t c_zigzag[64] = TRL_ZIGZAG_LIST;   // trl_zigzag.h, through the parser's header
 
 constexpr int kHuffBytes = 6 * (int)sizeof(JdHuff);
 

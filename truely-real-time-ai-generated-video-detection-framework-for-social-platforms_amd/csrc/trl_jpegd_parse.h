@@ -8,6 +8,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "trl_zigzag.h"
+
 // why a file is not attempted (trl_jpegd_info.reason, include/truely_hip.h)
 enum {
     JD_OK = 0,
@@ -25,9 +27,7 @@ enum {
     JD_SIZE = 12          // zero height or width (DNL).  (A size other than the decoder's is trl_jpegd_decode's to find: status 1)
 };
 
-static const uint8_t kJdZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+static const uint8_t kJdZigzag[64] = TRL_ZIGZAG_LIST;
 
 struct JdHuffSpec {
     uint8_t counts[16];   // codes of length 1..16

@@ -368,6 +368,33 @@ int  trl_debug_timings(trl_ctx* ctx, float* out4);
  * _masked / trl_facenet_features on n faces of h x w; 24 / 48 = trl_debug_rnet / trl_debug_onet on n crops (h, w ignored).
  * Nothing runs, nothing is allocated or synchronised.  (ABI v7, additive) */
 int  trl_debug_workspace(trl_ctx* ctx, int what, int n, int h, int w, long long* h_out6);
+/* Red zones: do the kernels store only inside the workspace block they were handed?  trl_debug_redzone(ctx, guard, byte), on an
+ * idle context, frees the context's two workspaces (cascade-list arena and scratch; no cascade state survives) and, for guard > 0
+ * (a multiple of 256, at most TRL_RZ_MAX_GUARD), makes every block they hand out be followed by `guard` bytes that belong to no
+ * block; dry runs count the same, so need == carve still holds (trl_debug_workspace).  `byte` (0..255) is the fill: it implies
+ * trl_debug_poison(byte) for memory allocated later, and trl_debug_poison itself is refused while the guard is on.  While it is
+ * on, the library SWEEPS a workspace before each rewind of its allocator, before it frees one to grow it, and at the end of every
+ * entry point that queued work on one: it waits for the device, compares every byte outside the live blocks (alignment padding,
+ * guards, the tail up to the capacity) with the fill byte, and records one hit per altered gap (the gap is then repaired, so it is
+ * reported once).  At a rewind everything from the new offset to the capacity is refilled; a sweep at the end of a call refills
+ * nothing.  A hit never fails a call.  guard = 0 switches the mode off and restores the poison setting from before.
+ * trl_debug_redzone_report: h_out4 = {sweeps, guard bytes checked, hits, hits copied to h_hits} since the switch was set (or the
+ * last clear); flags: TRL_RZ_CLEAR forgets them after reporting, TRL_RZ_SWEEP sweeps both workspaces first (site "report").
+ * A hit: arena 0 = cascade lists / 1 = scratch; site = the label of the rewind or entry point that swept ("stage_carve", "chunk",
+ * "scratch_begin", "embed_end", ...); block = ordinal of the block in front of the gap since the last full rewind and block_bytes
+ * its size (block = number of live blocks and block_bytes = 0: the tail behind the last guard); gap_off / gap_bytes = the gap
+ * within the workspace; first / last = first and last altered byte, relative to the gap; count = altered bytes.
+ * trl_debug_redzone_poke (self-test): one hipMemset of `value` (!= the fill byte) at byte `offset` of the gap behind block
+ * `block` (the tail: block = -1 or the number of live blocks) of arena `arena`; the next sweep reports exactly that.  (ABI v7, additive) */
+enum { TRL_RZ_MAX_GUARD = 1 << 20, TRL_RZ_MAX_HITS = 256, TRL_RZ_CLEAR = 1, TRL_RZ_SWEEP = 2 };
+typedef struct {
+    int32_t arena, block;
+    char site[24];
+    long long block_bytes, gap_off, gap_bytes, first, last, count;
+} trl_rz_hit;
+int  trl_debug_redzone(trl_ctx* ctx, long long guard, int byte);
+int  trl_debug_redzone_report(trl_ctx* ctx, int flags, long long* h_out4, trl_rz_hit* h_hits, int max_hits);
+int  trl_debug_redzone_poke(trl_ctx* ctx, int arena, int block, long long offset, int value);
 /* R-Net / O-Net candidate totals of the last call over the whole batch: h_out2[0] = boxes that entered stage 2, [1] = stage 3 */
 int  trl_debug_stage_totals(trl_ctx* ctx, int32_t* h_out2);
 /* test / tuning hook: consecutive tiles (band order: three tile rows, column by column) a workgroup of the fused PNet launch takes

@@ -26,8 +26,9 @@ def block35_grouped(n, h, w, es=4, no_fnconv=False):
     return es == 4 and not no_fnconv and n * r.OH * r.OW <= GROUPED_MAX_ROWS
 
 
-def embedder_bytes(n, h, w, es=4, no_fnconv=False):
-    """Bytes the embedder's walk takes for n faces of h x w: es = 4 (f32) or 2 (bf16 / fp16: every activation behind the stem conv)."""
+def embedder_bytes(n, h, w, es=4, no_fnconv=False, guard=0):
+    """Bytes the embedder's walk takes for n faces of h x w: es = 4 (f32) or 2 (bf16 / fp16: every activation behind the stem conv).
+    guard: the red zone behind every block (csrc/trl_arena.h; 0 = off, the shipped library)."""
     rows = facenet_geometry(h, w)
     geo = {r.layer[len("facenet."):]: r for r in rows}
     grouped = block35_grouped(n, h, w, es, no_fnconv)
@@ -35,7 +36,7 @@ def embedder_bytes(n, h, w, es=4, no_fnconv=False):
 
     def block(H, W, c, e):
         nonlocal off
-        off = (off + 255) // 256 * 256 + n * H * W * c * e + 64
+        off = (off + 255) // 256 * 256 + n * H * W * c * e + 64 + guard
 
     for r in rows:
         name = r.layer[len("facenet."):]

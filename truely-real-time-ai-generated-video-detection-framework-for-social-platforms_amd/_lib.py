@@ -24,6 +24,11 @@ class TrlJpegOptions(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("quality", "subsampling", "restart_rows", "restart_blocks", "optimize")]
 
 
+class TrlRzHit(C.Structure):
+    _fields_ = [("arena", C.c_int32), ("block", C.c_int32), ("site", C.c_char * 24)] + \
+               [(n, C.c_longlong) for n in ("block_bytes", "gap_off", "gap_bytes", "first", "last", "count")]
+
+
 class TrlError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"libtruely_hip status {status}: {msg}")
@@ -87,6 +92,9 @@ _SIGNATURES = {
     "trl_debug_crop_area": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "trl_debug_timings": (C.c_int, [_vp, C.POINTER(_f)]),
     "trl_debug_workspace": (C.c_int, [_vp, _i, _i, _i, _i, C.POINTER(C.c_longlong)]),
+    "trl_debug_redzone": (C.c_int, [_vp, C.c_longlong, _i]),
+    "trl_debug_redzone_report": (C.c_int, [_vp, _i, C.POINTER(C.c_longlong), C.POINTER(TrlRzHit), _i]),
+    "trl_debug_redzone_poke": (C.c_int, [_vp, _i, _i, C.c_longlong, _i]),
     "trl_debug_stage_totals": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "trl_debug_pnet_run": (C.c_int, [_vp, _i]),
     "trl_debug_pnet_kernel_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),

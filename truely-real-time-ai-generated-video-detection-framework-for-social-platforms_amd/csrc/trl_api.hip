@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <algorithm>
 
 #include "trl_ctx.h"
 
@@ -98,6 +99,7 @@ int trl_destroy(trl_ctx* c) {
     if (c->scratch.base) (void)hipFree(c->scratch.base);
     if (c->sims_tmp.base) (void)hipFree(c->sims_tmp.base);
     if (c->pyr_tab) (void)hipFree(c->pyr_tab);
+    if (c->rz.dev) (void)hipFree(c->rz.dev);
     for (auto& b : c->fn_cap) if (b.p) (void)hipFree(b.p);
     if (c->pnet_clk) {
         // TRL_PNET_CLOCK: where the waves of the fused PNet launches spent their time (shader clocks per tile and wave, DBG instantiation)
@@ -147,16 +149,128 @@ const DevV* trl_v(trl_ctx* c, const std::string& name) {
     return &it->second;
 }
 
+// ---- red zones (trl_debug_redzone) ---------------------------------------------------------------------
+// One workgroup column per gap: res[3 g] += bytes of gap g that differ from `byte`, res[3 g + 1] / [3 g + 2] = min / max of their
+// offsets within the gap.  gaps[2 g] / [2 g + 1] = the gap's offset in the workspace and its length.  Reads only, all inside the gap.
+__global__ void k_rz_scan(const unsigned char* __restrict__ base, const unsigned long long* __restrict__ gaps, unsigned long long* __restrict__ res,
+                          int g0, unsigned byte) {
+    const int g = g0 + blockIdx.y;
+    const unsigned long long len = gaps[2 * g + 1];
+    const unsigned char* p = base + gaps[2 * g];
+    unsigned long long head = (16 - ((uintptr_t)p & 15)) & 15;            // bytes in front of the first aligned 16
+    if (head > len) head = len;
+    const unsigned long long nw = (len - head) / 16, tail0 = head + nw * 16;
+    const unsigned long long w = 0x0101010101010101ull * (byte & 0xFF);
+    const unsigned long long tid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, nt = (unsigned long long)gridDim.x * blockDim.x;
+    unsigned long long cnt = 0, first = ~0ull, last = 0;
+    auto look = [&](unsigned long long i) {
+        if (p[i] == (unsigned char)byte) return;
+        cnt++;
+        if (i < first) first = i;
+        if (i > last) last = i;
+    };
+    if (tid == 0) {
+        for (unsigned long long i = 0; i < head; i++) look(i);
+        for (unsigned long long i = tail0; i < len; i++) look(i);
+    }
+    const ulonglong2* q = reinterpret_cast<const ulonglong2*>(p + head);
+    for (unsigned long long k = tid; k < nw; k += nt) {
+        const ulonglong2 v = q[k];
+        if (v.x == w && v.y == w) continue;
+        for (int b = 0; b < 16; b++) look(head + k * 16 + b);
+    }
+    if (cnt) {
+        atomicAdd(&res[3 * g], cnt);
+        atomicMin(&res[3 * g + 1], first);
+        atomicMax(&res[3 * g + 2], last);
+    }
+}
+
+namespace {
+struct RzGap { size_t off, len; int block; size_t block_bytes; };
+// every stretch of `a` that belongs to no block: behind each live block up to the next one (the last: up to a.off), then the tail
+void rz_gaps(const Arena& a, std::vector<RzGap>& out) {
+    const size_t nb = a.blocks.size();
+    for (size_t i = 0; i < nb; i++) {
+        const size_t end = a.blocks[i].off + a.blocks[i].bytes, next = i + 1 < nb ? a.blocks[i + 1].off : a.off;
+        if (next > end) out.push_back({end, next - end, (int)i, a.blocks[i].bytes});
+    }
+    if (a.cap > a.off) out.push_back({a.off, a.cap - a.off, (int)nb, 0});
+}
+// The sweep of one workspace.  refill_from >= 0 (a rewind to that offset): everything from there to the capacity is refilled
+int rz_sweep(trl_ctx* c, Arena& a, const char* site, long long refill_from) {
+    trl_ctx::RedZone& z = c->rz;
+    TRL_HIP(hipDeviceSynchronize());             // the call's stream, and every other one
+    if (!a.base) return TRL_OK;
+    std::vector<RzGap> gaps;
+    rz_gaps(a, gaps);
+    const size_t ng = gaps.size();
+    if (ng) {
+        if (z.dev_gaps < ng) {
+            if (z.dev) TRL_HIP(hipFree(z.dev));
+            z.dev = nullptr; z.dev_gaps = 0;
+            TRL_HIP(hipMalloc((void**)&z.dev, (ng + 256) * 5 * 8));
+            z.dev_gaps = ng + 256;
+        }
+        std::vector<unsigned long long> tab(5 * ng, 0);
+        for (size_t g = 0; g < ng; g++) { tab[2 * g] = gaps[g].off; tab[2 * g + 1] = gaps[g].len; tab[2 * ng + 3 * g + 1] = ~0ull; }
+        TRL_HIP(hipMemcpy(z.dev, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+        // the gaps behind blocks are a guard long: a few workgroups each, 32 K gaps per launch; the tail (last) is the long one
+        const bool has_tail = gaps.back().block == (int)a.blocks.size();
+        const size_t nshort = has_tail ? ng - 1 : ng;
+        for (size_t g0 = 0; g0 < nshort; g0 += 32768) {
+            const unsigned ny = (unsigned)std::min<size_t>(32768, nshort - g0);
+            k_rz_scan<<<dim3(4, ny), 256>>>((const unsigned char*)a.base, z.dev, z.dev + 2 * ng, (int)g0, (unsigned)z.byte);
+            TRL_LAUNCH_CHECK();
+        }
+        if (has_tail) {
+            k_rz_scan<<<dim3(4096, 1), 256>>>((const unsigned char*)a.base, z.dev, z.dev + 2 * ng, (int)(ng - 1), (unsigned)z.byte);
+            TRL_LAUNCH_CHECK();
+        }
+        TRL_HIP(hipMemcpy(tab.data() + 2 * ng, z.dev + 2 * ng, 3 * ng * 8, hipMemcpyDeviceToHost));
+        for (size_t g = 0; g < ng; g++) {
+            z.bytes += (long long)gaps[g].len;
+            const unsigned long long* r = &tab[2 * ng + 3 * g];
+            if (!r[0]) continue;
+            z.nhits++;
+            if (z.hits.size() < TRL_RZ_MAX_HITS) {
+                trl_rz_hit h;
+                memset(&h, 0, sizeof h);
+                h.arena = &a == &c->arena ? 0 : 1; h.block = gaps[g].block;
+                strncpy(h.site, site, sizeof(h.site) - 1);
+                h.block_bytes = (long long)gaps[g].block_bytes; h.gap_off = (long long)gaps[g].off; h.gap_bytes = (long long)gaps[g].len;
+                h.first = (long long)r[1]; h.last = (long long)r[2]; h.count = (long long)r[0];
+                z.hits.push_back(h);
+            }
+            TRL_HIP(hipMemset(a.base + gaps[g].off, z.byte, gaps[g].len));   // repaired: reported once
+        }
+    }
+    z.sweeps++;
+    if (refill_from >= 0 && (size_t)refill_from < a.cap) TRL_HIP(hipMemset(a.base + refill_from, z.byte, a.cap - (size_t)refill_from));
+    TRL_HIP(hipDeviceSynchronize());
+    return TRL_OK;
+}
+// Arena::on_rewind of the two workspaces while the guard is on (a failing HIP call here fails the next one of the entry point too)
+void rz_on_rewind(Arena& a, size_t mark, const char* site, void* owner) { (void)rz_sweep((trl_ctx*)owner, a, site, (long long)mark); }
+}  // namespace
+
+int trl_rz_sweep_all(trl_ctx* c, const char* site) {
+    TRL_CHECK(rz_sweep(c, c->arena, site, -1));
+    return rz_sweep(c, c->scratch, site, -1);
+}
+
 int trl_ensure(trl_ctx* c, Arena& a, size_t bytes) {
     if (bytes <= a.cap) return TRL_OK;
     // Growing frees the old block, so it is only called while nothing allocated from `a` is live:
     // at the start of a call (arena) or between cascade stages (scratch).
     const size_t ncap = bytes + (bytes >> 3) + (32u << 20);
     TRL_HIP(hipDeviceSynchronize());
+    if (a.guard && a.base) TRL_CHECK(rz_sweep(c, a, "ensure", -1));
     if (a.base) { TRL_HIP(hipFree(a.base)); a.base = nullptr; a.cap = 0; }
     TRL_HIP(hipMalloc((void**)&a.base, ncap));
     a.cap = ncap;
     a.off = 0;
+    a.blocks.clear();
     if (c->dbg_poison >= 0) TRL_HIP(hipMemset(a.base, c->dbg_poison, ncap));   // test hook: workspaces that grow stay poisoned
     return TRL_OK;
 }
@@ -314,7 +428,7 @@ extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
     // counting arena on one 160 x 160 face (every geometry names the same tensors).
     TRL_CHECK(trl_resolve_nets(c, host.data()));
     TRL_CHECK(trl_pnet_prepare(c, host.data()));
-    Arena count = Arena::counter();
+    Arena count = Arena::counter(c->scratch.guard);
     TRL_CHECK(trl_run_facenet(c, count, nullptr, 1, 160, 160, nullptr, nullptr, nullptr));
     c->fn_need_key[0] = 0;
     if (idx.count(lw_name)) {                        // (shapes checked above)
@@ -386,7 +500,7 @@ static int crop_embed(trl_ctx* c, Arena& X, const trl_ctx::Pending& q, hipStream
     const int n = q.n, H = q.H, W = q.W, S = c->cfg.embed_mode == 0 ? 80 : 160;
     float* faces = q.faces_out;
     if (!faces) {
-        X.reset();                                   // stream order: the cascade's kernels are done with it before these run
+        X.reset("crop_embed");                       // stream order: the cascade's kernels are done with it before these run
         faces = (float*)X.alloc((size_t)n * S * S * 3 * 4);
         if (!faces) { trl_set_error("arena exhausted"); return TRL_ERR_STATE; }
     }
@@ -402,7 +516,7 @@ static int crop_embed(trl_ctx* c, Arena& X, const trl_ctx::Pending& q, hipStream
 static int embed_need(trl_ctx* c, bool crops, int n, int h, int w) {
     const int key[6] = {n, h, w, c->cfg.embed_precision, g_trl_no_fnconv, crops};
     if (memcmp(key, c->fn_need_key, sizeof key) == 0) return TRL_OK;
-    Arena count = Arena::counter();
+    Arena count = Arena::counter(c->scratch.guard);
     trl_ctx::Pending q; q.n = n;
     TRL_CHECK(crops ? crop_embed(c, count, q, nullptr) : trl_run_facenet(c, count, nullptr, n, h, w, nullptr, nullptr, nullptr));
     memcpy(c->fn_need_key, key, sizeof key);
@@ -466,7 +580,7 @@ static int call_begin(trl_ctx* c, const trl_ctx::Pending& q) {
 // has no candidate limit, and neither has this call), it only turns a bug into an error.
 enum { TRL_MAX_ATTEMPTS = 12 };
 
-static int call_wait(trl_ctx* c) {
+static int call_wait(trl_ctx* c, const char* site) {
     if (!c) { trl_set_error("null context"); return TRL_ERR_INVALID; }
     if (!c->pend.active) { trl_set_error("no call in flight on this context"); return TRL_ERR_STATE; }
     TRL_HIP(hipSetDevice(c->cfg.device));
@@ -483,12 +597,13 @@ static int call_wait(trl_ctx* c) {
     }
     c->pend.active = false;
     if (st == TRL_OK) collect_timings(c);
+    if (st == TRL_OK) st = trl_rz_end(c, site);
     return st;
 }
 
-static int call_run(trl_ctx* c, const trl_ctx::Pending& q) {
+static int call_run(trl_ctx* c, const trl_ctx::Pending& q, const char* site) {
     TRL_CHECK(call_begin(c, q));
-    return call_wait(c);
+    return call_wait(c, site);
 }
 
 static trl_ctx::Pending detect_call(const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, float* d_points,
@@ -513,7 +628,7 @@ extern "C" {
 
 int trl_mtcnn_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs, int32_t* d_counts,
                      void* stream) {
-    return call_run(c, detect_call(d_frames, n, H, W, d_boxes, d_probs, nullptr, d_counts, stream, 0));
+    return call_run(c, detect_call(d_frames, n, H, W, d_boxes, d_probs, nullptr, d_counts, stream, 0), "mtcnn_detect");
 }
 
 int trl_mtcnn_detect_landmarks(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_boxes, float* d_probs,
@@ -525,19 +640,19 @@ int trl_mtcnn_detect_landmarks(trl_ctx* c, const uint8_t* d_frames, int n, int H
 int trl_mtcnn_detect_ordered(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, int order, float* d_boxes, float* d_probs,
                              float* d_points, int32_t* d_counts, void* stream) {
     if (order != 0 && order != 1) { trl_set_error("bad box order %d (0 = area, 1 = detection order)", order); return TRL_ERR_INVALID; }
-    return call_run(c, detect_call(d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, stream, order));
+    return call_run(c, detect_call(d_frames, n, H, W, d_boxes, d_probs, d_points, d_counts, stream, order), "mtcnn_detect");
 }
 
 int trl_detect_embed(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
                      uint8_t* d_valid, float* d_emb, void* stream) {
     if (!d_emb) { trl_set_error("null output"); return TRL_ERR_INVALID; }
-    return call_run(c, embed_call(d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, d_emb, nullptr, stream));
+    return call_run(c, embed_call(d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, d_emb, nullptr, stream), "detect_embed");
 }
 
 int trl_detect_crop(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
                     uint8_t* d_valid, float* d_faces, void* stream) {
     if (!d_faces) { trl_set_error("null output"); return TRL_ERR_INVALID; }
-    return call_run(c, embed_call(d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, nullptr, d_faces, stream));
+    return call_run(c, embed_call(d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, nullptr, d_faces, stream), "detect_crop");
 }
 
 int trl_detect_embed_begin(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_box, float* d_prob, int32_t* d_rect,
@@ -552,7 +667,7 @@ int trl_detect_crop_begin(trl_ctx* c, const uint8_t* d_frames, int n, int H, int
     return call_begin(c, embed_call(d_frames, n, H, W, d_box, d_prob, d_rect, d_valid, nullptr, d_faces, stream));
 }
 
-int trl_detect_embed_end(trl_ctx* c) { return call_wait(c); }
+int trl_detect_embed_end(trl_ctx* c) { return call_wait(c, "embed_end"); }
 
 }  // extern "C"
 
@@ -566,7 +681,8 @@ static int facenet_embed(trl_ctx* c, const float* d_faces, const uint8_t* d_vali
     TRL_CHECK(embed_need(c, false, n, h, w));
     TRL_CHECK(trl_scratch_begin(c, c->fn_need_bytes));
     TRL_CHECK(trl_run_facenet(c, c->scratch, d_faces, n, h, w, d_valid, d_emb, (hipStream_t)stream, features));
-    return trl_gate_record(c, (hipStream_t)stream);
+    TRL_CHECK(trl_gate_record(c, (hipStream_t)stream));
+    return trl_rz_end(c, "facenet");
 }
 
 // trl_drift_score / trl_drift_update: d_state nullable (no state carried across calls)
@@ -656,6 +772,7 @@ __global__ void k_poison_lds(unsigned word, int nwords) {
 // result that depends on workspace contents left by an earlier call or process shows up as a parity failure.
 int trl_debug_poison(trl_ctx* c, int byte) {
     TRL_CHECK(trl_check_idle(c));
+    if (c->rz.guard) { trl_set_error("red zones are on: their fill byte is the poison"); return TRL_ERR_STATE; }
     TRL_HIP(hipSetDevice(c->cfg.device));
     TRL_HIP(hipDeviceSynchronize());
     c->dbg_poison = byte & 0xFF;                 // sticky: blocks allocated later are filled too
@@ -723,7 +840,7 @@ int trl_debug_pyramid_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, in
     TRL_CHECK(trl_scratch_begin(c, trl_pnet_fused_bytes(c, 1, H, W) + (1u << 20)));
     TRL_CHECK(trl_pyramid_export(c, d_frame, H, W, level, d_out, h, w, s));
     TRL_HIP(hipStreamSynchronize(s));
-    return TRL_OK;
+    return trl_rz_end(c, "pyramid_level");
 }
 
 int trl_debug_pyramid_batch(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, float* d_out, long long* pyr_stride,
@@ -734,7 +851,7 @@ int trl_debug_pyramid_batch(trl_ctx* c, const uint8_t* d_frames, int n, int H, i
     if (d_out) TRL_CHECK(trl_scratch_begin(c, trl_pnet_fused_bytes(c, n, H, W) + (1u << 20)));
     TRL_CHECK(trl_pyramid_export_batch(c, d_frames, n, H, W, d_out, pyr_stride, h_levels, max_levels, n_levels, s));
     TRL_HIP(hipStreamSynchronize(s));
-    return TRL_OK;
+    return trl_rz_end(c, "pyramid_batch");
 }
 
 int trl_debug_pyramid_plan(trl_ctx* c, int32_t* h_rows, int max_levels, int* n_levels) {
@@ -786,14 +903,15 @@ int trl_debug_pnet_level(trl_ctx* c, const uint8_t* d_frame, int H, int W, int l
     TRL_CHECK(trl_launch_heads_to_maps(heads, g.oh * g.ow, d_prob, d_reg, s));
     *oh = g.oh; *ow = g.ow;
     TRL_HIP(hipStreamSynchronize(s));
-    return TRL_OK;
+    return trl_rz_end(c, "pnet_level_hook");
 }
 
 // test hooks: a whole net through the layer kernels over n crops [n][side][side][3]: d_out [n][6] (R-Net) / [n][16] (O-Net)
 static int debug_net(trl_ctx* c, const NetDesc& d, const float* d_crops, int n, float* d_out, void* stream) {
     if (!c || !c->have_weights || !d_crops || !d_out || n <= 0) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
     TRL_CHECK(trl_check_idle(c));
-    return trl_carve_scratch(c, [&](Arena& X) { return trl_run_net(c, X, d, 0, Act::dense(d_crops, n, d.side, d.side, 3), d_out, (hipStream_t)stream); });
+    TRL_CHECK(trl_carve_scratch(c, [&](Arena& X) { return trl_run_net(c, X, d, 0, Act::dense(d_crops, n, d.side, d.side, 3), d_out, (hipStream_t)stream); }));
+    return trl_rz_end(c, "debug_net");
 }
 int trl_debug_rnet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) { return debug_net(c, trl_nets[TRL_RNET], d_crops, n, d_out, stream); }
 int trl_debug_onet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* stream) { return debug_net(c, trl_nets[TRL_ONET], d_crops, n, d_out, stream); }
@@ -802,10 +920,12 @@ int trl_debug_onet(trl_ctx* c, const float* d_crops, int n, float* d_out, void* 
 static int upload_records(trl_ctx* c, int nf, int H, int W, const std::vector<int32_t>& hb, int slots, int nb, int32_t** total, hipStream_t s) {
     Arena& A = c->arena;
     TRL_CHECK(trl_ensure(c, A, (size_t)slots * 32 + (1u << 20)));
-    A.reset();
+    A.reset("records");
     CascadeBufs& B = c->cb;
     B = CascadeBufs();
     B.n = nf; B.H = H; B.W = W;
+    // + 32: one record of slack for READS only.  No kernel stores into it: with the slack at 0 and red zones on
+    // (trl_debug_redzone), the front kernel and the stage loop (capacity == count, > count, chunked) left every guard byte intact.
     B.cbox = (int32_t*)A.alloc((size_t)slots * 32 + 32);
     *total = (int32_t*)A.alloc(64);
     TRL_HIP(hipMemcpyAsync(B.cbox, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s));
@@ -846,7 +966,7 @@ static int stage_net_on_rows(trl_ctx* c, const uint8_t* d_frames, int nf, int H,
     TRL_CHECK(st);
     TRL_HIP(hipStreamSynchronize(s));
     c->cb = CascadeBufs();                                 // no cascade state to inspect after this hook
-    return TRL_OK;
+    return trl_rz_end(c, "stage_net");
 }
 
 // test hook: the production stage-2 / stage-3 network path -- the fused front kernel (k_mtcnn_front: pad(), crop, area resample,
@@ -902,7 +1022,7 @@ int trl_debug_front(trl_ctx* c, const uint8_t* d_frames, int nf, int H, int W, c
     TRL_CHECK(trl_launch_front(c, trl_net_of(net), d_frames, H, W, total, 0, capacity, d_pool, s));
     TRL_HIP(hipStreamSynchronize(s));
     c->cb = CascadeBufs();
-    return TRL_OK;
+    return trl_rz_end(c, "front");
 }
 
 // test hook: the cascade's list kernels on caller-built lists (trl_cascade_lists has the layout of every kind)
@@ -931,8 +1051,10 @@ int trl_debug_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* h_
     }
     if (total > 0 && (!h_rows || (kind > 1 && !h_logits))) { trl_set_error("null rows"); return TRL_ERR_INVALID; }
     TRL_HIP(hipSetDevice(c->cfg.device));
-    return trl_cascade_lists(c, kind, n, H, W, h_caps, n_levels, h_counts, h_rows, h_logits, h_pts, d_boxes, d_probs, d_points, d_counts,
-                             d_box0, d_prob0, d_rect, d_valid, (hipStream_t)stream);
+    const int st = trl_cascade_lists(c, kind, n, H, W, h_caps, n_levels, h_counts, h_rows, h_logits, h_pts, d_boxes, d_probs, d_points, d_counts,
+                                     d_box0, d_prob0, d_rect, d_valid, (hipStream_t)stream);
+    TRL_CHECK(trl_rz_end(c, "lists_hook"));         // (after a TRL_ERR_CAPACITY too: the kernels ran)
+    return st;
 }
 
 // the context's two arenas and, for `what` = 1 (embedder call on n faces of h x w) / 24 / 48 (trl_debug_rnet / _onet on n crops),
@@ -941,12 +1063,79 @@ int trl_debug_workspace(trl_ctx* c, int what, int n, int h, int w, long long* h_
     TRL_CHECK(trl_check_idle(c));
     if (!h_out6 || (what != 0 && what != 1 && what != 24 && what != 48) || (what && n <= 0) || (what == 1 && (h < 75 || w < 75))) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
     if (what && !c->have_weights) { trl_set_error("context without weights"); return TRL_ERR_STATE; }
-    Arena X = Arena::counter();
+    Arena X = Arena::counter(c->scratch.guard);
     if (what == 1) TRL_CHECK(embed_need(c, false, n, h, w));
     else if (what) { const NetDesc& d = trl_net_of(what); TRL_CHECK(trl_run_net(c, X, d, 0, Act::dense(nullptr, n, d.side, d.side, 3), nullptr, nullptr)); }
     const size_t v[6] = {c->scratch.cap, c->scratch.high, c->arena.cap, c->arena.off, c->arena_need, what == 1 ? c->fn_need_bytes : X.high};
     for (int k = 0; k < 6; k++) h_out6[k] = (long long)v[k];
     return TRL_OK;
+}
+
+// Red zones behind every block of the context's two workspaces, and the sweeps that check them (include/truely_hip.h; rz_sweep above)
+int trl_debug_redzone(trl_ctx* c, long long guard, int byte) {
+    TRL_CHECK(trl_check_idle(c));
+    if (guard < 0 || guard > TRL_RZ_MAX_GUARD || (guard & 255) || byte < 0 || byte > 255) {
+        trl_set_error("bad red zone: guard %lld (0, or a multiple of 256 up to %d), fill byte %d", guard, (int)TRL_RZ_MAX_GUARD, byte);
+        return TRL_ERR_INVALID;
+    }
+    trl_ctx::RedZone& z = c->rz;
+    if (!guard && !z.guard) return TRL_OK;
+    TRL_HIP(hipSetDevice(c->cfg.device));
+    TRL_HIP(hipDeviceSynchronize());
+    if (!z.guard) z.saved_poison = c->dbg_poison;
+    // both workspaces start over, so that every byte of them is filled by trl_ensure and every block is known
+    for (Arena* a : {&c->arena, &c->scratch}) {
+        if (a->base) TRL_HIP(hipFree(a->base));
+        a->base = nullptr; a->cap = a->off = a->high = 0;
+        a->blocks.clear();
+        a->guard = (size_t)guard; a->on_rewind = guard ? rz_on_rewind : nullptr; a->owner = c;
+    }
+    c->cb = CascadeBufs();
+    c->arena_need = 0;
+    c->fn_need_key[0] = 0;                       // the embedder's count depends on the guard
+    z.guard = (size_t)guard; z.byte = byte;
+    z.sweeps = z.bytes = z.nhits = 0;
+    z.hits.clear();
+    c->dbg_poison = guard ? byte : z.saved_poison;
+    return TRL_OK;
+}
+
+int trl_debug_redzone_report(trl_ctx* c, int flags, long long* h_out4, trl_rz_hit* h_hits, int max_hits) {
+    TRL_CHECK(trl_check_idle(c));
+    if (!h_out4 || (max_hits > 0 && !h_hits)) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
+    trl_ctx::RedZone& z = c->rz;
+    if ((flags & TRL_RZ_SWEEP) && z.guard) {
+        TRL_HIP(hipSetDevice(c->cfg.device));
+        TRL_CHECK(trl_rz_sweep_all(c, "report"));
+    }
+    int m = 0;
+    for (; m < (int)z.hits.size() && m < max_hits; m++) h_hits[m] = z.hits[m];
+    h_out4[0] = z.sweeps; h_out4[1] = z.bytes; h_out4[2] = z.nhits; h_out4[3] = m;
+    if (flags & TRL_RZ_CLEAR) { z.sweeps = z.bytes = z.nhits = 0; z.hits.clear(); }
+    return TRL_OK;
+}
+
+int trl_debug_redzone_poke(trl_ctx* c, int arena, int block, long long offset, int value) {
+    TRL_CHECK(trl_check_idle(c));
+    trl_ctx::RedZone& z = c->rz;
+    if (!z.guard) { trl_set_error("red zones are off"); return TRL_ERR_STATE; }
+    if ((arena != 0 && arena != 1) || value < 0 || value > 255 || value == z.byte) { trl_set_error("bad argument"); return TRL_ERR_INVALID; }
+    Arena& a = arena ? c->scratch : c->arena;
+    if (!a.base) { trl_set_error("the workspace has not been allocated"); return TRL_ERR_STATE; }
+    std::vector<RzGap> gaps;
+    rz_gaps(a, gaps);
+    if (block < 0) block = (int)a.blocks.size();                            // the tail
+    for (const RzGap& g : gaps) {
+        if (g.block != block) continue;
+        if (offset < 0 || (size_t)offset >= g.len) break;
+        TRL_HIP(hipSetDevice(c->cfg.device));
+        TRL_HIP(hipDeviceSynchronize());
+        TRL_HIP(hipMemset(a.base + g.off + (size_t)offset, value, 1));    // inside [0, cap): a gap of this workspace
+        TRL_HIP(hipDeviceSynchronize());
+        return TRL_OK;
+    }
+    trl_set_error("no byte %lld in the gap behind block %d (%zu live blocks)", offset, block, a.blocks.size());
+    return TRL_ERR_INVALID;
 }
 
 int trl_debug_mtcnn_plan(trl_ctx* c, trl_fn_plan_row* h_rows, int max_rows, int* n_rows) {
@@ -971,19 +1160,22 @@ static int check_crop_hook(trl_ctx* c, const void* d_frames, int n, int n_max, i
 int trl_debug_crop_resize(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid,
                           float* d_faces, void* stream) {
     TRL_CHECK(check_crop_hook(c, d_frames, n, INT_MAX, H, W, d_rect, d_valid, 80, d_faces));
-    return trl_launch_crop_resize80(d_frames, n, H, W, d_rect, d_valid, d_faces, (hipStream_t)stream);
+    TRL_CHECK(trl_launch_crop_resize80(d_frames, n, H, W, d_rect, d_valid, d_faces, (hipStream_t)stream));
+    return trl_rz_end(c, "crop_resize");
 }
 // embedding mode 3's crop alone: d_pts [n][10] (x0..x4, y0..y4 per frame) -> f32 [n][S][S][3]
 int trl_debug_crop_aligned(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, const float* d_pts, const uint8_t* d_valid, int S,
                            int rgb, float* d_faces, void* stream) {
     TRL_CHECK(check_crop_hook(c, d_frames, n, 65535, H, W, d_pts, d_valid, S, d_faces));
-    return trl_launch_crop_aligned(d_frames, n, H, W, d_pts, d_valid, S, rgb != 0, d_faces, (hipStream_t)stream);
+    TRL_CHECK(trl_launch_crop_aligned(d_frames, n, H, W, d_pts, d_valid, S, rgb != 0, d_faces, (hipStream_t)stream));
+    return trl_rz_end(c, "crop_aligned");
 }
 // embedding modes 1 / 2's crop alone: d_rect [n][4] -> f32 [n][S][S][3]
 int trl_debug_crop_area(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, const int32_t* d_rect, const uint8_t* d_valid, int S,
                         int rgb, float* d_faces, void* stream) {
     TRL_CHECK(check_crop_hook(c, d_frames, n, 65535, H, W, d_rect, d_valid, S, d_faces));
-    return trl_launch_crop_area_std(d_frames, n, H, W, d_rect, d_valid, S, rgb != 0, d_faces, (hipStream_t)stream);
+    TRL_CHECK(trl_launch_crop_area_std(d_frames, n, H, W, d_rect, d_valid, S, rgb != 0, d_faces, (hipStream_t)stream));
+    return trl_rz_end(c, "crop_area");
 }
 // test hook: set the optimistic R-/O-Net batch capacities (candidates per frame) the next call starts from, and read back how
 // many attempts the last call needed (> 1: a capacity was too small and the call was re-run with a larger one)

@@ -925,7 +925,7 @@ static int launch_stage_post(trl_ctx* c, const ListLaunch& ll, int st, int cap, 
 static void layout_lists(CascadeBufs& B, Arena& A, size_t spill) {
     const LvLayout& G = B.lay;
     const int n = B.n, L = B.L, capF = B.capF;
-    A.reset();
+    A.reset("lists");
     B.lvl_cnt = (int32_t*)A.alloc((size_t)n * L * 4);
     B.lvl_keep_cnt = (int32_t*)A.alloc((size_t)n * L * 4);
     B.lvl_rec = (Cand*)A.alloc((size_t)n * G.S * sizeof(Cand));
@@ -945,7 +945,7 @@ static void layout_lists(CascadeBufs& B, Arena& A, size_t spill) {
 // ... carved from c->arena (live for the whole call, and for the debug hooks after it) for the layout in c->cb, flags zeroed
 static int carve_lists(trl_ctx* c, size_t spill, hipStream_t s) {
     CascadeBufs& B = c->cb;
-    Arena count = Arena::counter();
+    Arena count = Arena::counter(c->arena.guard);
     layout_lists(B, count, spill);
     TRL_CHECK(trl_ensure(c, c->arena, c->arena_need = count.off));
     layout_lists(B, c->arena, spill);
@@ -955,7 +955,7 @@ static int carve_lists(trl_ctx* c, size_t spill, hipStream_t s) {
 }
 
 int trl_pnet_generic_level(trl_ctx* c, Arena& X, const uint8_t* d_frames, int nf, int H, int W, const LevelGeom& g, float** d_heads, hipStream_t s) {
-    X.reset();
+    X.reset("pnet_level");
     float* lvl = (float*)X.alloc((size_t)nf * g.h * g.w * 12);
     float* heads = (float*)X.alloc((size_t)nf * g.oh * g.ow * 24);
     if (!lvl || !heads) { trl_set_error("pnet generic workspace"); return TRL_ERR_STATE; }
@@ -979,7 +979,7 @@ static int next_pnet_events(trl_ctx* c, std::pair<hipEvent_t, hipEvent_t>*& out)
 // stage 2 / 3 carves X from its start (stream order: the stage in front is done with it): *d_out = [cap][nout], then trl_stage_net's
 static int stage_carve(trl_ctx* c, Arena& X, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float** d_out, hipStream_t s) {
     const NetDesc& d = trl_net_of(net);
-    X.reset();
+    X.reset("stage_carve");
     *d_out = (float*)X.alloc((size_t)cap * d.nout * 4);
     if (!*d_out) { trl_set_error("%s workspace", d.name); return TRL_ERR_STATE; }
     return trl_stage_net(c, X, net, d_frames, H, W, d_total, cap, *d_out, s);
@@ -989,7 +989,7 @@ static int stage_carve(trl_ctx* c, Arena& X, int net, const uint8_t* d_frames, i
 // anything of the call is queued (growing frees the old block)
 static int size_scratch(trl_ctx* c, int n, int H, int W, bool fused) {
     // one counting arena under all that carves the scratch in turn (each from a reset): its high-water mark is the call's need
-    Arena X = Arena::counter();
+    Arena X = Arena::counter(c->scratch.guard);
     X.high = std::max(c->scratch_after_cascade, fused ? trl_pnet_fused_bytes(c, n, H, W) + (1u << 20) : 0);
     float* o;
     for (int l = 0; l < c->cb.L && !fused; l++) {
@@ -1110,7 +1110,7 @@ int trl_stage_net(trl_ctx* c, Arena& X, int net, const uint8_t* d_frames, int H,
     const size_t mk = X.off;
     for (int t0 = 0; t0 < cap; t0 += CH) {
         const int nc = (cap - t0 < CH) ? cap - t0 : CH;
-        X.off = mk;
+        X.rewind(mk, "chunk");
         float* pool1 = (float*)X.alloc((size_t)nc * d.P * d.P * d.C1 * 4);
         if (!pool1) { trl_set_error("%s workspace", d.name); return TRL_ERR_STATE; }
         if (!X.counting) TRL_CHECK(trl_launch_front(c, d, d_frames, H, W, d_total, t0, nc, pool1, s));   // crop + conv1 + pool1 in LDS

@@ -9,6 +9,7 @@
 
 #include "../../include/truely_hip.h"
 #include "trl_tailpool.h"
+#include "trl_arena.h"
 
 // ---- error plumbing --------------------------------------------------------------------------
 void trl_set_error(const char* fmt, ...);
@@ -100,23 +101,7 @@ struct ConvPoolArgs : ConvArgs {
 };
 enum { TRL_TAIL_POOL_BM = 128 };   // rows per tile of the two kernels that have the pooling epilogue
 
-// bump allocator over one device allocation.  Every workspace is sized by a dry run of the code that carves it over a COUNTING arena
-// (no base, never full, the same alignment): code handed one launches nothing and does not dereference what alloc returns (a token).
-struct Arena {
-    char* base = nullptr;
-    size_t cap = 0, off = 0;
-    size_t high = 0;          // largest off since it was last zeroed (a reset() keeps it)
-    bool counting = false;
-    static Arena counter() { Arena a; a.counting = true; return a; }
-    void reset() { off = 0; }
-    void* alloc(size_t bytes) {
-        size_t a = (off + 255) & ~(size_t)255;
-        if (!counting && a + bytes > cap) return nullptr;
-        off = a + bytes;
-        if (off > high) high = off;
-        return counting ? (void*)this : base + a;
-    }
-};
+// struct Arena, the bump allocator of every workspace (and its optional red zones): trl_arena.h
 
 #ifdef __HIPCC__
 // max without the compiler's operand canonicalisation: with IEEE mode on, hipcc quiets possible signalling NaNs in front of a

@@ -93,6 +93,14 @@ struct trl_ctx {
     bool pnet_prof = false;                   // TRL_PNET_CLOCK: the DBG instantiation with per-phase wave clocks
     float pnet_kernel_ms = 0.f;      // its span in ms (collect_timings)
     int dbg_poison = -1;             // >= 0 after trl_debug_poison: byte written into every newly allocated workspace
+    // trl_debug_redzone (trl_api.hip): while rz.guard != 0, `arena` and `scratch` carry that guard, dbg_poison is the fill byte and
+    // every byte of the two that belongs to no block is checked against it at each rewind, before a grow and at the end of each call
+    struct RedZone {
+        size_t guard = 0; int byte = 0, saved_poison = -1;
+        long long sweeps = 0, bytes = 0, nhits = 0;
+        std::vector<trl_rz_hit> hits;                 // the first TRL_RZ_MAX_HITS
+        unsigned long long* dev = nullptr; size_t dev_gaps = 0;   // device: the gap table of a sweep and its results
+    } rz;
     // Optimistic capacities of the candidate lists, the spill pool and the R-Net / O-Net batches: launches and workspaces are sized
     // by them, and a call that overflows one is re-run with a larger value (trl_capacity.h)
     CascadeCaps caps;
@@ -147,9 +155,13 @@ extern int g_trl_pnet_gate;                        // trl_debug_option("pnet_gat
 int trl_ensure(trl_ctx* c, Arena& a, size_t bytes);   // grow (never while blocks of `a` are live)
 // a call's first use of the scratch: empty, a new high-water mark, at least `bytes` (the count of the carve that follows); where one
 // carve is the whole call (trl_carve_scratch), carve(X) over a counting arena, then over the scratch grown to that count
-inline int trl_scratch_begin(trl_ctx* c, size_t bytes) { c->scratch.off = c->scratch.high = 0; return trl_ensure(c, c->scratch, bytes); }
+inline int trl_scratch_begin(trl_ctx* c, size_t bytes) { c->scratch.reset("scratch_begin"); c->scratch.high = 0; return trl_ensure(c, c->scratch, bytes); }
+// the red-zone sweep at the end of an entry point that queued work on the arenas (trl_debug_redzone; nothing while it is off).
+// site: the entry point's label in the report
+int trl_rz_sweep_all(trl_ctx* c, const char* site);
+inline int trl_rz_end(trl_ctx* c, const char* site) { return c->rz.guard ? trl_rz_sweep_all(c, site) : TRL_OK; }
 template <class F> int trl_carve_scratch(trl_ctx* c, F&& carve) {
-    Arena X = Arena::counter();
+    Arena X = Arena::counter(c->scratch.guard);
     TRL_CHECK(carve(X)); TRL_CHECK(trl_scratch_begin(c, X.high));
     return carve(c->scratch);
 }

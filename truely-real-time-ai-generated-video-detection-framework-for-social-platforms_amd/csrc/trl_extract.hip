@@ -359,7 +359,8 @@ int trl_extract_faces(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, 
     TRL_LAUNCH_CHECK();
     k_extract<<<dim3((S + XBAND - 1) / XBAND, m), XB, 0, s>>>(H, W, d_frames, d_frame_of, S, resample, post_process, Kx, Ky, plan, d_out);
     TRL_LAUNCH_CHECK();
-    return trl_gate_record(c, s);
+    TRL_CHECK(trl_gate_record(c, s));
+    return trl_rz_end(c, "extract_faces");
 }
 
 }  // extern "C"

@@ -561,7 +561,7 @@ extern "C" int trl_gallery_scores(const float* d_q, int n, const float* d_mat, l
 extern "C" size_t trl_gallery_search_workspace(int n, long long m, int k, int max_strip_cols) {
     GlPlan p;
     if (gl_plan(n, m, k, max_strip_cols, &p)) return 0;
-    Arena a = Arena::counter();
+    Arena a = Arena::counter(0);
     TrlGlEntry* part;
     gl_carve(a, p, n, k, &part);
     return a.high;
@@ -631,7 +631,7 @@ extern "C" int trl_cluster_links(const float* d_q, const uint8_t* d_valid, int n
 
 extern "C" size_t trl_cluster_workspace(int n) {
     if (n < 0 || n > CL_MAX_N) return 0;
-    Arena a = Arena::counter();
+    Arena a = Arena::counter(0);
     ClWs w;
     cl_carve(a, n, &w);
     return a.high;

@@ -955,7 +955,7 @@ static int jpeg_create(const char* who, int device, int H, int W, const trl_jpeg
     e->nint = (nmcu + e->R - 1) / e->R;
     e->scratch_per_frame = (size_t)e->blocks * (kMaxBlockBits / 8);
     e->segs_per_frame = (int)((e->scratch_per_frame + kSeg - 1) / kSeg);
-    auto bytes = [&](size_t C) { Arena count = Arena::counter(); carve(count, C, e); return count.off; };
+    auto bytes = [&](size_t C) { Arena count = Arena::counter(0); carve(count, C, e); return count.off; };
     e->chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)max_frames, kChunkBudget / (bytes(1) - bytes(0))));
     const size_t total = bytes((size_t)e->chunk);
     uint8_t hdr[kHdrCap];

@@ -80,6 +80,9 @@ struct Runner {
     Act alloc(int n, int h, int w, int ch, bool bf = false) {
         Act a;
         a.n = n; a.h = h; a.w = w; a.c = ch; a.ld = ch; a.coff = 0; a.bf = bf;
+        // + 64: slack for READS only (vector loads of a map's last elements may run past its end).  No kernel stores into it: with
+        // the slack at 0 and red zones on (trl_debug_redzone), the embedder (f32 both block35 forms, no_fnconv, bf16, fp16), the
+        // R-/O-Net walks and the cascade left every guard byte intact.  The sweeps cannot see reads, so the slack stays.
         a.p = (float*)X.alloc((size_t)n * h * w * ch * (bf ? sizeof(uint16_t) : sizeof(float)) + 64);
         if (!a.p && err == TRL_OK) {
             trl_set_error("activation scratch exhausted (%zu of %zu bytes used)", X.off, X.cap);

@@ -506,6 +506,27 @@ class Engine:
         """Test hook: fill the activation workspaces with a byte pattern (0xFF = NaNs)."""
         _lib.check(self.lib.trl_debug_poison(self._h, int(byte)))
 
+    def redzone(self, guard: int, byte: int = 0xA5):
+        """Test hook (``trl_debug_redzone``): follow every block of the context's two workspaces with ``guard`` bytes of red zone
+        (a multiple of 256; 0 = off) filled with ``byte``, and sweep them at every rewind and at the end of every call."""
+        _lib.check(self.lib.trl_debug_redzone(self._h, int(guard), int(byte)))
+
+    def redzone_report(self, clear: bool = False, sweep: bool = False) -> dict:
+        """``sweeps`` made, guard ``bytes`` checked and ``hits`` (dicts: arena, site, block, block_bytes, gap_off, gap_bytes, first,
+        last, count; ``nhits`` counts those past the first 256 too) since ``redzone()`` or the last ``clear``.  ``sweep``: sweep
+        both workspaces first (site "report")."""
+        o = (C.c_longlong * 4)()
+        hits = (_lib.TrlRzHit * 256)()
+        _lib.check(self.lib.trl_debug_redzone_report(self._h, (1 if clear else 0) | (2 if sweep else 0), o, hits, 256))
+        rows = [dict(arena=int(h.arena), site=h.site.decode(), block=int(h.block), block_bytes=int(h.block_bytes), gap_off=int(h.gap_off),
+                     gap_bytes=int(h.gap_bytes), first=int(h.first), last=int(h.last), count=int(h.count)) for h in hits[:int(o[3])]]
+        return dict(sweeps=int(o[0]), bytes=int(o[1]), nhits=int(o[2]), hits=rows)
+
+    def redzone_poke(self, arena: int, block: int, offset: int, value: int = 0x3C):
+        """Self-test of the sweep: one byte ``value`` at ``offset`` of the gap behind block ``block`` (-1: the tail) of workspace
+        ``arena`` (0 = cascade lists, 1 = scratch).  The next sweep reports exactly that byte."""
+        _lib.check(self.lib.trl_debug_redzone_poke(self._h, int(arena), int(block), int(offset), int(value)))
+
     def level_counts(self, frame: int):
         a = np.zeros(32, np.int32); b = np.zeros(32, np.int32)
         L = C.c_int()

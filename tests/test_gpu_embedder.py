@@ -225,7 +225,7 @@ def _geometry(layer):
 
 
 def _layer_params(T, layer):
-    """(w [K][Cout], bias or None, scale or None, shift or None) as the library packs them (concat_cols in trl_load_weights concatenates columns)."""
+    """(w [K][Cout], bias or None, scale or None, shift or None) as the library packs them (a fused conv is its parts' columns side by side: csrc/trl_weights.h)."""
     if layer.endswith(".fused"):
         fam, blk, _ = _split(layer)
         cat = lambda suf: np.concatenate([T[f"{blk}.{q}.{suf}"] for q in FUSED_PARTS[fam]], axis=-1)
@@ -413,3 +413,19 @@ def test_fp16_weight_outside_range_is_refused(blob):
     Engine(truely_amd.weights.pack_tensors(T), embed_precision="bf16").close()   # bf16 has the range
     T[name][5, 7] = 65519.0                                             # rounds to 65504: accepted
     Engine(truely_amd.weights.pack_tensors(T), embed_precision="fp16").close()
+
+
+def test_second_load_into_one_context_with_16bit_copies(blob):
+    """trl_load_weights twice on one bf16 context: the first load's weights and 16-bit copies are freed, the second load's serve
+    the same bits, and the context closes (every copy freed once)."""
+    from truely_amd import _lib
+    from truely_amd.engine import Engine
+    eng = Engine(blob, embed_precision="bf16")
+    faces = torch.from_numpy(np.random.default_rng(21).uniform(-1, 1, (2, 80, 80, 3)).astype(np.float32))
+    first = eng.facenet_embed(faces).cpu().numpy()
+    _lib.check(eng.lib.trl_load_weights(eng._h, blob, len(blob)))
+    again = eng.facenet_embed(faces).cpu().numpy()
+    assert np.isfinite(first).all() and np.array_equal(first, again)
+    assert all(r["precision"] == 1 for r in eng.facenet_plan()[1:-1])
+    eng.close()
+    assert eng._h is None

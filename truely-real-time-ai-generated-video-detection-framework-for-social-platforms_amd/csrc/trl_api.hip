@@ -93,8 +93,7 @@ int trl_destroy(trl_ctx* c) {
     (void)hipSetDevice(c->cfg.device);
     (void)hipDeviceSynchronize();            // (also ends a call that was queued and never finished: its kernels are done)
     c->pend.active = false;
-    for (auto& kv : c->W) if (kv.second.pt) (void)hipFree(kv.second.pt);
-    if (c->wdev) (void)hipFree(c->wdev);
+    trl_free_weights(c);
     if (c->arena.base) (void)hipFree(c->arena.base);
     if (c->scratch.base) (void)hipFree(c->scratch.base);
     if (c->sims_tmp.base) (void)hipFree(c->sims_tmp.base);
@@ -125,29 +124,6 @@ int trl_destroy(trl_ctx* c) {
 }
 
 }  // extern "C"
-
-// ---- weights ---------------------------------------------------------------------------------------
-namespace {
-struct Entry {
-    char name[56];
-    uint32_t ndim;
-    uint32_t dims[4];
-    uint64_t offset;
-    uint64_t nbytes;
-};
-static_assert(sizeof(Entry) == 96, "TRLW entry layout");
-}  // namespace
-
-const DevW* trl_w(trl_ctx* c, const std::string& name) {
-    auto it = c->W.find(name);
-    if (it == c->W.end()) { trl_set_error("weight matrix '%s' not loaded", name.c_str()); return nullptr; }
-    return &it->second;
-}
-const DevV* trl_v(trl_ctx* c, const std::string& name) {
-    auto it = c->V.find(name);
-    if (it == c->V.end()) { trl_set_error("weight vector '%s' not loaded", name.c_str()); return nullptr; }
-    return &it->second;
-}
 
 // ---- red zones (trl_debug_redzone) ---------------------------------------------------------------------
 // One workgroup column per gap: res[3 g] += bytes of gap g that differ from `byte`, res[3 g + 1] / [3 g + 2] = min / max of their
@@ -272,179 +248,6 @@ int trl_ensure(trl_ctx* c, Arena& a, size_t bytes) {
     a.off = 0;
     a.blocks.clear();
     if (c->dbg_poison >= 0) TRL_HIP(hipMemset(a.base, c->dbg_poison, ncap));   // test hook: workspaces that grow stay poisoned
-    return TRL_OK;
-}
-
-extern "C" int trl_load_weights(trl_ctx* c, const void* blob, size_t nbytes) {
-    if (!c || !blob) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
-    const uint8_t* b = (const uint8_t*)blob;
-    if (nbytes < 16 || memcmp(b, "TRLW0001", 8) != 0) { trl_set_error("bad weights blob magic"); return TRL_ERR_WEIGHTS; }
-    uint32_t nt;
-    memcpy(&nt, b + 8, 4);
-    if (16 + (size_t)nt * sizeof(Entry) > nbytes) { trl_set_error("truncated weights blob"); return TRL_ERR_WEIGHTS; }
-    const Entry* ent = (const Entry*)(b + 16);
-    TRL_HIP(hipSetDevice(c->cfg.device));
-
-    struct Pending { std::string name; bool mat; int K, Cout, Kpad, ld, n; size_t off; const float* src; };
-    std::vector<Pending> items;
-    size_t total = 0;
-    auto add_mat = [&](const std::string& name, int K, int Cout, const float* src) {
-        Pending p; p.name = name; p.mat = true; p.K = K; p.Cout = Cout; p.Kpad = (K + 15) / 16 * 16; p.ld = (Cout + 31) / 32 * 32;
-        p.n = 0; p.src = src; p.off = total;
-        total += ((size_t)p.Kpad * p.ld * 4 + 255) & ~(size_t)255;
-        items.push_back(p);
-    };
-    auto add_vec = [&](const std::string& name, int n, const float* src) {
-        Pending p; p.name = name; p.mat = false; p.K = p.Cout = p.Kpad = p.ld = 0; p.n = n; p.src = src; p.off = total;
-        total += ((size_t)((n + 127) / 128 * 128) * 4 + 255) & ~(size_t)255;
-        items.push_back(p);
-    };
-    std::unordered_map<std::string, const Entry*> idx;
-    for (uint32_t i = 0; i < nt; i++) {
-        const Entry& e = ent[i];
-        if (e.offset > nbytes || e.nbytes > nbytes - e.offset || (e.offset & 3)) { trl_set_error("tensor out of blob bounds"); return TRL_ERR_WEIGHTS; }
-        std::string name(e.name, strnlen(e.name, 56));
-        // the declared shape must account for exactly the bytes the entry owns (the copies below trust the shape)
-        const uint64_t elems = e.ndim == 2 ? (uint64_t)e.dims[0] * e.dims[1] : (e.ndim == 1 ? (uint64_t)e.dims[0] : 0);
-        if ((e.ndim == 1 || e.ndim == 2) && (elems == 0 || elems > (1ull << 31) || elems * 4 != e.nbytes)) {
-            trl_set_error("tensor '%s': shape and byte count disagree", name.c_str());
-            return TRL_ERR_WEIGHTS;
-        }
-        idx[name] = &e;
-        const float* src = (const float*)(b + e.offset);
-        if (e.ndim == 2) add_mat(name, (int)e.dims[0], (int)e.dims[1], src);
-        else if (e.ndim == 1) add_vec(name, (int)e.dims[0], src);
-    }
-    // Convs that read the same input run as ONE conv: out + ".w" = the parts' matrices side by side (same K), out + suffix = their
-    // per-column vectors likewise, for every suffix.  Each output column keeps its own fmaf chain, so results are unchanged.
-    std::vector<std::vector<float>> keep_alive;
-    keep_alive.reserve(512);                       // (add_mat / add_vec keep pointers into it)
-    auto concat_cols = [&](const std::string& out, const std::vector<std::string>& parts, std::initializer_list<const char*> suffixes) -> int {
-        int K = -1, tot = 0;
-        for (auto& p : parts) {
-            auto it = idx.find(p + ".w");
-            if (it == idx.end() || it->second->ndim != 2) { trl_set_error("missing tensor %s.w", p.c_str()); return TRL_ERR_WEIGHTS; }
-            if (K < 0) K = (int)it->second->dims[0];
-            if (K != (int)it->second->dims[0]) { trl_set_error("%s.w: the convs merged into %s disagree on K", p.c_str(), out.c_str()); return TRL_ERR_WEIGHTS; }
-            for (const char* sfx : suffixes) {
-                auto iv = idx.find(p + sfx);
-                if (iv == idx.end()) { trl_set_error("missing tensor %s%s", p.c_str(), sfx); return TRL_ERR_WEIGHTS; }
-                if (iv->second->ndim != 1 || iv->second->dims[0] != it->second->dims[1]) { trl_set_error("tensor %s%s has an unexpected shape", p.c_str(), sfx); return TRL_ERR_WEIGHTS; }
-            }
-            tot += (int)it->second->dims[1];
-        }
-        keep_alive.emplace_back((size_t)K * tot);
-        std::vector<float>& wm = keep_alive.back();
-        int col = 0;
-        for (auto& p : parts) {
-            const Entry* e = idx[p + ".w"];
-            const float* src = (const float*)(b + e->offset);
-            const int co = (int)e->dims[1];
-            for (int k = 0; k < K; k++) for (int j = 0; j < co; j++) wm[(size_t)k * tot + col + j] = src[(size_t)k * co + j];
-            col += co;
-        }
-        add_mat(out + ".w", K, tot, wm.data());
-        for (const char* sfx : suffixes) {
-            keep_alive.emplace_back();
-            std::vector<float>& v = keep_alive.back();
-            for (auto& p : parts) {
-                const Entry* e = idx[p + sfx];
-                v.insert(v.end(), (const float*)(b + e->offset), (const float*)(b + e->offset) + e->dims[0]);
-            }
-            add_vec(out + sfx, tot, v.data());
-        }
-        return TRL_OK;
-    };
-    const auto bn = {".scale", ".shift"};           // FaceNet's 1x1 BasicConv2d branches: folded batch norm per column
-    for (int i = 0; i < 5; i++) {
-        const std::string p = "facenet.repeat_1." + std::to_string(i);
-        TRL_CHECK(concat_cols(p + ".fused", {p + ".branch0", p + ".branch2.0", p + ".branch1.0"}, bn));   // [b0 | b2.0 | b1.0]
-    }
-    for (int i = 0; i < 10; i++) {
-        const std::string p = "facenet.repeat_2." + std::to_string(i);
-        TRL_CHECK(concat_cols(p + ".fused", {p + ".branch0", p + ".branch1.0"}, bn));
-    }
-    for (int i = 0; i < 6; i++) {
-        const std::string p = i < 5 ? "facenet.repeat_3." + std::to_string(i) : std::string("facenet.block8");
-        TRL_CHECK(concat_cols(p + ".fused", {p + ".branch0", p + ".branch1.0"}, bn));
-    }
-    TRL_CHECK(concat_cols("facenet.mixed_7a.fused", {"facenet.mixed_7a.branch0.0", "facenet.mixed_7a.branch1.0", "facenet.mixed_7a.branch2.0"}, bn));
-    // merged heads: the 1x1 class and regression (and landmark) convs as one [K][6] / [K][16] matrix
-    TRL_CHECK(concat_cols("pnet.heads", {"pnet.conv4_1", "pnet.conv4_2"}, {".b"}));
-    TRL_CHECK(concat_cols("rnet.heads", {"rnet.dense5_1", "rnet.dense5_2"}, {".b"}));
-    TRL_CHECK(concat_cols("onet.heads", {"onet.dense6_1", "onet.dense6_2", "onet.dense6_3"}, {".b"}));
-    // InceptionResnetV1's classifier is optional (a blob packed from a checkpoint without `logits`, or with include_logits=False):
-    // both tensors or neither, w [512][C] and b [C], 1 <= C <= 65535 (the kernel's grid.y carries the class groups)
-    const char* const lw_name = "facenet.logits.w";
-    const char* const lb_name = "facenet.logits.b";
-    {
-        auto iw = idx.find(lw_name), ib = idx.find(lb_name);
-        const char* bad = nullptr;
-        if (iw != idx.end() || ib != idx.end()) {
-            if (iw == idx.end()) { trl_set_error("missing tensor %s (the blob holds %s)", lw_name, lb_name); bad = lw_name; }
-            else if (ib == idx.end()) { trl_set_error("missing tensor %s (the blob holds %s)", lb_name, lw_name); bad = lb_name; }
-            else if (iw->second->ndim != 2 || iw->second->dims[0] != 512 || iw->second->dims[1] < 1 || iw->second->dims[1] > 65535) {
-                trl_set_error("tensor '%s' must be [512][C] with 1 <= C <= 65535", lw_name);
-                bad = lw_name;
-            } else if (ib->second->ndim != 1 || ib->second->dims[0] != iw->second->dims[1]) {
-                trl_set_error("tensor '%s' must hold the %u biases of %s", lb_name, iw->second->dims[1], lw_name);
-                bad = lb_name;
-            }
-        }
-        if (bad) { c->have_weights = false; return TRL_ERR_WEIGHTS; }   // (a refused blob leaves the context without weights)
-    }
-
-    if (c->cfg.embed_precision == 2) {   // an fp16 conv weight that rounds past +-65504 would become inf: refuse the blob instead
-        for (auto& p : items) {
-            if (!p.mat || p.name.rfind("facenet.", 0) != 0 || p.name == "facenet.conv2d_1a.w" || p.name == "facenet.last_linear.w" || p.name == lw_name) continue;
-            for (size_t i = 0; i < (size_t)p.K * p.Cout; i++)
-                if (!(fabsf(p.src[i]) < 65520.f)) {   // 65520 is the rounding midpoint to the next (infinite) binade; NaN fails too
-                    trl_set_error("weight %s[%zu] = %g is outside the fp16 range", p.name.c_str(), i, p.src[i]);
-                    return TRL_ERR_WEIGHTS;
-                }
-        }
-    }
-    std::vector<char> host(total, 0);
-    for (auto& p : items) {
-        float* dst = (float*)(host.data() + p.off);
-        if (p.mat) { for (int k = 0; k < p.K; k++) memcpy(dst + (size_t)k * p.ld, p.src + (size_t)k * p.Cout, (size_t)p.Cout * 4); }
-        else memcpy(dst, p.src, (size_t)p.n * 4);
-    }
-    c->have_weights = false;                       // (a refused blob leaves the context without weights)
-    if (c->wdev) { TRL_HIP(hipDeviceSynchronize()); TRL_HIP(hipFree(c->wdev)); c->wdev = nullptr; }
-    TRL_HIP(hipMalloc((void**)&c->wdev, total));
-    TRL_HIP(hipMemcpy(c->wdev, host.data(), total, hipMemcpyHostToDevice));
-    c->wbytes = total;
-    for (auto& kv : c->W) if (kv.second.pt) (void)hipFree(kv.second.pt);
-    c->W.clear(); c->V.clear();
-    c->logits_w = nullptr; c->logits_b = nullptr; c->num_classes = 0;
-    for (auto& p : items) {
-        if (p.mat) { DevW w; w.p = (float*)(c->wdev + p.off); w.K = p.K; w.Cout = p.Cout; w.Kpad = p.Kpad; w.ld = p.ld; c->W[p.name] = w; }
-        else { DevV v; v.p = (float*)(c->wdev + p.off); v.n = p.n; c->V[p.name] = v; }
-    }
-
-    // Every tensor the four nets use is checked here, never at a call: the MTCNN layers resolve into c->mt, what the kernels
-    // choose by (slope classes, the conv3 screen bound) comes from the host image, and the embedder's walk runs once over a
-    // counting arena on one 160 x 160 face (every geometry names the same tensors).
-    TRL_CHECK(trl_resolve_nets(c, host.data()));
-    TRL_CHECK(trl_pnet_prepare(c, host.data()));
-    Arena count = Arena::counter(c->scratch.guard);
-    TRL_CHECK(trl_run_facenet(c, count, nullptr, 1, 160, 160, nullptr, nullptr, nullptr));
-    c->fn_need_key[0] = 0;
-    if (idx.count(lw_name)) {                        // (shapes checked above)
-        c->logits_w = trl_w(c, lw_name);
-        c->logits_b = trl_v(c, lb_name)->p;
-        c->num_classes = c->logits_w->Cout;
-    }
-    if (c->cfg.embed_precision >= 1) {   // bf16 / fp16 copies of the embedder's conv weights (all but the 3-channel stem, the final linear and the classifier)
-        for (auto& kv : c->W) {
-            const std::string& nm = kv.first;
-            if (nm.rfind("facenet.", 0) != 0 || nm == "facenet.conv2d_1a.w" || nm == "facenet.last_linear.w" || nm == lw_name) continue;
-            TRL_CHECK(trl_make_weight_bf16(&kv.second, nullptr, c->cfg.embed_precision));
-        }
-        TRL_HIP(hipDeviceSynchronize());
-    }
-    c->have_weights = true;
     return TRL_OK;
 }
 

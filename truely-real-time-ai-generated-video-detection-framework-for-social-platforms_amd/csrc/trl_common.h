@@ -4,7 +4,6 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/truely_hip.h"
@@ -51,10 +50,7 @@ struct DevW {          // a weight matrix on the device, [Kpad][ld] row-major, z
     uint16_t* pt = nullptr;   // optional bf16 copy, TRANSPOSED [Cout rounded to 64][ldt] (k contiguous: the MFMA B operand)
     int ldt = 0;              // K rounded up to 32
 };
-struct DevV {          // a per-channel vector, padded to a multiple of 128 floats
-    float* p = nullptr;
-    int n = 0;
-};
+// (a per-channel vector is a bare float*, padded to a multiple of 128 floats: its length was checked at load)
 
 // NHWC activation view
 struct Act {

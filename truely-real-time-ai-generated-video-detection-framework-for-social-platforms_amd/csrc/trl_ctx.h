@@ -2,6 +2,7 @@
 #pragma once
 #include "trl_common.h"
 #include "trl_capacity.h"   // LvLayout, the FLG_* words, CascadeCaps
+#include "trl_facenet.h"    // FaceNet's table of convs: FN_ROWS
 
 // One PNet candidate (generateBoundingBox row + its cell index).  40 bytes.
 struct Cand {
@@ -54,17 +55,19 @@ enum { TRL_PNET = 0, TRL_RNET = 1, TRL_ONET = 2 };
 extern const NetDesc trl_nets[3];
 inline const NetDesc& trl_net_of(int net) { return trl_nets[net == 24 ? TRL_RNET : TRL_ONET]; }   // the API's net argument: 24 / 48
 struct NetLayerW { const DevW* w = nullptr; const float* b = nullptr; const float* slope = nullptr; };   // a conv layer's device tensors
+struct FnW { const DevW* w = nullptr; const float* scale = nullptr; const float* shift = nullptr; const float* bias = nullptr; };   // a FaceNet row's
 
 struct trl_ctx {
     trl_config cfg;
     bool have_weights = false;
     char* wdev = nullptr;            // all weights, device
     size_t wbytes = 0;
-    std::unordered_map<std::string, DevW> W;
-    std::unordered_map<std::string, DevV> V;
-    // Resolved by trl_load_weights, which refuses a blob that lacks or mis-shapes any of them: the tensors of every layer of
-    // trl_nets[] and the conv1 PReLU slope class of R-Net / O-Net (trl_front.hip).  No MTCNN path looks a tensor up by name.
+    std::vector<DevW> wmat;          // the matrices in wdev, each the owner of its 16-bit copy where it has one; mt, fn and logits_w point into it
+    // Resolved by trl_load_weights (trl_weights.hip), which refuses a blob that lacks or mis-shapes any of them: the tensors of every
+    // layer of trl_nets[], of every row of FaceNet's table (trl_facenet.h), and the conv1 PReLU slope class of R-Net / O-Net
+    // (trl_front.hip).  No path looks a tensor up by name: the name -> tensor directory ends with the load.
     NetLayerW mt[3][9];
+    FnW fn[FN_ROWS];
     int front_mode[3] = {0, 0, 0};
     // InceptionResnetV1's classifier, when the blob holds one ("facenet.logits.w" [512][C] / ".b" [C], both or neither): always f32
     const DevW* logits_w = nullptr;
@@ -168,11 +171,10 @@ template <class F> int trl_carve_scratch(trl_ctx* c, F&& carve) {
 // A context holds at most one call in flight (trl_detect_embed_begin .. _end); anything else that touches its workspaces meanwhile
 // would corrupt that call silently: TRL_ERR_STATE (and TRL_ERR_INVALID for a null context)
 int trl_check_idle(trl_ctx* c);
-const DevW* trl_w(trl_ctx* c, const std::string& name);
-const DevV* trl_v(trl_ctx* c, const std::string& name);
+void trl_free_weights(trl_ctx* c);   // trl_weights.hip: the device weights and every 16-bit copy; the context then has none
 
-// networks (trl_nets.hip).  Every walk takes its activations from X; over a counting X it still checks every shape and tensor
-// (the walk of trl_load_weights).
+// networks (trl_nets.hip).  Every walk takes its activations from X; over a counting X it still checks every shape (the walk of
+// trl_load_weights).
 // features: d_emb receives the 512 values in front of F.normalize (last_bn's output) instead of the embedding
 int trl_run_facenet(trl_ctx* c, Arena& X, const float* d_faces, int n, int h, int w, const uint8_t* d_valid, float* d_emb, hipStream_t s,
                     bool features = false);
@@ -182,7 +184,6 @@ int trl_run_facenet(trl_ctx* c, Arena& X, const float* d_faces, int n, int h, in
 int trl_run_net(trl_ctx* c, Arena& X, const NetDesc& d, int first, const Act& x, float* d_out, hipStream_t s, const int32_t* m_dev = nullptr,
                 int m_base = 0);
 // trl_load_weights, after the upload: himg is the staged host image, laid out like c->wdev (trl_host_of reads a device tensor's copy)
-int trl_resolve_nets(trl_ctx* c, const char* himg);
 inline const float* trl_host_of(const trl_ctx* c, const char* himg, const float* dev) { return (const float*)(himg + ((const char*)dev - c->wdev)); }
 int trl_front_slope_class(const float* h_slope, int n);
 // the fused front kernel of R-Net / O-Net over records t0 .. t0 + nc - 1 of c->cb.cbox: pooled maps [nc][P][P][C1]

@@ -36,8 +36,8 @@ struct Runner {
     // the plan rows of trl_debug_facenet_plan and the armed capture of trl_debug_facenet_capture (conv index = walk order)
     std::vector<trl_fn_plan_row>* plan = nullptr;
     int nconv = 0;
-    std::string layer;                // name of the conv being issued (set by bconv / resid)
-    struct ConvMeta { int idx; std::string layer; Act x, y; bool has_res; Act res; };
+    const char* layer = "";           // name of the conv being issued: FaceNet's point into its table, they outlive the walk
+    struct ConvMeta { int idx; const char* layer; Act x, y; bool has_res; Act res; };
     std::vector<ConvMeta> pending_meta;
 
     // Host bookkeeping behind a launch: the plan row (g_trl_conv_choice is what the launcher just picked) and, when this conv is
@@ -49,7 +49,7 @@ struct Runner {
         const TrlConvChoice& ch = g_trl_conv_choice;
         r.conv = m.idx; r.family = ch.family; r.bm = ch.bm; r.bn = ch.bn; r.bk = ch.bk; r.pad = ch.pad; r.nz = ch.nz;
         r.m = a.M; r.cout = a.Cout; r.k = a.K; r.precision = a.lowp; r.has_res = m.has_res;
-        strncpy(r.layer, m.layer.c_str(), sizeof(r.layer) - 1);
+        strncpy(r.layer, m.layer, sizeof(r.layer) - 1);
         plan->push_back(r);
         if (plan != &c->fn_plan || c->fn_cap_arm != m.idx) return;   // captures are FaceNet convs only
         int st = capture(0, m.x, 1 << 30, 0);
@@ -130,18 +130,6 @@ struct Runner {
         const int st = launch();
         if (st != TRL_OK) err = st;
     }
-    // A tensor the walk names is required: a miss is TRL_ERR_WEIGHTS (trl_w / trl_v say which), never "this layer has none"
-    const DevW* mat(const std::string& name) {
-        const DevW* w = trl_w(c, name);
-        if (!w && err == TRL_OK) err = TRL_ERR_WEIGHTS;
-        return w;
-    }
-    const float* vec(const std::string& name, const DevW* w) {   // one value per output column of w
-        const DevV* v = trl_v(c, name);
-        if (v && w && v->n != w->Cout) { trl_set_error("weight vector '%s' has %d elements, its conv %d columns", name.c_str(), v->n, w->Cout); v = nullptr; }
-        if (!v && err == TRL_OK) err = TRL_ERR_WEIGHTS;
-        return v ? v->p : nullptr;
-    }
 
     // generic conv launcher; `into` selects a pre-allocated (concat) destination view
     Act conv(const Act& x, const DevW* w, const float* bias, const float* scale, const float* shift, const float* slope,
@@ -218,16 +206,14 @@ struct Runner {
         else launched(a, meta);
         return true;
     }
-    // BasicConv2d: conv(no bias) + folded BN + ReLU
-    Act bconv(const Act& x, const std::string& name, int kh, int kw, int sh, int sw, int ph, int pw, const Act* into = nullptr) {
-        if (plan) layer = name;
-        const DevW* w = mat(name + ".w");
-        return conv(x, w, nullptr, vec(name + ".scale", w), vec(name + ".shift", w), nullptr, kh, kw, sh, sw, ph, pw, TRL_ACT_RELU, into, nullptr, 0.f);
-    }
-    Act resid(const Act& cat, const Act& x, const std::string& name, float scale, bool relu) {
-        if (plan) layer = name;
-        const DevW* w = mat(name + ".w");
-        return conv(cat, w, vec(name + ".b", w), nullptr, nullptr, nullptr, 1, 1, 1, 1, 0, 0, relu ? TRL_ACT_RELU : TRL_ACT_NONE, nullptr, &x, scale);
+    // Row r of FaceNet's table (trl_facenet.h): its geometry, and the tensors trl_load_weights resolved for it.  A BasicConv2d ends
+    // in ReLU and the final linear in nothing; an up-projection adds scale * itself to the block input `res`, then ReLU or not
+    Act fconv(const Act& x, int r, const Act* into = nullptr, const Act* res = nullptr, float scale = 0.f, bool relu = true) {
+        const FnRow& g = trl_facenet_rows()[r];
+        const FnW& t = c->fn[r];
+        layer = g.name;
+        return conv(x, t.w, t.bias, t.scale, t.shift, nullptr, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw,
+                    g.kind == FN_LINEAR || !relu ? TRL_ACT_NONE : TRL_ACT_RELU, into, res, scale);
     }
     Act pool(const Act& x, int k, int st, int ceil_mode, const Act* into = nullptr) {
         const int OH = trl_pool_out(x.h, k, st, ceil_mode), OW = trl_pool_out(x.w, k, st, ceil_mode);
@@ -242,50 +228,45 @@ struct Runner {
     }
 };
 
-// The 1x1 branches that read the block input run as one fused conv (weights concatenated at load time);
-// the concat buffer doubles as their scratch: a slice is only overwritten after its last reader has run.
-Act block35(Runner& R, const Act& x, const std::string& p) {
+// The blocks of InceptionResnetV1, each over the rows of FaceNet's table that start at r0.  The 1x1 branches that read the block
+// input run as one fused conv (weights concatenated at load time); the concat buffer doubles as their scratch: a slice is only
+// overwritten after its last reader has run.
+Act block35(Runner& R, const Act& x, int r0) {
     Act cat = R.alloc(x.n, x.h, x.w, 96, x.bf);
     Act s1 = Runner::slice(cat, 32, 32), s2 = Runner::slice(cat, 64, 32);
-    R.bconv(x, p + ".fused", 1, 1, 1, 1, 0, 0, &cat);                 // [branch0 | branch2.0 | branch1.0]
-    Act b2 = R.bconv(s1, p + ".branch2.1", 3, 3, 1, 1, 1, 1);         // reads branch2.0 (cols 32:64)
-    R.bconv(s2, p + ".branch1.1", 3, 3, 1, 1, 1, 1, &s1);             // reads branch1.0 (64:96) -> final branch1 at 32:64
-    R.bconv(b2, p + ".branch2.2", 3, 3, 1, 1, 1, 1, &s2);             // final branch2 at 64:96
-    return R.resid(cat, x, p + ".conv2d", 0.17f, true);
+    R.fconv(x, r0 + B35_FUSED, &cat);                // [branch0 | branch2.0 | branch1.0]
+    Act b2 = R.fconv(s1, r0 + B35_B2_1);             // reads branch2.0 (cols 32:64)
+    R.fconv(s2, r0 + B35_B1_1, &s1);                 // reads branch1.0 (64:96) -> final branch1 at 32:64
+    R.fconv(b2, r0 + B35_B2_2, &s2);                 // final branch2 at 64:96
+    return R.fconv(cat, r0 + B35_UP, nullptr, &x, 0.17f);
 }
 // The same block in 4 launches for the small-map conv family (f32, M <= 16384): the fused 1x1 scatters its columns into a
 // 128-wide buffer W = [branch0 | (free) | branch2.0 | branch1.0], so the two independent 3x3s can share ONE launch without a
 // hazard -- branch1.1 reads W[96:128] and writes the free slot W[32:64] (nobody reads it), branch2.1 reads W[64:96] into a
 // temporary -- then branch2.2 writes W[64:96] and the up-projection reads W[0:96] = [branch0 | branch1 | branch2].
-Act block35_grouped(Runner& R, const Act& x, const std::string& p) {
+Act block35_grouped(Runner& R, const Act& x, int r0) {
     Act W = R.alloc(x.n, x.h, x.w, 128, false);
     Act w96 = Runner::slice(W, 0, 96);
     Act f1 = Runner::slice(W, 32, 32), f2 = Runner::slice(W, 64, 32), f3 = Runner::slice(W, 96, 32);
-    R.ysplit = 32; R.yskip = 32;                                      // columns >= 32 land 32 channels further right
-    R.bconv(x, p + ".fused", 1, 1, 1, 1, 0, 0, &w96);                 // [branch0 | - | branch2.0 | branch1.0]
+    R.ysplit = 32; R.yskip = 32;                     // columns >= 32 land 32 channels further right
+    R.fconv(x, r0 + B35_FUSED, &w96);                // [branch0 | - | branch2.0 | branch1.0]
     R.ysplit = 1 << 30; R.yskip = 0;
     R.begin_group();
-    Act b2 = R.bconv(f2, p + ".branch2.1", 3, 3, 1, 1, 1, 1);         // W[64:96] -> temporary
-    R.bconv(f3, p + ".branch1.1", 3, 3, 1, 1, 1, 1, &f1);             // W[96:128] -> W[32:64]
+    Act b2 = R.fconv(f2, r0 + B35_B2_1);             // W[64:96] -> temporary
+    R.fconv(f3, r0 + B35_B1_1, &f1);                 // W[96:128] -> W[32:64]
     R.end_group();
-    R.bconv(b2, p + ".branch2.2", 3, 3, 1, 1, 1, 1, &f2);             // -> W[64:96] (branch2.0 is dead)
-    return R.resid(w96, x, p + ".conv2d", 0.17f, true);
+    R.fconv(b2, r0 + B35_B2_2, &f2);                 // -> W[64:96] (branch2.0 is dead)
+    return R.fconv(w96, r0 + B35_UP, nullptr, &x, 0.17f);
 }
-Act block17(Runner& R, const Act& x, const std::string& p) {
-    Act cat = R.alloc(x.n, x.h, x.w, 256, x.bf);
-    Act s1 = Runner::slice(cat, 128, 128);
-    R.bconv(x, p + ".fused", 1, 1, 1, 1, 0, 0, &cat);                 // [branch0 | branch1.0]
-    Act a2 = R.bconv(s1, p + ".branch1.1", 1, 7, 1, 1, 0, 3);
-    R.bconv(a2, p + ".branch1.2", 7, 1, 1, 1, 3, 0, &s1);
-    return R.resid(cat, x, p + ".conv2d", 0.10f, true);
-}
-Act block8(Runner& R, const Act& x, const std::string& p, float scale, bool relu) {
-    Act cat = R.alloc(x.n, x.h, x.w, 384, x.bf);
-    Act s1 = Runner::slice(cat, 192, 192);
-    R.bconv(x, p + ".fused", 1, 1, 1, 1, 0, 0, &cat);                 // [branch0 | branch1.0]
-    Act a2 = R.bconv(s1, p + ".branch1.1", 1, 3, 1, 1, 0, 1);
-    R.bconv(a2, p + ".branch1.2", 3, 1, 1, 1, 1, 0, &s1);
-    return R.resid(cat, x, p + ".conv2d", scale, relu);
+// Block17 (two branches of 128, a 1x7 then a 7x1) and Block8 (of 192, 1x3 then 3x1): the same walk over rows of the same roles
+Act block17_8(Runner& R, const Act& x, int r0, float scale, bool relu = true) {
+    const int half = trl_facenet_rows()[r0 + B17_FUSED].cout / 2;
+    Act cat = R.alloc(x.n, x.h, x.w, 2 * half, x.bf);
+    Act s1 = Runner::slice(cat, half, half);
+    R.fconv(x, r0 + B17_FUSED, &cat);                // [branch0 | branch1.0]
+    Act a2 = R.fconv(s1, r0 + B17_B1_1);
+    R.fconv(a2, r0 + B17_B1_2, &s1);
+    return R.fconv(cat, r0 + B17_UP, nullptr, &x, scale, relu);
 }
 
 }  // namespace
@@ -302,55 +283,54 @@ int trl_run_facenet(trl_ctx* c, Arena& X, const float* d_faces, int n, int h, in
         if (c->fn_cap_arm >= 0) for (auto& b : c->fn_cap) b.dims[3] = 0;
     }
     const Act x0 = Act::dense(d_faces, n, h, w, 3);
-    const std::string f = "facenet.";
-    Act x = R.bconv(x0, f + "conv2d_1a", 3, 3, 2, 2, 0, 0);
+    Act x = R.fconv(x0, FN_STEM + 0);                // conv2d_1a
     if (c->cfg.embed_precision >= 1) {   // everything after the 3-channel stem conv runs on 16-bit activations (trl_bf16.hip)
         Act xb = R.alloc(x.n, x.h, x.w, x.c, true);
         R.issue([&] { return trl_launch_to_bf16(x.p, x.pixels() * x.c, reinterpret_cast<uint16_t*>(xb.p), s, c->cfg.embed_precision); });
         x = xb;
     }
-    x = R.bconv(x, f + "conv2d_2a", 3, 3, 1, 1, 0, 0);
-    x = R.bconv(x, f + "conv2d_2b", 3, 3, 1, 1, 1, 1);
+    x = R.fconv(x, FN_STEM + 1);                     // conv2d_2a
+    x = R.fconv(x, FN_STEM + 2);                     // conv2d_2b
     x = R.pool(x, 3, 2, 0);
-    x = R.bconv(x, f + "conv2d_3b", 1, 1, 1, 1, 0, 0);
-    x = R.bconv(x, f + "conv2d_4a", 3, 3, 1, 1, 0, 0);
-    x = R.bconv(x, f + "conv2d_4b", 3, 3, 2, 2, 0, 0);
+    x = R.fconv(x, FN_STEM + 3);                     // conv2d_3b
+    x = R.fconv(x, FN_STEM + 4);                     // conv2d_4a
+    x = R.fconv(x, FN_STEM + 5);                     // conv2d_4b
     if (R.err != TRL_OK) return R.err;
     if (x.h < 3 || x.w < 3) { trl_set_error("face crop %dx%d too small for InceptionResnetV1", h, w); return TRL_ERR_INVALID; }
     const bool small_f32 = !x.bf && (long long)x.n * x.h * x.w <= 16384 && g_trl_no_fnconv == 0;
-    for (int i = 0; i < 5; i++) x = small_f32 ? block35_grouped(R, x, f + "repeat_1." + std::to_string(i)) : block35(R, x, f + "repeat_1." + std::to_string(i));
+    for (int i = 0; i < 5; i++) x = (small_f32 ? block35_grouped : block35)(R, x, FN_B35 + i * B35_ROWS);
     {   // Mixed_6a
         const int OH = (x.h - 3) / 2 + 1, OW = (x.w - 3) / 2 + 1;
         Act cat = R.alloc(n, OH, OW, 896, x.bf);
         Act s0 = Runner::slice(cat, 0, 384), s1 = Runner::slice(cat, 384, 256), s2 = Runner::slice(cat, 640, 256);
-        R.bconv(x, f + "mixed_6a.branch0", 3, 3, 2, 2, 0, 0, &s0);
-        Act a = R.bconv(x, f + "mixed_6a.branch1.0", 1, 1, 1, 1, 0, 0);
-        Act a2 = R.bconv(a, f + "mixed_6a.branch1.1", 3, 3, 1, 1, 1, 1);
-        R.bconv(a2, f + "mixed_6a.branch1.2", 3, 3, 2, 2, 0, 0, &s1);
+        R.fconv(x, FN_M6A + M6A_B0, &s0);
+        Act a = R.fconv(x, FN_M6A + M6A_B1_0);
+        Act a2 = R.fconv(a, FN_M6A + M6A_B1_1);
+        R.fconv(a2, FN_M6A + M6A_B1_2, &s1);
         R.pool(x, 3, 2, 0, &s2);
         x = cat;
     }
     if (R.err != TRL_OK) return R.err;
     if (x.h < 3 || x.w < 3) { trl_set_error("face crop %dx%d too small for InceptionResnetV1", h, w); return TRL_ERR_INVALID; }
-    for (int i = 0; i < 10; i++) x = block17(R, x, f + "repeat_2." + std::to_string(i));
+    for (int i = 0; i < 10; i++) x = block17_8(R, x, FN_B17 + i * B17_ROWS, 0.10f);
     {   // Mixed_7a
         const int OH = (x.h - 3) / 2 + 1, OW = (x.w - 3) / 2 + 1;
         Act cat = R.alloc(n, OH, OW, 1792, x.bf);
         Act s0 = Runner::slice(cat, 0, 384), s1 = Runner::slice(cat, 384, 256), s2 = Runner::slice(cat, 640, 256),
             s3 = Runner::slice(cat, 896, 896);
-        Act t = R.bconv(x, f + "mixed_7a.fused", 1, 1, 1, 1, 0, 0);   // [branch0.0 | branch1.0 | branch2.0]
+        Act t = R.fconv(x, FN_M7A + M7A_FUSED);      // [branch0.0 | branch1.0 | branch2.0]
         Act t0 = Runner::slice(t, 0, 256), t1 = Runner::slice(t, 256, 256), t2 = Runner::slice(t, 512, 256);
-        R.begin_group();                                              // three independent convs over slices of t: one launch
-        R.bconv(t0, f + "mixed_7a.branch0.1", 3, 3, 2, 2, 0, 0, &s0);
-        R.bconv(t1, f + "mixed_7a.branch1.1", 3, 3, 2, 2, 0, 0, &s1);
-        Act a2 = R.bconv(t2, f + "mixed_7a.branch2.1", 3, 3, 1, 1, 1, 1);
+        R.begin_group();                             // three independent convs over slices of t: one launch
+        R.fconv(t0, FN_M7A + M7A_B0_1, &s0);
+        R.fconv(t1, FN_M7A + M7A_B1_1, &s1);
+        Act a2 = R.fconv(t2, FN_M7A + M7A_B2_1);
         R.end_group();
-        R.bconv(a2, f + "mixed_7a.branch2.2", 3, 3, 2, 2, 0, 0, &s2);
+        R.fconv(a2, FN_M7A + M7A_B2_2, &s2);
         R.pool(x, 3, 2, 0, &s3);
         x = cat;
     }
-    for (int i = 0; i < 5; i++) x = block8(R, x, f + "repeat_3." + std::to_string(i), 0.20f, true);
-    x = block8(R, x, f + "block8", 1.0f, false);
+    for (int i = 0; i < 5; i++) x = block17_8(R, x, FN_B8 + i * B17_ROWS, 0.20f);
+    x = block17_8(R, x, FN_B8 + 5 * B17_ROWS, 1.0f, false);   // block8: no ReLU
     if (R.err != TRL_OK) return R.err;
     // avgpool_1a -> last_linear (no bias) -> last_bn (folded) -> F.normalize
     Act g;
@@ -363,9 +343,7 @@ int trl_run_facenet(trl_ctx* c, Arena& X, const float* d_faces, int n, int h, in
             return trl_launch_gap(x.p, n, x.h * x.w, x.c, g.p, s);
         });
     }
-    R.layer = f + "last_linear";
-    const DevW* wl = R.mat(f + "last_linear.w");
-    Act e = R.conv(g, wl, nullptr, R.vec(f + "last_bn.scale", wl), R.vec(f + "last_bn.shift", wl), nullptr, 1, 1, 1, 1, 0, 0, TRL_ACT_NONE, nullptr, nullptr, 0.f);
+    Act e = R.fconv(g, FN_LAST);
     // (features: the walk ends in front of the normalisation -- trl_facenet_features, what the logits layer reads)
     R.issue([&] { return features ? trl_launch_feat512(e.p, d_valid, n, d_emb, s) : trl_launch_l2norm512(e.p, d_valid, n, d_emb, s); });
     return R.err;
@@ -382,7 +360,8 @@ int trl_run_net(trl_ctx* c, Arena& X, const NetDesc& d, int first, const Act& x0
     for (int i = first; i < d.nl; i++) {
         const NetLayer& L = d.layer[i];
         if (!L.name) { x = R.pool(x, L.k, L.st, 1); continue; }
-        if (R.plan) R.layer = std::string(d.name) + "." + L.name;
+        char layer[32];                  // (a conv of this walk is launched, and its plan row written, inside R.conv)
+        if (R.plan) { snprintf(layer, sizeof layer, "%s.%s", d.name, L.name); R.layer = layer; }
         // a pool directly behind the conv runs in the conv's epilogue where the kernel has one: the 128-row tiles of R-Net conv2 and
         // O-Net conv2 / conv3 at production capacities (smaller launches, PNet and every other pool: separate launches as below)
         if (c->tail_pool && i + 2 < d.nl && !d.layer[i + 1].name &&
@@ -396,37 +375,3 @@ int trl_run_net(trl_ctx* c, Arena& X, const NetDesc& d, int first, const Act& x0
     }
     return R.err;
 }
-
-// trl_load_weights: every tensor trl_nets[] names exists with the shape its layer gives it -- K = k k Cin, cout columns, cout
-// biases and slopes -- and is resolved into c->mt; then what the kernels choose by: the conv1 slope class of the front kernel
-int trl_resolve_nets(trl_ctx* c, const char* himg) {
-    for (int id = 0; id < 3; id++) {
-        const NetDesc& d = trl_nets[id];
-        int cin = 3;
-        for (int i = 0; i < d.nl; i++) {
-            const NetLayer& L = d.layer[i];
-            c->mt[id][i] = NetLayerW();
-            if (!L.name) continue;
-            const std::string net = std::string(d.name) + ".", base = net + L.name;
-            const DevW* w = trl_w(c, base + ".w");
-            const DevV* b = trl_v(c, base + ".b");
-            const DevV* sl = L.prelu ? trl_v(c, net + L.prelu) : nullptr;
-            if (!w || !b || (L.prelu && !sl)) return TRL_ERR_WEIGHTS;   // (trl_w / trl_v named it)
-            if (w->K != L.k * L.k * cin || w->Cout != L.cout) {
-                trl_set_error("tensor '%s.w' is [%d][%d], its layer needs [%d][%d]", base.c_str(), w->K, w->Cout, L.k * L.k * cin, L.cout);
-                return TRL_ERR_WEIGHTS;
-            }
-            if (b->n != L.cout || (sl && sl->n != L.cout)) {
-                trl_set_error("tensor '%s' has %d elements, its layer %d channels", b->n != L.cout ? (base + ".b").c_str() : (net + L.prelu).c_str(),
-                              b->n != L.cout ? b->n : sl->n, L.cout);
-                return TRL_ERR_WEIGHTS;
-            }
-            c->mt[id][i] = NetLayerW{w, b->p, sl ? sl->p : nullptr};
-            cin = L.cout;
-        }
-        if (d.side) c->front_mode[id] = trl_front_slope_class(trl_host_of(c, himg, c->mt[id][0].slope), d.layer[0].cout);
-    }
-    return TRL_OK;
-}
-
-

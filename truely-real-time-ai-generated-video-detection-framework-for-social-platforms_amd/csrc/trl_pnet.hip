@@ -40,6 +40,10 @@ constexpr int REGION_A = C2_T * C2_T * C2_LD;        // 5508 floats: input tile,
 constexpr int REGION_B = P1_T * P1_T * 10 + 224;     // 4000 floats of pooled conv1 + the reach of conv2's zero-weight k padding (k = 90, 91 of the last cells: finite, zeroed once)
 static_assert(3 * 7 * 256 <= REGION_A, "input tile (+ the 28 overhang pixels of the 7x256 copy) fits region A");
 static_assert(P1_T * P1_T * 10 <= REGION_B, "pooled tile fits region B");
+// Phase 3 reuses region B (dead between conv2 and the next tile's conv1) for the fp16 screen's activation operands: the conv2 tile
+// in fp16 as [half of the channels][324 cells][8] (16 bytes per item: one aligned ds_read_b128 per tap), then the largest |x| of
+// every item as [2][324] floats, from float offset SCR_XM.
+constexpr int SCR_XM = 2 * C2_T * C2_T * 4;          // 2592 floats of fp16 tile in front of the maxima
 // Horizontal carry between consecutive tiles of a tile row (a workgroup takes RUNS of consecutive tiles): the right-most 4 pooled
 // columns and 2 conv2 columns of tile (ty, tx) ARE the left-most ones of tile (ty, tx + 1) -- the halo that 16x16-cell tiles
 // otherwise compute twice (conv1 x1.56, conv2 x1.27 of the useful work).  They are kept in LDS across the tile boundary, and a tile
@@ -280,6 +284,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
     // 256 = 6*42 + 4, (iy, ix) of pixel i follow from (iy0, ix0) with one conditional wrap, and the address is
     // a scalar tile base plus a 32-bit lane offset.  Interior tiles (the bulk) load without bounds tests.
     const int pin_iy0 = tid / IN_T, pin_ix0 = tid - pin_iy0 * IN_T;
+    int ctid = tid;          // the thread index, laundered once per tile (see the strip copies below)
     float4 pre[7];
     auto issue_input = [&](const TileId& t) {
         const TileId& g = t;
@@ -287,20 +292,25 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
         const char* srcb = reinterpret_cast<const char*>(a.pyr + (long long)t.f * a.pyr_stride + g.pix0 + (long long)gy0 * g.w + gx0);
         const int w16 = g.w * 12;                  // bytes per pyramid row (12 B pixels)
         const int hrem = g.h - gy0, wrem = g.w - gx0;
+        // (the thread's first pixel laundered per call: hoisted out of the tile loop, the per-pixel rows, columns and wrap masks
+        // derived from it stay in ~20 VGPRs and 14 SGPRs for the whole launch, at the register limit; recomputed, they are a
+        // handful of VALU per tile)
+        int iy0 = pin_iy0, ix0 = pin_ix0;
+        asm volatile("" : "+v"(iy0), "+v"(ix0));
         if (hrem >= IN_T && wrem >= IN_T) {
-            const unsigned v0 = (unsigned)(pin_iy0 * w16 + pin_ix0 * 12);
+            const unsigned v0 = (unsigned)(iy0 * w16 + ix0 * 12);
 #pragma unroll
             for (int i = 0; i < 7; i++) {
-                unsigned vo = v0 + (unsigned)(i * (6 * w16 + 48)) + ((pin_ix0 >= IN_T - 4 * i) ? (unsigned)(w16 - IN_T * 12) : 0u);
-                if (i == 6) vo = (tid < IN_T * IN_T - 6 * 256) ? vo : 0u;     // p >= 42*42: reload pixel 0 (lands in the RA tail)
+                unsigned vo = v0 + (unsigned)(i * (6 * w16 + 48)) + ((ix0 >= IN_T - 4 * i) ? (unsigned)(w16 - IN_T * 12) : 0u);
+                if (i == 6) vo = (ctid < IN_T * IN_T - 6 * 256) ? vo : 0u;     // p >= 42*42: reload pixel 0 (lands in the RA tail)
                 { const f32x3_nt v3 = *reinterpret_cast<const f32x3_nt*>(srcb + vo); pre[i] = make_float4(v3[0], v3[1], v3[2], 0.f); }
             }
         } else {
 #pragma unroll
             for (int i = 0; i < 7; i++) {
-                const bool wrap = pin_ix0 >= IN_T - 4 * i;
-                const int iy = pin_iy0 + 6 * i + (wrap ? 1 : 0), ix = pin_ix0 + 4 * i - (wrap ? IN_T : 0);
-                const bool ok = iy < hrem && ix < wrem && (i < 6 || tid < IN_T * IN_T - 6 * 256);
+                const bool wrap = ix0 >= IN_T - 4 * i;
+                const int iy = iy0 + 6 * i + (wrap ? 1 : 0), ix = ix0 + 4 * i - (wrap ? IN_T : 0);
+                const bool ok = iy < hrem && ix < wrem && (i < 6 || ctid < IN_T * IN_T - 6 * 256);
                 pre[i] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (ok) { const f32x3_nt v3 = *reinterpret_cast<const f32x3_nt*>(srcb + (unsigned)(iy * w16 + ix * 12)); pre[i] = make_float4(v3[0], v3[1], v3[2], 0.f); }
             }
@@ -315,7 +325,6 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
     // (the copies index with `ctid`, the thread index laundered once per tile: their ~12 lane addresses are then recomputed, one VALU
     // each, instead of hoisted out of the tile loop and -- at 256 VGPRs -- spilled; a scratch reload waits on vmcnt(0), i.e. on
     // the next tile's input loads that are in flight for exactly that reason)
-    int ctid = tid;
     auto copy_pooled = [&](auto SAVE_T, float* CP) {
         constexpr bool SAVE = decltype(SAVE_T)::value;          // tile -> strip (columns 16..19), or strip -> tile (columns 0..3)
         const int q = ctid & 15;
@@ -726,6 +735,41 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
         __syncthreads();
         stamp(5);
 
+        // The screen's activation operands, once per tile: RA's 324 x 16 conv2 values rounded to fp16 (the same plain cast screen()
+        // applied per tap and M-tile, about eight times per cell) into XH, and the largest |x| of each cell's 8-channel half into XM.
+        // Both live in RB: its last readers are phase 2's copy_pooled / copy_rows and conv2's A operands, all in front of the barrier
+        // above, and its next writer is the next tile's phase 1 (copy_pooled / copy_rows in, then the units), two barriers on; phase 1
+        // rewrites all 400 x 10 pooled words of every tile, whatever it carries (strip columns 0..3 and / or rows 0..3 copied in, the
+        // rest computed), so phase 2 never reads a word written here as an f32: that alone keeps conv2's zero-weight k padding
+        // finite.  Beyond it: a word of XH has an fp16 in its upper half, whose five exponent bits and top three mantissa bits
+        // are the f32's exponent, so a finite or infinite fp16 (mantissa bits 000 under an all-ones exponent at most) never makes
+        // it 255 -- only the fp16 NaN of a conv2 value that is already a NaN can; XM is clamped to the largest finite float, which
+        // changes no decision: every X above 65504 confirms its M-tile.  The zeroed tail RB[4000..] that the k padding of the
+        // last cells reaches is not touched.
+        // Item i = 324 half + cell, thread t takes t, t + 256, t + 512: consecutive lanes read RA 17 floats apart and write
+        // consecutive 16-byte / 4-byte slots.  In front of the next tile's prefetch: its 21 registers are not live yet.
+        if (a.screen) {
+            static_assert(SCR_XM + 2 * 324 <= P1_T * P1_T * 10, "fp16 conv2 tile + maxima stay inside the pooled tile");
+#pragma unroll
+            for (int p = 0; p < 3; p++) {
+                int i = ctid + 256 * p;
+                if (p == 2) i = i < 2 * 324 ? i : 2 * 324 - 1;          // (the spare threads repeat the last item: same values, no branch)
+                const float* src = RA + (i < 324 ? i * C2_LD : (i - 324) * C2_LD + 8);
+                f16x8 hv;
+                float m = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const float v = src[j];
+                    m = fmaxf(m, fabsf(v));
+                    hv[j] = (_Float16)v;
+                }
+                *reinterpret_cast<f16x8*>(RB + 4 * i) = hv;
+                RB[SCR_XM + i] = fminf(m, 3.402823466e38f);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();   // (uniform: a.screen is a kernel argument)
+        }
+
         // next tile's input: global loads into registers only (RA is still read by phase 3)
         tile_nxt = __builtin_amdgcn_readfirstlane(next_tile_s);
         if (tile_nxt < t_end) { nxt = decode(tile_nxt); if (!(dbg_skip & 1)) issue_input(nxt); }
@@ -849,12 +893,13 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
             bool cf0 = has0, cf1 = has1;                        // M-tiles that take the exact f32 path
             // fp16 screen: conv3 of each M-tile on v_mfma_f32_32x32x16_f16, one instruction per 3x3 tap
             // (K = the 16 conv2 channels), in the transposed layout of conv3 below -- lane l: cell l & 31, channels
-            // 8 (q >> 2) + (q & 3) + 4 hh.  Operands are rounded from the f32 tile and weights in LDS as they are read.  Then PReLU and
+            // 8 (q >> 2) + (q & 3) + 4 hh.  The activations come from the tile's fp16 copy in region B (one 16-byte read per tap, the |x|
+            // maximum of the same eight values beside it), the weights are rounded from LDS as they are read.  Then PReLU and
             // the logit difference d (one 16-term chain per half, the halves added): an M-tile is confirmed when some valid cell
             // has d + A X + B >= dthr (X: the cell's largest |conv2 input|), d is not finite or X exceeds fp16.  A cell the exact
             // path would let through the prefilter (d_exact >= dthr) always confirms its M-tile, so the records are unchanged.
             if (has0 && a.screen) {
-                const int sb0 = ((mt0 * 2 + (l31 >> 4)) * C2_T + (l31 & 15)) * C2_LD + 8 * hh;
+                const int sb0 = 324 * hh + (mt0 * 2 + (l31 >> 4)) * C2_T + (l31 & 15);   // item of the lane's cell and channel half (XH / XM above)
                 auto screen = [&](int mt, int sb) __attribute__((always_inline)) {
                     f32x16 S;
 #pragma unroll
@@ -866,15 +911,12 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
                     float xm = 0.f;
 #pragma unroll
                     for (int tap = 0; tap < 9; tap++) {
-                        const int to = ((tap / 3) * C2_T + tap % 3) * C2_LD;
-                        f16x8 wv, xv;
+                        const int to = (tap / 3) * C2_T + tap % 3;
+                        f16x8 wv;
 #pragma unroll
-                        for (int j = 0; j < 8; j++) {
-                            wv[j] = (_Float16)B3S[(tap * 16 + 8 * hh + j) * 32 + l31];
-                            const float v = RA[sb + to + j];
-                            xm = fmaxf(xm, fabsf(v));
-                            xv[j] = (_Float16)v;
-                        }
+                        for (int j = 0; j < 8; j++) wv[j] = (_Float16)B3S[(tap * 16 + 8 * hh + j) * 32 + l31];
+                        const f16x8 xv = *reinterpret_cast<const f16x8*>(RB + 4 * (sb + to));
+                        xm = fmaxf(xm, RB[SCR_XM + sb + to]);
                         S = __builtin_amdgcn_mfma_f32_32x32x16_f16(wv, xv, S, 0, 0, 0);
                     }
                     float part = 0.f;
@@ -895,7 +937,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
                     return __builtin_amdgcn_ballot_w64(lane < 32 && oy < g.oh && ox < g.ow && hit) != 0;
                 };
                 cf0 = screen(mt0, sb0);
-                if (has1) cf1 = screen(mt1, sb0 + 8 * C2_T * C2_LD);   // M-tile mt0 + 4: 8 conv2 rows down
+                if (has1) cf1 = screen(mt1, sb0 + 8 * C2_T);   // M-tile mt0 + 4: 8 conv2 rows down
                 if (DBG) { nscr += has1 ? 2 : 1; ncnf += (cf0 ? 1 : 0) + (cf1 ? 1 : 0); }
             }
             if (cf0 && cf1) {

@@ -584,6 +584,33 @@ int    trl_cluster_labels(const uint32_t* d_adj, long long pitch_words, const in
                           int32_t* d_labels, uint8_t* d_core, int32_t* d_count, void* d_ws, size_t ws_bytes, int* rounds_out,
                           void* stream);
 
+/* ---- Score histograms ("which threshold?") -------------------------------------------------------------------------------------
+ * Exact pair counts per score bin, genuine (d_qid[i] == d_gid[j]) and impostor pairs apart, of n query rows against the m gallery
+ * rows, without the n x m score matrix: the gallery is streamed once and a few KB are written.  From the counts follow the false
+ * and true accept rates of identify / cluster at every candidate threshold.  Context-free, caller-owned memory, work queued on
+ * `stream`, no synchronisation, the device that of d_mat.  (ABI v7, additive)
+ *   score    the gallery's (above).
+ *   edges    d_edges[nedges] f32 candidate thresholds, 1 <= nedges <= 1023, strictly ascending, no NaN, +-inf allowed (THE CALLER
+ *            guarantees the values: unsorted edges give unspecified counts, never an access out of bounds).
+ *   bin      cosine: #{e : edges[e] <= score}; euclidean: #{e : edges[e] < score}; both in 0..nedges, plain f32 comparisons
+ *            (-0 == +0).  A NaN score goes to slot nedges + 1.  So cosine accepts score >= edges[e] <=> bin > e, and euclidean
+ *            accepts score <= edges[e] <=> bin <= e: cumulative sums of the counts are the shipped predicates' counts.
+ *   counted  pair (i, j): i < n, j < m, d_qvalid[i] != 0, d_gvalid[j] != 0 (either mask may be null: all valid) and, with
+ *            pairs = 1 (upper), j > i.
+ *   pairs    0 all n x m pairs.  1 upper: n == m and d_q are THE SAME rows as the gallery's (the caller guarantees it, as for
+ *            trl_cluster_links); each unordered pair is counted once and the scores below the diagonal are not computed.
+ *   counts   d_counts [2][nedges + 2] int64, class 0 impostor, 1 genuine.  The call writes all of it; nothing is pre-zeroed.
+ * Counts are integers summed exactly: the same whatever n, strip length or stream.
+ * TRL_ERR_INVALID with nothing queued: nedges outside 1..1023, a metric or pairs other than 0 / 1, upper with n != m, ld out of
+ * range or m > ld, negative sizes, m > 2^31 - 1, max_strip_cols no multiple of 128, a workspace too small or not 8-byte aligned, a
+ * null pointer (d_q and d_qid may be null when n = 0, d_gid when m = 0).  n = 0 or m = 0: the counts are zero. */
+/* Device bytes of trl_gallery_hist's d_ws: 2 (nedges + 2) uint32 counters per workgroup (row tile x strip).  0 on bad arguments. */
+size_t trl_gallery_hist_workspace(int n, long long m, int nedges, int max_strip_cols);
+int    trl_gallery_hist(const float* d_q, const uint8_t* d_qvalid, const int32_t* d_qid, int n, const float* d_mat, long long ld,
+                        const float* d_n2, const uint8_t* d_gvalid, const int32_t* d_gid, long long m, int metric, int pairs,
+                        const float* d_edges, int nedges, long long* d_counts, void* d_ws, size_t ws_bytes, int max_strip_cols,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,17 @@ Cluster mode (FaceGallery.cluster: trl_cluster_links + trl_cluster_labels), n ro
 Per n one process under the same trace: 3 + 5 calls of cluster() (cosine 0.5, min_samples 4, on n / 16 identities of 16 noisy unit
 rows each, so that there is a graph to label), then 3 + 5 of scores() on the same n x n -- k_gallery_scores, the kernel whose
 main loop k_gallery_links shares, is the yardstick.  A row of the table is one kernel: its launches per call and the median over the
-5 measured calls of its time per call (the label kernels run once per round)."""
+5 measured calls of its time per call (the label kernels run once per round).
+
+Histogram mode (FaceGallery.score_histogram: trl_gallery_hist), the same embeddings, labels = the identities, E = 1000 edges:
+
+    python tools/gallery_kernel_stats.py --hist out_dir > profiles/hist_kernel_stats.csv
+    python tools/gallery_kernel_stats.py --hist-table out_dir
+
+Per n one process under the same trace, 3 + 5 calls of each phase in turn: score_histogram(rows, labels) (ALL pairs) followed by
+score_histogram() (UPPER: each unordered pair once); cluster() and scores() as above -- k_gallery_links and k_gallery_scores of the
+same run are the yardsticks; and, where the matrix fits (n <= 8192), what a user would otherwise write: scores() + torch.bucketize
++ torch.bincount (every kernel the three launch, k_gallery_scores included), whose counts must equal the histogram's."""
 import csv
 import glob
 import json
@@ -153,6 +163,107 @@ def run_all_cluster(out):
     table_cluster(out)
 
 
+HI_EDGES, HI_TORCH_MAX_N = 1000, 8192
+
+
+def run_hist(n):
+    import torch
+    from truely_amd.gallery import FaceGallery
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    centres = torch.nn.functional.normalize(torch.randn((n // CL_PER_ID, 512), generator=gen, device="cuda"), dim=1)
+    rows = centres.repeat_interleave(CL_PER_ID, dim=0) + 0.03 * torch.randn((n, 512), generator=gen, device="cuda")
+    perm = torch.randperm(n, generator=gen, device="cuda")
+    rows = torch.nn.functional.normalize(rows, dim=1)[perm]
+    ids = perm // CL_PER_ID
+    labels = ids.tolist()
+    edges = torch.linspace(-1, 1, HI_EDGES)
+    gal = FaceGallery(metric="cosine", capacity=n)
+    gal.add(rows, labels)
+    torch.cuda.synchronize()
+    calls = CL_WARMUP + CL_WARM
+    for _ in range(calls):
+        h_all = gal.score_histogram(rows, labels, edges=edges)
+        h_up = gal.score_histogram(edges=edges)
+    torch.cuda.synchronize()
+    for _ in range(calls):
+        gal.cluster(0.5, min_samples=4)
+    torch.cuda.synchronize()
+    for _ in range(calls):
+        gal.scores(rows)
+    torch.cuda.synchronize()
+    agree = None
+    if n <= HI_TORCH_MAX_N:
+        e_dev, slots = h_all["edges"], HI_EDGES + 2
+        for _ in range(calls):
+            s = gal.scores(rows)
+            b = torch.bucketize(s, e_dev, right=True)             # (cosine's rule: edges <= score; these inputs give no NaN)
+            b += (ids[:, None] == ids[None, :]) * slots
+            c = torch.bincount(b.flatten(), minlength=2 * slots).reshape(2, slots)
+        torch.cuda.synchronize()
+        agree = bool(torch.equal(c[0, :-1], h_all["impostor"]) and torch.equal(c[1, :-1], h_all["genuine"]))
+    diag = n                                                  # ALL = 2 UPPER + the diagonal (genuine)
+    total_all = int(h_all["genuine"].sum() + h_all["impostor"].sum() + h_all["nan"].sum())
+    total_up = int(h_up["genuine"].sum() + h_up["impostor"].sum() + h_up["nan"].sum())
+    print(json.dumps({"n": n, "edges": HI_EDGES, "pairs_all": total_all, "pairs_upper": total_up, "all_is_2_upper_plus_diagonal":
+                      total_all == 2 * total_up + diag, "torch_counts_equal": agree,
+                      "occupied_bins_impostor": int((h_all["impostor"] > 0).sum()), "occupied_bins_genuine": int((h_all["genuine"] > 0).sum()),
+                      "workspace_bytes": int(gal.lib.trl_gallery_hist_workspace(n, n, HI_EDGES, 0))}))
+
+
+def table_hist(out):
+    print("n,metric,edges,what,launches_per_call,median_us_per_call,min_us_per_call,max_us_per_call,tflops,over_links,over_hist_all,"
+          "occupied_bins_impostor,workspace_bytes,torch_counts_equal")
+    for n in CL_SHAPES:
+        d = os.path.join(out, f"hist_{n}")
+        info = json.load(open(os.path.join(d, "info.json")))
+        tr = _trace(d)
+        calls = CL_WARMUP + CL_WARM
+        per_call = {}                                         # what -> [us per call], warm-up included
+
+        def series(key, times, per):
+            assert times and len(times) == per * calls, (n, key, len(times))
+            per_call[key] = (per, [sum(times[c * per:(c + 1) * per]) / 1e3 for c in range(calls)])
+
+        hist = [e - s for s, e, name in tr if "k_gallery_hist" in name and "k_gallery_hist_sum" not in name]
+        sums = [e - s for s, e, name in tr if "k_gallery_hist_sum" in name]
+        series("k_gallery_hist ALL", hist[0::2], 1)           # the calls alternate: ALL, UPPER
+        series("k_gallery_hist UPPER", hist[1::2], 1)
+        series("k_gallery_hist_sum ALL", sums[0::2], 1)
+        series("k_gallery_links", [e - s for s, e, name in tr if "k_gallery_links" in name], 1)
+        at = [i for i, r in enumerate(tr) if "k_gallery_scores" in r[2]]
+        if n <= HI_TORCH_MAX_N:                               # the last `calls` k_gallery_scores launches open a torch-route call each
+            assert len(at) == 2 * calls, (n, len(at))
+            series("k_gallery_scores", [tr[i][1] - tr[i][0] for i in at[:calls]], 1)
+            per = at[calls + 1] - at[calls]                   # kernels of one call (behind the last call come the run's own checks)
+            route = [sum(e - s for s, e, _name in tr[a:a + per]) for a in at[calls:]]
+            per_call["scores + bucketize + bincount"] = (per, [t / 1e3 for t in route])
+        else:
+            assert len(at) == calls, (n, len(at))
+            series("k_gallery_scores", [tr[i][1] - tr[i][0] for i in at], 1)
+        med = {k: statistics.median(v[CL_WARMUP:]) for k, (_p, v) in per_call.items()}
+        for k, (per, v) in per_call.items():
+            v = v[CL_WARMUP:]
+            flop = {"k_gallery_hist ALL": 2.0 * n * n * 512, "k_gallery_hist UPPER": 1.0 * n * (n - 1) * 512,
+                    "k_gallery_links": 2.0 * n * n * 512, "k_gallery_scores": 2.0 * n * n * 512}.get(k)
+            tf = f"{flop / med[k] / 1e6:.1f}" if flop else ""
+            print(f"{n},cosine,{info['edges']},{k},{per},{med[k]:.1f},{min(v):.1f},{max(v):.1f},{tf},{med[k] / med['k_gallery_links']:.3f},"
+                  f"{med[k] / med['k_gallery_hist ALL']:.3f},{info['occupied_bins_impostor']},{info['workspace_bytes']},{info['torch_counts_equal']}")
+
+
+def run_all_hist(out):
+    for n in CL_SHAPES:
+        d = os.path.join(out, f"hist_{n}")
+        os.makedirs(d, exist_ok=True)
+        r = subprocess.run(["rocprofv3", "--kernel-trace", "-d", d, "-o", "t", "-f", "csv", "--", sys.executable, os.path.abspath(__file__),
+                            "run-hist", str(n)], capture_output=True, text=True, timeout=300)
+        if r.returncode != 0:
+            sys.exit(f"hist shape {n} failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+        print(line, file=sys.stderr, flush=True)
+        open(os.path.join(d, "info.json"), "w").write(line)
+    table_hist(out)
+
+
 def run_all(out):
     for m in M_SHAPES:
         for n in N_SHAPES:
@@ -179,5 +290,11 @@ if __name__ == "__main__":
         table_cluster(sys.argv[2])
     elif sys.argv[1] == "run-cluster":
         run_cluster(int(sys.argv[2]))
+    elif sys.argv[1] == "--hist":
+        run_all_hist(sys.argv[2])
+    elif sys.argv[1] == "--hist-table":
+        table_hist(sys.argv[2])
+    elif sys.argv[1] == "run-hist":
+        run_hist(int(sys.argv[2]))
     else:
         run(int(sys.argv[2]), int(sys.argv[3]))

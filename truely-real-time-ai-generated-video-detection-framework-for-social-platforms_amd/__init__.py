@@ -1,13 +1,14 @@
 """truely_amd -- MI355X-native implementation of Truely's per-frame visual hot path
 (server/model.py::run of the reference): MTCNN detect -> largest-face crop -> FaceNet
 (InceptionResnetV1) embedding -> consecutive-frame cosine drift -> 0..100 score -- and, for the embeddings,
-FaceGallery / pairwise / cluster_embeddings: enrolment, distance tables, top-k identification and DBSCAN clustering on the device.
+FaceGallery / pairwise / cluster_embeddings: enrolment, distance tables, top-k identification, DBSCAN clustering and score
+histograms (threshold calibration: roc_from_counts / threshold_at_far) on the device.
 
 Importable as ``truely_amd`` (see truely_amd.py at the repository root; the directory name
 required by the build contract is not a valid Python identifier)."""
 from . import weights, synthetic  # noqa: F401  (pure numpy, usable without a GPU)
 
-__all__ = ["weights", "synthetic", "Engine", "MTCNN", "InceptionResnetV1", "FaceGallery", "pairwise", "cluster_embeddings", "run", "analyze_video"]
+__all__ = ["weights", "synthetic", "Engine", "MTCNN", "InceptionResnetV1", "FaceGallery", "pairwise", "cluster_embeddings", "roc_from_counts", "threshold_at_far", "run", "analyze_video"]
 
 
 def __getattr__(name):
@@ -21,7 +22,7 @@ def __getattr__(name):
     if name == "InceptionResnetV1":
         from .inception_resnet_v1 import InceptionResnetV1
         return InceptionResnetV1
-    if name in ("FaceGallery", "pairwise", "cluster_embeddings"):
+    if name in ("FaceGallery", "pairwise", "cluster_embeddings", "roc_from_counts", "threshold_at_far"):
         from . import gallery
         return getattr(gallery, name)
     if name in ("run", "analyze_video"):

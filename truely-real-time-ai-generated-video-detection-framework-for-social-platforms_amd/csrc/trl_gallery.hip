@@ -21,10 +21,14 @@
 //
 // Clustering (f-8) is the same main loop ended in a ballot: k_gallery_links writes the packed link bitmap of n rows against
 // themselves, and the k_cluster_* kernels turn it into DBSCAN labels by rounds of hooking and pointer jumping, a launch each.
+//
+// Score histograms (f-9) end it in counters: k_gallery_hist counts the pairs per score bin (trl_gallery_bins.h), genuine and
+// impostor apart, in LDS, and k_gallery_hist_sum adds the workgroups' counters into the int64 result.
 #include <algorithm>
 #include <utility>
 
 #include "trl_common.h"
+#include "trl_gallery_bins.h"
 #include "trl_gallery_order.h"
 
 namespace {
@@ -480,12 +484,103 @@ bool cl_carve(Arena& a, int n, ClWs* w) {
     return w->a && w->b && w->cid && w->changed;
 }
 
+// ---- score histograms: pair counts per score bin, genuine and impostor ------------------------------------
+// k_gallery_hist is k_gallery_links' frame with a fourth end: every accumulator's score is put into its bin (trl_gallery_bins.h, the
+// edges in LDS, padded with +inf to 1,023) and counted by an LDS atomic in the workgroup's own counters, [2][E + 2] uint32: class 0
+// impostor (qid != gid), 1 genuine; slot E + 1 the NaN scores.  Counted: rows < n, columns < m, both valid and, with `upper`, column >
+// row.  A workgroup sees 32 rows x gps x 128 columns < 2^32 pairs (HI_MAX_GPS).  It stores its counters as they stand -- zeros
+// included -- in its own slab of `part`, and k_gallery_hist_sum adds the slabs into the int64 output: integer sums, so the counts do
+// not depend on strips, launch geometry or arrival order, and nothing has to be zeroed in front of the call.
+// With `upper` the pairs below the diagonal are not computed: a workgroup starts at the column group that holds its first row, a wave
+// whose 32 columns all lie at or below that row skips its chain, and a strip wholly below the diagonal skips the tile too.
+// LDS: 4 KB of edges, the tile, the row info and ids, 2 (E + 2) counters -- 78.6 KB at E = 1023, two workgroups per CU as k_gallery_links.
+constexpr long long HI_MAX_GPS = 1 << 19;   // column groups of a strip: 32 x 2^19 x 128 = 2^31 pairs
+constexpr int HI_SQUARE_WGS = 2048;         // workgroups wanted when n == m: strips short enough that `upper` drops half of them
+constexpr int HI_EDGE_WORDS = TRL_GL_PADDED_EDGES + 1;
+constexpr int HI_SUM_SLOTS = 64;            // output slots of one k_gallery_hist_sum workgroup
+
+__global__ __launch_bounds__(256, 2) void k_gallery_hist(const float* __restrict__ q, const uint8_t* __restrict__ qvalid,
+                                                      const int32_t* __restrict__ qid, int n, const float* __restrict__ mat, long long ld,
+                                                      const float* __restrict__ gn2, const uint8_t* __restrict__ gvalid,
+                                                      const int32_t* __restrict__ gid, long long m, int metric, int upper,
+                                                      const float* __restrict__ d_edges, int E, int tiles, long long gps,
+                                                      long long groups, uint32_t* __restrict__ part) {
+    extern __shared__ float gl_lds[];
+    float* edges = gl_lds;                                 // (in front: a search trip's read is the count plus a constant offset)
+    float* tile = gl_lds + HI_EDGE_WORDS;
+    float* info = tile + GL_TILE_WORDS;
+    const int* rowok = reinterpret_cast<const int*>(info) + 2 * GL_ROWS;
+    int* rowid = reinterpret_cast<int*>(info) + GL_INFO_WORDS;
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(info) + GL_INFO_WORDS + GL_ROWS;
+    const int slots = 2 * (E + 2);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long row0 = (long long)(blockIdx.x % (unsigned)tiles) * GL_ROWS, strip = blockIdx.x / (unsigned)tiles;
+    for (int t = tid; t < TRL_GL_PADDED_EDGES; t += 256) edges[t] = t < E ? d_edges[t] : __builtin_inff();
+    for (int t = tid; t < slots; t += 256) cnt[t] = 0u;
+    if (tid < GL_ROWS) rowid[tid] = row0 + tid < n ? qid[row0 + tid] : 0;
+    const long long g_end = (strip + 1) * gps < groups ? (strip + 1) * gps : groups;
+    long long g_begin = strip * gps;
+    if (upper && g_begin < row0 / GL_GROUP) g_begin = row0 / GL_GROUP;       // (groups in front of it end at or below row0)
+    if (g_begin < g_end) {                                                    // (the same for every thread: the barriers are met by all)
+        gl_fill_tile(tile, info, q, qvalid, n, row0, tid);
+        const int j = lane & 31, h = lane >> 5;
+        for (long long g = g_begin; g < g_end; g++) {
+            const long long c0 = g * GL_GROUP + wave * 32;
+            if (c0 >= m) break;
+            if (upper && c0 + 31 <= row0) continue;
+            const f32x16 acc = gl_chain(tile, mat, (size_t)ld, c0, lane);
+            const long long col = c0 + j;
+            const float g2 = gn2[col], gs = __builtin_sqrtf(g2);          // (col < ld: n2 has ld entries)
+            const bool colok = col < m && (!gvalid || gvalid[col] != 0);
+            const int cid = col < m ? gid[col] : 0;                       // (gid has m entries)
+            int h_here = h;                                               // (as in k_gallery_search: the 16 rows' LDS addresses are
+            asm volatile("" : "+v"(h_here));                              // made here, not kept in registers across the chain)
+            auto tally = [&](auto METRIC) __attribute__((always_inline)) {
+                constexpr int mt = decltype(METRIC)::value;
+#pragma unroll
+                for (int i = 0; i < 16; i++) {
+                    const int r = (i & 3) + 8 * (i >> 2) + 4 * h_here;
+                    const float sc = gl_score(mt, acc[i], info[r], info[GL_ROWS + r], g2, gs);
+                    const bool counted = colok && rowok[r] != 0 && (!upper || col > row0 + r);
+                    const int bin = trl_gl_bin_padded(mt, sc, edges, E, TRL_GL_MAX_STEPS);
+                    if (counted) atomicAdd(cnt + (rowid[r] == cid ? E + 2 : 0) + bin, 1u);
+                }
+            };
+            if (metric == TRL_GL_COSINE) tally(std::integral_constant<int, TRL_GL_COSINE>{});
+            else tally(std::integral_constant<int, TRL_GL_EUCLIDEAN>{});
+        }
+    }
+    __syncthreads();
+    uint32_t* out = part + (size_t)blockIdx.x * (size_t)slots;
+    for (int t = tid; t < slots; t += 256) out[t] = cnt[t];
+}
+
+// counts[s] = the sum over the workgroups' slabs of slot s.  A workgroup takes HI_SUM_SLOTS slots: lane l of each of its 16 waves
+// reads slot l of every 16th slab (256 contiguous bytes per wave), then wave 0 adds the 16 partial sums.
+__global__ __launch_bounds__(1024) void k_gallery_hist_sum(const uint32_t* __restrict__ part, long long wgs, int slots,
+                                                           long long* __restrict__ counts) {
+    __shared__ unsigned long long sum[16][HI_SUM_SLOTS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = blockIdx.x * HI_SUM_SLOTS + lane;
+    unsigned long long acc = 0;
+    if (s < slots) {
+#pragma unroll 8
+        for (long long w = wave; w < wgs; w += 16) acc += part[(size_t)w * (size_t)slots + s];
+    }
+    sum[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && s < slots) {
+        for (int k = 1; k < 16; k++) acc += sum[k][lane];
+        counts[s] = (long long)acc;
+    }
+}
+
 // ---- the search's plan and workspace, written once: trl_gallery_search_workspace is a dry run of gl_carve -------------------------
 struct GlPlan {
     long long tiles = 0, groups = 0, gps = 0, strips = 0;
 };
 
-const char* gl_plan(int n, long long m, int k, int max_strip_cols, GlPlan* p) {
+const char* gl_plan(int n, long long m, int k, int max_strip_cols, GlPlan* p, int target_wgs = GL_TARGET_WGS) {
     if (n < 0 || m < 0 || m > 0x7fffffffLL) return "n or m out of range (n >= 0, 0 <= m <= 2^31 - 1)";
     if (k < 1 || k > TRL_GL_MAX_K) return "k outside 1..16";
     if (max_strip_cols < 0 || max_strip_cols % GL_GROUP) return "max_strip_cols is not a multiple of 128";
@@ -493,7 +588,7 @@ const char* gl_plan(int n, long long m, int k, int max_strip_cols, GlPlan* p) {
     if (n == 0 || m == 0) return nullptr;
     p->tiles = (n + GL_ROWS - 1) / GL_ROWS;
     p->groups = (m + GL_GROUP - 1) / GL_GROUP;
-    long long want = std::max<long long>(1, GL_TARGET_WGS / p->tiles);
+    long long want = std::max<long long>(1, target_wgs / p->tiles);
     want = std::min<long long>(want, std::min<long long>(GL_MAX_STRIPS, p->groups));
     p->gps = (p->groups + want - 1) / want;
     if (max_strip_cols > 0) p->gps = std::min<long long>(p->gps, max_strip_cols / GL_GROUP);
@@ -524,6 +619,29 @@ const char* gl_check_gallery(const float* d_mat, long long ld, const float* d_n2
     if (ld <= 0 || ld % 32) return "ld is not a positive multiple of 32";
     if (m > ld) return "m > ld";
     return nullptr;
+}
+
+// the histogram's plan: the search's, with strips short enough for 32-bit counters; n == m (the shape of `upper`, whose workgroups
+// below the diagonal do nothing) asks for four times the workgroups, so that those left still fill the device evenly
+const char* hi_plan(int n, long long m, int nedges, int max_strip_cols, GlPlan* p) {
+    if (nedges < 1 || nedges > TRL_GL_MAX_EDGES) return "nedges outside 1..1023";
+    if (const char* why = gl_plan(n, m, 1, max_strip_cols, p, n == m ? HI_SQUARE_WGS : GL_TARGET_WGS)) return why;
+    if (p->gps > HI_MAX_GPS) {
+        p->gps = HI_MAX_GPS;
+        p->strips = (p->groups + p->gps - 1) / p->gps;
+        if (p->strips * p->tiles > 0x7fffffffLL) return "too many workgroups";
+    }
+    return nullptr;
+}
+
+// the workgroups' counters [strips * tiles][2 (nedges + 2)] uint32; none for an empty problem
+bool hi_carve(Arena& a, const GlPlan& p, int nedges, uint32_t** part) {
+    *part = nullptr;
+    if (p.strips * p.tiles > 0) {
+        *part = (uint32_t*)a.alloc((size_t)(p.strips * p.tiles) * (size_t)(2 * (nedges + 2)) * sizeof(uint32_t));
+        if (!*part) return false;
+    }
+    return true;
 }
 
 }  // namespace
@@ -689,6 +807,52 @@ extern "C" int trl_cluster_labels(const uint32_t* d_adj, long long pitch_words, 
     k_cluster_number<<<1, 1024, 0, s>>>(w.a, n, (n + 1023) / 1024, w.cid, d_count);
     TRL_LAUNCH_CHECK();
     k_cluster_assign<<<per_wave, 256, 0, s>>>(d_adj, pitch_words, d_degree, n, words, w.a, w.cid, d_labels);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
+extern "C" size_t trl_gallery_hist_workspace(int n, long long m, int nedges, int max_strip_cols) {
+    GlPlan p;
+    if (hi_plan(n, m, nedges, max_strip_cols, &p)) return 0;
+    Arena a = Arena::counter(0);
+    uint32_t* part;
+    hi_carve(a, p, nedges, &part);
+    return a.high;
+}
+
+extern "C" int trl_gallery_hist(const float* d_q, const uint8_t* d_qvalid, const int32_t* d_qid, int n, const float* d_mat, long long ld,
+                                const float* d_n2, const uint8_t* d_gvalid, const int32_t* d_gid, long long m, int metric, int pairs,
+                                const float* d_edges, int nedges, long long* d_counts, void* d_ws, size_t ws_bytes, int max_strip_cols,
+                                void* stream) {
+    GlPlan p;
+    if (const char* why = hi_plan(n, m, nedges, max_strip_cols, &p)) { trl_set_error("trl_gallery_hist: %s", why); return TRL_ERR_INVALID; }
+    if (metric != TRL_GL_COSINE && metric != TRL_GL_EUCLIDEAN) { trl_set_error("trl_gallery_hist: metric %d (0 cosine, 1 euclidean)", metric); return TRL_ERR_INVALID; }
+    if (pairs != TRL_GL_PAIRS_ALL && pairs != TRL_GL_PAIRS_UPPER) { trl_set_error("trl_gallery_hist: pairs %d (0 all, 1 upper)", pairs); return TRL_ERR_INVALID; }
+    if (pairs == TRL_GL_PAIRS_UPPER && n != m) { trl_set_error("trl_gallery_hist: upper pairs need n == m, not %d and %lld", n, m); return TRL_ERR_INVALID; }
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) { trl_set_error("trl_gallery_hist: %s", why); return TRL_ERR_INVALID; }
+    if (!d_edges || !d_counts || (n > 0 && (!d_q || !d_qid)) || (m > 0 && !d_gid)) { trl_set_error("trl_gallery_hist: null argument"); return TRL_ERR_INVALID; }
+    Arena a;
+    a.base = (char*)d_ws;
+    a.cap = d_ws ? ws_bytes : 0;
+    uint32_t* part;
+    if (((uintptr_t)d_ws & 7) || !hi_carve(a, p, nedges, &part)) {
+        trl_set_error("trl_gallery_hist: workspace of %zu bytes (need %zu, 8-byte aligned)", ws_bytes, trl_gallery_hist_workspace(n, m, nedges, max_strip_cols));
+        return TRL_ERR_INVALID;
+    }
+    TRL_CHECK(gl_device_of(d_mat));
+    hipStream_t s = (hipStream_t)stream;
+    const int slots = 2 * (nedges + 2);
+    if (n == 0 || m == 0) {
+        TRL_HIP(hipMemsetAsync(d_counts, 0, (size_t)slots * sizeof(long long), s));
+        return TRL_OK;
+    }
+    const int lds = (HI_EDGE_WORDS + GL_TILE_WORDS + GL_INFO_WORDS + GL_ROWS + slots) * 4;
+    TRL_HIP(hipFuncSetAttribute((const void*)k_gallery_hist, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    const long long wgs = p.strips * p.tiles;
+    k_gallery_hist<<<(unsigned)wgs, 256, lds, s>>>(d_q, d_qvalid, d_qid, n, d_mat, ld, d_n2, d_gvalid, d_gid, m, metric, pairs, d_edges, nedges,
+                                                  (int)p.tiles, p.gps, p.groups, part);
+    TRL_LAUNCH_CHECK();
+    k_gallery_hist_sum<<<(unsigned)((slots + HI_SUM_SLOTS - 1) / HI_SUM_SLOTS), 1024, 0, s>>>(part, wgs, slots, d_counts);
     TRL_LAUNCH_CHECK();
     return TRL_OK;
 }

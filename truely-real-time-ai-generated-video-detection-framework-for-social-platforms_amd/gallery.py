@@ -15,7 +15,10 @@ product, then
 
 and matches are ordered better score first, equal scores to the lower gallery index, NaN last.  ``cluster`` /
 ``cluster_embeddings`` answer the question that needs no enrolled identities -- "which of these faces are the same person?" --
-with DBSCAN over the same scores, from a link bitmap instead of the score matrix.  Embeddings never visit the host."""
+with DBSCAN over the same scores, from a link bitmap instead of the score matrix.  ``score_histogram`` / ``roc`` / ``calibrate`` find
+the threshold both take: exact counts of same-label and different-label pairs per score bin, again without the score matrix, and
+from them the accept rates at every candidate threshold (``roc_from_counts``, ``threshold_at_far``).  Embeddings never visit the
+host."""
 from __future__ import annotations
 
 import ctypes as C
@@ -28,6 +31,7 @@ from . import _lib
 METRICS = {"cosine": 0, "euclidean": 1}
 MAX_K = 16
 MAX_CLUSTER_ROWS = 65536
+MAX_EDGES = 1023
 DIM = 512
 
 
@@ -183,6 +187,67 @@ class FaceGallery:
             return labels
         return {"labels": labels, "core": core, "degree": degree, "n_clusters": int(count.item()), "rounds": rounds.value}
 
+    def score_histogram(self, emb=None, labels=None, edges=None, valid=None, gallery_valid=None, max_strip_cols: int = 0) -> dict:
+        """Exact pair counts per score bin, same-label ("genuine") and different-label ("impostor") pairs apart: what a
+        threshold for ``identify`` / ``cluster`` is read from.  The gallery is streamed once; no score matrix is written.
+
+        ``emb`` (n, 512) with its n ``labels`` is compared against every enrolled row.  With ``emb=None`` the gallery is compared
+        against itself and each unordered pair (i < j) is counted once.  Labels are equal by ``==`` / hash.  ``edges``: E
+        candidate thresholds, 1 <= E <= 1023, strictly ascending, no NaN (default: 1,001 steps over -1..1 for cosine, over 0..2
+        for euclidean).  A score's bin is the number of edges <= it (cosine) or < it (euclidean), so the pairs that cosine
+        ``score >= edges[e]`` accepts are bins e + 1 .. E, and those that euclidean ``score <= edges[e]`` accepts bins 0 .. e:
+        exactly, in float32.  ``valid`` masks the query rows and ``gallery_valid`` the enrolled rows (with ``emb=None`` they are the
+        same rows: give either one).
+
+        Returns ``edges`` (E,) float32, ``genuine`` and ``impostor`` (E + 1,) int64, and ``nan`` (2,) int64 -- the pairs whose
+        score is NaN, impostor then genuine -- all on the device."""
+        m = self._m
+        ids: dict = {}
+        gid = [ids.setdefault(l, len(ids)) for l in self._labels]
+        if emb is None:
+            if labels is not None:
+                raise ValueError("labels belong to emb; the gallery's rows carry their own")
+            if valid is not None and gallery_valid is not None:
+                raise ValueError("with emb=None the query rows are the gallery's: give valid or gallery_valid, not both")
+            q, n, qid, pairs = (self.rows() if m else None), m, gid, 1
+            qv = gv = _valid(valid if gallery_valid is None else gallery_valid, m, self.device)
+        else:
+            q = _rows(emb, self.device)
+            n, pairs = q.shape[0], 0
+            if labels is None:
+                raise ValueError("emb needs its labels")
+            labels = list(labels)
+            if len(labels) != n:
+                raise ValueError(f"{n} embeddings but {len(labels)} labels")
+            qid = [ids.setdefault(l, len(ids)) for l in labels]
+            qv, gv = _valid(valid, n, self.device), _valid(gallery_valid, m, self.device)
+        edges = _edges(edges, self._metric, self.device)
+        E = edges.shape[0]
+        qid_t = torch.tensor(qid, dtype=torch.int32, device=self.device)
+        gid_t = qid_t if emb is None else torch.tensor(gid, dtype=torch.int32, device=self.device)
+        counts = torch.empty((2, E + 2), dtype=torch.int64, device=self.device)
+        need = self.lib.trl_gallery_hist_workspace(n, m, E, max_strip_cols)
+        ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
+        _lib.check(self.lib.trl_gallery_hist(_ptr(q), _ptr(qv), _ptr(qid_t), n, _ptr(self._mat), self.ld, _ptr(self._n2), _ptr(gv),
+                                             _ptr(gid_t), m, self._metric, pairs, _ptr(edges), E, _ptr(counts), _ptr(ws), need,
+                                             max_strip_cols, _stream(self.device)))
+        return {"edges": edges, "genuine": counts[1, :E + 1], "impostor": counts[0, :E + 1], "nan": counts[:, E + 1]}
+
+    def roc(self, emb=None, labels=None, edges=None, valid=None, gallery_valid=None, max_strip_cols: int = 0) -> dict:
+        """``score_histogram`` turned into rates: ``edges`` (E,) float32, ``tar`` and ``far`` (E,) float64, host arrays --
+        the share of genuine / impostor pairs that each edge, used as the threshold, accepts (``roc_from_counts``)."""
+        h = self.score_histogram(emb, labels, edges, valid, gallery_valid, max_strip_cols)
+        tar, far = roc_from_counts(h["genuine"], h["impostor"], h["nan"], self.metric)
+        return {"edges": h["edges"].cpu().numpy(), "tar": tar, "far": far}
+
+    def calibrate(self, far: float = 1e-3, emb=None, labels=None, edges=None, valid=None, gallery_valid=None,
+                  max_strip_cols: int = 0) -> dict:
+        """The loosest of ``edges`` whose false accept rate is at most ``far``: ``{"threshold", "tar", "far"}`` (floats; the rates
+        are those measured at the threshold).  ``ValueError`` when no edge qualifies (``threshold_at_far``)."""
+        r = self.roc(emb, labels, edges, valid, gallery_valid, max_strip_cols)
+        thr, t, f = threshold_at_far(r["edges"], r["tar"], r["far"], far, self.metric)
+        return {"threshold": thr, "tar": t, "far": f}
+
 
 def _valid(valid, n: int, device):
     """None, or the mask as (n,) uint8 on `device`."""
@@ -194,6 +259,55 @@ def _valid(valid, n: int, device):
     if valid.shape != (n,):
         raise ValueError(f"valid must have shape ({n},)")
     return valid
+
+
+def _edges(edges, metric: int, device) -> torch.Tensor:
+    """The candidate thresholds as (E,) float32 on `device`, checked: 1..MAX_EDGES of them, strictly ascending, no NaN."""
+    if edges is None:
+        edges = np.linspace(-1.0, 1.0, 1001) if metric == 0 else np.linspace(0.0, 2.0, 1001)
+    if isinstance(edges, torch.Tensor):
+        edges = edges.detach().cpu().numpy()
+    e = np.array(edges, np.float32).reshape(-1)
+    if not 1 <= len(e) <= MAX_EDGES:
+        raise ValueError(f"edges must hold 1..{MAX_EDGES} values, not {len(e)}")
+    if np.isnan(e).any() or not (e[1:] > e[:-1]).all():
+        raise ValueError("edges must be strictly ascending float32 values without NaN")
+    return torch.from_numpy(e).to(device)
+
+
+def _host(x, dtype) -> np.ndarray:
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype)
+
+
+def roc_from_counts(genuine, impostor, nan, metric: str = "cosine"):
+    """(tar, far), float64 arrays of length E, from ``score_histogram``'s counts (numpy arrays or tensors): the share of the
+    genuine / impostor pairs that threshold ``edges[e]`` accepts -- cosine ``score >= edges[e]`` (bins e + 1 .. E), euclidean
+    ``score <= edges[e]`` (bins 0 .. e).  Integer cumulative sums, then one division by the class total; that total includes the
+    class's NaN scores (``nan``: impostor, genuine), which no threshold accepts.  A class without pairs gives NaN."""
+    cosine = _metric(metric) == 0
+    nan = _host(nan, np.int64)
+    out = []
+    for counts, lost in ((genuine, nan[1]), (impostor, nan[0])):
+        c = _host(counts, np.int64)
+        accepted = np.cumsum(c[::-1])[::-1][1:] if cosine else np.cumsum(c)[:-1]
+        total = int(c.sum()) + int(lost)
+        out.append(accepted / np.float64(total) if total else np.full(len(c) - 1, np.nan))
+    return out[0], out[1]
+
+
+def threshold_at_far(edges, tar, far, target: float, metric: str = "cosine"):
+    """(threshold, tar, far): the loosest edge whose false accept rate is at most ``target`` -- the smallest such edge for cosine,
+    the largest for euclidean -- with the rates at it.  ``ValueError`` when no edge qualifies (a NaN rate never does)."""
+    cosine = _metric(metric) == 0
+    edges, tar, far = _host(edges, np.float32), _host(tar, np.float64), _host(far, np.float64)
+    with np.errstate(invalid="ignore"):
+        ok = np.nonzero(far <= target)[0]
+    if not len(ok):
+        raise ValueError(f"no edge has a false accept rate <= {target}")
+    e = int(ok.min() if cosine else ok.max())
+    return float(edges[e]), float(tar[e]), float(far[e])
 
 
 def cluster_embeddings(emb, threshold: float, metric: str = "cosine", min_samples: int = 1, valid=None, device=None,

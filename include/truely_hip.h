@@ -611,6 +611,41 @@ int    trl_gallery_hist(const float* d_q, const uint8_t* d_qvalid, const int32_t
                         const float* d_edges, int nedges, long long* d_counts, void* d_ws, size_t ws_bytes, int max_strip_cols,
                         void* stream);
 
+/* ---- Range search ("every enrolled row within the threshold") ------------------------------------------------------------------
+ * All matches of n query rows among the m gallery rows as CSR lists, without the n x m score matrix and without a buffer of n x m
+ * bits: the gallery is streamed twice, once to count and once to store.  Context-free, caller-owned memory, work queued on
+ * `stream`, no synchronisation, the device that of d_mat.  (ABI v7, additive)
+ *   score    the gallery's (above).
+ *   match    match(r, c) <=> d_qvalid[r] != 0 and d_gvalid[c] != 0 and (self == 0 or c != r) and
+ *            (cosine: score >= threshold | euclidean: score <= threshold), plain f32 comparisons: a NaN score never matches,
+ *            -0 == +0, +-inf scores compare as floats do.  Either mask may be null: all rows valid.
+ *   self     1: n == m and d_q are THE SAME rows as the gallery's (the caller guarantees it, as for trl_cluster_links); a row does
+ *            not match itself.  The lists are then the rows of trl_cluster_links' bitmap at the same threshold.
+ *   result   d_offsets [n + 1] int64: offsets[0] = 0, offsets[r + 1] - offsets[r] = the matches of row r, offsets[n] the total.
+ *            d_index [total] int32: row r's matching gallery rows in ASCENDING GALLERY INDEX at offsets[r] ..;
+ *            d_score [total] f32: their scores, the bits trl_gallery_scores writes.
+ * The result depends on the scores and the rule alone: not on n, strips, max_strip_cols, the stream or launch geometry.
+ * TRL_ERR_INVALID with nothing queued and nothing written: negative sizes, m > 2^31 - 1, ld out of range or m > ld, a metric or
+ * self other than 0 / 1, self = 1 with n != m, a threshold that is NaN or infinite, max_strip_cols no multiple of 128, a workspace
+ * too small or not 8-byte aligned, capacity < 0, a null pointer where one is needed (d_q may be null when m = 0, d_index and
+ * d_score when capacity = 0, everything but the gallery when n = 0). */
+/* Device bytes of d_ws: one uint32 per (strip, wave, row), 4 waves -- pass 1's counts, turned in place into the bases of pass 2.
+ * The strip count is trl_gallery_search's, so the size does not grow with m unless max_strip_cols forces shorter strips.  0 on bad
+ * arguments, and when n = 0 or m = 0. */
+size_t trl_gallery_range_workspace(int n, long long m, int max_strip_cols);
+/* Pass 1: streams the gallery once, writes d_offsets[0 .. n] and leaves pass 2's bases in d_ws.  No atomic on global memory.
+ * n = 0: nothing is done; m = 0: the offsets are all zero. */
+int    trl_gallery_range_count(const float* d_q, const uint8_t* d_qvalid, int n, const float* d_mat, long long ld, const float* d_n2,
+                               const uint8_t* d_gvalid, long long m, int metric, float threshold, int self, long long* d_offsets,
+                               void* d_ws, size_t ws_bytes, int max_strip_cols, void* stream);
+/* Pass 2: streams the gallery again and writes entry p of d_index / d_score iff p < capacity; entries at p >= capacity, and
+ * everything else, are not written (trl_jpeg_encode's capacity convention: the caller reads offsets[n] and sizes or refuses).
+ * Valid only behind a trl_gallery_range_count with the same arguments, d_offsets and d_ws, in stream order. */
+int    trl_gallery_range_fill(const float* d_q, const uint8_t* d_qvalid, int n, const float* d_mat, long long ld, const float* d_n2,
+                              const uint8_t* d_gvalid, long long m, int metric, float threshold, int self, const long long* d_offsets,
+                              const void* d_ws, size_t ws_bytes, long long capacity, int32_t* d_index, float* d_score,
+                              int max_strip_cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

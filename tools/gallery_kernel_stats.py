@@ -28,7 +28,19 @@ Histogram mode (FaceGallery.score_histogram: trl_gallery_hist), the same embeddi
 Per n one process under the same trace, 3 + 5 calls of each phase in turn: score_histogram(rows, labels) (ALL pairs) followed by
 score_histogram() (UPPER: each unordered pair once); cluster() and scores() as above -- k_gallery_links and k_gallery_scores of the
 same run are the yardsticks; and, where the matrix fits (n <= 8192), what a user would otherwise write: scores() + torch.bucketize
-+ torch.bincount (every kernel the three launch, k_gallery_scores included), whose counts must equal the histogram's."""
++ torch.bincount (every kernel the three launch, k_gallery_scores included), whose counts must equal the histogram's.
+
+Range mode (FaceGallery.range_search: trl_gallery_range_count + trl_gallery_range_fill), the same embeddings:
+
+    python tools/gallery_kernel_stats.py --range out_dir > profiles/range_kernel_stats.csv
+    python tools/gallery_kernel_stats.py --range-table out_dir
+
+Per shape one process under the same trace -- n = m in self mode (range_search(), the gallery against itself) and 256 of the rows as
+queries against 1,000,000 -- and in it 3 + 5 rounds, each round every phase once: range_search at cosine 0.5 (about 15 hits a row),
+at the smallest shape also at -2 (every pair), cluster() where n = m (k_gallery_links, the same main loop as pass 1) and scores()
+where the matrix is at most 2 GiB.  Then, where n <= 8192, what a user would otherwise write: scores() + a comparison + torch.nonzero
+(every kernel they launch), whose lists must equal the range search's.  A row of the table is one kernel of one phase: the median
+over the 5 measured rounds, the smallest and the largest."""
 import csv
 import glob
 import json
@@ -264,6 +276,107 @@ def run_all_hist(out):
     table_hist(out)
 
 
+RG_SHAPES = ((4_096, 4_096), (16_384, 16_384), (65_536, 65_536), (256, 1_000_000))
+RG_THR, RG_ALL_THR, RG_DENSE_N, RG_SCORES_MAX_BYTES = 0.5, -2.0, 4_096, 2 << 30
+RG_KERNELS = ("k_gallery_range_count", "k_range_rows", "k_range_scan", "k_gallery_range_fill")
+
+
+def run_range(n, m):
+    import torch
+    from truely_amd.gallery import FaceGallery
+    gen = torch.Generator(device="cuda").manual_seed(m)
+    centres = torch.nn.functional.normalize(torch.randn((m // CL_PER_ID, 512), generator=gen, device="cuda"), dim=1)
+    rows = centres.repeat_interleave(CL_PER_ID, dim=0) + 0.03 * torch.randn((m, 512), generator=gen, device="cuda")
+    rows = torch.nn.functional.normalize(rows, dim=1)[torch.randperm(m, generator=gen, device="cuda")]
+    gal = FaceGallery(metric="cosine", capacity=m)
+    gal.add(rows, range(m))
+    self_mode = n == m
+    q = None if self_mode else rows[:n].contiguous()
+    torch.cuda.synchronize()
+    dense = None
+    for _ in range(CL_WARMUP + CL_WARM):
+        off, idx, sc = gal.range_search(q, threshold=RG_THR)
+        if self_mode and n == RG_DENSE_N:
+            dense = gal.range_search(q, threshold=RG_ALL_THR)
+        if self_mode:
+            gal.cluster(RG_THR, min_samples=4)
+        if n * m * 4 <= RG_SCORES_MAX_BYTES:
+            gal.scores(rows if self_mode else q)
+    torch.cuda.synchronize()                                  # (not per round: a kernel that starts on a drained queue runs longer)
+    same = None
+    if self_mode and n <= HI_TORCH_MAX_N:
+        for _ in range(CL_WARMUP + CL_WARM):
+            s = gal.scores(rows)
+            hit = s >= RG_THR
+            hit.fill_diagonal_(False)
+            rc = torch.nonzero(hit)
+        torch.cuda.synchronize()
+        counts = torch.bincount(rc[:, 0], minlength=n)
+        same = bool(torch.equal(rc[:, 1].to(torch.int32), idx) and torch.equal(counts, off[1:] - off[:-1]) and torch.equal(s[hit], sc))
+    print(json.dumps({"n": n, "m": m, "self": self_mode, "hits": int(off[-1]), "hits_dense": None if dense is None else int(dense[0][-1]),
+                      "longest_row": int((off[1:] - off[:-1]).max()), "torch_lists_equal": same,
+                      "workspace_bytes": int(gal.lib.trl_gallery_range_workspace(n, m, 0))}))
+
+
+def table_range(out):
+    print("n,m,metric,threshold,what,launches_per_call,median_us_per_call,min_us_per_call,max_us_per_call,tflops,over_links,over_scores,hits,"
+          "workspace_bytes,torch_lists_equal")
+    calls = CL_WARMUP + CL_WARM
+    for n, m in RG_SHAPES:
+        d = os.path.join(out, f"range_{n}_{m}")
+        if not os.path.exists(os.path.join(d, "info.json")):
+            continue
+        info = json.load(open(os.path.join(d, "info.json")))
+        tr = _trace(d)
+        phases = [(RG_THR, info["hits"])] + ([(RG_ALL_THR, info["hits_dense"])] if info["hits_dense"] is not None else [])
+        per_call = {}                                         # (threshold, what) -> (hits, [us per call], warm-up included)
+        for k in RG_KERNELS:
+            times = [e - s for s, e, name in tr if k in name]
+            assert len(times) == len(phases) * calls, (n, m, k, len(times))
+            for p, (thr, hits) in enumerate(phases):          # the phases alternate within a round
+                per_call[(thr, k)] = (hits, [t / 1e3 for t in times[p::len(phases)]])
+        for thr, hits in phases:
+            per_call[(thr, "range_search (all four)")] = (hits, [sum(per_call[(thr, k)][1][c] for k in RG_KERNELS) for c in range(calls)])
+        links = [(e - s) / 1e3 for s, e, name in tr if "k_gallery_links" in name]
+        at = [i for i, r in enumerate(tr) if "k_gallery_scores" in r[2]]
+        if links:
+            assert len(links) == calls, (n, m, len(links))
+            per_call[("", "k_gallery_links")] = ("", links)
+        if info["torch_lists_equal"] is not None:             # the last `calls` k_gallery_scores launches open a torch-route call each
+            assert len(at) == 2 * calls, (n, m, len(at))
+            per = at[calls + 1] - at[calls]
+            per_call[(RG_THR, "scores + compare + nonzero")] = (info["hits"], [sum(e - s for s, e, _n in tr[a:a + per]) / 1e3 for a in at[calls:]])
+            at = at[:calls]
+        if at:
+            assert len(at) == calls, (n, m, len(at))
+            per_call[("", "k_gallery_scores")] = ("", [(tr[i][1] - tr[i][0]) / 1e3 for i in at])
+        med = {k: statistics.median(v[CL_WARMUP:]) for k, (_h, v) in per_call.items()}
+        for (thr, what), (hits, v) in per_call.items():
+            v = v[CL_WARMUP:]
+            mk = med[(thr, what)]
+            flop = 2.0 * n * m * 512 if what in ("k_gallery_range_count", "k_gallery_range_fill", "k_gallery_links", "k_gallery_scores") else None
+            tf = f"{flop / mk / 1e6:.1f}" if flop else ""
+            ol = f"{mk / med[('', 'k_gallery_links')]:.3f}" if ("", "k_gallery_links") in med else ""
+            osc = f"{mk / med[('', 'k_gallery_scores')]:.3f}" if ("", "k_gallery_scores") in med else ""
+            launches = 4 if what.startswith("range_search") else "" if what.startswith("scores +") else 1
+            print(f"{n},{m},cosine,{thr},{what},{launches},{mk:.1f},{min(v):.1f},{max(v):.1f},{tf},{ol},{osc},{hits},{info['workspace_bytes']},"
+                  f"{info['torch_lists_equal']}")
+
+
+def run_all_range(out):
+    for n, m in RG_SHAPES:
+        d = os.path.join(out, f"range_{n}_{m}")
+        os.makedirs(d, exist_ok=True)
+        r = subprocess.run(["rocprofv3", "--kernel-trace", "-d", d, "-o", "t", "-f", "csv", "--", sys.executable, os.path.abspath(__file__),
+                            "run-range", str(n), str(m)], capture_output=True, text=True, timeout=300)
+        if r.returncode != 0:
+            sys.exit(f"range shape {n} x {m} failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+        print(line, file=sys.stderr, flush=True)
+        open(os.path.join(d, "info.json"), "w").write(line)
+    table_range(out)
+
+
 def run_all(out):
     for m in M_SHAPES:
         for n in N_SHAPES:
@@ -296,5 +409,11 @@ if __name__ == "__main__":
         table_hist(sys.argv[2])
     elif sys.argv[1] == "run-hist":
         run_hist(int(sys.argv[2]))
+    elif sys.argv[1] == "--range":
+        run_all_range(sys.argv[2])
+    elif sys.argv[1] == "--range-table":
+        table_range(sys.argv[2])
+    elif sys.argv[1] == "run-range":
+        run_range(int(sys.argv[2]), int(sys.argv[3]))
     else:
         run(int(sys.argv[2]), int(sys.argv[3]))

@@ -123,6 +123,10 @@ _SIGNATURES = {
     "trl_cluster_labels": (C.c_int, [_vp, C.c_longlong, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(_i), _vp]),
     "trl_gallery_hist_workspace": (C.c_size_t, [_i, C.c_longlong, _i, _i]),
     "trl_gallery_hist": (C.c_int, [_vp, _vp, _vp, _i, _vp, C.c_longlong, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp, _i, _vp, _vp, C.c_size_t, _i, _vp]),
+    "trl_gallery_range_workspace": (C.c_size_t, [_i, C.c_longlong, _i]),
+    "trl_gallery_range_count": (C.c_int, [_vp, _vp, _i, _vp, C.c_longlong, _vp, _vp, C.c_longlong, _i, _f, _i, _vp, _vp, C.c_size_t, _i, _vp]),
+    "trl_gallery_range_fill": (C.c_int, [_vp, _vp, _i, _vp, C.c_longlong, _vp, _vp, C.c_longlong, _i, _f, _i, _vp, _vp, C.c_size_t, C.c_longlong,
+                                         _vp, _vp, _i, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

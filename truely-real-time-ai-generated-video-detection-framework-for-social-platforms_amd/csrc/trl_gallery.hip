@@ -24,6 +24,9 @@
 //
 // Score histograms (f-9) end it in counters: k_gallery_hist counts the pairs per score bin (trl_gallery_bins.h), genuine and
 // impostor apart, in LDS, and k_gallery_hist_sum adds the workgroups' counters into the int64 result.
+//
+// The range search (f-10) ends it in popcounts and ranked stores: k_gallery_range_count counts each row's matches per (strip, wave),
+// k_range_rows / k_range_scan turn the counts into bases and int64 offsets, k_gallery_range_fill stores the CSR lists.
 #include <algorithm>
 #include <utility>
 
@@ -575,6 +578,160 @@ __global__ __launch_bounds__(1024) void k_gallery_hist_sum(const uint32_t* __res
     }
 }
 
+// ---- range search: every match within a threshold, as CSR lists ----------------------------------------
+// Two passes over the gallery in k_gallery_links' frame, both through rg_walk: the first ends the ballot of the match predicate in
+// popcounts per row, the second in ranked stores.  A workgroup takes a strip of gps column groups = 4 gps slabs of 32 columns, and
+// wave w walks slabs w gps .. (w + 1) gps - 1 of them -- a contiguous quarter, not every fourth slab as in the kernels above -- so
+// (strip, wave, column) ascending is the gallery index ascending and a row's place in its list is wave-private: the loop over slabs
+// holds no barrier, as k_gallery_search's.  Pass 1 leaves one uint32 count per (strip, wave, row); k_range_rows turns each row's
+// counts into exclusive bases in place and writes the row's total, k_range_scan turns the totals into the int64 offsets; pass 2
+// starts row r of (strip, wave) at offsets[r] + base and stores hit number p of the whole result iff p < capacity.  No atomics: every
+// count, offset and entry is written once, by one lane, with a vector store.  Both passes recompute the scores -- one chain per
+// output, so the same bits -- and share the predicate, the masks and the C/D decode: all of it is rg_walk.
+constexpr int RG_WAVES = 4;
+
+struct RgArgs {
+    const float* q;
+    const uint8_t* qvalid;
+    int n;
+    const float* mat;
+    long long ld;
+    const float* gn2;
+    const uint8_t* gvalid;
+    long long m;
+    int metric;
+    float thr;
+    int self;
+    int tiles;
+    long long gps;
+};
+
+// match(r, c) of the header, but for the masks: plain f32 comparisons, false for a NaN score
+__device__ __forceinline__ bool rg_match(int metric, float sc, float thr) { return metric == TRL_GL_COSINE ? sc >= thr : sc <= thr; }
+
+// lane l's value of a position (l the same for the whole wave)
+__device__ __forceinline__ long long rg_lane_value(long long v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), l);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// One wave's walk over its quarter of a strip.  `run` is per lane: lanes j and j + 32 both carry row j's position -- the matches of
+// row row0 + j in front of the slab at hand, counted from the caller's start value.  Accumulator i holds row r = (i & 3) + 8 (i >> 2)
+// + 4 (lane >> 5) at column lane & 31, so the ballot of the predicate is two rows' hit masks, the low half row r_lo's, the high
+// half row r_lo + 4's.  With EMIT a hitting lane calls emit(position, column, score), position = its row's run + the hits of its
+// half below its own lane; then (in both passes) the two rows' runs advance by the halves' popcounts.  Returns the final run.
+template <bool EMIT, typename Pos, typename Emit>
+__device__ __forceinline__ Pos rg_walk(const RgArgs& a, const float* tile, const float* info, long long row0, long long strip, int wave,
+                                       int lane, Pos run, Emit&& emit) {
+    const int* rowok = reinterpret_cast<const int*>(info) + 2 * GL_ROWS;
+    const int j = lane & 31, h = lane >> 5;
+    long long c0 = (strip * RG_WAVES + wave) * a.gps * 32;                  // the quarter's first column
+    const long long ahead = a.m - c0 + 31;                                  // (slabs that begin in front of m: ahead / 32 of them)
+    const int slabs = ahead < 32 ? 0 : ahead / 32 < a.gps ? (int)(ahead / 32) : (int)a.gps;
+    for (int s = 0; s < slabs; s++, c0 += 32) {
+        const f32x16 acc = gl_chain(tile, a.mat, (size_t)a.ld, c0, lane);   // (c0 + 31 < ld: c0 < m <= ld, both multiples of 32)
+        const long long col = c0 + j;
+        const float g2 = a.gn2[col], gs = __builtin_sqrtf(g2);              // (col < ld: n2 has ld entries)
+        const bool colok = col < a.m && (!a.gvalid || a.gvalid[col] != 0);
+        const int own = a.self ? (int)(col - row0) : -1;                    // the tile row that IS this column, if it is one of the 32
+        int h_here = h;                                                     // (as in k_gallery_search: the 16 rows' LDS addresses are
+        asm volatile("" : "+v"(h_here));                                    // made here, not kept in registers across the chain)
+        const uint32_t below = (1u << j) - 1u;
+        // lane j (row j) takes accumulator mine's ballot, the high half when bit 2 of j is set.  Both are made here, per slab: as
+        // loop invariants the 32 lane masks "j == r_lo", "j == r_lo + 4" would be hoisted into 64 SGPRs, spilled to VGPR lanes
+        // and read back for every accumulator of every slab
+        int mine = (j & 3) | ((j >> 3) << 2), upper = j & 4;
+        asm volatile("" : "+v"(mine), "+v"(upper));
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int r_lo = (i & 3) + 8 * (i >> 2), r = r_lo + 4 * h_here;
+            const float sc = gl_score(a.metric, acc[i], info[r], info[GL_ROWS + r], g2, gs);
+            const bool hit = rg_match(a.metric, sc, a.thr) && colok && rowok[r] != 0 && r != own;
+            const unsigned long long b = __ballot(hit);
+            const uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32);
+            if (b != 0) {                                                   // (the same for the whole wave; rarely true at a useful threshold)
+                if constexpr (EMIT) {
+                    const Pos at_lo = rg_lane_value(run, r_lo), at_hi = rg_lane_value(run, r_lo + 4);
+                    if (hit) emit((h_here ? at_hi : at_lo) + (Pos)__popc((h_here ? hi : lo) & below), col, sc);
+                }
+                run += (Pos)(mine == i ? __popc(upper ? hi : lo) : 0);
+            }
+        }
+    }
+    return run;
+}
+
+// grid: x = strip * tiles + tile.  cnt [strips][4][n] uint32: every entry with row < n is written, a wave without slabs writes 0.
+__global__ __launch_bounds__(256, 2) void k_gallery_range_count(RgArgs a, uint32_t* __restrict__ cnt) {
+    extern __shared__ float gl_lds[];
+    float* tile = gl_lds;
+    float* info = gl_lds + GL_TILE_WORDS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long row0 = (long long)(blockIdx.x % (unsigned)a.tiles) * GL_ROWS, strip = blockIdx.x / (unsigned)a.tiles;
+    const int live = gl_fill_tile(tile, info, a.q, a.qvalid, a.n, row0, tid);
+    const uint32_t run = rg_walk<false, uint32_t>(a, tile, info, row0, strip, wave, lane, 0u, [](uint32_t, long long, float) {});
+    if (lane < live) cnt[(size_t)(strip * RG_WAVES + wave) * (size_t)a.n + (size_t)(row0 + lane)] = run;
+}
+
+// one thread per row: the row's counts over (strip, wave) ascending -> exclusive bases, in place; its total -> offsets[row + 1]
+__global__ __launch_bounds__(256) void k_range_rows(uint32_t* __restrict__ cnt, int n, long long parts, long long* __restrict__ offsets) {
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    uint32_t run = 0;
+    for (long long p = 0; p < parts; p++) {
+        uint32_t* c = cnt + (size_t)p * (size_t)n + (size_t)row;
+        const uint32_t v = *c;
+        *c = run;
+        run += v;
+    }
+    offsets[row + 1] = run;
+}
+
+// one workgroup: offsets[1 .. n] hold the rows' totals -> offsets[0 .. n], their exclusive sums (offsets[n] the grand total).  Thread t
+// owns rows t * per .. + per - 1, as k_cluster_number; the 1,024 partial sums are scanned in LDS.
+__global__ __launch_bounds__(1024) void k_range_scan(long long* __restrict__ offsets, int n, long long per) {
+    __shared__ long long part[1024];
+    const int t = threadIdx.x;
+    const long long lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+    long long c = 0;
+    for (long long i = lo; i < hi; i++) c += offsets[i + 1];
+    part[t] = c;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const long long add = t >= off ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    long long run = part[t] - c;
+    for (long long i = lo; i < hi; i++) {
+        run += offsets[i + 1];
+        offsets[i + 1] = run;
+    }
+    if (t == 0) offsets[0] = 0;
+}
+
+// grid as pass 1.  base = pass 1's counts after k_range_rows.  Entry p of the result is written iff 0 <= p < capacity.
+__global__ __launch_bounds__(256, 2) void k_gallery_range_fill(RgArgs a, const long long* __restrict__ offsets, const uint32_t* __restrict__ base,
+                                                            long long capacity, int32_t* __restrict__ d_index, float* __restrict__ d_score) {
+    extern __shared__ float gl_lds[];
+    float* tile = gl_lds;
+    float* info = gl_lds + GL_TILE_WORDS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long row0 = (long long)(blockIdx.x % (unsigned)a.tiles) * GL_ROWS, strip = blockIdx.x / (unsigned)a.tiles;
+    const int live = gl_fill_tile(tile, info, a.q, a.qvalid, a.n, row0, tid);
+    const int j = lane & 31;
+    long long start = 0;
+    if (j < live) start = offsets[row0 + j] + (long long)base[(size_t)(strip * RG_WAVES + wave) * (size_t)a.n + (size_t)(row0 + j)];
+    rg_walk<true, long long>(a, tile, info, row0, strip, wave, lane, start, [&](long long p, long long col, float sc) {
+        if ((unsigned long long)p < (unsigned long long)capacity) {
+            d_index[p] = (int32_t)col;
+            d_score[p] = sc;
+        }
+    });
+}
+
 // ---- the search's plan and workspace, written once: trl_gallery_search_workspace is a dry run of gl_carve -------------------------
 struct GlPlan {
     long long tiles = 0, groups = 0, gps = 0, strips = 0;
@@ -644,7 +801,117 @@ bool hi_carve(Arena& a, const GlPlan& p, int nedges, uint32_t** part) {
     return true;
 }
 
+// the range search's counts [strips][4][n] uint32 (pass 1's counts, then pass 2's bases); none for an empty problem.  The plan is the
+// search's, so at the default plan strips x n stays near GL_TARGET_WGS x 32 whatever m is.
+bool rg_carve(Arena& a, const GlPlan& p, int n, uint32_t** cnt) {
+    *cnt = nullptr;
+    if (p.strips * p.tiles > 0) {
+        *cnt = (uint32_t*)a.alloc((size_t)p.strips * RG_WAVES * (size_t)n * sizeof(uint32_t));
+        if (!*cnt) return false;
+    }
+    return true;
+}
+
+// what both passes refuse, in one place; null when the arguments are fine
+const char* rg_check(int n, const float* d_mat, long long ld, const float* d_n2, long long m, int metric, float threshold, int self,
+                     int max_strip_cols, GlPlan* p) {
+    if (const char* why = gl_plan(n, m, 1, max_strip_cols, p)) return why;
+    if (metric != TRL_GL_COSINE && metric != TRL_GL_EUCLIDEAN) return "the metric is neither 0 (cosine) nor 1 (euclidean)";
+    if (self != 0 && self != 1) return "self is neither 0 nor 1";
+    if (self && n != m) return "self = 1 needs n == m";
+    if (!(threshold - threshold == 0.f)) return "the threshold is not finite";
+    return gl_check_gallery(d_mat, ld, d_n2, m);
+}
+
+RgArgs rg_args(const float* d_q, const uint8_t* d_qvalid, int n, const float* d_mat, long long ld, const float* d_n2, const uint8_t* d_gvalid,
+               long long m, int metric, float threshold, int self, const GlPlan& p) {
+    RgArgs a;
+    a.q = d_q; a.qvalid = d_qvalid; a.n = n;
+    a.mat = d_mat; a.ld = ld; a.gn2 = d_n2; a.gvalid = d_gvalid; a.m = m;
+    a.metric = metric; a.thr = threshold; a.self = self;
+    a.tiles = (int)p.tiles; a.gps = p.gps;
+    return a;
+}
+
 }  // namespace
+
+extern "C" size_t trl_gallery_range_workspace(int n, long long m, int max_strip_cols) {
+    GlPlan p;
+    if (gl_plan(n, m, 1, max_strip_cols, &p)) return 0;
+    Arena a = Arena::counter(0);
+    uint32_t* cnt;
+    rg_carve(a, p, n, &cnt);
+    return a.high;
+}
+
+extern "C" int trl_gallery_range_count(const float* d_q, const uint8_t* d_qvalid, int n, const float* d_mat, long long ld, const float* d_n2,
+                                       const uint8_t* d_gvalid, long long m, int metric, float threshold, int self, long long* d_offsets,
+                                       void* d_ws, size_t ws_bytes, int max_strip_cols, void* stream) {
+    GlPlan p;
+    if (const char* why = rg_check(n, d_mat, ld, d_n2, m, metric, threshold, self, max_strip_cols, &p)) {
+        trl_set_error("trl_gallery_range_count: %s", why);
+        return TRL_ERR_INVALID;
+    }
+    if (n == 0) return TRL_OK;
+    if (!d_offsets || (m > 0 && !d_q)) { trl_set_error("trl_gallery_range_count: null argument"); return TRL_ERR_INVALID; }
+    Arena a;
+    a.base = (char*)d_ws;
+    a.cap = d_ws ? ws_bytes : 0;
+    uint32_t* cnt;
+    if (((uintptr_t)d_ws & 7) || !rg_carve(a, p, n, &cnt)) {
+        trl_set_error("trl_gallery_range_count: workspace of %zu bytes (need %zu, 8-byte aligned)", ws_bytes, trl_gallery_range_workspace(n, m, max_strip_cols));
+        return TRL_ERR_INVALID;
+    }
+    TRL_CHECK(gl_device_of(d_mat));
+    hipStream_t s = (hipStream_t)stream;
+    if (m == 0) {
+        TRL_HIP(hipMemsetAsync(d_offsets, 0, ((size_t)n + 1) * sizeof(long long), s));
+        return TRL_OK;
+    }
+    const int lds = (GL_TILE_WORDS + GL_INFO_WORDS) * 4;
+    TRL_HIP(hipFuncSetAttribute((const void*)k_gallery_range_count, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    k_gallery_range_count<<<(unsigned)(p.strips * p.tiles), 256, lds, s>>>(
+        rg_args(d_q, d_qvalid, n, d_mat, ld, d_n2, d_gvalid, m, metric, threshold, self, p), cnt);
+    TRL_LAUNCH_CHECK();
+    k_range_rows<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(cnt, n, p.strips * RG_WAVES, d_offsets);
+    TRL_LAUNCH_CHECK();
+    k_range_scan<<<1, 1024, 0, s>>>(d_offsets, n, ((long long)n + 1023) / 1024);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
+extern "C" int trl_gallery_range_fill(const float* d_q, const uint8_t* d_qvalid, int n, const float* d_mat, long long ld, const float* d_n2,
+                                      const uint8_t* d_gvalid, long long m, int metric, float threshold, int self, const long long* d_offsets,
+                                      const void* d_ws, size_t ws_bytes, long long capacity, int32_t* d_index, float* d_score,
+                                      int max_strip_cols, void* stream) {
+    GlPlan p;
+    if (const char* why = rg_check(n, d_mat, ld, d_n2, m, metric, threshold, self, max_strip_cols, &p)) {
+        trl_set_error("trl_gallery_range_fill: %s", why);
+        return TRL_ERR_INVALID;
+    }
+    if (capacity < 0) { trl_set_error("trl_gallery_range_fill: capacity = %lld < 0", capacity); return TRL_ERR_INVALID; }
+    if (n == 0) return TRL_OK;
+    if (!d_offsets || (m > 0 && !d_q) || (capacity > 0 && (!d_index || !d_score))) {
+        trl_set_error("trl_gallery_range_fill: null argument");
+        return TRL_ERR_INVALID;
+    }
+    Arena a;
+    a.base = (char*)const_cast<void*>(d_ws);
+    a.cap = d_ws ? ws_bytes : 0;
+    uint32_t* cnt;
+    if (((uintptr_t)d_ws & 7) || !rg_carve(a, p, n, &cnt)) {
+        trl_set_error("trl_gallery_range_fill: workspace of %zu bytes (need %zu, 8-byte aligned)", ws_bytes, trl_gallery_range_workspace(n, m, max_strip_cols));
+        return TRL_ERR_INVALID;
+    }
+    if (m == 0 || capacity == 0) return TRL_OK;
+    TRL_CHECK(gl_device_of(d_mat));
+    const int lds = (GL_TILE_WORDS + GL_INFO_WORDS) * 4;
+    TRL_HIP(hipFuncSetAttribute((const void*)k_gallery_range_fill, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    k_gallery_range_fill<<<(unsigned)(p.strips * p.tiles), 256, lds, (hipStream_t)stream>>>(
+        rg_args(d_q, d_qvalid, n, d_mat, ld, d_n2, d_gvalid, m, metric, threshold, self, p), d_offsets, cnt, capacity, d_index, d_score);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
 
 extern "C" int trl_gallery_pack(const float* d_rows, long long m, float* d_mat, long long ld, float* d_n2, long long c0, void* stream) {
     if (m < 0 || c0 < 0 || m > 0x7fffffffLL) { trl_set_error("trl_gallery_pack: m = %lld rows at column %lld", m, c0); return TRL_ERR_INVALID; }

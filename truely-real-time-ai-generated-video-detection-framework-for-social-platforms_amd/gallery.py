@@ -17,8 +17,9 @@ and matches are ordered better score first, equal scores to the lower gallery in
 ``cluster_embeddings`` answer the question that needs no enrolled identities -- "which of these faces are the same person?" --
 with DBSCAN over the same scores, from a link bitmap instead of the score matrix.  ``score_histogram`` / ``roc`` / ``calibrate`` find
 the threshold both take: exact counts of same-label and different-label pairs per score bin, again without the score matrix, and
-from them the accept rates at every candidate threshold (``roc_from_counts``, ``threshold_at_far``).  Embeddings never visit the
-host."""
+from them the accept rates at every candidate threshold (``roc_from_counts``, ``threshold_at_far``).  ``range_search`` /
+``range_count`` apply such a threshold to the whole gallery: every enrolled row that passes it, per query, as CSR lists in ascending
+gallery index -- two streamed passes, count then store, and still no score matrix.  Embeddings never visit the host."""
 from __future__ import annotations
 
 import ctypes as C
@@ -62,7 +63,8 @@ def _stream(device):
 
 
 class FaceGallery:
-    """Enrolled embeddings with a label each.  ``add`` appends; rows are never removed or changed."""
+    """Enrolled embeddings with a label each.  ``add`` appends; rows are never removed or changed.  ``search`` / ``identify`` give
+    the k best matches, ``range_search`` every match within a threshold, ``cluster`` groups, ``calibrate`` the threshold."""
 
     def __init__(self, metric: str = "cosine", device=None, capacity: int = 1024):
         self.metric = metric
@@ -232,6 +234,58 @@ class FaceGallery:
                                              _ptr(gid_t), m, self._metric, pairs, _ptr(edges), E, _ptr(counts), _ptr(ws), need,
                                              max_strip_cols, _stream(self.device)))
         return {"edges": edges, "genuine": counts[1, :E + 1], "impostor": counts[0, :E + 1], "nan": counts[:, E + 1]}
+
+    def _range_pass1(self, emb, threshold, valid, gallery_valid, max_strip_cols):
+        """Pass 1 of the range search queued on the current stream: (the arguments both passes share, offsets, workspace)."""
+        m = self._m
+        if threshold is None:
+            raise ValueError("a range search needs its threshold")
+        if emb is None:
+            if valid is not None and gallery_valid is not None:
+                raise ValueError("with emb=None the query rows are the gallery's: give valid or gallery_valid, not both")
+            q, n, self_pairs = (self.rows() if m else None), m, 1
+            qv = gv = _valid(valid if gallery_valid is None else gallery_valid, m, self.device)
+        else:
+            q = _rows(emb, self.device)
+            n, self_pairs = q.shape[0], 0
+            qv, gv = _valid(valid, n, self.device), _valid(gallery_valid, m, self.device)
+        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=self.device)
+        need = self.lib.trl_gallery_range_workspace(n, m, max_strip_cols)
+        ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
+        args = (_ptr(q), _ptr(qv), n, _ptr(self._mat), self.ld, _ptr(self._n2), _ptr(gv), m, self._metric, float(threshold), self_pairs)
+        _lib.check(self.lib.trl_gallery_range_count(*args, _ptr(offsets), _ptr(ws), need, max_strip_cols, _stream(self.device)))
+        return args, (q, qv, gv), offsets, ws, need
+
+    def range_count(self, emb=None, threshold: float | None = None, valid=None, gallery_valid=None, max_strip_cols: int = 0) -> torch.Tensor:
+        """(n,) int64 on the device: how many enrolled rows each query matches (``range_search``'s rule and arguments).  The gallery
+        is streamed once; the call does not synchronise."""
+        _args, _keep, offsets, _ws, _need = self._range_pass1(emb, threshold, valid, gallery_valid, max_strip_cols)
+        return offsets[1:] - offsets[:-1]
+
+    def range_search(self, emb=None, threshold: float | None = None, valid=None, gallery_valid=None, max_results: int | None = None,
+                     max_strip_cols: int = 0):
+        """Every enrolled row within ``threshold`` of each query, as CSR lists: ``(offsets (n + 1,) int64, index (total,) int32,
+        score (total,) float32)`` on the device.  Query r's matches are ``index[offsets[r]:offsets[r + 1]]`` in ascending gallery
+        index, with their scores (``scores``' bits) beside them.
+
+        A pair matches by identify's convention -- cosine ``score >= threshold``, euclidean ``score <= threshold``, in float32; a
+        NaN score never matches -- when the query's ``valid`` entry and the enrolled row's ``gallery_valid`` entry are non-zero.
+        With ``emb=None`` the gallery is searched against itself and a row does not match itself: near-duplicate enrolments,
+        exactly the rows of ``cluster``'s link bitmap at the same threshold (``valid`` and ``gallery_valid`` are then the same
+        rows: give either one).  Neither the (n, m) scores nor n x m bits are written: the gallery is streamed twice, once to
+        count and once to store.
+
+        The total is read back to size the outputs, so the call synchronises the current stream.  ``max_results``: raise
+        ``ValueError`` (naming the total, before anything is allocated for it) when there are more matches than that."""
+        args, _keep, offsets, ws, need = self._range_pass1(emb, threshold, valid, gallery_valid, max_strip_cols)
+        total = int(offsets[-1].item())
+        if max_results is not None and total > int(max_results):
+            raise ValueError(f"range_search found {total} matches, more than max_results = {int(max_results)}")
+        index = torch.empty((total,), dtype=torch.int32, device=self.device)
+        score = torch.empty((total,), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.trl_gallery_range_fill(*args, _ptr(offsets), _ptr(ws), need, total, _ptr(index), _ptr(score), max_strip_cols,
+                                                   _stream(self.device)))
+        return offsets, index, score
 
     def roc(self, emb=None, labels=None, edges=None, valid=None, gallery_valid=None, max_strip_cols: int = 0) -> dict:
         """``score_histogram`` turned into rates: ``edges`` (E,) float32, ``tar`` and ``far`` (E,) float64, host arrays --

@@ -646,6 +646,27 @@ int    trl_gallery_range_fill(const float* d_q, const uint8_t* d_qvalid, int n, 
                               const void* d_ws, size_t ws_bytes, long long capacity, int32_t* d_index, float* d_score,
                               int max_strip_cols, void* stream);
 
+/* ---- Grouped search ("the k most likely people, each with their best shot") -----------------------------------------------------
+ * trl_gallery_search over a gallery that enrols several rows per identity: per query the k best DISTINCT groups, each with its best
+ * row, without the n x m score matrix -- the gallery is streamed once.  Context-free, caller-owned memory, work queued on `stream`,
+ * no synchronisation, the device that of d_mat.  (ABI v7, additive)
+ *   group    d_gid [m] int32: gallery row c belongs to group d_gid[c]; a row with d_gid[c] < 0 is excluded (a gallery mask is
+ *            expressed this way).
+ *   rule     per query: take the rows that are not excluded in the match order above (better score first, equal scores to the lower
+ *            index, NaN last); keep a row iff no earlier row of that order has its group; the first k kept rows are the result,
+ *            k <= 16.  With all ids distinct this is trl_gallery_search's result.
+ *   result   d_score / d_index / d_group [n][k]: the kept rows' scores (trl_gallery_scores' bits), gallery indices and groups.
+ *            Slots past the last kept row, and every slot of a row with d_valid[r] == 0: NaN / -1 / -1.
+ * The result depends on the scores and the rule alone: not on n, strips, max_strip_cols, the stream or launch geometry.
+ * TRL_ERR_INVALID with nothing queued: what trl_gallery_search refuses, and a null d_gid when m > 0. */
+/* Device bytes of d_ws: n x k (score, index) pairs and n x k group ids per strip; trl_gallery_search's plan, so 0 when one strip
+ * writes the result itself and no growth with m unless max_strip_cols forces shorter strips.  0 on bad arguments. */
+size_t trl_gallery_search_groups_workspace(int n, long long m, int k, int max_strip_cols);
+/* n = 0: nothing is done; m = 0: the outputs are filled with NaN / -1 / -1. */
+int    trl_gallery_search_groups(const float* d_q, const uint8_t* d_valid, int n, const float* d_mat, long long ld, const float* d_n2,
+                                 const int32_t* d_gid, long long m, int metric, int k, float* d_score, int32_t* d_index,
+                                 int32_t* d_group, void* d_ws, size_t ws_bytes, int max_strip_cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,19 @@ queries against 1,000,000 -- and in it 3 + 5 rounds, each round every phase once
 at the smallest shape also at -2 (every pair), cluster() where n = m (k_gallery_links, the same main loop as pass 1) and scores()
 where the matrix is at most 2 GiB.  Then, where n <= 8192, what a user would otherwise write: scores() + a comparison + torch.nonzero
 (every kernel they launch), whose lists must equal the range search's.  A row of the table is one kernel of one phase: the median
-over the 5 measured rounds, the smallest and the largest."""
+over the 5 measured rounds, the smallest and the largest.
+
+Groups mode (FaceGallery.search_identities: trl_gallery_search_groups), the search's shapes, k = 1, 5, 16:
+
+    python tools/gallery_kernel_stats.py --groups out_dir > profiles/groups_kernel_stats.csv
+    python tools/gallery_kernel_stats.py --groups-table out_dir
+
+Per shape one process under the same trace.  The gallery is m / 8 identities of 8 noisy unit rows each, shuffled; the queries are
+noisy copies of n of the identities, so every query has eight strong matches of one group.  3 + 5 rounds, each round per k: search()
+(k_gallery_search + k_gallery_merge: the yardstick, the same main loop), then trl_gallery_search_groups with all ids distinct (whose
+result must equal the search's) and with the identities as ids (k_gallery_search_groups + k_gallery_merge_groups).  A row of the table
+is one of the three at one k: the median over the 5 measured rounds of search + merge, the merge's share, and the ratio to the plain
+search of the same rounds."""
 import csv
 import glob
 import json
@@ -377,6 +389,102 @@ def run_all_range(out):
     table_range(out)
 
 
+GG_KS, GG_PER_ID = (1, 5, 16), 8
+GG_WHAT = ("k_gallery_search", "k_gallery_search_groups distinct ids", "k_gallery_search_groups 8 rows per id")
+
+
+def run_groups(m, n):
+    import ctypes as C
+    import torch
+    from truely_amd import _lib
+    from truely_amd.gallery import FaceGallery
+    gen = torch.Generator(device="cuda").manual_seed(m + n)
+    ids_n = max(m // GG_PER_ID, 1)
+    centres = torch.nn.functional.normalize(torch.randn((ids_n, 512), generator=gen, device="cuda"), dim=1)
+    perm = torch.randperm(m, generator=gen, device="cuda")
+    ident = (perm % ids_n).to(torch.int32)                    # the identity of each enrolled row, scattered over the gallery
+    rows = torch.nn.functional.normalize(centres[ident.long()] + 0.03 * torch.randn((m, 512), generator=gen, device="cuda"), dim=1)
+    qid = torch.randint(0, ids_n, (n,), generator=gen, device="cuda")
+    q = torch.nn.functional.normalize(centres[qid] + 0.03 * torch.randn((n, 512), generator=gen, device="cuda"), dim=1)
+    del centres
+    gal = FaceGallery(metric="cosine", capacity=m)
+    gal.add(rows, range(m))
+    del rows
+    distinct = torch.arange(m, dtype=torch.int32, device="cuda")
+    lib, ptr = gal.lib, lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def grouped(gid, k):
+        out = (torch.empty((n, k), dtype=torch.float32, device="cuda"), torch.empty((n, k), dtype=torch.int32, device="cuda"),
+               torch.empty((n, k), dtype=torch.int32, device="cuda"))
+        need = lib.trl_gallery_search_groups_workspace(n, m, k, 0)
+        ws = torch.empty((need,), dtype=torch.uint8, device="cuda") if need else None
+        _lib.check(lib.trl_gallery_search_groups(ptr(q), None, n, ptr(gal._mat), gal.ld, ptr(gal._n2), ptr(gid), m, 0, k, ptr(out[0]), ptr(out[1]),
+                                                 ptr(out[2]), ptr(ws), need, 0, stream))
+        return out
+
+    torch.cuda.synchronize()
+    last = {}
+    for _ in range(CL_WARMUP + CL_WARM):
+        for k in GG_KS:
+            last[k] = (gal.search(q, k=k), grouped(distinct, k), grouped(ident, k))
+    torch.cuda.synchronize()                                  # (not per round: a kernel that starts on a drained queue runs longer)
+    same, own, filled = True, 0.0, 0.0
+    for k in GG_KS:
+        (idx, sc), d, g = last[k]
+        same = same and bool(torch.equal(idx, d[1]) and torch.equal(idx, d[2]) and torch.equal(sc.view(torch.int32), d[0].view(torch.int32)))
+        live = g[2] >= 0
+        per_row = [len(set(r[r >= 0].tolist())) == int((r >= 0).sum()) for r in g[2].cpu()]
+        same = same and all(per_row) and bool((ident[g[1][live].long()] == g[2][live]).all())
+        own, filled = float((g[2][:, 0] == qid.to(torch.int32)).float().mean()), float(live.float().mean())
+    print(json.dumps({"m": m, "n": n, "identities": ids_n, "distinct_equals_search": same, "first_is_own_identity": own, "slots_filled_k16": filled,
+                      "workspace_bytes_k16": int(lib.trl_gallery_search_groups_workspace(n, m, 16, 0)),
+                      "search_workspace_bytes_k16": int(lib.trl_gallery_search_workspace(n, m, 16, 0))}))
+
+
+def table_groups(out):
+    print("m,n,k,metric,what,launches,median_us,min_us,max_us,merge_median_us,over_search,distinct_equals_search,workspace_bytes_k16")
+    calls = CL_WARMUP + CL_WARM
+    for m in M_SHAPES:
+        for n in N_SHAPES:
+            d = os.path.join(out, f"groups_{m}_{n}")
+            if not os.path.exists(os.path.join(d, "info.json")):
+                continue
+            info = json.load(open(os.path.join(d, "info.json")))
+            launches = []                                     # per call, in launch order: [main ns, merge ns]
+            for s, e, name in _trace(d):
+                if "k_gallery_merge" in name:
+                    launches[-1][1] = e - s
+                elif "k_gallery_search" in name:
+                    launches.append([e - s, 0, "k_gallery_search_groups" in name])
+            assert len(launches) == calls * len(GG_KS) * 3, (m, n, len(launches))
+            for ki, k in enumerate(GG_KS):
+                med = {}
+                for w, what in enumerate(GG_WHAT):
+                    part = [launches[(r * len(GG_KS) + ki) * 3 + w] for r in range(CL_WARMUP, calls)]
+                    assert all(p[2] == (w > 0) for p in part), (m, n, k, what)
+                    tot = [(a + b) / 1e3 for a, b, _g in part]
+                    med[what] = statistics.median(tot)
+                    print(f"{m},{n},{k},cosine,{what},{len(part)},{med[what]:.1f},{min(tot):.1f},{max(tot):.1f},"
+                          f"{statistics.median(b for _a, b, _g in part) / 1e3:.1f},{med[what] / med[GG_WHAT[0]]:.3f},{info['distinct_equals_search']},"
+                          f"{info['workspace_bytes_k16'] if w else info['search_workspace_bytes_k16']}")
+
+
+def run_all_groups(out):
+    for m in M_SHAPES:
+        for n in N_SHAPES:
+            d = os.path.join(out, f"groups_{m}_{n}")
+            os.makedirs(d, exist_ok=True)
+            r = subprocess.run(["rocprofv3", "--kernel-trace", "-d", d, "-o", "t", "-f", "csv", "--", sys.executable, os.path.abspath(__file__),
+                                "run-groups", str(m), str(n)], capture_output=True, text=True, timeout=300)
+            if r.returncode != 0:
+                sys.exit(f"groups shape {m} x {n} failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+            print(line, file=sys.stderr, flush=True)
+            open(os.path.join(d, "info.json"), "w").write(line)
+    table_groups(out)
+
+
 def run_all(out):
     for m in M_SHAPES:
         for n in N_SHAPES:
@@ -415,5 +523,11 @@ if __name__ == "__main__":
         table_range(sys.argv[2])
     elif sys.argv[1] == "run-range":
         run_range(int(sys.argv[2]), int(sys.argv[3]))
+    elif sys.argv[1] == "--groups":
+        run_all_groups(sys.argv[2])
+    elif sys.argv[1] == "--groups-table":
+        table_groups(sys.argv[2])
+    elif sys.argv[1] == "run-groups":
+        run_groups(int(sys.argv[2]), int(sys.argv[3]))
     else:
         run(int(sys.argv[2]), int(sys.argv[3]))

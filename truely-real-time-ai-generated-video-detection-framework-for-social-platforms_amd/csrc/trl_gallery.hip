@@ -27,11 +27,15 @@
 //
 // The range search (f-10) ends it in popcounts and ranked stores: k_gallery_range_count counts each row's matches per (strip, wave),
 // k_range_rows / k_range_scan turn the counts into bases and int64 offsets, k_gallery_range_fill stores the CSR lists.
+//
+// The grouped search (f-11) ends it in lists of distinct groups: k_gallery_search_groups is k_gallery_search with a group id per gallery
+// row and lists that hold each group's best row only (trl_gallery_groups.h), k_gallery_merge_groups merges the strips by the same rule.
 #include <algorithm>
 #include <utility>
 
 #include "trl_common.h"
 #include "trl_gallery_bins.h"
+#include "trl_gallery_groups.h"
 #include "trl_gallery_order.h"
 
 namespace {
@@ -732,6 +736,153 @@ __global__ __launch_bounds__(256, 2) void k_gallery_range_fill(RgArgs a, const l
     });
 }
 
+// ---- grouped search: per query the k best DISTINCT groups, each with its best row ------------------------
+// k_gallery_search's frame with another list: every gallery row carries a group id (gid < 0: the row is excluded), and a list holds
+// the best row of each of the k best groups seen so far (trl_gallery_groups.h: 8-byte entries as before, their groups in a parallel
+// int32 array).  The slab's 32 ids are loaded like gn2 -- lane j loads gid[c0 + j], one line -- and staged behind the wave's scores.
+// The comparison with the list's k-th entry, kept in a register, is still a valid rejection: a full list holds better rows of k
+// distinct groups, so the newcomer is either beaten inside its own group or by k others.  A lane reads the scores and ids of four
+// columns together (one LDS round trip per quarter of its 16 columns); the list itself is touched for survivors only.
+// A strip's list of its k best distinct groups is enough for the merge.  Suppose group L's globally best row lies in strip s and is
+// not in strip s's list: then k other groups each have a row in strip s alone that comes before it, their globally best rows come
+// before it too, and L is not among the k best groups.  So every group of the answer reaches the merge with its globally best row,
+// and rows of it from other strips lose to that row in trl_gl_insert_group.  The same holds one level down for the eight lists of a
+// row inside a workgroup, and one level up for the 64 lanes of the merge kernel.
+// LDS at k = 16: 65,792 (tile) + 384 (info) + 17,408 (stages with ids) + 32,768 (entries) + 16,384 (groups) = 132,736 bytes.
+constexpr int GG_STAGE_WORDS = GL_STAGE_WORDS + GL_ROWS;   // a wave's 32 x 32 scores, then its slab's 32 group ids
+
+__global__ __launch_bounds__(256, 2) void k_gallery_search_groups(const float* __restrict__ q, const uint8_t* __restrict__ valid, int n,
+                                                               const float* __restrict__ mat, long long ld, const float* __restrict__ gn2,
+                                                               const int32_t* __restrict__ gid, long long m, int metric, int k, int tiles,
+                                                               long long gps, long long groups, TrlGlEntry* __restrict__ part,
+                                                               int32_t* __restrict__ part_ids, float* __restrict__ d_score,
+                                                               int32_t* __restrict__ d_index, int32_t* __restrict__ d_group) {
+    extern __shared__ float gl_lds[];
+    float* tile = gl_lds;
+    float* info = gl_lds + GL_TILE_WORDS;
+    const int* rowok = reinterpret_cast<const int*>(info) + 2 * GL_ROWS;
+    float* stages = gl_lds + GL_TILE_WORDS + GL_INFO_WORDS;
+    TrlGlEntry* lists = reinterpret_cast<TrlGlEntry*>(stages + 4 * GG_STAGE_WORDS);              // (8-byte aligned: even word offset)
+    int32_t* lids = reinterpret_cast<int32_t*>(lists + GL_LISTS * GL_ROWS * k);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long row0 = (long long)(blockIdx.x % (unsigned)tiles) * GL_ROWS, strip = blockIdx.x / (unsigned)tiles;
+    float* stage = stages + wave * GG_STAGE_WORDS;
+    int32_t* ids = reinterpret_cast<int32_t*>(stage + GL_STAGE_WORDS);
+    // lane l keeps the list of row l & 31 over columns 16 (l >> 5) .. + 15 of each of the wave's 32-column slabs
+    const int at = ((wave * 2 + (lane >> 5)) * GL_ROWS + (lane & 31)) * k;
+    TrlGlEntry* mine = lists + at;
+    int32_t* mine_ids = lids + at;
+    for (int e = 0; e < k; e++) {
+        mine[e] = trl_gl_empty();
+        mine_ids[e] = -1;
+    }
+    const int live = gl_fill_tile(tile, info, q, valid, n, row0, tid);
+    const int j = lane & 31, h = lane >> 5;
+    const long long g_end = (strip + 1) * gps < groups ? (strip + 1) * gps : groups;
+    for (long long g = strip * gps; g < g_end; g++) {
+        const long long c0 = g * GL_GROUP + wave * 32;
+        if (c0 >= m) break;
+        const f32x16 acc = gl_chain(tile, mat, (size_t)ld, c0, lane);
+        const long long col = c0 + j;
+        const float g2 = gn2[col], gs = __builtin_sqrtf(g2);          // (col < ld: n2 has ld entries)
+        const int32_t id = col < m ? gid[col] : -1;                   // (gid has m entries)
+        int h_here = h;                                               // (as in k_gallery_search: the 16 rows' LDS addresses are
+        asm volatile("" : "+v"(h_here));                              // made here, not kept in registers across the chain)
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int r = (i & 3) + 8 * (i >> 2) + 4 * h_here;
+            stage[r * 33 + j] = gl_score(metric, acc[i], info[r], info[GL_ROWS + r], g2, gs);
+        }
+        if (h_here == 0) ids[j] = id;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");        // (wave-private data: the fence orders the wave's own LDS traffic)
+        __builtin_amdgcn_wave_barrier();
+        if (rowok[j]) {
+            const float* sr = stage + j * 33 + 16 * h_here;
+            const int32_t* si = ids + 16 * h_here;
+            const long long cb = c0 + 16 * h_here;
+            TrlGlEntry last = mine[k - 1];
+            // four columns at a time: their scores and ids are read together (eight LDS reads in flight; all 32 columns of the
+            // stage exist, whatever m is), so a quarter that holds no survivor costs one LDS round trip, not four
+            for (int c4 = 0; c4 < 16 && cb + c4 < m; c4 += 4) {
+                float s4[4];
+                int32_t g4[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    s4[u] = sr[c4 + u];
+                    g4[u] = si[c4 + u];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const long long c = cb + c4 + u;
+                    if (c < m && g4[u] >= 0 && trl_gl_before(metric, s4[u], (int32_t)c, last.score, last.index) &&
+                        trl_gl_insert_group(mine, mine_ids, k, metric, s4[u], (int32_t)c, g4[u]))
+                        last = mine[k - 1];
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");        // the next group's scores and ids follow these reads
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    if (tid < live) {
+        TrlGlEntry* L = lists + tid * k;                 // the row's first list takes the other seven
+        int32_t* I = lids + tid * k;
+        trl_gl_merge_groups(L, I, k, metric, L + GL_ROWS * k, I + GL_ROWS * k, GL_LISTS - 1, (long long)GL_ROWS * k);
+        const size_t row = (size_t)(row0 + tid);
+        if (part) {
+            const size_t o = ((size_t)strip * (size_t)n + row) * (size_t)k;
+            for (int e = 0; e < k; e++) {
+                part[o + e] = L[e];
+                part_ids[o + e] = I[e];
+            }
+        } else {
+            for (int e = 0; e < k; e++) {
+                d_score[row * k + e] = L[e].score;
+                d_index[row * k + e] = L[e].index == TRL_GL_EMPTY ? -1 : L[e].index;
+                d_group[row * k + e] = I[e];
+            }
+        }
+    }
+}
+
+// one wave per query row, as k_gallery_merge: lane l puts strips l, l + 64, ... into a list of its own, then lane 0 merges the 64
+// lists -- with the grouped operations, so a group that reaches the merge from several strips keeps its best row
+__global__ __launch_bounds__(64) void k_gallery_merge_groups(const TrlGlEntry* __restrict__ part, const int32_t* __restrict__ part_ids, int n,
+                                                             long long strips, int k, int metric, float* __restrict__ d_score,
+                                                             int32_t* __restrict__ d_index, int32_t* __restrict__ d_group) {
+    __shared__ TrlGlEntry best[64 * TRL_GL_MAX_K];
+    __shared__ int32_t best_ids[64 * TRL_GL_MAX_K];
+    const int lane = threadIdx.x;
+    const size_t row = blockIdx.x;
+    TrlGlEntry* mine = best + lane * k;
+    int32_t* mine_ids = best_ids + lane * k;
+    for (int e = 0; e < k; e++) {
+        mine[e] = trl_gl_empty();
+        mine_ids[e] = -1;
+    }
+    for (long long s = lane; s < strips; s += 64) {
+        const size_t o = ((size_t)s * (size_t)n + row) * (size_t)k;
+        TrlGlEntry v[TRL_GL_MAX_K];
+        int32_t vi[TRL_GL_MAX_K];
+#pragma unroll
+        for (int e = 0; e < TRL_GL_MAX_K; e++) {
+            v[e] = e < k ? part[o + e] : trl_gl_empty();
+            vi[e] = e < k ? part_ids[o + e] : -1;
+        }
+#pragma unroll
+        for (int e = 0; e < TRL_GL_MAX_K; e++)
+            if (e < k && v[e].index != TRL_GL_EMPTY) trl_gl_insert_group(mine, mine_ids, k, metric, v[e].score, v[e].index, vi[e]);
+    }
+    __syncthreads();
+    if (lane == 0) trl_gl_merge_groups(best, best_ids, k, metric, best + k, best_ids + k, 63, k);
+    __syncthreads();
+    if (lane < k) {
+        d_score[row * k + lane] = best[lane].score;
+        d_index[row * k + lane] = best[lane].index == TRL_GL_EMPTY ? -1 : best[lane].index;
+        d_group[row * k + lane] = best_ids[lane];
+    }
+}
+
 // ---- the search's plan and workspace, written once: trl_gallery_search_workspace is a dry run of gl_carve -------------------------
 struct GlPlan {
     long long tiles = 0, groups = 0, gps = 0, strips = 0;
@@ -760,6 +911,17 @@ bool gl_carve(Arena& a, const GlPlan& p, int n, int k, TrlGlEntry** part) {
     if (p.strips > 1) {
         *part = (TrlGlEntry*)a.alloc((size_t)p.strips * (size_t)n * (size_t)k * sizeof(TrlGlEntry));
         if (!*part) return false;
+    }
+    return true;
+}
+
+// the grouped search's strip lists: gl_carve's entries [strips][n][k] and, in a block of their own, their group ids
+bool gg_carve(Arena& a, const GlPlan& p, int n, int k, TrlGlEntry** part, int32_t** part_ids) {
+    *part_ids = nullptr;
+    if (!gl_carve(a, p, n, k, part)) return false;
+    if (*part) {
+        *part_ids = (int32_t*)a.alloc((size_t)p.strips * (size_t)n * (size_t)k * sizeof(int32_t));
+        if (!*part_ids) return false;
     }
     return true;
 }
@@ -984,6 +1146,57 @@ extern "C" int trl_gallery_search(const float* d_q, const uint8_t* d_valid, int 
     TRL_LAUNCH_CHECK();
     if (part) {
         k_gallery_merge<<<(unsigned)n, 64, 0, s>>>(part, n, p.strips, k, metric, d_score, d_index);
+        TRL_LAUNCH_CHECK();
+    }
+    return TRL_OK;
+}
+
+extern "C" size_t trl_gallery_search_groups_workspace(int n, long long m, int k, int max_strip_cols) {
+    GlPlan p;
+    if (gl_plan(n, m, k, max_strip_cols, &p)) return 0;
+    Arena a = Arena::counter(0);
+    TrlGlEntry* part;
+    int32_t* part_ids;
+    gg_carve(a, p, n, k, &part, &part_ids);
+    return a.high;
+}
+
+extern "C" int trl_gallery_search_groups(const float* d_q, const uint8_t* d_valid, int n, const float* d_mat, long long ld, const float* d_n2,
+                                         const int32_t* d_gid, long long m, int metric, int k, float* d_score, int32_t* d_index,
+                                         int32_t* d_group, void* d_ws, size_t ws_bytes, int max_strip_cols, void* stream) {
+    GlPlan p;
+    if (const char* why = gl_plan(n, m, k, max_strip_cols, &p)) { trl_set_error("trl_gallery_search_groups: %s", why); return TRL_ERR_INVALID; }
+    if (metric != TRL_GL_COSINE && metric != TRL_GL_EUCLIDEAN) { trl_set_error("trl_gallery_search_groups: metric %d (0 cosine, 1 euclidean)", metric); return TRL_ERR_INVALID; }
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) { trl_set_error("trl_gallery_search_groups: %s", why); return TRL_ERR_INVALID; }
+    if (m > 0 && !d_gid) { trl_set_error("trl_gallery_search_groups: null group ids"); return TRL_ERR_INVALID; }
+    if (n == 0) return TRL_OK;
+    if (!d_q || !d_score || !d_index || !d_group) { trl_set_error("trl_gallery_search_groups: null argument"); return TRL_ERR_INVALID; }
+    Arena a;
+    a.base = (char*)d_ws;
+    a.cap = d_ws ? ws_bytes : 0;
+    TrlGlEntry* part;
+    int32_t* part_ids;
+    if (((uintptr_t)d_ws & 7) || !gg_carve(a, p, n, k, &part, &part_ids)) {
+        trl_set_error("trl_gallery_search_groups: workspace of %zu bytes (need %zu, 8-byte aligned)", ws_bytes,
+                      trl_gallery_search_groups_workspace(n, m, k, max_strip_cols));
+        return TRL_ERR_INVALID;
+    }
+    TRL_CHECK(gl_device_of(d_mat));
+    hipStream_t s = (hipStream_t)stream;
+    if (m == 0) {
+        const long long count = (long long)n * k;
+        k_gallery_fill<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(d_score, d_index, count);
+        TRL_LAUNCH_CHECK();
+        TRL_HIP(hipMemsetAsync(d_group, 0xff, (size_t)count * sizeof(int32_t), s));             // (-1)
+        return TRL_OK;
+    }
+    const int lds = (GL_TILE_WORDS + GL_INFO_WORDS + 4 * GG_STAGE_WORDS) * 4 + GL_LISTS * GL_ROWS * k * (int)(sizeof(TrlGlEntry) + sizeof(int32_t));
+    TRL_HIP(hipFuncSetAttribute((const void*)k_gallery_search_groups, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    k_gallery_search_groups<<<(unsigned)(p.strips * p.tiles), 256, lds, s>>>(d_q, d_valid, n, d_mat, ld, d_n2, d_gid, m, metric, k, (int)p.tiles,
+                                                                            p.gps, p.groups, part, part_ids, d_score, d_index, d_group);
+    TRL_LAUNCH_CHECK();
+    if (part) {
+        k_gallery_merge_groups<<<(unsigned)n, 64, 0, s>>>(part, part_ids, n, p.strips, k, metric, d_score, d_index, d_group);
         TRL_LAUNCH_CHECK();
     }
     return TRL_OK;

@@ -19,7 +19,10 @@ with DBSCAN over the same scores, from a link bitmap instead of the score matrix
 the threshold both take: exact counts of same-label and different-label pairs per score bin, again without the score matrix, and
 from them the accept rates at every candidate threshold (``roc_from_counts``, ``threshold_at_far``).  ``range_search`` /
 ``range_count`` apply such a threshold to the whole gallery: every enrolled row that passes it, per query, as CSR lists in ascending
-gallery index -- two streamed passes, count then store, and still no score matrix.  Embeddings never visit the host."""
+gallery index -- two streamed passes, count then store, and still no score matrix.  A gallery that enrols several rows per person
+(a few photos, every good frame of a clip) has ``identities``: the distinct labels in order of first enrolment.
+``search_identities`` / ``identify_topk`` give the k best distinct identities per query, each with its best row -- "the five most
+likely people", not five rows of one -- in one streamed pass as well.  Embeddings never visit the host."""
 from __future__ import annotations
 
 import ctypes as C
@@ -64,7 +67,8 @@ def _stream(device):
 
 class FaceGallery:
     """Enrolled embeddings with a label each.  ``add`` appends; rows are never removed or changed.  ``search`` / ``identify`` give
-    the k best matches, ``range_search`` every match within a threshold, ``cluster`` groups, ``calibrate`` the threshold."""
+    the k best matches, ``search_identities`` / ``identify_topk`` the k best distinct labels (``identities``), ``range_search``
+    every match within a threshold, ``cluster`` groups, ``calibrate`` the threshold."""
 
     def __init__(self, metric: str = "cosine", device=None, capacity: int = 1024):
         self.metric = metric
@@ -77,12 +81,16 @@ class FaceGallery:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._m = 0
         self._labels: list = []
+        self._identities: list = []                      # the distinct labels in order of first enrolment
+        self._identity_of: dict = {}                     # label -> its position there: the row's group id
+        self._unhashable: list = []                      # positions of the identities that cannot be keys of that dict
         self._alloc(max(int(capacity), 1))
 
     def _alloc(self, capacity: int):
         ld = (capacity + 31) // 32 * 32
         self._mat = torch.zeros((DIM, ld), dtype=torch.float32, device=self.device)      # (padding columns stay zero)
         self._n2 = torch.zeros((ld,), dtype=torch.float32, device=self.device)
+        self._gid = torch.full((ld,), -1, dtype=torch.int32, device=self.device)         # each row's group id, beside the matrix
 
     @property
     def ld(self) -> int:
@@ -95,6 +103,11 @@ class FaceGallery:
     def labels(self) -> list:
         return list(self._labels)
 
+    @property
+    def identities(self) -> list:
+        """The distinct labels (equal by ``==`` / hash) in order of first enrolment.  A row's group id is its label's position here."""
+        return list(self._identities)
+
     def add(self, embeddings, labels) -> None:
         """Append m embeddings, (m, 512), with their m labels (any objects)."""
         rows = _rows(embeddings, self.device)
@@ -103,11 +116,28 @@ class FaceGallery:
         if len(labels) != m:
             raise ValueError(f"{m} embeddings but {len(labels)} labels")
         if self._m + m > self.ld:                        # grow geometrically; the copy stays on the device
-            old_mat, old_n2, old_ld = self._mat, self._n2, self.ld
+            old_mat, old_n2, old_gid, old_ld = self._mat, self._n2, self._gid, self.ld
             self._alloc(max(2 * old_ld, self._m + m))
             self._mat[:, :old_ld].copy_(old_mat)
             self._n2[:old_ld].copy_(old_n2)
+            self._gid[:old_ld].copy_(old_gid)
         _lib.check(self.lib.trl_gallery_pack(_ptr(rows), m, _ptr(self._mat), self.ld, _ptr(self._n2), self._m, _stream(self.device)))
+        ids = []
+        for l in labels:
+            try:
+                i = self._identity_of.get(l)
+            except TypeError:                            # an unhashable label (add takes any object): found by == alone, slowly
+                i = next((j for j in self._unhashable if self._identities[j] == l), None)
+            if i is None:
+                i = len(self._identities)
+                self._identities.append(l)
+                try:
+                    self._identity_of[l] = i
+                except TypeError:
+                    self._unhashable.append(i)
+            ids.append(i)
+        if m:
+            self._gid[self._m:self._m + m].copy_(torch.tensor(ids, dtype=torch.int32), non_blocking=False)
         self._m += m
         self._labels.extend(labels)
 
@@ -151,6 +181,42 @@ class FaceGallery:
             ok &= (score >= threshold) if self._metric == 0 else (score <= threshold)
         picks = torch.where(ok, idx, torch.full_like(idx, -1)).tolist()          # n integers to the host: the labels live there
         return [self._labels[i] if i >= 0 else None for i in picks], score
+
+    def search_identities(self, emb, k: int = 5, valid=None, gallery_valid=None, max_strip_cols: int = 0):
+        """(group (n, k) int32, index (n, k) int32, score (n, k) float32) on the device: per query the k best DISTINCT identities,
+        best first, each with its best enrolled row -- ``identities[group]`` is the label, ``index`` that row, ``score`` its score
+        (``scores``' bits).  The enrolled rows are taken in ``search``'s order and a row is kept iff no earlier row has its label;
+        rows whose ``gallery_valid`` entry is zero are left out.  Slots past the last identity, and every slot of a row whose
+        ``valid`` entry is zero, hold -1 / -1 / NaN.  The gallery is streamed once; the call does not synchronise."""
+        q = _rows(emb, self.device)
+        n, m, k = q.shape[0], self._m, int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be 1..{MAX_K}")
+        valid, gv = _valid(valid, n, self.device), _valid(gallery_valid, m, self.device)
+        gid = self._gid[:m]
+        if gv is not None:
+            gid = torch.where(gv != 0, gid, torch.full_like(gid, -1))         # (on the device: a masked row is an excluded row)
+        group = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        score = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        need = self.lib.trl_gallery_search_groups_workspace(n, m, k, max_strip_cols)
+        ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
+        _lib.check(self.lib.trl_gallery_search_groups(_ptr(q), _ptr(valid), n, _ptr(self._mat), self.ld, _ptr(self._n2), _ptr(gid), m,
+                                                      self._metric, k, _ptr(score), _ptr(idx), _ptr(group), _ptr(ws), need, max_strip_cols,
+                                                      _stream(self.device)))
+        return group, idx, score
+
+    def identify_topk(self, emb, k: int = 5, threshold: float | None = None, valid=None, gallery_valid=None) -> list:
+        """Per query a list of ``(label, score)`` pairs, best first: its at most k best distinct identities, each with the score of
+        its best enrolled row.  Entries that are empty, whose score is NaN, or that fail ``threshold`` by identify's convention
+        (cosine: score < threshold; euclidean: score > threshold) are dropped, so a list may be shorter than k, or empty."""
+        group, _idx, score = self.search_identities(emb, k=k, valid=valid, gallery_valid=gallery_valid)
+        ok = (group >= 0) & ~torch.isnan(score)
+        if threshold is not None:
+            ok &= (score >= threshold) if self._metric == 0 else (score <= threshold)
+        picks = torch.where(ok, group, torch.full_like(group, -1)).tolist()   # n x k integers and scores to the host: the labels live there
+        scores = score.tolist()
+        return [[(self._identities[g], s) for g, s in zip(gs, ss) if g >= 0] for gs, ss in zip(picks, scores)]
 
     def cluster(self, threshold: float, min_samples: int = 1, valid=None, return_info: bool = False, max_strip_cols: int = 0):
         """DBSCAN labels of the enrolled rows, (len(self),) int32 on the device: "which of these are the same person?".

@@ -191,6 +191,8 @@ int  trl_detect_embed_end(trl_ctx* ctx);
  * run-length counter, and the 0..100 score.  n = number of sampled frames (in time order),
  * frame_count = frames decoded, fps as int(cap.get(CAP_PROP_FPS)) (model.py:28).
  *   d_sims   : f32 [n]  (2.0 where no comparison happened)        may be NULL
+ *              The value 2.0 marks "no comparison".  A NaN or infinite similarity (a zero or non-finite embedding, a norm
+ *              that underflows) is a comparison, and it resets the run unless it is -inf (model.py:62-65).
  *   d_flags  : u8  [n]  1 where the frame was counted "AI detected" (model.py:66)  may be NULL
  *   d_result : i32 [4]  {score, final run length, hits, total sampled frames} */
 int  trl_drift_score(trl_ctx* ctx, const float* d_emb, const uint8_t* d_valid, int n,

@@ -794,8 +794,8 @@ __global__ __launch_bounds__(256) void drift_scan_kernel(const float* __restrict
             for (int t = 0; t < m; t++) {
                 const float sim = sh[t];
                 uint8_t f = 0;
-                if (sim <= 1.5f) {          // a comparison happened
-                    run = (sim < thr_sim) ? run + 1 : 0;
+                if (sim != 2.0f) {          // a comparison happened: every value but the sentinel, NaN and +-inf included
+                    run = (sim < thr_sim) ? run + 1 : 0;   // (NaN and +inf are not below the threshold: model.py:62-65 resets)
                     if (run > thr_frames) { hits++; f = 1; }
                 }
                 fl[t] = f;

@@ -57,6 +57,11 @@ def analyze_video(frames, fps: int = 30, frame_count: int | None = None, engine:
     return out
 
 
+def compared(sims: np.ndarray) -> np.ndarray:
+    """Where a comparison happened (model.py:60): everywhere but at the 2.0 sentinel -- a NaN or infinite similarity is one."""
+    return sims != 2.0
+
+
 _RUN_CTX_LOCK = threading.Lock()                          # creates an engine's _RunCtx once, whichever run() call comes first
 
 
@@ -358,9 +363,10 @@ def _run_locked(ctx: _RunCtx, cap, fps: int, width: int, height: int, video_path
             return
         sims = d["sims"].cpu().numpy(); flags = d["flags"].cpu().numpy()
         vmask = out["valid"].cpu().numpy(); rect = out["rect"].cpu().numpy()
+        had = compared(sims)
         notes = {}
         for j in range(len(vmask)):
-            if vmask[j] and sims[j] <= 1.5:               # a face with a previous embedding (model.py:60,67-74)
+            if vmask[j] and had[j]:                       # a face with a previous embedding (model.py:60,67-74)
                 notes[j * step] = (first + j * step, rect[j], bool(flags[j]))
         if on_dev:                                        # the window's frames are the writer's own: drawn on and encoded in place
             writer.put_batch(frames[:nfr], [(k,) + notes[k] for k in sorted(notes)], ready)

@@ -258,6 +258,10 @@ int  trl_debug_option(trl_ctx* ctx, const char* key, int value);
  * fp16, or trl_debug_option(ctx, "pnet_screen", 0) switched it off; every M-tile then takes the exact path).  Results are the
  * same either way. (ABI v7) */
 int  trl_debug_pnet_screen_bound(trl_ctx* ctx, float* A, float* B, int* on);
+/* test hook: the bound the screen applies is per input, E = sum over the cell's 3 x 3 x 16 conv2 inputs of g[channel] |x| + B, with
+ * g[channel] the largest of that channel's nine per-tap coefficients of A (so 9 * sum(g) >= A, and E <= A X + B up to that slack).
+ * h_g16 receives the sixteen g (infinities where the conv3 weights do not fit fp16). */
+int  trl_debug_pnet_screen_weights(trl_ctx* ctx, float* h_g16);
 /* test hook: the R-/O-Net launches are sized by optimistic per-frame candidate capacities; set them (<= 0 keeps a value) and read
  * how many attempts the last call took (a too-small capacity makes the call re-run itself with a larger one) */
 int  trl_debug_batch_capacity(trl_ctx* ctx, float t2_per_frame, float t3_per_frame, int* last_attempts);

@@ -3,13 +3,15 @@
 The fused kernel computes conv3 (3x3, 16 -> 32) of every 32-cell M-tile (2 output rows x 16 columns of a 16 x 16-cell tile)
 first with fp16 operands, and recomputes the M-tile with the exact f32 chain only when some valid cell could pass the threshold:
 
-    d_screen + E >= dthr,   E = A * X_cell + B,
+    d_screen + E >= dthr,   E = sum over the cell's 3 x 3 x 16 conv2 inputs of ghat[channel] * |x| + B,
 
-X_cell = max |conv2 activation| over the cell's 3 x 3 x 16 receptive field, A and B the error bound of the screened logit
-difference (screen_bound below; the library computes the same bound in trl_pnet_prepare).  This tool estimates, on the CPU, the
-share of M-tiles the screen confirms for the seeded weights and the clips bench.py builds for configs 0, 1, 2 and 4: it evaluates
-PNet in float32 with torch (the pyramid by adaptive average pooling), takes d = logit1 - logit0 of every cell and counts the
-M-tiles with some valid cell at d + E >= dthr.  The E = 0 column is the kernel's older prefilter alone.
+ghat and B the error bound of the screened logit difference (screen_weights below; the library computes the same in
+trl_pnet_prepare).  The rule it replaced was E = A * X_cell + B, X_cell = max |conv2 activation| over the same receptive field
+(screen_bound; the library still reports A).  This tool estimates, on the CPU, the share of M-tiles the screen confirms for the
+seeded weights and the clips bench.py builds for configs 0, 1, 2 and 4: it evaluates PNet in float32 with torch (the pyramid by
+adaptive average pooling), takes d = logit1 - logit0 of every cell and counts the M-tiles with some valid cell at d + E >= dthr,
+under the kernel's rule (confirmed_share) and the replaced one (confirmed_share_max_rule).  The E = 0 column is the kernel's older
+prefilter alone.
 
     python tools/pnet_screen_audit.py [--frames 8] [--out profiles/pnet_screen_audit.json]
 """
@@ -75,8 +77,41 @@ def screen_bound(t):
     return up(A), up(B), True
 
 
-def pnet_maps(lvl, t):
-    """float32 PNet of one level [h][w][3] -> (d = logit1 - logit0 [oh][ow], X_cell [oh][ow])."""
+def screen_weights(t):
+    """(g [9][16], ghat [16], B, ok): the same bound with A's terms kept per input k = (tap, channel),
+
+        |d_screen - d_exact| <= sum_k g_k |x_k| + B,   sum_k g_k = A (before A's inflation),
+
+    every term of A in screen_bound being a sum over k of a non-negative coefficient times the bound X of |x_k|.  ghat[channel] =
+    max over the nine taps of g, multiplied by 1 + 2^-10 and rounded up to float32 like A and B: the weights the kernel applies
+    (one number per conv2 cell and channel half, nine cells added).  The factor also covers the kernel's f32 roundings of its sum:
+    at most 18 per term (8 fmaf of a cell half, 8 additions over the taps, the two halves, + B), all on non-negative terms.
+    g is returned without the inflation (float64)."""
+    w3 = t["pnet.conv3.w"].astype(np.float64)
+    s3 = t["pnet.prelu3"].astype(np.float64)
+    wl = t["pnet.conv4_1.w"].astype(np.float64)
+    _A, B, ok = screen_bound(t)
+    if not ok:
+        return np.full((9, 16), math.inf), [math.inf] * 16, B, False
+    aw = np.abs(w3)                                      # [144][32]: the per-input (|w_k|, D_k) in place of (W1, D)
+    h = w3.astype(np.float32).astype(np.float16).astype(np.float64)
+    dw = np.where(aw < TINY16, aw, np.abs(h - w3))
+    ge, gs = _gamma(145), _gamma(145, 2 * U32)
+    a3 = dw * (1 + U16) + aw * U16 + gs * (aw + dw) * (1 + U16) + ge * aw
+    aM = aw * (1 + ge)
+    L = np.maximum(1.0, np.abs(s3))
+    ap = L * (1 + U32) * a3 + 2 * U32 * L * aM
+    aP = L * (1 + U32) * aM
+    wd = np.abs(wl[:, 1] - wl[:, 0])
+    g = _gamma(35) * (aP @ (np.abs(wl[:, 0]) + np.abs(wl[:, 1]))) + ap @ wd + _gamma(36) * (1 + U32) * ((aP + ap) @ wd)
+    g = g.reshape(9, 16)
+    up = lambda v: float(np.nextafter(np.float32(v), np.float32(np.inf))) if np.float32(v) < v else float(np.float32(v))
+    return g, [up(v * (1 + 2.0 ** -10)) for v in g.max(0)], B, True
+
+
+def pnet_maps(lvl, t, ghat=None):
+    """float32 PNet of one level [h][w][3] -> (d = logit1 - logit0 [oh][ow], X_cell [oh][ow]) and, given ghat, the per-input error
+    sum of every cell, sum over its 3 x 3 x 16 conv2 inputs of ghat[channel] |x|, as a third map."""
     import torch
     import torch.nn.functional as F
 
@@ -97,7 +132,10 @@ def pnet_maps(lvl, t):
     wl = torch.from_numpy(t["pnet.conv4_1.w"].T.copy())[:, :, None, None]
     lg = F.conv2d(y, wl, torch.from_numpy(t["pnet.conv4_1.b"]))[0]
     X = F.max_pool2d(a2.abs().amax(1, keepdim=True), 3, 1)[0, 0]
-    return (lg[1] - lg[0]).numpy(), X.numpy()
+    if ghat is None:
+        return (lg[1] - lg[0]).numpy(), X.numpy()
+    m = (a2.abs().double() * torch.tensor(ghat, dtype=torch.float64).view(1, -1, 1, 1)).sum(1, keepdim=True)
+    return (lg[1] - lg[0]).numpy(), X.numpy(), (9.0 * F.avg_pool2d(m, 3, 1))[0, 0].numpy()
 
 
 def mtile_hits(ok):
@@ -113,7 +151,7 @@ def mtile_hits(ok):
     return int(val.sum()), int(hit.sum())
 
 
-def audit(cfg_id, frames, t, A, B, thr=0.6):
+def audit(cfg_id, frames, t, A, B, ghat, thr=0.6):
     import torch
     import torch.nn.functional as F
     import bench
@@ -124,17 +162,19 @@ def audit(cfg_id, frames, t, A, B, thr=0.6):
     clip = bench.make_clip(cfg, min(frames, cfg["batch"]), seed=0)
     orc = Oracle(weights.pack_tensors(t))
     dthr = math.log(thr / (1 - thr)) - 0.05
-    tot = hit_s = hit_0 = 0
+    tot = hit_s = hit_m = hit_0 = cells = 0
     for f in clip:
         src = torch.from_numpy(f.astype(np.float32).transpose(2, 0, 1).copy())[None]
         for _s, h, w in orc.scales(cfg["H"], cfg["W"], cfg["min_face"], 0.709):
             lvl = ((F.adaptive_avg_pool2d(src, (h, w))[0] - 127.5) * 0.0078125).permute(1, 2, 0).contiguous().numpy()
-            d, X = pnet_maps(lvl, t)
-            n, k = mtile_hits(d + (A * X + B) >= dthr)
+            d, X, S = pnet_maps(lvl, t, ghat)
+            n, k = mtile_hits(d + (S + B) >= dthr)           # the kernel's rule: per-input weights
+            _, kx = mtile_hits(d + (A * X + B) >= dthr)      # the rule it replaced: E = A X + B
             _, k0 = mtile_hits(d >= dthr)
-            tot += n; hit_s += k; hit_0 += k0
+            tot += n; hit_s += k; hit_m += kx; hit_0 += k0; cells += int((d + (S + B) >= dthr).sum())
     return dict(config=cfg_id, frames=len(clip), shape=[cfg["H"], cfg["W"]], min_face=cfg["min_face"], mtiles=tot,
-                confirmed_screen=hit_s, confirmed_share=hit_s / tot, prefilter_only=hit_0, prefilter_share=hit_0 / tot)
+                confirmed_screen=hit_s, confirmed_share=hit_s / tot, confirmed_max_rule=hit_m, confirmed_share_max_rule=hit_m / tot,
+                flagged_cells=cells, prefilter_only=hit_0, prefilter_share=hit_0 / tot)
 
 
 def main():
@@ -146,9 +186,10 @@ def main():
     from truely_amd import weights
     t = weights.unpack_tensors(weights.synthetic_blob(0))
     A, B, ok = screen_bound(t)
-    res = dict(A=A, B=B, screen_on=ok, dthr_thr0_0p6=math.log(1.5) - 0.05, results=[])
+    _g, ghat, _B, _ok = screen_weights(t)
+    res = dict(A=A, B=B, ghat=ghat, screen_on=ok, dthr_thr0_0p6=math.log(1.5) - 0.05, results=[])
     for c in (int(v) for v in args.configs.split(",")):
-        r = audit(c, args.frames, t, A, B)
+        r = audit(c, args.frames, t, A, B, ghat)
         print(json.dumps(r), flush=True)
         res["results"].append(r)
     print(f"A = {A:.6g}  B = {B:.6g}")

@@ -1033,6 +1033,12 @@ int trl_debug_pnet_screen_bound(trl_ctx* c, float* A, float* B, int* on) {
     return TRL_OK;
 }
 
+int trl_debug_pnet_screen_weights(trl_ctx* c, float* h_g16) {
+    if (!c || !h_g16) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
+    for (int i = 0; i < 16; i++) h_g16[i] = c->pnet_scrG[i];
+    return TRL_OK;
+}
+
 int trl_debug_batch_capacity(trl_ctx* c, float t2_per_frame, float t3_per_frame, int* last_attempts) {
     if (!c) { trl_set_error("null context"); return TRL_ERR_INVALID; }
     if (t2_per_frame > 0.f) c->caps.t_per_frame[0] = t2_per_frame;

@@ -88,6 +88,7 @@ struct trl_ctx {
     int pnet_mono1 = 0;              // conv1 PReLU slopes all >= 0
     int pnet_unit = 0;               // no PNet PReLU slope above 1 (negative ones allowed): prelu(v) == max(v, s v)
     float pnet_scrA = 0.f, pnet_scrB = 0.f;   // fp16 conv3 screen of the fused PNet: |d_screen - d_exact| <= A X + B (trl_pnet_prepare)
+    float pnet_scrG[16] = {};        // the bound the kernel applies: sum over the cell's 3x3x16 inputs of pnet_scrG[channel] |x|, + B (sum of the 144 coefficients <= A)
     int pnet_screen_ok = 0;          // the conv3 weights fit fp16 (else the screen is off for this net)
     int pnet_screen = 1;             // trl_debug_option "pnet_screen": 0 = every M-tile takes the exact f32 path
     int pnet_run = 0;                // > 0: tiles per cursor fetch of the fused PNet launch (trl_debug_pnet_run); 0 = automatic

@@ -41,9 +41,9 @@ constexpr int REGION_B = P1_T * P1_T * 10 + 224;     // 4000 floats of pooled co
 static_assert(3 * 7 * 256 <= REGION_A, "input tile (+ the 28 overhang pixels of the 7x256 copy) fits region A");
 static_assert(P1_T * P1_T * 10 <= REGION_B, "pooled tile fits region B");
 // Phase 3 reuses region B (dead between conv2 and the next tile's conv1) for the fp16 screen's activation operands: the conv2 tile
-// in fp16 as [half of the channels][324 cells][8] (16 bytes per item: one aligned ds_read_b128 per tap), then the largest |x| of
-// every item as [2][324] floats, from float offset SCR_XM.
-constexpr int SCR_XM = 2 * C2_T * C2_T * 4;          // 2592 floats of fp16 tile in front of the maxima
+// in fp16 as [half of the channels][324 cells][8] (16 bytes per item: one aligned ds_read_b128 per tap), then the error weight
+// m = sum of g[channel] |x| of every item as [2][324] floats, from float offset SCR_XM.
+constexpr int SCR_XM = 2 * C2_T * C2_T * 4;          // 2592 floats of fp16 tile in front of the error weights
 // Horizontal carry between consecutive tiles of a tile row (a workgroup takes RUNS of consecutive tiles): the right-most 4 pooled
 // columns and 2 conv2 columns of tile (ty, tx) ARE the left-most ones of tile (ty, tx + 1) -- the halo that 16x16-cell tiles
 // otherwise compute twice (conv1 x1.56, conv2 x1.27 of the useful work).  They are kept in LDS across the tile boundary, and a tile
@@ -89,7 +89,8 @@ struct PnetArgs {
     const float *b1, *b2, *b3, *bh, *s1, *s2, *s3;
     float thr; int rec_stride;                 // record slots per frame (LvLayout::S)
     float dthr;                                // logit-difference prefilter: no cell with logit1 - logit0 < dthr can reach thr (-inf: off)
-    float scrA, scrB; int screen;              // fp16 conv3 screen: |d_screen - d_exact| <= scrA X + scrB (screen = 0: every M-tile exact)
+    float scrB; int screen;                    // fp16 conv3 screen: |d_screen - d_exact| <= sum over the cell's 3x3x16 inputs of scrG[channel] |x| + scrB
+    float scrG[16];                            // (screen = 0: every M-tile exact)
     int dbg_skip;                              // timing-only ablation mask (TRL_PNET_SKIP); read by the DBG instantiation only
     int32_t* lvl_cnt; Cand* lvl_rec; int32_t* flags;
     int32_t* xcd_next;                         // per-XCD dynamic tile cursor (8 counters, zeroed before the launch)
@@ -736,7 +737,8 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
         stamp(5);
 
         // The screen's activation operands, once per tile: RA's 324 x 16 conv2 values rounded to fp16 (the same plain cast screen()
-        // applied per tap and M-tile, about eight times per cell) into XH, and the largest |x| of each cell's 8-channel half into XM.
+        // applied per tap and M-tile, about eight times per cell) into XH, and the error weight m = sum of g[channel] |x| over each cell's
+        // 8-channel half into XM (g: pnet_screen_bound's per-channel coefficients; eight fmaf, the order every cell's sum is taken in).
         // Both live in RB: its last readers are phase 2's copy_pooled / copy_rows and conv2's A operands, all in front of the barrier
         // above, and its next writer is the next tile's phase 1 (copy_pooled / copy_rows in, then the units), two barriers on; phase 1
         // rewrites all 400 x 10 pooled words of every tile, whatever it carries (strip columns 0..3 and / or rows 0..3 copied in, the
@@ -744,27 +746,35 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
         // finite.  Beyond it: a word of XH has an fp16 in its upper half, whose five exponent bits and top three mantissa bits
         // are the f32's exponent, so a finite or infinite fp16 (mantissa bits 000 under an all-ones exponent at most) never makes
         // it 255 -- only the fp16 NaN of a conv2 value that is already a NaN can; XM is clamped to the largest finite float, which
-        // changes no decision: every X above 65504 confirms its M-tile.  The zeroed tail RB[4000..] that the k padding of the
+        // changes no decision: every |x| above 65504 confirms its M-tile.  The zeroed tail RB[4000..] that the k padding of the
         // last cells reaches is not touched.
-        // Item i = 324 half + cell, thread t takes t, t + 256, t + 512: consecutive lanes read RA 17 floats apart and write
-        // consecutive 16-byte / 4-byte slots.  In front of the next tile's prefetch: its 21 registers are not live yet.
+        // Item i = 324 half + cell.  Thread t takes cell t of half 0, cell t of half 1, then cells 256..323: waves 0, 1 their half 0,
+        // waves 2, 3 their half 1.  Consecutive lanes read RA 17 floats apart and write consecutive 16-byte / 4-byte slots.  In front
+        // of the next tile's prefetch: its 21 registers are not live yet.
         if (a.screen) {
-            static_assert(SCR_XM + 2 * 324 <= P1_T * P1_T * 10, "fp16 conv2 tile + maxima stay inside the pooled tile");
+            static_assert(SCR_XM + 2 * 324 <= P1_T * P1_T * 10, "fp16 conv2 tile + error weights stay inside the pooled tile");
 #pragma unroll
             for (int p = 0; p < 3; p++) {
-                int i = ctid + 256 * p;
-                if (p == 2) i = i < 2 * 324 ? i : 2 * 324 - 1;          // (the spare threads repeat the last item: same values, no branch)
-                const float* src = RA + (i < 324 ? i * C2_LD : (i - 324) * C2_LD + 8);
+                // the channel half is uniform per wave, so its eight error weights are scalar operands (loaded from the argument block)
+                const int half = p < 2 ? p : wave >> 1;
+                int cell = ctid;
+                if (p == 2) { cell = ctid & 127; cell = 256 + (cell < 324 - 256 ? cell : 324 - 256 - 1); }   // (the spare threads repeat the last cell: same values, no branch)
+                const int i = 324 * half + cell;
+                const float* src = RA + cell * C2_LD + 8 * half;
+                const float* gs = a.scrG + 8 * half;
                 f16x8 hv;
-                float m = 0.f;
+                float m = 0.f, mx = 0.f;
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
-                    const float v = src[j];
-                    m = fmaxf(m, fabsf(v));
+                    const float v = src[j], av = fabsf(v);
+                    mx = fmaxf(mx, av);
+                    m = __builtin_fmaf(gs[j], av, m);
                     hv[j] = (_Float16)v;
                 }
                 *reinterpret_cast<f16x8*>(RB + 4 * i) = hv;
-                RB[SCR_XM + i] = fminf(m, 3.402823466e38f);
+                // the overflow rule, explicit: an item with an |x| beyond fp16 (or a sum that is not a finite float: a NaN input) stores
+                // the largest finite float -- no f32 infinity in region B; screen()'s E then reaches that value and the M-tile confirms
+                RB[SCR_XM + i] = mx > 65504.f ? 3.402823466e38f : fminf(m, 3.402823466e38f);
                 __builtin_amdgcn_sched_barrier(0);
             }
             __syncthreads();   // (uniform: a.screen is a kernel argument)
@@ -893,11 +903,12 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
             bool cf0 = has0, cf1 = has1;                        // M-tiles that take the exact f32 path
             // fp16 screen: conv3 of each M-tile on v_mfma_f32_32x32x16_f16, one instruction per 3x3 tap
             // (K = the 16 conv2 channels), in the transposed layout of conv3 below -- lane l: cell l & 31, channels
-            // 8 (q >> 2) + (q & 3) + 4 hh.  The activations come from the tile's fp16 copy in region B (one 16-byte read per tap, the |x|
-            // maximum of the same eight values beside it), the weights are rounded from LDS as they are read.  Then PReLU and
+            // 8 (q >> 2) + (q & 3) + 4 hh.  The activations come from the tile's fp16 copy in region B (one 16-byte read per tap, the
+            // error weight of the same eight values beside it), the weights are rounded from LDS as they are read.  Then PReLU and
             // the logit difference d (one 16-term chain per half, the halves added): an M-tile is confirmed when some valid cell
-            // has d + A X + B >= dthr (X: the cell's largest |conv2 input|), d is not finite or X exceeds fp16.  A cell the exact
-            // path would let through the prefilter (d_exact >= dthr) always confirms its M-tile, so the records are unchanged.
+            // has d + E >= dthr (E = sum over the cell's 3x3x16 conv2 inputs of g[channel] |x|, + B), d is not finite or an input
+            // exceeds fp16.  A cell the exact path would let through the prefilter (d_exact >= dthr) always confirms its M-tile, so
+            // the records are unchanged.
             if (has0 && a.screen) {
                 const int sb0 = 324 * hh + (mt0 * 2 + (l31 >> 4)) * C2_T + (l31 & 15);   // item of the lane's cell and channel half (XH / XM above)
                 auto screen = [&](int mt, int sb) __attribute__((always_inline)) {
@@ -908,7 +919,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
 #pragma unroll
                         for (int qb = 0; qb < 4; qb++) S[4 * qa + qb] = b4[qb];
                     }
-                    float xm = 0.f;
+                    float em = 0.f;
 #pragma unroll
                     for (int tap = 0; tap < 9; tap++) {
                         const int to = (tap / 3) * C2_T + tap % 3;
@@ -916,7 +927,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
 #pragma unroll
                         for (int j = 0; j < 8; j++) wv[j] = (_Float16)B3S[(tap * 16 + 8 * hh + j) * 32 + l31];
                         const f16x8 xv = *reinterpret_cast<const f16x8*>(RB + 4 * (sb + to));
-                        xm = fmaxf(xm, RB[SCR_XM + sb + to]);
+                        em += RB[SCR_XM + sb + to];
                         S = __builtin_amdgcn_mfma_f32_32x32x16_f16(wv, xv, S, 0, 0, 0);
                     }
                     float part = 0.f;
@@ -928,12 +939,13 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
                             part = __builtin_fmaf(w4[qb], prelu_t<UNIT>(S[4 * qa + qb], s4[qb], UNIT ? 0.f : trl_prelu_sel(s4[qb])), part);
                     }
                     const auto pp = __builtin_amdgcn_permlane32_swap(__float_as_uint(part), __float_as_uint(part), false, false);
-                    const auto px = __builtin_amdgcn_permlane32_swap(__float_as_uint(xm), __float_as_uint(xm), false, false);
+                    const auto px = __builtin_amdgcn_permlane32_swap(__float_as_uint(em), __float_as_uint(em), false, false);
                     const float d = (part + __uint_as_float(pp[1])) + T3all[104];
-                    const float X = fmaxf(xm, __uint_as_float(px[1]));
-                    const float E = __builtin_fmaf(a.scrA, X, a.scrB);
+                    // E = the 18 error weights of the cell's field + B; an item beyond fp16 stored the largest finite float, so E is
+                    // at least that (or overflows): every such cell confirms, as does one whose E a finite float cannot hold
+                    const float E = (em + __uint_as_float(px[1])) + a.scrB;
                     const int oy = ty * TS + mt * 2 + (lane >> 4), ox = tx * TS + (lane & 15);
-                    const bool hit = !(d + E < a.dthr) || !(fabsf(d) <= 3.402823466e38f) || X > 65504.f;
+                    const bool hit = !(d + E < a.dthr) || !(fabsf(d) <= 3.402823466e38f) || !(E < 3.402823466e38f);
                     return __builtin_amdgcn_ballot_w64(lane < 32 && oy < g.oh && ox < g.ow && hit) != 0;
                 };
                 cf0 = screen(mt0, sb0);
@@ -1004,14 +1016,23 @@ __global__ void k_pnet_span(unsigned long long* clk) {
 // difference head one 36-term chain over f32(w1 - w0).  Double precision, then A and B rounded up (tools/pnet_screen_audit.py
 // states the same bound, tests/test_pnet_screen_cpu.py compares the two).  W [144][32], H [32][32] (zero padded), b3, s3, bh: the
 // loader's host copies of conv3.w, heads.w, conv3.b, prelu3, heads.b.
+// Every term of A is a sum over the inputs k = (tap, channel) of a non-negative coefficient times X, and X enters only as the
+// bound |x_k| <= X: with the coefficients kept apart, |d_screen - d_exact| <= sum_k g_k |x_k| + B, sum_k g_k = A.  The kernel uses
+// g^[channel] = max over the nine taps of g_(tap, channel) (pnet_scrG), so that sum_k g^ |x_k| is a sum over the field's nine
+// conv2 cells of one number per cell and channel half.  g^ is multiplied by the same 1 + 2^-10 as A and B and rounded up to float.
+// That factor also has to cover the kernel's own f32 roundings of E, all of them in sums of non-negative terms: 8 for a cell half's
+// eight fmaf, 8 for the nine halves of a lane, 1 for the two lanes' sums, 1 for + B -- no term passes more than 18 roundings, a
+// relative loss below 18 * 2^-24 = 2^-19.8 against the 2^-10 granted (d + E is compared without a subtraction, as before).
 static void pnet_screen_bound(trl_ctx* c, const float* W, const float* H, const float* b3, const float* s3, const float* bh) {
     c->pnet_screen_ok = 0; c->pnet_scrA = c->pnet_scrB = __builtin_inff();
+    for (int i = 0; i < 16; i++) c->pnet_scrG[i] = __builtin_inff();
     for (int i = 0; i < 144 * 32; i++) if (!(fabsf(W[i]) <= 65504.f)) return;   // a weight fp16 cannot hold: no screen for this net
     const double u = ldexp(1.0, -24), uh = ldexp(1.0, -11), tiny = ldexp(1.0, -14);
     auto gamma = [](int n, double uu) { return n * uu / (1.0 - n * uu); };
     const double ge = gamma(145, u), gs = gamma(145, 2 * u), g35 = gamma(35, u), g36 = gamma(36, u);
     double Sa = 0, Sb = fabs((double)bh[0]) + fabs((double)bh[1]);
     double ad = 0, bd = 0, wdP_a = 0, wdP_b = 0;
+    double g[144] = {};                            // A's terms, per input k
     for (int co = 0; co < 32; co++) {
         double W1 = 0, D = 0;
         for (int k = 0; k < 144; k++) {
@@ -1029,12 +1050,23 @@ static void pnet_screen_bound(trl_ctx* c, const float* W, const float* H, const 
         Sa += (fabs(w0) + fabs(w1)) * aP; Sb += (fabs(w0) + fabs(w1)) * bP;
         ad += wd * ap; bd += wd * bp;
         wdP_a += wd * (aP + ap); wdP_b += wd * (bP + bp);
+        for (int k = 0; k < 144; k++) {            // the same a3, aM, ap, aP with (|w_k|, D_k) in place of (W1, D)
+            const double w = W[k * 32 + co], aw = fabs(w), Dk = aw < tiny ? aw : fabs((double)(float)(_Float16)W[k * 32 + co] - w);
+            const double a3k = Dk * (1 + uh) + aw * uh + gs * (aw + Dk) * (1 + uh) + ge * aw, aMk = aw * (1 + ge);
+            const double apk = L * (1 + u) * a3k + 2 * u * L * aMk, aPk = L * (1 + u) * aMk;
+            g[k] += g35 * (fabs(w0) + fabs(w1)) * aPk + wd * apk + g36 * (1 + u) * wd * (aPk + apk);
+        }
     }
     ad += g36 * (1 + u) * wdP_a;
     bd += g36 * (1 + u) * (fabs((double)bh[1] - (double)bh[0]) + wdP_b);
     const double A = (g35 * Sa + ad) * (1 + ldexp(1.0, -10)), B = (g35 * Sb + bd) * (1 + ldexp(1.0, -10));
     auto up = [](double v) { float f = (float)v; return (double)f < v ? nextafterf(f, __builtin_inff()) : f; };
     c->pnet_scrA = up(A); c->pnet_scrB = up(B); c->pnet_screen_ok = 1;
+    for (int ci = 0; ci < 16; ci++) {
+        double m = 0;
+        for (int tap = 0; tap < 9; tap++) m = fmax(m, g[tap * 16 + ci]);
+        c->pnet_scrG[ci] = up(m * (1 + ldexp(1.0, -10)));
+    }
 }
 
 // PNet's layers in c->mt (trl_resolve_nets has checked their shapes: [27][10], [90][16], [144][32], [32][6], each in 32 columns)
@@ -1087,7 +1119,8 @@ static void fill_args(trl_ctx* c, int n, int H, int W, const PyrLayout& lay, con
     // p = softmax(logit0, logit1)[1] >= thr needs logit1 - logit0 >= ln(thr / (1 - thr)) up to the rounding of the float softmax
     // (~1e-6 relative); 0.05 below that bound the probability is short of thr by 0.05 thr (1 - thr) >= 4.9e-4 for thr in [0.01, 0.99]
     a.dthr = (a.thr >= 0.01f && a.thr <= 0.99f) ? (float)(log((double)a.thr / (1.0 - (double)a.thr)) - 0.05) : -__builtin_inff();
-    a.scrA = c->pnet_scrA; a.scrB = c->pnet_scrB; a.screen = c->pnet_screen && c->pnet_screen_ok;
+    a.scrB = c->pnet_scrB; a.screen = c->pnet_screen && c->pnet_screen_ok;
+    for (int i = 0; i < 16; i++) a.scrG[i] = c->pnet_scrG[i];
     a.dbg_skip = trl_tune_int("TRL_PNET_SKIP", 0);
     a.lvl_cnt = c->cb.lvl_cnt; a.lvl_rec = c->cb.lvl_rec; a.flags = c->cb.flags;
     a.clk = c->pnet_clk; a.prof = c->pnet_prof ? 1 : 0;

@@ -484,6 +484,13 @@ class Engine:
         _lib.check(self.lib.trl_debug_pnet_screen_bound(self._h, C.byref(A), C.byref(B), C.byref(on)))
         return float(A.value), float(B.value), bool(on.value)
 
+    def pnet_screen_weights(self):
+        """Test hook: the sixteen per-channel error weights g of the screen's bound, E = sum of g[channel] |x| over a cell's
+        3 x 3 x 16 conv2 inputs + B."""
+        g = (C.c_float * 16)()
+        _lib.check(self.lib.trl_debug_pnet_screen_weights(self._h, g))
+        return [float(v) for v in g]
+
     def pnet_run(self, run: int = 0):
         """Test / tuning hook: tiles per cursor fetch of the fused PNet launch (0 = automatic); > 1 exercises the halo carry."""
         _lib.check(self.lib.trl_debug_pnet_run(self._h, int(run)))

@@ -673,6 +673,43 @@ int    trl_gallery_search_groups(const float* d_q, const uint8_t* d_valid, int n
                                  const int32_t* d_gid, long long m, int metric, int k, float* d_score, int32_t* d_index,
                                  int32_t* d_group, void* d_ws, size_t ws_bytes, int max_strip_cols, void* stream);
 
+/* ---- Face tracks ("which face of this frame is which face of the last one") ------------------------------------------------------
+ * Association of every face of a clip's sampled frames into tracks, with the drift state machine of trl_drift_update per track
+ * instead of per largest face.  Context-free, caller-owned memory, work queued on `stream`, no synchronisation, the device that of
+ * d_state.  (ABI v7, additive.)  The rules are DESIGN.md section 2, "Tracks"; in short, per frame of the window and in this order:
+ *   ageing    a track whose last matched frame lies more than max_age frames before the previous frame ends (INT32_MAX: never)
+ *   pairs     every (live track, detection): iou = torchvision's box_iou in float32; with d_emb, sim = drift_sims_kernel's cosine
+ *             of the detection's row and the row of the track's last matched detection.  Admissible iff (iou_min <= 0 or
+ *             iou >= iou_min) and (no d_emb or sim >= sim_min); NaN fails.  The key is sim with d_emb, iou without.
+ *   matching  greedy: the admissible pair of an unmatched track and an unmatched detection with the largest key, ties to the lower
+ *             track id, then the lower detection index; repeat
+ *   matched   the track takes the detection's box and row and, with d_emb, makes one state-machine step with the pair's sim
+ *   new       every unmatched detection, in ascending index, starts the track with the next id (0, 1, 2, ... over the clip) in the
+ *             free slot of the lowest index, else in the slot of the track not matched or created in this frame with the smallest
+ *             last frame (ties: smallest id), which ends
+ * A frame's detections past its first TRL_TRACK_SLOTS get no track and are counted as dropped.
+ *   d_state   TRL_TRACK_STATE_BYTES, 8-byte aligned, zero-filled before a clip's first window; the layout is private.  One clip
+ *             is tracked with d_emb in every window or in none.
+ *   window    d_counts [n] int32 faces per frame; d_boxes [m][4] f32 x1, y1, x2, y2 and d_emb [m][512] f32 (or NULL) hold the
+ *             frames' rows one after the other; rows past the sum of d_counts are not read.  Frame t of the window is the clip's
+ *             frame (frames seen by earlier calls) + t.  n = 0 and m = 0 are legal: frames without faces still age the tracks.
+ *   outputs   d_track [m] int32 (the row's track id, -1 for none), d_sim [m] f32 (the matched pair's sim; 2.0 = no comparison: a new
+ *             track, a dropped row, or no d_emb), d_flag [m] u8 (the state machine's flag).  Rows past the sum: -1 / 2.0 / 0.
+ *   d_table   [table_cap][8] int32, row = track id: first_frame, last_frame, n_obs, run, hits, slot (-1 once the track has ended),
+ *             0, 0; written whenever a frame touches the track.  A track whose id is >= table_cap is tracked all the same, its
+ *             row is not written, and the state counts it; nothing is written past the table.
+ * The outputs depend on the inputs and the rules alone: not on how the clip is cut into windows, the stream or launch geometry. */
+#define TRL_TRACK_SLOTS 64
+#define TRL_TRACK_STATE_BYTES 135200
+int    trl_track_update(void* d_state, const float* d_boxes, const int32_t* d_counts, int n, int m, const float* d_emb, float iou_min,
+                        float sim_min, int max_age, int32_t* d_track, float* d_sim, uint8_t* d_flag, int32_t* d_table, int table_cap,
+                        void* stream);
+/* d_score [table_cap] int32: per row the score of trl_drift_score from that track's run and hits and the clip's frame_count and
+ * fps (rows of ids not yet created: 0).  d_summary [4] int32: the clip's score (the largest; 0 without a track), the id of the
+ * track that has it (the lowest among equals, -1 without a track), the number of tracks created, the dropped detections. */
+int    trl_track_scores(const void* d_state, const int32_t* d_table, int table_cap, long long frame_count, int fps, int32_t* d_score,
+                        int32_t* d_summary, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,13 +2,14 @@
 (server/model.py::run of the reference): MTCNN detect -> largest-face crop -> FaceNet
 (InceptionResnetV1) embedding -> consecutive-frame cosine drift -> 0..100 score -- and, for the embeddings,
 FaceGallery / pairwise / cluster_embeddings: enrolment, distance tables, top-k identification, DBSCAN clustering and score
-histograms (threshold calibration: roc_from_counts / threshold_at_far) on the device.
+histograms (threshold calibration: roc_from_counts / threshold_at_far) on the device; FaceTracker associates every face of a
+clip's frames into tracks and keeps the drift state machine per person.
 
 Importable as ``truely_amd`` (see truely_amd.py at the repository root; the directory name
 required by the build contract is not a valid Python identifier)."""
 from . import weights, synthetic  # noqa: F401  (pure numpy, usable without a GPU)
 
-__all__ = ["weights", "synthetic", "Engine", "MTCNN", "InceptionResnetV1", "FaceGallery", "pairwise", "cluster_embeddings", "roc_from_counts", "threshold_at_far", "run", "analyze_video"]
+__all__ = ["weights", "synthetic", "Engine", "MTCNN", "InceptionResnetV1", "FaceGallery", "FaceTracker", "pairwise", "cluster_embeddings", "roc_from_counts", "threshold_at_far", "run", "analyze_video"]
 
 
 def __getattr__(name):
@@ -25,6 +26,9 @@ def __getattr__(name):
     if name in ("FaceGallery", "pairwise", "cluster_embeddings", "roc_from_counts", "threshold_at_far"):
         from . import gallery
         return getattr(gallery, name)
+    if name == "FaceTracker":
+        from .tracker import FaceTracker
+        return FaceTracker
     if name in ("run", "analyze_video"):
         from . import model
         return getattr(model, name)

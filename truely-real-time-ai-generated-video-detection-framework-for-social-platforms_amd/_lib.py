@@ -131,6 +131,8 @@ _SIGNATURES = {
     "trl_gallery_search_groups_workspace": (C.c_size_t, [_i, C.c_longlong, _i, _i]),
     "trl_gallery_search_groups": (C.c_int, [_vp, _vp, _i, _vp, C.c_longlong, _vp, _vp, C.c_longlong, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t,
                                             _i, _vp]),
+    "trl_track_update": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "trl_track_scores": (C.c_int, [_vp, _vp, _i, C.c_longlong, _i, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -233,6 +233,31 @@ __device__ __forceinline__ float trl_wave_dot512(const float* a, const float* b,
     for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
     return s;
 }
+// server/model.py:86-95 in double, like the reference's Python floats: the 0..100 score of a state machine that stands at
+// (hits, run) in a clip of frame_count frames; *total receives the clip's sampled-frame count (0 where model.py returns early).
+// drift_scan_kernel's score and k_track_scores' per-track score are this function.
+__device__ __forceinline__ int trl_drift_score_value(int hits, int run, long long frame_count, int fps, long long* total) {
+    const int thr_frames = 15;     // model.py:17
+    int score = 0;
+    *total = 0;
+    if (frame_count > 0 && fps > 0) {
+        int step = (int)((double)fps / 7.0);
+        if (step < 1) step = 1;
+        *total = (frame_count + step - 1) / step;
+        if (*total > 0) {
+            double pct = ((double)hits / (double)*total) * 100.0;
+            double conf = pct * ((double)run / (double)thr_frames);
+            if (conf > 100.0) conf = 100.0;
+            const double w = (frame_count > (long long)fps * 30) ? 0.5 : 0.3;
+            double ws = pct + conf * w;
+            if (ws > 100.0) ws = 100.0;
+            score = (int)ws;
+            if (score < 0) score = 0;
+            if (score > 100) score = 100;
+        }
+    }
+    return score;
+}
 // facenet-pytorch extract_face() for tensor input, one output pixel (ox, oy): imresample (area = adaptive average pooling) of the
 // iw x ih crop at (x0, y0) of the u8 frame fp [.][W][3] to S x S -- bins [floor(o*n/S), ceil((o+1)*n/S)), (float)sum / kh / kw --
 // then .byte() (truncation).  v receives the three channels in the frame's order.  Shared by k_crop_area_std and k_extract.

@@ -813,24 +813,8 @@ __global__ __launch_bounds__(256) void drift_scan_kernel(const float* __restrict
     }
     if (threadIdx.x == 0) {
         if (st) { st->run = run; st->hits = hits; if (last_valid >= 0) st->has_prev = 1; }
-        int score = 0;
         long long total = 0;
-        if (frame_count > 0 && fps > 0) {
-            int step = (int)((double)fps / 7.0);
-            if (step < 1) step = 1;
-            total = (frame_count + step - 1) / step;
-            if (total > 0) {
-                double pct = ((double)hits / (double)total) * 100.0;
-                double conf = pct * ((double)run / (double)thr_frames);
-                if (conf > 100.0) conf = 100.0;
-                const double w = (frame_count > (long long)fps * 30) ? 0.5 : 0.3;
-                double ws = pct + conf * w;
-                if (ws > 100.0) ws = 100.0;
-                score = (int)ws;
-                if (score < 0) score = 0;
-                if (score > 100) score = 100;
-            }
-        }
+        const int score = trl_drift_score_value(hits, run, frame_count, fps, &total);
         result[0] = score; result[1] = run; result[2] = hits; result[3] = (int32_t)total;
     }
 }

@@ -185,6 +185,17 @@ class Engine:
             out["valid"] = (status == 1).to(torch.uint8)
         return out
 
+    def track_faces(self, frames, tracker, **extract_kwargs) -> dict:
+        """Every face of a window of sampled frames, embedded and associated with the clip's tracks: ``extract_faces(frames,
+        keep_all=True, **extract_kwargs)``, ``facenet_embed`` of its faces, ``tracker.update(box, counts, emb)`` (a
+        :class:`~truely_amd.tracker.FaceTracker` that has seen the clip's earlier windows).  Returns the extraction's dict plus
+        ``emb`` [m, 512], ``track`` [m], ``sim`` [m], ``flag`` [m]."""
+        out = self.extract_faces(frames, keep_all=True, **extract_kwargs)
+        emb = self.facenet_embed(out["faces"].permute(0, 2, 3, 1))
+        out["emb"] = emb
+        out.update(tracker.update(out["box"], out["counts"], emb))
+        return out
+
     # server/model.py:59 for a batch; faces f32 (n, h, w, 3) NHWC in [0,1]
     def facenet_embed(self, faces: torch.Tensor) -> torch.Tensor:
         faces = faces.to(self.device, torch.float32).contiguous()

@@ -1,0 +1,139 @@
+"""Face tracks on the GPU: which face of this sampled frame is which face of the last one, and the drift score per person.
+
+    trk = FaceTracker(iou_min=0.1, sim_min=0.4, max_age=3)
+    for window in clip:                                           # consecutive windows of ONE clip
+        d = engine.extract_faces(window, keep_all=True)
+        out = trk.update(d["box"], d["counts"], engine.facenet_embed(d["faces"].permute(0, 2, 3, 1)))
+    trk.tracks(frame_count, fps)                                  # per track: id, first_frame, last_frame, n_obs, run, hits, score
+    trk.score(frame_count, fps)                                   # the clip's multi-face score: the maximum over its tracks
+
+``Engine.track_faces(frames, tracker)`` is the three calls of the loop body.  ``run()`` / ``analyze_video`` do not use this: they
+keep the reference's largest-face drift (``Engine.drift_update``), in which two people in one clip read as drift.
+
+The rules ("Tracks"; csrc/trl_tracks.h is their code, tests/track_ref.py their reference).  One update takes a
+window of n consecutive sampled frames: ``counts[n]`` and the window's detections as flat rows, frame by frame in detect's order --
+``boxes[m][4]`` (x1, y1, x2, y2) and optionally ``emb[m][512]`` -- the layout of ``extract_faces(keep_all=True)``.  Frame t of the
+window has absolute index ``frames_seen + t``.  A tracker has 64 slots; track ids are 0, 1, 2, ... in order of creation over the
+clip; a frame's detections past its first 64 get track -1 and are counted as dropped.
+
+    sim    the drift kernels' cosine: dot512(det, trk) / (sqrtf(dot512(det, det)) * sqrtf(dot512(trk, trk))), dot512 one wave's
+           fmaf chains and xor butterfly; trk is the embedding of the track's last matched detection
+    iou    torchvision's box_iou in float32, one rounding per operation
+
+Per frame f, in order:
+ 1. ageing: a track is live iff ``f - last_frame - 1 <= max_age`` (``2**31 - 1``: always); the others end, their slots are free
+ 2. a (live track, detection) pair is admissible iff ``iou_min <= 0 or iou >= iou_min`` and, with embeddings, ``sim >= sim_min``
+    (float32; NaN fails both; ``sim_min = -inf`` passes everything but NaN).  Its key is sim with embeddings, iou without.
+ 3. greedy matching: repeatedly the admissible pair of an unmatched track and an unmatched detection with the largest key; ties to
+    the lower track id, then the lower detection index
+ 4. a matched track takes the detection's box and embedding, ``last_frame = f``, ``n_obs += 1``, and with embeddings makes one
+    step of model.py's state machine with the pair's sim: ``run = run + 1 if sim < 0.99f else 0; run > 15: hits += 1, flag = 1``.
+    The detection's ``sim`` is the pair's (2.0 without embeddings).
+ 5. unmatched detections, in ascending index, each start a track with the next id in the free slot of the lowest index -- without
+    one, in the slot of the track not matched or created in this frame with the smallest last_frame (ties: smallest id), which
+    ends.  Output ``sim = 2.0`` ("no comparison", the drift kernels' sentinel), ``flag = 0``.
+ 6. every track touched writes its row of the track table
+
+A track's score is model.py:86-95 with the track's run and hits and the clip's frame_count and fps; the clip's is the maximum.  A
+clip with at most one face per frame, ``iou_min = 0``, ``sim_min = -inf``, ``max_age = 2**31 - 1`` and no NaN similarity has one
+track with, bit for bit, ``Engine.drift_update``'s sims, flags, run, hits and score.
+
+The defaults of ``iou_min``, ``sim_min`` and ``max_age`` are PLACEHOLDERS, not calibrated figures: no real checkpoint has been
+measured.  ``FaceGallery.calibrate`` on labelled embeddings of the checkpoint in use is the way to a ``sim_min``."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+SLOTS = 64
+STATE_BYTES = 135200
+INT32_MAX = 2 ** 31 - 1
+TABLE_COLUMNS = ("first_frame", "last_frame", "n_obs", "run", "hits", "slot")
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+
+
+class FaceTracker:
+    """The tracks of ONE clip (``reset()`` starts another).  State, table and outputs live on the device; ``update`` queues one
+    kernel on the current stream and does not synchronise."""
+
+    def __init__(self, iou_min: float = 0.1, sim_min: float = 0.4, max_age: int = 3, device=None):
+        if not (0 <= int(max_age) <= INT32_MAX):
+            raise ValueError("max_age must be in 0 .. 2**31 - 1")
+        if np.isnan(iou_min) or np.isnan(sim_min):
+            raise ValueError("iou_min / sim_min must not be NaN")
+        self.iou_min, self.sim_min, self.max_age = float(iou_min), float(sim_min), int(max_age)
+        self.lib = _lib.load()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("a FaceTracker lives on a GPU")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._state = torch.zeros((STATE_BYTES // 8,), dtype=torch.int64, device=self.device)
+        self._table = torch.zeros((256, 8), dtype=torch.int32, device=self.device)
+        self._id_bound = 0                                # next_id <= this: a row starts at most one track
+
+    def reset(self) -> None:
+        """Forget the clip: the next update is a clip's first window.  No synchronisation."""
+        self._state.zero_()
+        self._table.zero_()
+        self._id_bound = 0
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def update(self, boxes, counts, emb=None) -> dict:
+        """The clip's next window: ``boxes`` (m, 4), ``counts`` (n,), ``emb`` (m, 512) or None (every window of a clip alike).
+        -> ``track`` (m,) int32, ``sim`` (m,) float32, ``flag`` (m,) uint8 on the device."""
+        d = self.device
+        boxes = torch.as_tensor(boxes).to(d, torch.float32).reshape(-1, 4).contiguous()
+        counts = torch.as_tensor(counts).to(d, torch.int32).reshape(-1).contiguous()
+        m, n = boxes.shape[0], counts.shape[0]
+        if emb is not None:
+            emb = torch.as_tensor(emb).to(d, torch.float32).contiguous()
+            if tuple(emb.shape) != (m, 512):
+                raise ValueError(f"expected ({m}, 512) embeddings, got {tuple(emb.shape)}")
+        if self._id_bound + m > self._table.shape[0]:    # grow geometrically; the copy stays on the device
+            old = self._table
+            self._table = torch.zeros((max(2 * old.shape[0], self._id_bound + m), 8), dtype=torch.int32, device=d)
+            self._table[:old.shape[0]].copy_(old)
+        self._id_bound += m
+        track = torch.empty((m,), dtype=torch.int32, device=d)
+        sim = torch.empty((m,), dtype=torch.float32, device=d)
+        flag = torch.empty((m,), dtype=torch.uint8, device=d)
+        _lib.check(self.lib.trl_track_update(_ptr(self._state), _ptr(boxes), _ptr(counts), n, m,
+                                             _ptr(emb), self.iou_min, self.sim_min,
+                                             self.max_age, _ptr(track), _ptr(sim), _ptr(flag), _ptr(self._table), self._table.shape[0],
+                                             self._stream()))
+        return {"track": track, "sim": sim, "flag": flag}
+
+    def _scores(self, frame_count: int, fps: int) -> np.ndarray:
+        """[summary (4), table rows (bound x 8), scores (bound)] as one host array: one synchronisation."""
+        cap, k = self._table.shape[0], self._id_bound
+        score = torch.empty((cap,), dtype=torch.int32, device=self.device)
+        summary = torch.empty((4,), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.trl_track_scores(_ptr(self._state), _ptr(self._table), cap, int(frame_count), int(fps), _ptr(score),
+                                             _ptr(summary), self._stream()))
+        return torch.cat([summary, self._table[:k].reshape(-1), score[:k]]).cpu().numpy()
+
+    def tracks(self, frame_count: int, fps: int) -> dict:
+        """Every track of the clip so far, as host arrays indexed by track id: ``id``, ``first_frame``, ``last_frame``, ``n_obs``,
+        ``run``, ``hits``, ``slot`` (-1 once ended), ``score``; and ``clip_score``, ``clip_track`` (-1 without a track),
+        ``dropped``.  One synchronisation."""
+        a, k = self._scores(frame_count, fps), self._id_bound
+        n = int(a[2])
+        table, score = a[4:4 + 8 * k].reshape(k, 8)[:n], a[4 + 8 * k:][:n]
+        out = {"id": np.arange(n, dtype=np.int32), "score": score.copy()}
+        out.update({name: table[:, c].copy() for c, name in enumerate(TABLE_COLUMNS)})
+        out.update(clip_score=int(a[0]), clip_track=int(a[1]), dropped=int(a[3]))
+        return out
+
+    def score(self, frame_count: int, fps: int) -> int:
+        """The clip's multi-face score: the maximum of its tracks' scores, 0 without a track.  One synchronisation."""
+        return int(self._scores(frame_count, fps)[0])

@@ -589,6 +589,25 @@ size_t trl_cluster_workspace(int n);
 int    trl_cluster_labels(const uint32_t* d_adj, long long pitch_words, const int32_t* d_degree, int n, int min_samples,
                           int32_t* d_labels, uint8_t* d_core, int32_t* d_count, void* d_ws, size_t ws_bytes, int* rounds_out,
                           void* stream);
+/* The label stage over neighbour lists instead of bitmap rows: the same degree / core / cluster / label rules, for up to 16,777,216
+ * rows.  The links are CSR lists: d_offsets [n + 1] int64 (ascending from 0), d_index [offsets[n]] int32, row i's neighbours
+ * index[offsets[i] .. offsets[i + 1]) -- what trl_gallery_range_count / trl_gallery_range_fill write with self = 1; the scores are
+ * not an input.  The lists must be symmetric, without a self entry and without duplicates (the caller guarantees it, as for the
+ * bitmap); d_valid (n bytes, may be null: every row valid) tells a valid row without links (degree 1) from an invalid one (degree 0).
+ * Writes d_degree [n] (list length + 1 of a valid row, 0 of an invalid one), d_labels [n], d_core [n] and *d_count.  An entry of
+ * d_index outside 0 .. n - 1 is skipped and never followed; lists that are not symmetric give unspecified labels, no access out of
+ * bounds, and the rounds still end (labels only decrease).
+ *   lanes_per_row   4, 16 or 64: the lanes of a wave that walk one row's list.  0: chosen from the mean list length offsets[n] / n
+ *                   (4 below 384 entries, else 16: DESIGN section 7, f-8), which is read back first.  The result does not depend on it.
+ * Rounds, *rounds_out, the synchronisation of `stream` and TRL_ERR_STATE as for trl_cluster_labels.  TRL_ERR_INVALID with nothing
+ * queued and nothing written: n < 0 or n > 16,777,216, min_samples < 1, lanes_per_row not 0 / 4 / 16 / 64, a workspace too small or
+ * not 8-byte aligned, a null pointer where one is needed (d_index too unless n = 0; d_valid and rounds_out may be null).
+ * n = 0: *d_count = 0, nothing else. */
+/* Device bytes of trl_cluster_labels_lists' d_ws: three int32 per row and the change flags, nothing per link.  0 on bad arguments. */
+size_t trl_cluster_lists_workspace(int n);
+int    trl_cluster_labels_lists(const long long* d_offsets, const int32_t* d_index, const uint8_t* d_valid, int n, int min_samples,
+                                int lanes_per_row, int32_t* d_degree, int32_t* d_labels, uint8_t* d_core, int32_t* d_count,
+                                void* d_ws, size_t ws_bytes, int* rounds_out, void* stream);
 
 /* ---- Score histograms ("which threshold?") -------------------------------------------------------------------------------------
  * Exact pair counts per score bin, genuine (d_qid[i] == d_gid[j]) and impostor pairs apart, of n query rows against the m gallery

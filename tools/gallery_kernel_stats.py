@@ -20,6 +20,18 @@ rows each, so that there is a graph to label), then 3 + 5 of scores() on the sam
 main loop k_gallery_links shares, is the yardstick.  A row of the table is one kernel: its launches per call and the median over the
 5 measured calls of its time per call (the label kernels run once per round).
 
+Cluster-lists mode (FaceGallery.cluster(method="lists"): range_search() + trl_cluster_labels_lists), the same planted clusters:
+
+    python tools/gallery_kernel_stats.py --cluster-lists out_dir > profiles/cluster_lists_kernel_stats.csv
+    python tools/gallery_kernel_stats.py --cluster-lists-table out_dir
+
+Per n (the cluster mode's and 131,072) and per density -- 16 rows an identity (mean degree 16), 128 and 1,024 -- one process under the same
+trace: 3 + 5 calls of range_search() at cosine 0.5 (the two passes, the row sums and the scan); then, per forced lanes_per_row 4 / 16
+/ 64, 3 + 5 calls of trl_cluster_labels_lists at min_samples 4 on those lists; then, where the bitmap fits (n <= 65,536), 3 + 5 calls
+of cluster(method="bitmap"), whose labels must equal the lists'.  A row of the table is one kernel of one phase: its launches per
+call and the median over the 5 measured calls of its time per call (the hook kernels run once per round).  The auto choice of
+lanes_per_row (cl_list_lanes, csrc/trl_gallery.hip) is read from this table.
+
 Histogram mode (FaceGallery.score_histogram: trl_gallery_hist), the same embeddings, labels = the identities, E = 1000 edges:
 
     python tools/gallery_kernel_stats.py --hist out_dir > profiles/hist_kernel_stats.csv
@@ -57,6 +69,7 @@ import csv
 import glob
 import json
 import os
+import re
 import statistics
 import subprocess
 import sys
@@ -185,6 +198,100 @@ def run_all_cluster(out):
         print(line, file=sys.stderr, flush=True)
         open(os.path.join(d, "info.json"), "w").write(line)
     table_cluster(out)
+
+
+CLL_SHAPES, CLL_PER_ID, CLL_LANES, CLL_BITMAP_MAX_N = CL_SHAPES + (131_072,), (16, 128, 1024), (4, 16, 64), 65_536
+CLL_LIST_KERNELS = ("k_cluster_list_degree", "k_cluster_list_hook", "k_cluster_list_assign")
+CLL_BITMAP_KERNELS = ("k_gallery_links", "k_cluster_degree", "k_cluster_hook", "k_cluster_assign")
+
+
+def run_cluster_lists(n, per_id):
+    import ctypes as C
+    import torch
+    from truely_amd import _lib
+    from truely_amd.gallery import FaceGallery
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    centres = torch.nn.functional.normalize(torch.randn((n // per_id, 512), generator=gen, device="cuda"), dim=1)
+    rows = centres.repeat_interleave(per_id, dim=0) + 0.03 * torch.randn((n, 512), generator=gen, device="cuda")
+    rows = torch.nn.functional.normalize(rows, dim=1)[torch.randperm(n, generator=gen, device="cuda")]
+    gal = FaceGallery(metric="cosine", capacity=n)
+    gal.add(rows, range(n))
+    del rows, centres
+    lib, ptr = gal.lib, lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    calls = CL_WARMUP + CL_WARM
+    torch.cuda.synchronize()
+    for _ in range(calls):
+        off, idx, _sc = gal.range_search(threshold=0.5)
+    del _sc
+    torch.cuda.synchronize()
+    out = [torch.empty((n,), dtype=dt, device="cuda") for dt in (torch.int32, torch.int32, torch.uint8)]
+    count = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    need = lib.trl_cluster_lists_workspace(n)
+    ws = torch.empty((need,), dtype=torch.uint8, device="cuda")
+    rounds, labels = {}, {}
+    for lanes in CLL_LANES:
+        r = C.c_int(0)
+        for _ in range(calls):
+            _lib.check(lib.trl_cluster_labels_lists(ptr(off), ptr(idx), None, n, 4, lanes, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(count),
+                                                    ptr(ws), need, C.byref(r), stream))
+        torch.cuda.synchronize()
+        rounds[lanes], labels[lanes] = r.value, out[1].clone()
+    same, bitmap_rounds = all(torch.equal(labels[4], labels[lanes]) for lanes in CLL_LANES), None
+    if n <= CLL_BITMAP_MAX_N:
+        for _ in range(calls):
+            info = gal.cluster(0.5, min_samples=4, return_info=True, method="bitmap")
+        torch.cuda.synchronize()
+        same, bitmap_rounds = same and torch.equal(info["labels"], labels[4]) and torch.equal(info["degree"], out[0]), info["rounds"]
+    print(json.dumps({"n": n, "per_id": per_id, "links": int(off[-1]), "mean_list": float(off[-1]) / n, "longest_list": int((off[1:] - off[:-1]).max()),
+                      "rounds": rounds, "bitmap_rounds": bitmap_rounds, "n_clusters": int(count.item()), "labels_equal": bool(same),
+                      "workspace_bytes": int(need)}))
+
+
+def table_cluster_lists(out):
+    print("n,rows_per_identity,metric,what,lanes_per_row,launches_per_call,median_us_per_call,min_us_per_call,max_us_per_call,rounds,links,"
+          "mean_list,longest_list,n_clusters,labels_equal")
+    calls = CL_WARMUP + CL_WARM
+    for n in CLL_SHAPES:
+        for per_id in CLL_PER_ID:
+            d = os.path.join(out, f"cluster_lists_{n}_{per_id}")
+            if not os.path.exists(os.path.join(d, "info.json")):
+                continue
+            info = json.load(open(os.path.join(d, "info.json")))
+            tr = _trace(d)
+            tail = f"{info['links']},{info['mean_list']:.2f},{info['longest_list']},{info['n_clusters']},{info['labels_equal']}"
+
+            def row(what, lanes, times, rounds):
+                assert times and len(times) % calls == 0, (n, per_id, what, lanes, len(times))
+                per = len(times) // calls
+                tot = [sum(times[c * per:(c + 1) * per]) / 1e3 for c in range(CL_WARMUP, calls)]
+                print(f"{n},{per_id},cosine,{what},{lanes},{per},{statistics.median(tot):.1f},{min(tot):.1f},{max(tot):.1f},{rounds},{tail}")
+
+            for k in RG_KERNELS:
+                row(k, "", [e - s for s, e, name in tr if k in name], "")
+            degree = [e - s for s, e, name in tr if "k_cluster_list_degree" in name]
+            for i, lanes in enumerate(CLL_LANES):             # (the lanes' calls follow one another)
+                row("k_cluster_list_degree", lanes, degree[i * calls:(i + 1) * calls], info["rounds"][str(lanes)])
+                for k in CLL_LIST_KERNELS[1:]:
+                    row(k, lanes, [e - s for s, e, name in tr if re.search(rf"{k}<(\(int\))?{lanes}>", name)], info["rounds"][str(lanes)])
+            if info["bitmap_rounds"] is not None:
+                for k in CLL_BITMAP_KERNELS:
+                    row(k, "", [e - s for s, e, name in tr if k in name], info["bitmap_rounds"])
+
+
+def run_all_cluster_lists(out):
+    for n in CLL_SHAPES:
+        for per_id in CLL_PER_ID:
+            d = os.path.join(out, f"cluster_lists_{n}_{per_id}")
+            os.makedirs(d, exist_ok=True)
+            r = subprocess.run(["rocprofv3", "--kernel-trace", "-d", d, "-o", "t", "-f", "csv", "--", sys.executable, os.path.abspath(__file__),
+                                "run-cluster-lists", str(n), str(per_id)], capture_output=True, text=True, timeout=300)
+            if r.returncode != 0:
+                sys.exit(f"cluster-lists shape {n} / {per_id} failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+            print(line, file=sys.stderr, flush=True)
+            open(os.path.join(d, "info.json"), "w").write(line)
+    table_cluster_lists(out)
 
 
 HI_EDGES, HI_TORCH_MAX_N = 1000, 8192
@@ -511,6 +618,12 @@ if __name__ == "__main__":
         table_cluster(sys.argv[2])
     elif sys.argv[1] == "run-cluster":
         run_cluster(int(sys.argv[2]))
+    elif sys.argv[1] == "--cluster-lists":
+        run_all_cluster_lists(sys.argv[2])
+    elif sys.argv[1] == "--cluster-lists-table":
+        table_cluster_lists(sys.argv[2])
+    elif sys.argv[1] == "run-cluster-lists":
+        run_cluster_lists(int(sys.argv[2]), int(sys.argv[3]))
     elif sys.argv[1] == "--hist":
         run_all_hist(sys.argv[2])
     elif sys.argv[1] == "--hist-table":

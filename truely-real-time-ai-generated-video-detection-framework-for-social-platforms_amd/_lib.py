@@ -122,6 +122,8 @@ _SIGNATURES = {
     "trl_cluster_links": (C.c_int, [_vp, _vp, _i, _vp, C.c_longlong, _vp, _i, _f, _vp, C.c_longlong, _vp, _i, _vp]),
     "trl_cluster_workspace": (C.c_size_t, [_i]),
     "trl_cluster_labels": (C.c_int, [_vp, C.c_longlong, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(_i), _vp]),
+    "trl_cluster_lists_workspace": (C.c_size_t, [_i]),
+    "trl_cluster_labels_lists": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(_i), _vp]),
     "trl_gallery_hist_workspace": (C.c_size_t, [_i, C.c_longlong, _i, _i]),
     "trl_gallery_hist": (C.c_int, [_vp, _vp, _vp, _i, _vp, C.c_longlong, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp, _i, _vp, _vp, C.c_size_t, _i, _vp]),
     "trl_gallery_range_workspace": (C.c_size_t, [_i, C.c_longlong, _i]),

@@ -21,6 +21,7 @@
 //
 // Clustering (f-8) is the same main loop ended in a ballot: k_gallery_links writes the packed link bitmap of n rows against
 // themselves, and the k_cluster_* kernels turn it into DBSCAN labels by rounds of hooking and pointer jumping, a launch each.
+// Past the bitmap's 65,536 rows the k_cluster_list_* kernels hook and assign over the range search's neighbour lists instead.
 //
 // Score histograms (f-9) end it in counters: k_gallery_hist counts the pairs per score bin (trl_gallery_bins.h), genuine and
 // impostor apart, in LDS, and k_gallery_hist_sum adds the workgroups' counters into the int64 result.
@@ -490,6 +491,122 @@ bool cl_carve(Arena& a, int n, ClWs* w) {
     w->changed = (int*)a.alloc(CL_BATCH * sizeof(int));
     return w->a && w->b && w->cid && w->changed;
 }
+
+// The rounds of either label stage: copy, hook (a -> b, launched by `hook` with the round's change flag) and jump (b -> a) until a
+// round changes nothing, CL_BATCH rounds queued between two looks at the flags.  Every round before the last lowers at least one
+// label, and a label is at least 0 and at most its row's index -- whatever the links hold -- so the loop ends; the bound of n rounds
+// is a second line of defence.  *rounds_out (may be null): the rounds up to and including the first that changed nothing.
+template <typename Hook>
+int cl_rounds(const char* who, const ClWs& w, int n, hipStream_t s, int* rounds_out, Hook&& hook) {
+    int rounds = 0;
+    for (bool done = false; !done;) {
+        if (rounds >= n + CL_BATCH) { trl_set_error("%s: no fixed point after %d rounds", who, rounds); return TRL_ERR_STATE; }
+        TRL_HIP(hipMemsetAsync(w.changed, 0, CL_BATCH * sizeof(int), s));
+        for (int r = 0; r < CL_BATCH; r++) {
+            TRL_HIP(hipMemcpyAsync(w.b, w.a, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            hook(w.changed + r);
+            TRL_LAUNCH_CHECK();
+            k_cluster_jump<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(w.b, n, w.a, w.changed + r);
+            TRL_LAUNCH_CHECK();
+        }
+        int changed[CL_BATCH];
+        TRL_HIP(hipMemcpyAsync(changed, w.changed, sizeof(changed), hipMemcpyDeviceToHost, s));
+        TRL_HIP(hipStreamSynchronize(s));
+        for (int r = 0; r < CL_BATCH && !done; r++) {
+            rounds++;
+            done = changed[r] == 0;
+        }
+    }
+    if (rounds_out) *rounds_out = rounds;
+    return TRL_OK;
+}
+
+// ---- the label stage over neighbour lists: past the bitmap's 65,536 rows ---------------------------------
+// The links are CSR lists -- row i's neighbours are index[offsets[i] .. offsets[i + 1]), what the range search writes with self = 1 --
+// and k_cluster_init / jump / number run as they are: they never see the links.  Lists of face clusters hold tens of entries, so a
+// row is walked by L = 4 / 16 / 64 lanes of a wave, the 256 / L rows of a workgroup side by side.  The L lanes of a row are an
+// aligned group of their wave and leave a kernel together, so the xor shuffles below stay among lanes that are there.
+constexpr int CL_LIST_MAX_N = 1 << 24;
+
+// a thread per row: the row's list length, + 1 for the row itself; 0 for an invalid row
+__global__ void k_cluster_list_degree(const long long* __restrict__ offsets, const uint8_t* __restrict__ valid, int n, int32_t* __restrict__ degree) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    degree[i] = (!valid || valid[i] != 0) ? (int)(offsets[i + 1] - offsets[i]) + 1 : 0;
+}
+
+// the smallest of f(label of j) over the entries j of the list index[beg .. end), by the L lanes that share the row (each of them
+// returns it).  An entry outside 0 .. n - 1 is skipped, never followed; rows that are not core carry CL_NONE and drop out.
+template <int L, typename F>
+__device__ __forceinline__ int cl_list_min(const int32_t* __restrict__ index, long long beg, long long end, int n, const int32_t* __restrict__ lab,
+                                           int sub, F&& f) {
+    int m = CL_NONE;
+    for (long long p = beg + sub; p < end; p += L) {
+        const uint32_t j = (uint32_t)index[p];
+        if (j < (uint32_t)n) {
+            const int v = f(lab[j]);
+            m = v < m ? v : m;
+        }
+    }
+#pragma unroll
+    for (int off = L / 2; off >= 1; off >>= 1) {
+        const int o = __shfl_xor(m, off, 64);
+        m = o < m ? o : m;
+    }
+    return m;
+}
+
+// k_cluster_hook over a list: L lanes per core row, and the same stores -- `out` is a copy of `in` made in front of the launch and
+// is touched by atomicMin only, *changed by atomicOr only; nothing here reads what another workgroup writes in this launch.
+template <int L>
+__global__ __launch_bounds__(256) void k_cluster_list_hook(const long long* __restrict__ offsets, const int32_t* __restrict__ index, int n,
+                                                           const int32_t* __restrict__ in, int32_t* out, int* changed) {
+    const int sub = threadIdx.x & (L - 1);
+    const long long row = (long long)blockIdx.x * (256 / L) + threadIdx.x / L;
+    if (row >= n) return;
+    const int own = in[row];
+    if (own == CL_NONE) return;
+    const int m = cl_list_min<L>(index, offsets[row], offsets[row + 1], n, in, sub, [](int l) { return l; });
+    if (sub == 0 && m < own) {
+        atomicMin(out + row, m);
+        atomicMin(out + own, m);
+        atomicOr(changed, 1);
+    }
+}
+
+// k_cluster_assign over a list: L lanes per row
+template <int L>
+__global__ __launch_bounds__(256) void k_cluster_list_assign(const long long* __restrict__ offsets, const int32_t* __restrict__ index,
+                                                             const int32_t* __restrict__ degree, int n, const int32_t* __restrict__ lab,
+                                                             const int32_t* __restrict__ cid, int32_t* __restrict__ labels) {
+    const int sub = threadIdx.x & (L - 1);
+    const long long row = (long long)blockIdx.x * (256 / L) + threadIdx.x / L;
+    if (row >= n) return;
+    const int own = lab[row];
+    int out = -1;
+    if (own != CL_NONE) {
+        out = cid[own];
+    } else if (degree[row] > 0) {
+        const int m = cl_list_min<L>(index, offsets[row], offsets[row + 1], n, lab, sub, [&](int l) { return l == CL_NONE ? CL_NONE : cid[l]; });
+        out = m == CL_NONE ? -1 : m;
+    }
+    if (sub == 0) labels[row] = out;
+}
+
+template <int L>
+void cl_list_hook(const long long* offsets, const int32_t* index, int n, const int32_t* in, int32_t* out, int* changed, hipStream_t s) {
+    k_cluster_list_hook<L><<<(unsigned)((n + 256 / L - 1) / (256 / L)), 256, 0, s>>>(offsets, index, n, in, out, changed);
+}
+
+template <int L>
+void cl_list_assign(const long long* offsets, const int32_t* index, const int32_t* degree, int n, const int32_t* lab, const int32_t* cid,
+                    int32_t* labels, hipStream_t s) {
+    k_cluster_list_assign<L><<<(unsigned)((n + 256 / L - 1) / (256 / L)), 256, 0, s>>>(offsets, index, degree, n, lab, cid, labels);
+}
+
+// the lanes per row for lists of `mean` entries on average, from profiles/cluster_lists_kernel_stats.csv: at
+// the sizes this stage is for, 4 lanes win up to lists of 127 and 16 lanes at 1,023; 64 lanes won nowhere past 1,024 rows
+int cl_list_lanes(long long mean) { return mean < 384 ? 4 : 16; }
 
 // ---- score histograms: pair counts per score bin, genuine and impostor ------------------------------------
 // k_gallery_hist is k_gallery_links' frame with a fourth end: every accumulator's score is put into its bin (trl_gallery_bins.h, the
@@ -1262,31 +1379,72 @@ extern "C" int trl_cluster_labels(const uint32_t* d_adj, long long pitch_words, 
     const unsigned per_thread = (unsigned)((n + 255) / 256), per_wave = (unsigned)((n + 3) / 4);
     k_cluster_init<<<per_thread, 256, 0, s>>>(d_degree, n, min_samples, d_core, w.a);
     TRL_LAUNCH_CHECK();
-    // rounds of copy, hook (a -> b) and jump (b -> a) until one changes nothing.  Every round before that one lowers at least one label and
-    // a label is at least 0 and at most its row's index, so the loop ends; the bound of n rounds is a second line of defence.
-    int rounds = 0;
-    for (bool done = false; !done;) {
-        if (rounds >= n + CL_BATCH) { trl_set_error("trl_cluster_labels: no fixed point after %d rounds", rounds); return TRL_ERR_STATE; }
-        TRL_HIP(hipMemsetAsync(w.changed, 0, CL_BATCH * sizeof(int), s));
-        for (int r = 0; r < CL_BATCH; r++) {
-            TRL_HIP(hipMemcpyAsync(w.b, w.a, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-            k_cluster_hook<<<per_wave, 256, 0, s>>>(d_adj, pitch_words, n, words, w.a, w.b, w.changed + r);
-            TRL_LAUNCH_CHECK();
-            k_cluster_jump<<<per_thread, 256, 0, s>>>(w.b, n, w.a, w.changed + r);
-            TRL_LAUNCH_CHECK();
-        }
-        int changed[CL_BATCH];
-        TRL_HIP(hipMemcpyAsync(changed, w.changed, sizeof(changed), hipMemcpyDeviceToHost, s));
-        TRL_HIP(hipStreamSynchronize(s));
-        for (int r = 0; r < CL_BATCH && !done; r++) {
-            rounds++;
-            done = changed[r] == 0;
-        }
-    }
-    if (rounds_out) *rounds_out = rounds;
+    TRL_CHECK(cl_rounds("trl_cluster_labels", w, n, s, rounds_out, [&](int* changed) {
+        k_cluster_hook<<<per_wave, 256, 0, s>>>(d_adj, pitch_words, n, words, w.a, w.b, changed);
+    }));
     k_cluster_number<<<1, 1024, 0, s>>>(w.a, n, (n + 1023) / 1024, w.cid, d_count);
     TRL_LAUNCH_CHECK();
     k_cluster_assign<<<per_wave, 256, 0, s>>>(d_adj, pitch_words, d_degree, n, words, w.a, w.cid, d_labels);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+
+extern "C" size_t trl_cluster_lists_workspace(int n) {
+    if (n < 0 || n > CL_LIST_MAX_N) return 0;
+    Arena a = Arena::counter(0);
+    ClWs w;
+    cl_carve(a, n, &w);
+    return a.high;
+}
+
+extern "C" int trl_cluster_labels_lists(const long long* d_offsets, const int32_t* d_index, const uint8_t* d_valid, int n, int min_samples,
+                                        int lanes_per_row, int32_t* d_degree, int32_t* d_labels, uint8_t* d_core, int32_t* d_count,
+                                        void* d_ws, size_t ws_bytes, int* rounds_out, void* stream) {
+    if (n < 0 || n > CL_LIST_MAX_N) { trl_set_error("trl_cluster_labels_lists: n = %d outside 0..%d", n, CL_LIST_MAX_N); return TRL_ERR_INVALID; }
+    if (min_samples < 1) { trl_set_error("trl_cluster_labels_lists: min_samples = %d < 1", min_samples); return TRL_ERR_INVALID; }
+    if (lanes_per_row != 0 && lanes_per_row != 4 && lanes_per_row != 16 && lanes_per_row != 64) {
+        trl_set_error("trl_cluster_labels_lists: lanes_per_row = %d (0, 4, 16 or 64)", lanes_per_row);
+        return TRL_ERR_INVALID;
+    }
+    if (!d_count) { trl_set_error("trl_cluster_labels_lists: null count"); return TRL_ERR_INVALID; }
+    if (n > 0 && (!d_offsets || !d_index || !d_degree || !d_labels || !d_core)) { trl_set_error("trl_cluster_labels_lists: null argument"); return TRL_ERR_INVALID; }
+    Arena a;
+    a.base = (char*)d_ws;
+    a.cap = d_ws ? ws_bytes : 0;
+    ClWs w;
+    if (n > 0 && (((uintptr_t)d_ws & 7) || !cl_carve(a, n, &w))) {
+        trl_set_error("trl_cluster_labels_lists: workspace of %zu bytes (need %zu, 8-byte aligned)", ws_bytes, trl_cluster_lists_workspace(n));
+        return TRL_ERR_INVALID;
+    }
+    TRL_CHECK(gl_device_of(d_count));
+    hipStream_t s = (hipStream_t)stream;
+    if (rounds_out) *rounds_out = 0;
+    if (n == 0) {
+        TRL_HIP(hipMemsetAsync(d_count, 0, sizeof(int32_t), s));
+        return TRL_OK;
+    }
+    int L = lanes_per_row;
+    if (L == 0) {                     // the mean list length decides; the round loop below waits for the stream anyway
+        long long total = 0;
+        TRL_HIP(hipMemcpyAsync(&total, d_offsets + n, sizeof(total), hipMemcpyDeviceToHost, s));
+        TRL_HIP(hipStreamSynchronize(s));
+        L = cl_list_lanes(total / n);
+    }
+    const unsigned per_thread = (unsigned)((n + 255) / 256);
+    k_cluster_list_degree<<<per_thread, 256, 0, s>>>(d_offsets, d_valid, n, d_degree);
+    TRL_LAUNCH_CHECK();
+    k_cluster_init<<<per_thread, 256, 0, s>>>(d_degree, n, min_samples, d_core, w.a);
+    TRL_LAUNCH_CHECK();
+    TRL_CHECK(cl_rounds("trl_cluster_labels_lists", w, n, s, rounds_out, [&](int* changed) {
+        if (L == 4) cl_list_hook<4>(d_offsets, d_index, n, w.a, w.b, changed, s);
+        else if (L == 16) cl_list_hook<16>(d_offsets, d_index, n, w.a, w.b, changed, s);
+        else cl_list_hook<64>(d_offsets, d_index, n, w.a, w.b, changed, s);
+    }));
+    k_cluster_number<<<1, 1024, 0, s>>>(w.a, n, (n + 1023) / 1024, w.cid, d_count);
+    TRL_LAUNCH_CHECK();
+    if (L == 4) cl_list_assign<4>(d_offsets, d_index, d_degree, n, w.a, w.cid, d_labels, s);
+    else if (L == 16) cl_list_assign<16>(d_offsets, d_index, d_degree, n, w.a, w.cid, d_labels, s);
+    else cl_list_assign<64>(d_offsets, d_index, d_degree, n, w.a, w.cid, d_labels, s);
     TRL_LAUNCH_CHECK();
     return TRL_OK;
 }

@@ -15,7 +15,8 @@ product, then
 
 and matches are ordered better score first, equal scores to the lower gallery index, NaN last.  ``cluster`` /
 ``cluster_embeddings`` answer the question that needs no enrolled identities -- "which of these faces are the same person?" --
-with DBSCAN over the same scores, from a link bitmap instead of the score matrix.  ``score_histogram`` / ``roc`` / ``calibrate`` find
+with DBSCAN over the same scores, from a link bitmap instead of the score matrix, and past 65,536 rows from the range search's
+neighbour lists (``method``).  ``score_histogram`` / ``roc`` / ``calibrate`` find
 the threshold both take: exact counts of same-label and different-label pairs per score bin, again without the score matrix, and
 from them the accept rates at every candidate threshold (``roc_from_counts``, ``threshold_at_far``).  ``range_search`` /
 ``range_count`` apply such a threshold to the whole gallery: every enrolled row that passes it, per query, as CSR lists in ascending
@@ -34,7 +35,9 @@ from . import _lib
 
 METRICS = {"cosine": 0, "euclidean": 1}
 MAX_K = 16
-MAX_CLUSTER_ROWS = 65536
+MAX_CLUSTER_ROWS = 65536                 # the link bitmap's limit (n * n / 8 bytes: 512 MB there); cluster(method="auto") takes lists beyond
+MAX_CLUSTER_LIST_ROWS = 1 << 24
+CLUSTER_METHODS = ("auto", "bitmap", "lists")
 MAX_EDGES = 1023
 DIM = 512
 
@@ -218,7 +221,8 @@ class FaceGallery:
         scores = score.tolist()
         return [[(self._identities[g], s) for g, s in zip(gs, ss) if g >= 0] for gs, ss in zip(picks, scores)]
 
-    def cluster(self, threshold: float, min_samples: int = 1, valid=None, return_info: bool = False, max_strip_cols: int = 0):
+    def cluster(self, threshold: float, min_samples: int = 1, valid=None, return_info: bool = False, max_strip_cols: int = 0,
+                method: str = "auto", max_links: int | None = None):
         """DBSCAN labels of the enrolled rows, (len(self),) int32 on the device: "which of these are the same person?".
 
         Rows i != j are linked when their score passes ``threshold`` (identify's convention: cosine ``score >= threshold``,
@@ -227,33 +231,59 @@ class FaceGallery:
         numbered in ascending order of their smallest core member; a row that is not core takes the smallest number among its
         core neighbours' clusters, and -1 (noise) without one.  Rows whose ``valid`` entry is zero link to nothing and get -1.
         ``min_samples=1`` is plain threshold connected components.  This is ``sklearn.cluster.DBSCAN(metric="precomputed")``
-        exactly.  The n x n scores are never written: the links are a bitmap of n * n / 8 bytes (n <= 65,536).
+        exactly.  The n x n scores are never written.
+
+        ``method``: where the links are kept.  ``"bitmap"``: n * n / 8 bytes, one pass over the rows; ``ValueError`` past
+        65,536 rows (``MAX_CLUSTER_ROWS``).  ``"lists"``: ``range_search(emb=None)``'s neighbour lists, 8 bytes per link and two
+        passes over the rows, up to 16,777,216 rows; ``max_links`` is that search's ``max_results``: ``ValueError``, naming the
+        total, before anything is allocated for more links than that.  ``"auto"``: the bitmap up to its limit, lists beyond.  Labels,
+        core and degree are the same bits either way.
 
         With ``return_info`` a dict: ``labels``, ``core`` (n,) uint8, ``degree`` (n,) int32 (links + 1; 0 for an invalid row),
-        ``n_clusters`` and ``rounds`` (ints).  The call synchronises the current stream."""
+        ``n_clusters`` and ``rounds`` (ints), ``method`` (the one taken) and, for lists, ``links`` (the total length of the lists:
+        each linked pair counts twice).  The call synchronises the current stream."""
         n = self._m
-        if n > MAX_CLUSTER_ROWS:
-            raise ValueError(f"cluster takes at most {MAX_CLUSTER_ROWS} rows, not {n}")
+        if method not in CLUSTER_METHODS:
+            raise ValueError(f"method must be one of {CLUSTER_METHODS}, not {method!r}")
+        if method == "auto":
+            method = "bitmap" if n <= MAX_CLUSTER_ROWS else "lists"
+        if method == "bitmap" and n > MAX_CLUSTER_ROWS:
+            raise ValueError(f"cluster(method='bitmap') takes at most {MAX_CLUSTER_ROWS} rows, not {n}")
+        if method == "lists" and n > MAX_CLUSTER_LIST_ROWS:
+            raise ValueError(f"cluster takes at most {MAX_CLUSTER_LIST_ROWS} rows, not {n}")
         threshold, min_samples = float(threshold), int(min_samples)
         valid = _valid(valid, n, self.device)
-        words = (n + 31) // 32
-        adj = torch.empty((n, words), dtype=torch.int32, device=self.device)
         degree = torch.empty((n,), dtype=torch.int32, device=self.device)
         labels = torch.empty((n,), dtype=torch.int32, device=self.device)
         core = torch.empty((n,), dtype=torch.uint8, device=self.device)
         count = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        need = self.lib.trl_cluster_workspace(n)
-        ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
-        rows = self.rows() if n else None
         rounds = C.c_int(0)
         s = _stream(self.device)
-        _lib.check(self.lib.trl_cluster_links(_ptr(rows), _ptr(valid), n, _ptr(self._mat), self.ld, _ptr(self._n2), self._metric, threshold,
-                                              _ptr(adj), words, _ptr(degree), max_strip_cols, s))
-        _lib.check(self.lib.trl_cluster_labels(_ptr(adj), words, _ptr(degree), n, min_samples, _ptr(labels), _ptr(core), _ptr(count),
-                                               _ptr(ws), need, C.byref(rounds), s))
+        info = {"labels": labels, "core": core, "degree": degree}
+        if method == "bitmap":
+            words = (n + 31) // 32
+            adj = torch.empty((n, words), dtype=torch.int32, device=self.device)
+            need = self.lib.trl_cluster_workspace(n)
+            ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
+            rows = self.rows() if n else None
+            _lib.check(self.lib.trl_cluster_links(_ptr(rows), _ptr(valid), n, _ptr(self._mat), self.ld, _ptr(self._n2), self._metric,
+                                                  threshold, _ptr(adj), words, _ptr(degree), max_strip_cols, s))
+            _lib.check(self.lib.trl_cluster_labels(_ptr(adj), words, _ptr(degree), n, min_samples, _ptr(labels), _ptr(core), _ptr(count),
+                                                   _ptr(ws), need, C.byref(rounds), s))
+        else:
+            offsets, index, _score = self.range_search(None, threshold, valid=valid, max_results=max_links, max_strip_cols=max_strip_cols)
+            del _score                                   # (the fill pass writes the scores; the labels do not read them)
+            info["links"] = index.shape[0]
+            if not index.shape[0]:
+                index = torch.empty((1,), dtype=torch.int32, device=self.device)          # (an empty tensor has no address)
+            need = self.lib.trl_cluster_lists_workspace(n)
+            ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
+            _lib.check(self.lib.trl_cluster_labels_lists(_ptr(offsets), _ptr(index), _ptr(valid), n, min_samples, 0, _ptr(degree),
+                                                         _ptr(labels), _ptr(core), _ptr(count), _ptr(ws), need, C.byref(rounds), s))
         if not return_info:
             return labels
-        return {"labels": labels, "core": core, "degree": degree, "n_clusters": int(count.item()), "rounds": rounds.value}
+        info.update(n_clusters=int(count.item()), rounds=rounds.value, method=method)
+        return info
 
     def score_histogram(self, emb=None, labels=None, edges=None, valid=None, gallery_valid=None, max_strip_cols: int = 0) -> dict:
         """Exact pair counts per score bin, same-label ("genuine") and different-label ("impostor") pairs apart: what a
@@ -431,13 +461,14 @@ def threshold_at_far(edges, tar, far, target: float, metric: str = "cosine"):
 
 
 def cluster_embeddings(emb, threshold: float, metric: str = "cosine", min_samples: int = 1, valid=None, device=None,
-                       return_info: bool = False):
-    """``FaceGallery.cluster`` for loose embeddings, (n, 512): the faces of a clip, an enrolment set to de-duplicate."""
+                       return_info: bool = False, method: str = "auto", max_links: int | None = None):
+    """``FaceGallery.cluster`` for loose embeddings, (n, 512): the faces of a clip, an enrolment set to de-duplicate.  ``method``
+    and ``max_links`` are ``cluster``'s."""
     if device is None:
         device = emb.device if isinstance(emb, torch.Tensor) and emb.device.type == "cuda" else None
     g = FaceGallery(metric=metric, device=device, capacity=max(len(emb), 1))
     g.add(emb, range(len(emb)))
-    return g.cluster(threshold, min_samples=min_samples, valid=valid, return_info=return_info)
+    return g.cluster(threshold, min_samples=min_samples, valid=valid, return_info=return_info, method=method, max_links=max_links)
 
 
 def pairwise(a, b=None, metric: str = "euclidean", device=None) -> torch.Tensor:

@@ -10,6 +10,8 @@
 //                                                   k = 0: the value it had at the reset)
 //   counter         -> "c <guard> <counting>"     (Arena::counter(guard) of this arena's guard: what the library sizes it with)
 //   blocks          -> "b <n> <off>:<bytes> ..."  (the recorded blocks)
+//   over <0|1> <bytes> <want> -> "o <cap> <guard> <counting> <offset | null>"   (Arena::over(null or a base, bytes): what the library
+//                                                   lays over a caller's workspace, and one alloc of <want> bytes from it)
 // The rewind callback prints "w <mark> <site> <blocks recorded when it ran>" before the offset moves.
 #include <cinttypes>
 #include <cstdio>
@@ -30,7 +32,7 @@ int main(int argc, char** argv) {
     Arena a;
     static char token;                       // base + offset is only ever turned back into the offset
     if (!strcmp(argv[2], "count")) a = Arena::counter(guard);
-    else { a.base = &token; a.cap = strtoull(argv[2], nullptr, 10); a.guard = guard; a.on_rewind = on_rewind; a.owner = &a; }
+    else { a = Arena::over(&token, strtoull(argv[2], nullptr, 10)); a.guard = guard; a.on_rewind = on_rewind; a.owner = &a; }
     std::vector<size_t> marks{0};            // off after the k-th alloc since the last reset
     char op[32];
     while (scanf("%31s", op) == 1) {
@@ -55,6 +57,15 @@ int main(int argc, char** argv) {
         } else if (!strcmp(op, "counter")) {
             const Arena c = Arena::counter(a.guard);
             printf("c %zu %d\n", c.guard, (int)c.counting);
+        } else if (!strcmp(op, "over")) {
+            int has;
+            unsigned long long n, want;
+            if (scanf("%d %llu %llu", &has, &n, &want) != 3) return 2;
+            Arena o = Arena::over(has ? &token : nullptr, (size_t)n);
+            if (o.base != (has ? &token : nullptr) || o.off || o.high || !o.blocks.empty() || o.on_rewind || o.owner) return 3;
+            void* p = o.alloc((size_t)want);
+            if (p) printf("o %zu %zu %d %" PRIuPTR "\n", o.cap, o.guard, (int)o.counting, (uintptr_t)p - (uintptr_t)o.base);
+            else printf("o %zu %zu %d null\n", o.cap, o.guard, (int)o.counting);
         } else if (!strcmp(op, "blocks")) {
             printf("b %zu", a.blocks.size());
             for (const Arena::Block& b : a.blocks) printf(" %zu:%zu", b.off, b.bytes);

@@ -202,3 +202,11 @@ def test_partial_rewind_keeps_the_blocks_below_the_mark(sim_program, guard):
 def test_counter_carries_the_guard(sim_program, guard):
     assert run(sim_program, guard, 4096, ["counter"]) == [f"c {guard} 1"]
     assert run(sim_program, guard, None, ["counter"]) == [f"c {guard} 1"]
+
+
+def test_over_a_callers_workspace(sim_program):
+    """Arena::over: a real arena, guard off, with the workspace's size as its capacity -- and capacity 0 over a null workspace,
+    whatever size the caller claims, so that nothing is ever carved from a null pointer."""
+    script = ["over 1 1000 1000", "over 1 1000 1001", "over 1 0 1", "over 0 1000 1", "over 0 1000 0", "over 0 0 0", "over 1 %d %d" % (5 << 30, 5 << 30)]
+    assert run(sim_program, 256, 4096, script) == ["o 1000 0 0 0", "o 1000 0 0 null", "o 0 0 0 null", "o 0 0 0 null", "o 0 0 0 null",
+                                                   "o 0 0 0 null", "o %d 0 0 0" % (5 << 30)]

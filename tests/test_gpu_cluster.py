@@ -1,4 +1,4 @@
-"""The embedding clustering on the device (trl_cluster_links, trl_cluster_labels, csrc/trl_gallery.hip) against
+"""The embedding clustering on the device (trl_cluster_links in csrc/trl_gallery.hip, trl_cluster_labels in csrc/trl_cluster.hip) against
 tests/cluster_ref.py, exactly: bitmap words, degrees, labels, core flags and the cluster count; the refusals; gallery.py on top.
 
 k_gallery_links tiles rows by 32 and columns by 32 per wave / 128 per workgroup and walks strips of 128-column groups, so the

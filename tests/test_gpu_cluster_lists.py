@@ -1,4 +1,4 @@
-"""The label stage over neighbour lists on the device (trl_cluster_labels_lists, csrc/trl_gallery.hip) against tests/cluster_ref.py,
+"""The label stage over neighbour lists on the device (trl_cluster_labels_lists, csrc/trl_cluster.hip) against tests/cluster_ref.py,
 exactly: degrees, labels, core flags and the cluster count, with each lanes_per_row; the refusals; FaceGallery.cluster(method=...)
 on top, where the range search writes the lists, and past the bitmap's 65,536 rows.
 

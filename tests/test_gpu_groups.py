@@ -1,7 +1,7 @@
 """The grouped search on the device (k_gallery_search_groups / k_gallery_merge_groups in csrc/trl_gallery.hip) against
 tests/group_ref.py: trl_gallery_search_groups, its refusals, and FaceGallery.identities / search_identities / identify_topk.
 
-The kernel has k_gallery_search's frame, so the sweep is test_gpu_gallery.py's: m in {1, 31, 32, 33, 127, 128, 129, 257} (a lone
+The kernel has the shared search body, so the sweep is test_gpu_gallery.py's: m in {1, 31, 32, 33, 127, 128, 129, 257} (a lone
 column; a wave's slab short of / equal to / past 32; a group short of / equal to / past 128; three groups with a lone column in the
 third), n in {1, 33, 65} (one row, two tiles, three tiles with a lone row), k in {1, 2, 5, 16}, both metrics, every case once with
 the default strips and once with strips of 128 columns (one strip per column group: the merge kernel), and the two runs must be

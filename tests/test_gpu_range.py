@@ -384,6 +384,28 @@ def test_default_plan_with_many_strips():
         assert np.array_equal(gal.range_count(q, threshold=0.5, max_strip_cols=strip_cols).cpu().numpy(), per_row)
 
 
+@pytest.mark.parametrize("n", (1025, 2049))
+def test_more_rows_than_the_scan_has_threads(n):
+    """k_range_scan's 1,024 threads own ceil(n / 1024) rows each: n = 1,025 (two a thread, the last thread with rows has one, half the
+    threads none) and n = 2,049 (three a thread); every other shape of this file has n <= 257, one row a thread.  The queries are noisy
+    copies of 256 stored rows, eight loose copies of an identity, so a row has one to eight matches; the yardstick is scores() put
+    through the reference, as above."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from truely_amd.gallery import FaceGallery
+    rng = np.random.default_rng(n)
+    rows = _identities(32, 8, rng, noise=1.0)
+    q = rows[np.arange(n) % 256] * 0.8 + _identities(n, 1, rng) * 0.2
+    gal = FaceGallery(metric="cosine", capacity=256)
+    gal.add(rows, range(256))
+    want = R.range_ref(gal.scores(q).cpu().numpy(), G.COSINE, 0.5)
+    per_row = np.diff(want[0])
+    assert len(per_row) == n and (per_row >= 1).all() and per_row.max() <= 16 and len(np.unique(per_row)) > 2
+    off, idx, sc = gal.range_search(q, threshold=0.5)
+    _same((off.cpu().numpy(), idx.cpu().numpy(), sc.cpu().numpy()), want, what=("scan", n))
+    assert np.array_equal(gal.range_count(q, threshold=0.5).cpu().numpy(), per_row)
+
+
 def test_refusals_of_the_abi(lib, table):
     """Every refusal of the header, against the good call n = m = 33, self = 1: the status, the message's first word, and outputs
     that keep the sentinel."""

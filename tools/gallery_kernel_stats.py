@@ -30,7 +30,7 @@ trace: 3 + 5 calls of range_search() at cosine 0.5 (the two passes, the row sums
 / 64, 3 + 5 calls of trl_cluster_labels_lists at min_samples 4 on those lists; then, where the bitmap fits (n <= 65,536), 3 + 5 calls
 of cluster(method="bitmap"), whose labels must equal the lists'.  A row of the table is one kernel of one phase: its launches per
 call and the median over the 5 measured calls of its time per call (the hook kernels run once per round).  The auto choice of
-lanes_per_row (cl_list_lanes, csrc/trl_gallery.hip) is read from this table.
+lanes_per_row (cl_list_lanes, csrc/trl_cluster.hip) is read from this table.
 
 Histogram mode (FaceGallery.score_histogram: trl_gallery_hist), the same embeddings, labels = the identities, E = 1000 edges:
 

@@ -24,6 +24,8 @@ struct Arena {
 
     // the counting arena that sizes an arena with this guard
     static Arena counter(size_t guard) { Arena a; a.counting = true; a.guard = guard; return a; }
+    // a real arena over `bytes` bytes at `mem` that somebody else owns (a caller's workspace); a null `mem` holds nothing
+    static Arena over(const void* mem, size_t bytes) { Arena a; a.base = (char*)const_cast<void*>(mem); a.cap = mem ? bytes : 0; return a; }
 
     // site: a short label of the call site, for the sweep's report
     void reset(const char* site = "reset") { rewind(0, site); }

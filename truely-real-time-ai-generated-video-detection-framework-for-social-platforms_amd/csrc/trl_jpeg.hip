@@ -981,8 +981,7 @@ static int jpeg_create(const char* who, int device, int H, int W, const trl_jpeg
         delete e;
         return TRL_ERR_HIP;
     }
-    Arena a;
-    a.base = (char*)e->mem; a.cap = total;
+    Arena a = Arena::over(e->mem, total);
     carve(a, (size_t)e->chunk, e);
     st = hipMemcpy(e->tab, &tab, sizeof(JTab), hipMemcpyHostToDevice);
     if (st == hipSuccess) st = hipMemcpy(e->hdr, hdr, e->hdr_len, hipMemcpyHostToDevice);

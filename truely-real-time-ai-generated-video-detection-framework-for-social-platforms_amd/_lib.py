@@ -101,6 +101,7 @@ _SIGNATURES = {
     "trl_debug_pnet_span": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "trl_debug_pnet_screen_bound": (C.c_int, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "trl_debug_pnet_screen_weights": (C.c_int, [_vp, C.POINTER(_f)]),
+    "trl_debug_pnet_defer": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "trl_jpeg_create": (C.c_int, [_i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "trl_jpeg_destroy": (C.c_int, [_vp]),
     "trl_jpeg_encode": (C.c_int, [_vp, _vp, _i, C.c_longlong, _vp, C.c_longlong, _vp, _vp]),

@@ -76,7 +76,7 @@ int trl_create(const trl_config* cfg, trl_ctx** out) {
     // execution span of every fused PNet launch (two atomics per workgroup, summed on the device: trl_debug_pnet_span);
     // TRL_PNET_CLOCK additionally selects the DBG instantiation with per-phase wave clocks
     c->pnet_prof = trl_tune_set("TRL_PNET_CLOCK");
-    if (hipMalloc((void**)&c->pnet_clk, 8 * 41) != hipSuccess || hipMemset(c->pnet_clk, 0, 8 * 41) != hipSuccess || hipMemset(c->pnet_clk, 0xFF, 8) != hipSuccess ||
+    if (hipMalloc((void**)&c->pnet_clk, 8 * 44) != hipSuccess || hipMemset(c->pnet_clk, 0, 8 * 44) != hipSuccess || hipMemset(c->pnet_clk, 0xFF, 8) != hipSuccess ||
         hipMalloc((void**)&c->pnet_cursor, 64) != hipSuccess || hipHostMalloc((void**)&c->h_pinned, 1024) != hipSuccess ||
         hipEventCreate(&c->ev_call0) != hipSuccess || hipEventCreate(&c->ev_call1) != hipSuccess) {
         trl_set_error("context allocation failed: %s", hipGetErrorString(hipGetLastError()));
@@ -102,7 +102,7 @@ int trl_destroy(trl_ctx* c) {
     for (auto& b : c->fn_cap) if (b.p) (void)hipFree(b.p);
     if (c->pnet_clk) {
         // TRL_PNET_CLOCK: where the waves of the fused PNet launches spent their time (shader clocks per tile and wave, DBG instantiation)
-        unsigned long long t[41];
+        unsigned long long t[42];
         if (c->pnet_prof && hipMemcpy(t, c->pnet_clk, sizeof t, hipMemcpyDeviceToHost) == hipSuccess && t[2 + 32] > 0) {
             static const char* nm[8] = {"phase0", "barrier0", "phase1", "barrier1", "phase2", "barrier2", "phase3", "barrier3"};
             const double tiles = (double)t[2 + 32];
@@ -111,6 +111,7 @@ int trl_destroy(trl_ctx* c) {
                 fprintf(stderr, "[TRL_PNET_CLOCK] %-9s %8.0f %8.0f %8.0f %8.0f\n", nm[k], t[2 + k] / tiles, t[2 + 8 + k] / tiles, t[2 + 16 + k] / tiles, t[2 + 24 + k] / tiles);
             fprintf(stderr, "[TRL_PNET_CLOCK] fp16 screen: %llu M-tiles screened, %llu confirmed (%.2f %%)\n", t[39], t[40],
                     t[39] ? 100.0 * (double)t[40] / (double)t[39] : 0.0);
+            fprintf(stderr, "[TRL_PNET_CLOCK] confirm queue: %llu M-tiles queued, %.0f per launch\n", t[41], t[37] ? (double)t[41] / (double)t[37] : 0.0);
         }
         (void)hipFree(c->pnet_clk);
     }
@@ -275,7 +276,7 @@ static void collect_timings(trl_ctx* c) {
     (void)hipEventElapsedTime(&call_ms, c->ev_call0, c->ev_call1);
     int launches = 0;
     if (c->cfg.pnet_mode == 0 && c->pnet_ev_used >= 2) {
-        // pair 0 = pyramid kernel, pair 1 = the fused PNet kernel (the dominant kernel, one launch)
+        // pair 0 = pyramid kernel, pair 1 = the fused PNet kernel (the dominant kernel, one launch) with its confirm pass
         (void)hipEventElapsedTime(&pyr_ms, c->pnet_ev[0].first, c->pnet_ev[0].second);
         (void)hipEventElapsedTime(&pnet_ms, c->pnet_ev[1].first, c->pnet_ev[1].second);
         launches = 1;
@@ -1012,7 +1013,10 @@ int trl_debug_list_stats(trl_ctx* c, long long* h_out8) {
 // test hooks of the shipped library (it reads no environment variable): "rnet_chunk" / "onet_chunk" = candidates per R-/O-Net
 // launch set of this context (>= 16), "no_fnconv" = process-wide: FaceNet's small maps through the generic conv kernels,
 // "pyr_row_bands" = row bands of the streaming pyramid pass of this context (0 = the pass's own policy), "tail_pool" = 1 (default):
-// the R-/O-Net tail pools run in their conv's epilogue where one exists, 0: every pool is its own launch (the same bits)
+// the R-/O-Net tail pools run in their conv's epilogue where one exists, 0: every pool is its own launch (the same bits),
+// "pnet_defer" = 1: the fused PNet queues the conv3 M-tiles its screen confirms for a second kernel wherever the launch can defer,
+// 0: every launch runs them inline; "pnet_defer_cap" = slots the queue starts from in place of the policy's start (0: the policy).
+// Both forget what the queue's capacity had learned (trl_capacity.h)
 int trl_debug_option(trl_ctx* c, const char* key, int value) {
     if (!key) { trl_set_error("null key"); return TRL_ERR_INVALID; }
     if (!strcmp(key, "no_fnconv")) { g_trl_no_fnconv = value ? 1 : 0; return TRL_OK; }
@@ -1021,6 +1025,8 @@ int trl_debug_option(trl_ctx* c, const char* key, int value) {
     if (!strcmp(key, "rnet_chunk") && value >= 16) { c->rnet_chunk = value; return TRL_OK; }
     if (!strcmp(key, "onet_chunk") && value >= 16) { c->onet_chunk = value; return TRL_OK; }
     if (!strcmp(key, "pnet_screen") && (value == 0 || value == 1)) { c->pnet_screen = value; return TRL_OK; }
+    if (!strcmp(key, "pnet_defer") && (value == 0 || value == 1)) { c->pnet_defer = value; c->caps.defer = DeferCaps(); return TRL_OK; }
+    if (!strcmp(key, "pnet_defer_cap") && value >= 0) { c->caps.defer = DeferCaps(); c->caps.defer.forced = value; return TRL_OK; }
     if (!strcmp(key, "pyr_row_bands") && value >= 0) { c->pyr_row_bands = value; return TRL_OK; }
     if (!strcmp(key, "tail_pool") && (value == 0 || value == 1)) { c->tail_pool = value; return TRL_OK; }
     trl_set_error("unknown option '%s' (or value %d out of range)", key, value);
@@ -1030,6 +1036,15 @@ int trl_debug_option(trl_ctx* c, const char* key, int value) {
 int trl_debug_pnet_screen_bound(trl_ctx* c, float* A, float* B, int* on) {
     if (!c || !A || !B || !on) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
     *A = c->pnet_scrA; *B = c->pnet_scrB; *on = c->pnet_screen_ok && c->pnet_screen;
+    return TRL_OK;
+}
+
+// The confirm queue of the last attempt of the last call: h_out4 = {slots (0: the exact chain ran inline), M-tiles that asked for a
+// slot, M-tiles of the launch, calls the inline path is still held for}
+int trl_debug_pnet_defer(trl_ctx* c, long long* h_out4) {
+    if (!c || !h_out4) { trl_set_error("null argument"); return TRL_ERR_INVALID; }
+    const DeferCaps& d = c->caps.defer;
+    h_out4[0] = d.cap; h_out4[1] = d.cap > 0 ? c->h_pinned[4 + FLG_DEFER_N] : 0; h_out4[2] = d.mtiles; h_out4[3] = d.hold;
     return TRL_OK;
 }
 

@@ -1,4 +1,5 @@
-// trl_capacity.h -- the cascade's five optimistic capacities: their state, the plan of an attempt, the feedback after it.
+// trl_capacity.h -- the cascade's optimistic capacities (five list / batch capacities and the fused PNet's confirm queue): their state,
+// the plan of an attempt, the feedback after it.
 // Host arithmetic only (integers and floats in, integers and floats out): plain C++17, no HIP header, so a host compiler builds it
 // for tests/capacity_sim.cpp.  Built with -ffp-contract=off like the library: every float expression below is the operation
 // sequence it shows.
@@ -17,6 +18,8 @@ enum { TRL_NFLAGS = 64 };            // int32 words of CascadeBufs::flags (copie
 // attempt measured (the R-/O-Net candidate totals, the largest per-frame and per-level counts, the spill bytes asked for)
 enum { FLG_LEVEL = 0, FLG_FRAME = 1, FLG_T2 = 2, FLG_T3 = 3, FLG_T2N = 4, FLG_T3N = 5, FLG_FRAME_MAX = 6, FLG_SPILL = 7,
        FLG_SPILL_CUR = 8 /* u64 */, FLG_SPILL_LISTS = 10, FLG_LEVEL_MAX = 16 /* [32] */ };
+// ... and of the fused PNet's confirm queue (below): it was too small, and the M-tiles the launch asked slots for
+enum { FLG_DEFER = 11, FLG_DEFER_N = 12 };
 
 // Candidate lists of one call.  Level l of every frame owns capl[l] record slots (never more than the level has cells); a frame's
 // records are contiguous: record (f, l, slot) = lvl_rec[f * S + rec0[l] + slot], S = sum of capl.  The per-frame box lists of
@@ -37,6 +40,53 @@ inline float trl_cap_follow(const CapRule& r, float cur, float measured, float p
     return want > d ? want : (d > r.floor ? d : (cur < r.floor ? cur : r.floor));
 }
 
+// The fused PNet's confirm queue (trl_pnet.hip): the persistent kernel screens every conv3 M-tile (32 cells)
+// and queues the few that may hold a candidate; a second kernel runs the exact chain on them.  A slot holds what that kernel
+// reads: a header {frame, level, ty, tx, mt} and the M-tile's 4 x 18 conv2 cells of 17 floats.  The queue is a block of the
+// cascade workspace, `cap` slots; cap == 0: the attempt runs the exact chain inline, in the persistent kernel.
+//   start   START slots per M-tile of the launch (+ 64).  The most crowded of the five audited configurations
+//           (profiles/pnet_screen_audit.json, configs[4]) confirms ~20 % of its M-tiles; the flagship one 6.7 %.
+//           A launch whose every M-tile fits FULL_BYTES gets a slot per M-tile instead: a queue that small is not worth the risk
+//           of a re-run (a few frames; the start fraction decides from ~10 frames of 720p on)
+//   growth  the slot counter keeps counting past the capacity, so one overflow measures the need N: the re-run gets 1.25 N (+ 64)
+//   bound   N beyond BOUND of the M-tiles: the queue would carry the conv2 tile of most of the map through memory (4.9 KB per
+//           M-tile, against 2.4 KB of it in the tile): the next HOLD PNet attempts (the re-run is the first) take the inline path, then the queue is
+//           tried again (one PNet attempt lost per HOLD calls on content that confirms everywhere, none that oscillates)
+// A call that fitted lets the hint follow the need like every other capacity.
+enum { TRL_DEFER_HDR = 32, TRL_DEFER_BLOCK = 72 * 17 * 4, TRL_DEFER_SLOT = TRL_DEFER_HDR + TRL_DEFER_BLOCK };   // bytes
+static_assert(TRL_DEFER_SLOT % 16 == 0, "slots are copied in 16-byte words");
+struct DeferCaps {
+    static constexpr float START = 0.25f, BOUND = 0.5f;
+    static constexpr CapRule RULE = {1.25f, 0.f, 0.97f, 0.f};   // (the floor is START, applied by trl_defer_plan)
+    static constexpr int HOLD = 256;
+    static constexpr long long FULL_SLOTS = (64ll << 20) / TRL_DEFER_SLOT;  // 13,617 slots
+    static constexpr long long MAX_SLOTS = (4ll << 30) / TRL_DEFER_SLOT;   // a queue never exceeds 4 GiB; a need beyond it is past the bound
+    float frac = 0.f;               // slots per M-tile recent calls needed (0: none measured yet)
+    int hold = 0;                    // > 0: calls that still take the inline path
+    int forced = 0;                  // > 0: slots in place of the START floor (trl_debug_option "pnet_defer_cap")
+    int cap = 0; long long mtiles = 0;   // the attempt in progress (trl_defer_plan's result and argument)
+};
+// slots of an attempt over `mtiles` M-tiles; applicable: the launch can defer at all (screen on, a DEFER instantiation of the net)
+inline int trl_defer_plan(const DeferCaps& d, long long mtiles, bool applicable) {
+    if (!applicable || mtiles <= 0 || d.hold > 0) return 0;
+    long long want = d.forced > 0 ? d.forced : (long long)(DeferCaps::START * (float)mtiles) + 64;
+    if (d.forced <= 0 && want < DeferCaps::FULL_SLOTS) want = DeferCaps::FULL_SLOTS;   // (clamped to the M-tiles below)
+    const long long hint = d.frac > 0.f ? (long long)(d.frac * (float)mtiles) + 64 : 0;
+    if (hint > want) want = hint;
+    if (want > mtiles) want = mtiles;            // every M-tile queued: cannot overflow
+    if (want > DeferCaps::MAX_SLOTS) want = DeferCaps::MAX_SLOTS;
+    return (int)want;
+}
+// the queue's block: the same call sizes it (a counting arena) and carves it
+template <class ArenaT> inline void* trl_defer_carve(ArenaT& A, int cap) { return cap > 0 ? A.alloc((size_t)cap * TRL_DEFER_SLOT) : nullptr; }
+// after an attempt that ran on d.cap > 0 slots and queued `need` M-tiles.  true: the queue was too small, run PNet again
+inline bool trl_defer_check(DeferCaps& d, bool overflow, int need) {
+    const float per = (float)(d.mtiles > 0 ? d.mtiles : 1);
+    if ((float)need > DeferCaps::BOUND * per || (long long)(1.25f * (float)need) + 64 > DeferCaps::MAX_SLOTS) d.hold = DeferCaps::HOLD;
+    else d.frac = trl_cap_follow(DeferCaps::RULE, d.frac, (float)need, per, overflow);
+    return overflow;
+}
+
 struct CascadeCaps {
     static constexpr float T_START[2] = {160.f, 48.f};   // R-Net / O-Net candidates per frame of a fresh context
     // ~25 % head-room over the largest batch / list seen, 3 % decay per call.  Batches settle no lower than their start values; the
@@ -48,6 +98,7 @@ struct CascadeCaps {
     float lvl_hint[32] = {0}, frame_hint = 0.f;        // largest per-level count / per-frame stage-1 total recent calls needed
     size_t spill_hint = 0;                             // spill workspace, bytes
     int cap_t[2] = {0, 0};           // batch capacities of the call in progress (trl_caps_plan)
+    DeferCaps defer;                 // the fused PNet's confirm queue
     int resume_stage = 0;            // 2 / 3: the next attempt of the call in progress starts at that stage (trl_caps_check)
     int last_attempts = 0;           // attempts the last call took (test hook)
 };
@@ -93,6 +144,8 @@ inline CapsVerdict trl_caps_check(CascadeCaps& k, const int32_t* f, int n, const
     k.resume_stage = 0;
     unsigned long long spill_used = 0;
     memcpy(&spill_used, f + FLG_SPILL_CUR, 8);
+    // PNet's confirm queue first: M-tiles that found no slot were not run, so the level lists and everything behind them are incomplete
+    if (k.defer.cap > 0 && trl_defer_check(k.defer, f[FLG_DEFER] != 0, f[FLG_DEFER_N])) return {1, 0};
     if (f[FLG_LEVEL]) {                                  // every later stage ran on truncated lists: their totals mean nothing
         long long sum = 0;
         for (int l = 0; l < L; l++) {
@@ -127,6 +180,7 @@ inline CapsVerdict trl_caps_check(CascadeCaps& k, const int32_t* f, int n, const
     for (int l = 0; l < L; l++)
         k.lvl_hint[l] = trl_cap_follow(CascadeCaps::LIST_RULE, k.lvl_hint[l], (float)f[FLG_LEVEL_MAX + l], 1.f, false);
     k.frame_hint = trl_cap_follow(CascadeCaps::LIST_RULE, k.frame_hint, frame_max, 1.f, false);
+    if (k.defer.cap == 0 && k.defer.hold > 0) k.defer.hold--;
     {   // not trl_cap_follow: bytes in integers, 25 % head-room and 1/32 decay by shifts, and a pool under 1 MiB is given up
         const size_t want = (size_t)spill_used + (spill_used >> 2), d = k.spill_hint - (k.spill_hint >> 5);
         k.spill_hint = spill_used ? (want > d ? want : d) : (d > (1u << 20) ? d : 0);

@@ -818,8 +818,14 @@ int trl_launch_heads_to_maps(const float* d_heads, int cells, float* d_prob, flo
     return TRL_OK;
 }
 
+// the fused launch carries 16 level descriptors; taller pyramids (a 16 K frame at min_face_size 12) take the per-level path
+static bool pnet_is_fused(const trl_ctx* c, int L) { return c->cfg.pnet_mode == 0 && L <= 16; }
 // The capacities of this attempt (trl_capacity.h): record slots per level, rows per frame, the R-/O-Net batches
 static void plan_caps(trl_ctx* c, int L, int n) {
+    // the fused PNet's confirm queue (0 slots: the exact chain runs inline)
+    DeferCaps& d = c->caps.defer;
+    d.mtiles = trl_pnet_mtiles(c, L, n);
+    c->cb.pq_cap = d.cap = trl_defer_plan(d, d.mtiles, pnet_is_fused(c, L) && trl_pnet_can_defer(c));
     long long cells[32];
     for (int l = 0; l < L; l++) cells[l] = (long long)c->lv[l].oh * c->lv[l].ow;
     const CascadePlan p = trl_caps_plan(c->caps, c->cfg.cap_level, c->cfg.cap_frame, cells, L, n);
@@ -936,6 +942,7 @@ static void layout_lists(CascadeBufs& B, Arena& A, size_t spill) {
     for (int k = 0; k < 2; k++) B.off[k] = (int32_t*)A.alloc((size_t)(n + 1) * 4);
     B.cbox = (int32_t*)A.alloc((size_t)n * capF * 32);
     B.flags = (int32_t*)A.alloc(TRL_NFLAGS * 4);
+    B.pq = (char*)trl_defer_carve(A, B.pq_cap);
     B.spill = spill ? (char*)A.alloc(spill) : nullptr;
     B.spill_cap = B.spill ? spill : 0;
     B.box0 = (float*)A.alloc((size_t)n * 16); B.prob0 = (float*)A.alloc((size_t)n * 4);
@@ -1088,8 +1095,7 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
         TRL_HIP(hipMemsetAsync(B.lvl_cnt, 0, (size_t)n * L * 4, s));
         c->pnet_ev_used = 0;
     }
-    const bool fused = c->cfg.pnet_mode == 0 && L <= 16;   // the fused launch carries 16 level descriptors; taller pyramids (a
-                                                           // 16 K frame at min_face_size 12) take the per-level path
+    const bool fused = pnet_is_fused(c, L);
     TRL_CHECK(size_scratch(c, n, H, W, fused));
     if (!resume) TRL_CHECK(fused ? stage1_fused(c, d_frames, s) : stage1_generic(c, d_frames, s));
     ListLaunch ll;
@@ -1155,6 +1161,7 @@ int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* 
                       float* d_prob0, int32_t* d_rect, uint8_t* d_valid, hipStream_t s) {
     CascadeBufs& B = c->cb;
     B = CascadeBufs();
+    c->caps.defer.cap = 0;                                // (no PNet launch, no confirm queue)
     LvLayout& G = B.lay;
     G.L = L;
     for (int l = 0; l < L; l++) { G.capl[l] = h_caps[l]; G.rec0[l] = G.S; G.S += h_caps[l]; }

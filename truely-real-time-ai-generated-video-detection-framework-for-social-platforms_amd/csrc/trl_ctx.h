@@ -33,6 +33,8 @@ struct CascadeBufs {   // device pointers into the arena, valid until the next c
     int32_t* off[2] = {nullptr, nullptr};            // [n+1] exclusive scans of cnt[0] / cnt[1]: the R-Net / O-Net batch
     int32_t* cbox = nullptr;     // [n*capF][8]: candidate t of the current stage = {frame, y0, x0, ih, iw, 0, 0, 0} (pad()'s crop window)
     int32_t* flags = nullptr;        // [TRL_NFLAGS]: the FLG_* words (trl_capacity.h)
+    char* pq = nullptr;              // the fused PNet's confirm queue: pq_cap slots of TRL_DEFER_SLOT bytes (trl_capacity.h); none when 0
+    int pq_cap = 0;
     char* spill = nullptr;           // global-memory workspace of the NMS spill tier (lists longer than the LDS tier)
     size_t spill_cap = 0;
     float* box0 = nullptr; float* prob0 = nullptr; int32_t* rect = nullptr; uint8_t* valid = nullptr; float* pts0 = nullptr;   // k_select's per-frame outputs where the call asks for none
@@ -51,6 +53,7 @@ struct NetDesc {
     int nout;                        // output floats per item
     int trl_ctx::*chunk;             // the context's candidates-per-launch-set option of this net
 };
+enum { TRL_PNET_DEFER_DEFAULT = 1 };   // (the measurement behind the default)
 enum { TRL_PNET = 0, TRL_RNET = 1, TRL_ONET = 2 };
 extern const NetDesc trl_nets[3];
 inline const NetDesc& trl_net_of(int net) { return trl_nets[net == 24 ? TRL_RNET : TRL_ONET]; }   // the API's net argument: 24 / 48
@@ -91,9 +94,10 @@ struct trl_ctx {
     float pnet_scrG[16] = {};        // the bound the kernel applies: sum over the cell's 3x3x16 inputs of pnet_scrG[channel] |x|, + B (sum of the 144 coefficients <= A)
     int pnet_screen_ok = 0;          // the conv3 weights fit fp16 (else the screen is off for this net)
     int pnet_screen = 1;             // trl_debug_option "pnet_screen": 0 = every M-tile takes the exact f32 path
+    int pnet_defer = TRL_PNET_DEFER_DEFAULT;   // trl_debug_option "pnet_defer": 1 = confirmed conv3 M-tiles run in a second kernel where the launch can defer
     int pnet_run = 0;                // > 0: tiles per cursor fetch of the fused PNet launch (trl_debug_pnet_run); 0 = automatic
     int32_t* pnet_cursor = nullptr;           // device: 8 per-XCD tile cursors of the fused PNet launch
-    unsigned long long* pnet_clk = nullptr;   // device: [0] first-start / [1] last-end wall clock of the fused PNet launch in flight, [2..35] phase clocks (DBG), [36] summed spans, [37] launches, [39] / [40] screened / confirmed M-tiles (DBG)
+    unsigned long long* pnet_clk = nullptr;   // device: [0] first-start / [1] last-end wall clock of the fused PNet launch in flight, [2..35] phase clocks (DBG), [36] summed spans, [37] launches, [39] / [40] screened / confirmed M-tiles (DBG), [41] queued M-tiles, [42] / [43] a DEFER launch's own counts until it is known to have fitted
     bool pnet_prof = false;                   // TRL_PNET_CLOCK: the DBG instantiation with per-phase wave clocks
     float pnet_kernel_ms = 0.f;      // its span in ms (collect_timings)
     int dbg_poison = -1;             // >= 0 after trl_debug_poison: byte written into every newly allocated workspace
@@ -216,6 +220,8 @@ int trl_launch_crop_area_std(const uint8_t* d_frames, int n, int H, int W, const
 int trl_pnet_generic_level(trl_ctx* c, Arena& X, const uint8_t* d_frames, int nf, int H, int W, const LevelGeom& g, float** d_heads, hipStream_t s);
 // fused PNet (trl_pnet.hip)
 int trl_pnet_prepare(trl_ctx* c, const char* himg);   // slope classes and the screen bound, from the host image
+bool trl_pnet_can_defer(const trl_ctx* c);             // this context's fused launches have a DEFER instantiation and the screen is on
+long long trl_pnet_mtiles(const trl_ctx* c, int L, int n);   // conv3 M-tiles (2 output rows x 16 cells) of a fused launch over n frames
 size_t trl_pnet_fused_bytes(trl_ctx* c, int n, int H, int W);
 int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, hipEvent_t* ev, hipStream_t s);
 int trl_pyramid_export(trl_ctx* c, const uint8_t* d_frame, int H, int W, int level, float* d_out, int* h, int* w, hipStream_t s);

@@ -21,6 +21,11 @@
 //                 compile-time offsets, pooling precedes PReLU when the slopes allow, edge logic only on edge tiles.
 //                 blockIdx -> tile mapping keeps an XCD on a contiguous run of tiles (halo rows of
 //                 neighbouring tiles hit the same L2).
+//  k_pnet_confirm The few conv3 M-tiles (32 cells) the screen confirms are not run inside the persistent kernel, where one wave's exact
+//                 chain keeps the other three of its workgroup at the tile's last barrier: the DEFER instantiation queues them (the
+//                 M-tile's conv2 rows, 4.9 KB) and this ordinary kernel, launched right behind it, runs the same chain on every queued
+//                 M-tile, one wave each.  The queue is a block of the cascade workspace with a capacity that follows the content
+//                 (trl_capacity.h); launches that cannot defer, and content that confirms most M-tiles, run the chain inline.
 #include "trl_pyramid.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -28,6 +33,7 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -61,6 +67,7 @@ constexpr int BAND = 3;
 constexpr int VCARRY_P = 4 * P1_T * 10;              // 800 floats: 4 pooled rows x 20 columns x 10 channels (contiguous in the tile)
 constexpr int VCARRY_C = 2 * C2_T * C2_LD;           // 612 floats: 2 conv2 rows x 18 columns x 17
 constexpr int DYN_LDS = (144 * 32 + BAND * (CARRY_P + CARRY_C) + VCARRY_P + VCARRY_C) * 4;   // conv3 weights + the carry strips (dynamic: static LDS is capped at 64 KB)
+static_assert((2 * C2_T * C2_LD * 4) % 16 == 0 && 4 * C2_T * C2_LD * 4 == TRL_DEFER_BLOCK, "an M-tile's 4 conv2 rows: 16-byte words of region A, one queue block");
 static_assert((144 * 32) % 4 == 0 && CARRY_P % 4 == 0 && CARRY_C % 4 == 0 && VCARRY_P % 4 == 0, "strips stay 16-byte aligned");
 
 // A level as k_pnet_fused reads it.  The kernel indexes lv[] by sizeof(PLevel) and loads its members by their offsets, so both are
@@ -97,6 +104,7 @@ struct PnetArgs {
     int run;                                   // consecutive tiles a workgroup takes per cursor fetch (>= 1)
     unsigned long long* clk;                   // [0] = earliest workgroup start, [1] = latest workgroup end (device wall clock); DBG: [2..] phase clocks
     int prof;                                  // DBG instantiation: accumulate the per-phase wave clocks
+    char* q; int q_cap; int32_t* q_cnt;        // DEFER: the confirm queue (q_cap slots of TRL_DEFER_SLOT bytes) and its slot counter (zeroed with xcd_next)
 };
 
 // ---- fused PNet --------------------------------------------------------------------------------------
@@ -169,10 +177,132 @@ __device__ __forceinline__ float lane_sel(float if0, float if1, unsigned long lo
 template <int... I, typename F>
 __device__ __forceinline__ void pn_static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 
+// ---- conv3 -> heads -> candidates of ONE M-tile (32 cells = 2 output rows), register to register ---------------------------------
+// Written once for the two places that run them: phase 3 of k_pnet_fused (the inline instantiations: the M-tile of the conv2 tile
+// in region A) and k_pnet_confirm (the M-tile's 4 conv2 rows in a wave's own LDS area, laid out like region A's rows: mt = 0).
+//
+// conv3 runs TRANSPOSED on mfma_f32_32x32x2: the A operand is the weight (rows = output channels), the B operand the
+// activation (columns = the 32 cells of the M-tile = 2 output rows), the same two LDS words per lane and k-step as the
+// other way round and the same chain per output (acc = bias, k ascending).  Lane l then holds 16 channels --
+// 8 (q >> 2) + (q & 3) + 4 hh -- of ONE cell (l & 31): exactly what the heads' B operand wants, so nothing is staged
+// through LDS between conv3 and the heads (round 3 measured that round trip and the idle chain behind it at 6 % of the
+// kernel).  `between(sx, u)` is called after MFMA u of sixth sx: the previous M-tile's head chain rides in those slots.
+// R: conv2 rows [.][18][17], B3S: the conv3 weights [k][32], T3: bias[32], slopes[32], head bias[8] as f32x4 (all LDS).
+template <bool UNIT, typename Between>
+__device__ __forceinline__ void pn_conv3(const float* R, const float* B3S, const f32x4* T3, int mt, int l31, int hh, f32x16& P, Between&& between) {
+    const int y = mt * 2 + (l31 >> 4), x = l31 & 15;
+    const int base = (y * C2_T + x) * C2_LD + hh;
+    f32x16 acc;
+#pragma unroll
+    for (int qa = 0; qa < 4; qa++) {
+        const f32x4 b4 = T3[2 * qa + hh];                       // bias of channels 8 qa + 4 hh .. + 3
+        acc[4 * qa] = b4[0]; acc[4 * qa + 1] = b4[1]; acc[4 * qa + 2] = b4[2]; acc[4 * qa + 3] = b4[3];
+    }
+    // 6 x 12 k-steps, double buffered: the operands of sixth i+1 are requested before the MFMAs of sixth i
+    // issue, so only the first sixth's LDS latency is exposed.
+    float xa[2][12], wb[2][12];
+    auto read_sixth = [&](int sx, float* xo, float* wo) {
+#pragma unroll
+        for (int u = 0; u < 12; u++) {
+            const int s = sx * 12 + u, tap = s >> 3, ky = tap / 3, kx = tap - ky * 3;
+            xo[u] = R[base + (ky * C2_T + kx) * C2_LD + 2 * (s & 7)];
+            wo[u] = B3S[(2 * s + hh) * 32 + l31];
+        }
+    };
+    read_sixth(0, xa[0], wb[0]);
+    pn_static_for(std::make_integer_sequence<int, 6>{}, [&](auto SX) __attribute__((always_inline)) {
+        constexpr int sx = decltype(SX)::value;
+        if (sx < 5) read_sixth(sx + 1, xa[(sx + 1) & 1], wb[(sx + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        pn_static_for(std::make_integer_sequence<int, 12>{}, [&](auto UU) __attribute__((always_inline)) {
+            constexpr int u = decltype(UU)::value;
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[sx & 1][u], xa[sx & 1][u], acc, 0, 0, 0);
+            between(SX, UU);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+    });
+#pragma unroll
+    for (int qa = 0; qa < 4; qa++) {
+        const f32x4 s4 = T3[8 + 2 * qa + hh];                   // PReLU slopes of the same channels
+#pragma unroll
+        for (int qb = 0; qb < 4; qb++) P[4 * qa + qb] = prelu_t<UNIT>(acc[4 * qa + qb], s4[qb], UNIT ? 0.f : trl_prelu_sel(s4[qb]));
+    }
+}
+// heads (1x1, 32 -> 2 + 4) on v_mfma_f32_4x4x1_16B_f32: sixteen 4x4 blocks per instruction, ONE k per instruction.
+// Block b of lanes 4b..4b+3 = cells 4(b & 7) .. +3 (the B operand: the cell's conv3 value at k), outputs
+// 4(b >> 3) .. +3 (the A operand: weights W[k][4(b >> 3) + i], broadcast inside each group of eight blocks from block
+// k & 7 of register k >> 3 -- cbsz = 3, abid = k & 7): one instruction does both output groups of all 32 cells and
+// every lane ends up holding ITS cell's logits.  Same chain: acc = bias, k ascending.  Channel k of cell c sits in
+// lane c + 32 ((k >> 2) & 1), register 4 (k >> 3) + (k & 3): one v_permlane32_swap of the register with a copy of
+// itself yields the lower half's value in every lane (k & 4 == 0) and the upper half's (k & 4 == 4).
+struct PnHeads {
+    float WH[4];                 // the lane's head weights: load()
+    unsigned hlo[4], hhi[4];     // the swapped registers of the current group of eight k
+    __device__ __forceinline__ void load(const float* wh, int lane) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) WH[r] = wh[(((lane >> 2) & 7) + 8 * r) * 32 + 4 * (lane >> 5) + (lane & 3)];
+    }
+    template <int k>
+    __device__ __forceinline__ void step(const f32x16& P, f32x4& hq) {
+        constexpr int ga = k >> 3, gb = k & 7;
+        if constexpr (gb == 0) {
+#pragma unroll
+            for (int qb = 0; qb < 4; qb++) {
+                const unsigned v = __float_as_uint(P[4 * ga + qb]);
+                const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+                hlo[qb] = r[0]; hhi[qb] = r[1];
+            }
+        }
+        const float bk = __uint_as_float(gb < 4 ? hlo[gb & 3] : hhi[gb & 3]);
+        hq = __builtin_amdgcn_mfma_f32_4x4x1f32(WH[ga], bk, hq, 3, gb, 0);
+    }
+    __device__ __forceinline__ void all(const f32x16& P, f32x4& hq) {
+        pn_static_for(std::make_integer_sequence<int, 32>{}, [&](auto H_T) __attribute__((always_inline)) { step<decltype(H_T)::value>(P, hq); });
+    }
+};
+// lanes 0..31: {logit0, logit1, reg0, reg1} of cell = lane; lanes 32..63: {reg2, reg3, -, -} of cell = lane - 32
+// The softmax (two exps and a division: ~55 VALU beside the other workgroup's MFMAs) runs only for an M-tile in which
+// some cell's logit difference comes within reach of the threshold (a.dthr: a bound with a wide margin, fill_args) --
+// one compare and a scalar branch for the ~90 % of the M-tiles that hold no candidate.
+// (f, l): frame and level; (oy0, ox0): the M-tile's first output cell in the level's map of oh x ow cells; fscale: the level's scale
+__device__ __forceinline__ void pn_emit(const PnetArgs& a, int f, int l, int oy0, int ox0, int oh, int ow, float fscale, int dbg_skip, int lane,
+                                        const f32x4& hq) {
+    if (__builtin_amdgcn_ballot_w64(lane < 32 && hq[1] - hq[0] >= a.dthr) == 0) return;
+    const float p = trl_softmax2_p1(hq[0], hq[1]);
+    const auto u2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(hq[0]), __float_as_uint(hq[0]), false, false);
+    const auto u3 = __builtin_amdgcn_permlane32_swap(__float_as_uint(hq[1]), __float_as_uint(hq[1]), false, false);
+    if (lane < 32) {                                // one lane per cell of the 32-row tile
+        const int oy = oy0 + (lane >> 4), ox = ox0 + (lane & 15);
+        if (oy < oh && ox < ow) {
+            if (p >= a.thr && !(dbg_skip & 32)) {      // (bit 32: timing-only ablations emit no candidates)
+                const int seg = f * a.L + l;
+                const int sl = atomicAdd(&a.lvl_cnt[seg], 1);
+                if (sl < a.lv[l].cap) {            // (scalar loads inside the rare branch: the tile descriptor stays as small as it was)
+                    Cand c;
+                    c.x1 = floorf((2.f * (float)ox + 1.f) / fscale);
+                    c.y1 = floorf((2.f * (float)oy + 1.f) / fscale);
+                    c.x2 = floorf((2.f * (float)ox + 12.f) / fscale);
+                    c.y2 = floorf((2.f * (float)oy + 12.f) / fscale);
+                    c.score = p;
+                    c.r0 = hq[2]; c.r1 = hq[3]; c.r2 = __uint_as_float(u2[1]); c.r3 = __uint_as_float(u3[1]);
+                    c.cell = oy * ow + ox;
+                    a.lvl_rec[(size_t)f * a.rec_stride + a.lv[l].rec0 + sl] = c;
+                } else {
+                    a.flags[FLG_LEVEL] = 1;
+                }
+            }
+        }
+    }
+}
+
 // DBG: diagnostic instantiation -- records the launch's execution span on the device wall clock (TRL_PNET_CLOCK=1) and honours
 // the timing-only phase ablation mask (TRL_PNET_SKIP, tools/pnet_phase_pmc.sh).  The production instantiation (DBG = false)
 // carries neither: no instrumentation and no ablation tests on the hot path.
-template <bool UNIT, bool NEG1, bool DBG>
+// DEFER: an M-tile the screen confirms is not run here: the wave takes a slot of the confirm queue and copies what the exact chain
+// reads -- the M-tile's 4 conv2 rows, 72 consecutive cells of region A -- into it; k_pnet_confirm, launched behind this kernel,
+// runs conv3, the heads and the candidate write of every queued M-tile, one wave each and no barrier between them.  The
+// instantiation holds no conv3, no head chain and no candidate write.
+template <bool UNIT, bool NEG1, bool DBG, bool DEFER>
 __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
     __shared__ __attribute__((aligned(16))) float RA[REGION_A];   // input tile [42][42][3]  ->  conv2 out [324][17]
     __shared__ __attribute__((aligned(16))) float RB[REGION_B];   // pooled [400][10] (+ the reach of conv2's zero-weight k padding)
@@ -193,11 +323,11 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
 
     // ---- B operands: every weight matrix stays in registers for the whole launch -----------------------------
     for (int i = tid; i < 144 * 32; i += 256) B3S[i] = a.w3[i];          // conv3 B operand [k][32] in LDS (18 KB)
-    float B2[23], WH[4];
+    float B2[23];
 #pragma unroll
     for (int s = 0; s < 23; s++) B2[s] = a.w2[(4 * s + kq) * 32 + l15];
-#pragma unroll
-    for (int r = 0; r < 4; r++) WH[r] = a.wh[(((lane >> 2) & 7) + 8 * r) * 32 + 4 * (lane >> 5) + (lane & 3)];   // heads: see phase 3
+    PnHeads hd;
+    if constexpr (!DEFER) hd.load(a.wh, lane);                            // heads: see phase 3
     // (vectors are zero padded to 128 floats)
     const float bias2 = a.b2[l15], slope2 = a.s2[l15];
     if (tid < 32) { T3all[tid] = a.b3[tid]; T3all[32 + tid] = a.s3[tid]; if (tid < 8) T3all[64 + tid] = a.bh[tid]; }   // (published by the barrier below)
@@ -794,106 +924,10 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
         if (!(dbg_skip & 8)) {
             const float fscale = g.scale;
             const f32x4* T3 = reinterpret_cast<const f32x4*>(T3all);
-            // conv3 runs TRANSPOSED on mfma_f32_32x32x2: the A operand is the weight (rows = output channels), the B operand the
-            // activation (columns = the 32 cells of the M-tile = 2 output rows), the same two LDS words per lane and k-step as the
-            // other way round and the same chain per output (acc = bias, k ascending).  Lane l then holds 16 channels --
-            // 8 (q >> 2) + (q & 3) + 4 hh -- of ONE cell (l & 31): exactly what the heads' B operand wants, so nothing is staged
-            // through LDS between conv3 and the heads (round 3 measured that round trip and the idle chain behind it at 6 % of the
-            // kernel).  `between(sx, u)` is called after MFMA u of sixth sx: the previous M-tile's head chain rides in those slots.
-            auto conv3 = [&](int mt, f32x16& P, auto&& between) __attribute__((always_inline)) {
-                const int y = mt * 2 + (l31 >> 4), x = l31 & 15;
-                const int base = (y * C2_T + x) * C2_LD + hh;
-                f32x16 acc;
-#pragma unroll
-                for (int qa = 0; qa < 4; qa++) {
-                    const f32x4 b4 = T3[2 * qa + hh];                       // bias of channels 8 qa + 4 hh .. + 3
-                    acc[4 * qa] = b4[0]; acc[4 * qa + 1] = b4[1]; acc[4 * qa + 2] = b4[2]; acc[4 * qa + 3] = b4[3];
-                }
-                // 6 x 12 k-steps, double buffered: the operands of sixth i+1 are requested before the MFMAs of sixth i
-                // issue, so only the first sixth's LDS latency is exposed.
-                float xa[2][12], wb[2][12];
-                auto read_sixth = [&](int sx, float* xo, float* wo) {
-#pragma unroll
-                    for (int u = 0; u < 12; u++) {
-                        const int s = sx * 12 + u, tap = s >> 3, ky = tap / 3, kx = tap - ky * 3;
-                        xo[u] = RA[base + (ky * C2_T + kx) * C2_LD + 2 * (s & 7)];
-                        wo[u] = B3S[(2 * s + hh) * 32 + l31];
-                    }
-                };
-                read_sixth(0, xa[0], wb[0]);
-                pn_static_for(std::make_integer_sequence<int, 6>{}, [&](auto SX) __attribute__((always_inline)) {
-                    constexpr int sx = decltype(SX)::value;
-                    if (sx < 5) read_sixth(sx + 1, xa[(sx + 1) & 1], wb[(sx + 1) & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    pn_static_for(std::make_integer_sequence<int, 12>{}, [&](auto UU) __attribute__((always_inline)) {
-                        constexpr int u = decltype(UU)::value;
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[sx & 1][u], xa[sx & 1][u], acc, 0, 0, 0);
-                        between(SX, UU);
-                    });
-                    __builtin_amdgcn_sched_barrier(0);
-                });
-#pragma unroll
-                for (int qa = 0; qa < 4; qa++) {
-                    const f32x4 s4 = T3[8 + 2 * qa + hh];                   // PReLU slopes of the same channels
-#pragma unroll
-                    for (int qb = 0; qb < 4; qb++) P[4 * qa + qb] = prelu_t<UNIT>(acc[4 * qa + qb], s4[qb], UNIT ? 0.f : trl_prelu_sel(s4[qb]));
-                }
-            };
-            // heads (1x1, 32 -> 2 + 4) on v_mfma_f32_4x4x1_16B_f32: sixteen 4x4 blocks per instruction, ONE k per instruction.
-            // Block b of lanes 4b..4b+3 = cells 4(b & 7) .. +3 (the B operand: the cell's conv3 value at k), outputs
-            // 4(b >> 3) .. +3 (the A operand: weights W[k][4(b >> 3) + i], broadcast inside each group of eight blocks from block
-            // k & 7 of register k >> 3 -- cbsz = 3, abid = k & 7): one instruction does both output groups of all 32 cells and
-            // every lane ends up holding ITS cell's logits.  Same chain: acc = bias, k ascending.  Channel k of cell c sits in
-            // lane c + 32 ((k >> 2) & 1), register 4 (k >> 3) + (k & 3): one v_permlane32_swap of the register with a copy of
-            // itself yields the lower half's value in every lane (k & 4 == 0) and the upper half's (k & 4 == 4).
-            unsigned hlo[4], hhi[4];
-            auto head_step = [&](auto H_T, const f32x16& P, f32x4& hq) __attribute__((always_inline)) {
-                constexpr int k = decltype(H_T)::value, ga = k >> 3, gb = k & 7;
-                if constexpr (gb == 0) {
-#pragma unroll
-                    for (int qb = 0; qb < 4; qb++) {
-                        const unsigned v = __float_as_uint(P[4 * ga + qb]);
-                        const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-                        hlo[qb] = r[0]; hhi[qb] = r[1];
-                    }
-                }
-                const float bk = __uint_as_float(gb < 4 ? hlo[gb & 3] : hhi[gb & 3]);
-                hq = __builtin_amdgcn_mfma_f32_4x4x1f32(WH[ga], bk, hq, 3, gb, 0);
-            };
-            auto heads_all = [&](const f32x16& P, f32x4& hq) __attribute__((always_inline)) {
-                pn_static_for(std::make_integer_sequence<int, 32>{}, [&](auto H_T) __attribute__((always_inline)) { head_step(H_T, P, hq); });
-            };
-            // lanes 0..31: {logit0, logit1, reg0, reg1} of cell = lane; lanes 32..63: {reg2, reg3, -, -} of cell = lane - 32
-            // The softmax (two exps and a division: ~55 VALU beside the other workgroup's MFMAs) runs only for an M-tile in which
-            // some cell's logit difference comes within reach of the threshold (a.dthr: a bound with a wide margin, fill_args) --
-            // one compare and a scalar branch for the ~90 % of the M-tiles that hold no candidate.
-            auto emit = [&](int mt, const f32x4& hq) __attribute__((always_inline)) {
-                if (__builtin_amdgcn_ballot_w64(lane < 32 && hq[1] - hq[0] >= a.dthr) == 0) return;
-                const float p = trl_softmax2_p1(hq[0], hq[1]);
-                const auto u2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(hq[0]), __float_as_uint(hq[0]), false, false);
-                const auto u3 = __builtin_amdgcn_permlane32_swap(__float_as_uint(hq[1]), __float_as_uint(hq[1]), false, false);
-                if (lane < 32) {                                // one lane per cell of the 32-row tile
-                    const int oy = ty * TS + mt * 2 + (lane >> 4), ox = tx * TS + (lane & 15);
-                    if (oy < g.oh && ox < g.ow) {
-                        if (p >= a.thr && !(dbg_skip & 32)) {      // (bit 32: timing-only ablations emit no candidates)
-                            const int seg = f * a.L + l;
-                            const int sl = atomicAdd(&a.lvl_cnt[seg], 1);
-                            if (sl < a.lv[l].cap) {            // (scalar loads inside the rare branch: the tile descriptor stays as small as it was)
-                                Cand c;
-                                c.x1 = floorf((2.f * (float)ox + 1.f) / fscale);
-                                c.y1 = floorf((2.f * (float)oy + 1.f) / fscale);
-                                c.x2 = floorf((2.f * (float)ox + 12.f) / fscale);
-                                c.y2 = floorf((2.f * (float)oy + 12.f) / fscale);
-                                c.score = p;
-                                c.r0 = hq[2]; c.r1 = hq[3]; c.r2 = __uint_as_float(u2[1]); c.r3 = __uint_as_float(u3[1]);
-                                c.cell = oy * g.ow + ox;
-                                a.lvl_rec[(size_t)f * a.rec_stride + a.lv[l].rec0 + sl] = c;
-                            } else {
-                                a.flags[FLG_LEVEL] = 1;
-                            }
-                        }
-                    }
-                }
+            // the exact chain of an M-tile of this tile (pn_conv3, PnHeads, pn_emit above)
+            [[maybe_unused]] auto conv3 = [&](int mt, f32x16& P, auto&& between) __attribute__((always_inline)) { pn_conv3<UNIT>(RA, B3S, T3, mt, l31, hh, P, between); };
+            [[maybe_unused]] auto emit = [&](int mt, const f32x4& hq) __attribute__((always_inline)) {
+                pn_emit(a, f, l, ty * TS + mt * 2, tx * TS, g.oh, g.ow, fscale, dbg_skip, lane, hq);
             };
             // 8 M-tiles of 32 cells = 2 output rows each; wave w takes M-tiles w and w + 4 (a bottom-edge tile may have neither or
             // only the first: those output rows lie below the level).  The head chain of the first rides in the MFMA stream of the
@@ -952,7 +986,36 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
                 if (has1) cf1 = screen(mt1, sb0 + 8 * C2_T);   // M-tile mt0 + 4: 8 conv2 rows down
                 if (DBG) { nscr += has1 ? 2 : 1; ncnf += (cf0 ? 1 : 0) + (cf1 ? 1 : 0); }
             }
-            if (cf0 && cf1) {
+            if constexpr (DEFER) {
+                // a confirmed M-tile goes to the queue: one slot (the counter keeps counting past the capacity: the host learns the
+                // need), the M-tile's 72 conv2 cells = 306 16-byte words from region A (read-only until the barrier that ends the
+                // tile), the header.  A launch whose queue is full raises FLG_DEFER and is run again (trl_capacity.h)
+                auto defer = [&](int mt) __attribute__((always_inline)) {
+                    int slot = 0;
+                    if (lane == 0) slot = atomicAdd(a.q_cnt, 1);
+                    slot = __builtin_amdgcn_readfirstlane(slot);
+                    if (slot < a.q_cap) {
+                        char* const dst = a.q + (size_t)slot * TRL_DEFER_SLOT;
+                        const f32x4* src = reinterpret_cast<const f32x4*>(RA + mt * (2 * C2_T * C2_LD));
+                        f32x4* d4 = reinterpret_cast<f32x4*>(dst + TRL_DEFER_HDR);
+#pragma unroll
+                        for (int i = 0; i < (TRL_DEFER_BLOCK / 16 + 63) / 64; i++) {
+                            const int j = lane + 64 * i;
+                            if (j < TRL_DEFER_BLOCK / 16) d4[j] = src[j];
+                        }
+                        if (lane == 0) {
+                            int* h = reinterpret_cast<int*>(dst);
+                            *reinterpret_cast<i32x4*>(h) = i32x4{f, l, ty, tx};
+                            h[4] = mt;
+                        }
+                    } else if (lane == 0) {
+                        a.flags[FLG_DEFER] = 1;
+                    }
+                };
+                if (cf0) defer(mt0);
+                if (cf1) defer(mt1);
+                strips_get();
+            } else if (cf0 && cf1) {
                 f32x16 P0;
                 f32x4 hq0 = T3[16 + hh];                        // head bias of this half's output group
                 conv3(mt0, P0, [](auto, auto) {});
@@ -963,12 +1026,12 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
                         constexpr int sx = decltype(SX)::value, u = decltype(UU)::value, h = sx * 6 + (u >> 1);
                         if constexpr ((u & 1) == 1 && h < 32) {          // (pinned: the scheduler would bunch the block instructions)
                             __builtin_amdgcn_sched_barrier(0);
-                            head_step(std::integral_constant<int, h>{}, P0, hq0);
+                            hd.template step<h>(P0, hq0);
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     });
                     strips_get();
-                    heads_all(P1, hq1);
+                    hd.all(P1, hq1);
                     emit(mt0, hq0);
                     emit(mt1, hq1);
                 }
@@ -978,7 +1041,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
                 f32x4 hq0 = T3[16 + hh];
                 conv3(mt, P0, [](auto, auto) {});
                 strips_get();
-                heads_all(P0, hq0);
+                hd.all(P0, hq0);
                 emit(mt, hq0);
             } else {
                 strips_get();
@@ -995,18 +1058,73 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
         for (int k = 0; k < 8; k++) atomicAdd(&a.clk[2 + 8 * wave + k], pt[k]);
         if (wave == 0) atomicAdd(&a.clk[2 + 32], (unsigned long long)rot);
     }
-    if (DBG && lane == 0 && nscr) { atomicAdd(&a.clk[39], (unsigned long long)nscr); atomicAdd(&a.clk[40], (unsigned long long)ncnf); }
+    // (a DEFER launch counts into [42] / [43]: k_pnet_span adds them to the totals unless the queue overflowed -- that launch's records
+    // are dropped and its re-run counts the same M-tiles again)
+    if (DBG && lane == 0 && nscr) { atomicAdd(&a.clk[DEFER ? 42 : 39], (unsigned long long)nscr); atomicAdd(&a.clk[DEFER ? 43 : 40], (unsigned long long)ncnf); }
     if (DBG && tid == 0) atomicMax(&a.clk[1], (unsigned long long)wall_clock64());
+}
+
+// The second pass behind a DEFER launch: the exact f32 chain of every queued M-tile, ONE wave per slot, no barrier between the
+// waves once the conv3 weights are in LDS.  The grid is sized by the queue's capacity; workgroups past the device-side count
+// return at once (k_mtcnn_front's convention).  A wave loads its slot's 4 conv2 rows into its own LDS area, laid out like region
+// A's rows, and runs what the inline instantiations run for M-tile 0 of such a tile: pn_conv3, the head chain, pn_emit -- the same
+// instructions in the same order per output, so the records are the inline path's bit for bit; their order inside a level's list
+// is arbitrary on both paths (atomicAdd slots; the list kernels sort on (score, cell) keys).  8 waves per workgroup: 58 KB of LDS,
+// two workgroups per CU, 4 waves per SIMD (<= 128 VGPRs): the matrix pipe has another wave's chain to run while one waits on LDS.
+constexpr int CONFIRM_WAVES = 8;
+template <bool UNIT>
+__global__ __launch_bounds__(64 * CONFIRM_WAVES, 4) void k_pnet_confirm(PnetArgs a) {
+    __shared__ __attribute__((aligned(16))) float B3S[144 * 32];
+    __shared__ __attribute__((aligned(16))) float WA[CONFIRM_WAVES][4 * C2_T * C2_LD];
+    __shared__ __attribute__((aligned(16))) float T3all[72];     // conv3 bias[32], PReLU slopes[32], head bias[8]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int asked = *a.q_cnt;                                  // slots the fused launch asked for: beyond q_cap it stored nothing
+    if (blockIdx.x == 0 && tid == 0) a.flags[FLG_DEFER_N] = asked;
+    const int n = asked < a.q_cap ? asked : a.q_cap;
+    if ((int)blockIdx.x * CONFIRM_WAVES >= n) return;
+    for (int i = tid; i < 144 * 32; i += 64 * CONFIRM_WAVES) B3S[i] = a.w3[i];
+    if (tid < 32) { T3all[tid] = a.b3[tid]; T3all[32 + tid] = a.s3[tid]; if (tid < 8) T3all[64 + tid] = a.bh[tid]; }
+    const int slot = blockIdx.x * CONFIRM_WAVES + wave;
+    const char* const src = a.q + (size_t)(slot < n ? slot : 0) * TRL_DEFER_SLOT;
+    if (slot < n) {
+        const f32x4* s4 = reinterpret_cast<const f32x4*>(src + TRL_DEFER_HDR);
+        f32x4* d4 = reinterpret_cast<f32x4*>(WA[wave]);
+#pragma unroll
+        for (int i = 0; i < (TRL_DEFER_BLOCK / 16 + 63) / 64; i++) {
+            const int j = lane + 64 * i;
+            if (j < TRL_DEFER_BLOCK / 16) d4[j] = s4[j];
+        }
+    }
+    PnHeads hd;
+    hd.load(a.wh, lane);
+    __syncthreads();
+    if (slot >= n) return;
+    const int* h = reinterpret_cast<const int*>(src);
+    const int f = h[0], l = h[1], ty = h[2], tx = h[3], mt = h[4];
+    const PLevel& g = a.lv[l];
+    const int l31 = lane & 31, hh = lane >> 5;
+    const f32x4* T3 = reinterpret_cast<const f32x4*>(T3all);
+    f32x16 P;
+    f32x4 hq = T3[16 + hh];
+    pn_conv3<UNIT>(WA[wave], B3S, T3, 0, l31, hh, P, [](auto, auto) {});
+    hd.all(P, hq);
+    pn_emit(a, f, l, ty * TS + mt * 2, tx * TS, g.oh, g.ow, g.scale, 0, lane, hq);
 }
 
 }  // namespace
 
-// after a fused launch: [36] += its span, [37] += 1, [38] = its span; the start / end stamps are re-armed for the next launch
-__global__ void k_pnet_span(unsigned long long* clk) {
+// after a fused launch: [36] += its span, [37] += 1, [38] = its span; the start / end stamps are re-armed for the next launch;
+// a DEFER launch whose queue held every M-tile: [39] / [40] += the M-tiles it screened / confirmed, [41] += the M-tiles it queued
+__global__ void k_pnet_span(unsigned long long* clk, const int32_t* q_cnt, int q_cap) {
     const unsigned long long t0 = clk[0], t1 = clk[1];
     const unsigned long long d = t1 > t0 ? t1 - t0 : 0ull;
     clk[36] += d; clk[37] += 1ull; clk[38] = d;
     clk[0] = ~0ull; clk[1] = 0ull;
+    if (q_cnt) {
+        if (*q_cnt <= q_cap) { clk[39] += clk[42]; clk[40] += clk[43]; clk[41] += (unsigned long long)*q_cnt; }
+        clk[42] = clk[43] = 0ull;
+    }
 }
 
 // Error bound of the fp16 conv3 screen: for a cell whose 3x3x16 conv2 inputs satisfy |x| <= X <= 65504,
@@ -1125,6 +1243,19 @@ static void fill_args(trl_ctx* c, int n, int H, int W, const PyrLayout& lay, con
     a.lvl_cnt = c->cb.lvl_cnt; a.lvl_rec = c->cb.lvl_rec; a.flags = c->cb.flags;
     a.clk = c->pnet_clk; a.prof = c->pnet_prof ? 1 : 0;
     a.xcd_next = c->pnet_cursor;
+    a.q = c->cb.pq; a.q_cap = c->cb.pq ? c->cb.pq_cap : 0; a.q_cnt = c->pnet_cursor + 8;
+}
+
+// Deferral applies where the screen is on, leaves something out (thr0 inside the prefilter's range: outside it every M-tile
+// confirms) and the net has a DEFER instantiation (no slope above 1); every other launch runs the exact chain inline
+bool trl_pnet_can_defer(const trl_ctx* c) {
+    return c->pnet_defer && c->pnet_screen && c->pnet_screen_ok && c->pnet_unit && c->cfg.thr0 >= 0.01f && c->cfg.thr0 <= 0.99f &&
+           trl_tune_int("TRL_PNET_SKIP", 0) == 0;
+}
+long long trl_pnet_mtiles(const trl_ctx* c, int L, int n) {
+    long long m = 0;
+    for (int l = 0; l < L; l++) if (c->lv[l].oh > 0 && c->lv[l].ow > 0) m += (long long)((c->lv[l].ow + TS - 1) / TS) * ((c->lv[l].oh + 1) / 2);
+    return m * n;
 }
 
 size_t trl_pnet_fused_bytes(trl_ctx* c, int n, int H, int W) {
@@ -1134,7 +1265,8 @@ size_t trl_pnet_fused_bytes(trl_ctx* c, int n, int H, int W) {
 }
 
 // All pyramid levels of all n frames: the pyramid kernels + one persistent fused launch.
-// ev[0..1] bracket the pyramid kernels, ev[2..3] the fused kernel (HIP events on the same stream).
+// ev[0..1] bracket the pyramid kernels, ev[2..3] the fused kernel and, where the launch defers, k_pnet_confirm behind it (HIP events
+// on the same stream): both are PNet work.
 int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, hipEvent_t* ev, hipStream_t s) {
     PyrLayout lay;
     PyrPx* pyr = nullptr;
@@ -1145,12 +1277,12 @@ int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     int grid = 256 * 2;   // 2 resident workgroups per CU (<= 256 VGPRs)
     if (grid > ((total_tiles + 7) / 8) * 8) grid = ((total_tiles + 7) / 8) * 8;
     if (grid < 8) grid = 8;
-    TRL_HIP(hipMemsetAsync(c->pnet_cursor, 0, 8 * sizeof(int32_t), s));
+    TRL_HIP(hipMemsetAsync(c->pnet_cursor, 0, 9 * sizeof(int32_t), s));   // the 8 tile cursors and the confirm queue's slot counter
     // The persistent grid fills every CU: it waits for the end of the device's previous call (another context's cascade tail or
     // embedder) and then runs alone, so the event pair below is its duration; the pyramid kernels queued in front of it are
     // memory-bound and DO overlap that call's narrow kernels (trl_gate_wait, trl_api.hip).
     TRL_CHECK(trl_gate_wait(c, s));
-    if (ev) TRL_HIP(hipEventRecord(ev[2], s));   // the event pair brackets the kernel alone (HIP events on the launch's stream)
+    if (ev) TRL_HIP(hipEventRecord(ev[2], s));   // the event pair brackets PNet's kernels alone (HIP events on the launch's stream)
     // instantiation: slopes all <= 1 or not, a negative conv1 slope or not, diagnostics (TRL_PNET_CLOCK / TRL_PNET_SKIP) or not
 #ifdef TRL_TUNING
     const bool dbg = c->pnet_prof || a.dbg_skip || trl_tune_set("TRL_PNET_SPAN");   // the instantiation with clock stamps / ablations
@@ -1170,18 +1302,26 @@ int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     };
     bool launched = false;
 #ifdef TRL_TUNING
-#define TRL_PK(U, N) do { launched = dbg ? launch(k_pnet_fused<U, N, true>) : launch(k_pnet_fused<U, N, false>); } while (0)
+#define TRL_PK(U, N, D) do { launched = dbg ? launch(k_pnet_fused<U, N, true, D>) : launch(k_pnet_fused<U, N, false, D>); } while (0)
 #else
-#define TRL_PK(U, N) do { launched = launch(k_pnet_fused<U, N, false>); } while (0)
+#define TRL_PK(U, N, D) do { launched = launch(k_pnet_fused<U, N, false, D>); } while (0)
 #endif
-    if (c->pnet_unit) { if (c->pnet_mono1) TRL_PK(true, false); else TRL_PK(true, true); }
-    else { if (c->pnet_mono1) TRL_PK(false, false); else TRL_PK(false, true); }
+    // (the plan gave the call a confirm queue only where trl_pnet_can_defer held: a UNIT net with the screen on)
+    const bool defer = a.q_cap > 0;
+    if (defer && !(c->pnet_unit && a.screen)) { trl_set_error("confirm queue planned for a launch that cannot defer"); return TRL_ERR_STATE; }
+    if (defer) { if (c->pnet_mono1) TRL_PK(true, false, true); else TRL_PK(true, true, true); }
+    else if (c->pnet_unit) { if (c->pnet_mono1) TRL_PK(true, false, false); else TRL_PK(true, true, false); }
+    else { if (c->pnet_mono1) TRL_PK(false, false, false); else TRL_PK(false, true, false); }
 #undef TRL_PK
     if (!launched) { trl_set_error("k_pnet_fused: %d bytes of dynamic LDS refused", DYN_LDS); return TRL_ERR_HIP; }
     TRL_LAUNCH_CHECK();
+    if (defer) {   // the queued M-tiles, right behind it: PNet work, inside the event pair
+        k_pnet_confirm<true><<<(a.q_cap + CONFIRM_WAVES - 1) / CONFIRM_WAVES, 64 * CONFIRM_WAVES, 0, s>>>(a);
+        TRL_LAUNCH_CHECK();
+    }
     if (ev) TRL_HIP(hipEventRecord(ev[3], s));
     if (dbg) {
-        k_pnet_span<<<1, 1, 0, s>>>(c->pnet_clk);   // fold the launch's span into the running sums, re-arm the two stamps
+        k_pnet_span<<<1, 1, 0, s>>>(c->pnet_clk, defer ? a.q_cnt : nullptr, a.q_cap);   // fold the launch's span into the running sums, re-arm the two stamps
         TRL_LAUNCH_CHECK();
     }
     return TRL_OK;

@@ -473,8 +473,8 @@ class Engine:
         return k.value
 
     def option(self, key: str, value: int):
-        """Test hook (``trl_debug_option``): "rnet_chunk" / "onet_chunk" / "pnet_screen" / "pyr_row_bands" / "tail_pool" (this
-        context), "no_fnconv" (process-wide)."""
+        """Test hook (``trl_debug_option``): "rnet_chunk" / "onet_chunk" / "pnet_screen" / "pnet_defer" / "pnet_defer_cap" / "pyr_row_bands" /
+        "tail_pool" (this context), "no_fnconv" (process-wide)."""
         _lib.check(self.lib.trl_debug_option(self._h, key.encode(), int(value)))
 
     def nms_tiers(self, small: int = 0, full: int = 0):
@@ -501,6 +501,13 @@ class Engine:
         g = (C.c_float * 16)()
         _lib.check(self.lib.trl_debug_pnet_screen_weights(self._h, g))
         return [float(v) for v in g]
+
+    def pnet_defer(self) -> dict:
+        """Test hook: the fused PNet's confirm queue in the last attempt of the last call -- ``slots`` (0: the exact conv3 chain ran
+        inline), ``queued`` M-tiles that asked for a slot, ``mtiles`` of the launch, ``hold`` calls the inline path is kept for."""
+        t = (C.c_longlong * 4)()
+        _lib.check(self.lib.trl_debug_pnet_defer(self._h, t))
+        return dict(zip(("slots", "queued", "mtiles", "hold"), (int(v) for v in t)))
 
     def pnet_run(self, run: int = 0):
         """Test / tuning hook: tiles per cursor fetch of the fused PNet launch (0 = automatic); > 1 exercises the halo carry."""

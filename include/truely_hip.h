@@ -51,14 +51,21 @@ typedef struct trl_ctx trl_ctx;
 typedef struct {
     int    device;          /* HIP device ordinal */
     int    min_face_size;   /* 20 */
-    float  thr0, thr1, thr2;/* 0.6 0.7 0.7 */
+    float  thr0, thr1, thr2;/* 0.6 0.7 0.7   Stage 1 keeps a cell with p >= thr0; stages 2 and 3 keep a box with p > thr1 /
+                             * p > thr2, strictly, as detect_face does (`ipass = score > threshold`).  Any float is accepted
+                             * and compared as a float: a NaN threshold keeps nothing, a threshold of 1 or more keeps nothing
+                             * at stages 2 and 3, and a threshold of 0 or less keeps every box there (the softmax's smallest
+                             * value is 1.6458115e-38, never 0: DESIGN.md section 2). */
     double factor;          /* 0.709 */
     int    cap_level;       /* START capacity of the per-(frame, pyramid level) candidate lists   [2048] */
     int    cap_frame;       /* START capacity of the per-frame box lists of stages 1-3           [2048]
                              * Lists are never longer than the geometry allows (a level has oh x ow cells) and grow with
                              * the content: a call whose frames need more is re-run internally with larger lists (and
                              * sorted / suppressed through a global-memory tier beyond the LDS tier), never refused. */
-    int    max_faces;       /* max boxes returned per frame by trl_mtcnn_detect          [64]   */
+    int    max_faces;       /* max boxes returned per frame by trl_mtcnn_detect          [64]
+                             * (>= 1).  It bounds the rows RETURNED -- the second dimension of every [n][max_faces] output
+                             * and d_counts -- not the rows detected: the stages run on every box, and d_box / d_prob /
+                             * d_rect / d_valid / d_emb of trl_detect_embed (the largest face) do not depend on it. */
     int    pnet_mode;       /* 0 = fused PNet kernel, 1 = generic layer path (validation) */
     int    embed_mode;      /* 0 = reference: 80x80 INTER_LINEAR crop, BGR, /255 (model.py:41,57-58)  [default]
                              * 1 = SURVEY 8(f)-4 native mode: facenet-pytorch extract_face (160x160 area

@@ -22,12 +22,13 @@ def probs(expf, logits):
     expf = the oracle's orc_expf."""
     lg = np.asarray(logits, F32).reshape(len(logits), -1)
     out = np.empty(len(lg), F32)
-    for i in range(len(lg)):
-        a0, a1 = lg[i, 0], lg[i, 1]
-        m = max(a0, a1)
-        e0 = F32(expf(float(F32(a0 - m))))
-        e1 = F32(expf(float(F32(a1 - m))))
-        out[i] = F32(e1 / F32(e0 + e1))
+    with np.errstate(over="ignore"):                          # a0 - m may overflow to -inf, as in C: orc_expf clamps it
+        for i in range(len(lg)):
+            a0, a1 = lg[i, 0], lg[i, 1]
+            m = max(a0, a1)
+            e0 = F32(expf(float(F32(a0 - m))))
+            e1 = F32(expf(float(F32(a1 - m))))
+            out[i] = F32(e1 / F32(e0 + e1))
     return out
 
 
@@ -350,6 +351,48 @@ def build_case(kind, fam, n, part="level", seed=0, W=W0, H=H0):
             "n": n, "fam": fam}
 
 
+# Logit differences d = a1 - a0 that walk trl_softmax2_p1 over its whole range: equal logits, the smallest denormal, a difference
+# that rounds away next to 1, an ordinary one, both sides of the difference from which e1 / (e0 + e1) rounds to 1.0f (16.665...),
+# both sides of the exponent clamp at -87 and of the differences at which an unclamped exp turns denormal (-87.3) and zero (-103.97),
+# and differences far past both.
+RANGE_DIFFS = (0.0, 1e-45, 1e-8, 2.0, 16.6, 16.7, 17.4, 86.9, 87.0, 87.1, 88.7, 103.9, 104.0, 200.0, 1e4)
+RANGE_A0 = (0.0, -8.0, 3.25, 8.0)
+CLAMP_PROB = F32(1.6458115e-38)      # orc_expf(-87) / (1 + orc_expf(-87)): the smallest probability the reference softmax returns
+
+
+def range_logits(seed=3):
+    """Finite logit pairs (a0, a0 + d), f32: every RANGE_DIFFS difference and its negative at every RANGE_A0, the pair
+    (3e38, -3e38) and its mirror (the difference itself overflows to infinity), and 200 uniform differences in [-20, 20]."""
+    pairs = [(F32(a0), F32(a0) + F32(s * d)) for a0 in RANGE_A0 for d in RANGE_DIFFS for s in ((1,) if d == 0 else (1, -1))]
+    pairs += [(F32(3e38), F32(-3e38)), (F32(-3e38), F32(3e38))]
+    pairs += [(F32(0), d) for d in np.random.default_rng(seed).uniform(-20, 20, 200).astype(F32)]
+    lt = np.array(pairs, F32)
+    assert np.isfinite(lt).all()
+    return lt
+
+
+def range_case(kind, W=W0, H=H0, seed=3):
+    """A kind 2 / 3 hook input of one frame whose logits are range_logits(): disjoint 10 x 10 boxes on a 16-px lattice well inside
+    the frame (NMS and the pad test remove nothing: what comes out is decided by the probabilities alone), regression offsets zero
+    on two rows of three and small dyadic values on the third, dyadic landmarks."""
+    lt = range_logits(seed)
+    k = len(lt)
+    rng = np.random.default_rng(seed + 101 * kind)
+    cols = W // 16 - 2
+    assert k <= cols * (H // 16 - 2)
+    cell = rng.permutation(cols * (H // 16 - 2))[:k]
+    x, y = F32(16) * (cell % cols + 1).astype(F32), F32(16) * (cell // cols + 1).astype(F32)
+    boxes = np.stack([x, y, x + 10, y + 10], 1).astype(F32)
+    L = np.zeros((k, 6 if kind == 2 else 16), F32)
+    L[:, :2] = lt
+    L[:, 2:6] = rng.integers(-2, 3, (k, 4)).astype(F32) / F32(32) * (np.arange(k) % 3 == 0)[:, None]
+    if kind == 3:
+        L[:, 6:] = rng.integers(0, 17, (k, 10)).astype(F32) / F32(16)
+    rows = np.concatenate([boxes, np.linspace(0.99, 0.61, k).astype(F32)[:, None]], 1).astype(F32)
+    return {"kind": kind, "W": W, "H": H, "caps": [_round4(k)], "counts": np.array([k], np.int32), "rows": [rows], "logits": [L],
+            "n": k, "fam": "range"}
+
+
 def hook_args(case, order=None):
     """(caps, counts, rows, logits, sent) in the hook's packed layout; kind 1 records in append order `order` per list (a
     permutation seed; None = as built), sent[f][l] = the records of each list as sent (what the keep indices index)."""
@@ -364,9 +407,9 @@ def hook_args(case, order=None):
     return case["caps"], case["counts"], np.concatenate(case["rows"]), np.concatenate(case["logits"]), None
 
 
-def reference(case, expf, max_faces=None):
+def reference(case, expf, max_faces=None, thr=0.7):
     """What detect_face computes for the case, per frame: kind 1 {"keep_cells": per level, "rows1"}, kind 2 {"rows2"},
-    kind 3 {"rows3", "pts3", "sel"}."""
+    kind 3 {"rows3", "pts3", "sel"}.  thr: the stage's own threshold (kinds 2 and 3), any float."""
     out = []
     W, H = case["W"], case["H"]
     if case["kind"] == 1:
@@ -377,9 +420,9 @@ def reference(case, expf, max_faces=None):
     for rows, lg in zip(case["rows"], case["logits"]):
         p = probs(expf, lg) if len(lg) else np.zeros(0, F32)
         if case["kind"] == 2:
-            out.append({"rows2": stage2(rows, p, lg[:, 2:6], W, H)})
+            out.append({"rows2": stage2(rows, p, lg[:, 2:6], W, H, thr)})
         else:
-            r3, p3 = stage3(rows, p, lg[:, 2:6], lg[:, 6:16])
+            r3, p3 = stage3(rows, p, lg[:, 2:6], lg[:, 6:16], thr)
             out.append({"rows3": r3, "pts3": p3, "sel": select(r3, p3, W, H, max_faces or 1)})
     return out
 

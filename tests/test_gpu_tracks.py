@@ -3,7 +3,9 @@
 Every comparison is bit for bit against the reference, and nothing is left out of one: the three per-row outputs, the whole track
 table, the per-track scores and the summary.  One-hot and dyadic embeddings make every similarity exact and integer-grid boxes make
 every IoU a known fraction, so every decision is known in advance (tests/test_tracks_cpu.py asserts what each clip is meant to
-do); the one-face clips are drift_ref's and must equal Engine.drift_update.  No window exceeds 70 frames, no clip ~600 rows."""
+do); the one-face clips are drift_ref's and must equal Engine.drift_update.  The dense clips (track_ref.dense_cases) are the
+opposite: nothing about them is exact, so the kernel's arithmetic and its hand-over of whole rows decide, and the state block is
+compared as well.  No window exceeds 70 frames, no clip ~600 rows."""
 import ctypes as C
 import os
 
@@ -46,8 +48,9 @@ def tracker_of(clip, device):
     return truely_amd.FaceTracker(clip["iou_min"], clip["sim_min"], clip["max_age"], device=device)
 
 
-def run_windows(trk, clip, cuts=()):
-    """The clip through FaceTracker.update in the windows cuts[k]..cuts[k+1] of its frames (0 and n are added)."""
+def run_windows(trk, clip, cuts=(), after=None):
+    """The clip through FaceTracker.update in the windows cuts[k]..cuts[k+1] of its frames (0 and n are added); ``after(b)`` is
+    called after the window that ends before frame b."""
     import torch
     counts = np.asarray(clip["counts"], np.int32)
     n = len(counts)
@@ -60,6 +63,8 @@ def run_windows(trk, clip, cuts=()):
     for a, b in zip(cuts[:-1], cuts[1:]) if n else [(0, 0)]:
         ra, rb = int(rows[a]), int(rows[b])
         outs.append(trk.update(d_boxes[ra:rb], d_counts[a:b], None if d_emb is None else d_emb[ra:rb]))
+        if after is not None:
+            after(b)
     return {k: torch.cat([o[k] for o in outs]).cpu().numpy() for k in ("track", "sim", "flag")}
 
 
@@ -268,6 +273,95 @@ def test_reset_after_another_clip(engine, name):
     run_windows(trk, other, [2])
     trk.reset()
     check(trk, run_windows(trk, clip, [1]), ref_of(name), name)
+
+
+# ---- dense embeddings and real-valued boxes ---------------------------------------------------------------------------------------
+# The clips of track_ref.dense_cases(): every one of an embedding's 512 elements is non-zero, n2 differs between slots by up to
+# 2^80, no box coordinate is an integer, and the gates stand on computed values.  tests/test_tracks_cpu.py holds the reference to
+# float64 and rational arithmetic on these clips and asserts what each contains; here the kernel equals the reference bit for bit.
+@pytest.mark.parametrize("name", T.DENSE + T.GATE_NAMES)
+def test_dense_clip(engine, name):
+    clip = T.dense_clip(name)
+    trk = tracker_of(clip, engine.device)
+    check(trk, run_windows(trk, clip), T.dense_ref(name), name)
+
+
+@pytest.mark.parametrize("name", T.DENSE)
+def test_dense_every_cut(engine, name):
+    """test_every_cut on the dense clips: the hand-over of 512 non-zero floats and their n2 per touched slot.  A track matched in
+    the first window is read from the state in the second; for dense8 a three-window cut has a track matched in the first, absent
+    for the whole second and matched from the state's copy, which the second window left alone, in the third."""
+    clip, ref = T.dense_clip(name), T.dense_ref(name)
+    n = len(clip["counts"])
+    trk = tracker_of(clip, engine.device)
+    for cut in range(1, n):
+        trk.reset()
+        check(trk, run_windows(trk, clip, [cut]), ref, (name, cut))
+    trk.reset()
+    check(trk, run_windows(trk, clip, range(n)), ref, (name, "windows of 1"))
+    if name == "dense8":
+        person, (a, b) = 1, (7, 9)                                                 # T.DENSE8_ABSENT: seen in frame 6, not in 7 and 8
+        frame = np.repeat(np.arange(n), clip["counts"])
+        ids = ref["track"][clip["person"] == person]
+        at = frame[clip["person"] == person]
+        assert ids[at == a - 1] == ids[at == b] and not ((frame >= a) & (frame < b) & (ref["track"] == ids[at == b])).any()
+        trk.reset()
+        check(trk, run_windows(trk, clip, [a, b]), ref, (name, "three windows"))
+
+
+def check_state(trk, snap, emb, what):
+    """The device's state block against track_ref.state_block of the reference's snapshot, bit for bit."""
+    got = trk._state.cpu().numpy().view(np.uint8)
+    want, compared = T.state_block(snap, emb)
+    first = 32 + 64 * T.SLOTS
+    assert got.shape == want.shape
+    assert np.array_equal(got[:32].view(np.int32), want[:32].view(np.int32)), (what, "header")
+    g, w = got[32:first].view(np.int32).reshape(T.SLOTS, 16), want[32:first].view(np.int32).reshape(T.SLOTS, 16)
+    for lo, hi, field in ((0, 7, "used, id, first_frame, last_frame, n_obs, run, hits"), (7, 8, "src"), (8, 12, "box bits"),
+                          (12, 13, "n2 bits"), (13, 16, "pad")):
+        assert np.array_equal(g[:, lo:hi], w[:, lo:hi]), (what, field)
+    g, w, c = (x[first:].reshape(T.SLOTS, 2048) for x in (got, want, compared))
+    for s in range(T.SLOTS):
+        if c[s].all():
+            assert np.array_equal(g[s], w[s]), (what, "embedding of slot", s)
+    assert np.array_equal(got[compared], want[compared]), what
+    return compared
+
+
+@pytest.mark.parametrize("name,cuts", (("dense8", (8,)), ("dense8", (14,)), ("dense8", None), ("dense_crowd", (2,)), ("dense_crowd", (4,)),
+                                       ("dense_crowd", None)))
+def test_state_after_each_window(engine, name, cuts):
+    """After every window of a two-window run and of a run in windows of one frame (cuts = None), the whole state block: the
+    header, every slot's integer fields with src == -1, its box and n2 bits and its padding, and all 512 floats of the embedding
+    of every used slot against the row the reference names.  A slot never used holds zeros.  Left out, and nothing else: the
+    embedding block of a slot that ageing has freed -- it keeps what the ended track left there, which nothing reads."""
+    clip, ref = T.dense_clip(name), T.dense_ref(name)
+    n = len(clip["counts"])
+    trk = tracker_of(clip, engine.device)
+    left_out = []
+    after = lambda b: left_out.append(int((~check_state(trk, ref["states"][b], clip["emb"], (name, cuts, b))).sum()))
+    check(trk, run_windows(trk, clip, range(n) if cuts is None else cuts, after), ref, (name, cuts))
+    assert len(left_out) == (n if cuts is None else 2)
+    if name == "dense8":                                                           # ageing has freed a slot by the clip's end
+        assert left_out[-1] >= 2048
+    assert (ref["states"][n]["slots"][:, 0] == 1).sum() == (8 if name == "dense8" else 64)
+
+
+def test_rows_past_64_with_dense_rows(engine):
+    """dense_crowd with NaN in the embeddings of detections 64 and 65 of every frame of 66: they come back as -1 / 2.0 / 0, and
+    the answer for the rows before them is the one with numbers there -- the dropped rows are never read."""
+    clip, ref = T.dense_clip("dense_crowd"), T.dense_ref("dense_crowd")
+    emb = clip["emb"].copy()
+    past = np.concatenate([66 * t + np.array([64, 65]) for t in range(4)])
+    emb[past] = np.nan
+    clip = dict(clip, emb=emb)
+    trk = tracker_of(clip, engine.device)
+    for cuts in ((), range(5)):
+        trk.reset()
+        got = run_windows(trk, clip, cuts)
+        assert (got["track"][past] == -1).all() and (got["sim"][past] == 2.0).all() and not got["flag"][past].any()
+        check(trk, got, ref, cuts)
+        check_state(trk, ref["states"][5], clip["emb"], cuts)
 
 
 # ---- Engine.track_faces -----------------------------------------------------------------------------------------------------------

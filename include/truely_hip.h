@@ -740,6 +740,46 @@ int    trl_track_update(void* d_state, const float* d_boxes, const int32_t* d_co
 int    trl_track_scores(const void* d_state, const int32_t* d_table, int table_cap, long long frame_count, int fps, int32_t* d_score,
                         int32_t* d_summary, void* stream);
 
+/* ---- Templates ("several embeddings of one person into one") -------------------------------------------------------------------------
+ * The segmented, optionally weighted mean of unit embeddings, keyed by a group id per row: an identity's enrolled rows, a track's
+ * frames, a cluster's members.  Stateless on a caller-owned device state, work queued on `stream`, no synchronisation, the device
+ * that of d_state / d_key.  (ABI v7, additive.)  The rule is DESIGN.md section 2, "Templates" (csrc/trl_pool.h is its code); in
+ * short, for a state that covers groups g0 .. g0 + groups - 1:
+ *   ignored      a row whose d_gid lies outside that range is counted nowhere (-1 labels; groups held by another state)
+ *   contributes  iff 0 < w <= 1 (1.0f without d_w; NaN fails) and its n2 -- trl_gallery_pack's chain -- is finite and >= FLT_MIN;
+ *                else the row is skipped and counted in the state's `skipped`
+ *   term         c = w / sqrtf(n2); q_k = (int64) rintf((c * x[k]) * 2^32); wq = (int64) rintf(w * 2^32)
+ *   sum          A[g][k] += q_k, W[g] += wq, N[g] += 1: integers, so the bits depend on the set of rows alone -- not on tile_rows,
+ *                the split of the rows into calls, their order, or the stream
+ *   finish       t_k = (float)A[g][k] * 2^-32; Wf = (float)W[g] * 2^-32; template = t / sqrtf(n2 t) (mode 0, unit) or t / Wf (mode 1,
+ *                mean); cohesion = sqrtf(n2 t) / Wf, the mean resultant length; count = N[g]; weight = Wf.  A group without rows:
+ *                +0, 0, 0, 0.  A sum that cancels to zero gives what the formulas give (unit: NaN, as a zero gallery row does).
+ * PRECONDITION: a group receives at most 2^30 contributing rows over the life of a state (|q_k| < 2^32 (1 + 2^-15), so that many
+ * fit an int64).  One call takes at most 2^30 rows; the total is the caller's to keep (EmbeddingPool counts the rows it adds).
+ *   d_state   trl_pool_state_bytes(groups) bytes, 8-byte aligned, zeroed by trl_pool_reset; the layout is private
+ *   rows      d_rows [m] rows of 512 f32, ld_rows >= 512 floats apart, 4-byte aligned; d_gid [m] int32; d_w [m] f32 or NULL;
+ *             d_n2 [m] f32 or NULL -- when given it MUST hold trl_gallery_pack's bits for those rows (the caller guarantees it)
+ *   tile_rows rows per workgroup: 0 (the default, 32), 8, 16 or 32
+ * The representative of a group against a template row: among its contributing rows the one with the largest gallery cosine
+ * chain(x, T_g) / (sqrtf(n2 T_g) * sqrtf(n2 x)) -- trl_gallery_scores' bits for query T_g -- ties as floats (-0 == +0) to the lower
+ * row index row0 + i, a NaN cosine never chosen; a group without a candidate gives index -1 and score NaN.  d_key [groups] is
+ * zeroed by trl_pool_rep_reset and takes any number of trl_pool_rep_add calls; d_template [groups][512] is that state's result.
+ * TRL_ERR_INVALID with nothing queued: a null pointer where one is needed, a negative size, groups > 2^31 - 1, ld_rows < 512,
+ * m > 2^30, row0 + m > 2^31 - 1, an unsupported tile_rows, a mode other than 0 or 1, a state or key not 8-byte aligned.  m = 0 does
+ * nothing. */
+size_t trl_pool_state_bytes(long long groups);                                   /* 0 on bad arguments */
+int    trl_pool_reset(void* d_state, long long groups, void* stream);
+int    trl_pool_add(void* d_state, long long groups, long long g0, const float* d_rows, long long ld_rows, const float* d_n2,
+                    const int32_t* d_gid, const float* d_w, long long m, int tile_rows, void* stream);
+/* d_template [groups][512] f32, d_count [groups] int32, d_weight / d_cohesion [groups] f32, d_skipped (or NULL) one int64 */
+int    trl_pool_finish(const void* d_state, long long groups, int mode, float* d_template, int32_t* d_count, float* d_weight,
+                       float* d_cohesion, long long* d_skipped, void* stream);
+int    trl_pool_rep_reset(unsigned long long* d_key, long long groups, void* stream);
+int    trl_pool_rep_add(unsigned long long* d_key, long long groups, long long g0, const float* d_template, const float* d_rows,
+                        long long ld_rows, const float* d_n2, const int32_t* d_gid, const float* d_w, long long row0, long long m,
+                        int tile_rows, void* stream);
+int    trl_pool_rep_finish(const unsigned long long* d_key, long long groups, int32_t* d_index, float* d_score, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,13 +3,14 @@
 (InceptionResnetV1) embedding -> consecutive-frame cosine drift -> 0..100 score -- and, for the embeddings,
 FaceGallery / pairwise / cluster_embeddings: enrolment, distance tables, top-k identification, DBSCAN clustering and score
 histograms (threshold calibration: roc_from_counts / threshold_at_far) on the device; FaceTracker associates every face of a
-clip's frames into tracks and keeps the drift state machine per person.
+clip's frames into tracks and keeps the drift state machine per person; EmbeddingPool / pool_embeddings pool the embeddings of an
+identity, a track or a cluster into one exact template.
 
 Importable as ``truely_amd`` (see truely_amd.py at the repository root; the directory name
 required by the build contract is not a valid Python identifier)."""
 from . import weights, synthetic  # noqa: F401  (pure numpy, usable without a GPU)
 
-__all__ = ["weights", "synthetic", "Engine", "MTCNN", "InceptionResnetV1", "FaceGallery", "FaceTracker", "pairwise", "cluster_embeddings", "roc_from_counts", "threshold_at_far", "run", "analyze_video"]
+__all__ = ["weights", "synthetic", "Engine", "MTCNN", "InceptionResnetV1", "FaceGallery", "FaceTracker", "EmbeddingPool", "pool_embeddings", "pairwise", "cluster_embeddings", "roc_from_counts", "threshold_at_far", "run", "analyze_video"]
 
 
 def __getattr__(name):
@@ -26,6 +27,9 @@ def __getattr__(name):
     if name in ("FaceGallery", "pairwise", "cluster_embeddings", "roc_from_counts", "threshold_at_far"):
         from . import gallery
         return getattr(gallery, name)
+    if name in ("EmbeddingPool", "pool_embeddings"):
+        from . import pool
+        return getattr(pool, name)
     if name == "FaceTracker":
         from .tracker import FaceTracker
         return FaceTracker

@@ -136,6 +136,14 @@ _SIGNATURES = {
                                             _i, _vp]),
     "trl_track_update": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "trl_track_scores": (C.c_int, [_vp, _vp, _i, C.c_longlong, _i, _vp, _vp, _vp]),
+    "trl_pool_state_bytes": (C.c_size_t, [C.c_longlong]),
+    "trl_pool_reset": (C.c_int, [_vp, C.c_longlong, _vp]),
+    "trl_pool_add": (C.c_int, [_vp, C.c_longlong, C.c_longlong, _vp, C.c_longlong, _vp, _vp, _vp, C.c_longlong, _i, _vp]),
+    "trl_pool_finish": (C.c_int, [_vp, C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "trl_pool_rep_reset": (C.c_int, [_vp, C.c_longlong, _vp]),
+    "trl_pool_rep_add": (C.c_int, [_vp, C.c_longlong, C.c_longlong, _vp, _vp, C.c_longlong, _vp, _vp, _vp, C.c_longlong, C.c_longlong,
+                                   _i, _vp]),
+    "trl_pool_rep_finish": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

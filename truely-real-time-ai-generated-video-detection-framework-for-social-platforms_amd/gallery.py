@@ -23,7 +23,9 @@ from them the accept rates at every candidate threshold (``roc_from_counts``, ``
 gallery index -- two streamed passes, count then store, and still no score matrix.  A gallery that enrols several rows per person
 (a few photos, every good frame of a clip) has ``identities``: the distinct labels in order of first enrolment.
 ``search_identities`` / ``identify_topk`` give the k best distinct identities per query, each with its best row -- "the five most
-likely people", not five rows of one -- in one streamed pass as well.  Embeddings never visit the host."""
+likely people", not five rows of one -- in one streamed pass as well.  ``templates`` pools each identity's rows into one exact
+template (pool.py) and returns the gallery of those, one row per person; ``representatives`` names each identity's most typical
+enrolled row.  Embeddings never visit the host."""
 from __future__ import annotations
 
 import ctypes as C
@@ -40,6 +42,7 @@ MAX_CLUSTER_LIST_ROWS = 1 << 24
 CLUSTER_METHODS = ("auto", "bitmap", "lists")
 MAX_EDGES = 1023
 DIM = 512
+TEMPLATE_CHUNK = 8192                    # gallery columns turned into rows at a time by templates(): 16 MB
 
 
 def _ptr(t):
@@ -221,9 +224,51 @@ class FaceGallery:
         scores = score.tolist()
         return [[(self._identities[g], s) for g, s in zip(gs, ss) if g >= 0] for gs, ss in zip(picks, scores)]
 
+    def _pooled(self, weights, gallery_valid, unit: bool, representative: bool, max_state_bytes: int) -> dict:
+        """The enrolled rows pooled per identity (pool.py).  The k-major matrix is read in column chunks, each turned into rows once,
+        with the n2 the gallery keeps: no second copy of the gallery, no second n2 pass."""
+        from . import pool
+        m, G = self._m, len(self._identities)
+        gv = _valid(gallery_valid, m, self.device)
+        gid = self._gid[:m]
+        if gv is not None:
+            gid = torch.where(gv != 0, gid, torch.full_like(gid, -1))         # (search_identities' fold: a masked row is an excluded row)
+        w = pool._vector(weights, m, torch.float32, self.device, "weights")
+
+        def blocks():
+            for a in range(0, m, TEMPLATE_CHUNK):
+                b = min(a + TEMPLATE_CHUNK, m)
+                yield a, self._mat[:, a:b].t().contiguous(), self._n2[a:b]
+
+        return pool._pool_blocks(self.device, blocks, m, gid, w, G, unit, representative, max_state_bytes, 0)
+
+    def templates(self, weights=None, gallery_valid=None, unit: bool = True, representative: bool = False,
+                  max_state_bytes: int = 256 << 20):
+        """``(gallery, info)``: one template per identity.  ``gallery`` is a new ``FaceGallery`` of this metric and device that
+        holds, in ``identities`` order and labelled with the identity, the template of every identity with ``count > 0`` -- a
+        gallery with 20 rows per person becomes one a twentieth as wide to ``search`` / ``identify``.  ``info`` is
+        ``pool_embeddings``' dict over every identity (row g is ``identities[g]``): ``template``, ``count``, ``weight``,
+        ``cohesion``, ``skipped`` and, with ``representative=True``, ``representative`` (the enrolled row closest to its
+        identity's template, -1 without one) and ``rep_score``.  ``weights`` (len(self),) in (0, 1] weigh the rows; rows whose
+        ``gallery_valid`` entry is zero are left out, as in ``search_identities``.  ``count`` is read back to pick the rows: one
+        synchronisation."""
+        info = self._pooled(weights, gallery_valid, unit, representative, max_state_bytes)
+        keep = torch.nonzero(info["count"] > 0)[:, 0]
+        picks = keep.tolist()
+        g = FaceGallery(metric=self.metric, device=self.device, capacity=max(len(picks), 1))
+        g.add(info["template"][keep], [self._identities[i] for i in picks])
+        return g, info
+
+    def representatives(self, weights=None, gallery_valid=None, unit: bool = True) -> torch.Tensor:
+        """(len(identities),) int32 on the device: per identity its enrolled row closest to the identity's own template
+        (``templates(representative=True)``'s ``representative``); -1 for an identity without a contributing row.  No
+        synchronisation."""
+        return self._pooled(weights, gallery_valid, unit, True, 256 << 20)["representative"]
+
     def cluster(self, threshold: float, min_samples: int = 1, valid=None, return_info: bool = False, max_strip_cols: int = 0,
                 method: str = "auto", max_links: int | None = None):
         """DBSCAN labels of the enrolled rows, (len(self),) int32 on the device: "which of these are the same person?".
+        ``pool_embeddings(emb, labels)`` with these labels gives one template per cluster (noise, -1, is ignored there).
 
         Rows i != j are linked when their score passes ``threshold`` (identify's convention: cosine ``score >= threshold``,
         euclidean ``score <= threshold``, both in float32; a NaN score never links).  A row with at least ``min_samples`` rows in
@@ -463,7 +508,7 @@ def threshold_at_far(edges, tar, far, target: float, metric: str = "cosine"):
 def cluster_embeddings(emb, threshold: float, metric: str = "cosine", min_samples: int = 1, valid=None, device=None,
                        return_info: bool = False, method: str = "auto", max_links: int | None = None):
     """``FaceGallery.cluster`` for loose embeddings, (n, 512): the faces of a clip, an enrolment set to de-duplicate.  ``method``
-    and ``max_links`` are ``cluster``'s."""
+    and ``max_links`` are ``cluster``'s.  ``pool_embeddings(emb, labels)`` with the labels gives one template per cluster."""
     if device is None:
         device = emb.device if isinstance(emb, torch.Tensor) and emb.device.type == "cuda" else None
     g = FaceGallery(metric=metric, device=device, capacity=max(len(emb), 1))

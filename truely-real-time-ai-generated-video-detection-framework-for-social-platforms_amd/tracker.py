@@ -7,6 +7,8 @@
     trk.tracks(frame_count, fps)                                  # per track: id, first_frame, last_frame, n_obs, run, hits, score
     trk.score(frame_count, fps)                                   # the clip's multi-face score: the maximum over its tracks
 
+``FaceTracker(templates=True)`` also pools every track's embeddings into one exact template (pool.py): ``trk.templates()``, and
+``trk.identify_tracks(gallery)`` names each track once instead of each frame.
 ``Engine.track_faces(frames, tracker)`` is the three calls of the loop body.  ``run()`` / ``analyze_video`` do not use this: they
 keep the reference's largest-face drift (``Engine.drift_update``), in which two people in one clip read as drift.
 
@@ -63,7 +65,7 @@ class FaceTracker:
     """The tracks of ONE clip (``reset()`` starts another).  State, table and outputs live on the device; ``update`` queues one
     kernel on the current stream and does not synchronise."""
 
-    def __init__(self, iou_min: float = 0.1, sim_min: float = 0.4, max_age: int = 3, device=None):
+    def __init__(self, iou_min: float = 0.1, sim_min: float = 0.4, max_age: int = 3, device=None, templates: bool = False):
         if not (0 <= int(max_age) <= INT32_MAX):
             raise ValueError("max_age must be in 0 .. 2**31 - 1")
         if np.isnan(iou_min) or np.isnan(sim_min):
@@ -78,19 +80,31 @@ class FaceTracker:
         self._state = torch.zeros((STATE_BYTES // 8,), dtype=torch.int64, device=self.device)
         self._table = torch.zeros((256, 8), dtype=torch.int32, device=self.device)
         self._id_bound = 0                                # next_id <= this: a row starts at most one track
+        self._pool = None
+        if templates:                                     # one pooled template per track id (pool.py); it grows with the table
+            from .pool import EmbeddingPool
+            self._pool = EmbeddingPool(self._table.shape[0], self.device)
 
     def reset(self) -> None:
         """Forget the clip: the next update is a clip's first window.  No synchronisation."""
         self._state.zero_()
         self._table.zero_()
         self._id_bound = 0
+        if self._pool is not None:
+            self._pool.reset()
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def update(self, boxes, counts, emb=None) -> dict:
+    def update(self, boxes, counts, emb=None, weights=None) -> dict:
         """The clip's next window: ``boxes`` (m, 4), ``counts`` (n,), ``emb`` (m, 512) or None (every window of a clip alike).
-        -> ``track`` (m,) int32, ``sim`` (m,) float32, ``flag`` (m,) uint8 on the device."""
+        -> ``track`` (m,) int32, ``sim`` (m,) float32, ``flag`` (m,) uint8 on the device.  A tracker made with ``templates=True``
+        needs ``emb`` and then pools the window's rows by the track ids just written (rows without a track are ignored), each
+        weighed by ``weights`` (m,) in (0, 1] -- ``probs``, for one -- or 1."""
+        if self._pool is None and weights is not None:
+            raise ValueError("weights belong to the templates: make the tracker with templates=True")
+        if self._pool is not None and emb is None:
+            raise ValueError("a tracker with templates=True needs the embeddings of every window")
         d = self.device
         boxes = torch.as_tensor(boxes).to(d, torch.float32).reshape(-1, 4).contiguous()
         counts = torch.as_tensor(counts).to(d, torch.int32).reshape(-1).contiguous()
@@ -111,7 +125,35 @@ class FaceTracker:
                                              _ptr(emb), self.iou_min, self.sim_min,
                                              self.max_age, _ptr(track), _ptr(sim), _ptr(flag), _ptr(self._table), self._table.shape[0],
                                              self._stream()))
+        if self._pool is not None:
+            if self._pool.num_groups < self._table.shape[0]:
+                self._pool.grow(self._table.shape[0])
+            self._pool.add(emb, track, weights)
         return {"track": track, "sim": sim, "flag": flag}
+
+    def _num_tracks(self) -> int:
+        """The number of tracks created so far: one synchronisation."""
+        cap = self._table.shape[0]
+        score = torch.empty((cap,), dtype=torch.int32, device=self.device)
+        summary = torch.empty((4,), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.trl_track_scores(_ptr(self._state), _ptr(self._table), cap, 1, 1, _ptr(score), _ptr(summary), self._stream()))
+        return int(summary[2].item())
+
+    def templates(self, unit: bool = True) -> dict:
+        """``templates=True``: the pooled embeddings of the clip's tracks so far, ``EmbeddingPool.result``'s dict with row = track
+        id -- ``template``, ``count``, ``weight``, ``cohesion`` (1: every frame of the track the same face; low: a contaminated
+        track), ``skipped``.  The bits are ``pool_embeddings(all rows, all track ids)``', however the clip was cut into windows.
+        One synchronisation (the number of tracks)."""
+        if self._pool is None:
+            raise ValueError("make the tracker with templates=True")
+        r, n = self._pool.result(unit), self._num_tracks()
+        return {k: (v if k == "skipped" else v[:n]) for k, v in r.items()}
+
+    def identify_tracks(self, gallery, threshold: float | None = None):
+        """"Who is track 3?", once per track: ``gallery.identify`` of the tracks' templates -> (labels, score), entry = track id;
+        a track without a contributing row is None."""
+        t = self.templates()
+        return gallery.identify(t["template"], threshold, valid=t["count"] > 0)
 
     def _scores(self, frame_count: int, fps: int) -> np.ndarray:
         """[summary (4), table rows (bound x 8), scores (bound)] as one host array: one synchronisation."""

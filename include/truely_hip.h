@@ -780,6 +780,59 @@ int    trl_pool_rep_add(unsigned long long* d_key, long long groups, long long g
                         int tile_rows, void* stream);
 int    trl_pool_rep_finish(const unsigned long long* d_key, long long groups, int32_t* d_index, float* d_score, void* stream);
 
+/* ---- Face quality ("how good is this face": sharpness, exposure, pose, size; the best shot of a group) ------------------------------
+ * Context-free, work queued on `stream`, no synchronisation, the device that of d_ws / d_keys.  (ABI v7, additive.)  The rule is
+ * DESIGN.md section 2, "Face quality" (csrc/trl_quality.h is its code): every measure is an integer sum over the source pixels of
+ * a face's rectangle or a short float chain of + - * / sqrt in a fixed order, so a result is the same bits for any max_band_rows,
+ * any stream and whatever the workspace held before.  Per face row r, over frames d_frames [n][H][W][3] u8 BGR:
+ *   rectangle  X0 = clamp((int)floorf(x1), 0, W), X1 = clamp((int)ceilf(x2), 0, W), the same for y.  status 0 -- every output of
+ *              the row 0 -- for d_frame_of[r] outside 0 .. n - 1, a NaN or infinite coordinate, or X1 <= X0 || Y1 <= Y0; else
+ *              status 1, w = X1 - X0, h = Y1 - Y0, N = w h
+ *   luma       Y = (1868 B + 9617 G + 4899 R + 8192) >> 14                (OpenCV's 8-bit COLOR_BGR2GRAY as recalled: UNPINNED)
+ *   Laplacian  L = Y[y-1][x] + Y[y+1][x] + Y[y][x-1] + Y[y][x+1] - 4 Y[y][x], neighbours INSIDE the rectangle by reflect-101
+ *              (-1 -> 1, len -> len - 2, a single sample its own neighbour)       (cv2.Laplacian, ksize 1, as recalled: UNPINNED)
+ *   d_raw      [m][8] int64: N, sum Y, sum Y^2, sum L, sum L^2, n_dark (Y <= 15), n_bright (Y >= 240), w
+ *   d_hist     [m][256] int32 or NULL: the histogram of Y;  p05 / p95: the smallest v with 20 cum(v) >= N / >= 19 N
+ *   d_feat     [m][12] f32: quality, sharpness, mean_luma, dark_frac, bright_frac, contrast, yaw, pitch, roll, iod, p05, p95
+ *              sharpness = (float)((double)SL2 / N - ((double)SL / N)^2), the variance of the Laplacian; mean_luma and the two
+ *              fractions (float)((double)sum / N); contrast = p95 - p05
+ *   pose       from d_points [m][10] = x0..x4, y0..y4 (eyes, nose, mouth corners: trl_mtcnn_detect_landmarks' layout), RATIOS, no
+ *              atan: e = eyeR - eyeL, iod = sqrtf(e.e), roll = e.y / iod, yaw = 2 ((nose - eyeL).e / e.e) - 1, pitch = 2 ((nose -
+ *              eyeMid).v / v.v) - 1 with v = mouthMid - eyeMid; all NaN for a non-finite point or e.e == 0 or v.v == 0, and
+ *              without d_points
+ *   quality    ((q_sharp q_expo) q_pose) q_size in [0, 1]: q_sharp = min(max(0, sharpness) / sharp_ref, 1), q_expo = max(0, 1 -
+ *              (dark_frac + bright_frac) / clip_ref) min(contrast / contrast_ref, 1), q_pose = max(0, 1 - |yaw| / yaw_ref) max(0, 1 -
+ *              |pitch| / pitch_ref) (0 when either is NaN, 1 without d_points), q_size = min(min(w, h) / size_ref, 1).  A status-0
+ *              row has quality 0, which trl_pool_add skips as a weight.
+ * The defaults of the references (params = NULL: the values beside the struct's fields) are PLACEHOLDERS, not calibrated figures.
+ *   d_ws          trl_quality_workspace(m) bytes, 8-byte aligned; its contents before the call do not matter
+ *   max_band_rows rows of a rectangle one workgroup takes through LDS at a time: 0 = the library's choice; any value >= 1 gives
+ *                 the same bits (a test knob)
+ * TRL_ERR_INVALID with nothing queued: a null pointer where one is needed, n < 0, m outside 0 .. 2^24, H or W outside 1 .. 16384,
+ * max_band_rows < 0, a reference that is not finite and > 0, a workspace too small or not 8-byte aligned.  m = 0 does nothing. */
+typedef struct {
+    float sharp_ref;        /* 100   variance of the Laplacian that counts as fully sharp */
+    float clip_ref;         /* 0.5   fraction of clipped (dark + bright) pixels at which the exposure term reaches 0 */
+    float contrast_ref;     /* 64    p95 - p05 that counts as full contrast */
+    float yaw_ref;          /* 1     |yaw| at which the pose term reaches 0 (1: the nose over an eye) */
+    float pitch_ref;        /* 1     |pitch| at which the pose term reaches 0 */
+    float size_ref;         /* 80    min(w, h) in source pixels that counts as full size */
+} trl_quality_params;
+size_t trl_quality_workspace(long long m);                                       /* 0 on bad arguments */
+int    trl_face_quality(const uint8_t* d_frames, int n, int H, int W, const int32_t* d_frame_of, const float* d_boxes,
+                        const float* d_points, long long m, const trl_quality_params* params, int max_band_rows, void* d_ws,
+                        size_t ws_bytes, long long* d_raw, float* d_feat, int32_t* d_hist, int32_t* d_status, void* stream);
+/* Best shots: d_keys [groups] u64, zeroed by the caller for "none", keeps per group the row with the largest quality -- the key of
+ * the templates' representative: ties as floats (-0 == +0) to the lower absolute row row_base + r, a NaN never a candidate, a row
+ * whose d_gid lies outside 0 .. groups - 1 ignored.  With d_faces [m][face_floats] f32 and d_best_faces [groups][face_floats], a
+ * row that is its group's best after this call's rows is copied to its group's slot.  Any split of the rows into calls, in row
+ * order on one stream, leaves the same keys and faces.  trl_best_read decodes the keys: d_row (-1 for none), d_quality (NaN for none).
+ * TRL_ERR_INVALID: null d_keys (or d_quality / d_gid with m > 0), d_keys not 8-byte aligned, a negative size, groups > 2^31 - 1,
+ * row_base + m > 2^31 - 1, one of d_faces / d_best_faces without the other, face_floats < 1 with faces. */
+int    trl_best_update(unsigned long long* d_keys, long long groups, const float* d_quality, const int32_t* d_gid, long long m,
+                       long long row_base, const float* d_faces, long long face_floats, float* d_best_faces, void* stream);
+int    trl_best_read(const unsigned long long* d_keys, long long groups, int32_t* d_row, float* d_quality, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,10 @@ class TrlJpegOptions(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("quality", "subsampling", "restart_rows", "restart_blocks", "optimize")]
 
 
+class TrlQualityParams(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("sharp_ref", "clip_ref", "contrast_ref", "yaw_ref", "pitch_ref", "size_ref")]
+
+
 class TrlRzHit(C.Structure):
     _fields_ = [("arena", C.c_int32), ("block", C.c_int32), ("site", C.c_char * 24)] + \
                [(n, C.c_longlong) for n in ("block_bytes", "gap_off", "gap_bytes", "first", "last", "count")]
@@ -144,6 +148,11 @@ _SIGNATURES = {
     "trl_pool_rep_add": (C.c_int, [_vp, C.c_longlong, C.c_longlong, _vp, _vp, C.c_longlong, _vp, _vp, _vp, C.c_longlong, C.c_longlong,
                                    _i, _vp]),
     "trl_pool_rep_finish": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp]),
+    "trl_quality_workspace": (C.c_size_t, [C.c_longlong]),
+    "trl_face_quality": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, C.c_longlong, C.POINTER(TrlQualityParams), _i, _vp, C.c_size_t, _vp, _vp,
+                                   _vp, _vp, _vp]),
+    "trl_best_update": (C.c_int, [_vp, C.c_longlong, _vp, _vp, C.c_longlong, C.c_longlong, _vp, C.c_longlong, _vp, _vp]),
+    "trl_best_read": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -152,18 +152,25 @@ class Engine:
         return out.permute(0, 3, 1, 2), status
 
     def extract_faces(self, frames, image_size: int = 160, margin: int = 0, resample: str = "torch", post_process: bool = True,
-                      keep_all: bool = False, select_largest: bool = True, selection_method: str | None = None) -> dict:
+                      keep_all: bool = False, select_largest: bool = True, selection_method: str | None = None, quality: bool = False,
+                      quality_params=None) -> dict:
         """facenet-pytorch ``MTCNN(image_size, margin, post_process, select_largest, selection_method, keep_all)(frames)`` for a
         batch, device-resident.  resample: the input kind crop_resize sees ('torch' tensor, 'pil' image, 'cv2' numpy array).
         Returns device tensors: ``faces`` [m, 3, S, S] f32 (a permuted view of NHWC rows, the layout facenet_embed reads),
         ``frame`` [m] (frame of each row, -1 for none), ``box`` [m, 4], ``prob`` [m], ``status`` [m] (1 face, 0 none, -1 empty crop:
         the library raises), and ``valid`` [n] uint8 (keep_all=False: row i is frame i) or ``counts`` [n] (keep_all=True: the
         rows of every face, frame by frame in detect's order).  keep_all=False makes no host synchronisation after detect's;
-        keep_all=True makes one, for the number of faces."""
+        keep_all=True makes one, for the number of faces.  ``quality=True``: detection runs with landmarks, and the dict gains
+        ``points`` [m, 10] and ``face_quality``'s entries for the rows (quality.py: ``quality`` [m] in [0, 1], ``sharpness``, ...,
+        ``feat``, ``raw``; its ``status`` as ``quality_status``); a row without a face has quality 0."""
         fr = self._frames(frames)
         n = fr.shape[0]
         H, W = fr.shape[1], fr.shape[2]
-        boxes, probs, counts = self.mtcnn_detect(fr, select_largest=select_largest)
+        points = None
+        if quality:
+            boxes, probs, counts, points = self.mtcnn_detect(fr, landmarks=True, select_largest=select_largest)
+        else:
+            boxes, probs, counts = self.mtcnn_detect(fr, select_largest=select_largest)
         d = self.device
         if keep_all:
             total = int(counts.sum().item())                  # the one synchronisation: the face count sizes the outputs
@@ -171,29 +178,52 @@ class Engine:
             frame = torch.repeat_interleave(torch.arange(n, device=d), c64, output_size=total)
             slot = torch.arange(total, device=d) - (torch.cumsum(c64, 0) - c64)[frame]
             box, prob, frame_of = boxes[frame, slot], probs[frame, slot], frame.int()
+            pts = points[frame, slot] if quality else None
         else:
             method = selection_method or ("largest" if select_largest else "probability")
             pick = self.select_faces(boxes, probs, counts, H, W, method)
             idx, rows = pick.clamp(min=0).long(), torch.arange(n, device=d)
             box, prob = boxes[rows, idx], probs[rows, idx]
             frame_of = torch.where(pick >= 0, rows.int(), torch.full_like(pick, -1))
+            pts = points[rows, idx] if quality else None
         faces, status = self.extract_boxes(fr, frame_of, box, image_size, margin, resample, post_process)
         out = {"faces": faces, "frame": frame_of, "box": box, "prob": prob, "status": status}
         if keep_all:
             out["counts"] = counts
         else:
             out["valid"] = (status == 1).to(torch.uint8)
+        if quality:
+            q = self.face_quality(fr, frame_of, box, pts, params=quality_params)
+            q["quality_status"] = q.pop("status")
+            out["points"] = pts
+            out.update(q)
         return out
 
-    def track_faces(self, frames, tracker, **extract_kwargs) -> dict:
+    def face_quality(self, frames, frame_of, boxes, points=None, params=None, return_hist: bool = False, max_band_rows: int = 0) -> dict:
+        """``quality.face_quality`` on this engine's device: per face row (frame_of [m], boxes [m, 4], points [m, 10] or None) the
+        quality in [0, 1] and its measures -- sharpness, exposure, pose, size -- as device tensors.  No synchronisation."""
+        from .quality import face_quality
+        return face_quality(self._frames(frames), frame_of, boxes, points, params, return_hist, max_band_rows, self.device)
+
+    def track_faces(self, frames, tracker, quality: bool = False, **extract_kwargs) -> dict:
         """Every face of a window of sampled frames, embedded and associated with the clip's tracks: ``extract_faces(frames,
         keep_all=True, **extract_kwargs)``, ``facenet_embed`` of its faces, ``tracker.update(box, counts, emb)`` (a
         :class:`~truely_amd.tracker.FaceTracker` that has seen the clip's earlier windows).  Returns the extraction's dict plus
-        ``emb`` [m, 512], ``track`` [m], ``sim`` [m], ``flag`` [m]."""
-        out = self.extract_faces(frames, keep_all=True, **extract_kwargs)
+        ``emb`` [m, 512], ``track`` [m], ``sim`` [m], ``flag`` [m].  ``quality=True``: the extraction measures every face
+        (``extract_faces(quality=True)``) and its ``quality`` goes to the tracker -- as the rows' weights when it keeps templates,
+        and with the faces when it keeps best shots."""
+        if not quality:
+            out = self.extract_faces(frames, keep_all=True, **extract_kwargs)
+            emb = self.facenet_embed(out["faces"].permute(0, 2, 3, 1))
+            out["emb"] = emb
+            out.update(tracker.update(out["box"], out["counts"], emb))
+            return out
+        out = self.extract_faces(frames, keep_all=True, quality=True, **extract_kwargs)
         emb = self.facenet_embed(out["faces"].permute(0, 2, 3, 1))
         out["emb"] = emb
-        out.update(tracker.update(out["box"], out["counts"], emb))
+        has_best = getattr(tracker, "_best", None) is not None
+        out.update(tracker.update(out["box"], out["counts"], emb, weights=out["quality"] if tracker._pool is not None else None,
+                                  quality=out["quality"] if has_best else None, faces=out["faces"] if has_best else None))
         return out
 
     # server/model.py:59 for a batch; faces f32 (n, h, w, 3) NHWC in [0,1]

@@ -8,7 +8,8 @@
     trk.score(frame_count, fps)                                   # the clip's multi-face score: the maximum over its tracks
 
 ``FaceTracker(templates=True)`` also pools every track's embeddings into one exact template (pool.py): ``trk.templates()``, and
-``trk.identify_tracks(gallery)`` names each track once instead of each frame.
+``trk.identify_tracks(gallery)`` names each track once instead of each frame.  ``FaceTracker(best_shots=True)`` keeps, per track,
+the row of the largest ``quality`` (quality.py) and its face: ``trk.best_shots()``, the thumbnail of a report or an enrolment.
 ``Engine.track_faces(frames, tracker)`` is the three calls of the loop body.  ``run()`` / ``analyze_video`` do not use this: they
 keep the reference's largest-face drift (``Engine.drift_update``), in which two people in one clip read as drift.
 
@@ -65,7 +66,8 @@ class FaceTracker:
     """The tracks of ONE clip (``reset()`` starts another).  State, table and outputs live on the device; ``update`` queues one
     kernel on the current stream and does not synchronise."""
 
-    def __init__(self, iou_min: float = 0.1, sim_min: float = 0.4, max_age: int = 3, device=None, templates: bool = False):
+    def __init__(self, iou_min: float = 0.1, sim_min: float = 0.4, max_age: int = 3, device=None, templates: bool = False,
+                 best_shots: bool = False):
         if not (0 <= int(max_age) <= INT32_MAX):
             raise ValueError("max_age must be in 0 .. 2**31 - 1")
         if np.isnan(iou_min) or np.isnan(sim_min):
@@ -84,6 +86,10 @@ class FaceTracker:
         if templates:                                     # one pooled template per track id (pool.py); it grows with the table
             from .pool import EmbeddingPool
             self._pool = EmbeddingPool(self._table.shape[0], self.device)
+        self._best = None
+        if best_shots:                                    # the best row per track id (quality.py); it grows with the table too
+            from .quality import BestShots
+            self._best = BestShots(self._table.shape[0], self.device)
 
     def reset(self) -> None:
         """Forget the clip: the next update is a clip's first window.  No synchronisation."""
@@ -92,15 +98,23 @@ class FaceTracker:
         self._id_bound = 0
         if self._pool is not None:
             self._pool.reset()
+        if self._best is not None:
+            self._best.reset()
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def update(self, boxes, counts, emb=None, weights=None) -> dict:
+    def update(self, boxes, counts, emb=None, weights=None, quality=None, faces=None) -> dict:
         """The clip's next window: ``boxes`` (m, 4), ``counts`` (n,), ``emb`` (m, 512) or None (every window of a clip alike).
         -> ``track`` (m,) int32, ``sim`` (m,) float32, ``flag`` (m,) uint8 on the device.  A tracker made with ``templates=True``
         needs ``emb`` and then pools the window's rows by the track ids just written (rows without a track are ignored), each
-        weighed by ``weights`` (m,) in (0, 1] -- ``probs``, for one -- or 1."""
+        weighed by ``weights`` (m,) in (0, 1] -- ``face_quality``'s ``quality``, for one -- or 1.  A tracker made with
+        ``best_shots=True`` needs ``quality`` (m,) for every window and keeps, per track id, the row of the largest quality and --
+        when ``faces`` (m, 3, S, S) come with every window -- that row's face."""
+        if self._best is None and (quality is not None or faces is not None):
+            raise ValueError("quality and faces belong to the best shots: make the tracker with best_shots=True")
+        if self._best is not None and quality is None:
+            raise ValueError("a tracker with best_shots=True needs the quality of every window")
         if self._pool is None and weights is not None:
             raise ValueError("weights belong to the templates: make the tracker with templates=True")
         if self._pool is not None and emb is None:
@@ -129,6 +143,15 @@ class FaceTracker:
             if self._pool.num_groups < self._table.shape[0]:
                 self._pool.grow(self._table.shape[0])
             self._pool.add(emb, track, weights)
+        if self._best is not None:
+            if self._best.num_groups < self._table.shape[0]:
+                self._best.grow(self._table.shape[0])
+            if faces is not None and faces.dim() == 4 and faces.permute(0, 2, 3, 1).is_contiguous():
+                faces = faces.permute(0, 2, 3, 1)          # (extract_faces' view of NHWC rows: kept as they lie, without a copy)
+                self._best_nhwc = True
+            elif faces is not None:
+                self._best_nhwc = False
+            self._best.add(quality, track, faces)
         return {"track": track, "sim": sim, "flag": flag}
 
     def _num_tracks(self) -> int:
@@ -148,6 +171,19 @@ class FaceTracker:
             raise ValueError("make the tracker with templates=True")
         r, n = self._pool.result(unit), self._num_tracks()
         return {k: (v if k == "skipped" else v[:n]) for k, v in r.items()}
+
+    def best_shots(self) -> dict:
+        """``best_shots=True``: per track of the clip so far, ``track`` (T,) its id, ``row`` (T,) int32 the absolute detection row
+        over the clip -- the rows of every update, in order -- with the largest quality (ties: the earlier row; -1: no row with a
+        quality that is not NaN), ``quality`` (T,) that quality (NaN for none) and, when the updates brought faces, ``face``
+        (T, 3, S, S), that row's face.  However the clip was cut into windows.  One synchronisation (the number of tracks)."""
+        if self._best is None:
+            raise ValueError("make the tracker with best_shots=True")
+        r, n = self._best.read(), self._num_tracks()
+        out = {"track": torch.arange(n, dtype=torch.int32, device=self.device), "row": r["row"][:n], "quality": r["quality"][:n]}
+        if "face" in r:
+            out["face"] = r["face"][:n].permute(0, 3, 1, 2) if getattr(self, "_best_nhwc", False) else r["face"][:n]
+        return out
 
     def identify_tracks(self, gallery, threshold: float | None = None):
         """"Who is track 3?", once per track: ``gallery.identify`` of the tracks' templates -> (labels, score), entry = track id;

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <vector>
 
+#include "trl_bestkey.h"
 #include "trl_pool.h"
 
 static float f32_of(uint32_t u) {
@@ -79,13 +80,13 @@ int main() {
             const long long g = (long long)gid[i] - g0;
             const float* T = &unit[(size_t)g * TRL_POOL_K];
             const float* xi = &x[(size_t)i * TRL_POOL_K];
-            const unsigned long long k = trl_pool_key(trl_pool_cosine(trl_pool_chain(T, xi), trl_pool_chain(T, T), n2[i]), i);
+            const unsigned long long k = trl_best_key(trl_pool_cosine(trl_pool_chain(T, xi), trl_pool_chain(T, T), n2[i]), i);
             if (k > key[g]) key[g] = k;
         }
         for (long long g = 0; g < G; g++) {
             int32_t index;
             float score;
-            trl_pool_key_decode(key[g], &index, &score);
+            trl_best_key_decode(key[g], &index, &score);
             printf("%016llx %d %08x\n", key[g], index, bits_of(score));
         }
     }

@@ -14,7 +14,7 @@
 #include <cstring>
 #include <vector>
 
-#include "trl_pool.h"
+#include "trl_bestkey.h"
 #include "trl_quality.h"
 
 static float f32_of(uint32_t u) {
@@ -55,10 +55,10 @@ int main(int argc, char** argv) {
                 float q;
                 long long index;
                 if (!read_floats(&q, 1) || scanf("%lld", &index) != 1) return 2;
-                const unsigned long long key = trl_pool_key(q, index);
+                const unsigned long long key = trl_best_key(q, index);
                 int32_t back;
                 float score;
-                trl_pool_key_decode(key, &back, &score);
+                trl_best_key_decode(key, &back, &score);
                 printf("%016llx %d %08x\n", key, back, bits_of(score));
             }
             continue;

@@ -144,7 +144,7 @@ def quality_ref(frames: np.ndarray, frame_of, boxes, points=None, params=None) -
 
 # ---- best shots -----------------------------------------------------------------------------------------------------------------------
 def best_key(q, index: int) -> int:
-    """trl_pool_key: the larger quality wins, ties as floats (-0 == +0) go to the lower index, NaN is no candidate (0)"""
+    """trl_best_key (csrc/trl_bestkey.h): the larger quality wins, ties as floats (-0 == +0) go to the lower index, NaN is no candidate (0)"""
     q = F32(q)
     if np.isnan(q):
         return 0

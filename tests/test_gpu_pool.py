@@ -369,3 +369,30 @@ def test_identify_tracks_names_two_people(lib):
     t = trk.templates()
     assert t["count"].cpu().numpy().tolist() == [9, 9] and bool(((t["cohesion"] > 0.7) & (t["cohesion"] < 0.95)).all())
     assert trk.identify_tracks(gal, threshold=0.999)[0] == [None, None]
+
+
+@pytest.mark.parametrize("groups", (1, 255, 256, 257))
+def test_key_read_back_is_one_kernel_for_both_entries(lib, groups):
+    """trl_pool_rep_finish and trl_best_read decode the same array of keys (csrc/trl_bestkey.h; the reference is
+    tests/quality_ref.py's best_key) to the reference's rows and the scores' own bits -- -0.0 stays -0.0, an empty slot is row -1
+    and NaN -- and to the same bits as each other, at the edges of a 256-thread workgroup."""
+    import quality_ref as Q
+    scores = [-np.inf, -1.0, -0.0, 0.0, 1e-42, 1.0, np.inf]
+    cases = [(F32(s), row) for s in scores for row in (0, 2 ** 31 - 2)] + [(F32(0.5), 7), (F32(0.5), 8), None]      # (None: an empty slot)
+    cases = [cases[(i + 2 * 2 + 1) % len(cases)] for i in range(groups)]                # (one group: -0.0 at row 2^31 - 2)
+    keys = np.array([0 if c is None else Q.best_key(*c) for c in cases], np.uint64)
+    want_row = np.array([-1 if c is None else c[1] for c in cases], np.int32)
+    want_score = np.array([np.nan if c is None else c[0] for c in cases], F32)
+    assert groups > 1 or (np.signbit(want_score[0]) and want_score[0] == 0 and want_row[0] == 2 ** 31 - 2)
+    d_keys = torch.from_numpy(keys.view(np.int64)).cuda()
+    got = []
+    for entry in (lib.trl_pool_rep_finish, lib.trl_best_read):
+        row = torch.full((groups,), FILL_I, dtype=torch.int32, device="cuda")
+        score = torch.full((groups,), FILL_F, dtype=torch.float32, device="cuda")
+        _lib.check(entry(_ptr(d_keys), groups, _ptr(row), _ptr(score), _stream()))
+        got.append((row.cpu().numpy(), score.cpu().numpy()))
+        assert np.array_equal(got[-1][0], want_row)
+        empty = want_row < 0
+        assert np.isnan(got[-1][1][empty]).all() and np.array_equal(_bits(got[-1][1])[~empty], _bits(want_score)[~empty])
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(_bits(got[0][1]), _bits(got[1][1]))
+    assert np.array_equal(d_keys.cpu().numpy().view(np.uint64), keys)                   # (the keys are read, not written)

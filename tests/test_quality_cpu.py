@@ -182,7 +182,7 @@ def test_header_equals_reference(quality_program, tmp_path):
 
 def test_best_shot_keys(quality_program, tmp_path):
     """The key orders rows as the definition does -- larger quality, ties (-0 == +0 among them) to the lower row, NaN never -- for
-    every split of the rows into calls, ids outside the groups are ignored, and trl_pool_key on the host gives the reference's keys."""
+    every split of the rows into calls, ids outside the groups are ignored, and trl_best_key on the host gives the reference's keys."""
     q = Q.best_qualities()
     m = len(q)
     rng = np.random.default_rng(9)

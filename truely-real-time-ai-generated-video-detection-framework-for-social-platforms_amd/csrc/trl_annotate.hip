@@ -15,7 +15,7 @@
 // byte.  A frame's region is split in two so that a face box far from the caption does not cost the area between them:
 // part 1 is the box of the text (rectangle first, then the segments), part 0 the box of the rectangle minus part 1.
 // The work is tiny beside the encoder's (a caption is ~300 segments over ~450x40 pixels); frames without a note get no thread.
-#include "trl_common.h"
+#include "trl_host.h"
 
 #include <cmath>
 #include <string.h>
@@ -218,9 +218,7 @@ extern "C" int trl_draw(uint8_t* d_bgr, int n, long long frame_stride, int H, in
             }
     }
     if (max_tiles == 0) return TRL_OK;                     // every entry lies outside its frame
-    hipPointerAttribute_t attr;
-    TRL_HIP(hipPointerGetAttributes(&attr, d_bgr));
-    TRL_HIP(hipSetDevice(attr.device));
+    TRL_CHECK(trl_device_of(d_bgr));
     hipStream_t s = (hipStream_t)stream;
     // pageable source: the runtime stages it before the call returns; the copy itself is ordered on `stream`
     TRL_HIP(hipMemcpyAsync(d_work, host.data(), host.size(), hipMemcpyHostToDevice, s));

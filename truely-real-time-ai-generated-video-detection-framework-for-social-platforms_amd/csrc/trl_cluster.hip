@@ -3,10 +3,12 @@
 // search with self = 1 (up to 16,777,216), and the label stage is written once over a NEIGHBOUR SOURCE that enumerates a row's
 // neighbours either way.  Labels come from rounds of hooking and pointer jumping, a launch each.  Every kernel below reads buffers
 // that no workgroup writes in the same launch, so nothing depends on one workgroup seeing another's stores; a round is a copy and
-// two launches (b = a; hook: a -> b; jump: b -> a) and the host decides between small batches of rounds.
+// two launches (b = a; hook: a -> b; jump: b -> a) and the host decides between small batches of rounds.  Refusals, the workspace
+// check and the device lookup are trl_host.h's; the bitmap's row limit, shared with trl_cluster_links, is trl_cluster.h's.
 #include <type_traits>
 
-#include "trl_gallery_host.h"
+#include "trl_cluster.h"
+#include "trl_host.h"
 #include "trl_scan.h"
 
 namespace {
@@ -247,8 +249,8 @@ int cl_labels(const char* who, int max_n, Accept&& accept, bool links_null, cons
     if (n < 0 || n > max_n) { trl_set_error("%s: n = %d outside 0..%d", who, n, max_n); return TRL_ERR_INVALID; }
     if (min_samples < 1) { trl_set_error("%s: min_samples = %d < 1", who, min_samples); return TRL_ERR_INVALID; }
     if (!accept()) return TRL_ERR_INVALID;
-    if (!d_count) { trl_set_error("%s: null count", who); return TRL_ERR_INVALID; }
-    if (n > 0 && (links_null || !d_degree || !d_labels || !d_core)) { trl_set_error("%s: null argument", who); return TRL_ERR_INVALID; }
+    if (!d_count) return trl_refuse(who, "null count");
+    if (n > 0 && (links_null || !d_degree || !d_labels || !d_core)) return trl_refuse(who, "null argument");
     Arena a = Arena::over(d_ws, ws_bytes);
     ClWs w;
     if (n > 0 && !trl_workspace_ok(who, d_ws, ws_bytes, cl_carve(a, n, &w), [&] { return cl_workspace(n, max_n); })) return TRL_ERR_INVALID;

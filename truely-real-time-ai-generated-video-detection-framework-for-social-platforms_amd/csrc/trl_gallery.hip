@@ -29,10 +29,12 @@
 //                           the workgroups' counters
 //   k_gallery_range_count / _fill (f-10)  the ballot ends in popcounts per row, then in ranked stores of CSR lists; here wave w walks a
 //                           contiguous quarter of the strip (rg_walk), and k_range_rows / k_range_scan turn counts into offsets
+// The entry points refuse, find their device, check their workspace and launch the tile kernels through trl_host.h.
 #include <algorithm>
 #include <utility>
 
-#include "trl_gallery_host.h"
+#include "trl_cluster.h"
+#include "trl_host.h"
 #include "trl_gallery_bins.h"
 #include "trl_gallery_groups.h"
 #include "trl_gallery_order.h"
@@ -798,20 +800,6 @@ int gl_check_metric(const char* who, int metric) {
 
 const char* gl_check_threshold(float threshold) { return threshold - threshold == 0.f ? nullptr : "the threshold is not finite"; }
 
-int gl_refuse(const char* who, const char* why) {
-    trl_set_error("%s: %s", who, why);
-    return TRL_ERR_INVALID;
-}
-
-// a tile kernel's launch: 256 threads and `lds` bytes of dynamic LDS, which lie above the default limit of 64 KB
-template <typename... P, typename... A>
-int gl_launch(void (*kernel)(P...), long long wgs, size_t lds, hipStream_t s, A... args) {
-    TRL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kernel<<<(unsigned)wgs, 256, lds, s>>>(args...);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
-}
-
 // the histogram's plan: the search's, with strips short enough for 32-bit counters; n == m (the shape of `upper`, whose workgroups
 // below the diagonal do nothing) asks for four times the workgroups, so that those left still fill the device evenly
 const char* hi_plan(int n, long long m, int nedges, int max_strip_cols, GlPlan* p) {
@@ -882,12 +870,12 @@ int gl_search_entry(const char* who, bool grouped, const float* d_q, const uint8
                     const float* d_n2, const int32_t* d_gid, long long m, int metric, int k, float* d_score, int32_t* d_index, int32_t* d_group,
                     void* d_ws, size_t ws_bytes, int max_strip_cols, hipStream_t s) {
     GlPlan p;
-    if (const char* why = gl_plan(n, m, k, max_strip_cols, &p)) return gl_refuse(who, why);
+    if (const char* why = gl_plan(n, m, k, max_strip_cols, &p)) return trl_refuse(who, why);
     TRL_CHECK(gl_check_metric(who, metric));
-    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) return gl_refuse(who, why);
-    if (grouped && m > 0 && !d_gid) return gl_refuse(who, "null group ids");
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) return trl_refuse(who, why);
+    if (grouped && m > 0 && !d_gid) return trl_refuse(who, "null group ids");
     if (n == 0) return TRL_OK;
-    if (!d_q || !d_score || !d_index || (grouped && !d_group)) return gl_refuse(who, "null argument");
+    if (!d_q || !d_score || !d_index || (grouped && !d_group)) return trl_refuse(who, "null argument");
     Arena a = Arena::over(d_ws, ws_bytes);
     TrlGlEntry* part;
     int32_t* part_ids;
@@ -906,11 +894,11 @@ int gl_search_entry(const char* who, bool grouped, const float* d_q, const uint8
                                     (size_t)GL_LISTS * GL_ROWS * k * (sizeof(TrlGlEntry) + (grouped ? sizeof(int32_t) : 0)));
     const long long wgs = p.strips * p.tiles;
     if (grouped) {
-        TRL_CHECK(gl_launch(k_gallery_search_groups, wgs, lds, s, d_q, d_valid, n, d_mat, ld, d_n2, d_gid, m, metric, k, (int)p.tiles, p.gps,
+        TRL_CHECK(trl_launch_lds(k_gallery_search_groups, wgs, lds, s, d_q, d_valid, n, d_mat, ld, d_n2, d_gid, m, metric, k, (int)p.tiles, p.gps,
                             p.groups, part, part_ids, d_score, d_index, d_group));
         if (part) k_gallery_merge_groups<<<(unsigned)n, 64, 0, s>>>(part, part_ids, n, p.strips, k, metric, d_score, d_index, d_group);
     } else {
-        TRL_CHECK(gl_launch(k_gallery_search, wgs, lds, s, d_q, d_valid, n, d_mat, ld, d_n2, m, metric, k, (int)p.tiles, p.gps, p.groups, part,
+        TRL_CHECK(trl_launch_lds(k_gallery_search, wgs, lds, s, d_q, d_valid, n, d_mat, ld, d_n2, m, metric, k, (int)p.tiles, p.gps, p.groups, part,
                             d_score, d_index));
         if (part) k_gallery_merge<<<(unsigned)n, 64, 0, s>>>(part, n, p.strips, k, metric, d_score, d_index);
     }
@@ -934,9 +922,9 @@ extern "C" int trl_gallery_range_count(const float* d_q, const uint8_t* d_qvalid
                                        void* d_ws, size_t ws_bytes, int max_strip_cols, void* stream) {
     const char* who = "trl_gallery_range_count";
     GlPlan p;
-    if (const char* why = rg_check(n, d_mat, ld, d_n2, m, metric, threshold, self, max_strip_cols, &p)) return gl_refuse(who, why);
+    if (const char* why = rg_check(n, d_mat, ld, d_n2, m, metric, threshold, self, max_strip_cols, &p)) return trl_refuse(who, why);
     if (n == 0) return TRL_OK;
-    if (!d_offsets || (m > 0 && !d_q)) return gl_refuse(who, "null argument");
+    if (!d_offsets || (m > 0 && !d_q)) return trl_refuse(who, "null argument");
     Arena a = Arena::over(d_ws, ws_bytes);
     uint32_t* cnt;
     if (!trl_workspace_ok(who, d_ws, ws_bytes, rg_carve(a, p, n, &cnt), [&] { return trl_gallery_range_workspace(n, m, max_strip_cols); }))
@@ -947,7 +935,7 @@ extern "C" int trl_gallery_range_count(const float* d_q, const uint8_t* d_qvalid
         TRL_HIP(hipMemsetAsync(d_offsets, 0, ((size_t)n + 1) * sizeof(long long), s));
         return TRL_OK;
     }
-    TRL_CHECK(gl_launch(k_gallery_range_count, p.strips * p.tiles, gl_lds_bytes(), s,
+    TRL_CHECK(trl_launch_lds(k_gallery_range_count, p.strips * p.tiles, gl_lds_bytes(), s,
                         rg_args(d_q, d_qvalid, n, d_mat, ld, d_n2, d_gvalid, m, metric, threshold, self, p), cnt));
     k_range_rows<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(cnt, n, p.strips * RG_WAVES, d_offsets);
     TRL_LAUNCH_CHECK();
@@ -962,27 +950,27 @@ extern "C" int trl_gallery_range_fill(const float* d_q, const uint8_t* d_qvalid,
                                       int max_strip_cols, void* stream) {
     const char* who = "trl_gallery_range_fill";
     GlPlan p;
-    if (const char* why = rg_check(n, d_mat, ld, d_n2, m, metric, threshold, self, max_strip_cols, &p)) return gl_refuse(who, why);
+    if (const char* why = rg_check(n, d_mat, ld, d_n2, m, metric, threshold, self, max_strip_cols, &p)) return trl_refuse(who, why);
     if (capacity < 0) { trl_set_error("%s: capacity = %lld < 0", who, capacity); return TRL_ERR_INVALID; }
     if (n == 0) return TRL_OK;
-    if (!d_offsets || (m > 0 && !d_q) || (capacity > 0 && (!d_index || !d_score))) return gl_refuse(who, "null argument");
+    if (!d_offsets || (m > 0 && !d_q) || (capacity > 0 && (!d_index || !d_score))) return trl_refuse(who, "null argument");
     Arena a = Arena::over(d_ws, ws_bytes);
     uint32_t* cnt;
     if (!trl_workspace_ok(who, d_ws, ws_bytes, rg_carve(a, p, n, &cnt), [&] { return trl_gallery_range_workspace(n, m, max_strip_cols); }))
         return TRL_ERR_INVALID;
     if (m == 0 || capacity == 0) return TRL_OK;
     TRL_CHECK(trl_device_of(d_mat));
-    return gl_launch(k_gallery_range_fill, p.strips * p.tiles, gl_lds_bytes(), (hipStream_t)stream,
+    return trl_launch_lds(k_gallery_range_fill, p.strips * p.tiles, gl_lds_bytes(), (hipStream_t)stream,
                      rg_args(d_q, d_qvalid, n, d_mat, ld, d_n2, d_gvalid, m, metric, threshold, self, p), d_offsets, (const uint32_t*)cnt, capacity,
                      d_index, d_score);
 }
 
 extern "C" int trl_gallery_pack(const float* d_rows, long long m, float* d_mat, long long ld, float* d_n2, long long c0, void* stream) {
     if (m < 0 || c0 < 0 || m > 0x7fffffffLL) { trl_set_error("trl_gallery_pack: m = %lld rows at column %lld", m, c0); return TRL_ERR_INVALID; }
-    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, 0)) return gl_refuse("trl_gallery_pack", why);
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, 0)) return trl_refuse("trl_gallery_pack", why);
     if (c0 + m > ld) { trl_set_error("trl_gallery_pack: columns %lld..%lld of %lld", c0, c0 + m, ld); return TRL_ERR_INVALID; }
     if (m == 0) return TRL_OK;
-    if (!d_rows) return gl_refuse("trl_gallery_pack", "null rows");
+    if (!d_rows) return trl_refuse("trl_gallery_pack", "null rows");
     TRL_CHECK(trl_device_of(d_mat));
     k_gallery_pack<<<(unsigned)((m + GL_ROWS - 1) / GL_ROWS), 256, 0, (hipStream_t)stream>>>(d_rows, m, d_mat, ld, d_n2, c0);
     TRL_LAUNCH_CHECK();
@@ -994,14 +982,14 @@ extern "C" int trl_gallery_scores(const float* d_q, int n, const float* d_mat, l
     const char* who = "trl_gallery_scores";
     if (n < 0 || m < 0 || m > 0x7fffffffLL) { trl_set_error("%s: n = %d, m = %lld", who, n, m); return TRL_ERR_INVALID; }
     TRL_CHECK(gl_check_metric(who, metric));
-    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) return gl_refuse(who, why);
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) return trl_refuse(who, why);
     if (ldo < m) { trl_set_error("%s: ldo = %lld < m = %lld", who, ldo, m); return TRL_ERR_INVALID; }
     if (n == 0 || m == 0) return TRL_OK;
-    if (!d_q || !d_out) return gl_refuse(who, "null argument");
+    if (!d_q || !d_out) return trl_refuse(who, "null argument");
     const long long tiles = (n + GL_ROWS - 1) / GL_ROWS, groups = (m + GL_GROUP - 1) / GL_GROUP;
     if (tiles * groups > 0x7fffffffLL) { trl_set_error("%s: %lld x %lld workgroups", who, tiles, groups); return TRL_ERR_INVALID; }
     TRL_CHECK(trl_device_of(d_mat));
-    return gl_launch(k_gallery_scores, tiles * groups, gl_lds_bytes(), (hipStream_t)stream, d_q, n, d_mat, ld, d_n2, m, metric, d_out, ldo, (int)tiles);
+    return trl_launch_lds(k_gallery_scores, tiles * groups, gl_lds_bytes(), (hipStream_t)stream, d_q, n, d_mat, ld, d_n2, m, metric, d_out, ldo, (int)tiles);
 }
 
 extern "C" size_t trl_gallery_search_workspace(int n, long long m, int k, int max_strip_cols) {
@@ -1032,17 +1020,17 @@ extern "C" int trl_cluster_links(const float* d_q, const uint8_t* d_valid, int n
     const char* who = "trl_cluster_links";
     if (n < 0 || n > CL_MAX_N) { trl_set_error("%s: n = %d outside 0..%d", who, n, CL_MAX_N); return TRL_ERR_INVALID; }
     GlPlan p;
-    if (const char* why = gl_plan(n, n, 1, max_strip_cols, &p)) return gl_refuse(who, why);
+    if (const char* why = gl_plan(n, n, 1, max_strip_cols, &p)) return trl_refuse(who, why);
     TRL_CHECK(gl_check_metric(who, metric));
-    if (const char* why = gl_check_threshold(threshold)) return gl_refuse(who, why);
-    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, n)) return gl_refuse(who, why);
+    if (const char* why = gl_check_threshold(threshold)) return trl_refuse(who, why);
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, n)) return trl_refuse(who, why);
     const int words = (n + 31) / 32;
     if (pitch_words < words) { trl_set_error("%s: pitch_words = %lld < %d", who, pitch_words, words); return TRL_ERR_INVALID; }
     if (n == 0) return TRL_OK;
-    if (!d_q || !d_adj || !d_degree) return gl_refuse(who, "null argument");
+    if (!d_q || !d_adj || !d_degree) return trl_refuse(who, "null argument");
     TRL_CHECK(trl_device_of(d_mat));
     hipStream_t s = (hipStream_t)stream;
-    TRL_CHECK(gl_launch(k_gallery_links, p.strips * p.tiles, gl_lds_bytes(), s, d_q, d_valid, n, d_mat, ld, d_n2, metric, threshold, (int)p.tiles,
+    TRL_CHECK(trl_launch_lds(k_gallery_links, p.strips * p.tiles, gl_lds_bytes(), s, d_q, d_valid, n, d_mat, ld, d_n2, metric, threshold, (int)p.tiles,
                         p.gps, p.groups, d_adj, pitch_words));
     k_cluster_degree<<<(unsigned)((n + 3) / 4), 256, 0, s>>>(d_adj, pitch_words, d_valid, n, words, d_degree);
     TRL_LAUNCH_CHECK();
@@ -1064,12 +1052,12 @@ extern "C" int trl_gallery_hist(const float* d_q, const uint8_t* d_qvalid, const
                                 void* stream) {
     const char* who = "trl_gallery_hist";
     GlPlan p;
-    if (const char* why = hi_plan(n, m, nedges, max_strip_cols, &p)) return gl_refuse(who, why);
+    if (const char* why = hi_plan(n, m, nedges, max_strip_cols, &p)) return trl_refuse(who, why);
     TRL_CHECK(gl_check_metric(who, metric));
     if (pairs != TRL_GL_PAIRS_ALL && pairs != TRL_GL_PAIRS_UPPER) { trl_set_error("%s: pairs %d (0 all, 1 upper)", who, pairs); return TRL_ERR_INVALID; }
     if (pairs == TRL_GL_PAIRS_UPPER && n != m) { trl_set_error("%s: upper pairs need n == m, not %d and %lld", who, n, m); return TRL_ERR_INVALID; }
-    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) return gl_refuse(who, why);
-    if (!d_edges || !d_counts || (n > 0 && (!d_q || !d_qid)) || (m > 0 && !d_gid)) return gl_refuse(who, "null argument");
+    if (const char* why = gl_check_gallery(d_mat, ld, d_n2, m)) return trl_refuse(who, why);
+    if (!d_edges || !d_counts || (n > 0 && (!d_q || !d_qid)) || (m > 0 && !d_gid)) return trl_refuse(who, "null argument");
     Arena a = Arena::over(d_ws, ws_bytes);
     uint32_t* part;
     if (!trl_workspace_ok(who, d_ws, ws_bytes, hi_carve(a, p, nedges, &part), [&] { return trl_gallery_hist_workspace(n, m, nedges, max_strip_cols); }))
@@ -1082,7 +1070,7 @@ extern "C" int trl_gallery_hist(const float* d_q, const uint8_t* d_qvalid, const
         return TRL_OK;
     }
     const long long wgs = p.strips * p.tiles;
-    TRL_CHECK(gl_launch(k_gallery_hist, wgs, gl_lds_bytes((size_t)(GL_ROWS + slots) * 4, HI_EDGE_WORDS), s, d_q, d_qvalid, d_qid, n, d_mat, ld, d_n2,
+    TRL_CHECK(trl_launch_lds(k_gallery_hist, wgs, gl_lds_bytes((size_t)(GL_ROWS + slots) * 4, HI_EDGE_WORDS), s, d_q, d_qvalid, d_qid, n, d_mat, ld, d_n2,
                         d_gvalid, d_gid, m, metric, pairs, d_edges, nedges, (int)p.tiles, p.gps, p.groups, part));
     k_gallery_hist_sum<<<(unsigned)((slots + HI_SUM_SLOTS - 1) / HI_SUM_SLOTS), 1024, 0, s>>>(part, wgs, slots, d_counts);
     TRL_LAUNCH_CHECK();

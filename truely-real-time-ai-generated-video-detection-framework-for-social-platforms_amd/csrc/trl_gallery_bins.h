@@ -15,7 +15,7 @@
 enum { TRL_GL_MAX_EDGES = 1023, TRL_GL_PAIRS_ALL = 0, TRL_GL_PAIRS_UPPER = 1 };
 
 // ceil(log2(E + 1)): the trips of the search below
-TRL_GL_HD int trl_gl_bin_steps(int E) {
+TRL_HD int trl_gl_bin_steps(int E) {
     int s = 0;
     while ((1 << s) < E + 1) s++;
     return s;
@@ -23,7 +23,7 @@ TRL_GL_HD int trl_gl_bin_steps(int E) {
 
 // The count is built from its highest bit down: `steps` trips whatever the score, and an edge is read only at an index below E, so
 // edges that are not sorted give an unspecified bin in 0..E but never a read out of bounds.
-TRL_GL_HD int trl_gl_bin_in(int metric, float score, const float* edges, int E, int steps) {
+TRL_HD int trl_gl_bin_in(int metric, float score, const float* edges, int E, int steps) {
     if (score != score) return E + 1;
     int bin = 0;
     for (int s = steps - 1; s >= 0; s--) {
@@ -35,7 +35,7 @@ TRL_GL_HD int trl_gl_bin_in(int metric, float score, const float* edges, int E, 
     return bin;
 }
 
-TRL_GL_HD int trl_gl_bin(int metric, float score, const float* edges, int E) {
+TRL_HD int trl_gl_bin(int metric, float score, const float* edges, int E) {
     return trl_gl_bin_in(metric, score, edges, E, trl_gl_bin_steps(E));
 }
 
@@ -45,7 +45,7 @@ TRL_GL_HD int trl_gl_bin(int metric, float score, const float* edges, int E) {
 // a trip is one read at a constant offset from the running count, a comparison and a select.
 enum { TRL_GL_MAX_STEPS = 10, TRL_GL_PADDED_EDGES = (1 << TRL_GL_MAX_STEPS) - 1 };
 
-TRL_GL_HD int trl_gl_bin_padded(int metric, float score, const float* padded, int E, int steps) {
+TRL_HD int trl_gl_bin_padded(int metric, float score, const float* padded, int E, int steps) {
     if (score != score) return E + 1;
     int bin = 0;
     for (int s = steps - 1; s >= 0; s--) {

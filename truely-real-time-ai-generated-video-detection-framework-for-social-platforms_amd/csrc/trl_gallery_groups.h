@@ -14,7 +14,7 @@
 // k read slot k - 1 again) and there is no branch per slot: on the device the reads are in flight together, where a loop that stops
 // at the first hit pays a full LDS round trip per slot -- and this search runs in every wave in which any lane has a survivor.
 template <int N>
-TRL_GL_HD int trl_gl_find_group(const int32_t* groups, int k, int32_t group) {
+TRL_HD int trl_gl_find_group(const int32_t* groups, int k, int32_t group) {
     int32_t g[N];
 #if defined(__HIPCC__)
 #pragma unroll
@@ -35,7 +35,7 @@ TRL_GL_HD int trl_gl_find_group(const int32_t* groups, int k, int32_t group) {
 //   * the list holds an entry of the same group that comes before it.
 // An entry of the same group that comes after it is removed: the entries between the newcomer's place and that entry move down by
 // one, the entries behind it stay.  Without such an entry this is trl_gl_insert: the last entry is dropped.
-TRL_GL_HD bool trl_gl_insert_group(TrlGlEntry* list, int32_t* groups, int k, int metric, float score, int32_t index, int32_t group) {
+TRL_HD bool trl_gl_insert_group(TrlGlEntry* list, int32_t* groups, int k, int metric, float score, int32_t index, int32_t group) {
     if (!trl_gl_before(metric, score, index, list[k - 1].score, list[k - 1].index)) return false;
     // the slot that is given up: the same group's (at most one), or else the last
     const int f = k <= 4 ? trl_gl_find_group<4>(groups, k, group) : k <= 8 ? trl_gl_find_group<8>(groups, k, group)
@@ -57,7 +57,7 @@ TRL_GL_HD bool trl_gl_insert_group(TrlGlEntry* list, int32_t* groups, int k, int
 // A list is left at its first empty slot, and at its first entry that comes after out's k-th: nothing behind it comes before.
 // An entry that fails because out holds a better row of its group does NOT end its list -- the entries behind it belong to other
 // groups and may still get in (trl_gl_merge's early break would lose them).
-TRL_GL_HD void trl_gl_merge_groups(TrlGlEntry* out, int32_t* out_groups, int k, int metric, const TrlGlEntry* lists, const int32_t* groups,
+TRL_HD void trl_gl_merge_groups(TrlGlEntry* out, int32_t* out_groups, int k, int metric, const TrlGlEntry* lists, const int32_t* groups,
                                    long long count, long long stride) {
     for (long long l = 0; l < count; l++) {
         const TrlGlEntry* src = lists + l * stride;

@@ -10,11 +10,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define TRL_GL_HD __host__ __device__ __forceinline__
-#else
-#define TRL_GL_HD inline
-#endif
+#include "trl_hd.h"
 
 enum { TRL_GL_COSINE = 0, TRL_GL_EUCLIDEAN = 1, TRL_GL_MAX_K = 16 };
 #define TRL_GL_EMPTY 0x7fffffff
@@ -24,7 +20,7 @@ struct TrlGlEntry {
     int32_t index;
 };
 
-TRL_GL_HD TrlGlEntry trl_gl_empty() {
+TRL_HD TrlGlEntry trl_gl_empty() {
     TrlGlEntry e;
     e.score = __builtin_nanf("");
     e.index = TRL_GL_EMPTY;
@@ -32,7 +28,7 @@ TRL_GL_HD TrlGlEntry trl_gl_empty() {
 }
 
 // a comes before b
-TRL_GL_HD bool trl_gl_before(int metric, float sa, int32_t ia, float sb, int32_t ib) {
+TRL_HD bool trl_gl_before(int metric, float sa, int32_t ia, float sb, int32_t ib) {
     const bool na = sa != sa, nb = sb != sb;
     if (na != nb) return nb;
     if (!na && sa != sb) return metric == TRL_GL_COSINE ? sa > sb : sa < sb;
@@ -41,7 +37,7 @@ TRL_GL_HD bool trl_gl_before(int metric, float sa, int32_t ia, float sb, int32_t
 
 // list[0..k): matches in order, empty slots last.  Puts (score, index) where it belongs and drops the last entry; false, and the
 // list as it was, when it comes after all k.
-TRL_GL_HD bool trl_gl_insert(TrlGlEntry* list, int k, int metric, float score, int32_t index) {
+TRL_HD bool trl_gl_insert(TrlGlEntry* list, int k, int metric, float score, int32_t index) {
     int p = k - 1;
     if (!trl_gl_before(metric, score, index, list[p].score, list[p].index)) return false;
     for (; p > 0 && trl_gl_before(metric, score, index, list[p - 1].score, list[p - 1].index); p--) list[p] = list[p - 1];
@@ -52,7 +48,7 @@ TRL_GL_HD bool trl_gl_insert(TrlGlEntry* list, int k, int metric, float score, i
 
 // out[0..k) (a list as above) takes the matches of `count` lists of k entries, `stride` entries apart.  Each of them is in order,
 // so a list is left at its first entry that does not get in: nothing behind it would.
-TRL_GL_HD void trl_gl_merge(TrlGlEntry* out, int k, int metric, const TrlGlEntry* lists, long long count, long long stride) {
+TRL_HD void trl_gl_merge(TrlGlEntry* out, int k, int metric, const TrlGlEntry* lists, long long count, long long stride) {
     for (long long l = 0; l < count; l++) {
         const TrlGlEntry* src = lists + l * stride;
         for (int e = 0; e < k; e++)

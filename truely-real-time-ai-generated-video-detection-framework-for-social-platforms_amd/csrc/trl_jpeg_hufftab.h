@@ -12,11 +12,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define TRL_HUFFTAB_HD __host__ __device__
-#else
-#define TRL_HUFFTAB_HD
-#endif
+#include "trl_hd.h"
 
 struct trl_hufftab_work {
     uint32_t freq[257];
@@ -30,7 +26,7 @@ struct trl_hufftab_work {
 // hist: 256 counts.  bits[16]: codes per length 1..16.  vals: the symbols in code order (room for 256).  Returns their number.
 // *maxlen (optional): the longest code length before the limiting step (tests use it to know that the step ran).  A histogram
 // without any count gives an empty table.
-TRL_HUFFTAB_HD inline int trl_jpeg_hufftab(const uint32_t* hist, uint8_t* bits, uint8_t* vals, trl_hufftab_work* w, int* maxlen) {
+TRL_HD int trl_jpeg_hufftab(const uint32_t* hist, uint8_t* bits, uint8_t* vals, trl_hufftab_work* w, int* maxlen) {
     int nl = 0;
     for (int i = 0; i < 257; ++i) {
         w->freq[i] = i < 256 ? hist[i] : 1u;

@@ -12,11 +12,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define TRL_PL_HD __host__ __device__ __forceinline__
-#else
-#define TRL_PL_HD inline
-#endif
+#include "trl_hd.h"
 
 enum { TRL_POOL_K = 512, TRL_POOL_UNIT = 0, TRL_POOL_MEAN = 1 };
 enum { TRL_POOL_IGNORED = 0, TRL_POOL_SKIPPED = 1, TRL_POOL_CONTRIBUTES = 2 };
@@ -24,13 +20,13 @@ enum { TRL_POOL_IGNORED = 0, TRL_POOL_SKIPPED = 1, TRL_POOL_CONTRIBUTES = 2 };
 #define TRL_POOL_MAX_GROUPS 0x7fffffffLL
 
 // the state's layout, in int64 words
-TRL_PL_HD long long trl_pool_words(long long groups) { return 514 * groups + 1; }
-TRL_PL_HD long long trl_pool_w_at(long long groups) { (void)groups; return 1; }
-TRL_PL_HD long long trl_pool_n_at(long long groups) { return 1 + groups; }
-TRL_PL_HD long long trl_pool_a_at(long long groups) { return 1 + 2 * groups; }
+TRL_HD long long trl_pool_words(long long groups) { return 514 * groups + 1; }
+TRL_HD long long trl_pool_w_at(long long groups) { (void)groups; return 1; }
+TRL_HD long long trl_pool_n_at(long long groups) { return 1 + groups; }
+TRL_HD long long trl_pool_a_at(long long groups) { return 1 + 2 * groups; }
 
 // x[0..512) with itself: the gallery's chain, trl_gallery_pack's bits
-TRL_PL_HD float trl_pool_chain(const float* a, const float* b) {
+TRL_HD float trl_pool_chain(const float* a, const float* b) {
     float acc = 0.f;
     for (int k = 0; k < TRL_POOL_K; k++) acc = __builtin_fmaf(a[k], b[k], acc);
     return acc;
@@ -38,7 +34,7 @@ TRL_PL_HD float trl_pool_chain(const float* a, const float* b) {
 
 // What becomes of a row: IGNORED (its id lies outside g0 .. g0 + G - 1: counted nowhere), SKIPPED (counted in the state's
 // `skipped`) or CONTRIBUTES.  w: the row's weight (1.0f without weights); n2: its chain.  NaN fails every comparison.
-TRL_PL_HD int trl_pool_class(int32_t gid, long long g0, long long groups, float w, float n2) {
+TRL_HD int trl_pool_class(int32_t gid, long long g0, long long groups, float w, float n2) {
     const long long g = (long long)gid - g0;
     if (g < 0 || g >= groups) return TRL_POOL_IGNORED;
     if (!(w > 0.f && w <= 1.f)) return TRL_POOL_SKIPPED;
@@ -48,24 +44,24 @@ TRL_PL_HD int trl_pool_class(int32_t gid, long long g0, long long groups, float 
 
 // the factor of a contributing row, its terms and its weight in 2^-32 units.  |c x| <= 1 + 2^-15 (the chain's relative error on a
 // normal n2 is at most gamma_512), so |term| < 2^32 (1 + 2^-15): 2^30 terms fit an int64
-TRL_PL_HD float trl_pool_factor(float w, float n2) { return w / __builtin_sqrtf(n2); }
-TRL_PL_HD long long trl_pool_term(float c, float x) {
+TRL_HD float trl_pool_factor(float w, float n2) { return w / __builtin_sqrtf(n2); }
+TRL_HD long long trl_pool_term(float c, float x) {
     const float p = c * x;
     return (long long)__builtin_rintf(p * 0x1p32f);
 }
-TRL_PL_HD long long trl_pool_weight(float w) { return (long long)__builtin_rintf(w * 0x1p32f); }
+TRL_HD long long trl_pool_weight(float w) { return (long long)__builtin_rintf(w * 0x1p32f); }
 
 // finishing: an accumulator back to float32 (int64 -> float32 rounds to nearest), then the template's element
-TRL_PL_HD float trl_pool_value(long long a) { return (float)a * 0x1p-32f; }
-TRL_PL_HD float trl_pool_element(int mode, long long count, float t, float sq_n2t, float wf) {
+TRL_HD float trl_pool_value(long long a) { return (float)a * 0x1p-32f; }
+TRL_HD float trl_pool_element(int mode, long long count, float t, float sq_n2t, float wf) {
     if (count == 0) return 0.f;
     return mode == TRL_POOL_UNIT ? t / sq_n2t : t / wf;
 }
 // the mean resultant length: 1 for identical rows, near 0 for unrelated ones
-TRL_PL_HD float trl_pool_cohesion(long long count, float sq_n2t, float wf) { return count == 0 ? 0.f : sq_n2t / wf; }
+TRL_HD float trl_pool_cohesion(long long count, float sq_n2t, float wf) { return count == 0 ? 0.f : sq_n2t / wf; }
 
 // one group, finished on the host (the device spreads the elements over a wave): tmpl[512], *weight, *cohesion
-TRL_PL_HD void trl_pool_finish_group(int mode, const long long* a, long long w, long long count, float* tmpl, float* weight, float* cohesion) {
+TRL_HD void trl_pool_finish_group(int mode, const long long* a, long long w, long long count, float* tmpl, float* weight, float* cohesion) {
     float t[TRL_POOL_K];
     for (int k = 0; k < TRL_POOL_K; k++) t[k] = trl_pool_value(a[k]);
     const float wf = trl_pool_value(w), sq = __builtin_sqrtf(trl_pool_chain(t, t));
@@ -76,30 +72,5 @@ TRL_PL_HD void trl_pool_finish_group(int mode, const long long* a, long long w, 
 
 // ---- the representative: the contributing row of a group with the largest gallery cosine against the group's template row ------
 // cosine = chain(x, T) / (sqrtf(n2 T) * sqrtf(n2 x)): trl_gallery_scores' bits for query T and gallery row x
-TRL_PL_HD float trl_pool_cosine(float dot, float n2t, float n2x) { return dot / (__builtin_sqrtf(n2t) * __builtin_sqrtf(n2x)); }
-
-// A candidate's 64-bit key; the largest key wins.  0: no candidate (a NaN cosine is never one).  From the top: the score's bits in
-// an order that is the floats' (-0 counted as +0, so that the two tie), 0x7fffffff - index (ties go to the lower index), and one bit
-// that says the score was -0, which decides nothing -- indices are distinct -- and lets the decode give back the score's own bits.
-TRL_PL_HD unsigned long long trl_pool_key(float score, long long index) {
-    if (score != score) return 0;
-    union { float f; uint32_t u; } b;
-    b.f = score;
-    const uint32_t negzero = b.u == 0x80000000u;
-    if (negzero) b.u = 0;
-    const uint32_t ord = (b.u & 0x80000000u) ? ~b.u : (b.u | 0x80000000u);
-    return ((unsigned long long)ord << 32) | ((unsigned long long)(uint32_t)(0x7fffffff - (int32_t)index) << 1) | negzero;
-}
-TRL_PL_HD void trl_pool_key_decode(unsigned long long key, int32_t* index, float* score) {
-    if (key == 0) {
-        *index = -1;
-        *score = __builtin_nanf("");
-        return;
-    }
-    const uint32_t ord = (uint32_t)(key >> 32), low = (uint32_t)key;
-    union { float f; uint32_t u; } b;
-    b.u = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
-    if (low & 1) b.u = 0x80000000u;
-    *index = 0x7fffffff - (int32_t)(low >> 1);
-    *score = b.f;
-}
+TRL_HD float trl_pool_cosine(float dot, float n2t, float n2x) { return dot / (__builtin_sqrtf(n2t) * __builtin_sqrtf(n2x)); }
+// a candidate's key is trl_best_key(cosine, row) (trl_bestkey.h): the largest wins, ties to the lower row, a NaN cosine never

@@ -10,14 +10,17 @@
 // 64-bit integer atomicAdd; lane l of a wave owns columns 64 j + l, so a wave instruction adds 512 contiguous bytes.
 // k_pool_rep_add is the same walk: the template row of each distinct id of the tile is gathered into LDS beside the rows, thread r
 // runs row r's chain against it (and the template's own chain), and one 64-bit atomicMax of the tile's best key per group goes out.
-#include "trl_gallery_host.h"
+// The key is trl_bestkey.h's, which the best shots of trl_quality.hip share; k_best_key_read and its launcher trl_best_key_read
+// read an array of keys back for both.  The entry points' checks, device lookup and launches are trl_host.h's.
+#include "trl_bestkey.h"
+#include "trl_host.h"
 #include "trl_pool.h"
 
 namespace {
 
 constexpr int PL_K = TRL_POOL_K;
 constexpr int PL_PITCH = PL_K + 1;    // LDS row pitch in words: thread r walks row r, 32 rows on 32 banks
-constexpr int PL_THREADS = 256;
+constexpr int PL_THREADS = 256;      // (trl_launch_lds' workgroup)
 constexpr int PL_TILE_DEFAULT = 32;
 constexpr int PL_TILE_MAX = 32;
 
@@ -265,7 +268,7 @@ __global__ __launch_bounds__(PL_THREADS) void k_pool_rep_add(unsigned long long*
                 dot = __builtin_fmaf(tr[i], xr[i], dot);
                 n2t = __builtin_fmaf(tr[i], tr[i], n2t);
             }
-            k = trl_pool_key(trl_pool_cosine(dot, n2t, me.n2), row_base + row0 + tid);
+            k = trl_best_key(trl_pool_cosine(dot, n2t, me.n2), row_base + row0 + tid);
         }
         keys[tid] = k;
     }
@@ -278,31 +281,20 @@ __global__ __launch_bounds__(PL_THREADS) void k_pool_rep_add(unsigned long long*
     }
 }
 
-__global__ __launch_bounds__(PL_THREADS) void k_pool_rep_finish(const unsigned long long* __restrict__ key, long long groups,
-                                                                int32_t* __restrict__ index, float* __restrict__ score) {
+// the read-back of an array of best-row keys: trl_pool_rep_finish's and trl_best_read's (trl_quality.hip)
+__global__ __launch_bounds__(PL_THREADS) void k_best_key_read(const unsigned long long* __restrict__ key, long long groups,
+                                                              int32_t* __restrict__ index, float* __restrict__ score) {
     const long long g = (long long)blockIdx.x * PL_THREADS + threadIdx.x;
     if (g >= groups) return;
     int32_t i;
     float s;
-    trl_pool_key_decode(key[g], &i, &s);
+    trl_best_key_decode(key[g], &i, &s);
     index[g] = i;
     score[g] = s;
 }
 
-int pl_refuse(const char* who, const char* why) {
-    trl_set_error("%s: %s", who, why);
-    return TRL_ERR_INVALID;
-}
-
 // the tile a caller's tile_rows means; 0 when the kernels do not support it
 int pl_tile(int tile_rows) { return tile_rows == 0 ? PL_TILE_DEFAULT : tile_rows == 8 || tile_rows == 16 || tile_rows == 32 ? tile_rows : 0; }
-
-const char* pl_check_groups(const void* p, long long groups) {
-    if (groups < 0 || groups > TRL_POOL_MAX_GROUPS) return "groups outside 0..2^31 - 1";
-    if (!p) return "null state";
-    if ((uintptr_t)p & 7) return "the state is not 8-byte aligned";
-    return nullptr;
-}
 
 // what trl_pool_add and trl_pool_rep_add refuse alike
 const char* pl_check_rows(long long ld, long long m, long long row0, int tile_rows) {
@@ -313,18 +305,10 @@ const char* pl_check_rows(long long ld, long long m, long long row0, int tile_ro
     return nullptr;
 }
 
-template <typename... P, typename... A>
-int pl_launch_one(void (*kernel)(P...), long long wgs, size_t lds, hipStream_t s, A... args) {
-    TRL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kernel<<<(unsigned)wgs, PL_THREADS, lds, s>>>(args...);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
-}
-
 // the instantiation for a tile of `rows` rows (pl_tile's values)
 #define PL_LAUNCH(kernel, rows, ...)                                                  \
-    ((rows) == 8 ? pl_launch_one(kernel<8>, __VA_ARGS__) : (rows) == 16 ? pl_launch_one(kernel<16>, __VA_ARGS__) \
-                                                                         : pl_launch_one(kernel<32>, __VA_ARGS__))
+    ((rows) == 8 ? trl_launch_lds(kernel<8>, __VA_ARGS__) : (rows) == 16 ? trl_launch_lds(kernel<16>, __VA_ARGS__) \
+                                                                         : trl_launch_lds(kernel<32>, __VA_ARGS__))
 
 }  // namespace
 
@@ -334,7 +318,7 @@ extern "C" size_t trl_pool_state_bytes(long long groups) {
 }
 
 extern "C" int trl_pool_reset(void* d_state, long long groups, void* stream) {
-    if (const char* why = pl_check_groups(d_state, groups)) return pl_refuse("trl_pool_reset", why);
+    TRL_CHECK(trl_check_groups("trl_pool_reset", "state is", d_state, groups));
     TRL_CHECK(trl_device_of(d_state));
     TRL_HIP(hipMemsetAsync(d_state, 0, trl_pool_state_bytes(groups), (hipStream_t)stream));
     return TRL_OK;
@@ -343,10 +327,10 @@ extern "C" int trl_pool_reset(void* d_state, long long groups, void* stream) {
 extern "C" int trl_pool_add(void* d_state, long long groups, long long g0, const float* d_rows, long long ld_rows, const float* d_n2,
                             const int32_t* d_gid, const float* d_w, long long m, int tile_rows, void* stream) {
     const char* who = "trl_pool_add";
-    if (const char* why = pl_check_groups(d_state, groups)) return pl_refuse(who, why);
-    if (const char* why = pl_check_rows(ld_rows, m, 0, tile_rows)) return pl_refuse(who, why);
+    TRL_CHECK(trl_check_groups(who, "state is", d_state, groups));
+    if (const char* why = pl_check_rows(ld_rows, m, 0, tile_rows)) return trl_refuse(who, why);
     if (m == 0) return TRL_OK;
-    if (!d_rows || !d_gid) return pl_refuse(who, "null argument");
+    if (!d_rows || !d_gid) return trl_refuse(who, "null argument");
     const int rows = pl_tile(tile_rows);
     TRL_CHECK(trl_device_of(d_state));
     return PL_LAUNCH(k_pool_add, rows, (m + rows - 1) / rows, pl_lds_bytes(rows, 1), (hipStream_t)stream, (unsigned long long*)d_state, groups,
@@ -356,9 +340,9 @@ extern "C" int trl_pool_add(void* d_state, long long groups, long long g0, const
 extern "C" int trl_pool_finish(const void* d_state, long long groups, int mode, float* d_template, int32_t* d_count, float* d_weight,
                                float* d_cohesion, long long* d_skipped, void* stream) {
     const char* who = "trl_pool_finish";
-    if (const char* why = pl_check_groups(d_state, groups)) return pl_refuse(who, why);
-    if (mode != TRL_POOL_UNIT && mode != TRL_POOL_MEAN) return pl_refuse(who, "mode is not 0 (unit) or 1 (mean)");
-    if (groups > 0 && (!d_template || !d_count || !d_weight || !d_cohesion)) return pl_refuse(who, "null argument");
+    TRL_CHECK(trl_check_groups(who, "state is", d_state, groups));
+    if (mode != TRL_POOL_UNIT && mode != TRL_POOL_MEAN) return trl_refuse(who, "mode is not 0 (unit) or 1 (mean)");
+    if (groups > 0 && (!d_template || !d_count || !d_weight || !d_cohesion)) return trl_refuse(who, "null argument");
     if (groups == 0 && !d_skipped) return TRL_OK;
     TRL_CHECK(trl_device_of(d_state));
     k_pool_finish<<<(unsigned)(groups > 0 ? (groups + 3) / 4 : 1), PL_THREADS, 0, (hipStream_t)stream>>>(
@@ -368,7 +352,7 @@ extern "C" int trl_pool_finish(const void* d_state, long long groups, int mode, 
 }
 
 extern "C" int trl_pool_rep_reset(unsigned long long* d_key, long long groups, void* stream) {
-    if (const char* why = pl_check_groups(d_key, groups)) return pl_refuse("trl_pool_rep_reset", why);
+    TRL_CHECK(trl_check_groups("trl_pool_rep_reset", "state is", d_key, groups));
     if (groups == 0) return TRL_OK;
     TRL_CHECK(trl_device_of(d_key));
     TRL_HIP(hipMemsetAsync(d_key, 0, (size_t)groups * 8, (hipStream_t)stream));
@@ -379,23 +363,27 @@ extern "C" int trl_pool_rep_add(unsigned long long* d_key, long long groups, lon
                                 long long ld_rows, const float* d_n2, const int32_t* d_gid, const float* d_w, long long row0, long long m,
                                 int tile_rows, void* stream) {
     const char* who = "trl_pool_rep_add";
-    if (const char* why = pl_check_groups(d_key, groups)) return pl_refuse(who, why);
-    if (const char* why = pl_check_rows(ld_rows, m, row0, tile_rows)) return pl_refuse(who, why);
+    TRL_CHECK(trl_check_groups(who, "state is", d_key, groups));
+    if (const char* why = pl_check_rows(ld_rows, m, row0, tile_rows)) return trl_refuse(who, why);
     if (m == 0 || groups == 0) return TRL_OK;
-    if (!d_template || !d_rows || !d_gid) return pl_refuse(who, "null argument");
+    if (!d_template || !d_rows || !d_gid) return trl_refuse(who, "null argument");
     const int rows = pl_tile(tile_rows);
     TRL_CHECK(trl_device_of(d_key));
     return PL_LAUNCH(k_pool_rep_add, rows, (m + rows - 1) / rows, pl_lds_bytes(rows, 2) + (size_t)rows * 8 + 8, (hipStream_t)stream, d_key,
                      groups, g0, d_template, d_rows, ld_rows, d_n2, d_gid, d_w, row0, m);
 }
 
-extern "C" int trl_pool_rep_finish(const unsigned long long* d_key, long long groups, int32_t* d_index, float* d_score, void* stream) {
-    const char* who = "trl_pool_rep_finish";
-    if (const char* why = pl_check_groups(d_key, groups)) return pl_refuse(who, why);
+int trl_best_key_read(const char* who, const char* what, const unsigned long long* d_key, long long groups, int32_t* d_index, float* d_score,
+                      hipStream_t s) {
+    TRL_CHECK(trl_check_groups(who, what, d_key, groups));
     if (groups == 0) return TRL_OK;
-    if (!d_index || !d_score) return pl_refuse(who, "null argument");
+    if (!d_index || !d_score) return trl_refuse(who, "null argument");
     TRL_CHECK(trl_device_of(d_key));
-    k_pool_rep_finish<<<(unsigned)((groups + PL_THREADS - 1) / PL_THREADS), PL_THREADS, 0, (hipStream_t)stream>>>(d_key, groups, d_index, d_score);
+    k_best_key_read<<<(unsigned)((groups + PL_THREADS - 1) / PL_THREADS), PL_THREADS, 0, s>>>(d_key, groups, d_index, d_score);
     TRL_LAUNCH_CHECK();
     return TRL_OK;
+}
+
+extern "C" int trl_pool_rep_finish(const unsigned long long* d_key, long long groups, int32_t* d_index, float* d_score, void* stream) {
+    return trl_best_key_read("trl_pool_rep_finish", "state is", d_key, groups, d_index, d_score, (hipStream_t)stream);
 }

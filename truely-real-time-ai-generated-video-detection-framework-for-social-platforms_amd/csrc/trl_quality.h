@@ -16,12 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/truely_hip.h"
-
-#if defined(__HIPCC__)
-#define TRL_QL_HD __host__ __device__ __forceinline__
-#else
-#define TRL_QL_HD inline
-#endif
+#include "trl_hd.h"
 
 enum { TRL_QUALITY_RAW = 8, TRL_QUALITY_FEAT = 12, TRL_QUALITY_BINS = 256 };
 // raw[8], int64
@@ -32,24 +27,24 @@ enum { TRL_QF_QUALITY = 0, TRL_QF_SHARPNESS, TRL_QF_MEAN_LUMA, TRL_QF_DARK_FRAC,
 #define TRL_QUALITY_MAX_DIM 16384            /* H and W of a frame: a rectangle's row of luma fits the kernels' LDS three times */
 #define TRL_QUALITY_MAX_ROWS (1LL << 24)     /* face rows of one call */
 
-TRL_QL_HD trl_quality_params trl_quality_defaults() {
+TRL_HD trl_quality_params trl_quality_defaults() {
     trl_quality_params p;
     p.sharp_ref = 100.f, p.clip_ref = 0.5f, p.contrast_ref = 64.f, p.yaw_ref = 1.f, p.pitch_ref = 1.f, p.size_ref = 80.f;
     return p;
 }
 // every reference is a divisor: finite and > 0
-TRL_QL_HD bool trl_quality_ref_ok(float v) { return v > 0.f && v - v == 0.f; }
-TRL_QL_HD bool trl_quality_params_ok(const trl_quality_params& p) {
+TRL_HD bool trl_quality_ref_ok(float v) { return v > 0.f && v - v == 0.f; }
+TRL_HD bool trl_quality_params_ok(const trl_quality_params& p) {
     return trl_quality_ref_ok(p.sharp_ref) && trl_quality_ref_ok(p.clip_ref) && trl_quality_ref_ok(p.contrast_ref) &&
            trl_quality_ref_ok(p.yaw_ref) && trl_quality_ref_ok(p.pitch_ref) && trl_quality_ref_ok(p.size_ref);
 }
 
 // ---- the rectangle ------------------------------------------------------------------------------------------------------------------
 // clamp((int)v, 0, len) of an integral float v, without converting what an int cannot hold
-TRL_QL_HD int trl_quality_clamp(float v, int len) { return v <= 0.f ? 0 : v >= (float)len ? len : (int)v; }
+TRL_HD int trl_quality_clamp(float v, int len) { return v <= 0.f ? 0 : v >= (float)len ? len : (int)v; }
 // rect = X0, Y0, X1, Y1: columns X0 .. X1 - 1 and rows Y0 .. Y1 - 1 of frame frame_of.  0 (and a zero rect) for no face: a frame
 // index outside 0 .. n - 1, a NaN or infinite coordinate, or an empty rectangle
-TRL_QL_HD int trl_quality_rect(int frame_of, int n, int H, int W, const float* box, int* rect) {
+TRL_HD int trl_quality_rect(int frame_of, int n, int H, int W, const float* box, int* rect) {
     rect[0] = rect[1] = rect[2] = rect[3] = 0;
     if (frame_of < 0 || frame_of >= n) return 0;
     if (!(box[0] - box[0] == 0.f && box[1] - box[1] == 0.f && box[2] - box[2] == 0.f && box[3] - box[3] == 0.f)) return 0;
@@ -61,10 +56,10 @@ TRL_QL_HD int trl_quality_rect(int frame_of, int n, int H, int W, const float* b
 }
 
 // ---- the pixel rules ----------------------------------------------------------------------------------------------------------------
-TRL_QL_HD int trl_quality_luma(int b, int g, int r) { return (1868 * b + 9617 * g + 4899 * r + 8192) >> 14; }
+TRL_HD int trl_quality_luma(int b, int g, int r) { return (1868 * b + 9617 * g + 4899 * r + 8192) >> 14; }
 // reflect-101 inside 0 .. len - 1 for i in -1 .. len: -1 -> 1, len -> len - 2; a single sample is its own neighbour
-TRL_QL_HD int trl_quality_reflect(int i, int len) { return len == 1 ? 0 : i < 0 ? 1 : i >= len ? len - 2 : i; }
-TRL_QL_HD int trl_quality_laplacian(int c, int up, int down, int left, int right) { return up + down + left + right - 4 * c; }
+TRL_HD int trl_quality_reflect(int i, int len) { return len == 1 ? 0 : i < 0 ? 1 : i >= len ? len - 2 : i; }
+TRL_HD int trl_quality_laplacian(int c, int up, int down, int left, int right) { return up + down + left + right - 4 * c; }
 
 // The sums of rows y0 .. y1 - 1 of the rectangle (rows of the RECTANGLE: 0 .. h - 1), added to hist[256], *sl and *sl2: the host's
 // schedule (the kernels take a band through LDS).  Any split of 0 .. h - 1 into such bands gives the same totals.
@@ -90,7 +85,7 @@ inline void trl_quality_accumulate(const uint8_t* frame, int W, const int* rect,
 // ---- the raw integers ---------------------------------------------------------------------------------------------------------------
 // N, the sums of Y and Y^2 and the clipped counts are functions of the histogram (the kernels read them off it): raw[0 .. 7], p[0]
 // = p05 and p[1] = p95.  p05 is the smallest v with 20 cum(v) >= N, p95 the smallest with 20 cum(v) >= 19 N.
-TRL_QL_HD void trl_quality_raw(const int32_t* hist, long long sl, long long sl2, int width, long long* raw, int* p) {
+TRL_HD void trl_quality_raw(const int32_t* hist, long long sl, long long sl2, int width, long long* raw, int* p) {
     long long n = 0, sy = 0, sy2 = 0, dark = 0, bright = 0;
     for (int v = 0; v < TRL_QUALITY_BINS; v++) {
         const long long c = hist[v];
@@ -115,7 +110,7 @@ TRL_QL_HD void trl_quality_raw(const int32_t* hist, long long sl, long long sl2,
 //   iod = sqrtf(e.e);  roll = e.y / iod;  yaw = 2 ((nose - eyeL).e / e.e) - 1
 //   pitch = 2 ((nose - eyeMid).v / v.v) - 1,  v = mouthMid - eyeMid, the mids (a + b) * 0.5f
 // a dot product is (ax * bx) + (ay * by).  All four are NaN when a point is not finite or e.e or v.v is 0.
-TRL_QL_HD void trl_quality_pose(const float* pts, float* pose) {
+TRL_HD void trl_quality_pose(const float* pts, float* pose) {
     const float nan = __builtin_nanf("");
     pose[0] = pose[1] = pose[2] = pose[3] = nan;
     bool finite = true;
@@ -137,9 +132,9 @@ TRL_QL_HD void trl_quality_pose(const float* pts, float* pose) {
     pose[3] = iod;
 }
 
-TRL_QL_HD float trl_quality_unit_min(float v) { return v > 1.f ? 1.f : v; }            // min(v, 1)
-TRL_QL_HD float trl_quality_pos(float v) { return v > 0.f ? v : 0.f; }                  // max(0, v); NaN -> 0
-TRL_QL_HD float trl_quality_abs(float v) { return v < 0.f ? -v : v; }
+TRL_HD float trl_quality_unit_min(float v) { return v > 1.f ? 1.f : v; }            // min(v, 1)
+TRL_HD float trl_quality_pos(float v) { return v > 0.f ? v : 0.f; }                  // max(0, v); NaN -> 0
+TRL_HD float trl_quality_abs(float v) { return v < 0.f ? -v : v; }
 
 // One face: feat[12] from its raw integers, the percentiles, its rectangle's height and its points (read when has_pts).  status 0:
 // all +0.
@@ -150,7 +145,7 @@ TRL_QL_HD float trl_quality_abs(float v) { return v < 0.f ? -v : v; }
 //   q_pose     = max(0, 1 - |yaw| / yaw_ref) * max(0, 1 - |pitch| / pitch_ref);  0 when either is NaN, 1 without points
 //   q_size     = min((float)min(w, h) / size_ref, 1)
 //   quality    = ((q_sharp * q_expo) * q_pose) * q_size
-TRL_QL_HD void trl_quality_features(int status, const long long* raw, const int* p, int height, bool has_pts, const float* pts,
+TRL_HD void trl_quality_features(int status, const long long* raw, const int* p, int height, bool has_pts, const float* pts,
                                     const trl_quality_params& prm, float* feat) {
 #pragma unroll
     for (int i = 0; i < TRL_QUALITY_FEAT; i++) feat[i] = 0.f;
@@ -181,5 +176,5 @@ TRL_QL_HD void trl_quality_features(int status, const long long* raw, const int*
 }
 
 // ---- best shots -----------------------------------------------------------------------------------------------------------------------
-// The best row of a group is the one with the largest trl_pool_key(quality, absolute row) (trl_pool.h): the larger quality, ties as
+// The best row of a group is the one with the largest trl_best_key(quality, absolute row) (trl_bestkey.h): the larger quality, ties as
 // floats (-0 == +0) to the lower row, a NaN never a candidate, key 0 for none.

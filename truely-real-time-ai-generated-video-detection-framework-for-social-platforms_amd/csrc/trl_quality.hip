@@ -10,8 +10,10 @@
 // The accumulators live in the caller's workspace, zeroed on the stream in front of the kernel.
 // k_quality_finish: one wave per face reads N, the sums of Y and Y^2, the clipped counts and the two percentiles off the histogram
 // (a lane holds four bins; one scan) and lane 0 runs the float chains of trl_quality.h.
-#include "trl_gallery_host.h"
-#include "trl_pool.h"
+// Best shots: the key is trl_bestkey.h's (the templates' representative key), and trl_best_read ends in trl_pool.hip's
+// trl_best_key_read.  The entry points' checks and device lookup are trl_host.h's; the workspace is carved over an Arena (ql_carve).
+#include "trl_bestkey.h"
+#include "trl_host.h"
 #include "trl_quality.h"
 
 namespace {
@@ -22,10 +24,6 @@ constexpr int QL_BAND_DEFAULT = 32;
 constexpr int QL_LDS_MIN = 16384;                       // bytes of luma a workgroup holds: at least this, at least three frame rows
 constexpr int QL_LDS_MAX = 3 * TRL_QUALITY_MAX_DIM;     // 48 KiB
 constexpr int QL_GRID_BANDS = 64;                       // band slots of the grid; a workgroup strides over its face's bands
-
-// the workspace: per face the histogram (int32), then per face sum L, sum L^2 (int64)
-inline size_t ql_sums_at(long long m) { return (size_t)m * 4 * TRL_QUALITY_BINS; }
-inline size_t ql_ws_bytes(long long m) { return (size_t)m * (16 + 4 * TRL_QUALITY_BINS); }
 
 __device__ __forceinline__ long long ql_wave_sum(long long v) {
 #pragma unroll
@@ -169,7 +167,7 @@ __global__ __launch_bounds__(QL_THREADS) void k_best_max(unsigned long long* __r
     const long long r = (long long)blockIdx.x * QL_THREADS + threadIdx.x;
     if (r >= m) return;
     const long long g = gid[r];
-    const unsigned long long key = trl_pool_key(quality[r], row_base + r);
+    const unsigned long long key = trl_best_key(quality[r], row_base + r);
     if (key && g >= 0 && g < groups) atomicMax(keys + g, key);
 }
 
@@ -180,62 +178,52 @@ __global__ __launch_bounds__(QL_THREADS) void k_best_copy(const unsigned long lo
                                                           uint32_t* __restrict__ best) {
     const long long r = blockIdx.x, g = gid[r];
     if (g < 0 || g >= groups) return;
-    const unsigned long long key = trl_pool_key(quality[r], row_base + r);
+    const unsigned long long key = trl_best_key(quality[r], row_base + r);
     if (!key || keys[g] != key) return;
     const uint32_t* src = faces + (size_t)r * (size_t)face_floats;
     uint32_t* dst = best + (size_t)g * (size_t)face_floats;
     for (long long i = threadIdx.x; i < face_floats; i += QL_THREADS) dst[i] = src[i];
 }
 
-__global__ __launch_bounds__(QL_THREADS) void k_best_read(const unsigned long long* __restrict__ keys, long long groups,
-                                                          int32_t* __restrict__ row, float* __restrict__ quality) {
-    const long long g = (long long)blockIdx.x * QL_THREADS + threadIdx.x;
-    if (g >= groups) return;
-    int32_t i;
-    float q;
-    trl_pool_key_decode(keys[g], &i, &q);
-    row[g] = i;
-    quality[g] = q;
-}
-
-int ql_refuse(const char* who, const char* why) {
-    trl_set_error("%s: %s", who, why);
-    return TRL_ERR_INVALID;
-}
-
-const char* ql_check_keys(const void* d_keys, long long groups) {
-    if (groups < 0 || groups > 0x7fffffffLL) return "groups outside 0..2^31 - 1";
-    if (!d_keys) return "null keys";
-    if ((uintptr_t)d_keys & 7) return "the keys are not 8-byte aligned";
-    return nullptr;
+// the workspace of m face rows: per face the histogram (int32), then per face sum L, sum L^2 (int64).  trl_quality_workspace is a dry
+// run of this; a histogram is 1024 bytes, so the sums start where the histograms end and the blocks hold 1040 m bytes together
+bool ql_carve(Arena& a, long long m, int32_t** hists, unsigned long long** sums) {
+    *hists = (int32_t*)a.alloc((size_t)m * TRL_QUALITY_BINS * sizeof(int32_t));
+    *sums = (unsigned long long*)a.alloc((size_t)m * 2 * sizeof(unsigned long long));
+    return *hists && *sums;
 }
 
 }  // namespace
 
 extern "C" size_t trl_quality_workspace(long long m) {
     if (m < 0 || m > TRL_QUALITY_MAX_ROWS) return 0;
-    return ql_ws_bytes(m > 0 ? m : 1);
+    Arena a = Arena::counter(0);
+    int32_t* hists;
+    unsigned long long* sums;
+    ql_carve(a, m > 0 ? m : 1, &hists, &sums);
+    return a.high;
 }
 
 extern "C" int trl_face_quality(const uint8_t* d_frames, int n, int H, int W, const int32_t* d_frame_of, const float* d_boxes,
                                 const float* d_points, long long m, const trl_quality_params* params, int max_band_rows, void* d_ws,
                                 size_t ws_bytes, long long* d_raw, float* d_feat, int32_t* d_hist, int32_t* d_status, void* stream) {
     const char* who = "trl_face_quality";
-    if (m < 0 || m > TRL_QUALITY_MAX_ROWS) return ql_refuse(who, "m outside 0..2^24");
-    if (n < 0) return ql_refuse(who, "n < 0");
-    if (H < 1 || H > TRL_QUALITY_MAX_DIM || W < 1 || W > TRL_QUALITY_MAX_DIM) return ql_refuse(who, "H or W outside 1..16384");
-    if (max_band_rows < 0) return ql_refuse(who, "max_band_rows < 0");
+    if (m < 0 || m > TRL_QUALITY_MAX_ROWS) return trl_refuse(who, "m outside 0..2^24");
+    if (n < 0) return trl_refuse(who, "n < 0");
+    if (H < 1 || H > TRL_QUALITY_MAX_DIM || W < 1 || W > TRL_QUALITY_MAX_DIM) return trl_refuse(who, "H or W outside 1..16384");
+    if (max_band_rows < 0) return trl_refuse(who, "max_band_rows < 0");
     const trl_quality_params prm = params ? *params : trl_quality_defaults();
-    if (!trl_quality_params_ok(prm)) return ql_refuse(who, "a reference of the params is not finite and > 0");
+    if (!trl_quality_params_ok(prm)) return trl_refuse(who, "a reference of the params is not finite and > 0");
     if (m == 0) return TRL_OK;
-    if ((!d_frames && n > 0) || !d_frame_of || !d_boxes || !d_raw || !d_feat || !d_status) return ql_refuse(who, "null argument");
-    if (!d_ws) return ql_refuse(who, "null workspace");
-    if (!trl_workspace_ok(who, d_ws, ws_bytes, ws_bytes >= ql_ws_bytes(m), [&] { return trl_quality_workspace(m); })) return TRL_ERR_INVALID;
+    if ((!d_frames && n > 0) || !d_frame_of || !d_boxes || !d_raw || !d_feat || !d_status) return trl_refuse(who, "null argument");
+    if (!d_ws) return trl_refuse(who, "null workspace");
+    Arena a = Arena::over(d_ws, ws_bytes);
+    int32_t* hists;
+    unsigned long long* sums;
+    if (!trl_workspace_ok(who, d_ws, ws_bytes, ql_carve(a, m, &hists, &sums), [&] { return trl_quality_workspace(m); })) return TRL_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     TRL_CHECK(trl_device_of(d_ws));
-    int32_t* hists = (int32_t*)d_ws;
-    unsigned long long* sums = (unsigned long long*)((char*)d_ws + ql_sums_at(m));
-    TRL_HIP(hipMemsetAsync(d_ws, 0, ql_ws_bytes(m), s));
+    TRL_HIP(hipMemsetAsync(d_ws, 0, a.high, s));
     const int band_rows = max_band_rows ? max_band_rows : QL_BAND_DEFAULT;
     int lds_luma = (3 * W + 7) & ~7;
     if (lds_luma < QL_LDS_MIN) lds_luma = QL_LDS_MIN;
@@ -262,12 +250,12 @@ extern "C" int trl_face_quality(const uint8_t* d_frames, int n, int H, int W, co
 extern "C" int trl_best_update(unsigned long long* d_keys, long long groups, const float* d_quality, const int32_t* d_gid, long long m,
                                long long row_base, const float* d_faces, long long face_floats, float* d_best_faces, void* stream) {
     const char* who = "trl_best_update";
-    if (const char* why = ql_check_keys(d_keys, groups)) return ql_refuse(who, why);
-    if (m < 0 || row_base < 0 || row_base + m > 0x7fffffffLL) return ql_refuse(who, "row_base + m outside 0..2^31 - 1");
-    if ((d_faces != nullptr) != (d_best_faces != nullptr)) return ql_refuse(who, "faces without best_faces, or the reverse");
-    if (d_faces && face_floats < 1) return ql_refuse(who, "face_floats < 1");
+    TRL_CHECK(trl_check_groups(who, "keys are", d_keys, groups));
+    if (m < 0 || row_base < 0 || row_base + m > 0x7fffffffLL) return trl_refuse(who, "row_base + m outside 0..2^31 - 1");
+    if ((d_faces != nullptr) != (d_best_faces != nullptr)) return trl_refuse(who, "faces without best_faces, or the reverse");
+    if (d_faces && face_floats < 1) return trl_refuse(who, "face_floats < 1");
     if (m == 0 || groups == 0) return TRL_OK;
-    if (!d_quality || !d_gid) return ql_refuse(who, "null argument");
+    if (!d_quality || !d_gid) return trl_refuse(who, "null argument");
     hipStream_t s = (hipStream_t)stream;
     TRL_CHECK(trl_device_of(d_keys));
     k_best_max<<<(unsigned)((m + QL_THREADS - 1) / QL_THREADS), QL_THREADS, 0, s>>>(d_keys, groups, d_quality, d_gid, m, row_base);
@@ -281,12 +269,5 @@ extern "C" int trl_best_update(unsigned long long* d_keys, long long groups, con
 }
 
 extern "C" int trl_best_read(const unsigned long long* d_keys, long long groups, int32_t* d_row, float* d_quality, void* stream) {
-    const char* who = "trl_best_read";
-    if (const char* why = ql_check_keys(d_keys, groups)) return ql_refuse(who, why);
-    if (groups == 0) return TRL_OK;
-    if (!d_row || !d_quality) return ql_refuse(who, "null argument");
-    TRL_CHECK(trl_device_of(d_keys));
-    k_best_read<<<(unsigned)((groups + QL_THREADS - 1) / QL_THREADS), QL_THREADS, 0, (hipStream_t)stream>>>(d_keys, groups, d_row, d_quality);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
+    return trl_best_key_read("trl_best_read", "keys are", d_keys, groups, d_row, d_quality, (hipStream_t)stream);
 }

@@ -14,11 +14,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define TRL_TK_HD __host__ __device__ __forceinline__
-#else
-#define TRL_TK_HD inline
-#endif
+#include "trl_hd.h"
 
 #define TRL_TK_SLOTS 64
 #define TRL_TK_ROW 8              // int32 per table row
@@ -43,7 +39,7 @@ struct TrlTkHead {
 #define TRL_TK_STATE_BYTES (TRL_TK_EMB_OFFSET + TRL_TK_SLOTS * 512 * sizeof(float))
 
 // torchvision's box_iou in float32, one rounding per operation (build with -ffp-contract=off): trl_cascade.hip's non-MIN overlap.
-TRL_TK_HD float trl_tk_iou(const float* a, const float* b) {
+TRL_HD float trl_tk_iou(const float* a, const float* b) {
     const float area_a = (a[2] - a[0]) * (a[3] - a[1]);
     const float area_b = (b[2] - b[0]) * (b[3] - b[1]);
     const float x1 = a[0] > b[0] ? a[0] : b[0], y1 = a[1] > b[1] ? a[1] : b[1];
@@ -56,16 +52,16 @@ TRL_TK_HD float trl_tk_iou(const float* a, const float* b) {
 }
 
 // A track is live at frame f iff f - last_frame - 1 <= max_age (64-bit: max_age = INT32_MAX never ends a track)
-TRL_TK_HD bool trl_tk_live(long long f, int32_t last_frame, int32_t max_age) {
+TRL_HD bool trl_tk_live(long long f, int32_t last_frame, int32_t max_age) {
     return f - (long long)last_frame - 1 <= (long long)max_age;
 }
 
 // The IoU half of admissibility; a pair that fails it needs no similarity.
-TRL_TK_HD bool trl_tk_iou_ok(float iou, float iou_min) { return iou_min <= 0.f || iou >= iou_min; }
+TRL_HD bool trl_tk_iou_ok(float iou, float iou_min) { return iou_min <= 0.f || iou >= iou_min; }
 
 // The pair's key -- sim with embeddings, iou without -- or NaN when the pair is not admissible.  NaN fails every comparison, so
 // a NaN iou fails iou >= iou_min, a NaN sim fails sim >= sim_min, and a NaN key (iou_min <= 0, no embeddings) is returned as it is.
-TRL_TK_HD float trl_tk_pair_key(float iou, float sim, bool has_emb, float iou_min, float sim_min) {
+TRL_HD float trl_tk_pair_key(float iou, float sim, bool has_emb, float iou_min, float sim_min) {
     const float none = __builtin_nanf("");
     if (!trl_tk_iou_ok(iou, iou_min)) return none;
     if (!has_emb) return iou;
@@ -73,21 +69,21 @@ TRL_TK_HD float trl_tk_pair_key(float iou, float sim, bool has_emb, float iou_mi
 }
 
 // model.py:62-66,70 -- one comparison of the state machine (drift_scan_kernel's two lines); returns the frame's flag
-TRL_TK_HD int trl_tk_step(int32_t* run, int32_t* hits, float sim) {
+TRL_HD int trl_tk_step(int32_t* run, int32_t* hits, float sim) {
     *run = (sim < 0.99f) ? *run + 1 : 0;
     if (*run > 15) { *hits += 1; return 1; }
     return 0;
 }
 
 // {first_frame, last_frame, n_obs, run, hits, slot (-1 once ended), 0, 0} at row `id`; nothing for an id past the table
-TRL_TK_HD void trl_tk_row(const TrlTkSlot& s, int slot, int32_t* table, int table_cap) {
+TRL_HD void trl_tk_row(const TrlTkSlot& s, int slot, int32_t* table, int table_cap) {
     if (!table || s.id >= table_cap) return;
     int32_t* r = table + (long long)s.id * TRL_TK_ROW;
     r[0] = s.first_frame; r[1] = s.last_frame; r[2] = s.n_obs; r[3] = s.run; r[4] = s.hits; r[5] = slot; r[6] = 0; r[7] = 0;
 }
 
 // Ageing of one slot at frame f: a track that is not live ends.
-TRL_TK_HD void trl_tk_age(TrlTkSlot& s, long long f, int32_t max_age, int32_t* table, int table_cap) {
+TRL_HD void trl_tk_age(TrlTkSlot& s, long long f, int32_t max_age, int32_t* table, int table_cap) {
     if (!s.used || trl_tk_live(f, s.last_frame, max_age)) return;
     trl_tk_row(s, -1, table, table_cap);
     s.used = 0;
@@ -99,14 +95,14 @@ struct TrlTkCand {
     int32_t id, det, slot;        // slot < 0: no candidate
 };
 
-TRL_TK_HD TrlTkCand trl_tk_no_cand() {
+TRL_HD TrlTkCand trl_tk_no_cand() {
     TrlTkCand c;
     c.key = 0.f; c.id = 0; c.det = 0; c.slot = -1;
     return c;
 }
 
 // a is taken before b: the larger key (float comparison: -0 == +0), then the lower track id, then the lower detection index
-TRL_TK_HD bool trl_tk_cand_before(const TrlTkCand& a, const TrlTkCand& b) {
+TRL_HD bool trl_tk_cand_before(const TrlTkCand& a, const TrlTkCand& b) {
     if (a.slot < 0) return false;
     if (b.slot < 0) return true;
     if (a.key != b.key) return a.key > b.key;
@@ -116,7 +112,7 @@ TRL_TK_HD bool trl_tk_cand_before(const TrlTkCand& a, const TrlTkCand& b) {
 
 // The first candidate of detection `det`'s column: key[slot * ld + det] over the slots of `avail` (bit s: slot s is live and not
 // matched yet; slot_id[s] is its track's id).  The walk is over the set bits: a frame with three live tracks looks at three keys.
-TRL_TK_HD TrlTkCand trl_tk_column_first(const float* key, int ld, const int32_t* slot_id, unsigned long long avail, int det) {
+TRL_HD TrlTkCand trl_tk_column_first(const float* key, int ld, const int32_t* slot_id, unsigned long long avail, int det) {
     TrlTkCand best = trl_tk_no_cand();
     while (avail) {
         const int s = __builtin_ctzll(avail);
@@ -136,7 +132,7 @@ TRL_TK_HD TrlTkCand trl_tk_column_first(const float* key, int ld, const int32_t*
 // whose candidate sat on the matched track look again.  det_slot[d] receives the slot matched to detection d, -1 for none.
 // On the host NL = 1 and W::first is the identity.
 template <int NL, class W>
-TRL_TK_HD void trl_tk_greedy(W& w, int lane, const float* key, int ld, const int32_t* slot_id, unsigned long long live, int nd,
+TRL_HD void trl_tk_greedy(W& w, int lane, const float* key, int ld, const int32_t* slot_id, unsigned long long live, int nd,
                              int32_t* det_slot) {
     constexpr int PER = TRL_TK_SLOTS / NL;
     TrlTkCand cand[PER];
@@ -176,7 +172,7 @@ TRL_TK_HD void trl_tk_greedy(W& w, int lane, const float* key, int ld, const int
 // ---- what a frame does to the slots ----------------------------------------------------------------------------------------------
 // A matched track takes the detection (box, n2 = dot512(det, det), src = its row) at frame f; with embeddings it makes one step
 // of the state machine with the pair's similarity.  Returns the detection's flag.
-TRL_TK_HD int trl_tk_matched(TrlTkSlot& s, const float* box, float n2, int32_t src, long long f, float sim, bool has_emb) {
+TRL_HD int trl_tk_matched(TrlTkSlot& s, const float* box, float n2, int32_t src, long long f, float sim, bool has_emb) {
     s.box[0] = box[0]; s.box[1] = box[1]; s.box[2] = box[2]; s.box[3] = box[3];
     s.n2 = n2;
     s.src = src;
@@ -188,7 +184,7 @@ TRL_TK_HD int trl_tk_matched(TrlTkSlot& s, const float* box, float n2, int32_t s
 // The slot a new track takes at frame f: the free slot of the lowest index; else the slot of the track that was neither matched nor
 // created in this frame (those have last_frame == f) with the smallest last_frame, ties to the smallest id.  -1: none (more than
 // 64 detections in a frame, which the caller excludes).
-TRL_TK_HD int trl_tk_choose_slot(const TrlTkSlot* slots, long long f) {
+TRL_HD int trl_tk_choose_slot(const TrlTkSlot* slots, long long f) {
     int victim = -1;
     for (int s = 0; s < TRL_TK_SLOTS; s++) {
         if (!slots[s].used) return s;
@@ -203,7 +199,7 @@ TRL_TK_HD int trl_tk_choose_slot(const TrlTkSlot* slots, long long f) {
 // Every unmatched detection (det_slot[d] < 0) of the frame's first nd, in ascending d, starts a track with the next id.  box / n2
 // are indexed by d, row0 is the frame's first row in the window; det_slot[d] receives the new track's slot and track[row0 + d] its id.
 // An evicted track ends: its row is written with slot -1.  A new id past the table adds to table_overflow.
-TRL_TK_HD void trl_tk_create(TrlTkSlot* slots, TrlTkHead& head, int32_t* det_slot, int nd, const float* box, const float* n2, int row0,
+TRL_HD void trl_tk_create(TrlTkSlot* slots, TrlTkHead& head, int32_t* det_slot, int nd, const float* box, const float* n2, int row0,
                              long long f, int32_t* table, int table_cap, int32_t* track) {
     for (int d = 0; d < nd; d++) {
         if (det_slot[d] >= 0) continue;

@@ -2,8 +2,9 @@
 // machine per person.  trl_track_update, trl_track_scores; context-free like the gallery.
 //
 // The decisions are trl_tracks.h's (shared with tests/tracks_main.cpp); this file adds the arithmetic on embeddings
-// (trl_wave_dot512, drift_sims_kernel's expression), the schedule and the hand-over between windows.
-#include "trl_common.h"
+// (trl_wave_dot512, drift_sims_kernel's expression), the schedule and the hand-over between windows.  Refusals and the device
+// lookup are trl_host.h's.
+#include "trl_host.h"
 #include "trl_tracks.h"
 
 static_assert(TRL_TK_SLOTS == TRL_TRACK_SLOTS, "slot count");
@@ -236,13 +237,6 @@ __global__ __launch_bounds__(256) void k_track_scores(const char* state, const i
     }
 }
 
-int tk_device_of(const void* p) {
-    hipPointerAttribute_t attr;
-    TRL_HIP(hipPointerGetAttributes(&attr, p));
-    TRL_HIP(hipSetDevice(attr.device));
-    return TRL_OK;
-}
-
 }  // namespace
 
 extern "C" int trl_track_update(void* d_state, const float* d_boxes, const int32_t* d_counts, int n, int m, const float* d_emb, float iou_min,
@@ -252,13 +246,11 @@ extern "C" int trl_track_update(void* d_state, const float* d_boxes, const int32
         trl_set_error("trl_track_update: n = %d, m = %d, max_age = %d, table_cap = %d", n, m, max_age, table_cap);
         return TRL_ERR_INVALID;
     }
-    if (iou_min != iou_min || sim_min != sim_min) { trl_set_error("trl_track_update: a NaN threshold"); return TRL_ERR_INVALID; }
-    if (!d_state || ((uintptr_t)d_state & 7)) { trl_set_error("trl_track_update: the state is null or not 8-byte aligned"); return TRL_ERR_INVALID; }
-    if ((n > 0 && !d_counts) || (m > 0 && (!d_boxes || !d_track || !d_sim || !d_flag)) || (table_cap > 0 && !d_table)) {
-        trl_set_error("trl_track_update: null argument");
-        return TRL_ERR_INVALID;
-    }
-    TRL_CHECK(tk_device_of(d_state));
+    if (iou_min != iou_min || sim_min != sim_min) return trl_refuse("trl_track_update", "a NaN threshold");
+    if (!d_state || ((uintptr_t)d_state & 7)) return trl_refuse("trl_track_update", "the state is null or not 8-byte aligned");
+    if ((n > 0 && !d_counts) || (m > 0 && (!d_boxes || !d_track || !d_sim || !d_flag)) || (table_cap > 0 && !d_table))
+        return trl_refuse("trl_track_update", "null argument");
+    TRL_CHECK(trl_device_of(d_state));
     k_track_update<<<1, TK_THREADS, 0, (hipStream_t)stream>>>((char*)d_state, d_boxes, d_counts, n, m, d_emb, iou_min, sim_min, max_age, d_track,
                                                              d_sim, d_flag, d_table, table_cap);
     TRL_LAUNCH_CHECK();
@@ -268,8 +260,8 @@ extern "C" int trl_track_update(void* d_state, const float* d_boxes, const int32
 extern "C" int trl_track_scores(const void* d_state, const int32_t* d_table, int table_cap, long long frame_count, int fps, int32_t* d_score,
                                 int32_t* d_summary, void* stream) {
     if (table_cap < 0) { trl_set_error("trl_track_scores: table_cap = %d", table_cap); return TRL_ERR_INVALID; }
-    if (!d_state || !d_summary || (table_cap > 0 && (!d_table || !d_score))) { trl_set_error("trl_track_scores: null argument"); return TRL_ERR_INVALID; }
-    TRL_CHECK(tk_device_of(d_state));
+    if (!d_state || !d_summary || (table_cap > 0 && (!d_table || !d_score))) return trl_refuse("trl_track_scores", "null argument");
+    TRL_CHECK(trl_device_of(d_state));
     k_track_scores<<<1, 256, 0, (hipStream_t)stream>>>((const char*)d_state, d_table, table_cap, frame_count, fps, d_score, d_summary);
     TRL_LAUNCH_CHECK();
     return TRL_OK;

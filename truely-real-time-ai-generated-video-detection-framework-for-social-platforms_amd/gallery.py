@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._tensors import DIM, cuda_device, grown, ptr, rows, stream, vector
 
 METRICS = {"cosine": 0, "euclidean": 1}
 MAX_K = 16
@@ -41,34 +42,13 @@ MAX_CLUSTER_ROWS = 65536                 # the link bitmap's limit (n * n / 8 by
 MAX_CLUSTER_LIST_ROWS = 1 << 24
 CLUSTER_METHODS = ("auto", "bitmap", "lists")
 MAX_EDGES = 1023
-DIM = 512
 TEMPLATE_CHUNK = 8192                    # gallery columns turned into rows at a time by templates(): 16 MB
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None else 0)
 
 
 def _metric(metric) -> int:
     if metric not in METRICS:
         raise ValueError(f"metric must be one of {sorted(METRICS)}, not {metric!r}")
     return METRICS[metric]
-
-
-def _rows(x, device) -> torch.Tensor:
-    """(n, 512) float32, contiguous, on `device` (a host array or tensor is uploaded once)."""
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.array(x, np.float32))                 # (a copy: the caller's array may be read-only)
-    x = x.detach().to(device, torch.float32)
-    if x.dim() == 1:
-        x = x[None]
-    if x.dim() != 2 or x.shape[1] != DIM:
-        raise ValueError(f"expected (n, {DIM}) embeddings, got {tuple(x.shape)}")
-    return x.contiguous()
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class FaceGallery:
@@ -80,11 +60,7 @@ class FaceGallery:
         self.metric = metric
         self._metric = _metric(metric)
         self.lib = _lib.load()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("a FaceGallery lives on a GPU")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = cuda_device(device, "a FaceGallery lives on a GPU")
         self._m = 0
         self._labels: list = []
         self._identities: list = []                      # the distinct labels in order of first enrolment
@@ -116,18 +92,15 @@ class FaceGallery:
 
     def add(self, embeddings, labels) -> None:
         """Append m embeddings, (m, 512), with their m labels (any objects)."""
-        rows = _rows(embeddings, self.device)
+        emb = rows(embeddings, self.device)
         labels = list(labels)
-        m = rows.shape[0]
+        m = emb.shape[0]
         if len(labels) != m:
             raise ValueError(f"{m} embeddings but {len(labels)} labels")
         if self._m + m > self.ld:                        # grow geometrically; the copy stays on the device
-            old_mat, old_n2, old_gid, old_ld = self._mat, self._n2, self._gid, self.ld
-            self._alloc(max(2 * old_ld, self._m + m))
-            self._mat[:, :old_ld].copy_(old_mat)
-            self._n2[:old_ld].copy_(old_n2)
-            self._gid[:old_ld].copy_(old_gid)
-        _lib.check(self.lib.trl_gallery_pack(_ptr(rows), m, _ptr(self._mat), self.ld, _ptr(self._n2), self._m, _stream(self.device)))
+            ld = (max(2 * self.ld, self._m + m) + 31) // 32 * 32
+            self._mat, self._n2, self._gid = grown(self._mat, ld, dim=1), grown(self._n2, ld), grown(self._gid, ld, fill=-1)
+        _lib.check(self.lib.trl_gallery_pack(ptr(emb), m, ptr(self._mat), self.ld, ptr(self._n2), self._m, stream(self.device)))
         ids = []
         for l in labels:
             try:
@@ -153,17 +126,17 @@ class FaceGallery:
 
     def scores(self, emb) -> torch.Tensor:
         """(n, len(self)) scores of every query against every enrolled row."""
-        q = _rows(emb, self.device)
+        q = rows(emb, self.device)
         n, m = q.shape[0], self._m
         out = torch.empty((n, m), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.trl_gallery_scores(_ptr(q), n, _ptr(self._mat), self.ld, _ptr(self._n2), m, self._metric, _ptr(out), m,
-                                               _stream(self.device)))
+        _lib.check(self.lib.trl_gallery_scores(ptr(q), n, ptr(self._mat), self.ld, ptr(self._n2), m, self._metric, ptr(out), m,
+                                               stream(self.device)))
         return out
 
     def search(self, emb, k: int = 5, valid=None, max_strip_cols: int = 0):
         """(index (n, k) int32, score (n, k) float32), best match first.  Slots past the gallery, and every slot of a row whose
         ``valid`` entry is zero, hold index -1 and score NaN."""
-        q = _rows(emb, self.device)
+        q = rows(emb, self.device)
         n, m, k = q.shape[0], self._m, int(k)
         if not 1 <= k <= MAX_K:
             raise ValueError(f"k must be 1..{MAX_K}")
@@ -172,8 +145,8 @@ class FaceGallery:
         score = torch.empty((n, k), dtype=torch.float32, device=self.device)
         need = self.lib.trl_gallery_search_workspace(n, m, k, max_strip_cols)
         ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
-        _lib.check(self.lib.trl_gallery_search(_ptr(q), _ptr(valid), n, _ptr(self._mat), self.ld, _ptr(self._n2), m, self._metric, k,
-                                               _ptr(score), _ptr(idx), _ptr(ws), need, max_strip_cols, _stream(self.device)))
+        _lib.check(self.lib.trl_gallery_search(ptr(q), ptr(valid), n, ptr(self._mat), self.ld, ptr(self._n2), m, self._metric, k,
+                                               ptr(score), ptr(idx), ptr(ws), need, max_strip_cols, stream(self.device)))
         return idx, score
 
     def identify(self, emb, threshold: float | None = None, valid=None):
@@ -194,7 +167,7 @@ class FaceGallery:
         (``scores``' bits).  The enrolled rows are taken in ``search``'s order and a row is kept iff no earlier row has its label;
         rows whose ``gallery_valid`` entry is zero are left out.  Slots past the last identity, and every slot of a row whose
         ``valid`` entry is zero, hold -1 / -1 / NaN.  The gallery is streamed once; the call does not synchronise."""
-        q = _rows(emb, self.device)
+        q = rows(emb, self.device)
         n, m, k = q.shape[0], self._m, int(k)
         if not 1 <= k <= MAX_K:
             raise ValueError(f"k must be 1..{MAX_K}")
@@ -207,9 +180,9 @@ class FaceGallery:
         score = torch.empty((n, k), dtype=torch.float32, device=self.device)
         need = self.lib.trl_gallery_search_groups_workspace(n, m, k, max_strip_cols)
         ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
-        _lib.check(self.lib.trl_gallery_search_groups(_ptr(q), _ptr(valid), n, _ptr(self._mat), self.ld, _ptr(self._n2), _ptr(gid), m,
-                                                      self._metric, k, _ptr(score), _ptr(idx), _ptr(group), _ptr(ws), need, max_strip_cols,
-                                                      _stream(self.device)))
+        _lib.check(self.lib.trl_gallery_search_groups(ptr(q), ptr(valid), n, ptr(self._mat), self.ld, ptr(self._n2), ptr(gid), m,
+                                                      self._metric, k, ptr(score), ptr(idx), ptr(group), ptr(ws), need, max_strip_cols,
+                                                      stream(self.device)))
         return group, idx, score
 
     def identify_topk(self, emb, k: int = 5, threshold: float | None = None, valid=None, gallery_valid=None) -> list:
@@ -233,7 +206,7 @@ class FaceGallery:
         gid = self._gid[:m]
         if gv is not None:
             gid = torch.where(gv != 0, gid, torch.full_like(gid, -1))         # (search_identities' fold: a masked row is an excluded row)
-        w = pool._vector(weights, m, torch.float32, self.device, "weights")
+        w = vector(weights, m, torch.float32, self.device, "weights")
 
         def blocks():
             for a in range(0, m, TEMPLATE_CHUNK):
@@ -303,18 +276,18 @@ class FaceGallery:
         core = torch.empty((n,), dtype=torch.uint8, device=self.device)
         count = torch.zeros((1,), dtype=torch.int32, device=self.device)
         rounds = C.c_int(0)
-        s = _stream(self.device)
+        s = stream(self.device)
         info = {"labels": labels, "core": core, "degree": degree}
         if method == "bitmap":
             words = (n + 31) // 32
             adj = torch.empty((n, words), dtype=torch.int32, device=self.device)
             need = self.lib.trl_cluster_workspace(n)
             ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
-            rows = self.rows() if n else None
-            _lib.check(self.lib.trl_cluster_links(_ptr(rows), _ptr(valid), n, _ptr(self._mat), self.ld, _ptr(self._n2), self._metric,
-                                                  threshold, _ptr(adj), words, _ptr(degree), max_strip_cols, s))
-            _lib.check(self.lib.trl_cluster_labels(_ptr(adj), words, _ptr(degree), n, min_samples, _ptr(labels), _ptr(core), _ptr(count),
-                                                   _ptr(ws), need, C.byref(rounds), s))
+            q = self.rows() if n else None
+            _lib.check(self.lib.trl_cluster_links(ptr(q), ptr(valid), n, ptr(self._mat), self.ld, ptr(self._n2), self._metric,
+                                                  threshold, ptr(adj), words, ptr(degree), max_strip_cols, s))
+            _lib.check(self.lib.trl_cluster_labels(ptr(adj), words, ptr(degree), n, min_samples, ptr(labels), ptr(core), ptr(count),
+                                                   ptr(ws), need, C.byref(rounds), s))
         else:
             offsets, index, _score = self.range_search(None, threshold, valid=valid, max_results=max_links, max_strip_cols=max_strip_cols)
             del _score                                   # (the fill pass writes the scores; the labels do not read them)
@@ -323,8 +296,8 @@ class FaceGallery:
                 index = torch.empty((1,), dtype=torch.int32, device=self.device)          # (an empty tensor has no address)
             need = self.lib.trl_cluster_lists_workspace(n)
             ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
-            _lib.check(self.lib.trl_cluster_labels_lists(_ptr(offsets), _ptr(index), _ptr(valid), n, min_samples, 0, _ptr(degree),
-                                                         _ptr(labels), _ptr(core), _ptr(count), _ptr(ws), need, C.byref(rounds), s))
+            _lib.check(self.lib.trl_cluster_labels_lists(ptr(offsets), ptr(index), ptr(valid), n, min_samples, 0, ptr(degree),
+                                                         ptr(labels), ptr(core), ptr(count), ptr(ws), need, C.byref(rounds), s))
         if not return_info:
             return labels
         info.update(n_clusters=int(count.item()), rounds=rounds.value, method=method)
@@ -355,7 +328,7 @@ class FaceGallery:
             q, n, qid, pairs = (self.rows() if m else None), m, gid, 1
             qv = gv = _valid(valid if gallery_valid is None else gallery_valid, m, self.device)
         else:
-            q = _rows(emb, self.device)
+            q = rows(emb, self.device)
             n, pairs = q.shape[0], 0
             if labels is None:
                 raise ValueError("emb needs its labels")
@@ -371,9 +344,9 @@ class FaceGallery:
         counts = torch.empty((2, E + 2), dtype=torch.int64, device=self.device)
         need = self.lib.trl_gallery_hist_workspace(n, m, E, max_strip_cols)
         ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
-        _lib.check(self.lib.trl_gallery_hist(_ptr(q), _ptr(qv), _ptr(qid_t), n, _ptr(self._mat), self.ld, _ptr(self._n2), _ptr(gv),
-                                             _ptr(gid_t), m, self._metric, pairs, _ptr(edges), E, _ptr(counts), _ptr(ws), need,
-                                             max_strip_cols, _stream(self.device)))
+        _lib.check(self.lib.trl_gallery_hist(ptr(q), ptr(qv), ptr(qid_t), n, ptr(self._mat), self.ld, ptr(self._n2), ptr(gv),
+                                             ptr(gid_t), m, self._metric, pairs, ptr(edges), E, ptr(counts), ptr(ws), need,
+                                             max_strip_cols, stream(self.device)))
         return {"edges": edges, "genuine": counts[1, :E + 1], "impostor": counts[0, :E + 1], "nan": counts[:, E + 1]}
 
     def _range_pass1(self, emb, threshold, valid, gallery_valid, max_strip_cols):
@@ -387,14 +360,14 @@ class FaceGallery:
             q, n, self_pairs = (self.rows() if m else None), m, 1
             qv = gv = _valid(valid if gallery_valid is None else gallery_valid, m, self.device)
         else:
-            q = _rows(emb, self.device)
+            q = rows(emb, self.device)
             n, self_pairs = q.shape[0], 0
             qv, gv = _valid(valid, n, self.device), _valid(gallery_valid, m, self.device)
         offsets = torch.zeros((n + 1,), dtype=torch.int64, device=self.device)
         need = self.lib.trl_gallery_range_workspace(n, m, max_strip_cols)
         ws = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
-        args = (_ptr(q), _ptr(qv), n, _ptr(self._mat), self.ld, _ptr(self._n2), _ptr(gv), m, self._metric, float(threshold), self_pairs)
-        _lib.check(self.lib.trl_gallery_range_count(*args, _ptr(offsets), _ptr(ws), need, max_strip_cols, _stream(self.device)))
+        args = (ptr(q), ptr(qv), n, ptr(self._mat), self.ld, ptr(self._n2), ptr(gv), m, self._metric, float(threshold), self_pairs)
+        _lib.check(self.lib.trl_gallery_range_count(*args, ptr(offsets), ptr(ws), need, max_strip_cols, stream(self.device)))
         return args, (q, qv, gv), offsets, ws, need
 
     def range_count(self, emb=None, threshold: float | None = None, valid=None, gallery_valid=None, max_strip_cols: int = 0) -> torch.Tensor:
@@ -424,8 +397,8 @@ class FaceGallery:
             raise ValueError(f"range_search found {total} matches, more than max_results = {int(max_results)}")
         index = torch.empty((total,), dtype=torch.int32, device=self.device)
         score = torch.empty((total,), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.trl_gallery_range_fill(*args, _ptr(offsets), _ptr(ws), need, total, _ptr(index), _ptr(score), max_strip_cols,
-                                                   _stream(self.device)))
+        _lib.check(self.lib.trl_gallery_range_fill(*args, ptr(offsets), ptr(ws), need, total, ptr(index), ptr(score), max_strip_cols,
+                                                   stream(self.device)))
         return offsets, index, score
 
     def roc(self, emb=None, labels=None, edges=None, valid=None, gallery_valid=None, max_strip_cols: int = 0) -> dict:

@@ -31,57 +31,13 @@ candidate has index -1 and score NaN: "the most representative frame of a person
 of ``FaceGallery.cluster`` / ``cluster_embeddings`` need nothing more than ``pool_embeddings(emb, labels)`` with their labels."""
 from __future__ import annotations
 
-import ctypes as C
-
-import numpy as np
 import torch
 
 from . import _lib
+from ._tensors import DIM, cuda_device, grown, ptr, rows, stream, vector
 
-DIM = 512
 MAX_ROWS = 1 << 30                       # contributing rows of one group (csrc/trl_pool.h): the host's count of rows added stays below
 ROW_CHUNK = 1 << 20                      # rows of one trl_pool_add call made for a larger input
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-
-
-def _device(device) -> torch.device:
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if device.type != "cuda":
-        raise ValueError("embeddings are pooled on a GPU")
-    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _rows(x, device) -> torch.Tensor:
-    """(m, 512) float32 on `device` with unit stride along a row and rows at least 512 floats apart: a view that has that is taken
-    as it is (its row pitch is the kernel's ld_rows), anything else is made contiguous."""
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.array(x, np.float32))
-    x = torch.as_tensor(x).detach().to(device, torch.float32)
-    if x.dim() == 1:
-        x = x[None]
-    if x.dim() != 2 or x.shape[1] != DIM:
-        raise ValueError(f"expected (m, {DIM}) embeddings, got {tuple(x.shape)}")
-    if x.shape[0] <= 1 or x.stride(1) != 1 or x.stride(0) < DIM:
-        x = x.contiguous()
-    return x
-
-
-def _vector(v, m: int, dtype, device, name: str):
-    if v is None:
-        return None
-    if isinstance(v, np.ndarray):
-        v = torch.from_numpy(np.array(v))
-    v = torch.as_tensor(v).detach().to(device, dtype).reshape(-1).contiguous()
-    if v.shape[0] != m:
-        raise ValueError(f"{name} must have {m} entries, not {v.shape[0]}")
-    return v
 
 
 def _tile(tile_rows) -> int:
@@ -90,61 +46,68 @@ def _tile(tile_rows) -> int:
     return int(tile_rows)
 
 
+def _block(a: int, x, n2, gid, w) -> tuple:
+    """Rows a .. a + b - 1 as trl_pool_add and trl_pool_rep_add take them: (rows, ld_rows, n2, gid, w, b).  `x` (b, 512) and `n2`
+    (b,) or None are the block's own; `gid` and `w` (or None) cover every row and are cut here."""
+    b = x.shape[0]
+    return ptr(x), (x.stride(0) if b > 1 else DIM), ptr(n2), ptr(gid[a:a + b]), ptr(None if w is None else w[a:a + b]), b
+
+
 class EmbeddingPool:
     """The pooled sums of groups 0 .. num_groups - 1 on the device.  ``add`` takes rows in any number of calls and in any order;
     ``result`` finishes what has been added so far and may be called again after more.  No call synchronises."""
 
     def __init__(self, num_groups: int, device=None, _g0: int = 0):
         self.lib = _lib.load()
-        self.device = _device(device)
+        self.device = cuda_device(device, "embeddings are pooled on a GPU")
         self._g0 = int(_g0)
         self._rows_added = 0
-        self._alloc(int(num_groups))
+        self.num_groups = int(num_groups)
+        self._state = torch.zeros((self._words(self.num_groups),), dtype=torch.int64, device=self.device)
 
-    def _alloc(self, groups: int):
+    def _words(self, groups: int) -> int:
+        """The int64 words of a state of `groups` groups (csrc/trl_pool.h): skipped, W[G], N[G], A[G][512]."""
         nbytes = self.lib.trl_pool_state_bytes(groups)
         if groups < 0 or not nbytes:
             raise ValueError(f"num_groups must be in 0 .. 2**31 - 1, not {groups}")
-        self.num_groups = groups
-        self._state = torch.zeros((nbytes // 8,), dtype=torch.int64, device=self.device)
+        return nbytes // 8
 
     def reset(self) -> None:
         """Forget every row."""
-        _lib.check(self.lib.trl_pool_reset(_ptr(self._state), self.num_groups, _stream(self.device)))
+        _lib.check(self.lib.trl_pool_reset(ptr(self._state), self.num_groups, stream(self.device)))
         self._rows_added = 0
 
     def grow(self, num_groups: int) -> None:
         """Make room for groups up to ``num_groups - 1``: a device copy of the sums; the new groups are empty."""
-        old, g = self._state, self.num_groups
-        if int(num_groups) < g:
-            raise ValueError(f"a pool of {g} groups cannot shrink to {int(num_groups)}")
-        if int(num_groups) == g:
+        g, n = self.num_groups, int(num_groups)
+        if n < g:
+            raise ValueError(f"a pool of {g} groups cannot shrink to {n}")
+        if n == g:
             return
-        self._alloc(int(num_groups))
-        n = self.num_groups                               # layout (csrc/trl_pool.h): skipped, W[G], N[G], A[G][512]
-        self._state[0:1].copy_(old[0:1])
-        self._state[1:1 + g].copy_(old[1:1 + g])
-        self._state[1 + n:1 + n + g].copy_(old[1 + g:1 + 2 * g])
-        self._state[1 + 2 * n:1 + 2 * n + DIM * g].copy_(old[1 + 2 * g:])
+        self._words(n)
+        st = self._state                                  # each section grows on its own
+        self._state = torch.cat([st[:1], grown(st[1:1 + g], n), grown(st[1 + g:1 + 2 * g], n), grown(st[1 + 2 * g:], DIM * n)])
+        self.num_groups = n
 
     def add(self, emb, groups, weights=None, n2=None, tile_rows: int = 0) -> None:
         """Pool m more rows: ``emb`` (m, 512), ``groups`` (m,) integer ids, ``weights`` (m,) in (0, 1] or None (all 1), ``n2`` (m,)
         the rows' squared norms as ``FaceGallery`` keeps them, or None (they are computed).  A row whose id is outside the pool
         is ignored; a row with a bad weight or norm is skipped and counted in ``result()["skipped"]``."""
-        x = _rows(emb, self.device)
+        x = rows(emb, self.device, keep_pitch=True)
         m = x.shape[0]
-        gid = _vector(groups, m, torch.int32, self.device, "groups")
-        w = _vector(weights, m, torch.float32, self.device, "weights")
-        n2 = _vector(n2, m, torch.float32, self.device, "n2")
+        gid = vector(groups, m, torch.int32, self.device, "groups")
+        w = vector(weights, m, torch.float32, self.device, "weights")
+        n2 = vector(n2, m, torch.float32, self.device, "n2")
         if self._rows_added + m > MAX_ROWS:
             raise ValueError(f"an EmbeddingPool takes at most 2**30 rows: {self._rows_added} added, {m} more")
         self._rows_added += m
-        tile, ld, s = _tile(tile_rows), (x.stride(0) if m > 1 else DIM), _stream(self.device)
+        tile, s = _tile(tile_rows), stream(self.device)
         for a in range(0, m, ROW_CHUNK):
-            b = min(a + ROW_CHUNK, m)
-            _lib.check(self.lib.trl_pool_add(_ptr(self._state), self.num_groups, self._g0, _ptr(x[a:b]), ld,
-                                             _ptr(None if n2 is None else n2[a:b]), _ptr(gid[a:b]), _ptr(None if w is None else w[a:b]),
-                                             b - a, tile, s))
+            self._add_block(a, x[a:a + ROW_CHUNK], None if n2 is None else n2[a:a + ROW_CHUNK], gid, w, tile, s)
+
+    def _add_block(self, a: int, x, n2, gid, w, tile: int, s) -> None:
+        """The one trl_pool_add call: the block of rows `x` that starts at row `a` of `gid` and `w` (_block)."""
+        _lib.check(self.lib.trl_pool_add(ptr(self._state), self.num_groups, self._g0, *_block(a, x, n2, gid, w), tile, s))
 
     def result(self, unit: bool = True) -> dict:
         """``template`` (G, 512) float32 -- unit rows, or with ``unit=False`` the weighted mean of the unit rows --, ``count`` (G,)
@@ -154,24 +117,23 @@ class EmbeddingPool:
         out = {"template": torch.empty((g, DIM), dtype=torch.float32, device=d), "count": torch.empty((g,), dtype=torch.int32, device=d),
                "weight": torch.empty((g,), dtype=torch.float32, device=d), "cohesion": torch.empty((g,), dtype=torch.float32, device=d)}
         skipped = torch.empty((1,), dtype=torch.int64, device=d)
-        _lib.check(self.lib.trl_pool_finish(_ptr(self._state), g, 0 if unit else 1, _ptr(out["template"]), _ptr(out["count"]),
-                                            _ptr(out["weight"]), _ptr(out["cohesion"]), _ptr(skipped), _stream(d)))
+        _lib.check(self.lib.trl_pool_finish(ptr(self._state), g, 0 if unit else 1, ptr(out["template"]), ptr(out["count"]),
+                                            ptr(out["weight"]), ptr(out["cohesion"]), ptr(skipped), stream(d)))
         out["skipped"] = skipped[0]
         return out
 
     def _representatives(self, template, blocks, gid, w, tile_rows: int = 0):
         """(index (G,) int32, score (G,) float32) of the rows that `blocks` yields -- (first row, rows, n2 or None) -- against
         `template`, this pool's result."""
-        g, d, s = self.num_groups, self.device, _stream(self.device)
+        g, d, s = self.num_groups, self.device, stream(self.device)
         key = torch.empty((max(g, 1),), dtype=torch.int64, device=d)
         index = torch.empty((g,), dtype=torch.int32, device=d)
         score = torch.empty((g,), dtype=torch.float32, device=d)
-        _lib.check(self.lib.trl_pool_rep_reset(_ptr(key), g, s))
+        _lib.check(self.lib.trl_pool_rep_reset(ptr(key), g, s))
         for a, x, n2 in blocks():
-            m = x.shape[0]
-            _lib.check(self.lib.trl_pool_rep_add(_ptr(key), g, self._g0, _ptr(template), _ptr(x), x.stride(0) if m > 1 else DIM, _ptr(n2),
-                                                 _ptr(gid[a:a + m]), _ptr(None if w is None else w[a:a + m]), a, m, _tile(tile_rows), s))
-        _lib.check(self.lib.trl_pool_rep_finish(_ptr(key), g, _ptr(index), _ptr(score), s))
+            *block, m = _block(a, x, n2, gid, w)
+            _lib.check(self.lib.trl_pool_rep_add(ptr(key), g, self._g0, ptr(template), *block, a, m, _tile(tile_rows), s))
+        _lib.check(self.lib.trl_pool_rep_finish(ptr(key), g, ptr(index), ptr(score), s))
         return index, score
 
 
@@ -179,7 +141,6 @@ def _pool_blocks(device, blocks, m: int, gid, w, G: int, unit: bool, representat
     """The one-shot pool over rows that `blocks()` yields as (first row, rows (b, 512), n2 or None), in chunks of groups that fit
     `max_state_bytes`: a chunk's pool covers groups g0 .. g0 + c - 1 and ignores the rows of the others, so the bits are those of
     one pool over all."""
-    lib = _lib.load()
     per = max(1, (int(max_state_bytes) - 8) // (514 * 8))
     if m > MAX_ROWS:
         raise ValueError(f"at most 2**30 rows are pooled, not {m}")
@@ -189,14 +150,12 @@ def _pool_blocks(device, blocks, m: int, gid, w, G: int, unit: bool, representat
     if representative:
         out["representative"] = torch.empty((G,), dtype=torch.int32, device=device)
         out["rep_score"] = torch.empty((G,), dtype=torch.float32, device=device)
-    s = _stream(device)
+    s = stream(device)
     for g0 in range(0, G, per):
         c = min(per, G - g0)
         p = EmbeddingPool(c, device, _g0=g0)
         for a, x, n2 in blocks():
-            b = x.shape[0]
-            _lib.check(lib.trl_pool_add(_ptr(p._state), c, g0, _ptr(x), x.stride(0) if b > 1 else DIM, _ptr(n2), _ptr(gid[a:a + b]),
-                                        _ptr(None if w is None else w[a:a + b]), b, _tile(tile_rows), s))
+            p._add_block(a, x, n2, gid, w, _tile(tile_rows), s)
         r = p.result(unit)
         for name in ("template", "count", "weight", "cohesion"):
             out[name][g0:g0 + c].copy_(r[name])
@@ -218,11 +177,11 @@ def pool_embeddings(emb, groups, num_groups: int | None = None, weights=None, un
     ``FaceGallery.scores(template)``'s bits."""
     if device is None:
         device = emb.device if isinstance(emb, torch.Tensor) and emb.device.type == "cuda" else None
-    device = _device(device)
-    x = _rows(emb, device)
+    device = cuda_device(device, "embeddings are pooled on a GPU")
+    x = rows(emb, device, keep_pitch=True)
     m = x.shape[0]
-    gid = _vector(groups, m, torch.int32, device, "groups")
-    w = _vector(weights, m, torch.float32, device, "weights")
+    gid = vector(groups, m, torch.int32, device, "groups")
+    w = vector(weights, m, torch.float32, device, "weights")
     if num_groups is None:
         num_groups = max(int(gid.max().item()) + 1, 0) if m else 0
     G = int(num_groups)

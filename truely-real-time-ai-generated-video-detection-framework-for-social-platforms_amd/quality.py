@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pool import _device, _ptr, _stream, _vector
+from ._tensors import cuda_device, grown, ptr, stream, table, vector
 
 FEATURES = ("quality", "sharpness", "mean_luma", "dark_frac", "bright_frac", "contrast", "yaw", "pitch", "roll", "iod", "p05", "p95")
 RAW = ("n", "sum_y", "sum_y2", "sum_l", "sum_l2", "n_dark", "n_bright", "width")
@@ -75,7 +75,7 @@ def face_quality(frames, frame_of, boxes, points=None, params: QualityParams | N
     lib = _lib.load()
     if device is None:
         device = frames.device if isinstance(frames, torch.Tensor) and frames.device.type == "cuda" else None
-    device = _device(device)
+    device = cuda_device(device, "embeddings are pooled on a GPU")
     if isinstance(frames, np.ndarray):
         frames = torch.from_numpy(np.ascontiguousarray(frames))
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
@@ -86,15 +86,11 @@ def face_quality(frames, frame_of, boxes, points=None, params: QualityParams | N
         raise ValueError(f"frames of {H} x {W}: H and W must be in 1 .. {MAX_DIM}")
     if int(max_band_rows) < 0:
         raise ValueError("max_band_rows must be 0 (the library's choice) or positive")
-    if isinstance(boxes, np.ndarray):
-        boxes = torch.from_numpy(np.array(boxes, np.float32))
-    boxes = torch.as_tensor(boxes).detach().to(device, torch.float32).reshape(-1, 4).contiguous()
+    boxes = table(boxes, 4, device, "boxes")
     m = boxes.shape[0]
-    frame_of = _vector(frame_of, m, torch.int32, device, "frame_of")
+    frame_of = vector(frame_of, m, torch.int32, device, "frame_of")
     if points is not None:
-        if isinstance(points, np.ndarray):
-            points = torch.from_numpy(np.array(points, np.float32))
-        points = torch.as_tensor(points).detach().to(device, torch.float32).reshape(-1, 10).contiguous()
+        points = table(points, 10, device, "points")
         if points.shape[0] != m:
             raise ValueError(f"points must have {m} rows, not {points.shape[0]}")
     params = params or QualityParams()
@@ -107,9 +103,9 @@ def face_quality(frames, frame_of, boxes, points=None, params: QualityParams | N
     feat = torch.empty((m, 12), dtype=torch.float32, device=device)
     status = torch.empty((m,), dtype=torch.int32, device=device)
     hist = torch.empty((m, 256), dtype=torch.int32, device=device) if return_hist else None
-    _lib.check(lib.trl_face_quality(_ptr(fr), n, H, W, _ptr(frame_of), _ptr(boxes), _ptr(points), m, C.byref(prm), int(max_band_rows),
-                                    _ptr(ws), ws.numel() * ws.element_size(), _ptr(raw), _ptr(feat), _ptr(hist), _ptr(status),
-                                    _stream(device)))
+    _lib.check(lib.trl_face_quality(ptr(fr), n, H, W, ptr(frame_of), ptr(boxes), ptr(points), m, C.byref(prm), int(max_band_rows),
+                                    ptr(ws), ws.numel() * ws.element_size(), ptr(raw), ptr(feat), ptr(hist), ptr(status),
+                                    stream(device)))
     out = {name: feat[:, i] for i, name in enumerate(FEATURES[:10])}
     out.update(feat=feat, raw=raw, status=status)
     if return_hist:
@@ -124,7 +120,7 @@ class BestShots:
 
     def __init__(self, num_groups: int, device=None, face_shape=None):
         self.lib = _lib.load()
-        self.device = _device(device)
+        self.device = cuda_device(device, "embeddings are pooled on a GPU")
         if not (0 <= int(num_groups) <= 2 ** 31 - 1):
             raise ValueError(f"num_groups must be in 0 .. 2**31 - 1, not {num_groups}")
         self.num_groups = int(num_groups)
@@ -150,20 +146,17 @@ class BestShots:
             raise ValueError(f"{g} groups cannot shrink to {int(num_groups)}")
         if int(num_groups) == g:
             return
-        keys, faces = self._keys, self._faces
         self.num_groups = int(num_groups)
-        self._keys = torch.zeros((self.num_groups,), dtype=torch.int64, device=self.device)
-        self._keys[:g].copy_(keys[:g])
-        if faces is not None:
-            self._alloc_faces()
-            self._faces[:g].copy_(faces[:g])
+        self._keys = grown(self._keys[:g], self.num_groups)
+        if self._faces is not None:
+            self._faces = grown(self._faces[:g], self.num_groups)
 
     def add(self, quality, gid, faces=None) -> None:
         """m more rows: ``quality`` (m,) float32, ``gid`` (m,) integer group ids (outside 0 .. num_groups - 1: ignored), ``faces``
         (m, *face_shape) float32 or None.  The first call's faces give ``face_shape`` when the constructor did not."""
         q = torch.as_tensor(quality).detach().to(self.device, torch.float32).reshape(-1).contiguous()
         m = q.shape[0]
-        gid = _vector(gid, m, torch.int32, self.device, "gid")
+        gid = vector(gid, m, torch.int32, self.device, "gid")
         if self.rows_seen + m > 2 ** 31 - 1:
             raise ValueError("BestShots takes at most 2**31 - 1 rows")
         floats = 0
@@ -177,9 +170,9 @@ class BestShots:
             floats = int(np.prod(self.face_shape))
         elif self._faces is not None and m:
             raise ValueError("these BestShots keep faces: every add needs them")
-        _lib.check(self.lib.trl_best_update(_ptr(self._keys), self.num_groups, _ptr(q), _ptr(gid), m, self.rows_seen,
-                                            _ptr(faces if floats else None), floats, _ptr(self._faces if floats and m else None),
-                                            _stream(self.device)))
+        _lib.check(self.lib.trl_best_update(ptr(self._keys), self.num_groups, ptr(q), ptr(gid), m, self.rows_seen,
+                                            ptr(faces if floats else None), floats, ptr(self._faces if floats and m else None),
+                                            stream(self.device)))
         self.rows_seen += m
 
     def read(self) -> dict:
@@ -188,7 +181,7 @@ class BestShots:
         g, d = self.num_groups, self.device
         row = torch.empty((g,), dtype=torch.int32, device=d)
         quality = torch.empty((g,), dtype=torch.float32, device=d)
-        _lib.check(self.lib.trl_best_read(_ptr(self._keys), g, _ptr(row), _ptr(quality), _stream(d)))
+        _lib.check(self.lib.trl_best_read(ptr(self._keys), g, ptr(row), ptr(quality), stream(d)))
         out = {"row": row, "quality": quality}
         if self._faces is not None:
             out["face"] = self._faces[:g]

@@ -45,21 +45,16 @@ The defaults of ``iou_min``, ``sim_min`` and ``max_age`` are PLACEHOLDERS, not c
 measured.  ``FaceGallery.calibrate`` on labelled embeddings of the checkpoint in use is the way to a ``sim_min``."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._tensors import cuda_device, grown, ptr, stream, table
 
 SLOTS = 64
 STATE_BYTES = 135200
 INT32_MAX = 2 ** 31 - 1
 TABLE_COLUMNS = ("first_frame", "last_frame", "n_obs", "run", "hits", "slot")
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
 
 
 class FaceTracker:
@@ -74,11 +69,7 @@ class FaceTracker:
             raise ValueError("iou_min / sim_min must not be NaN")
         self.iou_min, self.sim_min, self.max_age = float(iou_min), float(sim_min), int(max_age)
         self.lib = _lib.load()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("a FaceTracker lives on a GPU")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = cuda_device(device, "a FaceTracker lives on a GPU")
         self._state = torch.zeros((STATE_BYTES // 8,), dtype=torch.int64, device=self.device)
         self._table = torch.zeros((256, 8), dtype=torch.int32, device=self.device)
         self._id_bound = 0                                # next_id <= this: a row starts at most one track
@@ -101,9 +92,6 @@ class FaceTracker:
         if self._best is not None:
             self._best.reset()
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def update(self, boxes, counts, emb=None, weights=None, quality=None, faces=None) -> dict:
         """The clip's next window: ``boxes`` (m, 4), ``counts`` (n,), ``emb`` (m, 512) or None (every window of a clip alike).
         -> ``track`` (m,) int32, ``sim`` (m,) float32, ``flag`` (m,) uint8 on the device.  A tracker made with ``templates=True``
@@ -120,7 +108,7 @@ class FaceTracker:
         if self._pool is not None and emb is None:
             raise ValueError("a tracker with templates=True needs the embeddings of every window")
         d = self.device
-        boxes = torch.as_tensor(boxes).to(d, torch.float32).reshape(-1, 4).contiguous()
+        boxes = table(boxes, 4, d, "boxes")
         counts = torch.as_tensor(counts).to(d, torch.int32).reshape(-1).contiguous()
         m, n = boxes.shape[0], counts.shape[0]
         if emb is not None:
@@ -128,17 +116,15 @@ class FaceTracker:
             if tuple(emb.shape) != (m, 512):
                 raise ValueError(f"expected ({m}, 512) embeddings, got {tuple(emb.shape)}")
         if self._id_bound + m > self._table.shape[0]:    # grow geometrically; the copy stays on the device
-            old = self._table
-            self._table = torch.zeros((max(2 * old.shape[0], self._id_bound + m), 8), dtype=torch.int32, device=d)
-            self._table[:old.shape[0]].copy_(old)
+            self._table = grown(self._table, max(2 * self._table.shape[0], self._id_bound + m))
         self._id_bound += m
         track = torch.empty((m,), dtype=torch.int32, device=d)
         sim = torch.empty((m,), dtype=torch.float32, device=d)
         flag = torch.empty((m,), dtype=torch.uint8, device=d)
-        _lib.check(self.lib.trl_track_update(_ptr(self._state), _ptr(boxes), _ptr(counts), n, m,
-                                             _ptr(emb), self.iou_min, self.sim_min,
-                                             self.max_age, _ptr(track), _ptr(sim), _ptr(flag), _ptr(self._table), self._table.shape[0],
-                                             self._stream()))
+        _lib.check(self.lib.trl_track_update(ptr(self._state), ptr(boxes), ptr(counts), n, m,
+                                             ptr(emb), self.iou_min, self.sim_min,
+                                             self.max_age, ptr(track), ptr(sim), ptr(flag), ptr(self._table), self._table.shape[0],
+                                             stream(self.device)))
         if self._pool is not None:
             if self._pool.num_groups < self._table.shape[0]:
                 self._pool.grow(self._table.shape[0])
@@ -159,7 +145,7 @@ class FaceTracker:
         cap = self._table.shape[0]
         score = torch.empty((cap,), dtype=torch.int32, device=self.device)
         summary = torch.empty((4,), dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.trl_track_scores(_ptr(self._state), _ptr(self._table), cap, 1, 1, _ptr(score), _ptr(summary), self._stream()))
+        _lib.check(self.lib.trl_track_scores(ptr(self._state), ptr(self._table), cap, 1, 1, ptr(score), ptr(summary), stream(self.device)))
         return int(summary[2].item())
 
     def templates(self, unit: bool = True) -> dict:
@@ -196,8 +182,8 @@ class FaceTracker:
         cap, k = self._table.shape[0], self._id_bound
         score = torch.empty((cap,), dtype=torch.int32, device=self.device)
         summary = torch.empty((4,), dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.trl_track_scores(_ptr(self._state), _ptr(self._table), cap, int(frame_count), int(fps), _ptr(score),
-                                             _ptr(summary), self._stream()))
+        _lib.check(self.lib.trl_track_scores(ptr(self._state), ptr(self._table), cap, int(frame_count), int(fps), ptr(score),
+                                             ptr(summary), stream(self.device)))
         return torch.cat([summary, self._table[:k].reshape(-1), score[:k]]).cpu().numpy()
 
     def tracks(self, frame_count: int, fps: int) -> dict:

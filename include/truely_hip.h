@@ -833,6 +833,61 @@ int    trl_best_update(unsigned long long* d_keys, long long groups, const float
                        long long row_base, const float* d_faces, long long face_floats, float* d_best_faces, void* stream);
 int    trl_best_read(const unsigned long long* d_keys, long long groups, int32_t* d_row, float* d_quality, void* stream);
 
+/* ---- Shots ("where does the scene change": frame signatures, their distance, cut flags and shot ids) ---------------------------------
+ * Context-free, caller-owned memory, work queued on `stream`, no synchronisation, the device that of d_ws / d_dist / d_state.
+ * (ABI v7, additive.)  The rule is DESIGN.md section 2, "Shots" (csrc/trl_shots.h is its code): every quantity is an integer count
+ * or one double division, so a result is the same bits for any max_band_rows, any stream, any split of a clip into windows and
+ * whatever the workspace held before.
+ *   signature  of a frame u8 [H][W][3], channels as stored, 4 <= H, W <= 16384: sig [16][3][32] int32.  Region r = 4 i + j covers
+ *              rows H i / 4 .. H (i + 1) / 4 - 1 and columns W j / 4 .. W (j + 1) / 4 - 1 (integer division), N_r pixels;
+ *              sig[r][c][v >> 3] += 1 for every pixel of the region and every channel c
+ *   distance   of two signatures of one H x W: per region d_r = sum_c sum_{k = 0 .. 30} |Ca[c][k] - Cb[c][k]| over the cumulative
+ *              counts C[c][k] = sum_{b <= k} sig[r][c][b] (int64; the 1-D earth mover's distance in bins); the regions in the order
+ *              (d_r ascending, r ascending), the first 16 - drop kept; dist = (float)((double)(sum of the kept d_r) / (double)(sum
+ *              of the kept 93 N_r)), in [0, 1]
+ *   cuts       dist[t] of a clip's first frame is 2.0 ("no comparison"); cut[t] = dist[t] != 2.0 && dist[t] >= threshold &&
+ *              t - last_cut >= min_shot, last_cut the clip's frame index of the last cut, -min_shot before the first;
+ *              shot[t] = the number of cuts at frames <= t
+ * NOT detected: dissolves and fades (no pair of consecutive frames is far apart); a flash gives a cut at its first frame and is
+ * only kept from giving a second one by min_shot.
+ * The defaults of the parameters (params = NULL: the values beside the struct's fields) are PLACEHOLDERS, not calibrated figures.
+ *   d_frames      [n][H][W][3] u8 at ANY byte address.  The signature kernel reads 16-byte words at 16-byte-aligned addresses: up
+ *                 to 15 bytes in front of d_frames and up to 15 bytes past its last byte are loaded -- they lie in the aligned
+ *                 words that hold the first and the last byte, so in the pages the frames lie in -- and are masked out: nothing
+ *                 outside the n H W 3 bytes reaches a result
+ *   d_ws          trl_shots_workspace(n, H, W, max_band_rows) bytes, 8-byte aligned; its contents before the call do not matter
+ *   max_band_rows rows of a row of regions that one workgroup takes at a time: 0 = the library's choice; any value >= 1 gives the
+ *                 same bits (a test knob)
+ *   d_sig         [n][16][3][32] int32
+ *   d_a, d_b      [pairs][16][3][32] int32: row i of a against row i of b -> d_dist [pairs] f32
+ *   d_state       TRL_SHOTS_STATE_BYTES, 8-byte aligned, zero-filled before a clip's first window; the layout is private: the last
+ *                 signature, the frames seen, the last cut and the cuts so far.  One clip has one H x W.
+ *   update        the clip's next n frames by their signatures d_sig -> d_dist [n] f32, d_cut [n] u8, d_shot [n] int32.  n = 0 is
+ *                 legal and does nothing.  Windows of any sizes give the bits of one call over the clip.
+ * TRL_ERR_INVALID with nothing queued: a null pointer where one is needed, n < 0 (pairs < 0), n > 65535 for trl_frame_signatures,
+ * H or W outside 4 .. 16384, drop outside 0 .. 15, a threshold that is not finite, min_shot < 1, max_band_rows < 0, a workspace too
+ * small or not 8-byte aligned, a state not 8-byte aligned. */
+typedef struct {
+    float threshold;        /* 0.12  dist at and above which a frame starts a shot */
+    int   drop;             /* 4     most-changed regions left out of the distance, 0 .. 15 */
+    int   min_shot;         /* 1     frames a shot lasts at least: a cut closer than this to the last one is not a cut */
+} trl_shots_params;
+#define TRL_SHOTS_STATE_BYTES 6176
+size_t trl_shots_workspace(int n, int H, int W, int max_band_rows);              /* 0 on bad arguments */
+int    trl_frame_signatures(const uint8_t* d_frames, int n, int H, int W, int max_band_rows, void* d_ws, size_t ws_bytes,
+                            int32_t* d_sig, void* stream);
+int    trl_signature_distance(const int32_t* d_a, const int32_t* d_b, long long pairs, int H, int W, int drop, float* d_dist,
+                              void* stream);
+int    trl_shots_update(void* d_state, const int32_t* d_sig, int n, int H, int W, const trl_shots_params* params, float* d_dist,
+                        uint8_t* d_cut, int32_t* d_shot, void* stream);
+/* trl_track_update with the window's cut flags d_cut [n] u8 (trl_shots_update's), or NULL for none -- which IS trl_track_update.
+ * At a frame with d_cut[t] != 0, BEFORE ageing and pairing, every live track ends exactly as an aged-out track ends: its slot is
+ * free and its table row gets slot -1.  The frame's detections then all start tracks under the "new" rule.  Ids, frame numbers,
+ * the dropped count and the table carry on.  A cut at a clip's first frame ends nothing. */
+int    trl_track_update_cuts(void* d_state, const float* d_boxes, const int32_t* d_counts, const uint8_t* d_cut, int n, int m,
+                             const float* d_emb, float iou_min, float sim_min, int max_age, int32_t* d_track, float* d_sim,
+                             uint8_t* d_flag, int32_t* d_table, int table_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,10 @@ class TrlQualityParams(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("sharp_ref", "clip_ref", "contrast_ref", "yaw_ref", "pitch_ref", "size_ref")]
 
 
+class TrlShotsParams(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("drop", C.c_int), ("min_shot", C.c_int)]
+
+
 class TrlRzHit(C.Structure):
     _fields_ = [("arena", C.c_int32), ("block", C.c_int32), ("site", C.c_char * 24)] + \
                [(n, C.c_longlong) for n in ("block_bytes", "gap_off", "gap_bytes", "first", "last", "count")]
@@ -153,6 +157,11 @@ _SIGNATURES = {
                                    _vp, _vp, _vp]),
     "trl_best_update": (C.c_int, [_vp, C.c_longlong, _vp, _vp, C.c_longlong, C.c_longlong, _vp, C.c_longlong, _vp, _vp]),
     "trl_best_read": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp]),
+    "trl_shots_workspace": (C.c_size_t, [_i, _i, _i, _i]),
+    "trl_frame_signatures": (C.c_int, [_vp, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp]),
+    "trl_signature_distance": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _i, _vp, _vp]),
+    "trl_shots_update": (C.c_int, [_vp, _vp, _i, _i, _i, C.POINTER(TrlShotsParams), _vp, _vp, _vp, _vp]),
+    "trl_track_update_cuts": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1,5 +1,5 @@
 // trl_host.h -- what the host entry points of the context-free files share (trl_gallery.hip, trl_cluster.hip, trl_tracks.hip,
-// trl_pool.hip, trl_quality.hip; trl_annotate.hip for the device lookup): how an entry refuses, which device it runs on, what it asks
+// trl_pool.hip, trl_quality.hip, trl_shots.hip; trl_annotate.hip for the device lookup): how an entry refuses, which device it runs on, what it asks
 // of a caller's workspace and of per-group state, and how a kernel with a large LDS frame is launched.
 #pragma once
 #include <string.h>

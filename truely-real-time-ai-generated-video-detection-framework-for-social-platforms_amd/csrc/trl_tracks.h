@@ -3,6 +3,7 @@
 // pair's similarity is an input (the kernel computes it with trl_wave_dot512, the host program reads it from a table).
 //
 // Per frame f, in this order (the caller composes them; each step's rule is the function's):
+//   trl_tk_cut         at a frame flagged as a shot boundary, every track ends and frees its slot
 //   trl_tk_age         a track with f - last_frame - 1 > max_age ends and frees its slot
 //   trl_tk_pair_key    the key of a (live track, detection) pair, NaN when the pair is not admissible
 //   trl_tk_greedy      repeat: match the admissible pair of an unmatched track and an unmatched detection with the largest key;
@@ -85,6 +86,13 @@ TRL_HD void trl_tk_row(const TrlTkSlot& s, int slot, int32_t* table, int table_c
 // Ageing of one slot at frame f: a track that is not live ends.
 TRL_HD void trl_tk_age(TrlTkSlot& s, long long f, int32_t max_age, int32_t* table, int table_cap) {
     if (!s.used || trl_tk_live(f, s.last_frame, max_age)) return;
+    trl_tk_row(s, -1, table, table_cap);
+    s.used = 0;
+}
+
+// A cut at this frame (trl_track_update_cuts), before ageing and pairing: a track ends exactly as an aged-out track ends.
+TRL_HD void trl_tk_cut(TrlTkSlot& s, int32_t* table, int table_cap) {
+    if (!s.used) return;
     trl_tk_row(s, -1, table, table_cap);
     s.used = 0;
 }

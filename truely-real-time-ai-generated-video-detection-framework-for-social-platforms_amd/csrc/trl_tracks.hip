@@ -1,5 +1,6 @@
 // trl_tracks.hip -- the face tracker: which face of sampled frame t is which face of frame t - 1, with model.py's drift state
-// machine per person.  trl_track_update, trl_track_scores; context-free like the gallery.
+// machine per person.  trl_track_update_cuts (trl_track_update is it without cut flags),
+// trl_track_scores; context-free like the gallery.
 //
 // The decisions are trl_tracks.h's (shared with tests/tracks_main.cpp); this file adds the arithmetic on embeddings
 // (trl_wave_dot512, drift_sims_kernel's expression), the schedule and the hand-over between windows.  Refusals and the device
@@ -47,8 +48,8 @@ __device__ __forceinline__ void tk_wave_sync() {
 //                       (64 x 2 KB, L2-resident), and a track matched in this window reads its embedding from the window's own
 //                       row (TrlTkSlot::src) -- the state's copy is written once, at the end of the call
 // No pointer is __restrict__: state, table and outputs are read and written by different lanes across barriers.
-__global__ __launch_bounds__(TK_THREADS) void k_track_update(char* state, const float* boxes, const int32_t* counts, int n, int m,
-                                                              const float* emb, float iou_min, float sim_min, int max_age,
+__global__ __launch_bounds__(TK_THREADS) void k_track_update(char* state, const float* boxes, const int32_t* counts, const uint8_t* cuts, int n,
+                                                              int m,                                                              const float* emb, float iou_min, float sim_min, int max_age,
                                                               int32_t* track, float* sim_out, uint8_t* flag_out, int32_t* table,
                                                               int table_cap) {
     __shared__ float key[TRL_TK_SLOTS * TRL_TK_SLOTS];
@@ -87,9 +88,11 @@ __global__ __launch_bounds__(TK_THREADS) void k_track_update(char* state, const 
             sim_out[off + d] = TRL_TK_NO_SIM;
             flag_out[off + d] = 0;
         }
-        // 1. ageing.  Wave 0 alone owns the slots between the last barrier of a frame and the first of the next: no barrier there.
+        // 1. a cut ends every track; ageing.  Wave 0 alone owns the slots between the last barrier of a frame and the first of the
+        // next: no barrier there.
         if (wave == 0) {
             if (lane == 0) head.dropped += c - nd;
+            if (cuts && cuts[t]) trl_tk_cut(slots[lane], table, table_cap);
             trl_tk_age(slots[lane], f, max_age, table, table_cap);
             slot_id[lane] = slots[lane].used ? slots[lane].id : -1;
             for (int i = lane; i < nd * 4; i += 64) dbox[i] = boxes[(size_t)off * 4 + i];
@@ -239,22 +242,40 @@ __global__ __launch_bounds__(256) void k_track_scores(const char* state, const i
 
 }  // namespace
 
+namespace {
+// both entries; `who` is the one that was called
+int tk_update(const char* who, void* d_state, const float* d_boxes, const int32_t* d_counts, const uint8_t* d_cut, int n, int m,
+              const float* d_emb, float iou_min, float sim_min, int max_age, int32_t* d_track, float* d_sim, uint8_t* d_flag, int32_t* d_table,
+              int table_cap, void* stream) {
+    if (n < 0 || m < 0 || max_age < 0 || table_cap < 0) {
+        trl_set_error("%s: n = %d, m = %d, max_age = %d, table_cap = %d", who, n, m, max_age, table_cap);
+        return TRL_ERR_INVALID;
+    }
+    if (iou_min != iou_min || sim_min != sim_min) return trl_refuse(who, "a NaN threshold");
+    if (!d_state || ((uintptr_t)d_state & 7)) return trl_refuse(who, "the state is null or not 8-byte aligned");
+    if ((n > 0 && !d_counts) || (m > 0 && (!d_boxes || !d_track || !d_sim || !d_flag)) || (table_cap > 0 && !d_table))
+        return trl_refuse(who, "null argument");
+    TRL_CHECK(trl_device_of(d_state));
+    k_track_update<<<1, TK_THREADS, 0, (hipStream_t)stream>>>((char*)d_state, d_boxes, d_counts, d_cut, n, m, d_emb, iou_min, sim_min, max_age,
+                                                             d_track, d_sim, d_flag, d_table, table_cap);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+}
+}  // namespace
+
+extern "C" int trl_track_update_cuts(void* d_state, const float* d_boxes, const int32_t* d_counts, const uint8_t* d_cut, int n, int m,
+                                     const float* d_emb, float iou_min, float sim_min, int max_age, int32_t* d_track, float* d_sim,
+                                     uint8_t* d_flag, int32_t* d_table, int table_cap, void* stream) {
+    return tk_update("trl_track_update_cuts", d_state, d_boxes, d_counts, d_cut, n, m, d_emb, iou_min, sim_min, max_age, d_track, d_sim, d_flag,
+                     d_table, table_cap, stream);
+}
+
+// no cut flags: the same call
 extern "C" int trl_track_update(void* d_state, const float* d_boxes, const int32_t* d_counts, int n, int m, const float* d_emb, float iou_min,
                                 float sim_min, int max_age, int32_t* d_track, float* d_sim, uint8_t* d_flag, int32_t* d_table, int table_cap,
                                 void* stream) {
-    if (n < 0 || m < 0 || max_age < 0 || table_cap < 0) {
-        trl_set_error("trl_track_update: n = %d, m = %d, max_age = %d, table_cap = %d", n, m, max_age, table_cap);
-        return TRL_ERR_INVALID;
-    }
-    if (iou_min != iou_min || sim_min != sim_min) return trl_refuse("trl_track_update", "a NaN threshold");
-    if (!d_state || ((uintptr_t)d_state & 7)) return trl_refuse("trl_track_update", "the state is null or not 8-byte aligned");
-    if ((n > 0 && !d_counts) || (m > 0 && (!d_boxes || !d_track || !d_sim || !d_flag)) || (table_cap > 0 && !d_table))
-        return trl_refuse("trl_track_update", "null argument");
-    TRL_CHECK(trl_device_of(d_state));
-    k_track_update<<<1, TK_THREADS, 0, (hipStream_t)stream>>>((char*)d_state, d_boxes, d_counts, n, m, d_emb, iou_min, sim_min, max_age, d_track,
-                                                             d_sim, d_flag, d_table, table_cap);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
+    return tk_update("trl_track_update", d_state, d_boxes, d_counts, nullptr, n, m, d_emb, iou_min, sim_min, max_age, d_track, d_sim, d_flag,
+                     d_table, table_cap, stream);
 }
 
 extern "C" int trl_track_scores(const void* d_state, const int32_t* d_table, int table_cap, long long frame_count, int fps, int32_t* d_score,

@@ -205,25 +205,35 @@ class Engine:
         from .quality import face_quality
         return face_quality(self._frames(frames), frame_of, boxes, points, params, return_hist, max_band_rows, self.device)
 
-    def track_faces(self, frames, tracker, quality: bool = False, **extract_kwargs) -> dict:
+    def track_faces(self, frames, tracker, quality: bool = False, shots=None, **extract_kwargs) -> dict:
         """Every face of a window of sampled frames, embedded and associated with the clip's tracks: ``extract_faces(frames,
         keep_all=True, **extract_kwargs)``, ``facenet_embed`` of its faces, ``tracker.update(box, counts, emb)`` (a
         :class:`~truely_amd.tracker.FaceTracker` that has seen the clip's earlier windows).  Returns the extraction's dict plus
         ``emb`` [m, 512], ``track`` [m], ``sim`` [m], ``flag`` [m].  ``quality=True``: the extraction measures every face
         (``extract_faces(quality=True)``) and its ``quality`` goes to the tracker -- as the rows' weights when it keeps templates,
-        and with the faces when it keeps best shots."""
+        and with the faces when it keeps best shots.  ``shots``: a :class:`~truely_amd.shots.ShotDetector` that has seen the
+        clip's earlier windows -- ``shots.update(frames)`` runs on the same stream, its ``cut`` goes to the tracker (every track
+        ends at a shot boundary) and ``dist``, ``cut``, ``shot`` [n] join the dict.  No synchronisation either way."""
+        cut = {}
+        if shots is not None:
+            frames = self._frames(frames)                 # (uploaded once for both)
+            cut = shots.update(frames)
+            cut.pop("sig")
         if not quality:
             out = self.extract_faces(frames, keep_all=True, **extract_kwargs)
             emb = self.facenet_embed(out["faces"].permute(0, 2, 3, 1))
             out["emb"] = emb
-            out.update(tracker.update(out["box"], out["counts"], emb))
+            out.update(tracker.update(out["box"], out["counts"], emb, cuts=cut.get("cut")))
+            out.update(cut)
             return out
         out = self.extract_faces(frames, keep_all=True, quality=True, **extract_kwargs)
         emb = self.facenet_embed(out["faces"].permute(0, 2, 3, 1))
         out["emb"] = emb
         has_best = getattr(tracker, "_best", None) is not None
         out.update(tracker.update(out["box"], out["counts"], emb, weights=out["quality"] if tracker._pool is not None else None,
-                                  quality=out["quality"] if has_best else None, faces=out["faces"] if has_best else None))
+                                  quality=out["quality"] if has_best else None, faces=out["faces"] if has_best else None,
+                                  cuts=cut.get("cut")))
+        out.update(cut)
         return out
 
     # server/model.py:59 for a batch; faces f32 (n, h, w, 3) NHWC in [0,1]

@@ -10,7 +10,8 @@
 ``FaceTracker(templates=True)`` also pools every track's embeddings into one exact template (pool.py): ``trk.templates()``, and
 ``trk.identify_tracks(gallery)`` names each track once instead of each frame.  ``FaceTracker(best_shots=True)`` keeps, per track,
 the row of the largest ``quality`` (quality.py) and its face: ``trk.best_shots()``, the thumbnail of a report or an enrolment.
-``Engine.track_faces(frames, tracker)`` is the three calls of the loop body.  ``run()`` / ``analyze_video`` do not use this: they
+``update(..., cuts=)`` takes the cut flags of a ``ShotDetector`` (shots.py) and ends every track at a shot boundary: a track is
+one person in ONE shot.  ``Engine.track_faces(frames, tracker)`` is the three calls of the loop body.  ``run()`` / ``analyze_video`` do not use this: they
 keep the reference's largest-face drift (``Engine.drift_update``), in which two people in one clip read as drift.
 
 The rules ("Tracks"; csrc/trl_tracks.h is their code, tests/track_ref.py their reference).  One update takes a
@@ -49,7 +50,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._tensors import cuda_device, grown, ptr, stream, table
+from ._tensors import cuda_device, grown, ptr, stream, table, vector
 
 SLOTS = 64
 STATE_BYTES = 135200
@@ -92,13 +93,15 @@ class FaceTracker:
         if self._best is not None:
             self._best.reset()
 
-    def update(self, boxes, counts, emb=None, weights=None, quality=None, faces=None) -> dict:
+    def update(self, boxes, counts, emb=None, weights=None, quality=None, faces=None, cuts=None) -> dict:
         """The clip's next window: ``boxes`` (m, 4), ``counts`` (n,), ``emb`` (m, 512) or None (every window of a clip alike).
         -> ``track`` (m,) int32, ``sim`` (m,) float32, ``flag`` (m,) uint8 on the device.  A tracker made with ``templates=True``
         needs ``emb`` and then pools the window's rows by the track ids just written (rows without a track are ignored), each
         weighed by ``weights`` (m,) in (0, 1] -- ``face_quality``'s ``quality``, for one -- or 1.  A tracker made with
         ``best_shots=True`` needs ``quality`` (m,) for every window and keeps, per track id, the row of the largest quality and --
-        when ``faces`` (m, 3, S, S) come with every window -- that row's face."""
+        when ``faces`` (m, 3, S, S) come with every window -- that row's face.  ``cuts`` (n,) uint8 -- ``ShotDetector.update``'s
+        ``cut`` -- ends every track at the frames it flags, before ageing and pairing, exactly as an aged-out track ends; the
+        frame's faces all start new tracks.  None: no cuts."""
         if self._best is None and (quality is not None or faces is not None):
             raise ValueError("quality and faces belong to the best shots: make the tracker with best_shots=True")
         if self._best is not None and quality is None:
@@ -115,16 +118,17 @@ class FaceTracker:
             emb = torch.as_tensor(emb).to(d, torch.float32).contiguous()
             if tuple(emb.shape) != (m, 512):
                 raise ValueError(f"expected ({m}, 512) embeddings, got {tuple(emb.shape)}")
+        cuts = vector(cuts, n, torch.uint8, d, "cuts")
         if self._id_bound + m > self._table.shape[0]:    # grow geometrically; the copy stays on the device
             self._table = grown(self._table, max(2 * self._table.shape[0], self._id_bound + m))
         self._id_bound += m
         track = torch.empty((m,), dtype=torch.int32, device=d)
         sim = torch.empty((m,), dtype=torch.float32, device=d)
         flag = torch.empty((m,), dtype=torch.uint8, device=d)
-        _lib.check(self.lib.trl_track_update(ptr(self._state), ptr(boxes), ptr(counts), n, m,
-                                             ptr(emb), self.iou_min, self.sim_min,
-                                             self.max_age, ptr(track), ptr(sim), ptr(flag), ptr(self._table), self._table.shape[0],
-                                             stream(self.device)))
+        _lib.check(self.lib.trl_track_update_cuts(ptr(self._state), ptr(boxes), ptr(counts), ptr(cuts), n, m,
+                                                  ptr(emb), self.iou_min, self.sim_min,
+                                                  self.max_age, ptr(track), ptr(sim), ptr(flag), ptr(self._table), self._table.shape[0],
+                                                  stream(self.device)))
         if self._pool is not None:
             if self._pool.num_groups < self._table.shape[0]:
                 self._pool.grow(self._table.shape[0])

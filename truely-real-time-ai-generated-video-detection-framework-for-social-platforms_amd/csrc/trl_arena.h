@@ -10,7 +10,7 @@
 // block -- a red zone -- and the next block still starts on a 256-byte boundary, so the gap behind a block is >= guard and
 // < guard + 256.  The red zone counts as used (`off` and `high` include it), so a counting arena with the same guard still counts
 // exactly what the real one carves.  While the guard is on, a real arena remembers the blocks handed out since the last rewind and
-// tells its owner before each rewind (on_rewind: the red-zone sweep of trl_api.hip looks at the gaps before the layout goes away).
+// tells its owner before each rewind (on_rewind: the red-zone sweep of trl_redzone.hip looks at the gaps before the layout goes away).
 struct Arena {
     struct Block { size_t off, bytes; };
     char* base = nullptr;

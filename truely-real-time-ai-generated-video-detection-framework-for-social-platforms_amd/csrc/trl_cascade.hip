@@ -843,7 +843,7 @@ static size_t spill_need(long long cnt, int W, int H) {   // upper bound of the 
 // by the re-run)
 static size_t spill_pool(const trl_ctx* c, int n, int H, int W) {
     const LvLayout& G = c->cb.lay;
-    const int lds_full = c->nms_full;
+    const int lds_full = c->opt.nms_full;
     size_t spill = c->caps.spill_hint;
     size_t per_frame = 0;
     for (int l = 0; l < G.L; l++) if (G.capl[l] > lds_full) per_frame += spill_need(G.capl[l], W, H);
@@ -863,7 +863,7 @@ struct ListLaunch {
 static int list_launch(trl_ctx* c, ListLaunch& ll) {
     const LvLayout& G = c->cb.lay;
     const int capF = c->cb.capF;
-    const int lds_full = c->nms_full, lds_small = c->nms_small < c->nms_full ? c->nms_small : c->nms_full;
+    const int lds_full = c->opt.nms_full, lds_small = c->opt.nms_small < c->opt.nms_full ? c->opt.nms_small : c->opt.nms_full;
     // LDS tiers: no list is longer than its capacity, so the carve never exceeds what the call can produce
     int max_capl = 4;
     for (int l = 0; l < G.L; l++) if (G.capl[l] > max_capl) max_capl = G.capl[l];
@@ -1105,14 +1105,14 @@ int trl_cascade_detect(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     return TRL_OK;
 }
 
-// One R-Net (net = 24) or O-Net (net = 48) stage over `cap` candidate slots: chunks of c->rnet_chunk / c->onet_chunk candidates,
+// One R-Net (net = 24) or O-Net (net = 48) stage over `cap` candidate slots: chunks of c->opt.rnet_chunk / c->opt.onet_chunk candidates,
 // each the fused front kernel (crop of record t0 + i of c->cb.cbox, conv1, pool1 in LDS) then the layer tail.  Launches are sized
 // by the capacity; the candidates that exist are the first *d_total, and every kernel skips the rest on the device.  The pooled
 // maps come from X behind its current offset (the caller's blocks below it stay intact).  d_out: [cap][6] / [cap][16].  Over a
 // counting X one chunk is walked: the first is the largest.
 int trl_stage_net(trl_ctx* c, Arena& X, int net, const uint8_t* d_frames, int H, int W, const int32_t* d_total, int cap, float* d_out, hipStream_t s) {
     const NetDesc& d = trl_net_of(net);
-    const int CH = c->*d.chunk;
+    const int CH = c->opt.*d.chunk;
     const size_t mk = X.off;
     for (int t0 = 0; t0 < cap; t0 += CH) {
         const int nc = (cap - t0 < CH) ? cap - t0 : CH;
@@ -1136,7 +1136,7 @@ int trl_cascade_finish(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     TRL_LAUNCH_CHECK();
     // overflow flags + stage totals travel to pinned host memory behind the kernels; trl_cascade_check reads them after the
     // call's ONE stream synchronisation (no host round trip inside the call)
-    TRL_HIP(hipMemcpyAsync(c->h_pinned + 4, B.flags, TRL_NFLAGS * 4, hipMemcpyDeviceToHost, s));
+    TRL_HIP(hipMemcpyAsync(trl_host_flags(c), B.flags, TRL_NFLAGS * 4, hipMemcpyDeviceToHost, s));
     return TRL_OK;
 }
 
@@ -1145,7 +1145,7 @@ int trl_cascade_finish(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
 // attempt measured and the caller runs the call again (results of the attempt are incomplete, not wrong-but-plausible, and are
 // never delivered).  No input can make this fail: detect_face() (server/model.py:47) has no candidate limit.
 int trl_cascade_check(trl_ctx* c, int n, int* retry) {
-    *retry = trl_caps_check(c->caps, c->h_pinned + 4, n, c->cb.lay).retry;
+    *retry = trl_caps_check(c->caps, trl_host_flags(c), n, c->cb.lay).retry;
     return TRL_OK;
 }
 
@@ -1172,7 +1172,7 @@ int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* 
     for (int i = 0; i < nc; i++) total += h_counts[i];
     const int carved = carve_lists(c, spill_pool(c, n, H, W), s);
     if (carved != TRL_OK) { B = CascadeBufs(); return carved; }
-    const int poison = c->dbg_poison >= 0 ? c->dbg_poison : 0xA5;
+    const int poison = c->hook.dbg_poison >= 0 ? c->hook.dbg_poison : 0xA5;
     TRL_HIP(hipMemsetAsync(c->arena.base, poison, (size_t)((char*)B.flags - c->arena.base), s));   // every list (the flags stay zero)
     // the caller's lists, packed, into the capacity layout; the poison stays in the slots behind the counts
     std::vector<int32_t> cnt(h_counts, h_counts + nc);
@@ -1220,11 +1220,11 @@ int trl_cascade_lists(trl_ctx* c, int kind, int n, int H, int W, const int32_t* 
         }
         TRL_HIP(hipStreamSynchronize(s));                 // (the logits vector)
     }
-    if (kind != 3) TRL_HIP(hipMemcpyAsync(c->h_pinned + 4, B.flags, TRL_NFLAGS * 4, hipMemcpyDeviceToHost, s));
+    if (kind != 3) TRL_HIP(hipMemcpyAsync(trl_host_flags(c), B.flags, TRL_NFLAGS * 4, hipMemcpyDeviceToHost, s));
     if (kind == 3 && h_pts) TRL_HIP(hipMemcpyAsync(h_pts, B.pts3, (size_t)n * capF * 40, hipMemcpyDeviceToHost, s));
     TRL_HIP(hipStreamSynchronize(s));
     c->caps.last_attempts = 1;
-    const int32_t* fl = c->h_pinned + 4;
+    const int32_t* fl = trl_host_flags(c);
     if (fl[FLG_LEVEL] || fl[FLG_FRAME] || fl[FLG_SPILL]) {
         trl_set_error("list hook: a capacity was too small (level %d, frame %d, spill %d)", fl[FLG_LEVEL], fl[FLG_FRAME], fl[FLG_SPILL]);
         return TRL_ERR_CAPACITY;

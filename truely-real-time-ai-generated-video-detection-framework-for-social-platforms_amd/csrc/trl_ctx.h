@@ -43,7 +43,19 @@ struct CascadeBufs {   // device pointers into the arena, valid until the next c
 // stage loop and the loader's tensor check all read it.
 struct NetLayer { const char* name; const char* prelu; int k, st, cout; };   // a valid k x k conv `name` (+ bias, + PReLU `prelu` or none) of
                                                                              // cout channels; name == null: a ceil-mode max pool k / st
-struct trl_ctx;
+enum { TRL_PNET_DEFER_DEFAULT = 1 };   // (DESIGN.md section 4: the measurement behind the default)
+// What only trl_debug_option, trl_debug_nms_tiers and trl_debug_pnet_run change (trl_hooks.hip): the product path reads these nine and
+// never writes them
+struct Options {
+    int rnet_chunk = 49152, onet_chunk = 16384;   // R-/O-Net candidates per launch set (trl_cascade.hip; trl_debug_option shrinks them for tests)
+    int tail_pool = 1;               // trl_debug_option "tail_pool": 0 = every R-/O-Net tail pool is its own launch (trl_run_net)
+    int nms_small = 512, nms_full = 2048;   // LDS tiers of the sort + NMS kernels (candidates); longer lists take the spill tier
+                                            // (trl_debug_nms_tiers lowers them so that small test inputs reach every tier)
+    int pnet_screen = 1;             // trl_debug_option "pnet_screen": 0 = every M-tile takes the exact f32 path
+    int pnet_defer = TRL_PNET_DEFER_DEFAULT;   // trl_debug_option "pnet_defer": 1 = confirmed conv3 M-tiles run in a second kernel where the launch can defer
+    int pnet_run = 0;                // > 0: tiles per cursor fetch of the fused PNet launch (trl_debug_pnet_run); 0 = automatic
+    int pyr_row_bands = 0;           // trl_debug_option "pyr_row_bands": > 0 forces the row bands of the streaming pyramid pass (tests)
+};
 struct NetDesc {
     const char* name;
     int side;                        // crop side (0: PNet takes any map)
@@ -51,14 +63,50 @@ struct NetDesc {
     int tail;                        // first layer behind the fused front kernel (trl_front.hip), whose pooled map is [P][P][C1]
     int P, C1;
     int nout;                        // output floats per item
-    int trl_ctx::*chunk;             // the context's candidates-per-launch-set option of this net
+    int Options::*chunk;             // the context's candidates-per-launch-set option of this net
 };
-enum { TRL_PNET_DEFER_DEFAULT = 1 };   // (DESIGN.md section 4: the measurement behind the default)
 enum { TRL_PNET = 0, TRL_RNET = 1, TRL_ONET = 2 };
 extern const NetDesc trl_nets[3];
 inline const NetDesc& trl_net_of(int net) { return trl_nets[net == 24 ? TRL_RNET : TRL_ONET]; }   // the API's net argument: 24 / 48
 struct NetLayerW { const DevW* w = nullptr; const float* b = nullptr; const float* slope = nullptr; };   // a conv layer's device tensors
 struct FnW { const DevW* w = nullptr; const float* scale = nullptr; const float* shift = nullptr; const float* bias = nullptr; };   // a FaceNet row's
+
+// The 64-bit diagnostic words of trl_ctx::pnet_clk (device).  The fused PNet kernel and k_pnet_span write them (trl_pnet.hip);
+// trl_destroy (the TRL_PNET_CLOCK report), collect_timings and trl_debug_pnet_span read them.
+enum {
+    CLK_START = 0, CLK_END = 1,      // first workgroup start / last workgroup end (wall clock) of the fused PNet launch in flight
+    CLK_PHASE = 2,                   // DBG: [CLK_PHASE + 8 wave + k], shader clocks of wave 0..3 in phase / at barrier k = 0..7
+    CLK_ROT = CLK_PHASE + 32,        // DBG: workgroup-tiles the phase clocks were summed over
+    CLK_SPAN_SUM = 36, CLK_LAUNCHES = 37, CLK_LAST_SPAN = 38,   // summed spans and their count (trl_debug_pnet_span), the last launch's span
+    CLK_SCREENED = 39, CLK_CONFIRMED = 40,   // DBG: conv3 M-tiles screened / confirmed
+    CLK_QUEUED = 41,                 // M-tiles queued for the confirm pass
+    CLK_PEND_SCREENED = 42, CLK_PEND_CONFIRMED = 43,   // DBG: a DEFER launch's own two counts until it is known to have fitted
+    CLK_WORDS = 44
+};
+static_assert(CLK_LAUNCHES == CLK_SPAN_SUM + 1, "trl_debug_pnet_span reads and clears the two as one pair");
+
+// State that only a test hook reads or writes (trl_hooks.hip, trl_redzone.hip); the product path feeds it where a hook asked for it
+struct Hooks {
+    int dbg_poison = -1;             // >= 0 after trl_debug_poison: byte written into every newly allocated workspace
+    // trl_debug_redzone (trl_redzone.hip): while rz.guard != 0, `arena` and `scratch` carry that guard, dbg_poison is the fill byte and
+    // every byte of the two that belongs to no block is checked against it at each rewind, before a grow and at the end of each call
+    struct RedZone {
+        size_t guard = 0; int byte = 0, saved_poison = -1;
+        long long sweeps = 0, bytes = 0, nhits = 0;
+        std::vector<trl_rz_hit> hits;                 // the first TRL_RZ_MAX_HITS
+        unsigned long long* dev = nullptr; size_t dev_gaps = 0;   // device: the gap table of a sweep and its results
+    } rz;
+    // what the last build_pyramid chose per level (trl_debug_pyramid_plan): rows of TRL_PYR_PLAN_COLS ints; L = 0 after a refused call
+    struct { int L = 0; int32_t row[16][TRL_PYR_PLAN_COLS] = {}; } pyr_plan;
+    std::vector<trl_fn_plan_row> fn_plan;   // the conv launches of the last embedder call (trl_debug_facenet_plan)
+    // the R-/O-Net tail conv launches of the last trl_debug_stage_net call, every chunk (trl_debug_mtcnn_plan); recorded only
+    // while that hook runs (mt_plan_arm)
+    std::vector<trl_fn_plan_row> mt_plan;
+    bool mt_plan_arm = false;
+    // trl_debug_facenet_capture: armed conv index (-1: off) and its three copied views (input / residual / output)
+    int fn_cap_arm = -1;
+    struct { void* p = nullptr; size_t cap = 0; int32_t dims[5] = {0, 0, 0, 0, 0}; } fn_cap[3];
+};
 
 struct trl_ctx {
     trl_config cfg;
@@ -79,9 +127,9 @@ struct trl_ctx {
     Arena arena;                     // per-call persistent blocks (cascade lists)
     Arena scratch;                   // transient activations; only ever grown while empty (trl_scratch_begin)
     size_t arena_need = 0;           // the count of the last list layout (trl_debug_workspace)
-    int fn_need_key[6] = {0}; size_t fn_need_bytes = 0;   // the last embedder dry run (embed_need): what its walk branches on, its count
+    int fn_need_key[6] = {0}; size_t fn_need_bytes = 0;   // the last embedder dry run (trl_embed_need): what its walk branches on, its count
     Arena sims_tmp;                  // similarities when trl_drift_score is called with d_sims == NULL
-    int32_t* h_pinned = nullptr;     // small pinned host scratch
+    int32_t* h_pinned = nullptr;     // pinned host copy of the FLG_* words (trl_host_flags): 1,024 bytes
     CascadeBufs cb;
     LevelGeom lv[32];
     hipEvent_t ev_call0 = nullptr, ev_call1 = nullptr;
@@ -93,29 +141,15 @@ struct trl_ctx {
     float pnet_scrA = 0.f, pnet_scrB = 0.f;   // fp16 conv3 screen of the fused PNet: |d_screen - d_exact| <= A X + B (trl_pnet_prepare)
     float pnet_scrG[16] = {};        // the bound the kernel applies: sum over the cell's 3x3x16 inputs of pnet_scrG[channel] |x|, + B (sum of the 144 coefficients <= A)
     int pnet_screen_ok = 0;          // the conv3 weights fit fp16 (else the screen is off for this net)
-    int pnet_screen = 1;             // trl_debug_option "pnet_screen": 0 = every M-tile takes the exact f32 path
-    int pnet_defer = TRL_PNET_DEFER_DEFAULT;   // trl_debug_option "pnet_defer": 1 = confirmed conv3 M-tiles run in a second kernel where the launch can defer
-    int pnet_run = 0;                // > 0: tiles per cursor fetch of the fused PNet launch (trl_debug_pnet_run); 0 = automatic
     int32_t* pnet_cursor = nullptr;           // device: 8 per-XCD tile cursors of the fused PNet launch
-    unsigned long long* pnet_clk = nullptr;   // device: [0] first-start / [1] last-end wall clock of the fused PNet launch in flight, [2..35] phase clocks (DBG), [36] summed spans, [37] launches, [39] / [40] screened / confirmed M-tiles (DBG), [41] queued M-tiles, [42] / [43] a DEFER launch's own counts until it is known to have fitted
+    unsigned long long* pnet_clk = nullptr;   // device: the CLK_WORDS diagnostic words of the fused PNet launches (the CLK_* enum above)
     bool pnet_prof = false;                   // TRL_PNET_CLOCK: the DBG instantiation with per-phase wave clocks
     float pnet_kernel_ms = 0.f;      // its span in ms (collect_timings)
-    int dbg_poison = -1;             // >= 0 after trl_debug_poison: byte written into every newly allocated workspace
-    // trl_debug_redzone (trl_api.hip): while rz.guard != 0, `arena` and `scratch` carry that guard, dbg_poison is the fill byte and
-    // every byte of the two that belongs to no block is checked against it at each rewind, before a grow and at the end of each call
-    struct RedZone {
-        size_t guard = 0; int byte = 0, saved_poison = -1;
-        long long sweeps = 0, bytes = 0, nhits = 0;
-        std::vector<trl_rz_hit> hits;                 // the first TRL_RZ_MAX_HITS
-        unsigned long long* dev = nullptr; size_t dev_gaps = 0;   // device: the gap table of a sweep and its results
-    } rz;
+    Options opt;
+    Hooks hook;
     // Optimistic capacities of the candidate lists, the spill pool and the R-Net / O-Net batches: launches and workspaces are sized
     // by them, and a call that overflows one is re-run with a larger value (trl_capacity.h)
     CascadeCaps caps;
-    int rnet_chunk = 49152, onet_chunk = 16384;   // R-/O-Net candidates per launch set (trl_cascade.hip; trl_debug_option shrinks them for tests)
-    int tail_pool = 1;               // trl_debug_option "tail_pool": 0 = every R-/O-Net tail pool is its own launch (trl_run_net)
-    int nms_small = 512, nms_full = 2048;   // LDS tiers of the sort + NMS kernels (candidates); longer lists take the spill tier
-                                            // (trl_debug_nms_tiers lowers them so that small test inputs reach every tier)
     size_t scratch_after_cascade = 0;   // scratch bytes the rest of the call needs (crops + FaceNet): sized with the cascade's
     // the call in progress: queued by trl_detect_embed_begin / trl_detect_crop_begin and not yet finished by trl_detect_embed_end,
     // or a blocking trl_detect_embed / trl_detect_crop / trl_mtcnn_detect* between its enqueue and its wait (trl_api.hip)
@@ -132,20 +166,10 @@ struct trl_ctx {
     } pend;
     uint32_t* pyr_tab = nullptr;     // pyramid bin-edge tables for the last (H, W)
     int pyr_tab_H = 0, pyr_tab_W = 0;
-    int pyr_row_bands = 0;           // trl_debug_option "pyr_row_bands": > 0 forces the row bands of the streaming pyramid pass (tests)
     // one-pass kernel for the finest levels (k_pyramid_fine): ownership table inside pyr_tab, source tile shape; nlev == 0: not usable for this shape
     struct { int nlev = 0, own0 = 0, band_cols = 0, strip_rows = 0, n_bands = 0, n_strips = 0; } pyr_fine;
-    // what the last build_pyramid chose per level (trl_debug_pyramid_plan): rows of TRL_PYR_PLAN_COLS ints; L = 0 after a refused call
-    struct { int L = 0; int32_t row[16][TRL_PYR_PLAN_COLS] = {}; } pyr_plan;
-    std::vector<trl_fn_plan_row> fn_plan;   // the conv launches of the last embedder call (trl_debug_facenet_plan)
-    // the R-/O-Net tail conv launches of the last trl_debug_stage_net call, every chunk (trl_debug_mtcnn_plan); recorded only
-    // while that hook runs (mt_plan_arm)
-    std::vector<trl_fn_plan_row> mt_plan;
-    bool mt_plan_arm = false;
-    // trl_debug_facenet_capture: armed conv index (-1: off) and its three copied views (input / residual / output)
-    int fn_cap_arm = -1;
-    struct { void* p = nullptr; size_t cap = 0; int32_t dims[5] = {0, 0, 0, 0, 0}; } fn_cap[3];
 };
+inline int32_t* trl_host_flags(const trl_ctx* c) { return c->h_pinned; }   // the FLG_* words of the last attempt, copied behind its kernels
 
 // The kernel a conv launcher picked (set by trl_launch_conv / trl_launch_fn_group / trl_launch_conv_bf16 as they choose, read by
 // the FaceNet walker for trl_debug_facenet_plan): host bookkeeping only.
@@ -165,9 +189,10 @@ int trl_ensure(trl_ctx* c, Arena& a, size_t bytes);   // grow (never while block
 // carve is the whole call (trl_carve_scratch), carve(X) over a counting arena, then over the scratch grown to that count
 inline int trl_scratch_begin(trl_ctx* c, size_t bytes) { c->scratch.reset("scratch_begin"); c->scratch.high = 0; return trl_ensure(c, c->scratch, bytes); }
 // the red-zone sweep at the end of an entry point that queued work on the arenas (trl_debug_redzone; nothing while it is off).
-// site: the entry point's label in the report
-int trl_rz_sweep_all(trl_ctx* c, const char* site);
-inline int trl_rz_end(trl_ctx* c, const char* site) { return c->rz.guard ? trl_rz_sweep_all(c, site) : TRL_OK; }
+// site: the entry point's label in the report.  trl_rz_sweep (trl_redzone.hip) sweeps both workspaces, or only `one` (trl_ensure,
+// before it frees a guarded workspace to grow it)
+int trl_rz_sweep(trl_ctx* c, const char* site, Arena* one = nullptr);
+inline int trl_rz_end(trl_ctx* c, const char* site) { return c->hook.rz.guard ? trl_rz_sweep(c, site) : TRL_OK; }
 template <class F> int trl_carve_scratch(trl_ctx* c, F&& carve) {
     Arena X = Arena::counter(c->scratch.guard);
     TRL_CHECK(carve(X)); TRL_CHECK(trl_scratch_begin(c, X.high));
@@ -176,6 +201,15 @@ template <class F> int trl_carve_scratch(trl_ctx* c, F&& carve) {
 // A context holds at most one call in flight (trl_detect_embed_begin .. _end); anything else that touches its workspaces meanwhile
 // would corrupt that call silently: TRL_ERR_STATE (and TRL_ERR_INVALID for a null context)
 int trl_check_idle(trl_ctx* c);
+// trl_check_idle, then what every entry point that takes frames requires: weights, 1..65535 frames of 12..16383 px per side, a
+// 4-byte aligned buffer (trl_api.hip; the stage hooks of trl_hooks.hip apply the same)
+int trl_check_call(trl_ctx* c, const void* frames, int n, int H, int W);
+// c->fn_need_bytes = the scratch count of an embedder call on n faces of h x w -- with `crops`, of an EMBED call's crops and
+// embedder on n frames (trl_api.hip; trl_debug_workspace reports it)
+int trl_embed_need(trl_ctx* c, bool crops, int n, int h, int w);
+// The way into a test hook that touches the device or the workspaces (trl_hooks.hip, trl_redzone.hip): no call in flight, and the
+// context's device current before the hook synchronises, copies or launches
+inline int trl_hook_device(trl_ctx* c) { TRL_CHECK(trl_check_idle(c)); TRL_HIP(hipSetDevice(c->cfg.device)); return TRL_OK; }
 void trl_free_weights(trl_ctx* c);   // trl_weights.hip: the device weights and every 16-bit copy; the context then has none
 
 // networks (trl_nets.hip).  Every walk takes its activations from X; over a counting X it still checks every shape (the walk of
@@ -185,7 +219,7 @@ int trl_run_facenet(trl_ctx* c, Arena& X, const float* d_faces, int n, int h, in
                     bool features = false);
 // Layers first .. last of net d over x (x.n items; the maps of layer `first`): d_out [x.n][oh][ow][d.nout].  With m_dev, x.n is the
 // CAPACITY of the launch and the items that exist are clamp(*m_dev - m_base, 0, x.n) (device-sized, no host sync).  While
-// c->mt_plan_arm its conv launches are appended to c->mt_plan ("rnet.conv2" .. "onet.heads").
+// c->hook.mt_plan_arm its conv launches are appended to c->hook.mt_plan ("rnet.conv2" .. "onet.heads").
 int trl_run_net(trl_ctx* c, Arena& X, const NetDesc& d, int first, const Act& x, float* d_out, hipStream_t s, const int32_t* m_dev = nullptr,
                 int m_base = 0);
 // trl_load_weights, after the upload: himg is the staged host image, laid out like c->wdev (trl_host_of reads a device tensor's copy)

@@ -16,11 +16,11 @@ const NetDesc trl_nets[3] = {
      0, 0, 0, 6, nullptr},
     {"rnet", 24, 7, {{"conv1", "prelu1", 3, 1, 28}, {nullptr, nullptr, 3, 2, 0}, {"conv2", "prelu2", 3, 1, 48}, {nullptr, nullptr, 3, 2, 0},
                      {"conv3", "prelu3", 2, 1, 64}, {"dense4", "prelu4", 3, 1, 128}, {"heads", nullptr, 1, 1, 6}},
-     2, 11, 28, 6, &trl_ctx::rnet_chunk},
+     2, 11, 28, 6, &Options::rnet_chunk},
     {"onet", 48, 9, {{"conv1", "prelu1", 3, 1, 32}, {nullptr, nullptr, 3, 2, 0}, {"conv2", "prelu2", 3, 1, 64}, {nullptr, nullptr, 3, 2, 0},
                      {"conv3", "prelu3", 3, 1, 64}, {nullptr, nullptr, 2, 2, 0}, {"conv4", "prelu4", 2, 1, 128}, {"dense5", "prelu5", 3, 1, 256},
                      {"heads", nullptr, 1, 1, 16}},
-     2, 23, 32, 16, &trl_ctx::onet_chunk},
+     2, 23, 32, 16, &Options::onet_chunk},
 };
 
 namespace {
@@ -51,14 +51,14 @@ struct Runner {
         r.m = a.M; r.cout = a.Cout; r.k = a.K; r.precision = a.lowp; r.has_res = m.has_res;
         strncpy(r.layer, m.layer, sizeof(r.layer) - 1);
         plan->push_back(r);
-        if (plan != &c->fn_plan || c->fn_cap_arm != m.idx) return;   // captures are FaceNet convs only
+        if (plan != &c->hook.fn_plan || c->hook.fn_cap_arm != m.idx) return;   // captures are FaceNet convs only
         int st = capture(0, m.x, 1 << 30, 0);
         if (st == TRL_OK && m.has_res) st = capture(1, m.res, 1 << 30, 0);
         if (st == TRL_OK) st = capture(2, m.y, a.ysplit, a.yskip);
         if (st != TRL_OK && err == TRL_OK) err = st;
     }
     int capture(int v, const Act& a, int ysplit, int yskip) {
-        auto& b = c->fn_cap[v];
+        auto& b = c->hook.fn_cap[v];
         const size_t es = a.bf ? sizeof(uint16_t) : sizeof(float), row = (size_t)a.c * es, need = row * a.pixels();
         if (b.cap < need) {
             if (b.p) TRL_HIP(hipFree(b.p));
@@ -276,11 +276,11 @@ int trl_run_facenet(trl_ctx* c, Arena& X, const float* d_faces, int n, int h, in
     if (n <= 0) return TRL_OK;
     Runner R{c, s, X};
     const bool check_only = X.counting;
-    struct Disarm { trl_ctx* c; ~Disarm() { if (c) c->fn_cap_arm = -1; } } disarm{check_only ? nullptr : c};   // a capture covers one call, whatever its outcome
+    struct Disarm { trl_ctx* c; ~Disarm() { if (c) c->hook.fn_cap_arm = -1; } } disarm{check_only ? nullptr : c};   // a capture covers one call, whatever its outcome
     if (!check_only) {
-        c->fn_plan.clear();
-        R.plan = &c->fn_plan;
-        if (c->fn_cap_arm >= 0) for (auto& b : c->fn_cap) b.dims[3] = 0;
+        c->hook.fn_plan.clear();
+        R.plan = &c->hook.fn_plan;
+        if (c->hook.fn_cap_arm >= 0) for (auto& b : c->hook.fn_cap) b.dims[3] = 0;
     }
     const Act x0 = Act::dense(d_faces, n, h, w, 3);
     Act x = R.fconv(x0, FN_STEM + 0);                // conv2d_1a
@@ -354,7 +354,7 @@ int trl_run_net(trl_ctx* c, Arena& X, const NetDesc& d, int first, const Act& x0
     if (x0.n <= 0) return TRL_OK;
     Runner R{c, s, X};
     R.m_dev = m_dev; R.m_base = m_base;
-    if (c->mt_plan_arm) { R.plan = &c->mt_plan; R.nconv = (int)c->mt_plan.size(); }   // trl_debug_stage_net: rows of every chunk
+    if (c->hook.mt_plan_arm) { R.plan = &c->hook.mt_plan; R.nconv = (int)c->hook.mt_plan.size(); }   // trl_debug_stage_net: rows of every chunk
     const NetLayerW* lw = c->mt[&d - trl_nets];
     Act x = x0;
     for (int i = first; i < d.nl; i++) {
@@ -364,7 +364,7 @@ int trl_run_net(trl_ctx* c, Arena& X, const NetDesc& d, int first, const Act& x0
         if (R.plan) { snprintf(layer, sizeof layer, "%s.%s", d.name, L.name); R.layer = layer; }
         // a pool directly behind the conv runs in the conv's epilogue where the kernel has one: the 128-row tiles of R-Net conv2 and
         // O-Net conv2 / conv3 at production capacities (smaller launches, PNet and every other pool: separate launches as below)
-        if (c->tail_pool && i + 2 < d.nl && !d.layer[i + 1].name &&
+        if (c->opt.tail_pool && i + 2 < d.nl && !d.layer[i + 1].name &&
             R.conv_pool(x, lw[i], L.k, L.prelu ? TRL_ACT_PRELU : TRL_ACT_NONE, d.layer[i + 1].k, d.layer[i + 1].st, &x)) {
             i++;
             continue;

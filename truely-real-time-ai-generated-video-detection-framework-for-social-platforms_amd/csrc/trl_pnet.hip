@@ -102,7 +102,7 @@ struct PnetArgs {
     int32_t* lvl_cnt; Cand* lvl_rec; int32_t* flags;
     int32_t* xcd_next;                         // per-XCD dynamic tile cursor (8 counters, zeroed before the launch)
     int run;                                   // consecutive tiles a workgroup takes per cursor fetch (>= 1)
-    unsigned long long* clk;                   // [0] = earliest workgroup start, [1] = latest workgroup end (device wall clock); DBG: [2..] phase clocks
+    unsigned long long* clk;                   // the CLK_* words (trl_ctx.h): CLK_START = earliest workgroup start, CLK_END = latest workgroup end (device wall clock); DBG: the phase clocks
     int prof;                                  // DBG instantiation: accumulate the per-phase wave clocks
     char* q; int q_cap; int32_t* q_cnt;        // DEFER: the confirm queue (q_cap slots of TRL_DEFER_SLOT bytes) and its slot counter (zeroed with xcd_next)
 };
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: every M-tile index below is SALU work
     const int dbg_skip = DBG ? a.dbg_skip : 0;                   // a compile-time 0 in production
-    if (DBG && tid == 0) atomicMin(&a.clk[0], (unsigned long long)wall_clock64());   // tuning build: execution span of the launch (first workgroup start .. last workgroup end)
+    if (DBG && tid == 0) atomicMin(&a.clk[CLK_START], (unsigned long long)wall_clock64());   // tuning build: execution span of the launch (first workgroup start .. last workgroup end)
     const int l15 = lane & 15, kq = lane >> 4;      // 16x16x4 operand coordinates
     const int l31 = lane & 31, hh = lane >> 5;      // 32x32x2 operand coordinates
 
@@ -519,14 +519,14 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
     int hs_tile[BAND], vs_tile = -1;
 #pragma unroll
     for (int i = 0; i < BAND; i++) hs_tile[i] = -1;
-    // DBG + TRL_PNET_CLOCK: shader-clock time of every wave in each phase and at each barrier, summed over the launch (clk[2 + 8 wave + k])
+    // DBG + TRL_PNET_CLOCK: shader-clock time of every wave in each phase and at each barrier, summed over the launch (clk[CLK_PHASE + 8 wave + k])
     unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt_last = 0;
     const bool prof = DBG && a.prof != 0;
     auto stamp = [&](int k) {
         if (DBG && prof) { const unsigned long long t = clock64(); pt[k] += t - pt_last; pt_last = t; }
     };
     if (DBG && prof) pt_last = clock64();
-    unsigned nscr = 0, ncnf = 0;                  // DBG: M-tiles this wave screened / confirmed (clk[39], clk[40])
+    unsigned nscr = 0, ncnf = 0;                  // DBG: M-tiles this wave screened / confirmed (clk[CLK_SCREENED], clk[CLK_CONFIRMED])
     for (; tile < t_end; tile = tile_nxt, cur = nxt, rot++) {
         const int f = cur.f, l = cur.l, ty = cur.ty, tx = cur.tx;
         const TileId& g = cur;
@@ -1055,13 +1055,13 @@ __global__ __launch_bounds__(256, 2) void k_pnet_fused(PnetArgs a) {
     }
     if (DBG && prof && lane == 0) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) atomicAdd(&a.clk[2 + 8 * wave + k], pt[k]);
-        if (wave == 0) atomicAdd(&a.clk[2 + 32], (unsigned long long)rot);
+        for (int k = 0; k < 8; k++) atomicAdd(&a.clk[CLK_PHASE + 8 * wave + k], pt[k]);
+        if (wave == 0) atomicAdd(&a.clk[CLK_ROT], (unsigned long long)rot);
     }
-    // (a DEFER launch counts into [42] / [43]: k_pnet_span adds them to the totals unless the queue overflowed -- that launch's records
+    // (a DEFER launch counts into CLK_PEND_SCREENED / CLK_PEND_CONFIRMED: k_pnet_span adds them to the totals unless the queue overflowed -- that launch's records
     // are dropped and its re-run counts the same M-tiles again)
-    if (DBG && lane == 0 && nscr) { atomicAdd(&a.clk[DEFER ? 42 : 39], (unsigned long long)nscr); atomicAdd(&a.clk[DEFER ? 43 : 40], (unsigned long long)ncnf); }
-    if (DBG && tid == 0) atomicMax(&a.clk[1], (unsigned long long)wall_clock64());
+    if (DBG && lane == 0 && nscr) { atomicAdd(&a.clk[DEFER ? CLK_PEND_SCREENED : CLK_SCREENED], (unsigned long long)nscr); atomicAdd(&a.clk[DEFER ? CLK_PEND_CONFIRMED : CLK_CONFIRMED], (unsigned long long)ncnf); }
+    if (DBG && tid == 0) atomicMax(&a.clk[CLK_END], (unsigned long long)wall_clock64());
 }
 
 // The second pass behind a DEFER launch: the exact f32 chain of every queued M-tile, ONE wave per slot, no barrier between the
@@ -1114,16 +1114,17 @@ __global__ __launch_bounds__(64 * CONFIRM_WAVES, 4) void k_pnet_confirm(PnetArgs
 
 }  // namespace
 
-// after a fused launch: [36] += its span, [37] += 1, [38] = its span; the start / end stamps are re-armed for the next launch;
-// a DEFER launch whose queue held every M-tile: [39] / [40] += the M-tiles it screened / confirmed, [41] += the M-tiles it queued
+// after a fused launch: CLK_SPAN_SUM += its span, CLK_LAUNCHES += 1, CLK_LAST_SPAN = its span; the start / end stamps are re-armed for
+// the next launch; a DEFER launch whose queue held every M-tile: CLK_SCREENED / CLK_CONFIRMED += the M-tiles it screened / confirmed,
+// CLK_QUEUED += the M-tiles it queued
 __global__ void k_pnet_span(unsigned long long* clk, const int32_t* q_cnt, int q_cap) {
-    const unsigned long long t0 = clk[0], t1 = clk[1];
+    const unsigned long long t0 = clk[CLK_START], t1 = clk[CLK_END];
     const unsigned long long d = t1 > t0 ? t1 - t0 : 0ull;
-    clk[36] += d; clk[37] += 1ull; clk[38] = d;
-    clk[0] = ~0ull; clk[1] = 0ull;
+    clk[CLK_SPAN_SUM] += d; clk[CLK_LAUNCHES] += 1ull; clk[CLK_LAST_SPAN] = d;
+    clk[CLK_START] = ~0ull; clk[CLK_END] = 0ull;
     if (q_cnt) {
-        if (*q_cnt <= q_cap) { clk[39] += clk[42]; clk[40] += clk[43]; clk[41] += (unsigned long long)*q_cnt; }
-        clk[42] = clk[43] = 0ull;
+        if (*q_cnt <= q_cap) { clk[CLK_SCREENED] += clk[CLK_PEND_SCREENED]; clk[CLK_CONFIRMED] += clk[CLK_PEND_CONFIRMED]; clk[CLK_QUEUED] += (unsigned long long)*q_cnt; }
+        clk[CLK_PEND_SCREENED] = clk[CLK_PEND_CONFIRMED] = 0ull;
     }
 }
 
@@ -1237,7 +1238,7 @@ static void fill_args(trl_ctx* c, int n, int H, int W, const PyrLayout& lay, con
     // p = softmax(logit0, logit1)[1] >= thr needs logit1 - logit0 >= ln(thr / (1 - thr)) up to the rounding of the float softmax
     // (~1e-6 relative); 0.05 below that bound the probability is short of thr by 0.05 thr (1 - thr) >= 4.9e-4 for thr in [0.01, 0.99]
     a.dthr = (a.thr >= 0.01f && a.thr <= 0.99f) ? (float)(log((double)a.thr / (1.0 - (double)a.thr)) - 0.05) : -__builtin_inff();
-    a.scrB = c->pnet_scrB; a.screen = c->pnet_screen && c->pnet_screen_ok;
+    a.scrB = c->pnet_scrB; a.screen = c->opt.pnet_screen && c->pnet_screen_ok;
     for (int i = 0; i < 16; i++) a.scrG[i] = c->pnet_scrG[i];
     a.dbg_skip = trl_tune_int("TRL_PNET_SKIP", 0);
     a.lvl_cnt = c->cb.lvl_cnt; a.lvl_rec = c->cb.lvl_rec; a.flags = c->cb.flags;
@@ -1249,7 +1250,7 @@ static void fill_args(trl_ctx* c, int n, int H, int W, const PyrLayout& lay, con
 // Deferral applies where the screen is on, leaves something out (thr0 inside the prefilter's range: outside it every M-tile
 // confirms) and the net has a DEFER instantiation (no slope above 1); every other launch runs the exact chain inline
 bool trl_pnet_can_defer(const trl_ctx* c) {
-    return c->pnet_defer && c->pnet_screen && c->pnet_screen_ok && c->pnet_unit && c->cfg.thr0 >= 0.01f && c->cfg.thr0 <= 0.99f &&
+    return c->opt.pnet_defer && c->opt.pnet_screen && c->pnet_screen_ok && c->pnet_unit && c->cfg.thr0 >= 0.01f && c->cfg.thr0 <= 0.99f &&
            trl_tune_int("TRL_PNET_SKIP", 0) == 0;
 }
 long long trl_pnet_mtiles(const trl_ctx* c, int L, int n) {
@@ -1293,7 +1294,7 @@ int trl_pnet_fused_all(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W,
     // small batches keep shorter runs, down to single tiles, so that every CU gets work
     // (trl_debug_pnet_run overrides it: tests that exercise the carry path on small frames)
     const int auto_run = (total_tiles / 8) / 128;
-    a.run = c->pnet_run > 0 ? c->pnet_run : (auto_run < 1 ? 1 : (auto_run > 8 * BAND ? 8 * BAND : auto_run));
+    a.run = c->opt.pnet_run > 0 ? c->opt.pnet_run : (auto_run < 1 ? 1 : (auto_run > 8 * BAND ? 8 * BAND : auto_run));
     auto launch = [&](auto kern) {
         // static + dynamic LDS exceed the default 64 KB per workgroup
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, DYN_LDS) != hipSuccess) return false;

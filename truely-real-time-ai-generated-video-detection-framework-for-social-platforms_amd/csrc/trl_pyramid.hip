@@ -854,7 +854,7 @@ static int pyr_tables(trl_ctx* c, int H, int W, const PyrLayout& lay, hipStream_
 // of each in the plan (trl_debug_pyramid_plan).
 struct PyrJob { trl_ctx* c; const uint8_t* frames; int n, H, W; const PyrLayout& lay; PyrPx* pyr; hipStream_t s; };
 static void plan_row(const PyrJob& j, int l, int kind, int rb, int cb, int cpb, int frames) {
-    int32_t* r = j.c->pyr_plan.row[l];
+    int32_t* r = j.c->hook.pyr_plan.row[l];
     r[0] = kind; r[1] = rb; r[2] = cb; r[3] = cpb; r[4] = frames; r[5] = j.lay.lv[l].khmax;
 }
 
@@ -887,7 +887,7 @@ static int launch_coarse(const PyrJob& j, bool (&taken)[16]) {
         const int stab_words = tab_hi - tab_lo;                               // rows + columns of the group's levels (they are neighbours)
         sa.tab0 = tab_lo; sa.tab_words = stab_words;
         sa.H = H; sa.W = W; sa.n_frames = n; sa.pyr_stride = j.lay.pyr_stride;
-        const int forced = j.c->pyr_row_bands;                                // test hook: 0 = the policy below
+        const int forced = j.c->opt.pyr_row_bands;                                // test hook: 0 = the policy below
         sa.row_bands = forced > 0 ? (forced < H ? forced : H) : (H >= 256 ? 3 : 1);
         sa.rows_per_band = (H + sa.row_bands - 1) / sa.row_bands;
         sa.row_bands = (H + sa.rows_per_band - 1) / sa.rows_per_band;         // every band has a row
@@ -974,7 +974,7 @@ static int launch_per_level(const PyrJob& j, bool (&taken)[16]) {
 int trl_pyramid_build(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, PyrLayout& lay, PyrPx** pyr_out, hipEvent_t* ev, hipStream_t s) {
     if (((uintptr_t)d_frames & 3) != 0) { trl_set_error("frame buffer must be 4-byte aligned"); return TRL_ERR_INVALID; }
     if (H > 16383 || W > 16383) { trl_set_error("frame larger than 16383 px"); return TRL_ERR_INVALID; }
-    c->pyr_plan.L = 0;
+    c->hook.pyr_plan.L = 0;
     TRL_CHECK(trl_pyramid_layout(c, H, W, lay));
     TRL_CHECK(pyr_tables(c, H, W, lay, s));
     PyrPx* pyr = (PyrPx*)c->scratch.alloc(trl_pyramid_bytes(lay, n));
@@ -986,7 +986,7 @@ int trl_pyramid_build(trl_ctx* c, const uint8_t* d_frames, int n, int H, int W, 
     TRL_CHECK(launch_fine(j, taken));
     TRL_CHECK(launch_per_level(j, taken));
     if (ev) TRL_HIP(hipEventRecord(ev[1], s));
-    c->pyr_plan.L = lay.L;
+    c->hook.pyr_plan.L = lay.L;
     *pyr_out = pyr;
     return TRL_OK;
 }
